@@ -756,6 +756,43 @@ def emit(out: dict) -> None:
     print(json.dumps(compact_line(out, shown)), flush=True)
 
 
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes of .npy data at most
+DUMP_ROWS = 1 << 20        # ... rows of the CSR sampled at most (seeded: the same rows in every run of the same arguments)
+
+
+def dump_outputs(directory: str, off: np.ndarray, nb: np.ndarray) -> dict:
+    """--dump-outputs DIR: what the timed step handed its caller in its last step — the d=1 network as a CSR (row offsets,
+    neighbour ids) — as DIR/<name>.npy in float64, for comparing two builds output for output.  A fixed, seeded sample of
+    rows (all of them when there are at most DUMP_ROWS):
+        csr_rows        the sampled row (amplicon) indices, ascending
+        csr_row_start   offsets[row] of each: where the row begins in the whole neighbour array (every earlier row's count in it)
+        csr_row_degree  offsets[row + 1] - offsets[row]
+        csr_neighbours  the neighbour ids of the sampled rows, row after row, as the step left them
+        neighbour_links the total number of links (one element)
+    The sample halves until everything fits in DUMP_LIMIT bytes."""
+    off = np.asarray(off, dtype=np.int64)
+    nb = np.asarray(nb)
+    n = int(off.shape[0]) - 1
+    order = np.random.default_rng(20240607).permutation(n) if n > DUMP_ROWS else np.arange(n)
+    take = min(n, DUMP_ROWS)
+    while True:
+        rows = np.sort(order[:take])
+        start, end = off[rows], off[rows + 1]
+        deg = end - start
+        total = int(deg.sum())
+        if 8 * (3 * take + total + 1) <= DUMP_LIMIT or take <= 1:
+            break
+        take //= 2
+    idx = np.repeat(start - np.cumsum(deg) + deg, deg) + np.arange(total, dtype=np.int64) if total else np.zeros(0, dtype=np.int64)
+    arrays = {"csr_rows": rows, "csr_row_start": start, "csr_row_degree": deg, "csr_neighbours": nb[idx],
+              "neighbour_links": np.array([int(off[-1])])}
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.asarray(a, dtype=np.float64))
+    return {"dir": str(out), "rows": int(rows.shape[0]), "of_rows": n, "bytes": sum(8 * int(a.size) for a in arrays.values())}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -786,7 +823,11 @@ def main() -> None:
     ap.add_argument("--dev-backend", default="nccl", choices=["nccl", "gloo"],
                     help="development aid: 'gloo' runs the N>1 flow with every rank on GPU 0 (collectives staged "
                          "through the host), to exercise the sharded step on a one-GPU box; marked simulated")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a seeded sample of the CSR's rows) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_extras:
         args.no_cpu_baseline = args.no_configs1 = True
 
@@ -955,6 +996,20 @@ def main() -> None:
         elapsed = float(t.item())
 
     timings = ctx.timing_read()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # (outside the timed region: the CSR of the last timed step, downloaded as the caller would receive it)
+        if gathered[0] is not None:
+            o_off, o_nb = gathered[0][0].cpu().numpy(), gathered[0][1].cpu().numpy()
+        elif owned:
+            # rank 0's share of a simulated job: its flat link list (source << 32 | target), as a CSR over every source
+            links = d_links[:hits_seen[0]].cpu().numpy()
+            src, tgt = links >> 32, links & 0xFFFFFFFF
+            o_nb = tgt[np.lexsort((tgt, src))]
+            o_off = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n_total))])
+        else:
+            o_off, o_nb = d_offsets[:q_count + 1].cpu().numpy(), d_nb[:hits_seen[0]].cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, o_off, o_nb)
     sharded_ok = None
     if one_gpu and rank == 0:
         # development aid only: the gathered CSR against the whole network computed by this rank alone
@@ -1055,6 +1110,8 @@ def main() -> None:
             },
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         run_cpp_multi = False
         extras = world == 1 and not sim_world and not args.no_extras
         if world == 1 and not sim_world and not args.no_configs1:

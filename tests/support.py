@@ -3,7 +3,7 @@ reference shim, synthetic input generation.
 
 Nothing in here is product code.  The db construction below is an independent numpy
 restatement of the reference's ``db_read`` ordering and packing
-(/root/reference/src/db.cc:100-114, 161-211, 388-413, 541-628) so that it can also
+(the reference's src/db.cc:100-114, 161-211, 388-413, 541-628) so that it can also
 cross-check the product's own FASTA reader.
 """
 from __future__ import annotations
@@ -272,16 +272,16 @@ def oracle_fastidious(db: Db, is_light: np.ndarray, bloom_bits: int = 16):
 # -------------------------------------------------------------------- reference
 
 def have_reference() -> bool:
-    """True when the compiled reference (oracle/_ref) is available or can be built."""
-    if (REF_DIR / "swarm").exists() and (REF_DIR / "libswarmref.so").exists():
-        return True
-    if Path("/root/reference/src/swarm.cc").exists():
+    """True when the compiled reference (oracle/_ref) is available or can be built.  Where it is absent, oracle/Makefile
+    decides whether the reference's sources can be reached (its REF); the tests never look outside the repository."""
+    def built() -> bool:
+        return (REF_DIR / "swarm").exists() and (REF_DIR / "libswarmref.so").exists()
+    if not built():
         try:
             _make("ref")
         except Exception:
             return False
-        return (REF_DIR / "swarm").exists()
-    return False
+    return built()
 
 
 def ref_swarm_bin() -> Path:

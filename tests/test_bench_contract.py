@@ -8,6 +8,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -101,10 +102,53 @@ def test_the_line_this_build_prints_on_the_gpu():
     assert "cpu_baseline" not in line                           # (--no-extras: nothing beside the headline)
 
 
+@pytest.mark.gpu
+def test_the_outputs_the_bench_dumps_on_the_gpu(tmp_path):
+    """--dump-outputs: the last timed step's CSR, sampled, as float64 .npy files that agree with the line."""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--no-extras", "--per-gpu", "200000",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2
+    a = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(a) == {"csr_rows", "csr_row_start", "csr_row_degree", "csr_neighbours", "neighbour_links"}
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["neighbour_links"][0] == line["config"]["neighbour_links"] > 0
+    assert np.array_equal(a["csr_rows"], np.arange(200_000))                   # (at most 2^20 rows: every one of them)
+    assert a["csr_row_degree"].sum() == a["csr_neighbours"].size == a["neighbour_links"][0]
+    assert np.array_equal(a["csr_row_start"][1:], np.cumsum(a["csr_row_degree"])[:-1])
+    assert a["csr_neighbours"].min() >= 0 and a["csr_neighbours"].max() < 200_000
+
+
+def test_dump_outputs_samples_whole_rows(tmp_path, monkeypatch):
+    """bench.dump_outputs on a made-up CSR: a seeded sample of whole rows, the same rows every time, within the byte limit."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    rng = np.random.default_rng(5)
+    n = 5000
+    deg = rng.integers(0, 9, n)
+    off = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    nb = rng.integers(0, n, int(off[-1])).astype(np.int32)
+    monkeypatch.setattr(bench, "DUMP_ROWS", 1000)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 8 * (3 * 500 + 4500))              # room for about 500 rows: the sample halves once
+    info = bench.dump_outputs(str(tmp_path / "a"), off, nb)
+    assert info["rows"] == 500 and info["of_rows"] == n and info["bytes"] <= bench.DUMP_LIMIT
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    rows = a["csr_rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows.size == 500
+    assert np.array_equal(a["csr_row_start"], off[rows]) and np.array_equal(a["csr_row_degree"], deg[rows])
+    assert np.array_equal(a["csr_neighbours"], np.concatenate([nb[off[i]:off[i + 1]] for i in rows]))
+    assert a["neighbour_links"].tolist() == [float(off[-1])]
+    bench.dump_outputs(str(tmp_path / "b"), off, nb)
+    for name, v in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.npy"), v)
+
+
 def test_bench_defaults_without_a_gpu():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--per-gpu", "--extras"):
+    for flag in ("--gpus", "--steps", "--warmup", "--per-gpu", "--extras", "--dump-outputs"):
         assert flag in r.stdout
     sys.path.insert(0, str(ROOT))
     import bench

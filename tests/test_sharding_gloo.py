@@ -5,7 +5,9 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import textwrap
+import time
 
 import numpy as np
 import pytest
@@ -39,7 +41,7 @@ WORKER = textwrap.dedent('''
         full_nb[int(full_off[i]):int(full_off[i + 1])].sort()
     assert np.array_equal(g_off.numpy().astype(np.uint64), full_off), "offsets differ"
     assert np.array_equal(g_nb.numpy().view(np.uint32), full_nb), "neighbours differ"
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # (a barrier on the CPU: dist.barrier() looks for a GPU)
     dist.destroy_process_group()
     print("rank", rank, "ok")
 ''')
@@ -49,6 +51,39 @@ def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
+
+
+def _run_ranks(world: int, script, *args) -> subprocess.CompletedProcess:
+    """`world` gloo ranks of `script` on this host, with the environment torch.distributed.run gives its workers (RANK,
+    WORLD_SIZE, LOCAL_RANK, MASTER_ADDR / MASTER_PORT) but without its agent, which asks torch whether there is a GPU:
+    these CPU tests must not open one.  The ranks' outputs concatenated; when a rank fails, the others are stopped."""
+    port = str(_free_port())
+    procs = []
+    for rank in range(world):
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, RANK=str(rank), WORLD_SIZE=str(world),
+                   LOCAL_RANK=str(rank), LOCAL_WORLD_SIZE=str(world), GROUP_RANK="0")
+        out, err = tempfile.TemporaryFile("w+"), tempfile.TemporaryFile("w+")
+        procs.append((subprocess.Popen([sys.executable, str(script)] + [str(a) for a in args], stdout=out, stderr=err, env=env), out, err))
+    deadline = time.monotonic() + 600
+    try:
+        while any(p.poll() is None for p, _, _ in procs) and not any(p.returncode for p, _, _ in procs):
+            if time.monotonic() > deadline:
+                break
+            time.sleep(0.05)
+    finally:
+        for p, _, _ in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    texts = []
+    for p, out, err in procs:
+        out.seek(0)
+        err.seek(0)
+        texts.append((out.read(), err.read()))
+        out.close()
+        err.close()
+    rc = next((p.returncode for p, _, _ in procs if p.returncode), 0)
+    return subprocess.CompletedProcess(str(script), rc, "".join(o for o, _ in texts), "".join(e for _, e in texts))
 
 
 def _star_fasta(path, arms=300):
@@ -74,10 +109,7 @@ def test_sharded_network_equals_single(tmp_path, world, mode):
         S.gen_fasta(fa, 3001, 90, 77)
     script = tmp_path / "worker.py"
     script.write_text(WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                        "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"], str(script), str(S.ROOT),
-                        str(fa), mode], capture_output=True, text=True, env=env, timeout=600)
+    r = _run_ranks(world, script, str(S.ROOT), str(fa), mode)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stdout.count("ok") == world
 
@@ -99,6 +131,7 @@ def test_partitions_cover_range():
 GRAFT_WORKER = textwrap.dedent('''
     import sys
     import numpy as np
+    import torch
     import torch.distributed as dist
     sys.path.insert(0, sys.argv[1])
     from swarm_amd import sharding
@@ -117,7 +150,7 @@ GRAFT_WORKER = textwrap.dedent('''
     assert g.dtype == np.uint32 and np.array_equal(g, full), "graft minimum differs"
     assert int(c[1]) == sum(100 + r for r in range(world)) and int(c[2]) == sum(7 * (r + 1) for r in range(world))
     assert [int(c[0]), int(c[3]), int(c[4])] == [1234, 4096, 6]
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # (a barrier on the CPU: dist.barrier() looks for a GPU)
     dist.destroy_process_group()
     print("rank", rank, "ok")
 ''')
@@ -127,10 +160,7 @@ GRAFT_WORKER = textwrap.dedent('''
 def test_combine_grafts_min_and_sum(tmp_path, world):
     script = tmp_path / "worker.py"
     script.write_text(GRAFT_WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                        "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"], str(script), str(S.ROOT)],
-                       capture_output=True, text=True, env=env, timeout=600)
+    r = _run_ranks(world, script, str(S.ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stdout.count("ok") == world
 
@@ -167,7 +197,7 @@ OWNED_WORKER = textwrap.dedent('''
     g_off, g_nb = sharding.allgather_csr(l_off, l_nb, int(l_nb.numel()), counts)
     assert np.array_equal(g_off.numpy().astype(np.uint64), full_off), "offsets differ"
     assert np.array_equal(g_nb.numpy().view(np.uint32), full_nb), "neighbours differ"
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # (a barrier on the CPU: dist.barrier() looks for a GPU)
     dist.destroy_process_group()
     print("rank", rank, "ok")
 ''')
@@ -181,10 +211,7 @@ def test_owned_links_merge_into_the_network(tmp_path, world, mode):
     S.gen_fasta(fa, 2503, 90, 78)
     script = tmp_path / "worker.py"
     script.write_text(OWNED_WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                        "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"], str(script), str(S.ROOT),
-                        str(fa), mode], capture_output=True, text=True, env=env, timeout=600)
+    r = _run_ranks(world, script, str(S.ROOT), str(fa), mode)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stdout.count("ok") == world
 
@@ -218,7 +245,7 @@ ROUTE_WORKER = textwrap.dedent('''
     for index in range(2):
         want = everybody[owner(everybody, index) == rank]                      # sources in rank order, ids ascending inside
         assert np.array_equal(got[index].numpy().astype(np.int64), want), (rank, index)
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # (a barrier on the CPU: dist.barrier() looks for a GPU)
     dist.destroy_process_group()
     print("rank", rank, "ok")
 ''')
@@ -254,7 +281,7 @@ RECORD_WORKER = textwrap.dedent('''
     for index, got in ((0, rec_p), (1, rec_s)):
         want = everybody[owner(everybody, index) == rank]                      # sources in rank order, ids ascending inside
         assert np.array_equal(got.numpy(), (key(want, index) << 32) | want), (rank, index)
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # (a barrier on the CPU: dist.barrier() looks for a GPU)
     dist.destroy_process_group()
     print("rank", rank, "ok")
 ''')
@@ -266,10 +293,7 @@ def test_routed_records_reach_their_owners(tmp_path, world):
     owning rank and index) arrives, all-to-all, as the arguments of swa_d1_index_build_records."""
     script = tmp_path / "record_worker.py"
     script.write_text(RECORD_WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                        "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"], str(script), str(S.ROOT)],
-                       capture_output=True, text=True, env=env, timeout=600)
+    r = _run_ranks(world, script, str(S.ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stdout.count("ok") == world
 
@@ -280,10 +304,7 @@ def test_routed_ids_reach_their_owners(tmp_path, world):
     index) arrives, all-to-all, as the member lists of swa_d1_index_build_routed."""
     script = tmp_path / "route_worker.py"
     script.write_text(ROUTE_WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                        "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"], str(script), str(S.ROOT)],
-                       capture_output=True, text=True, env=env, timeout=600)
+    r = _run_ranks(world, script, str(S.ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stdout.count("ok") == world
 
@@ -323,7 +344,7 @@ DN_WORKER = textwrap.dedent('''
         assert rows_sorted
     else:
         assert got is None
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # (a barrier on the CPU: dist.barrier() looks for a GPU)
     dist.destroy_process_group()
     print("rank", rank, "ok")
 ''')
@@ -335,10 +356,7 @@ def test_dn_triples_merge_into_the_graph(tmp_path, world, mode):
     the window groups it owns, rank 0 gathers and MERGES them (no sort of the whole) into the CSR the greedy walk reads."""
     script = tmp_path / "dn_worker.py"
     script.write_text(DN_WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                        "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"], str(script), str(S.ROOT), mode],
-                       capture_output=True, text=True, env=env, timeout=600)
+    r = _run_ranks(world, script, str(S.ROOT), mode)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stdout.count("ok") == world
 
