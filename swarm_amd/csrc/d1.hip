@@ -19,7 +19,7 @@
 //   * the hash table is one 16-byte slot per entry (hash, amplicon id): one transaction
 //     per probe step instead of the reference's three arrays;
 //   * hits leave a wave through its own segment of the edge buffer (one writer per segment,
-//     no atomics); a scan + scatter + per-row sort turns the segments into the canonical CSR.
+//     no atomics); the partition of d1_stream.inc sorts the segments' links into the canonical CSR.
 //
 // All arithmetic is 64-bit integer XOR/shift/compare; results are bit-exact.
 #include "swa_internal.h"
@@ -63,7 +63,6 @@ struct NetArgs {
   uint64_t * edges;             // (src << 32) | dst
   uint64_t seg_cap;             // edges are appended to per-wave segments: segment w = edges[w*seg_cap ..)
   uint32_t * seg_fill;          // [launch waves] fill of each segment (no atomics: one writer per segment)
-  uint32_t * counts;            // per query amplicon (index k = amp - first)
   unsigned long long * stats;   // [0] variants [1] bloom pass [2] hash match [3] verified
   // MODE 2 (seeds the anchored passes cannot serve): explicit (seed, position range) list
   const struct swa_fallback * fallback;
@@ -485,13 +484,7 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
       wave_lds_sync();
       drain(qn);
     }
-    if (MODE == 0) {
-      if (lane == 0) { a.counts[k] = row; }
-    } else if (MODE == 2) {
-      if (lane == 0 && row != 0u && a.counts != nullptr) { atomicAdd(&a.counts[seed - a.first], row); }
-    } else {
-      cand_total += row;
-    }
+    if (MODE == 1) { cand_total += row; }
     __builtin_amdgcn_wave_barrier();
   }
   if (MODE != 1 && lane == 0) { a.seg_fill[gwave] = seg_at; }
@@ -618,7 +611,7 @@ __global__ __launch_bounds__(kThreads) void k_d1_flex(const FlexArgs a) {
   if (lane == 0 && nvar != 0ull) { atomicAdd(a.variant_counter, nvar); }
 }
 
-// ---- CSR assembly: counts -> offsets (exclusive scan), edges -> rows, sort rows ------
+// ---- exclusive scans (the fastidious pass's offsets), the per-wave segments' totals and flat list ------
 constexpr int kScanItems = 8;
 constexpr int kScanBlock = 256;
 constexpr int kScanTile = kScanItems * kScanBlock;
@@ -756,75 +749,6 @@ __global__ __launch_bounds__(256) void k_seg_compact(const uint64_t * __restrict
     const uint64_t base = bases[s];
     for (uint64_t i = threadIdx.x; i < fill; i += blockDim.x) {
       if (base + i < cap) { out[base + i] = edges[(uint64_t)s * seg_cap + i]; }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scatter_edges(const uint64_t * __restrict__ edges,
-                                                       const uint32_t * __restrict__ seg_fill, uint32_t nseg,
-                                                       uint64_t seg_cap, uint32_t first,
-                                                       const uint64_t * __restrict__ offsets, uint32_t * cursor,
-                                                       uint32_t * __restrict__ neighbours, uint64_t cap) {
-  for (uint32_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-    const uint32_t filled = seg_fill[seg];                    // may exceed the capacity (the run is then repeated)
-    const uint32_t fill = filled < seg_cap ? filled : (uint32_t)seg_cap;
-    const uint64_t * e = edges + (uint64_t)seg * seg_cap;
-    for (uint32_t j = threadIdx.x; j < fill; j += blockDim.x) {
-      const uint64_t edge = e[j];
-      const uint32_t k = (uint32_t)(edge >> 32) - first;
-      const uint64_t at = offsets[k] + atomicAdd(&cursor[k], 1u);
-      if (at < cap) { neighbours[at] = (uint32_t)edge; }
-    }
-  }
-}
-
-// rows are tiny (about two neighbours per amplicon): one thread insertion-sorts a row; rows
-// longer than 64 are queued (long_rows[0] = count, then the row indices) and sorted by a whole
-// wave each with an odd-even transposition sort
-__global__ __launch_bounds__(256) void k_sort_rows(const uint64_t * __restrict__ offsets, uint32_t count,
-                                                   uint32_t * neighbours, uint64_t cap, uint32_t * long_rows,
-                                                   uint32_t long_cap) {
-  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-    const uint64_t b = offsets[k];
-    const uint64_t e = offsets[k + 1];
-    if (e > cap || e - b < 2) { continue; }
-    if (e - b > 64) {
-      const uint32_t at = atomicAdd(long_rows, 1u);
-      if (at < long_cap) { long_rows[1u + at] = k; }
-      continue;
-    }
-    for (uint64_t i = b + 1; i < e; ++i) {
-      const uint32_t v = neighbours[i];
-      uint64_t j = i;
-      while (j > b && neighbours[j - 1] > v) { neighbours[j] = neighbours[j - 1]; --j; }
-      neighbours[j] = v;
-    }
-  }
-}
-
-__global__ __launch_bounds__(64) void k_sort_long_rows(const uint64_t * __restrict__ offsets, uint32_t count,
-                                                       uint32_t * neighbours, uint64_t cap,
-                                                       const uint32_t * __restrict__ long_rows, uint32_t long_cap) {
-  // one wave per queued row; if the queue overflowed (more than long_cap long rows) every row is
-  // visited instead, as a fallback
-  const int lane = threadIdx.x;
-  const uint32_t queued = long_rows[0];
-  const bool all = queued > long_cap;
-  const uint32_t todo = all ? count : queued;
-  for (uint32_t q = blockIdx.x; q < todo; q += gridDim.x) {
-    const uint32_t k = all ? q : long_rows[1u + q];
-    const uint64_t b = offsets[k];
-    const uint64_t e = offsets[k + 1];
-    const uint64_t len = e - b;
-    if (e > cap || len <= 64) { continue; }
-    for (uint64_t phase = 0; phase < len; ++phase) {
-      for (uint64_t i = (phase & 1u) + 2ull * lane; i + 1 < len; i += 128) {
-        const uint32_t x = neighbours[b + i];
-        const uint32_t y = neighbours[b + i + 1];
-        if (x > y) { neighbours[b + i] = y; neighbours[b + i + 1] = x; }
-      }
-      __threadfence_block();
-      __builtin_amdgcn_wave_barrier();
     }
   }
 }
@@ -986,9 +910,7 @@ static PartPlan plan_levels(uint32_t total_bits, uint32_t max_bits = kPartMaxBit
 struct PartJob {
   uint32_t nidx = 1;
   const unsigned long long * in[kMaxIdx] = {};      // level-0 input (may be buf[i][1])
-  const uint32_t * in_f[kMaxIdx] = {};
   unsigned long long * buf[kMaxIdx][2] = {};
-  uint32_t * buf_f[kMaxIdx][2] = {};
   const uint64_t * cstart0[kMaxIdx] = {};           // level-0 chunks (nullptr: regular, PartIdx::cstride)
   uint64_t cstride0[kMaxIdx] = {};
   const uint32_t * csize0[kMaxIdx] = {};
@@ -997,7 +919,7 @@ struct PartJob {
   uint64_t max_records = 0, max_tiles0 = 0;         // host-side upper bounds (per set)
   uint64_t out_cap = 0;                             // entries every buf[][] holds
   uint32_t bias = 0, top_bit = 32;
-  uint32_t tile = 4096;                             // records per tile (2048 for the records that carry fingerprints)
+  uint32_t tile = 4096;                             // records per tile: 4096 (links), 2048 / 4096 / 8192 (key records: run_partition)
   bool hist0_done = false;                          // the flat counts of level 0 are there already (k_keys<W, true>)
   PartPlan plan{};
   uint32_t * out32[kMaxIdx] = {};                   // != nullptr: the last level writes only the low halves, here
@@ -1006,7 +928,7 @@ struct PartJob {
   uint32_t * total[kMaxIdx] = {};
   uint64_t starts_stride = 0;
   // results
-  const unsigned long long * out[kMaxIdx] = {}; const uint32_t * out_f[kMaxIdx] = {}; const uint64_t * bstart[kMaxIdx] = {};
+  const unsigned long long * out[kMaxIdx] = {}; const uint64_t * bstart[kMaxIdx] = {};
   uint32_t buckets = 0;
   int last = 0;                                     // buf[i][last] holds the result, buf[i][last ^ 1] is free
 };
@@ -1045,12 +967,10 @@ static int clear_launch(swa_ctx * ctx, const ClearList & c) {
   return SWA_OK;
 }
 
-// (experiment: SWA_D1_LINK_SPAN=0 cuts the first level's tiles chunk by chunk, as rounds 3-5 did)
-static bool part_span_enabled() {
-  static const bool on = [] { const char * e = getenv("SWA_D1_LINK_SPAN"); return !(e != nullptr && e[0] == '0'); }();
-  return on;
-}
-
+// The forms of a level, chosen by the job: 512 bins in tiles of 2048 (key records) or 4096 (links: the first level of
+// several chunks cuts its tiles from the chunks laid end to end — part_span); 1024 bins for the one-level key partition,
+// in tiles of 8192 when k_keys has taken the histogram, else of 4096 (routed builds).  out32: the last level keeps only
+// the low halves.
 static int run_partition(swa_ctx * ctx, PartJob & j) {
   uint64_t chunks = j.chunks0;
   bool single = j.single0;
@@ -1059,23 +979,26 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
   for (uint32_t l = 0; l < j.plan.levels; ++l) {
     const uint32_t bits = j.plan.bits[l];
     used_bits += bits;
-    const bool last_level = l + 1 == j.plan.levels;
+    const bool wide = bits > kPartMaxBits;                      // (1024 bins: the one-level key partition)
+    const bool hist_done = l == 0 && j.hist0_done;
+    const bool low_halves = l + 1 == j.plan.levels && j.out32[0] != nullptr;
+    // (k_part_hist holds tiles of up to 4096; out32 has the link forms only)
+    const bool have_form = wide ? (j.tile == 4096 || (j.tile == 8192 && hist_done)) && !low_halves
+                                : (j.tile == 2048 && !low_halves) || j.tile == 4096;
+    if (!have_form) { return swa_fail_msg(ctx, SWA_E_ARG, "partition: no kernel for this tile and bin count"); }
     PartArgs a{};
     a.single_seg = single ? 1u : 0u; a.bits = bits; a.shift = j.top_bit - used_bits; a.bias = j.bias; a.tile = j.tile;
-    // (the link segments: tiles over the chunks laid end to end — the kernels of the usual link tile have that form)
-    a.span = (single && l == 0 && chunks > 1 && !j.hist0_done && j.tile == 4096 && bits <= kPartMaxBits && j.buf_f[0][0] == nullptr && part_span_enabled()) ? 1u : 0u;
+    a.span = (single && l == 0 && chunks > 1 && j.tile == 4096 && !wide && !hist_done) ? 1u : 0u;
     // runs of 16 consecutive tiles per XCD (xcd_tile; measured at 10 M amplicons: key partition 0.44 -> 0.33 ms, link partition
     // 0.39 -> 0.36, the same for runs of 8 .. 64) — unless there are fewer tiles than workgroups in flight, where the runs
     // would leave XCDs without work
     const uint64_t tiles = (l == 0 ? j.max_tiles0 : j.max_records / j.tile + chunks + 1);
     a.run_bits = tiles >= (uint64_t)cu_grid ? 4u : 0u;
-    if (const char * e = getenv("SWA_D1_XCD_RUN_BITS")) { a.run_bits = (uint32_t)std::min(8, std::max(0, atoi(e))); }   // (experiment)
     for (uint32_t i = 0; i < j.nidx; ++i) {
       PartIdx & p = a.p[i];
       p.in = l == 0 ? j.in[i] : j.buf[i][(l - 1) & 1u];
-      p.in_f = l == 0 ? j.in_f[i] : j.buf_f[i][(l - 1) & 1u];
-      p.out = j.buf[i][l & 1u]; p.out_f = j.buf_f[i][l & 1u];
-      p.out32 = last_level ? j.out32[i] : nullptr;
+      p.out = j.buf[i][l & 1u];
+      p.out32 = low_halves ? j.out32[i] : nullptr;
       p.out_cap = j.out_cap;
       p.cstart = l == 0 ? j.cstart0[i] : j.starts[i] + ((l - 1) & 1u) * j.starts_stride;
       p.cstride = l == 0 ? j.cstride0[i] : 0;
@@ -1091,10 +1014,8 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
     const dim3 grid_t((unsigned)((std::min<uint64_t>(std::max<uint64_t>(tiles, 1), (uint64_t)cu_grid) + 7) & ~7ull), j.nidx);
     if (chunks > 2048) { hipLaunchKernelGGL(k_part_tiles<1024>, dim3(1, j.nidx), dim3(1024), 0, ctx->stream, a); }
     else { hipLaunchKernelGGL(k_part_tiles<256>, dim3(1, j.nidx), dim3(256), 0, ctx->stream, a); }
-    const bool bins1024 = bits > kPartMaxBits;                 // (the key records of the one-level form: 10 bits)
-    if (l == 0 && j.hist0_done) { /* (k_keys has left the counts) */ }
-    else if (bins1024) { hipLaunchKernelGGL((k_part_hist<1024, kPartTileMax, 256>), grid_t, dim3(256), 0, ctx->stream, a); }
-    else if (j.tile == 8192) { hipLaunchKernelGGL((k_part_hist<512, 8192, 512>), grid_t, dim3(512), 0, ctx->stream, a); }
+    if (hist_done) { /* (k_keys has left the counts) */ }
+    else if (wide) { hipLaunchKernelGGL((k_part_hist<1024, kPartTileMax, 256>), grid_t, dim3(256), 0, ctx->stream, a); }
     else if (a.span != 0u) { hipLaunchKernelGGL((k_part_hist<512, kPartTileMax, 256, true>), grid_t, dim3(256), 0, ctx->stream, a); }
     else { hipLaunchKernelGGL((k_part_hist<512, kPartTileMax, 256>), grid_t, dim3(256), 0, ctx->stream, a); }
     FlatScanArgs f{};
@@ -1103,45 +1024,22 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
     const dim3 grid_f((unsigned)std::min<uint64_t>(((tiles << bits) + 1 + kFlatChunk - 1) / kFlatChunk, (uint64_t)cu_grid), j.nidx);
     hipLaunchKernelGGL(k_flat_sums, grid_f, dim3(256), 0, ctx->stream, f);
     hipLaunchKernelGGL(k_flat_apply, grid_f, dim3(256), 0, ctx->stream, f);
-    {
-      static const int part_threads = [] { const char * e = getenv("SWA_D1_PART_THREADS"); const int v = e != nullptr ? atoi(e) : 512; return v == 256 || v == 1024 ? v : 512; }();   // (512: key partition 0.269 -> 0.239, link partition 0.317 -> 0.303 ms at 10 M against 256; 1024: 0.244 / 0.384)
-#define SWA_SCATTER(M, T, B)                                                                                                          \
-      do {                                                                                                                            \
-        constexpr size_t lds = part_scatter_lds(M, T, B);                                                                             \
-        if (part_threads == 1024) { hipLaunchKernelGGL((k_part_scatter<M, T, B, 1024>), grid_t, dim3(1024), lds, ctx->stream, a); }   \
-        else if (part_threads == 512) { hipLaunchKernelGGL((k_part_scatter<M, T, B, 512>), grid_t, dim3(512), lds, ctx->stream, a); } \
-        else { hipLaunchKernelGGL((k_part_scatter<M, T, B, 256>), grid_t, dim3(256), lds, ctx->stream, a); }                          \
-      } while (0)
-      // (beyond 64 KB of dynamic LDS the attribute is asked for: it belongs to the function on a device — once per context)
-#define SWA_SCATTER_WIDE(M, B, BIT)                                                                                                   \
-      do {                                                                                                                            \
-        constexpr size_t lds = part_scatter_lds(M, 8192, B);                                                                          \
-        if ((ctx->part_lds_opt_in & (1u << BIT)) == 0u) {                                                                             \
-          SWA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter<M, 8192, B, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-          ctx->part_lds_opt_in |= 1u << BIT;                                                                                          \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((k_part_scatter<M, 8192, B, 1024>), grid_t, dim3(1024), lds, ctx->stream, a);                              \
-      } while (0)
-      const bool payload = j.buf_f[0][0] != nullptr;           // (a second array travels with index 0's records: nobody's since round 6)
-      if (!payload && j.tile == 8192 && !bins1024) {
-        if (last_level && j.out32[0] != nullptr) { SWA_SCATTER_WIDE(2, 512, 1); } else { SWA_SCATTER_WIDE(0, 512, 2); }
+    // (512 threads a workgroup — key partition 0.269 -> 0.239, link partition 0.317 -> 0.303 ms at 10 M against 256 —, 1024
+    // for the tile of 8192, whose 76 KB of LDS are asked for: the attribute belongs to the function on a device, once per context)
+    if (wide && j.tile == 8192) {
+      constexpr size_t lds = part_scatter_lds(8192, 1024);
+      if (!ctx->part_lds_opt_in) {
+        SWA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter<0, 8192, 1024, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ctx->part_lds_opt_in = true;
       }
-      else if (a.span != 0u) {
-        // (4096 x 512, 512 threads: the form the link partition runs in; SWA_D1_PART_THREADS keeps the chunk-by-chunk kernels)
-        constexpr size_t lds = part_scatter_lds(0, 4096, 512);
-        if (last_level && j.out32[0] != nullptr) { hipLaunchKernelGGL((k_part_scatter<2, 4096, 512, 512, true>), grid_t, dim3(512), lds, ctx->stream, a); }
-        else { hipLaunchKernelGGL((k_part_scatter<0, 4096, 512, 512, true>), grid_t, dim3(512), lds, ctx->stream, a); }
-      }
-      else if (last_level && j.out32[0] != nullptr) { SWA_SCATTER(2, 4096, 512); }
-      else if (bins1024 && j.tile == 8192) { if (payload) { SWA_SCATTER_WIDE(1, 1024, 0); } else { SWA_SCATTER_WIDE(0, 1024, 3); } }
-      else if (bins1024 && j.tile == 4096) { if (payload) { SWA_SCATTER(1, 4096, 1024); } else { SWA_SCATTER(0, 4096, 1024); } }
-      else if (bins1024) { if (payload) { SWA_SCATTER(1, 2048, 1024); } else { SWA_SCATTER(0, 2048, 1024); } }
-      else if (payload) { SWA_SCATTER(1, 2048, 512); }
-      else if (j.tile == 2048) { SWA_SCATTER(0, 2048, 512); }
-      else { SWA_SCATTER(0, 4096, 512); }
-#undef SWA_SCATTER
-#undef SWA_SCATTER_WIDE
+      hipLaunchKernelGGL((k_part_scatter<0, 8192, 1024, 1024>), grid_t, dim3(1024), lds, ctx->stream, a);
     }
+    else if (wide) { hipLaunchKernelGGL((k_part_scatter<0, 4096, 1024, 512>), grid_t, dim3(512), part_scatter_lds(4096, 1024), ctx->stream, a); }
+    else if (j.tile == 2048) { hipLaunchKernelGGL((k_part_scatter<0, 2048, 512, 512>), grid_t, dim3(512), part_scatter_lds(2048, 512), ctx->stream, a); }
+    else if (a.span != 0u && low_halves) { hipLaunchKernelGGL((k_part_scatter<2, 4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
+    else if (a.span != 0u) { hipLaunchKernelGGL((k_part_scatter<0, 4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
+    else if (low_halves) { hipLaunchKernelGGL((k_part_scatter<2, 4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
+    else { hipLaunchKernelGGL((k_part_scatter<0, 4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
     chunks = (single ? 1 : chunks) << bits;
     single = false;
     hipLaunchKernelGGL(k_part_starts, dim3((unsigned)std::min<uint64_t>((chunks + 256) / 256, (uint64_t)cu_grid), j.nidx), dim3(256), 0, ctx->stream, a);
@@ -1150,7 +1048,7 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
   j.buckets = (uint32_t)chunks;
   j.last = (int)((j.plan.levels - 1) & 1u);
   for (uint32_t i = 0; i < j.nidx; ++i) {
-    j.out[i] = j.buf[i][j.last]; j.out_f[i] = j.buf_f[i][j.last];
+    j.out[i] = j.buf[i][j.last];
     j.bstart[i] = j.starts[i] + (uint64_t)j.last * j.starts_stride;
   }
   return SWA_OK;
@@ -1201,25 +1099,21 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   uint32_t total_bits = 1;
   while ((records >> total_bits) > target && total_bits < 3 * kPartMaxBits) { ++total_bits; }
   total_bits = std::min<uint32_t>(total_bits + ctx->stream_extra_bits, 3 * kPartMaxBits);
+  // the first partition level's histogram is taken on the way (one read pass over the records less: 0.07 ms at 10 M);
+  // not for routed id lists (their length is the device's to know)
+  const bool keys_hist = !routed;
   PartJob j;
   j.nidx = 2;
-  j.plan = plan_levels(total_bits, level_bits);
+  // (one level of up to 1024 bins, or levels of up to 512: the partition has 1024-bin forms for one level only)
+  j.plan = total_bits <= level_bits ? plan_levels(total_bits, level_bits) : plan_levels(total_bits);
   j.max_records = records;
   j.out_cap = records + 1;
-  // (tiles of 2048 records for 512 bins; one level of 1024 bins: 4096, or the flat count array — bins x tiles — and the 16-byte runs
-  // a tile leaves per bin cost more than the saved level: 0.56 -> 0.43 ms at 10 M amplicons)
-  {
-    // tiles of 2048 records for 512 bins; one level of 1024 bins: 4096 — or 8192 when k_keys takes the histogram (k_part_hist
-    // holds 4096 a workgroup): a tile then leaves runs of 64 bytes per bin, whole lines (key partition 0.239 -> 0.225 ms at 10 M)
-    const bool one_wide_level = total_bits > kPartMaxBits && j.plan.levels == 1;
-    const char * kh = getenv("SWA_D1_KEYS_HIST");
-    const bool hist_by_keys = !routed && !(kh != nullptr && kh[0] == '0');
-    j.tile = one_wide_level ? (hist_by_keys ? 8192 : 4096) : 2048;
-    if (const char * e = getenv("SWA_D1_KEY_TILE")) {          // (experiment)
-      const int v = atoi(e);
-      if (v == 2048 || (v == 4096 && one_wide_level) || (v == 8192 && one_wide_level && hist_by_keys)) { j.tile = (uint32_t)v; }
-    }
-  }
+  // tiles of 2048 records for 512 bins; one level of 1024 bins: 4096 (or the flat count array — bins x tiles — and the 16-byte
+  // runs a tile leaves per bin cost more than the saved level: 0.56 -> 0.43 ms at 10 M amplicons) — or 8192 when k_keys takes
+  // the histogram (k_part_hist holds 4096 a workgroup): a tile then leaves runs of 64 bytes per bin, whole lines (key
+  // partition 0.239 -> 0.225 ms at 10 M)
+  const bool one_wide_level = total_bits > kPartMaxBits && j.plan.levels == 1;
+  j.tile = one_wide_level ? (keys_hist ? 8192 : 4096) : 2048;
   j.max_tiles0 = records / j.tile + 2;
   j.chunks0 = 1; j.single0 = true; j.top_bit = 32; j.bias = 0;
   uint64_t e_cnt, e_tile, e_start, e_partial;
@@ -1285,10 +1179,6 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   if (by_rec) {   // (the records were made by the ranks that hold the amplicons' slices: what k_keys would have counted)
     hipLaunchKernelGGL(k_set_guard_made, dim3(1), dim3(1), 0, ctx->stream, k.guard, ctx->route_m[0], ctx->route_m[1]);
   }
-  // the first partition level's histogram is taken on the way (one read pass over the records less: 0.07 ms at 10 M);
-  // not for routed id lists (their length is the device's to know), SWA_D1_KEYS_HIST=0: comparison switch
-  const char * env_kh = getenv("SWA_D1_KEYS_HIST");
-  const bool keys_hist = !routed && !(env_kh != nullptr && env_kh[0] == '0');
   swa_t0(ctx, 8);
   if (by_rec) { /* nothing to key */ }
   else if (keys_hist) {
@@ -1356,7 +1246,6 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     x.kind_cnt = static_cast<uint32_t *>(ctx->d_stream[kSbKind + i].ptr);
   }
   g.pair_big = pair_big_limit(); g.group_cap = kStreamGroupCap;   // (the tiled pair kernel serves every group up to that)
-  if (const char * env_cap = getenv("SWA_D1_GROUP_CAP")) { g.group_cap = std::max<uint32_t>(g.pair_big, (uint32_t)atoi(env_cap)); }   // (experiments)
   g.flags = dflags;
   g.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
   g.over = static_cast<uint8_t *>(ctx->d_stream[kSbOver].ptr);
@@ -1403,11 +1292,6 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
 // source (relative to `first`) until a bucket holds 2^r consecutive sources, then one wave per bucket (k_csr_bucket).
 // link_cap: entries of the two internal link buffers; a run with more links than that leaves garbage and is repeated
 // by the caller with bigger buffers (the total is known after the host has synchronised).
-static bool stream_csr_enabled() {
-  const char * e = getenv("SWA_D1_CSR");
-  return !(e != nullptr && e[0] == 't');
-}
-
 // (the chunks of the first level: `chunks` runs of links, run c = links[cstart[c] .. + min(csize[c], csize_cap)) — the per-wave
 // segments of the pair kernels, or the ranks' lists of a multi-GPU job gathered on one device)
 static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const unsigned long long * links, const uint64_t * d_cstart, uint64_t cstride,
@@ -1423,7 +1307,6 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   j.max_records = link_cap;
   j.out_cap = link_cap;
   j.tile = 4096;
-  if (const char * e = getenv("SWA_D1_LINK_TILE")) { if (atoi(e) == 8192) { j.tile = 8192; } }   // (experiment: runs of 128 bytes, half the flat counts)
   j.max_tiles0 = max_tiles0;
   j.chunks0 = chunks; j.single0 = true; j.top_bit = nbits; j.bias = first;
   j.csize_cap = csize_cap;
@@ -1533,7 +1416,7 @@ static uint32_t seg_count(const swa_ctx * ctx) { return (uint32_t)ctx->num_cus *
 
 // anchored network over [first, first+count): per pass and width class the pair kernels over that class's work lists,
 // then the seeds (or halves of seeds) left to the plain kernel; links in the per-wave segments
-static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count, bool count_links) {
+static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count) {
   // d_acounters: [2] fallback seeds [8 + 2 (4 pass + class) + {0, 1}] work counters of the 65..256 groups / of the tiled kernel
   // [kCounterBase + 8 (4 index + class) + kind] the lists of k_group_lists (made at index build, not cleared here)
   auto * acounters = static_cast<uint32_t *>(ctx->d_acounters.ptr);
@@ -1541,18 +1424,14 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   ClearList clears{};
   clear_add(clears, ctx->d_stats.ptr, 16 * sizeof(uint64_t));
   clear_add(clears, static_cast<uint64_t *>(ctx->d_guard.ptr) + 8, 8 * sizeof(uint64_t));   // the guard's counters of this network call
-  if (count_links) { clear_add(clears, ctx->d_counts.ptr, uint64_t(count) * sizeof(uint32_t)); }
   clear_add(clears, acounters, kCounterBase * sizeof(uint32_t));
   clear_add(clears, ctx->d_seg_fill.ptr, 3ull * seg_count(ctx) * sizeof(uint32_t));   // segment fills | members staged, per pass
-  // work counters of k_d1_group_pairs (per pass and class): 2^shard_bits of them, sched_stride entries apart
-  uint32_t pair_batch = 0, shard_bits = 6, sched_stride = 64;   // (pair_batch 0: by the number of bundles, below)
-  if (const char * e = getenv("SWA_D1_PAIR_BATCH")) { pair_batch = (uint32_t)std::max(1, atoi(e)); }                           // (experiments)
-  if (const char * e = getenv("SWA_D1_PAIR_SHARD_BITS")) { shard_bits = (uint32_t)std::min(10, std::max(0, atoi(e))); }
-  if (const char * e = getenv("SWA_D1_SCHED_STRIDE")) { sched_stride = (uint32_t)std::min(4096, std::max(1, atoi(e))); }
+  // work counters of k_d1_group_pairs (per pass and class): 2^shard_bits of them, kSchedStride entries apart
   // (a workgroup serves the bundles of shard blockIdx.x mod 2^shard_bits: every shard needs a workgroup — ADVICE r03)
+  uint32_t shard_bits = 6;
   while (shard_bits > 0 && (1u << shard_bits) > (uint32_t)ctx->num_cus) { --shard_bits; }
   {
-    const uint64_t bytes = ((2ull * kWidthClasses) << shard_bits) * sched_stride * sizeof(uint32_t);
+    const uint64_t bytes = ((2ull * kWidthClasses) << shard_bits) * kSchedStride * sizeof(uint32_t);
     SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbSched], bytes));
     clear_add(clears, ctx->d_stream[kSbSched].ptr, bytes);
   }
@@ -1575,7 +1454,6 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
     a.edges = static_cast<uint64_t *>(ctx->d_edges.ptr);
     a.seg_cap = ctx->seg_cap;
     a.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
-    a.counts = count_links ? static_cast<uint32_t *>(ctx->d_counts.ptr) : nullptr;
     a.minlen = anchor_minlen(ctx);
     a.win_word = ctx->anchor_a / 32u;
     a.win_word_b = ctx->anchor_b / 32u;
@@ -1583,7 +1461,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
     a.seg_staged = static_cast<uint32_t *>(ctx->d_seg_fill.ptr) + (uint64_t)(1 + pass) * seg_count(ctx);
     a.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
     a.flags = static_cast<uint32_t *>(ctx->d_flags.ptr);
-    a.batch = pair_batch; a.shard_bits = shard_bits; a.sched_stride = sched_stride;
+    a.shard_bits = shard_bits;
     a.ids = static_cast<const uint32_t *>(ctx->d_stream[kSbMembers + pass].ptr);
     a.lines = static_cast<const uint4 *>(ctx->d_stream[kSbLines].ptr);
     a.line_quads = ctx->lines_quads;
@@ -1601,7 +1479,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
       a.item_count = a.pair_counters + kPairClasses + 1u;
       a.sched_big = acounters + 8 + 2 * pc;
       a.sched_tiled = acounters + 9 + 2 * pc;
-      a.sched_wide = static_cast<uint32_t *>(ctx->d_stream[kSbSched].ptr) + ((uint64_t)pc << shard_bits) * sched_stride;
+      a.sched_wide = static_cast<uint32_t *>(ctx->d_stream[kSbSched].ptr) + ((uint64_t)pc << shard_bits) * kSchedStride;
       // (the pair kernel hands its work out through counters: exactly the workgroups that are resident together, no second round;
       // no launch over lists the index build found empty)
       const uint32_t * have = ctx->list_counts_ready ? ctx->list_counts + pc * 8u : nullptr;
@@ -1611,8 +1489,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
       // are what limits then — 0.78 / 1.21 / 2.2 ms with 4 / 2 / 1), fewer where the waves' shares are what limits (1 M: 2.4
       // bundles a wave — 0.072 / 0.049 / 0.037 ms a pass with 4 / 2 / 1)
       const int pgrid = ctx->num_cus * pair_blocks_per_cu(ctx, cls);
-      a.batch = pair_batch;
-      if (pair_batch == 0) {
+      {
         uint64_t bundles = 0;
         for (uint32_t k = 0; k < kPairClasses && have != nullptr; ++k) { bundles += ((uint64_t)have[k] + (16u >> k) - 1u) >> (4u - k); }
         const uint64_t waves = (uint64_t)pgrid * 4u;
@@ -1647,7 +1524,6 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   f.seg_cap = ctx->seg_cap;
   f.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
   f.stats = stats;
-  f.counts = count_links ? static_cast<uint32_t *>(ctx->d_counts.ptr) : nullptr;
   f.fallback = static_cast<const swa_fallback *>(ctx->d_afallback.ptr);
   f.fallback_count = acounters + 2;
   f.aux = static_cast<const swa_aux *>(ctx->d_aux.ptr);
@@ -2024,8 +1900,7 @@ static size_t network_lds_bytes(const swa_ctx * ctx, bool zlds) {
   return sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + 1024ull + kWaves * per_wave);
 }
 
-// launches the network kernel for [first, first+count); leaves the edge list, the
-// per-amplicon counts and the edge counter on the device
+// launches the network kernel for [first, first+count); leaves the links in the per-wave segments
 static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count, bool stats) {
   NetArgs a{};
   a.seqs = ctx->db.seqs; a.seq_off = ctx->db.seq_off; a.seqlen = ctx->db.seqlen; a.abundance = ctx->db.abundance;
@@ -2043,11 +1918,9 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
   a.seg_cap = ctx->seg_cap;
   a.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
   a.stats = static_cast<unsigned long long *>(ctx->d_stats.ptr);
-  a.counts = static_cast<uint32_t *>(ctx->d_counts.ptr);
   a.owner_rank = ctx->owner_rank; a.owner_world = ctx->owner_world;
   a.anchor_w = 32;
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 16 * sizeof(uint64_t), ctx->stream));
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_counts.ptr, 0, uint64_t(count) * sizeof(uint32_t), ctx->stream));   // skipped seeds keep 0
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const size_t lds = network_lds_bytes(ctx, zlds);
   const int grid = grid_for(ctx, count, kWaves, 8);
@@ -2073,10 +1946,10 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
 //   records keyed per index (k_keys)  =  members of listed + singleton + oversized groups (k_group1)
 //   members of listed groups          =  members the pair kernels staged, per pass
 //   no member sits in a group whose window key is not its own (pair_misfiled; key collisions excepted, exactly)
+// and, for every CSR result whatever the route (csr_check),
 //   links in the wave segments        =  links the partition sorted  =  the last CSR offset
 // A mismatch is SWA_E_INTERNAL — never a short network.
-static int guard_check(swa_ctx * ctx, const uint64_t * g, const uint64_t * got, bool csr_stream, uint64_t csr_end, uint32_t links_sorted,
-                       uint64_t n_edges) {
+static int guard_check(swa_ctx * ctx, const uint64_t * g, const uint64_t * got) {
   char msg[256];
   if (g[10] != 0) {
     snprintf(msg, sizeof(msg), "d=1 guard: %llu member(s) filed under an anchor key that is not theirs", (unsigned long long)g[10]);
@@ -2107,7 +1980,11 @@ static int guard_check(swa_ctx * ctx, const uint64_t * g, const uint64_t * got, 
       }
     }
   }
-  if (csr_stream && (csr_end != n_edges || (uint64_t)links_sorted != (n_edges & 0xFFFFFFFFull))) {
+  return SWA_OK;
+}
+static int csr_check(swa_ctx * ctx, uint64_t csr_end, uint32_t links_sorted, uint64_t n_edges) {
+  if (csr_end != n_edges || (uint64_t)links_sorted != (n_edges & 0xFFFFFFFFull)) {
+    char msg[256];
     snprintf(msg, sizeof(msg), "d=1 guard: %llu links found, %u sorted, CSR ends at %llu", (unsigned long long)n_edges, links_sorted, (unsigned long long)csr_end);
     return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
   }
@@ -2121,10 +1998,6 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const char * env_stats = getenv("SWA_D1_STATS");
   const bool stats = env_stats != nullptr && env_stats[0] == '1';
-  SWA_TRY(swa_reserve(ctx, ctx->d_counts, uint64_t(count) * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_cursor, uint64_t(count) * sizeof(uint32_t)));
-  const uint32_t tiles = (count + kScanTile - 1) / kScanTile;
-  SWA_TRY(swa_reserve(ctx, ctx->d_scan_tmp, uint64_t(tiles) * sizeof(uint64_t)));
   // hits leave the kernels through per-wave segments of the edge buffer (no shared counter)
   const uint32_t nseg = (uint32_t)ctx->num_cus * 8u * kWaves;          // >= waves of any launch below
   SWA_TRY(swa_reserve(ctx, ctx->d_seg_fill, 3ull * nseg * sizeof(uint32_t)));   // fills | members staged, pass 0 | pass 1
@@ -2135,8 +2008,6 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     const char * env_cap = getenv("SWA_D1_SEG_CAP");          // test hook: start small, exercise the regrow path
     if (env_cap != nullptr && atoi(env_cap) > 0) { ctx->seg_cap = (uint64_t)atoi(env_cap); }
   }
-  constexpr uint32_t kLongRowCap = 1u << 16;
-  SWA_TRY(swa_reserve(ctx, ctx->d_long_rows, (kLongRowCap + 1ull) * sizeof(uint32_t)));
   uint64_t n_edges = 0;
   uint64_t stream_link_cap = 0;
   bool clean = false;                                        // the last attempt ran to the end without a retry condition
@@ -2145,8 +2016,6 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     SWA_TRY(swa_reserve(ctx, ctx->d_edges, uint64_t(nseg) * ctx->seg_cap * sizeof(uint64_t)));
     // (the segment fills start at zero: the anchored route clears them with its other counters — one launch —, the plain one here)
     if (!(ctx->anchor_usable && !stats)) { SWA_HIP(ctx, hipMemsetAsync(ctx->d_seg_fill.ptr, 0, 3ull * nseg * sizeof(uint32_t), ctx->stream)); }
-    // CSR by the streaming route (links sorted by source with the partition primitive) unless a flat list is wanted
-    const bool csr_stream = d_edge_list == nullptr && stream_csr_enabled() && ctx->anchor_usable && !stats;
     if (ctx->anchor_usable && !stats) {
       if (!(ctx->anchor_ready && ctx->stream_index)) {
         // (the streaming index serves any query range; it is rebuilt when the owner changed)
@@ -2168,7 +2037,7 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
           if (fl[3] != 0 || fl[4] != 0) { SWA_TRY(ensure_full_index(ctx)); }
         }
       }
-      SWA_TRY(launch_network_anchored(ctx, no_cluster_breaking, first, count, !csr_stream));
+      SWA_TRY(launch_network_anchored(ctx, no_cluster_breaking, first, count));
     }
     else {
       SWA_TRY(ensure_full_index(ctx));
@@ -2189,27 +2058,10 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       hipLaunchKernelGGL(k_seg_compact, dim3(std::min<uint32_t>(nseg, (uint32_t)ctx->num_cus * 8u)), dim3(256), 0, ctx->stream,
                          static_cast<const uint64_t *>(ctx->d_edges.ptr), static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
                          nseg, ctx->seg_cap, static_cast<const unsigned long long *>(ctx->d_seg_base.ptr), d_edge_list, cap);
-    } else if (csr_stream) {
+    } else {
+      // CSR: the links sorted by source with the partition primitive
       stream_link_cap = std::max<uint64_t>(std::max<uint64_t>(cap, stream_link_cap), 2ull * count + 1024);
       SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap));
-    } else {
-      hipLaunchKernelGGL((k_scan_tiles<uint32_t>), dim3(tiles), dim3(kScanBlock), 0, ctx->stream,
-                         static_cast<const uint32_t *>(ctx->d_counts.ptr), count, static_cast<uint64_t *>(ctx->d_scan_tmp.ptr));
-      hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, ctx->stream, static_cast<uint64_t *>(ctx->d_scan_tmp.ptr), tiles);
-      hipLaunchKernelGGL((k_scan_apply<uint32_t>), dim3(tiles), dim3(kScanBlock), 0, ctx->stream,
-                         static_cast<const uint32_t *>(ctx->d_counts.ptr), count,
-                         static_cast<const uint64_t *>(ctx->d_scan_tmp.ptr), d_offsets);
-      if (d_neighbours != nullptr && cap > 0) {
-        SWA_HIP(ctx, hipMemsetAsync(ctx->d_cursor.ptr, 0, uint64_t(count) * sizeof(uint32_t), ctx->stream));
-        SWA_HIP(ctx, hipMemsetAsync(ctx->d_long_rows.ptr, 0, sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(k_scatter_edges, dim3(std::min<uint32_t>(nseg, (uint32_t)ctx->num_cus * 8u)), dim3(256), 0, ctx->stream,
-                           static_cast<const uint64_t *>(ctx->d_edges.ptr), static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
-                           nseg, ctx->seg_cap, first, d_offsets, static_cast<uint32_t *>(ctx->d_cursor.ptr), d_neighbours, cap);
-        hipLaunchKernelGGL(k_sort_rows, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, d_offsets, count,
-                           d_neighbours, cap, static_cast<uint32_t *>(ctx->d_long_rows.ptr), kLongRowCap);
-        hipLaunchKernelGGL(k_sort_long_rows, dim3(ctx->num_cus), dim3(64), 0, ctx->stream, d_offsets, count, d_neighbours, cap,
-                           static_cast<const uint32_t *>(ctx->d_long_rows.ptr), kLongRowCap);
-      }
     }
     SWA_HIP(ctx, hipGetLastError());
     swa_t1(ctx, 4);
@@ -2241,14 +2093,15 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       SWA_TRY(ensure_full_index(ctx));
       continue;
     }
-    if (csr_stream && got[1] <= ctx->seg_cap && n_edges > stream_link_cap) {
+    if (d_edge_list == nullptr && got[1] <= ctx->seg_cap && n_edges > stream_link_cap) {
       // more links than the internal link buffers of the CSR stage hold (a first call with a small `cap`): bigger, again
       stream_link_cap = n_edges + 1024;
       continue;
     }
     if (got[1] <= ctx->seg_cap) {
       clean = true;
-      if (guarded) { SWA_TRY(guard_check(ctx, guard, got, csr_stream, csr_end, links_sorted, n_edges)); }
+      if (guarded) { SWA_TRY(guard_check(ctx, guard, got)); }
+      if (d_edge_list == nullptr) { SWA_TRY(csr_check(ctx, csr_end, links_sorted, n_edges)); }
       twins = guarded && reinterpret_cast<const uint32_t *>(status)[0] != 0u;     // (flags[0]: the prefix pass met two identical sequences)
       break;
     }

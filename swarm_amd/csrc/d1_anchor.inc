@@ -78,11 +78,9 @@ constexpr uint32_t kListsPerIndex = kWidthClasses * kListKinds;
 constexpr uint32_t kCounterBase = 64;       // d_acounters[kCounterBase + (index * kWidthClasses + class) * 8 + kind]: items in that list
 constexpr uint32_t kCounterWords = 256;
 struct ListRegions { uint64_t at[kWidthClasses][kListKinds + 1]; };   // first item of list (class, kind) in an index's item buffer; [.][kListKinds] = end
+constexpr uint32_t kSchedStride = 64;       // entries between two work counters of k_d1_group_pairs (own cache lines / channels)
 
 #else
-#ifndef SWA_PAIR_EXPERIMENT
-#define SWA_PAIR_EXPERIMENT 0     // (profiling only, never in a build that ships; bits: 1 = bundles without their turns, 2 = without their line fetches, 4 = without the emission of links)
-#endif
 #ifndef SWA_PAIR_WG
 #define SWA_PAIR_WG 5
 #endif
@@ -474,9 +472,8 @@ struct AnchorArgs {
   uint32_t * sched_big;             // work counter of the 65..pair_big groups of k_d1_group_pairs (zeroed per network call)
   uint32_t * sched_tiled;           // work counter of k_d1_pairs_tiled (zeroed per network call)
   uint32_t batch;                   // bundles a wave of k_d1_group_pairs takes per visit of the work counter
-  uint32_t * sched_wide;            // k_d1_group_pairs: 2^shard_bits work counters, sched_stride entries apart (own cache lines / channels)
-  uint32_t shard_bits, sched_stride;
-  uint32_t * counts;                // per query amplicon, accumulated with atomicAdd (table CSR only)
+  uint32_t * sched_wide;            // k_d1_group_pairs: 2^shard_bits work counters, kSchedStride entries apart
+  uint32_t shard_bits;
   uint32_t minlen;                  // seeds at least this long are served by the anchored passes (win_a + win_b + 2 w + 1)
   uint32_t win_word;                // window mode: the prefix-side window is word win_a / 32 of a sequence
   uint32_t window_mode;             // anchor windows moved inwards (anchor_key)
@@ -766,22 +763,16 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
 }
 
 // links of one turn: e1 = member -> partner, e2 = partner -> member; into the wave's output segment `seg` (room for cap
-// links; what does not fit is counted, not written: the caller repeats the call with larger segments).  counting: the
-// caller wants the links per amplicon as well (a.counts; not the streaming route, whose partition counts them) — the
-// member's in a register, the partner's in LDS.  Round 6: one branch a turn instead of six, no link counts nobody reads
-// (emission was 45 of a pass's 270 us at 10 M: profiles/r06/NOTES.md section 10).
-__device__ __forceinline__ void pair_emit(bool e1, bool e2, uint32_t id, uint32_t pid, unsigned long long * seg, uint32_t cap, bool counting,
-                                          uint32_t & seg_at, uint32_t & mycount, uint32_t * partner_count) {
+// links; what does not fit is counted, not written: the caller repeats the call with larger segments).  Round 6: one branch
+// a turn instead of six (emission was 45 of a pass's 270 us at 10 M: profiles/r06/NOTES.md section 10).
+__device__ __forceinline__ void pair_emit(bool e1, bool e2, uint32_t id, uint32_t pid, unsigned long long * seg, uint32_t cap,
+                                          uint32_t & seg_at) {
   const uint64_t m1 = __ballot(e1), m2 = __ballot(e2);
   if ((m1 | m2) == 0ull) { return; }
   const uint32_t n1 = (uint32_t)__popcll(m1);
   const uint32_t at1 = seg_at + lanes_below(m1), at2 = seg_at + n1 + lanes_below(m2);
   if (e1 && at1 < cap) { seg[at1] = ((unsigned long long)id << 32) | pid; }
   if (e2 && at2 < cap) { seg[at2] = ((unsigned long long)pid << 32) | id; }
-  if (counting) {
-    mycount += e1 ? 1u : 0u;
-    if (e2) { atomicAdd(partner_count, 1u); }
-  }
   seg_at += n1 + (uint32_t)__popcll(m2);
 }
 
@@ -796,7 +787,6 @@ template <int PASS, int W, int NW>
 __global__ __launch_bounds__(kThreads) void k_d1_pairs_tiled(const AnchorArgs a) {
   constexpr uint32_t RD = PairLayout<W>::kDwords;
   __shared__ __attribute__((aligned(16))) uint32_t row_recs[kSeedsPerItem * RD];
-  __shared__ uint32_t row_cnt[kSeedsPerItem];
   const uint32_t wave = threadIdx.x >> 6;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t nitems = *a.item_count;
@@ -804,7 +794,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_pairs_tiled(const AnchorArgs a)
   uint32_t seg_at = a.seg_fill[gwave];
   unsigned long long * const seg = reinterpret_cast<unsigned long long *>(a.edges) + (uint64_t)gwave * a.seg_cap;
   const uint32_t seg_room = (uint32_t)min(a.seg_cap, (uint64_t)0xFFFFFFFFu);
-  const bool counting = a.counts != nullptr;
   uint32_t staged_members = a.seg_staged[gwave], misfiled = 0u;   // (the guard: pair_misfiled)
   const uint32_t win_at = pair_window_at<PASS, W, NW>(a);
   const bool ncb = a.no_cluster_breaking != 0;
@@ -826,7 +815,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_pairs_tiled(const AnchorArgs a)
       const bool have = threadIdx.x < nrow;
       PairMember<W> staged;
       pair_stage<W>(a, have, (uint64_t)item.begin + r * kSeedsPerItem + threadIdx.x, row_recs + threadIdx.x * RD, staged);
-      row_cnt[threadIdx.x] = 0u;
       if (part == 0u) { staged_members += (uint32_t)__popcll(__ballot(have)); }   // (wave 0: every member of a group is a row member of ONE first part)
     }
     if (threadIdx.x == 0) { it_next = atomicInc(a.sched_tiled, 0xFFFFFFFFu); }   // (atomicInc, and nothing computed from it here: see `advance` in k_d1_group_pairs)
@@ -870,7 +858,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_pairs_tiled(const AnchorArgs a)
         }
         if (pair_misfiled<NW>(mine, first_win, 0u, PASS)) { ++misfiled; }
       }
-      uint32_t mycount = 0;
       for (uint32_t i = 0; i < nrow; ++i) {
         uint32_t p[RD];
         pair_load_record<W>(row_recs + i * RD, p);
@@ -881,14 +868,8 @@ __global__ __launch_bounds__(kThreads) void k_d1_pairs_tiled(const AnchorArgs a)
         const uint32_t pid = p[4 * W + 2], prank = p[4 * W + 4];
         const bool e1 = near && m.ok != 0u && (ncb || m.rank <= prank);
         const bool e2 = near && p[4 * W + 5] != 0u && (ncb || prank <= m.rank);
-        pair_emit(e1, e2, m.id, pid, seg, seg_room, counting, seg_at, mycount, &row_cnt[i]);
+        pair_emit(e1, e2, m.id, pid, seg, seg_room, seg_at);
       }
-      if (mycount != 0u && a.counts != nullptr) { atomicAdd(&a.counts[m.id - a.first], mycount); }
-    }
-    __syncthreads();
-    if (threadIdx.x < nrow) {
-      const uint32_t total = row_cnt[threadIdx.x];
-      if (total != 0u && a.counts != nullptr) { atomicAdd(&a.counts[row_recs[threadIdx.x * RD + 4 * W + 2] - a.first], total); }
     }
     if (threadIdx.x == 0) { sh_it = gridDim.x + it_next; }
     __syncthreads();                                          // (also: this item's row tile is no longer read)
@@ -908,14 +889,12 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
   __shared__ __attribute__((aligned(16))) uint32_t recs_static[kDynamic ? 4 : kThreads * RD];
   extern __shared__ __attribute__((aligned(16))) uint32_t recs_dynamic[];
   uint32_t * const recs = kDynamic ? recs_dynamic : recs_static;
-  __shared__ uint32_t lcnt[kThreads];
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (told to the compiler: the same in every lane)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t gwave = blockIdx.x * kWaves + wave;
   uint32_t seg_at = a.seg_fill[gwave];
   unsigned long long * const seg = reinterpret_cast<unsigned long long *>(a.edges) + (uint64_t)gwave * a.seg_cap;
   const uint32_t seg_room = (uint32_t)min(a.seg_cap, (uint64_t)0xFFFFFFFFu);
-  const bool counting = a.counts != nullptr;
   uint32_t staged_members = a.seg_staged[gwave], misfiled = 0u;   // (the guard: pair_misfiled)
   const uint32_t win_at = pair_window_at<PASS, W, NW>(a);
   const bool ncb = a.no_cluster_breaking != 0;
@@ -937,7 +916,6 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
       const bool have = threadIdx.x < g;
       PairMember<W> staged;
       pair_stage<W>(a, have, (uint64_t)item.begin + threadIdx.x, recs + threadIdx.x * RD, staged);
-      lcnt[threadIdx.x] = 0u;
       staged_members += (uint32_t)__popcll(__ballot(have));
     }
     if (threadIdx.x == 0) { it_next = atomicInc(a.sched_big, 0xFFFFFFFFu); }
@@ -948,7 +926,6 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
       const bool have = mslot < g;
       PairMember<W> m;
       pair_member_from<W>(recs + (have ? mslot : 0u) * RD, m);
-      uint32_t mycount = 0;
       for (uint32_t t = 1u + wave; t <= half; t += (uint32_t)kWaves) {
         const bool active = have && !(2u * t == g && mslot >= half);      // g even: the opposite member is met by one of the two
         uint32_t pj = mslot + t;
@@ -962,14 +939,8 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
         const uint32_t pid = p[4 * W + 2], prank = p[4 * W + 4];
         const bool e1 = near && m.ok != 0u && (ncb || m.rank <= prank);
         const bool e2 = near && p[4 * W + 5] != 0u && (ncb || prank <= m.rank);
-        pair_emit(e1, e2, m.id, pid, seg, seg_room, counting, seg_at, mycount, &lcnt[pj]);
+        pair_emit(e1, e2, m.id, pid, seg, seg_room, seg_at);
       }
-      if (mycount != 0u) { atomicAdd(&lcnt[mslot], mycount); }
-    }
-    __syncthreads();
-    if (threadIdx.x < g) {
-      const uint32_t total = lcnt[threadIdx.x];
-      if (total != 0u && a.counts != nullptr) { atomicAdd(&a.counts[recs[threadIdx.x * RD + 4 * W + 2] - a.first], total); }
     }
     if (threadIdx.x == 0) { sh_big = gridDim.x + it_next; }
     __syncthreads();                                            // (also: this group's records are no longer read)
@@ -996,17 +967,16 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
   }
   const uint32_t nbundles = upto[kPairClasses - 1u];
   uint32_t * const myrec = recs + (wave * 64u + lane) * RD;
-  uint32_t * const mycnt = lcnt + wave * 64u;
   // Bundles are handed out in batches through 2^shard_bits counters (bundle numbers base << shard_bits | shard).  A visit of
   // a counter is a device-scope atomic with a return value: counters that share a cache line serve ~125 M visits a second
   // between them (measured at 10 M amplicons: pair kernels 0.78 / 1.21 / 2.2 ms with 4 / 2 / 1 bundles per visit and 8
-  // adjacent counters), so (1) the counters lie sched_stride entries apart, (2) a wave's first batch is a fixed one — the
+  // adjacent counters), so (1) the counters lie kSchedStride entries apart, (2) a wave's first batch is a fixed one — the
   // counters start behind those — and (3) the visit for the NEXT batch is issued by the first bundle of the current
   // one, behind its line fetches, and is awaited only when that batch is finished: the compute of the batch hides it.
   const uint32_t kBatch = a.batch;
   const uint32_t nshards = 1u << a.shard_bits;
   const uint32_t shard = blockIdx.x & (nshards - 1u);
-  uint32_t * const my_sched = a.sched_wide + (uint64_t)shard * a.sched_stride;
+  uint32_t * const my_sched = a.sched_wide + (uint64_t)shard * kSchedStride;
   const uint32_t shard_waves = ((gridDim.x + nshards - 1u - shard) >> a.shard_bits) * (uint32_t)kWaves;
   uint32_t bi = 0, batch_left = 0;
   const uint32_t fixed_base = ((blockIdx.x >> a.shard_bits) * (uint32_t)kWaves + wave) * kBatch;
@@ -1081,19 +1051,11 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
     const uint32_t sub = lane >> shift, j = lane & (S - 1u);
     const uint32_t g = g0, half = g >> 1;
     const bool have = j < g;
-#if SWA_PAIR_EXPERIMENT & 2
-    rank = id0; len = have ? 32u * W - 10u : 0u;                  // (experiment: no line fetch — words made up from the id)
-#pragma unroll
-    for (int k = 0; k < W; ++k) { w64[k] = have ? mix64((uint64_t)id0 * 31u + (uint64_t)k) >> (k == W - 1 ? 20 : 0) : 0ull; }
-#endif
     PairMember<W> m;
     pair_stage_line<W>(a, have, id0, rank, len, w64, myrec, m);
-    if (counting) { mycnt[lane] = 0u; }
     staged_members += (uint32_t)__popcll(__ballot(have));
     // the fetches of the bundles behind this one, each a step further along its chain
-#if !(SWA_PAIR_EXPERIMENT & 2)
     if (more1) { pair_fetch_line<W>(a, (lane & ((1u << shift1) - 1u)) < g1, id1, rank, len, w64); }
-#endif
     uint32_t id2 = 0;
     if (more2) { id2 = member_id(shift2, item2); }
     const uint32_t g2 = item2.size;
@@ -1104,14 +1066,8 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if !(SWA_PAIR_EXPERIMENT & 2)
     if (have && pair_misfiled<NW>(myrec, recs + (wave * 64u + (sub << shift)) * RD, win_at, PASS)) { ++misfiled; }
-#endif
-    uint32_t mycount = 0;
     for (uint32_t t = 1u; t <= 32u; ++t) {
-#if SWA_PAIR_EXPERIMENT & 1
-      break;                                                      // (experiment: no turns — fetches and staging only)
-#endif
       const bool active = have && t <= half && !(2u * t == g && j >= half);
       if (__ballot(active) == 0ull) { break; }
       uint32_t pj = j + t;
@@ -1126,19 +1082,11 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
       const uint32_t pid = p[4 * W + 2], prank = p[4 * W + 4];
       const bool e1 = near && m.ok != 0u && (ncb || m.rank <= prank);
       const bool e2 = near && p[4 * W + 5] != 0u && (ncb || prank <= m.rank);
-#if SWA_PAIR_EXPERIMENT & 4
-      if (__ballot(e1 && e2 && pid == 0xFFFFFFFFu) != 0ull)          // (experiment: the comparisons without the emission)
-#endif
-      pair_emit(e1, e2, m.id, pid, seg, seg_room, counting, seg_at, mycount, &mycnt[pslot]);
+      pair_emit(e1, e2, m.id, pid, seg, seg_room, seg_at);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        // (the next bundle overwrites the records)
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (counting) {
-      const uint32_t total = mycount + mycnt[lane];
-      if (total != 0u) { atomicAdd(&a.counts[m.id - a.first], total); }
-    }
-    __builtin_amdgcn_wave_barrier();                              // (the next bundle overwrites records and counters)
     more0 = more1; shift0 = shift1; id0 = id1; g0 = g1;
     more1 = more2; shift1 = shift2; id1 = id2; g1 = g2;
     more2 = more3; shift2 = shift3; item2 = item3;

@@ -3,7 +3,7 @@
 //
 // Round 2 grouped the amplicons with hash tables in HBM: one device-scope atomic per amplicon and index
 // (k_anchor_place), one random 8-byte offset read + one random 16-byte record write per member (k_anchor_scatter),
-// one random offset read + cursor atomic + random 4-byte write per link (k_scatter_edges).  rocprofv3 showed what that
+// one random offset read + cursor atomic + random 4-byte write per link (a scatter of the links into counted rows).  rocprofv3 showed what that
 // costs on this memory system: an atomic drops its line from L2 and goes to the fabric, every 8- or 16-byte random
 // access moves 64-128 bytes — 3.2 of the step's 5.9 ms at 10 M amplicons, 4.4 x the bytes the algorithm needs.
 //
@@ -31,8 +31,8 @@
 //
 // Two keys with equal 32-bit values share a group (about n^2 / 2^33 group pairs): harmless — every pair test is exact.
 
-constexpr uint32_t kPartTileMax = 4096;           // records per tile of k_part_hist: 4096 (plain records: 32 KB of LDS staging; records + fingerprints with
-                                                  // 1024 bins: 48 KB) or 2048 (records + fingerprints, <= 512 bins: 24 KB) — PartArgs::tile
+constexpr uint32_t kPartTileMax = 4096;           // records per tile of k_part_hist (PartArgs::tile: 2048 or 4096; the one-level key
+                                                  // partition scatters tiles of 8192, its histogram taken by k_keys)
 constexpr uint32_t kPartMaxBits = 9;               // bits per level (512 bins) — 10 for the one-level key partition in front of k_group1;
                                                   // 2048 bins were tried: the flat count array — bins x tiles — grows with them and costs more than a level
 constexpr unsigned long long kRecAbsent = ~0ull;  // a record slot that holds nothing (amplicon without this window / not owned)
@@ -354,9 +354,7 @@ __global__ __launch_bounds__(256) void k_guard_records(const GuardRecArgs a) {
 // through LDS so that a tile's records for one digit leave as one contiguous run.
 struct PartIdx {
   const unsigned long long * in;
-  const uint32_t * in_f;             // second payload (fingerprints), or nullptr
   unsigned long long * out;
-  uint32_t * out_f;
   uint32_t * out32;                  // last level of the link sort: only the low halves (targets) are kept
   uint64_t out_cap;                  // entries the output buffers hold (writes beyond are dropped: the caller grows and repeats)
   const uint64_t * cstart;           // [chunks + 1] first record of chunk c (or [chunks] when csize is given); nullptr: chunk c
@@ -650,19 +648,17 @@ __device__ __forceinline__ uint64_t block_exclusive_scan_of(uint64_t v, uint64_t
   return wave_off + incl - v;
 }
 
-// MODE 0: records; 1: records + second payload (for the sets that have one); 2: only the low halves are written (out32)
-// THREADS: 256 / 512 / 1024 a workgroup for the same tile — the staging area (32–48 KB) allows two or three workgroups a
-// CU, so the waves that hide the loads' and stores' way are a matter of the workgroup's size
+// MODE 0: records; 2: only the low halves are written (out32)
+// THREADS: 512 a workgroup, 1024 for the tile of 8192 — the staging area (22–76 KB) allows one to three workgroups a CU,
+// so the waves that hide the loads' and stores' way are a matter of the workgroup's size
 // (SPAN: told to stay within the 64 registers that four 512-thread workgroups a CU need — it came out at 70)
 template <int MODE, uint32_t TILE, uint32_t BINS, uint32_t THREADS, bool SPAN = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN && THREADS == 512 ? 8 : 1))) void k_part_scatter(const PartArgs a) {
   constexpr uint32_t kPartPer = TILE / THREADS;
-  // (dynamic LDS — part_scatter_lds bytes: a tile of 8192 records with their fingerprints is 108 KB, beyond what a kernel
-  // gets unasked)
+  // (dynamic LDS — part_scatter_lds bytes: a tile of 8192 records with 1024 bins is 76 KB, beyond what a kernel gets unasked)
   extern __shared__ __attribute__((aligned(16))) unsigned long long part_lds[];
   unsigned long long * stage = part_lds;                                     // [TILE]
-  uint32_t * stage_f = reinterpret_cast<uint32_t *>(stage + TILE);            // [TILE] (MODE 1)
-  uint32_t * hist = stage_f + (MODE == 1 ? TILE : 0u);                        // [BINS]
+  uint32_t * hist = reinterpret_cast<uint32_t *>(stage + TILE);               // [BINS]
   uint32_t * lstart = hist + BINS;                                            // [BINS]
   uint32_t * goff = lstart + BINS;                                            // [BINS]
   __shared__ uint64_t smem[THREADS / 64u];
@@ -677,14 +673,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
     for (uint32_t b = threadIdx.x; b < bins; b += THREADS) { hist[b] = 0u; }
     PartTile tile{0u, 0u, 0ull};
     unsigned long long rec[kPartPer];
-    uint32_t f[kPartPer], pos[kPartPer];
+    uint32_t pos[kPartPer];
     const auto digit_of = [&](unsigned long long r) { return (((uint32_t)(r >> 32) - a.bias) >> a.shift) & (bins - 1u); };
     if constexpr (SPAN) {
 #pragma unroll
-      for (uint32_t k = 0; k < kPartPer; ++k) { rec[k] = kRecAbsent; f[k] = 0u; pos[k] = 0u; }
+      for (uint32_t k = 0; k < kPartPer; ++k) { rec[k] = kRecAbsent; pos[k] = 0u; }
       (void)part_span<kPartPer, THREADS>(p, TILE, t, span, [&](uint32_t k, uint64_t place) {
         rec[k] = p.in[place];
-        if (MODE == 1 && p.in_f != nullptr) { f[k] = p.in_f[place]; }
         if (rec[k] != kRecAbsent) { pos[k] = atomicAdd(&hist[digit_of(rec[k])], 1u); }
       });
     } else {
@@ -692,11 +687,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
 #pragma unroll
       for (uint32_t k = 0; k < kPartPer; ++k) {
         const uint32_t j = k * THREADS + threadIdx.x;
-        rec[k] = kRecAbsent; f[k] = 0u; pos[k] = 0u;
-        if (j < tile.count) {
-          rec[k] = p.in[tile.first + j];
-          if (MODE == 1 && p.in_f != nullptr) { f[k] = p.in_f[tile.first + j]; }
-        }
+        rec[k] = kRecAbsent; pos[k] = 0u;
+        if (j < tile.count) { rec[k] = p.in[tile.first + j]; }
         if (rec[k] != kRecAbsent) { pos[k] = atomicAdd(&hist[digit_of(rec[k])], 1u); }
       }
     }
@@ -723,7 +715,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
       if (rec[k] != kRecAbsent) {
         const uint32_t at = lstart[(((uint32_t)(rec[k] >> 32) - a.bias) >> a.shift) & (bins - 1u)] + pos[k];
         stage[at] = rec[k];
-        if (MODE == 1) { stage_f[at] = f[k]; }
       }
     }
     __syncthreads();
@@ -739,7 +730,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
         const uint64_t g = (uint64_t)goff[d] + (j - lstart[d]);
         if (g < p.out_cap) {
           if (MODE == 2) { p.out32[g] = (uint32_t)r; } else { p.out[g] = r; }
-          if (MODE == 1 && p.out_f != nullptr) { p.out_f[g] = stage_f[j]; }
         }
       }
     }
@@ -747,7 +737,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
   }
 }
 
-constexpr size_t part_scatter_lds(int mode, uint32_t tile, uint32_t bins) { return (size_t)tile * 8u + (mode == 1 ? (size_t)tile * 4u : 0u) + 3u * (size_t)bins * 4u; }
+constexpr size_t part_scatter_lds(uint32_t tile, uint32_t bins) { return (size_t)tile * 8u + 3u * (size_t)bins * 4u; }
 
 // first record of every bucket this level made: the chunk table of the next level (or of the consumer)
 __global__ __launch_bounds__(256) void k_part_starts(const PartArgs a) {

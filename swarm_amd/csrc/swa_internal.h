@@ -64,7 +64,7 @@ struct swa_ctx {
   swa_dbuf d_flags;              // u32[16]: [0] duplicate flag
   swa_dbuf d_stats;              // u64[8] probe statistics + [8] edge counter
   swa_dbuf d_edges;              // u64 edge list (src << 32 | dst)
-  swa_dbuf d_counts, d_cursor, d_scan_tmp, d_offsets_tmp, d_nb_tmp, d_long_rows;
+  swa_dbuf d_counts, d_cursor, d_scan_tmp, d_offsets_tmp, d_nb_tmp;
   // anchored d=1 index (d1_anchor.inc, d1_stream.inc): [0] prefix groups, [1] suffix groups
   bool anchor_usable = false;    // decided by swa_d1_index_build: lengths fit, db order holds, not switched off
   bool anchor_ready = false;     // the streaming index below exists (for the owner in owner_rank / owner_world)
@@ -161,7 +161,7 @@ struct swa_ctx {
   uint32_t cluster_maxgen = 0;
   int pair_blocks[4] = {};                      // workgroups of k_d1_group_pairs a CU holds, per width class (0: not asked yet)
   bool g1_lds_opt_in = false;                  // k_group1's dynamic-LDS attribute has been set on this context's device
-  uint32_t part_lds_opt_in = 0;    // ... and the wide-tile forms of k_part_scatter (one bit each)
+  bool part_lds_opt_in = false;                // ... and the wide-tile form of k_part_scatter
   uint32_t pair_lds_opt_in = 0;    // ... and the W = 15 / 21 forms of k_d1_group_pairs (pass + 2 (W = 21) + 4 (NW = 2) + 8 (NW = 4))
   bool csr_has_diffs = false;                 // the resident network is a d >= 2 graph: one byte of differences per link behind the neighbours
   uint64_t csr_total = 0;

@@ -44,18 +44,25 @@ def test_network_matches_oracle(gpu_ctx, tmp_path, n, L, seed, ncb):
     assert np.array_equal(nb, wnb)
 
 
-def test_network_subrange_and_capacity(gpu_ctx, tmp_path):
+def test_network_subrange_and_capacity(gpu_ctx, tmp_path, monkeypatch):
     fa = tmp_path / "in.fa"
     S.gen_fasta(fa, 5000, 150, 21)
     db = S.db_from_fasta(fa)
-    _upload(gpu_ctx, db)
-    gpu_ctx.d1_index_build()
-    full_off, full_nb = gpu_ctx.d1_network()
-    for first, count in [(0, 1), (17, 1000), (4000, 1000), (4999, 1)]:
-        off, nb = gpu_ctx.d1_network(False, first, count)
-        lo, hi = int(full_off[first]), int(full_off[first + count])
-        assert np.array_equal(off, full_off[first:first + count + 1] - full_off[first])
-        assert np.array_equal(nb, full_nb[lo:hi])
+    anchored = None
+    for plain in (False, True):            # (the plain route: the streaming CSR over the plain kernel's segments)
+        if plain:
+            monkeypatch.setenv("SWA_D1_PLAIN", "1")
+        _upload(gpu_ctx, db)
+        gpu_ctx.d1_index_build()
+        full_off, full_nb = gpu_ctx.d1_network()
+        if anchored is None:
+            anchored = (full_off, full_nb)
+        assert np.array_equal(full_off, anchored[0]) and np.array_equal(full_nb, anchored[1])
+        for first, count in [(0, 1), (17, 1000), (4000, 1000), (4999, 1)]:
+            off, nb = gpu_ctx.d1_network(False, first, count)
+            lo, hi = int(full_off[first]), int(full_off[first + count])
+            assert np.array_equal(off, full_off[first:first + count + 1] - full_off[first])
+            assert np.array_equal(nb, full_nb[lo:hi])
 
 
 def test_duplicates_are_reported(gpu_ctx, tmp_path):
