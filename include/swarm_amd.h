@@ -235,8 +235,7 @@ int swa_d1_guard_retries(const swa_ctx * ctx);
 
 /* Introspection used by the parity tests (bit-exact against the oracle): copies to host.
    what: 0 seqhash u64[n] · 1 Bloom bitmap u64[table_size/8] · 2 Zobrist table
-   u64[4*(longest+2)] · 3 probe statistics u64[8] of the last network call
-   {variants, bloom_pass, hash_match, verified, hits, 0,0,0} (0..3 build the database-wide structures on demand)
+   u64[4*(longest+2)] (0..2 build the database-wide structures on demand)
    · 10 / 11 member ids in group order of the streaming prefix / suffix index u32[n] · 12 / 13 their work-item
    buffers · 14 the counters u32[64] · 15 the amplicon lines (tools/check_index.py, tools/check_stream.py) */
 int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out_bytes);
@@ -366,12 +365,11 @@ int swa_dn_graph_totals(swa_ctx * ctx, uint64_t * out3);
 /* ---- d = 1 on several GPUs of one node --------------------------------
    Replaces the thread fan-out of src/algod1.cc:1166-1167 / src/utils/threads.h:145-162: one context, stream and
    host thread per listed device inside the calling process; the database replicated, the probing divided by
-   ownership of anchor groups (swa_d1_set_ownership): routed index build (the ranks' id lists all-to-all, grouped
-   ncclSend / ncclRecv over xGMI), every rank's flat link list gathered on rank 0 (grouped ncclSend / ncclRecv: the one
-   consumer of the network is the host behind rank 0 — an all-gather, which round 2 used and `bench.py --gpus N` still
-   times as the north star names it, moves world x the bytes), CSR assembled there on the device; fastidious: heavy
-   amplicons split, graft_cand combined with ncclAllReduce(min).  librccl.so is loaded when the first handle with ranks
-   on distinct devices is created, not with the library.  A device may be listed more than once (several ranks on one GPU: the exchange then uses
+   ownership of anchor groups (swa_d1_set_ownership): routed index build (every rank keys its own slice and the key
+   records travel to their owners, grouped ncclSend / ncclRecv over xGMI), every rank's flat link list gathered on
+   rank 0 only (grouped ncclSend / ncclRecv: the one consumer of the network is the host behind rank 0), CSR assembled
+   there on the device; fastidious: heavy amplicons split, graft_cand combined with ncclAllReduce(min).  librccl.so is
+   loaded when the first handle with ranks on distinct devices is created, not with the library.  A device may be listed more than once (several ranks on one GPU: the exchange then uses
    device-to-device copies — RCCL admits one rank per GPU); results never depend on the device list. */
 typedef struct swa_multi swa_multi;
 int  swa_multi_create(const int * devices, int ndevices, swa_multi ** out);

@@ -634,10 +634,9 @@ int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, 
     w.ring = std::min<uint32_t>(ctx->wfa_ring != 0 ? ctx->wfa_ring : ctx->wfa_steps, ctx->wfa_steps);
     // the diagonals a score <= T can reach: a gap of g columns costs open + g extend, so |k| <= (T - open) / extend — the band
     // of the wavefront kernel (the banded kernels keep the wider T / extend + 1).  Where band + guards fit 16 lanes, a wave
-    // takes four pairs (SWA_ALIGN_WFA_LANES=32: two, as until round 5)
+    // takes four pairs (two, as until round 5, where they need 32)
     const uint64_t wfa_w = T >= go + ge ? (T - go) / ge : 0;
-    static const bool lanes32 = [] { const char * e = std::getenv("SWA_ALIGN_WFA_LANES"); return e != nullptr && std::atoi(e) == 32; }();
-    const bool narrow = !lanes32 && 2 * wfa_w + 3 <= 16;
+    const bool narrow = 2 * wfa_w + 3 <= 16;
     const uint32_t per_block = narrow ? 8u : 4u;
     if (narrow) { w.a.W = (int)wfa_w; }
     uint64_t wblocks = ((uint64_t)max_count + per_block - 1) / per_block;

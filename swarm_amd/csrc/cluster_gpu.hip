@@ -41,16 +41,14 @@ __global__ __launch_bounds__(256) void k_label_init(uint32_t * label, uint32_t *
 // the last sweep that changed label[v]; a change made to v after v's own thread went by is handed on by the next sweep.
 // Sweeps are launched ahead in batches: one behind a sweep that changed nothing (the fixed point) returns at once.
 __global__ __launch_bounds__(256) void k_label_sweep(const uint64_t * __restrict__ offsets, const uint32_t * __restrict__ nb, uint32_t n,
-                                                     uint32_t * label, uint32_t * stamp, uint32_t s, uint32_t * flags, uint32_t jump_all) {
+                                                     uint32_t * label, uint32_t * stamp, uint32_t s, uint32_t * flags) {
   if (s > 1u && __hip_atomic_load(&flags[s - 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) { return; }
   bool any = false;
   for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < n; u += gridDim.x * blockDim.x) {
     uint32_t lu = label[u];
     bool active = stamp[u] + 1u >= s;
-    if (jump_all != 0u || active) {
-      const uint32_t ll = label[lu];
-      if (ll < lu) { atomicMin(&label[u], ll); lu = ll; stamp[u] = s; any = true; active = true; }
-    }
+    const uint32_t ll = label[lu];
+    if (ll < lu) { atomicMin(&label[u], ll); lu = ll; stamp[u] = s; any = true; active = true; }
     if (!active) { continue; }
     for (uint64_t e = offsets[u]; e < offsets[u + 1]; ++e) {
       const uint32_t v = nb[e];
@@ -214,14 +212,13 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     std::fprintf(stderr, "[cluster gpu] %-28s %8.3f ms  (%u)\n", what, t - t_last, count);
     t_last = t;
   };
-  static const bool jump_all = [] { const char * e = getenv("SWA_CLUSTER_JUMP"); return e == nullptr || e[0] != 'a'; }();   // ("active": experiment)
   lap("buffers", 0);
   hipLaunchKernelGGL(k_label_init, g, b, 0, ctx->stream, label, par, stamp, gen, n);
   // ---- swarms: the smallest id that reaches every vertex
   for (uint32_t s = 1;;) {
     if (s == 1u) { SWA_HIP(ctx, hipMemsetAsync(flags, 0, kSweepFlags * sizeof(uint32_t), ctx->stream)); }
     const uint32_t last = std::min(s + kSweepBatch, kSweepFlags) - 1u;
-    for (; s <= last; ++s) { hipLaunchKernelGGL(k_label_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, stamp, s, flags, jump_all ? 1u : 0u); }
+    for (; s <= last; ++s) { hipLaunchKernelGGL(k_label_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, stamp, s, flags); }
     uint32_t changed = 0;
     SWA_HIP(ctx, hipMemcpyAsync(&changed, flags + last, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));

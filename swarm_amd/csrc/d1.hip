@@ -63,7 +63,6 @@ struct NetArgs {
   uint64_t * edges;             // (src << 32) | dst
   uint64_t seg_cap;             // edges are appended to per-wave segments: segment w = edges[w*seg_cap ..)
   uint32_t * seg_fill;          // [launch waves] fill of each segment (no atomics: one writer per segment)
-  unsigned long long * stats;   // [0] variants [1] bloom pass [2] hash match [3] verified
   // MODE 2 (seeds the anchored passes cannot serve): explicit (seed, position range) list
   const struct swa_fallback * fallback;
   const uint32_t * fallback_count;
@@ -294,7 +293,7 @@ template <bool SECOND>
 __device__ __forceinline__ bool probe_and_verify(const NetArgs & a, const uint64_t * sw, uint32_t slen,
                                                  uint32_t snw, uint32_t seed, uint64_t seed_abundance,
                                                  uint64_t h, uint32_t code, uint32_t & out_amp,
-                                                 uint32_t & n_match, int window_filter = 0, uint32_t win_word = 0, uint32_t nwin = 1) {
+                                                 int window_filter = 0, uint32_t win_word = 0, uint32_t nwin = 1) {
   const uint32_t type = code & 3u;
   const uint32_t base = (code >> 2) & 3u;
   const uint32_t pos = code >> 4;
@@ -305,7 +304,6 @@ __device__ __forceinline__ bool probe_and_verify(const NetArgs & a, const uint64
     const swa_slot s = a.table[idx];
     if (s.amp == kEmpty) { return false; }
     if (s.hash == h) {
-      ++n_match;
       const uint32_t amp = s.amp;
       const uint32_t alen = a.seqlen[amp];
       bool allowed;
@@ -333,7 +331,7 @@ __device__ __forceinline__ bool probe_and_verify(const NetArgs & a, const uint64
 // MODE 0: the d=1 network (query = amplicon first+k of the database).
 // MODE 1: fastidious second level (query k = the microvariant tasks[k] of a heavy amplicon;
 //         every verified light amplicon gets graft_cand = min(heavy id), algod1.cc:244-258).
-template <bool ZLDS, bool STATS, int MODE>
+template <bool ZLDS, int MODE>
 __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
   extern __shared__ uint64_t lds[];
   // LDS carve-up (all 8-byte aligned)
@@ -355,7 +353,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
   __syncthreads();
   const uint64_t * zob = ZLDS ? zob_lds : a.zobrist;
 
-  unsigned long long st_var = 0, st_pass = 0, st_match = 0, st_ver = 0;
   unsigned long long cand_total = 0;                         // MODE 1: graft candidates found by this wave
   const uint64_t lane_lt = (1ull << lane) - 1ull;
   // this wave's private output segment (a single shared edge counter costs one contended
@@ -402,19 +399,14 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
     auto drain = [&](uint32_t cnt) {
       bool hit = false;
       uint32_t amp = 0;
-      uint32_t nmatch = 0;
       if ((uint32_t)lane < cnt) {
         // MODE 2: a seed's two halves are divided by the prefix-side window itself, as the pair kernels divide them — range 1
         // keeps only neighbours that share it, range 2 only those that do not.  (By position alone the halves overlap: a
         // deletion at position 31, or inside a run that ends there, is listed at a position >= pb AND changes the window.)
         const int wf = MODE != 2 ? 0 : (int)range;
-        hit = probe_and_verify<MODE == 1>(a, sw, len, nw, seed, seed_ab, qh[lane], qc[lane], amp, nmatch, wf, a.win_word, MODE == 2 ? a.anchor_w / 32u : 1u);
+        hit = probe_and_verify<MODE == 1>(a, sw, len, nw, seed, seed_ab, qh[lane], qc[lane], amp, wf, a.win_word, MODE == 2 ? a.anchor_w / 32u : 1u);
       }
       const uint64_t hm = __ballot(hit);
-      if (STATS) {
-        for (int o = 32; o > 0; o >>= 1) { nmatch += __shfl_down(nmatch, o, 64); }
-        st_match += __shfl(nmatch, 0, 64);
-      }
       if (hm != 0ull) {
         const uint32_t nh = (uint32_t)__popcll(hm);
         if (MODE == 0 || MODE == 2) {
@@ -427,7 +419,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
           if (hit) { atomicMin(&a.graft[amp], seed); }
         }
         row += nh;
-        if (STATS) { st_ver += nh; }
       }
     };
 
@@ -440,7 +431,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
         qc[at] = code;
       }
       qn += (uint32_t)__popcll(m);
-      if (STATS) { st_pass += (unsigned long long)__popcll(m); }
       if (qn >= 64u) {
         wave_lds_sync();
         drain(64u);
@@ -464,7 +454,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const bool pass = s.ok[i] && ((word[i] & pat[s.hs[i] & 1023u]) == 0ull);   // bloompat.cc:68-71
-        if (STATS) { st_var += (unsigned long long)__popcll(__ballot(s.ok[i])); }
         enqueue(pass, s.hs[i], s.code[i]);
       }
     };
@@ -489,12 +478,6 @@ __global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
   }
   if (MODE != 1 && lane == 0) { a.seg_fill[gwave] = seg_at; }
   if (MODE == 1 && lane == 0 && cand_total != 0ull) { atomicAdd(a.cand_counter, cand_total); }
-  if (STATS && lane == 0) {
-    atomicAdd(&a.stats[0], st_var);
-    atomicAdd(&a.stats[1], st_pass);
-    atomicAdd(&a.stats[2], st_match);
-    atomicAdd(&a.stats[3], st_ver);
-  }
 }
 
 #include "d1_anchor.inc"
@@ -794,12 +777,6 @@ static bool anchored_enabled() {
   return !(e != nullptr && e[0] == '1');
 }
 
-// SWA_D1_OWNED_FULL=1: the database-wide table and Bloom filter are built as well (test hook: the plain kernel's structures)
-static bool owned_index_enabled() {
-  const char * e = getenv("SWA_D1_OWNED_FULL");
-  return !(e != nullptr && e[0] == '1');
-}
-
 // shortest seed the anchored passes serve: two windows and a nucleotide (65 with the 32-nt windows of rounds 1-3)
 static uint32_t anchor_minlen(const swa_ctx * ctx) { return ctx->anchor_a + ctx->anchor_b + 2u * ctx->anchor_w + 1u; }
 
@@ -818,12 +795,10 @@ static uint32_t anchor_max_nwin(const swa_ctx *) {
   if (const char * e = getenv("SWA_D1_ANCHOR_W")) { cap = std::min(4u, std::max(1u, (uint32_t)atoi(e) / 32u)); }
   return cap;
 }
-// groups of 65..pair_big members go to the pair kernel as well (one workgroup each); SWA_D1_PAIR_BIG=64 leaves
-// them to the tiled kernel (test switch)
-static bool member_index_enabled();
-static uint32_t pair_big_limit() {
-  const char * env = getenv("SWA_D1_PAIR_BIG");
-  return env != nullptr ? std::min<uint32_t>(kPairBigCap, std::max<uint32_t>(kSeedsPerItem, (uint32_t)atoi(env))) : kPairBigCap;
+// SWA_D1_WINDOWS=0: the anchor windows stay at the ends (no sample, no search for windows moved inwards)
+static bool windows_search_off() {
+  const char * e = getenv("SWA_D1_WINDOWS");
+  return e != nullptr && e[0] == '0';
 }
 
 // Shortest sequence and the population of every width class: facts of the uploaded database (k_db_lengths), read once per
@@ -846,10 +821,10 @@ static int ensure_db_lengths(swa_ctx * ctx) {
 // Where the work lists of an index lie in its item buffer.  A group of width class c has a member of that class, and all
 // its members are of classes <= c; a group on size list k has at least least[k] members: so list (c, k) holds at most
 // min(pop[c], pop[<= c] / least[k]) groups, and the row tiles of class c (64 members each, of groups of more than 256)
-// number at most pop[<= c] / 64 + pop[<= c] / (pair_big + 1), pair_big = the largest group a workgroup takes by pairs
-// (256 unless SWA_D1_PAIR_BIG lowers it).  A database of one class — the usual one — pays for one class.
+// number at most pop[<= c] / 64 + pop[<= c] / (kPairBigCap + 1), kPairBigCap = the largest group a workgroup takes by
+// pairs.  A database of one class — the usual one — pays for one class.
 static ListRegions list_regions(const swa_ctx * ctx, uint64_t * total_items) {
-  const uint32_t least[kListKinds] = {2, 5, 9, 17, 33, 65, pair_big_limit() + 1u};
+  const uint32_t least[kListKinds] = {2, 5, 9, 17, 33, 65, kPairBigCap + 1u};
   ListRegions r{};
   uint64_t at = 0, upto = 0;
   for (uint32_t c = 0; c < kWidthClasses; ++c) {
@@ -1166,7 +1141,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   k.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
   // (single GPU, the whole database keyed: the short sequences and their possible neighbours become members of the plain
   // kernel's table; a rank of a multi-GPU job keeps the database-wide table for them)
-  k.mark_short = (!routed && ctx->owner_world == 1u && member_index_enabled()) ? static_cast<uint8_t *>(ctx->d_stream[kSbOver].ptr) : nullptr;
+  k.mark_short = (!routed && ctx->owner_world == 1u) ? static_cast<uint8_t *>(ctx->d_stream[kSbOver].ptr) : nullptr;
   if (const char * e = getenv("SWA_D1_GUARD_TEST")) {         // (test hook: a wrong index, on purpose; "...-once": only the first build)
     static int builds = 0;
     const bool once = strstr(e, "-once") != nullptr;
@@ -1245,7 +1220,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     x.items_tmp = j.buf[i][j.last ^ 1];
     x.kind_cnt = static_cast<uint32_t *>(ctx->d_stream[kSbKind + i].ptr);
   }
-  g.pair_big = pair_big_limit(); g.group_cap = kStreamGroupCap;   // (the tiled pair kernel serves every group up to that)
+  g.pair_big = kPairBigCap; g.group_cap = kStreamGroupCap;   // (the tiled pair kernel serves every group up to that)
   g.flags = dflags;
   g.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
   g.over = static_cast<uint8_t *>(ctx->d_stream[kSbOver].ptr);
@@ -1438,7 +1413,6 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   SWA_TRY(clear_launch(ctx, clears));
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const uint32_t maxwords = (ctx->db.longest + 31u) >> 5;
-  auto * stats = static_cast<unsigned long long *>(ctx->d_stats.ptr);
   swa_t0(ctx, 3);
   const bool window_mode = ctx->anchor_a != 0 || ctx->anchor_b != 0;
   uint64_t item_room = 0;
@@ -1523,7 +1497,6 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   f.edges = static_cast<uint64_t *>(ctx->d_edges.ptr);
   f.seg_cap = ctx->seg_cap;
   f.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
-  f.stats = stats;
   f.fallback = static_cast<const swa_fallback *>(ctx->d_afallback.ptr);
   f.fallback_count = acounters + 2;
   f.aux = static_cast<const swa_aux *>(ctx->d_aux.ptr);
@@ -1535,8 +1508,8 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   // (a rank that built only its owned groups has no table: by construction its fallback list is
   // empty — network_run checks the count and builds the full index if that ever fails to hold)
   if (!ctx->full_index && !ctx->member_index) { /* nothing to probe against */ }
-  else if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, false, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
-  else { hipLaunchKernelGGL((k_d1_probe<false, false, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
+  else if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
+  else { hipLaunchKernelGGL((k_d1_probe<false, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
   swa_t1(ctx, 3);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
@@ -1612,19 +1585,18 @@ static int ensure_full_index(swa_ctx * ctx) {
 
 // Anchor windows for this database, from a sample (k_anchor_sample): the smallest offset whose estimated share of
 // amplicons in oversized groups and of too-short seeds is below 1 / 64 each; (0, 0) when nothing is skewed, which is
-// the normal case.  Window mode needs the pair kernels (sequences up to 416 nt); SWA_D1_WINDOWS=0 switches it off.
+// the normal case.  Window mode needs the pair kernels (sequences up to 416 nt).
 static int choose_anchor_windows(swa_ctx * ctx) {
   ctx->anchor_a = ctx->anchor_b = 0;
   ctx->anchor_w = 32;
   SWA_TRY(ensure_db_lengths(ctx));
   const uint32_t shortest = ctx->db_shortest;
-  const char * env_win = getenv("SWA_D1_WINDOWS");
   const uint32_t n = ctx->db.n;
   const uint32_t max_nwin = anchor_max_nwin(ctx);
   // the ends, as wide as the shortest sequence allows — unless the sample finds them skewed (conserved flanks), then 32-nt
   // windows moved inwards
   ctx->anchor_w = 32u * anchor_nwin_for(shortest, 0u, max_nwin);
-  if (env_win != nullptr && env_win[0] == '0') { return SWA_OK; }
+  if (windows_search_off()) { return SWA_OK; }
   const uint32_t stride = std::max<uint32_t>(1u, n / 65536u);
   const uint32_t samples = (n + stride - 1) / stride;
   const size_t slots = (size_t)2 * kSampleCandidates * kSampleSlots;
@@ -1672,11 +1644,7 @@ static int ensure_anchor_windows(swa_ctx * ctx) {
 // a member of that group, so nothing else needs to be in the table — and a Bloom filter of a few megabytes stays in L2
 // where the database-wide one (one byte per table slot: 33 MB at 10 M) is a random HBM / Infinity-Cache line per probe.
 // Identical sequences among the members are found through the same table (k_dup_check), as the reference finds them
-// while it inserts (src/algod1.cc:1131-1150).  SWA_D1_MEMBER_TABLE=0: the database-wide structures instead.
-static bool member_index_enabled() {
-  const char * e = getenv("SWA_D1_MEMBER_TABLE");
-  return !(e != nullptr && e[0] == '0');
-}
+// while it inserts (src/algod1.cc:1131-1150).
 
 static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_count) {
   ctx->member_index = false;
@@ -1757,7 +1725,7 @@ static int build_owned_index(swa_ctx * ctx, uint32_t first, uint32_t count, bool
   // (groups left to the plain kernel — and, on a single GPU, sequences too short for two windows — are the ONLY reason: a
   // table of their members alone serves it — build_member_index)
   ctx->only_oversized = flags[1] == 0 && (flags[4] != 0 || flags[3] != 0) &&
-                        (flags[3] == 0 || (ctx->owner_world == 1u && ctx->route_ids[0] == nullptr && ctx->route_rec[0] == nullptr && member_index_enabled()));
+                        (flags[3] == 0 || (ctx->owner_world == 1u && ctx->route_ids[0] == nullptr && ctx->route_rec[0] == nullptr));
   ctx->over_mass = flags[5];
   return SWA_OK;
 }
@@ -1801,7 +1769,7 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
   uint32_t group_dups = 0;
   // The lean build (no database-wide table / Bloom / table-based duplicate check) serves a single GPU as well
   // as a rank of a multi-GPU job: with world = 1 this GPU owns every anchor group.
-  if (ctx->anchor_usable && owned_index_enabled()) {
+  if (ctx->anchor_usable) {
     bool needs_table = false;
     uint32_t mass = 0, shortest = 0;
     swa_lap(ctx, "(index build: before the windows)");
@@ -1812,14 +1780,12 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
     SWA_TRY(build_owned_index(ctx, first, count, &needs_table, &group_dups, &mass, &shortest));
     // Conserved flanks: when a noticeable part of the database sits in groups too large for LDS (everybody shares
     // the first or last 32 nt), the anchor windows move inwards, 32 nt at a time, as far as the shortest sequence
-    // allows (every seed needs win_a + win_b + 65 nt), and the setting with the fewest stranded members wins.  Window
-    // SWA_D1_WINDOWS=0 switches the search off.
-    const char * env_win = getenv("SWA_D1_WINDOWS");
+    // allows (every seed needs win_a + win_b + 65 nt), and the setting with the fewest stranded members wins.
     // (safety net behind the sample: the real build still found too many stranded members — try the next offsets.
     // Single GPU only: under ownership `mass` counts the oversized groups THIS rank owns, the ranks would settle on
     // different windows and divide the pairs differently; there the sampled choice — the same on every rank — stands
     // and oversized groups take the plain kernel)
-    if (!routed && ctx->owner_world == 1 && needs_table && mass > n / 64u && !(env_win != nullptr && env_win[0] == '0')) {
+    if (!routed && ctx->owner_world == 1 && needs_table && mass > n / 64u && !windows_search_off()) {
       uint32_t best = sampled, best_mass = mass;
       for (uint32_t w = sampled + 32u; 2u * w + kMinAnchoredLen <= shortest && w <= 96u; w += 32u) {
         ctx->anchor_a = ctx->anchor_b = w;
@@ -1840,7 +1806,7 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
     ctx->windows_chosen = ctx->anchor_a;                     // (what the safety net settled on, for the next build)
     ctx->windows_w = ctx->anchor_w;
     owned_ok = !needs_table;
-    if (!owned_ok && ctx->only_oversized && member_index_enabled()) {
+    if (!owned_ok && ctx->only_oversized) {
       // nothing but groups too large for the pair kernels stands in the way: a table of their members is all the plain kernel needs
       SWA_TRY(build_member_index(ctx, ctx->owner_world > 1 ? 0u : first, ctx->owner_world > 1 ? n : count));
       owned_ok = true;
@@ -1901,7 +1867,7 @@ static size_t network_lds_bytes(const swa_ctx * ctx, bool zlds) {
 }
 
 // launches the network kernel for [first, first+count); leaves the links in the per-wave segments
-static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count, bool stats) {
+static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count) {
   NetArgs a{};
   a.seqs = ctx->db.seqs; a.seq_off = ctx->db.seq_off; a.seqlen = ctx->db.seqlen; a.abundance = ctx->db.abundance;
   a.zobrist = static_cast<const uint64_t *>(ctx->d_zobrist.ptr);
@@ -1917,7 +1883,6 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
   a.edges = static_cast<uint64_t *>(ctx->d_edges.ptr);
   a.seg_cap = ctx->seg_cap;
   a.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
-  a.stats = static_cast<unsigned long long *>(ctx->d_stats.ptr);
   a.owner_rank = ctx->owner_rank; a.owner_world = ctx->owner_world;
   a.anchor_w = 32;
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 16 * sizeof(uint64_t), ctx->stream));
@@ -1925,15 +1890,8 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
   const size_t lds = network_lds_bytes(ctx, zlds);
   const int grid = grid_for(ctx, count, kWaves, 8);
   swa_t0(ctx, 3);
-  if (zlds && stats) {
-    hipLaunchKernelGGL((k_d1_probe<true, true, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a);
-  } else if (zlds) {
-    hipLaunchKernelGGL((k_d1_probe<true, false, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a);
-  } else if (stats) {
-    hipLaunchKernelGGL((k_d1_probe<false, true, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a);
-  } else {
-    hipLaunchKernelGGL((k_d1_probe<false, false, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a);
-  }
+  if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a); }
+  else { hipLaunchKernelGGL((k_d1_probe<false, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a); }
   swa_t1(ctx, 3);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
@@ -1996,8 +1954,6 @@ static int csr_check(swa_ctx * ctx, uint64_t csr_end, uint32_t links_sorted, uin
 static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, uint32_t count, uint64_t * d_offsets,
                        uint32_t * d_neighbours, uint64_t * d_edge_list, uint64_t cap, uint64_t * total) {
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  const char * env_stats = getenv("SWA_D1_STATS");
-  const bool stats = env_stats != nullptr && env_stats[0] == '1';
   // hits leave the kernels through per-wave segments of the edge buffer (no shared counter)
   const uint32_t nseg = (uint32_t)ctx->num_cus * 8u * kWaves;          // >= waves of any launch below
   SWA_TRY(swa_reserve(ctx, ctx->d_seg_fill, 3ull * nseg * sizeof(uint32_t)));   // fills | members staged, pass 0 | pass 1
@@ -2015,8 +1971,8 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
   for (int attempt = 0; attempt < 8 && !clean; ++attempt) {
     SWA_TRY(swa_reserve(ctx, ctx->d_edges, uint64_t(nseg) * ctx->seg_cap * sizeof(uint64_t)));
     // (the segment fills start at zero: the anchored route clears them with its other counters — one launch —, the plain one here)
-    if (!(ctx->anchor_usable && !stats)) { SWA_HIP(ctx, hipMemsetAsync(ctx->d_seg_fill.ptr, 0, 3ull * nseg * sizeof(uint32_t), ctx->stream)); }
-    if (ctx->anchor_usable && !stats) {
+    if (!ctx->anchor_usable) { SWA_HIP(ctx, hipMemsetAsync(ctx->d_seg_fill.ptr, 0, 3ull * nseg * sizeof(uint32_t), ctx->stream)); }
+    if (ctx->anchor_usable) {
       if (!(ctx->anchor_ready && ctx->stream_index)) {
         // (the streaming index serves any query range; it is rebuilt when the owner changed)
         swa_t0(ctx, 7);
@@ -2041,11 +1997,11 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     }
     else {
       SWA_TRY(ensure_full_index(ctx));
-      SWA_TRY(launch_network(ctx, no_cluster_breaking, first, count, stats));
+      SWA_TRY(launch_network(ctx, no_cluster_breaking, first, count));
     }
     hipLaunchKernelGGL(k_seg_reduce, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
                        nseg, static_cast<unsigned long long *>(ctx->d_stats.ptr) + 8);
-    const bool check_unserved = ctx->anchor_usable && !stats && !ctx->full_index && !ctx->member_index;
+    const bool check_unserved = ctx->anchor_usable && !ctx->full_index && !ctx->member_index;
     // CSR assembly is enqueued right behind, before the host looks at the totals: every kernel
     // below guards its writes with `cap` / the segment capacity, so a run that turns out to
     // need bigger segments or a bigger neighbour buffer has only wasted these launches.
@@ -2081,9 +2037,9 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     const uint32_t anchor_overflow = reinterpret_cast<const uint32_t *>(status)[2];
     const uint64_t csr_end = status[48];
     const uint32_t links_sorted = (uint32_t)status[49];
-    const bool guarded = ctx->anchor_usable && !stats;
+    const bool guarded = ctx->anchor_usable;
     n_edges = got[0];
-    if (ctx->anchor_usable && !stats && anchor_overflow != 0) {
+    if (guarded && anchor_overflow != 0) {
       // a bucket of the index rebuilt above held more distinct keys than the group kernel's table: partition finer, again
       ctx->stream_extra_bits = std::min<uint32_t>(ctx->stream_extra_bits + 2, 8);
       ctx->anchor_ready = false;
@@ -2351,7 +2307,6 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
     case 0: src = ctx->d_seqhash.ptr; bytes = uint64_t(ctx->db.n) * sizeof(uint64_t); break;
     case 1: src = ctx->d_bloom.ptr; bytes = ctx->bloom_words * sizeof(uint64_t); break;
     case 2: src = ctx->d_zobrist.ptr; bytes = 4ull * ctx->zobrist_len * sizeof(uint64_t); break;
-    case 3: src = ctx->d_stats.ptr; bytes = 8 * sizeof(uint64_t); break;
     default: return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: unknown selector");
   }
   if (out_bytes < bytes) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_debug_read: buffer too small"); }
@@ -2441,7 +2396,6 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   a.bloom = static_cast<const uint64_t *>(ctx->d_bloom.ptr);
   a.bmask = ctx->bloom_words - 1;
   a.patterns = static_cast<const uint64_t *>(ctx->d_patterns.ptr);
-  a.stats = static_cast<unsigned long long *>(ctx->d_stats.ptr);
   a.tasks = f.tasks;
   a.graft = static_cast<uint32_t *>(ctx->d_graft.ptr);
   a.cand_counter = fc + 2;
@@ -2475,8 +2429,8 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
     if (got[0] > 0) {
       a.count = static_cast<uint32_t>(got[0]);
       const int pgrid = grid_for(ctx, a.count, kWaves, 8);
-      if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, false, 1>), dim3(pgrid), dim3(kThreads), probe_lds, ctx->stream, a); }
-      else { hipLaunchKernelGGL((k_d1_probe<false, false, 1>), dim3(pgrid), dim3(kThreads), probe_lds, ctx->stream, a); }
+      if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 1>), dim3(pgrid), dim3(kThreads), probe_lds, ctx->stream, a); }
+      else { hipLaunchKernelGGL((k_d1_probe<false, 1>), dim3(pgrid), dim3(kThreads), probe_lds, ctx->stream, a); }
       SWA_HIP(ctx, hipGetLastError());
     }
     done += want;
@@ -2602,8 +2556,7 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     c.zlen = ctx->zobrist_len; c.maxwords = (ctx->db.longest + 31u) >> 5; c.slots = slots;
     c.pairs = static_cast<const unsigned long long *>(ctx->d_fpairs.ptr); c.npairs = npairs;
     c.graft = static_cast<uint32_t *>(ctx->d_graft.ptr); c.cand_counter = fc + 2;
-    const char * env_sets = getenv("SWA_FAST_COUNT_SETS");     // test switch: the LDS-set kernel whatever the length
-    const bool by_sites = ctx->db.longest <= 255u && !(env_sets != nullptr && env_sets[0] == '1');
+    const bool by_sites = ctx->db.longest <= 255u;
     if (by_sites) {
       uint64_t blocks = (npairs + kWaves - 1) / kWaves;
       const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;

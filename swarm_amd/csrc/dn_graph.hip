@@ -708,9 +708,8 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
                                              ctx->stream));
         hipLaunchKernelGGL(k_dg_scatter, gn, b, 0, ctx->stream, g, tot, goff, cur_t, cur_q, members);
         SWA_HIP(ctx, hipMemsetAsync(dflags + 8, 0, sizeof(uint32_t), ctx->stream));
-        // blocks of 64 targets x 256 queries for the LDS kernel (d = 2, 3; SWA_DN_PAIRS=plain: the per-pair kernel, as for other d)
-        static const bool plain_pairs = [] { const char * e = getenv("SWA_DN_PAIRS"); return e != nullptr && e[0] == 'p'; }();
-        const bool blocked = !plain_pairs && (d == 2u || d == 3u);
+        // blocks of 64 targets x 256 queries for the LDS kernel (d = 2, 3; the per-pair kernel for other d)
+        const bool blocked = d == 2u || d == 3u;
         if (blocked) { hipLaunchKernelGGL(k_dg_items<true>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap); }
         else { hipLaunchKernelGGL(k_dg_items<false>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap); }
         PairArgs p{};
@@ -753,16 +752,15 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
       const uint64_t nwork = npairs + extra;
       ctx->dn_aligned = nwork;
-      // the wavefront kernel's work in the order of its expected length (k_dg_work_keys; SWA_DN_ALIGN_ORDER=0: as found)
-      static const bool ordered = [] { const char * e = getenv("SWA_DN_ALIGN_ORDER"); return !(e != nullptr && e[0] == '0'); }();
-      static const uint32_t align_len_weight = [] { const char * e = getenv("SWA_DN_ALIGN_LEN_WEIGHT"); return e != nullptr ? (uint32_t)atoi(e) : 10u; }();   // (a nucleotide of length difference counts as ten signature bits: alignments + CSR 6.9-7.1 -> 6.5-6.6 ms against 0; 5 and 20: 7.0 / 6.8)
-      if (ordered && nwork > 1 && ctx->d_qgrams.ptr != nullptr) {
+      // the wavefront kernel's work in the order of its expected length (k_dg_work_keys)
+      constexpr uint32_t kAlignLenWeight = 10;   // (a nucleotide of length difference counts as ten signature bits: alignments + CSR 6.9-7.1 -> 6.5-6.6 ms against 0; 5 and 20: 7.0 / 6.8)
+      if (nwork > 1 && ctx->d_qgrams.ptr != nullptr) {
         SWA_TRY(swa_reserve(ctx, ctx->d_dn_keys, 2 * nwork * sizeof(uint64_t)));          // packed items: in | out (the edges' keys later)
         SWA_TRY(swa_reserve(ctx, ctx->d_dn_vals, 2 * nwork * sizeof(uint32_t)));          // keys: in | out (bytes; the edges' values later)
         auto * packed = static_cast<unsigned long long *>(ctx->d_dn_keys.ptr);
         auto * wkey = static_cast<unsigned char *>(ctx->d_dn_vals.ptr);
         hipLaunchKernelGGL(k_dg_work_keys, dim3(grid_for(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, nwork,
-                           static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr), ctx->db.seqlen, align_len_weight, wkey, packed);
+                           static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr), ctx->db.seqlen, kAlignLenWeight, wkey, packed);
         size_t order_bytes = 0;
         (void)rocprim::radix_sort_pairs(nullptr, order_bytes, wkey, wkey + nwork, packed, packed + nwork, nwork, 0, 6, ctx->stream);
         SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, order_bytes + 16));

@@ -338,11 +338,6 @@ extern "C" int swa_d1_result_prepare(swa_ctx * ctx, const swa_hostdb * db, swa_d
   r->order.resize(db->n);
   r->begin_tmp.resize((size_t)db->n + 1);
   // (pinning faults the pages in and maps them for the device; when it is refused the downloads are staged copies as before)
-  const char * how = std::getenv("SWARM_AMD_PIN_RESULTS");     // (experiments: "touch" = pages faulted in, not pinned)
-  if (how != nullptr && std::strcmp(how, "touch") == 0) {
-    std::memset(r->order.data(), 0, (size_t)db->n * sizeof(uint32_t));
-    return SWA_OK;
-  }
   r->pinned_order = swa_host_pin(ctx, r->order.data(), (size_t)db->n * sizeof(uint32_t)) == SWA_OK;
   // (the swarms' bounds are a few hundred kilobytes of an array sized for the worst case: not pinned, not touched — 40 MB of
   // pages this process would otherwise fault in and take apart again)
@@ -661,8 +656,7 @@ extern "C" uint32_t swa_d1_graft(swa_d1_result * r, const uint32_t * graft_cand)
   }
   __gnu_parallel::sort(pairs.begin(), pairs.end());
   const size_t npairs = pairs.size();
-  static const bool serial_env = std::getenv("SWARM_AMD_SERIAL_GRAFT") != nullptr;
-  if (npairs >= 50000 && blocks >= 3 && !serial_env) { return graft_sorted_pairs_in_parallel(r, pairs.data(), npairs, blocks); }
+  if (npairs >= 50000 && blocks >= 3) { return graft_sorted_pairs_in_parallel(r, pairs.data(), npairs, blocks); }
   uint32_t grafts = 0;
   // (a chain of dependent random reads — swarm of the child, swarm of the parent, both swarms' records — the ids of the
   // pairs 16 ahead and the records of the pairs 8 ahead are asked for early)

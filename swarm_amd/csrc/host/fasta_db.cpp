@@ -468,8 +468,7 @@ struct PhaseTimer {                       // SWARM_AMD_DB_TIMING=1 prints the ph
 template <class Rec, class Less>
 void parallel_sample_sort(Rec * a, Rec * tmp, uint16_t * where, uint64_t n, unsigned threads, Less less, PhaseTimer * timer = nullptr) {
   if (threads <= 1 || n < 100000) { std::sort(a, a + n, less); return; }
-  static const unsigned env_buckets = [] { const char * e = std::getenv("SWARM_AMD_SORT_BUCKETS"); return e != nullptr ? (unsigned)std::atoi(e) : 0u; }();
-  const unsigned buckets = env_buckets >= 2u ? std::min(env_buckets, 4096u) : std::min<unsigned>(threads * 8u, 1024u);
+  const unsigned buckets = std::min<unsigned>(threads * 8u, 1024u);
   constexpr uint64_t kOver = 64;                            // sampled records per bucket
   const uint64_t nsample = (uint64_t)buckets * kOver;
   std::vector<Rec> sample(nsample);
@@ -574,9 +573,7 @@ void lsd_sort_by_k(SortRec * r, SortRec * s, size_t n) {
 // prefetch a record's entry and, once that is there, its identifier; .key(rec) = identifier bytes [8, 16) big endian.
 template <class Less, class Deeper>
 bool parallel_radix_sort(SortRec * a, SortRec * tmp, uint16_t * where, uint64_t n, unsigned threads, Less full_less, Deeper deeper, PhaseTimer * timer) {
-  static const unsigned env_buckets = [] { const char * e = std::getenv("SWARM_AMD_SORT_BUCKETS"); return e != nullptr ? (unsigned)std::atoi(e) : 0u; }();
-  const unsigned buckets = env_buckets >= 2u ? std::min(env_buckets, 16384u)
-                                             : (unsigned)std::min<uint64_t>(std::max<uint64_t>(n / 8192u, (uint64_t)threads * 8u), 2048u);
+  const unsigned buckets = (unsigned)std::min<uint64_t>(std::max<uint64_t>(n / 8192u, (uint64_t)threads * 8u), 2048u);
   // (at most 2048: every thread files into all buckets at once — write streams — and searches log2(buckets) splitters a
   // record.  10^8 amplicons, build container: 12 207 buckets found / filed / sorted in 0.39 / 0.22 / 1.08 s, 2048 in
   // 0.30 / 0.16-0.26 / 1.14 s — no difference worth more streams)
@@ -1040,16 +1037,14 @@ extern "C" int swa_hostdb_read_fasta_staged(const char * path, int usearch, int6
     // bucket sorts took 17-20 ms on 32 and 56-93 ms on 64 threads beside the checks' 32 (lease r5b).
     SortRec * const other = recs + n;
     uint16_t * const where = reinterpret_cast<uint16_t *>(other + n);
-    const char * env_sort = std::getenv("SWARM_AMD_SORT_THREADS");
-    const unsigned sort_threads = std::max(1u, std::min(threads, env_sort != nullptr ? (unsigned)std::atoi(env_sort) : 32u));
+    const unsigned sort_threads = std::max(1u, std::min(threads, 32u));
     // The records' integer key (abundance, first 8 identifier bytes) sorts by radix — a third of the comparison sort's CPU
     // time at 10 M amplicons —; identifiers that mostly share their first 8 bytes and small inputs take the comparison sort.
     // Both leave the one db order (identifiers are unique: a strict total order).  Records whose abundance saturates the
     // key's 32 bits — a heavy-tailed set of 10^8 amplicons has a few — come before all others whatever their identifiers: they
     // are moved to the front and sorted among themselves through their entries; the radix sort gets the rest.
-    static const bool no_radix = std::getenv("SWARM_AMD_NO_RADIX_SORT") != nullptr;
     uint64_t nsat = 0;
-    if (!no_radix && saturated.load()) {
+    if (saturated.load()) {
       std::vector<std::vector<uint64_t>> found(threads);
       run_parallel(threads, [&](unsigned t) {
         for (uint64_t i = n64 * t / threads; i < n64 * (t + 1) / threads; ++i) { if (recs[i].abundance == 0xFFFFFFFFu) { found[t].push_back(i); } }
@@ -1071,7 +1066,7 @@ extern "C" int swa_hostdb_read_fasta_staged(const char * path, int usearch, int6
       for (const uint64_t p : at) { if (p >= nsat) { std::swap(recs[holes[h]], recs[p]); ++h; } }
       std::sort(recs, recs + nsat, less);
     }
-    const bool by_radix = !no_radix && sort_threads > 1 && n64 - nsat >= 100000 &&
+    const bool by_radix = sort_threads > 1 && n64 - nsat >= 100000 &&
                           parallel_radix_sort(recs + nsat, other + nsat, where + nsat, n64 - nsat, sort_threads, less, Deeper{entry_at, hdr_of}, &timer);
     if (!by_radix) { parallel_sample_sort(recs, other, where, n64, sort_threads, less, &timer); }
   }

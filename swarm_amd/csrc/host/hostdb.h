@@ -24,8 +24,8 @@
 // populated up front by a few threads (MADV_POPULATE_WRITE) when many workers will fill them: 64
 // threads first-touching 4 KiB pages of one fresh mapping contend in the kernel (the reader's
 // gather phase took 270 ms at 10 M amplicons that way, 177 ms populated; transparent huge pages
-// do as well but may stall in compaction).  SWARM_AMD_HOST_ALLOC: 0 plain, 1 transparent huge
-// pages, n >= 2 populate with n threads (default: 0 up to 32 usable CPUs, else 8).
+// do as well but may stall in compaction).  Up to 32 usable CPUs: plain first touch; more: populated
+// by 8 threads.
 template <class T>
 struct swa_default_init_allocator {
   using value_type = T;
@@ -40,10 +40,9 @@ struct swa_default_init_allocator {
       // (default: plain first touch by the workers that fill the block when there are few of them — 16 under the bench
       // box's CPU quota: the reader finishes 30 ms earlier than with the blocks populated up front, lease r5r —, populated by
       // 8 threads when there are many: 64 workers first-touching one fresh mapping contend in the kernel, round 4)
-      static const int mode = [] { const char * e = std::getenv("SWARM_AMD_HOST_ALLOC"); return e == nullptr ? (swa_host_cpus() > 32u ? 8 : 0) : std::atoi(e); }();
+      static const int mode = swa_host_cpus() > 32u ? 8 : 0;
       p = std::aligned_alloc(kHugePage, (bytes + kHugePage - 1) & ~(kHugePage - 1));
-      if (p != nullptr && mode == 1) { (void)::madvise(p, bytes, MADV_HUGEPAGE); }
-      if (p != nullptr && mode >= 2) {                         // populate with `mode` threads
+      if (p != nullptr && mode != 0) {                         // populate with `mode` threads
         std::vector<std::thread> pool;
         const size_t pages = (bytes + 4095) / 4096;
         for (int t = 0; t < mode; ++t) {

@@ -301,15 +301,11 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     early = std::thread([&early_ctx, &early_rc, &words_ready, device, warm_for]() {
       early_rc = swa_ctx_create(device, nullptr, &early_ctx);
       stamp("(helper thread) context created");
-      // (the first download's set-up beside the code objects and the staging copy: SWARM_AMD_WARM_DOWNLOADS=0 leaves it to the
-      // first result's download)
+      // (the first download's set-up beside the code objects and the staging copy)
       std::thread downloads;
-      {
-        const char * wd = std::getenv("SWARM_AMD_WARM_DOWNLOADS");
-        if (early_rc == SWA_OK && (wd == nullptr || wd[0] != '0')) {
-          swa_ctx * c = early_ctx;
-          downloads = std::thread([c]() { (void)swa_ctx_warmup_downloads(c); stamp("(second helper thread) download path warm"); });
-        }
+      if (early_rc == SWA_OK) {
+        swa_ctx * c = early_ctx;
+        downloads = std::thread([c]() { (void)swa_ctx_warmup_downloads(c); stamp("(second helper thread) download path warm"); });
       }
       struct Join { std::thread & t; ~Join() { if (t.joinable()) { t.join(); } } } join_downloads{downloads};
       // (the anomaly hunt, tools/stress/cold_runs.sh: no warm-up = every code object loaded by the step's own first launch;
@@ -426,16 +422,11 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       phase(o, "Building network: ");
     } else if (n > 0) {
       // beside the index and the network (12 ms at 10 M): the result's arrays sized and pinned, so that the member order comes
-      // home as one DMA (SWARM_AMD_PIN_RESULTS=0: the staged copy of round 5)
-      {
-        const char * pin = std::getenv("SWARM_AMD_PIN_RESULTS");
-        if (pin == nullptr || pin[0] != '0') {
-          preparing = std::thread([&prepared, &prepare_rc, ctx, db]() {
-            prepare_rc = swa_d1_result_prepare(ctx, db, &prepared);
-            stamp("(helper thread) result arrays pinned");
-          });
-        }
-      }
+      // home as one DMA
+      preparing = std::thread([&prepared, &prepare_rc, ctx, db]() {
+        prepare_rc = swa_d1_result_prepare(ctx, db, &prepared);
+        stamp("(helper thread) result arrays pinned");
+      });
       int dup = 0;
       rc = swa_d1_index_build(ctx, &dup);
       if (rc != SWA_OK && preparing.joinable()) { preparing.join(); }     // (no exit under a thread that is talking to the runtime)

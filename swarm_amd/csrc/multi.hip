@@ -30,7 +30,8 @@ struct swa_multi {
   std::vector<swa_ctx *> ctx;
   std::vector<int> devices;
   std::vector<ncclComm_t> comms;       // empty: in-process copies (several ranks on one device)
-  std::vector<swa_dbuf> links, gathered;
+  std::vector<swa_dbuf> links;
+  swa_dbuf gathered;                   // on rank 0: what the ranks send there (their link lists, graft candidates, graph shares)
   std::vector<swa_dbuf> routed, routed_counts, inbox;   // routed index build: a rank's outgoing id lists, their counts, what it received
   std::vector<uint64_t> link_cap;
   std::string err;
@@ -105,44 +106,6 @@ int fail(swa_multi * m, int code, const std::string & msg) { m->err = msg; retur
     if (r_ != ncclSuccess) { return fail((m), SWA_E_DEVICE, std::string(#expr) + ": " + swa_rccl().GetErrorString(r_)); } \
   } while (0)
 
-// every rank's buffer src[r] (count[r] elements of `bytes_per` bytes) into dst[k] + prefix(r) on every rank k
-int all_gather_v(swa_multi * m, const std::vector<const void *> & src, const std::vector<void *> & dst,
-                 const std::vector<uint64_t> & count, size_t bytes_per) {
-  const int world = (int)m->ctx.size();
-  std::vector<uint64_t> at((size_t)world + 1, 0);
-  for (int r = 0; r < world; ++r) { at[(size_t)r + 1] = at[(size_t)r] + count[(size_t)r]; }
-  if (!m->comms.empty()) {
-    NCCL_OK(m, swa_rccl().GroupStart());
-    for (int k = 0; k < world; ++k) {
-      for (int r = 0; r < world; ++r) {
-        if (count[(size_t)r] == 0) { continue; }
-        char * recv = static_cast<char *>(dst[(size_t)k]) + at[(size_t)r] * bytes_per;
-        // (the send buffer only matters on the root)
-        NCCL_OK(m, swa_rccl().Broadcast(k == r ? src[(size_t)r] : recv, recv, count[(size_t)r] * bytes_per, ncclUint8, r, m->comms[(size_t)k],
-                                 m->ctx[(size_t)k]->stream));
-      }
-    }
-    NCCL_OK(m, swa_rccl().GroupEnd());
-  } else {
-    for (int k = 0; k < world; ++k) {
-      if (hipSetDevice(m->devices[(size_t)k]) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
-      for (int r = 0; r < world; ++r) {
-        if (count[(size_t)r] == 0) { continue; }
-        char * recv = static_cast<char *>(dst[(size_t)k]) + at[(size_t)r] * bytes_per;
-        if (hipMemcpyAsync(recv, src[(size_t)r], count[(size_t)r] * bytes_per, hipMemcpyDefault, m->ctx[(size_t)k]->stream) != hipSuccess) {
-          return fail(m, SWA_E_DEVICE, "device-to-device copy of a link list failed");
-        }
-      }
-    }
-  }
-  for (int k = 0; k < world; ++k) {
-    if (hipSetDevice(m->devices[(size_t)k]) != hipSuccess || hipStreamSynchronize(m->ctx[(size_t)k]->stream) != hipSuccess) {
-      return fail(m, SWA_E_DEVICE, "synchronising the exchange failed");
-    }
-  }
-  return SWA_OK;
-}
-
 // every rank's buffer src[r] (count[r] elements of `bytes_per` bytes) into dst + prefix(r) on rank 0 ONLY: the consumer
 // of the gathered lists is the rank that builds the CSR, so nothing is sent to the others (an all-gather moved the
 // whole network into every GPU: 0.9 GB per rank at 8 x 10 M amplicons).  RCCL: one ncclSend per rank, the matching
@@ -184,7 +147,6 @@ extern "C" int swa_multi_create(const int * devices, int ndevices, swa_multi ** 
   m->devices.assign(devices, devices + ndevices);
   // (per-rank buffers first: swa_multi_destroy walks them for every context that exists, also after a failure below)
   m->links.resize((size_t)ndevices);
-  m->gathered.resize((size_t)ndevices);
   m->routed.resize((size_t)ndevices);
   m->routed_counts.resize((size_t)ndevices);
   m->inbox.resize((size_t)ndevices);
@@ -211,7 +173,7 @@ extern "C" void swa_multi_destroy(swa_multi * m) {
   for (size_t r = 0; r < m->ctx.size(); ++r) {
     (void)hipSetDevice(m->devices[r]);
     swa_release(m->links[r]);
-    swa_release(m->gathered[r]);
+    if (r == 0) { swa_release(m->gathered); }
     swa_release(m->routed[r]);
     swa_release(m->routed_counts[r]);
     swa_release(m->inbox[r]);
@@ -355,31 +317,18 @@ extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint
   {
     swa_ctx * c = m->ctx[0];
     if (hipSetDevice(c->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
-    rc = swa_reserve(c, m->gathered[0], (all + 2) * sizeof(uint64_t));
+    rc = swa_reserve(c, m->gathered, (all + 2) * sizeof(uint64_t));
     if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c)); }
   }
-  // (SWARM_AMD_MULTI_EXCHANGE=allgather: the literal all-gather of SURVEY 8e — every GPU ends with every list)
-  const char * env_x = getenv("SWARM_AMD_MULTI_EXCHANGE");
-  if (all != 0 && env_x != nullptr && env_x[0] == 'a') {
-    std::vector<void *> dst((size_t)world);
-    for (int r = 0; r < world; ++r) {
-      swa_ctx * c = m->ctx[(size_t)r];
-      if (hipSetDevice(c->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
-      rc = swa_reserve(c, m->gathered[(size_t)r], (all + 2) * sizeof(uint64_t));
-      if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c)); }
-      dst[(size_t)r] = m->gathered[(size_t)r].ptr;
-    }
-    rc = all_gather_v(m, src, dst, count, sizeof(uint64_t));
-    if (rc != SWA_OK) { return rc; }
-  } else if (all != 0) {
-    rc = gather_to_root_v(m, src, m->gathered[0].ptr, count, sizeof(uint64_t));
+  if (all != 0) {
+    rc = gather_to_root_v(m, src, m->gathered.ptr, count, sizeof(uint64_t));
     if (rc != SWA_OK) { return rc; }
   }
   // 3. rank 0: the gathered lists -> CSR -> host.  The partition + row kernels of the single-GPU step (d1.hip: csr_from_chunks,
   // the ranks' lists as the chunks of its first level) where round 3 ran a 64-bit radix sort over all links.
   swa_ctx * c0 = m->ctx[0];
   if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
-  auto * keys_in = static_cast<unsigned long long *>(m->gathered[0].ptr);
+  auto * keys_in = static_cast<unsigned long long *>(m->gathered.ptr);
   auto stage = [&]() -> int {
     c0->csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold the gathered network)
     SWA_TRY(swa_reserve(c0, c0->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
@@ -432,14 +381,14 @@ extern "C" int swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, 
   } else {
     swa_ctx * c0 = m->ctx[0];
     if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
-    rc = swa_reserve(c0, m->gathered[0], (uint64_t)n * sizeof(uint32_t));
+    rc = swa_reserve(c0, m->gathered, (uint64_t)n * sizeof(uint32_t));
     if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
     for (int r = 1; r < world; ++r) {
-      if (hipMemcpyAsync(m->gathered[0].ptr, m->ctx[(size_t)r]->d_graft.ptr, (uint64_t)n * sizeof(uint32_t), hipMemcpyDefault, c0->stream) != hipSuccess) {
+      if (hipMemcpyAsync(m->gathered.ptr, m->ctx[(size_t)r]->d_graft.ptr, (uint64_t)n * sizeof(uint32_t), hipMemcpyDefault, c0->stream) != hipSuccess) {
         return fail(m, SWA_E_DEVICE, "device-to-device copy of graft candidates failed");
       }
       hipLaunchKernelGGL(k_min_u32, dim3(blocks_for(c0, n)), dim3(256), 0, c0->stream, static_cast<uint32_t *>(c0->d_graft.ptr),
-                         static_cast<const uint32_t *>(m->gathered[0].ptr), (uint64_t)n);
+                         static_cast<const uint32_t *>(m->gathered.ptr), (uint64_t)n);
     }
   }
   swa_ctx * c0 = m->ctx[0];
@@ -494,10 +443,10 @@ extern "C" int swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64
   at[(size_t)world] = all;
   if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
   // rank 0's buffers: [all keys | sorted keys] and [all diffs | sorted diffs]
-  rc = swa_reserve(c0, m->gathered[0], (2 * all + 2) * sizeof(uint64_t));
+  rc = swa_reserve(c0, m->gathered, (2 * all + 2) * sizeof(uint64_t));
   if (rc == SWA_OK) { rc = swa_reserve(c0, m->links[0], (2 * all + 2) * sizeof(uint32_t)); }
   if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
-  auto * keys = static_cast<unsigned long long *>(m->gathered[0].ptr);
+  auto * keys = static_cast<unsigned long long *>(m->gathered.ptr);
   auto * vals = static_cast<uint32_t *>(m->links[0].ptr);
   if (!m->comms.empty()) { NCCL_OK(m, swa_rccl().GroupStart()); }
   for (int r = 0; r < world; ++r) {

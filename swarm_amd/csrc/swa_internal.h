@@ -62,7 +62,7 @@ struct swa_ctx {
   swa_dbuf d_status;
   void * h_status = nullptr;     // 4 KB of pinned host memory: where the d = 1 step looks at the status block
   swa_dbuf d_flags;              // u32[16]: [0] duplicate flag
-  swa_dbuf d_stats;              // u64[8] probe statistics + [8] edge counter
+  swa_dbuf d_stats;              // u64[16]: [8] links found [9] fullest segment [10, 12) members staged by pass
   swa_dbuf d_edges;              // u64 edge list (src << 32 | dst)
   swa_dbuf d_counts, d_cursor, d_scan_tmp, d_offsets_tmp, d_nb_tmp;
   // anchored d=1 index (d1_anchor.inc, d1_stream.inc): [0] prefix groups, [1] suffix groups

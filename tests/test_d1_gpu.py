@@ -652,10 +652,10 @@ def test_v4_like_reads_with_conserved_stretches(tmp_path, n, seed):
         ctx.close()
 
 
-def test_tiled_pair_kernel_on_big_groups(tmp_path, monkeypatch):
-    """k_d1_pairs_tiled (64 x 64 tiles) in place of the enumerating kernel for groups of 65..2048, default anchors."""
+def test_tiled_pair_kernel_on_big_groups(tmp_path):
+    """k_d1_pairs_tiled (64 x 64 tiles), default anchors: groups of more than kPairBigCap (256) members go to it by
+    default, and this test's two ~1200-member groups are such groups."""
     from swarm_amd import Context
-    monkeypatch.setenv("SWA_D1_PAIRS_TILED", "1")
     rng = np.random.default_rng(5)
     cent = "".join(rng.choice(list("ACGT"), 150))
     seqs = {cent}

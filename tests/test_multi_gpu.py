@@ -33,11 +33,12 @@ def light_set(tmp_path_factory):
     return fa, hdb, off, nb, flags, stats, graft, counters
 
 
-@pytest.mark.parametrize("devices,rccl,build", [([0, 0], False, "routed"), ([0, 0, 0], False, "routed"), ([0, 0, 0], False, "streamed"),
-                                                ([0], True, "routed")])
+@pytest.mark.parametrize("devices,rccl,build", [([0, 0], False, "records"), ([0, 0, 0], False, "records"), ([0, 0, 0], False, "streamed"),
+                                                ([0], True, "records")])
 def test_multi_matches_single(light_set, monkeypatch, devices, rccl, build):
-    """build: how the ranks get the members of their anchor groups — routed: every rank keys its slice and the ids travel
-    to the owners (swa_d1_route_slice / swa_d1_index_build_routed); streamed: every rank walks the whole database."""
+    """build: how the ranks get the members of their anchor groups — records (the default): every rank keys its slice and
+    the finished key records travel to the owners (swa_d1_route_slice_records / swa_d1_index_build_records); streamed:
+    every rank walks the whole database."""
     fa, hdb, off, nb, flags, stats, graft, counters = light_set
     if rccl:
         monkeypatch.setenv("SWARM_AMD_FORCE_RCCL", "1")
@@ -147,7 +148,7 @@ def _fasta_of(db, path):
 
 
 @pytest.mark.parametrize("which", ["flanks", "giant_groups", "length_mix"])
-@pytest.mark.parametrize("build", ["routed", "streamed"])
+@pytest.mark.parametrize("build", ["records", "streamed"])
 def test_multi_on_sets_that_leave_the_friendly_route(tmp_path, monkeypatch, which, build):
     """Separate contexts per rank (MultiContext: per-context state cannot leak between ranks as it can when one context
     plays them in turn) on the sets whose index build takes decisions: conserved flanks (the anchor windows move — the same
