@@ -19,6 +19,8 @@
  *   B3    db_qgrams_init + qgram_diff_fast (src/db.cc:819-842,       swa_qgram_build
  *         src/qgram.h:31-35)                                         swa_qgram_diff
  *   B4    search_begin + search_do (src/scan.h:30-37, 259)           swa_search_begin / swa_search_do
+ *   B5    nw() per H line of the uclust writers (src/algod1.cc:896-  swa_nw_batch
+ *         925, src/algo.cc:620-655, src/nw.cc:237-255)
  *
  * Amplicon numbering everywhere = the reference's db order after db_read():
  * abundance descending, then header ascending (src/db.cc:388-413).  Sequences are
@@ -336,6 +338,21 @@ int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * seeds, const
 int swa_scan_fetch(swa_ctx * ctx, uint32_t * hit_seedidx, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap);
 /* out3 = {q-gram comparisons, aligned pairs, launch sequences} since swa_scan_begin */
 int swa_scan_totals(swa_ctx * ctx, uint64_t * out3);
+
+/* ---- B5: the uclust alignments ------------------------------------------------------------
+   Seam B5 (src/algod1.cc:880-925, src/algo.cc:608-659, src/nw.cc:237-255): npairs global alignments of amplicon
+   d_ids[k] (the reference's dseq, the member) against q_ids[k] (qseq, the seed) of the resident database, with affine
+   gaps under the reduced penalties and the reference's tie-breaking.  diffs[k] / columns[k] = nw()'s nwdiff / alignment
+   length; cigar receives the pairs' CIGAR strings back to back (src/utils/cigar.cc:28-60: counts of 1 omitted, no NUL),
+   cigar_end[k] = end of pair k's.  No CIGAR is longer than dl + ql.  SWA_E_CAPACITY when cigar_cap is too small:
+   *cigar_total = the need (the other results are complete).  Banded tiers on the GPU, each result accepted only with its
+   certificate; what no tier certifies, and pairs too long or with penalties too large for 32-bit costs,
+   are aligned on the host within the call — the results are the same bit for bit either way. */
+int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
+                 const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
+                 uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total);
+/* out4 = pairs of the last swa_nw_batch per tier: 16-, 32-, 64-lane bands (half-width 6, 14, 30), host */
+int swa_nw_batch_totals(const swa_ctx * ctx, uint64_t * out4);
 
 /* ---- B3 + B4 in bulk: the whole d >= 2 search as ONE graph --------------------------------
    Everything qgram_diff_fast + search_do can ever answer during algo_run (src/algo.cc:423-602: per seed

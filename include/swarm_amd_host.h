@@ -92,6 +92,11 @@ int swa_d1_write_network(const swa_hostdb * db, const uint64_t * offsets, const 
 /* -u for d = 1 (src/algod1.cc:849-932); penalties after gcd reduction (18/24/13 by default) */
 int swa_d1_write_uclust(const swa_d1_result * res, const swa_hostdb * db, const char * path, int usearch_abundance,
                         int64_t append_abundance, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend);
+/* the same file with the alignments on the GPU (seam B5, swa_nw_batch on `ctx`, which holds the same database; NULL
+   only for a result without H lines).  SWA_NW_CHUNK=n (a test hook): n pairs per chunk instead of 2^20. */
+int swa_d1_write_uclust_gpu(swa_ctx * ctx, const swa_d1_result * res, const swa_hostdb * db, const char * path,
+                            int usearch_abundance, int64_t append_abundance, uint64_t mismatch, uint64_t gapopen,
+                            uint64_t gapextend);
 
 /* ---- d >= 2 host side: the greedy loop of algo_run over the GPU's fused scan step ------- */
 typedef struct swa_dn_result swa_dn_result;
@@ -117,6 +122,16 @@ int swa_dn_write_structure(const swa_dn_result * res, const swa_hostdb * db, con
 int swa_dn_write_seeds(const swa_dn_result * res, const swa_hostdb * db, const char * path, int usearch_abundance);
 int swa_dn_write_uclust(const swa_dn_result * res, const swa_hostdb * db, const char * path, int usearch_abundance,
                         int64_t append_abundance);
+/* the same file with the alignments on the GPU (as swa_d1_write_uclust_gpu) */
+int swa_dn_write_uclust_gpu(swa_ctx * ctx, const swa_dn_result * res, const swa_hostdb * db, const char * path,
+                            int usearch_abundance, int64_t append_abundance);
+
+/* ---- the uclust aligner on the host (src/nw.cc:237-255): what both -u writers print, and what swa_nw_batch must equal ----
+   dseq / qseq 2-bit packed.  Returns the differences (columns - matches); *columns = alignment length; the CIGAR into
+   cigar[cigar_cap] (NUL terminated, cut short if it does not fit), *cigar_len = its full length. */
+uint64_t swa_nw_align_host(const uint64_t * dseq, uint32_t dlen, const uint64_t * qseq, uint32_t qlen, uint64_t mismatch,
+                           uint64_t gapopen, uint64_t gapextend, uint64_t * columns, char * cigar, uint64_t cigar_cap,
+                           uint64_t * cigar_len);
 
 /* ---- d = 0: dereplication (src/derep.cc) ------------------------------------------------
    Clusters of identical sequences from swa_derep's array: members in db order, the first one

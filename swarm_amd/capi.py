@@ -632,6 +632,41 @@ class Context:
                                            _ptr(alens)))
         return scores, diffs, alens
 
+    def nw_batch(self, d_ids, q_ids, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
+        """Seam B5 (swa_nw_batch): global alignments of amplicons d_ids[k] (member) against q_ids[k] (seed) of the
+        resident database -> (diffs, columns, list of CIGAR strings)."""
+        lib = self.lib
+        _declare_dn(lib)
+        d_ids = np.ascontiguousarray(d_ids, dtype=np.uint32)
+        q_ids = np.ascontiguousarray(q_ids, dtype=np.uint32)
+        m = len(d_ids)
+        assert len(q_ids) == m
+        diffs = np.zeros(m, dtype=np.uint32)
+        cols = np.zeros(m, dtype=np.uint32)
+        ends = np.zeros(m, dtype=np.uint64)
+        total = C.c_uint64(0)
+        cap = 16 * m + 64
+        while True:
+            buf = C.create_string_buffer(max(cap, 1))
+            rc = lib.swa_nw_batch(self.h, mismatch, gapopen, gapextend, m, _ptr(d_ids), _ptr(q_ids), _ptr(diffs),
+                                  _ptr(cols), _ptr(ends), buf, cap, C.byref(total))
+            if rc == SWA_E_CAPACITY and total.value > cap:
+                cap = int(total.value)
+                continue
+            self._check(rc)
+            break
+        raw = buf.raw[:int(total.value)]
+        starts = np.concatenate(([0], ends[:-1])).astype(np.int64) if m else []
+        cigars = [raw[int(a):int(b)].decode() for a, b in zip(starts, ends)]
+        return diffs, cols, cigars
+
+    def nw_batch_totals(self) -> list:
+        """pairs of the last nw_batch per tier: [16-lane, 32-lane, 64-lane band, host]"""
+        _declare_dn(self.lib)
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.swa_nw_batch_totals(self.h, _p64(out)))
+        return [int(v) for v in out]
+
 
 # ---- d >= 2: host greedy loop over the GPU's fused scan step ---------------------------------
 
@@ -642,7 +677,8 @@ _DN_EXPORTS = ["swa_dn_cluster", "swa_dn_result_free", "swa_dn_result_error", "s
                "swa_multi_create", "swa_multi_destroy", "swa_multi_size", "swa_multi_uses_rccl", "swa_multi_ctx", "swa_multi_last_error",
                "swa_multi_db_upload", "swa_multi_d1_network", "swa_multi_d1_fastidious", "swa_dn_set_ownership", "swa_multi_dn_begin",
                "swa_multi_dn_graph_supported", "swa_multi_dn_graph", "swa_multi_dn_graph_totals", "swa_dn_cluster_multi",
-               "swa_timing_read_stream"]
+               "swa_timing_read_stream", "swa_nw_batch", "swa_nw_batch_totals", "swa_d1_write_uclust_gpu", "swa_dn_write_uclust_gpu",
+               "swa_nw_align_host"]
 EXPORTS.extend(_DN_EXPORTS)
 
 
@@ -677,6 +713,15 @@ def _declare_dn(lib) -> None:
     lib.swa_scan_step.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_uint32, u32p]
     lib.swa_scan_totals.argtypes = [C.c_void_p, u64p]
+    lib.swa_dn_write_uclust_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64]
+    lib.swa_d1_write_uclust_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint64,
+                                            C.c_uint64, C.c_uint64]
+    lib.swa_nw_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    lib.swa_nw_batch_totals.argtypes = [C.c_void_p, u64p]
+    lib.swa_nw_align_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                      u64p, C.c_char_p, C.c_uint64, u64p]
+    lib.swa_nw_align_host.restype = C.c_uint64
     lib._dn_declared = True
 
 
@@ -726,7 +771,12 @@ class DnClusters:
     def write_seeds(self, path, usearch=False) -> None:
         assert self.lib.swa_dn_write_seeds(self.h, self.hdb.h, str(path).encode(), int(usearch)) == SWA_OK
 
-    def write_uclust(self, path, usearch=False, append_abundance=0) -> None:
+    def write_uclust(self, path, usearch=False, append_abundance=0, ctx: "Context | None" = None) -> None:
+        """-u; with ctx= the alignments run on that context's GPU (seam B5, swa_dn_write_uclust_gpu)."""
+        if ctx is not None:
+            ctx._check(self.lib.swa_dn_write_uclust_gpu(ctx.h, self.h, self.hdb.h, str(path).encode(), int(usearch),
+                                                        append_abundance))
+            return
         assert self.lib.swa_dn_write_uclust(self.h, self.hdb.h, str(path).encode(), int(usearch),
                                             append_abundance) == SWA_OK
 
@@ -821,12 +871,35 @@ class D0Clusters:
             pass
 
 
-def d1_write_uclust(clusters: "D1Clusters", path, usearch=False, append_abundance=0, penalties=None) -> None:
+def d1_write_uclust(clusters: "D1Clusters", path, usearch=False, append_abundance=0, penalties=None,
+                    ctx: "Context | None" = None) -> None:
+    """-u for d = 1; with ctx= the alignments run on that context's GPU (seam B5, swa_d1_write_uclust_gpu)."""
     lib = load_library()
     _declare_dn(lib)
     mm, go, ge = penalties or reduced_penalties()
+    if ctx is not None:
+        ctx._check(lib.swa_d1_write_uclust_gpu(ctx.h, clusters.h, clusters.hdb.h, str(path).encode(), int(usearch),
+                                               append_abundance, mm, go, ge))
+        return
     assert lib.swa_d1_write_uclust(clusters.h, clusters.hdb.h, str(path).encode(), int(usearch), append_abundance,
                                    mm, go, ge) == SWA_OK
+
+
+def nw_align_host(dseq: np.ndarray, dlen: int, qseq: np.ndarray, qlen: int, mismatch: int = 18, gapopen: int = 24,
+                  gapextend: int = 13):
+    """The host's uclust aligner (swa_nw_align_host): (diffs, columns, CIGAR) of member dseq against seed qseq,
+    both 2-bit packed u64 words."""
+    lib = load_library()
+    _declare_dn(lib)
+    dseq = np.ascontiguousarray(dseq, dtype=np.uint64)
+    qseq = np.ascontiguousarray(qseq, dtype=np.uint64)
+    cols = C.c_uint64(0)
+    clen = C.c_uint64(0)
+    cap = int(dlen) + int(qlen) + 1
+    buf = C.create_string_buffer(cap)
+    diffs = lib.swa_nw_align_host(_ptr(dseq), int(dlen), _ptr(qseq), int(qlen), mismatch, gapopen, gapextend,
+                                  C.byref(cols), buf, cap, C.byref(clen))
+    return int(diffs), int(cols.value), buf.value[:clen.value].decode()
 
 
 # ---- d = 1 on several GPUs from one process (multi.hip) -----------------------------------------

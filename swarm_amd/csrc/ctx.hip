@@ -170,7 +170,8 @@ extern "C" void swa_ctx_destroy(swa_ctx * ctx) {
                        &ctx->d_afallback, &ctx->d_arank, &ctx->d_rank_tmp, &ctx->d_wfa, &ctx->d_seg_fill, &ctx->d_seg_base, &ctx->d_akeys[0], &ctx->d_acounts[0],
                        &ctx->d_aitems[0], &ctx->d_aitems[1],
                        &ctx->d_frole, &ctx->d_fkeys, &ctx->d_fcnt, &ctx->d_foff, &ctx->d_fslot, &ctx->d_fmembers, &ctx->d_fitems,
-                       &ctx->d_fpairs, &ctx->d_dn_keys, &ctx->d_dn_vals, &ctx->d_cluster, &ctx->d_cluster_ctl, &ctx->d_words_stage}) {
+                       &ctx->d_fpairs, &ctx->d_dn_keys, &ctx->d_dn_vals, &ctx->d_cluster, &ctx->d_cluster_ctl, &ctx->d_words_stage,
+                       &ctx->d_nw_ids, &ctx->d_nw_lists, &ctx->d_nw_res, &ctx->d_nw_text, &ctx->d_nw_gather}) {
     swa_release(*b);
   }
   for (auto & b : ctx->d_stream) { swa_release(b); }
@@ -229,6 +230,7 @@ static int check_view(swa_ctx * ctx, const swa_db_view * v) {
 
 static void invalidate(swa_ctx * ctx) {
   ctx->d1_ready = false;
+  ctx->nw_seqlen.clear();
   ctx->full_index = false;
   ctx->anchor_ready = false;
   ctx->rank_ready = false;

@@ -9,6 +9,7 @@
 #include "hostdb.h"
 #include "nw_host.h"
 #include "out.h"
+#include "uclust_gpu.h"
 
 #include <algorithm>
 #include <cinttypes>
@@ -857,30 +858,45 @@ extern "C" int swa_d1_write_uclust(const swa_d1_result * r, const swa_hostdb * d
       const auto & s = r->swarms[k];
       if (s.attached != 0) { continue; }
       const uint32_t cluster_no = number[k];
-      sink.str("C\t"); sink.u64(cluster_no); sink.put('\t'); sink.u64(s.size); sink.str("\t*\t*\t*\t*\t*\t");
-      swa_out::id(sink, db, s.seed, usearch != 0, append_abundance);
-      sink.str("\t*\n");
-      sink.str("S\t"); sink.u64(cluster_no); sink.put('\t'); sink.u64(db->seqlen[s.seed]); sink.str("\t*\t*\t*\t*\t*\t");
-      swa_out::id(sink, db, s.seed, usearch != 0, append_abundance);
-      sink.str("\t*\n");
+      swa_out::uclust_cluster(sink, db, cluster_no, s.size, s.seed, usearch != 0, append_abundance);
       for_each_member(r, s, [&](uint32_t a) {
         if (a == s.seed) { return; }
         const uint64_t nwdiff = swa_nw_align(db->words(a), db->seqlen[a],
                                              db->words(s.seed), db->seqlen[s.seed], mismatch, gapopen,
                                              gapextend, scratch);
-        const double columns = (double)scratch.ops.size();
-        const double percentid = 100.0 * (columns - (double)nwdiff) / columns;
-        sink.str("H\t"); sink.u64(cluster_no); sink.put('\t'); sink.u64(db->seqlen[a]); sink.put('\t'); sink.fixed1(percentid);
-        sink.str("\t+\t0\t0\t");
-        if (nwdiff > 0) { const std::string cigar = swa_cigar(scratch.ops); sink.write(cigar.data(), cigar.size()); }
-        else { sink.put('='); }
-        sink.put('\t');
-        swa_out::id(sink, db, a, usearch != 0, append_abundance);
-        sink.put('\t');
-        swa_out::id(sink, db, s.seed, usearch != 0, append_abundance);
-        sink.put('\n');
+        const std::string cigar = nwdiff > 0 ? swa_cigar(scratch.ops) : std::string();
+        swa_out::uclust_hit(sink, db, cluster_no, a, s.seed, nwdiff, scratch.ops.size(), cigar.data(), cigar.size(), usearch != 0,
+                            append_abundance);
       });
     }
   });
   return SWA_OK;
+}
+
+// -u with the alignments on the GPU (seam B5): the same lines as swa_d1_write_uclust, the pairs aligned by swa_nw_batch
+extern "C" int swa_d1_write_uclust_gpu(swa_ctx * ctx, const swa_d1_result * r, const swa_hostdb * db, const char * path, int usearch,
+                                       int64_t append_abundance, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend) {
+  if (!need_details(r)) { return details_failed(r); }
+  BufOut o(path);
+  if (!o.ok()) { return SWA_E_ARG; }
+  const std::vector<uint32_t> number = output_numbers(r);
+  return swa_uclust_gpu(ctx, db, o, r->swarms.size(), r->n >= kParallelUclustFrom, mismatch, gapopen, gapextend,
+    [&](size_t k, auto && push) {
+      const auto & s = r->swarms[k];
+      if (s.attached != 0) { return; }
+      for_each_member(r, s, [&](uint32_t a) { if (a != s.seed) { push(a, s.seed); } });
+    },
+    [&](size_t k) { return printed_members(r, k); },
+    [&](BufOut & sink, size_t k, const swa_uclust_chunk & c, uint64_t p) {
+      const auto & s = r->swarms[k];
+      if (s.attached != 0) { return; }
+      swa_out::uclust_cluster(sink, db, number[k], s.size, s.seed, usearch != 0, append_abundance);
+      for_each_member(r, s, [&](uint32_t a) {
+        if (a == s.seed) { return; }
+        size_t len = 0;
+        const char * cigar = swa_uclust_cigar(c, p, &len);
+        swa_out::uclust_hit(sink, db, number[k], a, s.seed, c.diffs[p], c.columns[p], cigar, len, usearch != 0, append_abundance);
+        ++p;
+      });
+    });
 }

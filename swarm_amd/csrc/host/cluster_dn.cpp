@@ -10,6 +10,7 @@
 #include "hostdb.h"
 #include "nw_host.h"
 #include "out.h"
+#include "uclust_gpu.h"
 
 #include <algorithm>
 #include <chrono>
@@ -435,30 +436,41 @@ extern "C" int swa_dn_write_uclust(const swa_dn_result * r, const swa_hostdb * d
     for (size_t cluster_no = begin; cluster_no < end; ++cluster_no) {
       const auto & s = r->swarms[cluster_no];
       const uint32_t seed = r->order[s.begin].id;
-      sink.str("C\t"); sink.u64(cluster_no); sink.put('\t'); sink.u64(s.end - s.begin); sink.str("\t*\t*\t*\t*\t*\t");
-      swa_out::id(sink, db, seed, usearch != 0, append_abundance);
-      sink.str("\t*\n");
-      sink.str("S\t"); sink.u64(cluster_no); sink.put('\t'); sink.u64(db->seqlen[seed]); sink.str("\t*\t*\t*\t*\t*\t");
-      swa_out::id(sink, db, seed, usearch != 0, append_abundance);
-      sink.str("\t*\n");
+      swa_out::uclust_cluster(sink, db, cluster_no, s.end - s.begin, seed, usearch != 0, append_abundance);
       for (uint32_t k = s.link_begin; k < s.link_end; ++k) {
         const uint32_t hit = r->links[k].child;
         const uint64_t nwdiff = swa_nw_align(db->words(hit), db->seqlen[hit],
                                              db->words(seed), db->seqlen[seed], r->pen_mismatch,
                                              r->pen_gapopen, r->pen_gapextend, scratch);
-        const double columns = (double)scratch.ops.size();
-        const double percentid = 100.0 * (columns - (double)nwdiff) / columns;
-        sink.str("H\t"); sink.u64(cluster_no); sink.put('\t'); sink.u64(db->seqlen[hit]); sink.put('\t'); sink.fixed1(percentid);
-        sink.str("\t+\t0\t0\t");
-        if (nwdiff > 0) { const std::string cigar = swa_cigar(scratch.ops); sink.write(cigar.data(), cigar.size()); }
-        else { sink.put('='); }
-        sink.put('\t');
-        swa_out::id(sink, db, hit, usearch != 0, append_abundance);
-        sink.put('\t');
-        swa_out::id(sink, db, seed, usearch != 0, append_abundance);
-        sink.put('\n');
+        const std::string cigar = nwdiff > 0 ? swa_cigar(scratch.ops) : std::string();
+        swa_out::uclust_hit(sink, db, cluster_no, hit, seed, nwdiff, scratch.ops.size(), cigar.data(), cigar.size(), usearch != 0,
+                            append_abundance);
       }
     }
   });
   return SWA_OK;
+}
+
+// -u with the alignments on the GPU (seam B5): the same lines as swa_dn_write_uclust, the pairs aligned by swa_nw_batch
+extern "C" int swa_dn_write_uclust_gpu(swa_ctx * ctx, const swa_dn_result * r, const swa_hostdb * db, const char * path, int usearch,
+                                       int64_t append_abundance) {
+  BufOut o(path);
+  if (!o.ok()) { return SWA_E_ARG; }
+  return swa_uclust_gpu(ctx, db, o, r->swarms.size(), r->order.size() >= 200, r->pen_mismatch, r->pen_gapopen, r->pen_gapextend,
+    [&](size_t k, auto && push) {
+      const auto & s = r->swarms[k];
+      const uint32_t seed = r->order[s.begin].id;
+      for (uint32_t l = s.link_begin; l < s.link_end; ++l) { push(r->links[l].child, seed); }
+    },
+    [&](size_t k) -> uint64_t { return 1u + (r->swarms[k].end - r->swarms[k].begin); },
+    [&](BufOut & sink, size_t k, const swa_uclust_chunk & c, uint64_t p) {
+      const auto & s = r->swarms[k];
+      const uint32_t seed = r->order[s.begin].id;
+      swa_out::uclust_cluster(sink, db, k, s.end - s.begin, seed, usearch != 0, append_abundance);
+      for (uint32_t l = s.link_begin; l < s.link_end; ++l, ++p) {
+        size_t len = 0;
+        const char * cigar = swa_uclust_cigar(c, p, &len);
+        swa_out::uclust_hit(sink, db, k, r->links[l].child, seed, c.diffs[p], c.columns[p], cigar, len, usearch != 0, append_abundance);
+      }
+    });
 }

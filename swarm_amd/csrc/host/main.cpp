@@ -237,6 +237,15 @@ void check_writer(int rc, const char * what, const swa_d1_result * res = nullptr
   if (rc != SWA_OK) { die(std::string("Unable to open ") + what + " file for writing."); }
 }
 
+// the -u writers that align on the GPU: a device failure is reported as such
+void check_gpu_writer(int rc, swa_ctx * ctx, const char * what, const swa_d1_result * res = nullptr) {
+  if (rc != SWA_OK && rc != SWA_E_ARG && ctx != nullptr && swa_last_error(ctx)[0] != '\0' &&
+      (res == nullptr || swa_d1_result_error(res)[0] == '\0')) {
+    die(swa_last_error(ctx));
+  }
+  check_writer(rc, what, res);
+}
+
 }  // namespace
 
 // The command line proper.  The executable (host/launcher.cpp) is a few lines that set the OpenMP wait policy and load this
@@ -533,8 +542,8 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     if (!o.seeds.empty()) { check_writer(swa_d1_write_seeds(res, db, o.seeds.c_str(), o.usearch), "seeds", res); phase(o, "Writing seeds:    "); }
     if (!o.structure.empty()) { check_writer(swa_d1_write_structure(res, db, o.structure.c_str(), o.usearch), "internal structure", res); phase(o, "Writing structure:"); }
     if (!o.uclust.empty()) {
-      check_writer(swa_d1_write_uclust(res, db, o.uclust.c_str(), o.usearch, o.append_abundance, (uint64_t)o.pen_mismatch,
-                                       (uint64_t)o.pen_gapopen, (uint64_t)o.pen_gapextend), "uclust", res);
+      check_gpu_writer(swa_d1_write_uclust_gpu(ctx, res, db, o.uclust.c_str(), o.usearch, o.append_abundance, (uint64_t)o.pen_mismatch,
+                                               (uint64_t)o.pen_gapopen, (uint64_t)o.pen_gapextend), ctx, "uclust", res);
       phase(o, "Writing UCLUST:   ");
     }
     if (!o.stats.empty()) { check_writer(swa_d1_write_stats(res, db, o.stats.c_str(), o.usearch), "statistics", res); phase(o, "Writing stats:    "); }
@@ -562,7 +571,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     if (res != nullptr) {
       check_writer(swa_dn_write_swarms(res, db, o.output.c_str(), o.mothur, o.usearch, o.append_abundance), "output");
       if (!o.structure.empty()) { check_writer(swa_dn_write_structure(res, db, o.structure.c_str(), o.usearch), "internal structure"); }
-      if (!o.uclust.empty()) { check_writer(swa_dn_write_uclust(res, db, o.uclust.c_str(), o.usearch, o.append_abundance), "uclust"); }
+      if (!o.uclust.empty()) { check_gpu_writer(swa_dn_write_uclust_gpu(ctx, res, db, o.uclust.c_str(), o.usearch, o.append_abundance), ctx, "uclust"); }
       if (!o.stats.empty()) { check_writer(swa_dn_write_stats(res, db, o.stats.c_str(), o.usearch), "statistics"); }
       if (!o.seeds.empty()) { check_writer(swa_dn_write_seeds(res, db, o.seeds.c_str(), o.usearch), "seeds"); phase(o, "Writing seeds:    "); }
       swa_dn_result_summary(res, sum);

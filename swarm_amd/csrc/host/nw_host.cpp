@@ -1,9 +1,10 @@
 // nw_host.cpp — see nw_host.h.  Minimum-cost global alignment with affine gaps and the
 // reference's tie-breaking (comparison semantics of src/nw.cc:91-103, walk-back priority of
-// src/nw.cc:139-172); only the uclust writer uses it.
+// src/nw.cc:139-172); the host uclust writers use it, and swa_nw_batch for the pairs it leaves to the host.
 #include "nw_host.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace {
 inline unsigned nt(const uint64_t * s, uint64_t p) { return (unsigned)((s[p >> 5] >> ((p & 31u) << 1)) & 3u); }
@@ -78,4 +79,21 @@ std::string swa_cigar(const std::string & ops) {
     i = j;
   }
   return out;
+}
+
+// the aligner behind the C ABI (include/swarm_amd_host.h), for tests and integrators
+extern "C" uint64_t swa_nw_align_host(const uint64_t * dseq, uint32_t dlen, const uint64_t * qseq, uint32_t qlen, uint64_t mismatch,
+                                      uint64_t gapopen, uint64_t gapextend, uint64_t * columns, char * cigar, uint64_t cigar_cap,
+                                      uint64_t * cigar_len) {
+  swa_nw_scratch sc;
+  const uint64_t diffs = swa_nw_align(dseq, dlen, qseq, qlen, mismatch, gapopen, gapextend, sc);
+  const std::string text = swa_cigar(sc.ops);
+  if (columns != nullptr) { *columns = sc.ops.size(); }
+  if (cigar_len != nullptr) { *cigar_len = text.size(); }
+  if (cigar != nullptr && cigar_cap > 0) {
+    const size_t n = std::min<size_t>(text.size(), (size_t)cigar_cap - 1);
+    std::memcpy(cigar, text.data(), n);
+    cigar[n] = '\0';
+  }
+  return diffs;
 }

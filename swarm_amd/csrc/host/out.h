@@ -218,4 +218,32 @@ inline void sequence(BufOut & o, const swa_hostdb * db, uint32_t i, std::string 
   o.put('\n');
 }
 
+// -u: the C and S lines that open one cluster (src/algod1.cc:870-893, src/algo.cc:610-619)
+inline void uclust_cluster(BufOut & o, const swa_hostdb * db, uint64_t cluster_no, uint64_t size, uint32_t seed, bool usearch,
+                           int64_t append_abundance) {
+  o.str("C\t"); o.u64(cluster_no); o.put('\t'); o.u64(size); o.str("\t*\t*\t*\t*\t*\t");
+  id(o, db, seed, usearch, append_abundance);
+  o.str("\t*\n");
+  o.str("S\t"); o.u64(cluster_no); o.put('\t'); o.u64(db->seqlen[seed]); o.str("\t*\t*\t*\t*\t*\t");
+  id(o, db, seed, usearch, append_abundance);
+  o.str("\t*\n");
+}
+
+// -u: the H line of a member aligned against its seed (src/algod1.cc:896-925, src/algo.cc:620-655) — the one formatter
+// of the host writers (swa_nw_align) and the GPU writers (swa_nw_batch)
+inline void uclust_hit(BufOut & o, const swa_hostdb * db, uint64_t cluster_no, uint32_t member, uint32_t seed, uint64_t diffs,
+                       uint64_t columns, const char * cigar, size_t cigar_len, bool usearch, int64_t append_abundance) {
+  const double cols = (double)columns;
+  const double percentid = 100.0 * (cols - (double)diffs) / cols;
+  o.str("H\t"); o.u64(cluster_no); o.put('\t'); o.u64(db->seqlen[member]); o.put('\t'); o.fixed1(percentid);
+  o.str("\t+\t0\t0\t");
+  if (diffs > 0) { o.write(cigar, cigar_len); }
+  else { o.put('='); }
+  o.put('\t');
+  id(o, db, member, usearch, append_abundance);
+  o.put('\t');
+  id(o, db, seed, usearch, append_abundance);
+  o.put('\n');
+}
+
 }  // namespace swa_out

@@ -1,0 +1,97 @@
+// uclust_gpu.h — the -u writers on the GPU (seam B5): the H lines' pairs collected in printing order, aligned by
+// swa_nw_batch in chunks of bounded size, and formatted by the multi-threaded formatter while the GPU aligns the next
+// chunk.  The d = 1 and d >= 2 writers differ only in how they walk their swarms.
+#pragma once
+
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <thread>
+#include <vector>
+
+#include "hostdb.h"
+#include "out.h"
+
+struct swa_uclust_chunk {
+  size_t begin = 0, end = 0;          // swarms [begin, end)
+  std::vector<uint64_t> first;        // per swarm of the chunk: its first pair; one more entry at the end
+  std::vector<uint32_t> d, q;         // (member, seed) of every H line, in printing order
+  std::vector<uint32_t> diffs, columns;
+  std::vector<uint64_t> cigar_end;
+  std::unique_ptr<char[]> cigar;
+  uint64_t cigar_cap = 0;             // sum of dl + ql: no CIGAR is longer than its alignment
+  int rc = SWA_OK;
+};
+
+// pairs per chunk: SWA_NW_CHUNK (a test hook: many chunks on small inputs), else 2^20
+inline uint64_t swa_uclust_chunk_pairs() {
+  const char * e = std::getenv("SWA_NW_CHUNK");
+  const long long v = e != nullptr ? std::atoll(e) : 0;
+  return v > 0 ? (uint64_t)v : (uint64_t)1 << 20;
+}
+
+// collect(k, push): push(member, seed) for every H line of swarm k, in printing order.  weight(k): what swarm k costs to
+// format.  format(sink, k, chunk, p): prints swarm k, whose first H line is pair p of the chunk.
+template <class Collect, class Weight, class Format>
+int swa_uclust_gpu(swa_ctx * ctx, const swa_hostdb * db, BufOut & o, size_t nswarms, bool parallel, uint64_t mismatch,
+                   uint64_t gapopen, uint64_t gapextend, Collect && collect, Weight && weight, Format && format) {
+  const uint64_t cap = swa_uclust_chunk_pairs();
+  auto fill = [&](swa_uclust_chunk & c, size_t from) {
+    c.begin = from;
+    c.first.clear(); c.d.clear(); c.q.clear();
+    c.cigar_cap = 0;
+    c.rc = SWA_OK;
+    size_t k = from;
+    for (; k < nswarms && c.d.size() < cap; ++k) {
+      c.first.push_back(c.d.size());
+      collect(k, [&](uint32_t member, uint32_t seed) {
+        c.d.push_back(member);
+        c.q.push_back(seed);
+        c.cigar_cap += (uint64_t)db->seqlen[member] + db->seqlen[seed];
+      });
+    }
+    c.first.push_back(c.d.size());
+    c.end = k;
+  };
+  uint64_t tiers[4] = {};
+  auto align = [&](swa_uclust_chunk & c) {
+    const size_t n = c.d.size();
+    c.diffs.resize(n); c.columns.resize(n); c.cigar_end.resize(n);
+    c.cigar.reset(new char[std::max<uint64_t>(c.cigar_cap, 1)]);
+    uint64_t total = 0;
+    // (a result without H lines needs no context, and the command line has none for an empty input)
+    if (n == 0) { c.rc = SWA_OK; return; }
+    if (ctx == nullptr) { c.rc = SWA_E_ARG; return; }
+    c.rc = swa_nw_batch(ctx, mismatch, gapopen, gapextend, n, c.d.data(), c.q.data(), c.diffs.data(), c.columns.data(),
+                        c.cigar_end.data(), c.cigar.get(), c.cigar_cap, &total);
+    uint64_t t[4] = {};
+    if (c.rc == SWA_OK && swa_nw_batch_totals(ctx, t) == SWA_OK) { for (int i = 0; i < 4; ++i) { tiers[i] += t[i]; } }
+  };
+  swa_uclust_chunk cur, next;
+  fill(cur, 0);
+  align(cur);
+  while (cur.rc == SWA_OK && cur.begin < cur.end) {
+    fill(next, cur.end);
+    std::thread gpu;
+    if (next.begin < next.end) { gpu = std::thread([&] { align(next); }); }
+    const swa_uclust_chunk & c = cur;
+    swa_format_in_weighted_pieces(o, c.end - c.begin, parallel, [&](size_t i) { return weight(c.begin + i); },
+                                  [&](BufOut & sink, size_t b, size_t e) {
+                                    for (size_t i = b; i < e; ++i) { format(sink, c.begin + i, c, c.first[i]); }
+                                  });
+    if (gpu.joinable()) { gpu.join(); }
+    std::swap(cur, next);
+  }
+  if (std::getenv("SWARM_AMD_TIMING") != nullptr) {      // (the CLI's milestones: where the pairs were aligned)
+    std::fprintf(stderr, "[nw] pairs by band half-width 6 / 14 / 30 / host: %llu %llu %llu %llu\n", (unsigned long long)tiers[0],
+                 (unsigned long long)tiers[1], (unsigned long long)tiers[2], (unsigned long long)tiers[3]);
+  }
+  return cur.rc;
+}
+
+// the CIGAR of pair p of a chunk
+inline const char * swa_uclust_cigar(const swa_uclust_chunk & c, uint64_t p, size_t * len) {
+  const uint64_t from = p == 0 ? 0 : c.cigar_end[p - 1];
+  *len = (size_t)(c.cigar_end[p] - from);
+  return c.cigar.get() + from;
+}

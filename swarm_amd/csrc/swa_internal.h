@@ -166,6 +166,12 @@ struct swa_ctx {
   bool csr_has_diffs = false;                 // the resident network is a d >= 2 graph: one byte of differences per link behind the neighbours
   uint64_t csr_total = 0;
   swa_dbuf d_cluster, d_cluster_ctl;
+
+  // the uclust alignments (nw_trace.hip): the database's lengths on the host (filled by the first swa_nw_batch after an
+  // upload), the pairs per tier of the last batch, and the device buffers of one slice
+  std::vector<uint32_t> nw_seqlen;
+  uint64_t nw_totals[4] = {};
+  swa_dbuf d_nw_ids, d_nw_lists, d_nw_res, d_nw_text, d_nw_gather;
 };
 
 int swa_fail(swa_ctx * ctx, int code, const char * what, hipError_t e);
