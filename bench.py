@@ -14,7 +14,8 @@ Workload at N = 1: the size BASELINE.json's metric string names — 10 M synthet
 weak-scaled: the database holds N x 10 M amplicons (N = 8: 80 M, the order of configs[4]), replicated on every GPU;
 rank r serves the anchor groups whose key maps to r (routed index build), the links travel all-to-all by seed range.
 
-At N = 1 the same run also measures, after the timed region (none of it enters `value`; --no-extras skips it):
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints its line: nothing else.  With
+--full, at N = 1 the same run also measures, after the timed region (none of it enters `value`):
   config.configs1 / configs2 / configs3   BASELINE configs[1..3]
   config.skewed / skewed_70 / v4_like / heavy_tail   the headline step on conserved flanks (40 nt; 70 nt: wider than a window) /
                                            on 250-nt reads with 60 % conserved positions / on Zipf-sized families
@@ -34,16 +35,21 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                    --pmc pass) / its duration (HIP events on the launch stream), peak = the guide's issue rate
                    (256 CUs x 4 SIMDs x 1/2 a cycle x 2.4 GHz = 1.23e12 wave-instr/s), the ceiling tools/ubench_lines measures on
                    this box beside it (peak_measured); roofline.hbm = the HBM view of the same kernel on COUNTER bytes
-                   (and on its algorithmic bytes).  Without the counter passes (--no-extras) the object falls back to the
+                   (and on its algorithmic bytes).  Without the counter passes (without --full) the object falls back to the
                    HBM view on algorithmic bytes.  The same per kernel group (kernels), the step as a whole (step,
                    step_traffic_over_minimum = measured bytes / (64 n + 12 e + 8 n)); SURVEY.md 8(d)'s figure — the
                    reference's probing loop, which this route never performs — kept as reference_equivalent_rate.
-  "cpu_baseline" — the unmodified reference (oracle/_ref/swarm, kind "reference") timed on this box's host cores on a
-                   bounded sample (1 M); cpu_baseline_10M: the same on the metric's own 10 M set, once.
+  "cpu_baseline" — (--full) the unmodified reference (oracle/_ref/swarm, kind "reference") timed on this box's host cores on
+                   a bounded sample (1 M); cpu_baseline_10M: the same on the metric's own 10 M set, once.
+At N > 1, --full also runs the command line's own multi-GPU driver on the same GPUs after the line (cpp_multi).
+
+Every synthetic set of a run is generated into a directory of its own, removed at exit: no run reads what an earlier run
+wrote.
 """
 from __future__ import annotations
 
 import argparse
+import atexit
 import json
 import os
 
@@ -62,6 +68,7 @@ def _usable_cpus() -> int:              # (affinity and cgroup CPU quota: swarm_
 
 
 os.environ.setdefault("OMP_NUM_THREADS", str(min(32, _usable_cpus())))   # (the host phases' OpenMP teams, as the command line sets them)
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -77,6 +84,10 @@ HBM_PEAK_GBS = 8000.0      # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROA
 # VALU issue peak of the chip, same guide ("Wave scheduling": 4 SIMD-32 per CU, a 64-lane wave issues each VALU instruction
 # over 2 cycles): 256 CUs x 4 SIMDs x 0.5 wave-instructions a cycle x 2.4 GHz
 VALU_PEAK_WAVE_INSTR_S = 256 * 4 * 0.5 * 2.4e9
+
+# where gen_fasta keeps the synthetic sets: the temp dir for callers that import this module (the tests); main() points it at
+# a fresh directory of the run's own
+DATA_DIR = Path(tempfile.gettempdir())
 
 
 def algorithmic_bytes(seqlen: np.ndarray, hits: int) -> float:
@@ -97,12 +108,12 @@ def gen_tool() -> Path:
 
 def gen_fasta(n: int, length: int, seed: int, edits: int = 1, light: float = 0.0, flank: int = 0, zipf: float = 0.0, conserved: int = 0) -> Path:
     """The synthetic amplicon set (SURVEY.md section 8d shapes; tools/gen_amplicons.c), cached in
-    the temp dir.  Sets above 2 M are generated as independent blocks of <= 2 M amplicons by
+    DATA_DIR.  Sets above 2 M are generated as independent blocks of <= 2 M amplicons by
     parallel processes (disjoint header numbers, seeds derived from `seed`) and concatenated.
     edits > 1 (the d >= 2 sets) or light > 0 (the --fastidious sets: that fraction of abundance-1
     amplicons 2-3 edits away from a heavy one) are one generator call whatever the size."""
     if edits != 1 or light != 0.0:
-        fasta = Path(tempfile.gettempdir()) / f"swa_cfg_{n}x{length}_s{seed}_e{edits}_l{light}.fa"
+        fasta = DATA_DIR / f"swa_cfg_{n}x{length}_s{seed}_e{edits}_l{light}.fa"
         if not fasta.exists():
             tmp = fasta.with_suffix(f".tmp{os.getpid()}")
             subprocess.run([str(gen_tool()), str(n), str(length), str(seed), str(edits), str(light), str(tmp)], check=True)
@@ -113,7 +124,7 @@ def gen_fasta(n: int, length: int, seed: int, edits: int = 1, light: float = 0.0
     # zipf > 0: family sizes follow Zipf's law (GEN_ZIPF): the largest family of every 2 M block is that share of the block
     # conserved > 0: that per cent of the positions, in stretches of 8..40 nt, is the same in every centroid (GEN_CONSERVED)
     tag = (f"_f{flank}" if flank else "") + (f"_z{zipf}" if zipf else "") + (f"_c{conserved}" if conserved else "")
-    fasta = Path(tempfile.gettempdir()) / f"swa_bench_{n}x{length}_s{seed}{tag}.fa"
+    fasta = DATA_DIR / f"swa_bench_{n}x{length}_s{seed}{tag}.fa"
     if fasta.exists():
         return fasta
     genv = dict(os.environ, **({"GEN_FLANK": str(flank)} if flank else {}), **({"GEN_ZIPF": str(zipf)} if zipf else {}),
@@ -195,7 +206,7 @@ def cpu_baseline(fasta: Path, n: int, length: int, seed: int) -> dict:
 def gen_mixed_fasta(n: int, length: int, seed: int) -> Path:
     """n x length amplicons plus one per cent of 420-480 nt ones (five blocks of lengths 425, 438, 450, 462, 475, each with
     its own families): the file a 16S V4 run with a few V3-V4 or chimeric reads in it looks like."""
-    fasta = Path(tempfile.gettempdir()) / f"swa_bench_{n}x{length}_s{seed}_mixed.fa"
+    fasta = DATA_DIR / f"swa_bench_{n}x{length}_s{seed}_mixed.fa"
     if fasta.exists():
         return fasta
     base = gen_fasta(n, length, seed)
@@ -551,7 +562,6 @@ def measured_pmc(args) -> dict | None:
     random lines, everything else streams.  WRITE_SIZE is taken as reported (exact for streaming stores)."""
     import csv
     import glob
-    import shutil
     if shutil.which("rocprofv3") is None:
         return None
     steps, warm = 2, 1
@@ -793,7 +803,7 @@ def dump_outputs(directory: str, off: np.ndarray, nb: np.ndarray) -> dict:
     return {"dir": str(out), "rows": int(rows.shape[0]), "of_rows": n, "bytes": sum(8 * int(a.size) for a in arrays.values())}
 
 
-def main() -> None:
+def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -801,13 +811,17 @@ def main() -> None:
     ap.add_argument("--per-gpu", type=int, default=10_000_000, help="amplicons queried per GPU")
     ap.add_argument("--length", type=int, default=150)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--extras", default="all", help="comma list of the config.* measurements to run after the timed region (default: all)")
-    ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline step: no cpu_baseline, no configs1/2/3, no whole-run / seam timings, no PMC traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: cpu_baseline, configs1/2/3, the other "
+                         "d=1 sets, whole-run / seam / first-step timings, ceilings and PMC traffic (N = 1); the multi-GPU "
+                         "command line's check (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference's timings")
+    ap.add_argument("--extras", default="all", help="with --full: comma list of the config.* measurements to run after the timed region (default: all)")
+    ap.add_argument("--no-extras", action="store_true", help="only the headline step, as without --full (overrides it)")
     ap.add_argument("--no-configs1", action="store_true",
-                    help="skip the extra configs[1] (1 M x 150) measurement reported under config.configs1 (N = 1 only)")
-    ap.add_argument("--whole-runs", type=int, default=24, help="runs of the command line on the headline's set behind whole_run's median / p95")
+                    help="with --full: skip the extra configs[1] (1 M x 150) measurement reported under config.configs1 (N = 1 only)")
+    ap.add_argument("--whole-runs", type=int, default=24,
+                    help="with --full: runs of the command line on the headline's set behind whole_run's median / p95")
     ap.add_argument("--simulate-world", type=int, default=0,
                     help="development aid: run rank 0's share of an N-GPU job on this one GPU (no collectives); "
                          "the JSON line is marked simulated and is not a result")
@@ -825,11 +839,18 @@ def main() -> None:
                          "through the host), to exercise the sharded step on a one-GPU box; marked simulated")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (a seeded sample of the CSR's rows) to DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.no_extras:
-        args.no_cpu_baseline = args.no_configs1 = True
+    if args.extras != "all" and not args.full:
+        ap.error("--extras selects among the measurements of --full")
+    if args.no_extras or not args.full:
+        args.no_extras = args.no_cpu_baseline = args.no_configs1 = True
+    return args
+
+
+def main() -> None:
+    args = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -853,7 +874,15 @@ def main() -> None:
 
     sim_world = args.simulate_world if world == 1 and args.simulate_world > 1 else 0
     n_total = args.per_gpu * (sim_world or world)
-    fasta = Path(tempfile.gettempdir()) / f"swa_bench_{n_total}x{args.length}_s{args.seed}.fa"
+    # the run's synthetic sets: a fresh directory (rank 0's, shared with the other ranks), removed at exit
+    global DATA_DIR
+    shared = [tempfile.mkdtemp(prefix="swa_bench_") if rank == 0 else None]
+    if world > 1:
+        dist.broadcast_object_list(shared, src=0)
+    DATA_DIR = Path(shared[0])
+    if rank == 0:
+        atexit.register(shutil.rmtree, DATA_DIR, True)
+    fasta = DATA_DIR / f"swa_bench_{n_total}x{args.length}_s{args.seed}.fa"
     if local_rank == 0:
         gen_fasta(n_total, args.length, args.seed)
     if world > 1:

@@ -157,3 +157,19 @@ def test_bench_defaults_without_a_gpu():
     assert m["keys"] == 80 * 10_000_000 and m["groups"] == 24 * 10_000_000
     assert all(v > 0 for v in m.values())
     assert bench.VALU_PEAK_WAVE_INSTR_S == 256 * 4 * 0.5 * 2.4e9 and bench.HBM_PEAK_GBS == 8000.0
+
+
+def test_a_plain_run_measures_the_headline_alone():
+    """Without --full the run stops after its line: no baselines, no other configs, no counter passes; --full turns them on
+    and --no-extras still turns them off."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    plain = bench.parse_args(["--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.no_extras and plain.no_cpu_baseline and plain.no_configs1
+    full = bench.parse_args(["--full"])
+    assert full.full and not (full.no_extras or full.no_cpu_baseline or full.no_configs1) and full.extras == "all"
+    narrowed = bench.parse_args(["--full", "--no-cpu-baseline", "--extras", "configs3"])
+    assert not narrowed.no_extras and narrowed.no_cpu_baseline and not narrowed.no_configs1 and narrowed.extras == "configs3"
+    assert bench.parse_args(["--full", "--no-extras"]).no_cpu_baseline
+    with pytest.raises(SystemExit):                              # (an extra named without --full would silently not run)
+        bench.parse_args(["--extras", "configs3"])
