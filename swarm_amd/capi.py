@@ -553,6 +553,23 @@ class Context:
         self._check(self.lib.swa_d1_network_fetch(self.h, _ptr(offsets), _ptr(nb), len(nb)))
         return offsets, nb[:total]
 
+    def d1_cluster_device(self):
+        """swa_d1_cluster_device on the resident network with all five result arrays on the host (none null):
+        (swarmid, generation, parent, order, begins); the members of swarm s are order[begins[s]:begins[s + 1]]."""
+        lib = self.lib
+        lib.swa_d1_cluster_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_uint32, u32p]
+        swarmid, generation, parent, order = (np.zeros(self.n, dtype=np.uint32) for _ in range(4))
+        nswarms = C.c_uint32(0)
+        begins = np.zeros(1, dtype=np.uint32)
+        rc = self._check(lib.swa_d1_cluster_device(self.h, _ptr(swarmid), _ptr(generation), _ptr(parent), _ptr(order), None, 0,
+                                                   C.byref(nswarms)), allow=(SWA_E_CAPACITY,))
+        if rc == SWA_E_CAPACITY:
+            begins = np.zeros(nswarms.value + 1, dtype=np.uint32)
+            self._check(lib.swa_d1_cluster_device(self.h, _ptr(swarmid), _ptr(generation), _ptr(parent), _ptr(order), _ptr(begins),
+                                                  nswarms.value, C.byref(nswarms)))
+        return swarmid, generation, parent, order, begins
+
     def d1_network_device(self, d_offsets, d_neighbours, cap: int, no_cluster_breaking: bool = False,
                           first: int = 0, count: int | None = None) -> int:
         """Device-resident CSR (torch tensors); returns the number of neighbours written."""

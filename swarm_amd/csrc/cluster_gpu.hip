@@ -276,12 +276,14 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, keys_in, keys_out, ids_in, ids_out, (size_t)n, 0, gbits + sbits, ctx->stream));
     hipLaunchKernelGGL(k_swarm_bounds<unsigned long long>, g, b, 0, ctx->stream, keys_out, n, gbits, *nswarms, begins);
   }
+  // the host pages are faulted in BEFORE any copy into them is queued (swa_touch_pages writes a zero byte a page: after a
+  // queued copy it would race with it — and clear bytes the copy had already landed)
+  for (uint32_t * out : {swarmid, generation, parent, order}) { swa_touch_pages(out, (uint64_t)n * sizeof(uint32_t)); }   // (pinned pages: nothing to do)
   if (swarmid != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(swarmid, sid, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
   if (generation != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(generation, gen, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
   if (parent != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(parent, par, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
   SWA_HIP(ctx, hipGetLastError());
   if (timing) { SWA_HIP(ctx, hipStreamSynchronize(ctx->stream)); lap("keys, sort, bounds", gbits + sbits); }
-  for (uint32_t * out : {swarmid, generation, parent, order}) { swa_touch_pages(out, (uint64_t)n * sizeof(uint32_t)); }   // (pinned pages: nothing to do)
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (timing) { for (auto & e : ev) { (void)hipEventCreate(&e); } (void)hipEventRecord(ev[0], ctx->stream); }
   SWA_HIP(ctx, hipMemcpyAsync(order, ids_out, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));

@@ -159,14 +159,22 @@ __global__ __launch_bounds__(256) void k_dg_scatter(const GroupArgs a, const uin
 }
 
 // BLOCKED = false: the tiles of k_dg_pairs (4096 pairs, at most kStride items a group); true: the blocks of k_dg_pairs_lds
-// (kBlockT targets x kBlockQ queries each, item.tile = target block + target blocks x query chunk)
+// (kBlockT targets x kBlockQ queries each, block b = target block + target blocks x query chunk), dealt round-robin to at most
+// kBlockStride items a group (item.tile = its first block).  Either way a group's items are bounded, and so is their sum:
+// min(S, x y) <= 1 + sqrt(S) (x - 1 + y - 1) for x, y >= 1, so a group of t targets and q >= 1 queries makes at most
+// 1 + t / 4 + q / 16 blocked items (S = 256, x = ceil(t / 64), y = ceil(q / 256)) and at most 1 + t / 8 + q / 8 tiles
+// (S = 64, 4096-pair tiles); over all groups t sums to <= n (2 d + 1), q to <= n, and the groups with items number <= n
+// (every one holds a query): the host's item_cap = n + n (2 d + 2) / 2 + 64 holds them (tests/test_pair_identity.py).
+// Items past the cap are not dropped quietly: *overflow is raised and the search fails.
 constexpr uint32_t kBlockT = 64;          // targets of a block: one per lane
 constexpr uint32_t kBlockQ = 256;         // queries of a block, staged kStageQ at a time
 constexpr uint32_t kStageQ = 16;
+constexpr uint32_t kBlockStride = 256;    // a group's blocks are dealt round-robin to at most this many items
 template <bool BLOCKED>
 __global__ __launch_bounds__(256) void k_dg_items(const uint32_t * __restrict__ cnt_t, const uint32_t * __restrict__ cnt_q,
                                                   const uint32_t * __restrict__ tot, const uint64_t * __restrict__ offsets,
-                                                  uint64_t asize, dg_item * items, uint32_t * counter, uint32_t cap) {
+                                                  uint64_t asize, dg_item * items, uint32_t * counter, uint32_t cap,
+                                                  uint32_t * overflow) {
   __shared__ uint32_t n_items, base;
   if (threadIdx.x == 0) { n_items = 0u; }
   __syncthreads();
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(256) void k_dg_items(const uint32_t * __restrict__ 
     if (tot[s] == 0u) { return 0u; }
     if (BLOCKED) {
       const uint64_t blocks = (uint64_t)((cnt_t[s] + kBlockT - 1u) / kBlockT) * ((cnt_q[s] + kBlockQ - 1u) / kBlockQ);
-      return (uint32_t)(blocks < 0x7FFFFFFFull ? blocks : 0x7FFFFFFFull);
+      return (uint32_t)(blocks < kBlockStride ? blocks : kBlockStride);
     }
     const uint64_t tiles = ((uint64_t)cnt_t[s] * cnt_q[s] + kTile - 1) / kTile;
     return (uint32_t)(tiles < kStride ? tiles : kStride);
@@ -194,7 +202,8 @@ __global__ __launch_bounds__(256) void k_dg_items(const uint32_t * __restrict__ 
     const uint32_t at = base + atomicAdd(&n_items, k);
     dg_item it;
     it.begin = (uint32_t)offsets[s]; it.nt = cnt_t[s]; it.nq = cnt_q[s];
-    for (uint32_t t = 0; t < k; ++t) { it.tile = t; if (at + t < cap) { items[at + t] = it; } }
+    if ((uint64_t)at + k > cap) { *overflow = 1u; }
+    for (uint32_t t = 0; t < k; ++t) { it.tile = t; if ((uint64_t)at + t < cap) { items[at + t] = it; } }
   }
 }
 
@@ -354,81 +363,84 @@ __global__ __launch_bounds__(256) void k_dg_pairs_lds(const PairArgs a) {
     const uint32_t * targets = a.members + item.begin;
     const uint32_t * queries = targets + item.nt;
     const uint32_t ntb = (item.nt + kBlockT - 1u) / kBlockT;
-    const uint32_t tb = item.tile % ntb, qc = item.tile / ntb;
-    // ---- my target: windows at every shift of the windows 0 .. K, validity, signature
-    const uint32_t ti = tb * kBlockT + (uint32_t)lane;
-    const bool have_t = ti < item.nt;
-    const uint32_t t = have_t ? targets[ti] : 0u;
-    const int lt = have_t ? (int)a.seqlen[t] : 0;
-    const uint64_t * st = a.seqs + a.seq_off[t];
-    uint64_t twin[D + 1][NS];
-    uint32_t valid = 0u;
+    const uint64_t nblocks = (uint64_t)ntb * ((item.nq + kBlockQ - 1u) / kBlockQ);
+    for (uint64_t blk = item.tile; blk < nblocks; blk += kBlockStride) {
+      const uint32_t tb = (uint32_t)(blk % ntb), qc = (uint32_t)(blk / ntb);
+      // ---- my target: windows at every shift of the windows 0 .. K, validity, signature
+      const uint32_t ti = tb * kBlockT + (uint32_t)lane;
+      const bool have_t = ti < item.nt;
+      const uint32_t t = have_t ? targets[ti] : 0u;
+      const int lt = have_t ? (int)a.seqlen[t] : 0;
+      const uint64_t * st = a.seqs + a.seq_off[t];
+      uint64_t twin[D + 1][NS];
+      uint32_t valid = 0u;
 #pragma unroll
-    for (int k2 = 0; k2 <= D; ++k2) {
+      for (int k2 = 0; k2 <= D; ++k2) {
 #pragma unroll
-      for (int s2 = 0; s2 < NS; ++s2) {
-        const int pos = k2 * (int)a.wlen + s2 - D;
-        const bool ok = have_t && (uint32_t)k2 <= K && pos >= 0 && pos + (int)a.wlen <= lt;
-        twin[k2][s2] = ok ? window(st, (uint32_t)pos, a.wlen) : 0ull;
-        valid |= ok ? 1u << (k2 * NS + s2) : 0u;
-      }
-    }
-    uint64_t tsig[16];
-    {
-      const ulonglong2 * gt = a.sigs + (uint64_t)t * 8u;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) { const ulonglong2 y = have_t ? gt[w] : make_ulonglong2(0ull, 0ull); tsig[2 * w] = y.x; tsig[2 * w + 1] = y.y; }
-    }
-    const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nq, q_begin + kBlockQ);
-    for (uint32_t qs = q_begin; qs < q_end; qs += kStageQ) {
-      const uint32_t nq_here = min(kStageQ, q_end - qs);
-      wave_lds_sync();
-      // ---- the next queries into LDS: lanes [16 j', 16 j' + 16) carry the signature words of query 4 r + j'
-      for (uint32_t r = 0; r < kStageQ / 4u; ++r) {
-        const uint32_t j = 4u * r + ((uint32_t)lane >> 4), w = (uint32_t)lane & 15u;
-        if (j < nq_here) {
-          const uint32_t q = queries[qs + j];
-          qrec[j].sig[w] = reinterpret_cast<const uint64_t *>(a.sigs + (uint64_t)q * 8u)[w];
+        for (int s2 = 0; s2 < NS; ++s2) {
+          const int pos = k2 * (int)a.wlen + s2 - D;
+          const bool ok = have_t && (uint32_t)k2 <= K && pos >= 0 && pos + (int)a.wlen <= lt;
+          twin[k2][s2] = ok ? window(st, (uint32_t)pos, a.wlen) : 0ull;
+          valid |= ok ? 1u << (k2 * NS + s2) : 0u;
         }
       }
-      if ((uint32_t)lane < nq_here) {
-        const uint32_t q = queries[qs + (uint32_t)lane];
-        const uint64_t * sq = a.seqs + a.seq_off[q];
-        qrec[lane].id = q; qrec[lane].len = a.seqlen[q];
+      uint64_t tsig[16];
+      {
+        const ulonglong2 * gt = a.sigs + (uint64_t)t * 8u;
 #pragma unroll
-        for (int k2 = 0; k2 <= D; ++k2) { qrec[lane].win[k2] = (uint32_t)k2 <= K ? window(sq, (uint32_t)k2 * a.wlen, a.wlen) : 0ull; }
+        for (int w = 0; w < 8; ++w) { const ulonglong2 y = have_t ? gt[w] : make_ulonglong2(0ull, 0ull); tsig[2 * w] = y.x; tsig[2 * w + 1] = y.y; }
       }
-      wave_lds_sync();
-      for (uint32_t j = 0; j < nq_here; ++j) {
-        const uint32_t q = qrec[j].id;
-        const int dl = (int)qrec[j].len - lt;
-        bool take = have_t && q < t && dl >= -D && dl <= D;
-        // the pair belongs to the FIRST window of the query that reappears (shifted) in the target
-        bool earlier = false, here = false;
-#pragma unroll
-        for (int k2 = 0; k2 <= D; ++k2) {
-          if ((uint32_t)k2 > K) { continue; }                  // (wave-uniform: the windows behind this launch's are nobody's business here)
-          const uint64_t wq = qrec[j].win[k2];
-          bool hit = false;
-#pragma unroll
-          for (int s2 = 0; s2 < NS; ++s2) { hit = hit || (((valid >> (k2 * NS + s2)) & 1u) != 0u && twin[k2][s2] == wq); }
-          earlier = earlier || ((uint32_t)k2 < K && hit);
-          here = here || ((uint32_t)k2 == K && hit);        // (the group key may collide: window K must really reappear)
+      const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nq, q_begin + kBlockQ);
+      for (uint32_t qs = q_begin; qs < q_end; qs += kStageQ) {
+        const uint32_t nq_here = min(kStageQ, q_end - qs);
+        wave_lds_sync();
+        // ---- the next queries into LDS: lanes [16 j', 16 j' + 16) carry the signature words of query 4 r + j'
+        for (uint32_t r = 0; r < kStageQ / 4u; ++r) {
+          const uint32_t j = 4u * r + ((uint32_t)lane >> 4), w = (uint32_t)lane & 15u;
+          if (j < nq_here) {
+            const uint32_t q = queries[qs + j];
+            qrec[j].sig[w] = reinterpret_cast<const uint64_t *>(a.sigs + (uint64_t)q * 8u)[w];
+          }
         }
-        take = take && !earlier && here;
-        if (__ballot(take) != 0ull) {
-          // q-gram bound (qgram_diff, src/qgram.cc:68-96): ceil(popcount(sig_q ^ sig_t) / 10) <= d
-          uint32_t pop = 0;
+        if ((uint32_t)lane < nq_here) {
+          const uint32_t q = queries[qs + (uint32_t)lane];
+          const uint64_t * sq = a.seqs + a.seq_off[q];
+          qrec[lane].id = q; qrec[lane].len = a.seqlen[q];
 #pragma unroll
-          for (int w = 0; w < 16; ++w) { pop += (uint32_t)__popcll(qrec[j].sig[w] ^ tsig[w]); }
-          if (take) { ++compared; }
-          take = take && (pop + 9u) / 10u <= (uint32_t)D;
+          for (int k2 = 0; k2 <= D; ++k2) { qrec[lane].win[k2] = (uint32_t)k2 <= K ? window(sq, (uint32_t)k2 * a.wlen, a.wlen) : 0ull; }
         }
-        const uint64_t m = __ballot(take);
-        if (m != 0ull) {
-          if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)q << 32) | t; }
-          nstage += (uint32_t)__popcll(m);
-          if (nstage > kStage - 64u) { flush(); }
+        wave_lds_sync();
+        for (uint32_t j = 0; j < nq_here; ++j) {
+          const uint32_t q = qrec[j].id;
+          const int dl = (int)qrec[j].len - lt;
+          bool take = have_t && q < t && dl >= -D && dl <= D;
+          // the pair belongs to the FIRST window of the query that reappears (shifted) in the target
+          bool earlier = false, here = false;
+#pragma unroll
+          for (int k2 = 0; k2 <= D; ++k2) {
+            if ((uint32_t)k2 > K) { continue; }                  // (wave-uniform: the windows behind this launch's are nobody's business here)
+            const uint64_t wq = qrec[j].win[k2];
+            bool hit = false;
+#pragma unroll
+            for (int s2 = 0; s2 < NS; ++s2) { hit = hit || (((valid >> (k2 * NS + s2)) & 1u) != 0u && twin[k2][s2] == wq); }
+            earlier = earlier || ((uint32_t)k2 < K && hit);
+            here = here || ((uint32_t)k2 == K && hit);        // (the group key may collide: window K must really reappear)
+          }
+          take = take && !earlier && here;
+          if (__ballot(take) != 0ull) {
+            // q-gram bound (qgram_diff, src/qgram.cc:68-96): ceil(popcount(sig_q ^ sig_t) / 10) <= d
+            uint32_t pop = 0;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) { pop += (uint32_t)__popcll(qrec[j].sig[w] ^ tsig[w]); }
+            if (take) { ++compared; }
+            take = take && (pop + 9u) / 10u <= (uint32_t)D;
+          }
+          const uint64_t m = __ballot(take);
+          if (m != 0ull) {
+            if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)q << 32) | t; }
+            nstage += (uint32_t)__popcll(m);
+            if (nstage > kStage - 64u) { flush(); }
+          }
         }
       }
     }
@@ -680,7 +692,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     auto * members = static_cast<uint32_t *>(ctx->d_fmembers.ptr);
     auto * items = static_cast<dg_item *>(ctx->d_fitems.ptr);
     auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);   // [0] pairs [1] comparisons [2] extra directions [3] edges
-    auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);             // [8] item counter [9] key table overflow
+    auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);             // [8] item counter [9] key table overflow [11] item overflow
     size_t scan_bytes = 0;
     auto tot64 = rocprim::make_transform_iterator(tot, widen_u32());
     (void)rocprim::exclusive_scan(nullptr, scan_bytes, tot64, goff, (uint64_t)0, asize + 1, rocprim::plus<uint64_t>(), ctx->stream);
@@ -694,6 +706,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->dn_pair_cap * sizeof(uint64_t)));
       SWA_HIP(ctx, hipMemsetAsync(fc, 0, 8 * sizeof(uint64_t), ctx->stream));
       SWA_HIP(ctx, hipMemsetAsync(dflags + 9, 0, sizeof(uint32_t), ctx->stream));
+      SWA_HIP(ctx, hipMemsetAsync(dflags + 11, 0, sizeof(uint32_t), ctx->stream));
       for (uint32_t k = 0; k <= d; ++k) {
         GroupArgs g{};
         g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen; g.n = n; g.d = d; g.k = k; g.wlen = wlen;
@@ -710,8 +723,8 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         SWA_HIP(ctx, hipMemsetAsync(dflags + 8, 0, sizeof(uint32_t), ctx->stream));
         // blocks of 64 targets x 256 queries for the LDS kernel (d = 2, 3; the per-pair kernel for other d)
         const bool blocked = d == 2u || d == 3u;
-        if (blocked) { hipLaunchKernelGGL(k_dg_items<true>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap); }
-        else { hipLaunchKernelGGL(k_dg_items<false>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap); }
+        if (blocked) { hipLaunchKernelGGL(k_dg_items<true>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap, dflags + 11); }
+        else { hipLaunchKernelGGL(k_dg_items<false>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap, dflags + 11); }
         PairArgs p{};
         p.seqs = ctx->db.seqs; p.seq_off = ctx->db.seq_off; p.seqlen = ctx->db.seqlen;
         p.sigs = static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr);
@@ -724,11 +737,12 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         launches += 9;
       }
       uint64_t got[2] = {0, 0};
-      uint32_t fl[2] = {0, 0};
+      uint32_t fl[4] = {0, 0, 0, 0};
       SWA_HIP(ctx, hipMemcpyAsync(got, fc, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
       SWA_HIP(ctx, hipMemcpyAsync(fl, dflags + 8, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
       if (fl[1] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, "swa_dn_graph: group key table overflow"); }
+      if (fl[3] != 0) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_dn_graph: the work items of a window outgrew item_cap"); }
       ctx->dn_comparisons = got[1];
       if (got[0] <= ctx->dn_pair_cap) { npairs = got[0]; break; }
       if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_dn_graph: pair list keeps overflowing"); }

@@ -332,3 +332,96 @@ def test_the_item_regions_hold_the_tiled_kernels_items_whatever_the_groups():
         assert items <= room, (pop, len(sizes), items, room)
     # the 16 bits an item's chunk has: row tile (6 bits) | part << 6
     assert (cap // 64 - 1) | (((cap // 64 + 3) // 4 - 1) << 6) < 1 << 16
+
+
+# ---- d >= 2: the work items of dn_graph.hip's pair kernels and the room swa_dn_graph_compute gives them ---------------------------
+def _dn_graph_constants() -> dict:
+    """kBlockT, kBlockQ, kBlockStride, kTile, kStride as dn_graph.hip declares them (read off the source, so that a change of
+    one of them is checked against the bound below)."""
+    import re
+    from pathlib import Path
+    src = (Path(__file__).resolve().parent.parent / "swarm_amd" / "csrc" / "dn_graph.hip").read_text()
+    out = {}
+    for name in ("kBlockT", "kBlockQ", "kBlockStride", "kTile", "kStride"):
+        m = re.search(r"constexpr uint32_t " + name + r" = (\d+);", src)
+        assert m is not None, name
+        out[name] = int(m.group(1))
+    # the host's room for the items: item_cap = n + member_cap / 2 + 64, member_cap = n (2 d + 2)
+    assert "const uint64_t member_cap = (uint64_t)n * (ns + 1u);" in src
+    assert "const uint64_t item_cap64 = (uint64_t)n + member_cap / 2 + 64;" in src
+    return out
+
+
+def _dn_item_cap(n: int, d: int) -> int:
+    return n + n * (2 * d + 2) // 2 + 64
+
+
+def _dn_blocked_items(t: int, q: int, c: dict) -> int:
+    """k_dg_items<true>: a group of t targets and q queries (t q >= 2) -> its blocks of kBlockT x kBlockQ, at most kBlockStride"""
+    if t * q < 2:
+        return 0
+    return min((t + c["kBlockT"] - 1) // c["kBlockT"] * ((q + c["kBlockQ"] - 1) // c["kBlockQ"]), c["kBlockStride"])
+
+
+def _dn_tiled_items(t: int, q: int, c: dict) -> int:
+    """k_dg_items<false>: tiles of kTile pairs, at most kStride"""
+    if t * q < 2:
+        return 0
+    return min((t * q + c["kTile"] - 1) // c["kTile"], c["kStride"])
+
+
+def test_the_dn_item_list_holds_every_windows_items_whatever_the_groups():
+    """One window's groups: every amplicon is a query in at most one group and a target in at most 2 d + 1 (its window at
+    the shifts -d .. +d), so over the groups q sums to <= n and t to <= n (2 d + 1), and a group with items holds a query.
+    Whatever groups those sums allow — one holding the whole database, many medium ones, t >> q, q >> t — their items fit
+    item_cap: a group's items are capped (kBlockStride / kStride), and min(S, x y) <= 1 + sqrt(S) (x - 1 + y - 1).
+    (Without the cap one group of 100 k amplicons made 611 k blocks at d = 2 against room for 400 k: items past the cap
+    were dropped and their pairs never found.)"""
+    c = _dn_graph_constants()
+    rng = np.random.default_rng(23)
+    # the per-group inequality the bound rests on, exhaustively over the block grid
+    for S, rt, rq in ((c["kBlockStride"], c["kBlockT"], c["kBlockQ"]), (c["kStride"], 64, 64)):
+        r = int(np.floor(np.sqrt(S)))
+        assert r * r == S
+        x = np.arange(1, 600)[:, None]
+        y = np.arange(1, 600)[None, :]
+        assert (np.minimum(S, x * y) <= 1 + r * (x - 1 + y - 1)).all()
+
+    def check(groups, n, d):
+        """groups: (t, q, how many such groups)"""
+        assert sum(t * k for t, _, k in groups) <= n * (2 * d + 1) and sum(q * k for _, q, k in groups) <= n
+        assert all(q >= 1 for _, q, _ in groups)
+        cap = _dn_item_cap(n, d)
+        for count in (_dn_blocked_items, _dn_tiled_items):
+            items = sum(count(t, q, c) * k for t, q, k in groups)
+            assert items <= cap, (count.__name__, n, d, groups, items, cap)
+
+    for d in (2, 3):
+        ns = 2 * d + 1
+        for n in (2, 3, 100, 4097, 65536, 100_000, 130_000, 1 << 20, 10_000_000, 100_000_000):
+            check([(n, n, 1)], n, d)                                         # one group holds the whole database
+            check([(n * ns, n, 1)], n, d)                                    # ... with every target membership
+            check([(2, 1, n)], n, d)                                         # every query with one other target
+            check([(ns, 1, n)], n, d)                                        # ... with 2 d + 1 targets
+            for m in (2, 64, 65, 256, 257, 4096, 16384, 16385, 65537):
+                if m <= n:
+                    check([(m, m, n // m)], n, d)                            # many medium groups, t = q = m
+                    check([(m * ns, m, n // m)], n, d)                       # t >> q
+                    check([(max(2, m // 64), m, n // m)], n, d)              # q >> t
+            big = n * ns // 2
+            check([(big, 1, 1), (ns // 2, 1, n - 1)], n, d)                  # one huge target list, many small groups
+        for _ in range(300):                                                 # random mixes within the sums
+            n = int(rng.integers(2, 3_000_000))
+            left_t, left_q, groups = n * ns, n, []
+            while left_q >= 1 and left_t >= 2:
+                q = min(left_q, [1, int(rng.integers(1, 300)), int(rng.integers(1, 70_000)), left_q][int(rng.integers(0, 4))])
+                t = max(2 if q == 1 else 1, min(left_t, [2, q * ns, int(rng.integers(1, 20_000)), int(rng.integers(64, 100_000))][int(rng.integers(0, 4))]))
+                k = max(1, min(int(rng.integers(1, 5000)), left_q // q, left_t // t))
+                if t * k > left_t or q * k > left_q:
+                    break
+                groups.append((t, q, k))
+                left_t -= t * k
+                left_q -= q * k
+            check(groups, n, d)
+    # what the cap replaced: one window shared by 100 k amplicons at d = 2 made more blocks than the list had room for
+    assert (100_000 + 63) // 64 * ((100_000 + 255) // 256) > _dn_item_cap(100_000, 2)
