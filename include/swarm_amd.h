@@ -303,9 +303,30 @@ int swa_search_begin(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, uint64_
    decomposes uniquely, so the optimal cost alone fixes diff and alignment length), 0 when the
    banded tie-tracking kernel is used.  Same results either way; informational. */
 int swa_search_uses_wavefront(const swa_ctx * ctx);
-/* diffs[i] == the reference's search8/search16 + backtrack value whenever that value
-   is <= d; otherwise some value > d (the caller only tests diff <= d, src/algo.cc:460,
-   554).  scores / alignlengths may be NULL (never read by the reference's caller). */
+/* The kernel form every alignment launch (swa_search_do, the fused scan, the d >= 2 graph) takes for the penalties / d
+   of swa_search_begin and the resident database's longest sequence: with_lengths != 0 for a launch that asks for
+   alignment lengths (swa_search_do with alignlengths != NULL), 0 for one that does not (the scan and graph routes).
+   *saturation = 255 or 65535 (the reference's 8- or 16-bit mode); *lds_bytes = the dynamic LDS a workgroup of the form
+   stages (0 for SWA_FORM_GENERIC, which keeps its state in global scratch: 24 B a thread per nucleotide of the longest
+   sequence, within 2 GiB).  A form whose staging does not fit the device's LDS is never chosen.  Any output may be
+   NULL.  SWA_E_ARG before swa_search_begin, without a database, or when the longest sequence is too long even for
+   the generic kernel (one thread's scratch above 2 GiB, ~89 M nt); every alignment launch then fails the same way. */
+typedef enum {
+  SWA_FORM_WFA16 = 1,          /* k_align_wfa<16>: wavefront, four pairs a wave */
+  SWA_FORM_WFA32 = 2,          /* k_align_wfa<32> */
+  SWA_FORM_BANDED32 = 3,       /* k_align<32, false> */
+  SWA_FORM_BANDED32_LEN = 4,   /* k_align<32, true> */
+  SWA_FORM_BANDED64 = 5,       /* k_align<64, false> */
+  SWA_FORM_BANDED64_LEN = 6,   /* k_align<64, true> */
+  SWA_FORM_GENERIC = 7         /* k_align_generic: one thread a pair, any band, any length */
+} swa_align_form;
+int swa_search_form(swa_ctx * ctx, int with_lengths, int * form, uint32_t * saturation, uint64_t * lds_bytes);
+/* diffs[i] == the reference's nw() value (src/nw.cc, which its search8/search16 + backtrack
+   follow) whenever that value is <= d; otherwise some value > d.  Known exceptions, where the
+   reference's 16-bit search departs from its own nw() and this library does not follow it: some
+   pairs at the default scoring in 16-bit mode (the -d 11 case of tests/test_align_forms_gpu.py, a strict xfail) and gapopen + gapextend
+   above 32767 (-g 30000: the search's 16-bit start value wraps).  The caller only tests diff <= d
+   (src/algo.cc:460, 554).  scores / alignlengths may be NULL (never read by the reference's caller). */
 int swa_search_do(swa_ctx * ctx, uint64_t query_no, uint64_t listlength, const uint64_t * targets,
                   uint64_t * scores, uint64_t * diffs, uint64_t * alignlengths);
 

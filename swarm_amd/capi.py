@@ -76,7 +76,7 @@ EXPORTS = [
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_qgram_build", "swa_qgram_diff",
-    "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_timing_enable", "swa_timing_read",
+    "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
     "swa_d1_result_parent", "swa_d1_result_generation", "swa_d1_light_flags", "swa_d1_graft", "swa_d1_write_swarms",
@@ -639,12 +639,26 @@ class Context:
         self.lib.swa_search_uses_wavefront.argtypes = [C.c_void_p]
         return bool(self.lib.swa_search_uses_wavefront(self.h))
 
-    def search_do(self, query: int, targets: np.ndarray):
+    SEARCH_FORMS = {1: "wfa16", 2: "wfa32", 3: "banded32", 4: "banded32_len", 5: "banded64", 6: "banded64_len", 7: "generic"}
+
+    def search_form(self, with_lengths: bool = True) -> tuple:
+        """(form, saturation, LDS bytes a workgroup) of the alignment kernel a launch takes for the penalties / d of
+        search_begin and the resident database (swa_search_form): form one of SEARCH_FORMS' names; with_lengths as
+        search_do(lengths=...)."""
+        self.lib.swa_search_form.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint64)]
+        form, sat, lds = C.c_int(0), C.c_uint32(0), C.c_uint64(0)
+        self._check(self.lib.swa_search_form(self.h, int(with_lengths), C.byref(form), C.byref(sat), C.byref(lds)))
+        return self.SEARCH_FORMS[form.value], int(sat.value), int(lds.value)
+
+    def search_do(self, query: int, targets: np.ndarray, lengths: bool = True):
+        """(scores, diffs, alignment lengths) of `query` against `targets`; lengths=False asks for the differences alone
+        (NULL scores and lengths: the kernel forms the scan and graph routes launch) and returns (None, diffs, None)."""
         targets = np.ascontiguousarray(targets, dtype=np.uint64)
         m = targets.shape[0]
-        scores = np.zeros(m, dtype=np.uint64)
         diffs = np.zeros(m, dtype=np.uint64)
-        alens = np.zeros(m, dtype=np.uint64)
+        scores = np.zeros(m, dtype=np.uint64) if lengths else None
+        alens = np.zeros(m, dtype=np.uint64) if lengths else None
         self._check(self.lib.swa_search_do(self.h, int(query), m, _ptr(targets), _ptr(scores), _ptr(diffs),
                                            _ptr(alens)))
         return scores, diffs, alens

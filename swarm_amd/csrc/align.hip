@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -592,6 +593,109 @@ __global__ __launch_bounds__(256) void k_widen(const uint32_t * __restrict__ in,
 
 }  // namespace
 
+namespace {
+
+// The form an alignment launch takes (swa_align_form) and what its launch needs.  Chosen from the penalties, d and the
+// database's longest sequence; each form stages the two sequences of every pair of a workgroup in dynamic LDS, sized by
+// the LONGEST sequence, and a form whose staging does not fit the device's LDS is passed over: the generic kernel,
+// whose state lies in global scratch, serves any length.
+struct AlignPlan {
+  int form = SWA_FORM_GENERIC;
+  uint32_t sat = 255;
+  uint64_t W = 0;             // band half-width (the wavefront forms: the diagonals a cost <= T reaches)
+  uint32_t maxwords = 0;      // words per staged sequence
+  uint32_t ring = 0;          // k_align_wfa's history
+  size_t lds = 0;             // dynamic LDS a workgroup
+};
+
+AlignPlan align_plan(const swa_ctx * ctx, bool with_lengths) {
+  const uint64_t mm = ctx->pen_mismatch, go = ctx->pen_gapopen, ge = ctx->pen_gapextend, d = ctx->resolution;
+  AlignPlan p;
+  // 8- or 16-bit arithmetic exactly as set_bit_mode decides (src/algo.cc:96-120)
+  const uint64_t diff_saturation = std::min<uint64_t>(255 / mm, 255 / (go + ge));
+  p.sat = d > diff_saturation ? 65535u : 255u;
+  const uint64_t T = d * std::max<uint64_t>(mm, go + ge);
+  const uint64_t W64 = T / ge + 1;
+  p.W = W64;
+  p.maxwords = ((ctx->db.longest + 31u) >> 5) + 1u;
+  const bool wide = 2 * W64 + 3 > 32;
+  const char * no_wfa = std::getenv("SWA_ALIGN_BANDED");         // test / comparison switch: force the banded kernel
+  if (ctx->wfa_steps != 0 && !wide && ctx->db.longest < 65000u && (no_wfa == nullptr || no_wfa[0] == '0')) {
+    p.ring = std::min<uint32_t>(ctx->wfa_ring != 0 ? ctx->wfa_ring : ctx->wfa_steps, ctx->wfa_steps);
+    // the diagonals a score <= T can reach: a gap of g columns costs open + g extend, so |k| <= (T - open) / extend — the band
+    // of the wavefront kernel (the banded kernels keep the wider T / extend + 1).  Where band + guards fit 16 lanes, a wave
+    // takes four pairs (two, as until round 5, where they need 32)
+    const uint64_t wfa_w = T >= go + ge ? (T - go) / ge : 0;
+    const bool narrow = 2 * wfa_w + 3 <= 16;
+    const size_t per_block = narrow ? 8u : 4u;
+    const size_t lds = sizeof(uint64_t) * (size_t)p.maxwords * 2 * per_block + sizeof(uint16_t) * per_block * (size_t)p.ring * 3 * (narrow ? 16 : 32);
+    if (lds <= ctx->max_lds) {
+      p.form = narrow ? SWA_FORM_WFA16 : SWA_FORM_WFA32;
+      if (narrow) { p.W = wfa_w; }
+      p.lds = lds;
+      return p;
+    }
+  }
+  if (2 * W64 + 3 <= 64) {                                   // band + the two guard lanes fit a group
+    const size_t lds = sizeof(uint64_t) * (size_t)p.maxwords * (2 * (wide ? 4 : 8));
+    if (lds <= ctx->max_lds) {
+      p.form = wide ? (with_lengths ? SWA_FORM_BANDED64_LEN : SWA_FORM_BANDED64)
+                    : (with_lengths ? SWA_FORM_BANDED32_LEN : SWA_FORM_BANDED32);
+      p.lds = lds;
+      return p;
+    }
+  }
+  p.form = SWA_FORM_GENERIC;
+  if (p.W > 0x3FFFFFFF) { p.W = 0x3FFFFFFF; }
+  return p;
+}
+
+// k_align_generic's scratch: six u32 planes of (longest + 1) columns a thread.  Its grid-stride loop serves any number of
+// threads, so the threads are cut (from one a pair, at most 65 536) until the scratch fits kGenericScratch; 0 when not
+// even one thread's does: no form serves the database.
+constexpr uint64_t kGenericScratch = 2ull << 30;
+uint64_t generic_threads(const swa_ctx * ctx, uint32_t max_count) {
+  const uint64_t per_thread = 6ull * ((uint64_t)ctx->db.longest + 1u) * sizeof(uint32_t);
+  if (per_thread > kGenericScratch) { return 0; }
+  uint64_t nthreads = max_count < 65536 ? (((uint64_t)max_count + 63) / 64) * 64 : 65536;
+  if (nthreads < 64) { nthreads = 64; }
+  while (nthreads > 1 && nthreads * per_thread > kGenericScratch) { nthreads /= 2; }
+  return nthreads;
+}
+
+int fail_unservable(swa_ctx * ctx) {
+  return swa_fail_msg(ctx, SWA_E_ARG, "alignment: the longest sequence (" + std::to_string(ctx->db.longest) +
+                      " nt) needs more scratch than any alignment kernel may use");
+}
+
+// Above the 64 KB a kernel gets unasked, its dynamic-LDS attribute is raised to the device's maximum: once per context and
+// form (the attribute belongs to the function on a device; swa_multi_* runs a context per GPU in one process)
+int align_lds_opt_in(swa_ctx * ctx, const AlignPlan & p, const void * fn) {
+  if (p.lds <= 65536 || (ctx->align_lds_opt_in & (1u << p.form)) != 0u) { return SWA_OK; }
+  SWA_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds));
+  ctx->align_lds_opt_in |= 1u << p.form;
+  return SWA_OK;
+}
+
+template <typename Args>
+int align_launch_staged(swa_ctx * ctx, const AlignPlan & p, void (*fn)(Args), uint64_t blocks, unsigned threads, const Args & args) {
+  SWA_TRY(align_lds_opt_in(ctx, p, reinterpret_cast<const void *>(fn)));
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(threads), p.lds, ctx->stream, args);
+  return SWA_OK;
+}
+
+}  // namespace
+
+extern "C" int swa_search_form(swa_ctx * ctx, int with_lengths, int * form, uint32_t * saturation, uint64_t * lds_bytes) {
+  if (ctx == nullptr || !ctx->search_ready || ctx->db.n == 0) { return SWA_E_ARG; }
+  const AlignPlan p = align_plan(ctx, with_lengths != 0);
+  if (p.form == SWA_FORM_GENERIC && generic_threads(ctx, 1) == 0) { return fail_unservable(ctx); }
+  if (form != nullptr) { *form = p.form; }
+  if (saturation != nullptr) { *saturation = p.sat; }
+  if (lds_bytes != nullptr) { *lds_bytes = p.lds; }
+  return SWA_OK;
+}
+
 // Enqueue the alignment of `query` against d_targets[0 .. count) on the context's stream.
 // count = *d_count (device) when d_count != nullptr, bounded by max_count; d_queries != nullptr
 // gives one query per pair (batched sub-seeds) instead of the single `query`; all pointers
@@ -599,13 +703,7 @@ __global__ __launch_bounds__(256) void k_widen(const uint32_t * __restrict__ in,
 int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, const uint32_t * d_targets,
                      const uint32_t * d_count, uint32_t max_count, uint32_t * d_diffs, uint32_t * d_scores,
                      uint32_t * d_alnlens) {
-  const uint64_t mm = ctx->pen_mismatch, go = ctx->pen_gapopen, ge = ctx->pen_gapextend, d = ctx->resolution;
-  // 8- or 16-bit arithmetic exactly as set_bit_mode decides (src/algo.cc:96-120)
-  const uint64_t diff_saturation = std::min<uint64_t>(255 / mm, 255 / (go + ge));
-  const uint32_t sat = d > diff_saturation ? 65535u : 255u;
-  const uint64_t T = d * std::max<uint64_t>(mm, go + ge);
-  const uint64_t W64 = T / ge + 1;
-  const bool generic = 2 * W64 + 3 > 64;                     // band + the two guard lanes must fit a group
+  const AlignPlan p = align_plan(ctx, d_alnlens != nullptr);
   AlignArgs a{};
   a.seqs = ctx->db.seqs; a.seq_off = ctx->db.seq_off; a.seqlen = ctx->db.seqlen;
   a.query = query;
@@ -614,52 +712,42 @@ int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, 
   a.ntargets_dev = d_count;
   a.targets = d_targets;
   a.diffs = d_diffs; a.scores = d_scores; a.alnlens = d_alnlens;
-  a.mismatch = (uint32_t)mm; a.gapopen = (uint32_t)go; a.gapextend = (uint32_t)ge;
-  a.sat = sat;
-  a.W = (int)W64;
-  a.maxwords = ((ctx->db.longest + 31u) >> 5) + 1u;
-  const bool wide = 2 * W64 + 3 > 32;
-  const int groups = wide ? 4 : 8;
-  uint64_t blocks = ((uint64_t)max_count + groups - 1) / groups;
+  a.mismatch = (uint32_t)ctx->pen_mismatch; a.gapopen = (uint32_t)ctx->pen_gapopen; a.gapextend = (uint32_t)ctx->pen_gapextend;
+  a.sat = p.sat;
+  a.W = (int)p.W;
+  a.maxwords = p.maxwords;
   const uint64_t cap = uint64_t(ctx->num_cus) * 8;
-  if (blocks > cap) { blocks = cap; }
-  if (blocks < 1) { blocks = 1; }
-  const size_t lds = sizeof(uint64_t) * (size_t)a.maxwords * (2 * groups);
-  const char * no_wfa = std::getenv("SWA_ALIGN_BANDED");         // test / comparison switch: force the banded kernel
-  if (ctx->wfa_steps != 0 && !wide && ctx->db.longest < 65000u && (no_wfa == nullptr || no_wfa[0] == '0')) {
+  if (p.form == SWA_FORM_WFA16 || p.form == SWA_FORM_WFA32) {
     WfaArgs w{};
     w.a = a;
     w.steps = static_cast<const swa_wfa_step *>(ctx->d_wfa.ptr);
     w.nsteps = ctx->wfa_steps;
-    w.ring = std::min<uint32_t>(ctx->wfa_ring != 0 ? ctx->wfa_ring : ctx->wfa_steps, ctx->wfa_steps);
-    // the diagonals a score <= T can reach: a gap of g columns costs open + g extend, so |k| <= (T - open) / extend — the band
-    // of the wavefront kernel (the banded kernels keep the wider T / extend + 1).  Where band + guards fit 16 lanes, a wave
-    // takes four pairs (two, as until round 5, where they need 32)
-    const uint64_t wfa_w = T >= go + ge ? (T - go) / ge : 0;
-    const bool narrow = 2 * wfa_w + 3 <= 16;
-    const uint32_t per_block = narrow ? 8u : 4u;
-    if (narrow) { w.a.W = (int)wfa_w; }
+    w.ring = p.ring;
+    const uint32_t per_block = p.form == SWA_FORM_WFA16 ? 8u : 4u;
     uint64_t wblocks = ((uint64_t)max_count + per_block - 1) / per_block;
     if (wblocks > 2 * cap) { wblocks = 2 * cap; }
     if (wblocks < 1) { wblocks = 1; }
-    const size_t wlds = sizeof(uint64_t) * (size_t)a.maxwords * 2 * per_block + sizeof(uint16_t) * per_block * (size_t)w.ring * 3 * (narrow ? 16 : 32);
-    if (narrow) { hipLaunchKernelGGL(k_align_wfa<16>, dim3((unsigned)wblocks), dim3(128), wlds, ctx->stream, w); }
-    else { hipLaunchKernelGGL(k_align_wfa<32>, dim3((unsigned)wblocks), dim3(128), wlds, ctx->stream, w); }
-  } else if (generic) {
-    a.W = W64 > 0x3FFFFFFF ? 0x3FFFFFFF : (int)W64;
+    if (p.form == SWA_FORM_WFA16) { SWA_TRY(align_launch_staged(ctx, p, k_align_wfa<16>, wblocks, 128, w)); }
+    else { SWA_TRY(align_launch_staged(ctx, p, k_align_wfa<32>, wblocks, 128, w)); }
+  } else if (p.form == SWA_FORM_GENERIC) {
     const uint32_t qcap = ctx->db.longest + 1u;
-    uint64_t nthreads = max_count < 65536 ? (((uint64_t)max_count + 63) / 64) * 64 : 65536;
-    if (nthreads < 64) { nthreads = 64; }
-    while (nthreads > 64 && nthreads * 6ull * qcap * sizeof(uint32_t) > (2ull << 30)) { nthreads /= 2; }
+    const uint64_t nthreads = generic_threads(ctx, max_count);
+    if (nthreads == 0) { return fail_unservable(ctx); }
     SWA_TRY(swa_reserve(ctx, ctx->d_queue, nthreads * 6ull * qcap * sizeof(uint32_t)));
     hipLaunchKernelGGL(k_align_generic, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, ctx->stream, a,
                        static_cast<uint32_t *>(ctx->d_queue.ptr), (uint32_t)nthreads, qcap);
-  } else if (d_alnlens != nullptr) {
-    if (wide) { hipLaunchKernelGGL((k_align<64, true>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); }
-    else { hipLaunchKernelGGL((k_align<32, true>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); }
   } else {
-    if (wide) { hipLaunchKernelGGL((k_align<64, false>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); }
-    else { hipLaunchKernelGGL((k_align<32, false>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); }
+    const bool wide = p.form == SWA_FORM_BANDED64 || p.form == SWA_FORM_BANDED64_LEN;
+    const int groups = wide ? 4 : 8;
+    uint64_t blocks = ((uint64_t)max_count + groups - 1) / groups;
+    if (blocks > cap) { blocks = cap; }
+    if (blocks < 1) { blocks = 1; }
+    switch (p.form) {
+      case SWA_FORM_BANDED64_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align<64, true>, blocks, 256, a)); break;
+      case SWA_FORM_BANDED32_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align<32, true>, blocks, 256, a)); break;
+      case SWA_FORM_BANDED64: SWA_TRY(align_launch_staged(ctx, p, k_align<64, false>, blocks, 256, a)); break;
+      default: SWA_TRY(align_launch_staged(ctx, p, k_align<32, false>, blocks, 256, a)); break;
+    }
   }
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;

@@ -3,6 +3,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 
@@ -61,6 +62,7 @@ extern "C" int swa_ctx_create(int device, void * stream, swa_ctx ** out) {
   auto * ctx = new swa_ctx();
   ctx->device = device;
   ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  ctx->max_lds = std::max<size_t>(65536, std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin));
   if (stream != nullptr) {
     ctx->stream = static_cast<hipStream_t>(stream);
   } else {

@@ -33,6 +33,7 @@ struct swa_ctx {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int num_cus = 256;
+  size_t max_lds = 65536;        // the most dynamic LDS a workgroup of this device can be given (opted in per kernel)
   std::string err;
 
   // optional per-kernel timing (HIP events on `stream`)
@@ -103,6 +104,7 @@ struct swa_ctx {
   bool search_ready = false;
   uint32_t wfa_steps = 0;        // > 0: the wavefront alignment kernel is exact for the penalties / d in use
   uint32_t wfa_ring = 0;         // steps of history k_align_wfa keeps (the furthest a step looks back + 1)
+  uint32_t align_lds_opt_in = 0; // the align kernels (bit = swa_align_form) whose dynamic-LDS attribute is set to max_lds
   swa_dbuf d_wfa;
 
   // fused d >= 2 scan state (scan.hip)

@@ -129,3 +129,61 @@ def test_network_against_reference_binary(tmp_path, n, length, seed, ncb):
         r = S.run_ref_swarm(["-d", "1", "-j", net, "-o", "/dev/null", "-l", "/dev/null"] + (["-n"] if ncb else []) + [fa])
         assert r.returncode == 0, r.stderr
         assert got == net.read_bytes()
+
+
+# the scorings the alignment-form tests (test_align_forms_gpu.py) take the oracle as ground truth at: gapopen = 0, one
+# gap opening at most in 16 bits, T = 255 exactly, a mismatch penalty of 255 and a representative of every kernel form
+_NEW_SCORINGS = [(4, 0, 3), (8, 0, 9), (2, 0, 1), (18, 60000, 13), (4, 14, 3), (12, 10, 19), (4, 2, 15), (4, 2, 1),
+                 (18, 24, 13), (255, 1, 2)]
+
+
+@pytest.mark.skipif(not S.have_reference(), reason="compiled reference not available on this box")
+@pytest.mark.parametrize("scoring", _NEW_SCORINGS, ids=[f"{m}-{o}-{e}" for m, o, e in _NEW_SCORINGS])
+def test_oracle_nw_at_new_scorings(scoring):
+    """orc_nw_diff against the reference's own nw() (ref_nw): differences and alignment length, on related pairs over
+    ACGT and over two letters, 1 to ~2 000 nt."""
+    ref = C.CDLL(str(S.REF_DIR / "libswarmref.so"))
+    ref.ref_nw.restype = C.c_uint64
+    lib = S.oracle()
+    mm, go, ge = scoring
+    rng = np.random.default_rng(sum(scoring))
+    for trial in range(60):
+        L = int(rng.integers(1, 2100)) if trial % 6 == 0 else int(rng.integers(1, 320))
+        alpha = list("ACGT" if trial % 2 else "AC")
+        a = "".join(rng.choice(alpha, size=L))
+        b = list(a)
+        for _ in range(int(rng.integers(0, 12))):
+            p = int(rng.integers(0, len(b) + 1))
+            u = rng.random()
+            if u < 0.5 and p < len(b):
+                b[p] = alpha[int(rng.integers(0, len(alpha)))]
+            elif u < 0.75 and p < len(b) and len(b) > 1:
+                del b[p]
+            else:
+                b.insert(p, alpha[int(rng.integers(0, len(alpha)))])
+        b = "".join(b)
+        wa, wb = S.pack_seq(a.encode()), S.pack_seq(b.encode())
+        alen, score = C.c_uint64(0), C.c_uint64(0)
+        got = lib.orc_nw_diff(wb.ctypes.data_as(S.u64p), len(b), wa.ctypes.data_as(S.u64p), len(a), mm, go, ge,
+                              C.byref(alen), C.byref(score))
+        ral, buf = C.c_uint64(0), C.create_string_buffer(len(a) + len(b) + 8)
+        want = ref.ref_nw(wb.ctypes.data_as(C.c_char_p), C.c_uint64(len(b)), wa.ctypes.data_as(C.c_char_p),
+                          C.c_uint64(len(a)), C.c_int64(mm), C.c_uint64(go), C.c_uint64(ge), buf, C.byref(ral))
+        assert (got, alen.value) == (want, ral.value), (scoring, a, b)
+        assert score.value == _path_cost(buf.raw[:ral.value][::-1], b, a, mm, go, ge), (scoring, a, b)
+
+
+def _path_cost(ops: bytes, d: str, q: str, mm: int, go: int, ge: int) -> int:
+    """The cost of the reference's own alignment path (ref_nw's operations, first column first): mismatches, and
+    gapopen + length * gapextend per gap run.  'I' consumes a nucleotide of d, 'D' one of q, 'M' one of each."""
+    cost, i, j, prev = 0, 0, 0, None
+    for op in ops:
+        if op == ord("M"):
+            cost += mm if d[i] != q[j] else 0
+            i, j = i + 1, j + 1
+        else:
+            cost += ge + (go if op != prev else 0)
+            i, j = (i + 1, j) if op == ord("I") else (i, j + 1)
+        prev = op
+    assert (i, j) == (len(d), len(q))
+    return cost
