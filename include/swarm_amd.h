@@ -384,7 +384,12 @@ int swa_nw_batch_totals(const swa_ctx * ctx, uint64_t * out4);
      diffs[e] = that diff (the reference's value, src/algo.cc:460, 554).
    The caller's greedy loop then needs no further device call.  Candidate pairs come from d + 1 disjoint
    windows per sequence (an alignment with <= d differences leaves one of them intact, shifted by at most
-   d), which every sequence must have room for: swa_dn_graph_supported != 0 (else use swa_scan_*).
+   d).  A sequence without room for them (fewer than 16 (d + 1) nucleotides: "short") joins no window group;
+   its pairs are found by comparing it with every sequence whose length differs by at most d (no pair within
+   d differences has a larger length difference).  That part is quadratic in the short sequences, so the
+   number B of its candidate pairs — known from the count of sequences per length — is capped at 16 n + 2^20
+   (test hook: SWA_DN_BRUTE_CAP): swa_dn_graph_supported != 0 when d <= 8 and B is within the cap (else use
+   swa_scan_*; swa_dn_graph then fails with SWA_E_ARG).
    Requires swa_qgram_build and swa_search_begin.  Buffers as swa_d1_network: offsets[n + 1] always
    filled, *total = entries needed, SWA_E_CAPACITY when total > cap (call again with room: nothing is
    recomputed). */
@@ -429,8 +434,9 @@ int  swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, uint64_t l
 /* ---- d >= 2 on several GPUs (second paragraph) --------------------------------------------------
    Replaces the scan fan-out of src/scan.cc:221-256 under the loop of src/algo.cc:505-602.  swa_dn_set_ownership(rank,
    world): this context makes only the window groups of swa_dn_graph whose key maps to `rank`; a pair is reported
-   through the first window it shares, and that window's group lives on one rank, so over all ranks every pair of the
-   graph is found exactly once.  swa_multi_dn_begin = swa_qgram_build + swa_search_begin on every rank;
+   through the first window it shares, and that window's group lives on one rank; a pair with a short member is
+   reported by the rank that owns the short sequence emitting it (id modulo world; of two short ones the lower id
+   emits); so over all ranks every pair of the graph is found exactly once.  swa_multi_dn_begin = swa_qgram_build + swa_search_begin on every rank;
    swa_multi_dn_graph = swa_dn_graph: every rank finds and aligns its share, the accepted (query, target, diff)
    triples travel to rank 0 (RCCL send / receive over xGMI, device-to-device copies for ranks sharing a GPU), which
    sorts them into the CSR; same buffers and capacity protocol as swa_dn_graph. */

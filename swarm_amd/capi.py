@@ -988,8 +988,9 @@ class MultiContext:
             cap = int(total.value)
 
     def dn_graph(self, d: int, no_cluster_breaking: bool = False, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
-        """swa_multi_dn_begin + swa_multi_dn_graph: (offsets, neighbours, diffs) of the whole d >= 2 graph, or None when a
-        sequence is too short for d + 1 windows."""
+        """swa_multi_dn_begin + swa_multi_dn_graph: (offsets, neighbours, diffs) of the whole d >= 2 graph, or None when the
+        graph route does not serve the database: d > 8, or more candidate pairs with a sequence too short for d + 1
+        windows than the brute-force part takes (16 n + 2^20; SWA_DN_BRUTE_CAP)."""
         lib = self.lib
         lib.swa_multi_dn_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
         lib.swa_multi_dn_graph_supported.argtypes = [C.c_void_p]

@@ -21,9 +21,17 @@
 // aligned by the B4 kernels (align.hip) in the direction(s) the abundance rule allows, and the
 // accepted (query, target, diff) triples are sorted into a CSR (rocPRIM radix sort).
 //
-// Applies when every sequence holds d + 1 windows of 32 (or 16) nucleotides; otherwise the fused
-// scan of scan.hip serves (swa_dn_graph_supported).  HBM traffic: group bookkeeping (a few tens of
-// bytes per amplicon and window) + the members' sequences and signatures, mostly from L2.
+// The windows need room: a sequence is SHORT when it has fewer than 16 (d + 1) nucleotides.  Short sequences stay
+// out of the groups, as targets and as queries, and the window length (32 or 16) is chosen from the shortest LONG
+// sequence.  A pair with a short member has a length difference of at most d like every other pair, so the partner of
+// a short sequence of length L has L - d .. L + d nucleotides: k_dg_brute compares every short sequence with all of
+// those (the sequences below 16 (d + 1) + d, sorted by length once), the same q-gram bound, into the same pair list.
+// The two parts are disjoint (a pair has a short member or it has none) and together complete; everything behind the
+// pair list does not know which part a pair came from.  The brute-force part is quadratic in the short sequences, so
+// the number B of its (short, partner) candidates — known from the count of sequences per length before anything is
+// launched — is capped (brute_cap): beyond it, and for d > 8, the fused scan of scan.hip serves
+// (swa_dn_graph_supported).  HBM traffic: group bookkeeping (a few tens of bytes per amplicon and window) + the
+// members' sequences and signatures, mostly from L2.
 #include "swa_internal.h"
 
 #include <rocprim/rocprim.hpp>
@@ -68,6 +76,7 @@ struct GroupArgs {
   const uint64_t * seq_off;
   const uint32_t * seqlen;
   uint32_t n, d, k, wlen;        // window k at offset k * wlen
+  uint32_t short_below;          // sequences with fewer nucleotides join no group (k_dg_brute finds their pairs)
   unsigned long long * keys;
   uint32_t * cnt_t, * cnt_q;
   uint64_t amask;
@@ -84,18 +93,19 @@ __global__ __launch_bounds__(256) void k_dg_clear(unsigned long long * keys, uin
   }
 }
 
-// every amplicon is a target under its window k at the shifts -d .. +d
+// every amplicon (that is not short) is a target under its window k at the shifts -d .. +d
 __global__ __launch_bounds__(256) void k_dg_targets(const GroupArgs a) {
   const uint32_t ns = 2u * a.d + 1u;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
     const uint32_t len = a.seqlen[i];
+    const bool is_short = len < a.short_below;
     const uint64_t * s = a.seqs + a.seq_off[i];
     uint64_t seen[kMaxShifts];
     for (uint32_t j = 0; j < ns; ++j) {
       uint32_t slot = kEmpty;
       const int64_t pos = (int64_t)a.k * a.wlen + (int64_t)j - (int64_t)a.d;
       seen[j] = kKeyEmpty;
-      if (pos >= 0 && (uint64_t)pos + a.wlen <= len) {
+      if (!is_short && pos >= 0 && (uint64_t)pos + a.wlen <= len) {
         const uint64_t key = window_key(window(s, (uint32_t)pos, a.wlen), a.k);
         bool repeat = false;                                  // (low complexity: the same window at two shifts — one membership)
         for (uint32_t q = 0; q < j; ++q) { repeat = repeat || seen[q] == key; }
@@ -122,6 +132,7 @@ __global__ __launch_bounds__(256) void k_dg_targets(const GroupArgs a) {
 // ... and a query under the unshifted window (its own target entry at shift 0 made the group)
 __global__ __launch_bounds__(256) void k_dg_queries(const GroupArgs a) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
+    if (a.seqlen[i] < a.short_below) { a.qslot[i] = kEmpty; continue; }      // (a short sequence has no window k to look up)
     const uint64_t key = window_key(window(a.seqs + a.seq_off[i], a.k * a.wlen, a.wlen), a.k);
     uint64_t idx = mix64(key) & a.amask;
     uint32_t slot = kEmpty;
@@ -450,6 +461,122 @@ __global__ __launch_bounds__(256) void k_dg_pairs_lds(const PairArgs a) {
   if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
 }
 
+// ---- the pairs with a short member -------------------------------------------------------------------------------
+// The ids of all sequences below `below` nucleotides (16 (d + 1) + d: the short ones and what they can pair with) in
+// the order of their lengths: start[L] = first entry of length L (from the host's counts), cursor[L] = entries placed.
+// The lanes of a wave that hold the same length share one atomic.
+__global__ __launch_bounds__(256) void k_dg_short_sort(const uint32_t * __restrict__ seqlen, uint32_t n, uint32_t below,
+                                                       const uint32_t * __restrict__ start, uint32_t * cursor,
+                                                       uint32_t * __restrict__ sorted, uint32_t cap) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t lane_lt = (1ull << lane) - 1ull;
+  const uint64_t first = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63ull;     // wave-uniform
+  for (uint64_t i0 = first; i0 < n; i0 += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i = i0 + (uint64_t)lane;
+    const uint32_t len = i < n ? seqlen[i] : below;
+    const bool near = len < below;
+    uint64_t todo = __ballot(near);
+    while (todo != 0ull) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const uint32_t L = (uint32_t)__shfl((int)len, leader, 64);
+      const uint64_t m = __ballot(near && len == L);
+      uint32_t base = 0;
+      if (lane == leader) { base = atomicAdd(&cursor[L], (uint32_t)__popcll(m)); }
+      base = (uint32_t)__shfl((int)base, leader, 64);
+      if (near && len == L) {
+        const uint32_t at = start[L] + base + (uint32_t)__popcll(m & lane_lt);
+        if (at < cap) { sorted[at] = (uint32_t)i; }
+      }
+      todo &= ~m;
+    }
+  }
+}
+
+struct BruteArgs {
+  const uint32_t * seqlen;
+  const ulonglong2 * sigs;       // q-gram signatures, 8 x 16 bytes per amplicon
+  const uint32_t * sorted;       // k_dg_short_sort's list: entries [0, nshort) are the short sequences
+  const uint32_t * start;        // [short_below + d + 1]
+  uint32_t nshort, short_below, d;
+  uint32_t tile, ntiles;         // a short sequence's partners are dealt to ntiles waves, `tile` (a multiple of 64) each
+  uint32_t owner_rank, owner_world;   // world > 1: only the short sequences with id % world == rank emit here
+  unsigned long long * pairs;    // (lower id << 32) | higher id, as k_dg_pairs
+  unsigned long long * counters; // [0] pairs [1] q-gram comparisons
+  uint64_t pair_cap;
+};
+
+// One wave per short sequence s and tile of its partners — the sequences of len(s) - d .. len(s) + d nucleotides, a
+// contiguous range of the sorted list: the signature of s in (scalar) registers, one partner per lane and turn.  A pair
+// of two short sequences is emitted by the one with the lower id.  The q-gram bound and the staging of the survivors
+// are k_dg_pairs'.
+__global__ __launch_bounds__(256) void k_dg_brute(const BruteArgs a) {
+  __shared__ unsigned long long stage_all[4][kStage];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned long long * stage = stage_all[wave];
+  uint32_t nstage = 0;
+  unsigned long long compared = 0;
+  const uint64_t lane_lt = (1ull << lane) - 1ull;
+  auto flush = [&]() {
+    wave_lds_sync();
+    unsigned long long base = 0;
+    if (lane == 0) { base = atomicAdd(&a.counters[0], (unsigned long long)nstage); }
+    base = shfl_u64(base, 0);
+    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
+    nstage = 0;
+    wave_lds_sync();
+  };
+  const uint64_t nitems = (uint64_t)a.nshort * a.ntiles;
+  const uint64_t nwaves = (uint64_t)gridDim.x * 4u;
+  const uint32_t top = a.short_below + a.d;                  // start[] has top + 1 entries
+  for (uint64_t it = (uint64_t)blockIdx.x * 4u + (uint64_t)wave; it < nitems; it += nwaves) {
+    const uint32_t si = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(it / a.ntiles));
+    const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(it % a.ntiles));
+    const uint32_t s = a.sorted[si];
+    if (a.owner_world != 1u && s % a.owner_world != a.owner_rank) { continue; }
+    const uint32_t len = a.seqlen[s];
+    const uint32_t lo = len > a.d ? len - a.d : 0u, hi = min(len + a.d + 1u, top);
+    const uint64_t r0 = (uint64_t)a.start[lo] + (uint64_t)tile * a.tile;
+    const uint64_t r1 = min((uint64_t)a.start[hi], r0 + a.tile);
+    if (r0 >= r1) { continue; }
+    uint64_t ssig[16];
+    {
+      const ulonglong2 * gs = a.sigs + (uint64_t)s * 8u;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) { const ulonglong2 x = gs[w]; ssig[2 * w] = x.x; ssig[2 * w + 1] = x.y; }
+    }
+    for (uint64_t r = r0; r < r1; r += 64u) {
+      const uint64_t at = r + (uint64_t)lane;
+      bool take = false;
+      uint32_t p = 0;
+      if (at < r1) {
+        p = a.sorted[at];
+        // (entries below nshort are short themselves: that pair belongs to the lower id of the two)
+        if (p != s && !(at < a.nshort && p < s)) {
+          // q-gram bound (qgram_diff, src/qgram.cc:68-96): ceil(popcount(sig_s ^ sig_p) / 10) <= d
+          const ulonglong2 * gp = a.sigs + (uint64_t)p * 8u;
+          uint32_t pop = 0;
+#pragma unroll
+          for (int w = 0; w < 8; ++w) {
+            const ulonglong2 y = gp[w];
+            pop += (uint32_t)__popcll(ssig[2 * w] ^ y.x) + (uint32_t)__popcll(ssig[2 * w + 1] ^ y.y);
+          }
+          ++compared;
+          take = (pop + 9u) / 10u <= a.d;
+        }
+      }
+      const uint64_t m = __ballot(take);
+      if (m != 0ull) {
+        if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)min(s, p) << 32) | max(s, p); }
+        nstage += (uint32_t)__popcll(m);
+        if (nstage > kStage - 64u) { flush(); }
+      }
+    }
+  }
+  if (nstage != 0u) { flush(); }
+  for (int o = 32; o > 0; o >>= 1) { compared += shfl_u64(compared, lane ^ o); }
+  if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
+}
+
 // the alignments a pair needs: (a, b) with a < b always (db order is abundance-descending, so b's
 // abundance is not the larger one); (b, a) as well when the abundance rule allows it: equal abundances,
 // or no rule (-n).  Queries / targets of the second kind are appended behind the first npairs entries.
@@ -610,11 +737,20 @@ __global__ __launch_bounds__(256) void k_dg_parent_diffs(const uint64_t * __rest
   }
 }
 
-__global__ __launch_bounds__(256) void k_dg_shortest(const uint32_t * __restrict__ seqlen, uint32_t n, uint32_t * out) {
+// how many sequences have each length below SWA_DN_HIST_LEN (out[L]) and the shortest of the others (out[SWA_DN_HIST_LEN])
+__global__ __launch_bounds__(256) void k_dg_lengths(const uint32_t * __restrict__ seqlen, uint32_t n, uint32_t * out) {
+  __shared__ uint32_t hist[SWA_DN_HIST_LEN];
+  for (uint32_t i = threadIdx.x; i < SWA_DN_HIST_LEN; i += blockDim.x) { hist[i] = 0u; }
+  __syncthreads();
   uint32_t mn = 0xFFFFFFFFu;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { mn = min(mn, seqlen[i]); }
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t len = seqlen[i];
+    if (len < SWA_DN_HIST_LEN) { atomicAdd(&hist[len], 1u); } else { mn = min(mn, len); }
+  }
   for (int o = 32; o > 0; o >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64)); }
-  if ((threadIdx.x & 63u) == 0u) { atomicMin(out, mn); }
+  if ((threadIdx.x & 63u) == 0u && mn != 0xFFFFFFFFu) { atomicMin(out + SWA_DN_HIST_LEN, mn); }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < SWA_DN_HIST_LEN; i += blockDim.x) { if (hist[i] != 0u) { atomicAdd(out + i, hist[i]); } }
 }
 
 struct widen_u32 {
@@ -627,22 +763,64 @@ int grid_for(const swa_ctx * ctx, uint64_t items) {
   return (int)std::max<uint64_t>(1, std::min(blocks, cap));
 }
 
-// window length for this database and d: 32, 16, or 0 (no room for d + 1 windows in the shortest sequence)
-int window_length(swa_ctx * ctx, uint32_t d, uint32_t * out) {
+// d_frole (the fastidious pair route's buffer, idle at d >= 2) in u32 words: the length counts as k_dg_lengths leaves
+// them, then what the brute-force part reads — start[] and cursor[] per length and the ids sorted by length
+constexpr uint32_t kShortStart = 160, kShortCursor = 320, kShortSorted = 480;
+
+// what the database's lengths decide for this d
+struct dn_plan {
+  uint32_t wlen = 0;             // window length: 32, 16, or 0 (the graph route does not serve this database)
+  uint32_t short_below = 0;      // 16 (d + 1): sequences below it are short
+  uint32_t nshort = 0, nnear = 0;   // short sequences; sequences below short_below + d (what a short one can pair with)
+  uint32_t max_range = 0;        // most partners of one short sequence
+  uint64_t brute = 0;            // B: (short, partner) candidates, every pair once
+};
+
+// the cap on B: the size the pair list starts with (every candidate may survive the q-gram bound), or SWA_DN_BRUTE_CAP
+uint64_t brute_cap(uint32_t n) {
+  const char * env = std::getenv("SWA_DN_BRUTE_CAP");
+  if (env != nullptr && env[0] != '\0') { return std::strtoull(env, nullptr, 10); }
+  return 16ull * n + (1ull << 20);
+}
+
+int window_length(swa_ctx * ctx, uint32_t d, dn_plan * out) {
   if (ctx->dn_shortest == 0) {
-    SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
-    auto * slot = static_cast<uint32_t *>(ctx->d_flags.ptr) + 10;
-    SWA_HIP(ctx, hipMemsetAsync(slot, 0xFF, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_dg_shortest, dim3(grid_for(ctx, ctx->db.n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, slot);
-    uint32_t mn = 0;
-    SWA_HIP(ctx, hipMemcpyAsync(&mn, slot, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SWA_TRY(swa_reserve(ctx, ctx->d_frole, (uint64_t)kShortSorted * sizeof(uint32_t)));
+    auto * slot = static_cast<uint32_t *>(ctx->d_frole.ptr);
+    SWA_HIP(ctx, hipMemsetAsync(slot, 0, SWA_DN_HIST_LEN * sizeof(uint32_t), ctx->stream));
+    SWA_HIP(ctx, hipMemsetAsync(slot + SWA_DN_HIST_LEN, 0xFF, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(k_dg_lengths, dim3(grid_for(ctx, ctx->db.n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, slot);
+    uint32_t got[SWA_DN_HIST_LEN + 1];
+    SWA_HIP(ctx, hipMemcpyAsync(got, slot, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t mn = got[SWA_DN_HIST_LEN];
+    for (uint32_t L = SWA_DN_HIST_LEN; L-- > 0;) { ctx->dn_len_hist[L] = got[L]; if (got[L] != 0u) { mn = L; } }
+    ctx->dn_shortest_rest = got[SWA_DN_HIST_LEN];
     ctx->dn_shortest = mn;
   }
-  *out = 0;
+  *out = dn_plan();
   if (2u * d + 1u > (uint32_t)kMaxShifts) { return SWA_OK; }
-  if (ctx->dn_shortest >= 32u * (d + 1u)) { *out = 32; }
-  else if (ctx->dn_shortest >= 16u * (d + 1u)) { *out = 16; }
+  const uint32_t * hist = ctx->dn_len_hist;
+  const uint32_t T = 16u * (d + 1u), top = T + d;              // (d <= 8: top <= SWA_DN_HIST_LEN)
+  out->short_below = T;
+  uint32_t shortest_long = ctx->dn_shortest_rest;
+  for (uint32_t L = SWA_DN_HIST_LEN; L-- > T;) { if (hist[L] != 0u) { shortest_long = L; } }
+  // (no long sequence at all: the windows find nothing whatever their length)
+  out->wlen = shortest_long >= 32u * (d + 1u) && shortest_long != 0xFFFFFFFFu ? 32u : 16u;
+  for (uint32_t L = 0; L < top; ++L) { out->nnear += hist[L]; if (L < T) { out->nshort += hist[L]; } }
+  if (out->nshort == 0) { return SWA_OK; }
+  // B: a short sequence of length L meets every other sequence of L - d .. L + d nucleotides; two short ones meet once
+  for (uint32_t L = 0; L < T; ++L) {
+    if (hist[L] == 0u) { continue; }
+    uint64_t range = 0, later = 0;
+    for (uint32_t M = L > d ? L - d : 0u; M <= L + d; ++M) {
+      range += hist[M];
+      if (M > L) { later += hist[M]; }
+    }
+    out->max_range = (uint32_t)std::max<uint64_t>(out->max_range, range);
+    out->brute += (uint64_t)hist[L] * (hist[L] - 1u) / 2u + (uint64_t)hist[L] * later;
+  }
+  if (out->brute > brute_cap(ctx->db.n)) { out->wlen = 0; }
   return SWA_OK;
 }
 
@@ -650,9 +828,9 @@ int window_length(swa_ctx * ctx, uint32_t d, uint32_t * out) {
 
 extern "C" int swa_dn_graph_supported(swa_ctx * ctx) {
   if (ctx == nullptr || !ctx->search_ready || ctx->db.n == 0) { return 0; }
-  uint32_t wlen = 0;
-  if (window_length(ctx, (uint32_t)ctx->resolution, &wlen) != SWA_OK) { return 0; }
-  return wlen != 0 ? 1 : 0;
+  dn_plan plan;
+  if (window_length(ctx, (uint32_t)ctx->resolution, &plan) != SWA_OK) { return 0; }
+  return plan.wlen != 0 ? 1 : 0;
 }
 
 // the search itself: the sorted (query << 32 | target, diff) list of this context's share of the graph, left in HBM
@@ -664,8 +842,9 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
   const uint32_t d = (uint32_t)ctx->resolution;
-  uint32_t wlen = 0;
-  SWA_TRY(window_length(ctx, d, &wlen));
+  dn_plan plan;
+  SWA_TRY(window_length(ctx, d, &plan));
+  const uint32_t wlen = plan.wlen;
   if (wlen == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_dn_graph: a sequence is too short for d + 1 windows (use the scan)"); }
 
   if (!ctx->dn_graph_ready || ctx->dn_graph_ncb != (no_cluster_breaking != 0)) {
@@ -702,6 +881,33 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     uint64_t launches = 0;
     for (int slot : {5, 6}) { ctx->ev_used[slot] = false; }
     swa_t0(ctx, 5);                                            // timing slot 5: groups + pairs, slot 6: alignments + CSR
+    // the short sequences and what they can pair with, by length (once: a regrow repeats only the search)
+    BruteArgs br{};
+    if (plan.nshort != 0) {
+      const uint32_t top = plan.short_below + d;
+      SWA_TRY(swa_reserve(ctx, ctx->d_frole, ((uint64_t)kShortSorted + plan.nnear) * sizeof(uint32_t)));
+      auto * words = static_cast<uint32_t *>(ctx->d_frole.ptr);
+      uint32_t start[SWA_DN_HIST_LEN + 1];
+      start[0] = 0;
+      for (uint32_t L = 0; L < top; ++L) { start[L + 1] = start[L] + ctx->dn_len_hist[L]; }
+      SWA_HIP(ctx, hipMemcpyAsync(words + kShortStart, start, (top + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+      SWA_HIP(ctx, hipMemsetAsync(words + kShortCursor, 0, top * sizeof(uint32_t), ctx->stream));
+      hipLaunchKernelGGL(k_dg_short_sort, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, n, top, words + kShortStart,
+                         words + kShortCursor, words + kShortSorted, plan.nnear);
+      SWA_HIP(ctx, hipGetLastError());
+      SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (start[] is on this stack)
+      ++launches;
+      br.seqlen = ctx->db.seqlen; br.sigs = static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr);
+      br.sorted = words + kShortSorted; br.start = words + kShortStart;
+      br.nshort = plan.nshort; br.short_below = plan.short_below; br.d = d;
+      // enough waves to fill the device when the short sequences are few, one wave each when they are many
+      const uint32_t want_tiles = std::max<uint32_t>(1u, 16384u / plan.nshort);
+      br.ntiles = std::min<uint32_t>(want_tiles, (plan.max_range + 255u) / 256u);
+      br.ntiles = std::max<uint32_t>(1u, br.ntiles);
+      br.tile = ((plan.max_range + br.ntiles - 1u) / br.ntiles + 63u) & ~63u;
+      br.owner_rank = ctx->dn_owner_rank; br.owner_world = ctx->dn_owner_world;
+      br.counters = fc;
+    }
     for (int attempt = 0; attempt < 6; ++attempt) {
       SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->dn_pair_cap * sizeof(uint64_t)));
       SWA_HIP(ctx, hipMemsetAsync(fc, 0, 8 * sizeof(uint64_t), ctx->stream));
@@ -709,7 +915,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       SWA_HIP(ctx, hipMemsetAsync(dflags + 11, 0, sizeof(uint32_t), ctx->stream));
       for (uint32_t k = 0; k <= d; ++k) {
         GroupArgs g{};
-        g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen; g.n = n; g.d = d; g.k = k; g.wlen = wlen;
+        g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen; g.n = n; g.d = d; g.k = k; g.wlen = wlen; g.short_below = plan.short_below;
         g.keys = keys; g.cnt_t = cnt_t; g.cnt_q = cnt_q; g.amask = asize - 1; g.tslot = tslot; g.qslot = qslot; g.overflow = dflags + 9;
         g.owner_rank = ctx->dn_owner_rank; g.owner_world = ctx->dn_owner_world;
         const dim3 gn(grid_for(ctx, n)), ga(grid_for(ctx, asize)), b(256);
@@ -735,6 +941,13 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         else { hipLaunchKernelGGL(k_dg_pairs, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
         SWA_HIP(ctx, hipGetLastError());
         launches += 9;
+      }
+      if (plan.nshort != 0) {
+        br.pairs = static_cast<unsigned long long *>(ctx->d_fpairs.ptr); br.pair_cap = ctx->dn_pair_cap;
+        const uint64_t blocks = ((uint64_t)br.nshort * br.ntiles + 3u) / 4u;
+        hipLaunchKernelGGL(k_dg_brute, dim3((unsigned)std::min<uint64_t>(blocks, (uint64_t)ctx->num_cus * 8u)), dim3(256), 0, ctx->stream, br);
+        SWA_HIP(ctx, hipGetLastError());
+        ++launches;
       }
       uint64_t got[2] = {0, 0};
       uint32_t fl[4] = {0, 0, 0, 0};
@@ -906,7 +1119,8 @@ extern "C" int swa_dn_parent_diffs(swa_ctx * ctx, uint8_t * pdiff) {
 
 // Multi-GPU by ownership of window groups (as swa_d1_set_ownership): with world > 1 this context makes only the groups
 // whose window key maps to `rank`.  A pair is reported through the FIRST window it shares ("not already found through
-// an earlier window" is decided on the two sequences), and that window's group lives on one rank: over all ranks every
+// an earlier window" is decided on the two sequences), and that window's group lives on one rank; a pair with a short
+// member comes from the rank with id % world of the short sequence that emits it (k_dg_brute): over all ranks every
 // pair of the graph is found exactly once.  world = 1 restores the complete graph.
 extern "C" int swa_dn_set_ownership(swa_ctx * ctx, uint32_t rank, uint32_t world) {
   if (ctx == nullptr) { return SWA_E_ARG; }

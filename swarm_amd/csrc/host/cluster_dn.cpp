@@ -194,8 +194,9 @@ static int cluster_on_device(swa_ctx * ctx, const swa_hostdb * db, int no_cluste
   return SWA_OK;
 }
 
-// d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups; a database the
-// graph route cannot serve (a sequence too short for d + 1 windows) is clustered by rank 0 alone with the fused scan.
+// d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups (and of the short
+// sequences, whose pairs are found by brute force); a database the graph route cannot serve (d > 8, or too many candidate
+// pairs with a sequence too short for d + 1 windows) is clustered by rank 0 alone with the fused scan.
 extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                                     uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
   if (multi == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
@@ -238,8 +239,9 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
   dn_stamp("search / scan begin");
   if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
 
-  // Bulk route (dn_graph.hip): when every sequence has room for d + 1 windows the GPU returns the whole graph of
-  // pairs within d differences at once and the greedy loop below runs over that CSR, like d = 1.
+  // Bulk route (dn_graph.hip): the GPU returns the whole graph of pairs within d differences at once and the greedy
+  // loop below runs over that CSR, like d = 1.  Taken when the sequences without room for d + 1 windows are few enough
+  // for their pairs to be found by brute force (swa_dn_graph_supported).
   // SWARM_AMD_DN=scan keeps the fused scan (one launch sequence per swarm generation), =graph insists on the graph.
   const char * route = std::getenv("SWARM_AMD_DN");
   const bool want_scan = route != nullptr && std::strcmp(route, "scan") == 0;

@@ -28,6 +28,9 @@ struct swa_dbuf {
   size_t bytes = 0;
 };
 
+// dn_graph.hip keeps a count per sequence length below this: 16 (d + 1) + d for d <= 8, the lengths a short sequence can pair with
+#define SWA_DN_HIST_LEN 152u
+
 struct swa_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -129,10 +132,14 @@ struct swa_ctx {
 
   // d >= 2 in bulk (dn_graph.hip): the graph of all pairs within d differences, kept sorted on the device
   uint32_t dn_shortest = 0;      // shortest sequence of the database (0 = not measured yet)
+  // ... with it: how many sequences have each length below SWA_DN_HIST_LEN, and the shortest of the others (none: ~0).
+  // What window_length() decides everything from: the shortest LONG sequence, the short ones and their candidates B.
+  uint32_t dn_len_hist[SWA_DN_HIST_LEN] = {};
+  uint32_t dn_shortest_rest = 0xFFFFFFFFu;
   bool dn_graph_ready = false, dn_graph_ncb = false;
   uint64_t dn_pair_cap = 0, dn_comparisons = 0, dn_aligned = 0, dn_launches = 0, dn_edges = 0, dn_work = 0;
   swa_dbuf d_dn_keys, d_dn_vals;
-  uint32_t dn_owner_rank = 0, dn_owner_world = 1;   // swa_dn_set_ownership: this context finds the pairs of the window groups it owns
+  uint32_t dn_owner_rank = 0, dn_owner_world = 1;   // swa_dn_set_ownership: this context finds the pairs of the window groups (and short sequences) it owns
 
   // streaming index build / CSR assembly (d1_stream.inc)
   bool lines_ready = false;      // d_lines holds this database's amplicon lines (made once per upload), lines_w words each
