@@ -367,13 +367,27 @@ int swa_scan_totals(swa_ctx * ctx, uint64_t * out3);
    length; cigar receives the pairs' CIGAR strings back to back (src/utils/cigar.cc:28-60: counts of 1 omitted, no NUL),
    cigar_end[k] = end of pair k's.  No CIGAR is longer than dl + ql.  SWA_E_CAPACITY when cigar_cap is too small:
    *cigar_total = the need (the other results are complete).  Banded tiers on the GPU, each result accepted only with its
-   certificate; what no tier certifies, and pairs too long or with penalties too large for 32-bit costs,
-   are aligned on the host within the call — the results are the same bit for bit either way. */
+   certificate: three tiers with the direction bits in LDS (16, 32, 64 lanes a pair: band half-width
+   W = 6, 14, 30; min(dl, ql) <= 1024 and |dl - ql| <= 30), then four wide tiers with the bits in a bounded global
+   scratch area (one wave a pair, 1, 2, 4, 8 band offsets a lane: W = 30, 62, 126, 254).  A pair enters at the narrowest
+   tier that covers |dl - ql| and moves to the next wider one when its end cost is not below gapopen + (W + 1) gapextend.
+   The host aligns, within the call and with the same result bit for bit, only:
+     - pairs with |dl - ql| > 254, or whose end cost is at least gapopen + 255 gapextend (the widest certificate);
+     - pairs with dl + ql > 32 768 (the length limit: two amplicons of 16 384 nt; sequences and CIGAR text of a pair are
+       kept in LDS);
+     - pairs whose costs could reach 2^30 (mismatch + 3 gapopen + (dl + ql + 4) gapextend), which need more than 32 bits;
+     - pairs that found the device's CIGAR buffer full (swa_nw_batch_text_full counts them). */
 int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
                  const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
                  uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total);
-/* out4 = pairs of the last swa_nw_batch per tier: 16-, 32-, 64-lane bands (half-width 6, 14, 30), host */
+/* out4 = pairs of the last swa_nw_batch: certified by the 16-, 32-, 64-lane LDS tiers (half-width 6, 14, 30), and
+   out4[3] = left by the LDS tiers (the wide tiers and the host together) */
 int swa_nw_batch_totals(const swa_ctx * ctx, uint64_t * out4);
+/* out8 = pairs of the last swa_nw_batch per tier: the three LDS tiers, the four wide tiers (half-width 30, 62, 126,
+   254), the host.  A pair is counted in the tier that certified it. */
+int swa_nw_batch_tiers(const swa_ctx * ctx, uint64_t * out8);
+/* *out1 = pairs of the last swa_nw_batch that the widest tier certified but that found the CIGAR buffer full (host pairs) */
+int swa_nw_batch_text_full(const swa_ctx * ctx, uint64_t * out1);
 
 /* ---- B3 + B4 in bulk: the whole d >= 2 search as ONE graph --------------------------------
    Everything qgram_diff_fast + search_do can ever answer during algo_run (src/algo.cc:423-602: per seed

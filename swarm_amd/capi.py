@@ -692,11 +692,26 @@ class Context:
         return diffs, cols, cigars
 
     def nw_batch_totals(self) -> list:
-        """pairs of the last nw_batch per tier: [16-lane, 32-lane, 64-lane band, host]"""
+        """pairs of the last nw_batch: [16-lane, 32-lane, 64-lane LDS tier, left by the LDS tiers (wide tiers + host)]"""
         _declare_dn(self.lib)
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.swa_nw_batch_totals(self.h, _p64(out)))
         return [int(v) for v in out]
+
+    def nw_batch_tiers(self) -> list:
+        """pairs of the last nw_batch per tier: the three LDS tiers (band half-width 6, 14, 30), the four wide tiers
+        (30, 62, 126, 254), the host"""
+        _declare_dn(self.lib)
+        out = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.swa_nw_batch_tiers(self.h, _p64(out)))
+        return [int(v) for v in out]
+
+    def nw_batch_text_full(self) -> int:
+        """pairs of the last nw_batch that went to the host only because the device's CIGAR buffer was full"""
+        _declare_dn(self.lib)
+        out = np.zeros(1, dtype=np.uint64)
+        self._check(self.lib.swa_nw_batch_text_full(self.h, _p64(out)))
+        return int(out[0])
 
 
 # ---- d >= 2: host greedy loop over the GPU's fused scan step ---------------------------------
@@ -708,7 +723,7 @@ _DN_EXPORTS = ["swa_dn_cluster", "swa_dn_result_free", "swa_dn_result_error", "s
                "swa_multi_create", "swa_multi_destroy", "swa_multi_size", "swa_multi_uses_rccl", "swa_multi_ctx", "swa_multi_last_error",
                "swa_multi_db_upload", "swa_multi_d1_network", "swa_multi_d1_fastidious", "swa_dn_set_ownership", "swa_multi_dn_begin",
                "swa_multi_dn_graph_supported", "swa_multi_dn_graph", "swa_multi_dn_graph_totals", "swa_dn_cluster_multi",
-               "swa_timing_read_stream", "swa_nw_batch", "swa_nw_batch_totals", "swa_d1_write_uclust_gpu", "swa_dn_write_uclust_gpu",
+               "swa_timing_read_stream", "swa_nw_batch", "swa_nw_batch_totals", "swa_nw_batch_tiers", "swa_nw_batch_text_full", "swa_d1_write_uclust_gpu", "swa_dn_write_uclust_gpu",
                "swa_nw_align_host"]
 EXPORTS.extend(_DN_EXPORTS)
 
@@ -750,6 +765,8 @@ def _declare_dn(lib) -> None:
     lib.swa_nw_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     lib.swa_nw_batch_totals.argtypes = [C.c_void_p, u64p]
+    lib.swa_nw_batch_tiers.argtypes = [C.c_void_p, u64p]
+    lib.swa_nw_batch_text_full.argtypes = [C.c_void_p, u64p]
     lib.swa_nw_align_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                       u64p, C.c_char_p, C.c_uint64, u64p]
     lib.swa_nw_align_host.restype = C.c_uint64

@@ -53,7 +53,7 @@ int swa_uclust_gpu(swa_ctx * ctx, const swa_hostdb * db, BufOut & o, size_t nswa
     c.first.push_back(c.d.size());
     c.end = k;
   };
-  uint64_t tiers[4] = {};
+  uint64_t tiers[4] = {}, all[8] = {}, text_full = 0;
   auto align = [&](swa_uclust_chunk & c) {
     const size_t n = c.d.size();
     c.diffs.resize(n); c.columns.resize(n); c.cigar_end.resize(n);
@@ -66,6 +66,9 @@ int swa_uclust_gpu(swa_ctx * ctx, const swa_hostdb * db, BufOut & o, size_t nswa
                         c.cigar_end.data(), c.cigar.get(), c.cigar_cap, &total);
     uint64_t t[4] = {};
     if (c.rc == SWA_OK && swa_nw_batch_totals(ctx, t) == SWA_OK) { for (int i = 0; i < 4; ++i) { tiers[i] += t[i]; } }
+    uint64_t t8[8] = {}, full = 0;
+    if (c.rc == SWA_OK && swa_nw_batch_tiers(ctx, t8) == SWA_OK) { for (int i = 0; i < 8; ++i) { all[i] += t8[i]; } }
+    if (c.rc == SWA_OK && swa_nw_batch_text_full(ctx, &full) == SWA_OK) { text_full += full; }
   };
   swa_uclust_chunk cur, next;
   fill(cur, 0);
@@ -85,6 +88,9 @@ int swa_uclust_gpu(swa_ctx * ctx, const swa_hostdb * db, BufOut & o, size_t nswa
   if (std::getenv("SWARM_AMD_TIMING") != nullptr) {      // (the CLI's milestones: where the pairs were aligned)
     std::fprintf(stderr, "[nw] pairs by band half-width 6 / 14 / 30 / host: %llu %llu %llu %llu\n", (unsigned long long)tiers[0],
                  (unsigned long long)tiers[1], (unsigned long long)tiers[2], (unsigned long long)tiers[3]);
+    std::fprintf(stderr, "[nw] pairs by tier, LDS 6 / 14 / 30, wide 30 / 62 / 126 / 254, host:");
+    for (int i = 0; i < 8; ++i) { std::fprintf(stderr, " %llu", (unsigned long long)all[i]); }
+    std::fprintf(stderr, "; of the host's, text buffer full: %llu\n", (unsigned long long)text_full);
   }
   return cur.rc;
 }

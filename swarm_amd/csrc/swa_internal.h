@@ -177,10 +177,13 @@ struct swa_ctx {
   swa_dbuf d_cluster, d_cluster_ctl;
 
   // the uclust alignments (nw_trace.hip): the database's lengths on the host (filled by the first swa_nw_batch after an
-  // upload), the pairs per tier of the last batch, and the device buffers of one slice
+  // upload), the pairs per tier of the last batch (three LDS tiers, four wide tiers, host), how many of them the widest
+  // tier certified but found the text buffer full, and the device buffers of one slice (d_nw_bits: the wide tiers'
+  // direction bits, one slot per wave; reserved on every run, 256 slots at least for what the LDS tiers may pass down)
   std::vector<uint32_t> nw_seqlen;
-  uint64_t nw_totals[4] = {};
-  swa_dbuf d_nw_ids, d_nw_lists, d_nw_res, d_nw_text, d_nw_gather;
+  uint64_t nw_totals[8] = {};
+  uint64_t nw_text_full = 0;
+  swa_dbuf d_nw_ids, d_nw_lists, d_nw_res, d_nw_text, d_nw_gather, d_nw_bits;
 };
 
 int swa_fail(swa_ctx * ctx, int code, const char * what, hipError_t e);
