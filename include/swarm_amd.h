@@ -402,8 +402,10 @@ int swa_nw_batch_text_full(const swa_ctx * ctx, uint64_t * out1);
    its pairs are found by comparing it with every sequence whose length differs by at most d (no pair within
    d differences has a larger length difference).  That part is quadratic in the short sequences, so the
    number B of its candidate pairs — known from the count of sequences per length — is capped at 16 n + 2^20
-   (test hook: SWA_DN_BRUTE_CAP): swa_dn_graph_supported != 0 when d <= 8 and B is within the cap (else use
-   swa_scan_*; swa_dn_graph then fails with SWA_E_ARG).
+   (test hook: SWA_DN_BRUTE_CAP): swa_dn_graph_supported != 0 when d <= 16 and B is within the cap (else use
+   swa_scan_*; swa_dn_graph then fails with SWA_E_ARG).  For 9 <= d <= 16 the pairs of a window group come from a
+   pair kernel of their own (k_dg_pairs_deep: runtime d, up to 33 shifts of up to 17 windows); everything behind the
+   pair list is the same for every d.
    Requires swa_qgram_build and swa_search_begin.  Buffers as swa_d1_network: offsets[n + 1] always
    filled, *total = entries needed, SWA_E_CAPACITY when total > cap (call again with room: nothing is
    recomputed). */

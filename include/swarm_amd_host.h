@@ -112,6 +112,9 @@ int  swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t diff
                           uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out);
 void swa_dn_result_free(swa_dn_result * res);
 const char * swa_dn_result_error(const swa_dn_result * res);
+/* 1 when the bulk graph (swa_dn_graph*) served the clustering, 0 when the fused scan did.  SWARM_AMD_DN=scan|graph
+   choose; without it the graph serves d <= 8 (where swa_dn_graph_supported) and the scan everything else. */
+int  swa_dn_result_over_graph(const swa_dn_result * res);
 /* out3 = {number of swarms, largest swarm, max generations} (src/algo.cc:699-705) */
 void swa_dn_result_summary(const swa_dn_result * res, uint64_t * out3);
 /* writers: -o/-r, -s, -i, -w, -u  (src/algo.cc:122-325, 473-488, 573-589, 608-674) */

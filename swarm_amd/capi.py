@@ -631,6 +631,51 @@ class Context:
         self._check(self.lib.swa_qgram_debug_read(self.h, _ptr(out), out.nbytes))
         return out
 
+    # ---- B3 + B4 in bulk (dn_graph.hip); after qgram_build + search_begin
+    def dn_graph_supported(self) -> bool:
+        """swa_dn_graph_supported: d <= 16 and few enough candidate pairs with a sequence too short for d + 1 windows"""
+        self.lib.swa_dn_graph_supported.argtypes = [C.c_void_p]
+        return bool(self.lib.swa_dn_graph_supported(self.h))
+
+    def dn_graph_raw(self, cap: int, no_cluster_breaking: bool = False):
+        """One swa_dn_graph call with room for `cap` entries: (return code, offsets, neighbours, diffs, total)."""
+        self.lib.swa_dn_graph.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+        offsets = np.zeros(self.n + 1, dtype=np.uint64)
+        nb = np.zeros(max(1, cap), dtype=np.uint32)
+        df = np.zeros(max(1, cap), dtype=np.uint8)
+        total = C.c_uint64(0)
+        rc = self.lib.swa_dn_graph(self.h, int(no_cluster_breaking), _ptr(offsets), _ptr(nb) if cap else None,
+                                   _ptr(df) if cap else None, cap, C.byref(total))
+        return rc, offsets, nb[:min(cap, total.value)], df[:min(cap, total.value)], int(total.value)
+
+    def dn_graph(self, no_cluster_breaking: bool = False):
+        """swa_dn_graph by its capacity protocol (cap = 0, then the total): (offsets, neighbours, diffs)."""
+        rc, offsets, nb, df, total = self.dn_graph_raw(0, no_cluster_breaking)
+        if rc == SWA_E_CAPACITY:
+            rc, offsets, nb, df, total = self.dn_graph_raw(total, no_cluster_breaking)
+        self._check(rc)
+        return offsets, nb, df
+
+    def dn_graph_totals(self) -> dict:
+        out = np.zeros(3, dtype=np.uint64)
+        self.lib.swa_dn_graph_totals.argtypes = [C.c_void_p, u64p]
+        self._check(self.lib.swa_dn_graph_totals(self.h, _p64(out)))
+        return {"qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
+
+    def dn_graph_resident(self, no_cluster_breaking: bool = False) -> int:
+        """swa_dn_graph_resident: the graph left in HBM for d1_cluster_device; returns its number of links."""
+        self.lib.swa_dn_graph_resident.argtypes = [C.c_void_p, C.c_int, u64p]
+        total = C.c_uint64(0)
+        self._check(self.lib.swa_dn_graph_resident(self.h, int(no_cluster_breaking), C.byref(total)))
+        return int(total.value)
+
+    def dn_parent_diffs(self) -> np.ndarray:
+        """swa_dn_parent_diffs: per amplicon the differences to its parent in the clustering d1_cluster_device just made"""
+        self.lib.swa_dn_parent_diffs.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(self.n, dtype=np.uint8)
+        self._check(self.lib.swa_dn_parent_diffs(self.h, _ptr(out)))
+        return out
+
     # ---- B4
     def search_begin(self, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13, d: int = 3) -> None:
         self._check(self.lib.swa_search_begin(self.h, mismatch, gapopen, gapextend, d))
@@ -716,7 +761,7 @@ class Context:
 
 # ---- d >= 2: host greedy loop over the GPU's fused scan step ---------------------------------
 
-_DN_EXPORTS = ["swa_dn_cluster", "swa_dn_result_free", "swa_dn_result_error", "swa_dn_result_summary",
+_DN_EXPORTS = ["swa_dn_cluster", "swa_dn_result_free", "swa_dn_result_error", "swa_dn_result_summary", "swa_dn_result_over_graph",
                "swa_dn_write_swarms", "swa_dn_write_stats", "swa_dn_write_structure", "swa_dn_write_seeds",
                "swa_dn_write_uclust", "swa_d1_write_uclust", "swa_scan_begin", "swa_scan_step", "swa_scan_batch", "swa_scan_fetch", "swa_scan_totals",
                "swa_dn_graph_supported", "swa_dn_graph", "swa_dn_graph_totals", "swa_dn_graph_resident", "swa_dn_parent_diffs",
@@ -799,8 +844,8 @@ class DnClusters:
         """Work counters of the route that ran: the bulk graph (swa_dn_graph) or the fused scan (swa_scan_*)."""
         out = np.zeros(3, dtype=np.uint64)
         self.lib.swa_dn_graph_totals.argtypes = [C.c_void_p, u64p]
-        self.lib.swa_dn_graph_supported.argtypes = [C.c_void_p]
-        if self.lib.swa_dn_graph_supported(self.ctx.h) and os.environ.get("SWARM_AMD_DN") != "scan":
+        self.lib.swa_dn_result_over_graph.argtypes = [C.c_void_p]
+        if self.lib.swa_dn_result_over_graph(self.h):
             self.ctx._check(self.lib.swa_dn_graph_totals(self.ctx.h, _p64(out)))
             return {"route": "graph", "qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
         self.ctx._check(self.lib.swa_scan_totals(self.ctx.h, _p64(out)))
@@ -1006,7 +1051,7 @@ class MultiContext:
 
     def dn_graph(self, d: int, no_cluster_breaking: bool = False, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
         """swa_multi_dn_begin + swa_multi_dn_graph: (offsets, neighbours, diffs) of the whole d >= 2 graph, or None when the
-        graph route does not serve the database: d > 8, or more candidate pairs with a sequence too short for d + 1
+        graph route does not serve the database: d > 16, or more candidate pairs with a sequence too short for d + 1
         windows than the brute-force part takes (16 n + 2^20; SWA_DN_BRUTE_CAP)."""
         lib = self.lib
         lib.swa_multi_dn_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]

@@ -29,8 +29,9 @@
 // The two parts are disjoint (a pair has a short member or it has none) and together complete; everything behind the
 // pair list does not know which part a pair came from.  The brute-force part is quadratic in the short sequences, so
 // the number B of its (short, partner) candidates — known from the count of sequences per length before anything is
-// launched — is capped (brute_cap): beyond it, and for d > 8, the fused scan of scan.hip serves
-// (swa_dn_graph_supported).  HBM traffic: group bookkeeping (a few tens of bytes per amplicon and window) + the
+// launched — is capped (brute_cap): beyond it, and for d > 16, the fused scan of scan.hip serves
+// (swa_dn_graph_supported).  Nothing in the method depends on d; 16 is where the constants stop (kMaxShifts, SWA_DN_HIST_LEN,
+// the unrolled windows of k_dg_pairs_deep).  HBM traffic: group bookkeeping (a few tens of bytes per amplicon and window) + the
 // members' sequences and signatures, mostly from L2.
 #include "swa_internal.h"
 
@@ -50,7 +51,9 @@ constexpr uint64_t kKeyEmpty = ~0ull;
 constexpr uint32_t kTile = 4096;          // (query, target) pairs per turn of a wave
 constexpr uint32_t kStride = 64;          // a group's tiles are dealt round-robin to at most this many items
 constexpr uint32_t kStage = 256;          // per-wave staging of found pairs
-constexpr int kMaxShifts = 17;            // 2 d + 1 for d <= 8
+constexpr int kMaxD = 16;                 // the graph route serves d <= kMaxD
+constexpr int kMaxShifts = 2 * kMaxD + 1; // 2 d + 1 for d <= 16
+constexpr int kSmallShifts = 17;          // ... and for d <= 8: k_dg_targets<kSmallShifts> is the kernel those d have always run
 
 struct dg_item { uint32_t begin, nt, nq, tile; };   // members[begin, begin+nt) targets, then nq queries
 
@@ -93,14 +96,15 @@ __global__ __launch_bounds__(256) void k_dg_clear(unsigned long long * keys, uin
   }
 }
 
-// every amplicon (that is not short) is a target under its window k at the shifts -d .. +d
+// every amplicon (that is not short) is a target under its window k at the shifts -d .. +d (MAXS >= 2 d + 1)
+template <int MAXS>
 __global__ __launch_bounds__(256) void k_dg_targets(const GroupArgs a) {
   const uint32_t ns = 2u * a.d + 1u;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
     const uint32_t len = a.seqlen[i];
     const bool is_short = len < a.short_below;
     const uint64_t * s = a.seqs + a.seq_off[i];
-    uint64_t seen[kMaxShifts];
+    uint64_t seen[MAXS];
     for (uint32_t j = 0; j < ns; ++j) {
       uint32_t slot = kEmpty;
       const int64_t pos = (int64_t)a.k * a.wlen + (int64_t)j - (int64_t)a.d;
@@ -461,6 +465,176 @@ __global__ __launch_bounds__(256) void k_dg_pairs_lds(const PairArgs a) {
   if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
 }
 
+// The same blocks for 9 <= d <= 16 (runtime d).  A target's windows at every shift are up to 17 x 33 words here: they fit
+// neither registers nor LDS (64 targets x 561 x 8 bytes a wave).  But the windows 0 .. K at the shifts -d .. +d all lie in
+// the target's first (K + 1) WLEN + d nucleotides — at most 560 (WLEN = 32) or 288 (WLEN = 16), 18 or 10 words — and those
+// stay in the lane's registers.  Window k2 at all its shifts is one REGION of WLEN + 2 d <= 64 nucleotides from position
+// k2 WLEN - d on: three of the words funnelled into 128 bits (which words is known at compile time: k2 is unrolled and
+// 32 - d or 16 - d of the offset is a shift), and the 2 d + 1 candidates are that region moved down two bits a step — a
+// few register instructions a shift, nothing from memory.  The queries pass by in LDS as in k_dg_pairs_lds (id, length,
+// signature, windows 0 .. K: read by all lanes at one address).  "Not already found through an earlier window" stops as
+// soon as no lane of the wave is still undecided: in a family nearly every pair shares window 0.
+// Registers, not LDS, for the words (figures of the compiler for gfx950 in DESIGN.md 3.5): as an LDS column a lane they
+// would add 36 KiB (WLEN = 32) to a workgroup's 25 KiB and leave two workgroups a CU.
+constexpr int kDeepWindows = kMaxD + 1;
+template <int WLEN>
+struct DeepWords { static constexpr int value = (kDeepWindows * WLEN + kMaxD + 31) / 32; };
+
+// does `wq` (WLEN nucleotides) occur in the target at k2 WLEN + s - d for one of the shifts s = 0 .. 2 d the target has
+// room for?  tw: the target's first words; 1 <= d <= 16.
+template <int WLEN, int K2, int NW>
+__device__ __forceinline__ bool deep_hit(const uint64_t (&tw)[NW], uint64_t wq, int d, int lt) {
+  // the region starts at nucleotide K2 WLEN - d = 32 (base - 1) + off of the target: word `base - 1` (none: zeros)
+  constexpr int at = K2 * WLEN;
+  constexpr int base = at / 32 + (at % 32 != 0 ? 1 : 0);
+  static_assert(base + 1 < NW + 1, "the target's words end before the region does");
+  const uint32_t sh = 2u * (uint32_t)((at % 32 != 0 ? 16 : 32) - d);          // 0 .. 62
+  const uint64_t w0 = base >= 1 ? tw[base >= 1 ? base - 1 : 0] : 0ull;
+  const uint64_t w1 = tw[base];
+  const uint64_t w2 = base + 1 < NW ? tw[base + 1 < NW ? base + 1 : 0] : 0ull;
+  uint64_t r0 = sh != 0u ? (w0 >> sh) | (w1 << (64u - sh)) : w0;
+  uint64_t r1 = sh != 0u ? (w1 >> sh) | (w2 << (64u - sh)) : w1;
+  // the shifts with the whole window inside the target: s >= d - K2 WLEN, s <= lt - (K2 + 1) WLEN + d
+  const int smin = max(0, d - at), smax = min(2 * d, lt - (at + WLEN) + d);
+  const uint32_t room = smax >= smin ? (uint32_t)(smax - smin + 1) : 0u;
+  bool hit = false;
+  for (int s = 0; s <= 2 * d; ++s) {
+    const uint64_t c = WLEN >= 32 ? r0 : (r0 & ((1ull << (2 * (WLEN & 31))) - 1ull));
+    hit = hit || ((uint32_t)(s - smin) < room && c == wq);
+    r0 = (r0 >> 2) | (r1 << 62);
+    r1 >>= 2;
+  }
+  return hit;
+}
+
+template <int WLEN, int K2, int NW>
+struct DeepEarlier {
+  // earlier |= window k2 reappears, for k2 = K2 .. K - 1, until no lane with `open` set is left without it
+  static __device__ __forceinline__ void run(const uint64_t (&tw)[NW], const uint64_t * qwin, uint32_t K, int d, int lt, bool open, bool & earlier) {
+    if constexpr (K2 < kDeepWindows - 1) {
+      if ((uint32_t)K2 >= K || __ballot(open && !earlier) == 0ull) { return; }
+      earlier = earlier || deep_hit<WLEN, K2, NW>(tw, qwin[K2], d, lt);
+      DeepEarlier<WLEN, K2 + 1, NW>::run(tw, qwin, K, d, lt, open, earlier);
+    }
+  }
+};
+
+template <int WLEN, int K2, int NW>
+struct DeepHere {
+  // window K itself (wave-uniform K picks the instance)
+  static __device__ __forceinline__ bool run(const uint64_t (&tw)[NW], const uint64_t * qwin, uint32_t K, int d, int lt) {
+    if constexpr (K2 < kDeepWindows) {
+      if ((uint32_t)K2 == K) { return deep_hit<WLEN, K2, NW>(tw, qwin[K2], d, lt); }
+      return DeepHere<WLEN, K2 + 1, NW>::run(tw, qwin, K, d, lt);
+    } else {
+      return false;
+    }
+  }
+};
+
+template <int WLEN>
+__global__ __launch_bounds__(256) void k_dg_pairs_deep(const PairArgs a) {
+  constexpr int NW = DeepWords<WLEN>::value;
+  struct QRec { uint64_t sig[16]; uint64_t win[kDeepWindows]; uint32_t id, len; };
+  __shared__ unsigned long long stage_all[4][kStage];
+  __shared__ QRec qrec_all[4][kStageQ];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned long long * stage = stage_all[wave];
+  QRec * qrec = qrec_all[wave];
+  uint32_t nstage = 0;
+  unsigned long long compared = 0;
+  const uint64_t lane_lt = (1ull << lane) - 1ull;
+  auto flush = [&]() {
+    wave_lds_sync();
+    unsigned long long base = 0;
+    if (lane == 0) { base = atomicAdd(&a.counters[0], (unsigned long long)nstage); }
+    base = shfl_u64(base, 0);
+    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
+    nstage = 0;
+    wave_lds_sync();
+  };
+  const uint32_t nitems = min(*a.item_count, a.item_cap);
+  const uint32_t nwaves = gridDim.x * 4u;
+  const uint32_t K = a.k;                                     // this launch's window (<= d), wave-uniform
+  const int d = (int)a.d;
+  for (uint32_t it = blockIdx.x * 4u + wave; it < nitems; it += nwaves) {
+    const dg_item item = a.items[it];
+    const uint32_t * targets = a.members + item.begin;
+    const uint32_t * queries = targets + item.nt;
+    const uint32_t ntb = (item.nt + kBlockT - 1u) / kBlockT;
+    const uint64_t nblocks = (uint64_t)ntb * ((item.nq + kBlockQ - 1u) / kBlockQ);
+    for (uint64_t blk = item.tile; blk < nblocks; blk += kBlockStride) {
+      const uint32_t tb = (uint32_t)(blk % ntb), qc = (uint32_t)(blk / ntb);
+      // ---- my target: its first words (only its own: what lies behind them is not read), signature
+      const uint32_t ti = tb * kBlockT + (uint32_t)lane;
+      const bool have_t = ti < item.nt;
+      const uint32_t t = have_t ? targets[ti] : 0u;
+      const int lt = have_t ? (int)a.seqlen[t] : 0;
+      const uint64_t * st = a.seqs + a.seq_off[t];
+      uint64_t tw[NW];
+#pragma unroll
+      for (int w = 0; w < NW; ++w) { tw[w] = 32 * w < lt ? st[w] : 0ull; }
+      uint64_t tsig[16];
+      {
+        const ulonglong2 * gt = a.sigs + (uint64_t)t * 8u;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) { const ulonglong2 y = have_t ? gt[w] : make_ulonglong2(0ull, 0ull); tsig[2 * w] = y.x; tsig[2 * w + 1] = y.y; }
+      }
+      const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nq, q_begin + kBlockQ);
+      for (uint32_t qs = q_begin; qs < q_end; qs += kStageQ) {
+        const uint32_t nq_here = min(kStageQ, q_end - qs);
+        wave_lds_sync();
+        // ---- the next queries into LDS: lanes [16 j', 16 j' + 16) carry the signature words of query 4 r + j'
+        for (uint32_t r = 0; r < kStageQ / 4u; ++r) {
+          const uint32_t j = 4u * r + ((uint32_t)lane >> 4), w = (uint32_t)lane & 15u;
+          if (j < nq_here) {
+            const uint32_t q = queries[qs + j];
+            qrec[j].sig[w] = reinterpret_cast<const uint64_t *>(a.sigs + (uint64_t)q * 8u)[w];
+          }
+        }
+        if ((uint32_t)lane < nq_here) {
+          const uint32_t q = queries[qs + (uint32_t)lane];
+          const uint64_t * sq = a.seqs + a.seq_off[q];
+          qrec[lane].id = q; qrec[lane].len = a.seqlen[q];
+          // (a query is long: it has all d + 1 windows)
+          for (uint32_t k2 = 0; k2 <= K; ++k2) { qrec[lane].win[k2] = window(sq, k2 * (uint32_t)WLEN, (uint32_t)WLEN); }
+        }
+        wave_lds_sync();
+        for (uint32_t j = 0; j < nq_here; ++j) {
+          const uint32_t q = qrec[j].id;
+          const int dl = (int)qrec[j].len - lt;
+          bool take = have_t && q < t && dl >= -d && dl <= d;
+          if (__ballot(take) == 0ull) { continue; }
+          // the pair belongs to the FIRST window of the query that reappears (shifted) in the target
+          bool earlier = false;
+          DeepEarlier<WLEN, 0, NW>::run(tw, qrec[j].win, K, d, lt, take, earlier);
+          take = take && !earlier;
+          if (__ballot(take) == 0ull) { continue; }
+          // (the group key may collide: window K must really reappear)
+          take = take && DeepHere<WLEN, 0, NW>::run(tw, qrec[j].win, K, d, lt);
+          if (__ballot(take) != 0ull) {
+            // q-gram bound (qgram_diff, src/qgram.cc:68-96): ceil(popcount(sig_q ^ sig_t) / 10) <= d
+            uint32_t pop = 0;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) { pop += (uint32_t)__popcll(qrec[j].sig[w] ^ tsig[w]); }
+            if (take) { ++compared; }
+            take = take && (pop + 9u) / 10u <= a.d;
+          }
+          const uint64_t m = __ballot(take);
+          if (m != 0ull) {
+            if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)q << 32) | t; }
+            nstage += (uint32_t)__popcll(m);
+            if (nstage > kStage - 64u) { flush(); }
+          }
+        }
+      }
+    }
+  }
+  if (nstage != 0u) { flush(); }
+  for (int o = 32; o > 0; o >>= 1) { compared += shfl_u64(compared, lane ^ o); }
+  if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
+}
+
 // ---- the pairs with a short member -------------------------------------------------------------------------------
 // The ids of all sequences below `below` nucleotides (16 (d + 1) + d: the short ones and what they can pair with) in
 // the order of their lengths: start[L] = first entry of length L (from the host's counts), cursor[L] = entries placed.
@@ -765,7 +939,8 @@ int grid_for(const swa_ctx * ctx, uint64_t items) {
 
 // d_frole (the fastidious pair route's buffer, idle at d >= 2) in u32 words: the length counts as k_dg_lengths leaves
 // them, then what the brute-force part reads — start[] and cursor[] per length and the ids sorted by length
-constexpr uint32_t kShortStart = 160, kShortCursor = 320, kShortSorted = 480;
+constexpr uint32_t kShortStart = 320, kShortCursor = 640, kShortSorted = 960;
+static_assert(kShortStart >= SWA_DN_HIST_LEN + 1u && kShortCursor >= kShortStart + SWA_DN_HIST_LEN + 1u && kShortSorted >= kShortCursor + SWA_DN_HIST_LEN, "d_frole layout");
 
 // what the database's lengths decide for this d
 struct dn_plan {
@@ -799,9 +974,9 @@ int window_length(swa_ctx * ctx, uint32_t d, dn_plan * out) {
     ctx->dn_shortest = mn;
   }
   *out = dn_plan();
-  if (2u * d + 1u > (uint32_t)kMaxShifts) { return SWA_OK; }
+  if (d > (uint32_t)kMaxD) { return SWA_OK; }
   const uint32_t * hist = ctx->dn_len_hist;
-  const uint32_t T = 16u * (d + 1u), top = T + d;              // (d <= 8: top <= SWA_DN_HIST_LEN)
+  const uint32_t T = 16u * (d + 1u), top = T + d;              // (d <= 16: top <= SWA_DN_HIST_LEN)
   out->short_below = T;
   uint32_t shortest_long = ctx->dn_shortest_rest;
   for (uint32_t L = SWA_DN_HIST_LEN; L-- > T;) { if (hist[L] != 0u) { shortest_long = L; } }
@@ -920,15 +1095,17 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         g.owner_rank = ctx->dn_owner_rank; g.owner_world = ctx->dn_owner_world;
         const dim3 gn(grid_for(ctx, n)), ga(grid_for(ctx, asize)), b(256);
         hipLaunchKernelGGL(k_dg_clear, ga, b, 0, ctx->stream, keys, cnt_t, cnt_q, cur_t, cur_q, asize);
-        hipLaunchKernelGGL(k_dg_targets, gn, b, 0, ctx->stream, g);
+        if (ns <= (uint32_t)kSmallShifts) { hipLaunchKernelGGL(k_dg_targets<kSmallShifts>, gn, b, 0, ctx->stream, g); }
+        else { hipLaunchKernelGGL(k_dg_targets<kMaxShifts>, gn, b, 0, ctx->stream, g); }
         hipLaunchKernelGGL(k_dg_queries, gn, b, 0, ctx->stream, g);
         hipLaunchKernelGGL(k_dg_totals, ga, b, 0, ctx->stream, cnt_t, cnt_q, asize, tot);
         SWA_HIP(ctx, rocprim::exclusive_scan(ctx->d_scan_tmp.ptr, scan_bytes, tot64, goff, (uint64_t)0, asize + 1, rocprim::plus<uint64_t>(),
                                              ctx->stream));
         hipLaunchKernelGGL(k_dg_scatter, gn, b, 0, ctx->stream, g, tot, goff, cur_t, cur_q, members);
         SWA_HIP(ctx, hipMemsetAsync(dflags + 8, 0, sizeof(uint32_t), ctx->stream));
-        // blocks of 64 targets x 256 queries for the LDS kernel (d = 2, 3; the per-pair kernel for other d)
-        const bool blocked = d == 2u || d == 3u;
+        // blocks of 64 targets x 256 queries for the LDS kernels (d = 2, 3 and 9 .. 16; the per-pair kernel for other d)
+        const bool deep = d >= 9u;
+        const bool blocked = d == 2u || d == 3u || deep;
         if (blocked) { hipLaunchKernelGGL(k_dg_items<true>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap, dflags + 11); }
         else { hipLaunchKernelGGL(k_dg_items<false>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap, dflags + 11); }
         PairArgs p{};
@@ -936,7 +1113,9 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         p.sigs = static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr);
         p.members = members; p.items = items; p.item_count = dflags + 8; p.item_cap = item_cap; p.d = d; p.k = k; p.wlen = wlen;
         p.pairs = static_cast<unsigned long long *>(ctx->d_fpairs.ptr); p.counters = fc; p.pair_cap = ctx->dn_pair_cap;
-        if (blocked && d == 2u) { hipLaunchKernelGGL(k_dg_pairs_lds<2>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
+        if (deep && wlen == 32u) { hipLaunchKernelGGL(k_dg_pairs_deep<32>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
+        else if (deep) { hipLaunchKernelGGL(k_dg_pairs_deep<16>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
+        else if (blocked && d == 2u) { hipLaunchKernelGGL(k_dg_pairs_lds<2>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
         else if (blocked) { hipLaunchKernelGGL(k_dg_pairs_lds<3>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
         else { hipLaunchKernelGGL(k_dg_pairs, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
         SWA_HIP(ctx, hipGetLastError());

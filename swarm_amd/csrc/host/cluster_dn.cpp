@@ -37,8 +37,20 @@ struct swa_dn_result {
   uint64_t largest = 0, maxgenerations = 0;
   int64_t differences = 0;
   uint64_t pen_mismatch = 18, pen_gapopen = 24, pen_gapextend = 13;
+  bool over_graph = false;                // the bulk graph served (dn_graph.hip), not the fused scan
   std::string error;
 };
+
+// Which route a run takes when the library can serve both: SWARM_AMD_DN=scan / =graph decide; otherwise the graph up to
+// kGraphDefaultMaxD differences.  Above it (9 <= d <= 16, where the graph route exists as well) the default follows the
+// measurement of profiles/r10/NOTES.md.
+constexpr int64_t kGraphDefaultMaxD = 8;
+static bool graph_route_wanted(int64_t differences) {
+  const char * route = std::getenv("SWARM_AMD_DN");
+  if (route != nullptr && std::strcmp(route, "scan") == 0) { return false; }
+  if (route != nullptr && std::strcmp(route, "graph") == 0) { return true; }
+  return differences <= kGraphDefaultMaxD;
+}
 
 // The greedy agglomeration of algo_run (src/algo.cc:384-602) over the complete graph of pairs within d differences
 // (swa_dn_graph: row q = the targets t with diff(q, t) <= d that the abundance rule lets q take, ascending, with
@@ -195,14 +207,13 @@ static int cluster_on_device(swa_ctx * ctx, const swa_hostdb * db, int no_cluste
 }
 
 // d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups (and of the short
-// sequences, whose pairs are found by brute force); a database the graph route cannot serve (d > 8, or too many candidate
-// pairs with a sequence too short for d + 1 windows) is clustered by rank 0 alone with the fused scan.
+// sequences, whose pairs are found by brute force); a database the graph route cannot serve (d > 16, or too many candidate
+// pairs with a sequence too short for d + 1 windows) or does not serve by default (graph_route_wanted) is clustered by
+// rank 0 alone with the fused scan.
 extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                                     uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
   if (multi == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
-  const char * route = std::getenv("SWARM_AMD_DN");
-  const bool want_scan = route != nullptr && std::strcmp(route, "scan") == 0;
-  if (db->n != 0 && !want_scan) {
+  if (db->n != 0 && graph_route_wanted(differences)) {
     int rc = swa_multi_dn_begin(multi, mismatch, gapopen, gapextend, (uint64_t)differences);
     if (rc != SWA_OK) {                                       // (no silent single-rank run behind a failed start: ADVICE r03)
       auto * r = new swa_dn_result();
@@ -216,6 +227,7 @@ extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, in
       *out = r;
       r->differences = differences;
       r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
+      r->over_graph = true;
       return cluster_over_graph(swa_multi_ctx(multi, 0), multi, db, no_cluster_breaking, r);
     }
   }
@@ -242,11 +254,12 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
   // Bulk route (dn_graph.hip): the GPU returns the whole graph of pairs within d differences at once and the greedy
   // loop below runs over that CSR, like d = 1.  Taken when the sequences without room for d + 1 windows are few enough
   // for their pairs to be found by brute force (swa_dn_graph_supported).
-  // SWARM_AMD_DN=scan keeps the fused scan (one launch sequence per swarm generation), =graph insists on the graph.
+  // SWARM_AMD_DN=scan keeps the fused scan (one launch sequence per swarm generation), =graph insists on the graph
+  // (and is how 9 <= d <= 16 reach it: graph_route_wanted).
   const char * route = std::getenv("SWARM_AMD_DN");
-  const bool want_scan = route != nullptr && std::strcmp(route, "scan") == 0;
   const bool want_graph = route != nullptr && std::strcmp(route, "graph") == 0;
-  if (!want_scan && swa_dn_graph_supported(ctx) != 0) {
+  if (graph_route_wanted(differences) && swa_dn_graph_supported(ctx) != 0) {
+    r->over_graph = true;
     // (SWARM_AMD_DN_WALK=host: the graph downloaded and walked on the host — comparison switch)
     const char * walk = std::getenv("SWARM_AMD_DN_WALK");
     // (differences of 255 are what the device walk's parent-difference bytes use for "no link": d >= 255 walks on the host)
@@ -254,7 +267,10 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
     (void)swa_dn_set_ownership(ctx, 0, 1);                    // (a context that served one rank's share before: the whole graph)
     return cluster_on_device(ctx, db, no_cluster_breaking, r);
   }
-  if (want_graph) { r->error = "SWARM_AMD_DN=graph: a sequence is too short for d + 1 windows"; return SWA_E_ARG; }
+  if (want_graph) {
+    r->error = differences > 16 ? "SWARM_AMD_DN=graph: the graph route serves d <= 16" : "SWARM_AMD_DN=graph: a sequence is too short for d + 1 windows";
+    return SWA_E_ARG;
+  }
 
   std::vector<uint8_t> swarmed(n, 0);
   std::vector<uint32_t> hit_ids(n), hit_diffs(n), hit_sidx(n), batch_ids, batch_radii;
@@ -337,6 +353,8 @@ extern "C" void swa_dn_result_free(swa_dn_result * r) { delete r; }
 extern "C" const char * swa_dn_result_error(const swa_dn_result * r) { return r != nullptr ? r->error.c_str() : ""; }
 
 // {number of swarms, largest swarm, max generations} — the log's summary (src/algo.cc:699-705)
+extern "C" int swa_dn_result_over_graph(const swa_dn_result * r) { return r != nullptr && r->over_graph ? 1 : 0; }
+
 extern "C" void swa_dn_result_summary(const swa_dn_result * r, uint64_t * out3) {
   out3[0] = r->swarms.size();
   out3[1] = r->largest;

@@ -28,8 +28,8 @@ struct swa_dbuf {
   size_t bytes = 0;
 };
 
-// dn_graph.hip keeps a count per sequence length below this: 16 (d + 1) + d for d <= 8, the lengths a short sequence can pair with
-#define SWA_DN_HIST_LEN 152u
+// dn_graph.hip keeps a count per sequence length below this: 16 (d + 1) + d for d <= 16, the lengths a short sequence can pair with
+#define SWA_DN_HIST_LEN 288u
 
 struct swa_ctx {
   int device = 0;
