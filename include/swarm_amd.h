@@ -277,6 +277,18 @@ int swa_d1_fastidious(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt
    counters[2] add up, counters[0], [3], [4] are identical on every shard. */
 int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
                             uint32_t shard, uint32_t nshards, uint32_t * graft_cand, uint64_t * counters);
+/* Which kernels the pass takes for the resident database: chosen from its longest sequence alone (and the switches
+   SWA_FAST_BLOOM / SWA_FAST_PAIRS), so valid once a database is resident; the launches read the same plan.
+   out[0] pair route on (1) or the Bloom route for every pair (0); [1] pair kernel: 5, 8, 13 = k_fast_pairs_lines on
+   that many register words, 0 = k_fast_pairs on the packed words; [2] count kernel: 5, 8 = k_fast_count_sites, 0 =
+   k_fast_count (the LDS set); [3] waves per block of k_fast_count, [4] slots of a wave's set, [5] its dynamic LDS in
+   bytes (all 0 where it does not run); [6] Bloom route: the Zobrist table in LDS (1) or read from memory (0);
+   [7] the shortest sequence the pair route takes (a pair with a shorter member goes the Bloom route). */
+int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]);
+/* Of the last swa_d1_fastidious[_shard] call: out[0] pairs within two edits found by the pair route, [1] light and
+   [2] heavy amplicons handed to the Bloom route, [3] attempts the pair list took (2 or more: it was regrown; 0: the
+   pair route did not run). */
+int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]);
 
 /* ---- d = 0: dereplication -------------------------------
    Replaces the bucket search of dereplicating() (src/derep.cc:276-354: Zobrist hash, open

@@ -2336,7 +2336,7 @@ extern "C" int swa_d1_fastidious(swa_ctx * ctx, const uint8_t * is_light, uint64
 // current batch [4] variants of the current batch [5] pairs found [6] short light amplicons [7] short heavy
 // amplicons [8] nucleotides of the short light amplicons [9] scratch
 static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_heavy, uint64_t light_nt, uint32_t bloom_bits,
-                                  uint32_t pair_route_min_len) {
+                                  uint32_t pair_route_min_len, bool zlds) {
   SWA_TRY(ensure_full_index(ctx));                           // hashes of every amplicon, room for the table
   uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
   if (k < 1) { k = 1; }
@@ -2373,7 +2373,6 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   f.tasks = static_cast<swa_task *>(ctx->d_queue.ptr);
   f.task_counter = fc + 3;
   f.task_cap = task_cap;
-  const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const size_t flex_lds = sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + kWaves * (size_t)(f.maxwords + 2u)) +
                           kWaves * 256 * sizeof(swa_task);
   // light side
@@ -2439,13 +2438,81 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
 }
 
 // LDS of k_fast_count for `waves` waves per block; 0 = does not fit
-static size_t fast_count_lds(const swa_ctx * ctx, uint32_t slots, int waves) {
-  const uint32_t maxwords = (ctx->db.longest + 31u) >> 5;
-  const size_t bytes = sizeof(uint64_t) * (4ull * ctx->zobrist_len + (size_t)waves * (2ull * (maxwords + 3u) + slots));
+static size_t fast_count_lds(uint32_t longest, uint32_t slots, int waves) {
+  const uint32_t maxwords = (longest + 31u) >> 5;
+  const size_t zlen = (size_t)longest + 2u;                  // = ctx->zobrist_len (prepare_hashing)
+  const size_t bytes = sizeof(uint64_t) * (4ull * zlen + (size_t)waves * (2ull * (maxwords + 3u) + slots));
   return bytes <= 160u * 1024u ? bytes : 0;
 }
 
-static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_heavy, uint32_t slots, int count_waves) {
+// Every choice of the pass, from the longest sequence of the database alone (and the two switches): what
+// swa_d1_fastidious_shard launches and what swa_d1_fastidious_plan reports.
+//   longest      pair kernel             count kernel
+//   < 112        none: every pair on the Bloom route
+//   112 .. 159   k_fast_pairs_lines<5>   k_fast_count_sites<5>   (a microvariant of 160 nt still fits 5 words)
+//   160          k_fast_pairs_lines<5>   k_fast_count_sites<8>
+//   161 .. 255   k_fast_pairs_lines<8>   k_fast_count_sites<8>
+//   256          k_fast_pairs_lines<8>   k_fast_count, 4 waves x 4096 slots
+//   257 .. 389   k_fast_pairs_lines<13>  k_fast_count, 4 waves x 4096
+//   390 .. 416   k_fast_pairs_lines<13>  k_fast_count, 2 waves x 8192
+//   417 .. 779   k_fast_pairs            k_fast_count, 2 waves x 8192
+//   780 .. 1004  k_fast_pairs            k_fast_count, 1 wave x 16384
+//   >= 1005      none: k_fast_count's set no longer fits 160 KB; Bloom route, Zobrist table in LDS up to 3070 nt
+struct FastPlan {
+  bool pair_route;               // false: the Bloom route for every pair
+  int pair_w;                    // k_fast_pairs_lines<., W>: 5, 8, 13; 0 = k_fast_pairs on the packed words
+  int count_w;                   // k_fast_count_sites<W>: 5, 8; 0 = k_fast_count
+  int count_waves;               // k_fast_count: waves per block, slots of a wave's set, dynamic LDS
+  uint32_t slots;
+  size_t count_lds;
+  bool zobrist_lds;              // Bloom route: the Zobrist table sits in LDS
+};
+
+static FastPlan fast_plan(const swa_ctx * ctx) {
+  const uint32_t longest = ctx->db.longest;
+  FastPlan p{};
+  // which pairs the pair route can take: k_fast_count's LDS set must hold the microvariants of the longest sequence
+  p.slots = 1024;
+  { const uint64_t v = 7ull * longest + 4ull; while (p.slots < v + v / 2) { p.slots <<= 1; } }
+  for (int w : {4, 2, 1}) { if (p.count_waves == 0 && fast_count_lds(longest, p.slots, w) != 0) { p.count_waves = w; } }
+  p.count_lds = p.count_waves != 0 ? fast_count_lds(longest, p.slots, p.count_waves) : 0;
+  const char * env_route = getenv("SWA_FAST_BLOOM");          // test hook: the reference's scheme for every pair
+  p.pair_route = p.count_waves != 0 && longest >= kFastMinLen && !(env_route != nullptr && env_route[0] == '1');
+  // pairs on the amplicon lines, sequences in registers (up to 416 nt; SWA_FAST_PAIRS=words: the round-2 kernel, which
+  // walks the packed sequences — comparison switch)
+  const char * env_fp = getenv("SWA_FAST_PAIRS");
+  // (the register kernels exist for 5, 8 and 13 words: sequences up to 416 nt, which 128-byte lines hold)
+  p.pair_w = (env_fp != nullptr && env_fp[0] == 'w') ? 0 : (longest <= 160u ? 5 : (longest <= 256u ? 8 : (longest <= 416u ? 13 : 0)));
+  p.count_w = longest <= 159u ? 5 : (longest <= 255u ? 8 : 0);
+  p.zobrist_lds = 4ull * ((size_t)longest + 2u) * sizeof(uint64_t) <= kMaxZobristLds;
+  return p;
+}
+
+extern "C" int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]) {
+  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
+  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_plan: no database is resident"); }
+  const FastPlan p = fast_plan(ctx);
+  const bool set = p.pair_route && p.count_w == 0;           // k_fast_count runs
+  out[0] = p.pair_route ? 1u : 0u;
+  out[1] = p.pair_route ? (uint32_t)p.pair_w : 0u;
+  out[2] = p.pair_route ? (uint32_t)p.count_w : 0u;
+  out[3] = set ? (uint32_t)p.count_waves : 0u;
+  out[4] = set ? p.slots : 0u;
+  out[5] = set ? (uint32_t)p.count_lds : 0u;
+  out[6] = p.zobrist_lds ? 1u : 0u;
+  out[7] = kFastMinLen;
+  return SWA_OK;
+}
+
+extern "C" int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]) {
+  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
+  for (int i = 0; i < 4; ++i) { out[i] = ctx->fast_totals[i]; }
+  return SWA_OK;
+}
+
+static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_heavy, const FastPlan & plan) {
+  const uint32_t slots = plan.slots;
+  const int count_waves = plan.count_waves;
   const uint32_t n = ctx->db.n;
   auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
   if (n_light == 0 || n_heavy == 0) { return SWA_OK; }
@@ -2463,7 +2530,11 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
   SWA_TRY(swa_reserve(ctx, ctx->d_fmembers, member_cap * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fitems, uint64_t(item_cap) * sizeof(swa_fitem)));
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_tmp, ((asize_max + kScanTile - 1) / kScanTile) * sizeof(uint64_t)));
-  if (ctx->fast_pair_cap == 0) { ctx->fast_pair_cap = 4ull * n_light + (1ull << 20); }
+  if (ctx->fast_pair_cap == 0) {
+    ctx->fast_pair_cap = 4ull * n_light + (1ull << 20);
+    const char * env_cap = getenv("SWA_FAST_PAIR_CAP");       // test hook: start small, exercise the regrow path
+    if (env_cap != nullptr && atoll(env_cap) > 0) { ctx->fast_pair_cap = (uint64_t)atoll(env_cap); }
+  }
   auto * keys = static_cast<unsigned long long *>(ctx->d_fkeys.ptr);
   auto * cnt_l = static_cast<uint32_t *>(ctx->d_fcnt.ptr);
   uint32_t * cnt_h = cnt_l + asize, * cur_l = cnt_h + asize, * cur_h = cur_l + asize, * tot = cur_h + asize;
@@ -2473,13 +2544,9 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
   auto * members = static_cast<uint32_t *>(ctx->d_fmembers.ptr);
   auto * items = static_cast<swa_fitem *>(ctx->d_fitems.ptr);
   auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);
-  auto * item_counter = dflags + 8;                          // [8] item counter, [9] key table overflow
+  // [8] key table overflow, [9 + type] the item counter of each group type (kept apart: the largest is checked below)
   uint64_t npairs = 0;
-  // pairs on the amplicon lines, sequences in registers (up to 416 nt; SWA_FAST_PAIRS=words: the round-2 kernel, which
-  // walks the packed sequences — comparison switch)
-  const char * env_fp = getenv("SWA_FAST_PAIRS");
-  // (the register kernels exist for 5, 8 and 13 words: sequences up to 416 nt, which 128-byte lines hold)
-  const int pair_w = (env_fp != nullptr && env_fp[0] == 'w') ? 0 : (ctx->db.longest <= 160u ? 5 : (ctx->db.longest <= 256u ? 8 : (ctx->db.longest <= 416u ? 13 : 0)));
+  const int pair_w = plan.pair_w;
   if (pair_w != 0) {
     SWA_TRY(launch_abundance_rank(ctx));
     SWA_TRY(ensure_lines(ctx));
@@ -2488,15 +2555,17 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
   for (int attempt = 0; attempt < 6; ++attempt) {
     SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->fast_pair_cap * sizeof(uint64_t)));
     SWA_HIP(ctx, hipMemsetAsync(fc + 5, 0, sizeof(uint64_t), ctx->stream));
-    SWA_HIP(ctx, hipMemsetAsync(dflags + 9, 0, sizeof(uint32_t), ctx->stream));
+    SWA_HIP(ctx, hipMemsetAsync(dflags + 8, 0, 4 * sizeof(uint32_t), ctx->stream));
+    ctx->fast_totals[3] = (uint64_t)attempt + 1u;
     for (int type = 0; type < 3; ++type) {
+      uint32_t * item_counter = dflags + 9 + type;
       asize = type == 2 ? asize_max : asize_ends;
       cnt_h = cnt_l + asize; cur_l = cnt_h + asize; cur_h = cur_l + asize; tot = cur_h + asize;
       const uint32_t tiles = (uint32_t)((asize + kScanTile - 1) / kScanTile);
       FastGroupArgs g{};
       g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen;
       g.role = static_cast<const uint8_t *>(ctx->d_frole.ptr); g.n = n;
-      g.keys = keys; g.cnt_l = cnt_l; g.cnt_h = cnt_h; g.amask = asize - 1; g.lslot = lslot; g.hslot = hslot; g.overflow = dflags + 9;
+      g.keys = keys; g.cnt_l = cnt_l; g.cnt_h = cnt_h; g.amask = asize - 1; g.lslot = lslot; g.hslot = hslot; g.overflow = dflags + 8;
       const dim3 gn(grid_for(ctx, n, 256, 8)), ga(grid_for(ctx, asize, 256, 8)), b(256);
       hipLaunchKernelGGL(k_fg_clear, ga, b, 0, ctx->stream, keys, cnt_l, cnt_h, cur_l, cur_h, asize);
       if (type == 0) { hipLaunchKernelGGL(k_fg_light<0>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<0>, gn, b, 0, ctx->stream, g); }
@@ -2510,7 +2579,6 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
       if (type == 0) { hipLaunchKernelGGL(k_fg_scatter<0>, gn, b, 0, ctx->stream, g, offsets, cur_l, cur_h, members); }
       else if (type == 1) { hipLaunchKernelGGL(k_fg_scatter<1>, gn, b, 0, ctx->stream, g, offsets, cur_l, cur_h, members); }
       else { hipLaunchKernelGGL(k_fg_scatter<2>, gn, b, 0, ctx->stream, g, offsets, cur_l, cur_h, members); }
-      SWA_HIP(ctx, hipMemsetAsync(item_counter, 0, sizeof(uint32_t), ctx->stream));
       hipLaunchKernelGGL(k_fg_items, ga, b, 0, ctx->stream, cnt_l, cnt_h, offsets, asize, items, item_counter, item_cap);
       FastPairArgs p{};
       p.seqs = ctx->db.seqs; p.seq_off = ctx->db.seq_off; p.seqlen = ctx->db.seqlen; p.members = members;
@@ -2538,11 +2606,14 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
       SWA_HIP(ctx, hipGetLastError());
     }
     uint64_t got = 0;
-    uint32_t fl[2] = {0, 0};
+    uint32_t fl[4] = {0, 0, 0, 0};
     SWA_HIP(ctx, hipMemcpyAsync(&got, fc + 5, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipMemcpyAsync(fl, dflags + 8, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (fl[1] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, "swa_d1_fastidious: group key table overflow"); }   // cannot happen: load <= 0.5
+    if (fl[0] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, "swa_d1_fastidious: group key table overflow"); }   // cannot happen: load <= 0.5
+    // (cannot happen either: a group of l light and h heavy amplicons makes at most l + h / 2 items,
+    // tests/test_fastidious_identity.py; the kernels drop what lies past the cap, so say it)
+    if (std::max(fl[1], std::max(fl[2], fl[3])) > item_cap) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_d1_fastidious: work item list overflow"); }
     if (got <= ctx->fast_pair_cap) { npairs = got; break; }
     if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_d1_fastidious: pair list keeps overflowing"); }
     ctx->fast_pair_cap = got + got / 8 + 1024;               // the count of a complete run: size for it (+ slack: none needed, it is exact)
@@ -2556,15 +2627,14 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     c.zlen = ctx->zobrist_len; c.maxwords = (ctx->db.longest + 31u) >> 5; c.slots = slots;
     c.pairs = static_cast<const unsigned long long *>(ctx->d_fpairs.ptr); c.npairs = npairs;
     c.graft = static_cast<uint32_t *>(ctx->d_graft.ptr); c.cand_counter = fc + 2;
-    const bool by_sites = ctx->db.longest <= 255u;
-    if (by_sites) {
+    if (plan.count_w != 0) {
       uint64_t blocks = (npairs + kWaves - 1) / kWaves;
       const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
       if (blocks > max_blocks) { blocks = max_blocks; }
-      if (ctx->db.longest <= 159u) { hipLaunchKernelGGL(k_fast_count_sites<5>, dim3((uint32_t)blocks), dim3(kThreads), 0, ctx->stream, c); }
+      if (plan.count_w == 5) { hipLaunchKernelGGL(k_fast_count_sites<5>, dim3((uint32_t)blocks), dim3(kThreads), 0, ctx->stream, c); }
       else { hipLaunchKernelGGL(k_fast_count_sites<8>, dim3((uint32_t)blocks), dim3(kThreads), 0, ctx->stream, c); }
     } else {
-    const size_t lds = fast_count_lds(ctx, slots, count_waves);
+    const size_t lds = plan.count_lds;
     uint64_t blocks = (npairs + count_waves - 1) / count_waves;
     const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
     if (blocks > max_blocks) { blocks = max_blocks; }
@@ -2623,13 +2693,9 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   });
   const uint64_t n_heavy = hi - lo;
 
-  // which pairs the pair route can take: k_fast_count's LDS set must hold the microvariants of the longest sequence
-  uint32_t slots = 1024;
-  { const uint64_t v = 7ull * ctx->db.longest + 4ull; while (slots < v + v / 2) { slots <<= 1; } }
-  int count_waves = 0;
-  for (int w : {4, 2, 1}) { if (count_waves == 0 && fast_count_lds(ctx, slots, w) != 0) { count_waves = w; } }
-  const char * env_route = getenv("SWA_FAST_BLOOM");          // test hook: the reference's scheme for every pair
-  const bool pair_route = count_waves != 0 && ctx->db.longest >= kFastMinLen && !(env_route != nullptr && env_route[0] == '1');
+  const FastPlan plan = fast_plan(ctx);
+  const bool pair_route = plan.pair_route;
+  for (uint64_t & t : ctx->fast_totals) { t = 0; }
   const uint32_t min_len = pair_route ? kFastMinLen : 0xFFFFFFFFu;
 
   SWA_TRY(swa_reserve(ctx, ctx->d_frole, n));
@@ -2657,9 +2723,9 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   SWA_HIP(ctx, hipMemcpyAsync(shorts, fc + 6, sizeof(shorts), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (role is a host temporary, too)
 
-  if (pair_route) { SWA_TRY(fastidious_pair_route(ctx, (uint32_t)n_light, (uint32_t)n_heavy, slots, count_waves)); }
+  if (pair_route) { SWA_TRY(fastidious_pair_route(ctx, (uint32_t)n_light, (uint32_t)n_heavy, plan)); }
   if (shorts[0] != 0 && shorts[1] != 0) {
-    SWA_TRY(fastidious_bloom_route(ctx, (uint32_t)shorts[0], (uint32_t)shorts[1], shorts[2], bloom_bits, min_len));
+    SWA_TRY(fastidious_bloom_route(ctx, (uint32_t)shorts[0], (uint32_t)shorts[1], shorts[2], bloom_bits, min_len, plan.zobrist_lds));
   }
 
   uint64_t host_fc[8] = {};
@@ -2672,5 +2738,6 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   counters[2] = host_fc[2];
   counters[3] = m;
   counters[4] = k;
+  for (int i = 0; i < 3; ++i) { ctx->fast_totals[i] = host_fc[5 + i]; }
   return SWA_OK;
 }

@@ -129,6 +129,7 @@ struct swa_ctx {
   // work items, the (heavy, light) pairs within two edits
   swa_dbuf d_frole, d_fkeys, d_fcnt, d_foff, d_fslot, d_fmembers, d_fitems, d_fpairs;
   uint64_t fast_pair_cap = 0;
+  uint64_t fast_totals[4] = {};  // of the last pass: pairs found, short light / heavy amplicons, attempts of the pair list
 
   // d >= 2 in bulk (dn_graph.hip): the graph of all pairs within d differences, kept sorted on the device
   uint32_t dn_shortest = 0;      // shortest sequence of the database (0 = not measured yet)

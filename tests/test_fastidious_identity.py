@@ -8,7 +8,9 @@ on the CPU against the oracle (which is pinned to the reference):
   * two sequences of >= 112 nt within two edits share their first 32 nt, or their last 32, or the window
     [40, 72) of one equals the window at 39 / 40 / 41 of the other."""
 import numpy as np
+import pytest
 
+import fastidious_sets as FS
 import support as S
 
 
@@ -359,3 +361,79 @@ def test_two_edit_test_on_register_words_is_exact():
         yes += want
         no += not want
     assert yes > 1500 and no > 500
+
+
+# ---- the work item list of the pair route (d1.hip: fastidious_pair_route, d1_fast.inc: k_fg_items) -------------------------
+def _items_of(l: int, h: int) -> int:
+    """k_fg_items: a group's 64 x 64 tiles, dealt to at most kFastStride = 64 items; none without both kinds"""
+    if l == 0 or h == 0:
+        return 0
+    return min(((l + 63) // 64) * ((h + 63) // 64), 64)
+
+
+def _item_cap(n_light: int, n_heavy: int) -> int:
+    return min(3 * n_light + (3 * n_light + n_heavy) // 2 + 64, 0xFFFFFFF0)
+
+
+def test_item_cap_holds_for_adversarial_group_shapes():
+    """The pair kernels drop items past item_cap (and the library now fails loudly if that ever happens).  It cannot:
+    a group of l light and h heavy members makes min(ceil(l / 64) ceil(h / 64), 64) <= l + h / 2 items (one tile row:
+    ceil(h / 64) <= h / 2 from h = 65 on, and 1 <= l; more rows: 64 <= l), a light amplicon is a member of at most
+    three groups of a type (the middle windows) and a heavy one of one, so a type's items are at most 3 n_light +
+    n_heavy / 2 < item_cap.  Checked on the bound itself for all small groups and on the shapes that come closest."""
+    for l in range(1, 300):
+        for h in list(range(1, 300)) + [4033, 4096, 4097, 100000]:
+            assert 2 * _items_of(l, h) <= 2 * l + h, (l, h)
+    shapes = {
+        "all lights in one group": lambda n: ([(n, n // 7 + 1)], n, n // 7 + 1),
+        "65 x 65": lambda n: ([(65, 65)] * n, 65 * n, 65 * n),
+        "65 x 4033": lambda n: ([(65, 4033)] * n, 65 * n, 4033 * n),
+        "449 x 449": lambda n: ([(449, 449)] * n, 449 * n, 449 * n),
+        "n groups of 1 x 1": lambda n: ([(1, 1)] * n, n, n),
+        # the middle type: every light amplicon in three groups of its own, one heavy amplicon in each
+        "three memberships per light": lambda n: ([(1, 1)] * (3 * n), n, 3 * n),
+        "three memberships, 64 lights a group": lambda n: ([(64, 1)] * (3 * n), 64 * n, 3 * n),
+        "one light, 65 heavies": lambda n: ([(1, 65)] * n, n, 65 * n),
+    }
+    for name, make in shapes.items():
+        for n in (1, 2, 63, 64, 65, 1000, 100000):
+            groups, n_light, n_heavy = make(n)
+            assert sum(l for l, _ in groups) <= 3 * n_light and sum(h for _, h in groups) <= n_heavy, name
+            assert sum(_items_of(l, h) for l, h in groups) <= _item_cap(n_light, n_heavy), (name, n)
+
+
+# ---- the dispatch table of the pass (d1.hip: fast_plan), restated in tests/fastidious_sets.py -----------------------------
+def test_restated_plan_gives_the_dispatch_table():
+    spans = []                                                # (first, last, plan[:5] + [plan[6]]) of every run of equal plans
+    for longest in range(34, 3300):
+        key = tuple(FS.expected_plan(longest)[:5] + FS.expected_plan(longest)[6:7])
+        if spans and spans[-1][2] == key:
+            spans[-1][1] = longest
+        else:
+            spans.append([longest, longest, key])
+    assert [tuple(v) for v in spans] == [
+        (34, 111, (0, 0, 0, 0, 0, 1)), (112, 159, (1, 5, 5, 0, 0, 1)), (160, 160, (1, 5, 8, 0, 0, 1)),
+        (161, 255, (1, 8, 8, 0, 0, 1)), (256, 256, (1, 8, 0, 4, 4096, 1)), (257, 389, (1, 13, 0, 4, 4096, 1)),
+        (390, 416, (1, 13, 0, 2, 8192, 1)), (417, 779, (1, 0, 0, 2, 8192, 1)), (780, 1004, (1, 0, 0, 1, 16384, 1)),
+        (1005, 3070, (0, 0, 0, 0, 0, 1)), (3071, 3299, (0, 0, 0, 0, 0, 0))]
+    assert FS.expected_plan(1004)[5] == 163824 and FS.expected_plan(400)[5] == 144448
+    assert FS.expected_plan(150, words=True)[:3] == [1, 0, 5] and FS.expected_plan(150, bloom=True)[:3] == [0, 0, 0]
+
+
+# ---- the generated sets are worth running: checked on the oracle's output, where the oracle runs ----------------------------
+@pytest.mark.parametrize("L", FS.NATURAL + [150])
+def test_edit_atlas_is_not_trivial(tmp_path, L):
+    db, flags, three = FS.build_case(L, tmp_path / "in.fa")
+    assert db.longest == L and 300 <= db.n <= 3000
+    graft, counters = S.oracle_fastidious(db, flags, 16)
+    FS.assert_not_trivial(db, flags, graft, three)
+
+
+def test_outlier_sorts_last_and_changes_no_graft(tmp_path):
+    db, flags, three = FS.build_case(150, tmp_path / "in.fa")
+    odb, oflags, _ = FS.build_case(150, tmp_path / "out.fa", 500)
+    assert odb.longest == 500 and odb.n == db.n + 1 and odb.headers[-1].decode() == FS.OUTLIER and odb.headers[:-1] == db.headers
+    assert np.array_equal(oflags[:-1], flags) and oflags[-1] == 1
+    graft, counters = S.oracle_fastidious(db, flags, 16)
+    ograft, ocounters = S.oracle_fastidious(odb, oflags, 16)
+    assert np.array_equal(ograft[:-1], graft) and ograft[-1] == FS.NO_GRAFT and int(ocounters[2]) == int(counters[2])
