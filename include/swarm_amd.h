@@ -371,6 +371,10 @@ int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * seeds, const
 int swa_scan_fetch(swa_ctx * ctx, uint32_t * hit_seedidx, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap);
 /* out3 = {q-gram comparisons, aligned pairs, launch sequences} since swa_scan_begin */
 int swa_scan_totals(swa_ctx * ctx, uint64_t * out3);
+/* test / triage read: out4 = {current capacity (pairs) of the scan's pair arrays, batches redone after the pair arrays
+   overflowed, re-lists of the candidate list, batches whose hits were fetched by copy (more than the pinned mirror
+   holds)}; the three counts run from the creation of the context */
+int swa_scan_debug_state(swa_ctx * ctx, uint64_t * out4);
 
 /* ---- B5: the uclust alignments ------------------------------------------------------------
    Seam B5 (src/algod1.cc:880-925, src/algo.cc:608-659, src/nw.cc:237-255): npairs global alignments of amplicon

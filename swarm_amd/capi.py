@@ -724,6 +724,46 @@ class Context:
                                            _ptr(alens)))
         return scores, diffs, alens
 
+    # ---- B3 + B4 fused, one batch of (sub)seeds at a time (scan.hip); after qgram_build + search_begin
+    def scan_begin(self) -> None:
+        _declare_dn(self.lib)
+        self._check(self.lib.swa_scan_begin(self.h))
+
+    def scan_batch(self, seeds, radii, lowest_unswarmed: int, first_generation: bool, ncb: bool, cap: int | None = None):
+        """One swa_scan_batch call with room for `cap` hits (default: the database): (return code, nhits, seed indices,
+        ids, diffs) — the three arrays hold min(nhits, cap) sorted triples after SWA_OK and nothing after another code."""
+        _declare_dn(self.lib)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        radii = np.ascontiguousarray(radii, dtype=np.uint32)
+        assert seeds.shape == radii.shape
+        cap = self.n if cap is None else int(cap)
+        sidx, ids, diffs = (np.zeros(max(1, cap), dtype=np.uint32) for _ in range(3))
+        nh = C.c_uint32(0)
+        rc = self.lib.swa_scan_batch(self.h, seeds.shape[0], _ptr(seeds), _ptr(radii), int(lowest_unswarmed), int(first_generation),
+                                     int(ncb), _ptr(sidx), _ptr(ids), _ptr(diffs), cap, C.byref(nh))
+        k = min(int(nh.value), cap) if rc == SWA_OK else 0
+        return rc, int(nh.value), sidx[:k], ids[:k], diffs[:k]
+
+    def scan_fetch(self, nhits: int):
+        """swa_scan_fetch: the sorted (seed indices, ids, diffs) of the most recent scan_batch"""
+        _declare_dn(self.lib)
+        sidx, ids, diffs = (np.zeros(max(1, int(nhits)), dtype=np.uint32) for _ in range(3))
+        self._check(self.lib.swa_scan_fetch(self.h, _ptr(sidx), _ptr(ids), _ptr(diffs), int(nhits)))
+        return sidx[:nhits], ids[:nhits], diffs[:nhits]
+
+    def scan_totals(self) -> dict:
+        _declare_dn(self.lib)
+        out = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.swa_scan_totals(self.h, _p64(out)))
+        return {"qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
+
+    def scan_debug_state(self) -> dict:
+        """swa_scan_debug_state: which of the scan step's rare branches this context has taken"""
+        _declare_dn(self.lib)
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.swa_scan_debug_state(self.h, _p64(out)))
+        return {"pair_cap": int(out[0]), "redone": int(out[1]), "relists": int(out[2]), "by_copy": int(out[3])}
+
     def nw_batch(self, d_ids, q_ids, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
         """Seam B5 (swa_nw_batch): global alignments of amplicons d_ids[k] (member) against q_ids[k] (seed) of the
         resident database -> (diffs, columns, list of CIGAR strings)."""
@@ -779,7 +819,7 @@ class Context:
 
 _DN_EXPORTS = ["swa_dn_cluster", "swa_dn_result_free", "swa_dn_result_error", "swa_dn_result_summary", "swa_dn_result_over_graph",
                "swa_dn_write_swarms", "swa_dn_write_stats", "swa_dn_write_structure", "swa_dn_write_seeds",
-               "swa_dn_write_uclust", "swa_d1_write_uclust", "swa_scan_begin", "swa_scan_step", "swa_scan_batch", "swa_scan_fetch", "swa_scan_totals",
+               "swa_dn_write_uclust", "swa_d1_write_uclust", "swa_scan_begin", "swa_scan_step", "swa_scan_batch", "swa_scan_fetch", "swa_scan_totals", "swa_scan_debug_state",
                "swa_dn_graph_supported", "swa_dn_graph", "swa_dn_graph_totals", "swa_dn_graph_resident", "swa_dn_parent_diffs",
                "swa_multi_create", "swa_multi_destroy", "swa_multi_size", "swa_multi_uses_rccl", "swa_multi_ctx", "swa_multi_last_error",
                "swa_multi_db_upload", "swa_multi_d1_network", "swa_multi_d1_fastidious", "swa_dn_set_ownership", "swa_multi_dn_begin",
@@ -819,7 +859,11 @@ def _declare_dn(lib) -> None:
     lib.swa_scan_begin.argtypes = [C.c_void_p]
     lib.swa_scan_step.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_uint32, u32p]
+    lib.swa_scan_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_uint32, u32p]
+    lib.swa_scan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.swa_scan_totals.argtypes = [C.c_void_p, u64p]
+    lib.swa_scan_debug_state.argtypes = [C.c_void_p, u64p]
     lib.swa_dn_write_uclust_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64]
     lib.swa_d1_write_uclust_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint64,
                                             C.c_uint64, C.c_uint64]

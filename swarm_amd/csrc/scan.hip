@@ -27,6 +27,7 @@
 #include "swa_internal.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <vector>
 
 int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, const uint32_t * d_targets,
@@ -67,6 +68,16 @@ struct ScanArgs {
 // ONE address per launch serialise in L2 (~100 per us) and were 90 % of the pool scan's time.
 // Every workgroup adds its sum to its own slot of a 4096-entry table (summed by swa_scan_totals).
 constexpr uint32_t kCompareSlots = 4096;
+
+int scan_compare_sum(swa_ctx * ctx, uint64_t * sum) {
+  std::vector<unsigned long long> slots(kCompareSlots);
+  SWA_HIP(ctx, hipMemcpyAsync(slots.data(), ctx->d_scan_compares.ptr, kCompareSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *sum = 0;
+  for (unsigned long long v : slots) { *sum += v; }
+  return SWA_OK;
+}
+
 __device__ __forceinline__ void add_comparisons(const ScanArgs & a, unsigned long long compared) {
   __shared__ unsigned long long block_sum;
   if (threadIdx.x == 0) { block_sum = 0ull; }
@@ -244,6 +255,8 @@ extern "C" int swa_scan_begin(swa_ctx * ctx) {
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_scan_swarmed.ptr, 0, n, ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_scan_counters.ptr, 0, 64, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->scan_launches = 0;                                  // (the totals count from here: swarm_amd.h)
+  ctx->scan_compare_discount = 0;
   ctx->scan_ready = true;
   return SWA_OK;
 }
@@ -284,8 +297,13 @@ extern "C" int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * s
   const uint32_t span = n - lo;
   // pair capacity: a first guess that is grown (and the batch redone) if it ever overflows
   uint64_t pair_cap = ctx->scan_pair_cap;
-  if (pair_cap == 0) { pair_cap = std::max<uint64_t>(1u << 16, (uint64_t)n); }
+  if (pair_cap == 0) {
+    pair_cap = std::max<uint64_t>(1u << 16, (uint64_t)n);
+    const char * env_cap = getenv("SWA_SCAN_PAIR_CAP");       // test hook: start small, exercise the redo path
+    if (env_cap != nullptr && atoll(env_cap) > 0) { pair_cap = (uint64_t)atoll(env_cap); }
+  }
   uint32_t got = 0;
+  uint64_t failed_passes = 0, compared_at_fail = 0;
   ++ctx->scan_launches;
   for (;;) {
     SWA_TRY(swa_reserve(ctx, ctx->d_scan_targets, 3 * pair_cap * sizeof(uint32_t)));
@@ -332,6 +350,7 @@ extern "C" int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * s
         hipLaunchKernelGGL(k_scan_filter, dim3((unsigned)blocks, nseeds), dim3(256), 0, ctx->stream, a);
       } else {
         if (relist) {                                      // (rare) the radius outgrew the list: collect it again, wider
+          ++ctx->scan_relists;
           ctx->scan_cand_bound = std::max(2u * ctx->scan_cand_bound, max_limit);
           hipLaunchKernelGGL(k_scan_relist, dim3((unsigned)std::min<uint64_t>(((uint64_t)span + 255) / 256, uint64_t(ctx->num_cus) * 8)),
                              dim3(256), 0, ctx->stream, a.est, a.swarmed, lo, n, ctx->scan_cand_bound, a.cand, a.cand_count);
@@ -356,7 +375,11 @@ extern "C" int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * s
     if (ctx->scan_host[2] != 0u) {
       // more (seed, target) pairs than the buffers hold.  Nothing irreversible happened (est
       // stores are idempotent, k_scan_collect marks nothing when the flag is set), so grow and
-      // run the batch again.
+      // run the batch again.  The pass counted its q-gram comparisons, and the next pass makes
+      // the same ones again (same pool, same list): the repeats leave the statistic below.
+      SWA_TRY(scan_compare_sum(ctx, &compared_at_fail));
+      ++failed_passes;
+      ++ctx->scan_redone;
       pair_cap = std::max<uint64_t>(2 * pair_cap, (uint64_t)ctx->scan_host[0] + 1024);
       continue;
     }
@@ -365,11 +388,17 @@ extern "C" int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * s
     if (got <= kMirrorHits) {
       std::copy(mirror + 4, mirror + 4 + 3 * (size_t)got, ctx->scan_host.begin() + 4);
     } else {                                                 // more hits than the mirror holds: fetch them all
+      ++ctx->scan_by_copy;
       SWA_HIP(ctx, hipMemcpyAsync(ctx->scan_host.data() + 4, hits + 4, 3 * (size_t)got * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, ctx->stream));
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     break;
+  }
+  if (failed_passes != 0) {
+    uint64_t compared_now = 0;
+    SWA_TRY(scan_compare_sum(ctx, &compared_now));
+    ctx->scan_compare_discount += failed_passes * (compared_now - compared_at_fail);
   }
   *nhits = got;
   // queue order of the seeds, then pool (= id) order of the targets; kept in the context so
@@ -419,13 +448,18 @@ extern "C" int swa_scan_totals(swa_ctx * ctx, uint64_t * out3) {
   if (!ctx->scan_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_scan_totals: no scan state"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   uint64_t t[4] = {};
-  std::vector<unsigned long long> slots(kCompareSlots);
   SWA_HIP(ctx, hipMemcpyAsync(t, static_cast<uint32_t *>(ctx->d_scan_counters.ptr) + 4, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipMemcpyAsync(slots.data(), ctx->d_scan_compares.ptr, kCompareSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint64_t compared = 0;
-  for (unsigned long long v : slots) { compared += v; }
-  out3[0] = compared; out3[1] = t[1]; out3[2] = ctx->scan_launches;
+  SWA_TRY(scan_compare_sum(ctx, &compared));
+  out3[0] = compared - ctx->scan_compare_discount; out3[1] = t[1]; out3[2] = ctx->scan_launches;
+  return SWA_OK;
+}
+
+// test / triage read: {pair capacity, batches redone after a pair overflow, candidate re-lists, batches whose hits
+// came by copy instead of from the pinned mirror}; the last three count from the creation of the context
+extern "C" int swa_scan_debug_state(swa_ctx * ctx, uint64_t * out4) {
+  if (ctx == nullptr || out4 == nullptr) { return SWA_E_ARG; }
+  out4[0] = ctx->scan_pair_cap; out4[1] = ctx->scan_redone; out4[2] = ctx->scan_relists; out4[3] = ctx->scan_by_copy;
   return SWA_OK;
 }
 

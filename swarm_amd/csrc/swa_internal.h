@@ -122,6 +122,8 @@ struct swa_ctx {
   std::vector<uint64_t> scan_sorted;
   uint64_t scan_pair_cap = 0;
   uint64_t scan_launches = 0;
+  uint64_t scan_compare_discount = 0;   // comparisons of passes that overflowed the pair arrays and were redone
+  uint64_t scan_redone = 0, scan_relists = 0, scan_by_copy = 0;   // swa_scan_debug_state
 
   // fastidious state
   swa_dbuf d_light, d_graft, d_bloomflex, d_fpatterns, d_queue, d_fcounters;
