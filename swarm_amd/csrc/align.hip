@@ -65,14 +65,7 @@ __device__ __forceinline__ uint32_t select_u32(bool c, uint32_t x, uint32_t y) {
   return (x & m) | (y & ~m);
 }
 
-// value of `v` in the neighbouring lane (full-wave DPP shifts, GFX9 family): a few cycles
-// instead of an LDS-crossbar ds_bpermute on the critical path of every anti-diagonal step
-__device__ __forceinline__ uint32_t from_lane_below(uint32_t v) {   // lane i <- lane i-1
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t from_lane_above(uint32_t v) {   // lane i <- lane i+1
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
-}
+#include "wave_ops.inc"   // from_lane_below, from_lane_above
 
 // Lane layout of one pair's group of G lanes: lane 0 and the lanes above 2W+1 are GUARD lanes,
 // lanes 1 .. 2W+1 carry the band offsets -W .. +W.  A guard lane never computes a cell, so what

@@ -279,11 +279,7 @@ __device__ __forceinline__ uint64_t enumerate_variants(const uint64_t * sw, uint
   return H;
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+#include "wave_ops.inc"   // wave_lds_sync
 
 // one probe of the candidate (hash h, edit code) drawn from the queue: walk the cluster,
 // apply the abundance rule, verify exactly (algod1.cc:558-603, variants.cc:118-165).

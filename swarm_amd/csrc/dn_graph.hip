@@ -237,11 +237,7 @@ struct PairArgs {
   uint64_t pair_cap;
 };
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+#include "wave_ops.inc"   // wave_lds_sync
 
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
   const int lo = __shfl((int)(uint32_t)v, src, 64);

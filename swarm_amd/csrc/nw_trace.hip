@@ -7,34 +7,34 @@
 // bits (src/nw.cc:91-103), same walk-back priority and state machine (src/nw.cc:139-172), so the result is equal bit for
 // bit, not merely equally optimal.
 //
-//   * banded: a group of G lanes aligns one pair, lane <-> band offset (column - row), one anti-diagonal per step, one DPP
-//     shift each way per step (as k_align in align.hip).  Lane 0 and the lanes above 2W + 1 are guards that hold the
-//     "outside the band" value for ever, so W = (G - 3) / 2: 6, 14, 30 for G = 16, 32, 64.
-//   * direction bits: 4 per cell, kept in LDS, one u32 column per lane (8 cells of its diagonal per word; cell (r, c)
-//     is cell min(r, c) of diagonal c - r).  One lane then walks back exactly as swa_nw_align does and writes the
-//     run-length CIGAR right to left into LDS; the group copies it out to a packed text buffer.
-//   * certificate: the result is accepted only when the band's end cost C satisfies C < gapopen + (W + 1) * gapextend.
-//     Any path that touches a cell outside the band has paid one gap opening and W + 1 gap columns by then; every value
-//     the walk-back compares has its smaller side <= C; so each comparison it reads — and each direction bit — is the
-//     full matrix's.  The argument uses neither where the bits are kept nor how many offsets a lane
-//     holds, so it covers the wide tiers below word for word.  Pairs that fail go to the next wider tier.
-//   * wide tiers (k_nw_trace_wide<K>, K = 1, 2, 4, 8): one wave aligns one pair, each of its 64 lanes owns K adjacent band
-//     offsets in registers (offset index x = lane * K + j; x = 0 and x > 2W + 1 are the guards), so W = (64 K - 3) / 2:
-//     30, 62, 126, 254.  Only a lane's outermost offsets cross to its neighbours, one DPP shift each way per anti-
-//     diagonal; for K > 1 the offsets of one parity are live on a step, so a step touches K / 2 cells per lane.  The
-//     direction bits go to a global scratch slot per wave, laid out [word][j][lane] (one word per lane = one 256-byte
-//     line); the walking lane reads them back through L2 with the last word kept in a register (8 cells of a diagonal
-//     run share it).  They take what the LDS tiers cannot: min(dl, ql) > 1024, |dl - ql| > 30, and what the 64-lane LDS
-//     tier failed to certify.  Slots are sized by the slice's longest min(dl, ql) and the grid is cut until they fit
-//     kBitsBudget.
-//   * the host (swa_nw_align, inside the same call) aligns what is left: pairs the widest tier cannot certify (|dl - ql|
-//     > 254 or an end cost of at least gapopen + 255 gapextend), pairs with dl + ql > kWideMaxSum, pairs whose costs
-//     could overflow 32 bits, and pairs that found the text buffer full (sent there at once, and counted).
+// What carries that equality is written once and both kernel templates call it: nw_cell (one cell of the recurrence),
+// nw_walk_back (one lane walks back and writes the run-length CIGAR into LDS) and nw_store_text (room in the packed text
+// buffer, the copy out of LDS, the pair's result; or "full").  The kernels differ in where a band offset (column - row)
+// lives, where the direction bits are kept and what a full text buffer means:
+//   * LDS tiers (k_nw_trace<G>, G = 16, 32, 64): a group of G lanes aligns one pair, lane <-> band offset, one anti-
+//     diagonal and one DPP shift each way per step (as k_align in align.hip).  Lane 0 and the lanes above 2W + 1 are guards
+//     that hold the "outside the band" value for ever, so W = (G - 3) / 2: 6, 14, 30.  Direction bits: LDS, one u32 column
+//     per lane.  A pair that finds the text buffer full goes to the next list, like one that is not certified.
+//   * wide tiers (k_nw_trace_wide<K>, K = 1, 2, 4, 8): one wave aligns one pair, each lane owns K adjacent band offsets in
+//     registers (offset index x = lane * K + j; x = 0 and x > 2W + 1 are the guards), so W = (64 K - 3) / 2: 30, 62, 126,
+//     254.  Only a lane's outermost offsets cross to its neighbours; for K > 1 the offsets of one parity are live on a
+//     step, K / 2 cells per lane.  Direction bits: a global scratch slot per wave, laid out [word][j][lane] (a word per
+//     lane = one 256-byte line), read back through L2 by the walking lane.  They take what the LDS tiers cannot: min(dl,
+//     ql) > 1024, |dl - ql| > 30, and what the 64-lane tier failed to certify.  Slots are sized by the slice's longest
+//     min(dl, ql) and the grid is cut until they fit kBitsBudget.  A pair that finds the text buffer full goes to the
+//     host at once, and is counted.
+//   * certificate: a result is accepted only when the band's end cost C satisfies C < gapopen + (W + 1) * gapextend.  A
+//     path that leaves the band has paid one gap opening and W + 1 gap columns by then, and every value the walk-back
+//     compares has its smaller side <= C; so each direction bit it reads is the full matrix's, wherever
+//     the bits are kept.  Pairs that fail go to a wider tier (kTier says which).
+//   * the host (swa_nw_align, inside the same call) aligns what is left: pairs the widest tier cannot certify, pairs with
+//     dl + ql > kWideMaxSum, pairs whose costs could overflow 32 bits, and the pairs a wide tier could not store.
 #include "swa_internal.h"
 #include "host/nw_host.h"
 #include "host/pool.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 
 namespace {
@@ -52,6 +52,19 @@ constexpr uint64_t kTextPerWidePair = 256;        // more CIGAR room for a pair 
 constexpr uint64_t kSlice = 1u << 20;             // pairs per device pass: device memory does not grow with the batch
 constexpr uint64_t kTextPerPair = 48;             // packed CIGAR room per pair (a pair that finds it full goes to the host)
 constexpr int kBlock = 64;                        // one wave per workgroup
+
+constexpr int lds_half_width(int G) { return (G - 3) / 2; }              // G lanes, one band offset each, two guards
+constexpr int wide_half_width(int K) { return (kBlock * K - 3) / 2; }    // 64 lanes, K band offsets each
+
+// the device's status block behind the lists
+struct NwStatus {
+  uint32_t count[kLists + 1];      // entries of each list (the tiers append to later ones; list kLists is the host's)
+  unsigned long long text_used;    // bytes asked of the packed text buffer (may pass its size)
+  uint32_t text_full;              // pairs a wide tier certified but could not store
+};
+constexpr size_t kStatusRoom = 64;   // bytes kept for it
+static_assert(sizeof(NwStatus) <= kStatusRoom && offsetof(NwStatus, count) == 0 && offsetof(NwStatus, text_used) == 4 * (kLists + 1) &&
+              offsetof(NwStatus, text_used) % 8 == 0 && offsetof(NwStatus, text_full) == offsetof(NwStatus, text_used) + 8, "NwStatus layout");
 
 struct NwArgs {
   const uint64_t * seqs;
@@ -81,24 +94,99 @@ struct NwArgs {
   uint32_t * host_count;
 };
 
-__device__ __forceinline__ uint32_t from_lane_below(uint32_t v) {   // lane i <- lane i-1
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t from_lane_above(uint32_t v) {   // lane i <- lane i+1
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+#include "wave_ops.inc"   // from_lane_below, from_lane_above, wave_mem_sync
+
 __device__ __forceinline__ uint32_t nt_at(const uint64_t * w, int p) { return (uint32_t)(w[p >> 5] >> ((p & 31) << 1)) & 3u; }
+
+struct NwCell { uint32_t h, bits, e, f; };   // cost, direction bits, the horizontal / vertical gap state handed on
+
+// A cell from the horizontal gap state of (r, c - 1), the vertical gap state of (r - 1, c) and H(r - 1, c - 1).  The callers
+// put the borders in (host/nw_host.cpp): H(-1, c) = go + (c + 1) ge, H(r, -1) = go + (r + 1) ge, H(-1, -1) = 0; horizontal
+// state entering column 0 = 2 go + (r + 2) ge, vertical state entering row 0 = 2 go + (c + 2) ge.  (Taking r and c in here
+// changes the induction variables the compiler picks for the anti-diagonal loops: profiles/r11/NOTES.md.)
+__device__ __forceinline__ NwCell nw_cell(uint32_t across, uint32_t down, uint32_t diag, bool mis, uint32_t mm,
+                                          uint32_t go, uint32_t ge) {
+  uint32_t h = diag + (mis ? mm : 0u);
+  uint32_t bits = 0;
+  if (across < h) { bits |= kUp; h = across; }
+  if (down < h) { h = down; }
+  if (down == h) { bits |= kLeft; }
+  const uint32_t opened = h + go + ge;
+  const uint32_t across_n = across + ge, down_n = down + ge;
+  if (across_n < opened) { bits |= kExtUp; }
+  if (down_n < opened) { bits |= kExtLeft; }
+  return {h, bits, min(across_n, opened), min(down_n, opened)};
+}
+
+struct NwWalk { int start; uint32_t diffs, columns; };   // the CIGAR is tx[start, textcap)
+
+// Walk back from the last cell (host/nw_host.cpp, src/nw.cc:139-172), one lane; the run-length CIGAR is written right
+// to left.  Direction bits: 4 a cell, 8 cells of a diagonal a u32, cell (r, c) being cell min(r, c) of diagonal c - r;
+// word_at(cell, offset) is the u32 that holds those of cell `cell` of diagonal `offset`.
+template <class WordAt>
+__device__ __forceinline__ NwWalk nw_walk_back(const uint64_t * dw, const uint64_t * qw, int dl, int ql, char * tx, uint32_t textcap,
+                                               WordAt word_at) {
+  int pos = (int)textcap;
+  char run_op = 0;
+  uint32_t run_len = 0, matches = 0, columns = 0;
+  auto flush = [&]() {                                         // one run, written right to left: count (if > 1), then op
+    if (run_len == 0) { return; }
+    tx[--pos] = run_op;
+    if (run_len > 1) { for (uint32_t v = run_len; v != 0; v /= 10) { tx[--pos] = (char)('0' + v % 10); } }
+  };
+  auto push = [&](char op, uint32_t n) {
+    if (op == run_op) { run_len += n; return; }
+    flush();
+    run_op = op;
+    run_len = n;
+  };
+  int row = dl, col = ql;
+  char op = 0;
+  while (row > 0 && col > 0) {
+    const int r = row - 1, c = col - 1;
+    const int cell = r < c ? r : c;
+    const uint32_t bits = (word_at(cell, c - r) >> ((cell & 7) << 2)) & 15u;
+    if (op == 'I' && (bits & kExtLeft)) { --row; op = 'I'; }
+    else if (op == 'D' && (bits & kExtUp)) { --col; op = 'D'; }
+    else if (bits & kLeft) { --row; op = 'I'; }
+    else if (bits & kUp) { --col; op = 'D'; }
+    else {
+      if (nt_at(dw, r) == nt_at(qw, c)) { ++matches; }
+      --row; --col; op = 'M';
+    }
+    ++columns;
+    push(op, 1);
+  }
+  if (col > 0) { push('D', (uint32_t)col); }
+  if (row > 0) { push('I', (uint32_t)row); }
+  flush();
+  columns += (uint32_t)(col + row);
+  return {pos, columns - matches, columns};
+}
+
+// The G lanes of a pair's group (t = 0 .. G - 1, the first of them lane `lead` of the wave) move its CIGAR tx[start,
+// textcap) to the packed text buffer and write the pair's result.  False: the buffer is full, nothing was written.
+template <int G>
+__device__ __forceinline__ bool nw_store_text(const NwArgs & a, uint32_t k, const char * tx, int start, uint32_t diffs, uint32_t columns,
+                                              int t, int lead) {
+  const uint32_t len = a.textcap - (uint32_t)start;
+  unsigned long long off = 0;
+  if (t == 0) { off = atomicAdd(a.text_used, (unsigned long long)len); }
+  off = (unsigned long long)__shfl((long long)off, lead, kBlock);
+  if (off + len > a.text_cap) { return false; }
+  for (uint32_t b = (uint32_t)t; b < len; b += G) { a.text[off + b] = tx[start + (int)b]; }
+  if (t == 0) {
+    a.res[k] = make_uint4(diffs, columns, len, a.tier + 1);
+    a.text_off[k] = off;
+  }
+  return true;
+}
 
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_nw_trace(const NwArgs a) {
   extern __shared__ uint64_t lds[];
   constexpr int kGroups = kBlock / G;
-  constexpr int W = (G - 3) / 2;
+  constexpr int W = lds_half_width(G);
   const int group = threadIdx.x / G;
   const int t = threadIdx.x % G;
   const int lane = threadIdx.x;
@@ -117,14 +205,14 @@ __global__ __launch_bounds__(kBlock) void k_nw_trace(const NwArgs a) {
     const uint32_t k = a.list[i];
     const uint32_t did = a.d_ids[k], qid = a.q_ids[k];
     const int dl = (int)a.seqlen[did], ql = (int)a.seqlen[qid];
-    wave_lds_sync();                                           // the previous pair's LDS readers are done
+    wave_mem_sync();                                           // the previous pair's LDS readers are done
     {
       const uint64_t * gd = a.seqs + a.seq_off[did];
       const uint64_t * gq = a.seqs + a.seq_off[qid];
       for (int w = t; w < ((dl + 31) >> 5); w += G) { dw[w] = gd[w]; }
       for (int w = t; w < ((ql + 31) >> 5); w += G) { qw[w] = gq[w]; }
     }
-    wave_lds_sync();
+    wave_mem_sync();
     const int delta = ql - dl;
     const bool feasible = delta <= W && -delta <= W;
     uint32_t h_own = 0, e_out = kInf, f_out = kInf, acc = 0;
@@ -141,26 +229,16 @@ __global__ __launch_bounds__(kBlock) void k_nw_trace(const NwArgs a) {
         const int rc_ = r < 0 ? 0 : (r >= dl ? dl - 1 : r);
         const int cc_ = c < 0 ? 0 : (c >= ql ? ql - 1 : c);
         const bool mis = nt_at(dw, rc_) != nt_at(qw, cc_);
-        // borders (host/nw_host.cpp): H(-1, c) = go + (c + 1) ge, H(r, -1) = go + (r + 1) ge, H(-1, -1) = 0;
-        // horizontal state entering column 0 = 2 go + (r + 2) ge, vertical state entering row 0 = 2 go + (c + 2) ge
         const uint32_t across = c == 0 ? 2u * go + (uint32_t)(r + 2) * ge : e_nb;
         const uint32_t down = r == 0 ? 2u * go + (uint32_t)(c + 2) * ge : f_nb;
         const uint32_t diag = (r == 0 || c == 0) ? ((r | c) == 0 ? 0u : go + (uint32_t)(r + c) * ge) : h_own;
-        uint32_t h = diag + (mis ? mm : 0u);
-        uint32_t bits = 0;
-        if (across < h) { bits |= kUp; h = across; }
-        if (down < h) { h = down; }
-        if (down == h) { bits |= kLeft; }
-        const uint32_t opened = h + go + ge;
-        const uint32_t across_n = across + ge, down_n = down + ge;
-        if (across_n < opened) { bits |= kExtUp; }
-        if (down_n < opened) { bits |= kExtLeft; }
+        const NwCell x = nw_cell(across, down, diag, mis, mm, go, ge);
         if (act) {
-          h_own = h;
-          e_out = min(across_n, opened);
-          f_out = min(down_n, opened);
+          h_own = x.h;
+          e_out = x.e;
+          f_out = x.f;
           const int cell = r < c ? r : c;
-          acc |= bits << ((cell & 7) << 2);
+          acc |= x.bits << ((cell & 7) << 2);
           if ((cell & 7) == 7 || r == dl - 1 || c == ql - 1) {   // a full word, or the last cell of the diagonal
             bitmem[(cell >> 3) * kBlock + lane] = acc;
             acc = 0;
@@ -171,76 +249,24 @@ __global__ __launch_bounds__(kBlock) void k_nw_trace(const NwArgs a) {
     // the end cell (dl - 1, ql - 1) lies on offset delta, in lane delta + W + 1 of the group
     const uint32_t cost = (uint32_t)__shfl((int)h_own, group * G + (feasible ? delta + W + 1 : 0), kBlock);
     const bool certified = feasible && cost < bound;
-    wave_lds_sync();
-    int start = 0;
-    uint32_t diffs = 0, columns = 0;
+    wave_mem_sync();
+    NwWalk w{0, 0, 0};
     if (certified && t == 0) {
-      // walk back from the last cell: host/nw_host.cpp, src/nw.cc:139-172
-      int pos = (int)a.textcap;
-      char run_op = 0;
-      uint32_t run_len = 0, matches = 0;
-      auto flush = [&]() {                                     // one run, written right to left: count (if > 1), then op
-        if (run_len == 0) { return; }
-        tx[--pos] = run_op;
-        if (run_len > 1) { for (uint32_t v = run_len; v != 0; v /= 10) { tx[--pos] = (char)('0' + v % 10); } }
-      };
-      auto push = [&](char op, uint32_t n) {
-        if (op == run_op) { run_len += n; return; }
-        flush();
-        run_op = op;
-        run_len = n;
-      };
-      int row = dl, col = ql;
-      char op = 0;
-      while (row > 0 && col > 0) {
-        const int r = row - 1, c = col - 1;
-        const int cell = r < c ? r : c;
-        const uint32_t bits = (bitmem[(cell >> 3) * kBlock + group * G + (c - r) + W + 1] >> ((cell & 7) << 2)) & 15u;
-        if (op == 'I' && (bits & kExtLeft)) { --row; op = 'I'; }
-        else if (op == 'D' && (bits & kExtUp)) { --col; op = 'D'; }
-        else if (bits & kLeft) { --row; op = 'I'; }
-        else if (bits & kUp) { --col; op = 'D'; }
-        else {
-          if (nt_at(dw, r) == nt_at(qw, c)) { ++matches; }
-          --row; --col; op = 'M';
-        }
-        ++columns;
-        push(op, 1);
-      }
-      if (col > 0) { push('D', (uint32_t)col); }
-      if (row > 0) { push('I', (uint32_t)row); }
-      flush();
-      columns += (uint32_t)(col + row);
-      diffs = columns - matches;
-      start = pos;
+      w = nw_walk_back(dw, qw, dl, ql, tx, a.textcap,
+                       [&](int cell, int offset) { return bitmem[(cell >> 3) * kBlock + group * G + offset + W + 1]; });
     }
-    wave_lds_sync();
-    start = __shfl(start, group * G, kBlock);
-    bool done = certified;
-    unsigned long long off = 0;
-    if (certified) {
-      const uint32_t len = a.textcap - (uint32_t)start;
-      if (t == 0) { off = atomicAdd(a.text_used, (unsigned long long)len); }
-      off = (unsigned long long)__shfl((long long)off, group * G, kBlock);
-      done = off + len <= a.text_cap;
-      if (done) {
-        for (uint32_t b = (uint32_t)t; b < len; b += G) { a.text[off + b] = tx[start + (int)b]; }
-        if (t == 0) {
-          a.res[k] = make_uint4(diffs, columns, len, a.tier + 1);
-          a.text_off[k] = off;
-        }
-      }
-    }
-    if (!done && t == 0) { a.next_list[atomicAdd(a.next_count, 1u)] = k; }
+    wave_mem_sync();
+    const int start = __shfl(w.start, group * G, kBlock);
+    const bool done = certified && nw_store_text<G>(a, k, tx, start, w.diffs, w.columns, t, group * G);
+    if (!done && t == 0) { a.next_list[atomicAdd(a.next_count, 1u)] = k; }   // not certified, or no room for its text
   }
 }
 
-// One wave, one pair, K band offsets a lane: offset index x = lane * K + j <-> band offset x - 1 - W.  The same recurrence,
-// direction bits, certificate and walk-back as k_nw_trace; the bits live in the wave's global slot.
+// One wave, one pair, K band offsets a lane: offset index x = lane * K + j <-> band offset x - 1 - W.
 template <int K>
 __global__ __launch_bounds__(kBlock) void k_nw_trace_wide(const NwArgs a) {
   extern __shared__ uint64_t lds[];
-  constexpr int W = (kBlock * K - 3) / 2;
+  constexpr int W = wide_half_width(K);
   constexpr int kShift = K == 1 ? 0 : K == 2 ? 1 : K == 4 ? 2 : 3;
   static_assert(K == 1 || (W & 1) == 0, "the parity of the live offsets is a compile-time fact only for even W");
   const int lane = threadIdx.x;
@@ -261,14 +287,14 @@ __global__ __launch_bounds__(kBlock) void k_nw_trace_wide(const NwArgs a) {
     // (the launch sized LDS and the slot for every pair of the list; a pair outside them is passed on, never written)
     const bool feasible = delta <= W && -delta <= W && (uint32_t)(dl + ql) <= a.textcap &&
                           (uint32_t)((max(dl, ql) + 31) >> 5) <= a.maxwords && (uint32_t)((min(dl, ql) + 7) >> 3) <= a.bitwords;
-    wave_lds_sync();                                           // the previous pair's LDS readers are done
+    wave_mem_sync();                                           // the previous pair's LDS readers are done
     if (feasible) {
       const uint64_t * gd = a.seqs + a.seq_off[did];
       const uint64_t * gq = a.seqs + a.seq_off[qid];
       for (int w = lane; w < ((dl + 31) >> 5); w += kBlock) { dw[w] = gd[w]; }
       for (int w = lane; w < ((ql + 31) >> 5); w += kBlock) { qw[w] = gq[w]; }
     }
-    wave_lds_sync();
+    wave_mem_sync();
     uint32_t h_own[K], e_out[K], f_out[K], acc[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) { h_own[j] = 0; e_out[j] = kInf; f_out[j] = kInf; acc[j] = 0; }
@@ -286,28 +312,19 @@ __global__ __launch_bounds__(kBlock) void k_nw_trace_wide(const NwArgs a) {
         const bool act = x >= 1 && x <= 2 * W + 1 && (K > 1 || (rs & 1) == 0) && r >= 0 && r < dl && c >= 0 && c < ql;
         const int rc_ = r < 0 ? 0 : (r >= dl ? dl - 1 : r);
         const int cc_ = c < 0 ? 0 : (c >= ql ? ql - 1 : c);
-        const bool mis = nt_at(dw, rc_) != nt_at(qw, cc_);
         const uint32_t e_nb = j == 0 ? e_in : e_out[j == 0 ? 0 : j - 1];
         const uint32_t f_nb = j == K - 1 ? f_in : f_out[j == K - 1 ? j : j + 1];
-        // borders and recurrence: exactly k_nw_trace's (host/nw_host.cpp)
+        const bool mis = nt_at(dw, rc_) != nt_at(qw, cc_);
         const uint32_t across = c == 0 ? 2u * go + (uint32_t)(r + 2) * ge : e_nb;
         const uint32_t down = r == 0 ? 2u * go + (uint32_t)(c + 2) * ge : f_nb;
         const uint32_t diag = (r == 0 || c == 0) ? ((r | c) == 0 ? 0u : go + (uint32_t)(r + c) * ge) : h_own[j];
-        uint32_t h = diag + (mis ? mm : 0u);
-        uint32_t bits = 0;
-        if (across < h) { bits |= kUp; h = across; }
-        if (down < h) { h = down; }
-        if (down == h) { bits |= kLeft; }
-        const uint32_t opened = h + go + ge;
-        const uint32_t across_n = across + ge, down_n = down + ge;
-        if (across_n < opened) { bits |= kExtUp; }
-        if (down_n < opened) { bits |= kExtLeft; }
+        const NwCell y = nw_cell(across, down, diag, mis, mm, go, ge);
         if (act) {
-          h_own[j] = h;
-          e_out[j] = min(across_n, opened);
-          f_out[j] = min(down_n, opened);
+          h_own[j] = y.h;
+          e_out[j] = y.e;
+          f_out[j] = y.f;
           const int cell = r < c ? r : c;
-          acc[j] |= bits << ((cell & 7) << 2);
+          acc[j] |= y.bits << ((cell & 7) << 2);
           if ((cell & 7) == 7 || r == dl - 1 || c == ql - 1) {   // a full word, or the last cell of the diagonal
             bitmem[((size_t)(cell >> 3) * K + j) * kBlock + lane] = acc[j];
             acc[j] = 0;
@@ -338,71 +355,23 @@ __global__ __launch_bounds__(kBlock) void k_nw_trace_wide(const NwArgs a) {
     const bool certified = feasible && cost < bound;
     // the walking lane reads what its own wave stored: producer and consumer share the CU's write-through L1, so the
     // workgroup-scope release / acquire around a wave barrier orders them without touching L2
-    wave_lds_sync();
-    int start = 0;
-    uint32_t diffs = 0, columns = 0;
+    wave_mem_sync();
+    NwWalk w{0, 0, 0};
     if (certified && lane == 0) {
-      // walk back from the last cell: host/nw_host.cpp, src/nw.cc:139-172
-      int pos = (int)a.textcap;
-      char run_op = 0;
-      uint32_t run_len = 0, matches = 0;
-      auto flush = [&]() {                                     // one run, written right to left: count (if > 1), then op
-        if (run_len == 0) { return; }
-        tx[--pos] = run_op;
-        if (run_len > 1) { for (uint32_t v = run_len; v != 0; v /= 10) { tx[--pos] = (char)('0' + v % 10); } }
-      };
-      auto push = [&](char op, uint32_t n) {
-        if (op == run_op) { run_len += n; return; }
-        flush();
-        run_op = op;
-        run_len = n;
-      };
-      int row = dl, col = ql;
-      char op = 0;
       size_t have = ~size_t(0);                                // the word held in `word`
       uint32_t word = 0;
-      while (row > 0 && col > 0) {
-        const int r = row - 1, c = col - 1;
-        const int cell = r < c ? r : c;
-        const int x = (c - r) + W + 1;
+      w = nw_walk_back(dw, qw, dl, ql, tx, a.textcap, [&](int cell, int offset) {
+        const int x = offset + W + 1;
         const size_t at = ((size_t)(cell >> 3) * K + (x & (K - 1))) * kBlock + (x >> kShift);
         if (at != have) { word = bitmem[at]; have = at; }
-        const uint32_t bits = (word >> ((cell & 7) << 2)) & 15u;
-        if (op == 'I' && (bits & kExtLeft)) { --row; op = 'I'; }
-        else if (op == 'D' && (bits & kExtUp)) { --col; op = 'D'; }
-        else if (bits & kLeft) { --row; op = 'I'; }
-        else if (bits & kUp) { --col; op = 'D'; }
-        else {
-          if (nt_at(dw, r) == nt_at(qw, c)) { ++matches; }
-          --row; --col; op = 'M';
-        }
-        ++columns;
-        push(op, 1);
-      }
-      if (col > 0) { push('D', (uint32_t)col); }
-      if (row > 0) { push('I', (uint32_t)row); }
-      flush();
-      columns += (uint32_t)(col + row);
-      diffs = columns - matches;
-      start = pos;
+        return word;
+      });
     }
-    wave_lds_sync();
-    start = __shfl(start, 0, kBlock);
-    bool done = certified;
-    unsigned long long off = 0;
+    wave_mem_sync();
+    const int start = __shfl(w.start, 0, kBlock);
     if (certified) {
-      const uint32_t len = a.textcap - (uint32_t)start;
-      if (lane == 0) { off = atomicAdd(a.text_used, (unsigned long long)len); }
-      off = (unsigned long long)__shfl((long long)off, 0, kBlock);
-      done = off + len <= a.text_cap;
-      if (done) {
-        for (uint32_t b = (uint32_t)lane; b < len; b += kBlock) { a.text[off + b] = tx[start + (int)b]; }
-        if (lane == 0) {
-          a.res[k] = make_uint4(diffs, columns, len, a.tier + 1);
-          a.text_off[k] = off;
-        }
-      } else if (lane == 0) {                                  // text buffer full: a wider band would find it full again
-        atomicAdd(a.text_full, 1u);
+      if (!nw_store_text<kBlock>(a, k, tx, start, w.diffs, w.columns, lane, 0) && lane == 0) {
+        atomicAdd(a.text_full, 1u);                            // text buffer full: a wider band would find it full again
         a.host_list[atomicAdd(a.host_count, 1u)] = k;
       }
     }
@@ -420,40 +389,54 @@ __global__ __launch_bounds__(256) void k_nw_gather(const uint64_t * seqs, const 
   }
 }
 
-template <int G>
-size_t lds_bytes(const NwArgs & a) {
-  return (size_t)2 * (kBlock / G) * a.maxwords * 8 + (size_t)a.bitwords * kBlock * 4 + (size_t)(kBlock / G) * a.textcap;
+// ---- the host side ----------------------------------------------------------------------------------------------------
+
+// The device tiers in the order they run.  A tier takes a pair with |dl - ql| <= W; what it cannot certify it appends to
+// list `fail_to` (kLists: the host's).  The 64-lane LDS tier skips the K = 1 wide tier, whose band is no wider.
+struct Tier { bool wide; int n; uint32_t W, fail_to; void (*kernel)(const NwArgs); };   // n: G lanes a pair, or K offsets a lane
+const Tier kTier[kLists] = {
+    {false, 16, lds_half_width(16), 1, k_nw_trace<16>},      {false, 32, lds_half_width(32), 2, k_nw_trace<32>},
+    {false, 64, lds_half_width(64), 4, k_nw_trace<64>},      {true, 1, wide_half_width(1), 4, k_nw_trace_wide<1>},
+    {true, 2, wide_half_width(2), 5, k_nw_trace_wide<2>},    {true, 4, wide_half_width(4), 6, k_nw_trace_wide<4>},
+    {true, 8, wide_half_width(8), kLists, k_nw_trace_wide<8>}};
+
+struct Scoring { uint64_t mismatch, gapopen, gapextend; };
+
+// 32-bit costs: every finite value the kernels form is below mm + 3 go + (dl + ql + 4) ge; it must stay below kInf
+bool fits(const Scoring & sc, uint32_t dl, uint32_t ql) {
+  const unsigned __int128 top = (unsigned __int128)sc.mismatch + 3 * (unsigned __int128)sc.gapopen + (unsigned __int128)(dl + ql + 4) * sc.gapextend;
+  return top < kInf;
+}
+// A wide tier takes a pair whose slot fits the budget at K = 8 (so that every later tier can take it too) and whose
+// sequences and CIGAR text fit LDS.
+bool wide_fits(uint32_t dl, uint32_t ql) {
+  return (uint64_t)dl + ql <= kWideMaxSum && (uint64_t)((std::min(dl, ql) + 7) / 8) * 8 * kBlock * 4 <= kBitsBudget;
 }
 
-template <int G>
-int launch_tier(swa_ctx * ctx, NwArgs a, uint32_t room) {
-  if (room == 0) { return SWA_OK; }
-  a.list_room = room;
-  constexpr uint32_t kGroups = kBlock / G;
-  const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((room + kGroups - 1) / kGroups, (uint32_t)ctx->num_cus * 32u));
-  hipLaunchKernelGGL(k_nw_trace<G>, dim3(grid), dim3(kBlock), lds_bytes<G>(a), ctx->stream, a);
-  SWA_HIP(ctx, hipGetLastError());
-  return SWA_OK;
-}
+struct Extent {                                                // what a launch sizes LDS and slots by
+  uint32_t maxlen = 1, maxmin = 1, maxsum = 1;
+  void add(uint32_t dl, uint32_t ql) { add(Extent{std::max(dl, ql), std::min(dl, ql), dl + ql}); }
+  void add(const Extent & o) { maxlen = std::max(maxlen, o.maxlen); maxmin = std::max(maxmin, o.maxmin); maxsum = std::max(maxsum, o.maxsum); }
+  uint32_t maxwords() const { return (maxlen + 31) / 32 + 1; }
+  uint32_t bitwords() const { return (maxmin + 7) / 8; }
+  uint32_t textcap() const { return (maxsum + 7) & ~7u; }
+};
 
-size_t wide_lds_bytes(const NwArgs & a) { return (size_t)2 * a.maxwords * 8 + a.textcap; }
+struct Pairs { uint32_t m; const uint32_t * d, * q; };         // one slice of the batch: kSlice pairs at most
 
-// waves of a wide tier: one a pair (`room` of them expected), at most 16 a CU, and no more slots than kBitsBudget holds
-template <int K>
-uint32_t wide_grid(const swa_ctx * ctx, uint32_t room, uint32_t bitwords) {
-  const uint64_t slot_bytes = (uint64_t)bitwords * K * kBlock * 4;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(room, (uint64_t)ctx->num_cus * 16u), kBitsBudget / slot_bytes));
-}
+struct Plan {                                                  // the device pass of a slice
+  std::vector<uint32_t> lists[kLists + 1];                     // pairs by the tier they enter at (kLists: the host)
+  struct { Extent ext; uint32_t room, grid; } tier[kLists];    // every pair that can reach the tier; a bound of its list (0: no launch)
+  unsigned long long text_cap;
+  size_t bits_bytes;                                           // the wide tiers' slots: the largest grid * slot of any of them
+};
 
-template <int K>
-int launch_wide(swa_ctx * ctx, NwArgs a, uint32_t room, uint32_t waves) {
-  if (room == 0) { return SWA_OK; }
-  a.list_room = room;
-  a.slot_words = (unsigned long long)a.bitwords * K * kBlock;
-  hipLaunchKernelGGL(k_nw_trace_wide<K>, dim3(wide_grid<K>(ctx, waves, a.bitwords)), dim3(kBlock), wide_lds_bytes(a), ctx->stream, a);
-  SWA_HIP(ctx, hipGetLastError());
-  return SWA_OK;
-}
+struct Results {                                               // of a slice
+  std::vector<uint4> res;                                      // per pair: diffs, columns, CIGAR length, tier + 1 (0: the host's)
+  std::vector<unsigned long long> toff;
+  std::string text;
+  std::vector<std::string> host_cigar;                         // of the host's list, entry by entry
+};
 
 // lengths of the resident database on the host: the batch sorts its pairs into tiers and sizes LDS by them
 int host_seqlen(swa_ctx * ctx) {
@@ -468,11 +451,8 @@ int host_seqlen(swa_ctx * ctx) {
 template <class T>
 T * buf(swa_dbuf & b) { return static_cast<T *>(b.ptr); }
 
-}  // namespace
-
-extern "C" int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
-                            const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
-                            uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total) {
+int check_args(swa_ctx * ctx, uint64_t npairs, const uint32_t * d_ids, const uint32_t * q_ids, const uint32_t * diffs,
+               const uint32_t * columns, const uint64_t * cigar_end) {
   if (ctx == nullptr) { return SWA_E_ARG; }
   if (npairs > 0 && (d_ids == nullptr || q_ids == nullptr || diffs == nullptr || columns == nullptr || cigar_end == nullptr)) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_nw_batch: null result array");
@@ -481,224 +461,196 @@ extern "C" int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, 
   for (uint64_t k = 0; k < npairs; ++k) {
     if (d_ids[k] >= ctx->db.n || q_ids[k] >= ctx->db.n) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_nw_batch: amplicon id out of range"); }
   }
+  return SWA_OK;
+}
+
+// Host only: every pair to the list of the narrowest tier that may take it, and what each launch is sized by.
+Plan plan_slice(const Pairs & s, const uint32_t * len, const Scoring & sc, uint32_t num_cus) {
+  Plan p{};
+  for (uint32_t k = 0; k < s.m; ++k) {
+    const uint32_t dl = len[s.d[k]], ql = len[s.q[k]];
+    const uint32_t delta = dl > ql ? dl - ql : ql - dl;
+    uint32_t first = kLists, end = kLists;                     // the tiers the pair may enter at
+    if (fits(sc, dl, ql)) {
+      if (std::min(dl, ql) <= kMaxCells && delta <= kTier[kTiers - 1].W) { first = 0; end = kTiers; }
+      else if (wide_fits(dl, ql)) { first = kTiers; }
+    }
+    uint32_t tier = kLists;
+    for (uint32_t t = first; t < end; ++t) { if (delta <= kTier[t].W) { tier = t; break; } }
+    p.lists[tier].push_back(k);
+    if (tier < kLists) { p.tier[tier].ext.add(dl, ql); }
+  }
+  // Tier t's list holds the pairs that enter there and whatever the tiers that fail to it pass on.  How many that will
+  // be is known only on the device: room bounds the list; waves sizes a wide tier's grid and slots, and counts what an LDS
+  // tier passes on as kPassedWaves at most (such pairs are rare: 1 and 10 of 10 M in profiles/r07; the kernel's loop
+  // strides by the grid)
+  uint32_t waves[kLists], wide_own = 0;
+  for (uint32_t t = 0; t < kLists; ++t) {
+    p.tier[t].room = waves[t] = (uint32_t)p.lists[t].size();
+    if (kTier[t].wide) { wide_own += waves[t]; }
+  }
+  p.text_cap = kTextPerPair * (s.m - p.lists[kLists].size()) + kTextPerWidePair * wide_own + (1u << 16);
+  for (uint32_t t = 0; t < kLists; ++t) {
+    const uint32_t to = kTier[t].fail_to;                      // a later tier: its figures are still open
+    if (to == kLists) { continue; }
+    p.tier[to].ext.add(p.tier[t].ext);
+    p.tier[to].room += p.tier[t].room;
+    waves[to] += kTier[t].wide ? waves[t] : std::min(p.tier[t].room, kPassedWaves);
+  }
+  p.tier[0].ext = p.tier[1].ext = p.tier[kTiers - 1].ext;      // the LDS tiers are sized alike, by all their pairs
+  for (uint32_t t = 0; t < kLists; ++t) {
+    const uint32_t n = (uint32_t)kTier[t].n, room = p.tier[t].room;
+    if (!kTier[t].wide) {                                      // kBlock / G pairs a workgroup, 32 workgroups a CU at most
+      p.tier[t].grid = std::max(1u, std::min((room + kBlock / n - 1) / (kBlock / n), num_cus * 32u));
+    } else if (room > 0) {             // a wave a pair, 16 a CU at most, and no more slots than kBitsBudget holds
+      const uint64_t slot_bytes = (uint64_t)p.tier[t].ext.bitwords() * n * kBlock * 4;
+      p.tier[t].grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(waves[t], (uint64_t)num_cus * 16u), kBitsBudget / slot_bytes));
+      p.bits_bytes = std::max<size_t>(p.bits_bytes, slot_bytes * p.tier[t].grid);
+    }
+  }
+  return p;
+}
+
+// The device pass of a planned slice: upload, the tiers in order, results and text back.  What the tiers left to the host
+// is appended to the plan's host list.
+int run_device_tiers(swa_ctx * ctx, const Pairs & s, Plan & p, const Scoring & sc, Results & out) {
+  const uint32_t m = s.m;
+  NwStatus st{};
+  for (uint32_t t = 0; t < kLists; ++t) { st.count[t] = (uint32_t)p.lists[t].size(); }
+  SWA_TRY(swa_reserve(ctx, ctx->d_nw_ids, (size_t)2 * m * sizeof(uint32_t)));
+  SWA_TRY(swa_reserve(ctx, ctx->d_nw_lists, (size_t)(kLists + 1) * m * sizeof(uint32_t) + kStatusRoom));
+  SWA_TRY(swa_reserve(ctx, ctx->d_nw_res, (size_t)m * (sizeof(uint4) + sizeof(unsigned long long))));
+  SWA_TRY(swa_reserve(ctx, ctx->d_nw_text, (size_t)p.text_cap));
+  if (p.bits_bytes > 0) { SWA_TRY(swa_reserve(ctx, ctx->d_nw_bits, p.bits_bytes)); }
+  uint32_t * ids = buf<uint32_t>(ctx->d_nw_ids);
+  uint32_t * d_lists = buf<uint32_t>(ctx->d_nw_lists);         // list t at d_lists + t * m, the status block behind them
+  NwStatus * d_st = reinterpret_cast<NwStatus *>(d_lists + (size_t)(kLists + 1) * m);
+  uint4 * d_res = buf<uint4>(ctx->d_nw_res);
+  unsigned long long * d_toff = reinterpret_cast<unsigned long long *>(d_res + m);
+  SWA_HIP(ctx, hipMemcpyAsync(ids, s.d, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(ids + m, s.q, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+  for (uint32_t t = 0; t < kLists; ++t) {
+    if (!p.lists[t].empty()) {
+      SWA_HIP(ctx, hipMemcpyAsync(d_lists + (size_t)t * m, p.lists[t].data(), p.lists[t].size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+  }
+  SWA_HIP(ctx, hipMemcpyAsync(d_st, &st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+  SWA_HIP(ctx, hipMemsetAsync(d_res, 0, (size_t)m * sizeof(uint4), ctx->stream));
+  NwArgs a{};
+  a.seqs = ctx->db.seqs; a.seq_off = ctx->db.seq_off; a.seqlen = ctx->db.seqlen;
+  a.d_ids = ids; a.q_ids = ids + m;
+  a.res = d_res; a.text_off = d_toff; a.text = buf<char>(ctx->d_nw_text);
+  a.text_used = &d_st->text_used; a.text_full = &d_st->text_full; a.text_cap = p.text_cap;
+  a.host_list = d_lists + (size_t)kLists * m; a.host_count = &d_st->count[kLists];
+  a.bits = buf<uint32_t>(ctx->d_nw_bits);
+  a.mismatch = (uint32_t)sc.mismatch; a.gapopen = (uint32_t)sc.gapopen; a.gapextend = (uint32_t)sc.gapextend;
+  for (uint32_t t = 0; t < kLists; ++t) {
+    const Tier & tier = kTier[t];
+    if (p.tier[t].room == 0) { continue; }
+    a.list = d_lists + (size_t)t * m; a.list_count = &d_st->count[t]; a.list_room = p.tier[t].room;
+    a.next_list = d_lists + (size_t)tier.fail_to * m; a.next_count = &d_st->count[tier.fail_to];
+    a.tier = t;
+    a.maxwords = p.tier[t].ext.maxwords(); a.bitwords = p.tier[t].ext.bitwords(); a.textcap = p.tier[t].ext.textcap();
+    a.slot_words = tier.wide ? (unsigned long long)a.bitwords * tier.n * kBlock : 0;
+    // LDS: member and seed words and the CIGAR text of each pair of the workgroup; an LDS tier's direction bits
+    const size_t groups = tier.wide ? 1 : kBlock / tier.n;
+    const size_t lds = groups * (2 * a.maxwords * 8 + a.textcap) + (tier.wide ? 0 : (size_t)a.bitwords * kBlock * 4);
+    hipLaunchKernelGGL(tier.kernel, dim3(p.tier[t].grid), dim3(kBlock), lds, ctx->stream, a);
+    SWA_HIP(ctx, hipGetLastError());
+  }
+  SWA_HIP(ctx, hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(out.res.data(), d_res, (size_t)m * sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(out.toff.data(), d_toff, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->nw_text_full += st.text_full;
+  out.text.resize(std::min<unsigned long long>(st.text_used, p.text_cap));
+  if (!out.text.empty()) { SWA_HIP(ctx, hipMemcpyAsync(out.text.data(), a.text, out.text.size(), hipMemcpyDeviceToHost, ctx->stream)); }
+  std::vector<uint32_t> & hl = p.lists[kLists];                // the tiers' list of what is the host's began at 0
+  const size_t classified = hl.size();
+  hl.resize(classified + st.count[kLists]);
+  if (hl.size() > classified) {
+    SWA_HIP(ctx, hipMemcpyAsync(hl.data() + classified, a.host_list, (size_t)st.count[kLists] * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
+// The host's list hl: the pairs' words fetched from the device in one gather, aligned by the host's workers.
+int align_on_host(swa_ctx * ctx, const Pairs & s, const std::vector<uint32_t> & hl, const uint32_t * len, const Scoring & sc, Results & out) {
+  out.host_cigar.assign(hl.size(), std::string());
+  if (hl.empty()) { return SWA_OK; }
+  std::vector<uint32_t> gids(2 * hl.size());
+  std::vector<uint64_t> goff(2 * hl.size() + 1, 0);
+  for (size_t j = 0; j < hl.size(); ++j) { gids[2 * j] = s.d[hl[j]]; gids[2 * j + 1] = s.q[hl[j]]; }
+  for (size_t j = 0; j < gids.size(); ++j) { goff[j + 1] = goff[j] + (len[gids[j]] + 31u) / 32u; }
+  std::vector<uint64_t> words(std::max<uint64_t>(goff.back(), 1));
+  const size_t ids_bytes = (gids.size() * 4 + 7) & ~size_t(7);
+  SWA_TRY(swa_reserve(ctx, ctx->d_nw_gather, ids_bytes + gids.size() * 8 + words.size() * 8));
+  uint32_t * g_ids = buf<uint32_t>(ctx->d_nw_gather);
+  uint64_t * g_off = reinterpret_cast<uint64_t *>(buf<char>(ctx->d_nw_gather) + ids_bytes);
+  uint64_t * g_words = g_off + gids.size();
+  SWA_HIP(ctx, hipMemcpyAsync(g_ids, gids.data(), gids.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(g_off, goff.data(), gids.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  const uint32_t grid = (uint32_t)std::min<size_t>(gids.size(), 4096);
+  hipLaunchKernelGGL(k_nw_gather, dim3(grid), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, g_ids, g_off,
+                     (uint32_t)gids.size(), g_words);
+  SWA_HIP(ctx, hipGetLastError());
+  SWA_HIP(ctx, hipMemcpyAsync(words.data(), g_words, goff.back() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const unsigned parts = (unsigned)std::max<size_t>(1, std::min<size_t>(hl.size() / 16 + 1, std::min<unsigned>(swa_pool::get().size(), 16u)));
+  swa_pool::get().run(parts, [&](unsigned part) {
+    swa_nw_scratch scratch;
+    for (size_t j = hl.size() * part / parts; j < hl.size() * (part + 1) / parts; ++j) {
+      const uint32_t k = hl[j];
+      const uint64_t nd = swa_nw_align(words.data() + goff[2 * j], len[s.d[k]], words.data() + goff[2 * j + 1], len[s.q[k]],
+                                       sc.mismatch, sc.gapopen, sc.gapextend, scratch);
+      out.res[k] = make_uint4((uint32_t)nd, (uint32_t)scratch.ops.size(), 0, 0);
+      out.host_cigar[j] = swa_cigar(scratch.ops);
+    }
+  });
+  return SWA_OK;
+}
+
+// The slice's results in pair order, its CIGARs back to back from cigar + total on; the tier counters.
+void assemble(swa_ctx * ctx, uint32_t m, const std::vector<uint32_t> & hl, const Results & r, uint32_t * diffs, uint32_t * columns,
+              uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t & total) {
+  ctx->nw_totals[kLists] += hl.size();
+  std::vector<uint32_t> host_slot(m, UINT32_MAX);              // pair -> its entry of host_cigar
+  for (size_t j = 0; j < hl.size(); ++j) { host_slot[hl[j]] = (uint32_t)j; }
+  for (uint32_t k = 0; k < m; ++k) {
+    if (r.res[k].w > 0) { ctx->nw_totals[r.res[k].w - 1] += 1; }   // the tier that certified it
+    diffs[k] = r.res[k].x;
+    columns[k] = r.res[k].y;
+    const bool host = host_slot[k] != UINT32_MAX;
+    const char * src = host ? r.host_cigar[host_slot[k]].data() : r.text.data() + r.toff[k];
+    const size_t n = host ? r.host_cigar[host_slot[k]].size() : r.res[k].z;
+    if (cigar != nullptr && total + n <= cigar_cap) { std::memcpy(cigar + total, src, n); }
+    total += n;
+    cigar_end[k] = total;
+  }
+}
+
+}  // namespace
+
+extern "C" int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
+                            const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
+                            uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total) {
+  if (const int rc = check_args(ctx, npairs, d_ids, q_ids, diffs, columns, cigar_end); rc != SWA_OK) { return rc; }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   SWA_TRY(host_seqlen(ctx));
   for (auto & v : ctx->nw_totals) { v = 0; }
   ctx->nw_text_full = 0;
   const uint32_t * len = ctx->nw_seqlen.data();
-  // 32-bit costs: every finite value the kernels form is below mm + 3 go + (dl + ql + 4) ge; it must stay below kInf
-  auto fits = [&](uint32_t dl, uint32_t ql) {
-    const unsigned __int128 top = (unsigned __int128)mismatch + 3 * (unsigned __int128)gapopen + (unsigned __int128)(dl + ql + 4) * gapextend;
-    return top < kInf;
-  };
-  // half-widths: the LDS tiers, then the wide tiers.  A wide tier takes a pair whose slot fits the budget at K = 8 (so
-  // that every later tier can take it too) and whose sequences and CIGAR text fit LDS.
-  static constexpr uint32_t kW[kLists] = {6, 14, 30, 30, 62, 126, 254};
-  auto wide_fits = [&](uint32_t dl, uint32_t ql) {
-    return (uint64_t)dl + ql <= kWideMaxSum && (uint64_t)((std::min(dl, ql) + 7) / 8) * 8 * kBlock * 4 <= kBitsBudget;
-  };
-  struct Extent {                                              // what a launch sizes LDS and slots by
-    uint32_t maxlen = 1, maxmin = 1, maxsum = 1;
-    void add(uint32_t dl, uint32_t ql) {
-      maxlen = std::max(maxlen, std::max(dl, ql));
-      maxmin = std::max(maxmin, std::min(dl, ql));
-      maxsum = std::max(maxsum, dl + ql);
-    }
-    void add(const Extent & o) { maxlen = std::max(maxlen, o.maxlen); maxmin = std::max(maxmin, o.maxmin); maxsum = std::max(maxsum, o.maxsum); }
-  };
-
-  std::vector<uint4> res;
-  std::vector<unsigned long long> toff;
-  std::string text;
-  std::vector<std::string> host_cigar;
-  std::vector<uint32_t> lists[kLists + 1];
-  std::vector<uint32_t> tmp, host_slot;
+  const Scoring sc{mismatch, gapopen, gapextend};
   uint64_t total = 0;
   for (uint64_t base = 0; base < npairs; base += kSlice) {
-    const uint32_t m = (uint32_t)std::min<uint64_t>(kSlice, npairs - base);
-    const uint32_t * sd = d_ids + base, * sq = q_ids + base;
-    for (auto & l : lists) { l.clear(); }
-    Extent lds_ext, wide_ext[kWide];                           // the LDS tiers' pairs; each wide tier's own pairs
-    for (uint32_t k = 0; k < m; ++k) {
-      const uint32_t dl = len[sd[k]], ql = len[sq[k]];
-      const uint32_t delta = dl > ql ? dl - ql : ql - dl;
-      uint32_t tier = kLists;
-      if (fits(dl, ql)) {
-        if (std::min(dl, ql) <= kMaxCells && delta <= kW[kTiers - 1]) {
-          for (uint32_t t = 0; t < kTiers; ++t) { if (delta <= kW[t]) { tier = t; break; } }
-        } else if (wide_fits(dl, ql)) {
-          for (uint32_t t = kTiers; t < kLists; ++t) { if (delta <= kW[t]) { tier = t; break; } }
-        }
-      }
-      lists[tier].push_back(k);
-      if (tier < kTiers) { lds_ext.add(dl, ql); }
-      else if (tier < kLists) { wide_ext[tier - kTiers].add(dl, ql); }
-    }
-    res.assign(m, make_uint4(0, 0, 0, 0));
-    toff.assign(m, 0);
-    const uint32_t on_device = m - (uint32_t)lists[kLists].size();
-    if (on_device > 0) {
-      uint32_t hcounts[16] = {};
-      uint32_t wide_own = 0;
-      for (uint32_t t = 0; t < kLists; ++t) { hcounts[t] = (uint32_t)lists[t].size(); if (t >= kTiers) { wide_own += hcounts[t]; } }
-      const unsigned long long text_cap = (unsigned long long)kTextPerPair * on_device + (unsigned long long)kTextPerWidePair * wide_own + (1u << 16);
-      // a wide tier aligns its own pairs and whatever came down to it: the pairs of the narrower wide tiers, and from
-      // K = 2 on what the 64-lane LDS tier passed on.  How many that will be is known only on the device: wroom bounds the
-      // list, wwaves sizes the grid and the slots, and counts the LDS tiers' pairs as kPassedWaves at most (they are rare:
-      // 1 and 10 of 10 M in profiles/r07; the kernel's loop strides by the grid)
-      Extent ext[kWide];
-      uint32_t wroom[kWide], wwaves[kWide];
-      size_t bits_bytes = 0;
-      {
-        Extent e;
-        uint32_t room = 0, waves = 0;
-        for (uint32_t w = 0; w < kWide; ++w) {
-          if (w == 1) {
-            const uint32_t passed = hcounts[0] + hcounts[1] + hcounts[2];
-            e.add(lds_ext); room += passed; waves += std::min(passed, kPassedWaves);
-          }
-          e.add(wide_ext[w]);
-          room += hcounts[kTiers + w];
-          waves += hcounts[kTiers + w];
-          ext[w] = e;
-          wroom[w] = room;
-          wwaves[w] = waves;
-          if (room == 0) { continue; }
-          const uint32_t bw = (e.maxmin + 7) / 8;
-          const uint64_t slot = (uint64_t)bw * (1u << w) * kBlock * 4;
-          const uint32_t grid = w == 0 ? wide_grid<1>(ctx, waves, bw) : w == 1 ? wide_grid<2>(ctx, waves, bw) : w == 2 ? wide_grid<4>(ctx, waves, bw)
-                                                                                                                    : wide_grid<8>(ctx, waves, bw);
-          bits_bytes = std::max<size_t>(bits_bytes, (size_t)(slot * grid));
-        }
-      }
-      // one u32 block behind the lists: [0, kLists] list counts, [8] text used (u64), [10] text-full pairs
-      SWA_TRY(swa_reserve(ctx, ctx->d_nw_ids, (size_t)2 * m * sizeof(uint32_t)));
-      SWA_TRY(swa_reserve(ctx, ctx->d_nw_lists, (size_t)(kLists + 1) * m * sizeof(uint32_t) + 64));
-      SWA_TRY(swa_reserve(ctx, ctx->d_nw_res, (size_t)m * (sizeof(uint4) + sizeof(unsigned long long))));
-      SWA_TRY(swa_reserve(ctx, ctx->d_nw_text, (size_t)text_cap));
-      if (bits_bytes > 0) { SWA_TRY(swa_reserve(ctx, ctx->d_nw_bits, bits_bytes)); }
-      uint32_t * ids = buf<uint32_t>(ctx->d_nw_ids);
-      uint32_t * dl_ = buf<uint32_t>(ctx->d_nw_lists);
-      uint32_t * counts = dl_ + (size_t)(kLists + 1) * m;
-      uint4 * d_res = buf<uint4>(ctx->d_nw_res);
-      unsigned long long * d_toff = reinterpret_cast<unsigned long long *>(d_res + m);
-      SWA_HIP(ctx, hipMemcpyAsync(ids, sd, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
-      SWA_HIP(ctx, hipMemcpyAsync(ids + m, sq, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
-      for (uint32_t t = 0; t < kLists; ++t) {
-        if (!lists[t].empty()) {
-          SWA_HIP(ctx, hipMemcpyAsync(dl_ + (size_t)t * m, lists[t].data(), lists[t].size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-      }
-      SWA_HIP(ctx, hipMemcpyAsync(counts, hcounts, sizeof(hcounts), hipMemcpyHostToDevice, ctx->stream));
-      SWA_HIP(ctx, hipMemsetAsync(d_res, 0, (size_t)m * sizeof(uint4), ctx->stream));
-      NwArgs a{};
-      a.seqs = ctx->db.seqs; a.seq_off = ctx->db.seq_off; a.seqlen = ctx->db.seqlen;
-      a.d_ids = ids; a.q_ids = ids + m;
-      a.res = d_res; a.text_off = d_toff; a.text = buf<char>(ctx->d_nw_text);
-      a.text_used = reinterpret_cast<unsigned long long *>(counts + 8);
-      a.text_full = counts + 10;
-      a.host_list = dl_ + (size_t)kLists * m; a.host_count = counts + kLists;
-      a.text_cap = text_cap;
-      a.bits = buf<uint32_t>(ctx->d_nw_bits);
-      a.mismatch = (uint32_t)mismatch; a.gapopen = (uint32_t)gapopen; a.gapextend = (uint32_t)gapextend;
-      a.maxwords = (lds_ext.maxlen + 31) / 32 + 1;
-      a.bitwords = (lds_ext.maxmin + 7) / 8;
-      a.textcap = (lds_ext.maxsum + 7) & ~7u;
-      uint32_t room = 0;
-      for (uint32_t t = 0; t < kTiers; ++t) {
-        a.list = dl_ + (size_t)t * m; a.list_count = counts + t;
-        // (the 64-lane tier's failures skip the K = 1 wide tier, whose band is no wider)
-        const uint32_t next = t + 1 < kTiers ? t + 1 : kTiers + 1;
-        a.next_list = dl_ + (size_t)next * m; a.next_count = counts + next;
-        a.tier = t;
-        room += hcounts[t];                                    // this tier's own pairs + whatever the tiers before it passed on
-        if (t == 0) { SWA_TRY(launch_tier<16>(ctx, a, room)); }
-        else if (t == 1) { SWA_TRY(launch_tier<32>(ctx, a, room)); }
-        else { SWA_TRY(launch_tier<64>(ctx, a, room)); }
-      }
-      for (uint32_t w = 0; w < kWide; ++w) {
-        const uint32_t t = kTiers + w;
-        a.list = dl_ + (size_t)t * m; a.list_count = counts + t;
-        a.next_list = dl_ + (size_t)(t + 1) * m; a.next_count = counts + t + 1;
-        a.tier = t;
-        a.maxwords = (ext[w].maxlen + 31) / 32 + 1;
-        a.bitwords = (ext[w].maxmin + 7) / 8;
-        a.textcap = (ext[w].maxsum + 7) & ~7u;
-        if (w == 0) { SWA_TRY(launch_wide<1>(ctx, a, wroom[w], wwaves[w])); }
-        else if (w == 1) { SWA_TRY(launch_wide<2>(ctx, a, wroom[w], wwaves[w])); }
-        else if (w == 2) { SWA_TRY(launch_wide<4>(ctx, a, wroom[w], wwaves[w])); }
-        else { SWA_TRY(launch_wide<8>(ctx, a, wroom[w], wwaves[w])); }
-      }
-      SWA_HIP(ctx, hipMemcpyAsync(hcounts, counts, sizeof(hcounts), hipMemcpyDeviceToHost, ctx->stream));
-      SWA_HIP(ctx, hipMemcpyAsync(res.data(), d_res, (size_t)m * sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream));
-      SWA_HIP(ctx, hipMemcpyAsync(toff.data(), d_toff, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-      SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      // the widest tier appended what it could not certify to the host's list (from entry 0 on: counts[kLists] began at 0)
-      const uint32_t appended = hcounts[kLists];
-      ctx->nw_text_full += hcounts[10];
-      const unsigned long long used = std::min<unsigned long long>(*reinterpret_cast<unsigned long long *>(hcounts + 8), text_cap);
-      text.resize(used);
-      if (used > 0) { SWA_HIP(ctx, hipMemcpyAsync(text.data(), a.text, used, hipMemcpyDeviceToHost, ctx->stream)); }
-      if (appended > 0) {
-        tmp.resize(appended);
-        SWA_HIP(ctx, hipMemcpyAsync(tmp.data(), dl_ + (size_t)kLists * m, (size_t)appended * 4, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (appended > 0) { lists[kLists].insert(lists[kLists].end(), tmp.begin(), tmp.begin() + appended); }
-    }
-    // pairs for the host: their words fetched from the device in one gather, aligned by the host's workers
-    const std::vector<uint32_t> & hl = lists[kLists];
-    host_cigar.assign(hl.size(), std::string());
-    if (!hl.empty()) {
-      std::vector<uint32_t> gids(2 * hl.size());
-      std::vector<uint64_t> goff(2 * hl.size() + 1, 0);
-      for (size_t j = 0; j < hl.size(); ++j) { gids[2 * j] = sd[hl[j]]; gids[2 * j + 1] = sq[hl[j]]; }
-      for (size_t j = 0; j < gids.size(); ++j) { goff[j + 1] = goff[j] + (len[gids[j]] + 31u) / 32u; }
-      std::vector<uint64_t> words(std::max<uint64_t>(goff.back(), 1));
-      const size_t ids_bytes = (gids.size() * 4 + 7) & ~size_t(7);
-      SWA_TRY(swa_reserve(ctx, ctx->d_nw_gather, ids_bytes + gids.size() * 8 + words.size() * 8));
-      uint32_t * g_ids = buf<uint32_t>(ctx->d_nw_gather);
-      uint64_t * g_off = reinterpret_cast<uint64_t *>(buf<char>(ctx->d_nw_gather) + ids_bytes);
-      uint64_t * g_words = g_off + gids.size();
-      SWA_HIP(ctx, hipMemcpyAsync(g_ids, gids.data(), gids.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-      SWA_HIP(ctx, hipMemcpyAsync(g_off, goff.data(), gids.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-      const uint32_t grid = (uint32_t)std::min<size_t>(gids.size(), 4096);
-      hipLaunchKernelGGL(k_nw_gather, dim3(grid), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, g_ids, g_off,
-                         (uint32_t)gids.size(), g_words);
-      SWA_HIP(ctx, hipGetLastError());
-      SWA_HIP(ctx, hipMemcpyAsync(words.data(), g_words, goff.back() * 8, hipMemcpyDeviceToHost, ctx->stream));
-      SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      const unsigned parts = (unsigned)std::max<size_t>(1, std::min<size_t>(hl.size() / 16 + 1, std::min<unsigned>(swa_pool::get().size(), 16u)));
-      swa_pool::get().run(parts, [&](unsigned p) {
-        swa_nw_scratch sc;
-        for (size_t j = hl.size() * p / parts; j < hl.size() * (p + 1) / parts; ++j) {
-          const uint32_t k = hl[j];
-          const uint64_t nd = swa_nw_align(words.data() + goff[2 * j], len[sd[k]], words.data() + goff[2 * j + 1], len[sq[k]],
-                                           mismatch, gapopen, gapextend, sc);
-          res[k] = make_uint4((uint32_t)nd, (uint32_t)sc.ops.size(), 0, 0);
-          host_cigar[j] = swa_cigar(sc.ops);
-        }
-      });
-    }
-    // results in pair order; the CIGARs back to back
-    for (uint32_t k = 0; k < m; ++k) {
-      const uint32_t tier = res[k].w;
-      if (tier > 0) { ctx->nw_totals[tier - 1] += 1; }
-    }
-    ctx->nw_totals[kLists] += hl.size();
-    host_slot.assign(m, UINT32_MAX);                           // pair -> its entry of host_cigar
-    for (size_t j = 0; j < hl.size(); ++j) { host_slot[hl[j]] = (uint32_t)j; }
-    for (uint32_t k = 0; k < m; ++k) {
-      diffs[base + k] = res[k].x;
-      columns[base + k] = res[k].y;
-      const char * src;
-      size_t n;
-      if (host_slot[k] != UINT32_MAX) { src = host_cigar[host_slot[k]].data(); n = host_cigar[host_slot[k]].size(); }
-      else { src = text.data() + toff[k]; n = res[k].z; }
-      if (cigar != nullptr && total + n <= cigar_cap) { std::memcpy(cigar + total, src, n); }
-      total += n;
-      cigar_end[base + k] = total;
-    }
+    const Pairs s{(uint32_t)std::min<uint64_t>(kSlice, npairs - base), d_ids + base, q_ids + base};
+    Plan p = plan_slice(s, len, sc, (uint32_t)ctx->num_cus);
+    const std::vector<uint32_t> & hl = p.lists[kLists];        // the host's pairs: the device pass may add to them
+    Results r{std::vector<uint4>(s.m, make_uint4(0, 0, 0, 0)), std::vector<unsigned long long>(s.m, 0), {}, {}};
+    if (hl.size() < s.m) { SWA_TRY(run_device_tiers(ctx, s, p, sc, r)); }
+    SWA_TRY(align_on_host(ctx, s, hl, len, sc, r));
+    assemble(ctx, s.m, hl, r, diffs + base, columns + base, cigar_end + base, cigar, cigar_cap, total);
   }
   if (cigar_total != nullptr) { *cigar_total = total; }
   if (total > cigar_cap || (cigar == nullptr && total > 0)) {

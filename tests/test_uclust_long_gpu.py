@@ -249,6 +249,40 @@ def test_slice_boundary_with_long_pairs_on_both_sides(gpu_ctx, tmp_path):
     assert tiers[0] == n - 12 and sum(tiers[3:7]) == 12 and tiers[7] == 0, tiers
 
 
+def test_a_full_text_buffer_sends_pairs_on_and_to_the_host(gpu_ctx, tmp_path):
+    """one pair the 64-lane LDS tier certifies, 4 096 times, with a CIGAR longer than the packed text buffer has room for
+    (48 bytes a pair + 64 KiB): the LDS tier passes the pairs it cannot store on, the wide tier that certifies them again
+    finds the buffer still full, counts them and hands them to the host"""
+    from swarm_amd import nw_align_host
+    scoring = (10, 1, 10)
+    n = 4096
+    rng = np.random.default_rng(41)
+    seed = _rand(rng, 600)
+    s = list(seed)
+    for i, p in enumerate(np.linspace(15, 585, 20).astype(int)[::-1]):     # single-nucleotide indels, evenly spread,
+        if i % 2:                                                          # insertion and deletion in turn: |dl - ql| <= 1
+            s[p:p] = [SUB[s[p]]]
+        else:
+            del s[p]
+    st = _Set()
+    st.add("".join(s), seed)
+    want = nw_align_host(S.pack_seq(st.seqs[0].encode()), len(st.seqs[0]), S.pack_seq(seed.encode()), len(seed), *scoring)
+    diffs, cols, cigar = want
+    assert abs(len(st.seqs[0]) - len(seed)) <= 1
+    assert 151 <= _cost(cigar, diffs, scoring) < 311                       # past the 32-lane certificate, inside the 64-lane one
+    assert len(cigar) * n > 48 * n + 65536                                 # the batch's text cannot fit
+    st.upload(gpu_ctx, tmp_path)
+    d_ids = np.zeros(n, dtype=np.uint32)
+    q_ids = np.ones(n, dtype=np.uint32)
+    got_diffs, got_cols, got_cigars = gpu_ctx.nw_batch(d_ids, q_ids, *scoring)
+    assert (got_diffs == diffs).all() and (got_cols == cols).all() and set(got_cigars) == {cigar}
+    assert len(got_cigars) == n
+    tiers, full = gpu_ctx.nw_batch_tiers(), gpu_ctx.nw_batch_text_full()
+    assert sum(tiers) == n, tiers
+    assert full > 0 and tiers[7] == full, (tiers, full)                    # the wide tier's text-full branch: the only way to the host
+    assert tiers[2] > 0, tiers                                             # some pairs did get their text in
+
+
 # ---- the writers and the command line on long amplicons -----------------------------------------------------------
 
 @pytest.fixture(scope="module")
