@@ -278,16 +278,41 @@ int swa_d1_fastidious(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt
 int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
                             uint32_t shard, uint32_t nshards, uint32_t * graft_cand, uint64_t * counters);
 /* Which kernels the pass takes for the resident database: chosen from its longest sequence alone (and the switches
-   SWA_FAST_BLOOM / SWA_FAST_PAIRS), so valid once a database is resident; the launches read the same plan.
+   SWA_FAST_BLOOM / SWA_FAST_PAIRS; SWA_FAST_LONG: below), so valid once a database is resident; the launches read the same plan.
    out[0] pair route on (1) or the Bloom route for every pair (0); [1] pair kernel: 5, 8, 13 = k_fast_pairs_lines on
    that many register words, 0 = k_fast_pairs on the packed words; [2] count kernel: 5, 8 = k_fast_count_sites, 0 =
    k_fast_count (the LDS set); [3] waves per block of k_fast_count, [4] slots of a wave's set, [5] its dynamic LDS in
    bytes (all 0 where it does not run); [6] Bloom route: the Zobrist table in LDS (1) or read from memory (0);
    [7] the shortest sequence the pair route takes (a pair with a shorter member goes the Bloom route). */
 int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]);
+/* SWA_FAST_LONG=split (opt-in; without it nothing below applies and the plan is the one above).  k_fast_count's LDS set
+   holds the microvariants of a sequence of up to cap nt (the largest length whose set fits 160 KB: 1004), so a single
+   longer sequence sends every pair of the database to the Bloom route.  Under the switch, and only when the longest
+   sequence exceeds cap, the pass is divided at the long end as it is at the short end.  Two sequences within two edits
+   differ in length by at most 2, so:
+     pair route:  the pairs whose two lengths both lie in [112, cap];
+     Bloom route: every other pair, min(len) < 112 or max(len) > cap; the amplicons that can be half of such a pair
+                  are those of len <= 113 or len >= cap - 1.
+   The two sets of pairs are disjoint and complete, so graft_cand (a minimum) and the candidate count (a sum) stay
+   exact.  The pair route's kernels are then chosen from pair_longest, the longest sequence <= cap, and the pair kernel
+   is always k_fast_pairs on the packed words (out[1] = 0): the amplicon lines of the d = 1 index follow the whole
+   database.  out[6] still follows the longest sequence.  SWA_FAST_BLOOM=1 wins over the switch; with no sequence of
+   112 .. cap nt the pass stays all Bloom.  Which of the two is faster has been measured on one mixed set only
+   (README, "Measured"): hence opt-in.
+   swa_d1_fastidious_plan reports the plan actually launched.
+   swa_d1_fastidious_split: out[0] 1 when the division is taken for the resident database, [1] cap, [2] pair_longest
+   (0: no sequence <= cap), [3] amplicons longer than cap.  SWA_E_ARG when no database is resident.  [2] and [3] are
+   facts of the database, reported with or without the switch: where the longest sequence exceeds cap, the first call
+   after an upload runs the length pass on the device (one kernel over the lengths, one synchronisation) and caches its
+   result; swa_d1_fastidious and swa_d1_fastidious_plan run that pass only under the split.
+   swa_d1_fastidious_plan_for: the same dispatch as a pure function of (longest sequence, pair_longest, the three
+   switches as 0 / 1), out laid out as in swa_d1_fastidious_plan; no context, no device.  pair_longest is read only
+   when split != 0 and longest > cap. */
+int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]);
+int swa_d1_fastidious_plan_for(uint32_t longest, uint32_t pair_longest, int split, int bloom, int words, uint32_t out[8]);
 /* Of the last swa_d1_fastidious[_shard] call: out[0] pairs within two edits found by the pair route, [1] light and
-   [2] heavy amplicons handed to the Bloom route, [3] attempts the pair list took (2 or more: it was regrown; 0: the
-   pair route did not run). */
+   [2] heavy amplicons handed to the Bloom route (those of the short band and, under the split, of the long band),
+   [3] attempts the pair list took (2 or more: it was regrown; 0: the pair route did not run). */
 int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]);
 
 /* ---- d = 0: dereplication -------------------------------

@@ -75,7 +75,7 @@ EXPORTS = [
     "swa_d1_network_resident", "swa_d1_network_fetch", "swa_d1_cluster_device", "swa_d1_cluster_fetch", "swa_d1_cluster_maxgen", "swa_d1_cluster_resident", "swa_d1_cluster_resident_lazy", "swa_d1_result_detach", "swa_d1_result_error", "swa_d1_result_prepare",
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
-    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_qgram_build", "swa_qgram_diff",
+    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_qgram_build", "swa_qgram_diff",
     "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
@@ -131,6 +131,8 @@ def load_library() -> C.CDLL:
                                             C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_plan.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_totals.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_fastidious_split.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_fastidious_plan_for.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.swa_qgram_build.argtypes = [C.c_void_p]
     lib.swa_qgram_diff.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.swa_qgram_debug_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -173,6 +175,18 @@ def load_library() -> C.CDLL:
     lib.swa_d1_write_network.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64]
     _lib = lib
     return lib
+
+
+def fastidious_plan_for(longest: int, pair_longest: int = 0, split: bool = False, bloom: bool = False,
+                        words: bool = False) -> list:
+    """swa_d1_fastidious_plan_for: the dispatch of the --fastidious pass as a pure function (no context, no device), laid
+    out as Context.d1_fastidious_plan.  split: SWA_FAST_LONG=split, with pair_longest the longest sequence <= the cap;
+    bloom: SWA_FAST_BLOOM=1; words: SWA_FAST_PAIRS=words."""
+    out = np.zeros(8, dtype=np.uint32)
+    rc = load_library().swa_d1_fastidious_plan_for(int(longest), int(pair_longest), int(split), int(bloom), int(words), _ptr(out))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_d1_fastidious_plan_for: bad argument")
+    return [int(v) for v in out]
 
 
 def _p64(a: np.ndarray):
@@ -625,9 +639,16 @@ class Context:
         self._check(self.lib.swa_d1_fastidious_plan(self.h, _ptr(out)))
         return [int(v) for v in out]
 
+    def d1_fastidious_split(self) -> list:
+        """swa_d1_fastidious_split: [1 when SWA_FAST_LONG=split divides the pass for the resident database, the cap of the
+        pair route, the longest sequence <= cap, amplicons longer than cap]"""
+        out = np.zeros(4, dtype=np.uint32)
+        self._check(self.lib.swa_d1_fastidious_split(self.h, _ptr(out)))
+        return [int(v) for v in out]
+
     def d1_fastidious_totals(self) -> list:
-        """swa_d1_fastidious_totals of the last d1_fastidious call: [pairs the pair route found, short light amplicons,
-        short heavy amplicons, attempts of the pair list]"""
+        """swa_d1_fastidious_totals of the last d1_fastidious call: [pairs the pair route found, light amplicons and
+        heavy amplicons handed to the Bloom route (short band and, under the split, long band), attempts of the pair list]"""
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.swa_d1_fastidious_totals(self.h, _ptr(out)))
         return [int(v) for v in out]

@@ -240,6 +240,7 @@ static void invalidate(swa_ctx * ctx) {
   ctx->props_ready = false;
   ctx->windows_ready = false;
   ctx->lines_ready = false;
+  ctx->fast_classes_ready = false;
   ctx->stream_index = false;
   ctx->member_index = false;
   ctx->stream_extra_bits = 0;

@@ -36,7 +36,7 @@ constexpr int kWaves = 4;                 // waves per workgroup
 constexpr int kThreads = kWaves * 64;
 constexpr int kQueueCap = 128;            // per-wave candidate queue (>= 64 + 63)
 constexpr uint32_t kEmpty = SWA_NO_AMPLICON;
-constexpr size_t kMaxZobristLds = 96 * 1024;
+constexpr size_t kMaxZobristLds = SWA_MAX_ZOBRIST_LDS;
 
 struct alignas(16) swa_task {   // one surviving first-level microvariant of a heavy amplicon
   uint64_t hash;
@@ -73,7 +73,8 @@ struct NetArgs {
   const swa_task * tasks;
   uint32_t * graft;
   unsigned long long * cand_counter;
-  uint32_t fast_min_len;        // a (heavy, light) pair with both lengths >= this belongs to the pair route (d1_fast.inc)
+  uint32_t fast_min_len;        // a (heavy, light) pair with both lengths in [fast_min_len, fast_max_len] belongs to the pair
+  uint32_t fast_max_len;        // route (d1_fast.inc); every other pair is admitted here (no upper bound: 0xFFFFFFFF)
   // MODE 2 in window mode (anchor windows moved inwards): a fallback seed's share is defined by the window itself —
   // range 1 = neighbours with the same prefix-side window (word win_word), range 2 = the others; all positions are
   // enumerated and the hits filtered
@@ -303,7 +304,7 @@ __device__ __forceinline__ bool probe_and_verify(const NetArgs & a, const uint64
       const uint32_t amp = s.amp;
       const uint32_t alen = a.seqlen[amp];
       bool allowed;
-      if (SECOND) { allowed = min(a.seqlen[seed], alen) < a.fast_min_len; }
+      if (SECOND) { const uint32_t hlen = a.seqlen[seed]; allowed = min(hlen, alen) < a.fast_min_len || max(hlen, alen) > a.fast_max_len; }
       else { allowed = amp != seed && (a.no_cluster_breaking != 0 || seed_abundance >= a.abundance[amp]); }
       if (allowed && alen == vlen) {
         const uint64_t * y = a.seqs + a.seq_off[amp];
@@ -2085,7 +2086,7 @@ static int network_run_guarded(swa_ctx * ctx, int no_cluster_breaking, uint32_t 
   const std::string first_msg = ctx->err;
   fprintf(stderr, "swarm-amd: %s; rebuilding the index from the packed database and repeating the step\n", first_msg.c_str());
   ++ctx->guard_retries;
-  ctx->lines_ready = ctx->props_ready = ctx->windows_ready = ctx->rank_ready = false;
+  ctx->lines_ready = ctx->props_ready = ctx->windows_ready = ctx->rank_ready = ctx->fast_classes_ready = false;
   ctx->anchor_ready = ctx->stream_index = ctx->member_index = ctx->full_index = false;
   ctx->guard_index = ctx->guard_keys_done = ctx->guard_keys_pending = false;
   ctx->stream_extra_bits = 0;
@@ -2314,10 +2315,10 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
 
 // ---- seam B2: the fastidious second pass --------------------------------------------------
 // algo_d1_run's fastidious branch (src/algod1.cc:1337-1467).  Two routes, chosen per PAIR of
-// (heavy, light) amplicons by the shorter of the two lengths:
-//   pair route  (both >= kFastMinLen; d1_fast.inc): groups by shared 32-nt windows, exact
-//               "within two edits" test per pair, exact |V1(h) ∩ V1(x)| per surviving pair;
-//   Bloom route (a sequence shorter than that; the reference's own scheme): light-only table + Bloom,
+// (heavy, light) amplicons by the shorter of the two lengths (and, under SWA_FAST_LONG=split, the longer):
+//   pair route  (both >= kFastMinLen, and both <= the cap under the split; d1_fast.inc): groups by shared
+//               32-nt windows, exact "within two edits" test per pair, exact |V1(h) ∩ V1(x)| per surviving pair;
+//   Bloom route (every other pair; the reference's own scheme): light-only table + Bloom,
 //               every microvariant of every light amplicon clears its k pattern bits in the flexible
 //               Bloom (atomicAnd: the reference's plain `&=` from many threads can lose a bit; -t 1 is
 //               the specification), every microvariant of every heavy amplicon is tested, survivors
@@ -2329,10 +2330,10 @@ extern "C" int swa_d1_fastidious(swa_ctx * ctx, const uint8_t * is_light, uint64
 }
 
 // fc layout (d_fcounters, u64[16]): [0] light variants [1] heavy variants [2] candidates [3] tasks of the
-// current batch [4] variants of the current batch [5] pairs found [6] short light amplicons [7] short heavy
-// amplicons [8] nucleotides of the short light amplicons [9] scratch
+// current batch [4] variants of the current batch [5] pairs found [6] light amplicons of the Bloom route's bands
+// [7] heavy amplicons of the bands [8] nucleotides of those light amplicons [9] scratch [12, 14) k_fast_length_classes (u32[4])
 static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_heavy, uint64_t light_nt, uint32_t bloom_bits,
-                                  uint32_t pair_route_min_len, bool zlds) {
+                                  uint32_t pair_route_min_len, uint32_t pair_route_max_len, bool zlds) {
   SWA_TRY(ensure_full_index(ctx));                           // hashes of every amplicon, room for the table
   uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
   if (k < 1) { k = 1; }
@@ -2352,7 +2353,7 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   SWA_TRY(swa_reserve(ctx, ctx->d_queue, task_cap * sizeof(swa_task)));
   SWA_HIP(ctx, hipMemcpyAsync(ctx->d_fpatterns.ptr, fpat.data(), fpat.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_bloomflex.ptr, 0xFF, fsize * sizeof(uint64_t), ctx->stream));
-  ctx->d1_ready = false;                                     // the table now holds (short) light amplicons only
+  ctx->d1_ready = false;                                     // the table now holds the light amplicons of the bands only
   ctx->full_index = false;
   SWA_TRY(swa_d1_rebuild_table(ctx, static_cast<const uint8_t *>(ctx->d_light.ptr)));
 
@@ -2395,6 +2396,7 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   a.graft = static_cast<uint32_t *>(ctx->d_graft.ptr);
   a.cand_counter = fc + 2;
   a.fast_min_len = pair_route_min_len;
+  a.fast_max_len = pair_route_max_len;
   const size_t probe_lds = sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + 1024ull +
                                                kWaves * ((size_t)(a.maxwords + 2u) + kQueueCap + kQueueCap / 2));
   uint64_t done = 0;
@@ -2433,16 +2435,8 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   return SWA_OK;
 }
 
-// LDS of k_fast_count for `waves` waves per block; 0 = does not fit
-static size_t fast_count_lds(uint32_t longest, uint32_t slots, int waves) {
-  const uint32_t maxwords = (longest + 31u) >> 5;
-  const size_t zlen = (size_t)longest + 2u;                  // = ctx->zobrist_len (prepare_hashing)
-  const size_t bytes = sizeof(uint64_t) * (4ull * zlen + (size_t)waves * (2ull * (maxwords + 3u) + slots));
-  return bytes <= 160u * 1024u ? bytes : 0;
-}
-
-// Every choice of the pass, from the longest sequence of the database alone (and the two switches): what
-// swa_d1_fastidious_shard launches and what swa_d1_fastidious_plan reports.
+// Every choice of the pass, from the longest sequence of the database alone (and the switches): what
+// swa_d1_fastidious_shard launches and what swa_d1_fastidious_plan reports (host_tables.cpp: swa_fast_plan_for).
 //   longest      pair kernel             count kernel
 //   < 112        none: every pair on the Bloom route
 //   112 .. 159   k_fast_pairs_lines<5>   k_fast_count_sites<5>   (a microvariant of 160 nt still fits 5 words)
@@ -2454,49 +2448,64 @@ static size_t fast_count_lds(uint32_t longest, uint32_t slots, int waves) {
 //   417 .. 779   k_fast_pairs            k_fast_count, 2 waves x 8192
 //   780 .. 1004  k_fast_pairs            k_fast_count, 1 wave x 16384
 //   >= 1005      none: k_fast_count's set no longer fits 160 KB; Bloom route, Zobrist table in LDS up to 3070 nt
-struct FastPlan {
-  bool pair_route;               // false: the Bloom route for every pair
-  int pair_w;                    // k_fast_pairs_lines<., W>: 5, 8, 13; 0 = k_fast_pairs on the packed words
-  int count_w;                   // k_fast_count_sites<W>: 5, 8; 0 = k_fast_count
-  int count_waves;               // k_fast_count: waves per block, slots of a wave's set, dynamic LDS
-  uint32_t slots;
-  size_t count_lds;
-  bool zobrist_lds;              // Bloom route: the Zobrist table sits in LDS
-};
+// SWA_FAST_LONG=split, longest > cap (= 1004, swa_fast_cap): the row of pair_longest, the longest sequence <= cap, with
+// k_fast_pairs as the pair kernel, for the pairs whose two lengths lie in [112, cap]; the Bloom route for every other pair.
+using FastPlan = swa_fast_plan;
 
-static FastPlan fast_plan(const swa_ctx * ctx) {
-  const uint32_t longest = ctx->db.longest;
-  FastPlan p{};
-  // which pairs the pair route can take: k_fast_count's LDS set must hold the microvariants of the longest sequence
-  p.slots = 1024;
-  { const uint64_t v = 7ull * longest + 4ull; while (p.slots < v + v / 2) { p.slots <<= 1; } }
-  for (int w : {4, 2, 1}) { if (p.count_waves == 0 && fast_count_lds(longest, p.slots, w) != 0) { p.count_waves = w; } }
-  p.count_lds = p.count_waves != 0 ? fast_count_lds(longest, p.slots, p.count_waves) : 0;
+// pair_longest, and how many amplicons are longer than the cap / can be half of a pair with one that is: a fact of the
+// uploaded database, read once
+static int ensure_length_classes(swa_ctx * ctx) {
+  if (ctx->fast_classes_ready) { return SWA_OK; }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
+  auto * out = reinterpret_cast<uint32_t *>(static_cast<uint64_t *>(ctx->d_fcounters.ptr) + 12);
+  SWA_HIP(ctx, hipMemsetAsync(out, 0, 4 * sizeof(uint32_t), ctx->stream));
+  hipLaunchKernelGGL(k_fast_length_classes, dim3(grid_for(ctx, ctx->db.n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n,
+                     swa_fast_cap(), out);
+  SWA_HIP(ctx, hipGetLastError());
+  uint32_t host[4] = {};
+  SWA_HIP(ctx, hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->fast_pair_longest = host[0]; ctx->fast_n_long = host[1]; ctx->fast_n_band = host[2];
+  ctx->fast_classes_ready = true;
+  return SWA_OK;
+}
+
+static int fast_plan(swa_ctx * ctx, FastPlan & p) {
   const char * env_route = getenv("SWA_FAST_BLOOM");          // test hook: the reference's scheme for every pair
-  p.pair_route = p.count_waves != 0 && longest >= kFastMinLen && !(env_route != nullptr && env_route[0] == '1');
-  // pairs on the amplicon lines, sequences in registers (up to 416 nt; SWA_FAST_PAIRS=words: the round-2 kernel, which
-  // walks the packed sequences — comparison switch)
-  const char * env_fp = getenv("SWA_FAST_PAIRS");
-  // (the register kernels exist for 5, 8 and 13 words: sequences up to 416 nt, which 128-byte lines hold)
-  p.pair_w = (env_fp != nullptr && env_fp[0] == 'w') ? 0 : (longest <= 160u ? 5 : (longest <= 256u ? 8 : (longest <= 416u ? 13 : 0)));
-  p.count_w = longest <= 159u ? 5 : (longest <= 255u ? 8 : 0);
-  p.zobrist_lds = 4ull * ((size_t)longest + 2u) * sizeof(uint64_t) <= kMaxZobristLds;
-  return p;
+  const char * env_fp = getenv("SWA_FAST_PAIRS");             // =words: the round-2 pair kernel, which walks the packed sequences — comparison switch
+  const char * env_long = getenv("SWA_FAST_LONG");            // =split: keep the pair route for the pairs up to the cap when longer sequences exist
+  const bool bloom = env_route != nullptr && env_route[0] == '1';
+  const bool split = env_long != nullptr && strcmp(env_long, "split") == 0 && !bloom && ctx->db.longest > swa_fast_cap();
+  uint32_t pair_longest = 0;
+  if (split) { SWA_TRY(ensure_length_classes(ctx)); pair_longest = ctx->fast_pair_longest; }
+  p = swa_fast_plan_for(ctx->db.longest, pair_longest, split, bloom, env_fp != nullptr && env_fp[0] == 'w');
+  return SWA_OK;
 }
 
 extern "C" int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
   if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_plan: no database is resident"); }
-  const FastPlan p = fast_plan(ctx);
-  const bool set = p.pair_route && p.count_w == 0;           // k_fast_count runs
-  out[0] = p.pair_route ? 1u : 0u;
-  out[1] = p.pair_route ? (uint32_t)p.pair_w : 0u;
-  out[2] = p.pair_route ? (uint32_t)p.count_w : 0u;
-  out[3] = set ? (uint32_t)p.count_waves : 0u;
-  out[4] = set ? p.slots : 0u;
-  out[5] = set ? (uint32_t)p.count_lds : 0u;
-  out[6] = p.zobrist_lds ? 1u : 0u;
-  out[7] = kFastMinLen;
+  FastPlan p{};
+  SWA_TRY(fast_plan(ctx, p));
+  swa_fast_plan_report(p, out);
+  return SWA_OK;
+}
+
+// The report reads the length classes whenever the longest sequence exceeds the cap, with or without the switch: its
+// first call after an upload then launches k_fast_length_classes and waits for it; later calls read the cached values.
+extern "C" int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]) {
+  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
+  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_split: no database is resident"); }
+  FastPlan p{};
+  SWA_TRY(fast_plan(ctx, p));
+  const uint32_t cap = swa_fast_cap();
+  const bool longer = ctx->db.longest > cap;
+  if (longer) { SWA_TRY(ensure_length_classes(ctx)); }
+  out[0] = p.split ? 1u : 0u;
+  out[1] = cap;
+  out[2] = longer ? ctx->fast_pair_longest : ctx->db.longest;
+  out[3] = longer ? ctx->fast_n_long : 0u;
   return SWA_OK;
 }
 
@@ -2560,7 +2569,7 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
       const uint32_t tiles = (uint32_t)((asize + kScanTile - 1) / kScanTile);
       FastGroupArgs g{};
       g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen;
-      g.role = static_cast<const uint8_t *>(ctx->d_frole.ptr); g.n = n;
+      g.role = static_cast<const uint8_t *>(ctx->d_frole.ptr); g.n = n; g.max_len = plan.max_len;
       g.keys = keys; g.cnt_l = cnt_l; g.cnt_h = cnt_h; g.amask = asize - 1; g.lslot = lslot; g.hslot = hslot; g.overflow = dflags + 8;
       const dim3 gn(grid_for(ctx, n, 256, 8)), ga(grid_for(ctx, asize, 256, 8)), b(256);
       hipLaunchKernelGGL(k_fg_clear, ga, b, 0, ctx->stream, keys, cnt_l, cnt_h, cur_l, cur_h, asize);
@@ -2620,7 +2629,11 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     FastCountArgs c{};
     c.seqs = ctx->db.seqs; c.seq_off = ctx->db.seq_off; c.seqlen = ctx->db.seqlen;
     c.zobrist = static_cast<const uint64_t *>(ctx->d_zobrist.ptr);
-    c.zlen = ctx->zobrist_len; c.maxwords = (ctx->db.longest + 31u) >> 5; c.slots = slots;
+    // the longest sequence a pair can hold: the database's, under the split pair_longest (k_fg_light / k_fg_heavy keep longer
+    // ones out of every group).  prepare_hashing lays the Zobrist table out by position, four values each, drawn in that
+    // order (host_tables.cpp: swa_zobrist_table): its first 4 * zlen words ARE the table of a database whose longest sequence
+    // is plan.served, so k_fast_count stages a prefix.
+    c.zlen = plan.served + 2u; c.maxwords = (plan.served + 31u) >> 5; c.slots = slots;
     c.pairs = static_cast<const unsigned long long *>(ctx->d_fpairs.ptr); c.npairs = npairs;
     c.graft = static_cast<uint32_t *>(ctx->d_graft.ptr); c.cand_counter = fc + 2;
     if (plan.count_w != 0) {
@@ -2689,10 +2702,12 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   });
   const uint64_t n_heavy = hi - lo;
 
-  const FastPlan plan = fast_plan(ctx);
+  FastPlan plan{};
+  SWA_TRY(fast_plan(ctx, plan));
   const bool pair_route = plan.pair_route;
   for (uint64_t & t : ctx->fast_totals) { t = 0; }
   const uint32_t min_len = pair_route ? kFastMinLen : 0xFFFFFFFFu;
+  const uint32_t max_len = plan.max_len;                     // (0xFFFFFFFF without the split)
 
   SWA_TRY(swa_reserve(ctx, ctx->d_frole, n));
   SWA_TRY(swa_reserve(ctx, ctx->d_light, n));
@@ -2707,21 +2722,22 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
   for (int slot : {5, 6}) { ctx->ev_used[slot] = false; }
 
-  // the log's variant totals, and the amplicons that can be part of a pair with a short sequence
+  // the log's variant totals, and the amplicons that can be part of a pair the pair route does not take
   hipLaunchKernelGGL(k_fast_variant_totals, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                      ctx->db.seqlen, static_cast<const uint8_t *>(ctx->d_frole.ptr), n, fc);
   const uint32_t short_cut = pair_route ? kFastMinLen + 1u : 0xFFFFFFFFu;   // len <= cut: may pair with a sequence < kFastMinLen
-  hipLaunchKernelGGL(k_fast_short_lists, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen,
-                     static_cast<const uint8_t *>(ctx->d_frole.ptr), n, short_cut, static_cast<uint8_t *>(ctx->d_light.ptr),
+  const uint32_t long_cut = plan.split ? max_len - 1u : 0xFFFFFFFFu;        // len >= cut: may pair with a sequence > the cap
+  hipLaunchKernelGGL(k_fast_band_lists, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen,
+                     static_cast<const uint8_t *>(ctx->d_frole.ptr), n, short_cut, long_cut, static_cast<uint8_t *>(ctx->d_light.ptr),
                      static_cast<uint32_t *>(ctx->d_list_a.ptr), static_cast<uint32_t *>(ctx->d_list_b.ptr), fc + 6);
   SWA_HIP(ctx, hipGetLastError());
-  uint64_t shorts[3] = {0, 0, 0};
-  SWA_HIP(ctx, hipMemcpyAsync(shorts, fc + 6, sizeof(shorts), hipMemcpyDeviceToHost, ctx->stream));
+  uint64_t bands[3] = {0, 0, 0};                             // light / heavy amplicons of the two bands, the lights' nucleotides
+  SWA_HIP(ctx, hipMemcpyAsync(bands, fc + 6, sizeof(bands), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (role is a host temporary, too)
 
   if (pair_route) { SWA_TRY(fastidious_pair_route(ctx, (uint32_t)n_light, (uint32_t)n_heavy, plan)); }
-  if (shorts[0] != 0 && shorts[1] != 0) {
-    SWA_TRY(fastidious_bloom_route(ctx, (uint32_t)shorts[0], (uint32_t)shorts[1], shorts[2], bloom_bits, min_len, plan.zobrist_lds));
+  if (bands[0] != 0 && bands[1] != 0) {
+    SWA_TRY(fastidious_bloom_route(ctx, (uint32_t)bands[0], (uint32_t)bands[1], bands[2], bloom_bits, min_len, max_len, plan.zobrist_lds));
   }
 
   uint64_t host_fc[8] = {};

@@ -28,8 +28,11 @@
 //      probed against it, matches verified on the materialised microvariants: |V1(h) ∩ V1(x)| exactly.
 // Pairs with a sequence shorter than kFastMinLen keep the Bloom route (k_d1_flex / k_d1_probe<MODE 1>,
 // restricted to them).  HBM traffic: the members' packed sequences, a few times, from L2.
+// SWA_FAST_LONG=split adds the same division at the long end: k_fast_count's LDS set holds the microvariants of a
+// sequence of up to cap = 1004 nt (swa_fast_cap), so where longer sequences exist the groups are made of the amplicons
+// of kFastMinLen .. cap nt only (FastGroupArgs.max_len) and the pairs with a longer member keep the Bloom route too.
 
-constexpr uint32_t kFastMinLen = 112;     // both sequences at least this long => the pair route is complete
+constexpr uint32_t kFastMinLen = SWA_FAST_MIN_LEN;   // (112) both sequences at least this long => the pair route is complete
 constexpr uint32_t kFastMid = 40;         // middle window of a heavy amplicon: [40, 72); light: 39, 40, 41
 constexpr uint32_t kFastStride = 64;      // a group's tiles are dealt round-robin to at most this many items
 constexpr uint32_t kFastStage = 256;      // per-wave staging of found pairs (one global atomic per flush)
@@ -58,6 +61,7 @@ struct FastGroupArgs {
   const uint32_t * seqlen;
   const uint8_t * role;          // 0 light, 1 heavy (this shard), 2 not taking part
   uint32_t n;
+  uint32_t max_len;              // longer amplicons join no group (0xFFFFFFFF: no bound)
   unsigned long long * keys;     // [asize]
   uint32_t * cnt_l, * cnt_h;     // [asize]
   uint64_t amask;
@@ -82,7 +86,7 @@ __global__ __launch_bounds__(256) void k_fg_light(const FastGroupArgs a) {
 #pragma unroll
     for (uint32_t j = 0; j < NK; ++j) { slots[j] = kEmpty; }
     const uint32_t len = a.seqlen[i];
-    if (a.role[i] == 0u && len >= kFastMinLen) {
+    if (a.role[i] == 0u && len >= kFastMinLen && len <= a.max_len) {
       const uint64_t * s = a.seqs + a.seq_off[i];
       uint64_t key[NK];
 #pragma unroll
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void k_fg_heavy(const FastGroupArgs a) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
     uint32_t slot = kEmpty;
     const uint32_t len = a.seqlen[i];
-    if (a.role[i] == 1u && len >= kFastMinLen) {
+    if (a.role[i] == 1u && len >= kFastMinLen && len <= a.max_len) {
       const uint64_t key = fast_key<TYPE>(a.seqs + a.seq_off[i], len, kFastMid);
       uint64_t idx = mix64(key) & a.amask;
       for (uint64_t probes = 0; probes <= a.amask; ++probes) {
@@ -684,12 +688,13 @@ __global__ __launch_bounds__(kThreads) void k_fast_count_sites(const FastCountAr
   if (lane == 0 && total != 0ull) { atomicAdd(a.cand_counter, total); }
 }
 
-// Amplicons that can be half of a pair with a sequence shorter than kFastMinLen (len <= cut): flags for the
+// Amplicons that can be half of a pair the pair route does not take — with a sequence shorter than kFastMinLen
+// (len <= short_cut) or, under the split, longer than the cap (len >= long_cut; 0xFFFFFFFF: no such band): flags for the
 // light-only table, id lists for the Bloom route; out[0] lights, out[1] heavies, out[2] nucleotides of the lights
-__global__ __launch_bounds__(256) void k_fast_short_lists(const uint32_t * __restrict__ seqlen, const uint8_t * __restrict__ role,
-                                                          uint32_t n, uint32_t cut, uint8_t * __restrict__ is_member,
-                                                          uint32_t * __restrict__ light_list, uint32_t * __restrict__ heavy_list,
-                                                          unsigned long long * out) {
+__global__ __launch_bounds__(256) void k_fast_band_lists(const uint32_t * __restrict__ seqlen, const uint8_t * __restrict__ role,
+                                                         uint32_t n, uint32_t short_cut, uint32_t long_cut, uint8_t * __restrict__ is_member,
+                                                         uint32_t * __restrict__ light_list, uint32_t * __restrict__ heavy_list,
+                                                         unsigned long long * out) {
   const int lane = threadIdx.x & 63;
   const uint64_t lane_lt = (1ull << lane) - 1ull;
   const uint32_t stride = gridDim.x * blockDim.x;
@@ -700,8 +705,9 @@ __global__ __launch_bounds__(256) void k_fast_short_lists(const uint32_t * __res
     if (i < n) {
       len = seqlen[i];
       const uint32_t r = role[i];
-      is_l = r == 0u && len <= cut;
-      is_h = r == 1u && len <= cut;
+      const bool band = len <= short_cut || len >= long_cut;
+      is_l = r == 0u && band;
+      is_h = r == 1u && band;
       is_member[i] = is_l ? 1 : 0;
     }
     const uint64_t ml = __ballot(is_l), mh = __ballot(is_h);
@@ -718,6 +724,29 @@ __global__ __launch_bounds__(256) void k_fast_short_lists(const uint32_t * __res
       base = swa_shfl_u64(base, 0);
       if (is_h) { heavy_list[base + (uint64_t)__popcll(mh & lane_lt)] = i; }
     }
+  }
+}
+
+// The lengths of the database against the pair route's cap: out[0] the longest sequence <= cap (0: none), out[1] the
+// amplicons longer than cap, out[2] those of cap - 1 nt or more (which can be half of a pair with a longer one).  One
+// atomic per wave and value.
+__global__ __launch_bounds__(256) void k_fast_length_classes(const uint32_t * __restrict__ seqlen, uint32_t n, uint32_t cap,
+                                                             uint32_t * out) {
+  uint32_t best = 0, n_long = 0, n_band = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t len = seqlen[i];
+    if (len <= cap) { best = max(best, len); } else { ++n_long; }
+    if (len + 1u >= cap) { ++n_band; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
+    n_long += (uint32_t)__shfl_xor((int)n_long, o, 64);
+    n_band += (uint32_t)__shfl_xor((int)n_band, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0u) {
+    if (best != 0u) { atomicMax(out + 0, best); }
+    if (n_long != 0u) { atomicAdd(out + 1, n_long); }
+    if (n_band != 0u) { atomicAdd(out + 2, n_band); }
   }
 }
 

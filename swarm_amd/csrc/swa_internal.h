@@ -131,7 +131,11 @@ struct swa_ctx {
   // work items, the (heavy, light) pairs within two edits
   swa_dbuf d_frole, d_fkeys, d_fcnt, d_foff, d_fslot, d_fmembers, d_fitems, d_fpairs;
   uint64_t fast_pair_cap = 0;
-  uint64_t fast_totals[4] = {};  // of the last pass: pairs found, short light / heavy amplicons, attempts of the pair list
+  uint64_t fast_totals[4] = {};  // of the last pass: pairs found, light / heavy amplicons of the Bloom route's bands, attempts of the pair list
+  // length classes of the database against the pair route's cap (k_fast_length_classes; read once per upload, and only
+  // where the longest sequence exceeds the cap: by the pass under SWA_FAST_LONG=split, by swa_d1_fastidious_split always): the longest sequence <= cap (0: none), amplicons > cap, amplicons >= cap - 1
+  bool fast_classes_ready = false;
+  uint32_t fast_pair_longest = 0, fast_n_long = 0, fast_n_band = 0;
 
   // d >= 2 in bulk (dn_graph.hip): the graph of all pairs within d differences, kept sorted on the device
   uint32_t dn_shortest = 0;      // shortest sequence of the database (0 = not measured yet)
@@ -233,6 +237,28 @@ inline void swa_t1(swa_ctx * ctx, int slot) {
 void swa_zobrist_table(uint32_t zobrist_len, std::vector<uint64_t> & tab);    // src/zobrist.cc:49-80
 void swa_bloom_patterns(uint32_t count, uint32_t k, std::vector<uint64_t> & pat); // src/bloompat.cc:74-90, src/bloomflex.cc:72-88
 uint64_t swa_hashtable_size(uint64_t n);                                       // src/utils/hashtable_size.cc:29-42
+
+// Every choice of the --fastidious pass (host_tables.cpp: pure arithmetic; d1.hip launches from it, swa_d1_fastidious_plan
+// and swa_d1_fastidious_plan_for report it)
+#define SWA_FAST_MIN_LEN 112u                       // both sequences at least this long => the pair route is complete (d1_fast.inc)
+#define SWA_MAX_ZOBRIST_LDS (96u * 1024u)           // the Zobrist table sits in LDS up to this many bytes
+struct swa_fast_plan {
+  bool pair_route;               // false: the Bloom route for every pair
+  int pair_w;                    // k_fast_pairs_lines<., W>: 5, 8, 13; 0 = k_fast_pairs on the packed words
+  int count_w;                   // k_fast_count_sites<W>: 5, 8; 0 = k_fast_count
+  int count_waves;               // k_fast_count: waves per block, slots of a wave's set, dynamic LDS
+  uint32_t slots;
+  size_t count_lds;
+  bool zobrist_lds;              // Bloom route: the Zobrist table sits in LDS
+  bool split;                    // SWA_FAST_LONG=split in effect: pairs with a member longer than max_len take the Bloom route
+  uint32_t served;               // the longest sequence the pair route holds: the database's, under the split pair_longest
+  uint32_t max_len;              // the longest sequence the pair route takes (0xFFFFFFFF without the split)
+};
+size_t swa_fast_count_lds(uint32_t longest, uint32_t slots, int waves);
+uint32_t swa_fast_count_slots(uint32_t longest);
+uint32_t swa_fast_cap();
+swa_fast_plan swa_fast_plan_for(uint32_t longest, uint32_t pair_longest, bool split, bool bloom, bool words);
+void swa_fast_plan_report(const swa_fast_plan & p, uint32_t out[8]);
 
 // ---- device helpers -------------------------------------------------------------
 #ifdef __HIPCC__
