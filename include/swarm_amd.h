@@ -172,8 +172,9 @@ uint32_t swa_d1_anchor_width(const swa_ctx * ctx);
    of once per rank —, its share of the seeds only the plain kernel can serve, and, when the
    anchored route is not in use, the seeds with id mod world == rank.  swa_d1_network[_device]
    over a range then returns the PARTIAL rows of that range; over all ranks every link of the
-   network appears exactly once (the host redistributes them: swarm_amd/sharding.py, and
-   swa_d1_network_edges_device below for the form that travels).
+   network appears exactly once (they are redistributed by source range: swa_d1_network_edges_device below for the
+   form that travels, swa_d1_links_split / swa_d1_csr_from_lists for the two ends of the exchange,
+   swarm_amd/sharding.py for the collectives between them).
    world = 1 restores the complete network.  Takes effect at the next network call.
    An index build made under ownership contains only what the rank's groups need: hashes of their
    members, duplicates found inside the owned prefix groups (identical sequences share one, so
@@ -228,6 +229,44 @@ int swa_d1_network_device(swa_ctx * ctx, int no_cluster_breaking, uint32_t first
    size.  cap = capacity in entries; SWA_E_CAPACITY / *total as above. */
 int swa_d1_network_edges_device(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, uint32_t count,
                                 uint64_t * d_edge_list, uint64_t cap, uint64_t * total);
+/* The link exchange of a multi-GPU job on the device (no reference counterpart: its threads share one network array,
+   src/algod1.cc:630-670).  Under swa_d1_set_ownership every rank holds the links of the anchor groups it owns, whichever
+   amplicons they start from (swa_d1_network_edges_device); the final partition gives every rank a contiguous range of
+   sources.  Three steps: split the rank's list by destination (swa_d1_links_split), exchange the runs all-to-all (RCCL /
+   torch.distributed: 8 bytes per link, no link travels twice), assemble what arrived into the rank's slice of the CSR
+   (swa_d1_csr_from_lists).  Neither call needs a database on the context.
+
+   swa_d1_links_split: d_links = m links (source << 32 | target) on the device; d_links, d_out and d_counts must be
+   8-byte aligned (SWA_E_ARG otherwise); bounds = world + 1 ascending
+   ids on the HOST, bounds[0] = 0: rank r owns the sources [bounds[r], bounds[r + 1]) — ranks that own nothing are fine;
+   world = 1 .. 64.  d_out (m entries) receives the links grouped by destination, run r beginning at the sum of
+   d_counts[0 .. r), in no particular order inside a run; d_counts (world + 1 entries, device) the size of every run and, in
+   [world], the links whose source is >= bounds[world]: those are written nowhere, and the call returns SWA_E_ARG.  d_out
+   must not overlap d_links.  Stream-ordered on the context's stream, two kernel launches (none when m = 0: only the
+   clear of d_counts), and then ONE 8-byte read of d_counts[world] on which the call waits (m = 0: it waits for the
+   clear): d_out and d_counts are complete when it returns, whatever m (a caller needs the counts on the host next
+   anyway, to size the exchange). */
+int swa_d1_links_split(swa_ctx * ctx, const uint64_t * d_links, uint64_t m, const uint32_t * bounds, uint32_t world,
+                       uint64_t * d_out, uint64_t * d_counts);
+/* swa_d1_csr_from_lists: the CSR of the sources [first, first + count) from `lists` runs of links in one device buffer,
+   run r = d_links[starts[r] .. starts[r] + counts[r]) (starts / counts on the HOST; runs may lie anywhere, be empty, and
+   hold their links in any order).  Row i of the result is source first + i: d_offsets[count + 1] beginning at 0,
+   d_neighbours ascending within a row.  Capacity protocol of swa_d1_network_device: the offsets are always complete,
+   *total = entries needed (the sum of the counts: every link lands in a row), SWA_E_CAPACITY when it exceeds cap — call
+   again with room; d_neighbours may be NULL with cap = 0.  Only enqueues (after the upload of starts / counts).
+   The call works in the context's own scratch of the d = 1 step (the partition buffers, the segment table, the words
+   "last CSR offset / links sorted" of the status block, timing slots 13 and 14): use it between the d = 1 calls of a
+   context, as any other call on it, never from a second thread while one of them runs, and do not expect
+   swa_timing_read's CSR slots to describe the last network call afterwards.
+   Every source must lie in [first, first + count).  One that does not yields a wrong network but no write outside the
+   buffers: with B = ceil(log2(count)), every partition level forms its bin as ((source - first) >> shift) & (bins - 1)
+   and the row kernels their row as (source - first) & (rows - 1), so such a link is filed under the source congruent
+   to it modulo 2^B; bins and rows are always inside their tables, the places of the links inside the count of links
+   (each level is a counting sort of exactly the links it was given), d_offsets is written for rows below count only
+   and d_neighbours below cap only.  (swa_d1_links_split + the exchange deliver in-range sources by construction.) */
+int swa_d1_csr_from_lists(swa_ctx * ctx, const uint64_t * d_links, const uint64_t * starts, const uint64_t * counts,
+                          uint32_t lists, uint32_t first, uint32_t count, uint64_t * d_offsets, uint32_t * d_neighbours,
+                          uint64_t cap, uint64_t * total);
 /* The guard (SWA_E_INTERNAL).  The reference's network thread cannot return a partial network
    (src/algod1.cc:630-670); the three calls above compare the counts their kernels hand to one another and,
    should they not balance, make everything derived from the uploaded database again and repeat the step ONCE
@@ -468,7 +507,7 @@ int swa_dn_graph_totals(swa_ctx * ctx, uint64_t * out3);
    ownership of anchor groups (swa_d1_set_ownership): routed index build (every rank keys its own slice and the key
    records travel to their owners, grouped ncclSend / ncclRecv over xGMI), every rank's flat link list gathered on
    rank 0 only (grouped ncclSend / ncclRecv: the one consumer of the network is the host behind rank 0), CSR assembled
-   there on the device; fastidious: heavy amplicons split, graft_cand combined with ncclAllReduce(min).  librccl.so is
+   there on the device (swa_d1_csr_from_lists over the whole range, the ranks' lists as its runs); fastidious: heavy amplicons split, graft_cand combined with ncclAllReduce(min).  librccl.so is
    loaded when the first handle with ranks on distinct devices is created, not with the library.  A device may be listed more than once (several ranks on one GPU: the exchange then uses
    device-to-device copies — RCCL admits one rank per GPU); results never depend on the device list. */
 typedef struct swa_multi swa_multi;

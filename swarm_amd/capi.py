@@ -75,6 +75,7 @@ EXPORTS = [
     "swa_d1_network_resident", "swa_d1_network_fetch", "swa_d1_cluster_device", "swa_d1_cluster_fetch", "swa_d1_cluster_maxgen", "swa_d1_cluster_resident", "swa_d1_cluster_resident_lazy", "swa_d1_result_detach", "swa_d1_result_error", "swa_d1_result_prepare",
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
+    "swa_d1_links_split", "swa_d1_csr_from_lists",
     "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_qgram_build", "swa_qgram_diff",
     "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
@@ -118,6 +119,9 @@ def load_library() -> C.CDLL:
     lib.swa_d1_network_device.argtypes = lib.swa_d1_network.argtypes
     lib.swa_d1_network_edges_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                                 C.POINTER(C.c_uint64)]
+    lib.swa_d1_links_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u32p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.swa_d1_csr_from_lists.argtypes = [C.c_void_p, C.c_void_p, u64p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_uint64, u64p]
     lib.swa_d1_set_ownership.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     lib.swa_d1_route_slice.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.swa_d1_index_build_routed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
@@ -200,6 +204,11 @@ def _ptr(a) -> int:
     if hasattr(a, "data_ptr"):
         return int(a.data_ptr())
     return int(a.ctypes.data)
+
+
+def _dev(a) -> int:
+    """A device address: a raw pointer (int) as it is, else _ptr()."""
+    return int(a) if isinstance(a, int) else _ptr(a)
 
 
 class HostDb:
@@ -610,6 +619,35 @@ class Context:
         total = C.c_uint64(0)
         self._check(self.lib.swa_d1_network_edges_device(self.h, int(no_cluster_breaking), first, count,
                                                          _ptr(d_edge_list), cap, C.byref(total)))
+        return int(total.value)
+
+    def d1_links_split(self, d_links, m: int, bounds, d_out, d_counts) -> None:
+        """The link exchange of a multi-GPU job, first half (swa_d1_links_split): the first m links of d_links
+        (source << 32 | target) grouped by the rank that owns their source — rank r owns [bounds[r], bounds[r + 1]);
+        bounds: world + 1 ascending ids on the host, bounds[0] = 0.  d_out [m] receives the runs, run r beginning at
+        sum(d_counts[:r]); d_counts [world + 1] their sizes and, in [world], the links no rank owns (SwaError SWA_E_ARG
+        then; they are written nowhere).  d_links / d_out / d_counts: 64-bit torch tensors on the context's device or raw
+        device pointers; complete on return."""
+        b = np.ascontiguousarray(bounds, dtype=np.uint32)
+        self._check(self.lib.swa_d1_links_split(self.h, C.c_void_p(_dev(d_links)), int(m), b.ctypes.data_as(u32p), len(b) - 1,
+                                                C.c_void_p(_dev(d_out)), C.c_void_p(_dev(d_counts))))
+
+    def d1_csr_from_lists(self, d_links, starts, counts, first: int, count: int, d_offsets, d_neighbours, cap: int) -> int:
+        """... second half (swa_d1_csr_from_lists): the CSR of the sources [first, first + count) from runs of links in one
+        device buffer, run r = d_links[starts[r]: starts[r] + counts[r]] (host sequences).  d_offsets [count + 1] (64-bit,
+        beginning at 0) is always complete; d_neighbours (32-bit, ascending within a row; None with cap = 0) is written up
+        to cap entries.  Returns the entries needed; when they exceed cap raises SwaError(SWA_E_CAPACITY) whose `total`
+        attribute holds the need.  Tensors on the context's device or raw device pointers."""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        ct = np.ascontiguousarray(counts, dtype=np.uint64)
+        assert st.shape == ct.shape and st.ndim == 1
+        total = C.c_uint64(0)
+        rc = self.lib.swa_d1_csr_from_lists(self.h, C.c_void_p(_dev(d_links)), _p64(st), _p64(ct), len(st), int(first), int(count),
+                                            C.c_void_p(_dev(d_offsets)), C.c_void_p(_dev(d_neighbours)), int(cap), C.byref(total))
+        if rc != SWA_OK:
+            err = SwaError(rc, self.lib.swa_last_error(self.h).decode())
+            err.total = int(total.value)
+            raise err
         return int(total.value)
 
     def d1_table_size(self) -> int:

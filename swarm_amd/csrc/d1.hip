@@ -2121,29 +2121,84 @@ extern "C" int swa_d1_network_edges_device(swa_ctx * ctx, int no_cluster_breakin
   return network_run_guarded(ctx, no_cluster_breaking, first, count, nullptr, nullptr, d_edge_list, cap, total);
 }
 
-// multi.hip: the CSR of the whole database from the ranks' link lists as they lie gathered on this device — `lists` runs of
-// (source << 32 | target) links, run r = d_links[starts[r] .. + counts[r]) — by the partition + row kernels of the
-// single-GPU step (two levels by source bits, then a wave per 256 sources) instead of a 64-bit radix sort of everything.
-// Leaves offsets [n + 1] and, if they fit `cap`, the neighbours (rows ascending) in the caller's device buffers.
-int swa_d1_csr_from_lists(swa_ctx * ctx, const unsigned long long * d_links, const uint64_t * starts, const uint64_t * counts, uint32_t lists,
-                          uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap) {
+// The link exchange of a multi-GPU job, second half (include/swarm_amd.h): the CSR of the sources [first, first + count)
+// from `lists` runs of (source << 32 | target) links as they lie on this context's device — the pieces a rank received, or
+// the ranks' lists gathered on one device (multi.hip) — by the partition + row kernels of the single-GPU step (levels by
+// source bits, then a wave per 256 sources) instead of a 64-bit radix sort of everything.  Every link lands in a row, so the
+// need is the sum of the counts: known before anything is launched, and nothing is read back.
+extern "C" int swa_d1_csr_from_lists(swa_ctx * ctx, const uint64_t * d_links, const uint64_t * starts, const uint64_t * counts, uint32_t lists,
+                                     uint32_t first, uint32_t count, uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap, uint64_t * total) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (count == 0 || (uint64_t)first + count > 0x100000000ull || d_offsets == nullptr || total == nullptr || (d_neighbours == nullptr && cap != 0) ||
+      (lists != 0 && (starts == nullptr || counts == nullptr))) {
+    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_csr_from_lists: bad range or null buffer");
+  }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t n = ctx->db.n;
+  const uint32_t chunks = std::max<uint32_t>(lists, 1u);      // (no list: one without links)
   uint64_t all = 0, tiles = 2;
-  std::vector<uint64_t> h_start(lists);
-  std::vector<uint32_t> h_size(lists);
+  std::vector<uint64_t> h_start(chunks, 0);
+  std::vector<uint32_t> h_size(chunks, 0);
   for (uint32_t r = 0; r < lists; ++r) {
     if (counts[r] > 0xFFFFFFFFull) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_csr_from_lists: a list of more than 2^32 links"); }
     h_start[r] = starts[r]; h_size[r] = (uint32_t)counts[r];
     all += counts[r]; tiles += (counts[r] + 4095) / 4096;
   }
-  SWA_TRY(swa_reserve(ctx, ctx->d_seg_base, ((uint64_t)lists * 3 / 2 + 2) * sizeof(uint64_t)));
+  if (all != 0 && d_links == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_csr_from_lists: null link buffer"); }
+  *total = all;
+  SWA_TRY(swa_reserve(ctx, ctx->d_seg_base, ((uint64_t)chunks * 3 / 2 + 2) * sizeof(uint64_t)));
   auto * d_start = static_cast<uint64_t *>(ctx->d_seg_base.ptr);
-  auto * d_size = reinterpret_cast<uint32_t *>(d_start + lists);
-  SWA_HIP(ctx, hipMemcpyAsync(d_start, h_start.data(), lists * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  SWA_HIP(ctx, hipMemcpyAsync(d_size, h_size.data(), lists * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  auto * d_size = reinterpret_cast<uint32_t *>(d_start + chunks);
+  SWA_HIP(ctx, hipMemcpyAsync(d_start, h_start.data(), chunks * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(d_size, h_size.data(), chunks * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the host vectors are temporaries)
-  return csr_from_chunks(ctx, 0, n, d_links, d_start, 0, d_size, lists, 0xFFFFFFFFu, tiles, all + 1, d_offsets, d_neighbours, cap);
+  SWA_TRY(csr_from_chunks(ctx, first, count, reinterpret_cast<const unsigned long long *>(d_links), d_start, 0, d_size, chunks, 0xFFFFFFFFu, tiles,
+                          all + 1, d_offsets, d_neighbours, cap));
+  if (all > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_csr_from_lists: neighbour buffer too small"); }
+  return SWA_OK;
+}
+
+// The link exchange, first half: a flat link list split by the rank that owns each link's source (d1_stream.inc: k_links_split).
+extern "C" int swa_d1_links_split(swa_ctx * ctx, const uint64_t * d_links, uint64_t m, const uint32_t * bounds, uint32_t world,
+                                  uint64_t * d_out, uint64_t * d_counts) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (world == 0 || world > kRouteMaxWorld || bounds == nullptr || d_counts == nullptr || (m != 0 && (d_links == nullptr || d_out == nullptr)) ||
+      ((reinterpret_cast<uintptr_t>(d_links) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_counts)) & 7u) != 0) {
+    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_links_split: bad argument (1..64 ranks, 8-byte aligned buffers)");
+  }
+  SplitArgs a{};
+  for (uint32_t r = 0; r <= world; ++r) {
+    if (r == 0 ? bounds[0] != 0 : bounds[r] < bounds[r - 1]) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_links_split: bounds must begin at 0 and ascend"); }
+    a.bounds[r] = bounds[r];
+  }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, ((uint64_t)world + 1) * sizeof(uint64_t), ctx->stream));
+  if (m == 0) {                                              // (nothing but the clear — and the counts are final on return here too)
+    SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SWA_OK;
+  }
+  // (the runs' cursors: bytes [2048, 2048 + 8 world) of the status block — swa_internal.h)
+  auto * cursor = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(ctx->d_status.ptr) + 2048);
+  SWA_HIP(ctx, hipMemsetAsync(cursor, 0, (uint64_t)world * sizeof(uint64_t), ctx->stream));
+  a.head = (uint32_t)((reinterpret_cast<uintptr_t>(d_links) >> 3) & 1u);
+  a.links = reinterpret_cast<const unsigned long long *>(d_links) - a.head;
+  a.end = a.head + m;
+  a.world = world;
+  a.counts = reinterpret_cast<unsigned long long *>(d_counts);
+  a.cursor = cursor;
+  a.out = reinterpret_cast<unsigned long long *>(d_out);
+  const uint64_t tiles = (a.end + kSplitTile - 1) / kSplitTile;
+  const dim3 grid((unsigned)std::min<uint64_t>(tiles, (uint64_t)ctx->num_cus * 8));
+  hipLaunchKernelGGL(k_links_split<false>, grid, dim3(kSplitThreads), 0, ctx->stream, a);
+  hipLaunchKernelGGL(k_links_split<true>, grid, dim3(kSplitThreads), 0, ctx->stream, a);
+  SWA_HIP(ctx, hipGetLastError());
+  // ONE read, of the links no rank owns, into the pinned mirror of the status block: the counts are final when this returns
+  auto * beyond = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(ctx->h_status) + 2048);
+  SWA_HIP(ctx, hipMemcpyAsync(beyond, d_counts + world, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (*beyond != 0) {
+    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_links_split: " + std::to_string(*beyond) + " links with a source beyond the last rank's range (not written)");
+  }
+  return SWA_OK;
 }
 
 extern "C" int swa_d1_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count, uint32_t world, uint32_t * d_ids, uint64_t cap,

@@ -151,6 +151,128 @@ __global__ __launch_bounds__(256) void k_anchor_route_records(const uint64_t * _
   }
 }
 
+// ---- link exchange of a multi-GPU job: a rank's flat link list split by the rank that owns each source -----------------------
+// (swa_d1_links_split.)  The owners' ranges are contiguous but arbitrary (sharding.partition_by_length), so the destination
+// of a link is found by a binary search of its source in the ranges' first ids, kept in LDS: six steps for up to 64 ranks —
+// where a 64-bit sort of the whole list used to make the destinations contiguous.  Two launches over tiles of 4096 links,
+// a lane reading two links at a time (16 bytes):
+//   <false>  counts: a histogram per workgroup in LDS over all its tiles, then ONE global atomic per destination it met;
+//   <true>   places: every workgroup turns the counts into the runs' first places (a scan over at most 64 values by one
+//            wave), and per tile: histogram in LDS whose atomic returns the link's rank among the tile's links of its
+//            destination, one global atomic per destination the tile met to reserve room in that run, the tile's links put
+//            in destination order in LDS and written as one contiguous piece per destination.
+// No global atomic per link.  A source >= bounds[world] is counted in counts[world] and written nowhere.
+struct SplitArgs {
+  const unsigned long long * links;  // 16-byte aligned: the caller's list begins `head` (0 or 1) entries behind it
+  uint32_t head;
+  uint64_t end;                      // head + links in the list
+  uint32_t world;
+  uint32_t bounds[kRouteMaxWorld + 1];   // rank r owns the sources [bounds[r], bounds[r + 1]); bounds[0] = 0
+  unsigned long long * counts;       // [world + 1] links per destination; [world]: sources beyond the last range
+  unsigned long long * cursor;       // [world] (places) links of every run that have their place so far
+  unsigned long long * out;          // [links]
+};
+constexpr uint32_t kSplitTile = 4096, kSplitThreads = 512;
+constexpr uint32_t kSplitPairs = kSplitTile / (2u * kSplitThreads);          // pairs of links a lane takes from a tile
+
+// the r with sb[r] <= src < sb[r + 1] (sb: the ranges' first ids, 0xFFFFFFFF behind the last rank; of equal ones — ranks that
+// own nothing — the last, whose range is the one that is not empty); `world` when no rank owns src
+__device__ __forceinline__ uint32_t split_dest(const uint32_t * sb, uint32_t beyond, uint32_t world, uint32_t src) {
+  if (src >= beyond) { return world; }
+  uint32_t pos = 0;
+#pragma unroll
+  for (uint32_t step = kRouteMaxWorld / 2u; step != 0u; step >>= 1) { if (sb[pos + step] <= src) { pos += step; } }
+  return pos;
+}
+
+template <bool PLACE>
+__global__ __launch_bounds__(kSplitThreads) void k_links_split(const SplitArgs a) {
+  __shared__ uint32_t sb[kRouteMaxWorld], hist[kRouteMaxWorld + 1], lstart[kRouteMaxWorld];
+  __shared__ unsigned long long gbase[kRouteMaxWorld];
+  __shared__ uint32_t present;
+  __shared__ __attribute__((aligned(16))) unsigned long long stage[PLACE ? kSplitTile : 1];
+  const uint32_t tid = threadIdx.x, world = a.world, beyond = a.bounds[world];
+  if (tid < kRouteMaxWorld) { sb[tid] = tid < world ? a.bounds[tid] : 0xFFFFFFFFu; }
+  if (tid <= kRouteMaxWorld) { hist[tid] = 0u; }
+  // (places) first place of run `tid`: the counts before it — lane d of the first wave keeps it
+  unsigned long long run_start = 0ull;
+  if (PLACE && tid < 64u) {
+    const unsigned long long mine = tid < world ? a.counts[tid] : 0ull;
+    unsigned long long incl = mine;
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) { const unsigned long long up = swa_shfl_up_u64(incl, d); if (tid >= d) { incl += up; } }
+    run_start = incl - mine;
+  }
+  __syncthreads();
+  const uint64_t links = a.end - a.head;
+  const uint64_t tiles = (a.end + kSplitTile - 1u) / kSplitTile;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    // the tile's links: pair k of the lane = entries j, j + 1 behind the aligned pointer, j even (one 16-byte load when both
+    // belong to the list; the list's first or last entry alone is read alone: nothing outside the list is touched)
+    unsigned long long rec[2u * kSplitPairs];
+    uint32_t valid = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kSplitPairs; ++k) {
+      const uint64_t j = t * kSplitTile + (uint64_t)k * (2u * kSplitThreads) + 2u * tid;
+      const bool v0 = j >= a.head && j < a.end, v1 = j + 1u < a.end;   // (j + 1 >= 1 >= head)
+      rec[2u * k] = rec[2u * k + 1u] = 0ull;
+      if (v0 && v1) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(a.links + j);
+        rec[2u * k] = (unsigned long long)q.x | (unsigned long long)q.y << 32;
+        rec[2u * k + 1u] = (unsigned long long)q.z | (unsigned long long)q.w << 32;
+      } else if (v0) { rec[2u * k] = a.links[j]; }
+      else if (v1) { rec[2u * k + 1u] = a.links[j + 1u]; }
+      valid |= (v0 ? 1u : 0u) << (2u * k) | (v1 ? 1u : 0u) << (2u * k + 1u);
+    }
+    uint32_t pos[2u * kSplitPairs];                              // destination << 16 | rank among the tile's links for it
+#pragma unroll
+    for (uint32_t k = 0; k < 2u * kSplitPairs; ++k) {
+      pos[k] = 0u;
+      if ((valid >> k & 1u) != 0u) {
+        const uint32_t d = split_dest(sb, beyond, world, (uint32_t)(rec[k] >> 32));
+        pos[k] = d << 16 | atomicAdd(&hist[d], 1u);
+        if (d == world) { valid &= ~(1u << k); }               // (counted, not placed)
+      }
+    }
+    if (!PLACE) { continue; }                                    // (the histogram runs on over the workgroup's tiles)
+    __syncthreads();
+    if (tid < 64u) {
+      // the tile's links per destination, where each destination's piece begins in the staging area, and the room
+      // reserved for it in its run
+      const uint32_t h = tid < world ? hist[tid] : 0u;
+      uint32_t incl = h;
+#pragma unroll
+      for (unsigned d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64); if (tid >= d) { incl += up; } }
+      lstart[tid] = incl - h;
+      if (h != 0u) { gbase[tid] = run_start + atomicAdd(&a.cursor[tid], (unsigned long long)h); }
+      if (tid == 63u) { present = incl; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < 2u * kSplitPairs; ++k) {
+      if ((valid >> k & 1u) != 0u) { stage[lstart[pos[k] >> 16] + (pos[k] & 0xFFFFu)] = rec[k]; }
+    }
+    __syncthreads();
+    const uint32_t staged = present;
+#pragma unroll
+    for (uint32_t k = 0; k < kSplitTile / kSplitThreads; ++k) {
+      const uint32_t j = k * kSplitThreads + tid;
+      if (j < staged) {
+        const unsigned long long r = stage[j];
+        const uint32_t d = split_dest(sb, beyond, world, (uint32_t)(r >> 32));
+        const uint64_t g = gbase[d] + (j - lstart[d]);
+        if (g < links) { a.out[g] = r; }                       // (always, when the list is what the counting launch saw)
+      }
+    }
+    if (tid <= kRouteMaxWorld) { hist[tid] = 0u; }
+    __syncthreads();
+  }
+  if (!PLACE) {
+    __syncthreads();
+    if (tid <= world && hist[tid] != 0u) { atomicAdd(&a.counts[tid], (unsigned long long)hist[tid]); }
+  }
+}
+
 struct KeyArgs {
   const uint4 * lines;               // line_quads quads per line
   uint32_t line_quads;

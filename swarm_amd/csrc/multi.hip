@@ -335,8 +335,10 @@ extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint
     SWA_TRY(swa_reserve(c0, c0->d_nb_tmp, (all + 1) * sizeof(uint32_t)));
     std::vector<uint64_t> starts((size_t)world, 0);
     for (int r = 1; r < world; ++r) { starts[(size_t)r] = starts[(size_t)r - 1] + count[(size_t)r - 1]; }
-    SWA_TRY(swa_d1_csr_from_lists(c0, keys_in, starts.data(), count.data(), (uint32_t)world, static_cast<uint64_t *>(c0->d_offsets_tmp.ptr),
-                                  static_cast<uint32_t *>(c0->d_nb_tmp.ptr), all + 1));
+    uint64_t need = 0;                                       // (= all: the buffer was sized for it, so SWA_E_CAPACITY cannot come back)
+    SWA_TRY(swa_d1_csr_from_lists(c0, reinterpret_cast<const uint64_t *>(keys_in), starts.data(), count.data(), (uint32_t)world, 0, n,
+                                  static_cast<uint64_t *>(c0->d_offsets_tmp.ptr), static_cast<uint32_t *>(c0->d_nb_tmp.ptr), all + 1, &need));
+    (void)need;
     SWA_HIP(c0, hipMemcpyAsync(offsets, c0->d_offsets_tmp.ptr, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c0->stream));
     if (all != 0 && all <= cap) {
       SWA_HIP(c0, hipMemcpyAsync(neighbours, c0->d_nb_tmp.ptr, all * sizeof(uint32_t), hipMemcpyDeviceToHost, c0->stream));

@@ -61,8 +61,9 @@ struct swa_ctx {
   // One 4 KB block holds every small status array of the context, so that the host reads them with ONE copy per phase (a
   // device-to-host copy of a few bytes is a kernel of its own, ~5 us with its gap: the step made nine):
   //   [0, 64) d_flags · [64, 192) d_stats · [192, 384) d_guard · [384, 512) d_extra: [0] last CSR offset [1] links the
-  //   partition sorted · [1024, 2048) d_acounters.  d_flags / d_stats / d_guard / d_acounters are VIEWS into it (never freed
-  //   on their own; their `bytes` is their room, so swa_reserve leaves them alone).
+  //   partition sorted · [1024, 2048) d_acounters · [2048, 2560) the run cursors of swa_d1_links_split (u64[64]).
+  //   d_flags / d_stats / d_guard / d_acounters are VIEWS into it (never freed on their own; their `bytes` is their room,
+  //   so swa_reserve leaves them alone).
   swa_dbuf d_status;
   void * h_status = nullptr;     // 4 KB of pinned host memory: where the d = 1 step looks at the status block
   swa_dbuf d_flags;              // u32[16]: [0] duplicate flag
@@ -207,10 +208,6 @@ int swa_hash_sequences(swa_ctx * ctx);                           // d1.hip: Zobr
 int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking);
 int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const uint32_t * svals, uint64_t nedges, uint64_t * offsets,
                       uint32_t * neighbours, uint8_t * diffs, uint64_t cap, uint64_t * total);
-
-// d1.hip, for multi.hip: CSR of the whole database from link lists gathered on this context's device (partition + row kernels)
-int swa_d1_csr_from_lists(swa_ctx * ctx, const unsigned long long * d_links, const uint64_t * starts, const uint64_t * counts, uint32_t lists,
-                          uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap);
 
 // RAII-less timing brackets: SWA_T0(ctx, slot) ... SWA_T1(ctx, slot)
 inline void swa_t0(swa_ctx * ctx, int slot) {

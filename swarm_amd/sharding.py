@@ -5,6 +5,9 @@ all-gather (RCCL over xGMI on GPUs — backend "nccl" IS RCCL on ROCm —, gloo 
 
 Everything here is backend-agnostic torch.distributed plumbing on tensors; the per-rank CSR
 comes from swa_d1_network_device on a GPU (bench.py) or from whatever the caller supplies.
+The one exception is the local work of exchange_owned_links on GPU tensors: the split by owner
+and the assembly of the received links are the library's kernels (swa_d1_links_split,
+swa_d1_csr_from_lists).
 """
 from __future__ import annotations
 
@@ -93,7 +96,59 @@ def allgather_csr(local_offsets: torch.Tensor, local_nb: torch.Tensor, local_tot
     return offsets, neighbours
 
 
-def exchange_owned_links(links: torch.Tensor, counts: list, group=None):
+# exchange_owned_links on GPU tensors without a caller's context: one helper Context per device, made at the first call
+_helper_contexts: dict = {}
+
+
+def _helper_context(dev: torch.device):
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    ctx = _helper_contexts.get(index)
+    if ctx is None:
+        from .capi import Context
+        ctx = _helper_contexts[index] = Context(index, torch.cuda.current_stream(dev).cuda_stream)
+    return ctx
+
+
+def _exchange_owned_links_device(links: torch.Tensor, counts: list, bounds: list, group, ctx):
+    """exchange_owned_links for links on a GPU: the library's split, the two collectives, the library's CSR assembly."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    dev = links.device
+    mine, first = counts[rank], bounds[rank]
+    if ctx is None:
+        ctx = _helper_context(dev)
+    # A context made for torch's default stream runs on a stream of its own (swa_ctx_create), so the two are joined on the
+    # host: torch's stream is waited for before each library call, the context's after the last (the split waits itself).
+    torch_stream = torch.cuda.current_stream(dev)
+    m = links.numel()
+    runs = torch.empty(m, dtype=torch.int64, device=dev)
+    # [0, world] this rank's run sizes and the links nobody owns (none: the split raises), behind them what the others send
+    sizes = torch.empty(2 * world + 1, dtype=torch.int64, device=dev)
+    torch_stream.synchronize()
+    ctx.d1_links_split(links, m, bounds, runs, sizes[:world + 1])
+    dist.all_to_all_single(sizes[world + 1:], sizes[:world], group=group)
+    sizes_host = sizes.tolist()                                # (the ONE host read: all_to_all_single takes host split sizes)
+    send_list, recv_list = sizes_host[:world], sizes_host[world + 1:]
+    total = sum(recv_list)
+    got = torch.empty(total, dtype=torch.int64, device=dev)
+    dist.all_to_all_single(got, runs, output_split_sizes=recv_list, input_split_sizes=send_list, group=group)
+    offsets = torch.empty(mine + 1, dtype=torch.int64, device=dev)
+    neighbours = torch.empty(total, dtype=torch.int32, device=dev)
+    if mine == 0:
+        assert total == 0
+        offsets.zero_()
+        return offsets, neighbours
+    starts, at = [], 0
+    for c in recv_list:
+        starts.append(at)
+        at += c
+    torch_stream.synchronize()
+    ctx.d1_csr_from_lists(got, starts, recv_list, first, mine, offsets, neighbours if total else None, total)
+    ctx.synchronize()
+    return offsets, neighbours
+
+
+def exchange_owned_links(links: torch.Tensor, counts: list, group=None, ctx=None):
     """Ownership sharding (swa_d1_set_ownership): every rank holds the links it found in the anchor
     groups it owns, as one flat list (swa_d1_network_edges_device), and every link of the network
     is held by exactly one rank.  The links are redistributed by contiguous seed range and turned
@@ -106,6 +161,16 @@ def exchange_owned_links(links: torch.Tensor, counts: list, group=None):
 
     Collectives: all-to-all of the split sizes (8 bytes per pair of ranks), all-to-all of the
     links (8 bytes each); no link travels twice.
+
+    Links on a GPU: the local work is the library's — Context.d1_links_split groups the links by
+    owner, Context.d1_csr_from_lists turns the received runs into the slice's CSR; no sort, search or
+    scan of torch's runs.  Between them the send and receive sizes are read with ONE host read
+    (all_to_all_single takes its split sizes from the host).  ctx: the Context whose stream the work
+    is queued on; None: a helper Context per device, kept by this module and bound, when it is made,
+    to torch's current stream of that device — a caller that works on another stream passes its own
+    ctx (made on that stream).  The results are complete when the call returns: the library's work and
+    torch's are joined on the host (a context made for the default stream has a stream of its own).
+    Links on the CPU (the gloo tests): plain torch, no context.
     """
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
@@ -114,6 +179,8 @@ def exchange_owned_links(links: torch.Tensor, counts: list, group=None):
     for c in counts:
         bounds.append(bounds[-1] + c)
     assert bounds[-1] < (1 << 31)
+    if dev.type == "cuda":
+        return _exchange_owned_links_device(links.contiguous(), counts, bounds, group, ctx)
     mine, first = counts[rank], bounds[rank]
 
     keys, _ = torch.sort(links)                               # by source: destinations become contiguous
