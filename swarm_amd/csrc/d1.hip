@@ -35,8 +35,10 @@ namespace {
 constexpr int kWaves = 4;                 // waves per workgroup
 constexpr int kThreads = kWaves * 64;
 constexpr int kQueueCap = 128;            // per-wave candidate queue (>= 64 + 63)
-constexpr uint32_t kEmpty = SWA_NO_AMPLICON;
 constexpr size_t kMaxZobristLds = SWA_MAX_ZOBRIST_LDS;
+
+#include "wave_ops.inc"     // wave_lds_sync
+#include "group_join.inc"   // kEmpty, kKeyEmpty, mix64, window32; the grouped join of the --fastidious pair route (d1_fast.inc)
 
 struct alignas(16) swa_task {   // one surviving first-level microvariant of a heavy amplicon
   uint64_t hash;
@@ -279,8 +281,6 @@ __device__ __forceinline__ uint64_t enumerate_variants(const uint64_t * sw, uint
   }
   return H;
 }
-
-#include "wave_ops.inc"   // wave_lds_sync
 
 // one probe of the candidate (hash h, edit code) drawn from the queue: walk the cluster,
 // apply the abundance rule, verify exactly (algod1.cc:558-603, variants.cc:118-165).
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(kThreads) void k_d1_flex(const FlexArgs a) {
   if (lane == 0 && nvar != 0ull) { atomicAdd(a.variant_counter, nvar); }
 }
 
-// ---- exclusive scans (the fastidious pass's offsets), the per-wave segments' totals and flat list ------
+// ---- exclusive scans (a workgroup's: d1_stream.inc too; the fastidious pass's offsets), the per-wave segments' totals and flat list ------
 constexpr int kScanItems = 8;
 constexpr int kScanBlock = 256;
 constexpr int kScanTile = kScanItems * kScanBlock;
@@ -619,14 +619,13 @@ __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t * 
   return wave_off + incl - v;
 }
 
-// (T = uint32_t: plain counts; T = unsigned long long: the slots of an anchor table, whose low halves are the group sizes)
-template <class T>
-__global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const T * __restrict__ counts, uint32_t n,
+// the fastidious groups' member offsets: exclusive scan of counts[0, n) into 64-bit offsets[0, n], three launches
+__global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const uint32_t * __restrict__ counts, uint32_t n,
                                                            uint64_t * __restrict__ tile_sums) {
   __shared__ uint64_t smem[4];
   const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
   uint64_t v = 0;
-  for (int i = 0; i < kScanItems; ++i) { if (base + i < n) { v += (uint32_t)counts[base + i]; } }
+  for (int i = 0; i < kScanItems; ++i) { if (base + i < n) { v += counts[base + i]; } }
   uint64_t total;
   (void)block_exclusive_scan(v, smem, total);
   if (threadIdx.x == 0) { tile_sums[blockIdx.x] = total; }
@@ -645,8 +644,7 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_sums(uint64_t * tile_sums, 
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(kScanBlock) void k_scan_apply(const T * __restrict__ counts, uint32_t n,
+__global__ __launch_bounds__(kScanBlock) void k_scan_apply(const uint32_t * __restrict__ counts, uint32_t n,
                                                            const uint64_t * __restrict__ tile_sums,
                                                            uint64_t * __restrict__ offsets) {
   __shared__ uint64_t smem[4];
@@ -654,7 +652,7 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_apply(const T * __restrict_
   uint32_t c[kScanItems];
   uint64_t v = 0;
   for (int i = 0; i < kScanItems; ++i) {
-    c[i] = (base + i < n) ? (uint32_t)counts[base + i] : 0u;
+    c[i] = (base + i < n) ? counts[base + i] : 0u;
     v += c[i];
   }
   uint64_t total;
@@ -2579,70 +2577,55 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
   uint64_t asize_max = 64, asize_ends = 64;
   while (asize_max < 6ull * n_light) { asize_max <<= 1; }    // load <= 0.5 with three memberships per light amplicon (middle windows)
   while (asize_ends < 2ull * n_light) { asize_ends <<= 1; }  // one membership (prefix / suffix groups): a smaller table to clear and scan
-  uint64_t asize = asize_max;
   const uint64_t member_cap = 3ull * n_light + n_heavy;
   const uint64_t item_cap64 = 3ull * n_light + (3ull * n_light + n_heavy) / 2 + 64;
   const uint32_t item_cap = item_cap64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)item_cap64;
-  SWA_TRY(swa_reserve(ctx, ctx->d_fkeys, asize * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fcnt, asize * 5 * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_foff, (asize + 1) * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fslot, uint64_t(n) * 4 * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fmembers, member_cap * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fitems, uint64_t(item_cap) * sizeof(swa_fitem)));
+  SWA_TRY(join_reserve(ctx, asize_max, n, 3u, member_cap, item_cap));
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_tmp, ((asize_max + kScanTile - 1) / kScanTile) * sizeof(uint64_t)));
+  // (the offsets by the three-launch scan above, not rocPRIM's as at d >= 2: DESIGN.md 3.5 has the measurement)
+  auto scan = [&](const JoinTable & t) -> int {
+    const uint32_t tiles = (uint32_t)((t.asize + kScanTile - 1) / kScanTile);
+    auto * sums = static_cast<uint64_t *>(ctx->d_scan_tmp.ptr);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, t.tot, (uint32_t)t.asize, sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, ctx->stream, sums, tiles);
+    hipLaunchKernelGGL(k_scan_apply, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, t.tot, (uint32_t)t.asize, sums, t.offsets);
+    return SWA_OK;
+  };
   if (ctx->fast_pair_cap == 0) {
     ctx->fast_pair_cap = 4ull * n_light + (1ull << 20);
     const char * env_cap = getenv("SWA_FAST_PAIR_CAP");       // test hook: start small, exercise the regrow path
     if (env_cap != nullptr && atoll(env_cap) > 0) { ctx->fast_pair_cap = (uint64_t)atoll(env_cap); }
   }
-  auto * keys = static_cast<unsigned long long *>(ctx->d_fkeys.ptr);
-  auto * cnt_l = static_cast<uint32_t *>(ctx->d_fcnt.ptr);
-  uint32_t * cnt_h = cnt_l + asize, * cur_l = cnt_h + asize, * cur_h = cur_l + asize, * tot = cur_h + asize;
-  auto * offsets = static_cast<uint64_t *>(ctx->d_foff.ptr);
-  auto * lslot = static_cast<uint32_t *>(ctx->d_fslot.ptr);
-  auto * hslot = lslot + 3ull * n;
-  auto * members = static_cast<uint32_t *>(ctx->d_fmembers.ptr);
-  auto * items = static_cast<swa_fitem *>(ctx->d_fitems.ptr);
-  auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);
-  // [8] key table overflow, [9 + type] the item counter of each group type (kept apart: the largest is checked below)
   uint64_t npairs = 0;
   const int pair_w = plan.pair_w;
   if (pair_w != 0) {
     SWA_TRY(launch_abundance_rank(ctx));
     SWA_TRY(ensure_lines(ctx));
   }
+  JoinTable jt = join_table(ctx, asize_max, n, 3u);
   swa_t0(ctx, 5);
   for (int attempt = 0; attempt < 6; ++attempt) {
     SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->fast_pair_cap * sizeof(uint64_t)));
     SWA_HIP(ctx, hipMemsetAsync(fc + 5, 0, sizeof(uint64_t), ctx->stream));
-    SWA_HIP(ctx, hipMemsetAsync(dflags + 8, 0, 4 * sizeof(uint32_t), ctx->stream));
+    SWA_HIP(ctx, hipMemsetAsync(jt.flags, 0, kJoinFlagWords * sizeof(uint32_t), ctx->stream));
     ctx->fast_totals[3] = (uint64_t)attempt + 1u;
     for (int type = 0; type < 3; ++type) {
-      uint32_t * item_counter = dflags + 9 + type;
-      asize = type == 2 ? asize_max : asize_ends;
-      cnt_h = cnt_l + asize; cur_l = cnt_h + asize; cur_h = cur_l + asize; tot = cur_h + asize;
-      const uint32_t tiles = (uint32_t)((asize + kScanTile - 1) / kScanTile);
+      // one membership a light amplicon in the prefix / suffix groups, three (the middle window at 39, 40, 41) in the middle ones
+      jt = join_table(ctx, type == 2 ? asize_max : asize_ends, n, type == 2 ? 3u : 1u);
+      uint32_t * item_counter = jt.flags + 2 + type;           // (one a type: the pair kernel of the type before still reads its own)
       FastGroupArgs g{};
       g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen;
       g.role = static_cast<const uint8_t *>(ctx->d_frole.ptr); g.n = n; g.max_len = plan.max_len;
-      g.keys = keys; g.cnt_l = cnt_l; g.cnt_h = cnt_h; g.amask = asize - 1; g.lslot = lslot; g.hslot = hslot; g.overflow = dflags + 8;
-      const dim3 gn(grid_for(ctx, n, 256, 8)), ga(grid_for(ctx, asize, 256, 8)), b(256);
-      hipLaunchKernelGGL(k_fg_clear, ga, b, 0, ctx->stream, keys, cnt_l, cnt_h, cur_l, cur_h, asize);
-      if (type == 0) { hipLaunchKernelGGL(k_fg_light<0>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<0>, gn, b, 0, ctx->stream, g); }
-      else if (type == 1) { hipLaunchKernelGGL(k_fg_light<1>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<1>, gn, b, 0, ctx->stream, g); }
-      else { hipLaunchKernelGGL(k_fg_light<2>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<2>, gn, b, 0, ctx->stream, g); }
-      hipLaunchKernelGGL(k_fg_totals, ga, b, 0, ctx->stream, cnt_l, cnt_h, asize, tot);
-      hipLaunchKernelGGL((k_scan_tiles<uint32_t>), dim3(tiles), dim3(kScanBlock), 0, ctx->stream, tot, (uint32_t)asize, static_cast<uint64_t *>(ctx->d_scan_tmp.ptr));
-      hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, ctx->stream, static_cast<uint64_t *>(ctx->d_scan_tmp.ptr), tiles);
-      hipLaunchKernelGGL((k_scan_apply<uint32_t>), dim3(tiles), dim3(kScanBlock), 0, ctx->stream, tot, (uint32_t)asize,
-                         static_cast<const uint64_t *>(ctx->d_scan_tmp.ptr), offsets);
-      if (type == 0) { hipLaunchKernelGGL(k_fg_scatter<0>, gn, b, 0, ctx->stream, g, offsets, cur_l, cur_h, members); }
-      else if (type == 1) { hipLaunchKernelGGL(k_fg_scatter<1>, gn, b, 0, ctx->stream, g, offsets, cur_l, cur_h, members); }
-      else { hipLaunchKernelGGL(k_fg_scatter<2>, gn, b, 0, ctx->stream, g, offsets, cur_l, cur_h, members); }
-      hipLaunchKernelGGL(k_fg_items, ga, b, 0, ctx->stream, cnt_l, cnt_h, offsets, asize, items, item_counter, item_cap);
+      g.keys = jt.keys; g.cnt_l = jt.cnt_a; g.cnt_h = jt.cnt_b; g.amask = jt.asize - 1; g.lslot = jt.aslot; g.hslot = jt.bslot; g.overflow = jt.flags;
+      // a group needs a light and a heavy amplicon: l h >= 1
+      SWA_TRY(join_run<FastTiles>(ctx, jt, 1u, item_counter, item_cap, [&](dim3 gn, dim3 b) {
+        if (type == 0) { hipLaunchKernelGGL(k_fg_light<0>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<0>, gn, b, 0, ctx->stream, g); }
+        else if (type == 1) { hipLaunchKernelGGL(k_fg_light<1>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<1>, gn, b, 0, ctx->stream, g); }
+        else { hipLaunchKernelGGL(k_fg_light<2>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<2>, gn, b, 0, ctx->stream, g); }
+      }, scan));
       FastPairArgs p{};
-      p.seqs = ctx->db.seqs; p.seq_off = ctx->db.seq_off; p.seqlen = ctx->db.seqlen; p.members = members;
-      p.items = items; p.item_count = item_counter; p.item_cap = item_cap;
+      p.seqs = ctx->db.seqs; p.seq_off = ctx->db.seq_off; p.seqlen = ctx->db.seqlen; p.members = jt.members;
+      p.items = jt.items; p.item_count = item_counter; p.item_cap = item_cap;
       p.pairs = static_cast<unsigned long long *>(ctx->d_fpairs.ptr); p.pair_counter = fc + 5; p.pair_cap = ctx->fast_pair_cap;
       const dim3 gp(ctx->num_cus * 8);
       p.lines = static_cast<const uint4 *>(ctx->d_stream[kSbLines].ptr);
@@ -2666,14 +2649,8 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
       SWA_HIP(ctx, hipGetLastError());
     }
     uint64_t got = 0;
-    uint32_t fl[4] = {0, 0, 0, 0};
-    SWA_HIP(ctx, hipMemcpyAsync(&got, fc + 5, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-    SWA_HIP(ctx, hipMemcpyAsync(fl, dflags + 8, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
-    SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (fl[0] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, "swa_d1_fastidious: group key table overflow"); }   // cannot happen: load <= 0.5
-    // (cannot happen either: a group of l light and h heavy amplicons makes at most l + h / 2 items,
-    // tests/test_fastidious_identity.py; the kernels drop what lies past the cap, so say it)
-    if (std::max(fl[1], std::max(fl[2], fl[3])) > item_cap) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_d1_fastidious: work item list overflow"); }
+    // (a group of l light and h heavy amplicons makes at most l + h / 2 items: tests/test_fastidious_identity.py)
+    SWA_TRY(join_status(ctx, jt, fc + 5, 1, &got, "swa_d1_fastidious: group key table overflow", "swa_d1_fastidious: work item list overflow"));
     if (got <= ctx->fast_pair_cap) { npairs = got; break; }
     if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_d1_fastidious: pair list keeps overflowing"); }
     ctx->fast_pair_cap = got + got / 8 + 1024;               // the count of a complete run: size for it (+ slack: none needed, it is exact)

@@ -60,7 +60,6 @@ __host__ __device__ constexpr inline uint32_t tiled_item_count(uint32_t members)
   return items;
 }
 constexpr uint32_t kPrefetchWords = 2;      // (anchor_applicable: sequences up to 64 * 2 * 32 - 64 nt)
-constexpr uint64_t kKeyEmpty = ~0ull;
 constexpr uint32_t kPairClasses = 5;        // size classes of the groups served by pairs in one wave: up to 4, 8, 16, 32, 64 members
 constexpr uint32_t kPairBigCap = 256;       // groups of 65..this many members: by pairs in one workgroup (k_d1_group_pairs)
 // Width classes (round 4; VERDICT r03 item 2).  The pair kernels keep a member's packed words in registers, W words each,
@@ -104,19 +103,6 @@ __device__ __forceinline__ void line_fetch(const uint4 * __restrict__ lines, uin
   for (int k = 0; k < W; ++k) { w64[k] = (uint64_t)d[2 + 2 * k] | ((uint64_t)d[3 + 2 * k] << 32); }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
-
-// 32 nucleotides from position pos on (may read the following word: the database ends in zero words)
-__device__ __forceinline__ uint64_t anchor_window(const uint64_t * seq, uint32_t pos) {
-  const uint32_t w = pos >> 5, sh = (pos & 31u) << 1;
-  uint64_t v = seq[w] >> sh;
-  if (sh != 0u) { v |= seq[w + 1] << (64u - sh); }
-  return v;
-}
-
 // key of the prefix-side (which = 0) or suffix-side (which = 1) anchor window.  Normally the first / last 32 * nwin
 // nucleotides (win_a = win_b = 0).  When those are (nearly) the same for everybody — conserved flanks — the windows
 // move inwards: [win_a, win_a + 32 nwin) from the start, [len - win_b - 32 nwin, len - win_b) from the end ("window
@@ -141,7 +127,7 @@ __device__ __forceinline__ uint32_t anchor_key29(const uint64_t * win, uint32_t 
 __device__ __forceinline__ uint64_t anchor_key(const uint64_t * seq, uint32_t len, int which, uint32_t win_a, uint32_t win_b, uint32_t nwin = 1u) {
   const uint32_t pos = which == 0 ? win_a : len - win_b - kAnchor * nwin;
   uint64_t win[4] = {0ull, 0ull, 0ull, 0ull};
-  for (uint32_t k = 0; k < nwin; ++k) { win[k] = anchor_window(seq, pos + kAnchor * k); }
+  for (uint32_t k = 0; k < nwin; ++k) { win[k] = window32(seq, pos + kAnchor * k); }
   return anchor_fold(win, nwin, which);
 }
 

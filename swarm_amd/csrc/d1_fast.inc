@@ -19,7 +19,8 @@
 //      their last 32, or — one edit in the first 32 nt, the other in the last 32 — the 32 nt at
 //      positions 40..71 up to a shift of one (both at least kFastMinLen long).  Light amplicons are
 //      grouped by those keys (the middle window at offsets 39, 40, 41), heavy amplicons join the
-//      groups that exist;
+//      groups that exist (k_fg_light, k_fg_heavy; the table, the member lists and the work items are
+//      the grouped join of group_join.inc);
 //   2. k_fast_pairs: all (light, heavy) pairs of a group, each lane one pair: exact "edit distance
 //      <= 2" by furthest-reaching diagonals with 32-nucleotide XOR + count-trailing-zeros extension
 //      (Landau-Vishkin, 9 extensions at most); a pair that shares its prefix is only taken in the
@@ -35,17 +36,7 @@
 constexpr uint32_t kFastMinLen = SWA_FAST_MIN_LEN;   // (112) both sequences at least this long => the pair route is complete
 constexpr uint32_t kFastMid = 40;         // middle window of a heavy amplicon: [40, 72); light: 39, 40, 41
 constexpr uint32_t kFastStride = 64;      // a group's tiles are dealt round-robin to at most this many items
-constexpr uint32_t kFastStage = 256;      // per-wave staging of found pairs (one global atomic per flush)
-
-struct swa_fitem { uint32_t begin, nl, nh, tile; };   // members[begin, begin+nl) light, then nh heavy; first tile
-
-// 32 nucleotides from position pos on (reads the following word too: the database ends in two zero words)
-__device__ __forceinline__ uint64_t window32(const uint64_t * seq, uint32_t pos) {
-  const uint32_t w = pos >> 5, sh = (pos & 31u) << 1;
-  uint64_t v = seq[w] >> sh;
-  if (sh != 0u) { v |= seq[w + 1] << (64u - sh); }
-  return v;
-}
+using FastTiles = JoinBlocks<64, 64, kFastStride>;   // the join's work items (group_join.inc): 64 lights x 64 heavies a tile
 
 // group key: TYPE 0 first 32 nt, 1 last 32 nt, 2 the 32 nt at `offset`
 template <int TYPE>
@@ -70,13 +61,6 @@ struct FastGroupArgs {
   uint32_t * overflow;
 };
 
-__global__ __launch_bounds__(256) void k_fg_clear(unsigned long long * keys, uint32_t * cnt_l, uint32_t * cnt_h, uint32_t * cur_l,
-                                                  uint32_t * cur_h, uint64_t asize) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < asize; i += (uint64_t)gridDim.x * blockDim.x) {
-    keys[i] = kKeyEmpty; cnt_l[i] = 0u; cnt_h[i] = 0u; cur_l[i] = 0u; cur_h[i] = 0u;
-  }
-}
-
 // light amplicons create the groups
 template <int TYPE>
 __global__ __launch_bounds__(256) void k_fg_light(const FastGroupArgs a) {
@@ -95,16 +79,9 @@ __global__ __launch_bounds__(256) void k_fg_light(const FastGroupArgs a) {
         bool repeat = false;                                 // a window that reads the same at two offsets: one membership
         for (uint32_t q = 0; q < j; ++q) { repeat = repeat || key[q] == key[j]; }
         if (repeat) { continue; }
-        uint64_t idx = mix64(key[j]) & a.amask;
-        bool placed = false;
-        for (uint64_t probes = 0; probes <= a.amask; ++probes) {
-          const unsigned long long old = atomicCAS(&a.keys[idx], kKeyEmpty, (unsigned long long)key[j]);
-          if (old == kKeyEmpty || old == key[j]) { placed = true; break; }
-          idx = (idx + 1) & a.amask;
-        }
-        if (!placed) { *a.overflow = 1u; continue; }
-        atomicAdd(&a.cnt_l[idx], 1u);
-        slots[j] = (uint32_t)idx;
+        slots[j] = join_claim(a.keys, a.amask, key[j]);
+        if (slots[j] != kEmpty) { atomicAdd(&a.cnt_l[slots[j]], 1u); }
+        else { *a.overflow = 1u; }
       }
     }
 #pragma unroll
@@ -119,72 +96,10 @@ __global__ __launch_bounds__(256) void k_fg_heavy(const FastGroupArgs a) {
     uint32_t slot = kEmpty;
     const uint32_t len = a.seqlen[i];
     if (a.role[i] == 1u && len >= kFastMinLen && len <= a.max_len) {
-      const uint64_t key = fast_key<TYPE>(a.seqs + a.seq_off[i], len, kFastMid);
-      uint64_t idx = mix64(key) & a.amask;
-      for (uint64_t probes = 0; probes <= a.amask; ++probes) {
-        const unsigned long long have = a.keys[idx];
-        if (have == key) { atomicAdd(&a.cnt_h[idx], 1u); slot = (uint32_t)idx; break; }
-        if (have == kKeyEmpty) { break; }
-        idx = (idx + 1) & a.amask;
-      }
+      slot = join_find(a.keys, a.amask, fast_key<TYPE>(a.seqs + a.seq_off[i], len, kFastMid));
+      if (slot != kEmpty) { atomicAdd(&a.cnt_h[slot], 1u); }
     }
     a.hslot[i] = slot;
-  }
-}
-
-// members of a group that has both kinds; 0 for the others (they get no room in the member list)
-__global__ __launch_bounds__(256) void k_fg_totals(const uint32_t * __restrict__ cnt_l, const uint32_t * __restrict__ cnt_h,
-                                                   uint64_t asize, uint32_t * __restrict__ tot) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < asize; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t l = cnt_l[i], h = cnt_h[i];
-    tot[i] = (l != 0u && h != 0u) ? l + h : 0u;
-  }
-}
-
-template <int TYPE>
-__global__ __launch_bounds__(256) void k_fg_scatter(const FastGroupArgs a, const uint64_t * __restrict__ offsets, uint32_t * cur_l,
-                                                    uint32_t * cur_h, uint32_t * __restrict__ members) {
-  constexpr uint32_t NK = TYPE == 2 ? 3u : 1u;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
-#pragma unroll
-    for (uint32_t j = 0; j < NK; ++j) {
-      const uint32_t s = a.lslot[(uint64_t)i * NK + j];
-      if (s != kEmpty && a.cnt_h[s] != 0u) { members[offsets[s] + atomicAdd(&cur_l[s], 1u)] = i; }
-    }
-    const uint32_t s = a.hslot[i];
-    if (s != kEmpty) { members[offsets[s] + a.cnt_l[s] + atomicAdd(&cur_h[s], 1u)] = i; }
-  }
-}
-
-// one thread per key slot: the group's work items (its tiles dealt round-robin to <= kFastStride items)
-__global__ __launch_bounds__(256) void k_fg_items(const uint32_t * __restrict__ cnt_l, const uint32_t * __restrict__ cnt_h,
-                                                  const uint64_t * __restrict__ offsets, uint64_t asize, swa_fitem * items,
-                                                  uint32_t * counter, uint32_t cap) {
-  __shared__ uint32_t n_items, base;
-  if (threadIdx.x == 0) { n_items = 0u; }
-  __syncthreads();
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t start = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  auto items_of = [&](uint64_t s) -> uint32_t {
-    const uint64_t l = cnt_l[s], h = cnt_h[s];
-    if (l == 0 || h == 0) { return 0u; }
-    const uint64_t tiles = ((l + 63) / 64) * ((h + 63) / 64);        // 64 lights x 64 heavies per tile
-    return (uint32_t)(tiles < kFastStride ? tiles : kFastStride);
-  };
-  for (uint64_t s = start; s < asize; s += stride) {
-    const uint32_t k = items_of(s);
-    if (k != 0u) { atomicAdd(&n_items, k); }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) { base = n_items != 0u ? atomicAdd(counter, n_items) : 0u; n_items = 0u; }
-  __syncthreads();
-  for (uint64_t s = start; s < asize; s += stride) {
-    const uint32_t k = items_of(s);
-    if (k == 0u) { continue; }
-    const uint32_t at = base + atomicAdd(&n_items, k);
-    swa_fitem it;
-    it.begin = (uint32_t)offsets[s]; it.nl = cnt_l[s]; it.nh = cnt_h[s];
-    for (uint32_t t = 0; t < k; ++t) { it.tile = t; if (at + t < cap) { items[at + t] = it; } }
   }
 }
 
@@ -230,7 +145,7 @@ struct FastPairArgs {
   const uint64_t * seq_off;
   const uint32_t * seqlen;
   const uint32_t * members;
-  const swa_fitem * items;
+  const join_item * items;
   const uint32_t * item_count;
   uint32_t item_cap;
   unsigned long long * pairs;          // (heavy << 32) | light
@@ -243,36 +158,25 @@ struct FastPairArgs {
 // all (light, heavy) pairs of a group, one pair per lane and turn
 template <int TYPE>
 __global__ __launch_bounds__(kThreads) void k_fast_pairs(const FastPairArgs a) {
-  __shared__ unsigned long long stage_all[kWaves][kFastStage];
+  __shared__ unsigned long long stage_rows[kWaves][kPairStage];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned long long * stage = stage_all[wave];
-  uint32_t nstage = 0;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(a.pair_counter, (unsigned long long)nstage); }
-    base = swa_shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
-    nstage = 0;
-    wave_lds_sync();
-  };
+  PairStage stage(stage_rows, a.pairs, a.pair_counter, a.pair_cap);
   const uint32_t nitems = min(*a.item_count, a.item_cap);
   const uint32_t nwaves = gridDim.x * kWaves;
   for (uint32_t it = blockIdx.x * kWaves + wave; it < nitems; it += nwaves) {
-    const swa_fitem item = a.items[it];
-    const uint64_t tiles_h = ((uint64_t)item.nh + 63) / 64;
-    const uint64_t ntiles = (((uint64_t)item.nl + 63) / 64) * tiles_h;
+    const join_item item = a.items[it];
+    const uint64_t tiles_h = ((uint64_t)item.nb + 63) / 64;
+    const uint64_t ntiles = (((uint64_t)item.na + 63) / 64) * tiles_h;
     const uint32_t * lights = a.members + item.begin;
-    const uint32_t * heavies = lights + item.nl;
+    const uint32_t * heavies = lights + item.na;
     for (uint64_t tile = item.tile; tile < ntiles; tile += kFastStride) {
       const uint32_t l0 = (uint32_t)(tile / tiles_h) * 64u, h0 = (uint32_t)(tile % tiles_h) * 64u;
       const uint32_t ih = h0 + (uint32_t)lane;
-      const bool have_h = ih < item.nh;
+      const bool have_h = ih < item.nb;
       const uint32_t h = have_h ? heavies[ih] : 0u;
       const int lh = have_h ? (int)a.seqlen[h] : 0;
       const uint64_t * sh = a.seqs + (have_h ? a.seq_off[h] : 0ull);
-      for (uint32_t il = l0; il < min(l0 + 64u, item.nl); ++il) {
+      for (uint32_t il = l0; il < min(l0 + 64u, item.na); ++il) {
         bool take = false;
         const uint32_t x = lights[il];
         if (have_h) {
@@ -293,16 +197,11 @@ __global__ __launch_bounds__(kThreads) void k_fast_pairs(const FastPairArgs a) {
             take = mine && within_two_edits(sh, lh, sx, lx);
           }
         }
-        const uint64_t m = __ballot(take);
-        if (m != 0ull) {
-          if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)h << 32) | x; }
-          nstage += (uint32_t)__popcll(m);
-          if (nstage > kFastStage - 64u) { flush(); }
-        }
+        stage.push(take, ((unsigned long long)h << 32) | x);
       }
     }
   }
-  if (nstage != 0u) { flush(); }
+  stage.finish();
 }
 
 // ---- the same on amplicon lines (round 3) -------------------------------------------------------------------------------
@@ -404,43 +303,24 @@ __device__ __forceinline__ bool fast_pair_test(const uint64_t (&Hw)[W], int lh, 
 
 template <int TYPE, int W>
 __global__ __launch_bounds__(kThreads) void k_fast_pairs_lines(const FastPairArgs a) {
-  __shared__ unsigned long long stage_all[kWaves][kFastStage];
+  __shared__ unsigned long long stage_rows[kWaves][kPairStage];
   __shared__ uint32_t psum_all[kWaves][64], begin_all[kWaves][64], nl_all[kWaves][64], nh_all[kWaves][64], tile_all[kWaves][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned long long * stage = stage_all[wave];
   uint32_t * psum = psum_all[wave], * ibegin = begin_all[wave], * inl = nl_all[wave], * inh = nh_all[wave], * itile = tile_all[wave];
-  uint32_t nstage = 0;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(a.pair_counter, (unsigned long long)nstage); }
-    base = swa_shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
-    nstage = 0;
-    wave_lds_sync();
-  };
-  auto keep = [&](bool take, uint32_t h, uint32_t x) {
-    const uint64_t m = __ballot(take);
-    if (m != 0ull) {
-      if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)h << 32) | x; }
-      nstage += (uint32_t)__popcll(m);
-      if (nstage > kFastStage - 64u) { flush(); }
-    }
-  };
+  PairStage stage(stage_rows, a.pairs, a.pair_counter, a.pair_cap);
   const uint32_t nitems = min(*a.item_count, a.item_cap);
   const uint32_t nwaves = gridDim.x * kWaves;
   for (uint32_t chunk = (blockIdx.x * kWaves + wave) * 64u; chunk < nitems; chunk += nwaves * 64u) {
     const uint32_t idx = chunk + (uint32_t)lane;
-    swa_fitem item{0u, 0u, 0u, 0u};
+    join_item item{0u, 0u, 0u, 0u};
     if (idx < nitems) { item = a.items[idx]; }
-    const bool small = idx < nitems && item.nl <= 64u && item.nh <= 64u;      // one tile: all its pairs dealt to lanes
+    const bool small = idx < nitems && item.na <= 64u && item.nb <= 64u;      // one tile: all its pairs dealt to lanes
     const bool large = idx < nitems && !small;
-    uint32_t incl = small ? item.nl * item.nh : 0u;
+    uint32_t incl = small ? item.na * item.nb : 0u;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, (unsigned)d, 64); if (lane >= d) { incl += up; } }
     wave_lds_sync();                                            // (the previous chunk's tables are no longer read)
-    psum[lane] = incl; ibegin[lane] = item.begin; inl[lane] = item.nl; inh[lane] = item.nh; itile[lane] = item.tile;
+    psum[lane] = incl; ibegin[lane] = item.begin; inl[lane] = item.na; inh[lane] = item.nb; itile[lane] = item.tile;
     wave_lds_sync();
     const uint32_t total = psum[63];
     for (uint32_t r = 0; r < total; r += 64u) {
@@ -464,7 +344,7 @@ __global__ __launch_bounds__(kThreads) void k_fast_pairs_lines(const FastPairArg
         line_fetch<W>(a.lines, a.line_quads, h, Hw, lh, rank);
         take = fast_pair_test<TYPE, W>(Hw, (int)lh, Xw, (int)lx);
       }
-      keep(take, h, x);
+      stage.push(take, ((unsigned long long)h << 32) | x);
     }
     // groups of more than one tile: lane = heavy amplicon of the tile, the light ones in turn (as k_fast_pairs)
     uint64_t todo = __ballot(large);
@@ -494,12 +374,12 @@ __global__ __launch_bounds__(kThreads) void k_fast_pairs_lines(const FastPairArg
           uint32_t lx;
           line_fetch<W>(a.lines, a.line_quads, x, Xw, lx, rank);
           const bool take = have_h && fast_pair_test<TYPE, W>(Hw, (int)lh, Xw, (int)lx);
-          keep(take, h, x);
+          stage.push(take, ((unsigned long long)h << 32) | x);
         }
       }
     }
   }
-  if (nstage != 0u) { flush(); }
+  stage.finish();
 }
 
 // ---- |V1(h) ∩ V1(x)| of every pair -------------------------------------------------------------

@@ -16,7 +16,7 @@
 // offsets 0, W, 2W, ...) at least one is untouched, and it reappears in the target shifted by the net
 // indels before it, -d .. +d.  Every amplicon is filed as a TARGET under its windows at all those
 // shifts and looks itself up as a QUERY under its unshifted windows ("groups", one window at a
-// time); inside a group every (query < target) pair goes through: length difference, "not already
+// time: the grouped join of group_join.inc, targets creating and queries joining); inside a group every (query < target) pair goes through: length difference, "not already
 // found through an earlier window", the q-gram bound (src/qgram.cc:68-96, B3) — survivors are
 // aligned by the B4 kernels (align.hip) in the direction(s) the abundance rule allows, and the
 // accepted (query, target, diff) triples are sorted into a CSR (rocPRIM radix sort).
@@ -46,27 +46,18 @@ int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, 
 
 namespace {
 
-constexpr uint32_t kEmpty = SWA_NO_AMPLICON;
-constexpr uint64_t kKeyEmpty = ~0ull;
+#include "wave_ops.inc"     // wave_lds_sync
+#include "group_join.inc"   // the window groups are a grouped join: targets create, queries join
+
 constexpr uint32_t kTile = 4096;          // (query, target) pairs per turn of a wave
 constexpr uint32_t kStride = 64;          // a group's tiles are dealt round-robin to at most this many items
-constexpr uint32_t kStage = 256;          // per-wave staging of found pairs
 constexpr int kMaxD = 16;                 // the graph route serves d <= kMaxD
 constexpr int kMaxShifts = 2 * kMaxD + 1; // 2 d + 1 for d <= 16
 constexpr int kSmallShifts = 17;          // ... and for d <= 8: k_dg_targets<kSmallShifts> is the kernel those d have always run
 
-struct dg_item { uint32_t begin, nt, nq, tile; };   // members[begin, begin+nt) targets, then nq queries
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
-
-// `wlen` (<= 32) nucleotides from position pos on (may read the following word: the database ends in zero words)
+// `wlen` (<= 32) nucleotides from position pos on: window32, masked
 __device__ __forceinline__ uint64_t window(const uint64_t * seq, uint32_t pos, uint32_t wlen) {
-  const uint32_t w = pos >> 5, sh = (pos & 31u) << 1;
-  uint64_t v = seq[w] >> sh;
-  if (sh != 0u) { v |= seq[w + 1] << (64u - sh); }
+  const uint64_t v = window32(seq, pos);
   return wlen >= 32u ? v : (v & ((1ull << (2u * wlen)) - 1ull));
 }
 
@@ -89,13 +80,6 @@ struct GroupArgs {
   uint32_t owner_rank, owner_world;   // world > 1: only the window keys this rank owns make groups here (swa_dn_set_ownership)
 };
 
-__global__ __launch_bounds__(256) void k_dg_clear(unsigned long long * keys, uint32_t * c0, uint32_t * c1, uint32_t * c2, uint32_t * c3,
-                                                  uint64_t asize) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < asize; i += (uint64_t)gridDim.x * blockDim.x) {
-    keys[i] = kKeyEmpty; c0[i] = 0u; c1[i] = 0u; c2[i] = 0u; c3[i] = 0u;
-  }
-}
-
 // every amplicon (that is not short) is a target under its window k at the shifts -d .. +d (MAXS >= 2 d + 1)
 template <int MAXS>
 __global__ __launch_bounds__(256) void k_dg_targets(const GroupArgs a) {
@@ -117,14 +101,8 @@ __global__ __launch_bounds__(256) void k_dg_targets(const GroupArgs a) {
         // (ownership by bits of the mixed key that the table index — its low bits — does not use alone)
         const bool owned = a.owner_world == 1u || (uint32_t)((((mix64(key) >> 40) & 0xFFFFFFull) * a.owner_world) >> 24) == a.owner_rank;
         if (!repeat && owned) {
-          uint64_t idx = mix64(key) & a.amask;
-          bool placed = false;
-          for (uint64_t probes = 0; probes <= a.amask; ++probes) {
-            const unsigned long long old = atomicCAS(&a.keys[idx], kKeyEmpty, (unsigned long long)key);
-            if (old == kKeyEmpty || old == key) { placed = true; break; }
-            idx = (idx + 1) & a.amask;
-          }
-          if (placed) { atomicAdd(&a.cnt_t[idx], 1u); slot = (uint32_t)idx; }
+          slot = join_claim(a.keys, a.amask, key);
+          if (slot != kEmpty) { atomicAdd(&a.cnt_t[slot], 1u); }
           else { *a.overflow = 1u; }
         }
       }
@@ -138,89 +116,27 @@ __global__ __launch_bounds__(256) void k_dg_queries(const GroupArgs a) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
     if (a.seqlen[i] < a.short_below) { a.qslot[i] = kEmpty; continue; }      // (a short sequence has no window k to look up)
     const uint64_t key = window_key(window(a.seqs + a.seq_off[i], a.k * a.wlen, a.wlen), a.k);
-    uint64_t idx = mix64(key) & a.amask;
-    uint32_t slot = kEmpty;
-    for (uint64_t probes = 0; probes <= a.amask; ++probes) {
-      const unsigned long long have = a.keys[idx];
-      if (have == key) { atomicAdd(&a.cnt_q[idx], 1u); slot = (uint32_t)idx; break; }
-      if (have == kKeyEmpty) { break; }
-      idx = (idx + 1) & a.amask;
-    }
+    const uint32_t slot = join_find(a.keys, a.amask, key);
+    if (slot != kEmpty) { atomicAdd(&a.cnt_q[slot], 1u); }
     a.qslot[i] = slot;
   }
 }
 
-// room in the member list only for groups with a pair of DIFFERENT amplicons (an amplicon alone is its own target)
-__global__ __launch_bounds__(256) void k_dg_totals(const uint32_t * __restrict__ cnt_t, const uint32_t * __restrict__ cnt_q,
-                                                   uint64_t asize, uint32_t * __restrict__ tot) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < asize; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t t = cnt_t[i], q = cnt_q[i];
-    tot[i] = t * q >= 2 ? (uint32_t)(t + q) : 0u;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_dg_scatter(const GroupArgs a, const uint32_t * __restrict__ tot,
-                                                    const uint64_t * __restrict__ offsets, uint32_t * cur_t, uint32_t * cur_q,
-                                                    uint32_t * __restrict__ members) {
-  const uint32_t ns = 2u * a.d + 1u;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
-    for (uint32_t j = 0; j < ns; ++j) {
-      const uint32_t s = a.tslot[(uint64_t)i * ns + j];
-      if (s != kEmpty && tot[s] != 0u) { members[offsets[s] + atomicAdd(&cur_t[s], 1u)] = i; }
-    }
-    const uint32_t s = a.qslot[i];
-    if (s != kEmpty && tot[s] != 0u) { members[offsets[s] + a.cnt_t[s] + atomicAdd(&cur_q[s], 1u)] = i; }
-  }
-}
-
-// BLOCKED = false: the tiles of k_dg_pairs (4096 pairs, at most kStride items a group); true: the blocks of k_dg_pairs_lds
+// The work items of a group (k_join_items): DnTiles, the tiles of k_dg_pairs (4096 pairs, at most kStride items a group), or
+// DnBlocks, the blocks of k_dg_pairs_lds
 // (kBlockT targets x kBlockQ queries each, block b = target block + target blocks x query chunk), dealt round-robin to at most
 // kBlockStride items a group (item.tile = its first block).  Either way a group's items are bounded, and so is their sum:
 // min(S, x y) <= 1 + sqrt(S) (x - 1 + y - 1) for x, y >= 1, so a group of t targets and q >= 1 queries makes at most
 // 1 + t / 4 + q / 16 blocked items (S = 256, x = ceil(t / 64), y = ceil(q / 256)) and at most 1 + t / 8 + q / 8 tiles
 // (S = 64, 4096-pair tiles); over all groups t sums to <= n (2 d + 1), q to <= n, and the groups with items number <= n
 // (every one holds a query): the host's item_cap = n + n (2 d + 2) / 2 + 64 holds them (tests/test_pair_identity.py).
-// Items past the cap are not dropped quietly: *overflow is raised and the search fails.
+// Items past the cap are not dropped quietly: the join raises its flag and the search fails.
 constexpr uint32_t kBlockT = 64;          // targets of a block: one per lane
 constexpr uint32_t kBlockQ = 256;         // queries of a block, staged kStageQ at a time
 constexpr uint32_t kStageQ = 16;
 constexpr uint32_t kBlockStride = 256;    // a group's blocks are dealt round-robin to at most this many items
-template <bool BLOCKED>
-__global__ __launch_bounds__(256) void k_dg_items(const uint32_t * __restrict__ cnt_t, const uint32_t * __restrict__ cnt_q,
-                                                  const uint32_t * __restrict__ tot, const uint64_t * __restrict__ offsets,
-                                                  uint64_t asize, dg_item * items, uint32_t * counter, uint32_t cap,
-                                                  uint32_t * overflow) {
-  __shared__ uint32_t n_items, base;
-  if (threadIdx.x == 0) { n_items = 0u; }
-  __syncthreads();
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t start = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  auto items_of = [&](uint64_t s) -> uint32_t {
-    if (tot[s] == 0u) { return 0u; }
-    if (BLOCKED) {
-      const uint64_t blocks = (uint64_t)((cnt_t[s] + kBlockT - 1u) / kBlockT) * ((cnt_q[s] + kBlockQ - 1u) / kBlockQ);
-      return (uint32_t)(blocks < kBlockStride ? blocks : kBlockStride);
-    }
-    const uint64_t tiles = ((uint64_t)cnt_t[s] * cnt_q[s] + kTile - 1) / kTile;
-    return (uint32_t)(tiles < kStride ? tiles : kStride);
-  };
-  for (uint64_t s = start; s < asize; s += stride) {
-    const uint32_t k = items_of(s);
-    if (k != 0u) { atomicAdd(&n_items, k); }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) { base = n_items != 0u ? atomicAdd(counter, n_items) : 0u; n_items = 0u; }
-  __syncthreads();
-  for (uint64_t s = start; s < asize; s += stride) {
-    const uint32_t k = items_of(s);
-    if (k == 0u) { continue; }
-    const uint32_t at = base + atomicAdd(&n_items, k);
-    dg_item it;
-    it.begin = (uint32_t)offsets[s]; it.nt = cnt_t[s]; it.nq = cnt_q[s];
-    if ((uint64_t)at + k > cap) { *overflow = 1u; }
-    for (uint32_t t = 0; t < k; ++t) { it.tile = t; if ((uint64_t)at + t < cap) { items[at + t] = it; } }
-  }
-}
+using DnBlocks = JoinBlocks<kBlockT, kBlockQ, kBlockStride>;
+using DnTiles = JoinPairTiles<kTile, kStride>;
 
 struct PairArgs {
   const uint64_t * seqs;
@@ -228,7 +144,7 @@ struct PairArgs {
   const uint32_t * seqlen;
   const ulonglong2 * sigs;       // q-gram signatures, 8 x 16 bytes per amplicon
   const uint32_t * members;
-  const dg_item * items;
+  const join_item * items;
   const uint32_t * item_count;
   uint32_t item_cap;
   uint32_t d, k, wlen;
@@ -237,40 +153,21 @@ struct PairArgs {
   uint64_t pair_cap;
 };
 
-#include "wave_ops.inc"   // wave_lds_sync
-
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
-  const int lo = __shfl((int)(uint32_t)v, src, 64);
-  const int hi = __shfl((int)(uint32_t)(v >> 32), src, 64);
-  return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
-
 // all (query, target) pairs of a group with query < target, one pair per lane and turn
 __global__ __launch_bounds__(256) void k_dg_pairs(const PairArgs a) {
-  __shared__ unsigned long long stage_all[4][kStage];
+  __shared__ unsigned long long stage_rows[4][kPairStage];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned long long * stage = stage_all[wave];
-  uint32_t nstage = 0;
+  PairStage stage(stage_rows, a.pairs, &a.counters[0], a.pair_cap);
   unsigned long long compared = 0;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(&a.counters[0], (unsigned long long)nstage); }
-    base = shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
-    nstage = 0;
-    wave_lds_sync();
-  };
   const uint32_t nitems = min(*a.item_count, a.item_cap);
   const uint32_t nwaves = gridDim.x * 4u;
   const int d = (int)a.d;
   for (uint32_t it = blockIdx.x * 4u + wave; it < nitems; it += nwaves) {
-    const dg_item item = a.items[it];
-    const uint64_t npairs = (uint64_t)item.nt * item.nq;
+    const join_item item = a.items[it];
+    const uint64_t npairs = (uint64_t)item.na * item.nb;
     const uint64_t ntiles = (npairs + kTile - 1) / kTile;
     const uint32_t * targets = a.members + item.begin;
-    const uint32_t * queries = targets + item.nt;
+    const uint32_t * queries = targets + item.na;
     for (uint64_t tile = item.tile; tile < ntiles; tile += kStride) {
       const uint64_t q0 = tile * kTile;
       const uint64_t q1 = min(q0 + (uint64_t)kTile, npairs);
@@ -279,8 +176,8 @@ __global__ __launch_bounds__(256) void k_dg_pairs(const PairArgs a) {
         bool take = false;
         uint32_t q = 0, t = 0;
         if (p < q1) {
-          const uint32_t iq = (uint32_t)(p / item.nt);
-          const uint32_t itg = (uint32_t)(p - (uint64_t)iq * item.nt);
+          const uint32_t iq = (uint32_t)(p / item.na);
+          const uint32_t itg = (uint32_t)(p - (uint64_t)iq * item.na);
           q = queries[iq];
           t = targets[itg];
           if (q < t) {
@@ -323,17 +220,12 @@ __global__ __launch_bounds__(256) void k_dg_pairs(const PairArgs a) {
             }
           }
         }
-        const uint64_t m = __ballot(take);
-        if (m != 0ull) {
-          if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)q << 32) | t; }
-          nstage += (uint32_t)__popcll(m);
-          if (nstage > kStage - 64u) { flush(); }
-        }
+        stage.push(take, ((unsigned long long)q << 32) | t);
       }
     }
   }
-  if (nstage != 0u) { flush(); }
-  for (int o = 32; o > 0; o >>= 1) { compared += shfl_u64(compared, lane ^ o); }
+  stage.finish();
+  for (int o = 32; o > 0; o >>= 1) { compared += swa_shfl_u64(compared, lane ^ o); }
   if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
 }
 
@@ -349,37 +241,26 @@ template <int D>
 __global__ __launch_bounds__(256) void k_dg_pairs_lds(const PairArgs a) {
   constexpr int NS = 2 * D + 1;
   struct QRec { uint64_t sig[16]; uint64_t win[D + 1]; uint32_t id, len; };
-  __shared__ unsigned long long stage_all[4][kStage];
+  __shared__ unsigned long long stage_rows[4][kPairStage];
   __shared__ QRec qrec_all[4][kStageQ];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned long long * stage = stage_all[wave];
   QRec * qrec = qrec_all[wave];
-  uint32_t nstage = 0;
+  PairStage stage(stage_rows, a.pairs, &a.counters[0], a.pair_cap);
   unsigned long long compared = 0;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(&a.counters[0], (unsigned long long)nstage); }
-    base = shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
-    nstage = 0;
-    wave_lds_sync();
-  };
   const uint32_t nitems = min(*a.item_count, a.item_cap);
   const uint32_t nwaves = gridDim.x * 4u;
   const uint32_t K = a.k;                                     // this launch's window (<= D), wave-uniform
   for (uint32_t it = blockIdx.x * 4u + wave; it < nitems; it += nwaves) {
-    const dg_item item = a.items[it];
+    const join_item item = a.items[it];
     const uint32_t * targets = a.members + item.begin;
-    const uint32_t * queries = targets + item.nt;
-    const uint32_t ntb = (item.nt + kBlockT - 1u) / kBlockT;
-    const uint64_t nblocks = (uint64_t)ntb * ((item.nq + kBlockQ - 1u) / kBlockQ);
+    const uint32_t * queries = targets + item.na;
+    const uint32_t ntb = (item.na + kBlockT - 1u) / kBlockT;
+    const uint64_t nblocks = (uint64_t)ntb * ((item.nb + kBlockQ - 1u) / kBlockQ);
     for (uint64_t blk = item.tile; blk < nblocks; blk += kBlockStride) {
       const uint32_t tb = (uint32_t)(blk % ntb), qc = (uint32_t)(blk / ntb);
       // ---- my target: windows at every shift of the windows 0 .. K, validity, signature
       const uint32_t ti = tb * kBlockT + (uint32_t)lane;
-      const bool have_t = ti < item.nt;
+      const bool have_t = ti < item.na;
       const uint32_t t = have_t ? targets[ti] : 0u;
       const int lt = have_t ? (int)a.seqlen[t] : 0;
       const uint64_t * st = a.seqs + a.seq_off[t];
@@ -401,7 +282,7 @@ __global__ __launch_bounds__(256) void k_dg_pairs_lds(const PairArgs a) {
 #pragma unroll
         for (int w = 0; w < 8; ++w) { const ulonglong2 y = have_t ? gt[w] : make_ulonglong2(0ull, 0ull); tsig[2 * w] = y.x; tsig[2 * w + 1] = y.y; }
       }
-      const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nq, q_begin + kBlockQ);
+      const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nb, q_begin + kBlockQ);
       for (uint32_t qs = q_begin; qs < q_end; qs += kStageQ) {
         const uint32_t nq_here = min(kStageQ, q_end - qs);
         wave_lds_sync();
@@ -446,18 +327,13 @@ __global__ __launch_bounds__(256) void k_dg_pairs_lds(const PairArgs a) {
             if (take) { ++compared; }
             take = take && (pop + 9u) / 10u <= (uint32_t)D;
           }
-          const uint64_t m = __ballot(take);
-          if (m != 0ull) {
-            if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)q << 32) | t; }
-            nstage += (uint32_t)__popcll(m);
-            if (nstage > kStage - 64u) { flush(); }
-          }
+          stage.push(take, ((unsigned long long)q << 32) | t);
         }
       }
     }
   }
-  if (nstage != 0u) { flush(); }
-  for (int o = 32; o > 0; o >>= 1) { compared += shfl_u64(compared, lane ^ o); }
+  stage.finish();
+  for (int o = 32; o > 0; o >>= 1) { compared += swa_shfl_u64(compared, lane ^ o); }
   if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
 }
 
@@ -532,38 +408,27 @@ template <int WLEN>
 __global__ __launch_bounds__(256) void k_dg_pairs_deep(const PairArgs a) {
   constexpr int NW = DeepWords<WLEN>::value;
   struct QRec { uint64_t sig[16]; uint64_t win[kDeepWindows]; uint32_t id, len; };
-  __shared__ unsigned long long stage_all[4][kStage];
+  __shared__ unsigned long long stage_rows[4][kPairStage];
   __shared__ QRec qrec_all[4][kStageQ];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned long long * stage = stage_all[wave];
   QRec * qrec = qrec_all[wave];
-  uint32_t nstage = 0;
+  PairStage stage(stage_rows, a.pairs, &a.counters[0], a.pair_cap);
   unsigned long long compared = 0;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(&a.counters[0], (unsigned long long)nstage); }
-    base = shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
-    nstage = 0;
-    wave_lds_sync();
-  };
   const uint32_t nitems = min(*a.item_count, a.item_cap);
   const uint32_t nwaves = gridDim.x * 4u;
   const uint32_t K = a.k;                                     // this launch's window (<= d), wave-uniform
   const int d = (int)a.d;
   for (uint32_t it = blockIdx.x * 4u + wave; it < nitems; it += nwaves) {
-    const dg_item item = a.items[it];
+    const join_item item = a.items[it];
     const uint32_t * targets = a.members + item.begin;
-    const uint32_t * queries = targets + item.nt;
-    const uint32_t ntb = (item.nt + kBlockT - 1u) / kBlockT;
-    const uint64_t nblocks = (uint64_t)ntb * ((item.nq + kBlockQ - 1u) / kBlockQ);
+    const uint32_t * queries = targets + item.na;
+    const uint32_t ntb = (item.na + kBlockT - 1u) / kBlockT;
+    const uint64_t nblocks = (uint64_t)ntb * ((item.nb + kBlockQ - 1u) / kBlockQ);
     for (uint64_t blk = item.tile; blk < nblocks; blk += kBlockStride) {
       const uint32_t tb = (uint32_t)(blk % ntb), qc = (uint32_t)(blk / ntb);
       // ---- my target: its first words (only its own: what lies behind them is not read), signature
       const uint32_t ti = tb * kBlockT + (uint32_t)lane;
-      const bool have_t = ti < item.nt;
+      const bool have_t = ti < item.na;
       const uint32_t t = have_t ? targets[ti] : 0u;
       const int lt = have_t ? (int)a.seqlen[t] : 0;
       const uint64_t * st = a.seqs + a.seq_off[t];
@@ -576,7 +441,7 @@ __global__ __launch_bounds__(256) void k_dg_pairs_deep(const PairArgs a) {
 #pragma unroll
         for (int w = 0; w < 8; ++w) { const ulonglong2 y = have_t ? gt[w] : make_ulonglong2(0ull, 0ull); tsig[2 * w] = y.x; tsig[2 * w + 1] = y.y; }
       }
-      const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nq, q_begin + kBlockQ);
+      const uint32_t q_begin = qc * kBlockQ, q_end = min(item.nb, q_begin + kBlockQ);
       for (uint32_t qs = q_begin; qs < q_end; qs += kStageQ) {
         const uint32_t nq_here = min(kStageQ, q_end - qs);
         wave_lds_sync();
@@ -616,18 +481,13 @@ __global__ __launch_bounds__(256) void k_dg_pairs_deep(const PairArgs a) {
             if (take) { ++compared; }
             take = take && (pop + 9u) / 10u <= a.d;
           }
-          const uint64_t m = __ballot(take);
-          if (m != 0ull) {
-            if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)q << 32) | t; }
-            nstage += (uint32_t)__popcll(m);
-            if (nstage > kStage - 64u) { flush(); }
-          }
+          stage.push(take, ((unsigned long long)q << 32) | t);
         }
       }
     }
   }
-  if (nstage != 0u) { flush(); }
-  for (int o = 32; o > 0; o >>= 1) { compared += shfl_u64(compared, lane ^ o); }
+  stage.finish();
+  for (int o = 32; o > 0; o >>= 1) { compared += swa_shfl_u64(compared, lane ^ o); }
   if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
 }
 
@@ -680,21 +540,10 @@ struct BruteArgs {
 // of two short sequences is emitted by the one with the lower id.  The q-gram bound and the staging of the survivors
 // are k_dg_pairs'.
 __global__ __launch_bounds__(256) void k_dg_brute(const BruteArgs a) {
-  __shared__ unsigned long long stage_all[4][kStage];
+  __shared__ unsigned long long stage_rows[4][kPairStage];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned long long * stage = stage_all[wave];
-  uint32_t nstage = 0;
+  PairStage stage(stage_rows, a.pairs, &a.counters[0], a.pair_cap);
   unsigned long long compared = 0;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(&a.counters[0], (unsigned long long)nstage); }
-    base = shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) { if (base + i < a.pair_cap) { a.pairs[base + i] = stage[i]; } }
-    nstage = 0;
-    wave_lds_sync();
-  };
   const uint64_t nitems = (uint64_t)a.nshort * a.ntiles;
   const uint64_t nwaves = (uint64_t)gridDim.x * 4u;
   const uint32_t top = a.short_below + a.d;                  // start[] has top + 1 entries
@@ -734,16 +583,11 @@ __global__ __launch_bounds__(256) void k_dg_brute(const BruteArgs a) {
           take = (pop + 9u) / 10u <= a.d;
         }
       }
-      const uint64_t m = __ballot(take);
-      if (m != 0ull) {
-        if (take) { stage[nstage + (uint32_t)__popcll(m & lane_lt)] = ((unsigned long long)min(s, p) << 32) | max(s, p); }
-        nstage += (uint32_t)__popcll(m);
-        if (nstage > kStage - 64u) { flush(); }
-      }
+      stage.push(take, ((unsigned long long)min(s, p) << 32) | max(s, p));
     }
   }
-  if (nstage != 0u) { flush(); }
-  for (int o = 32; o > 0; o >>= 1) { compared += shfl_u64(compared, lane ^ o); }
+  stage.finish();
+  for (int o = 32; o > 0; o >>= 1) { compared += swa_shfl_u64(compared, lane ^ o); }
   if (lane == 0 && compared != 0ull) { atomicAdd(&a.counters[1], compared); }
 }
 
@@ -927,12 +771,6 @@ struct widen_u32 {
   __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
 };
 
-int grid_for(const swa_ctx * ctx, uint64_t items) {
-  uint64_t blocks = (items + 255) / 256;
-  const uint64_t cap = (uint64_t)ctx->num_cus * 8;
-  return (int)std::max<uint64_t>(1, std::min(blocks, cap));
-}
-
 // d_frole (the fastidious pair route's buffer, idle at d >= 2) in u32 words: the length counts as k_dg_lengths leaves
 // them, then what the brute-force part reads — start[] and cursor[] per length and the ids sorted by length
 constexpr uint32_t kShortStart = 320, kShortCursor = 640, kShortSorted = 960;
@@ -960,7 +798,7 @@ int window_length(swa_ctx * ctx, uint32_t d, dn_plan * out) {
     auto * slot = static_cast<uint32_t *>(ctx->d_frole.ptr);
     SWA_HIP(ctx, hipMemsetAsync(slot, 0, SWA_DN_HIST_LEN * sizeof(uint32_t), ctx->stream));
     SWA_HIP(ctx, hipMemsetAsync(slot + SWA_DN_HIST_LEN, 0xFF, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_dg_lengths, dim3(grid_for(ctx, ctx->db.n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, slot);
+    hipLaunchKernelGGL(k_dg_lengths, dim3(join_grid(ctx, ctx->db.n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, slot);
     uint32_t got[SWA_DN_HIST_LEN + 1];
     SWA_HIP(ctx, hipMemcpyAsync(got, slot, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1025,28 +863,19 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     const uint64_t member_cap = (uint64_t)n * (ns + 1u);
     const uint64_t item_cap64 = (uint64_t)n + member_cap / 2 + 64;
     const uint32_t item_cap = item_cap64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)item_cap64;
-    SWA_TRY(swa_reserve(ctx, ctx->d_fkeys, asize * sizeof(uint64_t)));
-    SWA_TRY(swa_reserve(ctx, ctx->d_fcnt, (asize * 5 + 4) * sizeof(uint32_t)));              // (the scan reads one entry past `tot`)
-    SWA_TRY(swa_reserve(ctx, ctx->d_foff, (asize + 2) * sizeof(uint64_t)));
-    SWA_TRY(swa_reserve(ctx, ctx->d_fslot, (uint64_t)n * (ns + 1u) * sizeof(uint32_t)));
-    SWA_TRY(swa_reserve(ctx, ctx->d_fmembers, member_cap * sizeof(uint32_t)));
-    SWA_TRY(swa_reserve(ctx, ctx->d_fitems, (uint64_t)item_cap * sizeof(dg_item)));
+    SWA_TRY(join_reserve(ctx, asize, n, ns, member_cap, item_cap));
     SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
-    SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
-    auto * keys = static_cast<unsigned long long *>(ctx->d_fkeys.ptr);
-    auto * cnt_t = static_cast<uint32_t *>(ctx->d_fcnt.ptr);
-    auto * cnt_q = cnt_t + asize, * cur_t = cnt_q + asize, * cur_q = cur_t + asize, * tot = cur_q + asize;
-    auto * goff = static_cast<uint64_t *>(ctx->d_foff.ptr);
-    auto * tslot = static_cast<uint32_t *>(ctx->d_fslot.ptr);
-    auto * qslot = tslot + (uint64_t)n * ns;
-    auto * members = static_cast<uint32_t *>(ctx->d_fmembers.ptr);
-    auto * items = static_cast<dg_item *>(ctx->d_fitems.ptr);
-    auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);   // [0] pairs [1] comparisons [2] extra directions [3] edges
-    auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);             // [8] item counter [9] key table overflow [11] item overflow
+    const JoinTable jt = join_table(ctx, asize, n, ns);
+    auto tot64 = rocprim::make_transform_iterator(jt.tot, widen_u32());
     size_t scan_bytes = 0;
-    auto tot64 = rocprim::make_transform_iterator(tot, widen_u32());
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, tot64, goff, (uint64_t)0, asize + 1, rocprim::plus<uint64_t>(), ctx->stream);
+    (void)rocprim::exclusive_scan(nullptr, scan_bytes, tot64, jt.offsets, (uint64_t)0, asize + 1, rocprim::plus<uint64_t>(), ctx->stream);
     SWA_TRY(swa_reserve(ctx, ctx->d_scan_tmp, scan_bytes + 16));
+    auto scan = [&](const JoinTable &) -> int {
+      SWA_HIP(ctx, rocprim::exclusive_scan(ctx->d_scan_tmp.ptr, scan_bytes, tot64, jt.offsets, (uint64_t)0, asize + 1, rocprim::plus<uint64_t>(),
+                                           ctx->stream));
+      return SWA_OK;
+    };
+    auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);   // [0] pairs [1] comparisons [2] extra directions [3] edges
     if (ctx->dn_pair_cap == 0) { ctx->dn_pair_cap = 16ull * n + (1ull << 20); }
     uint64_t npairs = 0;
     uint64_t launches = 0;
@@ -1063,7 +892,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       for (uint32_t L = 0; L < top; ++L) { start[L + 1] = start[L] + ctx->dn_len_hist[L]; }
       SWA_HIP(ctx, hipMemcpyAsync(words + kShortStart, start, (top + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
       SWA_HIP(ctx, hipMemsetAsync(words + kShortCursor, 0, top * sizeof(uint32_t), ctx->stream));
-      hipLaunchKernelGGL(k_dg_short_sort, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, n, top, words + kShortStart,
+      hipLaunchKernelGGL(k_dg_short_sort, dim3(join_grid(ctx, n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, n, top, words + kShortStart,
                          words + kShortCursor, words + kShortSorted, plan.nnear);
       SWA_HIP(ctx, hipGetLastError());
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (start[] is on this stack)
@@ -1082,32 +911,29 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     for (int attempt = 0; attempt < 6; ++attempt) {
       SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->dn_pair_cap * sizeof(uint64_t)));
       SWA_HIP(ctx, hipMemsetAsync(fc, 0, 8 * sizeof(uint64_t), ctx->stream));
-      SWA_HIP(ctx, hipMemsetAsync(dflags + 9, 0, sizeof(uint32_t), ctx->stream));
-      SWA_HIP(ctx, hipMemsetAsync(dflags + 11, 0, sizeof(uint32_t), ctx->stream));
+      SWA_HIP(ctx, hipMemsetAsync(jt.flags, 0, 2 * sizeof(uint32_t), ctx->stream));
       for (uint32_t k = 0; k <= d; ++k) {
         GroupArgs g{};
         g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen; g.n = n; g.d = d; g.k = k; g.wlen = wlen; g.short_below = plan.short_below;
-        g.keys = keys; g.cnt_t = cnt_t; g.cnt_q = cnt_q; g.amask = asize - 1; g.tslot = tslot; g.qslot = qslot; g.overflow = dflags + 9;
+        g.keys = jt.keys; g.cnt_t = jt.cnt_a; g.cnt_q = jt.cnt_b; g.amask = asize - 1; g.tslot = jt.aslot; g.qslot = jt.bslot; g.overflow = jt.flags;
         g.owner_rank = ctx->dn_owner_rank; g.owner_world = ctx->dn_owner_world;
-        const dim3 gn(grid_for(ctx, n)), ga(grid_for(ctx, asize)), b(256);
-        hipLaunchKernelGGL(k_dg_clear, ga, b, 0, ctx->stream, keys, cnt_t, cnt_q, cur_t, cur_q, asize);
-        if (ns <= (uint32_t)kSmallShifts) { hipLaunchKernelGGL(k_dg_targets<kSmallShifts>, gn, b, 0, ctx->stream, g); }
-        else { hipLaunchKernelGGL(k_dg_targets<kMaxShifts>, gn, b, 0, ctx->stream, g); }
-        hipLaunchKernelGGL(k_dg_queries, gn, b, 0, ctx->stream, g);
-        hipLaunchKernelGGL(k_dg_totals, ga, b, 0, ctx->stream, cnt_t, cnt_q, asize, tot);
-        SWA_HIP(ctx, rocprim::exclusive_scan(ctx->d_scan_tmp.ptr, scan_bytes, tot64, goff, (uint64_t)0, asize + 1, rocprim::plus<uint64_t>(),
-                                             ctx->stream));
-        hipLaunchKernelGGL(k_dg_scatter, gn, b, 0, ctx->stream, g, tot, goff, cur_t, cur_q, members);
-        SWA_HIP(ctx, hipMemsetAsync(dflags + 8, 0, sizeof(uint32_t), ctx->stream));
-        // blocks of 64 targets x 256 queries for the LDS kernels (d = 2, 3 and 9 .. 16; the per-pair kernel for other d)
+        auto key_kernels = [&](dim3 gn, dim3 b) {
+          if (ns <= (uint32_t)kSmallShifts) { hipLaunchKernelGGL(k_dg_targets<kSmallShifts>, gn, b, 0, ctx->stream, g); }
+          else { hipLaunchKernelGGL(k_dg_targets<kMaxShifts>, gn, b, 0, ctx->stream, g); }
+          hipLaunchKernelGGL(k_dg_queries, gn, b, 0, ctx->stream, g);
+        };
+        uint32_t * item_count = jt.flags + 2;
+        SWA_HIP(ctx, hipMemsetAsync(item_count, 0, sizeof(uint32_t), ctx->stream));
+        // blocks of 64 targets x 256 queries for the LDS kernels (d = 2, 3 and 9 .. 16; the per-pair kernel for other d);
+        // a group needs a pair of DIFFERENT amplicons (an amplicon alone is its own target): t q >= 2
         const bool deep = d >= 9u;
         const bool blocked = d == 2u || d == 3u || deep;
-        if (blocked) { hipLaunchKernelGGL(k_dg_items<true>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap, dflags + 11); }
-        else { hipLaunchKernelGGL(k_dg_items<false>, ga, b, 0, ctx->stream, cnt_t, cnt_q, tot, goff, asize, items, dflags + 8, item_cap, dflags + 11); }
+        if (blocked) { SWA_TRY(join_run<DnBlocks>(ctx, jt, 2u, item_count, item_cap, key_kernels, scan)); }
+        else { SWA_TRY(join_run<DnTiles>(ctx, jt, 2u, item_count, item_cap, key_kernels, scan)); }
         PairArgs p{};
         p.seqs = ctx->db.seqs; p.seq_off = ctx->db.seq_off; p.seqlen = ctx->db.seqlen;
         p.sigs = static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr);
-        p.members = members; p.items = items; p.item_count = dflags + 8; p.item_cap = item_cap; p.d = d; p.k = k; p.wlen = wlen;
+        p.members = jt.members; p.items = jt.items; p.item_count = item_count; p.item_cap = item_cap; p.d = d; p.k = k; p.wlen = wlen;
         p.pairs = static_cast<unsigned long long *>(ctx->d_fpairs.ptr); p.counters = fc; p.pair_cap = ctx->dn_pair_cap;
         if (deep && wlen == 32u) { hipLaunchKernelGGL(k_dg_pairs_deep<32>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
         else if (deep) { hipLaunchKernelGGL(k_dg_pairs_deep<16>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, p); }
@@ -1125,12 +951,8 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         ++launches;
       }
       uint64_t got[2] = {0, 0};
-      uint32_t fl[4] = {0, 0, 0, 0};
-      SWA_HIP(ctx, hipMemcpyAsync(got, fc, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-      SWA_HIP(ctx, hipMemcpyAsync(fl, dflags + 8, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
-      SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (fl[1] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, "swa_dn_graph: group key table overflow"); }
-      if (fl[3] != 0) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_dn_graph: the work items of a window outgrew item_cap"); }
+      SWA_TRY(join_status(ctx, jt, fc, 2, got, "swa_dn_graph: group key table overflow",
+                          "swa_dn_graph: the work items of a window outgrew item_cap"));
       ctx->dn_comparisons = got[1];
       if (got[0] <= ctx->dn_pair_cap) { npairs = got[0]; break; }
       if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_dn_graph: pair list keeps overflowing"); }
@@ -1146,7 +968,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       auto * wq = static_cast<uint32_t *>(ctx->d_scan_targets.ptr);
       auto * wt = wq + 2 * npairs;
       auto * wd = static_cast<uint32_t *>(ctx->d_scan_diffs.ptr);
-      hipLaunchKernelGGL(k_dg_worklist, dim3(grid_for(ctx, npairs)), dim3(256), 0, ctx->stream,
+      hipLaunchKernelGGL(k_dg_worklist, dim3(join_grid(ctx, npairs)), dim3(256), 0, ctx->stream,
                          static_cast<const unsigned long long *>(ctx->d_fpairs.ptr), npairs, ctx->db.abundance, no_cluster_breaking,
                          wq, wt, fc + 2);
       uint64_t extra = 0;
@@ -1161,13 +983,13 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         SWA_TRY(swa_reserve(ctx, ctx->d_dn_vals, 2 * nwork * sizeof(uint32_t)));          // keys: in | out (bytes; the edges' values later)
         auto * packed = static_cast<unsigned long long *>(ctx->d_dn_keys.ptr);
         auto * wkey = static_cast<unsigned char *>(ctx->d_dn_vals.ptr);
-        hipLaunchKernelGGL(k_dg_work_keys, dim3(grid_for(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, nwork,
+        hipLaunchKernelGGL(k_dg_work_keys, dim3(join_grid(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, nwork,
                            static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr), ctx->db.seqlen, kAlignLenWeight, wkey, packed);
         size_t order_bytes = 0;
         (void)rocprim::radix_sort_pairs(nullptr, order_bytes, wkey, wkey + nwork, packed, packed + nwork, nwork, 0, 6, ctx->stream);
         SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, order_bytes + 16));
         SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, order_bytes, wkey, wkey + nwork, packed, packed + nwork, nwork, 0, 6, ctx->stream));
-        hipLaunchKernelGGL(k_dg_work_unpack, dim3(grid_for(ctx, nwork)), dim3(256), 0, ctx->stream, packed + nwork, nwork, wq, wt);
+        hipLaunchKernelGGL(k_dg_work_unpack, dim3(join_grid(ctx, nwork)), dim3(256), 0, ctx->stream, packed + nwork, nwork, wq, wt);
         launches += 4;
       }
       // (the launcher takes 32-bit counts: in slices)
@@ -1180,7 +1002,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       SWA_TRY(swa_reserve(ctx, ctx->d_dn_vals, 2 * nwork * sizeof(uint32_t)));
       auto * ekeys = static_cast<unsigned long long *>(ctx->d_dn_keys.ptr);
       auto * evals = static_cast<uint32_t *>(ctx->d_dn_vals.ptr);
-      hipLaunchKernelGGL(k_dg_edges, dim3(grid_for(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, wd, nwork, d, ekeys, evals, fc + 3);
+      hipLaunchKernelGGL(k_dg_edges, dim3(join_grid(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, wd, nwork, d, ekeys, evals, fc + 3);
       SWA_HIP(ctx, hipMemcpyAsync(&nedges, fc + 3, sizeof(nedges), hipMemcpyDeviceToHost, ctx->stream));
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
       if (nedges != 0) {
@@ -1210,7 +1032,7 @@ int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const ui
   *total = nedges;
   ctx->csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold this graph)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
-  hipLaunchKernelGGL(k_dg_offsets, dim3(grid_for(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
+  hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
                      static_cast<uint64_t *>(ctx->d_offsets_tmp.ptr));
   SWA_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_offsets_tmp.ptr, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   if (nedges > cap) {
@@ -1221,7 +1043,7 @@ int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const ui
     SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, nedges * (sizeof(uint32_t) + 1)));
     auto * nb32 = static_cast<uint32_t *>(ctx->d_nb_tmp.ptr);
     auto * df8 = reinterpret_cast<uint8_t *>(nb32 + nedges);
-    hipLaunchKernelGGL(k_dg_split, dim3(grid_for(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32, df8);
+    hipLaunchKernelGGL(k_dg_split, dim3(join_grid(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32, df8);
     SWA_HIP(ctx, hipMemcpyAsync(neighbours, nb32, nedges * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipMemcpyAsync(diffs, df8, nedges, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -1256,11 +1078,11 @@ extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uin
   ctx->csr_ready = false;
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, (nedges + 1) * (sizeof(uint32_t) + 1)));
-  hipLaunchKernelGGL(k_dg_offsets, dim3(grid_for(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
+  hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
                      static_cast<uint64_t *>(ctx->d_offsets_tmp.ptr));
   if (nedges != 0) {
     auto * nb32 = static_cast<uint32_t *>(ctx->d_nb_tmp.ptr);
-    hipLaunchKernelGGL(k_dg_split, dim3(grid_for(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32,
+    hipLaunchKernelGGL(k_dg_split, dim3(join_grid(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32,
                        reinterpret_cast<uint8_t *>(nb32 + nedges));
   }
   SWA_HIP(ctx, hipGetLastError());
@@ -1284,7 +1106,7 @@ extern "C" int swa_dn_parent_diffs(swa_ctx * ctx, uint8_t * pdiff) {
   const auto * parent = static_cast<const uint32_t *>(ctx->d_cluster.ptr) + 2ull * n;        // (layout of swa_d1_cluster_device: label | gen | parent)
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_diffs, (uint64_t)n + 16));
   auto * out = static_cast<uint8_t *>(ctx->d_scan_diffs.ptr);
-  hipLaunchKernelGGL(k_dg_parent_diffs, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr),
+  hipLaunchKernelGGL(k_dg_parent_diffs, dim3(join_grid(ctx, n)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr),
                      nb32, reinterpret_cast<const uint8_t *>(nb32 + ctx->csr_total), parent, n, out);
   SWA_HIP(ctx, hipGetLastError());
   SWA_HIP(ctx, hipMemcpyAsync(pdiff, out, n, hipMemcpyDeviceToHost, ctx->stream));

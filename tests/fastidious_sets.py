@@ -202,18 +202,99 @@ def is_small(L: int) -> bool:
     return L >= 1003
 
 
-def build_case(L: int, path, outlier: int | None = None):
-    """edit_atlas(L, seed L) (+ the outlier) written to `path`, clustered on the host from the oracle's network:
-    (db, light flags, headers of the three-edit sequences)"""
+def cluster_records(recs: list, path):
+    """the records written to `path` and clustered on the host from the oracle's network: (db, light flags)"""
     import support as S
     from swarm_amd import D1Clusters, HostDb
-    recs, three = edit_atlas(L, L, is_small(L))
-    write_fasta(path, recs if outlier is None else with_outlier(recs, outlier))
+    write_fasta(path, recs)
     db = S.db_from_fasta(path)
     off, nb, dup = S.oracle_d1_network(db)
     assert not dup
     flags, _ = D1Clusters(HostDb(path), off, nb).light_flags(3)
+    return db, flags
+
+
+def build_case(L: int, path, outlier: int | None = None):
+    """edit_atlas(L, seed L) (+ the outlier): (db, light flags, headers of the three-edit sequences)"""
+    recs, three = edit_atlas(L, L, is_small(L))
+    db, flags = cluster_records(recs if outlier is None else with_outlier(recs, outlier), path)
     return db, flags, three
+
+
+# ---- one group larger than the items' stride -------------------------------------------------------------------------------
+SHARED_HEAVY, SHARED_LIGHT = 500, 530
+
+
+def shared_ends(seed: int = 64) -> tuple:
+    """(records, three, planted): SHARED_HEAVY centroids (abundance 3) and 30 of their one-edit neighbours (abundance 1:
+    their centroid's swarm takes them) are the ~530 heavy amplicons, SHARED_LIGHT amplicons of abundance 2 the light
+    ones, all of 118 .. 122 nt with the same first 32 and the same last 32 nucleotides and random middles: the prefix
+    group and the suffix group of the pair route each hold everybody, ceil(530 / 64)^2 = 81 tiles of 64 x 64, more than
+    the 64 items a group's tiles are dealt to, so the tiles 64 .. 80 are somebody's SECOND turn.  The light amplicons
+    are swarms of their own (abundance 2, as edit_atlas's: more than the abundance-1 neighbours some of them are one
+    edit from, so nobody takes them; mass 2 < 3) and their headers put them in the order of k.  `planted` = k -> kind,
+    spread over the whole order so that their places in the member list lie in every tile row:
+      one   one edit from a centroid's neighbour (and two from the centroid), edits in the middle;
+      two   two edits from a centroid, both in the middle;
+      head  two edits from a centroid, one of them in the first 32 nt: out of the prefix group, so the suffix group's
+            tiles must find the pair;
+      three three substitutions in a centroid's middle: must not graft (`three`: their headers)."""
+    rng = np.random.default_rng(seed)
+    head, tail = _rand(rng, 32), _rand(rng, 32)
+    seen, recs, three, planted = set(), [], [], {}
+
+    def add(header: str, s: str) -> None:
+        assert s not in seen and 118 <= len(s) <= 122 and s.endswith(tail), header
+        seen.add(s)
+        recs.append((header, s))
+
+    def fresh(length: int) -> str:
+        return head + _rand(rng, length - 64) + tail
+
+    # the centroids edits are planted on have 120 nt: two insertions or two deletions stay within 118 .. 122
+    cents = [fresh(120 if c % 5 == 0 else 118 + int(rng.integers(0, 5))) for c in range(SHARED_HEAVY)]
+    for c, s in enumerate(cents):
+        add(f"h{c:04d}_3", s)
+
+    def edit(s: str, kind: str, p: int, step: int):
+        return (kind, p, "" if kind == "d" else (_other(s[p], step) if kind == "s" else "ACGT"[(step + p) % 4]))
+
+    neighbours = {}
+    for j in range(30):                                           # heavy amplicons that are no centroids
+        c = 5 * (3 * j + 1)
+        neighbours[c] = apply_edits(cents[c], [edit(cents[c], "sdi"[j % 3], 40 + j, j)])
+        add(f"m{c:04d}_1", neighbours[c])
+    ones, twos = sorted(neighbours), [5 * (3 * j + 2) for j in range(33)]
+    heads, threes = [15 * j for j in range(1, 9)], [15 * j for j in range(20, 26)]
+    where = {}                                                    # k -> (kind, which of its kind): every kind all over the order
+    for kind, every, first, count in (("one", 17, 1, len(ones)), ("two", 16, 3, len(twos)), ("head", 64, 7, len(heads)),
+                                      ("three", 85, 10, len(threes))):
+        for i in range(count):
+            k = every * i + first
+            while k in where:
+                k += 1
+            where[k] = (kind, i)
+    assert max(where) < SHARED_LIGHT
+    for k in range(SHARED_LIGHT):
+        kind, i = where.get(k, ("", 0))
+        if kind == "one":                                         # one edit from the neighbour, elsewhere in the middle
+            s = apply_edits(neighbours[ones[i]], [edit(neighbours[ones[i]], "sid"[i % 3], 75 + i % 8, i)])
+        elif kind == "two":
+            c, kk = cents[twos[i]], ["ss", "sd", "si", "dd", "ii", "di"][i % 6]
+            s = apply_edits(c, [edit(c, kk[0], 36 + i % 20, i), edit(c, kk[1], 70 + i % 15, i + 1)])
+        elif kind == "head":
+            s = apply_edits(cents[heads[i]], [edit(cents[heads[i]], "s", 3 * i + 2, i), edit(cents[heads[i]], "s", 50 + i, i)])
+        elif kind == "three":
+            s = apply_edits(cents[threes[i]], [edit(cents[threes[i]], "s", q, i) for q in (38, 59, 80)])
+        else:
+            s = fresh(118 + int(rng.integers(0, 5)))
+        header = f"x{k:04d}{kind}_2"
+        add(header, s)
+        if kind:
+            planted[k] = kind
+        if kind == "three":
+            three.append(header)
+    return recs, three, planted
 
 
 def assert_not_trivial(db, flags, graft, three) -> None:

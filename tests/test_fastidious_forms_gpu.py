@@ -142,6 +142,30 @@ def test_switches_show_in_the_plan(tmp_path, monkeypatch):
         monkeypatch.delenv(name)
 
 
+@pytest.mark.parametrize("words", [False, True])
+def test_a_group_of_more_tiles_than_items_matches_oracle(gpu_ctx, tmp_path, monkeypatch, words):
+    """FS.shared_ends: the prefix group and the suffix group hold all 530 light and 530 heavy amplicons, 81 tiles dealt to
+    64 items, so the pair kernel's strided walk (tile = item.tile, + 64) takes a second turn and the items kernel deals
+    a group more tiles than items: on k_fast_pairs_lines<5> and, under SWA_FAST_PAIRS=words, on k_fast_pairs.
+    (tests/test_fastidious_identity.py checks on the CPU that the set is what it says.)"""
+    if words:
+        monkeypatch.setenv("SWA_FAST_PAIRS", "words")
+    recs, three, planted = FS.shared_ends()
+    fa = tmp_path / "in.fa"
+    db, want_flags = FS.cluster_records(recs, fa)
+    hdb, cl, flags, stats, graft, counters = _pipeline(gpu_ctx, fa)
+    plan, totals = gpu_ctx.d1_fastidious_plan(), gpu_ctx.d1_fastidious_totals()
+    assert np.array_equal(flags, want_flags)
+    assert plan == FS.expected_plan(db.longest, words=words) and plan[:3] == ([1, 0, 5] if words else [1, 5, 5])
+    want_graft, want_counters = S.oracle_fastidious(db, flags, 16)
+    FS.assert_not_trivial(db, flags, want_graft, three)
+    print(f"words {words} n {db.n} plan {plan} totals {totals} candidates {int(counters[2])} / {int(want_counters[2])} "
+          f"grafts {int((want_graft != FS.NO_GRAFT).sum())}, differ at {int((graft != want_graft).sum())}")
+    assert np.array_equal(graft, want_graft)
+    assert [int(x) for x in counters[:5]] == [int(x) for x in want_counters[:5]]
+    assert totals[0] >= len(planted) - len(three) and totals[3] == 1
+
+
 @pytest.mark.parametrize("X", [500, 1005])
 def test_shards_of_borrowed_cells_combine_to_the_oracle(gpu_ctx, tmp_path, X):
     fa = tmp_path / "in.fa"

@@ -363,9 +363,9 @@ def test_two_edit_test_on_register_words_is_exact():
     assert yes > 1500 and no > 500
 
 
-# ---- the work item list of the pair route (d1.hip: fastidious_pair_route, d1_fast.inc: k_fg_items) -------------------------
+# ---- the work item list of the pair route (d1.hip: fastidious_pair_route; group_join.inc: k_join_items<FastTiles>) ----------
 def _items_of(l: int, h: int) -> int:
-    """k_fg_items: a group's 64 x 64 tiles, dealt to at most kFastStride = 64 items; none without both kinds"""
+    """k_join_items<FastTiles>: a group's 64 x 64 tiles, dealt to at most kFastStride = 64 items; none without both kinds"""
     if l == 0 or h == 0:
         return 0
     return min(((l + 63) // 64) * ((h + 63) // 64), 64)
@@ -437,3 +437,38 @@ def test_outlier_sorts_last_and_changes_no_graft(tmp_path):
     graft, counters = S.oracle_fastidious(db, flags, 16)
     ograft, ocounters = S.oracle_fastidious(odb, oflags, 16)
     assert np.array_equal(ograft[:-1], graft) and ograft[-1] == FS.NO_GRAFT and int(ocounters[2]) == int(counters[2])
+
+
+def test_shared_ends_has_a_group_of_more_tiles_than_items(tmp_path):
+    """FS.shared_ends is what tests/test_fastidious_forms_gpu.py needs it to be: distinct sequences, every planted light
+    amplicon of the kinds one / two / head grafted and no three-edit one, and the prefix group (all but the `head` kind)
+    and the suffix group (everybody) of more 64 x 64 tiles than the 64 items they are dealt to.  The members of a group
+    are listed in the order the scatter's atomics are served, close to the order of the ids but not defined: so the
+    planted amplicons are spread over all of it, and in the order of the ids their pairs lie in tiles below 64 and in
+    tiles from 64 on (a second turn of an item), for every kind that grafts."""
+    recs, three, planted = FS.shared_ends()
+    assert len({s for _, s in recs}) == len(recs) and len({h for h, _ in recs}) == len(recs)
+    assert all(118 <= len(s) <= 122 for _, s in recs)
+    assert len({s[-32:] for _, s in recs}) == 1
+    db, flags = FS.cluster_records(recs, tmp_path / "in.fa")
+    graft, counters = S.oracle_fastidious(db, flags, 16)
+    FS.assert_not_trivial(db, flags, graft, three)
+    light, heavy = np.flatnonzero(flags != 0), np.flatnonzero(flags == 0)
+    assert len(light) == FS.SHARED_LIGHT and len(heavy) == FS.SHARED_HEAVY + 30
+    ids = {h.decode(): i for i, h in enumerate(db.headers)}
+    heads = {ids[f"x{k:04d}head_2"] for k, kind in planted.items() if kind == "head"}
+    first = {s[:32] for h, s in recs if ids[h] not in heads}
+    assert len(first) == 1 and all(s[:32] not in first for h, s in recs if ids[h] in heads)
+    tiles_h = (len(heavy) + 63) // 64
+    assert ((len(light) - len(heads) + 63) // 64) * tiles_h > 64 and _items_of(len(light) - len(heads), len(heavy)) == 64
+    assert ((len(light) + 63) // 64) * tiles_h > 64 and _items_of(len(light), len(heavy)) == 64
+    rank_l = {int(x): r for r, x in enumerate(light)}             # (the suffix group's; the prefix group's lacks the heads)
+    rank_h = {int(h): r for r, h in enumerate(heavy)}
+    tiles = {}
+    for k, kind in planted.items():
+        x = ids[f"x{k:04d}{kind}_2"]
+        assert flags[x] and (graft[x] == FS.NO_GRAFT) == (kind == "three"), (k, kind)
+        if kind != "three":
+            tiles.setdefault(kind, []).append((rank_l[x] // 64) * tiles_h + rank_h[int(graft[x])] // 64)
+    for kind in ("one", "two", "head"):
+        assert min(tiles[kind]) < 64 <= max(tiles[kind]), (kind, sorted(tiles[kind]))

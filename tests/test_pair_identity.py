@@ -357,14 +357,14 @@ def _dn_item_cap(n: int, d: int) -> int:
 
 
 def _dn_blocked_items(t: int, q: int, c: dict) -> int:
-    """k_dg_items<true>: a group of t targets and q queries (t q >= 2) -> its blocks of kBlockT x kBlockQ, at most kBlockStride"""
+    """k_join_items<DnBlocks>: a group of t targets and q queries (t q >= 2) -> its blocks of kBlockT x kBlockQ, at most kBlockStride"""
     if t * q < 2:
         return 0
     return min((t + c["kBlockT"] - 1) // c["kBlockT"] * ((q + c["kBlockQ"] - 1) // c["kBlockQ"]), c["kBlockStride"])
 
 
 def _dn_tiled_items(t: int, q: int, c: dict) -> int:
-    """k_dg_items<false>: tiles of kTile pairs, at most kStride"""
+    """k_join_items<DnTiles>: tiles of kTile pairs, at most kStride"""
     if t * q < 2:
         return 0
     return min((t * q + c["kTile"] - 1) // c["kTile"], c["kStride"])
