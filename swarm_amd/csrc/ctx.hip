@@ -85,19 +85,14 @@ extern "C" int swa_ctx_create(int device, void * stream, swa_ctx ** out) {
     (void)hipDeviceSynchronize();
     for (void * p : held) { (void)hipFree(p); }
   }
-  // the status block and the views into it (swa_internal.h)
-  if (swa_reserve(ctx, ctx->d_status, 4096) != SWA_OK || hipMemset(ctx->d_status.ptr, 0, 4096) != hipSuccess ||
-      hipHostMalloc(&ctx->h_status, 4096, hipHostMallocDefault) != hipSuccess) {
+  // the status block and its pinned mirror (swa_internal.h)
+  if (swa_reserve(ctx, ctx->d_status, sizeof(swa_status_block)) != SWA_OK || hipMemset(ctx->d_status.ptr, 0, sizeof(swa_status_block)) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void **>(&ctx->h_status), sizeof(swa_status_block), hipHostMallocDefault) != hipSuccess) {
     swa_release(ctx->d_status);
     if (ctx->own_stream) { (void)hipStreamDestroy(ctx->stream); }
     delete ctx;
     return SWA_E_NOMEM;
   }
-  auto * base = static_cast<uint8_t *>(ctx->d_status.ptr);
-  ctx->d_flags.ptr = base;            ctx->d_flags.bytes = 64;
-  ctx->d_stats.ptr = base + 64;       ctx->d_stats.bytes = 128;
-  ctx->d_guard.ptr = base + 192;      ctx->d_guard.bytes = 192;
-  ctx->d_acounters.ptr = base + 1024; ctx->d_acounters.bytes = 1024;
   *out = ctx;
   return SWA_OK;
 }

@@ -838,11 +838,11 @@ static ListRegions list_regions(const swa_ctx * ctx, uint64_t * total_items) {
   return r;
 }
 
-// abundance rank of every amplicon (k_abundance_rank: three streaming passes); flags[1] is raised when the database is
+// abundance rank of every amplicon (k_abundance_rank: three streaming passes); kFlagUnordered is raised when the database is
 // not in abundance order
 static int launch_abundance_rank(swa_ctx * ctx) {
   if (ctx->rank_ready) {                                    // (a fact of the uploaded database: once per upload)
-    if (ctx->db_unordered) { SWA_HIP(ctx, hipMemsetAsync(static_cast<uint32_t *>(ctx->d_flags.ptr) + 1, 1, sizeof(uint32_t), ctx->stream)); }
+    if (ctx->db_unordered) { SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags + kFlagUnordered, 1, sizeof(uint32_t), ctx->stream)); }
     return SWA_OK;
   }
   ctx->rank_ready = true;
@@ -853,18 +853,16 @@ static int launch_abundance_rank(swa_ctx * ctx) {
   auto * rank = static_cast<uint32_t *>(ctx->d_arank.ptr);
   auto * tile_last = static_cast<uint32_t *>(ctx->d_rank_tmp.ptr);
   hipLaunchKernelGGL(k_abundance_rank, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.abundance, n, rank,
-                     static_cast<uint32_t *>(ctx->d_flags.ptr), tile_last);
+                     swa_status(ctx)->flags, tile_last);
   hipLaunchKernelGGL(k_abundance_rank_carry, dim3(1), dim3(256), 0, ctx->stream, tile_last, tiles);
   hipLaunchKernelGGL(k_abundance_rank_fill, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, n, rank, tile_last);
   return SWA_OK;
 }
 
-__global__ void k_set_flags(uint32_t * flags, uint32_t unserved, uint32_t shortest_code) { flags[3] = unserved; flags[6] = shortest_code; }
-__global__ void k_set_guard_made(unsigned long long * guard, uint32_t made0, uint32_t made1) { guard[0] = made0; guard[1] = made1; }
+__global__ void k_set_flags(uint32_t * flags, uint32_t unserved, uint32_t shortest_code) { flags[kFlagUnserved] = unserved; flags[kFlagShortest] = shortest_code; }
+__global__ void k_set_guard_made(unsigned long long * guard, uint32_t made0, uint32_t made1) { guard[kGuardMade] = made0; guard[kGuardMade + 1] = made1; }
 
 // ---- the streaming build (d1_stream.inc) ------------------------------------------------------
-enum { kSbLines = 0, kSbRec = 1, kSbFp = 5, kSbCnt = 8, kSbTile = 10, kSbStart = 12, kSbPartial = 14, kSbScal = 16,
-       kSbMembers = 17, kSbOver = 19, kSbKind = 20, kSbLinkA = 22, kSbLinkB = 23, kSbHeavy = 24, kSbMTable = 26, kSbMBloom = 27, kSbSched = 28 };
 
 struct PartPlan { uint32_t levels; uint32_t bits[4]; uint32_t total; };
 static PartPlan plan_levels(uint32_t total_bits, uint32_t max_bits = kPartMaxBits) {
@@ -1033,12 +1031,12 @@ static int ensure_lines(swa_ctx * ctx) {
   auto * lines = static_cast<uint4 *>(ctx->d_stream[kSbLines].ptr);
   const auto * rank = static_cast<const uint32_t *>(ctx->d_arank.ptr);
   SWA_HIP(ctx, hipMemsetAsync(reinterpret_cast<uint8_t *>(lines) + (uint64_t)n * lq * 16u, 0, 64, ctx->stream));
-  swa_t0(ctx, 15);
+  swa_t0(ctx, kTimeLines);
   const dim3 grid(grid_for(ctx, n, 256, 8));
   if (lq == 4u) { hipLaunchKernelGGL(k_lines_build<4>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
   else if (lq == 8u) { hipLaunchKernelGGL(k_lines_build<8>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
   else { hipLaunchKernelGGL(k_lines_build<16>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
-  swa_t1(ctx, 15);
+  swa_t1(ctx, kTimeLines);
   SWA_HIP(ctx, hipGetLastError());
   ctx->lines_ready = true;
   ctx->lines_quads = lq;
@@ -1047,12 +1045,13 @@ static int ensure_lines(swa_ctx * ctx) {
 
 // The two anchor indexes of the whole database (or of the routed id lists) by the streaming build: members in group
 // order (d_stream[kSbMembers + which]: ids), the work lists of the pair kernels, the flags build_owned_index reads
-// ([0] identical sequences [2] partition too coarse [3] unserved seeds [4, 5] oversized groups [6] shortest sequence).
+// (kFlagDuplicates, kFlagKeyOverflow, kFlagUnserved, kFlagOversized / kFlagOverMass, kFlagShortest).
 static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_count) {
   ctx->anchor_ready = false;
   ctx->stream_index = false;
   ctx->list_counts_ready = false;
   const uint32_t n = ctx->db.n;
+  swa_status_block * st = swa_status(ctx);
   swa_lap(ctx, "(build starts)");
   SWA_TRY(ensure_db_lengths(ctx));
   swa_lap(ctx, "db lengths");
@@ -1102,18 +1101,17 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   }
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbScal], 64 * sizeof(uint64_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbOver], ((uint64_t)n + 8) & ~3ull));
-  SWA_TRY(swa_reserve(ctx, ctx->d_acounters, kCounterWords * sizeof(uint32_t)));
   {
     ClearList c{};
-    clear_add(c, ctx->d_acounters.ptr, kCounterWords * sizeof(uint32_t));
-    clear_add(c, ctx->d_guard.ptr, 8 * sizeof(uint64_t));      // the guard's index counters: this build's
+    clear_add(c, st->counters, sizeof(st->counters));
+    clear_add(c, st->guard, kGuardCall * sizeof(uint64_t));    // the guard's index counters: this build's
     clear_add(c, ctx->d_stream[kSbOver].ptr, ((uint64_t)n + 8) & ~3ull);
     // (the entry behind the last bucket's counts of each index: the scan of the counts reads one past the end)
     for (int i = 0; i < 2; ++i) { clear_add(c, static_cast<uint32_t *>(ctx->d_stream[kSbKind + i].ptr) + (uint64_t)kListsPerIndex * buckets, sizeof(uint32_t)); }
     SWA_TRY(clear_launch(ctx, c));
   }
   swa_lap(ctx, "buffers reserved, counters cleared");
-  auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);                // (cleared by the caller: index build, or the retry)
+  uint32_t * dflags = st->flags;                            // (cleared by the caller: index build, or the retry)
   auto * scal = static_cast<uint64_t *>(ctx->d_stream[kSbScal].ptr);      // [0..3] level-0 chunk tables, [8 + i] totals (u32)
   const uint32_t win_a = ctx->anchor_a, win_b = ctx->anchor_b;
   const uint32_t minlen = anchor_minlen(ctx), window_mode = (win_a != 0 || win_b != 0) ? 1u : 0u;
@@ -1133,7 +1131,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   k.win_a = win_a; k.win_b = win_b; k.minlen = minlen; k.window_mode = window_mode;
   k.nwin = ctx->anchor_w / 32u;
   k.flags = dflags;
-  k.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
+  k.guard = reinterpret_cast<unsigned long long *>(st->guard);
   // (single GPU, the whole database keyed: the short sequences and their possible neighbours become members of the plain
   // kernel's table; a rank of a multi-GPU job keeps the database-wide table for them)
   k.mark_short = (!routed && ctx->owner_world == 1u) ? static_cast<uint8_t *>(ctx->d_stream[kSbOver].ptr) : nullptr;
@@ -1149,7 +1147,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   if (by_rec) {   // (the records were made by the ranks that hold the amplicons' slices: what k_keys would have counted)
     hipLaunchKernelGGL(k_set_guard_made, dim3(1), dim3(1), 0, ctx->stream, k.guard, ctx->route_m[0], ctx->route_m[1]);
   }
-  swa_t0(ctx, 8);
+  swa_t0(ctx, kTimeKeys);
   if (by_rec) { /* nothing to key */ }
   else if (keys_hist) {
     const uint32_t ntiles = (uint32_t)((records + j.tile - 1) / j.tile);
@@ -1163,7 +1161,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     const dim3 kgrid((unsigned)grid_for(ctx, records, 256, 8), routed ? 2u : 1u);
     hipLaunchKernelGGL(k_keys<false>, kgrid, dim3(256), 0, ctx->stream, k);
   }
-  swa_t1(ctx, 8);
+  swa_t1(ctx, kTimeKeys);
   swa_lap(ctx, "k_keys");
 
   // ---- partition by the top bits of the key
@@ -1181,24 +1179,24 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   // (no second array travels with the records: the fingerprints of rounds 3-5 served k_group1's search for identical
   // sequences, which the prefix pass of the pair kernels now does on the sequences themselves)
   j.starts_stride = e_start + 2;
-  swa_t0(ctx, 9);
+  swa_t0(ctx, kTimeKeyPartition);
   SWA_TRY(run_partition(ctx, j));
-  swa_t1(ctx, 9);
+  swa_t1(ctx, kTimeKeyPartition);
   swa_lap(ctx, "key partition");
   if (!ctx->guard_keys_done) {
     // the guard's second opinion on the key records, once per uploaded database: from the packed database against what the
     // partition holds (k_guard_db / k_guard_records); compared at the next guard_check
-    auto * gsum = static_cast<unsigned long long *>(ctx->d_guard.ptr) + 16;
-    SWA_HIP(ctx, hipMemsetAsync(gsum, 0, 8 * sizeof(uint64_t), ctx->stream));
+    auto * guard = reinterpret_cast<unsigned long long *>(st->guard);
+    SWA_HIP(ctx, hipMemsetAsync(guard + kGuardKeys, 0, sizeof(st->guard) - kGuardKeys * sizeof(uint64_t), ctx->stream));
     GuardDbArgs gd{};
     gd.seqs = ctx->db.seqs; gd.seq_off = ctx->db.seq_off; gd.seqlen = ctx->db.seqlen; gd.n = n;
     for (int i = 0; i < 2; ++i) { gd.list[i] = k.list[i]; gd.list_count[i] = routed ? ctx->route_m[i] : 0; gd.list_rec[i] = by_rec ? ctx->route_rec[i] : nullptr; }
     gd.owner_rank = k.owner_rank; gd.owner_world = k.owner_world; gd.win_a = win_a; gd.win_b = win_b; gd.nwin = k.nwin;
-    gd.out = gsum;
+    gd.out = guard + kGuardKeysDb;
     hipLaunchKernelGGL(k_guard_db, dim3((unsigned)grid_for(ctx, records, 256, 8), routed ? 2u : 1u), dim3(256), 0, ctx->stream, gd);
     GuardRecArgs gr{};
     for (int i = 0; i < 2; ++i) { gr.rec[i] = j.out[i]; gr.total[i] = j.total[i]; }
-    gr.out = gsum + 3;
+    gr.out = guard + kGuardKeysRec;
     hipLaunchKernelGGL(k_guard_records, dim3((unsigned)grid_for(ctx, records, 256, 8), 2u), dim3(256), 0, ctx->stream, gr);
     ctx->guard_keys_pending = true;
   }
@@ -1217,9 +1215,9 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   }
   g.pair_big = kPairBigCap; g.group_cap = kStreamGroupCap;   // (the tiled pair kernel serves every group up to that)
   g.flags = dflags;
-  g.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
+  g.guard = k.guard;
   g.over = static_cast<uint8_t *>(ctx->d_stream[kSbOver].ptr);
-  swa_t0(ctx, 10);
+  swa_t0(ctx, kTimeGroups);
   {
     if (!ctx->g1_lds_opt_in) {
       // (128 KB of dynamic LDS: above the 64 KB a kernel gets unasked.  The attribute belongs to the function ON A DEVICE:
@@ -1229,12 +1227,11 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     }
     hipLaunchKernelGGL(k_group1, dim3((unsigned)std::min<uint64_t>(buckets, (uint64_t)ctx->num_cus), 2), dim3(kG1Threads), kG1LdsBytes, ctx->stream, g);
   }
-  swa_t1(ctx, 10);                                            // (slot 10: k_group1 alone; the work lists below count in slot 7, the whole build)
+  swa_t1(ctx, kTimeGroups);                                   // (k_group1 alone; the work lists below count in kTimeIndex, the whole build)
 
   // ---- work lists
   FlatScanArgs f{};
   ListArgs la{};
-  auto * acounters = static_cast<uint32_t *>(ctx->d_acounters.ptr);
   for (int i = 0; i < 2; ++i) {
     f.v[i] = g.g[i].kind_cnt; f.units[i] = nullptr; f.fixed[i] = (uint64_t)kListsPerIndex * buckets + 1;
     f.partial[i] = j.partial[i]; f.total[i] = reinterpret_cast<uint32_t *>(scal + 10 + i);
@@ -1242,7 +1239,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     x.items_tmp = g.g[i].items_tmp; x.bstart = g.g[i].bstart; x.kind_pos = g.g[i].kind_cnt; x.buckets = (uint32_t)buckets;
     x.l.items = static_cast<swa_item *>(ctx->d_aitems[i].ptr);
     x.l.region = regions;
-    x.l.counters = acounters + kCounterBase + (uint32_t)i * kWidthClasses * 8u;
+    x.l.counters = st->counters + kCounterBase + (uint32_t)i * kWidthClasses * 8u;
     x.l.pair_big = g.pair_big;
   }
   const dim3 grid_k((unsigned)std::min<uint64_t>(((uint64_t)kListsPerIndex * buckets + kFlatChunk) / kFlatChunk, (uint64_t)ctx->num_cus * 8), 2);
@@ -1298,21 +1295,20 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   j.ctile[0] = static_cast<uint32_t *>(ctx->d_stream[kSbTile].ptr);
   j.starts[0] = static_cast<uint64_t *>(ctx->d_stream[kSbStart].ptr);
   j.partial[0] = static_cast<uint32_t *>(ctx->d_stream[kSbPartial].ptr);
-  auto * extra = static_cast<uint64_t *>(ctx->d_status.ptr) + 48;   // (status block, bytes [384, 512): [0] last CSR offset [1] links sorted)
-  j.total[0] = reinterpret_cast<uint32_t *>(extra + 1);
+  j.total[0] = &swa_status(ctx)->links_sorted;
   j.starts_stride = e_start + 2;
-  swa_t0(ctx, 13);
+  swa_t0(ctx, kTimeLinkPartition);
   SWA_TRY(run_partition(ctx, j));
-  swa_t1(ctx, 13);
+  swa_t1(ctx, kTimeLinkPartition);
   CsrArgs c{};
   c.links = j.out[0]; c.bstart = j.bstart[0]; c.buckets = j.buckets; c.r = r; c.first = first; c.count = count;
   c.offsets = d_offsets; c.neighbours = d_neighbours; c.cap = d_neighbours != nullptr ? cap : 0;
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbHeavy], ((uint64_t)j.buckets + 2) * sizeof(uint32_t)));
   c.heavy = static_cast<uint32_t *>(ctx->d_stream[kSbHeavy].ptr) + 1;
   c.heavy_count = static_cast<uint32_t *>(ctx->d_stream[kSbHeavy].ptr);
-  c.end_copy = extra;
+  c.end_copy = &swa_status(ctx)->csr_end;
   SWA_HIP(ctx, hipMemsetAsync(c.heavy_count, 0, sizeof(uint32_t), ctx->stream));
-  swa_t0(ctx, 14);
+  swa_t0(ctx, kTimeCsrRows);
   // (as many workgroups as are resident together — every wave walks its share of the buckets; a grid of 8 a CU ran a second,
   // partly empty round behind the first)
   static const int csr_per_cu[2] = {
@@ -1322,7 +1318,7 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   if (r <= 8) { hipLaunchKernelGGL(k_csr_bucket<8>, cgrid, dim3(256), 0, ctx->stream, c); }
   else { hipLaunchKernelGGL(k_csr_bucket<9>, cgrid, dim3(256), 0, ctx->stream, c); }
   hipLaunchKernelGGL(k_csr_bucket_big, dim3((unsigned)ctx->num_cus * 4), dim3(256), 0, ctx->stream, c);
-  swa_t1(ctx, 14);
+  swa_t1(ctx, kTimeCsrRows);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
 }
@@ -1387,13 +1383,15 @@ static uint32_t seg_count(const swa_ctx * ctx) { return (uint32_t)ctx->num_cus *
 // anchored network over [first, first+count): per pass and width class the pair kernels over that class's work lists,
 // then the seeds (or halves of seeds) left to the plain kernel; links in the per-wave segments
 static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count) {
-  // d_acounters: [2] fallback seeds [8 + 2 (4 pass + class) + {0, 1}] work counters of the 65..256 groups / of the tiled kernel
-  // [kCounterBase + 8 (4 index + class) + kind] the lists of k_group_lists (made at index build, not cleared here)
-  auto * acounters = static_cast<uint32_t *>(ctx->d_acounters.ptr);
+  // (the status block's counters from kCounterBase on — the lists of k_group_lists — were made at index build: not cleared here)
+  swa_status_block * st = swa_status(ctx);
+  uint32_t * acounters = st->counters;
   SWA_TRY(swa_reserve(ctx, ctx->d_afallback, (2ull * count + 16) * sizeof(swa_fallback)));
   ClearList clears{};
-  clear_add(clears, ctx->d_stats.ptr, 16 * sizeof(uint64_t));
-  clear_add(clears, static_cast<uint64_t *>(ctx->d_guard.ptr) + 8, 8 * sizeof(uint64_t));   // the guard's counters of this network call
+  clear_add(clears, st->stats, sizeof(st->stats));
+  // the guard's counters of this network call — and with kGuardMisfiled what k_group1 counted into the same word
+  // (kGuardBucketTotal) while the index was built: that count lives from the build to this clear and is never read
+  clear_add(clears, st->guard + kGuardCall, (kGuardKeys - kGuardCall) * sizeof(uint64_t));
   clear_add(clears, acounters, kCounterBase * sizeof(uint32_t));
   clear_add(clears, ctx->d_seg_fill.ptr, 3ull * seg_count(ctx) * sizeof(uint32_t));   // segment fills | members staged, per pass
   // work counters of k_d1_group_pairs (per pass and class): 2^shard_bits of them, kSchedStride entries apart
@@ -1408,14 +1406,14 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   SWA_TRY(clear_launch(ctx, clears));
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const uint32_t maxwords = (ctx->db.longest + 31u) >> 5;
-  swa_t0(ctx, 3);
+  swa_t0(ctx, kTimeNetwork);
   const bool window_mode = ctx->anchor_a != 0 || ctx->anchor_b != 0;
   uint64_t item_room = 0;
   const ListRegions regions = list_regions(ctx, &item_room);
   if (item_room != ctx->list_regions_items) { return swa_fail_msg(ctx, SWA_E_ARG, "d=1 network: the work lists in place were laid out for another database"); }
   const int nwin = (int)(ctx->anchor_w / 32u);
   for (int pass = 0; pass < 2; ++pass) {
-    swa_t0(ctx, 11 + pass);
+    swa_t0(ctx, kTimePass + pass);
     AnchorArgs a{};
     a.pass = pass;
     a.no_cluster_breaking = ncb;
@@ -1428,8 +1426,8 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
     a.win_word_b = ctx->anchor_b / 32u;
     a.window_mode = window_mode ? 1u : 0u;
     a.seg_staged = static_cast<uint32_t *>(ctx->d_seg_fill.ptr) + (uint64_t)(1 + pass) * seg_count(ctx);
-    a.guard = static_cast<unsigned long long *>(ctx->d_guard.ptr);
-    a.flags = static_cast<uint32_t *>(ctx->d_flags.ptr);
+    a.guard = reinterpret_cast<unsigned long long *>(st->guard);
+    a.flags = st->flags;
     a.shard_bits = shard_bits;
     a.ids = static_cast<const uint32_t *>(ctx->d_stream[kSbMembers + pass].ptr);
     a.lines = static_cast<const uint4 *>(ctx->d_stream[kSbLines].ptr);
@@ -1446,8 +1444,8 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
       a.pair_counters = acounters + kCounterBase + pc * 8u;
       a.items = a.pair_items + regions.at[cls][kPairClasses + 1u];
       a.item_count = a.pair_counters + kPairClasses + 1u;
-      a.sched_big = acounters + 8 + 2 * pc;
-      a.sched_tiled = acounters + 9 + 2 * pc;
+      a.sched_big = acounters + kCounterSchedBig + 2 * pc;
+      a.sched_tiled = acounters + kCounterSchedTiled + 2 * pc;
       a.sched_wide = static_cast<uint32_t *>(ctx->d_stream[kSbSched].ptr) + ((uint64_t)pc << shard_bits) * kSchedStride;
       // (the pair kernel hands its work out through counters: exactly the workgroups that are resident together, no second round;
       // no launch over lists the index build found empty)
@@ -1467,7 +1465,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
       if (any_pairs) { SWA_TRY(launch_group_pairs(ctx, pass, width, nwin, pgrid, a)); }
       if (have == nullptr || have[kPairClasses + 1u] != 0u) { SWA_TRY(launch_pairs_tiled(ctx, pass, width, nwin, ctx->num_cus * (cls <= 1u ? 8 : 4), a)); }
     }
-    swa_t1(ctx, 11 + pass);
+    swa_t1(ctx, kTimePass + pass);
     SWA_HIP(ctx, hipGetLastError());
   }
   // seeds (or halves of seeds) the anchored passes skipped (a lean build has made sure there are none: no sequence
@@ -1475,7 +1473,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   const bool use_member_table = ctx->member_index && !ctx->full_index;
   if (ctx->full_index || ctx->member_index) {
     hipLaunchKernelGGL(k_stream_fallback, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, first, count,
-                       static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr), static_cast<swa_fallback *>(ctx->d_afallback.ptr), acounters + 2,
+                       static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr), static_cast<swa_fallback *>(ctx->d_afallback.ptr), acounters + kCounterFallback,
                        ctx->owner_rank, ctx->owner_world, ctx->db.seqs, ctx->db.seq_off, anchor_minlen(ctx));
   }
   NetArgs f{};
@@ -1493,7 +1491,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   f.seg_cap = ctx->seg_cap;
   f.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
   f.fallback = static_cast<const swa_fallback *>(ctx->d_afallback.ptr);
-  f.fallback_count = acounters + 2;
+  f.fallback_count = acounters + kCounterFallback;
   f.aux = static_cast<const swa_aux *>(ctx->d_aux.ptr);
   f.owner_rank = 0; f.owner_world = 1;                       // the list already is this rank's share
   f.window_mode = window_mode ? 1u : 0u; f.win_word = ctx->anchor_a / 32u; f.anchor_w = ctx->anchor_w;
@@ -1505,7 +1503,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   if (!ctx->full_index && !ctx->member_index) { /* nothing to probe against */ }
   else if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
   else { hipLaunchKernelGGL((k_d1_probe<false, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
-  swa_t1(ctx, 3);
+  swa_t1(ctx, kTimeNetwork);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
 }
@@ -1534,7 +1532,7 @@ static int launch_seqhash(swa_ctx * ctx, const uint8_t * only = nullptr) {
   const uint32_t n = ctx->db.n;
   const size_t zbytes = 4ull * ctx->zobrist_len * sizeof(uint64_t);
   const bool zlds = zbytes <= kMaxZobristLds;
-  swa_t0(ctx, 0);
+  swa_t0(ctx, kTimeSeqhash);
   const int hgrid = grid_for(ctx, n, 256, 8);
   if (zlds) {
     hipLaunchKernelGGL(k_seqhash<true>, dim3(hgrid), dim3(256), zbytes, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
@@ -1546,7 +1544,7 @@ static int launch_seqhash(swa_ctx * ctx, const uint8_t * only = nullptr) {
                        static_cast<uint64_t *>(ctx->d_seqhash.ptr), static_cast<swa_aux *>(ctx->d_aux.ptr), ctx->anchor_w, only);
   }
   SWA_HIP(ctx, hipGetLastError());
-  swa_t1(ctx, 0);
+  swa_t1(ctx, kTimeSeqhash);
   return SWA_OK;
 }
 
@@ -1571,9 +1569,9 @@ static int ensure_full_index(swa_ctx * ctx) {
   SWA_TRY(swa_reserve(ctx, ctx->d_table, ctx->table_size * sizeof(swa_slot)));
   SWA_TRY(swa_reserve(ctx, ctx->d_bloom, ctx->bloom_words * sizeof(uint64_t)));
   SWA_TRY(swa_hash_sequences(ctx));
-  swa_t0(ctx, 1);
+  swa_t0(ctx, kTimeTable);
   SWA_TRY(swa_d1_rebuild_table(ctx, nullptr));
-  swa_t1(ctx, 1);
+  swa_t1(ctx, kTimeTable);
   ctx->full_index = true;
   return SWA_OK;
 }
@@ -1654,18 +1652,18 @@ static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbMBloom], words * sizeof(uint64_t)));
   auto * table = static_cast<swa_slot *>(ctx->d_stream[kSbMTable].ptr);
   auto * bloom = static_cast<uint64_t *>(ctx->d_stream[kSbMBloom].ptr);
-  swa_t0(ctx, 1);
+  swa_t0(ctx, kTimeTable);
   hipLaunchKernelGGL(k_table_clear, dim3(grid_for(ctx, slots, 256, 8)), dim3(256), 0, ctx->stream, table, slots, bloom, words);
   hipLaunchKernelGGL(k_table_insert, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_seqhash.ptr), n,
                      static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr), table, slots - 1, reinterpret_cast<unsigned long long *>(bloom), words - 1,
                      static_cast<const uint64_t *>(ctx->d_patterns.ptr));
-  swa_t1(ctx, 1);
-  swa_t0(ctx, 2);
+  swa_t1(ctx, kTimeTable);
+  swa_t0(ctx, kTimeDupCheck);
   if (dup_count != 0) {
     hipLaunchKernelGGL(k_dup_check, dim3(grid_for(ctx, dup_count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen,
-                       static_cast<const uint64_t *>(ctx->d_seqhash.ptr), dup_first, dup_count, table, slots - 1, static_cast<uint32_t *>(ctx->d_flags.ptr));
+                       static_cast<const uint64_t *>(ctx->d_seqhash.ptr), dup_first, dup_count, table, slots - 1, swa_status(ctx)->flags + kFlagDuplicates);
   }
-  swa_t1(ctx, 2);
+  swa_t1(ctx, kTimeDupCheck);
   SWA_HIP(ctx, hipGetLastError());
   ctx->mtable_size = slots;
   ctx->mbloom_words = words;
@@ -1682,7 +1680,6 @@ static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
 static int build_owned_index(swa_ctx * ctx, uint32_t first, uint32_t count, bool * needs_table, uint32_t * dups, uint32_t * oversized_mass = nullptr,
                              uint32_t * shortest = nullptr) {
   const uint32_t n = ctx->db.n;
-  auto * dflags = static_cast<uint32_t *>(ctx->d_flags.ptr);
   swa_lap(ctx, "(owned index starts)");
   // (no Zobrist table, no hash / XOR-stream arrays here: the pair route needs none of them — 240 MB of HBM at 10 M and an
   // upload with its synchronisation per build; the member table and the database-wide table prepare them when they are built)
@@ -1692,36 +1689,35 @@ static int build_owned_index(swa_ctx * ctx, uint32_t first, uint32_t count, bool
   // identical sequences is seen by exactly one rank); a single GPU honours the slice it was asked about
   const uint32_t dup_first = ctx->owner_world > 1 ? 0u : first, dup_count = ctx->owner_world > 1 ? n : count;
   // streaming build (d1_stream.inc): keys, partition, groups + work lists + identical sequences, all in one go
-  swa_t0(ctx, 7);
+  swa_t0(ctx, kTimeIndex);
   SWA_TRY(build_stream_index(ctx, dup_first, dup_count));
-  swa_t1(ctx, 7);
-  // [0] duplicates [1] order broken [2] a bucket's groups do not fit the table [3] a sequence too short for two windows
-  // [4] groups left to the plain kernel (oversized / a member too long) [5] their members [6] 0xFFFFFFFF - shortest sequence
-  // (ONE copy of the status block: the flags, and how long the work lists are — the network call then launches no kernel
-  // over an empty one)
+  swa_t1(ctx, kTimeIndex);
+  // (ONE copy of the status block up to the split cursors: the flags, and how long the work lists are — the network call
+  // then launches no kernel over an empty one)
   // (into the context's pinned mirror: a copy to pageable memory is staged by the runtime, ~15 us more per look)
-  auto * status = static_cast<uint32_t *>(ctx->h_status);
-  SWA_HIP(ctx, hipMemcpyAsync(status, ctx->d_status.ptr, 512 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  const swa_status_block * status = ctx->h_status;
+  SWA_HIP(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.ptr, offsetof(swa_status_block, cursors), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const uint32_t * flags = status;
-  *dups = flags[0];
-  memcpy(ctx->list_counts, status + 256 + kCounterBase, sizeof(ctx->list_counts));
+  const uint32_t * flags = status->flags;
+  *dups = flags[kFlagDuplicates];
+  memcpy(ctx->list_counts, status->counters + kCounterBase, sizeof(ctx->list_counts));
   ctx->list_counts_ready = true;
-  if (oversized_mass != nullptr) { *oversized_mass = flags[5]; }
-  if (shortest != nullptr) { *shortest = 0xFFFFFFFFu - flags[6]; }
-  if (flags[2] != 0) {                                      // a bucket with more distinct keys than the group kernel's table: finer
+  if (oversized_mass != nullptr) { *oversized_mass = flags[kFlagOverMass]; }
+  if (shortest != nullptr) { *shortest = 0xFFFFFFFFu - flags[kFlagShortest]; }
+  if (flags[kFlagKeyOverflow] != 0) {                       // a bucket with more distinct keys than the group kernel's table: finer
     if (ctx->stream_extra_bits >= 8) { return swa_fail_msg(ctx, SWA_E_DEVICE, "streaming index build: partition still too coarse"); }
     ctx->stream_extra_bits += 2;
-    SWA_HIP(ctx, hipMemsetAsync(dflags, 0, 16 * sizeof(uint32_t), ctx->stream));
+    SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags, 0, sizeof(status->flags), ctx->stream));
     return build_owned_index(ctx, first, count, needs_table, dups, oversized_mass, shortest);
   }
-  if (flags[1] != 0) { ctx->db_unordered = true; }
-  *needs_table = flags[1] != 0 || flags[3] != 0 || flags[4] != 0;
+  const bool unordered = flags[kFlagUnordered] != 0, unserved = flags[kFlagUnserved] != 0, oversized = flags[kFlagOversized] != 0;
+  if (unordered) { ctx->db_unordered = true; }
+  *needs_table = unordered || unserved || oversized;
   // (groups left to the plain kernel — and, on a single GPU, sequences too short for two windows — are the ONLY reason: a
   // table of their members alone serves it — build_member_index)
-  ctx->only_oversized = flags[1] == 0 && (flags[4] != 0 || flags[3] != 0) &&
-                        (flags[3] == 0 || (ctx->owner_world == 1u && ctx->route_ids[0] == nullptr && ctx->route_rec[0] == nullptr));
-  ctx->over_mass = flags[5];
+  ctx->only_oversized = !unordered && (oversized || unserved) &&
+                        (!unserved || (ctx->owner_world == 1u && ctx->route_ids[0] == nullptr && ctx->route_rec[0] == nullptr));
+  ctx->over_mass = flags[kFlagOverMass];
   return SWA_OK;
 }
 
@@ -1738,7 +1734,7 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
   ctx->full_index = false;
   ctx->member_index = false;
   ctx->anchor_a = ctx->anchor_b = 0;
-  for (int slot : {0, 1, 2, 7, 8, 9, 10, 15}) { ctx->ev_used[slot] = false; }   // phases this build does not run report 0
+  for (int slot : {kTimeSeqhash, kTimeTable, kTimeDupCheck, kTimeIndex, kTimeKeys, kTimeKeyPartition, kTimeGroups, kTimeLines}) { ctx->ev_used[slot] = false; }   // phases this build does not run report 0
   ctx->table_size = swa_hashtable_size(n);
   const uint64_t bloom_bytes = ctx->table_size < 8 ? 8 : ctx->table_size;   // bloompat.cc:100-113
   ctx->bloom_words = bloom_bytes >> 3;
@@ -1751,11 +1747,10 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));       // pat is a host temporary
     ctx->patterns_resident = true;
   }
-  SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stats, 16 * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_guard, 24 * sizeof(uint64_t)));
-  // (flags, stats and the guard's index / network counters lie together in the status block: one fill)
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_status.ptr, 0, 64 + 128 + 16 * sizeof(uint64_t), ctx->stream));
+  // (flags, stats and the guard's index / network counters lie together at the head of the status block: one fill, up to
+  // the guard's second opinion)
+  swa_status_block * st = swa_status(ctx);
+  SWA_HIP(ctx, hipMemsetAsync(st, 0, offsetof(swa_status_block, guard) + kGuardKeys * sizeof(uint64_t), ctx->stream));
   ctx->guard_index = false;
   ctx->anchor_w = 32;
   ctx->anchor_usable = anchor_applicable(ctx);
@@ -1785,7 +1780,7 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
       for (uint32_t w = sampled + 32u; 2u * w + kMinAnchoredLen <= shortest && w <= 96u; w += 32u) {
         ctx->anchor_a = ctx->anchor_b = w;
         ctx->anchor_w = 32;                                     // (moved windows: anchor_nwin_for)
-        SWA_HIP(ctx, hipMemsetAsync(ctx->d_flags.ptr, 0, 16 * sizeof(uint32_t), ctx->stream));
+        SWA_HIP(ctx, hipMemsetAsync(st->flags, 0, sizeof(st->flags), ctx->stream));
         uint32_t m = 0;
         SWA_TRY(build_owned_index(ctx, first, count, &needs_table, &group_dups, &m));
         if (m < best_mass) { best_mass = m; best = w; }
@@ -1794,7 +1789,7 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
       if (ctx->anchor_a != best) {                            // (the last one tried was not the best: build that one again)
         ctx->anchor_a = ctx->anchor_b = best;
         ctx->anchor_w = best == sampled ? ctx->windows_w : 32u;
-        SWA_HIP(ctx, hipMemsetAsync(ctx->d_flags.ptr, 0, 16 * sizeof(uint32_t), ctx->stream));
+        SWA_HIP(ctx, hipMemsetAsync(st->flags, 0, sizeof(st->flags), ctx->stream));
         SWA_TRY(build_owned_index(ctx, first, count, &needs_table, &group_dups));
       }
     }
@@ -1806,34 +1801,34 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
       SWA_TRY(build_member_index(ctx, ctx->owner_world > 1 ? 0u : first, ctx->owner_world > 1 ? n : count));
       owned_ok = true;
       // (the member table's own search for identical sequences may have raised the flag since the build looked at it)
-      auto * mirror = static_cast<uint32_t *>(ctx->h_status);
-      SWA_HIP(ctx, hipMemcpyAsync(mirror, ctx->d_flags.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+      uint32_t * mirror = &ctx->h_status->flags[kFlagDuplicates];
+      SWA_HIP(ctx, hipMemcpyAsync(mirror, st->flags + kFlagDuplicates, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      group_dups = mirror[0];
+      group_dups = *mirror;
     }
-    if (!owned_ok) { SWA_HIP(ctx, hipMemsetAsync(ctx->d_flags.ptr, 0, 16 * sizeof(uint32_t), ctx->stream)); }
+    if (!owned_ok) { SWA_HIP(ctx, hipMemsetAsync(st->flags, 0, sizeof(st->flags), ctx->stream)); }
   }
   uint32_t flag = group_dups;
   if (!owned_ok) {
     SWA_TRY(ensure_full_index(ctx));
-    swa_t0(ctx, 2);
+    swa_t0(ctx, kTimeDupCheck);
     if (count > 0) {
       hipLaunchKernelGGL(k_dup_check, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                          ctx->db.seqlen, static_cast<const uint64_t *>(ctx->d_seqhash.ptr), first, count,
                          static_cast<const swa_slot *>(ctx->d_table.ptr), ctx->table_size - 1,
-                         static_cast<uint32_t *>(ctx->d_flags.ptr));
+                         swa_status(ctx)->flags + kFlagDuplicates);
     }
     SWA_HIP(ctx, hipGetLastError());
-    swa_t1(ctx, 2);
+    swa_t1(ctx, kTimeDupCheck);
     if (ctx->anchor_usable) {
       SWA_TRY(launch_abundance_rank(ctx));
       SWA_HIP(ctx, hipGetLastError());
     }
-    uint32_t flags[2] = {0, 0};                             // [0] duplicates [1] abundances not in descending order
-    SWA_HIP(ctx, hipMemcpyAsync(flags, ctx->d_flags.ptr, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
+    uint32_t flags[kFlagUnordered + 1] = {};                // duplicates, abundances not in descending order
+    SWA_HIP(ctx, hipMemcpyAsync(flags, st->flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    flag |= flags[0];
-    if (flags[1] != 0) { ctx->anchor_usable = false; ctx->db_unordered = true; }   // the anchored passes rely on the db order
+    flag |= flags[kFlagDuplicates];
+    if (flags[kFlagUnordered] != 0) { ctx->anchor_usable = false; ctx->db_unordered = true; }   // the anchored passes rely on the db order
   }
   ctx->d1_ready = true;
   if (has_duplicates != nullptr) { *has_duplicates = flag != 0 ? 1 : 0; }
@@ -1880,14 +1875,14 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
   a.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
   a.owner_rank = ctx->owner_rank; a.owner_world = ctx->owner_world;
   a.anchor_w = 32;
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 16 * sizeof(uint64_t), ctx->stream));
+  SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->stats, 0, sizeof(swa_status_block::stats), ctx->stream));
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const size_t lds = network_lds_bytes(ctx, zlds);
   const int grid = grid_for(ctx, count, kWaves, 8);
-  swa_t0(ctx, 3);
+  swa_t0(ctx, kTimeNetwork);
   if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a); }
   else { hipLaunchKernelGGL((k_d1_probe<false, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a); }
-  swa_t1(ctx, 3);
+  swa_t1(ctx, kTimeNetwork);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
 }
@@ -1902,19 +1897,22 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
 // and, for every CSR result whatever the route (csr_check),
 //   links in the wave segments        =  links the partition sorted  =  the last CSR offset
 // A mismatch is SWA_E_INTERNAL — never a short network.
-static int guard_check(swa_ctx * ctx, const uint64_t * g, const uint64_t * got) {
+static int guard_check(swa_ctx * ctx, const swa_status_block & status) {
+  const uint64_t * g = status.guard, * staged = status.stats + kStatSeg + kSegStaged;
+  const uint64_t * made = g + kGuardMade, * listed = g + kGuardListed, * single = g + kGuardSingleton, * over = g + kGuardOversized;
   char msg[256];
-  if (g[10] != 0) {
-    snprintf(msg, sizeof(msg), "d=1 guard: %llu member(s) filed under an anchor key that is not theirs", (unsigned long long)g[10]);
+  if (g[kGuardMisfiled] != 0) {
+    snprintf(msg, sizeof(msg), "d=1 guard: %llu member(s) filed under an anchor key that is not theirs", (unsigned long long)g[kGuardMisfiled]);
     return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
   }
   if (ctx->stream_index && ctx->guard_keys_pending) {
     ctx->guard_keys_pending = false;
     for (int i = 0; i < 2; ++i) {
-      if (g[16 + i] != g[19 + i]) {
+      const uint64_t from_db = g[kGuardKeysDb + i], from_records = g[kGuardKeysRec + i];
+      if (from_db != from_records) {
         snprintf(msg, sizeof(msg), "d=1 guard: the %s derived from the amplicon lines are not the ones the packed database gives (%016llx / %016llx)",
-                 i == 0 ? "prefix-side key records" : "suffix-side key records", (unsigned long long)g[19 + i],
-                 (unsigned long long)g[16 + i]);
+                 i == 0 ? "prefix-side key records" : "suffix-side key records", (unsigned long long)from_records,
+                 (unsigned long long)from_db);
         return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
       }
     }
@@ -1922,13 +1920,13 @@ static int guard_check(swa_ctx * ctx, const uint64_t * g, const uint64_t * got) 
   }
   if (ctx->stream_index && ctx->guard_index) {
     for (int i = 0; i < 2; ++i) {
-      if (g[i] != g[2 + i] + g[4 + i] + g[6 + i]) {
-        snprintf(msg, sizeof(msg), "d=1 guard: index %d has %llu key records but %llu + %llu + %llu grouped members", i, (unsigned long long)g[i],
-                 (unsigned long long)g[2 + i], (unsigned long long)g[4 + i], (unsigned long long)g[6 + i]);
+      if (made[i] != listed[i] + single[i] + over[i]) {
+        snprintf(msg, sizeof(msg), "d=1 guard: index %d has %llu key records but %llu + %llu + %llu grouped members", i, (unsigned long long)made[i],
+                 (unsigned long long)listed[i], (unsigned long long)single[i], (unsigned long long)over[i]);
         return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
       }
-      if (got[2 + i] != g[2 + i]) {
-        snprintf(msg, sizeof(msg), "d=1 guard: pass %d staged %llu members of %llu listed", i, (unsigned long long)got[2 + i], (unsigned long long)g[2 + i]);
+      if (staged[i] != listed[i]) {
+        snprintf(msg, sizeof(msg), "d=1 guard: pass %d staged %llu members of %llu listed", i, (unsigned long long)staged[i], (unsigned long long)listed[i]);
         return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
       }
     }
@@ -1949,10 +1947,10 @@ static int csr_check(swa_ctx * ctx, uint64_t csr_end, uint32_t links_sorted, uin
 static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, uint32_t count, uint64_t * d_offsets,
                        uint32_t * d_neighbours, uint64_t * d_edge_list, uint64_t cap, uint64_t * total) {
   SWA_HIP(ctx, hipSetDevice(ctx->device));
+  swa_status_block * st = swa_status(ctx);
   // hits leave the kernels through per-wave segments of the edge buffer (no shared counter)
   const uint32_t nseg = (uint32_t)ctx->num_cus * 8u * kWaves;          // >= waves of any launch below
   SWA_TRY(swa_reserve(ctx, ctx->d_seg_fill, 3ull * nseg * sizeof(uint32_t)));   // fills | members staged, pass 0 | pass 1
-  SWA_TRY(swa_reserve(ctx, ctx->d_guard, 24 * sizeof(uint64_t)));
   if (ctx->seg_cap == 0) {
     ctx->seg_cap = 512;
     while (ctx->seg_cap < 8ull * count / nseg) { ctx->seg_cap <<= 1; }
@@ -1970,22 +1968,22 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     if (ctx->anchor_usable) {
       if (!(ctx->anchor_ready && ctx->stream_index)) {
         // (the streaming index serves any query range; it is rebuilt when the owner changed)
-        swa_t0(ctx, 7);
+        swa_t0(ctx, kTimeIndex);
         SWA_TRY(launch_abundance_rank(ctx));
-        // ([2] duplicates [3] seeds left to the plain kernel [4] oversized groups [5] their members: the previous owner's
-        // values must not survive into this owner's build — [3] is only ever set, [4] / [5] accumulate)
-        SWA_HIP(ctx, hipMemsetAsync(static_cast<uint32_t *>(ctx->d_flags.ptr) + 2, 0, 5 * sizeof(uint32_t), ctx->stream));
+        // (kFlagKeyOverflow .. kFlagShortest, what the streaming build raises: the previous owner's values must not survive
+        // into this owner's build — kFlagUnserved is only ever set, kFlagOversized / kFlagOverMass accumulate)
+        SWA_HIP(ctx, hipMemsetAsync(st->flags + kFlagKeyOverflow, 0, (kFlagsD1 - kFlagKeyOverflow) * sizeof(uint32_t), ctx->stream));
         SWA_TRY(build_stream_index(ctx, 0, 0));
-        swa_t1(ctx, 7);
+        swa_t1(ctx, kTimeIndex);
         // The index of another owner (swa_d1_set_ownership after the build): the member table and its Bloom filter hold the
         // previous owner's oversized groups, so they are dropped, and whatever this owner's groups leave to the plain kernel
-        // ([3] seeds the anchored passes cannot serve, [4] oversized groups) gets the database-wide table
+        // (kFlagUnserved, kFlagOversized) gets the database-wide table
         if (!ctx->full_index) {
-          uint32_t fl[6] = {};
-          SWA_HIP(ctx, hipMemcpyAsync(fl, ctx->d_flags.ptr, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
+          uint32_t fl[kFlagOverMass + 1] = {};
+          SWA_HIP(ctx, hipMemcpyAsync(fl, st->flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
           SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
           ctx->member_index = false;
-          if (fl[3] != 0 || fl[4] != 0) { SWA_TRY(ensure_full_index(ctx)); }
+          if (fl[kFlagUnserved] != 0 || fl[kFlagOversized] != 0) { SWA_TRY(ensure_full_index(ctx)); }
         }
       }
       SWA_TRY(launch_network_anchored(ctx, no_cluster_breaking, first, count));
@@ -1995,13 +1993,13 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       SWA_TRY(launch_network(ctx, no_cluster_breaking, first, count));
     }
     hipLaunchKernelGGL(k_seg_reduce, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
-                       nseg, static_cast<unsigned long long *>(ctx->d_stats.ptr) + 8);
+                       nseg, reinterpret_cast<unsigned long long *>(st->stats) + kStatSeg);
     const bool check_unserved = ctx->anchor_usable && !ctx->full_index && !ctx->member_index;
     // CSR assembly is enqueued right behind, before the host looks at the totals: every kernel
     // below guards its writes with `cap` / the segment capacity, so a run that turns out to
     // need bigger segments or a bigger neighbour buffer has only wasted these launches.
     // Offsets are always complete; neighbours only if they fit.
-    swa_t0(ctx, 4);
+    swa_t0(ctx, kTimeCsr);
     if (d_edge_list != nullptr) {
       SWA_TRY(swa_reserve(ctx, ctx->d_seg_base, uint64_t(nseg) * sizeof(uint64_t)));
       hipLaunchKernelGGL(k_seg_bases, dim3(1), dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr), nseg,
@@ -2015,25 +2013,22 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap));
     }
     SWA_HIP(ctx, hipGetLastError());
-    swa_t1(ctx, 4);
-    // ONE copy of the status block's first 512 bytes: flags | stats (links, fullest segment, members staged) | the guard's
-    // counters | last CSR offset, links sorted
-    auto * status = static_cast<uint64_t *>(ctx->h_status);   // (the pinned mirror)
-    SWA_HIP(ctx, hipMemcpyAsync(status, ctx->d_status.ptr, 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    uint32_t * unserved_at = reinterpret_cast<uint32_t *>(status + 64);
-    *unserved_at = 0;                                        // fallback seeds listed while there is no table to serve them
+    swa_t1(ctx, kTimeCsr);
+    // ONE copy of the status block's head, up to the host's own scratch: flags | stats (links, fullest segment, members
+    // staged) | the guard's counters | last CSR offset, links sorted
+    swa_status_block * status = ctx->h_status;               // (the pinned mirror)
+    SWA_HIP(ctx, hipMemcpyAsync(status, st, offsetof(swa_status_block, host_unserved), hipMemcpyDeviceToHost, ctx->stream));
+    status->host_unserved = 0;                               // fallback seeds listed while there is no table to serve them
     if (check_unserved) {
-      SWA_HIP(ctx, hipMemcpyAsync(unserved_at, static_cast<uint32_t *>(ctx->d_acounters.ptr) + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+      SWA_HIP(ctx, hipMemcpyAsync(&status->host_unserved, st->counters + kCounterFallback, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t unserved = *unserved_at;
-    const uint64_t * got = status + 8 + 8;                    // d_stats[8 ..]: links, fullest segment, members staged by pass
-    const uint64_t * guard = status + 24;
-    const uint32_t anchor_overflow = reinterpret_cast<const uint32_t *>(status)[2];
-    const uint64_t csr_end = status[48];
-    const uint32_t links_sorted = (uint32_t)status[49];
+    const uint32_t unserved = status->host_unserved;
+    const uint64_t * seg = status->stats + kStatSeg;          // what k_seg_reduce made of the segments
+    const uint64_t fullest = seg[kSegFullest];
+    const uint32_t anchor_overflow = status->flags[kFlagKeyOverflow];
     const bool guarded = ctx->anchor_usable;
-    n_edges = got[0];
+    n_edges = seg[kSegLinks];
     if (guarded && anchor_overflow != 0) {
       // a bucket of the index rebuilt above held more distinct keys than the group kernel's table: partition finer, again
       ctx->stream_extra_bits = std::min<uint32_t>(ctx->stream_extra_bits + 2, 8);
@@ -2044,22 +2039,22 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       SWA_TRY(ensure_full_index(ctx));
       continue;
     }
-    if (d_edge_list == nullptr && got[1] <= ctx->seg_cap && n_edges > stream_link_cap) {
+    if (d_edge_list == nullptr && fullest <= ctx->seg_cap && n_edges > stream_link_cap) {
       // more links than the internal link buffers of the CSR stage hold (a first call with a small `cap`): bigger, again
       stream_link_cap = n_edges + 1024;
       continue;
     }
-    if (got[1] <= ctx->seg_cap) {
+    if (fullest <= ctx->seg_cap) {
       clean = true;
-      if (guarded) { SWA_TRY(guard_check(ctx, guard, got)); }
-      if (d_edge_list == nullptr) { SWA_TRY(csr_check(ctx, csr_end, links_sorted, n_edges)); }
-      twins = guarded && reinterpret_cast<const uint32_t *>(status)[0] != 0u;     // (flags[0]: the prefix pass met two identical sequences)
+      if (guarded) { SWA_TRY(guard_check(ctx, *status)); }
+      if (d_edge_list == nullptr) { SWA_TRY(csr_check(ctx, status->csr_end, status->links_sorted, n_edges)); }
+      twins = guarded && status->flags[kFlagDuplicates] != 0u;   // (the prefix pass met two identical sequences)
       break;
     }
     // one wave found more hits than its segment holds: grow the segments and run again (rare).
     // The small-group passes hand out work dynamically, so a wave's fill differs from run to run:
     // twice the observed maximum, not just the maximum
-    while (ctx->seg_cap < 2 * got[1]) { ctx->seg_cap <<= 1; }
+    while (ctx->seg_cap < 2 * fullest) { ctx->seg_cap <<= 1; }
   }
   if (!clean) {
     // counts[] / offsets include links the segment guards dropped: never hand that out as a result
@@ -2174,8 +2169,8 @@ extern "C" int swa_d1_links_split(swa_ctx * ctx, const uint64_t * d_links, uint6
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SWA_OK;
   }
-  // (the runs' cursors: bytes [2048, 2048 + 8 world) of the status block — swa_internal.h)
-  auto * cursor = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(ctx->d_status.ptr) + 2048);
+  static_assert(kRouteMaxWorld * sizeof(uint64_t) <= sizeof(swa_status_block::cursors), "a run cursor for every rank");
+  auto * cursor = reinterpret_cast<unsigned long long *>(swa_status(ctx)->cursors);
   SWA_HIP(ctx, hipMemsetAsync(cursor, 0, (uint64_t)world * sizeof(uint64_t), ctx->stream));
   a.head = (uint32_t)((reinterpret_cast<uintptr_t>(d_links) >> 3) & 1u);
   a.links = reinterpret_cast<const unsigned long long *>(d_links) - a.head;
@@ -2190,7 +2185,7 @@ extern "C" int swa_d1_links_split(swa_ctx * ctx, const uint64_t * d_links, uint6
   hipLaunchKernelGGL(k_links_split<true>, grid, dim3(kSplitThreads), 0, ctx->stream, a);
   SWA_HIP(ctx, hipGetLastError());
   // ONE read, of the links no rank owns, into the pinned mirror of the status block: the counts are final when this returns
-  auto * beyond = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(ctx->h_status) + 2048);
+  uint64_t * beyond = ctx->h_status->cursors;
   SWA_HIP(ctx, hipMemcpyAsync(beyond, d_counts + world, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (*beyond != 0) {
@@ -2208,7 +2203,6 @@ extern "C" int swa_d1_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count,
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_route_slice: bad argument (1..64 ranks)");
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
   SWA_TRY(ensure_anchor_windows(ctx));
   SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, (2ull * world + 1) * sizeof(uint32_t), ctx->stream));
   if (count != 0) {
@@ -2251,7 +2245,6 @@ extern "C" int swa_d1_route_slice_records(swa_ctx * ctx, uint32_t first, uint32_
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_route_slice_records: bad argument (1..64 ranks)");
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
   SWA_TRY(ensure_anchor_windows(ctx));
   SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, (2ull * world + 1) * sizeof(uint32_t), ctx->stream));
   if (count != 0) {
@@ -2331,7 +2324,7 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
     size_t need = 0;
     if (what == 10 || what == 11) { from = ctx->d_stream[kSbMembers + (what - 10)].ptr; need = uint64_t(ctx->db.n) * sizeof(uint32_t); }
     else if (what == 12 || what == 13) { from = ctx->d_aitems[what - 12].ptr; need = ctx->list_regions_items * sizeof(swa_item); }
-    else if (what == 14) { from = ctx->d_acounters.ptr; need = kCounterWords * sizeof(uint32_t); }
+    else if (what == 14) { from = swa_status(ctx)->counters; need = kCounterWords * sizeof(uint32_t); }
     else if (what == 15) { from = ctx->d_stream[kSbLines].ptr; need = uint64_t(ctx->db.n) * ctx->lines_quads * 16u; }
     else if (what == 16) {                                    // (host-side facts: where the lists lie, how wide a line is)
       uint64_t total = 0;
@@ -2603,7 +2596,7 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     SWA_TRY(ensure_lines(ctx));
   }
   JoinTable jt = join_table(ctx, asize_max, n, 3u);
-  swa_t0(ctx, 5);
+  swa_t0(ctx, kTimePairs);
   for (int attempt = 0; attempt < 6; ++attempt) {
     SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->fast_pair_cap * sizeof(uint64_t)));
     SWA_HIP(ctx, hipMemsetAsync(fc + 5, 0, sizeof(uint64_t), ctx->stream));
@@ -2612,11 +2605,11 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     for (int type = 0; type < 3; ++type) {
       // one membership a light amplicon in the prefix / suffix groups, three (the middle window at 39, 40, 41) in the middle ones
       jt = join_table(ctx, type == 2 ? asize_max : asize_ends, n, type == 2 ? 3u : 1u);
-      uint32_t * item_counter = jt.flags + 2 + type;           // (one a type: the pair kernel of the type before still reads its own)
+      uint32_t * item_counter = jt.flags + kJoinItemCount + type;   // (one a type: the pair kernel of the type before still reads its own)
       FastGroupArgs g{};
       g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen;
       g.role = static_cast<const uint8_t *>(ctx->d_frole.ptr); g.n = n; g.max_len = plan.max_len;
-      g.keys = jt.keys; g.cnt_l = jt.cnt_a; g.cnt_h = jt.cnt_b; g.amask = jt.asize - 1; g.lslot = jt.aslot; g.hslot = jt.bslot; g.overflow = jt.flags;
+      g.keys = jt.keys; g.cnt_l = jt.cnt_a; g.cnt_h = jt.cnt_b; g.amask = jt.asize - 1; g.lslot = jt.aslot; g.hslot = jt.bslot; g.overflow = jt.flags + kJoinKeyOverflow;
       // a group needs a light and a heavy amplicon: l h >= 1
       SWA_TRY(join_run<FastTiles>(ctx, jt, 1u, item_counter, item_cap, [&](dim3 gn, dim3 b) {
         if (type == 0) { hipLaunchKernelGGL(k_fg_light<0>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<0>, gn, b, 0, ctx->stream, g); }
@@ -2655,8 +2648,8 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_d1_fastidious: pair list keeps overflowing"); }
     ctx->fast_pair_cap = got + got / 8 + 1024;               // the count of a complete run: size for it (+ slack: none needed, it is exact)
   }
-  swa_t1(ctx, 5);
-  swa_t0(ctx, 6);
+  swa_t1(ctx, kTimePairs);
+  swa_t0(ctx, kTimeAlign);
   if (npairs != 0) {
     FastCountArgs c{};
     c.seqs = ctx->db.seqs; c.seq_off = ctx->db.seq_off; c.seqlen = ctx->db.seqlen;
@@ -2683,7 +2676,7 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     }
     SWA_HIP(ctx, hipGetLastError());
   }
-  swa_t1(ctx, 6);
+  swa_t1(ctx, kTimeAlign);
   return SWA_OK;
 }
 
@@ -2747,12 +2740,11 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   SWA_TRY(swa_reserve(ctx, ctx->d_list_a, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_list_b, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
   SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, role.get(), n, hipMemcpyHostToDevice, ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_graft.ptr, 0xFF, uint64_t(n) * sizeof(uint32_t), ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_fcounters.ptr, 0, 16 * sizeof(uint64_t), ctx->stream));
   auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
-  for (int slot : {5, 6}) { ctx->ev_used[slot] = false; }
+  for (int slot : {kTimePairs, kTimeAlign}) { ctx->ev_used[slot] = false; }
 
   // the log's variant totals, and the amplicons that can be part of a pair the pair route does not take
   hipLaunchKernelGGL(k_fast_variant_totals, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,

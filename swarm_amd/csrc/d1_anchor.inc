@@ -74,8 +74,6 @@ __host__ __device__ inline int width_words(uint32_t cls) { return cls == 0u ? 5 
 // the groups of 65..pair_big (a workgroup each), one of 64-member row tiles of the larger ones (k_d1_pairs_tiled)
 constexpr uint32_t kListKinds = kPairClasses + 2;
 constexpr uint32_t kListsPerIndex = kWidthClasses * kListKinds;
-constexpr uint32_t kCounterBase = 64;       // d_acounters[kCounterBase + (index * kWidthClasses + class) * 8 + kind]: items in that list
-constexpr uint32_t kCounterWords = 256;
 struct ListRegions { uint64_t at[kWidthClasses][kListKinds + 1]; };   // first item of list (class, kind) in an index's item buffer; [.][kListKinds] = end
 constexpr uint32_t kSchedStride = 64;       // entries between two work counters of k_d1_group_pairs (own cache lines / channels)
 
@@ -280,7 +278,7 @@ __device__ __forceinline__ uint32_t pair_class(uint32_t g) {        // g in 2..6
 // rank[i] = index of the first amplicon with the same abundance as amplicon i.  The db order is
 // abundance descending (src/db.cc:388-413), so abundance[x] >= abundance[y] <=> rank[x] <= rank[y]
 // and the abundance rule of the network (algod1.cc:576-580) becomes a 32-bit compare that fits
-// next to the group table in LDS.  flags[1] is raised when the order does not hold (a caller
+// next to the group table in LDS.  flags[kFlagUnordered] is raised when the order does not hold (a caller
 // that uploaded some other order): the anchored passes are then not used.
 // Three streaming passes over tiles of 256 amplicons (a max-scan of "where did the current run of equal abundances
 // start"): the runs that start inside a tile, the tiles' last starts carried forward, the amplicons whose run
@@ -295,7 +293,7 @@ __global__ __launch_bounds__(256) void k_abundance_rank(const uint64_t * __restr
     const bool have = i < n;
     const uint64_t ab = have ? abundance[i] : 0ull;
     const uint64_t before = (have && i > 0u) ? abundance[i - 1u] : ~0ull;
-    if (have && before < ab) { atomicOr(flags + 1, 1u); }
+    if (have && before < ab) { atomicOr(flags + kFlagUnordered, 1u); }
     uint32_t start = (have && before != ab) ? i + 1u : 0u;     // 1 + position where a run starts, else 0
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -470,13 +468,13 @@ struct AnchorArgs {
   uint64_t pair_region[kPairClasses + 1];   // first item of each list,
   const uint32_t * pair_counters;   // items in each list
   uint32_t win_word_b;              // the suffix-side window ends win_b / 32 words before the end of the end-aligned words
-  // the guard (round 4): members staged per wave, this pass (one writer per entry, like seg_fill) and — [10] — members found
+  // the guard (round 4): members staged per wave, this pass (one writer per entry, like seg_fill) and — kGuardMisfiled — members found
   // in a group whose key is not theirs
   uint32_t * seg_staged;
   unsigned long long * guard;
   // identical sequences (round 6): two members of a prefix group whose every word agrees are the reference's "identical
   // sequences" (src/algod1.cc:1131-1150: fatal while it inserts) — seen by PASS 0 for two instructions a pair, where
-  // k_group1 ran a second hash table over fingerprints for them.  flags[0] |= 1 when one of the two is a seed of this call.
+  // k_group1 ran a second hash table over fingerprints for them.  flags[kFlagDuplicates] |= 1 when one of the two is a seed of this call.
   uint32_t * flags;
 };
 
@@ -740,7 +738,7 @@ __device__ __forceinline__ uint32_t pair_window_at(const AnchorArgs & a) {
 // two members with the same sequence: reported when one of them is a seed of this call (the reference's duplicate check is
 // per inserted amplicon, src/algod1.cc:1131-1150; a rank of a multi-GPU job answers for the groups it owns: first = 0, count = n)
 __device__ __forceinline__ void pair_twin(const AnchorArgs & a, uint32_t ida, uint32_t idb) {
-  if (ida != idb && ((ida - a.first < a.count) || (idb - a.first < a.count))) { atomicOr(a.flags, 1u); }
+  if (ida != idb && ((ida - a.first < a.count) || (idb - a.first < a.count))) { atomicOr(a.flags + kFlagDuplicates, 1u); }
 }
 
 // set bits of a ballot below this lane (v_mbcnt_lo / _hi: two instructions)
@@ -862,7 +860,7 @@ __global__ __launch_bounds__(kThreads) void k_d1_pairs_tiled(const AnchorArgs a)
     it = sh_it;
   }
   if (lane == 0u) { a.seg_fill[gwave] = seg_at; a.seg_staged[gwave] = staged_members; }
-  if (misfiled != 0u) { atomicAdd(a.guard + 10, (unsigned long long)misfiled); }
+  if (misfiled != 0u) { atomicAdd(a.guard + kGuardMisfiled, (unsigned long long)misfiled); }
 }
 
 // (W = 5: five workgroups per CU — 96 registers a lane; the prefix pass came out at 98 without being told)
@@ -1078,6 +1076,6 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
     more2 = more3; shift2 = shift3; item2 = item3;
   }
   if (lane == 0u) { a.seg_fill[gwave] = seg_at; a.seg_staged[gwave] = staged_members; }
-  if (misfiled != 0u) { atomicAdd(a.guard + 10, (unsigned long long)misfiled); }
+  if (misfiled != 0u) { atomicAdd(a.guard + kGuardMisfiled, (unsigned long long)misfiled); }
 }
 #endif  // SWA_ANCHOR_TYPES_ONLY

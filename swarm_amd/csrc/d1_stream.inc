@@ -284,11 +284,11 @@ struct KeyArgs {
   uint32_t owner_rank, owner_world;
   uint32_t win_a, win_b, minlen, window_mode;
   uint32_t nwin;                     // words (32 nt) per anchor window: 1, 2 or 4 (anchor_key)
-  uint32_t * flags;                  // [3] a seed the anchored passes cannot serve [6] 0xFFFFFFFF - shortest sequence
-  unsigned long long * guard;        // [which] records made for index `which` (the guard: what the groups must add up to)
+  uint32_t * flags;                  // the status block's: kFlagUnserved, kFlagOverMass, kFlagShortest
+  unsigned long long * guard;        // the status block's: [kGuardMade + which] records made for index `which` (what the groups must add up to)
   uint32_t fault;                    // test hook (SWA_D1_GUARD_TEST): 1 = a few suffix-side keys are wrong, 2 = a few records get lost
   // The too-short seeds (len < minlen) go to the enumerating kernel, and whatever is one edit from one of them is at most
-  // minlen long: those amplicons are marked (bit 2 of their `over` byte) and counted (flags[5]) as members of the table that
+  // minlen long: those amplicons are marked (bit 2 of their `over` byte) and counted (kFlagOverMass) as members of the table that
   // kernel probes — build_member_index — so that a few short reads do not cost the database-wide table (r05).  nullptr: off.
   uint8_t * mark_short;
   // k_keys<LQ, true>: the first partition level's histogram on the way (the flat count arrays of both indexes, layout of
@@ -385,10 +385,10 @@ __global__ __launch_bounds__(256) void k_keys(const KeyArgs a) {
     }
   }
   if (which_only < 0) {
-    if (unserved) { a.flags[3] = 1u; }
+    if (unserved) { a.flags[kFlagUnserved] = 1u; }
     if (a.mark_short != nullptr) {
       for (int o = 32; o > 0; o >>= 1) { marked += (uint32_t)__shfl_xor((int)marked, o, 64); }
-      if ((threadIdx.x & 63u) == 0u && marked != 0u) { atomicAdd(a.flags + 5, marked); }
+      if ((threadIdx.x & 63u) == 0u && marked != 0u) { atomicAdd(a.flags + kFlagOverMass, marked); }
     }
     // shortest sequence: one atomic per workgroup, and only if it can still raise the flag (a single address takes
     // ~88 atomics per microsecond: one per wave was 0.1 ms of nothing but that)
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256) void k_keys(const KeyArgs a) {
     __syncthreads();
     if (threadIdx.x == 0) {
       const uint32_t s4 = min(min(sh_short[0], sh_short[1]), min(sh_short[2], sh_short[3]));
-      if (s4 != 0xFFFFFFFFu && 0xFFFFFFFFu - s4 > a.flags[6]) { atomicMax(a.flags + 6, 0xFFFFFFFFu - s4); }
+      if (s4 != 0xFFFFFFFFu && 0xFFFFFFFFu - s4 > a.flags[kFlagShortest]) { atomicMax(a.flags + kFlagShortest, 0xFFFFFFFFu - s4); }
     }
   }
   // the guard: records made, per index (one atomic per workgroup and index)
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256) void k_keys(const KeyArgs a) {
       if ((threadIdx.x & 63u) == 0u && v != 0u) { atomicAdd(&sh_made[which], v); }
     }
     __syncthreads();
-    if (threadIdx.x < 2u && sh_made[threadIdx.x] != 0u) { atomicAdd(a.guard + threadIdx.x, (unsigned long long)sh_made[threadIdx.x]); }
+    if (threadIdx.x < 2u && sh_made[threadIdx.x] != 0u) { atomicAdd(a.guard + kGuardMade + threadIdx.x, (unsigned long long)sh_made[threadIdx.x]); }
   }
 }
 
@@ -891,10 +891,8 @@ struct GroupIdx {
 struct GroupArgs {
   GroupIdx g[kMaxIdx];
   uint32_t pair_big, group_cap;
-  uint32_t * flags;                  // [2] a bucket with more distinct keys than the table holds
-                                     // [4] oversized group [5] its members
-  unsigned long long * guard;        // the guard: [2 + which] members of listed groups, [4 + which] of singleton groups, [6 + which] of
-                                     // oversized groups, [10] a bucket whose groups do not add up to its records
+  uint32_t * flags;                  // the status block's: kFlagKeyOverflow, kFlagOversized, kFlagOverMass
+  unsigned long long * guard;        // the status block's: kGuardListed / kGuardSingleton / kGuardOversized + which, kGuardBucketTotal
   uint8_t * over;                    // per amplicon: bit `which` = member of an oversized group of that index
 };
 
@@ -1098,7 +1096,7 @@ __global__ __launch_bounds__(kG1Threads) void k_group1(const GroupArgs a) {
         atomicOr(reinterpret_cast<unsigned int *>(a.over + (id & ~3u)), (1u << which) << (8u * (id & 3u)));
       }
       if (tid < kListsPerIndex) { g.kind_cnt[tid * g.buckets + b] = 0u; }
-      if (tid == 0) { atomicOr(a.flags + 4, 1u); atomicAdd(a.flags + 5, c); atomicAdd(a.guard + 6u + which, (unsigned long long)c); }
+      if (tid == 0) { atomicOr(a.flags + kFlagOversized, 1u); atomicAdd(a.flags + kFlagOverMass, c); atomicAdd(a.guard + kGuardOversized + which, (unsigned long long)c); }
       continue;
     }
     const uint32_t cap = a.group_cap;
@@ -1169,7 +1167,7 @@ __global__ __launch_bounds__(kG1Threads) void k_group1(const GroupArgs a) {
     }
     __syncthreads();                                            // (every count is in)
     if (sh_fail != 0u) {                                        // more distinct keys than slots: the host partitions finer
-      if (tid == 0) { a.flags[2] = 1u; }
+      if (tid == 0) { a.flags[kFlagKeyOverflow] = 1u; }
       if (tid < kListsPerIndex) { g.kind_cnt[tid * g.buckets + b] = 0u; }
       __syncthreads();
       continue;
@@ -1208,12 +1206,12 @@ __global__ __launch_bounds__(kG1Threads) void k_group1(const GroupArgs a) {
       }
       *reinterpret_cast<uint4 *>(toff + tid * kPer) = make_uint4(off[0], off[1], off[2], off[3]);
       *reinterpret_cast<uint4 *>(toff + tid * kPer + 4u) = make_uint4(off[4], off[5], off[6], off[7]);
-      if (mass != 0u) { atomicOr(a.flags + 4, 1u); atomicAdd(a.flags + 5, mass); atomicAdd(&gsum[2], mass); }
+      if (mass != 0u) { atomicOr(a.flags + kFlagOversized, 1u); atomicAdd(a.flags + kFlagOverMass, mass); atomicAdd(&gsum[2], mass); }
       // the guard: what became of the bucket's records — members of singleton groups, of groups left to the plain kernel, the rest listed
       n_listed = (uint32_t)(total >> 32);
       if (tid == 0) {
         gsum[0] = (uint32_t)total & 0x1FFFFu; gsum[1] = ((uint32_t)total >> 17) & 0x7FFFu;
-        if (((uint32_t)total & 0x1FFFFu) != c) { atomicAdd(a.guard + 10, 1ull); }
+        if (((uint32_t)total & 0x1FFFFu) != c) { atomicAdd(a.guard + kGuardBucketTotal, 1ull); }   // (never read: swa_internal.h)
       }
     }
     __syncthreads();
@@ -1245,7 +1243,7 @@ __global__ __launch_bounds__(kG1Threads) void k_group1(const GroupArgs a) {
     if (tid >= 64u && tid < 67u) {
       const uint32_t j = tid - 64u;
       const uint32_t sum = j == 0u ? gsum[0] - gsum[1] - gsum[2] : gsum[j];
-      if (sum != 0u) { atomicAdd(a.guard + 2u + 2u * j + which, (unsigned long long)sum); }
+      if (sum != 0u) { atomicAdd(a.guard + kGuardListed + 2u * j + which, (unsigned long long)sum); }   // (j: listed, singleton, oversized)
     }
     __syncthreads();
     if (tid == 64u) { gsum[2] = 0u; }

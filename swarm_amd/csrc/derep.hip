@@ -94,7 +94,6 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
   SWA_TRY(swa_reserve(ctx, ctx->d_graft, uint64_t(n) * sizeof(uint32_t)));            // result
   SWA_TRY(swa_reserve(ctx, ctx->d_list_a, uint64_t(n) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_list_b, uint64_t(n) * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
   ctx->d1_ready = false;                                   // d_table is re-purposed
   ctx->full_index = false;
   ctx->anchor_ready = false;
@@ -105,7 +104,7 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
   auto * rep = static_cast<uint32_t *>(ctx->d_counts.ptr);
   auto * slot_of = static_cast<uint32_t *>(ctx->d_cursor.ptr);
   auto * result = static_cast<uint32_t *>(ctx->d_graft.ptr);
-  auto * next_count = static_cast<uint32_t *>(ctx->d_flags.ptr) + 4;
+  uint32_t * next_count = swa_status(ctx)->flags + kFlagDerepLeft;
   uint32_t * lists[2] = {static_cast<uint32_t *>(ctx->d_list_a.ptr), static_cast<uint32_t *>(ctx->d_list_b.ptr)};
   const uint32_t * active = nullptr;                       // round 0: every amplicon
   uint32_t count = n;

@@ -879,8 +879,8 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     if (ctx->dn_pair_cap == 0) { ctx->dn_pair_cap = 16ull * n + (1ull << 20); }
     uint64_t npairs = 0;
     uint64_t launches = 0;
-    for (int slot : {5, 6}) { ctx->ev_used[slot] = false; }
-    swa_t0(ctx, 5);                                            // timing slot 5: groups + pairs, slot 6: alignments + CSR
+    for (int slot : {kTimePairs, kTimeAlign}) { ctx->ev_used[slot] = false; }
+    swa_t0(ctx, kTimePairs);                                            // (groups + pairs; kTimeAlign: alignments + CSR)
     // the short sequences and what they can pair with, by length (once: a regrow repeats only the search)
     BruteArgs br{};
     if (plan.nshort != 0) {
@@ -911,18 +911,18 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     for (int attempt = 0; attempt < 6; ++attempt) {
       SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->dn_pair_cap * sizeof(uint64_t)));
       SWA_HIP(ctx, hipMemsetAsync(fc, 0, 8 * sizeof(uint64_t), ctx->stream));
-      SWA_HIP(ctx, hipMemsetAsync(jt.flags, 0, 2 * sizeof(uint32_t), ctx->stream));
+      SWA_HIP(ctx, hipMemsetAsync(jt.flags, 0, kJoinItemCount * sizeof(uint32_t), ctx->stream));
       for (uint32_t k = 0; k <= d; ++k) {
         GroupArgs g{};
         g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen; g.n = n; g.d = d; g.k = k; g.wlen = wlen; g.short_below = plan.short_below;
-        g.keys = jt.keys; g.cnt_t = jt.cnt_a; g.cnt_q = jt.cnt_b; g.amask = asize - 1; g.tslot = jt.aslot; g.qslot = jt.bslot; g.overflow = jt.flags;
+        g.keys = jt.keys; g.cnt_t = jt.cnt_a; g.cnt_q = jt.cnt_b; g.amask = asize - 1; g.tslot = jt.aslot; g.qslot = jt.bslot; g.overflow = jt.flags + kJoinKeyOverflow;
         g.owner_rank = ctx->dn_owner_rank; g.owner_world = ctx->dn_owner_world;
         auto key_kernels = [&](dim3 gn, dim3 b) {
           if (ns <= (uint32_t)kSmallShifts) { hipLaunchKernelGGL(k_dg_targets<kSmallShifts>, gn, b, 0, ctx->stream, g); }
           else { hipLaunchKernelGGL(k_dg_targets<kMaxShifts>, gn, b, 0, ctx->stream, g); }
           hipLaunchKernelGGL(k_dg_queries, gn, b, 0, ctx->stream, g);
         };
-        uint32_t * item_count = jt.flags + 2;
+        uint32_t * item_count = jt.flags + kJoinItemCount;
         SWA_HIP(ctx, hipMemsetAsync(item_count, 0, sizeof(uint32_t), ctx->stream));
         // blocks of 64 targets x 256 queries for the LDS kernels (d = 2, 3 and 9 .. 16; the per-pair kernel for other d);
         // a group needs a pair of DIFFERENT amplicons (an amplicon alone is its own target): t q >= 2
@@ -958,9 +958,9 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_dn_graph: pair list keeps overflowing"); }
       ctx->dn_pair_cap = got[0] + 1024;
     }
-    swa_t1(ctx, 5);
+    swa_t1(ctx, kTimePairs);
     // alignments in the direction(s) the abundance rule allows
-    swa_t0(ctx, 6);
+    swa_t0(ctx, kTimeAlign);
     uint64_t nedges = 0;
     if (npairs != 0) {
       SWA_TRY(swa_reserve(ctx, ctx->d_scan_targets, 4 * npairs * sizeof(uint32_t)));        // queries | targets, both directions
@@ -1014,7 +1014,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         launches += 6;
       }
     }
-    swa_t1(ctx, 6);
+    swa_t1(ctx, kTimeAlign);
     ctx->dn_edges = nedges;
     ctx->dn_work = npairs != 0 ? ctx->dn_aligned : 0;
     ctx->dn_launches = launches + 4;

@@ -75,12 +75,11 @@ struct JoinTable {
   uint32_t * bslot;              // [n] the slot it found
   uint32_t * members;
   join_item * items;
-  uint32_t * flags;              // [0] the key table overflowed [1] items past the cap [2 ..] item counters, one a join whose
-                                 // items are read while another join's are made
+  uint32_t * flags;              // the status block's flags + kFlagJoin: kJoinKeyOverflow, kJoinItemOverflow, and from kJoinItemCount
+                                 // on item counters, one a join whose items are read while another join's are made
   uint64_t asize;                // a power of two
   uint32_t n, per_a;
 };
-constexpr uint32_t kJoinFlagWords = 5;
 
 __global__ __launch_bounds__(256) void k_join_clear(const JoinTable t) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.asize; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(256) void k_join_scatter(const JoinTable t) {
 }
 
 // one thread per key slot: the group's work items, min(Shape::tiles, Shape::stride) of them, item.tile = its first tile.
-// Items past the cap are not dropped quietly: flags[1] is raised and the route fails.
+// Items past the cap are not dropped quietly: flags[kJoinItemOverflow] is raised and the route fails.
 template <class Shape>
 __global__ __launch_bounds__(256) void k_join_items(const JoinTable t, uint32_t * counter, uint32_t cap) {
   __shared__ uint32_t n_items, base;
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(256) void k_join_items(const JoinTable t, uint32_t 
     const uint32_t at = base + atomicAdd(&n_items, k);
     join_item it;
     it.begin = (uint32_t)t.offsets[s]; it.na = t.cnt_a[s]; it.nb = t.cnt_b[s];
-    if ((uint64_t)at + k > cap) { t.flags[1] = 1u; }
+    if ((uint64_t)at + k > cap) { t.flags[kJoinItemOverflow] = 1u; }
     for (uint32_t j = 0; j < k; ++j) { it.tile = j; if ((uint64_t)at + j < cap) { t.items[at + j] = it; } }
   }
 }
@@ -196,7 +195,6 @@ inline int join_reserve(swa_ctx * ctx, uint64_t asize, uint32_t n, uint32_t per_
   SWA_TRY(swa_reserve(ctx, ctx->d_fslot, (uint64_t)n * (per_a + 1u) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fmembers, member_cap * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fitems, (uint64_t)item_cap * sizeof(join_item)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_flags, 16 * sizeof(uint32_t)));
   return SWA_OK;
 }
 
@@ -210,7 +208,7 @@ inline JoinTable join_table(swa_ctx * ctx, uint64_t asize, uint32_t n, uint32_t 
   t.bslot = t.aslot + (uint64_t)n * per_a;
   t.members = static_cast<uint32_t *>(ctx->d_fmembers.ptr);
   t.items = static_cast<join_item *>(ctx->d_fitems.ptr);
-  t.flags = static_cast<uint32_t *>(ctx->d_flags.ptr) + 8;
+  t.flags = swa_status(ctx)->flags + kFlagJoin;
   t.asize = asize; t.n = n; t.per_a = per_a;
   return t;
 }
@@ -236,11 +234,11 @@ int join_run(swa_ctx * ctx, const JoinTable & t, uint32_t min_product, uint32_t 
 // tests/test_pair_identity.py), so either is an error with the route's message.
 inline int join_status(swa_ctx * ctx, const JoinTable & t, const unsigned long long * counters, uint32_t ngot, uint64_t * got,
                        const char * key_overflow, const char * item_overflow) {
-  uint32_t fl[2] = {0, 0};
+  uint32_t fl[kJoinItemCount] = {};
   SWA_HIP(ctx, hipMemcpyAsync(got, counters, ngot * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipMemcpyAsync(fl, t.flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (fl[0] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, key_overflow); }
-  if (fl[1] != 0) { return swa_fail_msg(ctx, SWA_E_INTERNAL, item_overflow); }
+  if (fl[kJoinKeyOverflow] != 0) { return swa_fail_msg(ctx, SWA_E_DEVICE, key_overflow); }
+  if (fl[kJoinItemOverflow] != 0) { return swa_fail_msg(ctx, SWA_E_INTERNAL, item_overflow); }
   return SWA_OK;
 }

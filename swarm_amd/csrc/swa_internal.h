@@ -3,11 +3,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/swarm_amd.h"
@@ -27,6 +29,85 @@ struct swa_dbuf {
   void * ptr = nullptr;
   size_t bytes = 0;
 };
+
+// ---- the status block ----------------------------------------------------------------
+// Every context owns one 4 KB block in HBM (d_status) and a pinned mirror of it (h_status): every small status array of
+// the context, so that the host reads them with ONE copy per phase (a device-to-host copy of a few bytes is a kernel of
+// its own, ~5 us with its gap: the d = 1 step made nine).  What a kernel writes here decides whether a step is repeated,
+// fails with SWA_E_INTERNAL or returns SWA_E_DUPLICATES.  The members and the k* indices below are the whole contract:
+// kernels get plain pointers to the arrays (or into them) and index them with the same names.
+struct swa_status_block {
+  uint32_t flags[16];            // kFlag*
+  uint64_t stats[16];            // kStat* (cleared per network call)
+  uint64_t guard[24];            // kGuard* (d1.hip: guard_check)
+  uint64_t csr_end;              // the last CSR offset once more (k_csr_*: CsrArgs::end_copy)
+  uint32_t links_sorted;         // links the partition of the CSR stage sorted (its total, 32 bits)
+  uint32_t pad0[29];
+  uint32_t host_unserved;        // HOST ONLY (the mirror): where network_run receives counters[kCounterFallback]
+  uint32_t pad1[127];
+  uint32_t counters[256];        // kCounter*: work counters of the d = 1 step (kCounterWords)
+  uint64_t cursors[64];          // swa_d1_links_split: the run cursor of every rank; in the mirror [0] receives the links no rank owns
+  uint8_t pad2[1536];
+};
+static_assert(std::is_standard_layout<swa_status_block>::value, "status block: plain data");
+static_assert(sizeof(swa_status_block) == 4096, "status block: 4 KB");
+static_assert(offsetof(swa_status_block, flags) == 0 && offsetof(swa_status_block, stats) == 64 &&
+              offsetof(swa_status_block, guard) == 192 && offsetof(swa_status_block, csr_end) == 384 &&
+              offsetof(swa_status_block, links_sorted) == 392 && offsetof(swa_status_block, host_unserved) == 512 &&
+              offsetof(swa_status_block, counters) == 1024 && offsetof(swa_status_block, cursors) == 2048,
+              "status block: the regions lie where the kernels and the debug reads expect them");
+
+// flags[]: the d = 1 index build and step ...
+constexpr uint32_t kFlagDuplicates = 0;    // identical sequences (k_dup_check; the prefix pass of the pair kernels: pair_twin)
+constexpr uint32_t kFlagUnordered = 1;     // the database is not in abundance order (k_abundance_rank)
+constexpr uint32_t kFlagKeyOverflow = 2;   // a bucket with more distinct keys than k_group1's table holds: partition finer
+constexpr uint32_t kFlagUnserved = 3;      // a sequence too short for two windows: a seed the anchored passes cannot serve
+constexpr uint32_t kFlagOversized = 4;     // groups left to the plain kernel (oversized / a member too long) ...
+constexpr uint32_t kFlagOverMass = 5;      // ... and how many members they have
+constexpr uint32_t kFlagShortest = 6;      // 0xFFFFFFFF - the shortest sequence
+constexpr uint32_t kFlagsD1 = 7;           // (so many of them)
+// ... the dereplication's count of amplicons left for the next round, ON THE WORD OF kFlagOversized: swa_derep drops the
+// d = 1 index before its first round (d1_ready = anchor_ready = false), so no build or step reads the flag it overwrites
+constexpr uint32_t kFlagDerepLeft = kFlagOversized;
+// ... and the grouped join (group_join.inc: JoinTable::flags = flags + kFlagJoin), indexed from there:
+constexpr uint32_t kFlagJoin = 8;
+constexpr uint32_t kJoinKeyOverflow = 0;   // the key table is full
+constexpr uint32_t kJoinItemOverflow = 1;  // more work items than the route's cap
+constexpr uint32_t kJoinItemCount = 2;     // item counters: one for d >= 2, one a group type (+ 0..2) for --fastidious
+constexpr uint32_t kJoinFlagWords = 5;
+static_assert(kFlagsD1 <= kFlagJoin && kFlagJoin + kJoinFlagWords <= 16, "status block: flags");
+
+// stats[]: [0, kStatSeg) unused; from kStatSeg on what k_seg_reduce makes of the per-wave segments, indexed from there:
+constexpr uint32_t kStatSeg = 8;
+constexpr uint32_t kSegLinks = 0;          // links found
+constexpr uint32_t kSegFullest = 1;        // the fullest segment
+constexpr uint32_t kSegStaged = 2;         // + pass: members the pair kernels staged
+
+// guard[]: [0, kGuardCall) describe the index in place (cleared by the streaming build), two words each, + index:
+constexpr uint32_t kGuardMade = 0;         // key records made (k_keys, k_set_guard_made)
+constexpr uint32_t kGuardListed = 2;       // members of listed groups        (k_group1 relies on these three lying
+constexpr uint32_t kGuardSingleton = 4;    // ... of singleton groups          two words apart in this order)
+constexpr uint32_t kGuardOversized = 6;    // ... of groups left to the plain kernel
+// [kGuardCall, kGuardKeys) belong to one network call (launch_network_anchored clears them at its start):
+constexpr uint32_t kGuardCall = 8;
+constexpr uint32_t kGuardMisfiled = 10;    // members found under an anchor key that is not theirs (the pair kernels)
+// k_group1 counts a bucket whose member total disagrees with its record count into THE SAME WORD while the index is
+// BUILT: the clear of the next network call wipes that count before guard_check reads the word, so it never reaches the
+// host.  Kept as it is (what the guard reports is unchanged); a word of its own, in [0, kGuardCall), would make it count.
+constexpr uint32_t kGuardBucketTotal = kGuardMisfiled;
+// [kGuardKeys, 24): the second opinion on the key records, once per uploaded database (cleared before it is taken): two
+// triples, the third word of each — once the fingerprints' sum — unused
+constexpr uint32_t kGuardKeys = 16;
+constexpr uint32_t kGuardKeysDb = 16;      // + index: sums from the packed database (k_guard_db)
+constexpr uint32_t kGuardKeysRec = 19;     // + index: sums of the partitioned records (k_guard_records)
+
+// counters[]: the streaming build clears all of them, every network call [0, kCounterBase)
+constexpr uint32_t kCounterFallback = 2;   // seeds (or halves of seeds) listed for the plain kernel (k_stream_fallback)
+constexpr uint32_t kCounterSchedBig = 8;   // + 2 (kWidthClasses pass + class): work counter of the 65..pair_big groups of k_d1_group_pairs
+constexpr uint32_t kCounterSchedTiled = 9; // + 2 (kWidthClasses pass + class): work counter of k_d1_pairs_tiled
+constexpr uint32_t kCounterBase = 64;      // + (index * kWidthClasses + class) * 8 + kind: items in that work list (k_group_lists)
+constexpr uint32_t kCounterWords = 256;
+static_assert(kCounterWords * sizeof(uint32_t) == sizeof(swa_status_block::counters), "status block: counters");
 
 // dn_graph.hip keeps a count per sequence length below this: 16 (d + 1) + d for d <= 16, the lengths a short sequence can pair with
 #define SWA_DN_HIST_LEN 288u
@@ -58,16 +139,8 @@ struct swa_ctx {
   uint32_t zobrist_resident = 0; // length of the table currently in d_zobrist (0 = none)
   bool patterns_resident = false;
   swa_dbuf d_zobrist, d_seqhash, d_table, d_bloom, d_patterns;
-  // One 4 KB block holds every small status array of the context, so that the host reads them with ONE copy per phase (a
-  // device-to-host copy of a few bytes is a kernel of its own, ~5 us with its gap: the step made nine):
-  //   [0, 64) d_flags · [64, 192) d_stats · [192, 384) d_guard · [384, 512) d_extra: [0] last CSR offset [1] links the
-  //   partition sorted · [1024, 2048) d_acounters · [2048, 2560) the run cursors of swa_d1_links_split (u64[64]).
-  //   d_flags / d_stats / d_guard / d_acounters are VIEWS into it (never freed on their own; their `bytes` is their room,
-  //   so swa_reserve leaves them alone).
-  swa_dbuf d_status;
-  void * h_status = nullptr;     // 4 KB of pinned host memory: where the d = 1 step looks at the status block
-  swa_dbuf d_flags;              // u32[16]: [0] duplicate flag
-  swa_dbuf d_stats;              // u64[16]: [8] links found [9] fullest segment [10, 12) members staged by pass
+  swa_dbuf d_status;             // one swa_status_block in HBM (swa_status(ctx): its device address) ...
+  swa_status_block * h_status = nullptr;   // ... and its mirror in pinned host memory: where the host looks at what it copied
   swa_dbuf d_edges;              // u64 edge list (src << 32 | dst)
   swa_dbuf d_counts, d_cursor, d_scan_tmp, d_offsets_tmp, d_nb_tmp;
   // anchored d=1 index (d1_anchor.inc, d1_stream.inc): [0] prefix groups, [1] suffix groups
@@ -90,13 +163,12 @@ struct swa_ctx {
   uint32_t anchor_a = 0, anchor_b = 0;   // anchor windows moved inwards by this many nt ("window mode", chosen at index build)
   uint32_t anchor_w = 32;        // width of the anchor windows in nt: 32, 64 or 128 (wider: fewer pairs per group; needs 2 w + 1 nt)
   uint32_t windows_w = 32;       // ... as chosen for this database (with windows_chosen)
-  swa_dbuf d_guard;              // u64[24] the guard's counters (d1.hip: guard_check)
-  bool guard_index = false;      // [0..8) describe the index in place (made by the streaming build since the last clear)
+  bool guard_index = false;      // guard[0, kGuardCall) of the status block describe the index in place (made by the streaming build since the last clear)
   bool guard_keys_done = false;  // the key records of this upload have had their second opinion (k_guard_db / k_guard_records)
-  bool guard_keys_pending = false;   // ... its sums, [16..22), wait for the next guard_check
+  bool guard_keys_pending = false;   // ... its sums, guard[kGuardKeys ..), wait for the next guard_check
   // d_akeys[0] / d_acounts[0]: scratch of the window sample; d_aitems: the work lists of the two indexes
   swa_dbuf d_aux, d_akeys[1], d_acounts[1], d_aitems[2];
-  swa_dbuf d_acounters, d_afallback, d_arank, d_rank_tmp;
+  swa_dbuf d_afallback, d_arank, d_rank_tmp;
   swa_dbuf d_seg_fill;           // u32 fill of every per-wave edge segment
   swa_dbuf d_seg_base;           // u64 start of every segment in the compacted edge list (swa_d1_network_edges_device)
   uint64_t seg_cap = 0;          // entries per segment
@@ -152,16 +224,12 @@ struct swa_ctx {
   // streaming index build / CSR assembly (d1_stream.inc)
   bool lines_ready = false;      // d_lines holds this database's amplicon lines (made once per upload), lines_w words each
   uint32_t lines_quads = 0;      // ... of this many 16-byte quads each (4, 8 or 16)
-  uint32_t list_counts[2 * 4 * 8] = {};   // items per work list of the index in place ([index][width class][8]: d_acounters + kCounterBase)
+  uint32_t list_counts[2 * 4 * 8] = {};   // items per work list of the index in place ([index][width class][8]: the status block's counters + kCounterBase)
   bool list_counts_ready = false;
   uint64_t list_regions_items = 0;   // entries of an index's item buffer (d1.hip: list_regions)
   bool stream_index = false;     // the anchor indexes in place were made by the streaming build: members = ids in d_members
   uint32_t stream_extra_bits = 0;   // finer partition after a bucket held more distinct keys than the group kernel's table
-  // [0] lines [1..4] records ping / pong per index [5, 6] fingerprints ping / pong [7] table slots of big buckets
-  // [8, 9] flat counts [10, 11] tile tables [12, 13] chunk starts [14, 15] scan partials [16] scalars
-  // [17, 18] members [19] oversized-group bits [20, 21] items per kind [22] link sort: records ping [23] pong
-  // [24] buckets of the CSR stage left to whole workgroups [26] member table [27] member Bloom
-  swa_dbuf d_stream[30];
+  swa_dbuf d_stream[30];         // indexed by kSb* (below)
   // member index: hash table + Bloom of the members of oversized groups only (what the plain kernel probes for them)
   bool member_index = false, only_oversized = false;
   uint32_t over_mass = 0;
@@ -194,6 +262,23 @@ struct swa_ctx {
   swa_dbuf d_nw_ids, d_nw_lists, d_nw_res, d_nw_text, d_nw_gather, d_nw_bits;
 };
 
+// the buffers of d_stream[]; where two are named, one per index (+ i), the records ping / pong per index (+ 2 i + h)
+enum { kSbLines = 0,             // the amplicon lines
+       kSbRec = 1,               // [1..4] key records
+       kSbCnt = 8, kSbTile = 10, kSbStart = 12, kSbPartial = 14,   // the partition's flat counts, tile tables, chunk starts, scan partials
+       kSbScal = 16,             // scalars
+       kSbMembers = 17,          // [17, 18] ids in group order
+       kSbOver = 19,             // oversized-group bits, a byte an amplicon
+       kSbKind = 20,             // [20, 21] items per list kind
+       kSbLinkA = 22, kSbLinkB = 23,   // link sort: records ping, pong
+       kSbHeavy = 24,            // buckets of the CSR stage left to whole workgroups
+       kSbMTable = 26, kSbMBloom = 27,   // member table and its Bloom filter
+       kSbSched = 28 };          // work counters of k_d1_group_pairs
+
+// the device address of the context's status block: for taking the addresses of members (kernel arguments, copies, fills),
+// never to be dereferenced on the host — the host reads ctx->h_status after a copy
+inline swa_status_block * swa_status(const swa_ctx * ctx) { return static_cast<swa_status_block *>(ctx->d_status.ptr); }
+
 int swa_fail(swa_ctx * ctx, int code, const char * what, hipError_t e);
 int swa_fail_msg(swa_ctx * ctx, int code, const std::string & msg);
 // SWARM_AMD_STEP_TIMING=1: wall-clock laps between the host-visible points of the d = 1 index build and network call, on
@@ -209,7 +294,15 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking);
 int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const uint32_t * svals, uint64_t nedges, uint64_t * offsets,
                       uint32_t * neighbours, uint8_t * diffs, uint64_t cap, uint64_t * total);
 
-// RAII-less timing brackets: SWA_T0(ctx, slot) ... SWA_T1(ctx, slot)
+// RAII-less timing brackets: swa_t0(ctx, slot) ... swa_t1(ctx, slot).  The slots: swa_timing_read reports [0, 8),
+// swa_timing_read_stream [8, 16), both by position (include/swarm_amd.h)
+enum { kTimeSeqhash = 0, kTimeTable = 1, kTimeDupCheck = 2, kTimeNetwork = 3, kTimeCsr = 4,
+       kTimePairs = 5,           // --fastidious: light pass; d >= 2: groups + pairs
+       kTimeAlign = 6,           // --fastidious: heavy pass; d >= 2: alignments + CSR
+       kTimeIndex = 7,           // the whole anchored-index build
+       kTimeKeys = 8, kTimeKeyPartition = 9, kTimeGroups = 10,
+       kTimePass = 11,           // + pass: the pair kernels of the prefix / suffix groups
+       kTimeLinkPartition = 13, kTimeCsrRows = 14, kTimeLines = 15 };
 inline void swa_t0(swa_ctx * ctx, int slot) {
   if (ctx->timing && ctx->ev_ready) { (void)hipEventRecord(ctx->ev[2 * slot], ctx->stream); }
 }
