@@ -278,8 +278,23 @@ int swa_d1_guard_retries(const swa_ctx * ctx);
    what: 0 seqhash u64[n] · 1 Bloom bitmap u64[table_size/8] · 2 Zobrist table
    u64[4*(longest+2)] (0..2 build the database-wide structures on demand)
    · 10 / 11 member ids in group order of the streaming prefix / suffix index u32[n] · 12 / 13 their work-item
-   buffers · 14 the counters u32[64] · 15 the amplicon lines (tools/check_index.py, tools/check_stream.py) */
+   buffers · 14 the counters u32[64] · 15 the amplicon lines (tools/check_index.py, tools/check_stream.py)
+   · 17 / 18 the bucket starts of the key partition of the prefix / suffix index, u64[buckets + 1] with buckets =
+   2^(total bits of swa_d1_part_plan); SWA_E_ARG once a network call has run (it sorts its links in the same scratch) */
 int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out_bytes);
+/* Which forms the two partitions of the d = 1 step take.  The number of records decides it, never the data:
+   swa_d1_part_plan_for: the key partition in front of the group kernel, as a pure function (no context, no device) of
+   the records per index, the bits a key-overflow retry has added (0, 2, .. 8), whether the build is routed (0 / 1) and
+   the bits forced by SWA_D1_PART_BITS (0: none; test hook).  out = {total bits, levels, bits of level 0, 1, 2 (0: no
+   such level), records per tile, 1 when k_keys takes the first level's histogram, 1 for the one level of 1024 bins}.
+   swa_d1_part_plan: the same for the streaming index in place, with the retry's bits in out[7] instead; SWA_E_ARG
+   without such an index.
+   swa_d1_csr_plan_for: the link partition and the row kernels of a CSR over `count` sources (swa_d1_network*,
+   swa_d1_csr_from_lists).  out = {bits of a source index, r (a bucket of the row kernels holds 2^r sources), levels,
+   bits of level 0, 1, 2}. */
+int swa_d1_part_plan_for(uint64_t records, uint32_t extra_bits, int routed, uint32_t forced_bits, uint32_t out[8]);
+int swa_d1_part_plan(const swa_ctx * ctx, uint32_t out[8]);
+int swa_d1_csr_plan_for(uint32_t count, uint32_t out[6]);
 uint64_t swa_d1_table_size(const swa_ctx * ctx);
 
 /* The same network computed into the context's own HBM buffers and kept there (no host copy):

@@ -76,7 +76,7 @@ EXPORTS = [
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_links_split", "swa_d1_csr_from_lists",
-    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_qgram_build", "swa_qgram_diff",
+    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_qgram_build", "swa_qgram_diff",
     "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
@@ -137,6 +137,9 @@ def load_library() -> C.CDLL:
     lib.swa_d1_fastidious_totals.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_split.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_plan_for.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.swa_d1_part_plan_for.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]
+    lib.swa_d1_part_plan.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_csr_plan_for.argtypes = [C.c_uint32, C.c_void_p]
     lib.swa_qgram_build.argtypes = [C.c_void_p]
     lib.swa_qgram_diff.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.swa_qgram_debug_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -190,6 +193,27 @@ def fastidious_plan_for(longest: int, pair_longest: int = 0, split: bool = False
     rc = load_library().swa_d1_fastidious_plan_for(int(longest), int(pair_longest), int(split), int(bloom), int(words), _ptr(out))
     if rc != SWA_OK:
         raise SwaError(rc, "swa_d1_fastidious_plan_for: bad argument")
+    return [int(v) for v in out]
+
+
+def part_plan_for(records: int, extra_bits: int = 0, routed: bool = False, forced_bits: int = 0) -> list:
+    """swa_d1_part_plan_for: the form of the key partition of the d = 1 index build as a pure function (no context, no
+    device): [total bits, levels, bits of level 0, 1, 2, records per tile, histogram taken by k_keys, one level of 1024
+    bins].  forced_bits: what SWA_D1_PART_BITS would set (0: unset)."""
+    out = np.zeros(8, dtype=np.uint32)
+    rc = load_library().swa_d1_part_plan_for(int(records), int(extra_bits), int(routed), int(forced_bits), _ptr(out))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_d1_part_plan_for: bad argument")
+    return [int(v) for v in out]
+
+
+def csr_plan_for(count: int) -> list:
+    """swa_d1_csr_plan_for: link partition and row kernels of a CSR over `count` sources: [bits of a source index, r (2^r
+    sources per bucket of the row kernels), levels, bits of level 0, 1, 2]."""
+    out = np.zeros(6, dtype=np.uint32)
+    rc = load_library().swa_d1_csr_plan_for(int(count), _ptr(out))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_d1_csr_plan_for: bad argument")
     return [int(v) for v in out]
 
 
@@ -657,6 +681,18 @@ class Context:
         out = np.zeros(count, dtype=np.uint64)
         self._check(self.lib.swa_d1_debug_read(self.h, what, _ptr(out), out.nbytes))
         return out
+
+    def d1_part_plan(self) -> list:
+        """swa_d1_part_plan: the key partition of the streaming index in place, laid out as part_plan_for() with the bits
+        a key-overflow retry added in [7]."""
+        out = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.swa_d1_part_plan(self.h, _ptr(out)))
+        return [int(v) for v in out]
+
+    def d1_bucket_starts(self, which: int) -> np.ndarray:
+        """Selectors 17 / 18 of swa_d1_debug_read: first record of every bucket of the key partition of the prefix (0) /
+        suffix (1) index and, last, the number of records; to be read before the first network call."""
+        return self.d1_debug(17 + int(which), (1 << self.d1_part_plan()[0]) + 1)
 
     # ---- B2
     def d1_fastidious(self, is_light: np.ndarray, light_nt: int, bloom_bits: int = 16, shard: int = 0,

@@ -864,14 +864,7 @@ __global__ void k_set_guard_made(unsigned long long * guard, uint32_t made0, uin
 
 // ---- the streaming build (d1_stream.inc) ------------------------------------------------------
 
-struct PartPlan { uint32_t levels; uint32_t bits[4]; uint32_t total; };
-static PartPlan plan_levels(uint32_t total_bits, uint32_t max_bits = kPartMaxBits) {
-  PartPlan p{};
-  p.total = std::max(1u, total_bits);
-  p.levels = (p.total + max_bits - 1) / max_bits;
-  for (uint32_t l = 0; l < p.levels; ++l) { p.bits[l] = p.total / p.levels + (l < p.total % p.levels ? 1u : 0u); }
-  return p;
-}
+using PartPlan = swa_part_levels;                  // (host_tables.cpp: swa_plan_levels, swa_part_plan_for, swa_csr_plan_for)
 
 // One multi-level partition (d1_stream.inc) over up to kMaxIdx record sets.  Level l reads what level l - 1 wrote
 // (ping / pong) and leaves, in starts[], the first record of every bucket; the last level's buckets are the result.
@@ -890,7 +883,6 @@ struct PartJob {
   uint32_t tile = 4096;                             // records per tile: 4096 (links), 2048 / 4096 / 8192 (key records: run_partition)
   bool hist0_done = false;                          // the flat counts of level 0 are there already (k_keys<W, true>)
   PartPlan plan{};
-  uint32_t * out32[kMaxIdx] = {};                   // != nullptr: the last level writes only the low halves, here
   // scratch, per set
   uint32_t * cnt[kMaxIdx] = {}; uint32_t * ctile[kMaxIdx] = {}; uint64_t * starts[kMaxIdx] = {}; uint32_t * partial[kMaxIdx] = {};
   uint32_t * total[kMaxIdx] = {};
@@ -937,8 +929,7 @@ static int clear_launch(swa_ctx * ctx, const ClearList & c) {
 
 // The forms of a level, chosen by the job: 512 bins in tiles of 2048 (key records) or 4096 (links: the first level of
 // several chunks cuts its tiles from the chunks laid end to end — part_span); 1024 bins for the one-level key partition,
-// in tiles of 8192 when k_keys has taken the histogram, else of 4096 (routed builds).  out32: the last level keeps only
-// the low halves.
+// in tiles of 8192 when k_keys has taken the histogram, else of 4096 (routed builds).
 static int run_partition(swa_ctx * ctx, PartJob & j) {
   uint64_t chunks = j.chunks0;
   bool single = j.single0;
@@ -949,10 +940,8 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
     used_bits += bits;
     const bool wide = bits > kPartMaxBits;                      // (1024 bins: the one-level key partition)
     const bool hist_done = l == 0 && j.hist0_done;
-    const bool low_halves = l + 1 == j.plan.levels && j.out32[0] != nullptr;
-    // (k_part_hist holds tiles of up to 4096; out32 has the link forms only)
-    const bool have_form = wide ? (j.tile == 4096 || (j.tile == 8192 && hist_done)) && !low_halves
-                                : (j.tile == 2048 && !low_halves) || j.tile == 4096;
+    // (k_part_hist holds tiles of up to 4096)
+    const bool have_form = wide ? j.tile == 4096 || (j.tile == 8192 && hist_done) : j.tile == 2048 || j.tile == 4096;
     if (!have_form) { return swa_fail_msg(ctx, SWA_E_ARG, "partition: no kernel for this tile and bin count"); }
     PartArgs a{};
     a.single_seg = single ? 1u : 0u; a.bits = bits; a.shift = j.top_bit - used_bits; a.bias = j.bias; a.tile = j.tile;
@@ -966,7 +955,6 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
       PartIdx & p = a.p[i];
       p.in = l == 0 ? j.in[i] : j.buf[i][(l - 1) & 1u];
       p.out = j.buf[i][l & 1u];
-      p.out32 = low_halves ? j.out32[i] : nullptr;
       p.out_cap = j.out_cap;
       p.cstart = l == 0 ? j.cstart0[i] : j.starts[i] + ((l - 1) & 1u) * j.starts_stride;
       p.cstride = l == 0 ? j.cstride0[i] : 0;
@@ -997,17 +985,15 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
     if (wide && j.tile == 8192) {
       constexpr size_t lds = part_scatter_lds(8192, 1024);
       if (!ctx->part_lds_opt_in) {
-        SWA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter<0, 8192, 1024, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SWA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter<8192, 1024, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ctx->part_lds_opt_in = true;
       }
-      hipLaunchKernelGGL((k_part_scatter<0, 8192, 1024, 1024>), grid_t, dim3(1024), lds, ctx->stream, a);
+      hipLaunchKernelGGL((k_part_scatter<8192, 1024, 1024>), grid_t, dim3(1024), lds, ctx->stream, a);
     }
-    else if (wide) { hipLaunchKernelGGL((k_part_scatter<0, 4096, 1024, 512>), grid_t, dim3(512), part_scatter_lds(4096, 1024), ctx->stream, a); }
-    else if (j.tile == 2048) { hipLaunchKernelGGL((k_part_scatter<0, 2048, 512, 512>), grid_t, dim3(512), part_scatter_lds(2048, 512), ctx->stream, a); }
-    else if (a.span != 0u && low_halves) { hipLaunchKernelGGL((k_part_scatter<2, 4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
-    else if (a.span != 0u) { hipLaunchKernelGGL((k_part_scatter<0, 4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
-    else if (low_halves) { hipLaunchKernelGGL((k_part_scatter<2, 4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
-    else { hipLaunchKernelGGL((k_part_scatter<0, 4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
+    else if (wide) { hipLaunchKernelGGL((k_part_scatter<4096, 1024, 512>), grid_t, dim3(512), part_scatter_lds(4096, 1024), ctx->stream, a); }
+    else if (j.tile == 2048) { hipLaunchKernelGGL((k_part_scatter<2048, 512, 512>), grid_t, dim3(512), part_scatter_lds(2048, 512), ctx->stream, a); }
+    else if (a.span != 0u) { hipLaunchKernelGGL((k_part_scatter<4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
+    else { hipLaunchKernelGGL((k_part_scatter<4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
     chunks = (single ? 1 : chunks) << bits;
     single = false;
     hipLaunchKernelGGL(k_part_starts, dim3((unsigned)std::min<uint64_t>((chunks + 256) / 256, (uint64_t)cu_grid), j.nidx), dim3(256), 0, ctx->stream, a);
@@ -1063,26 +1049,26 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   const bool by_rec = ctx->route_rec[0] != nullptr;           // routed, and the key records themselves arrived: no k_keys pass
   const bool routed = ctx->route_ids[0] != nullptr || by_rec;
   const uint64_t records = routed ? std::max<uint64_t>(std::max(ctx->route_m[0], ctx->route_m[1]), 1) : n;
-  // buckets of ~10 000 records for k_group1: ONE partition level of up to 10 bits at 10 M amplicons
-  const uint32_t target = kG1Target, level_bits = 10u;
-  uint32_t total_bits = 1;
-  while ((records >> total_bits) > target && total_bits < 3 * kPartMaxBits) { ++total_bits; }
-  total_bits = std::min<uint32_t>(total_bits + ctx->stream_extra_bits, 3 * kPartMaxBits);
-  // the first partition level's histogram is taken on the way (one read pass over the records less: 0.07 ms at 10 M);
-  // not for routed id lists (their length is the device's to know)
-  const bool keys_hist = !routed;
+  // buckets of ~10 000 records for k_group1, the levels, the tile and who takes the first histogram: swa_part_plan_for
+  // (host_tables.cpp).  SWA_D1_PART_BITS=1..27 (test hook, read at every build): that many bits instead of what the number
+  // of records gives; the bits of the key-overflow retry still come on top
+  uint32_t forced_bits = 0;
+  if (const char * e = getenv("SWA_D1_PART_BITS")) {
+    const int b = atoi(e);
+    if (b >= 1 && b <= (int)(3 * kPartMaxBits)) { forced_bits = (uint32_t)b; }
+  }
+  const swa_part_plan plan = swa_part_plan_for(records, ctx->stream_extra_bits, routed, forced_bits);
+  const uint32_t total_bits = plan.lv.total;
+  const bool keys_hist = plan.keys_hist;
   PartJob j;
   j.nidx = 2;
-  // (one level of up to 1024 bins, or levels of up to 512: the partition has 1024-bin forms for one level only)
-  j.plan = total_bits <= level_bits ? plan_levels(total_bits, level_bits) : plan_levels(total_bits);
+  j.plan = plan.lv;
   j.max_records = records;
   j.out_cap = records + 1;
-  // tiles of 2048 records for 512 bins; one level of 1024 bins: 4096 (or the flat count array — bins x tiles — and the 16-byte
-  // runs a tile leaves per bin cost more than the saved level: 0.56 -> 0.43 ms at 10 M amplicons) — or 8192 when k_keys takes
-  // the histogram (k_part_hist holds 4096 a workgroup): a tile then leaves runs of 64 bytes per bin, whole lines (key
-  // partition 0.239 -> 0.225 ms at 10 M)
-  const bool one_wide_level = total_bits > kPartMaxBits && j.plan.levels == 1;
-  j.tile = one_wide_level ? (keys_hist ? 8192 : 4096) : 2048;
+  j.tile = plan.tile;
+  swa_part_plan_report(plan, ctx->part_plan);
+  ctx->part_plan[7] = ctx->stream_extra_bits;                 // (swa_d1_part_plan: the retry's bits in place of `wide`)
+  ctx->part_starts_valid = false;
   j.max_tiles0 = records / j.tile + 2;
   j.chunks0 = 1; j.single0 = true; j.top_bit = 32; j.bias = 0;
   uint64_t e_cnt, e_tile, e_start, e_partial;
@@ -1183,6 +1169,9 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   SWA_TRY(run_partition(ctx, j));
   swa_t1(ctx, kTimeKeyPartition);
   swa_lap(ctx, "key partition");
+  ctx->part_starts_at = (uint64_t)(j.bstart[0] - j.starts[0]);   // (the same place in both indexes' buffers)
+  ctx->part_buckets = j.buckets;
+  ctx->part_starts_valid = true;
   if (!ctx->guard_keys_done) {
     // the guard's second opinion on the key records, once per uploaded database: from the packed database against what the
     // partition holds (k_guard_db / k_guard_records); compared at the next guard_check
@@ -1264,13 +1253,11 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
 static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const unsigned long long * links, const uint64_t * d_cstart, uint64_t cstride,
                            const uint32_t * d_csize, uint32_t chunks, uint32_t csize_cap, uint64_t max_tiles0, uint64_t link_cap,
                            uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap) {
-  uint32_t nbits = 1;
-  while (nbits < 32 && ((uint64_t)1 << nbits) < count) { ++nbits; }
-  uint32_t r = std::min<uint32_t>(8, nbits - 1);
-  if (nbits - r > 2 * kPartMaxBits) { r = std::min<uint32_t>(kCsrMaxR, nbits - 2 * kPartMaxBits); }
+  const swa_csr_plan plan = swa_csr_plan_for(count);          // (host_tables.cpp)
+  const uint32_t nbits = plan.nbits, r = plan.r;
   PartJob j;
   j.nidx = 1;
-  j.plan = plan_levels(nbits - r);
+  j.plan = plan.lv;
   j.max_records = link_cap;
   j.out_cap = link_cap;
   j.tile = 4096;
@@ -1294,6 +1281,7 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   j.cnt[0] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt].ptr);
   j.ctile[0] = static_cast<uint32_t *>(ctx->d_stream[kSbTile].ptr);
   j.starts[0] = static_cast<uint64_t *>(ctx->d_stream[kSbStart].ptr);
+  ctx->part_starts_valid = false;                             // (the prefix index's bucket starts lay there: selectors 17 / 18)
   j.partial[0] = static_cast<uint32_t *>(ctx->d_stream[kSbPartial].ptr);
   j.total[0] = &swa_status(ctx)->links_sorted;
   j.starts_stride = e_start + 2;
@@ -2326,6 +2314,15 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
     else if (what == 12 || what == 13) { from = ctx->d_aitems[what - 12].ptr; need = ctx->list_regions_items * sizeof(swa_item); }
     else if (what == 14) { from = swa_status(ctx)->counters; need = kCounterWords * sizeof(uint32_t); }
     else if (what == 15) { from = ctx->d_stream[kSbLines].ptr; need = uint64_t(ctx->db.n) * ctx->lines_quads * 16u; }
+    else if (what == 17 || what == 18) {
+      // the bucket starts of the key partition, u64[buckets + 1]: as the index build left them — a network call sorts its
+      // links in the same scratch, so they are there between the build and the first network call only
+      if (!ctx->part_starts_valid) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: the bucket starts are there only between the index build and the next network call"); }
+      const swa_dbuf & b = ctx->d_stream[kSbStart + (what - 17)];
+      need = ((uint64_t)ctx->part_buckets + 1) * sizeof(uint64_t);
+      if (b.ptr == nullptr || (ctx->part_starts_at + ctx->part_buckets + 1) * sizeof(uint64_t) > b.bytes) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_d1_debug_read: bucket starts outside their buffer"); }
+      from = static_cast<const uint64_t *>(b.ptr) + ctx->part_starts_at;
+    }
     else if (what == 16) {                                    // (host-side facts: where the lists lie, how wide a line is)
       uint64_t total = 0;
       const ListRegions r = list_regions(ctx, &total);
@@ -2356,6 +2353,15 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   SWA_HIP(ctx, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
+// The key partition of the streaming index in place: the layout of swa_d1_part_plan_for, with the bits the key-overflow
+// retry added in [7]
+extern "C" int swa_d1_part_plan(const swa_ctx * ctx, uint32_t out[8]) {
+  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
+  if (!ctx->d1_ready || !ctx->stream_index) { return SWA_E_ARG; }
+  memcpy(out, ctx->part_plan, sizeof(ctx->part_plan));
   return SWA_OK;
 }
 

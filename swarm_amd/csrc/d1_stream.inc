@@ -33,7 +33,7 @@
 
 constexpr uint32_t kPartTileMax = 4096;           // records per tile of k_part_hist (PartArgs::tile: 2048 or 4096; the one-level key
                                                   // partition scatters tiles of 8192, its histogram taken by k_keys)
-constexpr uint32_t kPartMaxBits = 9;               // bits per level (512 bins) — 10 for the one-level key partition in front of k_group1;
+constexpr uint32_t kPartMaxBits = SWA_PART_MAX_BITS;              // bits per level (512 bins) — 10 for the one-level key partition in front of k_group1;
                                                   // 2048 bins were tried: the flat count array — bins x tiles — grows with them and costs more than a level
 constexpr unsigned long long kRecAbsent = ~0ull;  // a record slot that holds nothing (amplicon without this window / not owned)
 constexpr uint32_t kMaxIdx = 2;                   // indexes handled per launch (blockIdx.y)
@@ -477,7 +477,6 @@ __global__ __launch_bounds__(256) void k_guard_records(const GuardRecArgs a) {
 struct PartIdx {
   const unsigned long long * in;
   unsigned long long * out;
-  uint32_t * out32;                  // last level of the link sort: only the low halves (targets) are kept
   uint64_t out_cap;                  // entries the output buffers hold (writes beyond are dropped: the caller grows and repeats)
   const uint64_t * cstart;           // [chunks + 1] first record of chunk c (or [chunks] when csize is given); nullptr: chunk c
   uint64_t cstride;                  // ... begins at c * cstride (the per-wave link segments; with csize), or — ONE chunk, no csize — is [0, cstride)
@@ -770,11 +769,10 @@ __device__ __forceinline__ uint64_t block_exclusive_scan_of(uint64_t v, uint64_t
   return wave_off + incl - v;
 }
 
-// MODE 0: records; 2: only the low halves are written (out32)
 // THREADS: 512 a workgroup, 1024 for the tile of 8192 — the staging area (22–76 KB) allows one to three workgroups a CU,
 // so the waves that hide the loads' and stores' way are a matter of the workgroup's size
 // (SPAN: told to stay within the 64 registers that four 512-thread workgroups a CU need — it came out at 70)
-template <int MODE, uint32_t TILE, uint32_t BINS, uint32_t THREADS, bool SPAN = false>
+template <uint32_t TILE, uint32_t BINS, uint32_t THREADS, bool SPAN = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN && THREADS == 512 ? 8 : 1))) void k_part_scatter(const PartArgs a) {
   constexpr uint32_t kPartPer = TILE / THREADS;
   // (dynamic LDS — part_scatter_lds bytes: a tile of 8192 records with 1024 bins is 76 KB, beyond what a kernel gets unasked)
@@ -851,7 +849,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
         const uint32_t d = (((uint32_t)(r >> 32) - a.bias) >> a.shift) & (bins - 1u);
         const uint64_t g = (uint64_t)goff[d] + (j - lstart[d]);
         if (g < p.out_cap) {
-          if (MODE == 2) { p.out32[g] = (uint32_t)r; } else { p.out[g] = r; }
+          p.out[g] = r;
         }
       }
     }
@@ -913,7 +911,7 @@ struct GroupArgs {
 constexpr uint32_t kG1Threads = 1024;
 constexpr uint32_t kG1SlotBits = 13, kG1Slots = 1u << kG1SlotBits;      // (a bucket holds ~2200 distinct keys: load ~0.3 — the probe loops run as long as the slowest of 64 lanes)
 constexpr uint32_t kG1DupBits = 14, kG1DupSlots = 1u << kG1DupBits;
-constexpr uint32_t kG1Target = 10240;            // records per bucket the partition aims at (on average, at most)
+constexpr uint32_t kG1Target = SWA_G1_TARGET;           // records per bucket the partition aims at (on average, at most)
 constexpr size_t kG1LdsBytes = kG1Slots * 4 * 2 + kG1DupSlots * 4;
 static_assert(kG1Slots * 4 <= kG1DupSlots * 4, "the groups' places lie in the area behind the two tables");
 constexpr uint32_t kG1OverBit = 0x80000000u;     // toff: the group is left to the plain kernel
@@ -1394,7 +1392,7 @@ __global__ __launch_bounds__(256) void k_stream_fallback(const uint32_t * __rest
 // link-rich sources sit together at its start: buckets with more links than a wave stages are listed and taken by a
 // whole workgroup each (k_csr_bucket_big); what even that cannot stage is placed directly in the neighbour array and
 // sorted there, one row at a time through LDS.
-constexpr uint32_t kCsrMaxR = 9;                  // sources per bucket: 2^r, r <= this
+constexpr uint32_t kCsrMaxR = SWA_CSR_MAX_R;                 // sources per bucket: 2^r, r <= this
 constexpr uint32_t kCsrStage = 1024;              // links a wave stages in LDS
 constexpr uint32_t kCsrBigStage = 8192;           // links a workgroup stages in LDS
 struct CsrArgs {

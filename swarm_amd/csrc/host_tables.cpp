@@ -4,6 +4,7 @@
 // compared word for word with the oracle; no output of the program depends on them.
 #include "swa_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <random>
 
@@ -115,5 +116,71 @@ void swa_fast_plan_report(const swa_fast_plan & p, uint32_t out[8]) {
 extern "C" int swa_d1_fastidious_plan_for(uint32_t longest, uint32_t pair_longest, int split, int bloom, int words, uint32_t out[8]) {
   if (out == nullptr || longest == 0) { return SWA_E_ARG; }
   swa_fast_plan_report(swa_fast_plan_for(longest, pair_longest, split != 0, bloom != 0, words != 0), out);
+  return SWA_OK;
+}
+
+// ---- the forms of the key partition and of the link partition (d1.hip: build_stream_index, csr_from_chunks) ----------
+// Pure host arithmetic, no HIP call: what d1.hip launches and what swa_d1_part_plan reports have this one source.
+
+// total_bits spread over as few levels of at most max_bits as hold them, the earlier levels one bit wider where it does not divide
+swa_part_levels swa_plan_levels(uint32_t total_bits, uint32_t max_bits) {
+  swa_part_levels p{};
+  p.total = std::max(1u, total_bits);
+  p.levels = (p.total + max_bits - 1) / max_bits;
+  for (uint32_t l = 0; l < p.levels; ++l) { p.bits[l] = p.total / p.levels + (l < p.total % p.levels ? 1u : 0u); }
+  return p;
+}
+
+// buckets of ~10 000 records for k_group1: ONE partition level of up to 10 bits at 10 M amplicons
+swa_part_plan swa_part_plan_for(uint64_t records, uint32_t extra_bits, bool routed, uint32_t forced_bits) {
+  const uint32_t most = 3 * SWA_PART_MAX_BITS;
+  uint32_t total_bits = 1;
+  if (forced_bits != 0) { total_bits = std::min(forced_bits, most); }
+  else { while ((records >> total_bits) > SWA_G1_TARGET && total_bits < most) { ++total_bits; } }
+  total_bits = std::min<uint32_t>(total_bits + extra_bits, most);
+  swa_part_plan p{};
+  // (one level of up to 1024 bins, or levels of up to 512: the partition has 1024-bin forms for one level only)
+  p.lv = total_bits <= SWA_PART_WIDE_BITS ? swa_plan_levels(total_bits, SWA_PART_WIDE_BITS) : swa_plan_levels(total_bits);
+  // the first partition level's histogram is taken on the way (one read pass over the records less: 0.07 ms at 10 M);
+  // not for routed id lists (their length is the device's to know)
+  p.keys_hist = !routed;
+  p.wide = total_bits > SWA_PART_MAX_BITS && p.lv.levels == 1;
+  // tiles of 2048 records for 512 bins; one level of 1024 bins: 4096 (or the flat count array — bins x tiles — and the 16-byte
+  // runs a tile leaves per bin cost more than the saved level: 0.56 -> 0.43 ms at 10 M amplicons) — or 8192 when k_keys takes
+  // the histogram (k_part_hist holds 4096 a workgroup): a tile then leaves runs of 64 bytes per bin, whole lines (key
+  // partition 0.239 -> 0.225 ms at 10 M)
+  p.tile = p.wide ? (p.keys_hist ? 8192u : 4096u) : 2048u;
+  return p;
+}
+
+void swa_part_plan_report(const swa_part_plan & p, uint32_t out[8]) {
+  out[0] = p.lv.total; out[1] = p.lv.levels;
+  for (uint32_t l = 0; l < 3; ++l) { out[2 + l] = l < p.lv.levels ? p.lv.bits[l] : 0u; }
+  out[5] = p.tile; out[6] = p.keys_hist ? 1u : 0u; out[7] = p.wide ? 1u : 0u;
+}
+
+extern "C" int swa_d1_part_plan_for(uint64_t records, uint32_t extra_bits, int routed, uint32_t forced_bits, uint32_t out[8]) {
+  if (out == nullptr || forced_bits > 3 * SWA_PART_MAX_BITS) { return SWA_E_ARG; }
+  swa_part_plan_report(swa_part_plan_for(records, extra_bits, routed != 0, forced_bits), out);
+  return SWA_OK;
+}
+
+// The links are partitioned by the top bits of their source until a bucket holds 2^r consecutive sources: r = 8 (fewer
+// for a handful of sources), 9 where that saves a third level
+swa_csr_plan swa_csr_plan_for(uint32_t count) {
+  swa_csr_plan p{};
+  p.nbits = 1;
+  while (p.nbits < 32 && ((uint64_t)1 << p.nbits) < count) { ++p.nbits; }
+  p.r = std::min<uint32_t>(8, p.nbits - 1);
+  if (p.nbits - p.r > 2 * SWA_PART_MAX_BITS) { p.r = std::min<uint32_t>(SWA_CSR_MAX_R, p.nbits - 2 * SWA_PART_MAX_BITS); }
+  p.lv = swa_plan_levels(p.nbits - p.r);
+  return p;
+}
+
+extern "C" int swa_d1_csr_plan_for(uint32_t count, uint32_t out[6]) {
+  if (out == nullptr || count == 0) { return SWA_E_ARG; }
+  const swa_csr_plan p = swa_csr_plan_for(count);
+  out[0] = p.nbits; out[1] = p.r; out[2] = p.lv.levels;
+  for (uint32_t l = 0; l < 3; ++l) { out[3 + l] = l < p.lv.levels ? p.lv.bits[l] : 0u; }
   return SWA_OK;
 }

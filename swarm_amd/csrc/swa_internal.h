@@ -229,6 +229,12 @@ struct swa_ctx {
   uint64_t list_regions_items = 0;   // entries of an index's item buffer (d1.hip: list_regions)
   bool stream_index = false;     // the anchor indexes in place were made by the streaming build: members = ids in d_members
   uint32_t stream_extra_bits = 0;   // finer partition after a bucket held more distinct keys than the group kernel's table
+  // the key partition of the index in place, as swa_d1_part_plan reports it, and where its bucket starts lie (u64 entries
+  // into d_stream[kSbStart + i]; the link partition of a network call reuses those buffers: part_starts_valid falls then)
+  uint32_t part_plan[8] = {};
+  uint64_t part_starts_at = 0;
+  uint32_t part_buckets = 0;
+  bool part_starts_valid = false;
   swa_dbuf d_stream[30];         // indexed by kSb* (below)
   // member index: hash table + Bloom of the members of oversized groups only (what the plain kernel probes for them)
   bool member_index = false, only_oversized = false;
@@ -349,6 +355,26 @@ uint32_t swa_fast_count_slots(uint32_t longest);
 uint32_t swa_fast_cap();
 swa_fast_plan swa_fast_plan_for(uint32_t longest, uint32_t pair_longest, bool split, bool bloom, bool words);
 void swa_fast_plan_report(const swa_fast_plan & p, uint32_t out[8]);
+
+// The forms of the two partitions of the d = 1 step (host_tables.cpp: pure arithmetic; d1.hip launches from it,
+// swa_d1_part_plan_for / swa_d1_csr_plan_for / swa_d1_part_plan report it)
+#define SWA_PART_MAX_BITS 9u                        // bits per partition level (512 bins); the one-level key partition takes 10
+#define SWA_PART_WIDE_BITS 10u
+#define SWA_G1_TARGET 10240u                        // records per bucket the key partition aims at (k_group1)
+#define SWA_CSR_MAX_R 9u                            // sources per bucket of the row kernels: 2^r, r <= this
+struct swa_part_levels { uint32_t levels; uint32_t bits[4]; uint32_t total; };
+swa_part_levels swa_plan_levels(uint32_t total_bits, uint32_t max_bits = SWA_PART_MAX_BITS);
+struct swa_part_plan {
+  swa_part_levels lv;
+  uint32_t tile;                 // records per tile: 2048 (512 bins), 8192 / 4096 (the one level of 1024 bins, whole database / routed)
+  bool keys_hist;                // k_keys takes the first level's histogram on the way (not for routed builds)
+  bool wide;                     // one level of 1024 bins
+};
+// forced_bits != 0 (SWA_D1_PART_BITS, a test hook) stands in for the bit count derived from `records`
+swa_part_plan swa_part_plan_for(uint64_t records, uint32_t extra_bits, bool routed, uint32_t forced_bits);
+void swa_part_plan_report(const swa_part_plan & p, uint32_t out[8]);
+struct swa_csr_plan { uint32_t nbits, r; swa_part_levels lv; };
+swa_csr_plan swa_csr_plan_for(uint32_t count);
 
 // ---- device helpers -------------------------------------------------------------
 #ifdef __HIPCC__

@@ -42,6 +42,7 @@ def main() -> None:
     assert not ctx.d1_index_build()
     nwin = ctx.d1_anchor_width() // 32
     print(f"anchor windows: {32 * nwin} nt")
+    print(f"key partition: {ctx.d1_part_plan()}")            # (SWA_D1_PART_BITS, if set, shows here)
     counters = np.zeros(128, dtype=np.uint64)
     ctx._check(ctx.lib.swa_d1_debug_read(ctx.h, 14, counters.ctypes.data, counters.nbytes))
     counters = counters.view(np.uint32)
