@@ -335,8 +335,10 @@ int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, uint64_t li
    SWA_FAST_BLOOM / SWA_FAST_PAIRS; SWA_FAST_LONG: below), so valid once a database is resident; the launches read the same plan.
    out[0] pair route on (1) or the Bloom route for every pair (0); [1] pair kernel: 5, 8, 13 = k_fast_pairs_lines on
    that many register words, 0 = k_fast_pairs on the packed words; [2] count kernel: 5, 8 = k_fast_count_sites, 0 =
-   k_fast_count (the LDS set); [3] waves per block of k_fast_count, [4] slots of a wave's set, [5] its dynamic LDS in
-   bytes (all 0 where it does not run); [6] Bloom route: the Zobrist table in LDS (1) or read from memory (0);
+   k_fast_count (the LDS set), 1 = k_fast_count_sites_words (the sites rule on words staged in LDS: SWA_FAST_LONG=pairs
+   and SWA_FAST_COUNT=sites, below); [3] waves per block of k_fast_count or k_fast_count_sites_words, [4] slots of a
+   wave's set (0 without a set), [5] the count kernel's dynamic LDS in bytes ([3] .. [5] all 0 under the register
+   forms); [6] Bloom route: the Zobrist table in LDS (1) or read from memory (0);
    [7] the shortest sequence the pair route takes (a pair with a shorter member goes the Bloom route). */
 int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]);
 /* SWA_FAST_LONG=split (opt-in; without it nothing below applies and the plan is the one above).  k_fast_count's LDS set
@@ -361,11 +363,31 @@ int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]);
    result; swa_d1_fastidious and swa_d1_fastidious_plan run that pass only under the split.
    swa_d1_fastidious_plan_for: the same dispatch as a pure function of (longest sequence, pair_longest, the three
    switches as 0 / 1), out laid out as in swa_d1_fastidious_plan; no context, no device.  pair_longest is read only
-   when split != 0 and longest > cap. */
+   when split != 0 and longest > cap.
+
+   SWA_FAST_LONG=pairs (opt-in, and like the split only where the longest sequence exceeds 1004 nt and SWA_FAST_BLOOM=1
+   is not set): the pair route itself serves the long sequences.  The count kernel of the whole pass is then
+   k_fast_count_sites_words, which keeps no set and no Zobrist table: one wave a pair, both sequences staged in LDS as
+   words + 3 64-bit words each, so 8 * waves * 2 * (words + 3) bytes, and the cap C is the longest sequence that fits
+   160 KB with one wave (10 237 words = 327 584 nt; four waves up to 2 557 words = 81 824 nt).  The pair kernel is
+   k_fast_pairs.  Every pair whose two lengths lie in [112, C] takes the pair route; the Bloom route keeps what the
+   split's rule leaves it with C in the place of cap.  SWA_FAST_SITES_CAP=n (a test hook) lowers C to n where
+   1004 <= n <= the derived cap, and is ignored otherwise.  The plan is [1, 0, 1, waves, 0, LDS bytes, [6], 112].
+   swa_d1_fastidious_split then reports out[0] = 2, [1] = C, [2] the longest sequence <= C, [3] the amplicons longer
+   than C (the length pass is cached per upload and cap).
+   SWA_FAST_COUNT=sites (a comparison switch, same results): wherever the plan would run k_fast_count (a served length
+   of 256 .. 1004, with or without the split), k_fast_count_sites_words runs in its place; out[2] = 1, [1] as without
+   it.  No effect on the register forms or on the Bloom route.  Unknown values of either variable change nothing.
+   swa_d1_fastidious_plan_modes: the dispatch with every switch as a pure function; long_mode 0 / 1 = split / 2 = pairs,
+   sites_cap 0 = derived.  With long_mode <= 1 and count_sites = 0 it equals swa_d1_fastidious_plan_for.
+   swa_d1_fastidious_sites_cap: C for a value of SWA_FAST_SITES_CAP (0: unset). */
 int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]);
 int swa_d1_fastidious_plan_for(uint32_t longest, uint32_t pair_longest, int split, int bloom, int words, uint32_t out[8]);
+int swa_d1_fastidious_plan_modes(uint32_t longest, uint32_t pair_longest, int long_mode, int bloom, int words, int count_sites,
+                                 uint32_t sites_cap, uint32_t out[8]);
+uint32_t swa_d1_fastidious_sites_cap(uint32_t sites_cap);
 /* Of the last swa_d1_fastidious[_shard] call: out[0] pairs within two edits found by the pair route, [1] light and
-   [2] heavy amplicons handed to the Bloom route (those of the short band and, under the split, of the long band),
+   [2] heavy amplicons handed to the Bloom route (those of the short band and, under the split or pairs, of the long band),
    [3] attempts the pair list took (2 or more: it was regrown; 0: the pair route did not run). */
 int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]);
 

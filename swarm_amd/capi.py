@@ -76,7 +76,7 @@ EXPORTS = [
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_links_split", "swa_d1_csr_from_lists",
-    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_qgram_build", "swa_qgram_diff",
+    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_fastidious_plan_modes", "swa_d1_fastidious_sites_cap", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_qgram_build", "swa_qgram_diff",
     "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
@@ -137,6 +137,9 @@ def load_library() -> C.CDLL:
     lib.swa_d1_fastidious_totals.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_split.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_plan_for.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.swa_d1_fastidious_plan_modes.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+    lib.swa_d1_fastidious_sites_cap.argtypes = [C.c_uint32]
+    lib.swa_d1_fastidious_sites_cap.restype = C.c_uint32
     lib.swa_d1_part_plan_for.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]
     lib.swa_d1_part_plan.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_csr_plan_for.argtypes = [C.c_uint32, C.c_void_p]
@@ -194,6 +197,25 @@ def fastidious_plan_for(longest: int, pair_longest: int = 0, split: bool = False
     if rc != SWA_OK:
         raise SwaError(rc, "swa_d1_fastidious_plan_for: bad argument")
     return [int(v) for v in out]
+
+
+def fastidious_plan_modes(longest: int, pair_longest: int = 0, long_mode: int = 0, bloom: bool = False, words: bool = False,
+                          count_sites: bool = False, sites_cap: int = 0) -> list:
+    """swa_d1_fastidious_plan_modes: fastidious_plan_for with every switch.  long_mode: 0, 1 = SWA_FAST_LONG=split, 2 =
+    SWA_FAST_LONG=pairs (pair_longest: the longest sequence <= the cap in effect, read where longer ones exist);
+    count_sites: SWA_FAST_COUNT=sites; sites_cap: SWA_FAST_SITES_CAP (0: the derived cap)."""
+    out = np.zeros(8, dtype=np.uint32)
+    rc = load_library().swa_d1_fastidious_plan_modes(int(longest), int(pair_longest), int(long_mode), int(bloom), int(words),
+                                                     int(count_sites), int(sites_cap), _ptr(out))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_d1_fastidious_plan_modes: bad argument")
+    return [int(v) for v in out]
+
+
+def fastidious_sites_cap(sites_cap: int = 0) -> int:
+    """swa_d1_fastidious_sites_cap: the longest sequence SWA_FAST_LONG=pairs keeps on the pair route — derived from the
+    LDS of k_fast_count_sites_words, or `sites_cap` (SWA_FAST_SITES_CAP) where that lies in [1004, the derived cap]."""
+    return int(load_library().swa_d1_fastidious_sites_cap(int(sites_cap)))
 
 
 def part_plan_for(records: int, extra_bits: int = 0, routed: bool = False, forced_bits: int = 0) -> list:
@@ -707,15 +729,15 @@ class Context:
         return graft, counters
 
     def d1_fastidious_plan(self) -> list:
-        """swa_d1_fastidious_plan: [pair route, pair kernel words (0: packed words), count kernel words (0: the LDS set),
-        k_fast_count's waves, slots, LDS bytes, Zobrist table in LDS on the Bloom route, kFastMinLen]"""
+        """swa_d1_fastidious_plan: [pair route, pair kernel words (0: packed words), count kernel words (0: the LDS set,
+        1: k_fast_count_sites_words), the count kernel's waves, slots, LDS bytes, Zobrist table in LDS on the Bloom route, kFastMinLen]"""
         out = np.zeros(8, dtype=np.uint32)
         self._check(self.lib.swa_d1_fastidious_plan(self.h, _ptr(out)))
         return [int(v) for v in out]
 
     def d1_fastidious_split(self) -> list:
-        """swa_d1_fastidious_split: [1 when SWA_FAST_LONG=split divides the pass for the resident database, the cap of the
-        pair route, the longest sequence <= cap, amplicons longer than cap]"""
+        """swa_d1_fastidious_split: [1 when SWA_FAST_LONG=split divides the pass for the resident database (2: SWA_FAST_LONG=pairs
+        serves it), the cap of the pair route in effect, the longest sequence <= cap, amplicons longer than cap]"""
         out = np.zeros(4, dtype=np.uint32)
         self._check(self.lib.swa_d1_fastidious_split(self.h, _ptr(out)))
         return [int(v) for v in out]

@@ -2367,8 +2367,8 @@ extern "C" int swa_d1_part_plan(const swa_ctx * ctx, uint32_t out[8]) {
 
 // ---- seam B2: the fastidious second pass --------------------------------------------------
 // algo_d1_run's fastidious branch (src/algod1.cc:1337-1467).  Two routes, chosen per PAIR of
-// (heavy, light) amplicons by the shorter of the two lengths (and, under SWA_FAST_LONG=split, the longer):
-//   pair route  (both >= kFastMinLen, and both <= the cap under the split; d1_fast.inc): groups by shared
+// (heavy, light) amplicons by the shorter of the two lengths (and, under SWA_FAST_LONG=split or =pairs, the longer):
+//   pair route  (both >= kFastMinLen, and both <= the cap under the split / pairs; d1_fast.inc): groups by shared
 //               32-nt windows, exact "within two edits" test per pair, exact |V1(h) ∩ V1(x)| per surviving pair;
 //   Bloom route (every other pair; the reference's own scheme): light-only table + Bloom,
 //               every microvariant of every light amplicon clears its k pattern bits in the flexible
@@ -2502,36 +2502,57 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
 //   >= 1005      none: k_fast_count's set no longer fits 160 KB; Bloom route, Zobrist table in LDS up to 3070 nt
 // SWA_FAST_LONG=split, longest > cap (= 1004, swa_fast_cap): the row of pair_longest, the longest sequence <= cap, with
 // k_fast_pairs as the pair kernel, for the pairs whose two lengths lie in [112, cap]; the Bloom route for every other pair.
+// SWA_FAST_LONG=pairs, longest > 1004: k_fast_pairs and k_fast_count_sites_words (4 / 2 / 1 waves, two staged sequences a
+// wave and nothing else in LDS) for the pairs whose two lengths lie in [112, C], C = swa_fast_sites_cap() = 327 584 nt (or
+// SWA_FAST_SITES_CAP, a test hook); where longer sequences exist, the split's division at C.
+// SWA_FAST_COUNT=sites: k_fast_count_sites_words on the rows of k_fast_count (256 .. 1004), a comparison switch.
 using FastPlan = swa_fast_plan;
 
 // pair_longest, and how many amplicons are longer than the cap / can be half of a pair with one that is: a fact of the
-// uploaded database, read once
-static int ensure_length_classes(swa_ctx * ctx) {
-  if (ctx->fast_classes_ready) { return SWA_OK; }
+// uploaded database and the cap (the split's, or the one of SWA_FAST_LONG=pairs: the environment is read at every call),
+// read once for each
+static int ensure_length_classes(swa_ctx * ctx, uint32_t cap) {
+  if (ctx->fast_classes_ready && ctx->fast_classes_cap == cap) { return SWA_OK; }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
   auto * out = reinterpret_cast<uint32_t *>(static_cast<uint64_t *>(ctx->d_fcounters.ptr) + 12);
   SWA_HIP(ctx, hipMemsetAsync(out, 0, 4 * sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(k_fast_length_classes, dim3(grid_for(ctx, ctx->db.n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n,
-                     swa_fast_cap(), out);
+                     cap, out);
   SWA_HIP(ctx, hipGetLastError());
   uint32_t host[4] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->fast_pair_longest = host[0]; ctx->fast_n_long = host[1]; ctx->fast_n_band = host[2];
   ctx->fast_classes_ready = true;
+  ctx->fast_classes_cap = cap;
   return SWA_OK;
 }
 
-static int fast_plan(swa_ctx * ctx, FastPlan & p) {
+// SWA_FAST_SITES_CAP=n, a test hook: the cap of SWA_FAST_LONG=pairs (swa_fast_sites_cap_in_effect decides whether it counts)
+static uint32_t fast_sites_cap_hook() {
+  const char * env = getenv("SWA_FAST_SITES_CAP");
+  const long long v = env != nullptr ? atoll(env) : 0;
+  return v > 0 && v <= 0xFFFFFFFFll ? (uint32_t)v : 0u;
+}
+
+// long_cap: the cap of the division at the long end that the switches ask for (SWA_FAST_LONG=pairs: C; else the split's)
+static int fast_plan(swa_ctx * ctx, FastPlan & p, uint32_t * long_cap = nullptr) {
   const char * env_route = getenv("SWA_FAST_BLOOM");          // test hook: the reference's scheme for every pair
   const char * env_fp = getenv("SWA_FAST_PAIRS");             // =words: the round-2 pair kernel, which walks the packed sequences — comparison switch
   const char * env_long = getenv("SWA_FAST_LONG");            // =split: keep the pair route for the pairs up to the cap when longer sequences exist
   const bool bloom = env_route != nullptr && env_route[0] == '1';
-  const bool split = env_long != nullptr && strcmp(env_long, "split") == 0 && !bloom && ctx->db.longest > swa_fast_cap();
+  const char * env_count = getenv("SWA_FAST_COUNT");          // =sites: k_fast_count_sites_words where k_fast_count would run — comparison switch
+  const bool past_cap = !bloom && ctx->db.longest > swa_fast_cap();
+  const bool split = env_long != nullptr && strcmp(env_long, "split") == 0 && past_cap;
+  const bool pairs = env_long != nullptr && strcmp(env_long, "pairs") == 0 && past_cap;   // =pairs: the pair route serves the long sequences
+  const uint32_t sites_cap = fast_sites_cap_hook();
+  const uint32_t cap = pairs ? swa_fast_sites_cap_in_effect(sites_cap) : swa_fast_cap();
+  if (long_cap != nullptr) { *long_cap = cap; }
   uint32_t pair_longest = 0;
-  if (split) { SWA_TRY(ensure_length_classes(ctx)); pair_longest = ctx->fast_pair_longest; }
-  p = swa_fast_plan_for(ctx->db.longest, pair_longest, split, bloom, env_fp != nullptr && env_fp[0] == 'w');
+  if ((split || pairs) && ctx->db.longest > cap) { SWA_TRY(ensure_length_classes(ctx, cap)); pair_longest = ctx->fast_pair_longest; }
+  p = swa_fast_plan_modes(ctx->db.longest, pair_longest, pairs ? 2 : (split ? 1 : 0), bloom, env_fp != nullptr && env_fp[0] == 'w',
+                          env_count != nullptr && strcmp(env_count, "sites") == 0, sites_cap);
   return SWA_OK;
 }
 
@@ -2550,11 +2571,11 @@ extern "C" int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
   if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_split: no database is resident"); }
   FastPlan p{};
-  SWA_TRY(fast_plan(ctx, p));
-  const uint32_t cap = swa_fast_cap();
+  uint32_t cap = 0;
+  SWA_TRY(fast_plan(ctx, p, &cap));
   const bool longer = ctx->db.longest > cap;
-  if (longer) { SWA_TRY(ensure_length_classes(ctx)); }
-  out[0] = p.split ? 1u : 0u;
+  if (longer) { SWA_TRY(ensure_length_classes(ctx, cap)); }
+  out[0] = (uint32_t)p.long_mode;
   out[1] = cap;
   out[2] = longer ? ctx->fast_pair_longest : ctx->db.longest;
   out[3] = longer ? ctx->fast_n_long : 0u;
@@ -2667,7 +2688,16 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
     c.zlen = plan.served + 2u; c.maxwords = (plan.served + 31u) >> 5; c.slots = slots;
     c.pairs = static_cast<const unsigned long long *>(ctx->d_fpairs.ptr); c.npairs = npairs;
     c.graft = static_cast<uint32_t *>(ctx->d_graft.ptr); c.cand_counter = fc + 2;
-    if (plan.count_w != 0) {
+    if (plan.count_words) {
+      // two staged sequences a wave: no set, no Zobrist table (c.zobrist, c.zlen and c.slots are not read)
+      uint64_t blocks = (npairs + count_waves - 1) / count_waves;
+      const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
+      if (blocks > max_blocks) { blocks = max_blocks; }
+      const dim3 gc((uint32_t)blocks);
+      if (count_waves == 4) { hipLaunchKernelGGL(k_fast_count_sites_words<4>, gc, dim3(256), plan.count_lds, ctx->stream, c); }
+      else if (count_waves == 2) { hipLaunchKernelGGL(k_fast_count_sites_words<2>, gc, dim3(128), plan.count_lds, ctx->stream, c); }
+      else { hipLaunchKernelGGL(k_fast_count_sites_words<1>, gc, dim3(64), plan.count_lds, ctx->stream, c); }
+    } else if (plan.count_w != 0) {
       uint64_t blocks = (npairs + kWaves - 1) / kWaves;
       const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
       if (blocks > max_blocks) { blocks = max_blocks; }
@@ -2738,7 +2768,7 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   const bool pair_route = plan.pair_route;
   for (uint64_t & t : ctx->fast_totals) { t = 0; }
   const uint32_t min_len = pair_route ? kFastMinLen : 0xFFFFFFFFu;
-  const uint32_t max_len = plan.max_len;                     // (0xFFFFFFFF without the split)
+  const uint32_t max_len = plan.max_len;                     // (0xFFFFFFFF without a division at the long end)
 
   SWA_TRY(swa_reserve(ctx, ctx->d_frole, n));
   SWA_TRY(swa_reserve(ctx, ctx->d_light, n));
@@ -2756,7 +2786,7 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   hipLaunchKernelGGL(k_fast_variant_totals, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                      ctx->db.seqlen, static_cast<const uint8_t *>(ctx->d_frole.ptr), n, fc);
   const uint32_t short_cut = pair_route ? kFastMinLen + 1u : 0xFFFFFFFFu;   // len <= cut: may pair with a sequence < kFastMinLen
-  const uint32_t long_cut = plan.split ? max_len - 1u : 0xFFFFFFFFu;        // len >= cut: may pair with a sequence > the cap
+  const uint32_t long_cut = max_len != 0xFFFFFFFFu ? max_len - 1u : 0xFFFFFFFFu;   // len >= cut: may pair with a sequence > the cap (split, pairs)
   hipLaunchKernelGGL(k_fast_band_lists, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen,
                      static_cast<const uint8_t *>(ctx->d_frole.ptr), n, short_cut, long_cut, static_cast<uint8_t *>(ctx->d_light.ptr),
                      static_cast<uint32_t *>(ctx->d_list_a.ptr), static_cast<uint32_t *>(ctx->d_list_b.ptr), fc + 6);

@@ -32,6 +32,10 @@
 // SWA_FAST_LONG=split adds the same division at the long end: k_fast_count's LDS set holds the microvariants of a
 // sequence of up to cap = 1004 nt (swa_fast_cap), so where longer sequences exist the groups are made of the amplicons
 // of kFastMinLen .. cap nt only (FastGroupArgs.max_len) and the pairs with a longer member keep the Bloom route too.
+// SWA_FAST_LONG=pairs serves those sequences on the pair route instead: neither the join (k_fg_light / k_fg_heavy key 32-nt
+// windows) nor k_fast_pairs (which walks packed words) has a length bound, and k_fast_count_sites_words counts a pair from
+// two staged copies alone, so its cap is 327 584 nt (swa_fast_sites_cap); SWA_FAST_COUNT=sites runs that kernel in
+// k_fast_count's place on 256 .. 1004 nt, for comparison.
 
 constexpr uint32_t kFastMinLen = SWA_FAST_MIN_LEN;   // (112) both sequences at least this long => the pair route is complete
 constexpr uint32_t kFastMid = 40;         // middle window of a heavy amplicon: [40, 72); light: 39, 40, 41
@@ -557,6 +561,117 @@ __global__ __launch_bounds__(kThreads) void k_fast_count_sites(const FastCountAr
         for (int w = 0; w < W; ++w) { v[w] = swa_variant_word(hw, nwh, type, p, base, (uint32_t)w); }
         const uint32_t lv = type == 0u ? (uint32_t)lh : (type == 1u ? (uint32_t)lh - 1u : (uint32_t)lh + 1u);
         near = one_edit_apart<W>(Xw, (uint32_t)lx, v, lv);
+      }
+      found += (uint32_t)__popcll(__ballot(near));
+    }
+    if (found != 0u) {
+      if (lane == 0) { atomicMin(&a.graft[x], h); }
+      total += found;
+    }
+  }
+  if (lane == 0 && total != 0ull) { atomicAdd(a.cand_counter, total); }
+}
+
+// ---- the same rule on words staged in LDS, any length (SWA_FAST_LONG=pairs, SWA_FAST_COUNT=sites) ---------------------------
+// k_fast_count_sites keeps both sequences in W register words and so ends at 255 nt; k_fast_count's set ends at 1004.  Here
+// h and x are staged per wave in dynamic LDS (maxwords + 3 words each, zero behind the sequence: no set, no Zobrist table),
+// the word count is a run-time value and nothing is materialised:
+//   P, E      the words dealt to the lanes in strides of 64, min / max over the wave; the end alignment's shifted word of x
+//             takes its neighbour word from LDS;
+//   positions exactly those of k_fast_count_sites, both forms; a homopolymer run may span many words: the walk back is
+//             uniform over the wave and ends at position 0 at the latest;
+//   the test  lane = (position, slot); the microvariant's words come from swa_variant_word as the loops ask for them, and
+//             "v is one edit from x" is one_edit_apart (d1_anchor.inc) with a run-time word count: lcp = the first mismatch
+//             of the forward words, hb = the last mismatch of the shorter against the longer moved down by one nucleotide
+//             (equal lengths: unmoved); one edit apart <=> hb < lcp (lengths n, n + 1), hb == lcp (equal lengths).  Each loop
+//             stops at the word that holds its mismatch, which IS lcp / hb: no word is skipped on an assumption.
+// tests/test_fastidious_long_identity.py restates all of it on 64-bit words and checks it against the set intersection.
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_fast_count_sites_words(const FastCountArgs a) {
+  extern __shared__ uint64_t lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t seed_words = a.maxwords + 3u;
+  uint64_t * swx = lds + (size_t)wave * 2u * seed_words;
+  uint64_t * swh = swx + seed_words;
+  unsigned long long total = 0;
+  const uint64_t nwaves = (uint64_t)gridDim.x * WAVES;
+  for (uint64_t k = (uint64_t)blockIdx.x * WAVES + wave; k < a.npairs; k += nwaves) {
+    const unsigned long long pr = a.pairs[k];
+    const uint32_t h = (uint32_t)(pr >> 32), x = (uint32_t)pr;
+    const int lh = (int)a.seqlen[h], lx = (int)a.seqlen[x];
+    const uint32_t nwh = ((uint32_t)lh + 31u) >> 5, nwx = ((uint32_t)lx + 31u) >> 5;
+    const uint32_t nmax = max(nwh, nwx);                      // <= maxwords
+    const uint64_t * gx = a.seqs + a.seq_off[x];
+    const uint64_t * gh = a.seqs + a.seq_off[h];
+    wave_lds_sync();                                          // (the previous pair's words are no longer read)
+    // every index read below is < nmax + 3 <= seed_words
+    for (uint32_t w = (uint32_t)lane; w < nmax + 3u; w += 64u) { swx[w] = w < nwx ? gx[w] : 0ull; swh[w] = w < nwh ? gh[w] : 0ull; }
+    wave_lds_sync();
+    // P: first position where h and x differ;  E: last position of h that differs from x aligned at the ends
+    const int dl = lx - lh;                                   // -2 .. 2
+    int P = min(lh, lx), E = -1;
+    for (uint32_t i = (uint32_t)lane; i < nmax; i += 64u) {
+      const uint64_t hv = swh[i], xv = swx[i];
+      const uint64_t d0 = hv ^ xv;
+      if (d0 != 0ull) { P = min(P, (int)(32u * i) + (__builtin_ctzll(d0) >> 1)); }
+      // x moved by dl nucleotides so that its end meets h's end: xs[q] = x[q + dl]
+      const uint64_t lo = i > 0u ? swx[i - 1u] : 0ull, hi = swx[i + 1u];
+      uint64_t xs = xv;
+      if (dl == 1) { xs = (xv >> 2) | (hi << 62); }
+      else if (dl == 2) { xs = (xv >> 4) | (hi << 60); }
+      else if (dl == -1) { xs = (xv << 2) | (lo >> 62); }
+      else if (dl == -2) { xs = (xv << 4) | (lo >> 60); }
+      uint64_t d = hv ^ xs;
+      if (i == 0u && dl < 0) { d |= dl == -1 ? 3ull : 15ull; }             // positions of h before x's first nucleotide: differences
+      if (d != 0ull) { E = max(E, (int)(32u * i) + ((63 - __builtin_clzll(d)) >> 1)); }
+    }
+    for (int o = 32; o > 0; o >>= 1) { P = min(P, __shfl_xor(P, o, 64)); E = max(E, __shfl_xor(E, o, 64)); }
+    P = min(P, lh - 1);
+    E = min(max(E, 0), lh - 1);
+    const int first = min(P, E), last = max(P, E);
+    int q = max(first - 1, 0);                                // start of the run that touches the interval
+    while (q > 0 && swa_nt(swh, (uint32_t)q - 1u) == swa_nt(swh, (uint32_t)q)) { --q; }
+    const int lo_pos = max(q - 1, 0), hi_pos = min(last + 1, lh);
+    // two edits far apart: the two neighbourhoods only (k_fast_count_sites has the argument)
+    int q2 = max(last - 1, 0);
+    while (q2 > 0 && swa_nt(swh, (uint32_t)q2 - 1u) == swa_nt(swh, (uint32_t)q2)) { --q2; }
+    const int lo_b = max(q2 - 1, 0), hi_a = min(first + 1, lh);
+    const bool two_windows = P <= E && lo_b > hi_a;
+    const int n_a = two_windows ? hi_a - lo_pos + 1 : hi_pos - lo_pos + 1;
+    const int slots = (n_a + (two_windows ? hi_pos - lo_b + 1 : 0)) * 8;
+    uint32_t found = 0;
+    for (int t0 = 0; t0 < slots; t0 += 64) {
+      const int t = t0 + lane;
+      const int at = t >> 3;
+      const uint32_t p = (uint32_t)(at < n_a ? lo_pos + at : lo_b + (at - n_a));
+      const uint32_t slot = (uint32_t)t & 7u;
+      bool ok = t < slots;
+      const uint32_t prevc = (ok && p >= 1u) ? swa_nt(swh, p - 1u) : 4u;
+      const uint32_t c = (ok && p < (uint32_t)lh) ? swa_nt(swh, p) : 4u;
+      uint32_t type, base;
+      if (slot < 4u) { type = 2u; base = slot; ok = ok && (p == 0u || base != prevc); }                       // insertion before p
+      else if (slot < 7u) { type = 0u; const uint32_t t3 = slot - 4u; base = t3 < c ? t3 : t3 + 1u; ok = ok && p < (uint32_t)lh; }
+      else { type = 1u; base = 0u; ok = ok && p < (uint32_t)lh && (p == 0u || c != prevc); }                  // deletion, once per run
+      const int lv = type == 0u ? lh : (type == 1u ? lh - 1 : lh + 1);
+      const int dv = lv - lx;                                 // v against x: one edit apart needs -1 .. 1
+      bool near = false;
+      if (ok && dv >= -1 && dv <= 1) {
+        const bool v_longer = dv == 1, shifted = dv != 0;
+        const uint32_t nw = ((uint32_t)max(lv, lx) + 31u) >> 5;   // words of the longer one: <= nmax + 1
+        int lcp = 0x7fffffff, hb = -1;
+        for (uint32_t w = 0; w < nw; ++w) {
+          const uint64_t d = swa_variant_word(swh, nwh, type, p, base, w) ^ swx[w];
+          if (d != 0ull) { lcp = (int)(32u * w) + (__builtin_ctzll(d) >> 1); break; }
+        }
+        uint64_t v_next = 0ull, x_next = 0ull;                // word nw of either is zero
+        for (uint32_t w = nw; w-- > 0u; ) {
+          const uint64_t vw = swa_variant_word(swh, nwh, type, p, base, w), xw = swx[w];
+          const uint64_t lw = v_longer ? vw : xw, ln = v_longer ? v_next : x_next, sw = v_longer ? xw : vw;
+          const uint64_t d = sw ^ (shifted ? ((lw >> 2) | (ln << 62)) : lw);
+          if (d != 0ull) { hb = (int)(32u * w) + ((63 - __builtin_clzll(d)) >> 1); break; }
+          v_next = vw; x_next = xw;
+        }
+        near = shifted ? hb < lcp : hb == lcp;
       }
       found += (uint32_t)__popcll(__ballot(near));
     }

@@ -62,7 +62,7 @@ size_t swa_fast_count_lds(uint32_t longest, uint32_t slots, int waves) {
 uint32_t swa_fast_count_slots(uint32_t longest) {
   uint32_t slots = 1024;
   const uint64_t v = 7ull * longest + 4ull;
-  while (slots < v + v / 2) { slots <<= 1; }
+  while (slots < v + v / 2 && slots < (1u << 31)) { slots <<= 1; }   // (2^31 slots fit no LDS: the search ends there for any length)
   return slots;
 }
 
@@ -77,12 +77,64 @@ uint32_t swa_fast_cap() {
   return cap;
 }
 
-swa_fast_plan swa_fast_plan_for(uint32_t longest, uint32_t pair_longest, bool split, bool bloom, bool words) {
+// LDS of k_fast_count_sites_words for `waves` waves per block: per wave two sequence copies (words + 3), nothing else;
+// 0 = does not fit 160 KB
+size_t swa_fast_sites_lds(uint32_t longest, int waves) {
+  const size_t maxwords = ((size_t)longest + 31u) >> 5;
+  const size_t bytes = sizeof(uint64_t) * (size_t)waves * 2ull * (maxwords + 3u);
+  return bytes <= 160u * 1024u ? bytes : 0;
+}
+
+// the longest sequence k_fast_count_sites_words serves (one wave per block): 10 237 words = 327 584 nt
+uint32_t swa_fast_sites_cap() {
+  static const uint32_t cap = [] {
+    uint32_t words = 1;
+    while (swa_fast_sites_lds(32u * (words + 1u), 1) != 0) { ++words; }
+    return 32u * words;
+  }();
+  return cap;
+}
+
+// the cap of SWA_FAST_LONG=pairs: the derived one, or a lower one from the test hook (counted only within [swa_fast_cap(),
+// the derived cap])
+uint32_t swa_fast_sites_cap_in_effect(uint32_t sites_cap) {
+  return sites_cap >= swa_fast_cap() && sites_cap <= swa_fast_sites_cap() ? sites_cap : swa_fast_sites_cap();
+}
+
+static void plan_count_sites_words(swa_fast_plan & p) {
+  p.count_words = true;
+  p.count_w = 0;
+  p.count_waves = 0;
+  p.slots = 0;
+  for (int w : {4, 2, 1}) { if (p.count_waves == 0 && swa_fast_sites_lds(p.served, w) != 0) { p.count_waves = w; } }
+  p.count_lds = p.count_waves != 0 ? swa_fast_sites_lds(p.served, p.count_waves) : 0;
+}
+
+swa_fast_plan swa_fast_plan_modes(uint32_t longest, uint32_t pair_longest, int long_mode, bool bloom, bool words, bool count_sites,
+                                  uint32_t sites_cap) {
   swa_fast_plan p{};
   const uint32_t cap = swa_fast_cap();
+  p.max_len = 0xFFFFFFFFu;
+  // SWA_FAST_LONG=pairs: only where the longest sequence alone would send every pair to the Bloom route.  Every sequence
+  // up to C stays on the pair route; where longer ones exist, the division of the split at C instead of cap.
+  if (long_mode == 2 && !bloom && longest > cap) {
+    const uint32_t C = swa_fast_sites_cap_in_effect(sites_cap);
+    const uint32_t served = longest <= C ? longest : pair_longest;
+    if (served >= SWA_FAST_MIN_LEN && served <= C) {
+      p.long_mode = 2;
+      p.served = served;
+      p.max_len = longest <= C ? 0xFFFFFFFFu : C;
+      p.pair_route = true;
+      p.pair_w = 0;                                           // k_fast_pairs, which walks the packed sequences
+      plan_count_sites_words(p);
+      p.zobrist_lds = 4ull * ((size_t)longest + 2u) * sizeof(uint64_t) <= SWA_MAX_ZOBRIST_LDS;
+      return p;
+    }
+  }
   // the division at the long end (SWA_FAST_LONG=split): only where the longest sequence alone would send every pair to the
   // Bloom route, and where some pair is left for the pair route
-  p.split = split && !bloom && longest > cap && pair_longest >= SWA_FAST_MIN_LEN && pair_longest <= cap;
+  p.split = long_mode == 1 && !bloom && longest > cap && pair_longest >= SWA_FAST_MIN_LEN && pair_longest <= cap;
+  p.long_mode = p.split ? 1 : 0;
   const uint32_t served = p.split ? pair_longest : longest;   // the longest sequence the pair route has to hold
   p.served = served;
   p.max_len = p.split ? cap : 0xFFFFFFFFu;
@@ -96,19 +148,26 @@ swa_fast_plan swa_fast_plan_for(uint32_t longest, uint32_t pair_longest, bool sp
   // the latter: the lines' width, and whether they exist, follow the whole database.
   p.pair_w = (words || p.split) ? 0 : (served <= 160u ? 5 : (served <= 256u ? 8 : (served <= 416u ? 13 : 0)));
   p.count_w = served <= 159u ? 5 : (served <= 255u ? 8 : 0);
+  // SWA_FAST_COUNT=sites: k_fast_count_sites_words where k_fast_count would run
+  if (count_sites && p.pair_route && p.count_w == 0) { plan_count_sites_words(p); }
   // the Bloom route stages the whole Zobrist table: by the longest sequence of the database, split or not
   p.zobrist_lds = 4ull * ((size_t)longest + 2u) * sizeof(uint64_t) <= SWA_MAX_ZOBRIST_LDS;
   return p;
 }
 
+swa_fast_plan swa_fast_plan_for(uint32_t longest, uint32_t pair_longest, bool split, bool bloom, bool words) {
+  return swa_fast_plan_modes(longest, pair_longest, split ? 1 : 0, bloom, words, false, 0u);
+}
+
 void swa_fast_plan_report(const swa_fast_plan & p, uint32_t out[8]) {
-  const bool set = p.pair_route && p.count_w == 0;           // k_fast_count runs
+  const bool set = p.pair_route && p.count_w == 0 && !p.count_words;   // k_fast_count runs
+  const bool staged = p.pair_route && p.count_words;                    // k_fast_count_sites_words runs
   out[0] = p.pair_route ? 1u : 0u;
   out[1] = p.pair_route ? (uint32_t)p.pair_w : 0u;
-  out[2] = p.pair_route ? (uint32_t)p.count_w : 0u;
-  out[3] = set ? (uint32_t)p.count_waves : 0u;
+  out[2] = staged ? 1u : (p.pair_route ? (uint32_t)p.count_w : 0u);
+  out[3] = set || staged ? (uint32_t)p.count_waves : 0u;
   out[4] = set ? p.slots : 0u;
-  out[5] = set ? (uint32_t)p.count_lds : 0u;
+  out[5] = set || staged ? (uint32_t)p.count_lds : 0u;
   out[6] = p.zobrist_lds ? 1u : 0u;
   out[7] = SWA_FAST_MIN_LEN;
 }
@@ -118,6 +177,15 @@ extern "C" int swa_d1_fastidious_plan_for(uint32_t longest, uint32_t pair_longes
   swa_fast_plan_report(swa_fast_plan_for(longest, pair_longest, split != 0, bloom != 0, words != 0), out);
   return SWA_OK;
 }
+
+extern "C" int swa_d1_fastidious_plan_modes(uint32_t longest, uint32_t pair_longest, int long_mode, int bloom, int words,
+                                            int count_sites, uint32_t sites_cap, uint32_t out[8]) {
+  if (out == nullptr || longest == 0 || long_mode < 0 || long_mode > 2) { return SWA_E_ARG; }
+  swa_fast_plan_report(swa_fast_plan_modes(longest, pair_longest, long_mode, bloom != 0, words != 0, count_sites != 0, sites_cap), out);
+  return SWA_OK;
+}
+
+extern "C" uint32_t swa_d1_fastidious_sites_cap(uint32_t sites_cap) { return swa_fast_sites_cap_in_effect(sites_cap); }
 
 // ---- the forms of the key partition and of the link partition (d1.hip: build_stream_index, csr_from_chunks) ----------
 // Pure host arithmetic, no HIP call: what d1.hip launches and what swa_d1_part_plan reports have this one source.

@@ -206,8 +206,9 @@ struct swa_ctx {
   uint64_t fast_pair_cap = 0;
   uint64_t fast_totals[4] = {};  // of the last pass: pairs found, light / heavy amplicons of the Bloom route's bands, attempts of the pair list
   // length classes of the database against the pair route's cap (k_fast_length_classes; read once per upload, and only
-  // where the longest sequence exceeds the cap: by the pass under SWA_FAST_LONG=split, by swa_d1_fastidious_split always): the longest sequence <= cap (0: none), amplicons > cap, amplicons >= cap - 1
+  // where the longest sequence exceeds the cap: by the pass under SWA_FAST_LONG=split or =pairs, by swa_d1_fastidious_split always): the longest sequence <= cap (0: none), amplicons > cap, amplicons >= cap - 1
   bool fast_classes_ready = false;
+  uint32_t fast_classes_cap = 0;  // ... the cap they were read against (SWA_FAST_LONG=pairs has its own)
   uint32_t fast_pair_longest = 0, fast_n_long = 0, fast_n_band = 0;
 
   // d >= 2 in bulk (dn_graph.hip): the graph of all pairs within d differences, kept sorted on the device
@@ -341,19 +342,27 @@ uint64_t swa_hashtable_size(uint64_t n);                                       /
 struct swa_fast_plan {
   bool pair_route;               // false: the Bloom route for every pair
   int pair_w;                    // k_fast_pairs_lines<., W>: 5, 8, 13; 0 = k_fast_pairs on the packed words
-  int count_w;                   // k_fast_count_sites<W>: 5, 8; 0 = k_fast_count
-  int count_waves;               // k_fast_count: waves per block, slots of a wave's set, dynamic LDS
+  int count_w;                   // k_fast_count_sites<W>: 5, 8; 0 = k_fast_count, or
+  bool count_words;              // k_fast_count_sites_words (SWA_FAST_LONG=pairs, SWA_FAST_COUNT=sites)
+  int count_waves;               // k_fast_count / k_fast_count_sites_words: waves per block, slots of a wave's set (0: no set), dynamic LDS
   uint32_t slots;
   size_t count_lds;
   bool zobrist_lds;              // Bloom route: the Zobrist table sits in LDS
   bool split;                    // SWA_FAST_LONG=split in effect: pairs with a member longer than max_len take the Bloom route
   uint32_t served;               // the longest sequence the pair route holds: the database's, under the split pair_longest
-  uint32_t max_len;              // the longest sequence the pair route takes (0xFFFFFFFF without the split)
+  uint32_t max_len;              // the longest sequence the pair route takes (0xFFFFFFFF: no bound)
+  int long_mode;                 // the division at the long end in effect: 0 none, 1 SWA_FAST_LONG=split, 2 =pairs
 };
 size_t swa_fast_count_lds(uint32_t longest, uint32_t slots, int waves);
 uint32_t swa_fast_count_slots(uint32_t longest);
 uint32_t swa_fast_cap();
 swa_fast_plan swa_fast_plan_for(uint32_t longest, uint32_t pair_longest, bool split, bool bloom, bool words);
+size_t swa_fast_sites_lds(uint32_t longest, int waves);         // k_fast_count_sites_words
+uint32_t swa_fast_sites_cap();
+uint32_t swa_fast_sites_cap_in_effect(uint32_t sites_cap);
+// ... with every switch: long_mode 0 / 1 = split / 2 = pairs, SWA_FAST_COUNT=sites, SWA_FAST_SITES_CAP (0: derived)
+swa_fast_plan swa_fast_plan_modes(uint32_t longest, uint32_t pair_longest, int long_mode, bool bloom, bool words, bool count_sites,
+                                  uint32_t sites_cap);
 void swa_fast_plan_report(const swa_fast_plan & p, uint32_t out[8]);
 
 // The forms of the two partitions of the d = 1 step (host_tables.cpp: pure arithmetic; d1.hip launches from it,
