@@ -295,6 +295,12 @@ int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out_bytes);
 int swa_d1_part_plan_for(uint64_t records, uint32_t extra_bits, int routed, uint32_t forced_bits, uint32_t out[8]);
 int swa_d1_part_plan(const swa_ctx * ctx, uint32_t out[8]);
 int swa_d1_csr_plan_for(uint32_t count, uint32_t out[6]);
+/* ... and the work lists behind the key partition: 1 when every workgroup of k_group_lists finds the positions of its
+   buckets' items itself (up to 1024 buckets), 0 when the counts are scanned by two launches first.
+   swa_d1_lists_form_for: as a pure function of the number of buckets (2^total bits of the plan); -1 for 0 buckets.
+   swa_d1_lists_form: what the streaming index in place was built with; -1 without such an index. */
+int swa_d1_lists_form_for(uint64_t buckets);
+int swa_d1_lists_form(const swa_ctx * ctx);
 uint64_t swa_d1_table_size(const swa_ctx * ctx);
 
 /* The same network computed into the context's own HBM buffers and kept there (no host copy):

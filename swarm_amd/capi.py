@@ -76,7 +76,7 @@ EXPORTS = [
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_links_split", "swa_d1_csr_from_lists",
-    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_fastidious_plan_modes", "swa_d1_fastidious_sites_cap", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_qgram_build", "swa_qgram_diff",
+    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_fastidious_plan_modes", "swa_d1_fastidious_sites_cap", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_d1_lists_form_for", "swa_d1_lists_form", "swa_qgram_build", "swa_qgram_diff",
     "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
@@ -143,6 +143,8 @@ def load_library() -> C.CDLL:
     lib.swa_d1_part_plan_for.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]
     lib.swa_d1_part_plan.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_csr_plan_for.argtypes = [C.c_uint32, C.c_void_p]
+    lib.swa_d1_lists_form_for.argtypes = [C.c_uint64]
+    lib.swa_d1_lists_form.argtypes = [C.c_void_p]
     lib.swa_qgram_build.argtypes = [C.c_void_p]
     lib.swa_qgram_diff.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.swa_qgram_debug_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -227,6 +229,15 @@ def part_plan_for(records: int, extra_bits: int = 0, routed: bool = False, force
     if rc != SWA_OK:
         raise SwaError(rc, "swa_d1_part_plan_for: bad argument")
     return [int(v) for v in out]
+
+
+def lists_form_for(buckets: int) -> int:
+    """swa_d1_lists_form_for: how the work lists behind a key partition of `buckets` buckets get their positions: 1 inside
+    k_group_lists, 0 by the two-launch scan of the counts."""
+    form = load_library().swa_d1_lists_form_for(int(buckets))
+    if form < 0:
+        raise SwaError(2, "swa_d1_lists_form_for: bad argument")
+    return form
 
 
 def csr_plan_for(count: int) -> list:
@@ -703,6 +714,13 @@ class Context:
         out = np.zeros(count, dtype=np.uint64)
         self._check(self.lib.swa_d1_debug_read(self.h, what, _ptr(out), out.nbytes))
         return out
+
+    def d1_lists_form(self) -> int:
+        """swa_d1_lists_form: the form the work lists of the streaming index in place were built with (lists_form_for)"""
+        form = self.lib.swa_d1_lists_form(self.h)
+        if form < 0:
+            raise SwaError(2, "swa_d1_lists_form: no streaming index in place")
+        return form
 
     def d1_part_plan(self) -> list:
         """swa_d1_part_plan: the key partition of the streaming index in place, laid out as part_plan_for() with the bits

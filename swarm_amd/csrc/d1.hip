@@ -668,8 +668,11 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_apply(const uint32_t * __re
 // guard; seg_fill + nseg, + 2 nseg: pass 0, pass 1) -> out[2], out[3]
 // (one workgroup of 1024 threads, eight loads in flight per thread: the 8192 fills of an MI355X in one round — with 256
 // threads and a load per turn this single workgroup took 11 us of every step)
+// ... and the count of fallback seeds next to them in the head of the status block (fallback_copy: the host's one copy).
+// The CSR route takes all of this in the first k_part_tiles of its link partition (d1_stream.inc: SegArgs); this kernel
+// serves the edge-list route.
 __global__ __launch_bounds__(1024) void k_seg_reduce(const uint32_t * __restrict__ seg_fill, uint32_t nseg,
-                                                     unsigned long long * out) {
+                                                     unsigned long long * out, const uint32_t * fallback, uint32_t * fallback_copy) {
   __shared__ unsigned long long ssum[16], smax[16], sst0[16], sst1[16];
   unsigned long long sum = 0, mx = 0, st0 = 0, st1 = 0;
   for (uint32_t base = 0; base < nseg; base += 8192u) {
@@ -695,6 +698,7 @@ __global__ __launch_bounds__(1024) void k_seg_reduce(const uint32_t * __restrict
     unsigned long long s = 0, m = 0, a0 = 0, a1 = 0;
     for (int w = 0; w < 16; ++w) { s += ssum[w]; m = m > smax[w] ? m : smax[w]; a0 += sst0[w]; a1 += sst1[w]; }
     out[0] = s; out[1] = m; out[2] = a0; out[3] = a1;
+    *fallback_copy = *fallback;
   }
 }
 
@@ -846,6 +850,8 @@ static int launch_abundance_rank(swa_ctx * ctx) {
     return SWA_OK;
   }
   ctx->rank_ready = true;
+  // (the flag is this database's from here on: the index build's clear leaves it alone)
+  SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags + kFlagUnordered, 0, sizeof(uint32_t), ctx->stream));
   const uint32_t n = ctx->db.n;
   const uint32_t tiles = (n + 255u) / 256u;
   SWA_TRY(swa_reserve(ctx, ctx->d_arank, uint64_t(n) * sizeof(uint32_t)));
@@ -882,6 +888,8 @@ struct PartJob {
   uint32_t bias = 0, top_bit = 32;
   uint32_t tile = 4096;                             // records per tile: 4096 (links), 2048 / 4096 / 8192 (key records: run_partition)
   bool hist0_done = false;                          // the flat counts of level 0 are there already (k_keys<W, true>)
+  bool tiles0_done = false;                         // ... and its tile table (one chunk of a size the host knows)
+  const SegArgs * seg = nullptr;                    // level 0's chunks are the per-wave link segments: k_part_tiles reduces their fills on the way
   PartPlan plan{};
   // scratch, per set
   uint32_t * cnt[kMaxIdx] = {}; uint32_t * ctile[kMaxIdx] = {}; uint64_t * starts[kMaxIdx] = {}; uint32_t * partial[kMaxIdx] = {};
@@ -968,8 +976,13 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
     }
     // (a multiple of 8 workgroups: turn v of the tile loops then stays on XCD v mod 8 — xcd_tile)
     const dim3 grid_t((unsigned)((std::min<uint64_t>(std::max<uint64_t>(tiles, 1), (uint64_t)cu_grid) + 7) & ~7ull), j.nidx);
-    if (chunks > 2048) { hipLaunchKernelGGL(k_part_tiles<1024>, dim3(1, j.nidx), dim3(1024), 0, ctx->stream, a); }
-    else { hipLaunchKernelGGL(k_part_tiles<256>, dim3(1, j.nidx), dim3(256), 0, ctx->stream, a); }
+    if (hist_done && j.tiles0_done) { /* (k_keys has left the three entries of the single chunk's table) */ }
+    else if (l == 0 && j.seg != nullptr) {
+      if (chunks > 2048) { hipLaunchKernelGGL((k_part_tiles<1024, true>), dim3(1, 1), dim3(1024), 0, ctx->stream, a, *j.seg); }
+      else { hipLaunchKernelGGL((k_part_tiles<256, true>), dim3(1, 1), dim3(256), 0, ctx->stream, a, *j.seg); }
+    }
+    else if (chunks > 2048) { hipLaunchKernelGGL(k_part_tiles<1024>, dim3(1, j.nidx), dim3(1024), 0, ctx->stream, a, SegArgs{}); }
+    else { hipLaunchKernelGGL(k_part_tiles<256>, dim3(1, j.nidx), dim3(256), 0, ctx->stream, a, SegArgs{}); }
     if (hist_done) { /* (k_keys has left the counts) */ }
     else if (wide) { hipLaunchKernelGGL((k_part_hist<1024, kPartTileMax, 256>), grid_t, dim3(256), 0, ctx->stream, a); }
     else if (a.span != 0u) { hipLaunchKernelGGL((k_part_hist<512, kPartTileMax, 256, true>), grid_t, dim3(256), 0, ctx->stream, a); }
@@ -994,9 +1007,9 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
     else if (j.tile == 2048) { hipLaunchKernelGGL((k_part_scatter<2048, 512, 512>), grid_t, dim3(512), part_scatter_lds(2048, 512), ctx->stream, a); }
     else if (a.span != 0u) { hipLaunchKernelGGL((k_part_scatter<4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
     else { hipLaunchKernelGGL((k_part_scatter<4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
+    // (the scatter has written the bucket starts on its way: part_write_starts)
     chunks = (single ? 1 : chunks) << bits;
     single = false;
-    hipLaunchKernelGGL(k_part_starts, dim3((unsigned)std::min<uint64_t>((chunks + 256) / 256, (uint64_t)cu_grid), j.nidx), dim3(256), 0, ctx->stream, a);
     SWA_HIP(ctx, hipGetLastError());
   }
   j.buckets = (uint32_t)chunks;
@@ -1033,6 +1046,8 @@ static int ensure_lines(swa_ctx * ctx) {
 // order (d_stream[kSbMembers + which]: ids), the work lists of the pair kernels, the flags build_owned_index reads
 // (kFlagDuplicates, kFlagKeyOverflow, kFlagUnserved, kFlagOversized / kFlagOverMass, kFlagShortest).
 static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_count) {
+  const bool clear_head = ctx->head_clear_pending;            // (swa_d1_index_build_range: the first build of the call)
+  ctx->head_clear_pending = false;
   ctx->anchor_ready = false;
   ctx->stream_index = false;
   ctx->list_counts_ready = false;
@@ -1090,14 +1105,24 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   {
     ClearList c{};
     clear_add(c, st->counters, sizeof(st->counters));
-    clear_add(c, st->guard, kGuardCall * sizeof(uint64_t));    // the guard's index counters: this build's
+    if (clear_head) {
+      // the head of the status block for a new index: the flags — but kFlagUnordered, which the abundance ranks in front of
+      // this build have just set or left at 0 (launch_abundance_rank) —, the stats, the guard's counters up to its second
+      // opinion.  (A retry, or the build of a network call, comes with its flags cleared by its caller and clears the
+      // guard's index counters alone.)
+      static_assert(kFlagDuplicates == 0 && kFlagUnordered == 1, "status block: the flags around kFlagUnordered");
+      clear_add(c, st->flags + kFlagDuplicates, sizeof(uint32_t));
+      clear_add(c, st->flags + kFlagUnordered + 1, offsetof(swa_status_block, guard) + kGuardKeys * sizeof(uint64_t) - (kFlagUnordered + 1) * sizeof(uint32_t));
+    } else {
+      clear_add(c, st->guard, kGuardCall * sizeof(uint64_t));  // the guard's index counters: this build's
+    }
     clear_add(c, ctx->d_stream[kSbOver].ptr, ((uint64_t)n + 8) & ~3ull);
     // (the entry behind the last bucket's counts of each index: the scan of the counts reads one past the end)
     for (int i = 0; i < 2; ++i) { clear_add(c, static_cast<uint32_t *>(ctx->d_stream[kSbKind + i].ptr) + (uint64_t)kListsPerIndex * buckets, sizeof(uint32_t)); }
     SWA_TRY(clear_launch(ctx, c));
   }
   swa_lap(ctx, "buffers reserved, counters cleared");
-  uint32_t * dflags = st->flags;                            // (cleared by the caller: index build, or the retry)
+  uint32_t * dflags = st->flags;                            // (cleared above — a new index — or by the caller: a retry, a network call's build)
   auto * scal = static_cast<uint64_t *>(ctx->d_stream[kSbScal].ptr);      // [0..3] level-0 chunk tables, [8 + i] totals (u32)
   const uint32_t win_a = ctx->anchor_a, win_b = ctx->anchor_b;
   const uint32_t minlen = anchor_minlen(ctx), window_mode = (win_a != 0 || win_b != 0) ? 1u : 0u;
@@ -1137,12 +1162,16 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   if (by_rec) { /* nothing to key */ }
   else if (keys_hist) {
     const uint32_t ntiles = (uint32_t)((records + j.tile - 1) / j.tile);
-    for (int i = 0; i < 2; ++i) { k.hist_cnt[i] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt + i].ptr); }
+    for (int i = 0; i < 2; ++i) {
+      k.hist_cnt[i] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt + i].ptr);
+      k.hist_ctile[i] = static_cast<uint32_t *>(ctx->d_stream[kSbTile + i].ptr);
+    }
     k.hist_bits = j.plan.bits[0]; k.hist_tile = j.tile; k.hist_ntiles = ntiles;
     k.hist_run_bits = j.max_tiles0 >= (uint64_t)ctx->num_cus * 8 ? 4u : 0u;
     const dim3 hgrid((unsigned)((std::min<uint64_t>(ntiles, (uint64_t)ctx->num_cus * 8) + 7) & ~7ull), 1u);
     hipLaunchKernelGGL(k_keys<true>, hgrid, dim3(256), 0, ctx->stream, k);
     j.hist0_done = true;
+    j.tiles0_done = true;
   } else {
     const dim3 kgrid((unsigned)grid_for(ctx, records, 256, 8), routed ? 2u : 1u);
     hipLaunchKernelGGL(k_keys<false>, kgrid, dim3(256), 0, ctx->stream, k);
@@ -1231,10 +1260,20 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     x.l.counters = st->counters + kCounterBase + (uint32_t)i * kWidthClasses * 8u;
     x.l.pair_big = g.pair_big;
   }
-  const dim3 grid_k((unsigned)std::min<uint64_t>(((uint64_t)kListsPerIndex * buckets + kFlatChunk) / kFlatChunk, (uint64_t)ctx->num_cus * 8), 2);
-  hipLaunchKernelGGL(k_flat_sums, grid_k, dim3(256), 0, ctx->stream, f);
-  hipLaunchKernelGGL(k_flat_apply, grid_k, dim3(256), 0, ctx->stream, f);
-  hipLaunchKernelGGL(k_group_lists, dim3((unsigned)std::min<uint64_t>((buckets + 3) / 4, (uint64_t)ctx->num_cus * 8), 2), dim3(256), 0, ctx->stream, la);
+  const dim3 grid_l((unsigned)std::min<uint64_t>((buckets + 3) / 4, (uint64_t)ctx->num_cus * 8), 2);
+  if (plan.lists_inline) {
+    // (every workgroup adds up the counts before its buckets itself — only the lists of width classes this database has)
+    uint32_t mask = 0;
+    for (uint32_t c = 0; c < kWidthClasses; ++c) { if (ctx->class_pop[c] != 0) { mask |= ((1u << kListKinds) - 1u) << (c * kListKinds); } }
+    for (int i = 0; i < 2; ++i) { la.x[i].list_mask = mask; }
+    hipLaunchKernelGGL(k_group_lists<true>, grid_l, dim3(256), 0, ctx->stream, la);
+  } else {
+    const dim3 grid_k((unsigned)std::min<uint64_t>(((uint64_t)kListsPerIndex * buckets + kFlatChunk) / kFlatChunk, (uint64_t)ctx->num_cus * 8), 2);
+    hipLaunchKernelGGL(k_flat_sums, grid_k, dim3(256), 0, ctx->stream, f);
+    hipLaunchKernelGGL(k_flat_apply, grid_k, dim3(256), 0, ctx->stream, f);
+    hipLaunchKernelGGL(k_group_lists<false>, grid_l, dim3(256), 0, ctx->stream, la);
+  }
+  ctx->lists_form = plan.lists_inline ? 1 : 0;
   SWA_HIP(ctx, hipGetLastError());
   swa_lap(ctx, "groups + work lists");
   ctx->list_regions_items = item_room;
@@ -1244,6 +1283,9 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   return SWA_OK;
 }
 
+// the list of the buckets k_csr_bucket leaves to whole workgroups, its count in front: a word per bucket of the CSR over `count` sources
+static uint64_t csr_heavy_bytes(uint32_t count) { return ((1ull << swa_csr_plan_for(count).lv.total) + 2) * sizeof(uint32_t); }
+
 // CSR of the links in the per-wave segments by the streaming route: the links partitioned by the top bits of their
 // source (relative to `first`) until a bucket holds 2^r consecutive sources, then one wave per bucket (k_csr_bucket).
 // link_cap: entries of the two internal link buffers; a run with more links than that leaves garbage and is repeated
@@ -1252,7 +1294,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
 // segments of the pair kernels, or the ranks' lists of a multi-GPU job gathered on one device)
 static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const unsigned long long * links, const uint64_t * d_cstart, uint64_t cstride,
                            const uint32_t * d_csize, uint32_t chunks, uint32_t csize_cap, uint64_t max_tiles0, uint64_t link_cap,
-                           uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap) {
+                           uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap, const SegArgs * seg = nullptr, bool heavy_cleared = false) {
   const swa_csr_plan plan = swa_csr_plan_for(count);          // (host_tables.cpp)
   const uint32_t nbits = plan.nbits, r = plan.r;
   PartJob j;
@@ -1278,6 +1320,7 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   j.buf[0][1] = static_cast<unsigned long long *>(ctx->d_stream[kSbLinkB].ptr);
   j.cstart0[0] = d_cstart; j.cstride0[0] = cstride;
   j.csize0[0] = d_csize;
+  j.seg = d_csize != nullptr && j.nidx == 1 ? seg : nullptr;
   j.cnt[0] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt].ptr);
   j.ctile[0] = static_cast<uint32_t *>(ctx->d_stream[kSbTile].ptr);
   j.starts[0] = static_cast<uint64_t *>(ctx->d_stream[kSbStart].ptr);
@@ -1291,11 +1334,14 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   CsrArgs c{};
   c.links = j.out[0]; c.bstart = j.bstart[0]; c.buckets = j.buckets; c.r = r; c.first = first; c.count = count;
   c.offsets = d_offsets; c.neighbours = d_neighbours; c.cap = d_neighbours != nullptr ? cap : 0;
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbHeavy], ((uint64_t)j.buckets + 2) * sizeof(uint32_t)));
+  const void * heavy_before = ctx->d_stream[kSbHeavy].ptr;
+  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbHeavy], csr_heavy_bytes(count)));
   c.heavy = static_cast<uint32_t *>(ctx->d_stream[kSbHeavy].ptr) + 1;
   c.heavy_count = static_cast<uint32_t *>(ctx->d_stream[kSbHeavy].ptr);
   c.end_copy = &swa_status(ctx)->csr_end;
-  SWA_HIP(ctx, hipMemsetAsync(c.heavy_count, 0, sizeof(uint32_t), ctx->stream));
+  // (the anchored network call has cleared the count with its other counters — launch_network_anchored — unless the
+  // buffer is a new one since)
+  if (!heavy_cleared || ctx->d_stream[kSbHeavy].ptr != heavy_before) { SWA_HIP(ctx, hipMemsetAsync(c.heavy_count, 0, sizeof(uint32_t), ctx->stream)); }
   swa_t0(ctx, kTimeCsrRows);
   // (as many workgroups as are resident together — every wave walks its share of the buckets; a grid of 8 a CU ran a second,
   // partly empty round behind the first)
@@ -1312,11 +1358,17 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
 }
 
 static int launch_csr_stream(swa_ctx * ctx, uint32_t first, uint32_t count, uint32_t nseg, uint64_t link_cap, uint64_t * d_offsets,
-                             uint32_t * d_neighbours, uint64_t cap) {
+                             uint32_t * d_neighbours, uint64_t cap, bool heavy_cleared) {
+  // (the first level's k_part_tiles also makes of the segment fills what k_seg_reduce does: SegArgs)
+  swa_status_block * st = swa_status(ctx);
+  SegArgs seg{};
+  seg.staged = static_cast<const uint32_t *>(ctx->d_seg_fill.ptr) + nseg;
+  seg.out = reinterpret_cast<unsigned long long *>(st->stats) + kStatSeg;
+  seg.fallback = st->counters + kCounterFallback; seg.fallback_copy = &st->fallback_copy;
   const uint64_t tiles_per_seg = (ctx->seg_cap + 4096 - 1) / 4096;
   return csr_from_chunks(ctx, first, count, static_cast<const unsigned long long *>(ctx->d_edges.ptr), nullptr, ctx->seg_cap,
                          static_cast<const uint32_t *>(ctx->d_seg_fill.ptr), nseg, (uint32_t)std::min<uint64_t>(ctx->seg_cap, 0xFFFFFFFFu),
-                         (uint64_t)nseg * tiles_per_seg + 2, link_cap, d_offsets, d_neighbours, cap);
+                         (uint64_t)nseg * tiles_per_seg + 2, link_cap, d_offsets, d_neighbours, cap, &seg, heavy_cleared);
 }
 
 // the pair kernels by (pass, record width W in words, window width NW in words): W = 5 / 8 / 15 / 21 (width_words), NW = 1 / 2
@@ -1391,6 +1443,9 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
     SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbSched], bytes));
     clear_add(clears, ctx->d_stream[kSbSched].ptr, bytes);
   }
+  // (the CSR stage's count of buckets left to whole workgroups: csr_from_chunks)
+  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbHeavy], csr_heavy_bytes(count)));
+  clear_add(clears, ctx->d_stream[kSbHeavy].ptr, sizeof(uint32_t));
   SWA_TRY(clear_launch(ctx, clears));
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const uint32_t maxwords = (ctx->db.longest + 31u) >> 5;
@@ -1738,10 +1793,13 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
   // (flags, stats and the guard's index / network counters lie together at the head of the status block: one fill, up to
   // the guard's second opinion)
   swa_status_block * st = swa_status(ctx);
-  SWA_HIP(ctx, hipMemsetAsync(st, 0, offsetof(swa_status_block, guard) + kGuardKeys * sizeof(uint64_t), ctx->stream));
   ctx->guard_index = false;
   ctx->anchor_w = 32;
   ctx->anchor_usable = anchor_applicable(ctx);
+  // (the streaming build clears this head with its own counters, one launch: nothing before its clear writes there but the
+  // abundance ranks' kFlagUnordered, which that clear leaves alone; the other route fills it here)
+  ctx->head_clear_pending = ctx->anchor_usable;
+  if (!ctx->anchor_usable) { SWA_HIP(ctx, hipMemsetAsync(st, 0, offsetof(swa_status_block, guard) + kGuardKeys * sizeof(uint64_t), ctx->stream)); }
 
   bool owned_ok = false;                                    // served without the database-wide table
   uint32_t group_dups = 0;
@@ -1980,8 +2038,6 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       SWA_TRY(ensure_full_index(ctx));
       SWA_TRY(launch_network(ctx, no_cluster_breaking, first, count));
     }
-    hipLaunchKernelGGL(k_seg_reduce, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
-                       nseg, reinterpret_cast<unsigned long long *>(st->stats) + kStatSeg);
     const bool check_unserved = ctx->anchor_usable && !ctx->full_index && !ctx->member_index;
     // CSR assembly is enqueued right behind, before the host looks at the totals: every kernel
     // below guards its writes with `cap` / the segment capacity, so a run that turns out to
@@ -1990,6 +2046,8 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     swa_t0(ctx, kTimeCsr);
     if (d_edge_list != nullptr) {
       SWA_TRY(swa_reserve(ctx, ctx->d_seg_base, uint64_t(nseg) * sizeof(uint64_t)));
+      hipLaunchKernelGGL(k_seg_reduce, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
+                         nseg, reinterpret_cast<unsigned long long *>(st->stats) + kStatSeg, st->counters + kCounterFallback, &st->fallback_copy);
       hipLaunchKernelGGL(k_seg_bases, dim3(1), dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr), nseg,
                          static_cast<unsigned long long *>(ctx->d_seg_base.ptr));
       hipLaunchKernelGGL(k_seg_compact, dim3(std::min<uint32_t>(nseg, (uint32_t)ctx->num_cus * 8u)), dim3(256), 0, ctx->stream,
@@ -1998,21 +2056,17 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     } else {
       // CSR: the links sorted by source with the partition primitive
       stream_link_cap = std::max<uint64_t>(std::max<uint64_t>(cap, stream_link_cap), 2ull * count + 1024);
-      SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap));
+      SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap, ctx->anchor_usable));
     }
     SWA_HIP(ctx, hipGetLastError());
     swa_t1(ctx, kTimeCsr);
-    // ONE copy of the status block's head, up to the host's own scratch: flags | stats (links, fullest segment, members
-    // staged) | the guard's counters | last CSR offset, links sorted
+    // ONE copy of the status block's head: flags | stats (links, fullest segment, members staged) | the guard's counters |
+    // last CSR offset, links sorted, fallback seeds listed
     swa_status_block * status = ctx->h_status;               // (the pinned mirror)
     SWA_HIP(ctx, hipMemcpyAsync(status, st, offsetof(swa_status_block, host_unserved), hipMemcpyDeviceToHost, ctx->stream));
-    status->host_unserved = 0;                               // fallback seeds listed while there is no table to serve them
-    if (check_unserved) {
-      SWA_HIP(ctx, hipMemcpyAsync(&status->host_unserved, st->counters + kCounterFallback, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t unserved = status->host_unserved;
-    const uint64_t * seg = status->stats + kStatSeg;          // what k_seg_reduce made of the segments
+    const uint32_t unserved = check_unserved ? status->fallback_copy : 0u;   // fallback seeds listed while there is no table to serve them
+    const uint64_t * seg = status->stats + kStatSeg;          // what was made of the segments (SegArgs / k_seg_reduce)
     const uint64_t fullest = seg[kSegFullest];
     const uint32_t anchor_overflow = status->flags[kFlagKeyOverflow];
     const bool guarded = ctx->anchor_usable;
@@ -2354,6 +2408,12 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
   SWA_HIP(ctx, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SWA_OK;
+}
+
+// How the work lists of the streaming index in place got their positions: 1 inside k_group_lists, 0 by the two-launch scan
+// (swa_lists_inline); -1 without such an index
+extern "C" int swa_d1_lists_form(const swa_ctx * ctx) {
+  return ctx != nullptr && ctx->stream_index && ctx->anchor_ready ? ctx->lists_form : -1;
 }
 
 // The key partition of the streaming index in place: the layout of swa_d1_part_plan_for, with the bits the key-overflow

@@ -16,7 +16,9 @@
 //                    window (the high half of the mixed 64-bit key the tables of round 2 used); records key << 32 | id —
 //                    and, on the way, the first partition level's histogram.
 //   partition        records grouped by the top bits of the key in LDS-staged, coalesced radix levels (k_part_hist /
-//                    flat scan / k_part_scatter: counting sort by digit, tile by tile; no atomics in HBM).  Default:
+//                    flat scan / k_part_scatter: counting sort by digit, tile by tile; no atomics in HBM).  The bucket
+//                    starts a level leaves for the next one (or for k_group1 / k_csr_bucket) are written by the
+//                    scatter launch itself, from the scanned counts (part_write_starts).  Default:
 //                    ONE level of up to 1024 bins until a bucket holds ~10 000 records (k_group1).  Runs of 16 consecutive
 //                    tiles go to one XCD (xcd_tile), whose L2 merges their partial lines.  (Round 3 also carried buckets of
 //                    ~600 records — k_group — and one-pass first levels with decoupled look-back — k_sweep_*: both measured
@@ -295,6 +297,9 @@ struct KeyArgs {
   // part_flat for one segment: digit * tiles + tile); a workgroup then takes whole tiles of hist_tile amplicons
   uint32_t * hist_cnt[kMaxIdx];
   uint32_t hist_bits, hist_tile, hist_ntiles, hist_run_bits;
+  // ... and that level's tile table (what k_part_tiles makes of ONE chunk whose size the host knows: first tile 0, the
+  // number of tiles, the entry behind the last count — the scan's total); nullptr: k_part_tiles runs
+  uint32_t * hist_ctile[kMaxIdx];
 };
 
 // One pass over the lines: per index the key record of every amplicon (the 29-bit key of its window | its width class |
@@ -383,6 +388,11 @@ __global__ __launch_bounds__(256) void k_keys(const KeyArgs a) {
       }
       __syncthreads();
     }
+  }
+  if (HIST && blockIdx.x == 0 && threadIdx.x < kMaxIdx && a.hist_ctile[threadIdx.x] != nullptr) {
+    uint32_t * ctile = a.hist_ctile[threadIdx.x];
+    ctile[0] = 0u; ctile[1] = a.hist_ntiles;
+    a.hist_cnt[threadIdx.x][(uint64_t)a.hist_ntiles << a.hist_bits] = 0u;
   }
   if (which_only < 0) {
     if (unserved) { a.flags[kFlagUnserved] = 1u; }
@@ -508,11 +518,22 @@ __device__ __forceinline__ uint32_t part_chunk_size(const PartIdx & p, uint32_t 
 // first tile of every chunk (one workgroup per index)
 template <uint32_t THREADS> __device__ __forceinline__ uint64_t block_exclusive_scan_of(uint64_t v, uint64_t * smem, uint64_t & total);
 // (THREADS = 1024 for the thousands of link segments: one round of the scan instead of three dependent ones)
-template <uint32_t THREADS>
-__global__ __launch_bounds__(THREADS) void k_part_tiles(const PartArgs a) {
+// SEG — the first level of the link partition of a network call, whose chunks are the per-wave segments of the pair kernels:
+// the same pass over the segment fills yields what k_seg_reduce makes of them (links in all — the fills as they are, not
+// clamped to a segment's capacity —, the fullest segment, the members staged per pass) and leaves, next to it in the head
+// of the status block, the count of fallback seeds: one single-workgroup launch and one copy to the host instead of two each.
+struct SegArgs {
+  const uint32_t * staged;           // [2][chunks] members the pair kernels staged, per pass (behind the fills)
+  unsigned long long * out;          // the status block's stats + kStatSeg: kSegLinks, kSegFullest, kSegStaged + pass
+  const uint32_t * fallback;         // the status block's counters + kCounterFallback ...
+  uint32_t * fallback_copy;          // ... and where the head of the block carries it to the host
+};
+template <uint32_t THREADS, bool SEG = false>
+__global__ __launch_bounds__(THREADS) void k_part_tiles(const PartArgs a, const SegArgs sg) {
   __shared__ uint64_t smem[THREADS / 64u];
   const PartIdx & p = a.p[blockIdx.y];
   uint64_t carry = 0;
+  unsigned long long seg_sum = 0, seg_max = 0, seg_st0 = 0, seg_st1 = 0;
   const bool tile_pow2 = (a.tile & (a.tile - 1u)) == 0u;
   const uint32_t tile_shift = 31u - (uint32_t)__clz((int)a.tile);
   // (rounds of 8 THREADS chunks, eight per thread with their loads in flight together: the 8192 wave segments of the link
@@ -523,7 +544,14 @@ __global__ __launch_bounds__(THREADS) void k_part_tiles(const PartArgs a) {
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k) {
       const uint32_t c = base + threadIdx.x * 8u + k;
-      v[k] = c < p.chunks ? (a.span != 0u ? part_chunk_size(p, c) : (part_chunk_size(p, c) + a.tile - 1u) / a.tile) : 0u;
+      if constexpr (SEG) {
+        const uint32_t fill = c < p.chunks ? p.csize[c] : 0u, size = min(fill, p.csize_cap);
+        v[k] = a.span != 0u ? size : (size + a.tile - 1u) / a.tile;
+        seg_sum += fill; seg_max = seg_max > fill ? seg_max : fill;
+        if (c < p.chunks) { seg_st0 += sg.staged[c]; seg_st1 += sg.staged[(uint64_t)p.chunks + c]; }
+      } else {
+        v[k] = c < p.chunks ? (a.span != 0u ? part_chunk_size(p, c) : (part_chunk_size(p, c) + a.tile - 1u) / a.tile) : 0u;
+      }
     }
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k) { mine += v[k]; }
@@ -559,6 +587,22 @@ __global__ __launch_bounds__(THREADS) void k_part_tiles(const PartArgs a) {
     if (a.span != 0u) { carry = ((uint32_t)carry + a.tile - 1u) / a.tile; }
     p.ctile[p.chunks] = (uint32_t)carry;
     p.cnt[carry << a.bits] = 0u;                              // the entry behind the last count: after the scan, the total
+  }
+  if constexpr (SEG) {
+    __shared__ unsigned long long ssum[THREADS / 64u], smax[THREADS / 64u], sst0[THREADS / 64u], sst1[THREADS / 64u];
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long m2 = swa_shfl_xor_u64(seg_max, o);
+      seg_sum += swa_shfl_xor_u64(seg_sum, o); seg_max = seg_max > m2 ? seg_max : m2;
+      seg_st0 += swa_shfl_xor_u64(seg_st0, o); seg_st1 += swa_shfl_xor_u64(seg_st1, o);
+    }
+    if ((threadIdx.x & 63u) == 0u) { ssum[threadIdx.x >> 6] = seg_sum; smax[threadIdx.x >> 6] = seg_max; sst0[threadIdx.x >> 6] = seg_st0; sst1[threadIdx.x >> 6] = seg_st1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long s = 0, m = 0, a0 = 0, a1 = 0;
+      for (uint32_t w = 0; w < THREADS / 64u; ++w) { s += ssum[w]; m = m > smax[w] ? m : smax[w]; a0 += sst0[w]; a1 += sst1[w]; }
+      sg.out[0] = s; sg.out[1] = m; sg.out[2] = a0; sg.out[3] = a1;
+      *sg.fallback_copy = *sg.fallback;
+    }
   }
 }
 
@@ -769,6 +813,27 @@ __device__ __forceinline__ uint64_t block_exclusive_scan_of(uint64_t v, uint64_t
   return wave_off + incl - v;
 }
 
+// first record of every bucket this level makes: the chunk table of the next level (or of the consumer).  The tail of
+// k_part_scatter (a launch of its own until round 17): the scanned counts it reads are final before that launch starts,
+// and next_start is the half of the ping-pong starts buffer that no workgroup of the launch reads.  Grid-stride: a small
+// input has 8 workgroups and up to 2^17 + 1 entries.  (Behind the tiles, not in front of them, and with 32-bit indices — a
+// level has at most 2^27 buckets: in front, the scatter kernels came out 4-8 registers larger and two of them lost a
+// workgroup a CU.)
+__device__ __forceinline__ void part_write_starts(const PartArgs & a, const PartIdx & p) {
+  const uint32_t buckets = (a.single_seg != 0u ? 1u : p.chunks) << a.bits;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= buckets; i += gridDim.x * blockDim.x) {
+    uint64_t at;
+    if (i == buckets) { at = *p.total; }
+    else if (a.single_seg != 0u) { at = p.cnt[(uint64_t)i * p.ctile[p.chunks]]; }
+    else {
+      // (a chunk without tiles reads the entry of whatever follows it: the position where the next records begin)
+      const uint32_t c = i >> a.bits, b = i & ((1u << a.bits) - 1u), t0 = p.ctile[c];
+      at = p.cnt[((uint64_t)t0 << a.bits) + (uint64_t)b * (p.ctile[c + 1] - t0)];
+    }
+    p.next_start[i] = at;
+  }
+}
+
 // THREADS: 512 a workgroup, 1024 for the tile of 8192 — the staging area (22–76 KB) allows one to three workgroups a CU,
 // so the waves that hide the loads' and stores' way are a matter of the workgroup's size
 // (SPAN: told to stay within the 64 registers that four 512-thread workgroups a CU need — it came out at 70)
@@ -855,22 +920,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SPAN &&
     }
     __syncthreads();
   }
+  part_write_starts(a, p);
 }
 
 constexpr size_t part_scatter_lds(uint32_t tile, uint32_t bins) { return (size_t)tile * 8u + 3u * (size_t)bins * 4u; }
-
-// first record of every bucket this level made: the chunk table of the next level (or of the consumer)
-__global__ __launch_bounds__(256) void k_part_starts(const PartArgs a) {
-  const PartIdx & p = a.p[blockIdx.y];
-  const uint32_t segs = a.single_seg != 0u ? 1u : p.chunks;
-  const uint64_t buckets = (uint64_t)segs << a.bits;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= buckets; i += (uint64_t)gridDim.x * blockDim.x) {
-    if (i == buckets) { p.next_start[i] = *p.total; continue; }
-    const uint32_t c = (uint32_t)(i >> a.bits), b = (uint32_t)i & ((1u << a.bits) - 1u);
-    // (a chunk without tiles reads the entry of whatever follows it: the position where the next records begin)
-    p.next_start[i] = p.cnt[a.single_seg != 0u ? (uint64_t)b * p.ctile[p.chunks] : ((uint64_t)p.ctile[c] << a.bits) + (uint64_t)b * (p.ctile[c + 1] - p.ctile[c])];
-  }
-}
 
 // ---- groups of one bucket -----------------------------------------------------------------------------------------
 // One workgroup per bucket and index.  The bucket's distinct keys go into an LDS table (slot = key << 32 | members so
@@ -1311,32 +1364,71 @@ __global__ __launch_bounds__(kG1Threads) void k_group1(const GroupArgs a) {
 }
 
 // ---- work lists ----------------------------------------------------------------------------------------------------
-// kind_cnt (scanned in place, list-major: entry [l][b] = items of all lists < l plus those of list l in buckets < b)
-// -> every bucket's items into the lists the pair kernels read (PairLists: one region per width class and size kind),
-// the lists' lengths into their counters.  One wave per bucket.
+// kind_cnt (list-major: entry [l][b] = items of list l in bucket b) -> every bucket's items into the lists the pair kernels
+// read (PairLists: one region per width class and size kind), the lists' lengths into their counters.  One wave per bucket.
+// Where a bucket's items go in list l is the number of items of that list in the buckets before it.  Two forms
+// (swa_lists_inline: by the number of buckets alone):
+//   INLINE   up to 1024 buckets: every workgroup adds up, list by list, the counts of the buckets before its own — at most
+//            28 x 1024 values out of L2, and only the lists of width classes the database has —, and the wave of the last
+//            bucket, which then knows the lists' lengths, writes the counters.  No launch but this one.
+//   else     kind_cnt arrives scanned in place by k_flat_sums / k_flat_apply (entry [l][b] = items of all lists < l plus
+//            those of list l in buckets < b, + a closing entry), two launches more.
 struct ListIdx {
   const unsigned long long * items_tmp;
   const uint64_t * bstart;
-  const uint32_t * kind_pos;         // scanned kind_cnt [kListsPerIndex][buckets] + closing entry
+  const uint32_t * kind_pos;         // kind_cnt [kListsPerIndex][buckets]: as k_group1 left it (INLINE), or scanned + closing entry
   uint32_t buckets;
+  uint32_t list_mask;                // (INLINE) bit l: list l may hold items (its width class has sequences)
   PairLists l;
 };
 struct ListArgs { ListIdx x[kMaxIdx]; };
+static_assert(kListsPerIndex <= 32u, "k_group_lists: a bit per list");
 
+template <bool INLINE>
 __global__ __launch_bounds__(256) void k_group_lists(const ListArgs a) {
   const ListIdx & x = a.x[blockIdx.y];
-  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t nwaves = gridDim.x * 4u;
   const uint64_t entries = (uint64_t)kListsPerIndex * x.buckets;
-  for (uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6); b < x.buckets; b += nwaves) {
+  // (INLINE) lbase[l]: items of list l in the buckets before the workgroup's first bucket of this round
+  __shared__ uint32_t lbase[kListsPerIndex], wsum[4][kListsPerIndex];
+  uint32_t summed = 0;                                          // (INLINE) lbase covers the buckets [0, summed)
+  if (INLINE && threadIdx.x < kListsPerIndex) { lbase[threadIdx.x] = 0u; }
+  // (b0: the same for the whole workgroup, so that its barriers are met by every wave)
+  for (uint32_t b0 = blockIdx.x * 4u; b0 < x.buckets; b0 += nwaves) {
+    const uint32_t b = b0 + wave;
+    if constexpr (INLINE) {
+#pragma unroll 1
+      for (uint32_t l = 0; l < kListsPerIndex; ++l) {
+        if ((x.list_mask >> l & 1u) == 0u) { continue; }
+        uint32_t part = 0;
+        for (uint32_t q = summed + threadIdx.x; q < b0; q += 256u) { part += x.kind_pos[(uint64_t)l * x.buckets + q]; }
+        for (int o = 32; o > 0; o >>= 1) { part += (uint32_t)__shfl_xor((int)part, o, 64); }
+        if (lane == 0u) { wsum[wave][l] = part; }
+      }
+      __syncthreads();
+      if (threadIdx.x < kListsPerIndex && (x.list_mask >> threadIdx.x & 1u) != 0u) {
+        lbase[threadIdx.x] += wsum[0][threadIdx.x] + wsum[1][threadIdx.x] + wsum[2][threadIdx.x] + wsum[3][threadIdx.x];
+      }
+      __syncthreads();
+      summed = b0;
+    }
+    if (b >= x.buckets) { continue; }
     const uint64_t start = x.bstart[b];
-    // lane l < kListsPerIndex: where list l of this bucket begins and how long it is (all loads at once, not one list after
-    // the other: 28 dependent round trips per bucket were 0.05 ms of the step)
-    uint32_t my_pos = 0, my_cnt = 0, my_first = 0;
+    // lane l < kListsPerIndex: where in list l this bucket's items go and how many they are (all loads at once, not one list
+    // after the other: 28 dependent round trips per bucket were 0.05 ms of the step)
+    uint32_t my_at = 0, my_cnt = 0;
     if (lane < kListsPerIndex) {
       const uint64_t e = (uint64_t)lane * x.buckets + b;
-      my_pos = x.kind_pos[e]; my_cnt = x.kind_pos[e + 1] - my_pos;             // (e + 1 <= entries: the closing entry)
-      my_first = x.kind_pos[(uint64_t)lane * x.buckets];
+      if constexpr (INLINE) {
+        my_cnt = x.kind_pos[e];
+        my_at = lbase[lane];
+        for (uint32_t w = 0; w < wave; ++w) { my_at += x.kind_pos[(uint64_t)lane * x.buckets + b0 + w]; }
+      } else {
+        const uint32_t my_pos = x.kind_pos[e];
+        my_cnt = x.kind_pos[e + 1] - my_pos;                                     // (e + 1 <= entries: the closing entry)
+        my_at = my_pos - x.kind_pos[(uint64_t)lane * x.buckets];
+      }
     }
     uint32_t local = 0;
     unsigned long long todo = __ballot(my_cnt != 0u);
@@ -1344,7 +1436,7 @@ __global__ __launch_bounds__(256) void k_group_lists(const ListArgs a) {
       const int l = __ffsll((long long)todo) - 1;
       todo &= todo - 1ull;
       // (lists before l that are empty add nothing to `local`: the items of a bucket lie list after list)
-      const uint32_t cnt = lane_value(my_cnt, l), at = lane_value(my_pos, l) - lane_value(my_first, l);
+      const uint32_t cnt = lane_value(my_cnt, l), at = lane_value(my_at, l);
       const uint64_t base = x.l.region.at[(uint32_t)l / kListKinds][(uint32_t)l % kListKinds];
       const uint64_t room = x.l.region.at[(uint32_t)l / kListKinds][(uint32_t)l % kListKinds + 1u] - base;
       for (uint32_t j = lane; j < cnt; j += 64u) {
@@ -1355,12 +1447,17 @@ __global__ __launch_bounds__(256) void k_group_lists(const ListArgs a) {
       }
       local += cnt;
     }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < kListsPerIndex) {
-    const uint32_t l = threadIdx.x;
-    const uint32_t len = x.kind_pos[l + 1u < kListsPerIndex ? (uint64_t)(l + 1u) * x.buckets : entries] - x.kind_pos[(uint64_t)l * x.buckets];
     // (never more items than the list's region holds: the copy above drops what does not fit, the guard's member
     // counts then fail to balance and the step ends in SWA_E_INTERNAL instead of a kernel reading its neighbour's list)
+    if (INLINE && b + 1u == x.buckets && lane < kListsPerIndex) {             // (the last bucket: what lies before it + its own)
+      const uint32_t l = lane;
+      const uint64_t room = x.l.region.at[l / kListKinds][l % kListKinds + 1u] - x.l.region.at[l / kListKinds][l % kListKinds];
+      x.l.counters[(l / kListKinds) * 8u + l % kListKinds] = (uint32_t)min((uint64_t)(my_at + my_cnt), room);
+    }
+  }
+  if (!INLINE && blockIdx.x == 0 && threadIdx.x < kListsPerIndex) {
+    const uint32_t l = threadIdx.x;
+    const uint32_t len = x.kind_pos[l + 1u < kListsPerIndex ? (uint64_t)(l + 1u) * x.buckets : entries] - x.kind_pos[(uint64_t)l * x.buckets];
     const uint64_t room = x.l.region.at[l / kListKinds][l % kListKinds + 1u] - x.l.region.at[l / kListKinds][l % kListKinds];
     x.l.counters[(l / kListKinds) * 8u + l % kListKinds] = (uint32_t)min((uint64_t)len, room);
   }

@@ -218,8 +218,13 @@ swa_part_plan swa_part_plan_for(uint64_t records, uint32_t extra_bits, bool rout
   // the histogram (k_part_hist holds 4096 a workgroup): a tile then leaves runs of 64 bytes per bin, whole lines (key
   // partition 0.239 -> 0.225 ms at 10 M)
   p.tile = p.wide ? (p.keys_hist ? 8192u : 4096u) : 2048u;
+  p.lists_inline = swa_lists_inline(1ull << p.lv.total);
   return p;
 }
+
+bool swa_lists_inline(uint64_t buckets) { return buckets <= SWA_LISTS_INLINE_BUCKETS; }
+
+extern "C" int swa_d1_lists_form_for(uint64_t buckets) { return buckets == 0 ? -1 : (swa_lists_inline(buckets) ? 1 : 0); }
 
 void swa_part_plan_report(const swa_part_plan & p, uint32_t out[8]) {
   out[0] = p.lv.total; out[1] = p.lv.levels;

@@ -42,8 +42,9 @@ struct swa_status_block {
   uint64_t guard[24];            // kGuard* (d1.hip: guard_check)
   uint64_t csr_end;              // the last CSR offset once more (k_csr_*: CsrArgs::end_copy)
   uint32_t links_sorted;         // links the partition of the CSR stage sorted (its total, 32 bits)
-  uint32_t pad0[29];
-  uint32_t host_unserved;        // HOST ONLY (the mirror): where network_run receives counters[kCounterFallback]
+  uint32_t fallback_copy;        // counters[kCounterFallback] once more, in the head the host copies anyway (k_part_tiles<., true> / k_seg_reduce)
+  uint32_t pad0[28];
+  uint32_t host_unserved;        // (the end of the head that network_run copies; no longer written)
   uint32_t pad1[127];
   uint32_t counters[256];        // kCounter*: work counters of the d = 1 step (kCounterWords)
   uint64_t cursors[64];          // swa_d1_links_split: the run cursor of every rank; in the mirror [0] receives the links no rank owns
@@ -53,7 +54,8 @@ static_assert(std::is_standard_layout<swa_status_block>::value, "status block: p
 static_assert(sizeof(swa_status_block) == 4096, "status block: 4 KB");
 static_assert(offsetof(swa_status_block, flags) == 0 && offsetof(swa_status_block, stats) == 64 &&
               offsetof(swa_status_block, guard) == 192 && offsetof(swa_status_block, csr_end) == 384 &&
-              offsetof(swa_status_block, links_sorted) == 392 && offsetof(swa_status_block, host_unserved) == 512 &&
+              offsetof(swa_status_block, links_sorted) == 392 && offsetof(swa_status_block, fallback_copy) == 396 &&
+              offsetof(swa_status_block, host_unserved) == 512 &&
               offsetof(swa_status_block, counters) == 1024 && offsetof(swa_status_block, cursors) == 2048,
               "status block: the regions lie where the kernels and the debug reads expect them");
 
@@ -163,6 +165,7 @@ struct swa_ctx {
   uint32_t anchor_a = 0, anchor_b = 0;   // anchor windows moved inwards by this many nt ("window mode", chosen at index build)
   uint32_t anchor_w = 32;        // width of the anchor windows in nt: 32, 64 or 128 (wider: fewer pairs per group; needs 2 w + 1 nt)
   uint32_t windows_w = 32;       // ... as chosen for this database (with windows_chosen)
+  bool head_clear_pending = false;   // swa_d1_index_build_range has left the clear of the status block's head to the streaming build's own clear
   bool guard_index = false;      // guard[0, kGuardCall) of the status block describe the index in place (made by the streaming build since the last clear)
   bool guard_keys_done = false;  // the key records of this upload have had their second opinion (k_guard_db / k_guard_records)
   bool guard_keys_pending = false;   // ... its sums, guard[kGuardKeys ..), wait for the next guard_check
@@ -233,6 +236,7 @@ struct swa_ctx {
   // the key partition of the index in place, as swa_d1_part_plan reports it, and where its bucket starts lie (u64 entries
   // into d_stream[kSbStart + i]; the link partition of a network call reuses those buffers: part_starts_valid falls then)
   uint32_t part_plan[8] = {};
+  int lists_form = -1;           // the work lists of the index in place: 1 positions inside k_group_lists, 0 the two-launch scan (swa_d1_lists_form)
   uint64_t part_starts_at = 0;
   uint32_t part_buckets = 0;
   bool part_starts_valid = false;
@@ -378,9 +382,14 @@ struct swa_part_plan {
   uint32_t tile;                 // records per tile: 2048 (512 bins), 8192 / 4096 (the one level of 1024 bins, whole database / routed)
   bool keys_hist;                // k_keys takes the first level's histogram on the way (not for routed builds)
   bool wide;                     // one level of 1024 bins
+  bool lists_inline;             // swa_lists_inline(2^lv.total)
 };
 // forced_bits != 0 (SWA_D1_PART_BITS, a test hook) stands in for the bit count derived from `records`
 swa_part_plan swa_part_plan_for(uint64_t records, uint32_t extra_bits, bool routed, uint32_t forced_bits);
+// the work lists behind the partition: up to this many buckets every workgroup of k_group_lists adds up the positions it needs
+// itself, beyond it the counts are scanned by two launches first (a pure function of the bucket count; swa_d1_lists_form_for)
+#define SWA_LISTS_INLINE_BUCKETS 1024u
+bool swa_lists_inline(uint64_t buckets);
 void swa_part_plan_report(const swa_part_plan & p, uint32_t out[8]);
 struct swa_csr_plan { uint32_t nbits, r; swa_part_levels lv; };
 swa_csr_plan swa_csr_plan_for(uint32_t count);
