@@ -320,6 +320,15 @@ int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t * generati
    build, network or clustering call of the context.  swa_d1_cluster_maxgen: the deepest generation ("Max generations"). */
 int swa_d1_cluster_fetch(swa_ctx * ctx, uint32_t * swarmid, uint32_t * generation, uint32_t * parent);
 uint32_t swa_d1_cluster_maxgen(const swa_ctx * ctx);
+/* A caller's own CSR over the n amplicons of the resident database installed as the resident network, for
+   swa_d1_cluster_device (and, with one byte of differences per link in `diffs`, swa_dn_parent_diffs; diffs may be null).
+   Checked on the host before anything is copied or launched: offsets[0] = 0, offsets never falling, offsets[n] = total,
+   every neighbour < n, every row strictly ascending, no link from an amplicon to itself.  SWA_E_ARG otherwise, and no
+   resident network is left.  The arrays are the caller's again on return.
+   swa_d1_cluster_effort: what the last swa_d1_cluster_device call cost, out3 = {label sweeps launched, restarts of their
+   numbering (a graph that needs more than 1023 sweeps), level batches (32 generations each)}. */
+int swa_d1_network_adopt(swa_ctx * ctx, const uint64_t * offsets, const uint32_t * neighbours, const uint8_t * diffs, uint64_t total);
+int swa_d1_cluster_effort(const swa_ctx * ctx, uint32_t out3[3]);
 
 /* ---- B2: fastidious second pass ------------------------------------------------- */
 /* is_light[n]: != 0 when the amplicon's swarm has mass < boundary.  light_nt: total

@@ -72,7 +72,7 @@ class DbUnorderedView(C.Structure):
 
 EXPORTS = [
     "swa_abi_version", "swa_ctx_create", "swa_ctx_destroy", "swa_last_error", "swa_ctx_synchronize", "swa_ctx_warmup", "swa_ctx_warmup_for", "swa_d1_anchor_windows", "swa_d1_anchor_width",
-    "swa_d1_network_resident", "swa_d1_network_fetch", "swa_d1_cluster_device", "swa_d1_cluster_fetch", "swa_d1_cluster_maxgen", "swa_d1_cluster_resident", "swa_d1_cluster_resident_lazy", "swa_d1_result_detach", "swa_d1_result_error", "swa_d1_result_prepare",
+    "swa_d1_network_resident", "swa_d1_network_fetch", "swa_d1_cluster_device", "swa_d1_cluster_fetch", "swa_d1_cluster_maxgen", "swa_d1_network_adopt", "swa_d1_cluster_effort", "swa_d1_cluster_resident", "swa_d1_cluster_resident_lazy", "swa_d1_result_detach", "swa_d1_result_error", "swa_d1_result_prepare",
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_links_split", "swa_d1_csr_from_lists",
@@ -635,21 +635,75 @@ class Context:
         self._check(self.lib.swa_d1_network_fetch(self.h, _ptr(offsets), _ptr(nb), len(nb)))
         return offsets, nb[:total]
 
-    def d1_cluster_device(self):
+    def d1_network_adopt(self, offsets, neighbours, diffs=None) -> int:
+        """swa_d1_network_adopt: a host CSR over the resident database's amplicons installed as the resident network (with
+        `diffs`, a byte per link, as swa_dn_graph_resident leaves it).  Validated on the host before anything reaches the
+        device; SwaError(SWA_E_ARG) for a malformed graph.  Returns the number of links."""
+        self.lib.swa_d1_network_adopt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        neighbours = np.ascontiguousarray(neighbours, dtype=np.uint32)
+        total = len(neighbours)
+        if diffs is not None:
+            diffs = np.ascontiguousarray(diffs, dtype=np.uint8)
+            if len(diffs) != total:
+                raise ValueError("d1_network_adopt: one byte of differences per link")
+        if len(offsets) != self.n + 1:
+            raise ValueError("d1_network_adopt: offsets needs one entry per amplicon of the resident database and one more")
+        if diffs is not None and total == 0:
+            diffs = np.zeros(1, dtype=np.uint8)                     # (a graph without links still says "with differences")
+        self._check(self.lib.swa_d1_network_adopt(self.h, _ptr(offsets), _ptr(neighbours) if total else None,
+                                                  _ptr(diffs) if diffs is not None else None, total))
+        return total
+
+    def d1_cluster_effort(self):
+        """swa_d1_cluster_effort: (label sweeps launched, restarts of their numbering, level batches) of the last
+        d1_cluster_device call."""
+        self.lib.swa_d1_cluster_effort.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(3, dtype=np.uint32)
+        self._check(self.lib.swa_d1_cluster_effort(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def d1_cluster_maxgen(self) -> int:
+        """swa_d1_cluster_maxgen: the deepest generation of the clustering in place"""
+        self.lib.swa_d1_cluster_maxgen.argtypes = [C.c_void_p]
+        self.lib.swa_d1_cluster_maxgen.restype = C.c_uint32
+        return int(self.lib.swa_d1_cluster_maxgen(self.h))
+
+    def d1_cluster_fetch(self):
+        """swa_d1_cluster_fetch: (swarmid, generation, parent) of the clustering d1_cluster_device left in HBM"""
+        self.lib.swa_d1_cluster_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        swarmid, generation, parent = (np.zeros(self.n, dtype=np.uint32) for _ in range(3))
+        self._check(self.lib.swa_d1_cluster_fetch(self.h, _ptr(swarmid), _ptr(generation), _ptr(parent)))
+        return swarmid, generation, parent
+
+    def d1_cluster_device(self, swarm_cap: int | None = None, details: bool = True):
         """swa_d1_cluster_device on the resident network with all five result arrays on the host (none null):
-        (swarmid, generation, parent, order, begins); the members of swarm s are order[begins[s]:begins[s + 1]]."""
+        (swarmid, generation, parent, order, begins); the members of swarm s are order[begins[s]:begins[s + 1]].
+        swarm_cap: the entries of the swarm table handed over at once (default: asked for first, by a call without a
+        table); when it is too small, SwaError(SWA_E_CAPACITY) whose `nswarms` is the number needed.  details = False:
+        swarmid / generation / parent are passed as null and stay in HBM (d1_cluster_fetch); three None come back."""
         lib = self.lib
         lib.swa_d1_cluster_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, u32p]
         swarmid, generation, parent, order = (np.zeros(self.n, dtype=np.uint32) for _ in range(4))
+        three = (_ptr(swarmid), _ptr(generation), _ptr(parent)) if details else (None, None, None)
         nswarms = C.c_uint32(0)
-        begins = np.zeros(1, dtype=np.uint32)
-        rc = self._check(lib.swa_d1_cluster_device(self.h, _ptr(swarmid), _ptr(generation), _ptr(parent), _ptr(order), None, 0,
-                                                   C.byref(nswarms)), allow=(SWA_E_CAPACITY,))
-        if rc == SWA_E_CAPACITY:
-            begins = np.zeros(nswarms.value + 1, dtype=np.uint32)
-            self._check(lib.swa_d1_cluster_device(self.h, _ptr(swarmid), _ptr(generation), _ptr(parent), _ptr(order), _ptr(begins),
-                                                  nswarms.value, C.byref(nswarms)))
+        if swarm_cap is None:
+            rc = self._check(lib.swa_d1_cluster_device(self.h, *three, _ptr(order), None, 0, C.byref(nswarms)), allow=(SWA_E_CAPACITY,))
+            begins = np.zeros(1, dtype=np.uint32)
+            if rc == SWA_E_CAPACITY:
+                begins = np.zeros(nswarms.value + 1, dtype=np.uint32)
+                self._check(lib.swa_d1_cluster_device(self.h, *three, _ptr(order), _ptr(begins), nswarms.value, C.byref(nswarms)))
+        else:
+            begins = np.zeros(int(swarm_cap) + 1, dtype=np.uint32)
+            try:
+                self._check(lib.swa_d1_cluster_device(self.h, *three, _ptr(order), _ptr(begins), int(swarm_cap), C.byref(nswarms)))
+            except SwaError as e:
+                e.nswarms = int(nswarms.value)
+                raise
+            begins = begins[:nswarms.value + 1]
+        if not details:
+            swarmid = generation = parent = None
         return swarmid, generation, parent, order, begins
 
     def d1_network_device(self, d_offsets, d_neighbours, cap: int, no_cluster_breaking: bool = False,

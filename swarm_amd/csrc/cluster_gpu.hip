@@ -16,6 +16,10 @@
 //                     (swarm << gbits | generation) over the bits that vary (23 of them at 10 M amplicons, 32-bit keys), the ids
 //                     ascending as payload; k_swarm_bounds reads the swarms' first members off the sorted keys
 // Round 6: 17.4 -> ~5 ms at 10 M for the device part + download (profiles/r06/NOTES.md).
+//
+// swa_d1_network_adopt installs a caller's own CSR as the resident network (validated on the host before anything is
+// copied or launched); swa_d1_cluster_effort reports what the last swa_d1_cluster_device call cost — label sweeps launched,
+// restarts of their numbering, level batches —, three host-side counters (tests/test_cluster_forms_gpu.py).
 #include "swa_internal.h"
 
 #include <rocprim/rocprim.hpp>
@@ -158,6 +162,49 @@ extern "C" int swa_d1_network_resident(swa_ctx * ctx, int no_cluster_breaking, u
   return SWA_OK;
 }
 
+// A caller's own CSR over the n amplicons of the resident database installed as the resident network: the state
+// swa_d1_network_resident (diffs == nullptr) / swa_dn_graph_resident (one byte of differences per link, laid behind the
+// neighbours) leave.  Everything the kernels rely on is checked on the host BEFORE anything is copied or launched — offsets
+// from 0 to total and never falling, every neighbour below n, every row strictly ascending (k_dg_parent_diffs searches rows
+// by bisection), no link from a vertex to itself —; a graph that fails a check never reaches the device: SWA_E_ARG, and no
+// resident network afterwards.
+extern "C" int swa_d1_network_adopt(swa_ctx * ctx, const uint64_t * offsets, const uint32_t * neighbours, const uint8_t * diffs, uint64_t total) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  ctx->csr_ready = false;
+  ctx->cluster_ready = false;
+  const uint32_t n = ctx->db.n;
+  if (n == 0 || ctx->db.seqlen == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: no resident database"); }
+  if (offsets == nullptr || (total != 0 && neighbours == nullptr)) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: null array"); }
+  if (offsets[0] != 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: offsets[0] is not 0"); }
+  for (uint32_t u = 0; u < n; ++u) {
+    if (offsets[u + 1] < offsets[u]) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: offsets decrease"); }
+    if (offsets[u + 1] > total) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: an offset beyond the number of links"); }
+  }
+  if (offsets[n] != total) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: offsets[n] is not the number of links"); }
+  for (uint32_t u = 0; u < n; ++u) {
+    for (uint64_t e = offsets[u]; e < offsets[u + 1]; ++e) {
+      const uint32_t v = neighbours[e];
+      if (v >= n) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: a neighbour is not an amplicon of the database"); }
+      if (v == u) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: a link from an amplicon to itself"); }
+      if (e > offsets[u] && neighbours[e - 1] >= v) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: a row is not strictly ascending"); }
+    }
+  }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
+  SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, (total + 1) * (sizeof(uint32_t) + 1)));           // (as swa_dn_graph_resident sizes it)
+  SWA_HIP(ctx, hipMemcpyAsync(ctx->d_offsets_tmp.ptr, offsets, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  if (total != 0) {
+    auto * nb32 = static_cast<uint32_t *>(ctx->d_nb_tmp.ptr);
+    SWA_HIP(ctx, hipMemcpyAsync(nb32, neighbours, total * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (diffs != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(nb32 + total, diffs, total, hipMemcpyHostToDevice, ctx->stream)); }
+  }
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's arrays are free again on return)
+  ctx->csr_ready = true;
+  ctx->csr_has_diffs = diffs != nullptr;
+  ctx->csr_total = total;
+  return SWA_OK;
+}
+
 // the resident CSR -> host (for -j and for callers that want the lists themselves)
 extern "C" int swa_d1_network_fetch(swa_ctx * ctx, uint64_t * offsets, uint32_t * neighbours, uint64_t cap) {
   if (ctx == nullptr || offsets == nullptr) { return SWA_E_ARG; }
@@ -184,6 +231,12 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   if (ctx == nullptr || order == nullptr || nswarms == nullptr) { return SWA_E_ARG; }
   ctx->cluster_ready = false;
   if (!ctx->csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_device: no resident network (swa_d1_network_resident)"); }
+  for (uint32_t & e : ctx->cluster_effort) { e = 0; }
+  if (ctx->db.n == 0) {                                   // (nothing to cluster: seed_rank + (n - 1) below would lie in front of the buffer)
+    *nswarms = 0;
+    if (swarm_begin != nullptr) { swarm_begin[0] = 0; }
+    return SWA_OK;
+  }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
   const auto * offsets = static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr);
@@ -218,6 +271,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   for (uint32_t s = 1;;) {
     if (s == 1u) { SWA_HIP(ctx, hipMemsetAsync(flags, 0, kSweepFlags * sizeof(uint32_t), ctx->stream)); }
     const uint32_t last = std::min(s + kSweepBatch, kSweepFlags) - 1u;
+    ctx->cluster_effort[0] += last + 1u - s;
     for (; s <= last; ++s) { hipLaunchKernelGGL(k_label_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, stamp, s, flags); }
     uint32_t changed = 0;
     SWA_HIP(ctx, hipMemcpyAsync(&changed, flags + last, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -227,6 +281,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     if (s == kSweepFlags) {                            // (a graph that needs a thousand sweeps: start the numbering again, everybody active)
       SWA_HIP(ctx, hipMemsetAsync(stamp, 0, (uint64_t)n * sizeof(uint32_t), ctx->stream));
       s = 1;
+      ++ctx->cluster_effort[1];
     }
   }
   // ---- swarm numbers = rank of the seed among the seeds (queued behind the first frontiers; read with them)
@@ -250,6 +305,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   SWA_HIP(ctx, hipMemcpyAsync(&last_seed, is_seed + (n - 1), 1, hipMemcpyDeviceToHost, ctx->stream));
   for (uint32_t level0 = 1;; level0 += kLevelBatch) {   // (level0 = the generation the batch's first sweep hands out)
     SWA_HIP(ctx, hipMemsetAsync(any, 0, kLevelBatch * sizeof(uint32_t), ctx->stream));
+    ++ctx->cluster_effort[2];
     for (uint32_t r = 0; r < kLevelBatch; ++r) {
       hipLaunchKernelGGL(k_level_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, gen, par, level0 + r, any, r);
     }
@@ -319,6 +375,14 @@ extern "C" int swa_d1_cluster_fetch(swa_ctx * ctx, uint32_t * swarmid, uint32_t 
   if (generation != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(generation, gen, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
   if (parent != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(parent, par, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
+// what the last swa_d1_cluster_device call of this context cost: label sweeps launched, restarts of their numbering, level
+// batches (host-side counters; the number of sweeps depends on how the device scheduled them)
+extern "C" int swa_d1_cluster_effort(const swa_ctx * ctx, uint32_t out3[3]) {
+  if (ctx == nullptr || out3 == nullptr) { return SWA_E_ARG; }
+  for (int k = 0; k < 3; ++k) { out3[k] = ctx->cluster_effort[k]; }
   return SWA_OK;
 }
 

@@ -255,6 +255,7 @@ struct swa_ctx {
   const void * staged_first = nullptr; uint64_t staged_words = 0;
   bool cluster_ready = false;                  // swa_d1_cluster_device's arrays lie in d_cluster (swa_d1_cluster_fetch)
   uint32_t cluster_maxgen = 0;
+  uint32_t cluster_effort[3] = {};             // of the last swa_d1_cluster_device call: label sweeps launched, restarts of their numbering, level batches
   int pair_blocks[4] = {};                      // workgroups of k_d1_group_pairs a CU holds, per width class (0: not asked yet)
   bool g1_lds_opt_in = false;                  // k_group1's dynamic-LDS attribute has been set on this context's device
   bool part_lds_opt_in = false;                // ... and the wide-tile form of k_part_scatter

@@ -60,7 +60,7 @@ def _greedy_walk(rows):
 
 
 def _functional_form(rows):
-    """what k_label_step / k_level_step / the sort compute, and what cluster_on_device builds from it"""
+    """what k_label_sweep / k_level_sweep / the sort compute, and what cluster_on_device builds from it"""
     n = len(rows)
     label = list(range(n))
     changed = True
