@@ -142,10 +142,10 @@ void swa_warm_cluster(swa_ctx * ctx) {
 // swa_d1_network does up to the download.  *total = number of links.
 extern "C" int swa_d1_network_resident(swa_ctx * ctx, int no_cluster_breaking, uint64_t * total) {
   if (ctx == nullptr || total == nullptr) { return SWA_E_ARG; }
-  if (!ctx->d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_resident: call swa_d1_index_build first"); }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_resident: call swa_d1_index_build first"); }
   const uint32_t n = ctx->db.n;
-  ctx->csr_ready = false;
-  ctx->cluster_ready = false;
+  ctx->res.csr_ready = false;
+  ctx->res.cluster_ready = false;
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   uint64_t cap = std::max<uint64_t>(ctx->d_nb_tmp.bytes / sizeof(uint32_t), 4ull * n + 1024);
   for (;;) {
@@ -156,9 +156,9 @@ extern "C" int swa_d1_network_resident(swa_ctx * ctx, int no_cluster_breaking, u
     if (rc != SWA_OK) { return rc; }
     break;
   }
-  ctx->csr_ready = true;
-  ctx->csr_has_diffs = false;
-  ctx->csr_total = *total;
+  ctx->res.csr_ready = true;
+  ctx->res.csr_has_diffs = false;
+  ctx->res.csr_total = *total;
   return SWA_OK;
 }
 
@@ -170,8 +170,8 @@ extern "C" int swa_d1_network_resident(swa_ctx * ctx, int no_cluster_breaking, u
 // resident network afterwards.
 extern "C" int swa_d1_network_adopt(swa_ctx * ctx, const uint64_t * offsets, const uint32_t * neighbours, const uint8_t * diffs, uint64_t total) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  ctx->csr_ready = false;
-  ctx->cluster_ready = false;
+  ctx->res.csr_ready = false;
+  ctx->res.cluster_ready = false;
   const uint32_t n = ctx->db.n;
   if (n == 0 || ctx->db.seqlen == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: no resident database"); }
   if (offsets == nullptr || (total != 0 && neighbours == nullptr)) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: null array"); }
@@ -199,23 +199,23 @@ extern "C" int swa_d1_network_adopt(swa_ctx * ctx, const uint64_t * offsets, con
     if (diffs != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(nb32 + total, diffs, total, hipMemcpyHostToDevice, ctx->stream)); }
   }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's arrays are free again on return)
-  ctx->csr_ready = true;
-  ctx->csr_has_diffs = diffs != nullptr;
-  ctx->csr_total = total;
+  ctx->res.csr_ready = true;
+  ctx->res.csr_has_diffs = diffs != nullptr;
+  ctx->res.csr_total = total;
   return SWA_OK;
 }
 
 // the resident CSR -> host (for -j and for callers that want the lists themselves)
 extern "C" int swa_d1_network_fetch(swa_ctx * ctx, uint64_t * offsets, uint32_t * neighbours, uint64_t cap) {
   if (ctx == nullptr || offsets == nullptr) { return SWA_E_ARG; }
-  if (!ctx->csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_fetch: no resident network"); }
-  if (ctx->csr_total > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_network_fetch: neighbour buffer too small"); }
+  if (!ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_fetch: no resident network"); }
+  if (ctx->res.csr_total > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_network_fetch: neighbour buffer too small"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   swa_touch_pages(offsets, ((uint64_t)ctx->db.n + 1) * sizeof(uint64_t));
-  swa_touch_pages(neighbours, ctx->csr_total * sizeof(uint32_t));
+  swa_touch_pages(neighbours, ctx->res.csr_total * sizeof(uint32_t));
   SWA_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_offsets_tmp.ptr, ((uint64_t)ctx->db.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (ctx->csr_total != 0) {
-    SWA_HIP(ctx, hipMemcpyAsync(neighbours, ctx->d_nb_tmp.ptr, ctx->csr_total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->res.csr_total != 0) {
+    SWA_HIP(ctx, hipMemcpyAsync(neighbours, ctx->d_nb_tmp.ptr, ctx->res.csr_total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SWA_OK;
@@ -229,9 +229,9 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   // (swarmid / generation / parent may be null: they stay in HBM for swa_d1_cluster_fetch — a run that only writes the
   // swarms, the usual one, never looks at them)
   if (ctx == nullptr || order == nullptr || nswarms == nullptr) { return SWA_E_ARG; }
-  ctx->cluster_ready = false;
-  if (!ctx->csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_device: no resident network (swa_d1_network_resident)"); }
-  for (uint32_t & e : ctx->cluster_effort) { e = 0; }
+  ctx->res.cluster_ready = false;
+  if (!ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_device: no resident network (swa_d1_network_resident)"); }
+  for (uint32_t & e : ctx->res.cluster_effort) { e = 0; }
   if (ctx->db.n == 0) {                                   // (nothing to cluster: seed_rank + (n - 1) below would lie in front of the buffer)
     *nswarms = 0;
     if (swarm_begin != nullptr) { swarm_begin[0] = 0; }
@@ -271,7 +271,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   for (uint32_t s = 1;;) {
     if (s == 1u) { SWA_HIP(ctx, hipMemsetAsync(flags, 0, kSweepFlags * sizeof(uint32_t), ctx->stream)); }
     const uint32_t last = std::min(s + kSweepBatch, kSweepFlags) - 1u;
-    ctx->cluster_effort[0] += last + 1u - s;
+    ctx->res.cluster_effort[0] += last + 1u - s;
     for (; s <= last; ++s) { hipLaunchKernelGGL(k_label_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, stamp, s, flags); }
     uint32_t changed = 0;
     SWA_HIP(ctx, hipMemcpyAsync(&changed, flags + last, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -281,7 +281,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     if (s == kSweepFlags) {                            // (a graph that needs a thousand sweeps: start the numbering again, everybody active)
       SWA_HIP(ctx, hipMemsetAsync(stamp, 0, (uint64_t)n * sizeof(uint32_t), ctx->stream));
       s = 1;
-      ++ctx->cluster_effort[1];
+      ++ctx->res.cluster_effort[1];
     }
   }
   // ---- swarm numbers = rank of the seed among the seeds (queued behind the first frontiers; read with them)
@@ -305,7 +305,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   SWA_HIP(ctx, hipMemcpyAsync(&last_seed, is_seed + (n - 1), 1, hipMemcpyDeviceToHost, ctx->stream));
   for (uint32_t level0 = 1;; level0 += kLevelBatch) {   // (level0 = the generation the batch's first sweep hands out)
     SWA_HIP(ctx, hipMemsetAsync(any, 0, kLevelBatch * sizeof(uint32_t), ctx->stream));
-    ++ctx->cluster_effort[2];
+    ++ctx->res.cluster_effort[2];
     for (uint32_t r = 0; r < kLevelBatch; ++r) {
       hipLaunchKernelGGL(k_level_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, gen, par, level0 + r, any, r);
     }
@@ -315,7 +315,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     for (uint32_t r = 0; r < kLevelBatch; ++r) { if (host_ctl[r] != 0u) { maxgen = level0 + r; } }
     if (host_ctl[kLevelBatch - 1u] == 0u) { break; }     // (the batch's last generation is empty: nobody is left to claim anybody)
   }
-  ctx->cluster_maxgen = maxgen;
+  ctx->res.cluster_maxgen = maxgen;
   *nswarms = last_rank + last_seed;
   if (*nswarms > swarm_cap || swarm_begin == nullptr) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_cluster_device: swarm table too small"); }
   // ---- members by (swarm, generation, id): one stable radix sort over the bits that vary, ids ascending going in
@@ -356,7 +356,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     std::fprintf(stderr, "[cluster gpu] by the stream's own events: order copy %.3f ms, bounds copy %.3f ms\n", a, b);
     for (auto & e : ev) { (void)hipEventDestroy(e); }
   }
-  ctx->cluster_ready = true;
+  ctx->res.cluster_ready = true;
   return SWA_OK;
 }
 
@@ -365,7 +365,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
 // network or clustering call of this context.
 extern "C" int swa_d1_cluster_fetch(swa_ctx * ctx, uint32_t * swarmid, uint32_t * generation, uint32_t * parent) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->cluster_ready || !ctx->csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_fetch: no clustering in place (swa_d1_cluster_device)"); }
+  if (!ctx->res.cluster_ready || !ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_fetch: no clustering in place (swa_d1_cluster_device)"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
   const auto * label = static_cast<const uint32_t *>(ctx->d_cluster.ptr);
@@ -382,9 +382,9 @@ extern "C" int swa_d1_cluster_fetch(swa_ctx * ctx, uint32_t * swarmid, uint32_t 
 // batches (host-side counters; the number of sweeps depends on how the device scheduled them)
 extern "C" int swa_d1_cluster_effort(const swa_ctx * ctx, uint32_t out3[3]) {
   if (ctx == nullptr || out3 == nullptr) { return SWA_E_ARG; }
-  for (int k = 0; k < 3; ++k) { out3[k] = ctx->cluster_effort[k]; }
+  for (int k = 0; k < 3; ++k) { out3[k] = ctx->res.cluster_effort[k]; }
   return SWA_OK;
 }
 
 // the deepest generation of the clustering in place (what the log calls "Max generations")
-extern "C" uint32_t swa_d1_cluster_maxgen(const swa_ctx * ctx) { return ctx != nullptr && ctx->cluster_ready ? ctx->cluster_maxgen : 0u; }
+extern "C" uint32_t swa_d1_cluster_maxgen(const swa_ctx * ctx) { return ctx != nullptr && ctx->res.cluster_ready ? ctx->res.cluster_maxgen : 0u; }

@@ -225,30 +225,10 @@ static int check_view(swa_ctx * ctx, const swa_db_view * v) {
   return SWA_OK;
 }
 
-static void invalidate(swa_ctx * ctx) {
-  ctx->d1_ready = false;
-  ctx->nw_seqlen.clear();
-  ctx->full_index = false;
-  ctx->anchor_ready = false;
-  ctx->rank_ready = false;
-  ctx->db_unordered = false;
-  ctx->props_ready = false;
-  ctx->windows_ready = false;
-  ctx->lines_ready = false;
-  ctx->fast_classes_ready = false;
-  ctx->stream_index = false;
-  ctx->member_index = false;
-  ctx->stream_extra_bits = 0;
-  ctx->anchor_a = ctx->anchor_b = 0;
-  ctx->anchor_w = ctx->windows_w = 32;
-  ctx->guard_index = false;
-  ctx->guard_keys_done = ctx->guard_keys_pending = false;
-  ctx->qgram_ready = false;
-  ctx->scan_ready = false;
-  ctx->dn_graph_ready = false;
-  ctx->dn_shortest = 0;
-  ctx->csr_ready = false;
-  ctx->cluster_ready = false;
+static void invalidate(swa_ctx * ctx) {   // a new database: what was known of the previous one, its index, its network
+  ctx->up = {};
+  ctx->ix = {};
+  ctx->res = {};
 }
 
 extern "C" int swa_db_upload(swa_ctx * ctx, const swa_db_view * h) {

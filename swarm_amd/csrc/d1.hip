@@ -757,13 +757,13 @@ void swa_warm_d1(swa_ctx * ctx) {
 // shared with fastidious.hip
 int swa_d1_rebuild_table(swa_ctx * ctx, const uint8_t * d_is_member) {
   const uint32_t n = ctx->db.n;
-  hipLaunchKernelGGL(k_table_clear, dim3(grid_for(ctx, ctx->table_size, 256, 8)), dim3(256), 0, ctx->stream,
-                     static_cast<swa_slot *>(ctx->d_table.ptr), ctx->table_size,
-                     static_cast<uint64_t *>(ctx->d_bloom.ptr), ctx->bloom_words);
+  hipLaunchKernelGGL(k_table_clear, dim3(grid_for(ctx, ctx->ix.table_size, 256, 8)), dim3(256), 0, ctx->stream,
+                     static_cast<swa_slot *>(ctx->d_table.ptr), ctx->ix.table_size,
+                     static_cast<uint64_t *>(ctx->d_bloom.ptr), ctx->ix.bloom_words);
   hipLaunchKernelGGL(k_table_insert, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream,
                      static_cast<const uint64_t *>(ctx->d_seqhash.ptr), n, d_is_member,
-                     static_cast<swa_slot *>(ctx->d_table.ptr), ctx->table_size - 1,
-                     static_cast<unsigned long long *>(ctx->d_bloom.ptr), ctx->bloom_words - 1,
+                     static_cast<swa_slot *>(ctx->d_table.ptr), ctx->ix.table_size - 1,
+                     static_cast<unsigned long long *>(ctx->d_bloom.ptr), ctx->ix.bloom_words - 1,
                      static_cast<const uint64_t *>(ctx->d_patterns.ptr));
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
@@ -777,7 +777,7 @@ static bool anchored_enabled() {
 }
 
 // shortest seed the anchored passes serve: two windows and a nucleotide (65 with the 32-nt windows of rounds 1-3)
-static uint32_t anchor_minlen(const swa_ctx * ctx) { return ctx->anchor_a + ctx->anchor_b + 2u * ctx->anchor_w + 1u; }
+static uint32_t anchor_minlen(const swa_ctx * ctx) { return ctx->ix.anchor_a + ctx->ix.anchor_b + 2u * ctx->ix.anchor_w + 1u; }
 
 // whether the anchored passes may be used at all for this database (decided at index build)
 static bool anchor_applicable(const swa_ctx * ctx) {
@@ -803,7 +803,7 @@ static bool windows_search_off() {
 // Shortest sequence and the population of every width class: facts of the uploaded database (k_db_lengths), read once per
 // upload.  The work lists of an index are laid out from the populations (list_regions).
 static int ensure_db_lengths(swa_ctx * ctx) {
-  if (ctx->props_ready) { return SWA_OK; }
+  if (ctx->up.d1.props_ready) { return SWA_OK; }
   SWA_TRY(swa_reserve(ctx, ctx->d_rank_tmp, std::max<size_t>(ctx->d_rank_tmp.bytes, 64)));
   auto * out = static_cast<uint32_t *>(ctx->d_rank_tmp.ptr);
   SWA_HIP(ctx, hipMemsetAsync(out, 0, 8 * sizeof(uint32_t), ctx->stream));
@@ -811,9 +811,9 @@ static int ensure_db_lengths(swa_ctx * ctx) {
   uint32_t host[8] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->db_shortest = 0xFFFFFFFFu - host[0];
-  for (uint32_t c = 0; c <= kWidthClasses; ++c) { ctx->class_pop[c] = host[1 + c]; }
-  ctx->props_ready = true;
+  ctx->up.d1.db_shortest = 0xFFFFFFFFu - host[0];
+  for (uint32_t c = 0; c <= kWidthClasses; ++c) { ctx->up.d1.class_pop[c] = host[1 + c]; }
+  ctx->up.d1.props_ready = true;
   return SWA_OK;
 }
 
@@ -827,13 +827,13 @@ static ListRegions list_regions(const swa_ctx * ctx, uint64_t * total_items) {
   ListRegions r{};
   uint64_t at = 0, upto = 0;
   for (uint32_t c = 0; c < kWidthClasses; ++c) {
-    upto += ctx->class_pop[c];
+    upto += ctx->up.d1.class_pop[c];
     for (uint32_t k = 0; k < kListKinds; ++k) {
       r.at[c][k] = at;
       uint64_t room = 64;
       // (the tiled kernel's items: a row tile against kTiledCols column tiles — per row tile at most what the largest group has)
       constexpr uint64_t per_row_tile = (tiled_item_count(kStreamGroupCap) + kStreamGroupCap / 64u - 1u) / (kStreamGroupCap / 64u);
-      if (ctx->class_pop[c] != 0) { room += k + 1 < kListKinds ? std::min<uint64_t>(ctx->class_pop[c], upto / least[k]) : per_row_tile * (upto / 64 + upto / least[k]); }
+      if (ctx->up.d1.class_pop[c] != 0) { room += k + 1 < kListKinds ? std::min<uint64_t>(ctx->up.d1.class_pop[c], upto / least[k]) : per_row_tile * (upto / 64 + upto / least[k]); }
       at += room;
     }
     r.at[c][kListKinds] = at;
@@ -845,11 +845,11 @@ static ListRegions list_regions(const swa_ctx * ctx, uint64_t * total_items) {
 // abundance rank of every amplicon (k_abundance_rank: three streaming passes); kFlagUnordered is raised when the database is
 // not in abundance order
 static int launch_abundance_rank(swa_ctx * ctx) {
-  if (ctx->rank_ready) {                                    // (a fact of the uploaded database: once per upload)
-    if (ctx->db_unordered) { SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags + kFlagUnordered, 1, sizeof(uint32_t), ctx->stream)); }
+  if (ctx->up.d1.rank_ready) {                                    // (a fact of the uploaded database: once per upload)
+    if (ctx->up.d1.db_unordered) { SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags + kFlagUnordered, 1, sizeof(uint32_t), ctx->stream)); }
     return SWA_OK;
   }
-  ctx->rank_ready = true;
+  ctx->up.d1.rank_ready = true;
   // (the flag is this database's from here on: the index build's clear leaves it alone)
   SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags + kFlagUnordered, 0, sizeof(uint32_t), ctx->stream));
   const uint32_t n = ctx->db.n;
@@ -1024,7 +1024,7 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
 // the amplicon lines of the uploaded database (once per upload; needs the abundance ranks)
 static int ensure_lines(swa_ctx * ctx) {
   const uint32_t lq = line_quads_for(ctx);
-  if (ctx->lines_ready && ctx->lines_quads == lq) { return SWA_OK; }
+  if (ctx->up.d1.lines_ready && ctx->up.d1.lines_quads == lq) { return SWA_OK; }
   const uint32_t n = ctx->db.n;
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbLines], (uint64_t)n * lq * 16u + 64u));   // (+ what window_at may read behind the last line)
   auto * lines = static_cast<uint4 *>(ctx->d_stream[kSbLines].ptr);
@@ -1037,20 +1037,32 @@ static int ensure_lines(swa_ctx * ctx) {
   else { hipLaunchKernelGGL(k_lines_build<16>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
   swa_t1(ctx, kTimeLines);
   SWA_HIP(ctx, hipGetLastError());
-  ctx->lines_ready = true;
-  ctx->lines_quads = lq;
+  ctx->up.d1.lines_ready = true;
+  ctx->up.d1.lines_quads = lq;
   return SWA_OK;
 }
 
 // The two anchor indexes of the whole database (or of the routed id lists) by the streaming build: members in group
 // order (d_stream[kSbMembers + which]: ids), the work lists of the pair kernels, the flags build_owned_index reads
 // (kFlagDuplicates, kFlagKeyOverflow, kFlagUnserved, kFlagOversized / kFlagOverMass, kFlagShortest).
-static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_count) {
-  const bool clear_head = ctx->head_clear_pending;            // (swa_d1_index_build_range: the first build of the call)
-  ctx->head_clear_pending = false;
-  ctx->anchor_ready = false;
-  ctx->stream_index = false;
-  ctx->list_counts_ready = false;
+// What a routed build is given (swa_d1_index_build_routed / _records): the members of this rank's groups as two id lists,
+// or — the key records themselves travelled: no k_keys pass — as two record lists; [0] prefix side, [1] suffix side.  The
+// lists are the caller's, for the one call.  A default one: not routed (every build the library starts on its own); an
+// empty list still counts as routed (the entry points pass a pointer to nothing then, and so do the kernels' arguments).
+struct RouteLists {
+  const uint32_t * ids[2] = {nullptr, nullptr};
+  const unsigned long long * rec[2] = {nullptr, nullptr};
+  uint32_t m[2] = {0, 0};
+  bool routed() const { return ids[0] != nullptr || rec[0] != nullptr; }
+  bool by_rec() const { return rec[0] != nullptr; }
+};
+
+static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
+  const bool clear_head = ctx->ix.head_clear_pending;            // (index_build: the first build of the call)
+  ctx->ix.head_clear_pending = false;
+  ctx->ix.anchor_ready = false;
+  ctx->ix.stream_index = false;
+  ctx->ix.list_counts_ready = false;
   const uint32_t n = ctx->db.n;
   swa_status_block * st = swa_status(ctx);
   swa_lap(ctx, "(build starts)");
@@ -1058,12 +1070,12 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   swa_lap(ctx, "db lengths");
   SWA_TRY(ensure_lines(ctx));
   swa_lap(ctx, "amplicon lines");
-  const uint32_t lq = ctx->lines_quads;
+  const uint32_t lq = ctx->up.d1.lines_quads;
   uint64_t item_room = 0;
   const ListRegions regions = list_regions(ctx, &item_room);
-  const bool by_rec = ctx->route_rec[0] != nullptr;           // routed, and the key records themselves arrived: no k_keys pass
-  const bool routed = ctx->route_ids[0] != nullptr || by_rec;
-  const uint64_t records = routed ? std::max<uint64_t>(std::max(ctx->route_m[0], ctx->route_m[1]), 1) : n;
+  const bool by_rec = route.by_rec();                         // routed, and the key records themselves arrived: no k_keys pass
+  const bool routed = route.routed();
+  const uint64_t records = routed ? std::max<uint64_t>(std::max(route.m[0], route.m[1]), 1) : n;
   // buckets of ~10 000 records for k_group1, the levels, the tile and who takes the first histogram: swa_part_plan_for
   // (host_tables.cpp).  SWA_D1_PART_BITS=1..27 (test hook, read at every build): that many bits instead of what the number
   // of records gives; the bits of the key-overflow retry still come on top
@@ -1072,7 +1084,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     const int b = atoi(e);
     if (b >= 1 && b <= (int)(3 * kPartMaxBits)) { forced_bits = (uint32_t)b; }
   }
-  const swa_part_plan plan = swa_part_plan_for(records, ctx->stream_extra_bits, routed, forced_bits);
+  const swa_part_plan plan = swa_part_plan_for(records, ctx->up.d1.stream_extra_bits, routed, forced_bits);
   const uint32_t total_bits = plan.lv.total;
   const bool keys_hist = plan.keys_hist;
   PartJob j;
@@ -1081,9 +1093,9 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   j.max_records = records;
   j.out_cap = records + 1;
   j.tile = plan.tile;
-  swa_part_plan_report(plan, ctx->part_plan);
-  ctx->part_plan[7] = ctx->stream_extra_bits;                 // (swa_d1_part_plan: the retry's bits in place of `wide`)
-  ctx->part_starts_valid = false;
+  swa_part_plan_report(plan, ctx->ix.part_plan);
+  ctx->ix.part_plan[7] = ctx->up.d1.stream_extra_bits;                 // (swa_d1_part_plan: the retry's bits in place of `wide`)
+  ctx->ix.part_starts_valid = false;
   j.max_tiles0 = records / j.tile + 2;
   j.chunks0 = 1; j.single0 = true; j.top_bit = 32; j.bias = 0;
   uint64_t e_cnt, e_tile, e_start, e_partial;
@@ -1124,7 +1136,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   swa_lap(ctx, "buffers reserved, counters cleared");
   uint32_t * dflags = st->flags;                            // (cleared above — a new index — or by the caller: a retry, a network call's build)
   auto * scal = static_cast<uint64_t *>(ctx->d_stream[kSbScal].ptr);      // [0..3] level-0 chunk tables, [8 + i] totals (u32)
-  const uint32_t win_a = ctx->anchor_a, win_b = ctx->anchor_b;
+  const uint32_t win_a = ctx->ix.anchor_a, win_b = ctx->ix.anchor_b;
   const uint32_t minlen = anchor_minlen(ctx), window_mode = (win_a != 0 || win_b != 0) ? 1u : 0u;
 
   // ---- keys: records into the PONG halves (level 0 reads them from there), fingerprints likewise
@@ -1134,13 +1146,13 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   k.seqs = ctx->db.seqs; k.seq_off = ctx->db.seq_off;
   k.n = n;
   for (int i = 0; i < 2; ++i) {
-    k.list[i] = routed && !by_rec ? ctx->route_ids[i] : nullptr;
-    k.list_count[i] = routed ? ctx->route_m[i] : 0;
+    k.list[i] = routed && !by_rec ? route.ids[i] : nullptr;
+    k.list_count[i] = routed ? route.m[i] : 0;
     k.rec[i] = static_cast<unsigned long long *>(ctx->d_stream[kSbRec + 2 * i + 1].ptr);
   }
   k.owner_rank = ctx->owner_rank; k.owner_world = ctx->owner_world;
   k.win_a = win_a; k.win_b = win_b; k.minlen = minlen; k.window_mode = window_mode;
-  k.nwin = ctx->anchor_w / 32u;
+  k.nwin = ctx->ix.anchor_w / 32u;
   k.flags = dflags;
   k.guard = reinterpret_cast<unsigned long long *>(st->guard);
   // (single GPU, the whole database keyed: the short sequences and their possible neighbours become members of the plain
@@ -1153,10 +1165,10 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   }
   if (routed) {
     hipLaunchKernelGGL(k_set_flags, dim3(1), dim3(1), 0, ctx->stream, dflags,
-                       ctx->db_shortest < minlen ? 1u : 0u, 0xFFFFFFFFu - ctx->db_shortest);
+                       ctx->up.d1.db_shortest < minlen ? 1u : 0u, 0xFFFFFFFFu - ctx->up.d1.db_shortest);
   }
   if (by_rec) {   // (the records were made by the ranks that hold the amplicons' slices: what k_keys would have counted)
-    hipLaunchKernelGGL(k_set_guard_made, dim3(1), dim3(1), 0, ctx->stream, k.guard, ctx->route_m[0], ctx->route_m[1]);
+    hipLaunchKernelGGL(k_set_guard_made, dim3(1), dim3(1), 0, ctx->stream, k.guard, route.m[0], route.m[1]);
   }
   swa_t0(ctx, kTimeKeys);
   if (by_rec) { /* nothing to key */ }
@@ -1183,8 +1195,8 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   for (int i = 0; i < 2; ++i) {
     j.buf[i][0] = static_cast<unsigned long long *>(ctx->d_stream[kSbRec + 2 * i].ptr);
     j.buf[i][1] = static_cast<unsigned long long *>(ctx->d_stream[kSbRec + 2 * i + 1].ptr);
-    j.in[i] = by_rec ? ctx->route_rec[i] : j.buf[i][1];
-    j.cstart0[i] = nullptr; j.cstride0[i] = routed ? ctx->route_m[i] : n;   // (one chunk: [0, records of this index))
+    j.in[i] = by_rec ? route.rec[i] : j.buf[i][1];
+    j.cstart0[i] = nullptr; j.cstride0[i] = routed ? route.m[i] : n;   // (one chunk: [0, records of this index))
     j.cnt[i] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt + i].ptr);
     j.ctile[i] = static_cast<uint32_t *>(ctx->d_stream[kSbTile + i].ptr);
     j.starts[i] = static_cast<uint64_t *>(ctx->d_stream[kSbStart + i].ptr);
@@ -1198,17 +1210,17 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   SWA_TRY(run_partition(ctx, j));
   swa_t1(ctx, kTimeKeyPartition);
   swa_lap(ctx, "key partition");
-  ctx->part_starts_at = (uint64_t)(j.bstart[0] - j.starts[0]);   // (the same place in both indexes' buffers)
-  ctx->part_buckets = j.buckets;
-  ctx->part_starts_valid = true;
-  if (!ctx->guard_keys_done) {
+  ctx->ix.part_starts_at = (uint64_t)(j.bstart[0] - j.starts[0]);   // (the same place in both indexes' buffers)
+  ctx->ix.part_buckets = j.buckets;
+  ctx->ix.part_starts_valid = true;
+  if (!ctx->up.d1.guard_keys_done) {
     // the guard's second opinion on the key records, once per uploaded database: from the packed database against what the
     // partition holds (k_guard_db / k_guard_records); compared at the next guard_check
     auto * guard = reinterpret_cast<unsigned long long *>(st->guard);
     SWA_HIP(ctx, hipMemsetAsync(guard + kGuardKeys, 0, sizeof(st->guard) - kGuardKeys * sizeof(uint64_t), ctx->stream));
     GuardDbArgs gd{};
     gd.seqs = ctx->db.seqs; gd.seq_off = ctx->db.seq_off; gd.seqlen = ctx->db.seqlen; gd.n = n;
-    for (int i = 0; i < 2; ++i) { gd.list[i] = k.list[i]; gd.list_count[i] = routed ? ctx->route_m[i] : 0; gd.list_rec[i] = by_rec ? ctx->route_rec[i] : nullptr; }
+    for (int i = 0; i < 2; ++i) { gd.list[i] = k.list[i]; gd.list_count[i] = routed ? route.m[i] : 0; gd.list_rec[i] = by_rec ? route.rec[i] : nullptr; }
     gd.owner_rank = k.owner_rank; gd.owner_world = k.owner_world; gd.win_a = win_a; gd.win_b = win_b; gd.nwin = k.nwin;
     gd.out = guard + kGuardKeysDb;
     hipLaunchKernelGGL(k_guard_db, dim3((unsigned)grid_for(ctx, records, 256, 8), routed ? 2u : 1u), dim3(256), 0, ctx->stream, gd);
@@ -1216,7 +1228,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     for (int i = 0; i < 2; ++i) { gr.rec[i] = j.out[i]; gr.total[i] = j.total[i]; }
     gr.out = guard + kGuardKeysRec;
     hipLaunchKernelGGL(k_guard_records, dim3((unsigned)grid_for(ctx, records, 256, 8), 2u), dim3(256), 0, ctx->stream, gr);
-    ctx->guard_keys_pending = true;
+    ctx->up.d1.guard_keys_pending = true;
   }
 
   swa_lap(ctx, "guard: second opinion");
@@ -1264,7 +1276,7 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   if (plan.lists_inline) {
     // (every workgroup adds up the counts before its buckets itself — only the lists of width classes this database has)
     uint32_t mask = 0;
-    for (uint32_t c = 0; c < kWidthClasses; ++c) { if (ctx->class_pop[c] != 0) { mask |= ((1u << kListKinds) - 1u) << (c * kListKinds); } }
+    for (uint32_t c = 0; c < kWidthClasses; ++c) { if (ctx->up.d1.class_pop[c] != 0) { mask |= ((1u << kListKinds) - 1u) << (c * kListKinds); } }
     for (int i = 0; i < 2; ++i) { la.x[i].list_mask = mask; }
     hipLaunchKernelGGL(k_group_lists<true>, grid_l, dim3(256), 0, ctx->stream, la);
   } else {
@@ -1273,13 +1285,13 @@ static int build_stream_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
     hipLaunchKernelGGL(k_flat_apply, grid_k, dim3(256), 0, ctx->stream, f);
     hipLaunchKernelGGL(k_group_lists<false>, grid_l, dim3(256), 0, ctx->stream, la);
   }
-  ctx->lists_form = plan.lists_inline ? 1 : 0;
+  ctx->ix.lists_form = plan.lists_inline ? 1 : 0;
   SWA_HIP(ctx, hipGetLastError());
   swa_lap(ctx, "groups + work lists");
-  ctx->list_regions_items = item_room;
-  ctx->anchor_ready = true;
-  ctx->stream_index = true;
-  ctx->guard_index = true;
+  ctx->ix.list_regions_items = item_room;
+  ctx->ix.anchor_ready = true;
+  ctx->ix.stream_index = true;
+  ctx->ix.guard_index = true;
   return SWA_OK;
 }
 
@@ -1324,7 +1336,7 @@ static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const 
   j.cnt[0] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt].ptr);
   j.ctile[0] = static_cast<uint32_t *>(ctx->d_stream[kSbTile].ptr);
   j.starts[0] = static_cast<uint64_t *>(ctx->d_stream[kSbStart].ptr);
-  ctx->part_starts_valid = false;                             // (the prefix index's bucket starts lay there: selectors 17 / 18)
+  ctx->ix.part_starts_valid = false;                             // (the prefix index's bucket starts lay there: selectors 17 / 18)
   j.partial[0] = static_cast<uint32_t *>(ctx->d_stream[kSbPartial].ptr);
   j.total[0] = &swa_status(ctx)->links_sorted;
   j.starts_stride = e_start + 2;
@@ -1450,11 +1462,11 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const uint32_t maxwords = (ctx->db.longest + 31u) >> 5;
   swa_t0(ctx, kTimeNetwork);
-  const bool window_mode = ctx->anchor_a != 0 || ctx->anchor_b != 0;
+  const bool window_mode = ctx->ix.anchor_a != 0 || ctx->ix.anchor_b != 0;
   uint64_t item_room = 0;
   const ListRegions regions = list_regions(ctx, &item_room);
-  if (item_room != ctx->list_regions_items) { return swa_fail_msg(ctx, SWA_E_ARG, "d=1 network: the work lists in place were laid out for another database"); }
-  const int nwin = (int)(ctx->anchor_w / 32u);
+  if (item_room != ctx->ix.list_regions_items) { return swa_fail_msg(ctx, SWA_E_ARG, "d=1 network: the work lists in place were laid out for another database"); }
+  const int nwin = (int)(ctx->ix.anchor_w / 32u);
   for (int pass = 0; pass < 2; ++pass) {
     swa_t0(ctx, kTimePass + pass);
     AnchorArgs a{};
@@ -1465,8 +1477,8 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
     a.seg_cap = ctx->seg_cap;
     a.seg_fill = static_cast<uint32_t *>(ctx->d_seg_fill.ptr);
     a.minlen = anchor_minlen(ctx);
-    a.win_word = ctx->anchor_a / 32u;
-    a.win_word_b = ctx->anchor_b / 32u;
+    a.win_word = ctx->ix.anchor_a / 32u;
+    a.win_word_b = ctx->ix.anchor_b / 32u;
     a.window_mode = window_mode ? 1u : 0u;
     a.seg_staged = static_cast<uint32_t *>(ctx->d_seg_fill.ptr) + (uint64_t)(1 + pass) * seg_count(ctx);
     a.guard = reinterpret_cast<unsigned long long *>(st->guard);
@@ -1474,12 +1486,12 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
     a.shard_bits = shard_bits;
     a.ids = static_cast<const uint32_t *>(ctx->d_stream[kSbMembers + pass].ptr);
     a.lines = static_cast<const uint4 *>(ctx->d_stream[kSbLines].ptr);
-    a.line_quads = ctx->lines_quads;
+    a.line_quads = ctx->up.d1.lines_quads;
     a.pair_items = static_cast<const swa_item *>(ctx->d_aitems[pass].ptr);
     for (uint32_t cls = 0; cls < kWidthClasses; ++cls) {
       // (a group of class c has a member of class c: no such sequences, no such groups.  Lines too narrow for the class's
       // records cannot occur: the lines are as wide as the longest sequence needs)
-      if (ctx->class_pop[cls] == 0) { continue; }
+      if (ctx->up.d1.class_pop[cls] == 0) { continue; }
       const int width = width_words(cls);
       if (nwin == 4 && width < 15) { return swa_fail_msg(ctx, SWA_E_ARG, "pair kernels: 128-nt windows with sequences of 256 nt or less"); }
       const uint32_t pc = (uint32_t)pass * kWidthClasses + cls;
@@ -1492,7 +1504,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
       a.sched_wide = static_cast<uint32_t *>(ctx->d_stream[kSbSched].ptr) + ((uint64_t)pc << shard_bits) * kSchedStride;
       // (the pair kernel hands its work out through counters: exactly the workgroups that are resident together, no second round;
       // no launch over lists the index build found empty)
-      const uint32_t * have = ctx->list_counts_ready ? ctx->list_counts + pc * 8u : nullptr;
+      const uint32_t * have = ctx->ix.list_counts_ready ? ctx->ix.list_counts + pc * 8u : nullptr;
       bool any_pairs = have == nullptr;
       for (uint32_t k = 0; k <= kPairClasses && have != nullptr; ++k) { any_pairs = any_pairs || have[k] != 0u; }
       // Bundles per visit of a work counter: 4 where every wave has dozens of bundles to go through (10 M amplicons: the counters
@@ -1513,8 +1525,8 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   }
   // seeds (or halves of seeds) the anchored passes skipped (a lean build has made sure there are none: no sequence
   // too short, no oversized group — and what holds for the whole database holds for every part of it)
-  const bool use_member_table = ctx->member_index && !ctx->full_index;
-  if (ctx->full_index || ctx->member_index) {
+  const bool use_member_table = ctx->ix.member_index && !ctx->ix.full_index;
+  if (ctx->ix.full_index || ctx->ix.member_index) {
     hipLaunchKernelGGL(k_stream_fallback, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, first, count,
                        static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr), static_cast<swa_fallback *>(ctx->d_afallback.ptr), acounters + kCounterFallback,
                        ctx->owner_rank, ctx->owner_world, ctx->db.seqs, ctx->db.seq_off, anchor_minlen(ctx));
@@ -1524,9 +1536,9 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   f.zobrist = static_cast<const uint64_t *>(ctx->d_zobrist.ptr);
   f.zlen = ctx->zobrist_len; f.maxwords = maxwords;
   f.table = static_cast<const swa_slot *>(use_member_table ? ctx->d_stream[kSbMTable].ptr : ctx->d_table.ptr);
-  f.tmask = (use_member_table ? ctx->mtable_size : ctx->table_size) - 1;
+  f.tmask = (use_member_table ? ctx->ix.mtable_size : ctx->ix.table_size) - 1;
   f.bloom = static_cast<const uint64_t *>(use_member_table ? ctx->d_stream[kSbMBloom].ptr : ctx->d_bloom.ptr);
-  f.bmask = (use_member_table ? ctx->mbloom_words : ctx->bloom_words) - 1;
+  f.bmask = (use_member_table ? ctx->ix.mbloom_words : ctx->ix.bloom_words) - 1;
   f.patterns = static_cast<const uint64_t *>(ctx->d_patterns.ptr);
   f.no_cluster_breaking = ncb;
   f.first = first; f.count = count;
@@ -1537,13 +1549,13 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   f.fallback_count = acounters + kCounterFallback;
   f.aux = static_cast<const swa_aux *>(ctx->d_aux.ptr);
   f.owner_rank = 0; f.owner_world = 1;                       // the list already is this rank's share
-  f.window_mode = window_mode ? 1u : 0u; f.win_word = ctx->anchor_a / 32u; f.anchor_w = ctx->anchor_w;
+  f.window_mode = window_mode ? 1u : 0u; f.win_word = ctx->ix.anchor_a / 32u; f.anchor_w = ctx->ix.anchor_w;
   const size_t flds = sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + 1024ull +
                                           kWaves * ((size_t)(maxwords + 2u) + kQueueCap + kQueueCap / 2));
   const int fgrid = grid_for(ctx, count, kWaves, 8);
   // (a rank that built only its owned groups has no table: by construction its fallback list is
   // empty — network_run checks the count and builds the full index if that ever fails to hold)
-  if (!ctx->full_index && !ctx->member_index) { /* nothing to probe against */ }
+  if (!ctx->ix.full_index && !ctx->ix.member_index) { /* nothing to probe against */ }
   else if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
   else { hipLaunchKernelGGL((k_d1_probe<false, 2>), dim3(fgrid), dim3(kThreads), flds, ctx->stream, f); }
   swa_t1(ctx, kTimeNetwork);
@@ -1551,8 +1563,6 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   return SWA_OK;
 }
 
-// Zobrist table + per-amplicon sequence hashes (src/db.cc:761, src/zobrist.cc:89-112) and the
-// anchored-index metadata; shared by the d = 1 index and the d = 0 dereplication
 // Zobrist table in HBM (it only depends on its length: uploaded once) + room for the hashes
 static int prepare_hashing(swa_ctx * ctx) {
   const uint32_t n = ctx->db.n;
@@ -1580,11 +1590,11 @@ static int launch_seqhash(swa_ctx * ctx, const uint8_t * only = nullptr) {
   if (zlds) {
     hipLaunchKernelGGL(k_seqhash<true>, dim3(hgrid), dim3(256), zbytes, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                        ctx->db.seqlen, static_cast<const uint64_t *>(ctx->d_zobrist.ptr), ctx->zobrist_len, n,
-                       static_cast<uint64_t *>(ctx->d_seqhash.ptr), static_cast<swa_aux *>(ctx->d_aux.ptr), ctx->anchor_w, only);
+                       static_cast<uint64_t *>(ctx->d_seqhash.ptr), static_cast<swa_aux *>(ctx->d_aux.ptr), ctx->ix.anchor_w, only);
   } else {
     hipLaunchKernelGGL(k_seqhash<false>, dim3(hgrid), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                        ctx->db.seqlen, static_cast<const uint64_t *>(ctx->d_zobrist.ptr), ctx->zobrist_len, n,
-                       static_cast<uint64_t *>(ctx->d_seqhash.ptr), static_cast<swa_aux *>(ctx->d_aux.ptr), ctx->anchor_w, only);
+                       static_cast<uint64_t *>(ctx->d_seqhash.ptr), static_cast<swa_aux *>(ctx->d_aux.ptr), ctx->ix.anchor_w, only);
   }
   SWA_HIP(ctx, hipGetLastError());
   swa_t1(ctx, kTimeSeqhash);
@@ -1598,24 +1608,19 @@ int swa_hash_sequences(swa_ctx * ctx) {
   return launch_seqhash(ctx);
 }
 
-extern "C" int swa_d1_index_build(swa_ctx * ctx, int * has_duplicates) {
-  if (ctx == nullptr) { return SWA_E_ARG; }
-  return swa_d1_index_build_range(ctx, 0, ctx->db.n, has_duplicates);
-}
-
 // hashes of ALL amplicons + the database-wide table and Bloom filter (src/algod1.cc:188-208,
 // src/bloompat.cc): what the plain kernel, the fastidious pass and the debug readers work on.
 // Always built by a single-GPU index build; a rank that serves only the anchor groups it owns
 // builds it on demand (rarely: see build_owned_index).
 static int ensure_full_index(swa_ctx * ctx) {
-  if (ctx->full_index) { return SWA_OK; }
-  SWA_TRY(swa_reserve(ctx, ctx->d_table, ctx->table_size * sizeof(swa_slot)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_bloom, ctx->bloom_words * sizeof(uint64_t)));
+  if (ctx->ix.full_index) { return SWA_OK; }
+  SWA_TRY(swa_reserve(ctx, ctx->d_table, ctx->ix.table_size * sizeof(swa_slot)));
+  SWA_TRY(swa_reserve(ctx, ctx->d_bloom, ctx->ix.bloom_words * sizeof(uint64_t)));
   SWA_TRY(swa_hash_sequences(ctx));
   swa_t0(ctx, kTimeTable);
   SWA_TRY(swa_d1_rebuild_table(ctx, nullptr));
   swa_t1(ctx, kTimeTable);
-  ctx->full_index = true;
+  ctx->ix.full_index = true;
   return SWA_OK;
 }
 
@@ -1623,15 +1628,15 @@ static int ensure_full_index(swa_ctx * ctx) {
 // amplicons in oversized groups and of too-short seeds is below 1 / 64 each; (0, 0) when nothing is skewed, which is
 // the normal case.  Window mode needs the pair kernels (sequences up to 416 nt).
 static int choose_anchor_windows(swa_ctx * ctx) {
-  ctx->anchor_a = ctx->anchor_b = 0;
-  ctx->anchor_w = 32;
+  ctx->ix.anchor_a = ctx->ix.anchor_b = 0;
+  ctx->ix.anchor_w = 32;
   SWA_TRY(ensure_db_lengths(ctx));
-  const uint32_t shortest = ctx->db_shortest;
+  const uint32_t shortest = ctx->up.d1.db_shortest;
   const uint32_t n = ctx->db.n;
   const uint32_t max_nwin = anchor_max_nwin(ctx);
   // the ends, as wide as the shortest sequence allows — unless the sample finds them skewed (conserved flanks), then 32-nt
   // windows moved inwards
-  ctx->anchor_w = 32u * anchor_nwin_for(shortest, 0u, max_nwin);
+  ctx->ix.anchor_w = 32u * anchor_nwin_for(shortest, 0u, max_nwin);
   if (windows_search_off()) { return SWA_OK; }
   const uint32_t stride = std::max<uint32_t>(1u, n / 65536u);
   const uint32_t samples = (n + stride - 1) / stride;
@@ -1652,8 +1657,8 @@ static int choose_anchor_windows(swa_ctx * ctx) {
   for (uint32_t c = 0; c < kSampleCandidates; ++c) {
     const bool few_short = host[c] <= samples / 64u || c == 0;
     if (host[4 + c] <= samples / 64u && few_short) {
-      ctx->anchor_a = ctx->anchor_b = 32u * c;
-      ctx->anchor_w = 32u * anchor_nwin_for(shortest, 32u * c, max_nwin);
+      ctx->ix.anchor_a = ctx->ix.anchor_b = 32u * c;
+      ctx->ix.anchor_w = 32u * anchor_nwin_for(shortest, 32u * c, max_nwin);
       return SWA_OK;
     }
     if (!few_short) { break; }                               // (larger offsets only strand more seeds)
@@ -1664,14 +1669,14 @@ static int choose_anchor_windows(swa_ctx * ctx) {
 // the anchor windows of this database: chosen from a sample once per upload (and corrected by the safety net of the
 // first build if the sample misjudged), then reused
 static int ensure_anchor_windows(swa_ctx * ctx) {
-  if (!ctx->windows_ready) {
+  if (!ctx->up.d1.windows_ready) {
     SWA_TRY(choose_anchor_windows(ctx));
-    ctx->windows_chosen = ctx->anchor_a;
-    ctx->windows_w = ctx->anchor_w;
-    ctx->windows_ready = true;
+    ctx->up.d1.windows_chosen = ctx->ix.anchor_a;
+    ctx->up.d1.windows_w = ctx->ix.anchor_w;
+    ctx->up.d1.windows_ready = true;
   }
-  ctx->anchor_a = ctx->anchor_b = ctx->windows_chosen;
-  ctx->anchor_w = ctx->windows_w;
+  ctx->ix.anchor_a = ctx->ix.anchor_b = ctx->up.d1.windows_chosen;
+  ctx->ix.anchor_w = ctx->up.d1.windows_w;
   return SWA_OK;
 }
 
@@ -1683,13 +1688,13 @@ static int ensure_anchor_windows(swa_ctx * ctx) {
 // while it inserts (src/algod1.cc:1131-1150).
 
 static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_count) {
-  ctx->member_index = false;
+  ctx->ix.member_index = false;
   const uint32_t n = ctx->db.n;
   // Zobrist hashes + the XOR streams of the members (k_seqhash: nobody else is inserted, probed for or enumerated)
   SWA_TRY(prepare_hashing(ctx));
   SWA_TRY(launch_seqhash(ctx, static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr)));
   uint64_t slots = 1024;
-  while (slots < 2ull * ctx->over_mass) { slots <<= 1; }
+  while (slots < 2ull * ctx->ix.over_mass) { slots <<= 1; }
   const uint64_t words = std::max<uint64_t>(slots >> 3, 1);  // one byte of filter per slot, as the reference sizes it
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbMTable], slots * sizeof(swa_slot)));
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbMBloom], words * sizeof(uint64_t)));
@@ -1708,9 +1713,9 @@ static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   }
   swa_t1(ctx, kTimeDupCheck);
   SWA_HIP(ctx, hipGetLastError());
-  ctx->mtable_size = slots;
-  ctx->mbloom_words = words;
-  ctx->member_index = true;
+  ctx->ix.mtable_size = slots;
+  ctx->ix.mbloom_words = words;
+  ctx->ix.member_index = true;
   return SWA_OK;
 }
 
@@ -1720,20 +1725,16 @@ static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
 // those members only, duplicates inside the owned prefix groups.  *needs_table is set when some
 // seed can only be served by the plain kernel (a sequence shorter than 65 nt anywhere, a group
 // too large for LDS) or the db order does not hold: the caller then builds the full index.
-static int build_owned_index(swa_ctx * ctx, uint32_t first, uint32_t count, bool * needs_table, uint32_t * dups, uint32_t * oversized_mass = nullptr,
+static int build_owned_index(swa_ctx * ctx, const RouteLists & route, bool * needs_table, uint32_t * dups, uint32_t * oversized_mass = nullptr,
                              uint32_t * shortest = nullptr) {
-  const uint32_t n = ctx->db.n;
   swa_lap(ctx, "(owned index starts)");
   // (no Zobrist table, no hash / XOR-stream arrays here: the pair route needs none of them — 240 MB of HBM at 10 M and an
   // upload with its synchronisation per build; the member table and the database-wide table prepare them when they are built)
   SWA_TRY(launch_abundance_rank(ctx));
   swa_lap(ctx, "abundance ranks");
-  // a rank of a multi-GPU job answers for the groups it owns, whichever slice their members lie in (each pair of
-  // identical sequences is seen by exactly one rank); a single GPU honours the slice it was asked about
-  const uint32_t dup_first = ctx->owner_world > 1 ? 0u : first, dup_count = ctx->owner_world > 1 ? n : count;
   // streaming build (d1_stream.inc): keys, partition, groups + work lists + identical sequences, all in one go
   swa_t0(ctx, kTimeIndex);
-  SWA_TRY(build_stream_index(ctx, dup_first, dup_count));
+  SWA_TRY(build_stream_index(ctx, route));
   swa_t1(ctx, kTimeIndex);
   // (ONE copy of the status block up to the split cursors: the flags, and how long the work lists are — the network call
   // then launches no kernel over an empty one)
@@ -1743,44 +1744,42 @@ static int build_owned_index(swa_ctx * ctx, uint32_t first, uint32_t count, bool
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const uint32_t * flags = status->flags;
   *dups = flags[kFlagDuplicates];
-  memcpy(ctx->list_counts, status->counters + kCounterBase, sizeof(ctx->list_counts));
-  ctx->list_counts_ready = true;
+  memcpy(ctx->ix.list_counts, status->counters + kCounterBase, sizeof(ctx->ix.list_counts));
+  ctx->ix.list_counts_ready = true;
   if (oversized_mass != nullptr) { *oversized_mass = flags[kFlagOverMass]; }
   if (shortest != nullptr) { *shortest = 0xFFFFFFFFu - flags[kFlagShortest]; }
   if (flags[kFlagKeyOverflow] != 0) {                       // a bucket with more distinct keys than the group kernel's table: finer
-    if (ctx->stream_extra_bits >= 8) { return swa_fail_msg(ctx, SWA_E_DEVICE, "streaming index build: partition still too coarse"); }
-    ctx->stream_extra_bits += 2;
+    if (ctx->up.d1.stream_extra_bits >= 8) { return swa_fail_msg(ctx, SWA_E_DEVICE, "streaming index build: partition still too coarse"); }
+    ctx->up.d1.stream_extra_bits += 2;
     SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags, 0, sizeof(status->flags), ctx->stream));
-    return build_owned_index(ctx, first, count, needs_table, dups, oversized_mass, shortest);
+    return build_owned_index(ctx, route, needs_table, dups, oversized_mass, shortest);
   }
   const bool unordered = flags[kFlagUnordered] != 0, unserved = flags[kFlagUnserved] != 0, oversized = flags[kFlagOversized] != 0;
-  if (unordered) { ctx->db_unordered = true; }
+  if (unordered) { ctx->up.d1.db_unordered = true; }
   *needs_table = unordered || unserved || oversized;
   // (groups left to the plain kernel — and, on a single GPU, sequences too short for two windows — are the ONLY reason: a
   // table of their members alone serves it — build_member_index)
-  ctx->only_oversized = !unordered && (oversized || unserved) &&
-                        (!unserved || (ctx->owner_world == 1u && ctx->route_ids[0] == nullptr && ctx->route_rec[0] == nullptr));
-  ctx->over_mass = flags[kFlagOverMass];
+  ctx->ix.only_oversized = !unordered && (oversized || unserved) &&
+                        (!unserved || (ctx->owner_world == 1u && !route.routed()));
+  ctx->ix.over_mass = flags[kFlagOverMass];
   return SWA_OK;
 }
 
-extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t count, int * has_duplicates) {
+// The index build behind swa_d1_index_build, _range, _routed and _records, and the guard's rebuild
+static int index_build(swa_ctx * ctx, uint32_t first, uint32_t count, const RouteLists & route, int * has_duplicates) {
   if (ctx == nullptr) { return SWA_E_ARG; }
   if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_index_build: no database"); }
   if (first > ctx->db.n || count > ctx->db.n - first) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_index_build_range: bad range"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
-  ctx->index_first = first; ctx->index_count = count; ctx->index_routed = ctx->route_ids[0] != nullptr || ctx->route_rec[0] != nullptr;   // (network_run_guarded repeats it)
-  ctx->d1_ready = false;
-  ctx->csr_ready = false;                                   // (a resident network belongs to the index it was made from)
-  ctx->anchor_ready = false;
-  ctx->full_index = false;
-  ctx->member_index = false;
-  ctx->anchor_a = ctx->anchor_b = 0;
+  ctx->ix = {};                                             // the index in place ends here ...
+  ctx->res = {};                                            // ... and a resident network belongs to the index it was made from
+  const bool routed = route.routed();
+  ctx->ix.index_first = first; ctx->ix.index_count = count; ctx->ix.index_routed = routed;   // (network_run_guarded repeats it)
   for (int slot : {kTimeSeqhash, kTimeTable, kTimeDupCheck, kTimeIndex, kTimeKeys, kTimeKeyPartition, kTimeGroups, kTimeLines}) { ctx->ev_used[slot] = false; }   // phases this build does not run report 0
-  ctx->table_size = swa_hashtable_size(n);
-  const uint64_t bloom_bytes = ctx->table_size < 8 ? 8 : ctx->table_size;   // bloompat.cc:100-113
-  ctx->bloom_words = bloom_bytes >> 3;
+  ctx->ix.table_size = swa_hashtable_size(n);
+  const uint64_t bloom_bytes = ctx->ix.table_size < 8 ? 8 : ctx->ix.table_size;   // bloompat.cc:100-113
+  ctx->ix.bloom_words = bloom_bytes >> 3;
 
   if (!ctx->patterns_resident) {                            // the 1024 Bloom patterns are constants: upload once
     std::vector<uint64_t> pat;
@@ -1793,27 +1792,24 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
   // (flags, stats and the guard's index / network counters lie together at the head of the status block: one fill, up to
   // the guard's second opinion)
   swa_status_block * st = swa_status(ctx);
-  ctx->guard_index = false;
-  ctx->anchor_w = 32;
-  ctx->anchor_usable = anchor_applicable(ctx);
+  ctx->ix.anchor_usable = anchor_applicable(ctx);
   // (the streaming build clears this head with its own counters, one launch: nothing before its clear writes there but the
   // abundance ranks' kFlagUnordered, which that clear leaves alone; the other route fills it here)
-  ctx->head_clear_pending = ctx->anchor_usable;
-  if (!ctx->anchor_usable) { SWA_HIP(ctx, hipMemsetAsync(st, 0, offsetof(swa_status_block, guard) + kGuardKeys * sizeof(uint64_t), ctx->stream)); }
+  ctx->ix.head_clear_pending = ctx->ix.anchor_usable;
+  if (!ctx->ix.anchor_usable) { SWA_HIP(ctx, hipMemsetAsync(st, 0, offsetof(swa_status_block, guard) + kGuardKeys * sizeof(uint64_t), ctx->stream)); }
 
   bool owned_ok = false;                                    // served without the database-wide table
   uint32_t group_dups = 0;
   // The lean build (no database-wide table / Bloom / table-based duplicate check) serves a single GPU as well
   // as a rank of a multi-GPU job: with world = 1 this GPU owns every anchor group.
-  if (ctx->anchor_usable) {
+  if (ctx->ix.anchor_usable) {
     bool needs_table = false;
     uint32_t mass = 0, shortest = 0;
     swa_lap(ctx, "(index build: before the windows)");
     SWA_TRY(ensure_anchor_windows(ctx));
     swa_lap(ctx, "anchor windows");
-    const uint32_t sampled = ctx->anchor_a;
-    const bool routed = ctx->route_ids[0] != nullptr || ctx->route_rec[0] != nullptr;        // (the lists were made under these windows: no second thoughts)
-    SWA_TRY(build_owned_index(ctx, first, count, &needs_table, &group_dups, &mass, &shortest));
+    const uint32_t sampled = ctx->ix.anchor_a;
+    SWA_TRY(build_owned_index(ctx, route, &needs_table, &group_dups, &mass, &shortest));
     // Conserved flanks: when a noticeable part of the database sits in groups too large for LDS (everybody shares
     // the first or last 32 nt), the anchor windows move inwards, 32 nt at a time, as far as the shortest sequence
     // allows (every seed needs win_a + win_b + 65 nt), and the setting with the fewest stranded members wins.
@@ -1821,29 +1817,31 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
     // Single GPU only: under ownership `mass` counts the oversized groups THIS rank owns, the ranks would settle on
     // different windows and divide the pairs differently; there the sampled choice — the same on every rank — stands
     // and oversized groups take the plain kernel)
+    // (a routed build's lists were made under the sampled windows: no second thoughts)
     if (!routed && ctx->owner_world == 1 && needs_table && mass > n / 64u && !windows_search_off()) {
       uint32_t best = sampled, best_mass = mass;
       for (uint32_t w = sampled + 32u; 2u * w + kMinAnchoredLen <= shortest && w <= 96u; w += 32u) {
-        ctx->anchor_a = ctx->anchor_b = w;
-        ctx->anchor_w = 32;                                     // (moved windows: anchor_nwin_for)
+        ctx->ix.anchor_a = ctx->ix.anchor_b = w;
+        ctx->ix.anchor_w = 32;                                     // (moved windows: anchor_nwin_for)
         SWA_HIP(ctx, hipMemsetAsync(st->flags, 0, sizeof(st->flags), ctx->stream));
         uint32_t m = 0;
-        SWA_TRY(build_owned_index(ctx, first, count, &needs_table, &group_dups, &m));
+        SWA_TRY(build_owned_index(ctx, route, &needs_table, &group_dups, &m));
         if (m < best_mass) { best_mass = m; best = w; }
         if (m <= n / 64u) { break; }
       }
-      if (ctx->anchor_a != best) {                            // (the last one tried was not the best: build that one again)
-        ctx->anchor_a = ctx->anchor_b = best;
-        ctx->anchor_w = best == sampled ? ctx->windows_w : 32u;
+      if (ctx->ix.anchor_a != best) {                            // (the last one tried was not the best: build that one again)
+        ctx->ix.anchor_a = ctx->ix.anchor_b = best;
+        ctx->ix.anchor_w = best == sampled ? ctx->up.d1.windows_w : 32u;
         SWA_HIP(ctx, hipMemsetAsync(st->flags, 0, sizeof(st->flags), ctx->stream));
-        SWA_TRY(build_owned_index(ctx, first, count, &needs_table, &group_dups));
+        SWA_TRY(build_owned_index(ctx, route, &needs_table, &group_dups));
       }
     }
-    ctx->windows_chosen = ctx->anchor_a;                     // (what the safety net settled on, for the next build)
-    ctx->windows_w = ctx->anchor_w;
+    ctx->up.d1.windows_chosen = ctx->ix.anchor_a;                     // (what the safety net settled on, for the next build)
+    ctx->up.d1.windows_w = ctx->ix.anchor_w;
     owned_ok = !needs_table;
-    if (!owned_ok && ctx->only_oversized) {
-      // nothing but groups too large for the pair kernels stands in the way: a table of their members is all the plain kernel needs
+    if (!owned_ok && ctx->ix.only_oversized) {
+      // nothing but groups too large for the pair kernels stands in the way: a table of their members is all the plain kernel needs.  Their
+      // twins: a rank of a multi-GPU job answers for the groups it owns, whichever slice the members lie in; a single GPU honours the slice asked about
       SWA_TRY(build_member_index(ctx, ctx->owner_world > 1 ? 0u : first, ctx->owner_world > 1 ? n : count));
       owned_ok = true;
       // (the member table's own search for identical sequences may have raised the flag since the build looked at it)
@@ -1861,12 +1859,12 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
     if (count > 0) {
       hipLaunchKernelGGL(k_dup_check, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                          ctx->db.seqlen, static_cast<const uint64_t *>(ctx->d_seqhash.ptr), first, count,
-                         static_cast<const swa_slot *>(ctx->d_table.ptr), ctx->table_size - 1,
+                         static_cast<const swa_slot *>(ctx->d_table.ptr), ctx->ix.table_size - 1,
                          swa_status(ctx)->flags + kFlagDuplicates);
     }
     SWA_HIP(ctx, hipGetLastError());
     swa_t1(ctx, kTimeDupCheck);
-    if (ctx->anchor_usable) {
+    if (ctx->ix.anchor_usable) {
       SWA_TRY(launch_abundance_rank(ctx));
       SWA_HIP(ctx, hipGetLastError());
     }
@@ -1874,9 +1872,9 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
     SWA_HIP(ctx, hipMemcpyAsync(flags, st->flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     flag |= flags[kFlagDuplicates];
-    if (flags[kFlagUnordered] != 0) { ctx->anchor_usable = false; ctx->db_unordered = true; }   // the anchored passes rely on the db order
+    if (flags[kFlagUnordered] != 0) { ctx->ix.anchor_usable = false; ctx->up.d1.db_unordered = true; }   // the anchored passes rely on the db order
   }
-  ctx->d1_ready = true;
+  ctx->ix.d1_ready = true;
   if (has_duplicates != nullptr) { *has_duplicates = flag != 0 ? 1 : 0; }
   if (flag != 0) {
     return swa_fail_msg(ctx, SWA_E_DUPLICATES, "some fasta entries have identical sequences");
@@ -1884,15 +1882,20 @@ extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t 
   return SWA_OK;
 }
 
-// width of the anchor windows the last index build chose, in nucleotides (32, 64 or 128)
-extern "C" uint32_t swa_d1_anchor_width(const swa_ctx * ctx) { return ctx != nullptr ? ctx->anchor_w : 0; }
+extern "C" int swa_d1_index_build_range(swa_ctx * ctx, uint32_t first, uint32_t count, int * has_duplicates) {
+  return index_build(ctx, first, count, RouteLists{}, has_duplicates);
+}
+extern "C" int swa_d1_index_build(swa_ctx * ctx, int * has_duplicates) { return swa_d1_index_build_range(ctx, 0, ctx != nullptr ? ctx->db.n : 0, has_duplicates); }
 
-extern "C" uint64_t swa_d1_table_size(const swa_ctx * ctx) { return ctx != nullptr ? ctx->table_size : 0; }
+// width of the anchor windows the last index build chose, in nucleotides (32, 64 or 128)
+extern "C" uint32_t swa_d1_anchor_width(const swa_ctx * ctx) { return ctx != nullptr ? ctx->ix.anchor_w : 0; }
+
+extern "C" uint64_t swa_d1_table_size(const swa_ctx * ctx) { return ctx != nullptr ? ctx->ix.table_size : 0; }
 
 // the anchor windows the last index build chose: out2 = {nt from the start, nt from the end} (0, 0 = the first / last 32 nt)
 extern "C" int swa_d1_anchor_windows(const swa_ctx * ctx, uint32_t * out2) {
   if (ctx == nullptr || out2 == nullptr) { return SWA_E_ARG; }
-  out2[0] = ctx->anchor_a; out2[1] = ctx->anchor_b;
+  out2[0] = ctx->ix.anchor_a; out2[1] = ctx->ix.anchor_b;
   return SWA_OK;
 }
 
@@ -1910,9 +1913,9 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
   a.zlen = ctx->zobrist_len;
   a.maxwords = (ctx->db.longest + 31u) >> 5;
   a.table = static_cast<const swa_slot *>(ctx->d_table.ptr);
-  a.tmask = ctx->table_size - 1;
+  a.tmask = ctx->ix.table_size - 1;
   a.bloom = static_cast<const uint64_t *>(ctx->d_bloom.ptr);
-  a.bmask = ctx->bloom_words - 1;
+  a.bmask = ctx->ix.bloom_words - 1;
   a.patterns = static_cast<const uint64_t *>(ctx->d_patterns.ptr);
   a.no_cluster_breaking = ncb;
   a.first = first; a.count = count;
@@ -1951,8 +1954,8 @@ static int guard_check(swa_ctx * ctx, const swa_status_block & status) {
     snprintf(msg, sizeof(msg), "d=1 guard: %llu member(s) filed under an anchor key that is not theirs", (unsigned long long)g[kGuardMisfiled]);
     return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
   }
-  if (ctx->stream_index && ctx->guard_keys_pending) {
-    ctx->guard_keys_pending = false;
+  if (ctx->ix.stream_index && ctx->up.d1.guard_keys_pending) {
+    ctx->up.d1.guard_keys_pending = false;
     for (int i = 0; i < 2; ++i) {
       const uint64_t from_db = g[kGuardKeysDb + i], from_records = g[kGuardKeysRec + i];
       if (from_db != from_records) {
@@ -1962,9 +1965,9 @@ static int guard_check(swa_ctx * ctx, const swa_status_block & status) {
         return swa_fail_msg(ctx, SWA_E_INTERNAL, msg);
       }
     }
-    ctx->guard_keys_done = true;
+    ctx->up.d1.guard_keys_done = true;
   }
-  if (ctx->stream_index && ctx->guard_index) {
+  if (ctx->ix.stream_index && ctx->ix.guard_index) {
     for (int i = 0; i < 2; ++i) {
       if (made[i] != listed[i] + single[i] + over[i]) {
         snprintf(msg, sizeof(msg), "d=1 guard: index %d has %llu key records but %llu + %llu + %llu grouped members", i, (unsigned long long)made[i],
@@ -1995,7 +1998,7 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   swa_status_block * st = swa_status(ctx);
   // hits leave the kernels through per-wave segments of the edge buffer (no shared counter)
-  const uint32_t nseg = (uint32_t)ctx->num_cus * 8u * kWaves;          // >= waves of any launch below
+  const uint32_t nseg = seg_count(ctx);                       // >= waves of any launch below
   SWA_TRY(swa_reserve(ctx, ctx->d_seg_fill, 3ull * nseg * sizeof(uint32_t)));   // fills | members staged, pass 0 | pass 1
   if (ctx->seg_cap == 0) {
     ctx->seg_cap = 512;
@@ -2010,25 +2013,25 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
   for (int attempt = 0; attempt < 8 && !clean; ++attempt) {
     SWA_TRY(swa_reserve(ctx, ctx->d_edges, uint64_t(nseg) * ctx->seg_cap * sizeof(uint64_t)));
     // (the segment fills start at zero: the anchored route clears them with its other counters — one launch —, the plain one here)
-    if (!ctx->anchor_usable) { SWA_HIP(ctx, hipMemsetAsync(ctx->d_seg_fill.ptr, 0, 3ull * nseg * sizeof(uint32_t), ctx->stream)); }
-    if (ctx->anchor_usable) {
-      if (!(ctx->anchor_ready && ctx->stream_index)) {
+    if (!ctx->ix.anchor_usable) { SWA_HIP(ctx, hipMemsetAsync(ctx->d_seg_fill.ptr, 0, 3ull * nseg * sizeof(uint32_t), ctx->stream)); }
+    if (ctx->ix.anchor_usable) {
+      if (!(ctx->ix.anchor_ready && ctx->ix.stream_index)) {
         // (the streaming index serves any query range; it is rebuilt when the owner changed)
         swa_t0(ctx, kTimeIndex);
         SWA_TRY(launch_abundance_rank(ctx));
         // (kFlagKeyOverflow .. kFlagShortest, what the streaming build raises: the previous owner's values must not survive
         // into this owner's build — kFlagUnserved is only ever set, kFlagOversized / kFlagOverMass accumulate)
         SWA_HIP(ctx, hipMemsetAsync(st->flags + kFlagKeyOverflow, 0, (kFlagsD1 - kFlagKeyOverflow) * sizeof(uint32_t), ctx->stream));
-        SWA_TRY(build_stream_index(ctx, 0, 0));
+        SWA_TRY(build_stream_index(ctx, RouteLists{}));
         swa_t1(ctx, kTimeIndex);
         // The index of another owner (swa_d1_set_ownership after the build): the member table and its Bloom filter hold the
         // previous owner's oversized groups, so they are dropped, and whatever this owner's groups leave to the plain kernel
         // (kFlagUnserved, kFlagOversized) gets the database-wide table
-        if (!ctx->full_index) {
+        if (!ctx->ix.full_index) {
           uint32_t fl[kFlagOverMass + 1] = {};
           SWA_HIP(ctx, hipMemcpyAsync(fl, st->flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
           SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-          ctx->member_index = false;
+          ctx->ix.member_index = false;
           if (fl[kFlagUnserved] != 0 || fl[kFlagOversized] != 0) { SWA_TRY(ensure_full_index(ctx)); }
         }
       }
@@ -2038,7 +2041,7 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       SWA_TRY(ensure_full_index(ctx));
       SWA_TRY(launch_network(ctx, no_cluster_breaking, first, count));
     }
-    const bool check_unserved = ctx->anchor_usable && !ctx->full_index && !ctx->member_index;
+    const bool check_unserved = ctx->ix.anchor_usable && !ctx->ix.full_index && !ctx->ix.member_index;
     // CSR assembly is enqueued right behind, before the host looks at the totals: every kernel
     // below guards its writes with `cap` / the segment capacity, so a run that turns out to
     // need bigger segments or a bigger neighbour buffer has only wasted these launches.
@@ -2056,7 +2059,7 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     } else {
       // CSR: the links sorted by source with the partition primitive
       stream_link_cap = std::max<uint64_t>(std::max<uint64_t>(cap, stream_link_cap), 2ull * count + 1024);
-      SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap, ctx->anchor_usable));
+      SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap, ctx->ix.anchor_usable));
     }
     SWA_HIP(ctx, hipGetLastError());
     swa_t1(ctx, kTimeCsr);
@@ -2069,12 +2072,12 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     const uint64_t * seg = status->stats + kStatSeg;          // what was made of the segments (SegArgs / k_seg_reduce)
     const uint64_t fullest = seg[kSegFullest];
     const uint32_t anchor_overflow = status->flags[kFlagKeyOverflow];
-    const bool guarded = ctx->anchor_usable;
+    const bool guarded = ctx->ix.anchor_usable;
     n_edges = seg[kSegLinks];
     if (guarded && anchor_overflow != 0) {
       // a bucket of the index rebuilt above held more distinct keys than the group kernel's table: partition finer, again
-      ctx->stream_extra_bits = std::min<uint32_t>(ctx->stream_extra_bits + 2, 8);
-      ctx->anchor_ready = false;
+      ctx->up.d1.stream_extra_bits = std::min<uint32_t>(ctx->up.d1.stream_extra_bits + 2, 8);
+      ctx->ix.anchor_ready = false;
       continue;
     }
     if (check_unserved && unserved != 0) {                   // should not happen (build_owned_index looks for such seeds)
@@ -2117,16 +2120,15 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
 static int network_run_guarded(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, uint32_t count, uint64_t * d_offsets,
                                uint32_t * d_neighbours, uint64_t * d_edge_list, uint64_t cap, uint64_t * total) {
   const int rc = network_run(ctx, no_cluster_breaking, first, count, d_offsets, d_neighbours, d_edge_list, cap, total);
-  if (rc != SWA_E_INTERNAL || ctx->index_routed) { return rc; }
+  if (rc != SWA_E_INTERNAL || ctx->ix.index_routed) { return rc; }
   const std::string first_msg = ctx->err;
   fprintf(stderr, "swarm-amd: %s; rebuilding the index from the packed database and repeating the step\n", first_msg.c_str());
   ++ctx->guard_retries;
-  ctx->lines_ready = ctx->props_ready = ctx->windows_ready = ctx->rank_ready = ctx->fast_classes_ready = false;
-  ctx->anchor_ready = ctx->stream_index = ctx->member_index = ctx->full_index = false;
-  ctx->guard_index = ctx->guard_keys_done = ctx->guard_keys_pending = false;
-  ctx->stream_extra_bits = 0;
+  const uint32_t index_first = ctx->ix.index_first, index_count = ctx->ix.index_count;
+  ctx->up.d1 = {};
+  ctx->ix = {};
   int dup = 0;
-  const int rb = swa_d1_index_build_range(ctx, ctx->index_first, ctx->index_count, &dup);
+  const int rb = index_build(ctx, index_first, index_count, RouteLists{}, &dup);
   if (rb != SWA_OK && rb != SWA_E_DUPLICATES) { return rb; }
   const int again = network_run(ctx, no_cluster_breaking, first, count, d_offsets, d_neighbours, d_edge_list, cap, total);
   if (again == SWA_E_INTERNAL) { ctx->err = first_msg + "; after a rebuild: " + ctx->err; }
@@ -2138,7 +2140,7 @@ extern "C" int swa_d1_guard_retries(const swa_ctx * ctx) { return ctx != nullptr
 extern "C" int swa_d1_network_device(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, uint32_t count,
                                      uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap, uint64_t * total) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network: call swa_d1_index_build first"); }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network: call swa_d1_index_build first"); }
   if (count == 0 || (uint64_t)first + count > ctx->db.n || d_offsets == nullptr || total == nullptr ||
       (d_neighbours == nullptr && cap != 0)) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network: bad range or null buffer");
@@ -2149,7 +2151,7 @@ extern "C" int swa_d1_network_device(swa_ctx * ctx, int no_cluster_breaking, uin
 extern "C" int swa_d1_network_edges_device(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, uint32_t count,
                                            uint64_t * d_edge_list, uint64_t cap, uint64_t * total) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network: call swa_d1_index_build first"); }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network: call swa_d1_index_build first"); }
   if (count == 0 || (uint64_t)first + count > ctx->db.n || d_edge_list == nullptr || total == nullptr) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_edges: bad range or null buffer");
   }
@@ -2249,7 +2251,7 @@ extern "C" int swa_d1_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count,
   SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, (2ull * world + 1) * sizeof(uint32_t), ctx->stream));
   if (count != 0) {
     hipLaunchKernelGGL(k_anchor_route, dim3(grid_for(ctx, (count + kRoutePerThread - 1) / kRoutePerThread, 256, 8)), dim3(256), 0, ctx->stream,
-                       ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, first, count, world, ctx->anchor_a, ctx->anchor_b, ctx->anchor_w / 32u, d_ids, cap,
+                       ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, first, count, world, ctx->ix.anchor_a, ctx->ix.anchor_b, ctx->ix.anchor_w / 32u, d_ids, cap,
                        d_counts);
   }
   SWA_HIP(ctx, hipGetLastError());
@@ -2268,12 +2270,10 @@ extern "C" int swa_d1_index_build_routed(swa_ctx * ctx, const uint32_t * d_ids_p
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   SWA_TRY(ensure_db_lengths(ctx));
   static const uint32_t nothing = 0;                         // (an empty list still marks the build as routed)
-  ctx->route_ids[0] = n_prefix != 0 ? d_ids_prefix : &nothing; ctx->route_m[0] = n_prefix;
-  ctx->route_ids[1] = n_suffix != 0 ? d_ids_suffix : &nothing; ctx->route_m[1] = n_suffix;
-  const int rc = swa_d1_index_build_range(ctx, 0, ctx->db.n, has_duplicates);
-  ctx->route_ids[0] = ctx->route_ids[1] = nullptr;
-  ctx->route_m[0] = ctx->route_m[1] = 0;
-  return rc;
+  RouteLists route;
+  route.ids[0] = n_prefix != 0 ? d_ids_prefix : &nothing; route.m[0] = n_prefix;
+  route.ids[1] = n_suffix != 0 ? d_ids_suffix : &nothing; route.m[1] = n_suffix;
+  return index_build(ctx, 0, ctx->db.n, route, has_duplicates);
 }
 
 // The same exchange with the KEY RECORDS travelling (d1_stream.inc: k_anchor_route_records): 8 bytes per amplicon and index;
@@ -2291,7 +2291,7 @@ extern "C" int swa_d1_route_slice_records(swa_ctx * ctx, uint32_t first, uint32_
   SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, (2ull * world + 1) * sizeof(uint32_t), ctx->stream));
   if (count != 0) {
     hipLaunchKernelGGL(k_anchor_route_records, dim3(grid_for(ctx, (count + 3) / 4, 256, 8)), dim3(256), 0, ctx->stream,
-                       ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, first, count, world, ctx->anchor_a, ctx->anchor_b, ctx->anchor_w / 32u,
+                       ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, first, count, world, ctx->ix.anchor_a, ctx->ix.anchor_b, ctx->ix.anchor_w / 32u,
                        reinterpret_cast<unsigned long long *>(d_records), cap, d_counts);
   }
   SWA_HIP(ctx, hipGetLastError());
@@ -2310,12 +2310,10 @@ extern "C" int swa_d1_index_build_records(swa_ctx * ctx, const uint64_t * d_rec_
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   SWA_TRY(ensure_db_lengths(ctx));
   static const unsigned long long nothing = 0;               // (an empty list still marks the build as routed)
-  ctx->route_rec[0] = n_prefix != 0 ? reinterpret_cast<const unsigned long long *>(d_rec_prefix) : &nothing; ctx->route_m[0] = n_prefix;
-  ctx->route_rec[1] = n_suffix != 0 ? reinterpret_cast<const unsigned long long *>(d_rec_suffix) : &nothing; ctx->route_m[1] = n_suffix;
-  const int rc = swa_d1_index_build_range(ctx, 0, ctx->db.n, has_duplicates);
-  ctx->route_rec[0] = ctx->route_rec[1] = nullptr;
-  ctx->route_m[0] = ctx->route_m[1] = 0;
-  return rc;
+  RouteLists route;
+  route.rec[0] = n_prefix != 0 ? reinterpret_cast<const unsigned long long *>(d_rec_prefix) : &nothing; route.m[0] = n_prefix;
+  route.rec[1] = n_suffix != 0 ? reinterpret_cast<const unsigned long long *>(d_rec_suffix) : &nothing; route.m[1] = n_suffix;
+  return index_build(ctx, 0, ctx->db.n, route, has_duplicates);
 }
 
 extern "C" int swa_d1_set_ownership(swa_ctx * ctx, uint32_t rank, uint32_t world) {
@@ -2324,9 +2322,8 @@ extern "C" int swa_d1_set_ownership(swa_ctx * ctx, uint32_t rank, uint32_t world
   if (rank != ctx->owner_rank || world != ctx->owner_world) {
     ctx->owner_rank = rank;
     ctx->owner_world = world;
-    ctx->csr_ready = false;
-    ctx->anchor_ready = false;                               // the next network call indexes this rank's groups
-    ctx->member_index = false;                               // (the table of the previous owner's oversized groups is not this one's)
+    ctx->ix.owner_changed();                                 // the next network call indexes this rank's groups
+    ctx->res = {};
   }
   return SWA_OK;
 }
@@ -2335,7 +2332,7 @@ extern "C" int swa_d1_network(swa_ctx * ctx, int no_cluster_breaking, uint32_t f
                               uint64_t * offsets, uint32_t * neighbours, uint64_t cap, uint64_t * total) {
   if (ctx == nullptr) { return SWA_E_ARG; }
   if (offsets == nullptr || total == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network: null buffer"); }
-  ctx->csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp are about to hold this call's rows)
+  ctx->res.csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp are about to hold this call's rows)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, (uint64_t(count) + 1) * sizeof(uint64_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, (cap > 0 ? cap : 1) * sizeof(uint32_t)));
   const int rc = swa_d1_network_device(ctx, no_cluster_breaking, first, count,
@@ -2356,26 +2353,26 @@ extern "C" int swa_d1_network(swa_ctx * ctx, int no_cluster_breaking, uint32_t f
 
 extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out_bytes) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  if (!ctx->d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: no index"); }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: no index"); }
   if (what >= 10) {
     // the streaming index as it lies in HBM (tools/check_stream.py validates it on the host): 10 + i: ids in group order of
     // index i, u32[n] · 12 + i: its item buffer, swa_item[regions' end] · 14: the counters, u32[kCounterWords] · 15: the amplicon lines,
     // lines_quads x 16 bytes each · 16: u64[kWidthClasses][kListKinds + 1] first items of the lists (ListRegions) + [.][0] = line quads behind
-    if (!ctx->stream_index) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: no streaming index in place"); }
+    if (!ctx->ix.stream_index) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: no streaming index in place"); }
     const void * from = nullptr;
     size_t need = 0;
     if (what == 10 || what == 11) { from = ctx->d_stream[kSbMembers + (what - 10)].ptr; need = uint64_t(ctx->db.n) * sizeof(uint32_t); }
-    else if (what == 12 || what == 13) { from = ctx->d_aitems[what - 12].ptr; need = ctx->list_regions_items * sizeof(swa_item); }
+    else if (what == 12 || what == 13) { from = ctx->d_aitems[what - 12].ptr; need = ctx->ix.list_regions_items * sizeof(swa_item); }
     else if (what == 14) { from = swa_status(ctx)->counters; need = kCounterWords * sizeof(uint32_t); }
-    else if (what == 15) { from = ctx->d_stream[kSbLines].ptr; need = uint64_t(ctx->db.n) * ctx->lines_quads * 16u; }
+    else if (what == 15) { from = ctx->d_stream[kSbLines].ptr; need = uint64_t(ctx->db.n) * ctx->up.d1.lines_quads * 16u; }
     else if (what == 17 || what == 18) {
       // the bucket starts of the key partition, u64[buckets + 1]: as the index build left them — a network call sorts its
       // links in the same scratch, so they are there between the build and the first network call only
-      if (!ctx->part_starts_valid) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: the bucket starts are there only between the index build and the next network call"); }
+      if (!ctx->ix.part_starts_valid) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: the bucket starts are there only between the index build and the next network call"); }
       const swa_dbuf & b = ctx->d_stream[kSbStart + (what - 17)];
-      need = ((uint64_t)ctx->part_buckets + 1) * sizeof(uint64_t);
-      if (b.ptr == nullptr || (ctx->part_starts_at + ctx->part_buckets + 1) * sizeof(uint64_t) > b.bytes) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_d1_debug_read: bucket starts outside their buffer"); }
-      from = static_cast<const uint64_t *>(b.ptr) + ctx->part_starts_at;
+      need = ((uint64_t)ctx->ix.part_buckets + 1) * sizeof(uint64_t);
+      if (b.ptr == nullptr || (ctx->ix.part_starts_at + ctx->ix.part_buckets + 1) * sizeof(uint64_t) > b.bytes) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_d1_debug_read: bucket starts outside their buffer"); }
+      from = static_cast<const uint64_t *>(b.ptr) + ctx->ix.part_starts_at;
     }
     else if (what == 16) {                                    // (host-side facts: where the lists lie, how wide a line is)
       uint64_t total = 0;
@@ -2383,7 +2380,7 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
       const size_t bytes = sizeof(r) + 2 * sizeof(uint64_t);
       if (out_bytes < bytes) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_debug_read: buffer too small"); }
       memcpy(out, &r, sizeof(r));
-      const uint64_t tail[2] = {total, ctx->lines_quads};
+      const uint64_t tail[2] = {total, ctx->up.d1.lines_quads};
       memcpy(static_cast<char *>(out) + sizeof(r), tail, sizeof(tail));
       return SWA_OK;
     }
@@ -2399,7 +2396,7 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
   size_t bytes = 0;
   switch (what) {
     case 0: src = ctx->d_seqhash.ptr; bytes = uint64_t(ctx->db.n) * sizeof(uint64_t); break;
-    case 1: src = ctx->d_bloom.ptr; bytes = ctx->bloom_words * sizeof(uint64_t); break;
+    case 1: src = ctx->d_bloom.ptr; bytes = ctx->ix.bloom_words * sizeof(uint64_t); break;
     case 2: src = ctx->d_zobrist.ptr; bytes = 4ull * ctx->zobrist_len * sizeof(uint64_t); break;
     default: return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: unknown selector");
   }
@@ -2413,15 +2410,15 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
 // How the work lists of the streaming index in place got their positions: 1 inside k_group_lists, 0 by the two-launch scan
 // (swa_lists_inline); -1 without such an index
 extern "C" int swa_d1_lists_form(const swa_ctx * ctx) {
-  return ctx != nullptr && ctx->stream_index && ctx->anchor_ready ? ctx->lists_form : -1;
+  return ctx != nullptr && ctx->ix.stream_index && ctx->ix.anchor_ready ? ctx->ix.lists_form : -1;
 }
 
 // The key partition of the streaming index in place: the layout of swa_d1_part_plan_for, with the bits the key-overflow
 // retry added in [7]
 extern "C" int swa_d1_part_plan(const swa_ctx * ctx, uint32_t out[8]) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  if (!ctx->d1_ready || !ctx->stream_index) { return SWA_E_ARG; }
-  memcpy(out, ctx->part_plan, sizeof(ctx->part_plan));
+  if (!ctx->ix.d1_ready || !ctx->ix.stream_index) { return SWA_E_ARG; }
+  memcpy(out, ctx->ix.part_plan, sizeof(ctx->ix.part_plan));
   return SWA_OK;
 }
 
@@ -2465,8 +2462,7 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   SWA_TRY(swa_reserve(ctx, ctx->d_queue, task_cap * sizeof(swa_task)));
   SWA_HIP(ctx, hipMemcpyAsync(ctx->d_fpatterns.ptr, fpat.data(), fpat.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_bloomflex.ptr, 0xFF, fsize * sizeof(uint64_t), ctx->stream));
-  ctx->d1_ready = false;                                     // the table now holds the light amplicons of the bands only
-  ctx->full_index = false;
+  ctx->ix.table_repurposed();                                // the table now holds the light amplicons of the bands only
   SWA_TRY(swa_d1_rebuild_table(ctx, static_cast<const uint8_t *>(ctx->d_light.ptr)));
 
   auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
@@ -2500,9 +2496,9 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   a.zobrist = f.zobrist; a.zlen = ctx->zobrist_len;
   a.maxwords = f.maxwords;                                   // a microvariant can be one nt longer
   a.table = static_cast<const swa_slot *>(ctx->d_table.ptr);
-  a.tmask = ctx->table_size - 1;
+  a.tmask = ctx->ix.table_size - 1;
   a.bloom = static_cast<const uint64_t *>(ctx->d_bloom.ptr);
-  a.bmask = ctx->bloom_words - 1;
+  a.bmask = ctx->ix.bloom_words - 1;
   a.patterns = static_cast<const uint64_t *>(ctx->d_patterns.ptr);
   a.tasks = f.tasks;
   a.graft = static_cast<uint32_t *>(ctx->d_graft.ptr);
@@ -2572,7 +2568,7 @@ using FastPlan = swa_fast_plan;
 // uploaded database and the cap (the split's, or the one of SWA_FAST_LONG=pairs: the environment is read at every call),
 // read once for each
 static int ensure_length_classes(swa_ctx * ctx, uint32_t cap) {
-  if (ctx->fast_classes_ready && ctx->fast_classes_cap == cap) { return SWA_OK; }
+  if (ctx->up.d1.fast_classes_ready && ctx->up.d1.fast_classes_cap == cap) { return SWA_OK; }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
   auto * out = reinterpret_cast<uint32_t *>(static_cast<uint64_t *>(ctx->d_fcounters.ptr) + 12);
@@ -2583,9 +2579,9 @@ static int ensure_length_classes(swa_ctx * ctx, uint32_t cap) {
   uint32_t host[4] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->fast_pair_longest = host[0]; ctx->fast_n_long = host[1]; ctx->fast_n_band = host[2];
-  ctx->fast_classes_ready = true;
-  ctx->fast_classes_cap = cap;
+  ctx->up.d1.fast_pair_longest = host[0]; ctx->up.d1.fast_n_long = host[1]; ctx->up.d1.fast_n_band = host[2];
+  ctx->up.d1.fast_classes_ready = true;
+  ctx->up.d1.fast_classes_cap = cap;
   return SWA_OK;
 }
 
@@ -2610,7 +2606,7 @@ static int fast_plan(swa_ctx * ctx, FastPlan & p, uint32_t * long_cap = nullptr)
   const uint32_t cap = pairs ? swa_fast_sites_cap_in_effect(sites_cap) : swa_fast_cap();
   if (long_cap != nullptr) { *long_cap = cap; }
   uint32_t pair_longest = 0;
-  if ((split || pairs) && ctx->db.longest > cap) { SWA_TRY(ensure_length_classes(ctx, cap)); pair_longest = ctx->fast_pair_longest; }
+  if ((split || pairs) && ctx->db.longest > cap) { SWA_TRY(ensure_length_classes(ctx, cap)); pair_longest = ctx->up.d1.fast_pair_longest; }
   p = swa_fast_plan_modes(ctx->db.longest, pair_longest, pairs ? 2 : (split ? 1 : 0), bloom, env_fp != nullptr && env_fp[0] == 'w',
                           env_count != nullptr && strcmp(env_count, "sites") == 0, sites_cap);
   return SWA_OK;
@@ -2637,8 +2633,8 @@ extern "C" int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]) {
   if (longer) { SWA_TRY(ensure_length_classes(ctx, cap)); }
   out[0] = (uint32_t)p.long_mode;
   out[1] = cap;
-  out[2] = longer ? ctx->fast_pair_longest : ctx->db.longest;
-  out[3] = longer ? ctx->fast_n_long : 0u;
+  out[2] = longer ? ctx->up.d1.fast_pair_longest : ctx->db.longest;
+  out[3] = longer ? ctx->up.d1.fast_n_long : 0u;
   return SWA_OK;
 }
 
@@ -2709,7 +2705,7 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
       p.pairs = static_cast<unsigned long long *>(ctx->d_fpairs.ptr); p.pair_counter = fc + 5; p.pair_cap = ctx->fast_pair_cap;
       const dim3 gp(ctx->num_cus * 8);
       p.lines = static_cast<const uint4 *>(ctx->d_stream[kSbLines].ptr);
-      p.line_quads = ctx->lines_quads;
+      p.line_quads = ctx->up.d1.lines_quads;
       if (pair_w == 5) {
         if (type == 0) { hipLaunchKernelGGL((k_fast_pairs_lines<0, 5>), gp, dim3(kThreads), 0, ctx->stream, p); }
         else if (type == 1) { hipLaunchKernelGGL((k_fast_pairs_lines<1, 5>), gp, dim3(kThreads), 0, ctx->stream, p); }
@@ -2780,7 +2776,7 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
                                        uint32_t shard, uint32_t nshards, uint32_t * graft_cand, uint64_t * counters) {
   if (ctx == nullptr) { return SWA_E_ARG; }
   if (nshards == 0 || shard >= nshards) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_shard: bad shard"); }
-  if (!ctx->d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: call swa_d1_index_build first"); }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: call swa_d1_index_build first"); }
   if (is_light == nullptr || graft_cand == nullptr || counters == nullptr || bloom_bits < 2 || bloom_bits > 64) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: bad argument");
   }

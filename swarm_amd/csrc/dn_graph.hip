@@ -793,7 +793,7 @@ uint64_t brute_cap(uint32_t n) {
 }
 
 int window_length(swa_ctx * ctx, uint32_t d, dn_plan * out) {
-  if (ctx->dn_shortest == 0) {
+  if (ctx->up.dn_shortest == 0) {
     SWA_TRY(swa_reserve(ctx, ctx->d_frole, (uint64_t)kShortSorted * sizeof(uint32_t)));
     auto * slot = static_cast<uint32_t *>(ctx->d_frole.ptr);
     SWA_HIP(ctx, hipMemsetAsync(slot, 0, SWA_DN_HIST_LEN * sizeof(uint32_t), ctx->stream));
@@ -803,16 +803,16 @@ int window_length(swa_ctx * ctx, uint32_t d, dn_plan * out) {
     SWA_HIP(ctx, hipMemcpyAsync(got, slot, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint32_t mn = got[SWA_DN_HIST_LEN];
-    for (uint32_t L = SWA_DN_HIST_LEN; L-- > 0;) { ctx->dn_len_hist[L] = got[L]; if (got[L] != 0u) { mn = L; } }
-    ctx->dn_shortest_rest = got[SWA_DN_HIST_LEN];
-    ctx->dn_shortest = mn;
+    for (uint32_t L = SWA_DN_HIST_LEN; L-- > 0;) { ctx->up.dn_len_hist[L] = got[L]; if (got[L] != 0u) { mn = L; } }
+    ctx->up.dn_shortest_rest = got[SWA_DN_HIST_LEN];
+    ctx->up.dn_shortest = mn;
   }
   *out = dn_plan();
   if (d > (uint32_t)kMaxD) { return SWA_OK; }
-  const uint32_t * hist = ctx->dn_len_hist;
+  const uint32_t * hist = ctx->up.dn_len_hist;
   const uint32_t T = 16u * (d + 1u), top = T + d;              // (d <= 16: top <= SWA_DN_HIST_LEN)
   out->short_below = T;
-  uint32_t shortest_long = ctx->dn_shortest_rest;
+  uint32_t shortest_long = ctx->up.dn_shortest_rest;
   for (uint32_t L = SWA_DN_HIST_LEN; L-- > T;) { if (hist[L] != 0u) { shortest_long = L; } }
   // (no long sequence at all: the windows find nothing whatever their length)
   out->wlen = shortest_long >= 32u * (d + 1u) && shortest_long != 0xFFFFFFFFu ? 32u : 16u;
@@ -845,7 +845,7 @@ extern "C" int swa_dn_graph_supported(swa_ctx * ctx) {
 // the search itself: the sorted (query << 32 | target, diff) list of this context's share of the graph, left in HBM
 int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->qgram_ready || !ctx->search_ready) {
+  if (!ctx->up.qgram_ready || !ctx->search_ready) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_dn_graph: call swa_qgram_build and swa_search_begin first");
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
@@ -856,7 +856,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
   const uint32_t wlen = plan.wlen;
   if (wlen == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_dn_graph: a sequence is too short for d + 1 windows (use the scan)"); }
 
-  if (!ctx->dn_graph_ready || ctx->dn_graph_ncb != (no_cluster_breaking != 0)) {
+  if (!ctx->up.dn_graph_ready || ctx->up.dn_graph_ncb != (no_cluster_breaking != 0)) {
     const uint32_t ns = 2u * d + 1u;
     uint64_t asize = 64;
     while (asize < 2ull * n * ns) { asize <<= 1; }
@@ -889,7 +889,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       auto * words = static_cast<uint32_t *>(ctx->d_frole.ptr);
       uint32_t start[SWA_DN_HIST_LEN + 1];
       start[0] = 0;
-      for (uint32_t L = 0; L < top; ++L) { start[L + 1] = start[L] + ctx->dn_len_hist[L]; }
+      for (uint32_t L = 0; L < top; ++L) { start[L + 1] = start[L] + ctx->up.dn_len_hist[L]; }
       SWA_HIP(ctx, hipMemcpyAsync(words + kShortStart, start, (top + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
       SWA_HIP(ctx, hipMemsetAsync(words + kShortCursor, 0, top * sizeof(uint32_t), ctx->stream));
       hipLaunchKernelGGL(k_dg_short_sort, dim3(join_grid(ctx, n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, n, top, words + kShortStart,
@@ -1018,8 +1018,8 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
     ctx->dn_edges = nedges;
     ctx->dn_work = npairs != 0 ? ctx->dn_aligned : 0;
     ctx->dn_launches = launches + 4;
-    ctx->dn_graph_ready = true;
-    ctx->dn_graph_ncb = no_cluster_breaking != 0;
+    ctx->up.dn_graph_ready = true;
+    ctx->up.dn_graph_ncb = no_cluster_breaking != 0;
   }
   return SWA_OK;
 }
@@ -1030,7 +1030,7 @@ int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const ui
   const uint32_t n = ctx->db.n;
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   *total = nedges;
-  ctx->csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold this graph)
+  ctx->res.csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold this graph)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
                      static_cast<uint64_t *>(ctx->d_offsets_tmp.ptr));
@@ -1075,7 +1075,7 @@ extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uin
   const uint64_t nedges = ctx->dn_edges;
   const unsigned long long * sorted = ctx->dn_work != 0 ? static_cast<const unsigned long long *>(ctx->d_dn_keys.ptr) + ctx->dn_work : nullptr;
   const uint32_t * svals = ctx->dn_work != 0 ? static_cast<const uint32_t *>(ctx->d_dn_vals.ptr) + ctx->dn_work : nullptr;
-  ctx->csr_ready = false;
+  ctx->res.csr_ready = false;
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, (nedges + 1) * (sizeof(uint32_t) + 1)));
   hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
@@ -1086,9 +1086,9 @@ extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uin
                        reinterpret_cast<uint8_t *>(nb32 + nedges));
   }
   SWA_HIP(ctx, hipGetLastError());
-  ctx->csr_ready = true;
-  ctx->csr_total = nedges;
-  ctx->csr_has_diffs = true;
+  ctx->res.csr_ready = true;
+  ctx->res.csr_total = nedges;
+  ctx->res.csr_has_diffs = true;
   *total = nedges;
   return SWA_OK;
 }
@@ -1097,7 +1097,7 @@ extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uin
 // (0 for seeds); n bytes on the host.  radius(v) = radius(parent) + pdiff[v] (src/algo.cc:560-574).
 extern "C" int swa_dn_parent_diffs(swa_ctx * ctx, uint8_t * pdiff) {
   if (ctx == nullptr || pdiff == nullptr) { return SWA_E_ARG; }
-  if (!ctx->csr_ready || !ctx->csr_has_diffs || ctx->d_cluster.ptr == nullptr) {
+  if (!ctx->res.csr_ready || !ctx->res.csr_has_diffs || ctx->d_cluster.ptr == nullptr) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_dn_parent_diffs: call swa_dn_graph_resident and swa_d1_cluster_device first");
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
@@ -1107,7 +1107,7 @@ extern "C" int swa_dn_parent_diffs(swa_ctx * ctx, uint8_t * pdiff) {
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_diffs, (uint64_t)n + 16));
   auto * out = static_cast<uint8_t *>(ctx->d_scan_diffs.ptr);
   hipLaunchKernelGGL(k_dg_parent_diffs, dim3(join_grid(ctx, n)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr),
-                     nb32, reinterpret_cast<const uint8_t *>(nb32 + ctx->csr_total), parent, n, out);
+                     nb32, reinterpret_cast<const uint8_t *>(nb32 + ctx->res.csr_total), parent, n, out);
   SWA_HIP(ctx, hipGetLastError());
   SWA_HIP(ctx, hipMemcpyAsync(pdiff, out, n, hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1124,7 +1124,7 @@ extern "C" int swa_dn_set_ownership(swa_ctx * ctx, uint32_t rank, uint32_t world
   if (world == 0 || rank >= world) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_dn_set_ownership: bad rank / world"); }
   if (rank != ctx->dn_owner_rank || world != ctx->dn_owner_world) {
     ctx->dn_owner_rank = rank; ctx->dn_owner_world = world;
-    ctx->dn_graph_ready = false;
+    ctx->up.dn_graph_ready = false;
   }
   return SWA_OK;
 }

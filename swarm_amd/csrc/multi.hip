@@ -330,7 +330,7 @@ extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint
   if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
   auto * keys_in = static_cast<unsigned long long *>(m->gathered.ptr);
   auto stage = [&]() -> int {
-    c0->csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold the gathered network)
+    c0->res.csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold the gathered network)
     SWA_TRY(swa_reserve(c0, c0->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
     SWA_TRY(swa_reserve(c0, c0->d_nb_tmp, (all + 1) * sizeof(uint32_t)));
     std::vector<uint64_t> starts((size_t)world, 0);
@@ -363,7 +363,7 @@ extern "C" int swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, 
   std::vector<std::vector<uint64_t>> cnt((size_t)world, std::vector<uint64_t>(8, 0));
   int rc = on_all(m, [&](int r) {
     swa_ctx * c = m->ctx[(size_t)r];
-    if (!c->d1_ready) { int dup = 0; SWA_TRY(swa_d1_index_build(c, &dup)); }
+    if (!c->ix.d1_ready) { int dup = 0; SWA_TRY(swa_d1_index_build(c, &dup)); }
     uint32_t * host = graft_cand;
     if (r != 0) { scratch[(size_t)r].resize(n); host = scratch[(size_t)r].data(); }   // (the per-rank host copy is not the result)
     return swa_d1_fastidious_shard(c, is_light, light_nt, bloom_bits, (uint32_t)r, (uint32_t)world, host, cnt[(size_t)r].data());

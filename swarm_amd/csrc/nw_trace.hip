@@ -440,10 +440,10 @@ struct Results {                                               // of a slice
 
 // lengths of the resident database on the host: the batch sorts its pairs into tiers and sizes LDS by them
 int host_seqlen(swa_ctx * ctx) {
-  if (ctx->nw_seqlen.size() == ctx->db.n) { return SWA_OK; }
-  ctx->nw_seqlen.resize(ctx->db.n);
+  if (ctx->up.nw_seqlen.size() == ctx->db.n) { return SWA_OK; }
+  ctx->up.nw_seqlen.resize(ctx->db.n);
   if (ctx->db.n == 0) { return SWA_OK; }
-  SWA_HIP(ctx, hipMemcpyAsync(ctx->nw_seqlen.data(), ctx->db.seqlen, (size_t)ctx->db.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(ctx->up.nw_seqlen.data(), ctx->db.seqlen, (size_t)ctx->db.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SWA_OK;
 }
@@ -640,7 +640,7 @@ extern "C" int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, 
   SWA_TRY(host_seqlen(ctx));
   for (auto & v : ctx->nw_totals) { v = 0; }
   ctx->nw_text_full = 0;
-  const uint32_t * len = ctx->nw_seqlen.data();
+  const uint32_t * len = ctx->up.nw_seqlen.data();
   const Scoring sc{mismatch, gapopen, gapextend};
   uint64_t total = 0;
   for (uint64_t base = 0; base < npairs; base += kSlice) {

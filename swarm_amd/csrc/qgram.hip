@@ -78,14 +78,14 @@ extern "C" int swa_qgram_build(swa_ctx * ctx) {
                      ctx->db.seqlen, n, static_cast<uint32_t *>(ctx->d_qgrams.ptr));
   SWA_HIP(ctx, hipGetLastError());
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->qgram_ready = true;
+  ctx->up.qgram_ready = true;
   return SWA_OK;
 }
 
 extern "C" int swa_qgram_diff(swa_ctx * ctx, uint64_t seed, uint64_t listlen, const uint64_t * amplist,
                               uint64_t * difflist) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->qgram_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_qgram_diff: call swa_qgram_build first"); }
+  if (!ctx->up.qgram_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_qgram_diff: call swa_qgram_build first"); }
   if (listlen == 0) { return SWA_OK; }
   if (amplist == nullptr || difflist == nullptr || seed >= ctx->db.n) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_qgram_diff: bad argument");
@@ -108,7 +108,7 @@ extern "C" int swa_qgram_diff(swa_ctx * ctx, uint64_t seed, uint64_t listlen, co
 
 extern "C" int swa_qgram_debug_read(swa_ctx * ctx, uint8_t * out, size_t out_bytes) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  if (!ctx->qgram_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_qgram_debug_read: no signatures"); }
+  if (!ctx->up.qgram_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_qgram_debug_read: no signatures"); }
   const size_t bytes = size_t(ctx->db.n) * 128u;
   if (out_bytes < bytes) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_qgram_debug_read: buffer too small"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));

@@ -241,7 +241,7 @@ __global__ void k_scan_stage(const uint32_t * __restrict__ pinned, uint32_t * __
 
 extern "C" int swa_scan_begin(swa_ctx * ctx) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->qgram_ready || !ctx->search_ready) {
+  if (!ctx->up.qgram_ready || !ctx->search_ready) {
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_scan_begin: call swa_qgram_build and swa_search_begin first");
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
@@ -257,7 +257,7 @@ extern "C" int swa_scan_begin(swa_ctx * ctx) {
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->scan_launches = 0;                                  // (the totals count from here: swarm_amd.h)
   ctx->scan_compare_discount = 0;
-  ctx->scan_ready = true;
+  ctx->up.scan_ready = true;
   return SWA_OK;
 }
 
@@ -268,7 +268,7 @@ extern "C" int swa_scan_batch(swa_ctx * ctx, uint32_t nseeds, const uint32_t * s
                               uint32_t * hit_seedidx, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap,
                               uint32_t * nhits) {
   if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->scan_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_scan_batch: call swa_scan_begin first"); }
+  if (!ctx->up.scan_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_scan_batch: call swa_scan_begin first"); }
   if (nhits == nullptr || seeds == nullptr || radii == nullptr || nseeds == 0 || nseeds > 65535 ||
       (first_generation != 0 && nseeds != 1) ||
       (cap != 0 && (hit_ids == nullptr || hit_diffs == nullptr || hit_seedidx == nullptr))) {
@@ -445,7 +445,7 @@ extern "C" int swa_scan_step(swa_ctx * ctx, uint32_t seed, uint32_t lowest_unswa
 
 extern "C" int swa_scan_totals(swa_ctx * ctx, uint64_t * out3) {
   if (ctx == nullptr || out3 == nullptr) { return SWA_E_ARG; }
-  if (!ctx->scan_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_scan_totals: no scan state"); }
+  if (!ctx->up.scan_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_scan_totals: no scan state"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   uint64_t t[4] = {};
   SWA_HIP(ctx, hipMemcpyAsync(t, static_cast<uint32_t *>(ctx->d_scan_counters.ptr) + 4, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));

@@ -69,7 +69,7 @@ constexpr uint32_t kFlagOverMass = 5;      // ... and how many members they have
 constexpr uint32_t kFlagShortest = 6;      // 0xFFFFFFFF - the shortest sequence
 constexpr uint32_t kFlagsD1 = 7;           // (so many of them)
 // ... the dereplication's count of amplicons left for the next round, ON THE WORD OF kFlagOversized: swa_derep drops the
-// d = 1 index before its first round (d1_ready = anchor_ready = false), so no build or step reads the flag it overwrites
+// d = 1 index before its first round (swa_d1_index::table_repurposed), so no build or step reads the flag it overwrites
 constexpr uint32_t kFlagDerepLeft = kFlagOversized;
 // ... and the grouped join (group_join.inc: JoinTable::flags = flags + kFlagJoin), indexed from there:
 constexpr uint32_t kFlagJoin = 8;
@@ -114,6 +114,95 @@ static_assert(kCounterWords * sizeof(uint32_t) == sizeof(swa_status_block::count
 // dn_graph.hip keeps a count per sequence length below this: 16 (d + 1) + d for d <= 16, the lengths a short sequence can pair with
 #define SWA_DN_HIST_LEN 288u
 
+// ---- the context's state, by lifetime ----------------------------------------------------------
+// A member that is a fact OF something lies in that something's group, default-initialised to "nothing there": ending a
+// lifetime is `group = {}`.  What lives as long as the context (buffers, capacities, the owner ...): in swa_ctx.
+
+// facts of the uploaded database (ended by swa_db_upload* / swa_db_attach)
+struct swa_db_facts {
+  // ... those the d = 1 step derives from the packed database: a guard retry (d1.hip: network_run_guarded) makes them again
+  struct d1_facts {
+    bool rank_ready = false;       // d_arank holds the abundance ranks of this database
+    bool db_unordered = false;     // ... which is not in abundance order (the anchored passes are then not used)
+    bool props_ready = false;      // db_shortest / class_pop below
+    uint32_t db_shortest = 0;      // shortest sequence
+    uint32_t class_pop[8] = {};    // sequences per width class (d1_anchor.inc: width_class; [kTooLong]: beyond the pair kernels)
+    bool windows_ready = false;    // the anchor windows of this database are known (choose_anchor_windows + the safety net):
+    uint32_t windows_chosen = 0;   // anchor_a = anchor_b = this
+    uint32_t windows_w = 32;       // ... and anchor_w = this
+    bool lines_ready = false;      // d_lines holds this database's amplicon lines (made once per upload), lines_w words each
+    uint32_t lines_quads = 0;      // ... of this many 16-byte quads each (4, 8 or 16)
+    // length classes of the database against the pair route's cap (k_fast_length_classes; read once per upload, and only
+    // where the longest sequence exceeds the cap: by the pass under SWA_FAST_LONG=split or =pairs, by swa_d1_fastidious_split always): the longest sequence <= cap (0: none), amplicons > cap, amplicons >= cap - 1
+    bool fast_classes_ready = false;
+    uint32_t fast_classes_cap = 0;  // ... the cap they were read against (SWA_FAST_LONG=pairs has its own)
+    uint32_t fast_pair_longest = 0, fast_n_long = 0, fast_n_band = 0;
+    bool guard_keys_done = false;  // the key records of this upload have had their second opinion (k_guard_db / k_guard_records)
+    bool guard_keys_pending = false;   // ... its sums, guard[kGuardKeys ..), wait for the next guard_check
+    uint32_t stream_extra_bits = 0;   // finer partition after a bucket held more distinct keys than the group kernel's table
+  } d1;
+  // the uclust alignments (nw_trace.hip): the database's lengths on the host (filled by the first swa_nw_batch after an upload)
+  std::vector<uint32_t> nw_seqlen;
+  bool qgram_ready = false, scan_ready = false;
+  // d >= 2 in bulk (dn_graph.hip): the graph of all pairs within d differences, kept sorted on the device
+  bool dn_graph_ready = false, dn_graph_ncb = false;
+  uint32_t dn_shortest = 0;      // shortest sequence of the database (0 = not measured yet)
+  // ... with it: how many sequences have each length below SWA_DN_HIST_LEN, and the shortest of the others (none: ~0).
+  // What window_length() decides everything from: the shortest LONG sequence, the short ones and their candidates B.
+  uint32_t dn_len_hist[SWA_DN_HIST_LEN] = {};
+  uint32_t dn_shortest_rest = 0xFFFFFFFFu;
+};
+
+// the d = 1 index in place (ended when an index build starts: d1.hip, index_build)
+struct swa_d1_index {
+  bool d1_ready = false;
+  uint64_t table_size = 0;       // slots, power of two
+  uint64_t bloom_words = 0;      // u64 words in the amplicon Bloom
+  // anchored d=1 index (d1_anchor.inc, d1_stream.inc): [0] prefix groups, [1] suffix groups
+  bool anchor_usable = false;    // decided by swa_d1_index_build: lengths fit, db order holds, not switched off
+  bool anchor_ready = false;     // the streaming index below exists (for the owner in owner_rank / owner_world)
+  bool full_index = false;       // d_seqhash / d_aux cover ALL amplicons and d_table / d_bloom are built (ensure_full_index)
+  uint32_t anchor_a = 0, anchor_b = 0;   // anchor windows moved inwards by this many nt ("window mode", chosen at index build)
+  uint32_t anchor_w = 32;        // width of the anchor windows in nt: 32, 64 or 128 (wider: fewer pairs per group; needs 2 w + 1 nt)
+  bool head_clear_pending = false;   // index_build has left the clear of the status block's head to the streaming build's own clear
+  bool guard_index = false;      // guard[0, kGuardCall) of the status block describe the index in place (made by the streaming build since the last clear)
+  // streaming index build / CSR assembly (d1_stream.inc)
+  uint32_t list_counts[2 * 4 * 8] = {};   // items per work list of the index in place ([index][width class][8]: the status block's counters + kCounterBase)
+  bool list_counts_ready = false;
+  uint64_t list_regions_items = 0;   // entries of an index's item buffer (d1.hip: list_regions)
+  bool stream_index = false;     // the anchor indexes in place were made by the streaming build: members = ids in d_members
+  // the key partition of the index in place, as swa_d1_part_plan reports it, and where its bucket starts lie (u64 entries
+  // into d_stream[kSbStart + i]; the link partition of a network call reuses those buffers: part_starts_valid falls then)
+  uint32_t part_plan[8] = {};
+  int lists_form = -1;           // the work lists of the index in place: 1 positions inside k_group_lists, 0 the two-launch scan (swa_d1_lists_form)
+  uint64_t part_starts_at = 0;
+  uint32_t part_buckets = 0;
+  bool part_starts_valid = false;
+  // member index: hash table + Bloom of the members of oversized groups only (what the plain kernel probes for them)
+  bool member_index = false, only_oversized = false;
+  uint32_t over_mass = 0;
+  uint64_t mtable_size = 0, mbloom_words = 0;
+  uint32_t index_first = 0, index_count = 0;   // the range of the last index build (network_run_guarded repeats it)
+  bool index_routed = false;
+
+  // A partial end: the owner changed (swa_d1_set_ownership).  The database-wide table, if built, serves any owner (d1_ready,
+  // full_index stay); the streaming index and the member table were the previous owner's: the next network call makes this one's
+  void owner_changed() { anchor_ready = false; member_index = false; }
+  // ... and d_table / d_bloom were given another content (swa_derep; the Bloom route of --fastidious, which goes on to
+  // fill the table it has the size of): nothing is served until the next build, which ends the rest
+  void table_repurposed() { d1_ready = false; full_index = false; anchor_ready = false; }
+};
+
+// the network resident in d_offsets_tmp / d_nb_tmp and its clustering (cluster_gpu.hip); ended with the index it was made from
+struct swa_resident {
+  bool csr_ready = false;
+  bool csr_has_diffs = false;                 // the resident network is a d >= 2 graph: one byte of differences per link behind the neighbours
+  uint64_t csr_total = 0;
+  bool cluster_ready = false;                  // swa_d1_cluster_device's arrays lie in d_cluster (swa_d1_cluster_fetch)
+  uint32_t cluster_maxgen = 0;
+  uint32_t cluster_effort[3] = {};             // of the last swa_d1_cluster_device call: label sweeps launched, restarts of their numbering, level batches
+};
+
 struct swa_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -128,16 +217,17 @@ struct swa_ctx {
   bool ev_ready = false;
   bool ev_used[16] = {};
 
+  swa_db_facts up;               // what is known of the uploaded database
+  swa_d1_index ix;               // the d = 1 index in place
+  swa_resident res;              // the resident network and its clustering
+
   // database (device pointers)
   swa_db_view db{};
   bool db_owned = false;
   swa_dbuf d_seqs, d_seq_off, d_seqlen, d_abund;
 
   // d=1 index
-  bool d1_ready = false;
-  uint64_t table_size = 0;       // slots, power of two
-  uint64_t bloom_words = 0;      // u64 words in the amplicon Bloom
-  uint32_t zobrist_len = 0;      // positions in the Zobrist table (longest + 2)
+  uint32_t zobrist_len = 0;      // positions in the Zobrist table (longest + 2; set by whoever hashes: prepare_hashing)
   uint32_t zobrist_resident = 0; // length of the table currently in d_zobrist (0 = none)
   bool patterns_resident = false;
   swa_dbuf d_zobrist, d_seqhash, d_table, d_bloom, d_patterns;
@@ -145,30 +235,7 @@ struct swa_ctx {
   swa_status_block * h_status = nullptr;   // ... and its mirror in pinned host memory: where the host looks at what it copied
   swa_dbuf d_edges;              // u64 edge list (src << 32 | dst)
   swa_dbuf d_counts, d_cursor, d_scan_tmp, d_offsets_tmp, d_nb_tmp;
-  // anchored d=1 index (d1_anchor.inc, d1_stream.inc): [0] prefix groups, [1] suffix groups
-  bool anchor_usable = false;    // decided by swa_d1_index_build: lengths fit, db order holds, not switched off
-  bool anchor_ready = false;     // the streaming index below exists (for the owner in owner_rank / owner_world)
-  bool full_index = false;       // d_seqhash / d_aux cover ALL amplicons and d_table / d_bloom are built (ensure_full_index)
-  // routed build (swa_d1_index_build_routed): the members of this rank's groups arrive as id lists; and what is a fact
-  // of the uploaded database rather than of one index build, kept until the next upload
-  const uint32_t * route_ids[2] = {nullptr, nullptr};
-  const unsigned long long * route_rec[2] = {nullptr, nullptr};   // routed by key records (swa_d1_index_build_records): no k_keys pass
-  uint32_t route_m[2] = {0, 0};
-  bool rank_ready = false;       // d_arank holds the abundance ranks of this database
-  bool db_unordered = false;     // ... which is not in abundance order (the anchored passes are then not used)
-  bool props_ready = false;      // db_shortest / class_pop below
-  uint32_t db_shortest = 0;      // shortest sequence
-  uint32_t class_pop[8] = {};    // sequences per width class (d1_anchor.inc: width_class; [kTooLong]: beyond the pair kernels)
-  bool windows_ready = false;    // the anchor windows of this database are known (choose_anchor_windows + the safety net):
-  uint32_t windows_chosen = 0;   // anchor_a = anchor_b = this
   uint32_t owner_rank = 0, owner_world = 1;   // swa_d1_set_ownership: this context serves the anchor groups of one rank
-  uint32_t anchor_a = 0, anchor_b = 0;   // anchor windows moved inwards by this many nt ("window mode", chosen at index build)
-  uint32_t anchor_w = 32;        // width of the anchor windows in nt: 32, 64 or 128 (wider: fewer pairs per group; needs 2 w + 1 nt)
-  uint32_t windows_w = 32;       // ... as chosen for this database (with windows_chosen)
-  bool head_clear_pending = false;   // swa_d1_index_build_range has left the clear of the status block's head to the streaming build's own clear
-  bool guard_index = false;      // guard[0, kGuardCall) of the status block describe the index in place (made by the streaming build since the last clear)
-  bool guard_keys_done = false;  // the key records of this upload have had their second opinion (k_guard_db / k_guard_records)
-  bool guard_keys_pending = false;   // ... its sums, guard[kGuardKeys ..), wait for the next guard_check
   // d_akeys[0] / d_acounts[0]: scratch of the window sample; d_aitems: the work lists of the two indexes
   swa_dbuf d_aux, d_akeys[1], d_acounts[1], d_aitems[2];
   swa_dbuf d_afallback, d_arank, d_rank_tmp;
@@ -177,7 +244,6 @@ struct swa_ctx {
   uint64_t seg_cap = 0;          // entries per segment
 
   // q-gram / alignment state
-  bool qgram_ready = false;
   swa_dbuf d_qgrams, d_list_a, d_list_b, d_list_c, d_list_d;
   uint64_t pen_mismatch = 18, pen_gapopen = 24, pen_gapextend = 13, resolution = 1;
   bool search_ready = false;
@@ -187,7 +253,6 @@ struct swa_ctx {
   swa_dbuf d_wfa;
 
   // fused d >= 2 scan state (scan.hip)
-  bool scan_ready = false;
   swa_dbuf d_scan_est, d_scan_swarmed, d_scan_targets, d_scan_diffs, d_scan_hits, d_scan_counters;
   swa_dbuf d_scan_cand;          // candidate list of the current swarm (scan.hip)
   swa_dbuf d_scan_seeds;         // seeds + limits of the current batch
@@ -208,67 +273,26 @@ struct swa_ctx {
   swa_dbuf d_frole, d_fkeys, d_fcnt, d_foff, d_fslot, d_fmembers, d_fitems, d_fpairs;
   uint64_t fast_pair_cap = 0;
   uint64_t fast_totals[4] = {};  // of the last pass: pairs found, light / heavy amplicons of the Bloom route's bands, attempts of the pair list
-  // length classes of the database against the pair route's cap (k_fast_length_classes; read once per upload, and only
-  // where the longest sequence exceeds the cap: by the pass under SWA_FAST_LONG=split or =pairs, by swa_d1_fastidious_split always): the longest sequence <= cap (0: none), amplicons > cap, amplicons >= cap - 1
-  bool fast_classes_ready = false;
-  uint32_t fast_classes_cap = 0;  // ... the cap they were read against (SWA_FAST_LONG=pairs has its own)
-  uint32_t fast_pair_longest = 0, fast_n_long = 0, fast_n_band = 0;
 
-  // d >= 2 in bulk (dn_graph.hip): the graph of all pairs within d differences, kept sorted on the device
-  uint32_t dn_shortest = 0;      // shortest sequence of the database (0 = not measured yet)
-  // ... with it: how many sequences have each length below SWA_DN_HIST_LEN, and the shortest of the others (none: ~0).
-  // What window_length() decides everything from: the shortest LONG sequence, the short ones and their candidates B.
-  uint32_t dn_len_hist[SWA_DN_HIST_LEN] = {};
-  uint32_t dn_shortest_rest = 0xFFFFFFFFu;
-  bool dn_graph_ready = false, dn_graph_ncb = false;
+  // d >= 2 in bulk (dn_graph.hip)
   uint64_t dn_pair_cap = 0, dn_comparisons = 0, dn_aligned = 0, dn_launches = 0, dn_edges = 0, dn_work = 0;
   swa_dbuf d_dn_keys, d_dn_vals;
   uint32_t dn_owner_rank = 0, dn_owner_world = 1;   // swa_dn_set_ownership: this context finds the pairs of the window groups (and short sequences) it owns
 
-  // streaming index build / CSR assembly (d1_stream.inc)
-  bool lines_ready = false;      // d_lines holds this database's amplicon lines (made once per upload), lines_w words each
-  uint32_t lines_quads = 0;      // ... of this many 16-byte quads each (4, 8 or 16)
-  uint32_t list_counts[2 * 4 * 8] = {};   // items per work list of the index in place ([index][width class][8]: the status block's counters + kCounterBase)
-  bool list_counts_ready = false;
-  uint64_t list_regions_items = 0;   // entries of an index's item buffer (d1.hip: list_regions)
-  bool stream_index = false;     // the anchor indexes in place were made by the streaming build: members = ids in d_members
-  uint32_t stream_extra_bits = 0;   // finer partition after a bucket held more distinct keys than the group kernel's table
-  // the key partition of the index in place, as swa_d1_part_plan reports it, and where its bucket starts lie (u64 entries
-  // into d_stream[kSbStart + i]; the link partition of a network call reuses those buffers: part_starts_valid falls then)
-  uint32_t part_plan[8] = {};
-  int lists_form = -1;           // the work lists of the index in place: 1 positions inside k_group_lists, 0 the two-launch scan (swa_d1_lists_form)
-  uint64_t part_starts_at = 0;
-  uint32_t part_buckets = 0;
-  bool part_starts_valid = false;
-  swa_dbuf d_stream[30];         // indexed by kSb* (below)
-  // member index: hash table + Bloom of the members of oversized groups only (what the plain kernel probes for them)
-  bool member_index = false, only_oversized = false;
-  uint32_t over_mass = 0;
-  uint64_t mtable_size = 0, mbloom_words = 0;
+  swa_dbuf d_stream[30];         // streaming index build / CSR assembly (d1_stream.inc): indexed by kSb* (below)
 
-  // the d = 1 network kept in d_offsets_tmp / d_nb_tmp (swa_d1_network_resident) and its clustering (cluster_gpu.hip)
-  bool csr_ready = false;
-  uint32_t index_first = 0, index_count = 0;   // the range of the last index build (network_run_guarded repeats it)
-  bool index_routed = false;
   uint32_t guard_retries = 0;                  // steps repeated after the guard found counts that did not balance
   swa_dbuf d_words_stage;                      // swa_db_stage_words: the reader's word pools, file order
   const void * staged_first = nullptr; uint64_t staged_words = 0;
-  bool cluster_ready = false;                  // swa_d1_cluster_device's arrays lie in d_cluster (swa_d1_cluster_fetch)
-  uint32_t cluster_maxgen = 0;
-  uint32_t cluster_effort[3] = {};             // of the last swa_d1_cluster_device call: label sweeps launched, restarts of their numbering, level batches
   int pair_blocks[4] = {};                      // workgroups of k_d1_group_pairs a CU holds, per width class (0: not asked yet)
   bool g1_lds_opt_in = false;                  // k_group1's dynamic-LDS attribute has been set on this context's device
   bool part_lds_opt_in = false;                // ... and the wide-tile form of k_part_scatter
   uint32_t pair_lds_opt_in = 0;    // ... and the W = 15 / 21 forms of k_d1_group_pairs (pass + 2 (W = 21) + 4 (NW = 2) + 8 (NW = 4))
-  bool csr_has_diffs = false;                 // the resident network is a d >= 2 graph: one byte of differences per link behind the neighbours
-  uint64_t csr_total = 0;
   swa_dbuf d_cluster, d_cluster_ctl;
 
-  // the uclust alignments (nw_trace.hip): the database's lengths on the host (filled by the first swa_nw_batch after an
-  // upload), the pairs per tier of the last batch (three LDS tiers, four wide tiers, host), how many of them the widest
-  // tier certified but found the text buffer full, and the device buffers of one slice (d_nw_bits: the wide tiers'
+  // the uclust alignments (nw_trace.hip): the pairs per tier of the last batch (three LDS tiers, four wide tiers, host), how
+  // many of them the widest tier certified but found the text buffer full, and the device buffers of one slice (d_nw_bits: the wide tiers'
   // direction bits, one slot per wave; reserved on every run, 256 slots at least for what the LDS tiers may pass down)
-  std::vector<uint32_t> nw_seqlen;
   uint64_t nw_totals[8] = {};
   uint64_t nw_text_full = 0;
   swa_dbuf d_nw_ids, d_nw_lists, d_nw_res, d_nw_text, d_nw_gather, d_nw_bits;
