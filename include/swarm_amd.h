@@ -406,6 +406,50 @@ uint32_t swa_d1_fastidious_sites_cap(uint32_t sites_cap);
    [3] attempts the pair list took (2 or more: it was regrown; 0: the pair route did not run). */
 int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]);
 
+/* ---- B2 on the clustering in place: swarm sums, light flags, candidates and grafting without the host ----------------
+   The reference does its fastidious bookkeeping on the host, around the two passes above; a caller that binds seam B2 and
+   clusters with swa_d1_cluster_device has everything that bookkeeping reads in HBM already, and these calls do it there.
+   All of them work on the clustering swa_d1_cluster_device left in place and fail with SWA_E_ARG and a message without one.
+   Integer sums, minima and maxima only: every result is independent of scheduling.
+   What ends what: an upload, index build, network or clustering call ends all of it (as for swa_d1_cluster_fetch).
+   swa_d1_fastidious, _shard and _resident leave the clustering and the sums in place (they work in buffers of their own)
+   and replace the candidates; swa_derep ends the candidates.
+
+   swa_d1_swarm_sums_device (src/algod1.cc:1232-1257, where the reference adds them up while it clusters): per swarm, in
+   swarm order, the sum of the members' abundances, of their lengths, the members of abundance 1 and the deepest
+   generation — one pass over the member order on the device.  `nswarms` = entries of the caller's arrays (SWA_E_CAPACITY
+   when that is fewer than there are swarms); any output may be NULL: the sums stay in HBM for the calls below, which make
+   them themselves when nobody has.  Sizes are not among them: they follow from swarm_begin.  After swa_d1_graft_device
+   the call returns the sums as the grafts grew them.
+   swa_d1_light_flags_device (src/algod1.cc:1291-1328, = swa_d1_light_flags of the host header): a swarm is light when its
+   mass is below `boundary`.  is_light[n] (may be NULL) != 0 for the amplicons of light swarms; stats5 = {light swarms,
+   amplicons in them, their nucleotides, heavy swarms, amplicons in them}.  The flags stay in HBM in the form the second
+   pass reads; only the five numbers (and is_light, when asked for) are read back.  The masses are the sums in HBM as
+   they are: call it before swa_d1_graft_device, as the reference does.
+   swa_d1_fastidious_resident (src/algod1.cc:1337-1467, = swa_d1_fastidious): the second pass with its roles taken from
+   the flags of the last swa_d1_light_flags_device call instead of a host array.  graft_cand may be NULL: the
+   candidates are then not downloaded.  counters as swa_d1_fastidious.  Needs the d = 1 index (swa_d1_index_build).
+   swa_d1_graft_device (attach_candidates and attach, src/algod1.cc:214-336): the reference sorts the (parent, child)
+   pairs and walks them; what the walk decides is: a light swarm hangs on the parent of the smallest pair
+   parent << 32 | child among its members' candidates, and a heavy swarm's chain holds the light swarms it won in
+   ascending order of those pairs.  graft_cand = n candidates on the host (SWA_NO_AMPLICON: none; every other value must
+   be an amplicon, SWA_E_ARG otherwise), or NULL for the candidates the last whole swa_d1_fastidious* pass of the context
+   left in HBM.  No swarm with a candidate child may hold a candidate parent (light swarms have the children, heavy ones
+   the parents).  *grafts = G; the four arrays (any may be NULL) receive the grafts in chain order — sorted by (heavy
+   swarm, pair): heavy swarm, light swarm, parent amplicon, child amplicon.  SWA_E_CAPACITY with *grafts = the need when
+   cap < G: nothing but the withdrawal below has happened then; call again with room (and the same graft_cand, or
+   NULL).  The candidates of the children that did not win are withdrawn (SWA_NO_AMPLICON) in HBM, and the heavy swarms'
+   sums grow by their light swarms' mass, length and singletons (the deepest generation stays, like the reference).  A
+   further call starts from the swarms' own sums again.
+   swa_d1_graft_candidates_fetch: the n candidates as they lie in HBM (after swa_d1_graft_device: the winners'). */
+int swa_d1_swarm_sums_device(swa_ctx * ctx, uint64_t * mass, uint64_t * sumlen, uint32_t * singletons, uint32_t * maxgen,
+                             uint32_t nswarms);
+int swa_d1_light_flags_device(swa_ctx * ctx, uint64_t boundary, uint8_t * is_light, uint64_t stats5[5]);
+int swa_d1_fastidious_resident(swa_ctx * ctx, uint64_t light_nt, uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
+int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, uint32_t * heavy_swarm, uint32_t * light_swarm,
+                        uint32_t * parent, uint32_t * child, uint32_t cap, uint32_t * grafts);
+int swa_d1_graft_candidates_fetch(swa_ctx * ctx, uint32_t * graft_cand);
+
 /* ---- d = 0: dereplication -------------------------------
    Replaces the bucket search of dereplicating() (src/derep.cc:276-354: Zobrist hash, open
    addressing, exact sequence comparison on a hash match).  first_identical[i] = the smallest

@@ -80,6 +80,16 @@ int  swa_d1_light_flags(const swa_d1_result * res, int64_t boundary, uint8_t * i
 /* attach_candidates (src/algod1.cc:274-336): graft_cand[n] as returned by swa_d1_fastidious;
    returns the number of grafts made */
 uint32_t swa_d1_graft(swa_d1_result * res, const uint32_t * graft_cand);
+/* The same from the four arrays of swa_d1_graft_device (grafts in chain order: heavy swarm, light swarm, parent amplicon,
+   child amplicon), one pass over them: chain links, the grown sizes, the largest swarm, the swarm count, graft_cand of the
+   winning children.  On a result whose details are still in HBM (swa_d1_cluster_resident_lazy) nothing is fetched: the
+   sums and graft_cand are settled when a writer or accessor asks for the details, and -s, -w, -i, -u come out as after
+   swa_d1_graft.  SWA_E_ARG (nothing installed) for arrays that are no graft of this result: a swarm or amplicon it
+   does not have, a light swarm listed twice, attached already or with a chain of its own, a heavy swarm that is attached. */
+int  swa_d1_result_install_graft(swa_d1_result * res, const uint32_t * heavy_swarm, const uint32_t * light_swarm,
+                                 const uint32_t * parent, const uint32_t * child, uint32_t grafts);
+/* how often swarm id, generation and parent were downloaded for this result (0 for a plain -o run, with or without -f) */
+uint32_t swa_d1_result_detail_fetches(const swa_d1_result * res);
 /* writers (path "-" = stdout): -o/-r, -s, -i, -w, -j  (src/algod1.cc:755-1062) */
 int swa_d1_write_swarms(const swa_d1_result * res, const swa_hostdb * db, const char * path, int mothur,
                         int usearch_abundance, int64_t append_abundance, int64_t differences);

@@ -82,6 +82,8 @@ EXPORTS = [
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
     "swa_d1_result_parent", "swa_d1_result_generation", "swa_d1_light_flags", "swa_d1_graft", "swa_d1_write_swarms",
     "swa_d1_write_stats", "swa_d1_write_structure", "swa_d1_write_seeds", "swa_d1_write_network",
+    "swa_d1_swarm_sums_device", "swa_d1_light_flags_device", "swa_d1_fastidious_resident", "swa_d1_graft_device",
+    "swa_d1_graft_candidates_fetch", "swa_d1_result_install_graft", "swa_d1_result_detail_fetches",
 ]
 
 
@@ -133,6 +135,14 @@ def load_library() -> C.CDLL:
     lib.swa_d1_fastidious.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_shard.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p]
+    lib.swa_d1_swarm_sums_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.swa_d1_light_flags_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u64p]
+    lib.swa_d1_fastidious_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.swa_d1_graft_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, u32p]
+    lib.swa_d1_graft_candidates_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_result_install_graft.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.swa_d1_result_detail_fetches.argtypes = [C.c_void_p]
+    lib.swa_d1_result_detail_fetches.restype = C.c_uint32
     lib.swa_d1_fastidious_plan.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_totals.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_split.argtypes = [C.c_void_p, C.c_void_p]
@@ -417,6 +427,19 @@ class D1Clusters:
     def graft(self, graft_cand: np.ndarray) -> int:
         g = np.ascontiguousarray(graft_cand, dtype=np.uint32)
         return int(self.lib.swa_d1_graft(self.h, _ptr(g)))
+
+    def install_graft(self, heavy_swarm, light_swarm, parent, child) -> None:
+        """swa_d1_result_install_graft: the grafts of Context.d1_graft_device (chain order) installed as graft() would
+        leave them; a lazy result downloads nothing for it."""
+        four = [np.ascontiguousarray(a, dtype=np.uint32) for a in (heavy_swarm, light_swarm, parent, child)]
+        assert len({len(a) for a in four}) == 1
+        rc = self.lib.swa_d1_result_install_graft(self.h, *(_ptr(a) if len(a) else None for a in four), len(four[0]))
+        if rc != SWA_OK:
+            raise SwaError(rc, "swa_d1_result_install_graft failed: " + self.lib.swa_d1_result_error(self.h).decode())
+
+    def detail_fetches(self) -> int:
+        """swa_d1_result_detail_fetches: downloads of swarm id / generation / parent made for this result"""
+        return int(self.lib.swa_d1_result_detail_fetches(self.h))
 
     def write_swarms(self, path, mothur=False, usearch=False, append_abundance=0, differences=1) -> None:
         assert self.lib.swa_d1_write_swarms(self.h, self.hdb.h, str(path).encode(), int(mothur), int(usearch),
@@ -799,6 +822,63 @@ class Context:
         self._check(self.lib.swa_d1_fastidious_shard(self.h, _ptr(is_light), int(light_nt), int(bloom_bits),
                                                      int(shard), int(nshards), _ptr(graft), _ptr(counters)))
         return graft, counters
+
+    def d1_swarm_sums_device(self, nswarms: int | None = None):
+        """swa_d1_swarm_sums_device: (mass u64, sumlen u64, singletons u32, maxgen u32) of every swarm of the clustering
+        in place, summed on the device.  nswarms: the entries of the arrays to hand over (the number of swarms, which
+        d1_cluster_device told; fewer: SwaError SWA_E_CAPACITY); None: no array, the sums only stay in HBM."""
+        if nswarms is None:
+            self._check(self.lib.swa_d1_swarm_sums_device(self.h, None, None, None, None, 0))
+            return None
+        w = int(nswarms)
+        mass, sumlen = np.zeros(w, dtype=np.uint64), np.zeros(w, dtype=np.uint64)
+        singletons, maxgen = np.zeros(w, dtype=np.uint32), np.zeros(w, dtype=np.uint32)
+        self._check(self.lib.swa_d1_swarm_sums_device(self.h, _ptr(mass), _ptr(sumlen), _ptr(singletons), _ptr(maxgen), w))
+        return mass, sumlen, singletons, maxgen
+
+    def d1_light_flags_device(self, boundary: int = 3, flags: bool = True):
+        """swa_d1_light_flags_device: (is_light u8[n] or None, [light swarms, light amplicons, their nt, heavy swarms,
+        heavy amplicons]); the flags stay in HBM for d1_fastidious_resident either way."""
+        is_light = np.zeros(self.n, dtype=np.uint8) if flags else None
+        stats = np.zeros(5, dtype=np.uint64)
+        self._check(self.lib.swa_d1_light_flags_device(self.h, int(boundary), _ptr(is_light), _p64(stats)))
+        return is_light, [int(x) for x in stats]
+
+    def d1_fastidious_resident(self, light_nt: int, bloom_bits: int = 16, fetch: bool = True):
+        """swa_d1_fastidious_resident: the second pass with its roles from the flags d1_light_flags_device left in HBM.
+        (graft_cand or None when fetch is False: the candidates then stay in HBM for d1_graft_device, counters)."""
+        graft = np.zeros(self.n, dtype=np.uint32) if fetch else None
+        counters = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.swa_d1_fastidious_resident(self.h, int(light_nt), int(bloom_bits), _ptr(graft), _ptr(counters)))
+        return graft, counters
+
+    def d1_graft_device(self, graft_cand=None, cap: int | None = None):
+        """swa_d1_graft_device: (heavy swarm, light swarm, parent, child) of the G grafts in chain order.  graft_cand: n
+        candidates on the host, or None for those the last fastidious pass left in HBM.  cap: entries of the result arrays
+        (default: asked for first); SwaError(SWA_E_CAPACITY) whose `grafts` is the need when it is too small."""
+        cand = None if graft_cand is None else np.ascontiguousarray(graft_cand, dtype=np.uint32)
+        if cand is not None and len(cand) != self.n:
+            raise ValueError("d1_graft_device: one candidate per amplicon of the resident database")
+        made = C.c_uint32(0)
+        if cap is None:
+            rc = self._check(self.lib.swa_d1_graft_device(self.h, _ptr(cand), None, None, None, _ptr(np.zeros(1, dtype=np.uint32)), 0,
+                                                          C.byref(made)), allow=(SWA_E_CAPACITY,))
+            cap = int(made.value)
+            if rc == SWA_OK:
+                return tuple(np.zeros(0, dtype=np.uint32) for _ in range(4))
+        four = [np.zeros(max(int(cap), 1), dtype=np.uint32) for _ in range(4)]
+        rc = self.lib.swa_d1_graft_device(self.h, _ptr(cand), *(_ptr(a) for a in four), int(cap), C.byref(made))
+        if rc != SWA_OK:
+            err = SwaError(rc, self.lib.swa_last_error(self.h).decode())
+            err.grafts = int(made.value)
+            raise err
+        return tuple(a[:made.value] for a in four)
+
+    def d1_graft_candidates(self) -> np.ndarray:
+        """swa_d1_graft_candidates_fetch: the candidates as they lie in HBM (after d1_graft_device: the winners' only)"""
+        out = np.zeros(self.n, dtype=np.uint32)
+        self._check(self.lib.swa_d1_graft_candidates_fetch(self.h, _ptr(out)))
+        return out
 
     def d1_fastidious_plan(self) -> list:
         """swa_d1_fastidious_plan: [pair route, pair kernel words (0: packed words), count kernel words (0: the LDS set,

@@ -230,6 +230,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   // swarms, the usual one, never looks at them)
   if (ctx == nullptr || order == nullptr || nswarms == nullptr) { return SWA_E_ARG; }
   ctx->res.cluster_ready = false;
+  ctx->res.fast = {};                                       // (sums, roles and candidates belonged to the clustering that ends here)
   if (!ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_device: no resident network (swa_d1_network_resident)"); }
   for (uint32_t & e : ctx->res.cluster_effort) { e = 0; }
   if (ctx->db.n == 0) {                                   // (nothing to cluster: seed_rank + (n - 1) below would lie in front of the buffer)
@@ -317,6 +318,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   }
   ctx->res.cluster_maxgen = maxgen;
   *nswarms = last_rank + last_seed;
+  ctx->res.cluster_nswarms = *nswarms;
   if (*nswarms > swarm_cap || swarm_begin == nullptr) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_cluster_device: swarm table too small"); }
   // ---- members by (swarm, generation, id): one stable radix sort over the bits that vary, ids ascending going in
   const uint32_t gbits = bit_width_u32(maxgen), sbits = bit_width_u32(*nswarms - 1u);
@@ -388,3 +390,5 @@ extern "C" int swa_d1_cluster_effort(const swa_ctx * ctx, uint32_t out3[3]) {
 
 // the deepest generation of the clustering in place (what the log calls "Max generations")
 extern "C" uint32_t swa_d1_cluster_maxgen(const swa_ctx * ctx) { return ctx != nullptr && ctx->res.cluster_ready ? ctx->res.cluster_maxgen : 0u; }
+
+#include "fast_graft.inc"

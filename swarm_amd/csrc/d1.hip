@@ -2772,6 +2772,9 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
   return SWA_OK;
 }
 
+static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
+                                 uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
+
 extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
                                        uint32_t shard, uint32_t nshards, uint32_t * graft_cand, uint64_t * counters) {
   if (ctx == nullptr) { return SWA_E_ARG; }
@@ -2781,13 +2784,7 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: bad argument");
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  SWA_TRY(prepare_hashing(ctx));                             // the Zobrist table
   const uint32_t n = ctx->db.n;
-  // the numbers of the reference's log line (src/algod1.cc:1337-1357, 1383-1403; bloomflex.cc:91-115)
-  uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
-  if (k < 1) { k = 1; }
-  uint64_t m = light_nt * 7ull * bloom_bits;
-  if (m < 64) { m = 64; }
 
   // role of every amplicon: 0 light, 1 heavy and in this shard's contiguous slice of the heavy ones, 2 neither
   // (by blocks on a few threads: two serial passes over 10 M flags were 15 ms of this call, lease r6j)
@@ -2818,6 +2815,26 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
     }
   });
   const uint64_t n_heavy = hi - lo;
+  const int rc = fastidious_with_roles(ctx, role.get(), n_light, n_heavy, light_nt, bloom_bits, graft_cand, counters);
+  if (rc != SWA_OK) { (void)hipStreamSynchronize(ctx->stream); }     // (role is a host temporary)
+  ctx->res.fast.cand_ready = rc == SWA_OK && nshards == 1u;   // (d_graft: the candidates of the whole pass, for swa_d1_graft_device)
+  return rc;
+}
+
+// The pass from the roles on (0 light, 1 heavy and to be expanded here, 2 neither): what swa_d1_fastidious_shard and
+// swa_d1_fastidious_resident share.  host_role: the shard form's array, uploaded into d_frole; null: the bytes
+// swa_d1_light_flags_device left in d_swarm_role, copied on the device.  Reservations, copies and launches come in the order
+// swa_d1_fastidious_shard has always made them.  graft_cand may be null: the candidates then stay in HBM (d_graft) only.
+static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
+                                 uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
+  SWA_TRY(prepare_hashing(ctx));                             // the Zobrist table
+  const uint32_t n = ctx->db.n;
+  ctx->res.fast.cand_ready = false;
+  // the numbers of the reference's log line (src/algod1.cc:1337-1357, 1383-1403; bloomflex.cc:91-115)
+  uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
+  if (k < 1) { k = 1; }
+  uint64_t m = light_nt * 7ull * bloom_bits;
+  if (m < 64) { m = 64; }
 
   FastPlan plan{};
   SWA_TRY(fast_plan(ctx, plan));
@@ -2832,7 +2849,8 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   SWA_TRY(swa_reserve(ctx, ctx->d_list_a, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_list_b, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
-  SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, role.get(), n, hipMemcpyHostToDevice, ctx->stream));
+  if (host_role != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, host_role, n, hipMemcpyHostToDevice, ctx->stream)); }
+  else { SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, ctx->d_swarm_role.ptr, n, hipMemcpyDeviceToDevice, ctx->stream)); }
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_graft.ptr, 0xFF, uint64_t(n) * sizeof(uint32_t), ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_fcounters.ptr, 0, 16 * sizeof(uint64_t), ctx->stream));
   auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
@@ -2858,8 +2876,10 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
 
   uint64_t host_fc[8] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host_fc, fc, sizeof(host_fc), hipMemcpyDeviceToHost, ctx->stream));
-  swa_touch_pages(graft_cand, uint64_t(n) * sizeof(uint32_t));
-  SWA_HIP(ctx, hipMemcpyAsync(graft_cand, ctx->d_graft.ptr, uint64_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (graft_cand != nullptr) {
+    swa_touch_pages(graft_cand, uint64_t(n) * sizeof(uint32_t));
+    SWA_HIP(ctx, hipMemcpyAsync(graft_cand, ctx->d_graft.ptr, uint64_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   counters[0] = host_fc[0];
   counters[1] = host_fc[1];
@@ -2867,5 +2887,22 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
   counters[3] = m;
   counters[4] = k;
   for (int i = 0; i < 3; ++i) { ctx->fast_totals[i] = host_fc[5 + i]; }
+  return SWA_OK;
+}
+
+// The same pass fed from the device: the roles are the bytes swa_d1_light_flags_device left in HBM for the clustering in
+// place (no host flags, no role passes on the host, no upload), and the candidates come home only when the caller hands
+// over a buffer — swa_d1_graft_device reads them where they lie.
+extern "C" int swa_d1_fastidious_resident(swa_ctx * ctx, uint64_t light_nt, uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (!ctx->res.cluster_ready || !ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_resident: no clustering in place (swa_d1_cluster_device)"); }
+  if (!ctx->res.fast.roles_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_resident: call swa_d1_light_flags_device first"); }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: call swa_d1_index_build first"); }
+  if (counters == nullptr || bloom_bits < 2 || bloom_bits > 64) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: bad argument"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = ctx->db.n;
+  const uint64_t n_light = ctx->res.fast.light_amps;
+  SWA_TRY(fastidious_with_roles(ctx, nullptr, n_light, n - n_light, light_nt, bloom_bits, graft_cand, counters));
+  ctx->res.fast.cand_ready = true;
   return SWA_OK;
 }

@@ -51,6 +51,10 @@ struct swa_d1_result {
   swa_ctx * lazy_ctx = nullptr;
   const swa_hostdb * lazy_db = nullptr;
   bool details = true;
+  uint32_t detail_fetches = 0;              // downloads of swarm id / generation / parent made for this result (swa_d1_result_detail_fetches)
+  // swa_d1_result_install_graft on a result whose details are still lazy: the grafts, folded into the sums and graft_cand
+  // when the details are made after all (need_details)
+  std::vector<uint32_t> pending_heavy, pending_light, pending_parent, pending_child;
   // swa_d1_result_prepare: order and the download area of the swarms' bounds sized ahead — and pinned, when the runtime agreed
   swa_vec<uint32_t> begin_tmp;
   bool prepared = false, pinned_order = false, pinned_begin = false;
@@ -128,6 +132,18 @@ bool need_details(const swa_d1_result * cr) {
       sw.maxgen = std::max(sw.maxgen, gen[a]);
     }
   }
+  ++r->detail_fetches;
+  // grafts installed while the details were lazy: the heavy swarms' sums grow by their light swarms' (no light swarm is
+  // anybody's heavy swarm, so the order does not matter), the winning children keep their candidate
+  for (size_t i = 0; i < r->pending_heavy.size(); ++i) {
+    auto & heavy = r->swarms[r->pending_heavy[i]];
+    const auto & light = r->swarms[r->pending_light[i]];
+    heavy.singletons += light.singletons;
+    heavy.mass += light.mass;
+    heavy.sumlen += light.sumlen;                         // maxgen untouched, like the reference
+    r->graft_cand[r->pending_child[i]] = r->pending_parent[i];
+  }
+  for (auto * v : {&r->pending_heavy, &r->pending_light, &r->pending_parent, &r->pending_child}) { std::vector<uint32_t>().swap(*v); }
   r->details = true;
   r->lazy_ctx = nullptr;                                    // (nothing of the context is needed from here on)
   return true;
@@ -693,6 +709,64 @@ extern "C" uint32_t swa_d1_graft(swa_d1_result * r, const uint32_t * graft_cand)
   }
   return grafts;
 }
+
+// The grafts swa_d1_graft_device made (chain order: by heavy swarm, then by the winning pair) installed into the result:
+// what swa_d1_graft leaves — chain links, `attached`, the grown sizes, `largest`, the adjusted swarm count, graft_cand of the
+// winning children — in one pass over the G entries.  The per-swarm sums and graft_cand of a result whose details are still
+// on the device are settled when somebody asks for the details (need_details); a plain -o never does.
+extern "C" int swa_d1_result_install_graft(swa_d1_result * r, const uint32_t * heavy_swarm, const uint32_t * light_swarm,
+                                           const uint32_t * parent, const uint32_t * child, uint32_t grafts) {
+  if (r == nullptr || (grafts != 0 && (heavy_swarm == nullptr || light_swarm == nullptr || parent == nullptr || child == nullptr))) { return SWA_E_ARG; }
+  const size_t nswarms = r->swarms.size();
+  // checked before anything is linked: swarms and amplicons of this result, every light swarm once and free, no heavy
+  // swarm among the light ones (a light swarm is marked 2 while the check runs)
+  bool fits = true;
+  uint32_t marked = 0;
+  for (; fits && marked < grafts; ++marked) {
+    const uint32_t i = marked;
+    fits = heavy_swarm[i] < nswarms && light_swarm[i] < nswarms && parent[i] < r->n && child[i] < r->n &&
+           r->swarms[light_swarm[i]].attached == 0 && r->swarms[light_swarm[i]].graft_head == SWA_NO_AMPLICON;
+    if (fits) { r->swarms[light_swarm[i]].attached = 2; }
+  }
+  if (!fits) { --marked; }                                   // (the entry that failed was not marked)
+  for (uint32_t i = 0; fits && i < grafts; ++i) { fits = r->swarms[heavy_swarm[i]].attached == 0; }
+  for (uint32_t i = 0; i < marked; ++i) { r->swarms[light_swarm[i]].attached = 0; }
+  if (!fits) {
+    r->error = "swa_d1_result_install_graft: not a graft of this clustering";
+    return SWA_E_ARG;
+  }
+  const bool lazy = !r->details;
+  if (lazy) {
+    r->pending_heavy.insert(r->pending_heavy.end(), heavy_swarm, heavy_swarm + grafts);
+    r->pending_light.insert(r->pending_light.end(), light_swarm, light_swarm + grafts);
+    r->pending_parent.insert(r->pending_parent.end(), parent, parent + grafts);
+    r->pending_child.insert(r->pending_child.end(), child, child + grafts);
+  } else {
+    // (the candidates of the children that did not win are withdrawn: only the winners keep one)
+    fill_parallel(r->graft_cand, r->n, (uint32_t)SWA_NO_AMPLICON);
+  }
+  for (uint32_t i = 0; i < grafts; ++i) {
+    const uint32_t light_id = light_swarm[i];
+    auto & heavy = r->swarms[heavy_swarm[i]];
+    auto & light = r->swarms[light_id];
+    if (heavy.graft_head == SWA_NO_AMPLICON) { heavy.graft_head = light_id; }
+    else { r->swarms[heavy.graft_tail].graft_next = light_id; }
+    heavy.graft_tail = light_id;
+    heavy.size += light.size;
+    if (!lazy) {
+      heavy.singletons += light.singletons;
+      heavy.mass += light.mass;
+      heavy.sumlen += light.sumlen;                 // maxgen untouched, like the reference
+      r->graft_cand[child[i]] = parent[i];
+    }
+    light.attached = 1;
+    r->largest = std::max(r->largest, heavy.size);
+  }
+  r->swarmcount_adjusted -= grafts;
+  return SWA_OK;
+}
+
+extern "C" uint32_t swa_d1_result_detail_fetches(const swa_d1_result * r) { return r == nullptr ? 0u : r->detail_fetches; }
 
 // ---- writers ------------------------------------------------------------------------------
 // -o / -r  (src/algod1.cc:790-846)

@@ -381,6 +381,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     }
   }
 
+  long d1_detail_fetches = -1;              // (d = 1, for the closing line of SWARM_AMD_TIMING)
   if (o.differences == 0) {
     // ---- d = 0: identical-sequence search on the GPU, cluster bookkeeping on the host
     std::vector<uint32_t> first_identical(n);
@@ -482,9 +483,15 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       std::fprintf(g_log, "\nResults before fastidious processing:\n");
       std::fprintf(g_log, "Number of swarms:  %" PRIu64 "\n", sum[0]);
       std::fprintf(g_log, "Largest swarm:     %" PRIu64 "\n\n", sum[1]);
-      swa_vec<uint8_t> is_light(n);                         // (every entry is written by swa_d1_light_flags: each amplicon is in one swarm)
+      // One context with the clustering still in HBM (the usual run): sums, flags, candidates and grafting stay on the GPU
+      // (swa_d1_light_flags_device .. swa_d1_graft_device).  Several GPUs and a clustering made on the host take the host's
+      // bookkeeping; SWARM_AMD_FASTIDIOUS=host selects it for comparison.
+      const char * fast_route = std::getenv("SWARM_AMD_FASTIDIOUS");
+      const bool on_device = resident && multi == nullptr && !(fast_route != nullptr && std::strcmp(fast_route, "host") == 0);
+      swa_vec<uint8_t> is_light(on_device ? 0 : n);         // (every entry is written by swa_d1_light_flags: each amplicon is in one swarm)
       uint64_t st[5];
-      if (swa_d1_light_flags(res, o.boundary, is_light.data(), st) != SWA_OK) { die(swa_d1_result_error(res)); }
+      if (on_device) { if (swa_d1_light_flags_device(ctx, (uint64_t)o.boundary, nullptr, st) != SWA_OK) { die(swa_last_error(ctx)); } }
+      else if (swa_d1_light_flags(res, o.boundary, is_light.data(), st) != SWA_OK) { die(swa_d1_result_error(res)); }
       phase(o, "Counting amplicons in heavy and light swarms");
       std::fprintf(g_log, "Heavy swarms: %" PRIu64 ", with %" PRIu64 " amplicons\n", st[3], st[4]);
       std::fprintf(g_log, "Light swarms: %" PRIu64 ", with %" PRIu64 " amplicons\n", st[0], st[1]);
@@ -504,8 +511,8 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
             bits = new_bits;
           }
         }
-        swa_vec<uint32_t> graft(n);                         // (the download writes every entry; its pages are faulted in by all threads first:
-        {                                                   //  one thread's fill of 40 MB was 10 ms of this phase)
+        swa_vec<uint32_t> graft(on_device ? 0 : n);         // (the download writes every entry; its pages are faulted in by all threads first:
+        if (!on_device) {                                   //  one thread's fill of 40 MB was 10 ms of this phase)
           char * gp = reinterpret_cast<char *>(graft.data());
           const int64_t pages = (int64_t)(((size_t)n * sizeof(uint32_t) + 4095) / 4096);
 #pragma omp parallel for schedule(static)
@@ -519,7 +526,10 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
         if (m < 64) { m = 64; }
         std::fprintf(g_log, "Bloom filter: bits=%" PRIu64 ", m=%" PRIu64 ", k=%u, size=%.1fMB\n", bits, m, k,
                      (double)m / (8.0 * 1024.0 * 1024.0));
-        if (multi != nullptr) {
+        if (on_device) {
+          rc = swa_d1_fastidious_resident(ctx, st[2], (uint32_t)bits, nullptr, counters);
+          if (rc != SWA_OK) { die(swa_last_error(ctx)); }
+        } else if (multi != nullptr) {
           rc = swa_multi_d1_fastidious(multi, is_light.data(), st[2], (uint32_t)bits, graft.data(), counters);
           if (rc != SWA_OK) { die(swa_multi_last_error(multi)); }
         } else {
@@ -531,7 +541,17 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
         phase(o, "Checking heavy swarm amplicons against Bloom filter");
         std::fprintf(g_log, "Heavy variants: %" PRIu64 "\n", counters[1]);
         std::fprintf(g_log, "Got %" PRIu64 " graft candidates\n", counters[2]);
-        const uint32_t grafts = swa_d1_graft(res, graft.data());
+        uint32_t grafts = 0;
+        if (on_device) {
+          // (a graft needs a candidate and a light swarm of its own: never more than either)
+          const uint32_t room = (uint32_t)std::min<uint64_t>(counters[2], st[0]);
+          swa_vec<uint32_t> chain((size_t)room * 4);
+          uint32_t * heavy = chain.data(), * light = heavy + room, * parent = light + room, * child = parent + room;
+          if (swa_d1_graft_device(ctx, nullptr, heavy, light, parent, child, room, &grafts) != SWA_OK) { die(swa_last_error(ctx)); }
+          if (swa_d1_result_install_graft(res, heavy, light, parent, child, grafts) != SWA_OK) { die(swa_d1_result_error(res)); }
+        } else {
+          grafts = swa_d1_graft(res, graft.data());
+        }
         phase(o, "Grafting light swarms on heavy swarms");
         std::fprintf(g_log, "Made %u grafts\n\n", grafts);
       }
@@ -550,6 +570,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     swa_d1_result_summary(res, sum);
     std::fprintf(g_log, "\nNumber of swarms:  %" PRIu64 "\nLargest swarm:     %" PRIu64 "\nMax generations:   %" PRIu64 "\n", sum[0],
                  sum[1], sum[2]);
+    d1_detail_fetches = (long)swa_d1_result_detail_fetches(res);
     // (the result's arrays are left to the kernel with the rest, unless an orderly teardown was asked for: unmapping them
     // here is time the caller waits, lease r5j)
     if (std::getenv("SWARM_AMD_FULL_TEARDOWN") != nullptr) { swa_d1_result_free(res); }
@@ -586,6 +607,9 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
                  sum[1], sum[2]);
   }
   stamp("results written");
+  if (std::getenv("SWARM_AMD_TIMING") != nullptr && d1_detail_fetches >= 0) {
+    std::fprintf(stderr, "[details] swarm id, generation and parent downloaded %ld time(s)\n", d1_detail_fetches);
+  }
   stamp_usage("results written");
   // Every output file is closed at this point.  What the process still holds costs at exit by what the kernel has to take
   // apart on ONE thread — ~75 ms per GB of host pages on the bench host, nothing measurable for device memory — or next

@@ -201,6 +201,15 @@ struct swa_resident {
   bool cluster_ready = false;                  // swa_d1_cluster_device's arrays lie in d_cluster (swa_d1_cluster_fetch)
   uint32_t cluster_maxgen = 0;
   uint32_t cluster_effort[3] = {};             // of the last swa_d1_cluster_device call: label sweeps launched, restarts of their numbering, level batches
+  uint32_t cluster_nswarms = 0;                // swarms of the clustering in place
+  // what --fastidious derives from the clustering in place and keeps in HBM (fast_graft.inc); ended with it
+  struct fastidious_facts {
+    bool sums_ready = false;                   // d_swarm_sums: mass | sumlen | singletons | maxgen of every swarm
+    bool sums_grafted = false;                 // ... grown by swa_d1_graft_device (its next call makes the swarms' own sums again first)
+    bool roles_ready = false;                  // d_swarm_role: 0 light / 1 heavy per amplicon, against the boundary of the last flags call
+    uint64_t light_amps = 0;                   // ... and how many amplicons it found in light swarms
+    bool cand_ready = false;                   // d_graft: the candidates of a whole swa_d1_fastidious* pass (or a caller's) over this clustering
+  } fast;
 };
 
 struct swa_ctx {
@@ -289,6 +298,9 @@ struct swa_ctx {
   bool part_lds_opt_in = false;                // ... and the wide-tile form of k_part_scatter
   uint32_t pair_lds_opt_in = 0;    // ... and the W = 15 / 21 forms of k_d1_group_pairs (pass + 2 (W = 21) + 4 (NW = 2) + 8 (NW = 4))
   swa_dbuf d_cluster, d_cluster_ctl;
+  // --fastidious on the clustering in place (fast_graft.inc): the per-swarm sums, the role byte of every amplicon, and the
+  // grafting's slots, winner lists and result arrays
+  swa_dbuf d_swarm_sums, d_swarm_role, d_graft_work;
 
   // the uclust alignments (nw_trace.hip): the pairs per tier of the last batch (three LDS tiers, four wide tiers, host), how
   // many of them the widest tier certified but found the text buffer full, and the device buffers of one slice (d_nw_bits: the wide tiers'
