@@ -405,6 +405,11 @@ uint32_t swa_d1_fastidious_sites_cap(uint32_t sites_cap);
    [2] heavy amplicons handed to the Bloom route (those of the short band and, under the split or pairs, of the long band),
    [3] attempts the pair list took (2 or more: it was regrown; 0: the pair route did not run). */
 int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]);
+/* Of the last swa_d1_fastidious[_shard] call, the batch loop of the Bloom route: out[0] launches of the heavy side's
+   enumeration (k_d1_flex<., 1>), [1] how many of them produced more tasks than the list holds and were redone smaller,
+   [2] the task cap in effect (1 GiB of tasks, or SWA_FAST_TASK_CAP; never below 7 longest + 4), [3] the most tasks a batch
+   that ran produced (<= [2]).  All zero when the Bloom route did not run. */
+int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]);
 
 /* ---- B2 on the clustering in place: swarm sums, light flags, candidates and grafting without the host ----------------
    The reference does its fastidious bookkeeping on the host, around the two passes above; a caller that binds seam B2 and

@@ -2456,9 +2456,12 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   SWA_TRY(swa_reserve(ctx, ctx->d_fpatterns, fpat.size() * sizeof(uint64_t)));
   const uint64_t maxv = 7ull * ctx->db.longest + 4ull;
   uint64_t task_cap = uint64_t(n_heavy) * maxv;
-  const uint64_t cap_limit = (1ull << 30) / sizeof(swa_task);            // 1 GiB of tasks
+  uint64_t cap_limit = (1ull << 30) / sizeof(swa_task);                  // 1 GiB of tasks
+  const char * env_cap = getenv("SWA_FAST_TASK_CAP");         // test hook: so many tasks instead (the floor below stays), exercise the batch loop
+  if (env_cap != nullptr && atoll(env_cap) > 0) { cap_limit = (uint64_t)atoll(env_cap); }
   if (task_cap > cap_limit) { task_cap = cap_limit; }
-  if (task_cap < maxv) { task_cap = maxv; }
+  if (task_cap < maxv) { task_cap = maxv; }                  // (what makes a batch of task_cap / maxv heavy amplicons unable to overflow)
+  ctx->fast_batches[2] = task_cap;
   SWA_TRY(swa_reserve(ctx, ctx->d_queue, task_cap * sizeof(swa_task)));
   SWA_HIP(ctx, hipMemcpyAsync(ctx->d_fpatterns.ptr, fpat.data(), fpat.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_bloomflex.ptr, 0xFF, fsize * sizeof(uint64_t), ctx->stream));
@@ -2530,7 +2533,9 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
     SWA_HIP(ctx, hipMemcpyAsync(got, fc + 3, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rate = static_cast<double>(got[0]) / static_cast<double>(want);
-    if (got[0] > task_cap) { continue; }                     // optimistic batch did not fit: redo it smaller
+    ++ctx->fast_batches[0];
+    if (got[0] > task_cap) { ++ctx->fast_batches[1]; continue; }   // optimistic batch did not fit: redo it smaller
+    if (got[0] > ctx->fast_batches[3]) { ctx->fast_batches[3] = got[0]; }
     if (got[0] > 0) {
       a.count = static_cast<uint32_t>(got[0]);
       const int pgrid = grid_for(ctx, a.count, kWaves, 8);
@@ -2641,6 +2646,12 @@ extern "C" int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]) {
 extern "C" int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
   for (int i = 0; i < 4; ++i) { out[i] = ctx->fast_totals[i]; }
+  return SWA_OK;
+}
+
+extern "C" int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]) {
+  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
+  for (int i = 0; i < 4; ++i) { out[i] = ctx->fast_batches[i]; }
   return SWA_OK;
 }
 
@@ -2840,6 +2851,7 @@ static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint6
   SWA_TRY(fast_plan(ctx, plan));
   const bool pair_route = plan.pair_route;
   for (uint64_t & t : ctx->fast_totals) { t = 0; }
+  for (uint64_t & t : ctx->fast_batches) { t = 0; }
   const uint32_t min_len = pair_route ? kFastMinLen : 0xFFFFFFFFu;
   const uint32_t max_len = plan.max_len;                     // (0xFFFFFFFF without a division at the long end)
 

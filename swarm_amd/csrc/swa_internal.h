@@ -282,6 +282,7 @@ struct swa_ctx {
   swa_dbuf d_frole, d_fkeys, d_fcnt, d_foff, d_fslot, d_fmembers, d_fitems, d_fpairs;
   uint64_t fast_pair_cap = 0;
   uint64_t fast_totals[4] = {};  // of the last pass: pairs found, light / heavy amplicons of the Bloom route's bands, attempts of the pair list
+  uint64_t fast_batches[4] = {}; // of the last pass's Bloom route: k_d1_flex<., 1> launches, those that overflowed and were redone, the task cap, the most tasks of a batch that ran
 
   // d >= 2 in bulk (dn_graph.hip)
   uint64_t dn_pair_cap = 0, dn_comparisons = 0, dn_aligned = 0, dn_launches = 0, dn_edges = 0, dn_work = 0;
