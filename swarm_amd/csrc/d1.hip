@@ -11,8 +11,8 @@
 //     (exclusive prefix of Z[p][s_p], suffixes of Z[p-1][s_p] and Z[p+1][s_p]);
 //   * default route (d1_anchor.inc): amplicons grouped by their first / last 32 nucleotides,
 //     a group's members in an LDS table + LDS Bloom, every probe answered from LDS;
-//   * plain route (k_d1_probe, this file: statistics, sequences the anchored passes cannot
-//     serve, the fastidious second level): the 2-bit packed query, the Zobrist table and the
+//   * plain route (k_d1_probe, d1_probe.inc: statistics, sequences the anchored passes cannot
+//     serve; its MODE 1, the fastidious second level, belongs to fastidious.hip): the 2-bit packed query, the Zobrist table and the
 //     1024 Bloom patterns in LDS, Bloom-word loads issued 8 at a time per lane, survivors
 //     compacted with __ballot/__popcll into a per-wave LDS queue and drained 64 at a time so
 //     that table walk, abundance rule and exact verification run with full lanes;
@@ -22,71 +22,25 @@
 //     no atomics); the partition of d1_stream.inc sorts the segments' links into the canonical CSR.
 //
 // All arithmetic is 64-bit integer XOR/shift/compare; results are bit-exact.
+//
+// In this unit: hashing, the table, the plain probe (MODE 0 / 2), the anchored passes (d1_anchor.inc), the streaming index
+// build and the CSR assembly (d1_stream.inc), the guard, the multi-GPU route and link-exchange entry points, the debug
+// readers.  The --fastidious pass is a unit of its own (fastidious.hip); the few host functions it calls here are declared
+// in one block of swa_internal.h ("what fastidious.hip takes from d1.hip"), the device code both compile is in
+// d1_common.inc and d1_probe.inc.
 #include "swa_internal.h"
 
 #include <algorithm>
-#include <type_traits>
+#include <type_traits>   // (d1_stream.inc: std::conditional, std::true_type)
 #include <cstdlib>
-#include <memory>
-#include <thread>
 
 namespace {
 
-constexpr int kWaves = 4;                 // waves per workgroup
-constexpr int kThreads = kWaves * 64;
-constexpr int kQueueCap = 128;            // per-wave candidate queue (>= 64 + 63)
 constexpr size_t kMaxZobristLds = SWA_MAX_ZOBRIST_LDS;
 
 #include "wave_ops.inc"     // wave_lds_sync
-#include "group_join.inc"   // kEmpty, kKeyEmpty, mix64, window32; the grouped join of the --fastidious pair route (d1_fast.inc)
-
-struct alignas(16) swa_task {   // one surviving first-level microvariant of a heavy amplicon
-  uint64_t hash;
-  uint32_t heavy;
-  uint32_t code;
-};
-
-struct NetArgs {
-  const uint64_t * seqs;
-  const uint64_t * seq_off;
-  const uint32_t * seqlen;
-  const uint64_t * abundance;
-  const uint64_t * zobrist;     // 4 * zlen
-  uint32_t zlen;
-  uint32_t maxwords;            // ceil(longest / 32)
-  const swa_slot * table;
-  uint64_t tmask;
-  const uint64_t * bloom;
-  uint64_t bmask;
-  const uint64_t * patterns;    // 1024
-  int no_cluster_breaking;
-  uint32_t first;
-  uint32_t count;
-  uint64_t * edges;             // (src << 32) | dst
-  uint64_t seg_cap;             // edges are appended to per-wave segments: segment w = edges[w*seg_cap ..)
-  uint32_t * seg_fill;          // [launch waves] fill of each segment (no atomics: one writer per segment)
-  // MODE 2 (seeds the anchored passes cannot serve): explicit (seed, position range) list
-  const struct swa_fallback * fallback;
-  const uint32_t * fallback_count;
-  const struct swa_aux * aux;
-  // MODE 0 in a multi-GPU job (swa_d1_set_ownership, world > 1): only seeds with id mod world == rank
-  uint32_t owner_rank, owner_world;
-  // MODE 1 (fastidious second level)
-  const swa_task * tasks;
-  uint32_t * graft;
-  unsigned long long * cand_counter;
-  uint32_t fast_min_len;        // a (heavy, light) pair with both lengths in [fast_min_len, fast_max_len] belongs to the pair
-  uint32_t fast_max_len;        // route (d1_fast.inc); every other pair is admitted here (no upper bound: 0xFFFFFFFF)
-  // MODE 2 in window mode (anchor windows moved inwards): a fallback seed's share is defined by the window itself —
-  // range 1 = neighbours with the same prefix-side window (word win_word), range 2 = the others; all positions are
-  // enumerated and the hits filtered
-  uint32_t window_mode, win_word;
-  uint32_t anchor_w;            // width of the anchor windows in nt (32 / 64 / 128): the window is words [win_word, win_word + anchor_w / 32)
-};
-
-#define SWA_ANCHOR_TYPES_ONLY
-#include "d1_anchor.inc"
-#undef SWA_ANCHOR_TYPES_ONLY
+#include "key_ops.inc"      // kEmpty, kKeyEmpty, mix64, window32
+#include "d1_common.inc"    // kWaves / kThreads / kQueueCap, swa_aux, swa_item, the width classes, the amplicon lines, the anchor keys
 
 // ---- sequence hashes (db.cc:761 zobrist_hash) --------------------------------------
 template <bool ZLDS>
@@ -193,403 +147,9 @@ __global__ __launch_bounds__(256) void k_dup_check(const uint64_t * __restrict__
   }
 }
 
-// ---- the probe kernels ------------------------------------------------------------------
-
-// Wave-cooperative enumeration of all microvariants of the staged sequence `sw` (len nt).
-// Lane l owns positions [l*K, (l+1)*K), K = ceil((len+1)/64); `f(slots)` is called once
-// per owned position (K times, wave-uniformly) with that position's 8 candidate slots:
-//   [0..3] insertion of base b before p        (variants.cc:226-246)
-//   [4..6] substitution of p by the 3 others   (variants.cc:192-206)
-//   [7]    deletion of p, once per run          (variants.cc:210-222)
-// code = type | base << 2 | pos << 4.  Returns the sequence's own hash.
-struct Slots {
-  uint64_t hs[8];
-  bool ok[8];
-  uint32_t code[8];
-};
-
-template <class F>
-__device__ __forceinline__ uint64_t enumerate_variants(const uint64_t * sw, uint32_t len, const uint64_t * zob,
-                                                       int lane, F && f) {
-  // pass 1: per-lane XOR of the three Zobrist streams over the owned positions
-  const uint32_t K = (len + 64u) >> 6;                     // ceil((len + 1) / 64)
-  const uint32_t p0 = (uint32_t)lane * K;
-  uint64_t xa = 0, xd = 0, xi = 0;
-  for (uint32_t j = 0; j < K; ++j) {
-    const uint32_t p = p0 + j;
-    if (p < len) {
-      const uint32_t c = swa_nt(sw, p);
-      xa ^= zob[4u * p + c];
-      if (p >= 1u) { xd ^= zob[4u * (p - 1u) + c]; }
-      xi ^= zob[4u * (p + 1u) + c];
-    }
-  }
-  // wave scans: exclusive prefix of xa; inclusive suffixes of xd, xi
-  uint64_t pa = xa, sd = xd, si = xi;
-#pragma unroll
-  for (unsigned d = 1; d < 64; d <<= 1) {
-    const uint64_t ta = swa_shfl_up_u64(pa, d);
-    const uint64_t td = swa_shfl_down_u64(sd, d);
-    const uint64_t ti = swa_shfl_down_u64(si, d);
-    if (lane >= (int)d) { pa ^= ta; }
-    if (lane + (int)d < 64) { sd ^= td; si ^= ti; }
-  }
-  const uint64_t H = swa_shfl_u64(pa, 63);                 // hash of the whole sequence
-  pa ^= xa;                                                // exclusive
-
-  // pass 2: the variants of the owned positions
-  uint32_t prevc = (p0 >= 1u && p0 - 1u < len) ? swa_nt(sw, p0 - 1u) : 4u;
-  for (uint32_t j = 0; j < K; ++j) {
-    const uint32_t p = p0 + j;
-    const bool in_seq = p < len;
-    const bool in_ins = p <= len;
-    const uint32_t c = in_seq ? swa_nt(sw, p) : 4u;
-    uint64_t z[4];
-#pragma unroll
-    for (uint32_t b = 0; b < 4u; ++b) { z[b] = in_ins ? zob[4u * p + b] : 0ull; }
-    // z[c] without dynamic register indexing
-    const uint64_t zc = (c == 0u) ? z[0] : (c == 1u) ? z[1] : (c == 2u) ? z[2] : z[3];
-    const uint64_t za = in_seq ? zc : 0ull;
-    const uint64_t zd = (in_seq && p >= 1u) ? zob[4u * (p - 1u) + c] : 0ull;
-    const uint64_t zi = in_seq ? zob[4u * (p + 1u) + c] : 0ull;
-
-    Slots s;
-#pragma unroll
-    for (uint32_t b = 0; b < 4u; ++b) {
-      s.hs[b] = pa ^ z[b] ^ si;
-      s.ok[b] = in_ins && (p == 0u || b != prevc);
-      s.code[b] = 2u | (b << 2) | (p << 4);
-    }
-#pragma unroll
-    for (uint32_t t = 0; t < 3u; ++t) {
-      const uint32_t b = (t < c) ? t : t + 1u;               // the t-th base that is not c
-      s.hs[4 + t] = H ^ za ^ ((t < c) ? z[t] : z[t + 1u]);
-      s.ok[4 + t] = in_seq;
-      s.code[4 + t] = 0u | (b << 2) | (p << 4);
-    }
-    s.hs[7] = pa ^ sd ^ zd;
-    s.ok[7] = in_seq && (p == 0u || c != prevc);
-    s.code[7] = 1u | (p << 4);
-
-    f(s);
-
-    // advance the running prefix / suffixes past position p
-    pa ^= za;
-    sd ^= zd;
-    si ^= zi;
-    prevc = c;
-  }
-  return H;
-}
-
-// one probe of the candidate (hash h, edit code) drawn from the queue: walk the cluster,
-// apply the abundance rule, verify exactly (algod1.cc:558-603, variants.cc:118-165).
-// SECOND = the fastidious second level (hash_check_attach, algod1.cc:339-371): no self /
-// abundance test there.
-template <bool SECOND>
-__device__ __forceinline__ bool probe_and_verify(const NetArgs & a, const uint64_t * sw, uint32_t slen,
-                                                 uint32_t snw, uint32_t seed, uint64_t seed_abundance,
-                                                 uint64_t h, uint32_t code, uint32_t & out_amp,
-                                                 int window_filter = 0, uint32_t win_word = 0, uint32_t nwin = 1) {
-  const uint32_t type = code & 3u;
-  const uint32_t base = (code >> 2) & 3u;
-  const uint32_t pos = code >> 4;
-  const uint32_t vlen = (type == 0u) ? slen : (type == 1u ? slen - 1u : slen + 1u);
-  const uint32_t vnw = (vlen + 31u) >> 5;
-  uint64_t idx = (h >> 32) & a.tmask;
-  for (;;) {
-    const swa_slot s = a.table[idx];
-    if (s.amp == kEmpty) { return false; }
-    if (s.hash == h) {
-      const uint32_t amp = s.amp;
-      const uint32_t alen = a.seqlen[amp];
-      bool allowed;
-      if (SECOND) { const uint32_t hlen = a.seqlen[seed]; allowed = min(hlen, alen) < a.fast_min_len || max(hlen, alen) > a.fast_max_len; }
-      else { allowed = amp != seed && (a.no_cluster_breaking != 0 || seed_abundance >= a.abundance[amp]); }
-      if (allowed && alen == vlen) {
-        const uint64_t * y = a.seqs + a.seq_off[amp];
-        // window_filter 1: only neighbours that share the seed's prefix-side window, 2: only those that do not
-        bool shared = true;                                    // the seed's prefix-side window, in the neighbour
-        for (uint32_t w = 0; w < nwin; ++w) { shared = shared && y[win_word + w] == sw[win_word + w]; }
-        bool same = window_filter == 0 || (window_filter == 1 ? shared : !shared);
-        for (uint32_t w = 0; w < vnw; ++w) {
-          same = same && (swa_variant_word(sw, snw, type, pos, base, w) == y[w]);
-        }
-        if (same) {
-          out_amp = amp;
-          return true;
-        }
-      }
-    }
-    idx = (idx + 1) & a.tmask;
-  }
-}
-
-// MODE 0: the d=1 network (query = amplicon first+k of the database).
-// MODE 1: fastidious second level (query k = the microvariant tasks[k] of a heavy amplicon;
-//         every verified light amplicon gets graft_cand = min(heavy id), algod1.cc:244-258).
-template <bool ZLDS, int MODE>
-__global__ __launch_bounds__(kThreads) void k_d1_probe(const NetArgs a) {
-  extern __shared__ uint64_t lds[];
-  // LDS carve-up (all 8-byte aligned)
-  uint64_t * zob_lds = lds;
-  uint64_t * pat = lds + (ZLDS ? 4u * a.zlen : 0u);
-  uint64_t * wave_base = pat + 1024;
-  const uint32_t seed_words = a.maxwords + 2u;               // + zero padding words
-  const uint32_t per_wave = seed_words + kQueueCap + kQueueCap / 2;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  uint64_t * sw = wave_base + (size_t)wave * per_wave;       // staged query words
-  uint64_t * qh = sw + seed_words;                           // queue: hashes
-  uint32_t * qc = reinterpret_cast<uint32_t *>(qh + kQueueCap);   // queue: edit codes
-
-  if (ZLDS) {
-    for (uint32_t i = threadIdx.x; i < 4u * a.zlen; i += kThreads) { zob_lds[i] = a.zobrist[i]; }
-  }
-  for (uint32_t i = threadIdx.x; i < 1024u; i += kThreads) { pat[i] = a.patterns[i]; }
-  __syncthreads();
-  const uint64_t * zob = ZLDS ? zob_lds : a.zobrist;
-
-  unsigned long long cand_total = 0;                         // MODE 1: graft candidates found by this wave
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  // this wave's private output segment (a single shared edge counter costs one contended
-  // returning atomic per query — measured: ~88 atomics/us on one address bound the kernel)
-  const uint32_t gwave = blockIdx.x * kWaves + wave;
-  uint32_t seg_at = (MODE == 1) ? 0u : a.seg_fill[gwave];
-
-  const uint32_t nwaves = gridDim.x * kWaves;
-  const uint32_t nqueries = (MODE == 2) ? *a.fallback_count : a.count;
-  for (uint32_t k = blockIdx.x * kWaves + wave; k < nqueries; k += nwaves) {
-    uint32_t seed, len, nw;
-    uint32_t range = 0;                                      // MODE 2: 0 all positions, 1 p >= 32, 2 p < 32
-    uint64_t seed_ab = 0;
-    if (MODE == 0 || MODE == 2) {
-      if (MODE == 2) { seed = a.fallback[k].seed; range = a.fallback[k].range; }
-      else {
-        seed = a.first + k;
-        if (a.owner_world > 1u && seed % a.owner_world != a.owner_rank) { continue; }   // another rank's seed (wave-uniform)
-      }
-      len = a.seqlen[seed];
-      nw = (len + 31u) >> 5;
-      const uint64_t * gs = a.seqs + a.seq_off[seed];
-      seed_ab = a.abundance[seed];
-      for (uint32_t w = lane; w < nw + 2u; w += 64u) { sw[w] = (w < nw) ? gs[w] : 0ull; }
-    } else {
-      // materialise the first-level microvariant (generate_variant_sequence, variants.cc:78-115)
-      const swa_task t = a.tasks[k];
-      seed = t.heavy;
-      const uint32_t hlen = a.seqlen[seed];
-      const uint32_t hnw = (hlen + 31u) >> 5;
-      const uint64_t * gs = a.seqs + a.seq_off[seed];
-      const uint32_t type = t.code & 3u;
-      len = (type == 0u) ? hlen : (type == 1u ? hlen - 1u : hlen + 1u);
-      nw = (len + 31u) >> 5;
-      for (uint32_t w = lane; w < nw + 2u; w += 64u) {
-        sw[w] = (w < nw) ? swa_variant_word(gs, hnw, type, t.code >> 4, (t.code >> 2) & 3u, w) : 0ull;
-      }
-    }
-    wave_lds_sync();
-
-    uint32_t qn = 0;          // queue fill (wave uniform)
-    uint32_t row = 0;         // hits of this query (wave uniform)
-
-    auto drain = [&](uint32_t cnt) {
-      bool hit = false;
-      uint32_t amp = 0;
-      if ((uint32_t)lane < cnt) {
-        // MODE 2: a seed's two halves are divided by the prefix-side window itself, as the pair kernels divide them — range 1
-        // keeps only neighbours that share it, range 2 only those that do not.  (By position alone the halves overlap: a
-        // deletion at position 31, or inside a run that ends there, is listed at a position >= pb AND changes the window.)
-        const int wf = MODE != 2 ? 0 : (int)range;
-        hit = probe_and_verify<MODE == 1>(a, sw, len, nw, seed, seed_ab, qh[lane], qc[lane], amp, wf, a.win_word, MODE == 2 ? a.anchor_w / 32u : 1u);
-      }
-      const uint64_t hm = __ballot(hit);
-      if (hm != 0ull) {
-        const uint32_t nh = (uint32_t)__popcll(hm);
-        if (MODE == 0 || MODE == 2) {
-          if (hit) {
-            const uint64_t at = (uint64_t)seg_at + (uint64_t)__popcll(hm & lane_lt);
-            if (at < a.seg_cap) { a.edges[(uint64_t)gwave * a.seg_cap + at] = ((uint64_t)seed << 32) | amp; }
-          }
-          seg_at += nh;
-        } else {
-          if (hit) { atomicMin(&a.graft[amp], seed); }
-        }
-        row += nh;
-      }
-    };
-
-    auto enqueue = [&](bool pass, uint64_t h, uint32_t code) {
-      const uint64_t m = __ballot(pass);
-      if (m == 0ull) { return; }
-      if (pass) {
-        const uint32_t at = qn + (uint32_t)__popcll(m & lane_lt);
-        qh[at] = h;
-        qc[at] = code;
-      }
-      qn += (uint32_t)__popcll(m);
-      if (qn >= 64u) {
-        wave_lds_sync();
-        drain(64u);
-        const uint32_t rest = qn - 64u;
-        uint64_t th = 0;
-        uint32_t tc = 0;
-        if ((uint32_t)lane < rest) { th = qh[64 + lane]; tc = qc[64 + lane]; }
-        __builtin_amdgcn_wave_barrier();
-        if ((uint32_t)lane < rest) { qh[lane] = th; qc[lane] = tc; }
-        qn = rest;
-      }
-    };
-
-    // 8 Bloom-word loads in flight per lane, then test + compact
-    auto probe_slots = [&](const auto & s) {
-      uint64_t word[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        word[i] = s.ok[i] ? a.bloom[(s.hs[i] >> 10) & a.bmask] : ~0ull;
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool pass = s.ok[i] && ((word[i] & pat[s.hs[i] & 1023u]) == 0ull);   // bloompat.cc:68-71
-        enqueue(pass, s.hs[i], s.code[i]);
-      }
-    };
-    if (MODE == 2) {
-      const swa_aux ax = a.aux[seed];
-      const bool by_position = a.window_mode == 0u;           // (window mode: every position, the hits are filtered)
-      const uint32_t pb = by_position && range == 1u ? ax.pb : 0u;   // range 1 = what the prefix pass would have done (swa_aux::pb)
-      const uint32_t pe = by_position && range == 2u ? a.anchor_w : len + 1u;
-      const uint32_t erange = by_position ? range : 0u;       // (`range` itself still selects the filter in drain())
-      enumerate_range(sw, len, zob, lane, pb, pe < len + 1u ? pe : len + 1u, ax.h, erange == 1u ? ax.a32 : 0ull,
-                      erange == 1u ? (ax.dall ^ ax.d32) : ax.dall, erange == 1u ? (ax.iall ^ ax.i32) : ax.iall,
-                      probe_slots);
-    } else {
-      (void)enumerate_variants(sw, len, zob, lane, probe_slots);
-    }
-    if (qn > 0u) {
-      wave_lds_sync();
-      drain(qn);
-    }
-    if (MODE == 1) { cand_total += row; }
-    __builtin_amdgcn_wave_barrier();
-  }
-  if (MODE != 1 && lane == 0) { a.seg_fill[gwave] = seg_at; }
-  if (MODE == 1 && lane == 0 && cand_total != 0ull) { atomicAdd(a.cand_counter, cand_total); }
-}
+#include "d1_probe.inc"   // enumerate_variants / enumerate_range, k_d1_probe: MODE 0 and MODE 2 are launched (and instantiated) here
 
 #include "d1_anchor.inc"
-
-// ---- fastidious first level (algod1.cc:495-518 mark_light_var, 398-450 check_heavy_var) ---
-struct FlexArgs {
-  const uint64_t * seqs;
-  const uint64_t * seq_off;
-  const uint32_t * seqlen;
-  const uint64_t * zobrist;
-  uint32_t zlen;
-  uint32_t maxwords;
-  unsigned long long * fbits;     // the flexible Bloom, inverted polarity (bloomflex.cc:61-70)
-  uint64_t fsize;                 // words
-  double finv;                    // 1.0 / fsize
-  const uint64_t * fpat;          // 65536 patterns with k bits
-  const uint32_t * list;          // amplicon ids to process
-  uint32_t count;
-  swa_task * tasks;               // PASS 1: surviving (heavy, variant) pairs
-  unsigned long long * task_counter;
-  uint64_t task_cap;
-  unsigned long long * variant_counter;
-};
-
-// (h >> 16) % fsize for an arbitrary (non power-of-two) fsize: bloomflex.cc:43-49.
-// x < 2^48 is exact in a double, so the quotient estimate is off by at most one.
-__device__ __forceinline__ uint64_t flex_word(uint64_t h, uint64_t fsize, double finv) {
-  const uint64_t x = h >> 16;
-  uint64_t q = (uint64_t)((double)x * finv);
-  int64_t r = (int64_t)(x - q * fsize);
-  if (r < 0) { r += (int64_t)fsize; }
-  else if ((uint64_t)r >= fsize) { r -= (int64_t)fsize; }
-  return (uint64_t)r;
-}
-
-// PASS 0: clear the pattern bits of every microvariant of a light amplicon.
-// PASS 1: test every microvariant of a heavy amplicon, emit the survivors as tasks.
-template <bool ZLDS, int PASS>
-__global__ __launch_bounds__(kThreads) void k_d1_flex(const FlexArgs a) {
-  extern __shared__ uint64_t lds[];
-  uint64_t * zob_lds = lds;
-  uint64_t * wave_base = lds + (ZLDS ? 4u * a.zlen : 0u);
-  const uint32_t seed_words = a.maxwords + 2u;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  uint64_t * sw = wave_base + (size_t)wave * seed_words;
-  // PASS 1 stages its surviving tasks in LDS and reserves space in the global task list in
-  // bulk: one returning atomic per ~200 tasks instead of one per ballot (a single address
-  // sustains only ~88 atomics/us, which bound this kernel)
-  constexpr uint32_t kStage = 256;
-  swa_task * stage = reinterpret_cast<swa_task *>(wave_base + (size_t)kWaves * seed_words) + (size_t)wave * kStage;
-  uint32_t nstage = 0;
-  if (ZLDS) {
-    for (uint32_t i = threadIdx.x; i < 4u * a.zlen; i += kThreads) { zob_lds[i] = a.zobrist[i]; }
-    __syncthreads();
-  }
-  const uint64_t * zob = ZLDS ? zob_lds : a.zobrist;
-  const uint64_t lane_lt = (1ull << lane) - 1ull;
-  unsigned long long nvar = 0;
-  auto flush = [&]() {
-    wave_lds_sync();
-    unsigned long long base = 0;
-    if (lane == 0) { base = atomicAdd(a.task_counter, (unsigned long long)nstage); }
-    base = swa_shfl_u64(base, 0);
-    for (uint32_t i = lane; i < nstage; i += 64u) {
-      if (base + i < a.task_cap) { a.tasks[base + i] = stage[i]; }
-    }
-    nstage = 0;
-    wave_lds_sync();
-  };
-  const uint32_t nwaves = gridDim.x * kWaves;
-  for (uint32_t k = blockIdx.x * kWaves + wave; k < a.count; k += nwaves) {
-    const uint32_t amp = a.list[k];
-    const uint32_t len = a.seqlen[amp];
-    const uint32_t nw = (len + 31u) >> 5;
-    const uint64_t * gs = a.seqs + a.seq_off[amp];
-    for (uint32_t w = lane; w < nw + 2u; w += 64u) { sw[w] = (w < nw) ? gs[w] : 0ull; }
-    wave_lds_sync();
-    (void)enumerate_variants(sw, len, zob, lane, [&](const Slots & s) {
-      if (PASS == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          if (s.ok[i]) {
-            atomicAnd(&a.fbits[flex_word(s.hs[i], a.fsize, a.finv)], ~(unsigned long long)a.fpat[s.hs[i] & 0xFFFFu]);
-          }
-          nvar += (unsigned long long)__popcll(__ballot(s.ok[i]));
-        }
-      } else {
-        uint64_t word[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          word[i] = s.ok[i] ? (uint64_t)a.fbits[flex_word(s.hs[i], a.fsize, a.finv)] : ~0ull;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const bool pass = s.ok[i] && ((word[i] & a.fpat[s.hs[i] & 0xFFFFu]) == 0ull);   // bloomflex_get
-          nvar += (unsigned long long)__popcll(__ballot(s.ok[i]));
-          const uint64_t m = __ballot(pass);
-          if (m != 0ull) {
-            if (pass) {
-              swa_task t;
-              t.hash = s.hs[i]; t.heavy = amp; t.code = s.code[i];
-              stage[nstage + (uint32_t)__popcll(m & lane_lt)] = t;
-            }
-            nstage += (uint32_t)__popcll(m);
-            if (nstage > kStage - 64u) { flush(); }
-          }
-        }
-      }
-    });
-    __builtin_amdgcn_wave_barrier();
-  }
-  if (PASS == 1 && nstage != 0u) { flush(); }
-  if (lane == 0 && nvar != 0ull) { atomicAdd(a.variant_counter, nvar); }
-}
 
 // ---- exclusive scans (a workgroup's: d1_stream.inc too; the fastidious pass's offsets), the per-wave segments' totals and flat list ------
 constexpr int kScanItems = 8;
@@ -619,7 +179,7 @@ __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t * 
   return wave_off + incl - v;
 }
 
-// the fastidious groups' member offsets: exclusive scan of counts[0, n) into 64-bit offsets[0, n], three launches
+// swa_scan_offsets (the fastidious groups' member offsets): exclusive scan of counts[0, n) into 64-bit offsets[0, n], three launches
 __global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const uint32_t * __restrict__ counts, uint32_t n,
                                                            uint64_t * __restrict__ tile_sums) {
   __shared__ uint64_t smem[4];
@@ -735,10 +295,11 @@ __global__ __launch_bounds__(256) void k_seg_compact(const uint64_t * __restrict
   }
 }
 
-#include "d1_fast.inc"
 #include "d1_stream.inc"
 
-int grid_for(const swa_ctx * ctx, uint64_t items, int per_block, int max_per_cu) {
+}  // namespace
+
+int swa_grid_for(const swa_ctx * ctx, uint64_t items, int per_block, int max_per_cu) {
   uint64_t blocks = (items + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)ctx->num_cus * max_per_cu;
   if (blocks > cap) { blocks = cap; }
@@ -746,21 +307,31 @@ int grid_for(const swa_ctx * ctx, uint64_t items, int per_block, int max_per_cu)
   return (int)blocks;
 }
 
-}  // namespace
-
 // loads this translation unit's code object (see swa_ctx_warmup): an empty launch
 void swa_warm_d1(swa_ctx * ctx) {
   hipLaunchKernelGGL(k_table_clear, dim3(1), dim3(64), 0, ctx->stream, static_cast<swa_slot *>(nullptr), (uint64_t)0,
                      static_cast<uint64_t *>(nullptr), (uint64_t)0);
 }
 
-// shared with fastidious.hip
+// (the member offsets of the --fastidious groups: its only caller is the pair route of fastidious.hip)
+int swa_scan_offsets(swa_ctx * ctx, const uint32_t * counts, uint32_t n, uint64_t * offsets) {
+  static_assert(kScanTile == (int)kScanOffsetsTile, "swa_scan_offsets: the tile the caller sized d_scan_tmp for");
+  const uint32_t tiles = (uint32_t)(((uint64_t)n + kScanTile - 1) / kScanTile);
+  auto * sums = static_cast<uint64_t *>(ctx->d_scan_tmp.ptr);
+  hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, counts, n, sums);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, ctx->stream, sums, tiles);
+  hipLaunchKernelGGL(k_scan_apply, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, counts, n, sums, offsets);
+  return SWA_OK;
+}
+
+// d_table and d_bloom cleared and filled again: with all amplicons (swa_ensure_full_index) or with those a byte array marks
+// (the light amplicons of the Bloom route's bands: fastidious.hip)
 int swa_d1_rebuild_table(swa_ctx * ctx, const uint8_t * d_is_member) {
   const uint32_t n = ctx->db.n;
-  hipLaunchKernelGGL(k_table_clear, dim3(grid_for(ctx, ctx->ix.table_size, 256, 8)), dim3(256), 0, ctx->stream,
+  hipLaunchKernelGGL(k_table_clear, dim3(swa_grid_for(ctx, ctx->ix.table_size, 256, 8)), dim3(256), 0, ctx->stream,
                      static_cast<swa_slot *>(ctx->d_table.ptr), ctx->ix.table_size,
                      static_cast<uint64_t *>(ctx->d_bloom.ptr), ctx->ix.bloom_words);
-  hipLaunchKernelGGL(k_table_insert, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream,
+  hipLaunchKernelGGL(k_table_insert, dim3(swa_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream,
                      static_cast<const uint64_t *>(ctx->d_seqhash.ptr), n, d_is_member,
                      static_cast<swa_slot *>(ctx->d_table.ptr), ctx->ix.table_size - 1,
                      static_cast<unsigned long long *>(ctx->d_bloom.ptr), ctx->ix.bloom_words - 1,
@@ -807,7 +378,7 @@ static int ensure_db_lengths(swa_ctx * ctx) {
   SWA_TRY(swa_reserve(ctx, ctx->d_rank_tmp, std::max<size_t>(ctx->d_rank_tmp.bytes, 64)));
   auto * out = static_cast<uint32_t *>(ctx->d_rank_tmp.ptr);
   SWA_HIP(ctx, hipMemsetAsync(out, 0, 8 * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL(k_db_lengths, dim3(grid_for(ctx, ctx->db.n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, out);
+  hipLaunchKernelGGL(k_db_lengths, dim3(swa_grid_for(ctx, ctx->db.n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, out);
   uint32_t host[8] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -844,7 +415,7 @@ static ListRegions list_regions(const swa_ctx * ctx, uint64_t * total_items) {
 
 // abundance rank of every amplicon (k_abundance_rank: three streaming passes); kFlagUnordered is raised when the database is
 // not in abundance order
-static int launch_abundance_rank(swa_ctx * ctx) {
+int swa_launch_abundance_rank(swa_ctx * ctx) {
   if (ctx->up.d1.rank_ready) {                                    // (a fact of the uploaded database: once per upload)
     if (ctx->up.d1.db_unordered) { SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->flags + kFlagUnordered, 1, sizeof(uint32_t), ctx->stream)); }
     return SWA_OK;
@@ -858,10 +429,10 @@ static int launch_abundance_rank(swa_ctx * ctx) {
   SWA_TRY(swa_reserve(ctx, ctx->d_rank_tmp, uint64_t(tiles) * sizeof(uint32_t)));
   auto * rank = static_cast<uint32_t *>(ctx->d_arank.ptr);
   auto * tile_last = static_cast<uint32_t *>(ctx->d_rank_tmp.ptr);
-  hipLaunchKernelGGL(k_abundance_rank, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.abundance, n, rank,
+  hipLaunchKernelGGL(k_abundance_rank, dim3(swa_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.abundance, n, rank,
                      swa_status(ctx)->flags, tile_last);
   hipLaunchKernelGGL(k_abundance_rank_carry, dim3(1), dim3(256), 0, ctx->stream, tile_last, tiles);
-  hipLaunchKernelGGL(k_abundance_rank_fill, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, n, rank, tile_last);
+  hipLaunchKernelGGL(k_abundance_rank_fill, dim3(swa_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, n, rank, tile_last);
   return SWA_OK;
 }
 
@@ -930,7 +501,7 @@ static int clear_launch(swa_ctx * ctx, const ClearList & c) {
   uint64_t most = 0;
   for (uint32_t k = 0; k < c.n; ++k) { most = std::max(most, c.words[k]); }
   if (c.n == 0 || most == 0) { return SWA_OK; }
-  hipLaunchKernelGGL(k_clear_many, dim3(grid_for(ctx, most, 256, 8)), dim3(256), 0, ctx->stream, c);
+  hipLaunchKernelGGL(k_clear_many, dim3(swa_grid_for(ctx, most, 256, 8)), dim3(256), 0, ctx->stream, c);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
 }
@@ -1022,7 +593,7 @@ static int run_partition(swa_ctx * ctx, PartJob & j) {
 }
 
 // the amplicon lines of the uploaded database (once per upload; needs the abundance ranks)
-static int ensure_lines(swa_ctx * ctx) {
+int swa_ensure_lines(swa_ctx * ctx) {
   const uint32_t lq = line_quads_for(ctx);
   if (ctx->up.d1.lines_ready && ctx->up.d1.lines_quads == lq) { return SWA_OK; }
   const uint32_t n = ctx->db.n;
@@ -1031,7 +602,7 @@ static int ensure_lines(swa_ctx * ctx) {
   const auto * rank = static_cast<const uint32_t *>(ctx->d_arank.ptr);
   SWA_HIP(ctx, hipMemsetAsync(reinterpret_cast<uint8_t *>(lines) + (uint64_t)n * lq * 16u, 0, 64, ctx->stream));
   swa_t0(ctx, kTimeLines);
-  const dim3 grid(grid_for(ctx, n, 256, 8));
+  const dim3 grid(swa_grid_for(ctx, n, 256, 8));
   if (lq == 4u) { hipLaunchKernelGGL(k_lines_build<4>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
   else if (lq == 8u) { hipLaunchKernelGGL(k_lines_build<8>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
   else { hipLaunchKernelGGL(k_lines_build<16>, grid, dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, rank, n, lines); }
@@ -1068,7 +639,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
   swa_lap(ctx, "(build starts)");
   SWA_TRY(ensure_db_lengths(ctx));
   swa_lap(ctx, "db lengths");
-  SWA_TRY(ensure_lines(ctx));
+  SWA_TRY(swa_ensure_lines(ctx));
   swa_lap(ctx, "amplicon lines");
   const uint32_t lq = ctx->up.d1.lines_quads;
   uint64_t item_room = 0;
@@ -1119,7 +690,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
     clear_add(c, st->counters, sizeof(st->counters));
     if (clear_head) {
       // the head of the status block for a new index: the flags — but kFlagUnordered, which the abundance ranks in front of
-      // this build have just set or left at 0 (launch_abundance_rank) —, the stats, the guard's counters up to its second
+      // this build have just set or left at 0 (swa_launch_abundance_rank) —, the stats, the guard's counters up to its second
       // opinion.  (A retry, or the build of a network call, comes with its flags cleared by its caller and clears the
       // guard's index counters alone.)
       static_assert(kFlagDuplicates == 0 && kFlagUnordered == 1, "status block: the flags around kFlagUnordered");
@@ -1185,7 +756,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
     j.hist0_done = true;
     j.tiles0_done = true;
   } else {
-    const dim3 kgrid((unsigned)grid_for(ctx, records, 256, 8), routed ? 2u : 1u);
+    const dim3 kgrid((unsigned)swa_grid_for(ctx, records, 256, 8), routed ? 2u : 1u);
     hipLaunchKernelGGL(k_keys<false>, kgrid, dim3(256), 0, ctx->stream, k);
   }
   swa_t1(ctx, kTimeKeys);
@@ -1223,11 +794,11 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
     for (int i = 0; i < 2; ++i) { gd.list[i] = k.list[i]; gd.list_count[i] = routed ? route.m[i] : 0; gd.list_rec[i] = by_rec ? route.rec[i] : nullptr; }
     gd.owner_rank = k.owner_rank; gd.owner_world = k.owner_world; gd.win_a = win_a; gd.win_b = win_b; gd.nwin = k.nwin;
     gd.out = guard + kGuardKeysDb;
-    hipLaunchKernelGGL(k_guard_db, dim3((unsigned)grid_for(ctx, records, 256, 8), routed ? 2u : 1u), dim3(256), 0, ctx->stream, gd);
+    hipLaunchKernelGGL(k_guard_db, dim3((unsigned)swa_grid_for(ctx, records, 256, 8), routed ? 2u : 1u), dim3(256), 0, ctx->stream, gd);
     GuardRecArgs gr{};
     for (int i = 0; i < 2; ++i) { gr.rec[i] = j.out[i]; gr.total[i] = j.total[i]; }
     gr.out = guard + kGuardKeysRec;
-    hipLaunchKernelGGL(k_guard_records, dim3((unsigned)grid_for(ctx, records, 256, 8), 2u), dim3(256), 0, ctx->stream, gr);
+    hipLaunchKernelGGL(k_guard_records, dim3((unsigned)swa_grid_for(ctx, records, 256, 8), 2u), dim3(256), 0, ctx->stream, gr);
     ctx->up.d1.guard_keys_pending = true;
   }
 
@@ -1527,7 +1098,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   // too short, no oversized group — and what holds for the whole database holds for every part of it)
   const bool use_member_table = ctx->ix.member_index && !ctx->ix.full_index;
   if (ctx->ix.full_index || ctx->ix.member_index) {
-    hipLaunchKernelGGL(k_stream_fallback, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, first, count,
+    hipLaunchKernelGGL(k_stream_fallback, dim3(swa_grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, first, count,
                        static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr), static_cast<swa_fallback *>(ctx->d_afallback.ptr), acounters + kCounterFallback,
                        ctx->owner_rank, ctx->owner_world, ctx->db.seqs, ctx->db.seq_off, anchor_minlen(ctx));
   }
@@ -1552,7 +1123,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   f.window_mode = window_mode ? 1u : 0u; f.win_word = ctx->ix.anchor_a / 32u; f.anchor_w = ctx->ix.anchor_w;
   const size_t flds = sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + 1024ull +
                                           kWaves * ((size_t)(maxwords + 2u) + kQueueCap + kQueueCap / 2));
-  const int fgrid = grid_for(ctx, count, kWaves, 8);
+  const int fgrid = swa_grid_for(ctx, count, kWaves, 8);
   // (a rank that built only its owned groups has no table: by construction its fallback list is
   // empty — network_run checks the count and builds the full index if that ever fails to hold)
   if (!ctx->ix.full_index && !ctx->ix.member_index) { /* nothing to probe against */ }
@@ -1564,7 +1135,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
 }
 
 // Zobrist table in HBM (it only depends on its length: uploaded once) + room for the hashes
-static int prepare_hashing(swa_ctx * ctx) {
+int swa_prepare_hashing(swa_ctx * ctx) {
   const uint32_t n = ctx->db.n;
   ctx->zobrist_len = ctx->db.longest + 2;                  // db.cc:652-653 (sequence part)
   SWA_TRY(swa_reserve(ctx, ctx->d_seqhash, uint64_t(n) * sizeof(uint64_t)));
@@ -1586,7 +1157,7 @@ static int launch_seqhash(swa_ctx * ctx, const uint8_t * only = nullptr) {
   const size_t zbytes = 4ull * ctx->zobrist_len * sizeof(uint64_t);
   const bool zlds = zbytes <= kMaxZobristLds;
   swa_t0(ctx, kTimeSeqhash);
-  const int hgrid = grid_for(ctx, n, 256, 8);
+  const int hgrid = swa_grid_for(ctx, n, 256, 8);
   if (zlds) {
     hipLaunchKernelGGL(k_seqhash<true>, dim3(hgrid), dim3(256), zbytes, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                        ctx->db.seqlen, static_cast<const uint64_t *>(ctx->d_zobrist.ptr), ctx->zobrist_len, n,
@@ -1604,7 +1175,7 @@ static int launch_seqhash(swa_ctx * ctx, const uint8_t * only = nullptr) {
 // Zobrist table + per-amplicon sequence hashes (src/db.cc:761, src/zobrist.cc:89-112) and the
 // anchored-index metadata; shared by the d = 1 index and the d = 0 dereplication
 int swa_hash_sequences(swa_ctx * ctx) {
-  SWA_TRY(prepare_hashing(ctx));
+  SWA_TRY(swa_prepare_hashing(ctx));
   return launch_seqhash(ctx);
 }
 
@@ -1612,7 +1183,7 @@ int swa_hash_sequences(swa_ctx * ctx) {
 // src/bloompat.cc): what the plain kernel, the fastidious pass and the debug readers work on.
 // Always built by a single-GPU index build; a rank that serves only the anchor groups it owns
 // builds it on demand (rarely: see build_owned_index).
-static int ensure_full_index(swa_ctx * ctx) {
+int swa_ensure_full_index(swa_ctx * ctx) {
   if (ctx->ix.full_index) { return SWA_OK; }
   SWA_TRY(swa_reserve(ctx, ctx->d_table, ctx->ix.table_size * sizeof(swa_slot)));
   SWA_TRY(swa_reserve(ctx, ctx->d_bloom, ctx->ix.bloom_words * sizeof(uint64_t)));
@@ -1648,9 +1219,9 @@ static int choose_anchor_windows(swa_ctx * ctx) {
   uint32_t * stats = counts + slots;                         // [0..4) too short, [4..8) mass
   SWA_HIP(ctx, hipMemsetAsync(keys, 0xFF, slots * sizeof(uint64_t), ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(counts, 0, (slots + 16) * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL(k_anchor_sample, dim3(grid_for(ctx, samples, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
+  hipLaunchKernelGGL(k_anchor_sample, dim3(swa_grid_for(ctx, samples, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                      ctx->db.seqlen, n, stride, keys, counts, stats, shortest, max_nwin);
-  hipLaunchKernelGGL(k_sample_mass, dim3(grid_for(ctx, slots, 256, 8)), dim3(256), 0, ctx->stream, counts, stride, stats + 4);
+  hipLaunchKernelGGL(k_sample_mass, dim3(swa_grid_for(ctx, slots, 256, 8)), dim3(256), 0, ctx->stream, counts, stride, stats + 4);
   uint32_t host[8] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host, stats, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1691,7 +1262,7 @@ static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   ctx->ix.member_index = false;
   const uint32_t n = ctx->db.n;
   // Zobrist hashes + the XOR streams of the members (k_seqhash: nobody else is inserted, probed for or enumerated)
-  SWA_TRY(prepare_hashing(ctx));
+  SWA_TRY(swa_prepare_hashing(ctx));
   SWA_TRY(launch_seqhash(ctx, static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr)));
   uint64_t slots = 1024;
   while (slots < 2ull * ctx->ix.over_mass) { slots <<= 1; }
@@ -1701,14 +1272,14 @@ static int build_member_index(swa_ctx * ctx, uint32_t dup_first, uint32_t dup_co
   auto * table = static_cast<swa_slot *>(ctx->d_stream[kSbMTable].ptr);
   auto * bloom = static_cast<uint64_t *>(ctx->d_stream[kSbMBloom].ptr);
   swa_t0(ctx, kTimeTable);
-  hipLaunchKernelGGL(k_table_clear, dim3(grid_for(ctx, slots, 256, 8)), dim3(256), 0, ctx->stream, table, slots, bloom, words);
-  hipLaunchKernelGGL(k_table_insert, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_seqhash.ptr), n,
+  hipLaunchKernelGGL(k_table_clear, dim3(swa_grid_for(ctx, slots, 256, 8)), dim3(256), 0, ctx->stream, table, slots, bloom, words);
+  hipLaunchKernelGGL(k_table_insert, dim3(swa_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_seqhash.ptr), n,
                      static_cast<const uint8_t *>(ctx->d_stream[kSbOver].ptr), table, slots - 1, reinterpret_cast<unsigned long long *>(bloom), words - 1,
                      static_cast<const uint64_t *>(ctx->d_patterns.ptr));
   swa_t1(ctx, kTimeTable);
   swa_t0(ctx, kTimeDupCheck);
   if (dup_count != 0) {
-    hipLaunchKernelGGL(k_dup_check, dim3(grid_for(ctx, dup_count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen,
+    hipLaunchKernelGGL(k_dup_check, dim3(swa_grid_for(ctx, dup_count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen,
                        static_cast<const uint64_t *>(ctx->d_seqhash.ptr), dup_first, dup_count, table, slots - 1, swa_status(ctx)->flags + kFlagDuplicates);
   }
   swa_t1(ctx, kTimeDupCheck);
@@ -1730,7 +1301,7 @@ static int build_owned_index(swa_ctx * ctx, const RouteLists & route, bool * nee
   swa_lap(ctx, "(owned index starts)");
   // (no Zobrist table, no hash / XOR-stream arrays here: the pair route needs none of them — 240 MB of HBM at 10 M and an
   // upload with its synchronisation per build; the member table and the database-wide table prepare them when they are built)
-  SWA_TRY(launch_abundance_rank(ctx));
+  SWA_TRY(swa_launch_abundance_rank(ctx));
   swa_lap(ctx, "abundance ranks");
   // streaming build (d1_stream.inc): keys, partition, groups + work lists + identical sequences, all in one go
   swa_t0(ctx, kTimeIndex);
@@ -1854,10 +1425,10 @@ static int index_build(swa_ctx * ctx, uint32_t first, uint32_t count, const Rout
   }
   uint32_t flag = group_dups;
   if (!owned_ok) {
-    SWA_TRY(ensure_full_index(ctx));
+    SWA_TRY(swa_ensure_full_index(ctx));
     swa_t0(ctx, kTimeDupCheck);
     if (count > 0) {
-      hipLaunchKernelGGL(k_dup_check, dim3(grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
+      hipLaunchKernelGGL(k_dup_check, dim3(swa_grid_for(ctx, count, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
                          ctx->db.seqlen, static_cast<const uint64_t *>(ctx->d_seqhash.ptr), first, count,
                          static_cast<const swa_slot *>(ctx->d_table.ptr), ctx->ix.table_size - 1,
                          swa_status(ctx)->flags + kFlagDuplicates);
@@ -1865,7 +1436,7 @@ static int index_build(swa_ctx * ctx, uint32_t first, uint32_t count, const Rout
     SWA_HIP(ctx, hipGetLastError());
     swa_t1(ctx, kTimeDupCheck);
     if (ctx->ix.anchor_usable) {
-      SWA_TRY(launch_abundance_rank(ctx));
+      SWA_TRY(swa_launch_abundance_rank(ctx));
       SWA_HIP(ctx, hipGetLastError());
     }
     uint32_t flags[kFlagUnordered + 1] = {};                // duplicates, abundances not in descending order
@@ -1927,7 +1498,7 @@ static int launch_network(swa_ctx * ctx, int ncb, uint32_t first, uint32_t count
   SWA_HIP(ctx, hipMemsetAsync(swa_status(ctx)->stats, 0, sizeof(swa_status_block::stats), ctx->stream));
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const size_t lds = network_lds_bytes(ctx, zlds);
-  const int grid = grid_for(ctx, count, kWaves, 8);
+  const int grid = swa_grid_for(ctx, count, kWaves, 8);
   swa_t0(ctx, kTimeNetwork);
   if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a); }
   else { hipLaunchKernelGGL((k_d1_probe<false, 0>), dim3(grid), dim3(kThreads), lds, ctx->stream, a); }
@@ -2018,7 +1589,7 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       if (!(ctx->ix.anchor_ready && ctx->ix.stream_index)) {
         // (the streaming index serves any query range; it is rebuilt when the owner changed)
         swa_t0(ctx, kTimeIndex);
-        SWA_TRY(launch_abundance_rank(ctx));
+        SWA_TRY(swa_launch_abundance_rank(ctx));
         // (kFlagKeyOverflow .. kFlagShortest, what the streaming build raises: the previous owner's values must not survive
         // into this owner's build — kFlagUnserved is only ever set, kFlagOversized / kFlagOverMass accumulate)
         SWA_HIP(ctx, hipMemsetAsync(st->flags + kFlagKeyOverflow, 0, (kFlagsD1 - kFlagKeyOverflow) * sizeof(uint32_t), ctx->stream));
@@ -2032,13 +1603,13 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
           SWA_HIP(ctx, hipMemcpyAsync(fl, st->flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
           SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
           ctx->ix.member_index = false;
-          if (fl[kFlagUnserved] != 0 || fl[kFlagOversized] != 0) { SWA_TRY(ensure_full_index(ctx)); }
+          if (fl[kFlagUnserved] != 0 || fl[kFlagOversized] != 0) { SWA_TRY(swa_ensure_full_index(ctx)); }
         }
       }
       SWA_TRY(launch_network_anchored(ctx, no_cluster_breaking, first, count));
     }
     else {
-      SWA_TRY(ensure_full_index(ctx));
+      SWA_TRY(swa_ensure_full_index(ctx));
       SWA_TRY(launch_network(ctx, no_cluster_breaking, first, count));
     }
     const bool check_unserved = ctx->ix.anchor_usable && !ctx->ix.full_index && !ctx->ix.member_index;
@@ -2081,7 +1652,7 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
       continue;
     }
     if (check_unserved && unserved != 0) {                   // should not happen (build_owned_index looks for such seeds)
-      SWA_TRY(ensure_full_index(ctx));
+      SWA_TRY(swa_ensure_full_index(ctx));
       continue;
     }
     if (d_edge_list == nullptr && fullest <= ctx->seg_cap && n_edges > stream_link_cap) {
@@ -2250,7 +1821,7 @@ extern "C" int swa_d1_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count,
   SWA_TRY(ensure_anchor_windows(ctx));
   SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, (2ull * world + 1) * sizeof(uint32_t), ctx->stream));
   if (count != 0) {
-    hipLaunchKernelGGL(k_anchor_route, dim3(grid_for(ctx, (count + kRoutePerThread - 1) / kRoutePerThread, 256, 8)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(k_anchor_route, dim3(swa_grid_for(ctx, (count + kRoutePerThread - 1) / kRoutePerThread, 256, 8)), dim3(256), 0, ctx->stream,
                        ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, first, count, world, ctx->ix.anchor_a, ctx->ix.anchor_b, ctx->ix.anchor_w / 32u, d_ids, cap,
                        d_counts);
   }
@@ -2290,7 +1861,7 @@ extern "C" int swa_d1_route_slice_records(swa_ctx * ctx, uint32_t first, uint32_
   SWA_TRY(ensure_anchor_windows(ctx));
   SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, (2ull * world + 1) * sizeof(uint32_t), ctx->stream));
   if (count != 0) {
-    hipLaunchKernelGGL(k_anchor_route_records, dim3(grid_for(ctx, (count + 3) / 4, 256, 8)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(k_anchor_route_records, dim3(swa_grid_for(ctx, (count + 3) / 4, 256, 8)), dim3(256), 0, ctx->stream,
                        ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen, first, count, world, ctx->ix.anchor_a, ctx->ix.anchor_b, ctx->ix.anchor_w / 32u,
                        reinterpret_cast<unsigned long long *>(d_records), cap, d_counts);
   }
@@ -2391,7 +1962,7 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SWA_OK;
   }
-  SWA_TRY(ensure_full_index(ctx));
+  SWA_TRY(swa_ensure_full_index(ctx));
   const void * src = nullptr;
   size_t bytes = 0;
   switch (what) {
@@ -2419,502 +1990,5 @@ extern "C" int swa_d1_part_plan(const swa_ctx * ctx, uint32_t out[8]) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
   if (!ctx->ix.d1_ready || !ctx->ix.stream_index) { return SWA_E_ARG; }
   memcpy(out, ctx->ix.part_plan, sizeof(ctx->ix.part_plan));
-  return SWA_OK;
-}
-
-// ---- seam B2: the fastidious second pass --------------------------------------------------
-// algo_d1_run's fastidious branch (src/algod1.cc:1337-1467).  Two routes, chosen per PAIR of
-// (heavy, light) amplicons by the shorter of the two lengths (and, under SWA_FAST_LONG=split or =pairs, the longer):
-//   pair route  (both >= kFastMinLen, and both <= the cap under the split / pairs; d1_fast.inc): groups by shared
-//               32-nt windows, exact "within two edits" test per pair, exact |V1(h) ∩ V1(x)| per surviving pair;
-//   Bloom route (every other pair; the reference's own scheme): light-only table + Bloom,
-//               every microvariant of every light amplicon clears its k pattern bits in the flexible
-//               Bloom (atomicAnd: the reference's plain `&=` from many threads can lose a bit; -t 1 is
-//               the specification), every microvariant of every heavy amplicon is tested, survivors
-//               become 16-byte tasks, one wave per task re-runs the d=1 probe (k_d1_probe<MODE 1>).
-// Both end in atomicMin on graft_cand = add_graft_candidate (src/algod1.cc:244-258) and one counter.
-extern "C" int swa_d1_fastidious(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
-                                 uint32_t * graft_cand, uint64_t * counters) {
-  return swa_d1_fastidious_shard(ctx, is_light, light_nt, bloom_bits, 0, 1, graft_cand, counters);
-}
-
-// fc layout (d_fcounters, u64[16]): [0] light variants [1] heavy variants [2] candidates [3] tasks of the
-// current batch [4] variants of the current batch [5] pairs found [6] light amplicons of the Bloom route's bands
-// [7] heavy amplicons of the bands [8] nucleotides of those light amplicons [9] scratch [12, 14) k_fast_length_classes (u32[4])
-static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_heavy, uint64_t light_nt, uint32_t bloom_bits,
-                                  uint32_t pair_route_min_len, uint32_t pair_route_max_len, bool zlds) {
-  SWA_TRY(ensure_full_index(ctx));                           // hashes of every amplicon, room for the table
-  uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
-  if (k < 1) { k = 1; }
-  uint64_t m = light_nt * 7ull * bloom_bits;
-  if (m < 64) { m = 64; }
-  const uint64_t n_bytes = ((m - 1) / 8) + 1;
-  const uint64_t fsize = n_bytes >> 3;
-  std::vector<uint64_t> fpat;
-  swa_bloom_patterns(65536, k, fpat);
-  SWA_TRY(swa_reserve(ctx, ctx->d_bloomflex, fsize * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fpatterns, fpat.size() * sizeof(uint64_t)));
-  const uint64_t maxv = 7ull * ctx->db.longest + 4ull;
-  uint64_t task_cap = uint64_t(n_heavy) * maxv;
-  uint64_t cap_limit = (1ull << 30) / sizeof(swa_task);                  // 1 GiB of tasks
-  const char * env_cap = getenv("SWA_FAST_TASK_CAP");         // test hook: so many tasks instead (the floor below stays), exercise the batch loop
-  if (env_cap != nullptr && atoll(env_cap) > 0) { cap_limit = (uint64_t)atoll(env_cap); }
-  if (task_cap > cap_limit) { task_cap = cap_limit; }
-  if (task_cap < maxv) { task_cap = maxv; }                  // (what makes a batch of task_cap / maxv heavy amplicons unable to overflow)
-  ctx->fast_batches[2] = task_cap;
-  SWA_TRY(swa_reserve(ctx, ctx->d_queue, task_cap * sizeof(swa_task)));
-  SWA_HIP(ctx, hipMemcpyAsync(ctx->d_fpatterns.ptr, fpat.data(), fpat.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_bloomflex.ptr, 0xFF, fsize * sizeof(uint64_t), ctx->stream));
-  ctx->ix.table_repurposed();                                // the table now holds the light amplicons of the bands only
-  SWA_TRY(swa_d1_rebuild_table(ctx, static_cast<const uint8_t *>(ctx->d_light.ptr)));
-
-  auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
-  FlexArgs f{};
-  f.seqs = ctx->db.seqs; f.seq_off = ctx->db.seq_off; f.seqlen = ctx->db.seqlen;
-  f.zobrist = static_cast<const uint64_t *>(ctx->d_zobrist.ptr);
-  f.zlen = ctx->zobrist_len;
-  f.maxwords = (ctx->db.longest + 1u + 31u) >> 5;
-  f.fbits = static_cast<unsigned long long *>(ctx->d_bloomflex.ptr);
-  f.fsize = fsize;
-  f.finv = 1.0 / static_cast<double>(fsize);
-  f.fpat = static_cast<const uint64_t *>(ctx->d_fpatterns.ptr);
-  f.tasks = static_cast<swa_task *>(ctx->d_queue.ptr);
-  f.task_counter = fc + 3;
-  f.task_cap = task_cap;
-  const size_t flex_lds = sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + kWaves * (size_t)(f.maxwords + 2u)) +
-                          kWaves * 256 * sizeof(swa_task);
-  // light side
-  f.list = static_cast<const uint32_t *>(ctx->d_list_a.ptr);
-  f.count = n_light;
-  f.variant_counter = fc + 9;                                // (the reported totals are computed for all amplicons, not here)
-  {
-    const int grid = grid_for(ctx, f.count, kWaves, 8);
-    if (zlds) { hipLaunchKernelGGL((k_d1_flex<true, 0>), dim3(grid), dim3(kThreads), flex_lds, ctx->stream, f); }
-    else { hipLaunchKernelGGL((k_d1_flex<false, 0>), dim3(grid), dim3(kThreads), flex_lds, ctx->stream, f); }
-    SWA_HIP(ctx, hipGetLastError());
-  }
-  // heavy side
-  NetArgs a{};
-  a.seqs = ctx->db.seqs; a.seq_off = ctx->db.seq_off; a.seqlen = ctx->db.seqlen; a.abundance = ctx->db.abundance;
-  a.zobrist = f.zobrist; a.zlen = ctx->zobrist_len;
-  a.maxwords = f.maxwords;                                   // a microvariant can be one nt longer
-  a.table = static_cast<const swa_slot *>(ctx->d_table.ptr);
-  a.tmask = ctx->ix.table_size - 1;
-  a.bloom = static_cast<const uint64_t *>(ctx->d_bloom.ptr);
-  a.bmask = ctx->ix.bloom_words - 1;
-  a.patterns = static_cast<const uint64_t *>(ctx->d_patterns.ptr);
-  a.tasks = f.tasks;
-  a.graft = static_cast<uint32_t *>(ctx->d_graft.ptr);
-  a.cand_counter = fc + 2;
-  a.fast_min_len = pair_route_min_len;
-  a.fast_max_len = pair_route_max_len;
-  const size_t probe_lds = sizeof(uint64_t) * ((zlds ? 4ull * ctx->zobrist_len : 0ull) + 1024ull +
-                                               kWaves * ((size_t)(a.maxwords + 2u) + kQueueCap + kQueueCap / 2));
-  uint64_t done = 0;
-  uint64_t batch = task_cap / maxv;                          // cannot overflow
-  double rate = -1.0;                                        // observed tasks per heavy amplicon
-  while (done < n_heavy) {
-    uint64_t want = batch;
-    if (rate >= 0.0) {                                       // optimistic sizing, overflow is detected below
-      const double est = static_cast<double>(task_cap) / (4.0 * rate + 1.0);
-      want = est > 4.0e9 ? 4000000000ull : static_cast<uint64_t>(est);
-      if (want < batch) { want = batch; }
-    }
-    if (want > n_heavy - done) { want = n_heavy - done; }
-    SWA_HIP(ctx, hipMemsetAsync(fc + 3, 0, 2 * sizeof(uint64_t), ctx->stream));    // tasks + batch variants
-    f.list = static_cast<const uint32_t *>(ctx->d_list_b.ptr) + done;
-    f.count = static_cast<uint32_t>(want);
-    f.variant_counter = fc + 4;
-    const int grid = grid_for(ctx, f.count, kWaves, 8);
-    if (zlds) { hipLaunchKernelGGL((k_d1_flex<true, 1>), dim3(grid), dim3(kThreads), flex_lds, ctx->stream, f); }
-    else { hipLaunchKernelGGL((k_d1_flex<false, 1>), dim3(grid), dim3(kThreads), flex_lds, ctx->stream, f); }
-    SWA_HIP(ctx, hipGetLastError());
-    uint64_t got[2] = {0, 0};
-    SWA_HIP(ctx, hipMemcpyAsync(got, fc + 3, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-    SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rate = static_cast<double>(got[0]) / static_cast<double>(want);
-    ++ctx->fast_batches[0];
-    if (got[0] > task_cap) { ++ctx->fast_batches[1]; continue; }   // optimistic batch did not fit: redo it smaller
-    if (got[0] > ctx->fast_batches[3]) { ctx->fast_batches[3] = got[0]; }
-    if (got[0] > 0) {
-      a.count = static_cast<uint32_t>(got[0]);
-      const int pgrid = grid_for(ctx, a.count, kWaves, 8);
-      if (zlds) { hipLaunchKernelGGL((k_d1_probe<true, 1>), dim3(pgrid), dim3(kThreads), probe_lds, ctx->stream, a); }
-      else { hipLaunchKernelGGL((k_d1_probe<false, 1>), dim3(pgrid), dim3(kThreads), probe_lds, ctx->stream, a); }
-      SWA_HIP(ctx, hipGetLastError());
-    }
-    done += want;
-  }
-  return SWA_OK;
-}
-
-// Every choice of the pass, from the longest sequence of the database alone (and the switches): what
-// swa_d1_fastidious_shard launches and what swa_d1_fastidious_plan reports (host_tables.cpp: swa_fast_plan_for).
-//   longest      pair kernel             count kernel
-//   < 112        none: every pair on the Bloom route
-//   112 .. 159   k_fast_pairs_lines<5>   k_fast_count_sites<5>   (a microvariant of 160 nt still fits 5 words)
-//   160          k_fast_pairs_lines<5>   k_fast_count_sites<8>
-//   161 .. 255   k_fast_pairs_lines<8>   k_fast_count_sites<8>
-//   256          k_fast_pairs_lines<8>   k_fast_count, 4 waves x 4096 slots
-//   257 .. 389   k_fast_pairs_lines<13>  k_fast_count, 4 waves x 4096
-//   390 .. 416   k_fast_pairs_lines<13>  k_fast_count, 2 waves x 8192
-//   417 .. 779   k_fast_pairs            k_fast_count, 2 waves x 8192
-//   780 .. 1004  k_fast_pairs            k_fast_count, 1 wave x 16384
-//   >= 1005      none: k_fast_count's set no longer fits 160 KB; Bloom route, Zobrist table in LDS up to 3070 nt
-// SWA_FAST_LONG=split, longest > cap (= 1004, swa_fast_cap): the row of pair_longest, the longest sequence <= cap, with
-// k_fast_pairs as the pair kernel, for the pairs whose two lengths lie in [112, cap]; the Bloom route for every other pair.
-// SWA_FAST_LONG=pairs, longest > 1004: k_fast_pairs and k_fast_count_sites_words (4 / 2 / 1 waves, two staged sequences a
-// wave and nothing else in LDS) for the pairs whose two lengths lie in [112, C], C = swa_fast_sites_cap() = 327 584 nt (or
-// SWA_FAST_SITES_CAP, a test hook); where longer sequences exist, the split's division at C.
-// SWA_FAST_COUNT=sites: k_fast_count_sites_words on the rows of k_fast_count (256 .. 1004), a comparison switch.
-using FastPlan = swa_fast_plan;
-
-// pair_longest, and how many amplicons are longer than the cap / can be half of a pair with one that is: a fact of the
-// uploaded database and the cap (the split's, or the one of SWA_FAST_LONG=pairs: the environment is read at every call),
-// read once for each
-static int ensure_length_classes(swa_ctx * ctx, uint32_t cap) {
-  if (ctx->up.d1.fast_classes_ready && ctx->up.d1.fast_classes_cap == cap) { return SWA_OK; }
-  SWA_HIP(ctx, hipSetDevice(ctx->device));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
-  auto * out = reinterpret_cast<uint32_t *>(static_cast<uint64_t *>(ctx->d_fcounters.ptr) + 12);
-  SWA_HIP(ctx, hipMemsetAsync(out, 0, 4 * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL(k_fast_length_classes, dim3(grid_for(ctx, ctx->db.n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n,
-                     cap, out);
-  SWA_HIP(ctx, hipGetLastError());
-  uint32_t host[4] = {};
-  SWA_HIP(ctx, hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->up.d1.fast_pair_longest = host[0]; ctx->up.d1.fast_n_long = host[1]; ctx->up.d1.fast_n_band = host[2];
-  ctx->up.d1.fast_classes_ready = true;
-  ctx->up.d1.fast_classes_cap = cap;
-  return SWA_OK;
-}
-
-// SWA_FAST_SITES_CAP=n, a test hook: the cap of SWA_FAST_LONG=pairs (swa_fast_sites_cap_in_effect decides whether it counts)
-static uint32_t fast_sites_cap_hook() {
-  const char * env = getenv("SWA_FAST_SITES_CAP");
-  const long long v = env != nullptr ? atoll(env) : 0;
-  return v > 0 && v <= 0xFFFFFFFFll ? (uint32_t)v : 0u;
-}
-
-// long_cap: the cap of the division at the long end that the switches ask for (SWA_FAST_LONG=pairs: C; else the split's)
-static int fast_plan(swa_ctx * ctx, FastPlan & p, uint32_t * long_cap = nullptr) {
-  const char * env_route = getenv("SWA_FAST_BLOOM");          // test hook: the reference's scheme for every pair
-  const char * env_fp = getenv("SWA_FAST_PAIRS");             // =words: the round-2 pair kernel, which walks the packed sequences — comparison switch
-  const char * env_long = getenv("SWA_FAST_LONG");            // =split: keep the pair route for the pairs up to the cap when longer sequences exist
-  const bool bloom = env_route != nullptr && env_route[0] == '1';
-  const char * env_count = getenv("SWA_FAST_COUNT");          // =sites: k_fast_count_sites_words where k_fast_count would run — comparison switch
-  const bool past_cap = !bloom && ctx->db.longest > swa_fast_cap();
-  const bool split = env_long != nullptr && strcmp(env_long, "split") == 0 && past_cap;
-  const bool pairs = env_long != nullptr && strcmp(env_long, "pairs") == 0 && past_cap;   // =pairs: the pair route serves the long sequences
-  const uint32_t sites_cap = fast_sites_cap_hook();
-  const uint32_t cap = pairs ? swa_fast_sites_cap_in_effect(sites_cap) : swa_fast_cap();
-  if (long_cap != nullptr) { *long_cap = cap; }
-  uint32_t pair_longest = 0;
-  if ((split || pairs) && ctx->db.longest > cap) { SWA_TRY(ensure_length_classes(ctx, cap)); pair_longest = ctx->up.d1.fast_pair_longest; }
-  p = swa_fast_plan_modes(ctx->db.longest, pair_longest, pairs ? 2 : (split ? 1 : 0), bloom, env_fp != nullptr && env_fp[0] == 'w',
-                          env_count != nullptr && strcmp(env_count, "sites") == 0, sites_cap);
-  return SWA_OK;
-}
-
-extern "C" int swa_d1_fastidious_plan(swa_ctx * ctx, uint32_t out[8]) {
-  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_plan: no database is resident"); }
-  FastPlan p{};
-  SWA_TRY(fast_plan(ctx, p));
-  swa_fast_plan_report(p, out);
-  return SWA_OK;
-}
-
-// The report reads the length classes whenever the longest sequence exceeds the cap, with or without the switch: its
-// first call after an upload then launches k_fast_length_classes and waits for it; later calls read the cached values.
-extern "C" int swa_d1_fastidious_split(swa_ctx * ctx, uint32_t out[4]) {
-  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_split: no database is resident"); }
-  FastPlan p{};
-  uint32_t cap = 0;
-  SWA_TRY(fast_plan(ctx, p, &cap));
-  const bool longer = ctx->db.longest > cap;
-  if (longer) { SWA_TRY(ensure_length_classes(ctx, cap)); }
-  out[0] = (uint32_t)p.long_mode;
-  out[1] = cap;
-  out[2] = longer ? ctx->up.d1.fast_pair_longest : ctx->db.longest;
-  out[3] = longer ? ctx->up.d1.fast_n_long : 0u;
-  return SWA_OK;
-}
-
-extern "C" int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]) {
-  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  for (int i = 0; i < 4; ++i) { out[i] = ctx->fast_totals[i]; }
-  return SWA_OK;
-}
-
-extern "C" int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]) {
-  if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
-  for (int i = 0; i < 4; ++i) { out[i] = ctx->fast_batches[i]; }
-  return SWA_OK;
-}
-
-static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_heavy, const FastPlan & plan) {
-  const uint32_t slots = plan.slots;
-  const int count_waves = plan.count_waves;
-  const uint32_t n = ctx->db.n;
-  auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
-  if (n_light == 0 || n_heavy == 0) { return SWA_OK; }
-  uint64_t asize_max = 64, asize_ends = 64;
-  while (asize_max < 6ull * n_light) { asize_max <<= 1; }    // load <= 0.5 with three memberships per light amplicon (middle windows)
-  while (asize_ends < 2ull * n_light) { asize_ends <<= 1; }  // one membership (prefix / suffix groups): a smaller table to clear and scan
-  const uint64_t member_cap = 3ull * n_light + n_heavy;
-  const uint64_t item_cap64 = 3ull * n_light + (3ull * n_light + n_heavy) / 2 + 64;
-  const uint32_t item_cap = item_cap64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)item_cap64;
-  SWA_TRY(join_reserve(ctx, asize_max, n, 3u, member_cap, item_cap));
-  SWA_TRY(swa_reserve(ctx, ctx->d_scan_tmp, ((asize_max + kScanTile - 1) / kScanTile) * sizeof(uint64_t)));
-  // (the offsets by the three-launch scan above, not rocPRIM's as at d >= 2: DESIGN.md 3.5 has the measurement)
-  auto scan = [&](const JoinTable & t) -> int {
-    const uint32_t tiles = (uint32_t)((t.asize + kScanTile - 1) / kScanTile);
-    auto * sums = static_cast<uint64_t *>(ctx->d_scan_tmp.ptr);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, t.tot, (uint32_t)t.asize, sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, ctx->stream, sums, tiles);
-    hipLaunchKernelGGL(k_scan_apply, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, t.tot, (uint32_t)t.asize, sums, t.offsets);
-    return SWA_OK;
-  };
-  if (ctx->fast_pair_cap == 0) {
-    ctx->fast_pair_cap = 4ull * n_light + (1ull << 20);
-    const char * env_cap = getenv("SWA_FAST_PAIR_CAP");       // test hook: start small, exercise the regrow path
-    if (env_cap != nullptr && atoll(env_cap) > 0) { ctx->fast_pair_cap = (uint64_t)atoll(env_cap); }
-  }
-  uint64_t npairs = 0;
-  const int pair_w = plan.pair_w;
-  if (pair_w != 0) {
-    SWA_TRY(launch_abundance_rank(ctx));
-    SWA_TRY(ensure_lines(ctx));
-  }
-  JoinTable jt = join_table(ctx, asize_max, n, 3u);
-  swa_t0(ctx, kTimePairs);
-  for (int attempt = 0; attempt < 6; ++attempt) {
-    SWA_TRY(swa_reserve(ctx, ctx->d_fpairs, ctx->fast_pair_cap * sizeof(uint64_t)));
-    SWA_HIP(ctx, hipMemsetAsync(fc + 5, 0, sizeof(uint64_t), ctx->stream));
-    SWA_HIP(ctx, hipMemsetAsync(jt.flags, 0, kJoinFlagWords * sizeof(uint32_t), ctx->stream));
-    ctx->fast_totals[3] = (uint64_t)attempt + 1u;
-    for (int type = 0; type < 3; ++type) {
-      // one membership a light amplicon in the prefix / suffix groups, three (the middle window at 39, 40, 41) in the middle ones
-      jt = join_table(ctx, type == 2 ? asize_max : asize_ends, n, type == 2 ? 3u : 1u);
-      uint32_t * item_counter = jt.flags + kJoinItemCount + type;   // (one a type: the pair kernel of the type before still reads its own)
-      FastGroupArgs g{};
-      g.seqs = ctx->db.seqs; g.seq_off = ctx->db.seq_off; g.seqlen = ctx->db.seqlen;
-      g.role = static_cast<const uint8_t *>(ctx->d_frole.ptr); g.n = n; g.max_len = plan.max_len;
-      g.keys = jt.keys; g.cnt_l = jt.cnt_a; g.cnt_h = jt.cnt_b; g.amask = jt.asize - 1; g.lslot = jt.aslot; g.hslot = jt.bslot; g.overflow = jt.flags + kJoinKeyOverflow;
-      // a group needs a light and a heavy amplicon: l h >= 1
-      SWA_TRY(join_run<FastTiles>(ctx, jt, 1u, item_counter, item_cap, [&](dim3 gn, dim3 b) {
-        if (type == 0) { hipLaunchKernelGGL(k_fg_light<0>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<0>, gn, b, 0, ctx->stream, g); }
-        else if (type == 1) { hipLaunchKernelGGL(k_fg_light<1>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<1>, gn, b, 0, ctx->stream, g); }
-        else { hipLaunchKernelGGL(k_fg_light<2>, gn, b, 0, ctx->stream, g); hipLaunchKernelGGL(k_fg_heavy<2>, gn, b, 0, ctx->stream, g); }
-      }, scan));
-      FastPairArgs p{};
-      p.seqs = ctx->db.seqs; p.seq_off = ctx->db.seq_off; p.seqlen = ctx->db.seqlen; p.members = jt.members;
-      p.items = jt.items; p.item_count = item_counter; p.item_cap = item_cap;
-      p.pairs = static_cast<unsigned long long *>(ctx->d_fpairs.ptr); p.pair_counter = fc + 5; p.pair_cap = ctx->fast_pair_cap;
-      const dim3 gp(ctx->num_cus * 8);
-      p.lines = static_cast<const uint4 *>(ctx->d_stream[kSbLines].ptr);
-      p.line_quads = ctx->up.d1.lines_quads;
-      if (pair_w == 5) {
-        if (type == 0) { hipLaunchKernelGGL((k_fast_pairs_lines<0, 5>), gp, dim3(kThreads), 0, ctx->stream, p); }
-        else if (type == 1) { hipLaunchKernelGGL((k_fast_pairs_lines<1, 5>), gp, dim3(kThreads), 0, ctx->stream, p); }
-        else { hipLaunchKernelGGL((k_fast_pairs_lines<2, 5>), gp, dim3(kThreads), 0, ctx->stream, p); }
-      } else if (pair_w == 8) {
-        if (type == 0) { hipLaunchKernelGGL((k_fast_pairs_lines<0, 8>), gp, dim3(kThreads), 0, ctx->stream, p); }
-        else if (type == 1) { hipLaunchKernelGGL((k_fast_pairs_lines<1, 8>), gp, dim3(kThreads), 0, ctx->stream, p); }
-        else { hipLaunchKernelGGL((k_fast_pairs_lines<2, 8>), gp, dim3(kThreads), 0, ctx->stream, p); }
-      } else if (pair_w == 13) {
-        if (type == 0) { hipLaunchKernelGGL((k_fast_pairs_lines<0, 13>), gp, dim3(kThreads), 0, ctx->stream, p); }
-        else if (type == 1) { hipLaunchKernelGGL((k_fast_pairs_lines<1, 13>), gp, dim3(kThreads), 0, ctx->stream, p); }
-        else { hipLaunchKernelGGL((k_fast_pairs_lines<2, 13>), gp, dim3(kThreads), 0, ctx->stream, p); }
-      }
-      else if (type == 0) { hipLaunchKernelGGL(k_fast_pairs<0>, gp, dim3(kThreads), 0, ctx->stream, p); }
-      else if (type == 1) { hipLaunchKernelGGL(k_fast_pairs<1>, gp, dim3(kThreads), 0, ctx->stream, p); }
-      else { hipLaunchKernelGGL(k_fast_pairs<2>, gp, dim3(kThreads), 0, ctx->stream, p); }
-      SWA_HIP(ctx, hipGetLastError());
-    }
-    uint64_t got = 0;
-    // (a group of l light and h heavy amplicons makes at most l + h / 2 items: tests/test_fastidious_identity.py)
-    SWA_TRY(join_status(ctx, jt, fc + 5, 1, &got, "swa_d1_fastidious: group key table overflow", "swa_d1_fastidious: work item list overflow"));
-    if (got <= ctx->fast_pair_cap) { npairs = got; break; }
-    if (attempt == 5) { return swa_fail_msg(ctx, SWA_E_NOMEM, "swa_d1_fastidious: pair list keeps overflowing"); }
-    ctx->fast_pair_cap = got + got / 8 + 1024;               // the count of a complete run: size for it (+ slack: none needed, it is exact)
-  }
-  swa_t1(ctx, kTimePairs);
-  swa_t0(ctx, kTimeAlign);
-  if (npairs != 0) {
-    FastCountArgs c{};
-    c.seqs = ctx->db.seqs; c.seq_off = ctx->db.seq_off; c.seqlen = ctx->db.seqlen;
-    c.zobrist = static_cast<const uint64_t *>(ctx->d_zobrist.ptr);
-    // the longest sequence a pair can hold: the database's, under the split pair_longest (k_fg_light / k_fg_heavy keep longer
-    // ones out of every group).  prepare_hashing lays the Zobrist table out by position, four values each, drawn in that
-    // order (host_tables.cpp: swa_zobrist_table): its first 4 * zlen words ARE the table of a database whose longest sequence
-    // is plan.served, so k_fast_count stages a prefix.
-    c.zlen = plan.served + 2u; c.maxwords = (plan.served + 31u) >> 5; c.slots = slots;
-    c.pairs = static_cast<const unsigned long long *>(ctx->d_fpairs.ptr); c.npairs = npairs;
-    c.graft = static_cast<uint32_t *>(ctx->d_graft.ptr); c.cand_counter = fc + 2;
-    if (plan.count_words) {
-      // two staged sequences a wave: no set, no Zobrist table (c.zobrist, c.zlen and c.slots are not read)
-      uint64_t blocks = (npairs + count_waves - 1) / count_waves;
-      const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
-      if (blocks > max_blocks) { blocks = max_blocks; }
-      const dim3 gc((uint32_t)blocks);
-      if (count_waves == 4) { hipLaunchKernelGGL(k_fast_count_sites_words<4>, gc, dim3(256), plan.count_lds, ctx->stream, c); }
-      else if (count_waves == 2) { hipLaunchKernelGGL(k_fast_count_sites_words<2>, gc, dim3(128), plan.count_lds, ctx->stream, c); }
-      else { hipLaunchKernelGGL(k_fast_count_sites_words<1>, gc, dim3(64), plan.count_lds, ctx->stream, c); }
-    } else if (plan.count_w != 0) {
-      uint64_t blocks = (npairs + kWaves - 1) / kWaves;
-      const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
-      if (blocks > max_blocks) { blocks = max_blocks; }
-      if (plan.count_w == 5) { hipLaunchKernelGGL(k_fast_count_sites<5>, dim3((uint32_t)blocks), dim3(kThreads), 0, ctx->stream, c); }
-      else { hipLaunchKernelGGL(k_fast_count_sites<8>, dim3((uint32_t)blocks), dim3(kThreads), 0, ctx->stream, c); }
-    } else {
-    const size_t lds = plan.count_lds;
-    uint64_t blocks = (npairs + count_waves - 1) / count_waves;
-    const uint64_t max_blocks = (uint64_t)ctx->num_cus * 8;
-    if (blocks > max_blocks) { blocks = max_blocks; }
-    hipLaunchKernelGGL(k_fast_count, dim3((uint32_t)blocks), dim3(64 * count_waves), lds, ctx->stream, c);
-    }
-    SWA_HIP(ctx, hipGetLastError());
-  }
-  swa_t1(ctx, kTimeAlign);
-  return SWA_OK;
-}
-
-static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
-                                 uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
-
-extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
-                                       uint32_t shard, uint32_t nshards, uint32_t * graft_cand, uint64_t * counters) {
-  if (ctx == nullptr) { return SWA_E_ARG; }
-  if (nshards == 0 || shard >= nshards) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_shard: bad shard"); }
-  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: call swa_d1_index_build first"); }
-  if (is_light == nullptr || graft_cand == nullptr || counters == nullptr || bloom_bits < 2 || bloom_bits > 64) {
-    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: bad argument");
-  }
-  SWA_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t n = ctx->db.n;
-
-  // role of every amplicon: 0 light, 1 heavy and in this shard's contiguous slice of the heavy ones, 2 neither
-  // (by blocks on a few threads: two serial passes over 10 M flags were 15 ms of this call, lease r6j)
-  std::unique_ptr<uint8_t[]> role(new uint8_t[n]);
-  uint64_t n_light = 0, n_heavy_all = 0;
-  const unsigned blocks = n >= (1u << 20) ? std::min(16u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
-  std::vector<uint64_t> heavy_before(blocks + 1, 0);
-  auto in_blocks = [&](auto && body) {
-    std::vector<std::thread> team;
-    for (unsigned b = 1; b < blocks; ++b) { team.emplace_back([&, b] { body(b); }); }
-    body(0u);
-    for (auto & t : team) { t.join(); }
-  };
-  in_blocks([&](unsigned b) {
-    uint64_t heavy = 0;
-    for (uint64_t i = (uint64_t)n * b / blocks; i < (uint64_t)n * (b + 1) / blocks; ++i) { heavy += is_light[i] == 0 ? 1u : 0u; }
-    heavy_before[b + 1] = heavy;
-  });
-  for (unsigned b = 0; b < blocks; ++b) { heavy_before[b + 1] += heavy_before[b]; }
-  n_heavy_all = heavy_before[blocks];
-  n_light = n - n_heavy_all;
-  const uint64_t lo = n_heavy_all * shard / nshards, hi = n_heavy_all * (shard + 1ull) / nshards;
-  in_blocks([&](unsigned b) {
-    uint64_t seen = heavy_before[b];
-    for (uint64_t i = (uint64_t)n * b / blocks; i < (uint64_t)n * (b + 1) / blocks; ++i) {
-      if (is_light[i] != 0) { role[i] = 0; }
-      else { role[i] = (seen >= lo && seen < hi) ? 1 : 2; ++seen; }
-    }
-  });
-  const uint64_t n_heavy = hi - lo;
-  const int rc = fastidious_with_roles(ctx, role.get(), n_light, n_heavy, light_nt, bloom_bits, graft_cand, counters);
-  if (rc != SWA_OK) { (void)hipStreamSynchronize(ctx->stream); }     // (role is a host temporary)
-  ctx->res.fast.cand_ready = rc == SWA_OK && nshards == 1u;   // (d_graft: the candidates of the whole pass, for swa_d1_graft_device)
-  return rc;
-}
-
-// The pass from the roles on (0 light, 1 heavy and to be expanded here, 2 neither): what swa_d1_fastidious_shard and
-// swa_d1_fastidious_resident share.  host_role: the shard form's array, uploaded into d_frole; null: the bytes
-// swa_d1_light_flags_device left in d_swarm_role, copied on the device.  Reservations, copies and launches come in the order
-// swa_d1_fastidious_shard has always made them.  graft_cand may be null: the candidates then stay in HBM (d_graft) only.
-static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
-                                 uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
-  SWA_TRY(prepare_hashing(ctx));                             // the Zobrist table
-  const uint32_t n = ctx->db.n;
-  ctx->res.fast.cand_ready = false;
-  // the numbers of the reference's log line (src/algod1.cc:1337-1357, 1383-1403; bloomflex.cc:91-115)
-  uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
-  if (k < 1) { k = 1; }
-  uint64_t m = light_nt * 7ull * bloom_bits;
-  if (m < 64) { m = 64; }
-
-  FastPlan plan{};
-  SWA_TRY(fast_plan(ctx, plan));
-  const bool pair_route = plan.pair_route;
-  for (uint64_t & t : ctx->fast_totals) { t = 0; }
-  for (uint64_t & t : ctx->fast_batches) { t = 0; }
-  const uint32_t min_len = pair_route ? kFastMinLen : 0xFFFFFFFFu;
-  const uint32_t max_len = plan.max_len;                     // (0xFFFFFFFF without a division at the long end)
-
-  SWA_TRY(swa_reserve(ctx, ctx->d_frole, n));
-  SWA_TRY(swa_reserve(ctx, ctx->d_light, n));
-  SWA_TRY(swa_reserve(ctx, ctx->d_graft, uint64_t(n) * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_list_a, (uint64_t(n) + 1) * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_list_b, (uint64_t(n) + 1) * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, 16 * sizeof(uint64_t)));
-  if (host_role != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, host_role, n, hipMemcpyHostToDevice, ctx->stream)); }
-  else { SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, ctx->d_swarm_role.ptr, n, hipMemcpyDeviceToDevice, ctx->stream)); }
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_graft.ptr, 0xFF, uint64_t(n) * sizeof(uint32_t), ctx->stream));
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_fcounters.ptr, 0, 16 * sizeof(uint64_t), ctx->stream));
-  auto * fc = static_cast<unsigned long long *>(ctx->d_fcounters.ptr);
-  for (int slot : {kTimePairs, kTimeAlign}) { ctx->ev_used[slot] = false; }
-
-  // the log's variant totals, and the amplicons that can be part of a pair the pair route does not take
-  hipLaunchKernelGGL(k_fast_variant_totals, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off,
-                     ctx->db.seqlen, static_cast<const uint8_t *>(ctx->d_frole.ptr), n, fc);
-  const uint32_t short_cut = pair_route ? kFastMinLen + 1u : 0xFFFFFFFFu;   // len <= cut: may pair with a sequence < kFastMinLen
-  const uint32_t long_cut = max_len != 0xFFFFFFFFu ? max_len - 1u : 0xFFFFFFFFu;   // len >= cut: may pair with a sequence > the cap (split, pairs)
-  hipLaunchKernelGGL(k_fast_band_lists, dim3(grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, ctx->db.seqlen,
-                     static_cast<const uint8_t *>(ctx->d_frole.ptr), n, short_cut, long_cut, static_cast<uint8_t *>(ctx->d_light.ptr),
-                     static_cast<uint32_t *>(ctx->d_list_a.ptr), static_cast<uint32_t *>(ctx->d_list_b.ptr), fc + 6);
-  SWA_HIP(ctx, hipGetLastError());
-  uint64_t bands[3] = {0, 0, 0};                             // light / heavy amplicons of the two bands, the lights' nucleotides
-  SWA_HIP(ctx, hipMemcpyAsync(bands, fc + 6, sizeof(bands), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (role is a host temporary, too)
-
-  if (pair_route) { SWA_TRY(fastidious_pair_route(ctx, (uint32_t)n_light, (uint32_t)n_heavy, plan)); }
-  if (bands[0] != 0 && bands[1] != 0) {
-    SWA_TRY(fastidious_bloom_route(ctx, (uint32_t)bands[0], (uint32_t)bands[1], bands[2], bloom_bits, min_len, max_len, plan.zobrist_lds));
-  }
-
-  uint64_t host_fc[8] = {};
-  SWA_HIP(ctx, hipMemcpyAsync(host_fc, fc, sizeof(host_fc), hipMemcpyDeviceToHost, ctx->stream));
-  if (graft_cand != nullptr) {
-    swa_touch_pages(graft_cand, uint64_t(n) * sizeof(uint32_t));
-    SWA_HIP(ctx, hipMemcpyAsync(graft_cand, ctx->d_graft.ptr, uint64_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  counters[0] = host_fc[0];
-  counters[1] = host_fc[1];
-  counters[2] = host_fc[2];
-  counters[3] = m;
-  counters[4] = k;
-  for (int i = 0; i < 3; ++i) { ctx->fast_totals[i] = host_fc[5 + i]; }
-  return SWA_OK;
-}
-
-// The same pass fed from the device: the roles are the bytes swa_d1_light_flags_device left in HBM for the clustering in
-// place (no host flags, no role passes on the host, no upload), and the candidates come home only when the caller hands
-// over a buffer — swa_d1_graft_device reads them where they lie.
-extern "C" int swa_d1_fastidious_resident(swa_ctx * ctx, uint64_t light_nt, uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
-  if (ctx == nullptr) { return SWA_E_ARG; }
-  if (!ctx->res.cluster_ready || !ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_resident: no clustering in place (swa_d1_cluster_device)"); }
-  if (!ctx->res.fast.roles_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious_resident: call swa_d1_light_flags_device first"); }
-  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: call swa_d1_index_build first"); }
-  if (counters == nullptr || bloom_bits < 2 || bloom_bits > 64) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: bad argument"); }
-  SWA_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t n = ctx->db.n;
-  const uint64_t n_light = ctx->res.fast.light_amps;
-  SWA_TRY(fastidious_with_roles(ctx, nullptr, n_light, n - n_light, light_nt, bloom_bits, graft_cand, counters));
-  ctx->res.fast.cand_ready = true;
   return SWA_OK;
 }

@@ -1,4 +1,5 @@
-// d1_anchor.inc — device code of the ANCHORED d=1 network (included by d1.hip inside its anonymous namespace).
+// d1_anchor.inc — device code of the ANCHORED d=1 network (included once, by d1.hip alone, inside its anonymous namespace
+// after d1_common.inc).
 //
 // Why: the plain kernel (k_d1_probe<MODE 0>) issues one divergent 8-byte Bloom read per microvariant — ~1000 random L2
 // requests per query amplicon — and rocprofv3 shows it bound by exactly that request rate (profiles/r01).  The fix is
@@ -21,113 +22,14 @@
 // hash-table index build it read (k_anchor_place / k_anchor_scatter): retired in round 4 — the streaming build
 // (d1_stream.inc) and the pair kernels serve every length now.
 //
-// In this file, in order: types; amplicon lines; anchor keys; routing and the window sample; abundance ranks;
-// enumerate_range (the plain kernel's restricted enumeration); the pair machinery (records, pair_stage, pair_near,
-// pair_emit, the guard) and its two kernels.
+// In this file, in order: routing and the window sample; abundance ranks; the pair machinery (records, pair_stage,
+// pair_near, pair_emit, the guard) and its two kernels.  The types, the amplicon lines and the anchor keys are in
+// d1_common.inc (the --fastidious pass reads them too), the plain kernel's restricted enumeration (enumerate_range) is
+// with that kernel in d1_probe.inc.
 
-#ifdef SWA_ANCHOR_TYPES_ONLY
-struct alignas(16) swa_aux {     // per amplicon, written by k_seqhash
-  uint64_t h;                    // Zobrist hash of the sequence           (XOR of Z[p][s_p])
-  uint64_t dall, iall;           // XOR of Z[p-1][s_p] (p >= 1) / of Z[p+1][s_p] over all p
-  uint64_t a32, d32, i32;        // the same three streams restricted to p < pb
-  // pb = first position of the homopolymer run that contains position 31 (<= 31).  The passes divide a seed's
-  // microvariants by what they SHARE with the seed: the prefix pass takes those that keep the first 32 nucleotides —
-  // every edit at a canonical position >= 32, and the run edits (deletion of / insertion into the run around
-  // position 31, listed at the run's first position by generate_variants) — so it enumerates positions >= pb against
-  // the prefix group; the suffix pass takes the microvariants whose first 32 nucleotides differ (positions < 32,
-  // a hit that shares the prefix is dropped).  pb = 0 (first 32 nt one run): the seed goes to the plain kernel.
-  uint32_t pb;
-  uint32_t pad[3];
-};
-
-struct swa_item { uint32_t begin, size, chunk; };      // members [begin, begin + size) of the group-order id list; chunk (tiled kernel): row tile | column part << 6
-struct swa_fallback { uint32_t seed, range; };         // range: 0 all positions, 1 the neighbours that share the prefix-side window, 2 the others
-
-constexpr uint32_t kAnchor = 32;            // one word of an anchor window, in nucleotides
-constexpr uint32_t kMinAnchoredLen = 65;    // no database whose longest sequence is shorter has anchored passes
-constexpr uint32_t kGroupCap = 2048;        // (window sample: a group this large counts as stranded)
-constexpr uint32_t kSeedsPerItem = 64;
-// An item of the tiled kernel: a row tile of a group against up to kTiledCols of its column tiles — one a wave (round 6: it
-// was the row tile against ALL its column tiles — items of 1 to 64 tiles of work; the kernel's time was its few longest items')
-#ifndef SWA_TILED_COLS
-#define SWA_TILED_COLS 4            // (pair passes of the Zipf set with 4 / 8 / 16: 0.60 + 0.58 / 0.63 + 0.60 / 0.67 + 0.64 ms, lease z33)
-#endif
-constexpr uint32_t kTiledCols = SWA_TILED_COLS;
-__host__ __device__ constexpr inline uint32_t tiled_item_count(uint32_t members) {
-  const uint32_t tiles = (members + kSeedsPerItem - 1u) / kSeedsPerItem;
-  uint32_t items = 0;
-  for (uint32_t r = 0; r < tiles; ++r) { items += (tiles - r + kTiledCols - 1u) / kTiledCols; }
-  return items;
-}
-constexpr uint32_t kPrefetchWords = 2;      // (anchor_applicable: sequences up to 64 * 2 * 32 - 64 nt)
-constexpr uint32_t kPairClasses = 5;        // size classes of the groups served by pairs in one wave: up to 4, 8, 16, 32, 64 members
-constexpr uint32_t kPairBigCap = 256;       // groups of 65..this many members: by pairs in one workgroup (k_d1_group_pairs)
-// Width classes (round 4; VERDICT r03 item 2).  The pair kernels keep a member's packed words in registers, W words each,
-// and W is chosen per GROUP — by its longest member — not per database: one 460-nt read in a file of 150-nt reads puts its
-// own groups on the 15-word kernels and nobody else's.  Class of a sequence: the smallest W in {5, 8, 15, 21} that holds it;
-// kTooLong: beyond the widest kernel — its groups go to the plain kernel, like oversized ones.
-constexpr uint32_t kWidthClasses = 4;
-constexpr uint32_t kTooLong = kWidthClasses;
-__host__ __device__ inline uint32_t width_class(uint32_t len) { return len <= 160u ? 0u : (len <= 256u ? 1u : (len <= 480u ? 2u : (len <= 672u ? 3u : kTooLong))); }
-__host__ __device__ inline int width_words(uint32_t cls) { return cls == 0u ? 5 : (cls == 1u ? 8 : (cls == 2u ? 15 : 21)); }
-// work lists of an index: per width class the groups by size kind — kPairClasses lists of small groups (bundles), one of
-// the groups of 65..pair_big (a workgroup each), one of 64-member row tiles of the larger ones (k_d1_pairs_tiled)
-constexpr uint32_t kListKinds = kPairClasses + 2;
-constexpr uint32_t kListsPerIndex = kWidthClasses * kListKinds;
-struct ListRegions { uint64_t at[kWidthClasses][kListKinds + 1]; };   // first item of list (class, kind) in an index's item buffer; [.][kListKinds] = end
-constexpr uint32_t kSchedStride = 64;       // entries between two work counters of k_d1_group_pairs (own cache lines / channels)
-
-#else
 #ifndef SWA_PAIR_WG
 #define SWA_PAIR_WG 5
 #endif
-// ---- amplicon lines (streaming build, d1_stream.inc): every amplicon as ONE aligned line of 64, 128 or 256 bytes (one
-// stride per database, by its longest sequence: up to 160 / 480 / beyond) ---------------------------------------------------------
-// dword [0] length | [1] abundance rank | [2, 2 + 2 C) packed sequence, zero padded; C = 2 quads - 1 words fit (7 / 15 / 31).
-// A sequence longer than 32 C nt has its first C words there (nobody reads them: its groups go to the plain kernel).
-// A reader takes the quads its own width needs: 3 of a line for W = 5, 5 for 8, 8 for 15, 11 for 21.
-__host__ __device__ inline uint32_t line_capacity_words(uint32_t quads) { return 2u * quads - 1u; }
-
-// words + length + rank of amplicon `id` from its line (W <= the line's capacity)
-template <int W>
-__device__ __forceinline__ void line_fetch(const uint4 * __restrict__ lines, uint32_t quads, uint32_t id, uint64_t (&w64)[W], uint32_t & len, uint32_t & rank) {
-  constexpr uint32_t used = (2 * W + 2 + 3) / 4;                  // quads that carry anything
-  const uint4 * L = lines + (uint64_t)id * quads;
-  uint32_t d[4 * used + 2];
-#pragma unroll
-  for (uint32_t q = 0; q < used; ++q) { const uint4 v = L[q]; d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w; }
-  len = d[0]; rank = d[1];
-#pragma unroll
-  for (int k = 0; k < W; ++k) { w64[k] = (uint64_t)d[2 + 2 * k] | ((uint64_t)d[3 + 2 * k] << 32); }
-}
-
-// key of the prefix-side (which = 0) or suffix-side (which = 1) anchor window.  Normally the first / last 32 * nwin
-// nucleotides (win_a = win_b = 0).  When those are (nearly) the same for everybody — conserved flanks — the windows
-// move inwards: [win_a, win_a + 32 nwin) from the start, [len - win_b - 32 nwin, len - win_b) from the end ("window
-// mode", chosen per database at index build).  len >= win_a + 32 nwin resp. win_b + 32 nwin.
-// Width (round 4): two sequences of >= 2 w + 1 nucleotides one edit apart share their first w or their last w nucleotides
-// for ANY w, and a wider window keeps a family member in its parent's group only if its edit misses the window: at w = 64
-// a 150-nt family leaves (86 / 150)^2 of its pairs to each pass where w = 32 left (118 / 150)^2.  nwin = w / 32 words
-// (1, 2 or 4: chosen per database from its shortest sequence, anchor_width_for); one word: the key of rounds 1-3.
-constexpr uint64_t kSuffixSalt = 0x9E3779B97F4A7C15ull;
-__device__ __forceinline__ uint64_t anchor_fold(const uint64_t * win, uint32_t nwin, int which) {
-  uint64_t h = mix64(win[0] ^ (which ? kSuffixSalt : 0ull));
-  for (uint32_t k = 1; k < nwin; ++k) { h = mix64(h ^ win[k]); }
-  return h & 0x7FFFFFFFFFFFFFFFull;
-}
-// the 32 bits of a key record (k_keys): the top 29 bits of the mixed key — what a group is — and, below them, the width
-// class of the amplicon, which k_group1 gathers into the class of the group
-__device__ __forceinline__ uint32_t record_key(uint64_t mixed, uint32_t len) { return ((uint32_t)(mixed >> 32) & ~7u) | width_class(len); }
-// the 29 bits a window stands for (the guard of the pair kernels)
-__device__ __forceinline__ uint32_t anchor_key29(const uint64_t * win, uint32_t nwin, int which) {
-  return (uint32_t)(mix64(anchor_fold(win, nwin, which)) >> 35);
-}
-__device__ __forceinline__ uint64_t anchor_key(const uint64_t * seq, uint32_t len, int which, uint32_t win_a, uint32_t win_b, uint32_t nwin = 1u) {
-  const uint32_t pos = which == 0 ? win_a : len - win_b - kAnchor * nwin;
-  uint64_t win[4] = {0ull, 0ull, 0ull, 0ull};
-  for (uint32_t k = 0; k < nwin; ++k) { win[k] = window32(seq, pos + kAnchor * k); }
-  return anchor_fold(win, nwin, which);
-}
 
 // which rank of a multi-GPU job serves the group of this anchor key: bits of the MIXED key that neither the table index
 // (its low bits) nor the slot tag (its high half) depend on alone; multiply-shift, no division
@@ -361,89 +263,6 @@ __device__ __forceinline__ bool identical_sequences(const uint64_t * seqs, const
   return same;
 }
 
-// Microvariants of positions [pb, pe) only (pe <= len + 1; position len carries insertions
-// only).  H = hash of the sequence, baseA = XOR of Z[q][s_q] over q < pb, tailD / tailI = XOR
-// of Z[q-1][s_q] / Z[q+1][s_q] over q >= pb.  Same slot layout as enumerate_variants.
-// Written without data-dependent branches: every table read uses a clamped (always valid)
-// index and validity travels as 0/1 integers, because on this kernel the CU's single scalar
-// unit (exec-mask bookkeeping of divergent branches), not the vector ALUs, was the limiter.
-struct SlotsI {
-  uint64_t hs[8];
-  uint32_t ok[8];       // 0 / 1
-  uint32_t code[8];
-};
-
-template <class F>
-__device__ __forceinline__ void enumerate_range(const uint64_t * sw, uint32_t len, const uint64_t * zob, int lane,
-                                                uint32_t pb, uint32_t pe, uint64_t H, uint64_t baseA, uint64_t tailD,
-                                                uint64_t tailI, F && f) {
-  const uint32_t K = (pe - pb + 63u) >> 6;
-  const uint32_t p0 = pb + (uint32_t)lane * K;
-  const uint32_t lim = pe < len ? pe : len;                  // positions that carry a nucleotide
-  uint64_t xa = 0, xd = 0, xi = 0;
-  for (uint32_t j = 0; j < K; ++j) {
-    const uint32_t p = p0 + j;
-    const uint32_t pc = p < len ? p : len - 1u;              // clamped: always a real position
-    const uint64_t live = p < lim ? ~0ull : 0ull;
-    const uint32_t c = swa_nt(sw, pc);
-    xa ^= zob[4u * pc + c] & live;
-    xd ^= zob[4u * (pc > 0u ? pc - 1u : 0u) + c] & (pc > 0u ? live : 0ull);
-    xi ^= zob[4u * (pc + 1u) + c] & live;
-  }
-  uint64_t ea = xa, ed = xd, ei = xi;                        // inclusive prefix scans over the lanes
-#pragma unroll
-  for (unsigned d = 1; d < 64; d <<= 1) {
-    const uint64_t ta = swa_shfl_up_u64(ea, d);
-    const uint64_t td = swa_shfl_up_u64(ed, d);
-    const uint64_t ti = swa_shfl_up_u64(ei, d);
-    const uint64_t take = lane >= (int)d ? ~0ull : 0ull;
-    ea ^= ta & take; ed ^= td & take; ei ^= ti & take;
-  }
-  uint64_t pa = baseA ^ ea ^ xa;                             // prefix of the a-stream below p0
-  uint64_t sd = tailD ^ ed ^ xd;                             // suffix of the d-stream from p0 on
-  uint64_t si = tailI ^ ei ^ xi;                             // suffix of the i-stream from p0 on
-
-  uint32_t prevc = (p0 >= 1u && p0 - 1u < len) ? swa_nt(sw, p0 - 1u) : 4u;
-  for (uint32_t j = 0; j < K; ++j) {
-    const uint32_t p = p0 + j;
-    const uint32_t pc = p < len ? p : len;                   // clamped row of the Zobrist table (len is valid)
-    const uint32_t in_seq = (p < lim) ? 1u : 0u;
-    const uint32_t in_ins = (p < pe && p <= len) ? 1u : 0u;
-    const uint32_t c = swa_nt(sw, p < len ? p : len - 1u);
-    const uint64_t seq_mask = in_seq ? ~0ull : 0ull;
-    uint64_t z[4];
-#pragma unroll
-    for (uint32_t b = 0; b < 4u; ++b) { z[b] = zob[4u * pc + b]; }
-    const uint64_t zc = (c == 0u) ? z[0] : (c == 1u) ? z[1] : (c == 2u) ? z[2] : z[3];
-    const uint64_t za = zc & seq_mask;
-    const uint64_t zd = zob[4u * (pc > 0u ? pc - 1u : 0u) + c] & (pc > 0u ? seq_mask : 0ull);
-    const uint64_t zi = zob[4u * (pc + 1u) + c] & seq_mask;
-    const uint32_t first = (p == 0u) ? 1u : 0u;
-    SlotsI s;
-#pragma unroll
-    for (uint32_t b = 0; b < 4u; ++b) {
-      s.hs[b] = pa ^ z[b] ^ si;
-      s.ok[b] = in_ins & (first | (b != prevc ? 1u : 0u));
-      s.code[b] = 2u | (b << 2) | (p << 4);
-    }
-#pragma unroll
-    for (uint32_t t = 0; t < 3u; ++t) {
-      const uint32_t b = (t < c) ? t : t + 1u;
-      s.hs[4 + t] = H ^ za ^ ((t < c) ? z[t] : z[t + 1u]);
-      s.ok[4 + t] = in_seq;
-      s.code[4 + t] = 0u | (b << 2) | (p << 4);
-    }
-    s.hs[7] = pa ^ sd ^ zd;
-    s.ok[7] = in_seq & (first | (c != prevc ? 1u : 0u));
-    s.code[7] = 1u | (p << 4);
-    f(s);
-    pa ^= za;
-    sd ^= zd;
-    si ^= zi;
-    prevc = c;
-  }
-}
-
 struct AnchorArgs {
   const swa_item * items;           // row tiles of the groups beyond pair_big (k_d1_pairs_tiled): this launch's class
   const uint32_t * item_count;      // device counter
@@ -478,15 +297,6 @@ struct AnchorArgs {
   uint32_t * flags;
 };
 
-// value of lane `src` when src is wave-uniform: v_readlane_b32 (no LDS crossbar round trip,
-// unlike ds_bpermute behind __shfl), and the result lives in an SGPR
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, int src) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(src));
-}
-__device__ __forceinline__ uint64_t lane_value64(uint64_t v, int src) {
-  return ((uint64_t)lane_value((uint32_t)(v >> 32), src) << 32) | lane_value((uint32_t)v, src);
-}
-
 // ---- groups by PAIRS ----------------------------------------------------------------------------------
 // Enumerating ~7 L microvariants per seed and probing an LDS table costs about 600 wave-instructions per seed;
 // comparing two members directly costs less than two.  No hashes, no Bloom filter, no table, no separate
@@ -494,37 +304,6 @@ __device__ __forceinline__ uint64_t lane_value64(uint64_t v, int src) {
 // rule allows in either direction.
 // PASS 0 (prefix groups): pairs that share the prefix-side window; PASS 1 (suffix groups): pairs that do not — the
 // same division the plain kernel applies to the seeds it serves (k_d1_probe<MODE 2>: window_filter).
-
-// exactly one edit apart, on packed 64-bit words held in registers (the fastidious site count, k_fast_count_sites,
-// compares a microvariant built in registers with a sequence this way; the pair kernels below use lcp + lcs instead)
-template <int W>
-__device__ __forceinline__ bool one_edit_apart(const uint64_t (&sw)[W], uint32_t slen, const uint64_t (&w)[W], uint32_t len) {
-  // L = the longer of the two (either, when the lengths are equal), S = the other (n nucleotides).
-  //   lengths differ by one: one edit apart <=> there is a p with S[0, p) = L[0, p) and S[p, n) = L[p + 1, n + 1).  The
-  //     largest candidate p is the first mismatch of S against L (lcp); it works iff the last mismatch of S against L
-  //     shifted down by one nucleotide (hb) lies below it.  Zero padding behind both sequences makes positions >= n
-  //     compare equal in the shifted comparison.
-  //   equal lengths: one substitution <=> the first and the last mismatch of S against L are the same position.
-  // One code path for both (the shift is a per-lane select): lanes of a wave hold members of different lengths.
-  const int dl = (int)len - (int)slen;
-  const bool mine_longer = dl == 1, shifted = dl != 0;
-  auto longer = [&](int k) { return mine_longer ? w[k] : sw[k]; };
-  auto shorter = [&](int k) { return mine_longer ? sw[k] : w[k]; };
-  int lcp = 0x7fffffff, hb = -1;
-#pragma unroll
-  for (int k = W - 1; k >= 0; --k) {
-    const uint64_t a = shorter(k) ^ longer(k);
-    lcp = a != 0ull ? 32 * k + (__builtin_ctzll(a) >> 1) : lcp;
-  }
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const uint64_t next = k + 1 < W ? longer(k + 1 < W ? k + 1 : k) : 0ull;
-    const uint64_t other = shifted ? ((longer(k) >> 2) | (next << 62)) : longer(k);
-    const uint64_t b = shorter(k) ^ other;
-    hb = b != 0ull ? 32 * k + ((63 - __builtin_clzll(b)) >> 1) : hb;
-  }
-  return (dl >= -1 && dl <= 1) && (shifted ? hb < lcp : hb == lcp);
-}
 
 // ---- groups up to pair_big members by pairs, every lane a pair -------------------------------------------------------
 // k_d1_group_pairs.  Each member of a group is staged once in LDS as a record: its packed words, the same words
@@ -1078,4 +857,3 @@ __global__ __launch_bounds__(kThreads, W == 5 ? SWA_PAIR_WG : 1) void k_d1_group
   if (lane == 0u) { a.seg_fill[gwave] = seg_at; a.seg_staged[gwave] = staged_members; }
   if (misfiled != 0u) { atomicAdd(a.guard + kGuardMisfiled, (unsigned long long)misfiled); }
 }
-#endif  // SWA_ANCHOR_TYPES_ONLY

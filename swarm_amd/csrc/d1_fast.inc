@@ -1,4 +1,5 @@
-// d1_fast.inc — seam B2 (--fastidious) by PAIRS (included by d1.hip inside its anonymous namespace).
+// d1_fast.inc — seam B2 (--fastidious) by PAIRS (included once, by fastidious.hip alone, inside its anonymous namespace after
+// group_join.inc, d1_common.inc and d1_probe.inc).
 //
 // What the reference computes (src/algod1.cc:339-552): for every heavy amplicon h, every
 // microvariant v of h that the Bloom filter of the light microvariants lets through is
@@ -484,7 +485,39 @@ __global__ void k_fast_count(const FastCountArgs a) {
 // and periodic sequences: tests/test_fastidious_identity.py.)  So only the canonical positions
 //     [ runstart(h, min(P, E) - 1) - 1 ,  max(P, E) + 1 ]
 // of h are expanded: lane = (position, slot), the microvariant is materialised in registers (swa_variant_word) and
-// compared with x by the exact one-edit test of the d=1 pair kernel.  No hashes, no LDS set.
+// compared with x by an exact one-edit test on registers (one_edit_apart).  No hashes, no LDS set.
+
+// exactly one edit apart, on packed 64-bit words held in registers (a microvariant built in registers against a sequence;
+// the pair kernels of the d = 1 step, d1_anchor.inc, use lcp + lcs on staged records instead)
+template <int W>
+__device__ __forceinline__ bool one_edit_apart(const uint64_t (&sw)[W], uint32_t slen, const uint64_t (&w)[W], uint32_t len) {
+  // L = the longer of the two (either, when the lengths are equal), S = the other (n nucleotides).
+  //   lengths differ by one: one edit apart <=> there is a p with S[0, p) = L[0, p) and S[p, n) = L[p + 1, n + 1).  The
+  //     largest candidate p is the first mismatch of S against L (lcp); it works iff the last mismatch of S against L
+  //     shifted down by one nucleotide (hb) lies below it.  Zero padding behind both sequences makes positions >= n
+  //     compare equal in the shifted comparison.
+  //   equal lengths: one substitution <=> the first and the last mismatch of S against L are the same position.
+  // One code path for both (the shift is a per-lane select): lanes of a wave hold members of different lengths.
+  const int dl = (int)len - (int)slen;
+  const bool mine_longer = dl == 1, shifted = dl != 0;
+  auto longer = [&](int k) { return mine_longer ? w[k] : sw[k]; };
+  auto shorter = [&](int k) { return mine_longer ? sw[k] : w[k]; };
+  int lcp = 0x7fffffff, hb = -1;
+#pragma unroll
+  for (int k = W - 1; k >= 0; --k) {
+    const uint64_t a = shorter(k) ^ longer(k);
+    lcp = a != 0ull ? 32 * k + (__builtin_ctzll(a) >> 1) : lcp;
+  }
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    const uint64_t next = k + 1 < W ? longer(k + 1 < W ? k + 1 : k) : 0ull;
+    const uint64_t other = shifted ? ((longer(k) >> 2) | (next << 62)) : longer(k);
+    const uint64_t b = shorter(k) ^ other;
+    hb = b != 0ull ? 32 * k + ((63 - __builtin_clzll(b)) >> 1) : hb;
+  }
+  return (dl >= -1 && dl <= 1) && (shifted ? hb < lcp : hb == lcp);
+}
+
 template <int W>
 __global__ __launch_bounds__(kThreads) void k_fast_count_sites(const FastCountArgs a) {
   __shared__ uint64_t hw_all[kWaves][W + 2];
@@ -581,7 +614,7 @@ __global__ __launch_bounds__(kThreads) void k_fast_count_sites(const FastCountAr
 //   positions exactly those of k_fast_count_sites, both forms; a homopolymer run may span many words: the walk back is
 //             uniform over the wave and ends at position 0 at the latest;
 //   the test  lane = (position, slot); the microvariant's words come from swa_variant_word as the loops ask for them, and
-//             "v is one edit from x" is one_edit_apart (d1_anchor.inc) with a run-time word count: lcp = the first mismatch
+//             "v is one edit from x" is one_edit_apart (above) with a run-time word count: lcp = the first mismatch
 //             of the forward words, hb = the last mismatch of the shorter against the longer moved down by one nucleotide
 //             (equal lengths: unmoved); one edit apart <=> hb < lcp (lengths n, n + 1), hb == lcp (equal lengths).  Each loop
 //             stops at the word that holds its mismatch, which IS lcp / hb: no word is skipped on an assumption.

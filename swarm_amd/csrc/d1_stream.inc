@@ -830,7 +830,11 @@ __device__ __forceinline__ void part_write_starts(const PartArgs & a, const Part
       const uint32_t c = i >> a.bits, b = i & ((1u << a.bits) - 1u), t0 = p.ctile[c];
       at = p.cnt[((uint64_t)t0 << a.bits) + (uint64_t)b * (p.ctile[c + 1] - t0)];
     }
-    p.next_start[i] = at;
+    // Never past what the output buffer holds.  The counts include the records the scatter dropped at out_cap (a link
+    // partition whose caller guessed too few links: network_run sees the total and repeats with bigger buffers); with the
+    // starts as counted, the next level and k_csr_bucket* READ the buffer up to that total — as far past its end as the
+    // guess was short, into whatever lies behind the allocation: an illegal access when nothing is mapped there.
+    p.next_start[i] = at < p.out_cap ? at : p.out_cap;
   }
 }
 

@@ -47,6 +47,7 @@ int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, 
 namespace {
 
 #include "wave_ops.inc"     // wave_lds_sync
+#include "key_ops.inc"      // kEmpty, kKeyEmpty, mix64, window32
 #include "group_join.inc"   // the window groups are a grouped join: targets create, queries join
 
 constexpr uint32_t kTile = 4096;          // (query, target) pairs per turn of a wave

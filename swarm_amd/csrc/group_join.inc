@@ -1,5 +1,6 @@
-// group_join.inc — the grouped join of the --fastidious pair route (d1.hip, d1_fast.inc) and of the bulk d >= 2 graph route
-// (dn_graph.hip), included inside each file's anonymous namespace after wave_ops.inc.
+// group_join.inc — the grouped join of the --fastidious pair route (fastidious.hip, d1_fast.inc) and of the bulk d >= 2 graph
+// route (dn_graph.hip), included inside each file's anonymous namespace after wave_ops.inc and key_ops.inc (kEmpty, kKeyEmpty,
+// mix64).
 //
 // Two kinds of amplicons meet under 63-bit keys.  CREATORS (light amplicons; targets at all their shifts) claim slots of
 // an open-addressing key table and count themselves, up to per_a keys each; JOINERS (heavy amplicons; queries) look one
@@ -9,22 +10,6 @@
 // turns the totals into member offsets, a scatter writes the member lists (creators first, then joiners), and an items
 // pass deals every group's tiles round-robin to at most Shape::stride work items.  The route's pair kernel walks the
 // items (tile = item.tile, + stride, ...) and keeps what it finds in a PairStage.
-
-constexpr uint32_t kEmpty = SWA_NO_AMPLICON;
-constexpr uint64_t kKeyEmpty = ~0ull;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
-
-// 32 nucleotides from position pos on (may read the following word: the database ends in two zero words)
-__device__ __forceinline__ uint64_t window32(const uint64_t * seq, uint32_t pos) {
-  const uint32_t w = pos >> 5, sh = (pos & 31u) << 1;
-  uint64_t v = seq[w] >> sh;
-  if (sh != 0u) { v |= seq[w + 1] << (64u - sh); }
-  return v;
-}
 
 // ---- the key table --------------------------------------------------------------------------------------------------
 // the slot of `key`, claimed if nobody had it (linear probing from the mixed key); kEmpty: the table is full

@@ -46,14 +46,14 @@ uint64_t swa_hashtable_size(uint64_t n) {
   return static_cast<uint64_t>(std::pow(2.0, std::ceil(std::log(static_cast<double>(quotient)) / std::log(2.0))));
 }
 
-// ---- the dispatch of the --fastidious pass (d1.hip: fast_plan; d1_fast.inc) -------------------------------------------
-// Pure host arithmetic, no HIP call: what d1.hip launches and what swa_d1_fastidious_plan reports have this one source.
+// ---- the dispatch of the --fastidious pass (fastidious.hip: fast_plan; d1_fast.inc) -----------------------------------
+// Pure host arithmetic, no HIP call: what fastidious.hip launches and what swa_d1_fastidious_plan reports have this one source.
 
 // LDS of k_fast_count for `waves` waves per block: the Zobrist table of longest + 2 positions, and per wave two sequence
 // copies (words + 3) and the set; 0 = does not fit 160 KB
 size_t swa_fast_count_lds(uint32_t longest, uint32_t slots, int waves) {
   const uint32_t maxwords = (longest + 31u) >> 5;
-  const size_t zlen = (size_t)longest + 2u;                  // = ctx->zobrist_len (prepare_hashing) when longest is the database's
+  const size_t zlen = (size_t)longest + 2u;                  // = ctx->zobrist_len (swa_prepare_hashing) when longest is the database's
   const size_t bytes = sizeof(uint64_t) * (4ull * zlen + (size_t)waves * (2ull * (maxwords + 3u) + slots));
   return bytes <= 160u * 1024u ? bytes : 0;
 }

@@ -111,6 +111,33 @@ constexpr uint32_t kCounterBase = 64;      // + (index * kWidthClasses + class) 
 constexpr uint32_t kCounterWords = 256;
 static_assert(kCounterWords * sizeof(uint32_t) == sizeof(swa_status_block::counters), "status block: counters");
 
+// ---- the device counters of the --fastidious pass ---------------------------------------------------------------------
+// d_fcounters as fastidious.hip lays it out (dn_graph.hip keeps a layout of its own in the same buffer for its own pass).
+// As with the status block the members are the whole contract: kernels get plain pointers to them, the host copies
+// neighbouring members with one copy.  unsigned long long: what the kernels' atomics take.
+struct swa_fast_counters {
+  unsigned long long light_variants;   // sum of |V1(x)| over the light amplicons (k_fast_variant_totals: counters[0]) ...
+  unsigned long long heavy_variants;   // ... and over this shard's heavy ones (counters[1])
+  unsigned long long candidates;       // graft candidates (k_d1_probe<., 1>, k_fast_count*)
+  unsigned long long batch_tasks;      // Bloom route, the current batch of heavy amplicons: tasks k_d1_flex<., 1> made ...
+  unsigned long long batch_variants;   // ... and microvariants it tested (cleared and read together with the tasks)
+  unsigned long long pairs;            // pair route: (heavy, light) pairs within two edits
+  unsigned long long bands[3];         // k_fast_band_lists: light / heavy amplicons of the Bloom route's bands, nucleotides of those light ones
+  unsigned long long scratch;          // the variant count of the Bloom route's light side: written, never read
+  unsigned long long pad0[2];
+  uint32_t length_classes[4];          // k_fast_length_classes: longest sequence <= cap, amplicons > cap, amplicons >= cap - 1, unused
+  unsigned long long pad1[2];
+};
+static_assert(std::is_standard_layout<swa_fast_counters>::value, "fastidious counters: plain data");
+static_assert(sizeof(swa_fast_counters) == 128, "fastidious counters: sixteen 64-bit words");
+static_assert(offsetof(swa_fast_counters, light_variants) == 0 && offsetof(swa_fast_counters, heavy_variants) == 8 &&
+              offsetof(swa_fast_counters, candidates) == 16 && offsetof(swa_fast_counters, batch_tasks) == 24 &&
+              offsetof(swa_fast_counters, batch_variants) == 32 && offsetof(swa_fast_counters, pairs) == 40 &&
+              offsetof(swa_fast_counters, bands) == 48 && offsetof(swa_fast_counters, scratch) == 72 &&
+              offsetof(swa_fast_counters, pad0) == 80 && offsetof(swa_fast_counters, length_classes) == 96 &&
+              offsetof(swa_fast_counters, pad1) == 112,
+              "fastidious counters: every member lies on the word the pass has always used for it");
+
 // dn_graph.hip keeps a count per sequence length below this: 16 (d + 1) + d for d <= 16, the lengths a short sequence can pair with
 #define SWA_DN_HIST_LEN 288u
 
@@ -161,7 +188,7 @@ struct swa_d1_index {
   // anchored d=1 index (d1_anchor.inc, d1_stream.inc): [0] prefix groups, [1] suffix groups
   bool anchor_usable = false;    // decided by swa_d1_index_build: lengths fit, db order holds, not switched off
   bool anchor_ready = false;     // the streaming index below exists (for the owner in owner_rank / owner_world)
-  bool full_index = false;       // d_seqhash / d_aux cover ALL amplicons and d_table / d_bloom are built (ensure_full_index)
+  bool full_index = false;       // d_seqhash / d_aux cover ALL amplicons and d_table / d_bloom are built (swa_ensure_full_index)
   uint32_t anchor_a = 0, anchor_b = 0;   // anchor windows moved inwards by this many nt ("window mode", chosen at index build)
   uint32_t anchor_w = 32;        // width of the anchor windows in nt: 32, 64 or 128 (wider: fewer pairs per group; needs 2 w + 1 nt)
   bool head_clear_pending = false;   // index_build has left the clear of the status block's head to the streaming build's own clear
@@ -236,7 +263,7 @@ struct swa_ctx {
   swa_dbuf d_seqs, d_seq_off, d_seqlen, d_abund;
 
   // d=1 index
-  uint32_t zobrist_len = 0;      // positions in the Zobrist table (longest + 2; set by whoever hashes: prepare_hashing)
+  uint32_t zobrist_len = 0;      // positions in the Zobrist table (longest + 2; set by whoever hashes: swa_prepare_hashing)
   uint32_t zobrist_resident = 0; // length of the table currently in d_zobrist (0 = none)
   bool patterns_resident = false;
   swa_dbuf d_zobrist, d_seqhash, d_table, d_bloom, d_patterns;
@@ -337,6 +364,22 @@ inline void swa_lap(swa_ctx * ctx, const char * what);
 int swa_reserve(swa_ctx * ctx, swa_dbuf & buf, size_t bytes);   // grow-only hipMalloc
 void swa_release(swa_dbuf & buf);
 int swa_hash_sequences(swa_ctx * ctx);                           // d1.hip: Zobrist table + d_seqhash + d_aux
+
+// ---- what fastidious.hip takes from d1.hip ----------------------------------------------------------------------------
+// Host functions, defined in d1.hip, whose kernels stay in its code object.  All enqueue on ctx->stream and return SWA_OK
+// or the error they recorded.
+int swa_prepare_hashing(swa_ctx * ctx);        // the Zobrist table for this database's longest sequence in HBM (uploaded when its length changes), room for d_seqhash / d_aux
+int swa_ensure_full_index(swa_ctx * ctx);      // hashes of ALL amplicons, the database-wide table and its Bloom filter: built unless swa_d1_index::full_index says they stand
+int swa_launch_abundance_rank(swa_ctx * ctx);  // d_arank, once per upload; raises (or restores) kFlagUnordered
+int swa_ensure_lines(swa_ctx * ctx);           // the amplicon lines (d_stream[kSbLines]), once per upload and line width; needs the abundance ranks
+int swa_grid_for(const swa_ctx * ctx, uint64_t items, int per_block, int max_per_cu);   // workgroups for `items` at per_block each: 1 .. num_cus * max_per_cu
+// exclusive scan of counts[0, n) into the 64-bit offsets[0, n] (three launches); the caller has reserved d_scan_tmp: a uint64_t
+// per kScanOffsetsTile counts
+constexpr uint32_t kScanOffsetsTile = 2048;
+int swa_scan_offsets(swa_ctx * ctx, const uint32_t * counts, uint32_t n, uint64_t * offsets);
+// d_table / d_bloom cleared and refilled with the amplicons whose byte in d_is_member is not 0 (nullptr: all of them);
+// hashes and room as swa_ensure_full_index left them
+int swa_d1_rebuild_table(swa_ctx * ctx, const uint8_t * d_is_member);
 // dn_graph.hip, for multi.hip: the (partial, under ownership) graph computed and left sorted in HBM — d_dn_keys / d_dn_vals
 // from entry dn_work on, dn_edges entries —, and a sorted (query << 32 | target, diff) list written out as the CSR of swa_dn_graph
 int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking);
@@ -377,7 +420,7 @@ void swa_zobrist_table(uint32_t zobrist_len, std::vector<uint64_t> & tab);    //
 void swa_bloom_patterns(uint32_t count, uint32_t k, std::vector<uint64_t> & pat); // src/bloompat.cc:74-90, src/bloomflex.cc:72-88
 uint64_t swa_hashtable_size(uint64_t n);                                       // src/utils/hashtable_size.cc:29-42
 
-// Every choice of the --fastidious pass (host_tables.cpp: pure arithmetic; d1.hip launches from it, swa_d1_fastidious_plan
+// Every choice of the --fastidious pass (host_tables.cpp: pure arithmetic; fastidious.hip launches from it, swa_d1_fastidious_plan
 // and swa_d1_fastidious_plan_for report it)
 #define SWA_FAST_MIN_LEN 112u                       // both sequences at least this long => the pair route is complete (d1_fast.inc)
 #define SWA_MAX_ZOBRIST_LDS (96u * 1024u)           // the Zobrist table sits in LDS up to this many bytes
