@@ -462,6 +462,24 @@ int swa_d1_graft_candidates_fetch(swa_ctx * ctx, uint32_t * graft_cand);
    caller allocates u32[n].  Independent of swa_d1_index_build, and invalidates a d = 1 index
    built on the same context. */
 int swa_derep(swa_ctx * ctx, uint32_t * first_identical);
+/* The same search without the download: first_identical stays in HBM for swa_d0_cluster_device (swa_derep is this plus
+   the copy).  What ends it, and the tables made from it: an upload or attach, the next swa_derep / swa_derep_resident,
+   and the calls that reuse its buffer for graft candidates (swa_d1_fastidious*, swa_d1_graft_device). */
+int swa_derep_resident(swa_ctx * ctx);
+/* The clustering of dereplicating() and its order (src/derep.cc:276-354 and 67-90) made on the device from the resident
+   array: what swa_d0_cluster of the host header makes, array for array.  Clusters in output order — mass descending, ties
+   by the seed's db index ascending —, each with its seed (first member in db order), mass (sum of the members'
+   abundances), size, singletons (members of abundance 1) and begin: its members are members[begin, begin + size),
+   ascending db index, the seed first (members[] is grouped by cluster in SEED order, as the host's is).
+   summary3 (may be NULL) = {clusters, largest size, heaviest mass}  (src/derep.cc:405-410).
+   SWA_E_ARG with a message without a resident array.  Integer sums, maxima and stable sorts only: nothing depends on
+   scheduling.
+   swa_d0_cluster_fetch copies out any of the six arrays (NULL: not wanted): the five cluster arrays hold cluster_cap
+   entries, members n.  *clusters (may be NULL) = the number of clusters; SWA_E_CAPACITY when a cluster array is wanted
+   and cluster_cap is smaller than that (nothing is copied then).  SWA_E_ARG with a message without tables in place. */
+int swa_d0_cluster_device(swa_ctx * ctx, uint64_t * summary3);
+int swa_d0_cluster_fetch(swa_ctx * ctx, uint32_t * seed, uint64_t * mass, uint32_t * size, uint32_t * singletons,
+                         uint32_t * begin, uint32_t cluster_cap, uint32_t * members, uint32_t * clusters);
 
 /* ---- B3: q-gram prefilter -------------------------------------------------------- */
 /* 1024-bit 5-mer parity signature per amplicon (src/qgram.cc:68-96), kept in HBM */

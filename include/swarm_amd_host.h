@@ -151,8 +151,18 @@ uint64_t swa_nw_align_host(const uint64_t * dseq, uint32_t dlen, const uint64_t 
    is the seed; clusters by decreasing mass, then by seed index (src/derep.cc:67-90). */
 typedef struct swa_d0_result swa_d0_result;
 int  swa_d0_cluster(const swa_hostdb * db, const uint32_t * first_identical, swa_d0_result ** out);
+/* The same result with the clustering made on the device (src/derep.cc:276-354, 67-90): swa_derep_resident has left
+   first_identical in HBM on `ctx`, swa_d0_cluster_device makes the tables there and swa_d0_cluster_fetch brings them
+   home.  No first_identical array on the host; every writer below works on the result unchanged. */
+int  swa_d0_cluster_resident(swa_ctx * ctx, const swa_hostdb * db, swa_d0_result ** out);
 void swa_d0_result_free(swa_d0_result * res);
-/* out3 = {clusters, largest cluster (members), heaviest cluster (mass)}  (src/derep.cc:405-410) */
+/* A result of either origin as plain arrays, in output order: seed, mass, size, singletons and begin of every cluster
+   (cluster_cap entries each) and members[n] — cluster c's are members[begin[c], begin[c] + size[c]), db order, seed first.
+   Any array may be NULL.  *clusters (may be NULL) = the number of clusters; SWA_E_CAPACITY when a cluster array is wanted
+   and cluster_cap is smaller (nothing is copied then). */
+int  swa_d0_result_tables(const swa_d0_result * res, uint32_t * seed, uint64_t * mass, uint32_t * size, uint32_t * singletons,
+                          uint32_t * begin, uint32_t cluster_cap, uint32_t * members, uint32_t * clusters);
+/* out3 ={clusters, largest cluster (members), heaviest cluster (mass)}  (src/derep.cc:405-410) */
 void swa_d0_result_summary(const swa_d0_result * res, uint64_t * out3);
 /* writers: src/derep.cc:207-273 (-o / -r), 188-204 (-w), 107-124 (-s), 127-148 (-i), 151-185 (-u) */
 int swa_d0_write_swarms(const swa_d0_result * res, const swa_hostdb * db, const char * path, int mothur,

@@ -551,6 +551,39 @@ class Context:
         self._keep = (seqs, seq_off, seqlen, abundance)
         self.n = n
 
+    # ---- d = 0 on the device
+    def derep_resident(self) -> None:
+        """swa_derep_resident: the identical-sequence search with its array left in HBM (for d0_cluster_device)."""
+        _declare_d0(self.lib)
+        self._check(self.lib.swa_derep_resident(self.h))
+
+    def d0_cluster_device(self) -> dict:
+        """swa_d0_cluster_device + swa_d0_cluster_fetch: the clusters of the resident dereplication, made on the GPU.  The six
+        arrays in output order (mass descending, then seed ascending) — seed, mass (u64), size, singletons, begin, and
+        members[n] — plus the summary's three numbers."""
+        _declare_d0(self.lib)
+        s = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.swa_d0_cluster_device(self.h, _p64(s)))
+        out = self.d0_cluster_fetch(int(s[0]))
+        out.update(swarms=int(s[0]), largest=int(s[1]), heaviest=int(s[2]))
+        return out
+
+    def d0_cluster_fetch(self, cluster_cap: int | None = None) -> dict:
+        """swa_d0_cluster_fetch alone: the arrays of the tables in place (cluster_cap None: asked for first)."""
+        _declare_d0(self.lib)
+        nc = C.c_uint32(0)
+        if cluster_cap is None:
+            self._check(self.lib.swa_d0_cluster_fetch(self.h, None, None, None, None, None, 0, None, C.byref(nc)))
+            cluster_cap = int(nc.value)
+        u32 = {k: np.zeros(cluster_cap, dtype=np.uint32) for k in ("seed", "size", "singletons", "begin")}
+        mass = np.zeros(cluster_cap, dtype=np.uint64)
+        members = np.zeros(self.n, dtype=np.uint32)
+        self._check(self.lib.swa_d0_cluster_fetch(self.h, _ptr(u32["seed"]), _ptr(mass), _ptr(u32["size"]), _ptr(u32["singletons"]),
+                                                  _ptr(u32["begin"]), cluster_cap, _ptr(members), C.byref(nc)))
+        c = int(nc.value)
+        return {"seed": u32["seed"][:c], "mass": mass[:c], "size": u32["size"][:c], "singletons": u32["singletons"][:c],
+                "begin": u32["begin"][:c], "members": members}
+
     # ---- B1
     def d1_index_build(self, first: int = 0, count: int | None = None) -> bool:
         """Returns True when duplicate sequences were found (the reference aborts in that case).
@@ -1225,7 +1258,8 @@ class DnClusters:
 
 # ---- d = 0: dereplication ----------------------------------------------------------------------
 
-_D0_EXPORTS = ["swa_derep", "swa_d0_cluster", "swa_d0_result_free", "swa_d0_result_summary", "swa_d0_write_swarms",
+_D0_EXPORTS = ["swa_derep", "swa_derep_resident", "swa_d0_cluster_device", "swa_d0_cluster_fetch", "swa_d0_cluster_resident",
+               "swa_d0_result_tables", "swa_d0_cluster", "swa_d0_result_free", "swa_d0_result_summary", "swa_d0_write_swarms",
                "swa_d0_write_seeds", "swa_d0_write_stats", "swa_d0_write_structure", "swa_d0_write_uclust"]
 EXPORTS.extend(_D0_EXPORTS)
 
@@ -1235,6 +1269,13 @@ def _declare_d0(lib) -> None:
         return
     lib.swa_derep.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d0_cluster.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.swa_derep_resident.argtypes = [C.c_void_p]
+    lib.swa_d0_cluster_device.argtypes = [C.c_void_p, u64p]
+    lib.swa_d0_cluster_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                         C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.swa_d0_cluster_resident.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.swa_d0_result_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                         C.c_void_p, C.POINTER(C.c_uint32)]
     lib.swa_d0_result_free.argtypes = [C.c_void_p]
     lib.swa_d0_result_free.restype = None
     lib.swa_d0_result_summary.argtypes = [C.c_void_p, u64p]
@@ -1255,7 +1296,8 @@ def derep(ctx: "Context") -> np.ndarray:
 
 
 class D0Clusters:
-    """d = 0 clustering (src/derep.cc) from swa_derep's array; host side only."""
+    """d = 0 clustering (src/derep.cc): from swa_derep's array on the host, or — from_device — from the tables the GPU makes
+    of the resident array.  The writers work on either."""
 
     def __init__(self, hdb: HostDb, first_identical: np.ndarray):
         self.lib = load_library()
@@ -1267,6 +1309,33 @@ class D0Clusters:
         if rc != SWA_OK:
             raise SwaError(rc, "swa_d0_cluster failed")
         self.h = h
+
+    @classmethod
+    def from_device(cls, ctx: "Context", hdb: HostDb) -> "D0Clusters":
+        """swa_d0_cluster_resident: ctx.derep_resident() has run on hdb's database; the clusters are made on the GPU."""
+        self = cls.__new__(cls)
+        self.lib = ctx.lib
+        _declare_d0(self.lib)
+        self.hdb = hdb
+        h = C.c_void_p()
+        ctx._check(self.lib.swa_d0_cluster_resident(ctx.h, hdb.h, C.byref(h)))
+        self.h = h
+        return self
+
+    def tables(self) -> dict:
+        """swa_d0_result_tables: seed, mass, size, singletons, begin of every cluster in output order, members[n], and the
+        summary — the same keys as Context.d0_cluster_device."""
+        nc = C.c_uint32(0)
+        assert self.lib.swa_d0_result_tables(self.h, None, None, None, None, None, 0, None, C.byref(nc)) == SWA_OK
+        c = int(nc.value)
+        u32 = {k: np.zeros(c, dtype=np.uint32) for k in ("seed", "size", "singletons", "begin")}
+        mass = np.zeros(c, dtype=np.uint64)
+        members = np.zeros(self.hdb.n, dtype=np.uint32)
+        assert self.lib.swa_d0_result_tables(self.h, _ptr(u32["seed"]), _ptr(mass), _ptr(u32["size"]), _ptr(u32["singletons"]),
+                                             _ptr(u32["begin"]), c, _ptr(members), C.byref(nc)) == SWA_OK
+        out = dict(u32, mass=mass, members=members)
+        out.update(self.summary())
+        return out
 
     def summary(self) -> dict:
         out = np.zeros(3, dtype=np.uint64)

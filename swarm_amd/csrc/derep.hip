@@ -15,6 +15,10 @@
 // re-mixed key until nobody is left.
 #include "swa_internal.h"
 
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+
 namespace {
 
 // key of hash h in round `round`: the hash itself first, a splitmix64 re-mix of it afterwards.
@@ -74,10 +78,11 @@ __global__ __launch_bounds__(256) void k_derep_resolve(const uint64_t * __restri
 
 }  // namespace
 
-extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
+// What swa_derep does up to the download: first_identical stays in HBM (d_graft) for swa_d0_cluster_device.
+extern "C" int swa_derep_resident(swa_ctx * ctx) {
   if (ctx == nullptr) { return SWA_E_ARG; }
+  ctx->dr = {};                                             // the previous dereplication and its tables end here
   if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: no database"); }
-  if (first_identical == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: bad argument"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
   SWA_TRY(swa_hash_sequences(ctx));
@@ -124,7 +129,240 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
     active = next;
     count = left;
   }
-  SWA_HIP(ctx, hipMemcpyAsync(first_identical, result, uint64_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->dr.first_ready = true;
+  return SWA_OK;
+}
+
+extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: no database"); }
+  if (first_identical == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: bad argument"); }
+  SWA_TRY(swa_derep_resident(ctx));
+  SWA_HIP(ctx, hipMemcpyAsync(first_identical, ctx->d_graft.ptr, uint64_t(ctx->db.n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
+// ---- the clusters, their sums and their order, from the resident array (src/derep.cc:276-354, 67-90) --------------------
+// swa_d0_cluster (host/cluster_d0.cpp) walks first_identical[] twice with one thread and sorts the clusters; everything it
+// makes is integer sums, a stable grouping and a stable order, all of it a function of first_identical[] and abundance[],
+// which are both in HBM.  Here:
+//
+//   k_d0_seed_flags   flag[i] = first[i] == i; rocPRIM's exclusive scan of the flags numbers the clusters in db order (=
+//                     seed order) and counts them
+//   k_d0_keys         (cluster number of first[i], i); one stable radix sort over the bits the cluster count needs groups
+//                     the members, ascending db index inside every cluster: the layout of swa_d0_result::members
+//   k_d0_sums         one position per lane over the grouped order: the cluster number never falls along it, so a wave sums
+//                     its runs of equal numbers with a segmented scan and the last lane of a run writes — a plain store
+//                     when the run is the whole cluster, one atomic per (wave, cluster) otherwise (a sequence with 10^6
+//                     copies: 15 625 atomics on its words); the first position of a cluster writes its seed and begin
+//   k_d0_maxima       largest size and heaviest mass, a wave's maximum per atomic
+//   k_d0_order_keys   heaviest - mass: one stable radix sort of the cluster numbers over the bits the heaviest mass needs
+//                     leaves them by mass descending, ties in seed order as they went in
+//   k_d0_gather       the five tables in that order
+// Nothing depends on scheduling: sums, maxima and stable sorts of integers.
+namespace {
+
+// d_d0: five arrays of n words — rank (cluster number of a seed) | keys in | keys out | ids in | members
+struct D0Work { uint32_t * rank, * keys_in, * keys_out, * ids_in, * members; };
+D0Work d0_work(const swa_ctx * ctx) {
+  const uint64_t n = ctx->db.n;
+  auto * rank = static_cast<uint32_t *>(ctx->d_d0.ptr);
+  return D0Work{rank, rank + n, rank + 2 * n, rank + 3 * n, rank + 4 * n};
+}
+
+// d_d0_tab, c = clusters: maxima (heaviest u64, largest u64) | mass u64[c] seed order | order keys in, out u64[c] | mass u64[c]
+// output order | then u32[c] each: seed, size, singletons, begin in seed order | numbers in, out | seed, size, singletons,
+// begin in output order
+struct D0Tables {
+  unsigned long long * maxima, * mass_s, * okeys_in, * okeys_out, * mass;
+  uint32_t * seed_s, * size_s, * singles_s, * begin_s, * num_in, * num_out, * seed, * size, * singles, * begin;
+};
+constexpr uint64_t d0_tables_bytes(uint64_t c) { return 16 + 4 * c * 8 + 10 * c * 4; }
+D0Tables d0_tables(const swa_ctx * ctx, uint64_t c) {
+  auto * maxima = static_cast<unsigned long long *>(ctx->d_d0_tab.ptr);
+  auto * mass_s = maxima + 2;
+  auto * seed_s = reinterpret_cast<uint32_t *>(mass_s + 4 * c);
+  return D0Tables{maxima, mass_s, mass_s + c, mass_s + 2 * c, mass_s + 3 * c,
+                  seed_s, seed_s + c, seed_s + 2 * c, seed_s + 3 * c, seed_s + 4 * c, seed_s + 5 * c,
+                  seed_s + 6 * c, seed_s + 7 * c, seed_s + 8 * c, seed_s + 9 * c};
+}
+
+__global__ __launch_bounds__(256) void k_d0_seed_flags(const uint32_t * __restrict__ first, uint32_t n, uint32_t * __restrict__ flag) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    flag[i] = first[i] == (uint32_t)i ? 1u : 0u;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_d0_keys(const uint32_t * __restrict__ first, const uint32_t * __restrict__ rank, uint32_t n,
+                                                 uint32_t * __restrict__ keys, uint32_t * __restrict__ ids) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    keys[i] = rank[first[i]];
+    ids[i] = (uint32_t)i;
+  }
+}
+
+// The lanes of a wave hold keys that never fall from lane to lane: every run of equal keys is summed into its LAST lane
+// (the segmented inclusive scan of fast_graft.inc's wave_run_reduce, with the three sums d = 0 needs).  Every lane takes part.
+__device__ __forceinline__ void d0_run_reduce(uint32_t key, unsigned long long & mass, uint32_t & singles, uint32_t & count) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t key2 = __shfl_up(key, d, 64);
+    const unsigned long long mass2 = swa_shfl_up_u64(mass, d);
+    const uint32_t singles2 = __shfl_up(singles, d, 64), count2 = __shfl_up(count, d, 64);
+    if (lane >= d && key2 == key) { mass += mass2; singles += singles2; count += count2; }
+  }
+}
+
+// cluster[k] = the cluster number of position k of the grouped order (never falls along k), members[k] the amplicon there.
+// mass / size / singles were cleared before the launch.
+__global__ __launch_bounds__(256) void k_d0_sums(const uint32_t * __restrict__ cluster, const uint32_t * __restrict__ members,
+                                                 const uint64_t * __restrict__ abundance, uint32_t n, unsigned long long * mass,
+                                                 uint32_t * size, uint32_t * singles, uint32_t * __restrict__ seed, uint32_t * __restrict__ begin) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t span = ((uint64_t)n + 63u) & ~uint64_t(63);          // whole waves take part
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < span; k += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t c = SWA_NO_AMPLICON, single = 0, count = 0;              // (beyond the order: a run of its own that writes nothing)
+    unsigned long long m = 0;
+    if (k < n) {
+      c = cluster[k];
+      const uint32_t a = members[k];
+      m = abundance[a]; single = m == 1ull ? 1u : 0u; count = 1;
+      if (k == 0 || cluster[k - 1] != c) { seed[c] = a; begin[c] = (uint32_t)k; }   // the cluster's first position: its seed
+    }
+    d0_run_reduce(c, m, single, count);
+    const uint32_t next = __shfl_down(c, 1, 64);
+    if (k >= n || (lane != 63u && next == c)) { continue; }           // (not the last lane of its run)
+    // the run [k + 1 - count, k]: the whole cluster when nothing of it lies in front of or behind it — nobody else writes its sums
+    const uint64_t start = k + 1 - count;
+    const bool whole = (start == 0 || cluster[start - 1] != c) && (k + 1 == n || cluster[k + 1] != c);
+    if (whole) { mass[c] = m; size[c] = count; singles[c] = single; }
+    else { atomicAdd(&mass[c], m); atomicAdd(&size[c], count); atomicAdd(&singles[c], single); }
+  }
+}
+
+// maxima[0] = heaviest mass, maxima[1] = largest size (cleared before the launch): a wave's maxima per atomic
+__global__ __launch_bounds__(256) void k_d0_maxima(const unsigned long long * __restrict__ mass, const uint32_t * __restrict__ size,
+                                                   uint32_t clusters, unsigned long long * maxima) {
+  unsigned long long heavy = 0, large = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < clusters; c += (uint64_t)gridDim.x * blockDim.x) {
+    heavy = mass[c] > heavy ? mass[c] : heavy;
+    large = size[c] > large ? size[c] : large;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned long long h2 = swa_shfl_xor_u64(heavy, d), l2 = swa_shfl_xor_u64(large, d);
+    heavy = h2 > heavy ? h2 : heavy;
+    large = l2 > large ? l2 : large;
+  }
+  if ((threadIdx.x & 63u) == 0u && large != 0ull) { atomicMax(&maxima[0], heavy); atomicMax(&maxima[1], large); }
+}
+
+__global__ __launch_bounds__(256) void k_d0_order_keys(const unsigned long long * __restrict__ mass, unsigned long long heaviest,
+                                                       uint32_t clusters, unsigned long long * __restrict__ keys, uint32_t * __restrict__ num) {
+  for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < clusters; c += (uint64_t)gridDim.x * blockDim.x) {
+    keys[c] = heaviest - mass[c];
+    num[c] = (uint32_t)c;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_d0_gather(D0Tables t, uint32_t clusters) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < clusters; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t c = t.num_out[r];
+    t.mass[r] = t.mass_s[c]; t.seed[r] = t.seed_s[c]; t.size[r] = t.size_s[c]; t.singles[r] = t.singles_s[c]; t.begin[r] = t.begin_s[c];
+  }
+}
+
+uint32_t d0_bit_width(uint64_t v) { uint32_t b = 0; while (v != 0u) { ++b; v >>= 1; } return b; }
+
+}  // namespace
+
+extern "C" int swa_d0_cluster_device(swa_ctx * ctx, uint64_t * summary3) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (!ctx->dr.first_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d0_cluster_device: no resident first_identical array (call swa_derep_resident first)"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->dr.tables_ready = false;
+  const uint32_t n = ctx->db.n;
+  const auto * first = static_cast<const uint32_t *>(ctx->d_graft.ptr);
+  SWA_TRY(swa_reserve(ctx, ctx->d_d0, (uint64_t)n * 5 * sizeof(uint32_t)));
+  const D0Work w = d0_work(ctx);
+  const dim3 g((unsigned)swa_grid_for(ctx, n, 256, 8)), b(256);
+  // rocPRIM's scratch: the most any of the three calls asks for at n items (the clusters are never more)
+  size_t tmp_bytes = 0, need = 0;
+  auto * k64 = static_cast<unsigned long long *>(nullptr);
+  (void)rocprim::exclusive_scan(nullptr, need, w.keys_in, w.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
+  tmp_bytes = std::max(tmp_bytes, need);
+  (void)rocprim::radix_sort_pairs(nullptr, need, w.keys_in, w.keys_out, w.ids_in, w.members, (size_t)n, 0, 32, ctx->stream);
+  tmp_bytes = std::max(tmp_bytes, need);
+  (void)rocprim::radix_sort_pairs(nullptr, need, k64, k64, w.ids_in, w.members, (size_t)n, 0, 64, ctx->stream);
+  tmp_bytes = std::max(tmp_bytes, need);
+  SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, tmp_bytes + 16));
+  // ---- cluster numbers in seed order, and how many
+  hipLaunchKernelGGL(k_d0_seed_flags, g, b, 0, ctx->stream, first, n, w.keys_in);
+  need = tmp_bytes;
+  SWA_HIP(ctx, rocprim::exclusive_scan(ctx->d_scan_hits.ptr, need, w.keys_in, w.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
+  uint32_t last_rank = 0, last_first = 0;
+  SWA_HIP(ctx, hipMemcpyAsync(&last_rank, w.rank + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(&last_first, first + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  hipLaunchKernelGGL(k_d0_keys, g, b, 0, ctx->stream, first, w.rank, n, w.keys_in, w.ids_in);     // (needs no count: queued in front of the wait)
+  SWA_HIP(ctx, hipGetLastError());
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint32_t clusters = last_rank + (last_first == n - 1 ? 1u : 0u);
+  if (clusters == 0 || clusters > n) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_d0_cluster_device: the resident array has no seed"); }
+  // ---- members grouped by cluster, db order inside (zero key bits — one cluster — sort on one bit that is 0 everywhere)
+  need = tmp_bytes;
+  SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, w.keys_in, w.keys_out, w.ids_in, w.members, (size_t)n, 0,
+                                         std::max(1u, d0_bit_width(clusters - 1u)), ctx->stream));
+  // ---- sums over the runs, seeds, begins; the maxima
+  SWA_TRY(swa_reserve(ctx, ctx->d_d0_tab, d0_tables_bytes(clusters)));
+  const D0Tables t = d0_tables(ctx, clusters);
+  const dim3 gc((unsigned)swa_grid_for(ctx, clusters, 256, 8));
+  SWA_HIP(ctx, hipMemsetAsync(t.maxima, 0, 16 + (uint64_t)clusters * 8, ctx->stream));                       // maxima, mass_s
+  SWA_HIP(ctx, hipMemsetAsync(t.size_s, 0, (uint64_t)clusters * 2 * sizeof(uint32_t), ctx->stream));          // size_s, singles_s
+  hipLaunchKernelGGL(k_d0_sums, g, b, 0, ctx->stream, w.keys_out, w.members, ctx->db.abundance, n, t.mass_s, t.size_s, t.singles_s, t.seed_s, t.begin_s);
+  hipLaunchKernelGGL(k_d0_maxima, gc, b, 0, ctx->stream, t.mass_s, t.size_s, clusters, t.maxima);
+  SWA_HIP(ctx, hipGetLastError());
+  unsigned long long maxima[2] = {0, 0};
+  SWA_HIP(ctx, hipMemcpyAsync(maxima, t.maxima, sizeof(maxima), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // ---- output order: mass descending, seed order among equals (the numbers go in ascending: the sort is stable)
+  hipLaunchKernelGGL(k_d0_order_keys, gc, b, 0, ctx->stream, t.mass_s, maxima[0], clusters, t.okeys_in, t.num_in);
+  need = tmp_bytes;
+  SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, t.okeys_in, t.okeys_out, t.num_in, t.num_out, (size_t)clusters, 0,
+                                         std::max(1u, d0_bit_width(maxima[0])), ctx->stream));
+  hipLaunchKernelGGL(k_d0_gather, gc, b, 0, ctx->stream, t, clusters);
+  SWA_HIP(ctx, hipGetLastError());
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->dr.tables_ready = true;
+  ctx->dr.clusters = clusters;
+  ctx->dr.largest = (uint32_t)maxima[1];
+  ctx->dr.heaviest = maxima[0];
+  if (summary3 != nullptr) { summary3[0] = clusters; summary3[1] = maxima[1]; summary3[2] = maxima[0]; }
+  return SWA_OK;
+}
+
+extern "C" int swa_d0_cluster_fetch(swa_ctx * ctx, uint32_t * seed, uint64_t * mass, uint32_t * size, uint32_t * singletons, uint32_t * begin,
+                                    uint32_t cluster_cap, uint32_t * members, uint32_t * clusters) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (!ctx->dr.tables_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d0_cluster_fetch: no cluster tables in place (call swa_d0_cluster_device first)"); }
+  const uint32_t c = ctx->dr.clusters, n = ctx->db.n;
+  if (clusters != nullptr) { *clusters = c; }
+  const bool wants_tables = seed != nullptr || mass != nullptr || size != nullptr || singletons != nullptr || begin != nullptr;
+  if (wants_tables && cluster_cap < c) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d0_cluster_fetch: cluster arrays too small"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  const D0Tables t = d0_tables(ctx, c);
+  // the host pages are faulted in BEFORE any copy into them is queued (see swa_d1_cluster_device)
+  swa_touch_pages(members, (uint64_t)n * sizeof(uint32_t));
+  swa_touch_pages(mass, (uint64_t)c * sizeof(uint64_t));
+  for (uint32_t * out : {seed, size, singletons, begin}) { swa_touch_pages(out, (uint64_t)c * sizeof(uint32_t)); }
+  if (members != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(members, d0_work(ctx).members, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
+  if (mass != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(mass, t.mass, (uint64_t)c * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream)); }
+  const uint32_t * from[4] = {t.seed, t.size, t.singles, t.begin};
+  uint32_t * to[4] = {seed, size, singletons, begin};
+  for (int k = 0; k < 4; ++k) {
+    if (to[k] != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(to[k], from[k], (uint64_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
+  }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SWA_OK;
 }

@@ -280,6 +280,7 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
   if (ctx->res.fast.sums_grafted) { ctx->res.fast.sums_ready = false; ctx->res.fast.sums_grafted = false; }   // (every call grows the swarms' own sums)
   SWA_TRY(ensure_swarm_sums(ctx));
   SWA_TRY(swa_reserve(ctx, ctx->d_graft, (uint64_t)n * sizeof(uint32_t)));
+  ctx->dr = {};                                             // (d_graft: candidates from here on, no dereplication's array)
   SWA_TRY(swa_reserve(ctx, ctx->d_graft_work, kCtlWords * sizeof(uint64_t) + (uint64_t)w * 32));
   auto * ctl = static_cast<unsigned long long *>(ctx->d_graft_work.ptr);
   auto * slot = ctl + kCtlWords, * pairs0 = slot + w, * pairs1 = pairs0 + w;

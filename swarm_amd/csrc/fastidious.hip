@@ -525,6 +525,7 @@ static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint6
   SWA_TRY(swa_reserve(ctx, ctx->d_frole, n));
   SWA_TRY(swa_reserve(ctx, ctx->d_light, n));
   SWA_TRY(swa_reserve(ctx, ctx->d_graft, uint64_t(n) * sizeof(uint32_t)));
+  ctx->dr = {};                                             // (d_graft no longer holds a dereplication's array)
   SWA_TRY(swa_reserve(ctx, ctx->d_list_a, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_list_b, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, sizeof(swa_fast_counters)));

@@ -23,7 +23,7 @@ struct swa_d0_result {
     uint32_t begin = 0;                     // members = members[begin, begin + size), db order, seed first
   };
   std::vector<Cluster> clusters;            // output order
-  std::vector<uint32_t> members;
+  swa_vec<uint32_t> members;                // (default-initialised: the device route's copy or the loop below writes all of it)
   uint64_t heaviest = 0;
   uint32_t largest = 0;
 };
@@ -68,7 +68,56 @@ extern "C" int swa_d0_cluster(const swa_hostdb * db, const uint32_t * first_iden
   return SWA_OK;
 }
 
+// The same result from the tables swa_d0_cluster_device makes in HBM (derep.hip): no first_identical array on the host, no
+// serial walk, no sort.  The members' pages are faulted in by swa_d0_cluster_fetch itself BEFORE it queues the copy into
+// them (several threads, a byte a page); they are not pinned: the array receives one copy, and registering it was not measured to pay.
+extern "C" int swa_d0_cluster_resident(swa_ctx * ctx, const swa_hostdb * db, swa_d0_result ** out) {
+  if (ctx == nullptr || db == nullptr || out == nullptr) { return SWA_E_ARG; }
+  *out = nullptr;
+  uint64_t sum[3] = {0, 0, 0};
+  const int rc = swa_d0_cluster_device(ctx, sum);
+  if (rc != SWA_OK) { return rc; }
+  const uint32_t nc = (uint32_t)sum[0];
+  auto * r = new swa_d0_result();
+  r->largest = (uint32_t)sum[1];
+  r->heaviest = sum[2];
+  r->members.resize(db->n);
+  swa_vec<uint64_t> mass(nc);
+  swa_vec<uint32_t> words((size_t)nc * 4);
+  uint32_t * seed = words.data(), * size = seed + nc, * singles = size + nc, * begin = singles + nc;
+  const int frc = swa_d0_cluster_fetch(ctx, seed, mass.data(), size, singles, begin, nc, r->members.data(), nullptr);
+  if (frc != SWA_OK) { delete r; return frc; }
+  r->clusters.resize(nc);
+#pragma omp parallel for schedule(static) if (nc >= kParallelOutputFrom)
+  for (uint32_t c = 0; c < nc; ++c) {
+    auto & k = r->clusters[c];
+    k.mass = mass[c]; k.seed = seed[c]; k.size = size[c]; k.singletons = singles[c]; k.begin = begin[c];
+  }
+  *out = r;
+  return SWA_OK;
+}
+
 extern "C" void swa_d0_result_free(swa_d0_result * r) { delete r; }
+
+// a result of either origin as plain arrays, output order
+extern "C" int swa_d0_result_tables(const swa_d0_result * r, uint32_t * seed, uint64_t * mass, uint32_t * size, uint32_t * singletons,
+                                    uint32_t * begin, uint32_t cluster_cap, uint32_t * members, uint32_t * clusters) {
+  if (r == nullptr) { return SWA_E_ARG; }
+  const size_t nc = r->clusters.size();
+  if (clusters != nullptr) { *clusters = (uint32_t)nc; }
+  const bool wants_tables = seed != nullptr || mass != nullptr || size != nullptr || singletons != nullptr || begin != nullptr;
+  if (wants_tables && cluster_cap < nc) { return SWA_E_CAPACITY; }
+  for (size_t c = 0; wants_tables && c < nc; ++c) {
+    const auto & k = r->clusters[c];
+    if (seed != nullptr) { seed[c] = k.seed; }
+    if (mass != nullptr) { mass[c] = k.mass; }
+    if (size != nullptr) { size[c] = k.size; }
+    if (singletons != nullptr) { singletons[c] = k.singletons; }
+    if (begin != nullptr) { begin[c] = k.begin; }
+  }
+  if (members != nullptr && !r->members.empty()) { std::memcpy(members, r->members.data(), r->members.size() * sizeof(uint32_t)); }
+  return SWA_OK;
+}
 
 // out3 = {clusters, largest (members), heaviest (mass)}: the log lines of src/derep.cc:405-410
 extern "C" void swa_d0_result_summary(const swa_d0_result * r, uint64_t * out3) {

@@ -5,7 +5,7 @@
 //
 //   d = 1      swa_d1_index_build + swa_d1_network -> swa_d1_cluster [-> swa_d1_fastidious -> graft]
 //   d >= 2     swa_dn_cluster (the whole graph of pairs within d at once, or one swa_scan_step per swarm generation)
-//   d = 0      swa_derep -> swa_d0_cluster
+//   d = 0      swa_derep_resident -> swa_d0_cluster_resident (SWARM_AMD_D0=host: swa_derep -> swa_d0_cluster)
 //
 // Environment (no new flags, to stay drop-in): SWARM_AMD_DEVICE = HIP device ordinal (default 0);
 // SWARM_AMD_DEVICES = 0,1,2,... : d >= 1 on several GPUs (swa_multi_*: one rank per entry, RCCL exchange).
@@ -383,11 +383,23 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
 
   long d1_detail_fetches = -1;              // (d = 1, for the closing line of SWARM_AMD_TIMING)
   if (o.differences == 0) {
-    // ---- d = 0: identical-sequence search on the GPU, cluster bookkeeping on the host
-    std::vector<uint32_t> first_identical(n);
-    if (n > 0 && swa_derep(ctx, first_identical.data()) != SWA_OK) { die(swa_last_error(ctx)); }
+    // ---- d = 0: identical-sequence search on the GPU; the clusters, their sums and their order are made there too, from the
+    // array where it lies (derep.hip) — the default by measurement (profiles/r21/NOTES.md) —, or, under SWARM_AMD_D0=host,
+    // by the host from the downloaded array (swa_d0_cluster): same files, same log
+    const char * d0_route = std::getenv("SWARM_AMD_D0");
+    const bool d0_device = !(d0_route != nullptr && std::strcmp(d0_route, "host") == 0);
     swa_d0_result * res = nullptr;
-    if (swa_d0_cluster(db, first_identical.data(), &res) != SWA_OK) { die("dereplication failed"); }
+    if (n > 0 && d0_device) {
+      if (swa_derep_resident(ctx) != SWA_OK) { die(swa_last_error(ctx)); }
+      stamp("dereplicated");                                 // (its last round has been waited for)
+      if (swa_d0_cluster_resident(ctx, db, &res) != SWA_OK) { die(swa_last_error(ctx)); }
+    } else {
+      std::vector<uint32_t> first_identical(n);
+      if (n > 0 && swa_derep(ctx, first_identical.data()) != SWA_OK) { die(swa_last_error(ctx)); }
+      stamp("dereplicated");
+      if (swa_d0_cluster(db, first_identical.data(), &res) != SWA_OK) { die("dereplication failed"); }
+    }
+    stamp("clusters made");
     phase(o, "Dereplicating:    ");
     phase(o, "Sorting:          ");
     check_writer(swa_d0_write_swarms(res, db, o.output.c_str(), o.mothur, o.usearch, o.append_abundance, o.differences), "output");

@@ -239,6 +239,16 @@ struct swa_resident {
   } fast;
 };
 
+// the dereplication in place (derep.hip): ended by swa_db_upload* / swa_db_attach, by the start of every swa_derep* and by
+// every call that writes d_graft, where its array lies (the --fastidious pass, swa_d1_graft_device with a caller's candidates)
+struct swa_derep_facts {
+  bool first_ready = false;      // d_graft holds first_identical[] of the database in place (swa_derep_resident)
+  bool tables_ready = false;     // d_d0 / d_d0_tab hold the clusters made from it (swa_d0_cluster_device; swa_d0_cluster_fetch)
+  uint32_t clusters = 0;         // ... so many of them,
+  uint32_t largest = 0;          // the members of the largest
+  uint64_t heaviest = 0;         // and the mass of the heaviest
+};
+
 struct swa_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -256,6 +266,7 @@ struct swa_ctx {
   swa_db_facts up;               // what is known of the uploaded database
   swa_d1_index ix;               // the d = 1 index in place
   swa_resident res;              // the resident network and its clustering
+  swa_derep_facts dr;            // the dereplication in place and its cluster tables
 
   // database (device pointers)
   swa_db_view db{};
@@ -329,6 +340,8 @@ struct swa_ctx {
   // --fastidious on the clustering in place (fast_graft.inc): the per-swarm sums, the role byte of every amplicon, and the
   // grafting's slots, winner lists and result arrays
   swa_dbuf d_swarm_sums, d_swarm_role, d_graft_work;
+  // d = 0 (derep.hip): the grouping's work arrays with the member order (n words each), and the cluster tables
+  swa_dbuf d_d0, d_d0_tab;
 
   // the uclust alignments (nw_trace.hip): the pairs per tier of the last batch (three LDS tiers, four wide tiers, host), how
   // many of them the widest tier certified but found the text buffer full, and the device buffers of one slice (d_nw_bits: the wide tiers'
