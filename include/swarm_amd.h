@@ -617,6 +617,23 @@ int swa_dn_graph(swa_ctx * ctx, int no_cluster_breaking, uint64_t * offsets, uin
    its parent in that clustering (0 for seeds; n bytes): radius(v) = radius(parent) + that (src/algo.cc:560-574). */
 int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uint64_t * total);
 int swa_dn_parent_diffs(swa_ctx * ctx, uint8_t * pdiff);
+/* What the writers need beyond the member order, made in HBM from that clustering instead of on the host (dn_tables.inc):
+   radius of every amplicon (pointer jumping along the parents, bit_width(deepest generation) rounds), mass / singletons /
+   deepest generation / deepest radius of every swarm, and the -i / -u links in acceptance order — the non-seed positions
+   of the member order, stably sorted by their parent's position; swarm s owns the links [begin[s] - s, begin[s + 1] - s - 1).
+   swa_dn_tables_device makes them and returns the sizes: *nswarms, *nlinks = n - *nswarms.  swa_dn_tables_fetch downloads
+   what the caller asks for: radius[n]; mass, singletons, maxgen (0 for a swarm of one), maxradius [nswarms each];
+   link_parent, link_child, link_generation, link_diff [nlinks each]; every output may be null.  Both return SWA_E_ARG
+   with a message when no clustering is in place or the resident network carries no differences (as
+   swa_dn_parent_diffs), the fetch also when no tables are in place; swa_dn_tables_device returns SWA_E_DEVICE ("a parent
+   without a link to its child") when a member's parent has no link to it (or one of 255 differences: the byte that
+   says so).  An empty database succeeds with nothing made.  The tables end with the clustering: upload, index build,
+   network, adopt, swa_d1_cluster_device.  swa_dn_tables_serial: which swa_dn_tables_device call of this context made the
+   tables in place (counted from 1; 0: none in place) — a caller that fetches later can tell whether they are still its own. */
+uint64_t swa_dn_tables_serial(const swa_ctx * ctx);
+int swa_dn_tables_device(swa_ctx * ctx, uint32_t * nswarms, uint64_t * nlinks);
+int swa_dn_tables_fetch(swa_ctx * ctx, uint32_t * radius, uint64_t * mass, uint32_t * singletons, uint32_t * maxgen, uint32_t * maxradius,
+                        uint32_t * link_parent, uint32_t * link_child, uint32_t * link_generation, uint8_t * link_diff);
 /* out3 = {q-gram comparisons, aligned pairs, kernel launches} of the last swa_dn_graph */
 int swa_dn_graph_totals(swa_ctx * ctx, uint64_t * out3);
 

@@ -125,6 +125,12 @@ const char * swa_dn_result_error(const swa_dn_result * res);
 /* 1 when the bulk graph (swa_dn_graph*) served the clustering, 0 when the fused scan did.  SWARM_AMD_DN=scan|graph
    choose; without it the graph serves d <= 8 (where swa_dn_graph_supported) and the scan everything else. */
 int  swa_dn_result_over_graph(const swa_dn_result * res);
+/* The graph route's swarm tables are made on the host from five downloaded arrays (SWARM_AMD_DN_TABLES=host, the default) or
+   in HBM (=device: swa_dn_tables_device).  On the device route the links stay in HBM until the first writer that reads them
+   (-i, -u) asks; this is how often they were downloaded for this result (0 for a run that writes -o, -s, -w alone; else 1).
+   Until then the result needs its context alive and with this clustering still in place: after another upload, network or
+   clustering call on it, -i and -u of this result fail with a message (swa_dn_result_error); -o, -s, -w never need it. */
+uint32_t swa_dn_result_link_fetches(const swa_dn_result * res);
 /* out3 = {number of swarms, largest swarm, max generations} (src/algo.cc:699-705) */
 void swa_dn_result_summary(const swa_dn_result * res, uint64_t * out3);
 /* writers: -o/-r, -s, -i, -w, -u  (src/algo.cc:122-325, 473-488, 573-589, 608-674) */

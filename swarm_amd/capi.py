@@ -1003,6 +1003,34 @@ class Context:
         self._check(self.lib.swa_dn_parent_diffs(self.h, _ptr(out)))
         return out
 
+    def dn_tables_device(self) -> tuple:
+        """swa_dn_tables_device: radii, per-swarm sums and the links in acceptance order of the clustering d1_cluster_device
+        just made of a graph with differences, made and left in HBM; returns (nswarms, nlinks)"""
+        _declare_dn(self.lib)
+        nswarms, nlinks = C.c_uint32(0), C.c_uint64(0)
+        self._check(self.lib.swa_dn_tables_device(self.h, C.byref(nswarms), C.byref(nlinks)))
+        self._dn_tables_sizes = (int(nswarms.value), int(nlinks.value))
+        return self._dn_tables_sizes
+
+    def dn_tables_serial(self) -> int:
+        """swa_dn_tables_serial: which dn_tables_device call of this context made the tables in place (from 1), 0: none"""
+        _declare_dn(self.lib)
+        return int(self.lib.swa_dn_tables_serial(self.h))
+
+    def dn_tables_fetch(self) -> dict:
+        """swa_dn_tables_fetch: the nine arrays of the tables dn_tables_device made — radius [n]; mass, singletons, maxgen,
+        maxradius [nswarms]; link_parent, link_child, link_generation, link_diff [nlinks]"""
+        _declare_dn(self.lib)
+        nswarms, nlinks = getattr(self, "_dn_tables_sizes", (0, 0))
+        out = {"radius": np.zeros(self.n, dtype=np.uint32), "mass": np.zeros(nswarms, dtype=np.uint64)}
+        for name in ("singletons", "maxgen", "maxradius"):
+            out[name] = np.zeros(nswarms, dtype=np.uint32)
+        for name in ("link_parent", "link_child", "link_generation"):
+            out[name] = np.zeros(nlinks, dtype=np.uint32)
+        out["link_diff"] = np.zeros(nlinks, dtype=np.uint8)
+        self._check(self.lib.swa_dn_tables_fetch(self.h, *(_ptr(a) for a in out.values())))
+        return out
+
     # ---- B4
     def search_begin(self, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13, d: int = 3) -> None:
         self._check(self.lib.swa_search_begin(self.h, mismatch, gapopen, gapextend, d))
@@ -1132,6 +1160,7 @@ _DN_EXPORTS = ["swa_dn_cluster", "swa_dn_result_free", "swa_dn_result_error", "s
                "swa_dn_write_swarms", "swa_dn_write_stats", "swa_dn_write_structure", "swa_dn_write_seeds",
                "swa_dn_write_uclust", "swa_d1_write_uclust", "swa_scan_begin", "swa_scan_step", "swa_scan_batch", "swa_scan_fetch", "swa_scan_totals", "swa_scan_debug_state",
                "swa_dn_graph_supported", "swa_dn_graph", "swa_dn_graph_totals", "swa_dn_graph_resident", "swa_dn_parent_diffs",
+               "swa_dn_tables_device", "swa_dn_tables_fetch", "swa_dn_tables_serial", "swa_dn_result_link_fetches",
                "swa_multi_create", "swa_multi_destroy", "swa_multi_size", "swa_multi_uses_rccl", "swa_multi_ctx", "swa_multi_last_error",
                "swa_multi_db_upload", "swa_multi_d1_network", "swa_multi_d1_fastidious", "swa_dn_set_ownership", "swa_multi_dn_begin",
                "swa_multi_dn_graph_supported", "swa_multi_dn_graph", "swa_multi_dn_graph_totals", "swa_dn_cluster_multi",
@@ -1161,6 +1190,12 @@ def _declare_dn(lib) -> None:
     lib.swa_dn_result_error.restype = C.c_char_p
     lib.swa_dn_result_summary.argtypes = [C.c_void_p, u64p]
     lib.swa_dn_result_summary.restype = None
+    lib.swa_dn_result_link_fetches.argtypes = [C.c_void_p]
+    lib.swa_dn_result_link_fetches.restype = C.c_uint32
+    lib.swa_dn_tables_device.argtypes = [C.c_void_p, u32p, u64p]
+    lib.swa_dn_tables_fetch.argtypes = [C.c_void_p] + [C.c_void_p] * 9
+    lib.swa_dn_tables_serial.argtypes = [C.c_void_p]
+    lib.swa_dn_tables_serial.restype = C.c_uint64
     lib.swa_dn_write_swarms.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int64]
     for fn in (lib.swa_dn_write_stats, lib.swa_dn_write_structure, lib.swa_dn_write_seeds):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
@@ -1210,6 +1245,11 @@ class DnClusters:
         out = np.zeros(3, dtype=np.uint64)
         self.lib.swa_dn_result_summary(self.h, _p64(out))
         return {"swarms": int(out[0]), "largest": int(out[1]), "maxgen": int(out[2])}
+
+    def link_fetches(self) -> int:
+        """swa_dn_result_link_fetches: downloads of the -i / -u links made for this result (SWARM_AMD_DN_TABLES=device keeps
+        them in HBM until a writer reads them: 0 after -o, -s, -w alone, else 1)"""
+        return int(self.lib.swa_dn_result_link_fetches(self.h))
 
     def scan_totals(self) -> dict:
         """Work counters of the route that ran: the bulk graph (swa_dn_graph) or the fused scan (swa_scan_*)."""

@@ -146,6 +146,7 @@ extern "C" int swa_d1_network_resident(swa_ctx * ctx, int no_cluster_breaking, u
   const uint32_t n = ctx->db.n;
   ctx->res.csr_ready = false;
   ctx->res.cluster_ready = false;
+  ctx->res.tables = {};
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   uint64_t cap = std::max<uint64_t>(ctx->d_nb_tmp.bytes / sizeof(uint32_t), 4ull * n + 1024);
   for (;;) {
@@ -172,6 +173,7 @@ extern "C" int swa_d1_network_adopt(swa_ctx * ctx, const uint64_t * offsets, con
   if (ctx == nullptr) { return SWA_E_ARG; }
   ctx->res.csr_ready = false;
   ctx->res.cluster_ready = false;
+  ctx->res.tables = {};
   const uint32_t n = ctx->db.n;
   if (n == 0 || ctx->db.seqlen == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: no resident database"); }
   if (offsets == nullptr || (total != 0 && neighbours == nullptr)) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_adopt: null array"); }
@@ -231,6 +233,7 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   if (ctx == nullptr || order == nullptr || nswarms == nullptr) { return SWA_E_ARG; }
   ctx->res.cluster_ready = false;
   ctx->res.fast = {};                                       // (sums, roles and candidates belonged to the clustering that ends here)
+  ctx->res.tables = {};                                     // (... and so did the radii and links of dn_tables.inc)
   if (!ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_device: no resident network (swa_d1_network_resident)"); }
   for (uint32_t & e : ctx->res.cluster_effort) { e = 0; }
   if (ctx->db.n == 0) {                                   // (nothing to cluster: seed_rank + (n - 1) below would lie in front of the buffer)
@@ -392,3 +395,4 @@ extern "C" int swa_d1_cluster_effort(const swa_ctx * ctx, uint32_t out3[3]) {
 extern "C" uint32_t swa_d1_cluster_maxgen(const swa_ctx * ctx) { return ctx != nullptr && ctx->res.cluster_ready ? ctx->res.cluster_maxgen : 0u; }
 
 #include "fast_graft.inc"
+#include "dn_tables.inc"

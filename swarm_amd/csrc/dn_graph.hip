@@ -1077,6 +1077,7 @@ extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uin
   const unsigned long long * sorted = ctx->dn_work != 0 ? static_cast<const unsigned long long *>(ctx->d_dn_keys.ptr) + ctx->dn_work : nullptr;
   const uint32_t * svals = ctx->dn_work != 0 ? static_cast<const uint32_t *>(ctx->d_dn_vals.ptr) + ctx->dn_work : nullptr;
   ctx->res.csr_ready = false;
+  ctx->res.tables = {};                                     // (radii and links of the graph that is replaced here: dn_tables.inc)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, (nedges + 1) * (sizeof(uint32_t) + 1)));
   hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,

@@ -31,9 +31,14 @@ struct swa_dn_result {
   };
   struct Link { uint32_t parent, child, diff, swarm, generation; };
   // (swa_vec: sized without a serial fill — the device route writes every entry from all threads, hostdb.h)
-  swa_vec<Member> order;
+  swa_vec<uint32_t> order;                // the members' ids, swarm after swarm (generation and radius live in the walk's queues only)
   std::vector<Swarm> swarms;
   swa_vec<Link> links;                    // the -i lines, in acceptance order
+  // The device route of the swarm tables (cluster_on_device_tables) leaves the links in HBM; the first writer that reads
+  // them (-i, -u) downloads them once (need_links).  A run that writes -o, -s, -w alone never does.
+  swa_ctx * lazy_ctx = nullptr;
+  uint64_t lazy_serial = 0;               // swa_dn_tables_serial of the tables this result was made with
+  uint32_t link_fetches = 0;              // swa_dn_result_link_fetches
   uint64_t largest = 0, maxgenerations = 0;
   int64_t differences = 0;
   uint64_t pen_mismatch = 18, pen_gapopen = 24, pen_gapextend = 13;
@@ -106,7 +111,7 @@ static int cluster_over_graph(swa_ctx * ctx, swa_multi * multi, const swa_hostdb
     sw.link_end = (uint32_t)r->links.size();
     sw.begin = (uint32_t)r->order.size();
     for (const auto & m : queue) {
-      r->order.push_back(m);
+      r->order.push_back(m.id);
       sw.mass += db->abundance[m.id];
       if (db->abundance[m.id] == 1) { ++sw.singletons; }
     }
@@ -178,7 +183,7 @@ static int cluster_on_device(swa_ctx * ctx, const swa_hostdb * db, int no_cluste
       const uint32_t rad = g == 0 ? 0u : radius[parent[v]] + pdiff[v];
       radius[v] = rad;
       pos_of[v] = at;
-      r->order[at] = {v, g, rad};
+      r->order[at] = v;
       sw.mass += db->abundance[v];
       if (db->abundance[v] == 1) { ++sw.singletons; }
       sw.maxgen = std::max(sw.maxgen, g);
@@ -204,6 +209,83 @@ static int cluster_on_device(swa_ctx * ctx, const swa_hostdb * db, int no_cluste
   r->maxgenerations = std::max<uint64_t>(r->maxgenerations, maxgenerations);
   dn_stamp("swarm tables on the host");
   return SWA_OK;
+}
+
+// SWARM_AMD_DN_TABLES=host|device: where the tables behind the walk are made.  =device: in HBM (swa_dn_tables_device) — the
+// walk's swarm ids, generations and parents are never downloaded, the member order lands in the result itself, the swarms'
+// four sums come back as four arrays of one entry a swarm, and the links wait in HBM for a writer that reads them.  The
+// default follows the measurement of profiles/r22/NOTES.md (1 M x 400, d = 3: 2.5 ms from the resident graph to the tables
+// against 6.1 on the host, with -o alone and with -o -s -i -w).
+static bool tables_on_device() {
+  const char * where = std::getenv("SWARM_AMD_DN_TABLES");
+  return where == nullptr || std::strcmp(where, "host") != 0;
+}
+
+static int cluster_on_device_tables(swa_ctx * ctx, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
+  const uint32_t n = db->n;
+  uint64_t total = 0, nlinks = 0;
+  dn_stamp("graph: start");
+  int rc = swa_dn_graph_resident(ctx, no_cluster_breaking, &total);
+  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+  dn_stamp("graph: resident");
+  swa_vec<uint32_t> begins((size_t)n + 1);
+  r->order.resize(n);
+  uint32_t nswarms = 0, counted = 0;
+  rc = swa_d1_cluster_device(ctx, nullptr, nullptr, nullptr, r->order.data(), begins.data(), n, &nswarms);
+  dn_stamp("walk on the device: labels, generations, parents, order");
+  if (rc == SWA_OK) { rc = swa_dn_tables_device(ctx, &counted, &nlinks); }
+  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+  swa_vec<uint64_t> mass(nswarms);
+  swa_vec<uint32_t> singletons(nswarms), maxgen(nswarms), maxradius(nswarms);
+  rc = swa_dn_tables_fetch(ctx, nullptr, mass.data(), singletons.data(), maxgen.data(), maxradius.data(), nullptr, nullptr, nullptr, nullptr);
+  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+  r->swarms.resize(nswarms);
+  uint64_t largest = 0;
+#pragma omp parallel for schedule(static) reduction(max : largest) num_threads(swa_host_team()) if (nswarms >= 65536)
+  for (uint32_t s = 0; s < nswarms; ++s) {
+    swa_dn_result::Swarm & sw = r->swarms[s];
+    sw.begin = begins[s]; sw.end = begins[s + 1];
+    sw.mass = mass[s]; sw.singletons = singletons[s];
+    sw.maxgen = std::max(1u, maxgen[s]);                      // (what the other routes start a swarm's deepest generation from)
+    sw.maxradius = maxradius[s];
+    sw.link_begin = begins[s] - s; sw.link_end = begins[s + 1] - s - 1;   // (one link per member but the seed)
+    largest = std::max<uint64_t>(largest, sw.end - sw.begin);
+  }
+  r->largest = std::max<uint64_t>(r->largest, largest);
+  r->maxgenerations = std::max<uint64_t>(r->maxgenerations, std::max(1u, swa_d1_cluster_maxgen(ctx)));
+  r->lazy_ctx = nlinks != 0 ? ctx : nullptr;
+  r->lazy_serial = swa_dn_tables_serial(ctx);
+  dn_stamp("swarm tables on the device");
+  return SWA_OK;
+}
+
+// the links of a result of cluster_on_device_tables, downloaded when the first writer that reads them asks (once)
+static bool need_links(const swa_dn_result * cr) {
+  if (cr->lazy_ctx == nullptr) { return cr->error.empty(); }
+  auto * r = const_cast<swa_dn_result *>(cr);
+  const size_t nlinks = r->order.size() - r->swarms.size();
+  swa_vec<uint32_t> parent(nlinks), child(nlinks), generation(nlinks);
+  swa_vec<uint8_t> diff(nlinks);
+  swa_ctx * ctx = r->lazy_ctx;
+  r->lazy_ctx = nullptr;
+  if (swa_dn_tables_serial(ctx) != r->lazy_serial) {
+    r->error = "the links of this clustering were left on the GPU for the first writer that reads them (-i, -u), and the context has since been given other work";
+    return false;
+  }
+  if (swa_dn_tables_fetch(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, parent.data(), child.data(), generation.data(), diff.data()) != SWA_OK) {
+    r->error = swa_last_error(ctx);
+    return false;
+  }
+  r->links.resize(nlinks);
+  const int64_t nswarms = (int64_t)r->swarms.size();
+#pragma omp parallel for schedule(dynamic, 1024) num_threads(swa_host_team()) if (nlinks >= 65536)
+  for (int64_t s = 0; s < nswarms; ++s) {
+    for (uint32_t k = r->swarms[s].link_begin; k < r->swarms[s].link_end; ++k) {
+      r->links[k] = {parent[k], child[k], diff[k], (uint32_t)s + 1, generation[k]};
+    }
+  }
+  ++r->link_fetches;
+  return true;
 }
 
 // d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups (and of the short
@@ -265,7 +347,7 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
     // (differences of 255 are what the device walk's parent-difference bytes use for "no link": d >= 255 walks on the host)
     if ((walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) { return cluster_over_graph(ctx, nullptr, db, no_cluster_breaking, r); }
     (void)swa_dn_set_ownership(ctx, 0, 1);                    // (a context that served one rank's share before: the whole graph)
-    return cluster_on_device(ctx, db, no_cluster_breaking, r);
+    return tables_on_device() ? cluster_on_device_tables(ctx, db, no_cluster_breaking, r) : cluster_on_device(ctx, db, no_cluster_breaking, r);
   }
   if (want_graph) {
     r->error = differences > 16 ? "SWARM_AMD_DN=graph: the graph route serves d <= 16" : "SWARM_AMD_DN=graph: a sequence is too short for d + 1 windows";
@@ -337,7 +419,7 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
     sw.link_end = (uint32_t)r->links.size();
     sw.begin = (uint32_t)r->order.size();
     for (const auto & m : queue) {
-      r->order.push_back(m);
+      r->order.push_back(m.id);
       sw.mass += db->abundance[m.id];
       if (db->abundance[m.id] == 1) { ++sw.singletons; }
     }
@@ -353,6 +435,7 @@ extern "C" void swa_dn_result_free(swa_dn_result * r) { delete r; }
 extern "C" const char * swa_dn_result_error(const swa_dn_result * r) { return r != nullptr ? r->error.c_str() : ""; }
 
 // {number of swarms, largest swarm, max generations} — the log's summary (src/algo.cc:699-705)
+extern "C" uint32_t swa_dn_result_link_fetches(const swa_dn_result * r) { return r != nullptr ? r->link_fetches : 0u; }
 extern "C" int swa_dn_result_over_graph(const swa_dn_result * r) { return r != nullptr && r->over_graph ? 1 : 0; }
 
 extern "C" void swa_dn_result_summary(const swa_dn_result * r, uint64_t * out3) {
@@ -378,11 +461,11 @@ extern "C" int swa_dn_write_swarms(const swa_dn_result * r, const swa_hostdb * d
         const auto & s = r->swarms[si];
         if (si != 0) { sink.put(mothur ? '\t' : '\n'); }
         for (uint32_t k = s.begin; k < s.end; ++k) {
-          if ((size_t)k + 24 < total) { __builtin_prefetch(&db->ent[order[k + 24].id]); }
-          if ((size_t)k + 16 < total) { __builtin_prefetch(db->ent[order[k + 16].id]); }
-          if ((size_t)k + 8 < total) { __builtin_prefetch(db->hdr(order[k + 8].id)); }
+          if ((size_t)k + 24 < total) { __builtin_prefetch(&db->ent[order[k + 24]]); }
+          if ((size_t)k + 16 < total) { __builtin_prefetch(db->ent[order[k + 16]]); }
+          if ((size_t)k + 8 < total) { __builtin_prefetch(db->hdr(order[k + 8])); }
           if (k != s.begin) { sink.put(mothur ? ',' : ' '); }
-          swa_out::id(sink, db, order[k].id, usearch != 0, append_abundance);
+          swa_out::id(sink, db, order[k], usearch != 0, append_abundance);
         }
       }
     };
@@ -397,7 +480,7 @@ extern "C" int swa_dn_write_stats(const swa_dn_result * r, const swa_hostdb * db
   BufOut o(path);
   if (!o.ok()) { return SWA_E_ARG; }
   for (const auto & s : r->swarms) {
-    const uint32_t seed = r->order[s.begin].id;
+    const uint32_t seed = r->order[s.begin];
     o.u64(s.end - s.begin); o.put('\t'); o.u64(s.mass); o.put('\t');
     swa_out::id_noabundance(o, db, seed, usearch != 0);
     o.put('\t'); o.u64(db->abundance[seed]); o.put('\t'); o.u64(s.singletons); o.put('\t'); o.u64(s.maxgen);
@@ -408,6 +491,7 @@ extern "C" int swa_dn_write_stats(const swa_dn_result * r, const swa_hostdb * db
 
 // -i  (src/algo.cc:473-488, 573-589): one line per accepted pair, in acceptance order
 extern "C" int swa_dn_write_structure(const swa_dn_result * r, const swa_hostdb * db, const char * path, int usearch) {
+  if (!need_links(r)) { return SWA_E_DEVICE; }
   BufOut o(path);
   if (!o.ok()) { return SWA_E_ARG; }
   for (const auto & l : r->links) {
@@ -427,7 +511,7 @@ extern "C" int swa_dn_write_seeds(const swa_dn_result * r, const swa_hostdb * db
   if (!o.ok()) { return SWA_E_ARG; }
   struct Seed { uint64_t mass; uint32_t seed; };
   std::vector<Seed> seeds;
-  for (const auto & s : r->swarms) { seeds.push_back({s.mass, r->order[s.begin].id}); }
+  for (const auto & s : r->swarms) { seeds.push_back({s.mass, r->order[s.begin]}); }
   std::sort(seeds.begin(), seeds.end(), [&](const Seed & a, const Seed & b) {
     if (a.mass > b.mass) { return true; }
     if (a.mass < b.mass) { return false; }
@@ -447,6 +531,7 @@ extern "C" int swa_dn_write_seeds(const swa_dn_result * r, const swa_hostdb * db
 // hits[] array), aligned against its swarm's seed with the scalar aligner
 extern "C" int swa_dn_write_uclust(const swa_dn_result * r, const swa_hostdb * db, const char * path, int usearch,
                                    int64_t append_abundance) {
+  if (!need_links(r)) { return SWA_E_DEVICE; }
   BufOut o(path);
   if (!o.ok()) { return SWA_E_ARG; }
   // one alignment per member — the most expensive writer by far (the reference's is serial, too),
@@ -455,7 +540,7 @@ extern "C" int swa_dn_write_uclust(const swa_dn_result * r, const swa_hostdb * d
     swa_nw_scratch scratch;
     for (size_t cluster_no = begin; cluster_no < end; ++cluster_no) {
       const auto & s = r->swarms[cluster_no];
-      const uint32_t seed = r->order[s.begin].id;
+      const uint32_t seed = r->order[s.begin];
       swa_out::uclust_cluster(sink, db, cluster_no, s.end - s.begin, seed, usearch != 0, append_abundance);
       for (uint32_t k = s.link_begin; k < s.link_end; ++k) {
         const uint32_t hit = r->links[k].child;
@@ -474,18 +559,19 @@ extern "C" int swa_dn_write_uclust(const swa_dn_result * r, const swa_hostdb * d
 // -u with the alignments on the GPU (seam B5): the same lines as swa_dn_write_uclust, the pairs aligned by swa_nw_batch
 extern "C" int swa_dn_write_uclust_gpu(swa_ctx * ctx, const swa_dn_result * r, const swa_hostdb * db, const char * path, int usearch,
                                        int64_t append_abundance) {
+  if (!need_links(r)) { return SWA_E_DEVICE; }               // (before swa_nw_batch starts on the context)
   BufOut o(path);
   if (!o.ok()) { return SWA_E_ARG; }
   return swa_uclust_gpu(ctx, db, o, r->swarms.size(), r->order.size() >= 200, r->pen_mismatch, r->pen_gapopen, r->pen_gapextend,
     [&](size_t k, auto && push) {
       const auto & s = r->swarms[k];
-      const uint32_t seed = r->order[s.begin].id;
+      const uint32_t seed = r->order[s.begin];
       for (uint32_t l = s.link_begin; l < s.link_end; ++l) { push(r->links[l].child, seed); }
     },
     [&](size_t k) -> uint64_t { return 1u + (r->swarms[k].end - r->swarms[k].begin); },
     [&](BufOut & sink, size_t k, const swa_uclust_chunk & c, uint64_t p) {
       const auto & s = r->swarms[k];
-      const uint32_t seed = r->order[s.begin].id;
+      const uint32_t seed = r->order[s.begin];
       swa_out::uclust_cluster(sink, db, k, s.end - s.begin, seed, usearch != 0, append_abundance);
       for (uint32_t l = s.link_begin; l < s.link_end; ++l, ++p) {
         size_t len = 0;

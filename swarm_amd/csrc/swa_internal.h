@@ -237,6 +237,14 @@ struct swa_resident {
     uint64_t light_amps = 0;                   // ... and how many amplicons it found in light swarms
     bool cand_ready = false;                   // d_graft: the candidates of a whole swa_d1_fastidious* pass (or a caller's) over this clustering
   } fast;
+  // what the d >= 2 graph route derives from the clustering in place and keeps in HBM (dn_tables.inc): every member's radius,
+  // the deepest radius of every swarm, the -i links in acceptance order; ended with the clustering
+  struct dn_tables_facts {
+    bool ready = false;                        // d_dn_tables holds them (swa_dn_tables_fetch)
+    uint64_t nlinks = 0;                       // n - swarms
+    uint32_t radius_at = 0;                    // which of the two jumping buffers the last round wrote
+    uint64_t serial = 0;                       // which swa_dn_tables_device call of this context made them (swa_dn_tables_serial)
+  } tables;
 };
 
 // the dereplication in place (derep.hip): ended by swa_db_upload* / swa_db_attach, by the start of every swa_derep* and by
@@ -340,6 +348,9 @@ struct swa_ctx {
   // --fastidious on the clustering in place (fast_graft.inc): the per-swarm sums, the role byte of every amplicon, and the
   // grafting's slots, winner lists and result arrays
   swa_dbuf d_swarm_sums, d_swarm_role, d_graft_work;
+  // d >= 2 on the clustering in place (dn_tables.inc): jumping buffers, positions, sort keys, the four link arrays
+  swa_dbuf d_dn_tables;
+  uint64_t dn_tables_made = 0;                 // swa_dn_tables_device calls of this context that left tables
   // d = 0 (derep.hip): the grouping's work arrays with the member order (n words each), and the cluster tables
   swa_dbuf d_d0, d_d0_tab;
 
