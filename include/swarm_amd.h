@@ -312,6 +312,9 @@ uint64_t swa_d1_table_size(const swa_ctx * ctx);
    with *nswarms = the number of swarms when that is too small (n always suffices). */
 int swa_d1_network_resident(swa_ctx * ctx, int no_cluster_breaking, uint64_t * total);
 int swa_d1_network_fetch(swa_ctx * ctx, uint64_t * offsets, uint32_t * neighbours, uint64_t cap);
+/* the differences of every link of a resident d >= 2 graph (swa_dn_graph_resident, swa_multi_dn_graph_resident, an adopted
+   graph with diffs), one byte per link in the order of swa_d1_network_fetch's neighbours; SWA_E_ARG for a network without */
+int swa_d1_network_fetch_diffs(swa_ctx * ctx, uint8_t * diffs, uint64_t cap);
 int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t * generation, uint32_t * parent, uint32_t * order,
                           uint32_t * swarm_begin, uint32_t swarm_cap, uint32_t * nswarms);
 /* swarmid / generation / parent may be null in swa_d1_cluster_device: they stay in HBM, and a caller that wants them
@@ -454,6 +457,17 @@ int swa_d1_fastidious_resident(swa_ctx * ctx, uint64_t light_nt, uint32_t bloom_
 int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, uint32_t * heavy_swarm, uint32_t * light_swarm,
                         uint32_t * parent, uint32_t * child, uint32_t cap, uint32_t * grafts);
 int swa_d1_graft_candidates_fetch(swa_ctx * ctx, uint32_t * graft_cand);
+/* Shard owners: who expands which heavy amplicon when the second pass is divided among S shards (swa_d1_fastidious_shard:
+   shard s takes the heavy amplicons whose ordinal h among the H heavy ones, in amplicon order, lies in
+   [floor(H s / S), floor(H (s + 1) / S))).  swa_d1_shard_owners_device makes, from the flags of the last
+   swa_d1_light_flags_device call and where they lie, one owner byte per amplicon: 255 for an amplicon of a light swarm, else
+   the shard that owns it, floor(((h + 1) S - 1) / H); nshards = 1 .. 64; *heavy = H; owners (n bytes on the host) may be NULL:
+   the bytes stay in HBM either way.  SWA_E_ARG without flags in place.  swa_d1_shard_owner_for: that closed form as a pure
+   function (no device; SWA_E_ARG unless h < heavy <= 2^32 - 1 and 1 <= nshards <= 64).  swa_d1_shard_owner_plan: out =
+   {amplicons per tile of the kernels, tiles per turn of the scan of the tiles' counts}. */
+int swa_d1_shard_owners_device(swa_ctx * ctx, uint32_t nshards, uint8_t * owners, uint64_t * heavy);
+int swa_d1_shard_owner_for(uint64_t heavy, uint32_t nshards, uint64_t h, uint32_t * owner);
+int swa_d1_shard_owner_plan(uint32_t out[2]);
 
 /* ---- d = 0: dereplication -------------------------------
    Replaces the bucket search of dereplicating() (src/derep.cc:276-354: Zobrist hash, open
@@ -642,8 +656,12 @@ int swa_dn_graph_totals(swa_ctx * ctx, uint64_t * out3);
    host thread per listed device inside the calling process; the database replicated, the probing divided by
    ownership of anchor groups (swa_d1_set_ownership): routed index build (every rank keys its own slice and the key
    records travel to their owners, grouped ncclSend / ncclRecv over xGMI), every rank's flat link list gathered on
-   rank 0 only (grouped ncclSend / ncclRecv: the one consumer of the network is the host behind rank 0), CSR assembled
-   there on the device (swa_d1_csr_from_lists over the whole range, the ranks' lists as its runs); fastidious: heavy amplicons split, graft_cand combined with ncclAllReduce(min).  librccl.so is
+   rank 0 only (grouped ncclSend / ncclRecv: the network has one consumer, rank 0), CSR assembled
+   there on the device (swa_d1_csr_from_lists over the whole range, the ranks' lists as its runs) and either downloaded for the
+   host (swa_multi_d1_network) or left as rank 0's resident network, where the agglomeration, the swarm sums, the light flags
+   and the grafting run as on a single GPU (swa_multi_d1_network_resident); fastidious: heavy amplicons split — by the host from
+   host flags (swa_multi_d1_fastidious) or by owner bytes made on rank 0's GPU and broadcast (swa_multi_d1_fastidious_resident)
+   —, graft_cand combined with ncclAllReduce(min).  librccl.so is
    loaded when the first handle with ranks on distinct devices is created, not with the library.  A device may be listed more than once (several ranks on one GPU: the exchange then uses
    device-to-device copies — RCCL admits one rank per GPU); results never depend on the device list. */
 typedef struct swa_multi swa_multi;
@@ -661,6 +679,16 @@ int  swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint64_t * off
 /* = swa_d1_fastidious */
 int  swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
                              uint32_t * graft_cand, uint64_t * counters);
+/* = swa_d1_index_build + swa_d1_network_resident on swa_multi_ctx(m, 0): the network stays on rank 0's device, nothing is
+   downloaded; swa_d1_network_fetch, swa_d1_cluster_device and the calls behind it then work on that context.  After a
+   failure rank 0 holds no resident network. */
+int  swa_multi_d1_network_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total, int * has_duplicates);
+/* = swa_d1_fastidious_resident on swa_multi_ctx(m, 0), the heavy amplicons divided among the ranks: needs rank 0's clustering
+   and the flags of swa_d1_light_flags_device on it (SWA_E_ARG otherwise).  The owner bytes (swa_d1_shard_owners_device, S =
+   the ranks) go from rank 0 to every rank (ncclBroadcast; device-to-device copies between ranks on one GPU), every rank runs
+   its share, the candidates are combined in rank 0's HBM, where swa_d1_graft_device(ctx0, NULL, ...) reads them; graft_cand
+   may be NULL: they are then not downloaded.  counters as swa_multi_d1_fastidious. */
+int  swa_multi_d1_fastidious_resident(swa_multi * m, uint64_t light_nt, uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
 
 
 /* ---- d >= 2 on several GPUs (second paragraph) --------------------------------------------------
@@ -671,12 +699,15 @@ int  swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, uint64_t l
    emits); so over all ranks every pair of the graph is found exactly once.  swa_multi_dn_begin = swa_qgram_build + swa_search_begin on every rank;
    swa_multi_dn_graph = swa_dn_graph: every rank finds and aligns its share, the accepted (query, target, diff)
    triples travel to rank 0 (RCCL send / receive over xGMI, device-to-device copies for ranks sharing a GPU), which
-   sorts them into the CSR; same buffers and capacity protocol as swa_dn_graph. */
+   merges them into the CSR; same buffers and capacity protocol as swa_dn_graph.  swa_multi_dn_graph_resident =
+   swa_dn_graph_resident on swa_multi_ctx(m, 0): the merged graph is left there as the resident network (with differences),
+   for swa_d1_cluster_device, swa_dn_parent_diffs and swa_dn_tables_device on that context. */
 int  swa_dn_set_ownership(swa_ctx * ctx, uint32_t rank, uint32_t world);
 int  swa_multi_dn_begin(swa_multi * m, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t d);
 int  swa_multi_dn_graph_supported(swa_multi * m);
 int  swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64_t * offsets, uint32_t * neighbours, uint8_t * diffs,
                         uint64_t cap, uint64_t * total);
+int  swa_multi_dn_graph_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total);
 int  swa_multi_dn_graph_totals(swa_multi * m, uint64_t * out3);
 
 #ifdef __cplusplus

@@ -117,9 +117,13 @@ typedef struct swa_dn_result swa_dn_result;
    Penalties after the reference's gcd reduction (src/swarm.cc:466-483). */
 int  swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                     uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out);
-/* the same on the GPUs of a swa_multi (d >= 2 graph divided by ownership of window groups, swa_multi_dn_graph) */
+/* the same on the GPUs of a swa_multi (d >= 2 graph divided by ownership of window groups: swa_multi_dn_graph and the walk on
+   the host, or — where swa_multi_cluster_on_device() — swa_multi_dn_graph_resident and the walk and tables on rank 0's GPU) */
 int  swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                           uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out);
+/* SWARM_AMD_MULTI_CLUSTER=device|host: where a run on several GPUs clusters what the exchange assembled on rank 0 — there
+   (1: the network or graph stays resident, as on one GPU; the default, by the measurement of profiles/r23/NOTES.md) or on the host behind a download (0: =host). */
+int  swa_multi_cluster_on_device(void);
 void swa_dn_result_free(swa_dn_result * res);
 const char * swa_dn_result_error(const swa_dn_result * res);
 /* 1 when the bulk graph (swa_dn_graph*) served the clustering, 0 when the fused scan did.  SWARM_AMD_DN=scan|graph

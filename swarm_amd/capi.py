@@ -84,6 +84,8 @@ EXPORTS = [
     "swa_d1_write_stats", "swa_d1_write_structure", "swa_d1_write_seeds", "swa_d1_write_network",
     "swa_d1_swarm_sums_device", "swa_d1_light_flags_device", "swa_d1_fastidious_resident", "swa_d1_graft_device",
     "swa_d1_graft_candidates_fetch", "swa_d1_result_install_graft", "swa_d1_result_detail_fetches",
+    "swa_d1_network_fetch_diffs", "swa_d1_shard_owners_device", "swa_d1_shard_owner_for", "swa_d1_shard_owner_plan",
+    "swa_multi_d1_network_resident", "swa_multi_d1_fastidious_resident", "swa_multi_dn_graph_resident",
 ]
 
 
@@ -141,6 +143,9 @@ def load_library() -> C.CDLL:
     lib.swa_d1_graft_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, u32p]
     lib.swa_d1_graft_candidates_fetch.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_result_install_graft.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.swa_d1_shard_owners_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p]
+    lib.swa_d1_shard_owner_for.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, u32p]
+    lib.swa_d1_shard_owner_plan.argtypes = [C.c_void_p]
     lib.swa_d1_result_detail_fetches.argtypes = [C.c_void_p]
     lib.swa_d1_result_detail_fetches.restype = C.c_uint32
     lib.swa_d1_fastidious_plan.argtypes = [C.c_void_p, C.c_void_p]
@@ -209,6 +214,26 @@ def fastidious_plan_for(longest: int, pair_longest: int = 0, split: bool = False
     rc = load_library().swa_d1_fastidious_plan_for(int(longest), int(pair_longest), int(split), int(bloom), int(words), _ptr(out))
     if rc != SWA_OK:
         raise SwaError(rc, "swa_d1_fastidious_plan_for: bad argument")
+    return [int(v) for v in out]
+
+
+def shard_owner_for(heavy: int, nshards: int, h: int) -> int:
+    """swa_d1_shard_owner_for: the shard (of nshards) that expands the h-th of `heavy` heavy amplicons — the one whose
+    slice [heavy * s // nshards, heavy * (s + 1) // nshards) holds h — in closed form; no context, no device."""
+    owner = C.c_uint32(0)
+    rc = load_library().swa_d1_shard_owner_for(int(heavy), int(nshards), int(h), C.byref(owner))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_d1_shard_owner_for: bad argument")
+    return int(owner.value)
+
+
+def shard_owner_plan() -> list:
+    """swa_d1_shard_owner_plan: [amplicons per tile of the owner kernels, tiles per turn of the scan of the tiles' counts
+    (0: the scan has no turns)]."""
+    out = np.zeros(2, dtype=np.uint32)
+    rc = load_library().swa_d1_shard_owner_plan(_ptr(out))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_d1_shard_owner_plan failed")
     return [int(v) for v in out]
 
 
@@ -484,10 +509,23 @@ class Context:
         self.h = h
         self.n = 0
         self._keep = None
+        self._owned = True
+
+    @classmethod
+    def _view(cls, handle, n: int, keep) -> "Context":
+        """A Context over a handle somebody else owns (MultiContext.ctx): close() lets go of it without destroying it."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.h = C.c_void_p(handle)
+        self.n = n
+        self._keep = keep
+        self._owned = False
+        return self
 
     def close(self) -> None:
         if self.h:
-            self.lib.swa_ctx_destroy(self.h)
+            if getattr(self, "_owned", True):
+                self.lib.swa_ctx_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -692,6 +730,14 @@ class Context:
         self._check(self.lib.swa_d1_network_fetch(self.h, _ptr(offsets), _ptr(nb), len(nb)))
         return offsets, nb[:total]
 
+    def d1_network_fetch_diffs(self, total: int) -> np.ndarray:
+        """swa_d1_network_fetch_diffs: the byte of differences of every link of the resident d >= 2 graph, in the order
+        of d1_network_fetch's neighbours"""
+        self.lib.swa_d1_network_fetch_diffs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        diffs = np.zeros(max(total, 1), dtype=np.uint8)
+        self._check(self.lib.swa_d1_network_fetch_diffs(self.h, _ptr(diffs), len(diffs)))
+        return diffs[:total]
+
     def d1_network_adopt(self, offsets, neighbours, diffs=None) -> int:
         """swa_d1_network_adopt: a host CSR over the resident database's amplicons installed as the resident network (with
         `diffs`, a byte per link, as swa_dn_graph_resident leaves it).  Validated on the host before anything reaches the
@@ -885,6 +931,15 @@ class Context:
         counters = np.zeros(8, dtype=np.uint64)
         self._check(self.lib.swa_d1_fastidious_resident(self.h, int(light_nt), int(bloom_bits), _ptr(graft), _ptr(counters)))
         return graft, counters
+
+    def d1_shard_owners_device(self, nshards: int, fetch: bool = True):
+        """swa_d1_shard_owners_device: (owner u8[n] or None, H).  owner[a] = 255 for an amplicon of a light swarm, else the
+        shard of `nshards` that expands heavy amplicon a; made from the flags d1_light_flags_device left in HBM, where the
+        bytes stay."""
+        owners = np.zeros(self.n, dtype=np.uint8) if fetch else None
+        heavy = C.c_uint64(0)
+        self._check(self.lib.swa_d1_shard_owners_device(self.h, int(nshards), _ptr(owners), C.byref(heavy)))
+        return owners, int(heavy.value)
 
     def d1_graft_device(self, graft_cand=None, cap: int | None = None):
         """swa_d1_graft_device: (heavy swarm, light swarm, parent, child) of the G grafts in chain order.  graft_cand: n
@@ -1460,6 +1515,12 @@ class MultiContext:
         lib.swa_multi_db_upload.argtypes = [C.c_void_p, C.POINTER(DbView)]
         lib.swa_multi_d1_network.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.POINTER(C.c_int)]
         lib.swa_multi_d1_fastidious.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.swa_multi_size.argtypes = [C.c_void_p]
+        lib.swa_multi_ctx.argtypes = [C.c_void_p, C.c_int]
+        lib.swa_multi_ctx.restype = C.c_void_p
+        lib.swa_multi_d1_network_resident.argtypes = [C.c_void_p, C.c_int, u64p, C.POINTER(C.c_int)]
+        lib.swa_multi_d1_fastidious_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.swa_multi_dn_graph_resident.argtypes = [C.c_void_p, C.c_int, u64p]
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
         rc = lib.swa_multi_create(arr, len(devices), C.byref(h))
@@ -1515,6 +1576,45 @@ class MultiContext:
         if rc == SWA_E_CAPACITY:
             self._check(lib.swa_multi_dn_graph(self.h, int(no_cluster_breaking), _ptr(offsets), _ptr(nb), _ptr(df), total.value, C.byref(total)))
         return offsets, nb[:total.value], df[:total.value]
+
+    def ctx(self, rank: int = 0) -> "Context":
+        """swa_multi_ctx: rank's context as a Context that neither owns nor closes the handle (it lives as long as this
+        MultiContext, which the view keeps alive)."""
+        handle = self.lib.swa_multi_ctx(self.h, int(rank))
+        if not handle:
+            raise SwaError(SWA_E_ARG, f"swa_multi_ctx: no rank {rank}")
+        return Context._view(handle, self.n, self)
+
+    def d1_network_resident(self, no_cluster_breaking: bool = False) -> int:
+        """swa_multi_d1_network_resident: the network of the whole database left resident on rank 0's GPU (ctx(0):
+        d1_network_fetch, d1_cluster_device, ...); returns the number of links.  SwaError(SWA_E_DUPLICATES) as d1_network."""
+        total = C.c_uint64(0)
+        dup = C.c_int(0)
+        self._check(self.lib.swa_multi_d1_network_resident(self.h, int(no_cluster_breaking), C.byref(total), C.byref(dup)))
+        return int(total.value)
+
+    def dn_graph_resident(self, d: int, no_cluster_breaking: bool = False, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
+        """swa_multi_dn_begin + swa_multi_dn_graph_resident: the whole d >= 2 graph left resident on rank 0's GPU (ctx(0):
+        d1_cluster_device, dn_parent_diffs, dn_tables_device); the number of links, or None when the graph route does
+        not serve the database (as dn_graph)."""
+        lib = self.lib
+        lib.swa_multi_dn_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+        lib.swa_multi_dn_graph_supported.argtypes = [C.c_void_p]
+        self._check(lib.swa_multi_dn_begin(self.h, mismatch, gapopen, gapextend, d))
+        if not lib.swa_multi_dn_graph_supported(self.h):
+            return None
+        total = C.c_uint64(0)
+        self._check(lib.swa_multi_dn_graph_resident(self.h, int(no_cluster_breaking), C.byref(total)))
+        return int(total.value)
+
+    def d1_fastidious_resident(self, light_nt: int, bloom_bits: int = 16, fetch: bool = True):
+        """swa_multi_d1_fastidious_resident: the second pass on all ranks from the flags ctx(0).d1_light_flags_device left
+        in rank 0's HBM.  (graft_cand or None when fetch is False: the combined candidates then stay on rank 0 for
+        ctx(0).d1_graft_device(None), counters)."""
+        graft = np.zeros(self.n, dtype=np.uint32) if fetch else None
+        counters = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.swa_multi_d1_fastidious_resident(self.h, int(light_nt), int(bloom_bits), _ptr(graft), _ptr(counters)))
+        return graft, counters
 
     def d1_fastidious(self, is_light: np.ndarray, light_nt: int, bloom_bits: int = 16):
         is_light = np.ascontiguousarray(is_light, dtype=np.uint8)

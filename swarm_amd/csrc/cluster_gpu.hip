@@ -223,6 +223,19 @@ extern "C" int swa_d1_network_fetch(swa_ctx * ctx, uint64_t * offsets, uint32_t 
   return SWA_OK;
 }
 
+// ... and the byte of differences of every link of a resident d >= 2 graph, in the neighbours' order
+extern "C" int swa_d1_network_fetch_diffs(swa_ctx * ctx, uint8_t * diffs, uint64_t cap) {
+  if (ctx == nullptr || (diffs == nullptr && cap != 0)) { return SWA_E_ARG; }
+  if (!ctx->res.csr_ready || !ctx->res.csr_has_diffs) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_fetch_diffs: no resident network with differences"); }
+  if (ctx->res.csr_total > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_network_fetch_diffs: buffer too small"); }
+  if (ctx->res.csr_total == 0) { return SWA_OK; }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  const auto * nb32 = static_cast<const uint32_t *>(ctx->d_nb_tmp.ptr);
+  SWA_HIP(ctx, hipMemcpyAsync(diffs, nb32 + ctx->res.csr_total, ctx->res.csr_total, hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
 // Clustering of the resident network.  All arrays have n entries (order: the members of swarm s are
 // order[swarm_begin[s], swarm_begin[s + 1]), seed first, then by generation and id); swarm_begin needs
 // swarm_cap + 1 entries: SWA_E_CAPACITY with *nswarms = the number needed when it is too small.

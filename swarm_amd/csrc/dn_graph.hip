@@ -1069,13 +1069,11 @@ extern "C" int swa_dn_graph(swa_ctx * ctx, int no_cluster_breaking, uint64_t * o
 // swa_d1_cluster_device then evaluates the agglomeration of src/algo.cc:384-602 on it where it lies — the same pure
 // function of the directed graph as for d = 1 (seeds by lowest id, generations by distance, members by generation then
 // id: find_correct_position_in_list, src/algo.cc:205-219) — and swa_dn_parent_diffs adds what the radius needs.
-extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uint64_t * total) {
-  if (ctx == nullptr || total == nullptr) { return SWA_E_ARG; }
-  SWA_TRY(swa_dn_graph_compute(ctx, no_cluster_breaking));
+// swa_dn_graph_install: from a sorted link list in HBM — this context's own (swa_dn_graph_resident), or the ranks' shares
+// merged on rank 0 (multi.hip: swa_multi_dn_graph_resident).
+int swa_dn_graph_install(swa_ctx * ctx, const unsigned long long * sorted, const uint32_t * svals, uint64_t nedges) {
   const uint32_t n = ctx->db.n;
-  const uint64_t nedges = ctx->dn_edges;
-  const unsigned long long * sorted = ctx->dn_work != 0 ? static_cast<const unsigned long long *>(ctx->d_dn_keys.ptr) + ctx->dn_work : nullptr;
-  const uint32_t * svals = ctx->dn_work != 0 ? static_cast<const uint32_t *>(ctx->d_dn_vals.ptr) + ctx->dn_work : nullptr;
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
   ctx->res.csr_ready = false;
   ctx->res.tables = {};                                     // (radii and links of the graph that is replaced here: dn_tables.inc)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
@@ -1091,6 +1089,16 @@ extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uin
   ctx->res.csr_ready = true;
   ctx->res.csr_total = nedges;
   ctx->res.csr_has_diffs = true;
+  return SWA_OK;
+}
+
+extern "C" int swa_dn_graph_resident(swa_ctx * ctx, int no_cluster_breaking, uint64_t * total) {
+  if (ctx == nullptr || total == nullptr) { return SWA_E_ARG; }
+  SWA_TRY(swa_dn_graph_compute(ctx, no_cluster_breaking));
+  const uint64_t nedges = ctx->dn_edges;
+  const unsigned long long * sorted = ctx->dn_work != 0 ? static_cast<const unsigned long long *>(ctx->d_dn_keys.ptr) + ctx->dn_work : nullptr;
+  const uint32_t * svals = ctx->dn_work != 0 ? static_cast<const uint32_t *>(ctx->d_dn_vals.ptr) + ctx->dn_work : nullptr;
+  SWA_TRY(swa_dn_graph_install(ctx, sorted, svals, nedges));
   *total = nedges;
   return SWA_OK;
 }

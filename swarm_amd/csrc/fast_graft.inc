@@ -12,6 +12,8 @@
 //                     members), one atomic per (wave, swarm) otherwise (a swarm of millions spans thousands of waves)
 //   k_light_roles     role[a] = mass[sid[a]] < boundary ? 0 : 1, the byte the fastidious pass reads; k_light_stats the five
 //                     numbers of the log, reduced per wave
+//   k_owner_counts, k_owner_scan, k_owner_write   the owner byte of every amplicon (255 light, else the shard of a run on several
+//                     GPUs that expands this heavy amplicon) from the role bytes: an exclusive count of the heavy ones
 //   k_graft_min       slot[swarm of the child] = min(parent << 32 | child) over the candidates: what the sequential walk
 //                     over the sorted pairs decides (cluster_d1.cpp: graft_sorted_pairs_in_parallel) without the walk
 //   k_graft_winners   the winners compacted, the losers' candidates withdrawn
@@ -175,6 +177,106 @@ __global__ __launch_bounds__(256) void k_graft_apply(const uint32_t * __restrict
   }
 }
 
+// ---- shard owners: which of S shards expands a heavy amplicon (swa_d1_fastidious_shard's slices, made where the flags lie) ----
+// The h-th heavy amplicon (amplicon order, H in all) belongs to the shard s with floor(H s / S) <= h < floor(H (s + 1) / S), which is
+// floor(((h + 1) S - 1) / H): h needs the number of heavy bytes in front of it, an exclusive count.  Three launches, none of
+// which waits for another workgroup: the heavy bytes of every tile (k_owner_counts), the tiles' counts scanned by one
+// workgroup in turns of kOwnerTurn tiles (k_owner_scan), then every tile scans its own words again from its base and writes
+// the owner bytes (k_owner_write).  A thread takes four role bytes as one 32-bit load (k_light_roles stores them so); the
+// word that holds the last n & 3 bytes is masked when counted and written byte by byte (both buffers are reserved with four
+// bytes to spare).  Integer sums only.
+constexpr uint32_t kOwnerBlock = 256, kOwnerTile = 4 * kOwnerBlock, kOwnerTurn = 256;
+constexpr uint8_t kOwnerLight = 255;
+
+// the role word q of n bytes, bytes beyond n as light
+__device__ __forceinline__ uint32_t owner_role_word(const uint8_t * __restrict__ role, uint64_t q, uint32_t n) {
+  const uint32_t w = reinterpret_cast<const uint32_t *>(role)[q];
+  const uint64_t left = (uint64_t)n - 4u * q;                // (> 0: q < ceil(n / 4))
+  return left >= 4u ? w : w & ((1u << (8u * (uint32_t)left)) - 1u);
+}
+
+// inclusive scan of v over the 256 threads of the workgroup; *total = the sum.  lds: four words
+__device__ __forceinline__ uint32_t owner_block_scan(uint32_t v, uint32_t * lds, uint32_t * total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t up = __shfl_up(v, d, 64);
+    if (lane >= d) { v += up; }
+  }
+  __syncthreads();                                          // (the previous turn's readers are done with lds)
+  if (lane == 63u) { lds[wave] = v; }
+  __syncthreads();
+  const uint32_t w0 = lds[0], w1 = lds[1], w2 = lds[2], w3 = lds[3];
+  *total = w0 + w1 + w2 + w3;
+  return v + (wave > 0u ? w0 : 0u) + (wave > 1u ? w1 : 0u) + (wave > 2u ? w2 : 0u);
+}
+
+// counts[b] = heavy bytes of tile b; one workgroup a tile
+__global__ __launch_bounds__(kOwnerBlock) void k_owner_counts(const uint8_t * __restrict__ role, uint32_t n, uint32_t * __restrict__ counts) {
+  __shared__ uint32_t lds[4];
+  const uint64_t words = ((uint64_t)n + 3u) / 4u, q = (uint64_t)blockIdx.x * kOwnerBlock + threadIdx.x;
+  const uint32_t mine = q < words ? (uint32_t)__popc(owner_role_word(role, q, n) & 0x01010101u) : 0u;
+  uint32_t total = 0;
+  (void)owner_block_scan(mine, lds, &total);
+  if (threadIdx.x == 0) { counts[blockIdx.x] = total; }
+}
+
+// base[t] = heavy bytes in front of tile t, base[tiles] = H; one workgroup, a carry from turn to turn
+__global__ __launch_bounds__(kOwnerTurn) void k_owner_scan(const uint32_t * __restrict__ counts, uint32_t tiles, unsigned long long * __restrict__ base) {
+  static_assert(kOwnerTurn == kOwnerBlock, "owner_block_scan: 256 threads");
+  __shared__ uint32_t lds[4];
+  unsigned long long carry = 0;
+  for (uint32_t first = 0; first < tiles; first += kOwnerTurn) {
+    const uint32_t t = first + threadIdx.x;
+    const uint32_t mine = t < tiles ? counts[t] : 0u;
+    uint32_t total = 0;
+    const uint32_t incl = owner_block_scan(mine, lds, &total);   // (a turn holds 256 * 1024 bytes at most: 32 bits)
+    if (t < tiles) { base[t] = carry + (incl - mine); }
+    carry += total;
+  }
+  if (threadIdx.x == 0) { base[tiles] = carry; }
+}
+
+__global__ __launch_bounds__(kOwnerBlock) void k_owner_write(const uint8_t * __restrict__ role, uint32_t n, const unsigned long long * __restrict__ base,
+                                                             uint32_t tiles, uint32_t nshards, uint8_t * __restrict__ owner) {
+  __shared__ uint32_t lds[4];
+  const uint64_t words = ((uint64_t)n + 3u) / 4u, q = (uint64_t)blockIdx.x * kOwnerBlock + threadIdx.x;
+  const uint32_t w = q < words ? owner_role_word(role, q, n) : 0u;
+  const uint32_t mine = (uint32_t)__popc(w & 0x01010101u);
+  uint32_t total = 0;
+  const uint32_t incl = owner_block_scan(mine, lds, &total);
+  if (q >= words) { return; }
+  const unsigned long long heavy = base[tiles];
+  unsigned long long h = base[blockIdx.x] + (incl - mine);
+  uint32_t four = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j) {
+    uint32_t o = kOwnerLight;
+    if (((w >> (8u * j)) & 1u) != 0u) { o = (uint32_t)(((h + 1ull) * nshards - 1ull) / heavy); ++h; }
+    four |= o << (8u * j);
+  }
+  const uint64_t left = (uint64_t)n - 4u * q;
+  if (left >= 4u) { reinterpret_cast<uint32_t *>(owner)[q] = four; }
+  else { for (uint32_t j = 0; j < (uint32_t)left; ++j) { owner[4u * q + j] = (uint8_t)(four >> (8u * j)); } }
+}
+
+// four amplicons a thread, the tail one by one (as k_light_roles)
+__device__ __forceinline__ uint32_t role_of_owner(uint32_t o, uint32_t shard) { return o == kOwnerLight ? 0u : (o == shard ? 1u : 2u); }
+__global__ __launch_bounds__(256) void k_roles_from_owners(const uint8_t * __restrict__ owner, uint32_t shard, uint32_t n, uint8_t * __restrict__ role) {
+  const uint64_t quads = (uint64_t)n / 4u;
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t w = reinterpret_cast<const uint32_t *>(owner)[q];
+    uint32_t four = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) { four |= role_of_owner((w >> (8u * j)) & 0xFFu, shard) << (8u * j); }
+    reinterpret_cast<uint32_t *>(role)[q] = four;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3u)) {
+    const uint64_t a = 4u * quads + threadIdx.x;
+    role[a] = (uint8_t)role_of_owner(owner[a], shard);
+  }
+}
+
 int need_clustering(swa_ctx * ctx, const char * who) {
   if (ctx->res.cluster_ready && ctx->res.csr_ready) { return SWA_OK; }
   return swa_fail_msg(ctx, SWA_E_ARG, std::string(who) + ": no clustering in place (swa_d1_cluster_device)");
@@ -222,6 +324,7 @@ extern "C" int swa_d1_light_flags_device(swa_ctx * ctx, uint64_t boundary, uint8
   SWA_TRY(need_clustering(ctx, "swa_d1_light_flags_device"));
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   ctx->res.fast.roles_ready = false;
+  ctx->res.fast.owners_ready = false;                       // (owner bytes are made from the role bytes that are replaced here)
   SWA_TRY(ensure_swarm_sums(ctx));
   const uint32_t n = ctx->db.n, w = ctx->res.cluster_nswarms;
   SWA_TRY(swa_reserve(ctx, ctx->d_swarm_role, (uint64_t)n + 4));
@@ -329,5 +432,63 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
   if (parent != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(parent, parent_d, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
   if (child != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(child, child_d, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
+// ---- shard owners ------------------------------------------------------------------------------------------------------
+// owner(h) of the h-th of `heavy` heavy amplicons among nshards shards: the shard whose slice [floor(heavy s / nshards),
+// floor(heavy (s + 1) / nshards)) holds h — the slices of swa_d1_fastidious_shard — in closed form; no device
+extern "C" int swa_d1_shard_owner_for(uint64_t heavy, uint32_t nshards, uint64_t h, uint32_t * owner) {
+  if (owner == nullptr || nshards < 1 || nshards > 64 || heavy > 0xFFFFFFFFull || h >= heavy) { return SWA_E_ARG; }
+  *owner = (uint32_t)(((h + 1ull) * nshards - 1ull) / heavy);
+  return SWA_OK;
+}
+
+// {amplicons per tile of the owner kernels, tiles per turn of the scan of their counts}
+extern "C" int swa_d1_shard_owner_plan(uint32_t out[2]) {
+  if (out == nullptr) { return SWA_E_ARG; }
+  out[0] = kOwnerTile; out[1] = kOwnerTurn;
+  return SWA_OK;
+}
+
+// The owner byte of every amplicon — 255 light, else the shard (of nshards) that expands it — from the role bytes of the last
+// swa_d1_light_flags_device call; left in HBM (d_shard_owner).  owners: n bytes on the host, or null; *heavy = H.
+extern "C" int swa_d1_shard_owners_device(swa_ctx * ctx, uint32_t nshards, uint8_t * owners, uint64_t * heavy) {
+  if (ctx == nullptr || heavy == nullptr) { return SWA_E_ARG; }
+  SWA_TRY(need_clustering(ctx, "swa_d1_shard_owners_device"));
+  if (!ctx->res.fast.roles_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_shard_owners_device: call swa_d1_light_flags_device first"); }
+  if (nshards < 1 || nshards > 64) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_shard_owners_device: 1 to 64 shards"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->res.fast.owners_ready = false;
+  const uint32_t n = ctx->db.n;
+  const uint64_t words = ((uint64_t)n + 3u) / 4u, tiles = (words + kOwnerBlock - 1u) / kOwnerBlock;
+  const uint64_t owner_bytes = ((uint64_t)n + 4u + 7u) & ~uint64_t(7);
+  SWA_TRY(swa_reserve(ctx, ctx->d_shard_owner, owner_bytes + (tiles + 1u) * sizeof(uint64_t) + tiles * sizeof(uint32_t)));
+  auto * owner = static_cast<uint8_t *>(ctx->d_shard_owner.ptr);
+  auto * base = reinterpret_cast<unsigned long long *>(owner + owner_bytes);
+  auto * counts = reinterpret_cast<uint32_t *>(base + tiles + 1u);
+  const auto * role = static_cast<const uint8_t *>(ctx->d_swarm_role.ptr);
+  hipLaunchKernelGGL(k_owner_counts, dim3((uint32_t)tiles), dim3(kOwnerBlock), 0, ctx->stream, role, n, counts);
+  hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(kOwnerTurn), 0, ctx->stream, counts, (uint32_t)tiles, base);
+  hipLaunchKernelGGL(k_owner_write, dim3((uint32_t)tiles), dim3(kOwnerBlock), 0, ctx->stream, role, n, base, (uint32_t)tiles, nshards, owner);
+  SWA_HIP(ctx, hipGetLastError());
+  uint64_t h = 0;
+  SWA_HIP(ctx, hipMemcpyAsync(&h, base + tiles, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  if (owners != nullptr) {
+    swa_touch_pages(owners, n);
+    SWA_HIP(ctx, hipMemcpyAsync(owners, owner, n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *heavy = h;
+  ctx->res.fast.owners_ready = true;
+  ctx->res.fast.owners_shards = nshards;
+  ctx->res.fast.owners_heavy = h;
+  return SWA_OK;
+}
+
+int swa_d1_roles_from_owners(swa_ctx * ctx, const uint8_t * d_owner, uint32_t shard, uint8_t * d_role) {
+  const uint32_t n = ctx->db.n;
+  hipLaunchKernelGGL(k_roles_from_owners, dim3(blocks_for(ctx, n / 4u + 1u)), dim3(256), 0, ctx->stream, d_owner, shard, n, d_role);
+  SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
 }

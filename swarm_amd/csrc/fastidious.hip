@@ -500,10 +500,11 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
 }
 
 // The pass from the roles on (0 light, 1 heavy and to be expanded here, 2 neither): what swa_d1_fastidious_shard and
-// swa_d1_fastidious_resident share.  host_role: the shard form's array, uploaded into d_frole; null: the bytes
+// swa_d1_fastidious_resident share.  host_role: the shard form's array, uploaded into d_frole; d_owner: owner bytes in this
+// context's HBM (swa_d1_shard_owners_device, on rank 0 or as it sent them), mapped for `shard` on the device; neither: the bytes
 // swa_d1_light_flags_device left in d_swarm_role, copied on the device.  Reservations, copies and launches come in the order
 // swa_d1_fastidious_shard has always made them.  graft_cand may be null: the candidates then stay in HBM (d_graft) only.
-static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
+static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, const uint8_t * d_owner, uint32_t shard, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
                                  uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
   SWA_TRY(swa_prepare_hashing(ctx));                         // the Zobrist table
   const uint32_t n = ctx->db.n;
@@ -530,6 +531,7 @@ static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, uint6
   SWA_TRY(swa_reserve(ctx, ctx->d_list_b, (uint64_t(n) + 1) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_fcounters, sizeof(swa_fast_counters)));
   if (host_role != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, host_role, n, hipMemcpyHostToDevice, ctx->stream)); }
+  else if (d_owner != nullptr) { SWA_TRY(swa_d1_roles_from_owners(ctx, d_owner, shard, static_cast<uint8_t *>(ctx->d_frole.ptr))); }
   else { SWA_HIP(ctx, hipMemcpyAsync(ctx->d_frole.ptr, ctx->d_swarm_role.ptr, n, hipMemcpyDeviceToDevice, ctx->stream)); }
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_graft.ptr, 0xFF, uint64_t(n) * sizeof(uint32_t), ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_fcounters.ptr, 0, sizeof(swa_fast_counters), ctx->stream));
@@ -615,7 +617,7 @@ extern "C" int swa_d1_fastidious_shard(swa_ctx * ctx, const uint8_t * is_light, 
     }
   });
   const uint64_t n_heavy = hi - lo;
-  const int rc = fastidious_with_roles(ctx, role.get(), n_light, n_heavy, light_nt, bloom_bits, graft_cand, counters);
+  const int rc = fastidious_with_roles(ctx, role.get(), nullptr, 0, n_light, n_heavy, light_nt, bloom_bits, graft_cand, counters);
   if (rc != SWA_OK) { (void)hipStreamSynchronize(ctx->stream); }     // (role is a host temporary)
   ctx->res.fast.cand_ready = rc == SWA_OK && nshards == 1u;   // (d_graft: the candidates of the whole pass, for swa_d1_graft_device)
   return rc;
@@ -638,7 +640,18 @@ extern "C" int swa_d1_fastidious_resident(swa_ctx * ctx, uint64_t light_nt, uint
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
   const uint64_t n_light = ctx->res.fast.light_amps;
-  SWA_TRY(fastidious_with_roles(ctx, nullptr, n_light, n - n_light, light_nt, bloom_bits, graft_cand, counters));
+  SWA_TRY(fastidious_with_roles(ctx, nullptr, nullptr, 0, n_light, n - n_light, light_nt, bloom_bits, graft_cand, counters));
   ctx->res.fast.cand_ready = true;
   return SWA_OK;
+}
+
+// One shard of the pass with its roles from owner bytes in HBM: what a rank of swa_multi_d1_fastidious_resident runs.  The
+// candidates of this shard alone are left in d_graft (cand_ready stays false: the caller combines the shards first).
+int swa_d1_fastidious_owned(swa_ctx * ctx, const uint8_t * d_owner, uint32_t shard, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
+                            uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (!ctx->ix.d1_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: call swa_d1_index_build first"); }
+  if (d_owner == nullptr || counters == nullptr || bloom_bits < 2 || bloom_bits > 64) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_fastidious: bad argument"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  return fastidious_with_roles(ctx, nullptr, d_owner, shard, n_light, n_heavy, light_nt, bloom_bits, graft_cand, counters);
 }

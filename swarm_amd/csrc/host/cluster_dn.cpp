@@ -57,17 +57,25 @@ static bool graph_route_wanted(int64_t differences) {
   return differences <= kGraphDefaultMaxD;
 }
 
+// SWARM_AMD_TIMING=1: milliseconds since the first stamp of the clustering phase at every milestone, on stderr
+static void dn_stamp(const char * what) {
+  static const bool on = std::getenv("SWARM_AMD_TIMING") != nullptr;
+  static const auto t0 = std::chrono::steady_clock::now();
+  if (on) { std::fprintf(stderr, "[dn %8.3f ms] %s\n", 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), what); }
+}
+
 // The greedy agglomeration of algo_run (src/algo.cc:384-602) over the complete graph of pairs within d differences
 // (swa_dn_graph: row q = the targets t with diff(q, t) <= d that the abundance rule lets q take, ascending, with
 // their diffs).  Same order-defining rules as the loop in swa_dn_cluster: seeds by lowest unswarmed id, a sub-seed's
 // hits in pool (= id) order, queue kept sorted by generation then id (src/algo.cc:205-219).
-// (multi != nullptr: the graph comes from several GPUs, swa_multi_dn_graph)
+// (multi != nullptr: the graph comes from several GPUs, swa_multi_dn_graph — the route of SWARM_AMD_MULTI_CLUSTER=host)
 static int cluster_over_graph(swa_ctx * ctx, swa_multi * multi, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
   const uint32_t n = db->n;
   std::vector<uint64_t> off((size_t)n + 1);
   std::vector<uint32_t> nb;
   std::vector<uint8_t> df;
   uint64_t total = 0;
+  dn_stamp("graph: start");
   auto graph = [&](uint32_t * nbp, uint8_t * dfp, uint64_t cap) {
     return multi != nullptr ? swa_multi_dn_graph(multi, no_cluster_breaking, off.data(), nbp, dfp, cap, &total)
                             : swa_dn_graph(ctx, no_cluster_breaking, off.data(), nbp, dfp, cap, &total);
@@ -78,6 +86,7 @@ static int cluster_over_graph(swa_ctx * ctx, swa_multi * multi, const swa_hostdb
     rc = graph(nb.data(), df.data(), total);
   }
   if (rc != SWA_OK) { r->error = multi != nullptr ? swa_multi_last_error(multi) : swa_last_error(ctx); return rc; }
+  dn_stamp("graph: downloaded");
   std::vector<uint8_t> swarmed(n, 0);
   std::vector<swa_dn_result::Member> queue;
   r->order.reserve(n);
@@ -120,6 +129,7 @@ static int cluster_over_graph(swa_ctx * ctx, swa_multi * multi, const swa_hostdb
     r->maxgenerations = std::max<uint64_t>(r->maxgenerations, sw.maxgen);
     r->swarms.push_back(sw);
   }
+  dn_stamp("host walk: swarms made");
   return SWA_OK;
 }
 
@@ -128,19 +138,19 @@ static int cluster_over_graph(swa_ctx * ctx, swa_multi * multi, const swa_hostdb
 // its seed reaches, a member's generation = its distance from the seed, its parent = the smallest id of the previous
 // generation that points at it — cluster_gpu.hip), and only five arrays of n entries come back instead of the graph.
 // Radii and the -i lines (acceptance order: sub-seeds in queue order, each one's hits by id) follow from the parents.
-// SWARM_AMD_TIMING=1: milliseconds since the first stamp of the clustering phase at every milestone, on stderr
-static void dn_stamp(const char * what) {
-  static const bool on = std::getenv("SWARM_AMD_TIMING") != nullptr;
-  static const auto t0 = std::chrono::steady_clock::now();
-  if (on) { std::fprintf(stderr, "[dn %8.3f ms] %s\n", 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), what); }
+// the graph of the whole database resident on ctx: its own, or (multi != nullptr, ctx = its rank 0) merged from all ranks' shares
+static int graph_resident(swa_ctx * ctx, swa_multi * multi, int no_cluster_breaking, uint64_t * total, swa_dn_result * r) {
+  const int rc = multi != nullptr ? swa_multi_dn_graph_resident(multi, no_cluster_breaking, total) : swa_dn_graph_resident(ctx, no_cluster_breaking, total);
+  if (rc != SWA_OK) { r->error = multi != nullptr ? swa_multi_last_error(multi) : swa_last_error(ctx); }
+  return rc;
 }
 
-static int cluster_on_device(swa_ctx * ctx, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
+static int cluster_on_device(swa_ctx * ctx, swa_multi * multi, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
   const uint32_t n = db->n;
   uint64_t total = 0;
   dn_stamp("graph: start");
-  int rc = swa_dn_graph_resident(ctx, no_cluster_breaking, &total);
-  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+  int rc = graph_resident(ctx, multi, no_cluster_breaking, &total, r);
+  if (rc != SWA_OK) { return rc; }
   dn_stamp("graph: resident");
   // (no serial zero fill of arrays the downloads overwrite: 40 MB of them at 1 M amplicons were a third of the 11 ms the
   // tables below took, lease r6j; their pages faulted in by the team instead of the copying thread)
@@ -221,12 +231,12 @@ static bool tables_on_device() {
   return where == nullptr || std::strcmp(where, "host") != 0;
 }
 
-static int cluster_on_device_tables(swa_ctx * ctx, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
+static int cluster_on_device_tables(swa_ctx * ctx, swa_multi * multi, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
   const uint32_t n = db->n;
   uint64_t total = 0, nlinks = 0;
   dn_stamp("graph: start");
-  int rc = swa_dn_graph_resident(ctx, no_cluster_breaking, &total);
-  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+  int rc = graph_resident(ctx, multi, no_cluster_breaking, &total, r);
+  if (rc != SWA_OK) { return rc; }
   dn_stamp("graph: resident");
   swa_vec<uint32_t> begins((size_t)n + 1);
   r->order.resize(n);
@@ -288,10 +298,19 @@ static bool need_links(const swa_dn_result * cr) {
   return true;
 }
 
+// SWARM_AMD_MULTI_CLUSTER=device|host: where a run on several GPUs clusters what the exchange assembled on rank 0.  The
+// default follows the measurement of profiles/r23/NOTES.md (two ranks on one MI355X; from the assembled network or graph to
+// the clustering: 20 ms against 255 at d = 1 on 10 M x 150, 104 against 252 with -f, 2.4 against 68 at d = 3 on 1 M x 400).
+extern "C" int swa_multi_cluster_on_device(void) {
+  const char * where = std::getenv("SWARM_AMD_MULTI_CLUSTER");
+  return where == nullptr || std::strcmp(where, "host") != 0 ? 1 : 0;
+}
+
 // d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups (and of the short
 // sequences, whose pairs are found by brute force); a database the graph route cannot serve (d > 16, or too many candidate
 // pairs with a sequence too short for d + 1 windows) or does not serve by default (graph_route_wanted) is clustered by
-// rank 0 alone with the fused scan.
+// rank 0 alone with the fused scan.  The merged graph stays on rank 0's GPU, where the walk and the tables of the single-GPU
+// graph route run on it (swa_multi_dn_graph_resident), unless SWARM_AMD_MULTI_CLUSTER=host asks for the download and the host's walk.
 extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                                     uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
   if (multi == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
@@ -310,7 +329,13 @@ extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, in
       r->differences = differences;
       r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
       r->over_graph = true;
-      return cluster_over_graph(swa_multi_ctx(multi, 0), multi, db, no_cluster_breaking, r);
+      swa_ctx * ctx0 = swa_multi_ctx(multi, 0);
+      // (the switches of the single-GPU walk keep their meaning: SWARM_AMD_DN_WALK=host, and d >= 255, walk on the host)
+      const char * walk = std::getenv("SWARM_AMD_DN_WALK");
+      if (swa_multi_cluster_on_device() == 0 || (walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) {
+        return cluster_over_graph(ctx0, multi, db, no_cluster_breaking, r);
+      }
+      return tables_on_device() ? cluster_on_device_tables(ctx0, multi, db, no_cluster_breaking, r) : cluster_on_device(ctx0, multi, db, no_cluster_breaking, r);
     }
   }
   return swa_dn_cluster(swa_multi_ctx(multi, 0), db, differences, no_cluster_breaking, mismatch, gapopen, gapextend, out);
@@ -347,7 +372,7 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
     // (differences of 255 are what the device walk's parent-difference bytes use for "no link": d >= 255 walks on the host)
     if ((walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) { return cluster_over_graph(ctx, nullptr, db, no_cluster_breaking, r); }
     (void)swa_dn_set_ownership(ctx, 0, 1);                    // (a context that served one rank's share before: the whole graph)
-    return tables_on_device() ? cluster_on_device_tables(ctx, db, no_cluster_breaking, r) : cluster_on_device(ctx, db, no_cluster_breaking, r);
+    return tables_on_device() ? cluster_on_device_tables(ctx, nullptr, db, no_cluster_breaking, r) : cluster_on_device(ctx, nullptr, db, no_cluster_breaking, r);
   }
   if (want_graph) {
     r->error = differences > 16 ? "SWARM_AMD_DN=graph: the graph route serves d <= 16" : "SWARM_AMD_DN=graph: a sequence is too short for d + 1 windows";

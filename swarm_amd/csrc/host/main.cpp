@@ -358,7 +358,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
 
   const uint32_t n = uview.n;
   swa_ctx * ctx = nullptr;
-  swa_multi * multi = nullptr;           // d = 1 on several GPUs: SWARM_AMD_DEVICES=0,1,2,... (one rank per entry)
+  swa_multi * multi = nullptr;           // d >= 1 on several GPUs: SWARM_AMD_DEVICES=0,1,2,... (one rank per entry)
   if (n > 0) {
     if (use_multi) {
       if (swa_multi_create(devices.data(), (int)devices.size(), &multi) != SWA_OK) {
@@ -366,6 +366,8 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       }
       if (std::getenv("SWARM_AMD_MULTI_REPORT") != nullptr) {      // (tools/scale_check.sh asserts on this line)
         std::fprintf(stderr, "multi: %d ranks, exchange = %s\n", swa_multi_size(multi), swa_multi_uses_rccl(multi) ? "rccl" : "device-to-device copies");
+        // (what SWARM_AMD_MULTI_CLUSTER selects for d >= 1; d >= 2 still walks on the host where SWARM_AMD_DN_WALK=host or the scan route says so)
+        if (o.differences >= 1) { std::fprintf(stderr, "multi: clustering on %s\n", swa_multi_cluster_on_device() != 0 ? "rank 0's GPU" : "the host"); }
       }
       swa_db_view view{};                                    // (several GPUs: the db-order host arrays, gathered on the host)
       swa_hostdb_view(db, &view);
@@ -418,17 +420,37 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     swa_d1_result * prepared = nullptr;
     int prepare_rc = SWA_OK;
     std::thread preparing;
-    std::vector<uint64_t> offsets;              // (the CSR only comes to the host for -j and from several GPUs)
+    std::vector<uint64_t> offsets;              // (the CSR only comes to the host for -j, and from several GPUs under SWARM_AMD_MULTI_CLUSTER=host)
     std::vector<uint32_t> neighbours;
     bool resident = false;
-    if (multi != nullptr || !o.network.empty()) { offsets.assign((size_t)n + 1, 0); }
+    if ((multi != nullptr && swa_multi_cluster_on_device() == 0) || !o.network.empty()) { offsets.assign((size_t)n + 1, 0); }
     const char * dup_text = "some fasta entries have identical sequences.\n"
                             "Swarm expects dereplicated fasta files.\n"
                             "Such files can be produced with swarm or vsearch:\n"
                             " swarm -d 0 -w derep.fasta -o /dev/null input.fasta\n"
                             "or\n"
                             " vsearch --derep_fulllength input.fasta --sizein --sizeout --output derep.fasta\n";
-    if (n > 0 && multi != nullptr) {
+    if (n > 0 && multi != nullptr && swa_multi_cluster_on_device() != 0) {
+      // several GPUs, the network left on rank 0's GPU (ctx): from here on the run is the single-GPU one below
+      preparing = std::thread([&prepared, &prepare_rc, ctx, db]() {
+        prepare_rc = swa_d1_result_prepare(ctx, db, &prepared);
+        stamp("(helper thread) result arrays pinned");
+      });
+      uint64_t total = 0;
+      int dup = 0;
+      rc = swa_multi_d1_network_resident(multi, o.no_break ? 1 : 0, &total, &dup);
+      if (rc != SWA_OK && preparing.joinable()) { preparing.join(); }
+      if (rc == SWA_E_DUPLICATES) { die(dup_text); }
+      if (rc != SWA_OK) { die(swa_multi_last_error(multi)); }
+      stamp("network resident on rank 0");
+      resident = true;
+      if (!o.network.empty()) {
+        neighbours.resize(total);
+        if (swa_d1_network_fetch(ctx, offsets.data(), neighbours.data(), neighbours.size()) != SWA_OK) { die(swa_last_error(ctx)); }
+      }
+      phase(o, "Hashing sequences:");
+      phase(o, "Building network: ");
+    } else if (n > 0 && multi != nullptr) {
       uint64_t total = 0;
       int dup = 0;
       neighbours.resize(std::max<size_t>(4 * (size_t)n, 1024));
@@ -440,6 +462,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
         break;
       }
       neighbours.resize(total);
+      stamp("network assembled and downloaded");
       phase(o, "Hashing sequences:");
       phase(o, "Building network: ");
     } else if (n > 0) {
@@ -496,10 +519,11 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       std::fprintf(g_log, "Number of swarms:  %" PRIu64 "\n", sum[0]);
       std::fprintf(g_log, "Largest swarm:     %" PRIu64 "\n\n", sum[1]);
       // One context with the clustering still in HBM (the usual run): sums, flags, candidates and grafting stay on the GPU
-      // (swa_d1_light_flags_device .. swa_d1_graft_device).  Several GPUs and a clustering made on the host take the host's
-      // bookkeeping; SWARM_AMD_FASTIDIOUS=host selects it for comparison.
+      // (swa_d1_light_flags_device .. swa_d1_graft_device) — with several GPUs rank 0's, the second pass shared out from its
+      // flags (swa_multi_d1_fastidious_resident).  A clustering made on the host takes the host's bookkeeping;
+      // SWARM_AMD_FASTIDIOUS=host selects it for comparison.
       const char * fast_route = std::getenv("SWARM_AMD_FASTIDIOUS");
-      const bool on_device = resident && multi == nullptr && !(fast_route != nullptr && std::strcmp(fast_route, "host") == 0);
+      const bool on_device = resident && !(fast_route != nullptr && std::strcmp(fast_route, "host") == 0);
       swa_vec<uint8_t> is_light(on_device ? 0 : n);         // (every entry is written by swa_d1_light_flags: each amplicon is in one swarm)
       uint64_t st[5];
       if (on_device) { if (swa_d1_light_flags_device(ctx, (uint64_t)o.boundary, nullptr, st) != SWA_OK) { die(swa_last_error(ctx)); } }
@@ -538,7 +562,10 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
         if (m < 64) { m = 64; }
         std::fprintf(g_log, "Bloom filter: bits=%" PRIu64 ", m=%" PRIu64 ", k=%u, size=%.1fMB\n", bits, m, k,
                      (double)m / (8.0 * 1024.0 * 1024.0));
-        if (on_device) {
+        if (on_device && multi != nullptr) {
+          rc = swa_multi_d1_fastidious_resident(multi, st[2], (uint32_t)bits, nullptr, counters);
+          if (rc != SWA_OK) { die(swa_multi_last_error(multi)); }
+        } else if (on_device) {
           rc = swa_d1_fastidious_resident(ctx, st[2], (uint32_t)bits, nullptr, counters);
           if (rc != SWA_OK) { die(swa_last_error(ctx)); }
         } else if (multi != nullptr) {

@@ -8,9 +8,12 @@
 // link of the network is found by exactly one rank.  Exchange, as SURVEY 8e / the north star name it: the
 // per-rank hit counts are known on the host when the kernels return, then every rank's flat link list is
 // gathered on rank 0 — the one consumer: grouped ncclSend / ncclRecv (round 2 all-gathered the whole network into every
-// GPU) —, and the CSR is made there by the partition + row kernels of the single-GPU step (swa_d1_csr_from_lists).  Fastidious: the heavy amplicons are split
-// (swa_d1_fastidious_shard), graft_cand is combined with swa_rccl().AllReduce(min) (src/algod1.cc:244-258 keeps
-// the smallest heavy id), the two heavy-side counters add up.
+// GPU) —, and the CSR is made there by the partition + row kernels of the single-GPU step (swa_d1_csr_from_lists).  It is
+// then downloaded for the host (swa_multi_d1_network) or left as rank 0's resident network (swa_multi_d1_network_resident):
+// agglomeration, swarm sums, light flags and grafting then run on rank 0's GPU as they do on a single one.  Fastidious: the
+// heavy amplicons are split — by the host from host flags (swa_d1_fastidious_shard), or by owner bytes that rank 0 makes
+// from its flags in HBM and broadcasts (swa_multi_d1_fastidious_resident) —, graft_cand is combined with
+// swa_rccl().AllReduce(min) (src/algod1.cc:244-258 keeps the smallest heavy id), the two heavy-side counters add up.
 //
 // The same code runs with several contexts on ONE device (SWARM_AMD_DEVICES=0,0: what a one-GPU box can
 // test); RCCL refuses two ranks on one GPU, so that configuration moves the same bytes with device-to-
@@ -269,13 +272,16 @@ static int routed_index_build(swa_multi * m, std::vector<int> & dup, bool * rout
   });
 }
 
-// the whole network of the database as a CSR on the host (buffers and capacity protocol of swa_d1_network)
-extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint64_t * offsets, uint32_t * neighbours, uint64_t cap,
-                                    uint64_t * total, int * has_duplicates) {
-  if (m == nullptr || offsets == nullptr || total == nullptr || (neighbours == nullptr && cap != 0)) { return SWA_E_ARG; }
+// The whole network of the database assembled as a CSR on rank 0's device, and then either downloaded (resident = false:
+// swa_multi_d1_network) or left there as rank 0's resident network (swa_multi_d1_network_resident: offsets and neighbours unused).
+static int d1_network_on_root(swa_multi * m, int no_cluster_breaking, bool resident, uint64_t * offsets, uint32_t * neighbours, uint64_t cap,
+                              uint64_t * total, int * has_duplicates) {
   const int world = (int)m->ctx.size();
   const uint32_t n = m->ctx[0]->db.n;
   if (n == 0) { return fail(m, SWA_E_ARG, "swa_multi_d1_network: no database"); }
+  m->ctx[0]->res.csr_ready = false;                            // (whatever fails below: no resident network on rank 0)
+  m->ctx[0]->res.cluster_ready = false;
+  m->ctx[0]->res.tables = {};
   // 1. every rank indexes and probes the anchor groups it owns
   std::vector<int> dup((size_t)world, 0);
   std::vector<uint64_t> count((size_t)world, 0);
@@ -324,7 +330,7 @@ extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint
     rc = gather_to_root_v(m, src, m->gathered.ptr, count, sizeof(uint64_t));
     if (rc != SWA_OK) { return rc; }
   }
-  // 3. rank 0: the gathered lists -> CSR -> host.  The partition + row kernels of the single-GPU step (d1.hip: csr_from_chunks,
+  // 3. rank 0: the gathered lists -> CSR (-> host).  The partition + row kernels of the single-GPU step (d1.hip: csr_from_chunks,
   // the ranks' lists as the chunks of its first level) where round 3 ran a 64-bit radix sort over all links.
   swa_ctx * c0 = m->ctx[0];
   if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
@@ -339,18 +345,39 @@ extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint
     SWA_TRY(swa_d1_csr_from_lists(c0, reinterpret_cast<const uint64_t *>(keys_in), starts.data(), count.data(), (uint32_t)world, 0, n,
                                   static_cast<uint64_t *>(c0->d_offsets_tmp.ptr), static_cast<uint32_t *>(c0->d_nb_tmp.ptr), all + 1, &need));
     (void)need;
-    SWA_HIP(c0, hipMemcpyAsync(offsets, c0->d_offsets_tmp.ptr, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c0->stream));
-    if (all != 0 && all <= cap) {
-      SWA_HIP(c0, hipMemcpyAsync(neighbours, c0->d_nb_tmp.ptr, all * sizeof(uint32_t), hipMemcpyDeviceToHost, c0->stream));
+    if (!resident) {
+      SWA_HIP(c0, hipMemcpyAsync(offsets, c0->d_offsets_tmp.ptr, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c0->stream));
+      if (all != 0 && all <= cap) {
+        SWA_HIP(c0, hipMemcpyAsync(neighbours, c0->d_nb_tmp.ptr, all * sizeof(uint32_t), hipMemcpyDeviceToHost, c0->stream));
+      }
     }
     SWA_HIP(c0, hipGetLastError());
-    SWA_HIP(c0, hipStreamSynchronize(c0->stream));
+    SWA_HIP(c0, hipStreamSynchronize(c0->stream));           // (m->gathered, which the row kernels read, is free for the next exchange)
+    if (resident) {                                            // the state swa_d1_network_resident leaves
+      c0->res.csr_ready = true;
+      c0->res.csr_has_diffs = false;
+      c0->res.csr_total = all;
+    }
     return SWA_OK;
   };
   rc = stage();
   if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
-  if (all > cap) { return fail(m, SWA_E_CAPACITY, "swa_multi_d1_network: neighbour buffer too small"); }
+  if (!resident && all > cap) { return fail(m, SWA_E_CAPACITY, "swa_multi_d1_network: neighbour buffer too small"); }
   return SWA_OK;
+}
+
+// the whole network of the database as a CSR on the host (buffers and capacity protocol of swa_d1_network)
+extern "C" int swa_multi_d1_network(swa_multi * m, int no_cluster_breaking, uint64_t * offsets, uint32_t * neighbours, uint64_t cap,
+                                    uint64_t * total, int * has_duplicates) {
+  if (m == nullptr || offsets == nullptr || total == nullptr || (neighbours == nullptr && cap != 0)) { return SWA_E_ARG; }
+  return d1_network_on_root(m, no_cluster_breaking, false, offsets, neighbours, cap, total, has_duplicates);
+}
+
+// ... or left where it was assembled: rank 0's context holds it as swa_d1_network_resident would (swa_d1_network_fetch,
+// swa_d1_cluster_device and everything behind it work on swa_multi_ctx(m, 0)); nothing comes to the host
+extern "C" int swa_multi_d1_network_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total, int * has_duplicates) {
+  if (m == nullptr || total == nullptr) { return SWA_E_ARG; }
+  return d1_network_on_root(m, no_cluster_breaking, true, nullptr, nullptr, 0, total, has_duplicates);
 }
 
 // B2 on all GPUs: heavy amplicons split over the ranks, graft_cand combined with MIN, heavy counters summed
@@ -402,11 +429,101 @@ extern "C" int swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, 
   return SWA_OK;
 }
 
+// B2 on all GPUs from the flags in rank 0's HBM (swa_d1_light_flags_device on swa_multi_ctx(m, 0)): rank 0 makes the owner byte
+// of every amplicon (swa_d1_shard_owners_device, S = world), the bytes travel to every rank — ncclBroadcast, or device-to-
+// device copies when ranks share a device —, every rank maps them to its roles on its own GPU and runs its shard of the pass,
+// and the candidates are combined into rank 0's d_graft, where swa_d1_graft_device(ctx0, NULL, ...) reads them.  No flag, role
+// or candidate array crosses the host (the candidates only when graft_cand is not null).
+extern "C" int swa_multi_d1_fastidious_resident(swa_multi * m, uint64_t light_nt, uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
+  if (m == nullptr || counters == nullptr) { return SWA_E_ARG; }
+  const int world = (int)m->ctx.size();
+  swa_ctx * c0 = m->ctx[0];
+  const uint32_t n = c0->db.n;
+  if (!c0->res.cluster_ready || !c0->res.csr_ready || !c0->res.fast.roles_ready) {
+    return fail(m, SWA_E_ARG, "swa_multi_d1_fastidious_resident: rank 0 holds no clustering with flags (swa_d1_cluster_device, swa_d1_light_flags_device)");
+  }
+  if (!c0->ix.d1_ready) { return fail(m, SWA_E_ARG, "swa_multi_d1_fastidious_resident: rank 0's index has been given up (its clustering would end with a new one)"); }
+  uint64_t heavy = 0;
+  // (returns with rank 0's stream synchronised: the other ranks' streams, which do not order against it, may read the bytes)
+  int rc = swa_d1_shard_owners_device(c0, (uint32_t)world, nullptr, &heavy);
+  if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
+  const uint64_t n_light = c0->res.fast.light_amps;
+  for (int r = 1; r < world; ++r) {
+    swa_ctx * c = m->ctx[(size_t)r];
+    if (hipSetDevice(c->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
+    rc = swa_reserve(c, c->d_shard_owner, (uint64_t)n + 4);
+    if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c)); }
+  }
+  if (!m->comms.empty()) {
+    NCCL_OK(m, swa_rccl().GroupStart());
+    for (int r = 0; r < world; ++r) {
+      swa_ctx * c = m->ctx[(size_t)r];
+      NCCL_OK(m, swa_rccl().Broadcast(c->d_shard_owner.ptr, c->d_shard_owner.ptr, n, ncclUint8, 0, m->comms[(size_t)r], c->stream));
+    }
+    NCCL_OK(m, swa_rccl().GroupEnd());
+  } else {
+    for (int r = 1; r < world; ++r) {
+      swa_ctx * c = m->ctx[(size_t)r];
+      if (hipSetDevice(c->device) != hipSuccess ||
+          hipMemcpyAsync(c->d_shard_owner.ptr, c0->d_shard_owner.ptr, n, hipMemcpyDefault, c->stream) != hipSuccess) {
+        return fail(m, SWA_E_DEVICE, "device-to-device copy of the owner bytes failed");
+      }
+    }
+  }
+  std::vector<std::vector<uint64_t>> cnt((size_t)world, std::vector<uint64_t>(8, 0));
+  rc = on_all(m, [&](int r) {
+    swa_ctx * c = m->ctx[(size_t)r];
+    if (r != 0 && !c->ix.d1_ready) { int dup = 0; SWA_TRY(swa_d1_index_build(c, &dup)); }
+    const uint64_t lo = heavy * (uint64_t)r / (uint64_t)world, hi = heavy * ((uint64_t)r + 1) / (uint64_t)world;
+    return swa_d1_fastidious_owned(c, static_cast<const uint8_t *>(c->d_shard_owner.ptr), (uint32_t)r, n_light, hi - lo, light_nt, bloom_bits,
+                                   nullptr, cnt[(size_t)r].data());
+  });
+  if (rc != SWA_OK) { return rc; }                           // (every rank's pass ends with its stream synchronised)
+  for (int k = 0; k < 5; ++k) { counters[k] = cnt[0][(size_t)k]; }
+  for (int r = 1; r < world; ++r) { counters[1] += cnt[(size_t)r][1]; counters[2] += cnt[(size_t)r][2]; }
+  // element-wise minimum of the ranks' candidates into rank 0's d_graft
+  if (!m->comms.empty()) {
+    NCCL_OK(m, swa_rccl().GroupStart());
+    for (int r = 0; r < world; ++r) {
+      swa_ctx * c = m->ctx[(size_t)r];
+      NCCL_OK(m, swa_rccl().AllReduce(c->d_graft.ptr, c->d_graft.ptr, n, ncclUint32, ncclMin, m->comms[(size_t)r], c->stream));
+    }
+    NCCL_OK(m, swa_rccl().GroupEnd());
+    for (int r = 1; r < world; ++r) {
+      if (hipSetDevice(m->devices[(size_t)r]) != hipSuccess || hipStreamSynchronize(m->ctx[(size_t)r]->stream) != hipSuccess) {
+        return fail(m, SWA_E_DEVICE, "synchronising the exchange of the graft candidates failed");
+      }
+    }
+    if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
+  } else if (world > 1) {
+    if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
+    rc = swa_reserve(c0, m->gathered, (uint64_t)n * sizeof(uint32_t));
+    if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
+    for (int r = 1; r < world; ++r) {
+      if (hipMemcpyAsync(m->gathered.ptr, m->ctx[(size_t)r]->d_graft.ptr, (uint64_t)n * sizeof(uint32_t), hipMemcpyDefault, c0->stream) != hipSuccess) {
+        return fail(m, SWA_E_DEVICE, "device-to-device copy of graft candidates failed");
+      }
+      hipLaunchKernelGGL(k_min_u32, dim3(blocks_for(c0, n)), dim3(256), 0, c0->stream, static_cast<uint32_t *>(c0->d_graft.ptr),
+                         static_cast<const uint32_t *>(m->gathered.ptr), (uint64_t)n);
+    }
+  }
+  if (graft_cand != nullptr) {
+    swa_touch_pages(graft_cand, (uint64_t)n * sizeof(uint32_t));
+    if (hipMemcpyAsync(graft_cand, c0->d_graft.ptr, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c0->stream) != hipSuccess) {
+      return fail(m, SWA_E_DEVICE, "download of the combined graft candidates failed");
+    }
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c0->stream) != hipSuccess) { return fail(m, SWA_E_DEVICE, "combining the graft candidates failed"); }
+  c0->res.fast.cand_ready = true;                              // (d_graft on rank 0: the candidates of the whole pass)
+  return SWA_OK;
+}
+
 // ---- d >= 2 on several GPUs: the bulk graph (dn_graph.hip) divided by ownership of window groups ------------------
 // Replaces the scan fan-out of src/scan.cc:221-256 under the loop of src/algo.cc:505-602: every rank finds the pairs of
 // the window groups it owns (swa_dn_set_ownership) and aligns them; the accepted (query, target, diff) triples travel
 // to rank 0 — ncclSend / ncclRecv over RCCL, device-to-device copies when ranks share a device —, which sorts them
-// into the CSR of swa_dn_graph.  The greedy walk over it stays on the host (cluster_dn.cpp).
+// into the CSR of swa_dn_graph — downloaded for the host's greedy walk (swa_multi_dn_graph), or left as rank 0's resident
+// network, where swa_d1_cluster_device walks it and dn_tables.inc makes radii and links (swa_multi_dn_graph_resident).
 extern "C" int swa_multi_dn_begin(swa_multi * m, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t d) {
   if (m == nullptr) { return SWA_E_ARG; }
   return on_all(m, [&](int r) {
@@ -422,10 +539,13 @@ extern "C" int swa_multi_dn_graph_supported(swa_multi * m) {
   return 1;
 }
 
-extern "C" int swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64_t * offsets, uint32_t * neighbours, uint8_t * diffs,
-                                  uint64_t cap, uint64_t * total) {
-  if (m == nullptr || offsets == nullptr || total == nullptr || (cap != 0 && (neighbours == nullptr || diffs == nullptr))) { return SWA_E_ARG; }
+static int dn_graph_on_root(swa_multi * m, int no_cluster_breaking, bool resident, uint64_t * offsets, uint32_t * neighbours, uint8_t * diffs,
+                            uint64_t cap, uint64_t * total) {
   const int world = (int)m->ctx.size();
+  if (resident) {                                              // (whatever fails below: no resident network on rank 0)
+    m->ctx[0]->res.csr_ready = false;
+    m->ctx[0]->res.tables = {};
+  }
   int rc = on_all(m, [&](int r) {
     swa_ctx * c = m->ctx[(size_t)r];
     SWA_TRY(swa_dn_set_ownership(c, (uint32_t)r, (uint32_t)world));
@@ -486,11 +606,30 @@ extern "C" int swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64
       hipLaunchKernelGGL(k_merge_sorted_lists, dim3(blocks_for(c0, all)), dim3(256), 0, c0->stream, ma);
       SWA_HIP(c0, hipGetLastError());
     }
-    return swa_dn_graph_emit(c0, all != 0 ? keys + all + 1 : nullptr, all != 0 ? vals + all + 1 : nullptr, all, offsets, neighbours, diffs, cap, total);
+    const unsigned long long * sorted = all != 0 ? keys + all + 1 : nullptr;
+    const uint32_t * svals = all != 0 ? vals + all + 1 : nullptr;
+    if (!resident) { return swa_dn_graph_emit(c0, sorted, svals, all, offsets, neighbours, diffs, cap, total); }
+    SWA_TRY(swa_dn_graph_install(c0, sorted, svals, all));
+    *total = all;
+    // (m->gathered and m->links[0], which the split reads, are free for the next exchange once it has run)
+    if (hipStreamSynchronize(c0->stream) != hipSuccess) { c0->res.csr_ready = false; return swa_fail_msg(c0, SWA_E_DEVICE, "swa_multi_dn_graph_resident: the split of the merged graph failed"); }
+    return SWA_OK;
   };
   rc = stage();
   if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
   return SWA_OK;
+}
+
+extern "C" int swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64_t * offsets, uint32_t * neighbours, uint8_t * diffs,
+                                  uint64_t cap, uint64_t * total) {
+  if (m == nullptr || offsets == nullptr || total == nullptr || (cap != 0 && (neighbours == nullptr || diffs == nullptr))) { return SWA_E_ARG; }
+  return dn_graph_on_root(m, no_cluster_breaking, false, offsets, neighbours, diffs, cap, total);
+}
+
+// ... or left on rank 0 as its resident network, as swa_dn_graph_resident leaves a single context's (csr_has_diffs)
+extern "C" int swa_multi_dn_graph_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total) {
+  if (m == nullptr || total == nullptr) { return SWA_E_ARG; }
+  return dn_graph_on_root(m, no_cluster_breaking, true, nullptr, nullptr, nullptr, 0, total);
 }
 
 // out3 = {q-gram comparisons, aligned pairs, kernel launches} over all ranks

@@ -236,6 +236,9 @@ struct swa_resident {
     bool roles_ready = false;                  // d_swarm_role: 0 light / 1 heavy per amplicon, against the boundary of the last flags call
     uint64_t light_amps = 0;                   // ... and how many amplicons it found in light swarms
     bool cand_ready = false;                   // d_graft: the candidates of a whole swa_d1_fastidious* pass (or a caller's) over this clustering
+    bool owners_ready = false;                 // d_shard_owner: the owner byte of every amplicon, made from d_swarm_role (swa_d1_shard_owners_device)
+    uint32_t owners_shards = 0;                // ... for so many shards,
+    uint64_t owners_heavy = 0;                 // and how many heavy amplicons it counted
   } fast;
   // what the d >= 2 graph route derives from the clustering in place and keeps in HBM (dn_tables.inc): every member's radius,
   // the deepest radius of every swarm, the -i links in acceptance order; ended with the clustering
@@ -348,6 +351,9 @@ struct swa_ctx {
   // --fastidious on the clustering in place (fast_graft.inc): the per-swarm sums, the role byte of every amplicon, and the
   // grafting's slots, winner lists and result arrays
   swa_dbuf d_swarm_sums, d_swarm_role, d_graft_work;
+  // the shard owner of every amplicon (fast_graft.inc): owner u8[n + 4, rounded up to 8] | tile bases u64[tiles + 1] | tile counts u32[tiles];
+  // on the other ranks of a swa_multi the owner bytes alone, as rank 0 sent them
+  swa_dbuf d_shard_owner;
   // d >= 2 on the clustering in place (dn_tables.inc): jumping buffers, positions, sort keys, the four link arrays
   swa_dbuf d_dn_tables;
   uint64_t dn_tables_made = 0;                 // swa_dn_tables_device calls of this context that left tables
@@ -409,6 +415,16 @@ int swa_d1_rebuild_table(swa_ctx * ctx, const uint8_t * d_is_member);
 int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking);
 int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const uint32_t * svals, uint64_t nedges, uint64_t * offsets,
                       uint32_t * neighbours, uint8_t * diffs, uint64_t cap, uint64_t * total);
+// ... or left in HBM as the resident network (the tail of swa_dn_graph_resident: offsets, neighbours | diffs, csr_has_diffs)
+int swa_dn_graph_install(swa_ctx * ctx, const unsigned long long * sorted, const uint32_t * svals, uint64_t nedges);
+// cluster_gpu.hip (fast_graft.inc), for fastidious.hip: role[a] = 0 where owner[a] is 255 (light), 1 where it is `shard`, else 2;
+// both arrays in HBM, n bytes (the owners reserved with four more)
+int swa_d1_roles_from_owners(swa_ctx * ctx, const uint8_t * d_owner, uint32_t shard, uint8_t * d_role);
+// fastidious.hip, for multi.hip: the pass of swa_d1_fastidious_shard with its roles made on the device from owner bytes in this
+// context's HBM (n_light / n_heavy: the light amplicons and this shard's heavy ones); the candidates are left in d_graft and come
+// home only when graft_cand is not null
+int swa_d1_fastidious_owned(swa_ctx * ctx, const uint8_t * d_owner, uint32_t shard, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
+                            uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
 
 // RAII-less timing brackets: swa_t0(ctx, slot) ... swa_t1(ctx, slot).  The slots: swa_timing_read reports [0, 8),
 // swa_timing_read_stream [8, 16), both by position (include/swarm_amd.h)

@@ -17,12 +17,15 @@ DEV=$(seq -s, 0 $((G-1)))
 echo "== one GPU"
 SWARM_AMD_TIMING=1 "$R/swarm_amd/bin/swarm" -d 1 -o "$OUT/one.o" -j "$OUT/one.j" -l "$OUT/one.log" "$FA" 2> "$OUT/one.err" || { cat "$OUT/one.err"; exit 1; }
 grep -E '^\[t' "$OUT/one.err"
+# (SWARM_AMD_MULTI_CLUSTER: the routed build with the clustering on rank 0's GPU, the streamed one with it on the host)
 for build in records streamed; do
-  echo "== $G GPUs ($DEV), index build $build"
-  SWARM_AMD_MULTI_BUILD=$build SWARM_AMD_MULTI_REPORT=1 SWARM_AMD_TIMING=1 SWARM_AMD_DEVICES=$DEV "$R/swarm_amd/bin/swarm" -d 1 \
+  if [ $build = records ]; then cluster=device; where="rank 0's GPU"; else cluster=host; where="the host"; fi
+  echo "== $G GPUs ($DEV), index build $build, clustering on $where"
+  SWARM_AMD_MULTI_CLUSTER=$cluster SWARM_AMD_MULTI_BUILD=$build SWARM_AMD_MULTI_REPORT=1 SWARM_AMD_TIMING=1 SWARM_AMD_DEVICES=$DEV "$R/swarm_amd/bin/swarm" -d 1 \
       -o "$OUT/$build.o" -j "$OUT/$build.j" -l "$OUT/$build.log" "$FA" 2> "$OUT/$build.err" || { cat "$OUT/$build.err"; exit 1; }
   grep -E '^\[t|^multi:' "$OUT/$build.err"
   grep -q "exchange = rccl" "$OUT/$build.err" || { echo "FAIL: the $G-GPU run did not use RCCL"; exit 1; }
+  grep -q "^multi: clustering on $where\$" "$OUT/$build.err" || { echo "FAIL: the $G-GPU run did not cluster on $where"; exit 1; }
   cmp "$OUT/one.o" "$OUT/$build.o" || { echo "FAIL: -o differs ($build)"; exit 1; }
   cmp "$OUT/one.j" "$OUT/$build.j" || { echo "FAIL: -j differs ($build)"; exit 1; }
 done
