@@ -15,6 +15,7 @@
 //   rocPRIM           seeds -> swarm numbers (exclusive scan); members ordered by one stable radix sort of
 //                     (swarm << gbits | generation) over the bits that vary (23 of them at 10 M amplicons, 32-bit keys), the ids
 //                     ascending as payload; k_swarm_bounds reads the swarms' first members off the sorted keys
+// All of it works in d_cluster: swa_cluster_arrays (swa_internal.h), for fast_graft.inc, dn_tables.inc and dn_graph.hip alike.
 // Round 6: 17.4 -> ~5 ms at 10 M for the device part + download (profiles/r06/NOTES.md).
 //
 // swa_d1_network_adopt installs a caller's own CSR as the resident network (validated on the host before anything is
@@ -123,13 +124,6 @@ __global__ __launch_bounds__(256) void k_swarm_bounds(const K * __restrict__ sor
 
 struct widen_u8 { __host__ __device__ uint32_t operator()(uint8_t v) const { return (uint32_t)v; } };
 
-int blocks_for(const swa_ctx * ctx, uint64_t items) {
-  const uint64_t b = (items + 255) / 256, cap = (uint64_t)ctx->num_cus * 8;
-  return (int)std::max<uint64_t>(1, std::min(b, cap));
-}
-
-uint32_t bit_width_u32(uint32_t v) { uint32_t b = 0; while (v != 0u) { ++b; v >>= 1; } return b; }
-
 }  // namespace
 
 // loads this translation unit's code object (see swa_ctx_warmup): an empty launch
@@ -213,14 +207,8 @@ extern "C" int swa_d1_network_fetch(swa_ctx * ctx, uint64_t * offsets, uint32_t 
   if (!ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_fetch: no resident network"); }
   if (ctx->res.csr_total > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_network_fetch: neighbour buffer too small"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  swa_touch_pages(offsets, ((uint64_t)ctx->db.n + 1) * sizeof(uint64_t));
-  swa_touch_pages(neighbours, ctx->res.csr_total * sizeof(uint32_t));
-  SWA_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_offsets_tmp.ptr, ((uint64_t)ctx->db.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (ctx->res.csr_total != 0) {
-    SWA_HIP(ctx, hipMemcpyAsync(neighbours, ctx->d_nb_tmp.ptr, ctx->res.csr_total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  return swa_download(ctx, {{offsets, ctx->d_offsets_tmp.ptr, ((uint64_t)ctx->db.n + 1) * sizeof(uint64_t)},
+                            {neighbours, ctx->d_nb_tmp.ptr, ctx->res.csr_total * sizeof(uint32_t)}});
 }
 
 // ... and the byte of differences of every link of a resident d >= 2 graph, in the neighbours' order
@@ -258,20 +246,14 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   const uint32_t n = ctx->db.n;
   const auto * offsets = static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr);
   const auto * nb = static_cast<const uint32_t *>(ctx->d_nb_tmp.ptr);
-  // label | gen | parent | swarmid | ids_in | ids_out | seed_rank | begins (n + 2) | stamp, then keys in / out (u64 room), seed flags
-  SWA_TRY(swa_reserve(ctx, ctx->d_cluster, (uint64_t)n * 4 * 10 + 64 + (uint64_t)n * 8 * 2 + n + 64));
-  auto * label = static_cast<uint32_t *>(ctx->d_cluster.ptr);
-  auto * gen = label + n, * par = gen + n, * sid = par + n, * ids_in = sid + n, * ids_out = ids_in + n, * seed_rank = ids_out + n;
-  auto * begins = seed_rank + n, * stamp = begins + n + 4;
-  auto * keys_in = reinterpret_cast<unsigned long long *>(stamp + n + (n & 1u));      // (8-byte aligned: 9 n + 4 words before it, one more when n is odd)
-  auto * keys_out = keys_in + n;
-  auto * is_seed = reinterpret_cast<uint8_t *>(keys_out + n);
+  swa_cluster_arrays cl;
+  SWA_TRY(swa_carve(ctx, ctx->d_cluster, n, true, cl));
   // control words: [0, kSweepFlags) sweep flags, then kLevelBatch "this generation took somebody in" flags
   SWA_TRY(swa_reserve(ctx, ctx->d_cluster_ctl, (kSweepFlags + kLevelBatch) * sizeof(uint32_t)));
   auto * flags = static_cast<uint32_t *>(ctx->d_cluster_ctl.ptr);
   auto * cnt = flags + kSweepFlags;
   uint32_t host_ctl[kLevelBatch];
-  const dim3 g(blocks_for(ctx, n)), b(256);
+  const dim3 g(swa_grid256(ctx, n)), b(256);
   // SWARM_AMD_CLUSTER_TIMING: wall clock between the host's synchronisation points
   static const bool timing = getenv("SWARM_AMD_CLUSTER_TIMING") != nullptr;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -283,48 +265,46 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
     t_last = t;
   };
   lap("buffers", 0);
-  hipLaunchKernelGGL(k_label_init, g, b, 0, ctx->stream, label, par, stamp, gen, n);
+  hipLaunchKernelGGL(k_label_init, g, b, 0, ctx->stream, cl.label, cl.parent, cl.stamp, cl.gen, n);
   // ---- swarms: the smallest id that reaches every vertex
   for (uint32_t s = 1;;) {
     if (s == 1u) { SWA_HIP(ctx, hipMemsetAsync(flags, 0, kSweepFlags * sizeof(uint32_t), ctx->stream)); }
     const uint32_t last = std::min(s + kSweepBatch, kSweepFlags) - 1u;
     ctx->res.cluster_effort[0] += last + 1u - s;
-    for (; s <= last; ++s) { hipLaunchKernelGGL(k_label_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, stamp, s, flags); }
+    for (; s <= last; ++s) { hipLaunchKernelGGL(k_label_sweep, g, b, 0, ctx->stream, offsets, nb, n, cl.label, cl.stamp, s, flags); }
     uint32_t changed = 0;
     SWA_HIP(ctx, hipMemcpyAsync(&changed, flags + last, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     lap("label sweeps, batch", s - 1u);
     if (changed == 0) { break; }                       // (the batch's last sweep changed nothing — or was behind one that did not)
     if (s == kSweepFlags) {                            // (a graph that needs a thousand sweeps: start the numbering again, everybody active)
-      SWA_HIP(ctx, hipMemsetAsync(stamp, 0, (uint64_t)n * sizeof(uint32_t), ctx->stream));
+      SWA_HIP(ctx, hipMemsetAsync(cl.stamp, 0, (uint64_t)n * sizeof(uint32_t), ctx->stream));
       s = 1;
       ++ctx->res.cluster_effort[1];
     }
   }
   // ---- swarm numbers = rank of the seed among the seeds (queued behind the first frontiers; read with them)
-  size_t tmp_bytes = 0, need = 0;
-  auto seeds32 = rocprim::make_transform_iterator(is_seed, widen_u8());
-  (void)rocprim::exclusive_scan(nullptr, need, seeds32, seed_rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
-  (void)rocprim::radix_sort_pairs(nullptr, need, keys_in, keys_out, ids_in, ids_out, (size_t)n, 0, 64, ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
-  (void)rocprim::radix_sort_pairs(nullptr, need, reinterpret_cast<uint32_t *>(keys_in), reinterpret_cast<uint32_t *>(keys_out), ids_in, ids_out, (size_t)n, 0, 32, ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
+  size_t asked[3] = {}, need = 0;
+  auto seeds32 = rocprim::make_transform_iterator(cl.is_seed, widen_u8());
+  (void)rocprim::exclusive_scan(nullptr, asked[0], seeds32, cl.seed_rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
+  (void)rocprim::radix_sort_pairs(nullptr, asked[1], cl.keys_in, cl.keys_out, cl.ids_in, cl.order, (size_t)n, 0, 64, ctx->stream);
+  (void)rocprim::radix_sort_pairs(nullptr, asked[2], reinterpret_cast<uint32_t *>(cl.keys_in), reinterpret_cast<uint32_t *>(cl.keys_out), cl.ids_in, cl.order, (size_t)n, 0, 32, ctx->stream);
+  const size_t tmp_bytes = *std::max_element(asked, asked + 3);
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, tmp_bytes + 16));
   // ---- generations and parents, and — queued with them — the swarm numbers = rank of the seed among the seeds
   auto * any = cnt;
-  hipLaunchKernelGGL(k_level_init, g, b, 0, ctx->stream, label, gen, is_seed, n);
+  hipLaunchKernelGGL(k_level_init, g, b, 0, ctx->stream, cl.label, cl.gen, cl.is_seed, n);
   need = tmp_bytes;
-  SWA_HIP(ctx, rocprim::exclusive_scan(ctx->d_scan_hits.ptr, need, seeds32, seed_rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
+  SWA_HIP(ctx, rocprim::exclusive_scan(ctx->d_scan_hits.ptr, need, seeds32, cl.seed_rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
   uint32_t last_rank = 0, maxgen = 0;
   uint8_t last_seed = 0;
-  SWA_HIP(ctx, hipMemcpyAsync(&last_rank, seed_rank + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipMemcpyAsync(&last_seed, is_seed + (n - 1), 1, hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(&last_rank, cl.seed_rank + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(&last_seed, cl.is_seed + (n - 1), 1, hipMemcpyDeviceToHost, ctx->stream));
   for (uint32_t level0 = 1;; level0 += kLevelBatch) {   // (level0 = the generation the batch's first sweep hands out)
     SWA_HIP(ctx, hipMemsetAsync(any, 0, kLevelBatch * sizeof(uint32_t), ctx->stream));
     ++ctx->res.cluster_effort[2];
     for (uint32_t r = 0; r < kLevelBatch; ++r) {
-      hipLaunchKernelGGL(k_level_sweep, g, b, 0, ctx->stream, offsets, nb, n, label, gen, par, level0 + r, any, r);
+      hipLaunchKernelGGL(k_level_sweep, g, b, 0, ctx->stream, offsets, nb, n, cl.label, cl.gen, cl.parent, level0 + r, any, r);
     }
     SWA_HIP(ctx, hipMemcpyAsync(host_ctl, any, kLevelBatch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -337,33 +317,31 @@ extern "C" int swa_d1_cluster_device(swa_ctx * ctx, uint32_t * swarmid, uint32_t
   ctx->res.cluster_nswarms = *nswarms;
   if (*nswarms > swarm_cap || swarm_begin == nullptr) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_cluster_device: swarm table too small"); }
   // ---- members by (swarm, generation, id): one stable radix sort over the bits that vary, ids ascending going in
-  const uint32_t gbits = bit_width_u32(maxgen), sbits = bit_width_u32(*nswarms - 1u);
+  const uint32_t gbits = swa_bit_width(maxgen), sbits = swa_bit_width(*nswarms - 1u);
   const bool narrow = gbits + sbits <= 32u;
   need = tmp_bytes;
   if (narrow) {
-    auto * k_in = reinterpret_cast<uint32_t *>(keys_in), * k_out = reinterpret_cast<uint32_t *>(keys_out);
-    hipLaunchKernelGGL(k_swarm_keys<uint32_t>, g, b, 0, ctx->stream, label, gen, seed_rank, n, gbits, sid, k_in, ids_in);
-    SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, k_in, k_out, ids_in, ids_out, (size_t)n, 0, std::max(1u, gbits + sbits), ctx->stream));
-    hipLaunchKernelGGL(k_swarm_bounds<uint32_t>, g, b, 0, ctx->stream, k_out, n, gbits, *nswarms, begins);
+    auto * k_in = reinterpret_cast<uint32_t *>(cl.keys_in), * k_out = reinterpret_cast<uint32_t *>(cl.keys_out);
+    hipLaunchKernelGGL(k_swarm_keys<uint32_t>, g, b, 0, ctx->stream, cl.label, cl.gen, cl.seed_rank, n, gbits, cl.swarmid, k_in, cl.ids_in);
+    SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, k_in, k_out, cl.ids_in, cl.order, (size_t)n, 0, std::max(1u, gbits + sbits), ctx->stream));
+    hipLaunchKernelGGL(k_swarm_bounds<uint32_t>, g, b, 0, ctx->stream, k_out, n, gbits, *nswarms, cl.begins);
   } else {
-    hipLaunchKernelGGL(k_swarm_keys<unsigned long long>, g, b, 0, ctx->stream, label, gen, seed_rank, n, gbits, sid, keys_in, ids_in);
-    SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, keys_in, keys_out, ids_in, ids_out, (size_t)n, 0, gbits + sbits, ctx->stream));
-    hipLaunchKernelGGL(k_swarm_bounds<unsigned long long>, g, b, 0, ctx->stream, keys_out, n, gbits, *nswarms, begins);
+    hipLaunchKernelGGL(k_swarm_keys<unsigned long long>, g, b, 0, ctx->stream, cl.label, cl.gen, cl.seed_rank, n, gbits, cl.swarmid, cl.keys_in, cl.ids_in);
+    SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, cl.keys_in, cl.keys_out, cl.ids_in, cl.order, (size_t)n, 0, gbits + sbits, ctx->stream));
+    hipLaunchKernelGGL(k_swarm_bounds<unsigned long long>, g, b, 0, ctx->stream, cl.keys_out, n, gbits, *nswarms, cl.begins);
   }
-  // the host pages are faulted in BEFORE any copy into them is queued (swa_touch_pages writes a zero byte a page: after a
-  // queued copy it would race with it — and clear bytes the copy had already landed)
-  for (uint32_t * out : {swarmid, generation, parent, order}) { swa_touch_pages(out, (uint64_t)n * sizeof(uint32_t)); }   // (pinned pages: nothing to do)
-  if (swarmid != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(swarmid, sid, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (generation != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(generation, gen, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (parent != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(parent, par, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
+  // (the pages of `order` too before any copy is queued: the rule of swa_download; pinned pages: nothing to do)
+  const uint64_t nbytes = (uint64_t)n * sizeof(uint32_t);
+  swa_touch_pages(order, nbytes);
+  SWA_TRY(swa_download(ctx, {{swarmid, cl.swarmid, nbytes}, {generation, cl.gen, nbytes}, {parent, cl.parent, nbytes}}, false));
   SWA_HIP(ctx, hipGetLastError());
   if (timing) { SWA_HIP(ctx, hipStreamSynchronize(ctx->stream)); lap("keys, sort, bounds", gbits + sbits); }
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (timing) { for (auto & e : ev) { (void)hipEventCreate(&e); } (void)hipEventRecord(ev[0], ctx->stream); }
-  SWA_HIP(ctx, hipMemcpyAsync(order, ids_out, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(order, cl.order, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   lap("  order copy queued", 0);
   if (timing) { (void)hipEventRecord(ev[1], ctx->stream); }
-  SWA_HIP(ctx, hipMemcpyAsync(swarm_begin, begins, ((uint64_t)*nswarms + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(swarm_begin, cl.begins, ((uint64_t)*nswarms + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   lap("  bounds copy queued", 0);
   if (timing) { (void)hipEventRecord(ev[2], ctx->stream); }
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -386,14 +364,10 @@ extern "C" int swa_d1_cluster_fetch(swa_ctx * ctx, uint32_t * swarmid, uint32_t 
   if (!ctx->res.cluster_ready || !ctx->res.csr_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_cluster_fetch: no clustering in place (swa_d1_cluster_device)"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
-  const auto * label = static_cast<const uint32_t *>(ctx->d_cluster.ptr);
-  const uint32_t * gen = label + n, * par = gen + n, * sid = par + n;
-  for (uint32_t * out : {swarmid, generation, parent}) { swa_touch_pages(out, (uint64_t)n * sizeof(uint32_t)); }
-  if (swarmid != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(swarmid, sid, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (generation != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(generation, gen, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (parent != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(parent, par, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  swa_cluster_arrays cl;
+  SWA_TRY(swa_carve(ctx, ctx->d_cluster, n, false, cl));
+  const uint64_t nbytes = (uint64_t)n * sizeof(uint32_t);
+  return swa_download(ctx, {{swarmid, cl.swarmid, nbytes}, {generation, cl.gen, nbytes}, {parent, cl.parent, nbytes}});
 }
 
 // what the last swa_d1_cluster_device call of this context cost: label sweeps launched, restarts of their numbering, level

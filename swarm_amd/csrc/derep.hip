@@ -138,9 +138,7 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
   if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: no database"); }
   if (first_identical == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: bad argument"); }
   SWA_TRY(swa_derep_resident(ctx));
-  SWA_HIP(ctx, hipMemcpyAsync(first_identical, ctx->d_graft.ptr, uint64_t(ctx->db.n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  return swa_download(ctx, {{first_identical, ctx->d_graft.ptr, uint64_t(ctx->db.n) * sizeof(uint32_t)}});
 }
 
 // ---- the clusters, their sums and their order, from the resident array (src/derep.cc:276-354, 67-90) --------------------
@@ -152,10 +150,9 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
 //                     seed order) and counts them
 //   k_d0_keys         (cluster number of first[i], i); one stable radix sort over the bits the cluster count needs groups
 //                     the members, ascending db index inside every cluster: the layout of swa_d0_result::members
-//   k_d0_sums         one position per lane over the grouped order: the cluster number never falls along it, so a wave sums
-//                     its runs of equal numbers with a segmented scan and the last lane of a run writes — a plain store
-//                     when the run is the whole cluster, one atomic per (wave, cluster) otherwise (a sequence with 10^6
-//                     copies: 15 625 atomics on its words); the first position of a cluster writes its seed and begin
+//   k_d0_sums         one position per lane over the grouped order: the cluster number never falls along it, so mass, size
+//                     and singletons come from the run reduction of swa_internal.h (swa_wave_run_reduce; a sequence with
+//                     10^6 copies: 15 625 atomics on its words); the first position of a cluster writes its seed and begin
 //   k_d0_maxima       largest size and heaviest mass, a wave's maximum per atomic
 //   k_d0_order_keys   heaviest - mass: one stable radix sort of the cluster numbers over the bits the heaviest mass needs
 //                     leaves them by mass descending, ties in seed order as they went in
@@ -163,30 +160,25 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
 // Nothing depends on scheduling: sums, maxima and stable sorts of integers.
 namespace {
 
-// d_d0: five arrays of n words — rank (cluster number of a seed) | keys in | keys out | ids in | members
-struct D0Work { uint32_t * rank, * keys_in, * keys_out, * ids_in, * members; };
-D0Work d0_work(const swa_ctx * ctx) {
-  const uint64_t n = ctx->db.n;
-  auto * rank = static_cast<uint32_t *>(ctx->d_d0.ptr);
-  return D0Work{rank, rank + n, rank + 2 * n, rank + 3 * n, rank + 4 * n};
-}
+// d_d0, n amplicons: rank (cluster number of a seed), the grouping sort's keys and ids, the members in grouped order
+struct D0Work {
+  uint32_t * rank, * keys_in, * keys_out, * ids_in, * members;  void lay(swa_carver & c, uint64_t n) { c.take(n, rank, keys_in, keys_out, ids_in, members); }
+};
 
-// d_d0_tab, c = clusters: maxima (heaviest u64, largest u64) | mass u64[c] seed order | order keys in, out u64[c] | mass u64[c]
-// output order | then u32[c] each: seed, size, singletons, begin in seed order | numbers in, out | seed, size, singletons,
-// begin in output order
+// d_d0_tab, c clusters: maxima (heaviest, largest); the tables in seed order (*_s), the order sort's keys and cluster numbers, the tables
+// in output order.  k_d0_sums and k_d0_maxima add into what two fills clear: maxima with mass_s (`cleared64`), size_s with singles_s (`cleared32`)
 struct D0Tables {
   unsigned long long * maxima, * mass_s, * okeys_in, * okeys_out, * mass;
   uint32_t * seed_s, * size_s, * singles_s, * begin_s, * num_in, * num_out, * seed, * size, * singles, * begin;
+  swa_extent cleared64, cleared32;
+  void lay(swa_carver & at, uint64_t c) {
+    at.take(2, maxima); at.take(c, mass_s);
+    cleared64 = at.extent(maxima);
+    at.take(c, okeys_in, okeys_out, mass, seed_s, size_s, singles_s);
+    cleared32 = at.extent(size_s);
+    at.take(c, begin_s, num_in, num_out, seed, size, singles, begin);
+  }
 };
-constexpr uint64_t d0_tables_bytes(uint64_t c) { return 16 + 4 * c * 8 + 10 * c * 4; }
-D0Tables d0_tables(const swa_ctx * ctx, uint64_t c) {
-  auto * maxima = static_cast<unsigned long long *>(ctx->d_d0_tab.ptr);
-  auto * mass_s = maxima + 2;
-  auto * seed_s = reinterpret_cast<uint32_t *>(mass_s + 4 * c);
-  return D0Tables{maxima, mass_s, mass_s + c, mass_s + 2 * c, mass_s + 3 * c,
-                  seed_s, seed_s + c, seed_s + 2 * c, seed_s + 3 * c, seed_s + 4 * c, seed_s + 5 * c,
-                  seed_s + 6 * c, seed_s + 7 * c, seed_s + 8 * c, seed_s + 9 * c};
-}
 
 __global__ __launch_bounds__(256) void k_d0_seed_flags(const uint32_t * __restrict__ first, uint32_t n, uint32_t * __restrict__ flag) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -202,43 +194,34 @@ __global__ __launch_bounds__(256) void k_d0_keys(const uint32_t * __restrict__ f
   }
 }
 
-// The lanes of a wave hold keys that never fall from lane to lane: every run of equal keys is summed into its LAST lane
-// (the segmented inclusive scan of fast_graft.inc's wave_run_reduce, with the three sums d = 0 needs).  Every lane takes part.
-__device__ __forceinline__ void d0_run_reduce(uint32_t key, unsigned long long & mass, uint32_t & singles, uint32_t & count) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) {
-    const uint32_t key2 = __shfl_up(key, d, 64);
-    const unsigned long long mass2 = swa_shfl_up_u64(mass, d);
-    const uint32_t singles2 = __shfl_up(singles, d, 64), count2 = __shfl_up(count, d, 64);
-    if (lane >= d && key2 == key) { mass += mass2; singles += singles2; count += count2; }
-  }
-}
+// mass and singletons of a run of one cluster (swa_wave_run_reduce, swa_internal.h; the run's length is its size)
+struct D0Run {
+  unsigned long long mass; uint32_t singles;
+  __device__ __forceinline__ D0Run shfl_up(uint32_t d) const { return D0Run{swa_shfl_up_u64(mass, d), __shfl_up(singles, d, 64)}; }
+  __device__ __forceinline__ void absorb(const D0Run & o) { mass += o.mass; singles += o.singles; }
+};
 
 // cluster[k] = the cluster number of position k of the grouped order (never falls along k), members[k] the amplicon there.
 // mass / size / singles were cleared before the launch.
 __global__ __launch_bounds__(256) void k_d0_sums(const uint32_t * __restrict__ cluster, const uint32_t * __restrict__ members,
                                                  const uint64_t * __restrict__ abundance, uint32_t n, unsigned long long * mass,
                                                  uint32_t * size, uint32_t * singles, uint32_t * __restrict__ seed, uint32_t * __restrict__ begin) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t span = ((uint64_t)n + 63u) & ~uint64_t(63);          // whole waves take part
-  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < span; k += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t c = SWA_NO_AMPLICON, single = 0, count = 0;              // (beyond the order: a run of its own that writes nothing)
-    unsigned long long m = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < swa_wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t c = SWA_NO_AMPLICON;                                     // (beyond the order: a run of its own that writes nothing)
+    D0Run r{0, 0};
     if (k < n) {
       c = cluster[k];
       const uint32_t a = members[k];
-      m = abundance[a]; single = m == 1ull ? 1u : 0u; count = 1;
+      r.mass = abundance[a]; r.singles = r.mass == 1ull ? 1u : 0u;
       if (k == 0 || cluster[k - 1] != c) { seed[c] = a; begin[c] = (uint32_t)k; }   // the cluster's first position: its seed
     }
-    d0_run_reduce(c, m, single, count);
-    const uint32_t next = __shfl_down(c, 1, 64);
-    if (k >= n || (lane != 63u && next == c)) { continue; }           // (not the last lane of its run)
-    // the run [k + 1 - count, k]: the whole cluster when nothing of it lies in front of or behind it — nobody else writes its sums
-    const uint64_t start = k + 1 - count;
+    const swa_run run = swa_wave_run_reduce(c, r);
+    if (k >= n || !run.last) { continue; }
+    // the run [k + 1 - length, k]: the whole cluster when nothing of it lies in front of or behind it — nobody else writes its sums
+    const uint64_t start = k + 1 - run.length;
     const bool whole = (start == 0 || cluster[start - 1] != c) && (k + 1 == n || cluster[k + 1] != c);
-    if (whole) { mass[c] = m; size[c] = count; singles[c] = single; }
-    else { atomicAdd(&mass[c], m); atomicAdd(&size[c], count); atomicAdd(&singles[c], single); }
+    if (whole) { mass[c] = r.mass; size[c] = run.length; singles[c] = r.singles; }
+    else { atomicAdd(&mass[c], r.mass); atomicAdd(&size[c], run.length); atomicAdd(&singles[c], r.singles); }
   }
 }
 
@@ -274,8 +257,6 @@ __global__ __launch_bounds__(256) void k_d0_gather(D0Tables t, uint32_t clusters
   }
 }
 
-uint32_t d0_bit_width(uint64_t v) { uint32_t b = 0; while (v != 0u) { ++b; v >>= 1; } return b; }
-
 }  // namespace
 
 extern "C" int swa_d0_cluster_device(swa_ctx * ctx, uint64_t * summary3) {
@@ -285,18 +266,16 @@ extern "C" int swa_d0_cluster_device(swa_ctx * ctx, uint64_t * summary3) {
   ctx->dr.tables_ready = false;
   const uint32_t n = ctx->db.n;
   const auto * first = static_cast<const uint32_t *>(ctx->d_graft.ptr);
-  SWA_TRY(swa_reserve(ctx, ctx->d_d0, (uint64_t)n * 5 * sizeof(uint32_t)));
-  const D0Work w = d0_work(ctx);
-  const dim3 g((unsigned)swa_grid_for(ctx, n, 256, 8)), b(256);
+  D0Work w;
+  SWA_TRY(swa_carve(ctx, ctx->d_d0, n, true, w));
+  const dim3 g((unsigned)swa_grid256(ctx, n)), b(256);
   // rocPRIM's scratch: the most any of the three calls asks for at n items (the clusters are never more)
-  size_t tmp_bytes = 0, need = 0;
+  size_t asked[3] = {}, need = 0;
   auto * k64 = static_cast<unsigned long long *>(nullptr);
-  (void)rocprim::exclusive_scan(nullptr, need, w.keys_in, w.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
-  (void)rocprim::radix_sort_pairs(nullptr, need, w.keys_in, w.keys_out, w.ids_in, w.members, (size_t)n, 0, 32, ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
-  (void)rocprim::radix_sort_pairs(nullptr, need, k64, k64, w.ids_in, w.members, (size_t)n, 0, 64, ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
+  (void)rocprim::exclusive_scan(nullptr, asked[0], w.keys_in, w.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
+  (void)rocprim::radix_sort_pairs(nullptr, asked[1], w.keys_in, w.keys_out, w.ids_in, w.members, (size_t)n, 0, 32, ctx->stream);
+  (void)rocprim::radix_sort_pairs(nullptr, asked[2], k64, k64, w.ids_in, w.members, (size_t)n, 0, 64, ctx->stream);
+  const size_t tmp_bytes = *std::max_element(asked, asked + 3);
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, tmp_bytes + 16));
   // ---- cluster numbers in seed order, and how many
   hipLaunchKernelGGL(k_d0_seed_flags, g, b, 0, ctx->stream, first, n, w.keys_in);
@@ -313,13 +292,13 @@ extern "C" int swa_d0_cluster_device(swa_ctx * ctx, uint64_t * summary3) {
   // ---- members grouped by cluster, db order inside (zero key bits — one cluster — sort on one bit that is 0 everywhere)
   need = tmp_bytes;
   SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, w.keys_in, w.keys_out, w.ids_in, w.members, (size_t)n, 0,
-                                         std::max(1u, d0_bit_width(clusters - 1u)), ctx->stream));
+                                         std::max(1u, swa_bit_width(clusters - 1u)), ctx->stream));
   // ---- sums over the runs, seeds, begins; the maxima
-  SWA_TRY(swa_reserve(ctx, ctx->d_d0_tab, d0_tables_bytes(clusters)));
-  const D0Tables t = d0_tables(ctx, clusters);
-  const dim3 gc((unsigned)swa_grid_for(ctx, clusters, 256, 8));
-  SWA_HIP(ctx, hipMemsetAsync(t.maxima, 0, 16 + (uint64_t)clusters * 8, ctx->stream));                       // maxima, mass_s
-  SWA_HIP(ctx, hipMemsetAsync(t.size_s, 0, (uint64_t)clusters * 2 * sizeof(uint32_t), ctx->stream));          // size_s, singles_s
+  D0Tables t;
+  SWA_TRY(swa_carve(ctx, ctx->d_d0_tab, clusters, true, t));
+  const dim3 gc((unsigned)swa_grid256(ctx, clusters));
+  SWA_HIP(ctx, hipMemsetAsync(t.cleared64.ptr, 0, t.cleared64.bytes, ctx->stream));
+  SWA_HIP(ctx, hipMemsetAsync(t.cleared32.ptr, 0, t.cleared32.bytes, ctx->stream));
   hipLaunchKernelGGL(k_d0_sums, g, b, 0, ctx->stream, w.keys_out, w.members, ctx->db.abundance, n, t.mass_s, t.size_s, t.singles_s, t.seed_s, t.begin_s);
   hipLaunchKernelGGL(k_d0_maxima, gc, b, 0, ctx->stream, t.mass_s, t.size_s, clusters, t.maxima);
   SWA_HIP(ctx, hipGetLastError());
@@ -330,7 +309,7 @@ extern "C" int swa_d0_cluster_device(swa_ctx * ctx, uint64_t * summary3) {
   hipLaunchKernelGGL(k_d0_order_keys, gc, b, 0, ctx->stream, t.mass_s, maxima[0], clusters, t.okeys_in, t.num_in);
   need = tmp_bytes;
   SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, t.okeys_in, t.okeys_out, t.num_in, t.num_out, (size_t)clusters, 0,
-                                         std::max(1u, d0_bit_width(maxima[0])), ctx->stream));
+                                         std::max(1u, swa_bit_width(maxima[0])), ctx->stream));
   hipLaunchKernelGGL(k_d0_gather, gc, b, 0, ctx->stream, t, clusters);
   SWA_HIP(ctx, hipGetLastError());
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -351,18 +330,11 @@ extern "C" int swa_d0_cluster_fetch(swa_ctx * ctx, uint32_t * seed, uint64_t * m
   const bool wants_tables = seed != nullptr || mass != nullptr || size != nullptr || singletons != nullptr || begin != nullptr;
   if (wants_tables && cluster_cap < c) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d0_cluster_fetch: cluster arrays too small"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  const D0Tables t = d0_tables(ctx, c);
-  // the host pages are faulted in BEFORE any copy into them is queued (see swa_d1_cluster_device)
-  swa_touch_pages(members, (uint64_t)n * sizeof(uint32_t));
-  swa_touch_pages(mass, (uint64_t)c * sizeof(uint64_t));
-  for (uint32_t * out : {seed, size, singletons, begin}) { swa_touch_pages(out, (uint64_t)c * sizeof(uint32_t)); }
-  if (members != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(members, d0_work(ctx).members, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (mass != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(mass, t.mass, (uint64_t)c * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  const uint32_t * from[4] = {t.seed, t.size, t.singles, t.begin};
-  uint32_t * to[4] = {seed, size, singletons, begin};
-  for (int k = 0; k < 4; ++k) {
-    if (to[k] != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(to[k], from[k], (uint64_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  D0Work w;
+  SWA_TRY(swa_carve(ctx, ctx->d_d0, n, false, w));
+  D0Tables t;
+  SWA_TRY(swa_carve(ctx, ctx->d_d0_tab, c, false, t));
+  const uint64_t c4 = (uint64_t)c * sizeof(uint32_t);
+  return swa_download(ctx, {{members, w.members, (uint64_t)n * sizeof(uint32_t)}, {mass, t.mass, (uint64_t)c * sizeof(uint64_t)},
+                            {seed, t.seed, c4}, {size, t.size, c4}, {singletons, t.singles, c4}, {begin, t.begin, c4}});
 }

@@ -741,12 +741,8 @@ __global__ __launch_bounds__(256) void k_dg_parent_diffs(const uint64_t * __rest
     const uint32_t p = parent[v];
     uint8_t d = 0;
     if (p != SWA_NO_AMPLICON) {
-      uint64_t lo = offsets[p], hi = offsets[p + 1];
-      while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (nb[mid] < v) { lo = mid + 1; } else { hi = mid; }
-      }
-      d = (lo < offsets[p + 1] && nb[lo] == v) ? df[lo] : (uint8_t)0xFF;
+      uint64_t at;
+      d = swa_row_find(offsets, nb, p, v, at) ? df[at] : (uint8_t)0xFF;
     }
     out[v] = d;
   }
@@ -799,7 +795,7 @@ int window_length(swa_ctx * ctx, uint32_t d, dn_plan * out) {
     auto * slot = static_cast<uint32_t *>(ctx->d_frole.ptr);
     SWA_HIP(ctx, hipMemsetAsync(slot, 0, SWA_DN_HIST_LEN * sizeof(uint32_t), ctx->stream));
     SWA_HIP(ctx, hipMemsetAsync(slot + SWA_DN_HIST_LEN, 0xFF, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_dg_lengths, dim3(join_grid(ctx, ctx->db.n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, slot);
+    hipLaunchKernelGGL(k_dg_lengths, dim3(swa_grid256(ctx, ctx->db.n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, ctx->db.n, slot);
     uint32_t got[SWA_DN_HIST_LEN + 1];
     SWA_HIP(ctx, hipMemcpyAsync(got, slot, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -893,7 +889,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       for (uint32_t L = 0; L < top; ++L) { start[L + 1] = start[L] + ctx->up.dn_len_hist[L]; }
       SWA_HIP(ctx, hipMemcpyAsync(words + kShortStart, start, (top + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
       SWA_HIP(ctx, hipMemsetAsync(words + kShortCursor, 0, top * sizeof(uint32_t), ctx->stream));
-      hipLaunchKernelGGL(k_dg_short_sort, dim3(join_grid(ctx, n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, n, top, words + kShortStart,
+      hipLaunchKernelGGL(k_dg_short_sort, dim3(swa_grid256(ctx, n)), dim3(256), 0, ctx->stream, ctx->db.seqlen, n, top, words + kShortStart,
                          words + kShortCursor, words + kShortSorted, plan.nnear);
       SWA_HIP(ctx, hipGetLastError());
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (start[] is on this stack)
@@ -969,7 +965,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       auto * wq = static_cast<uint32_t *>(ctx->d_scan_targets.ptr);
       auto * wt = wq + 2 * npairs;
       auto * wd = static_cast<uint32_t *>(ctx->d_scan_diffs.ptr);
-      hipLaunchKernelGGL(k_dg_worklist, dim3(join_grid(ctx, npairs)), dim3(256), 0, ctx->stream,
+      hipLaunchKernelGGL(k_dg_worklist, dim3(swa_grid256(ctx, npairs)), dim3(256), 0, ctx->stream,
                          static_cast<const unsigned long long *>(ctx->d_fpairs.ptr), npairs, ctx->db.abundance, no_cluster_breaking,
                          wq, wt, fc + 2);
       uint64_t extra = 0;
@@ -984,13 +980,13 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
         SWA_TRY(swa_reserve(ctx, ctx->d_dn_vals, 2 * nwork * sizeof(uint32_t)));          // keys: in | out (bytes; the edges' values later)
         auto * packed = static_cast<unsigned long long *>(ctx->d_dn_keys.ptr);
         auto * wkey = static_cast<unsigned char *>(ctx->d_dn_vals.ptr);
-        hipLaunchKernelGGL(k_dg_work_keys, dim3(join_grid(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, nwork,
+        hipLaunchKernelGGL(k_dg_work_keys, dim3(swa_grid256(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, nwork,
                            static_cast<const ulonglong2 *>(ctx->d_qgrams.ptr), ctx->db.seqlen, kAlignLenWeight, wkey, packed);
         size_t order_bytes = 0;
         (void)rocprim::radix_sort_pairs(nullptr, order_bytes, wkey, wkey + nwork, packed, packed + nwork, nwork, 0, 6, ctx->stream);
         SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, order_bytes + 16));
         SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, order_bytes, wkey, wkey + nwork, packed, packed + nwork, nwork, 0, 6, ctx->stream));
-        hipLaunchKernelGGL(k_dg_work_unpack, dim3(join_grid(ctx, nwork)), dim3(256), 0, ctx->stream, packed + nwork, nwork, wq, wt);
+        hipLaunchKernelGGL(k_dg_work_unpack, dim3(swa_grid256(ctx, nwork)), dim3(256), 0, ctx->stream, packed + nwork, nwork, wq, wt);
         launches += 4;
       }
       // (the launcher takes 32-bit counts: in slices)
@@ -1003,7 +999,7 @@ int swa_dn_graph_compute(swa_ctx * ctx, int no_cluster_breaking) {
       SWA_TRY(swa_reserve(ctx, ctx->d_dn_vals, 2 * nwork * sizeof(uint32_t)));
       auto * ekeys = static_cast<unsigned long long *>(ctx->d_dn_keys.ptr);
       auto * evals = static_cast<uint32_t *>(ctx->d_dn_vals.ptr);
-      hipLaunchKernelGGL(k_dg_edges, dim3(join_grid(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, wd, nwork, d, ekeys, evals, fc + 3);
+      hipLaunchKernelGGL(k_dg_edges, dim3(swa_grid256(ctx, nwork)), dim3(256), 0, ctx->stream, wq, wt, wd, nwork, d, ekeys, evals, fc + 3);
       SWA_HIP(ctx, hipMemcpyAsync(&nedges, fc + 3, sizeof(nedges), hipMemcpyDeviceToHost, ctx->stream));
       SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
       if (nedges != 0) {
@@ -1033,7 +1029,7 @@ int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const ui
   *total = nedges;
   ctx->res.csr_ready = false;                                   // (d_offsets_tmp / d_nb_tmp now hold this graph)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
-  hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
+  hipLaunchKernelGGL(k_dg_offsets, dim3(swa_grid256(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
                      static_cast<uint64_t *>(ctx->d_offsets_tmp.ptr));
   SWA_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_offsets_tmp.ptr, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   if (nedges > cap) {
@@ -1044,7 +1040,7 @@ int swa_dn_graph_emit(swa_ctx * ctx, const unsigned long long * sorted, const ui
     SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, nedges * (sizeof(uint32_t) + 1)));
     auto * nb32 = static_cast<uint32_t *>(ctx->d_nb_tmp.ptr);
     auto * df8 = reinterpret_cast<uint8_t *>(nb32 + nedges);
-    hipLaunchKernelGGL(k_dg_split, dim3(join_grid(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32, df8);
+    hipLaunchKernelGGL(k_dg_split, dim3(swa_grid256(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32, df8);
     SWA_HIP(ctx, hipMemcpyAsync(neighbours, nb32, nedges * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SWA_HIP(ctx, hipMemcpyAsync(diffs, df8, nedges, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -1078,11 +1074,11 @@ int swa_dn_graph_install(swa_ctx * ctx, const unsigned long long * sorted, const
   ctx->res.tables = {};                                     // (radii and links of the graph that is replaced here: dn_tables.inc)
   SWA_TRY(swa_reserve(ctx, ctx->d_offsets_tmp, ((uint64_t)n + 1) * sizeof(uint64_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_nb_tmp, (nedges + 1) * (sizeof(uint32_t) + 1)));
-  hipLaunchKernelGGL(k_dg_offsets, dim3(join_grid(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
+  hipLaunchKernelGGL(k_dg_offsets, dim3(swa_grid256(ctx, (uint64_t)n + 1)), dim3(256), 0, ctx->stream, sorted, nedges, n,
                      static_cast<uint64_t *>(ctx->d_offsets_tmp.ptr));
   if (nedges != 0) {
     auto * nb32 = static_cast<uint32_t *>(ctx->d_nb_tmp.ptr);
-    hipLaunchKernelGGL(k_dg_split, dim3(join_grid(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32,
+    hipLaunchKernelGGL(k_dg_split, dim3(swa_grid256(ctx, nedges)), dim3(256), 0, ctx->stream, sorted, svals, nedges, nb32,
                        reinterpret_cast<uint8_t *>(nb32 + nedges));
   }
   SWA_HIP(ctx, hipGetLastError());
@@ -1113,11 +1109,12 @@ extern "C" int swa_dn_parent_diffs(swa_ctx * ctx, uint8_t * pdiff) {
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n;
   const auto * nb32 = static_cast<const uint32_t *>(ctx->d_nb_tmp.ptr);
-  const auto * parent = static_cast<const uint32_t *>(ctx->d_cluster.ptr) + 2ull * n;        // (layout of swa_d1_cluster_device: label | gen | parent)
+  swa_cluster_arrays cl;
+  SWA_TRY(swa_carve(ctx, ctx->d_cluster, n, false, cl));
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_diffs, (uint64_t)n + 16));
   auto * out = static_cast<uint8_t *>(ctx->d_scan_diffs.ptr);
-  hipLaunchKernelGGL(k_dg_parent_diffs, dim3(join_grid(ctx, n)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr),
-                     nb32, reinterpret_cast<const uint8_t *>(nb32 + ctx->res.csr_total), parent, n, out);
+  hipLaunchKernelGGL(k_dg_parent_diffs, dim3(swa_grid256(ctx, n)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr),
+                     nb32, reinterpret_cast<const uint8_t *>(nb32 + ctx->res.csr_total), cl.parent, n, out);
   SWA_HIP(ctx, hipGetLastError());
   SWA_HIP(ctx, hipMemcpyAsync(pdiff, out, n, hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));

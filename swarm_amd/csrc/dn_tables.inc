@@ -6,16 +6,15 @@
 // swarm, member order, bounds), the differences behind the resident graph's links, the abundances — so they are made there,
 // and a run that writes the swarms alone downloads the member order, the bounds and four numbers a swarm:
 //
-//   k_dt_init         diff(parent, v) looked up in the parent's row (the bisection of k_dg_parent_diffs, dn_graph.hip), the
+//   k_dt_init         diff(parent, v) looked up in the parent's row (swa_row_find, as k_dg_parent_diffs of dn_graph.hip), the
 //                     first (ancestor, accumulated differences) pair of every amplicon = (parent, that difference), members
 //                     without a link from their parent counted into a control word, pos_of[order[k]] = k
 //   k_dt_jump         pointer jumping: (a, r) -> (ancestor of a, r + accumulated of a), from one buffer into the other — a
 //                     round reads only what the round before wrote, nobody waits for anybody; a pair whose ancestor has passed
 //                     the seed stands still.  bit_width(deepest generation) rounds: radius(v) = the differences summed along
 //                     the parent chain up to the seed (src/algo.cc:560-574)
-//   k_dt_maxradius    the deepest radius of every swarm: the runs of equal swarms along the member order reduced per wave, a
-//                     plain store where the run is the whole swarm, one atomicMax per (wave, swarm) otherwise (k_swarm_sums'
-//                     rule; mass, singletons and deepest generation come from k_swarm_sums itself)
+//   k_dt_maxradius    the deepest radius of every swarm: swa_wave_run_reduce (swa_internal.h) along the member order with
+//                     k_swarm_sums' rule for the whole swarm; mass, singletons and deepest generation are k_swarm_sums' own
 //   k_dt_link_keys    the links of the whole clustering in acceptance order = the non-seed positions k of the member order,
 //   rocPRIM           stably sorted by pos_of[parent[order[k]]], k ascending going in (the host's counting sort per swarm:
 //   k_dt_link_gather  swarms are contiguous in the order, so one sort groups by swarm; children of one parent share a
@@ -27,25 +26,25 @@ namespace {
 
 constexpr uint32_t kDtCtlBroken = 0, kDtCtlWords = 16;
 
-// d_dn_tables: kDtCtlWords control words, then twelve arrays of n words — the two jumping buffers (ancestor, accumulated),
-// pos_of, sort keys and values in / out, the links' parent / child / generation — the swarms' deepest radius (n words of
-// room), the parent differences and the links' differences (n bytes each)
+// d_dn_tables, n amplicons: the control words, then n entries each — the two jumping buffers (ancestor, accumulated), pos_of, sort
+// keys and values in / out, the links' parent / child / generation, the swarms' deepest radius, the parents' and the links' differences
 struct DnTables {
   uint32_t * ctl, * anc[2], * acc[2], * pos_of, * keys[2], * vals[2], * link_parent, * link_child, * link_gen, * maxradius;
   uint8_t * pdiff, * link_diff;
+  void lay(swa_carver & c, uint64_t n) {
+    c.take(kDtCtlWords, ctl);
+    c.take(n, anc[0], anc[1], acc[0], acc[1], pos_of, keys[0], keys[1], vals[0], vals[1], link_parent, link_child, link_gen, maxradius,
+           pdiff, link_diff);
+    c.spare(64);
+  }
 };
-uint64_t dn_tables_bytes(uint64_t n) { return kDtCtlWords * sizeof(uint32_t) + n * 4 * 13 + n * 2 + 64; }
-DnTables dn_tables(const swa_ctx * ctx) {
-  const uint64_t n = ctx->db.n;
-  DnTables t;
-  t.ctl = static_cast<uint32_t *>(ctx->d_dn_tables.ptr);
-  uint32_t * at = t.ctl + kDtCtlWords;
-  for (uint32_t ** a : {&t.anc[0], &t.anc[1], &t.acc[0], &t.acc[1], &t.pos_of, &t.keys[0], &t.keys[1], &t.vals[0], &t.vals[1],
-                        &t.link_parent, &t.link_child, &t.link_gen, &t.maxradius}) { *a = at; at += n; }
-  t.pdiff = reinterpret_cast<uint8_t *>(at);
-  t.link_diff = t.pdiff + n;
-  return t;
-}
+
+// the deepest radius of a run of one swarm (swa_wave_run_reduce, swa_internal.h)
+struct RadiusRun {
+  uint32_t deepest;
+  __device__ __forceinline__ RadiusRun shfl_up(uint32_t d) const { return RadiusRun{__shfl_up(deepest, d, 64)}; }
+  __device__ __forceinline__ void absorb(const RadiusRun & o) { deepest = o.deepest > deepest ? o.deepest : deepest; }
+};
 
 __global__ __launch_bounds__(256) void k_dt_init(const uint64_t * __restrict__ offsets, const uint32_t * __restrict__ nb,
                                                  const uint8_t * __restrict__ df, const uint32_t * __restrict__ parent,
@@ -53,19 +52,14 @@ __global__ __launch_bounds__(256) void k_dt_init(const uint64_t * __restrict__ o
                                                  uint32_t * __restrict__ anc, uint32_t * __restrict__ acc, uint8_t * __restrict__ pdiff,
                                                  uint32_t * __restrict__ pos_of, uint32_t * ctl) {
   const uint32_t lane = threadIdx.x & 63u;
-  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < swa_wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
     bool broken = false;
     if (k < n) {
       const uint32_t v = (uint32_t)k, p = parent[v];
       uint32_t d = 0;
       if (p != kUnset) {                                    // (rows ascend strictly: swa_d1_network_adopt, k_dg_split)
-        uint64_t lo = offsets[p], hi = offsets[p + 1];
-        const uint64_t end = hi;
-        while (lo < hi) {
-          const uint64_t mid = (lo + hi) >> 1;
-          if (nb[mid] < v) { lo = mid + 1; } else { hi = mid; }
-        }
-        d = (lo < end && nb[lo] == v) ? (uint32_t)df[lo] : 0xFFu;
+        uint64_t at;
+        d = swa_row_find(offsets, nb, p, v, at) ? (uint32_t)df[at] : 0xFFu;
       }
       broken = gen[v] != 0u && d == 0xFFu;
       pdiff[v] = (uint8_t)d;
@@ -91,22 +85,17 @@ __global__ __launch_bounds__(256) void k_dt_jump(const uint32_t * __restrict__ a
 __global__ __launch_bounds__(256) void k_dt_maxradius(const uint32_t * __restrict__ order, const uint32_t * __restrict__ sid,
                                                       const uint32_t * __restrict__ radius, const uint32_t * __restrict__ begins, uint32_t n,
                                                       uint32_t * out) {
-  const uint32_t lane = threadIdx.x & 63u;
-  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t s = kUnset, m = 0, members = 0;                  // (beyond the order: a run of its own that writes nothing)
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < swa_wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t s = kUnset;                                      // (beyond the order: a run of its own that writes nothing)
+    RadiusRun r{0};
     if (k < n) {
       const uint32_t a = order[k];
-      s = sid[a]; m = radius[a]; members = 1;
+      s = sid[a]; r.deepest = radius[a];
     }
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {                  // (the runs' maxima and lengths into their last lanes)
-      const uint32_t s2 = __shfl_up(s, d, 64), m2 = __shfl_up(m, d, 64), members2 = __shfl_up(members, d, 64);
-      if (lane >= d && s2 == s) { m = m2 > m ? m2 : m; members += members2; }
-    }
-    const uint32_t next = __shfl_down(s, 1, 64);
-    if (k >= n || (lane != 63u && next == s)) { continue; }   // (not the last lane of its run)
-    if ((uint32_t)k + 1u - members == begins[s] && (uint32_t)k + 1u == begins[s + 1u]) { out[s] = m; }   // (cleared before the launch)
-    else { atomicMax(&out[s], m); }
+    const swa_run run = swa_wave_run_reduce(s, r);
+    if (k >= n || !run.last) { continue; }
+    if ((uint32_t)k + 1u - run.length == begins[s] && (uint32_t)k + 1u == begins[s + 1u]) { out[s] = r.deepest; }   // (cleared before the launch)
+    else { atomicMax(&out[s], r.deepest); }
   }
 }
 
@@ -153,10 +142,11 @@ extern "C" int swa_dn_tables_device(swa_ctx * ctx, uint32_t * nswarms, uint64_t 
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t n = ctx->db.n, w = ctx->res.cluster_nswarms;
   const uint64_t links = (uint64_t)n - w;
-  const uint32_t rounds = bit_width_u32(ctx->res.cluster_maxgen), key_bits = std::max(1u, bit_width_u32(n - 1u));
-  SWA_TRY(ensure_swarm_sums(ctx));
-  SWA_TRY(swa_reserve(ctx, ctx->d_dn_tables, dn_tables_bytes(n)));
-  const DnTables t = dn_tables(ctx);
+  const uint32_t rounds = swa_bit_width(ctx->res.cluster_maxgen), key_bits = std::max(1u, swa_bit_width(n - 1u));
+  SwarmSums sums;
+  SWA_TRY(ensure_swarm_sums(ctx, sums));
+  DnTables t;
+  SWA_TRY(swa_carve(ctx, ctx->d_dn_tables, n, true, t));
   size_t tmp_bytes = 0;
   if (links != 0) {
     (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes, t.keys[0], t.keys[1], t.vals[0], t.vals[1], (size_t)links, 0, key_bits, ctx->stream);
@@ -165,21 +155,21 @@ extern "C" int swa_dn_tables_device(swa_ctx * ctx, uint32_t * nswarms, uint64_t 
   const auto * offsets = static_cast<const uint64_t *>(ctx->d_offsets_tmp.ptr);
   const auto * nb = static_cast<const uint32_t *>(ctx->d_nb_tmp.ptr);
   const auto * df = reinterpret_cast<const uint8_t *>(nb + ctx->res.csr_total);
-  const ClusterView cv = cluster_view(ctx);
-  const uint32_t * parent = cv.gen + n;                      // (label | gen | parent)
-  const dim3 g(blocks_for(ctx, n)), b(256);
+  swa_cluster_arrays cv;
+  SWA_TRY(cluster_arrays(ctx, cv));
+  const dim3 g(swa_grid256(ctx, n)), b(256);
   SWA_HIP(ctx, hipMemsetAsync(t.ctl, 0, kDtCtlWords * sizeof(uint32_t), ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(t.maxradius, 0, (uint64_t)w * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL(k_dt_init, g, b, 0, ctx->stream, offsets, nb, df, parent, cv.gen, cv.order, n, t.anc[0], t.acc[0], t.pdiff, t.pos_of, t.ctl);
+  hipLaunchKernelGGL(k_dt_init, g, b, 0, ctx->stream, offsets, nb, df, cv.parent, cv.gen, cv.order, n, t.anc[0], t.acc[0], t.pdiff, t.pos_of, t.ctl);
   for (uint32_t r = 0; r < rounds; ++r) {
     hipLaunchKernelGGL(k_dt_jump, g, b, 0, ctx->stream, t.anc[r & 1u], t.acc[r & 1u], n, t.anc[(r + 1u) & 1u], t.acc[(r + 1u) & 1u]);
   }
   const uint32_t radius_at = rounds & 1u;
-  hipLaunchKernelGGL(k_dt_maxradius, g, b, 0, ctx->stream, cv.order, cv.sid, t.acc[radius_at], cv.begins, n, t.maxradius);
+  hipLaunchKernelGGL(k_dt_maxradius, g, b, 0, ctx->stream, cv.order, cv.swarmid, t.acc[radius_at], cv.begins, n, t.maxradius);
   if (links != 0) {
-    hipLaunchKernelGGL(k_dt_link_keys, g, b, 0, ctx->stream, cv.order, cv.sid, parent, t.pos_of, cv.begins, n, t.keys[0], t.vals[0]);
+    hipLaunchKernelGGL(k_dt_link_keys, g, b, 0, ctx->stream, cv.order, cv.swarmid, cv.parent, t.pos_of, cv.begins, n, t.keys[0], t.vals[0]);
     SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, tmp_bytes, t.keys[0], t.keys[1], t.vals[0], t.vals[1], (size_t)links, 0, key_bits, ctx->stream));
-    hipLaunchKernelGGL(k_dt_link_gather, dim3(blocks_for(ctx, links)), b, 0, ctx->stream, t.vals[1], cv.order, parent, cv.gen, t.pdiff, links,
+    hipLaunchKernelGGL(k_dt_link_gather, dim3(swa_grid256(ctx, links)), b, 0, ctx->stream, t.vals[1], cv.order, cv.parent, cv.gen, t.pdiff, links,
                        t.link_parent, t.link_child, t.link_gen, t.link_diff);
   }
   SWA_HIP(ctx, hipGetLastError());
@@ -211,19 +201,13 @@ extern "C" int swa_dn_tables_fetch(swa_ctx * ctx, uint32_t * radius, uint64_t * 
   if (!ctx->res.tables.ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_dn_tables_fetch: no tables in place (swa_dn_tables_device)"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   const uint64_t n = ctx->db.n, w = ctx->res.cluster_nswarms, links = ctx->res.tables.nlinks;
-  const DnTables t = dn_tables(ctx);
-  const SwarmSums s = swarm_sums(ctx);
-  struct Copy { void * to; const void * from; uint64_t bytes; };
-  const Copy copies[] = {{radius, t.acc[ctx->res.tables.radius_at], n * sizeof(uint32_t)},
-                         {mass, s.mass, w * sizeof(uint64_t)}, {singletons, s.singles, w * sizeof(uint32_t)},
-                         {maxgen, s.maxgen, w * sizeof(uint32_t)}, {maxradius, t.maxradius, w * sizeof(uint32_t)},
-                         {link_parent, t.link_parent, links * sizeof(uint32_t)}, {link_child, t.link_child, links * sizeof(uint32_t)},
-                         {link_generation, t.link_gen, links * sizeof(uint32_t)}, {link_diff, t.link_diff, links}};
-  // (every page faulted in before the first copy is queued: the rule of swa_d1_cluster_device)
-  for (const Copy & c : copies) { swa_touch_pages(c.to, c.bytes); }
-  for (const Copy & c : copies) {
-    if (c.to != nullptr && c.bytes != 0) { SWA_HIP(ctx, hipMemcpyAsync(c.to, c.from, c.bytes, hipMemcpyDeviceToHost, ctx->stream)); }
-  }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  DnTables t;
+  SWA_TRY(swa_carve(ctx, ctx->d_dn_tables, n, false, t));
+  SwarmSums s;
+  SWA_TRY(swa_carve(ctx, ctx->d_swarm_sums, w, false, s));
+  return swa_download(ctx, {{radius, t.acc[ctx->res.tables.radius_at], n * sizeof(uint32_t)},
+                            {mass, s.mass, w * sizeof(uint64_t)}, {singletons, s.singles, w * sizeof(uint32_t)},
+                            {maxgen, s.maxgen, w * sizeof(uint32_t)}, {maxradius, t.maxradius, w * sizeof(uint32_t)},
+                            {link_parent, t.link_parent, links * sizeof(uint32_t)}, {link_child, t.link_child, links * sizeof(uint32_t)},
+                            {link_generation, t.link_gen, links * sizeof(uint32_t)}, {link_diff, t.link_diff, links}});
 }

@@ -6,10 +6,7 @@
 // amplicon, generation, member order, bounds), the database (abundance, length), d_graft (the candidates) — so it is done
 // there, and a plain `-f -o` run downloads none of those arrays:
 //
-//   k_swarm_sums      one pass over the member order: position k belongs to swarm sid[order[k]], which never falls along
-//                     k, so a wave sums its runs of equal swarms with a segmented scan over the lanes and the last lane of
-//                     a run writes — a plain store when the run is the whole swarm (most swarms have one to three
-//                     members), one atomic per (wave, swarm) otherwise (a swarm of millions spans thousands of waves)
+//   k_swarm_sums      mass, length, singletons, deepest generation of every swarm: swa_wave_run_reduce over the member order
 //   k_light_roles     role[a] = mass[sid[a]] < boundary ? 0 : 1, the byte the fastidious pass reads; k_light_stats the five
 //                     numbers of the log, reduced per wave
 //   k_owner_counts, k_owner_scan, k_owner_write   the owner byte of every amplicon (255 light, else the shard of a run on several
@@ -19,68 +16,61 @@
 //   k_graft_winners   the winners compacted, the losers' candidates withdrawn
 //   rocPRIM           winners by (heavy swarm, pair): a radix sort on the pair, a stable one on the heavy swarm's bits
 //   k_graft_apply     light swarm / parent / child of every graft in chain order; the heavy swarms' sums grown by their
-//                     lights', a wave's run of one heavy swarm reduced first as above
+//                     lights', a wave's run of one heavy swarm reduced first in the same way
 // Integer sums, minima and maxima only: every result is independent of scheduling.
 
 namespace {
 
-// d_cluster as swa_d1_cluster_device lays it out: label | gen | parent | swarmid | ids_in | ids_out (the order) | seed_rank | begins
-struct ClusterView { const uint32_t * gen, * sid, * order, * begins; };
-ClusterView cluster_view(const swa_ctx * ctx) {
-  const uint64_t n = ctx->db.n;
-  const auto * label = static_cast<const uint32_t *>(ctx->d_cluster.ptr);
-  return ClusterView{label + n, label + 3 * n, label + 5 * n, label + 7 * n};
-}
+// d_swarm_sums, w = swarms of the clustering in place; one fill clears all four arrays (`all`)
+struct SwarmSums {
+  unsigned long long * mass, * sumlen; uint32_t * singles, * maxgen; swa_extent all;
+  void lay(swa_carver & c, uint64_t w) { c.take(w, mass, sumlen, singles, maxgen); all = c.extent(mass); c.spare(64); }
+};
 
-// d_swarm_sums: mass u64[w] | sumlen u64[w] | singletons u32[w] | maxgen u32[w], w = swarms of the clustering in place
-struct SwarmSums { unsigned long long * mass, * sumlen; uint32_t * singles, * maxgen; };
-SwarmSums swarm_sums(const swa_ctx * ctx) {
-  const uint64_t w = ctx->res.cluster_nswarms;
-  auto * mass = static_cast<unsigned long long *>(ctx->d_swarm_sums.ptr);
-  auto * singles = reinterpret_cast<uint32_t *>(mass + 2 * w);
-  return SwarmSums{mass, mass + w, singles, singles + w};
-}
-
-// d_graft_work: eight control words (kCtl*), then slot u64[w] | pairs u64[2][w] | heavy u32[2][w]
-constexpr uint32_t kCtlLightSwarms = 0, kCtlLightAmps = 1, kCtlLightNt = 2, kCtlWinners = 3, kCtlWords = 8;
-
-// The lanes of a wave hold keys that never fall from lane to lane: every run of equal keys is summed (a, b, c, count) and
-// its maximum taken (m) into its LAST lane — a segmented inclusive scan, six steps.  Every lane of the wave takes part.
-__device__ __forceinline__ void wave_run_reduce(uint32_t key, unsigned long long & a, unsigned long long & b, uint32_t & c, uint32_t & m,
-                                                uint32_t & count) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) {
-    const uint32_t key2 = __shfl_up(key, d, 64);
-    const unsigned long long a2 = swa_shfl_up_u64(a, d), b2 = swa_shfl_up_u64(b, d);
-    const uint32_t c2 = __shfl_up(c, d, 64), m2 = __shfl_up(m, d, 64), count2 = __shfl_up(count, d, 64);
-    if (lane >= d && key2 == key) { a += a2; b += b2; c += c2; m = m2 > m ? m2 : m; count += count2; }
+// d_graft_work: the control words, then — w entries each — the slot of every swarm and the winners' (pair, heavy swarm) lists twice
+// over, for the sorts; k_graft_apply's results go where the sorts are done with: light swarms -> heavy[1], parents | children -> pairs[1]
+struct GraftCounters { unsigned long long light_swarms, light_amps, light_nt, winners, pad[4]; };
+struct GraftWork {
+  GraftCounters * ctl;
+  unsigned long long * slot, * pairs[2];
+  uint32_t * heavy[2], * light_out, * parent_out, * child_out;
+  void lay(swa_carver & c, uint64_t w) {
+    c.take(1, ctl);
+    c.take(w, slot, pairs[0], pairs[1], heavy[0], heavy[1]);
+    light_out = heavy[1]; parent_out = reinterpret_cast<uint32_t *>(pairs[1]); child_out = parent_out + w;
   }
-}
+};
 
-// positions of a grid-stride loop in which whole waves take part: the count rounded up to the wave
-__device__ __forceinline__ uint64_t wave_span(uint64_t count) { return (count + 63u) & ~uint64_t(63); }
+// the sums of a run of one swarm (swa_wave_run_reduce, swa_internal.h): k_graft_apply leaves the deepest generation alone
+struct GraftRun {
+  unsigned long long mass, len; uint32_t singles;
+  __device__ __forceinline__ GraftRun shfl_up(uint32_t d) const { return GraftRun{swa_shfl_up_u64(mass, d), swa_shfl_up_u64(len, d), __shfl_up(singles, d, 64)}; }
+  __device__ __forceinline__ void absorb(const GraftRun & o) { mass += o.mass; len += o.len; singles += o.singles; }
+};
+struct SumsRun {
+  GraftRun sums; uint32_t maxgen;
+  __device__ __forceinline__ SumsRun shfl_up(uint32_t d) const { return SumsRun{sums.shfl_up(d), __shfl_up(maxgen, d, 64)}; }
+  __device__ __forceinline__ void absorb(const SumsRun & o) { sums.absorb(o.sums); maxgen = o.maxgen > maxgen ? o.maxgen : maxgen; }
+};
 
 __global__ __launch_bounds__(256) void k_swarm_sums(const uint32_t * __restrict__ order, const uint32_t * __restrict__ sid,
                                                     const uint32_t * __restrict__ gen, const uint32_t * __restrict__ begins,
                                                     const uint64_t * __restrict__ abundance, const uint32_t * __restrict__ seqlen, uint32_t n,
                                                     SwarmSums out) {
-  const uint32_t lane = threadIdx.x & 63u;
-  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t s = kUnset, single = 0, g = 0, members = 0;       // (beyond the order: a run of its own that writes nothing)
-    unsigned long long mass = 0, len = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < swa_wave_span(n); k += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t s = kUnset;                                      // (beyond the order: a run of its own that writes nothing)
+    SumsRun r{{0, 0, 0}, 0};
     if (k < n) {
       const uint32_t a = order[k];
-      s = sid[a]; mass = abundance[a]; len = seqlen[a]; single = mass == 1ull ? 1u : 0u; g = gen[a]; members = 1;
+      s = sid[a]; r.sums.mass = abundance[a]; r.sums.len = seqlen[a]; r.sums.singles = r.sums.mass == 1ull ? 1u : 0u; r.maxgen = gen[a];
     }
-    wave_run_reduce(s, mass, len, single, g, members);
-    const uint32_t next = __shfl_down(s, 1, 64);
-    if (k >= n || (lane != 63u && next == s)) { continue; }   // (not the last lane of its run)
-    // the run [k + 1 - members, k] is the whole swarm: nobody else writes its sums (they were cleared before the launch)
-    if ((uint32_t)k + 1u - members == begins[s] && (uint32_t)k + 1u == begins[s + 1u]) {
-      out.mass[s] = mass; out.sumlen[s] = len; out.singles[s] = single; out.maxgen[s] = g;
+    const swa_run run = swa_wave_run_reduce(s, r);
+    if (k >= n || !run.last) { continue; }
+    // the run [k + 1 - length, k] is the whole swarm: nobody else writes its sums (they were cleared before the launch)
+    if ((uint32_t)k + 1u - run.length == begins[s] && (uint32_t)k + 1u == begins[s + 1u]) {
+      out.mass[s] = r.sums.mass; out.sumlen[s] = r.sums.len; out.singles[s] = r.sums.singles; out.maxgen[s] = r.maxgen;
     } else {
-      atomicAdd(&out.mass[s], mass); atomicAdd(&out.sumlen[s], len); atomicAdd(&out.singles[s], single); atomicMax(&out.maxgen[s], g);
+      atomicAdd(&out.mass[s], r.sums.mass); atomicAdd(&out.sumlen[s], r.sums.len); atomicAdd(&out.singles[s], r.sums.singles); atomicMax(&out.maxgen[s], r.maxgen);
     }
   }
 }
@@ -101,10 +91,10 @@ __global__ __launch_bounds__(256) void k_light_roles(const uint32_t * __restrict
   }
 }
 
-// ctl[kCtlLightSwarms .. kCtlLightNt] += light swarms, their amplicons (sizes from the bounds), their nucleotides
+// ctl->light_swarms, light_amps, light_nt += light swarms, their amplicons (sizes from the bounds), their nucleotides
 __global__ __launch_bounds__(256) void k_light_stats(const unsigned long long * __restrict__ mass, const unsigned long long * __restrict__ sumlen,
                                                      const uint32_t * __restrict__ begins, unsigned long long boundary, uint32_t nswarms,
-                                                     unsigned long long * ctl) {
+                                                     GraftCounters * ctl) {
   unsigned long long swarms = 0, amps = 0, nt = 0;
   for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nswarms; s += (uint64_t)gridDim.x * blockDim.x) {
     if (mass[s] < boundary) { ++swarms; amps += begins[s + 1u] - begins[s]; nt += sumlen[s]; }
@@ -114,7 +104,7 @@ __global__ __launch_bounds__(256) void k_light_stats(const unsigned long long * 
     swarms += swa_shfl_xor_u64(swarms, d); amps += swa_shfl_xor_u64(amps, d); nt += swa_shfl_xor_u64(nt, d);
   }
   if ((threadIdx.x & 63u) == 0u && swarms != 0ull) {
-    atomicAdd(&ctl[kCtlLightSwarms], swarms); atomicAdd(&ctl[kCtlLightAmps], amps); atomicAdd(&ctl[kCtlLightNt], nt);
+    atomicAdd(&ctl->light_swarms, swarms); atomicAdd(&ctl->light_amps, amps); atomicAdd(&ctl->light_nt, nt);
   }
 }
 
@@ -130,9 +120,9 @@ __global__ __launch_bounds__(256) void k_graft_min(const uint32_t * __restrict__
 // swarms); every other candidate is withdrawn.  Winners are appended a wave at a time, in no particular order: the sort fixes it.
 __global__ __launch_bounds__(256) void k_graft_winners(uint32_t * __restrict__ cand, const uint32_t * __restrict__ sid, uint32_t n,
                                                        const unsigned long long * __restrict__ slot, unsigned long long * __restrict__ pairs,
-                                                       uint32_t * __restrict__ heavy, unsigned long long * ctl) {
+                                                       uint32_t * __restrict__ heavy, GraftCounters * ctl) {
   const uint32_t lane = threadIdx.x & 63u;
-  for (uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; a < wave_span(n); a += (uint64_t)gridDim.x * blockDim.x) {
+  for (uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; a < swa_wave_span(n); a += (uint64_t)gridDim.x * blockDim.x) {
     bool win = false;
     unsigned long long pair = 0;
     uint32_t p = kUnset;
@@ -145,7 +135,7 @@ __global__ __launch_bounds__(256) void k_graft_winners(uint32_t * __restrict__ c
     const unsigned long long mask = __ballot(win);
     if (mask == 0ull) { continue; }
     unsigned long long base = 0;
-    if (lane == 0u) { base = atomicAdd(&ctl[kCtlWinners], (unsigned long long)__popcll(mask)); }
+    if (lane == 0u) { base = atomicAdd(&ctl->winners, (unsigned long long)__popcll(mask)); }
     base = swa_shfl_u64(base, 0);
     if (win) {
       const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
@@ -159,21 +149,19 @@ __global__ __launch_bounds__(256) void k_graft_winners(uint32_t * __restrict__ c
 __global__ __launch_bounds__(256) void k_graft_apply(const uint32_t * __restrict__ heavy, const unsigned long long * __restrict__ pairs,
                                                      const uint32_t * __restrict__ sid, uint32_t grafts, uint32_t * __restrict__ light_out,
                                                      uint32_t * __restrict__ parent_out, uint32_t * __restrict__ child_out, SwarmSums sums) {
-  const uint32_t lane = threadIdx.x & 63u;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < wave_span(grafts); i += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t h = kUnset, single = 0, unused = 0, count = 0;
-    unsigned long long mass = 0, len = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < swa_wave_span(grafts); i += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t h = kUnset;
+    GraftRun r{0, 0, 0};
     if (i < grafts) {
       const unsigned long long pair = pairs[i];
       const uint32_t child = (uint32_t)pair, l = sid[child];
       h = heavy[i];
       light_out[i] = l; parent_out[i] = (uint32_t)(pair >> 32); child_out[i] = child;
-      mass = sums.mass[l]; len = sums.sumlen[l]; single = sums.singles[l]; count = 1;   // (a light swarm is nobody's heavy swarm: its sums stand still)
+      r.mass = sums.mass[l]; r.len = sums.sumlen[l]; r.singles = sums.singles[l];   // (a light swarm is nobody's heavy swarm: its sums stand still)
     }
-    wave_run_reduce(h, mass, len, single, unused, count);
-    const uint32_t next = __shfl_down(h, 1, 64);
-    if (i >= grafts || (lane != 63u && next == h)) { continue; }
-    atomicAdd(&sums.mass[h], mass); atomicAdd(&sums.sumlen[h], len); atomicAdd(&sums.singles[h], single);   // (maxgen untouched, like the reference)
+    const swa_run run = swa_wave_run_reduce(h, r);            // (every lane takes part)
+    if (i >= grafts || !run.last) { continue; }
+    atomicAdd(&sums.mass[h], r.mass); atomicAdd(&sums.sumlen[h], r.len); atomicAdd(&sums.singles[h], r.singles);   // (maxgen untouched, like the reference)
   }
 }
 
@@ -187,6 +175,14 @@ __global__ __launch_bounds__(256) void k_graft_apply(const uint32_t * __restrict
 // bytes to spare).  Integer sums only.
 constexpr uint32_t kOwnerBlock = 256, kOwnerTile = 4 * kOwnerBlock, kOwnerTurn = 256;
 constexpr uint8_t kOwnerLight = 255;
+
+// d_shard_owner on the rank that makes the owners, n amplicons: the owner bytes (four to spare: the kernels store whole
+// words), the bases of the tiles and of the end, the tiles' counts.  The other ranks of a swa_multi hold the owner bytes alone.
+uint64_t owner_tiles(uint64_t n) { return ((n + 3u) / 4u + kOwnerBlock - 1u) / kOwnerBlock; }
+struct ShardOwners {
+  uint8_t * owner; unsigned long long * base; uint32_t * counts;
+  void lay(swa_carver & c, uint64_t n) { c.take(n + 4u, owner); c.take(owner_tiles(n) + 1u, base); c.take(owner_tiles(n), counts); }
+};
 
 // the role word q of n bytes, bytes beyond n as light
 __device__ __forceinline__ uint32_t owner_role_word(const uint8_t * __restrict__ role, uint64_t q, uint32_t n) {
@@ -282,14 +278,18 @@ int need_clustering(swa_ctx * ctx, const char * who) {
   return swa_fail_msg(ctx, SWA_E_ARG, std::string(who) + ": no clustering in place (swa_d1_cluster_device)");
 }
 
-int ensure_swarm_sums(swa_ctx * ctx) {
-  if (ctx->res.fast.sums_ready) { return SWA_OK; }
+// the arrays of the clustering in place / the sums of its swarms (made on first use: `s` is valid on return)
+int cluster_arrays(swa_ctx * ctx, swa_cluster_arrays & cl) { return swa_carve(ctx, ctx->d_cluster, ctx->db.n, false, cl); }
+
+int ensure_swarm_sums(swa_ctx * ctx, SwarmSums & s) {
   const uint32_t n = ctx->db.n, w = ctx->res.cluster_nswarms;
-  SWA_TRY(swa_reserve(ctx, ctx->d_swarm_sums, (uint64_t)w * 24 + 64));
-  SWA_HIP(ctx, hipMemsetAsync(ctx->d_swarm_sums.ptr, 0, (uint64_t)w * 24, ctx->stream));
-  const ClusterView cv = cluster_view(ctx);
-  hipLaunchKernelGGL(k_swarm_sums, dim3(blocks_for(ctx, n)), dim3(256), 0, ctx->stream, cv.order, cv.sid, cv.gen, cv.begins,
-                     ctx->db.abundance, ctx->db.seqlen, n, swarm_sums(ctx));
+  SWA_TRY(swa_carve(ctx, ctx->d_swarm_sums, w, !ctx->res.fast.sums_ready, s));
+  if (ctx->res.fast.sums_ready) { return SWA_OK; }
+  swa_cluster_arrays cl;
+  SWA_TRY(cluster_arrays(ctx, cl));
+  SWA_HIP(ctx, hipMemsetAsync(s.all.ptr, 0, s.all.bytes, ctx->stream));
+  hipLaunchKernelGGL(k_swarm_sums, dim3(swa_grid256(ctx, n)), dim3(256), 0, ctx->stream, cl.order, cl.swarmid, cl.gen, cl.begins,
+                     ctx->db.abundance, ctx->db.seqlen, n, s);
   SWA_HIP(ctx, hipGetLastError());
   ctx->res.fast.sums_ready = true;
   return SWA_OK;
@@ -307,15 +307,11 @@ extern "C" int swa_d1_swarm_sums_device(swa_ctx * ctx, uint64_t * mass, uint64_t
   const bool wanted = mass != nullptr || sumlen != nullptr || singletons != nullptr || maxgen != nullptr;
   if (wanted && nswarms < w) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_swarm_sums_device: the arrays hold fewer entries than there are swarms"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  SWA_TRY(ensure_swarm_sums(ctx));
+  SwarmSums s;
+  SWA_TRY(ensure_swarm_sums(ctx, s));
   if (!wanted) { return SWA_OK; }
-  const SwarmSums s = swarm_sums(ctx);
-  if (mass != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(mass, s.mass, (uint64_t)w * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (sumlen != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(sumlen, s.sumlen, (uint64_t)w * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (singletons != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(singletons, s.singles, (uint64_t)w * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  if (maxgen != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(maxgen, s.maxgen, (uint64_t)w * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)); }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  const uint64_t w8 = (uint64_t)w * sizeof(uint64_t), w4 = (uint64_t)w * sizeof(uint32_t);
+  return swa_download(ctx, {{mass, s.mass, w8}, {sumlen, s.sumlen, w8}, {singletons, s.singles, w4}, {maxgen, s.maxgen, w4}});
 }
 
 // src/algod1.cc:1291-1328 on the device: the role byte of every amplicon stays in HBM for swa_d1_fastidious_resident
@@ -325,30 +321,26 @@ extern "C" int swa_d1_light_flags_device(swa_ctx * ctx, uint64_t boundary, uint8
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   ctx->res.fast.roles_ready = false;
   ctx->res.fast.owners_ready = false;                       // (owner bytes are made from the role bytes that are replaced here)
-  SWA_TRY(ensure_swarm_sums(ctx));
+  SwarmSums s;
+  SWA_TRY(ensure_swarm_sums(ctx, s));
   const uint32_t n = ctx->db.n, w = ctx->res.cluster_nswarms;
   SWA_TRY(swa_reserve(ctx, ctx->d_swarm_role, (uint64_t)n + 4));
-  SWA_TRY(swa_reserve(ctx, ctx->d_graft_work, kCtlWords * sizeof(uint64_t)));
-  auto * ctl = static_cast<unsigned long long *>(ctx->d_graft_work.ptr);
+  GraftWork gw;                                             // (the control words alone: no array of it is used here)
+  SWA_TRY(swa_carve(ctx, ctx->d_graft_work, 0, true, gw));
   auto * role = static_cast<uint8_t *>(ctx->d_swarm_role.ptr);
-  const ClusterView cv = cluster_view(ctx);
-  const SwarmSums s = swarm_sums(ctx);
-  SWA_HIP(ctx, hipMemsetAsync(ctl, 0, kCtlWords * sizeof(uint64_t), ctx->stream));
-  hipLaunchKernelGGL(k_light_roles, dim3(blocks_for(ctx, n / 4u + 1u)), dim3(256), 0, ctx->stream, cv.sid, s.mass, (unsigned long long)boundary, n, role);
-  hipLaunchKernelGGL(k_light_stats, dim3(blocks_for(ctx, w)), dim3(256), 0, ctx->stream, s.mass, s.sumlen, cv.begins, (unsigned long long)boundary, w, ctl);
+  swa_cluster_arrays cl;
+  SWA_TRY(cluster_arrays(ctx, cl));
+  SWA_HIP(ctx, hipMemsetAsync(gw.ctl, 0, sizeof(GraftCounters), ctx->stream));
+  hipLaunchKernelGGL(k_light_roles, dim3(swa_grid256(ctx, n / 4u + 1u)), dim3(256), 0, ctx->stream, cl.swarmid, s.mass, (unsigned long long)boundary, n, role);
+  hipLaunchKernelGGL(k_light_stats, dim3(swa_grid256(ctx, w)), dim3(256), 0, ctx->stream, s.mass, s.sumlen, cl.begins, (unsigned long long)boundary, w, gw.ctl);
   SWA_HIP(ctx, hipGetLastError());
-  uint64_t host[3] = {};
-  SWA_HIP(ctx, hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-  if (is_light != nullptr) {
-    swa_touch_pages(is_light, n);
-    SWA_HIP(ctx, hipMemcpyAsync(is_light, role, n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  GraftCounters host = {};
+  SWA_TRY(swa_download(ctx, {{&host, gw.ctl, offsetof(GraftCounters, winners)}, {is_light, role, n}}));
   if (is_light != nullptr) { for (uint32_t a = 0; a < n; ++a) { is_light[a] ^= 1; } }   // (the role byte is 0 for light: the caller's flag is the other way round)
-  stats5[0] = host[kCtlLightSwarms]; stats5[1] = host[kCtlLightAmps]; stats5[2] = host[kCtlLightNt];
-  stats5[3] = w - host[kCtlLightSwarms]; stats5[4] = n - host[kCtlLightAmps];
+  stats5[0] = host.light_swarms; stats5[1] = host.light_amps; stats5[2] = host.light_nt;
+  stats5[3] = w - host.light_swarms; stats5[4] = n - host.light_amps;
   ctx->res.fast.roles_ready = true;
-  ctx->res.fast.light_amps = host[kCtlLightAmps];
+  ctx->res.fast.light_amps = host.light_amps;
   return SWA_OK;
 }
 
@@ -358,10 +350,7 @@ extern "C" int swa_d1_graft_candidates_fetch(swa_ctx * ctx, uint32_t * graft_can
   SWA_TRY(need_clustering(ctx, "swa_d1_graft_candidates_fetch"));
   if (!ctx->res.fast.cand_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_graft_candidates_fetch: no candidates in place (swa_d1_fastidious*, swa_d1_graft_device)"); }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
-  swa_touch_pages(graft_cand, (uint64_t)ctx->db.n * sizeof(uint32_t));
-  SWA_HIP(ctx, hipMemcpyAsync(graft_cand, ctx->d_graft.ptr, (uint64_t)ctx->db.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  return swa_download(ctx, {{graft_cand, ctx->d_graft.ptr, (uint64_t)ctx->db.n * sizeof(uint32_t)}});
 }
 
 // attach_candidates (src/algod1.cc:214-336) on the device: G grafts in chain order
@@ -381,34 +370,33 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   if (ctx->res.fast.sums_grafted) { ctx->res.fast.sums_ready = false; ctx->res.fast.sums_grafted = false; }   // (every call grows the swarms' own sums)
-  SWA_TRY(ensure_swarm_sums(ctx));
+  SwarmSums sums;
+  SWA_TRY(ensure_swarm_sums(ctx, sums));
   SWA_TRY(swa_reserve(ctx, ctx->d_graft, (uint64_t)n * sizeof(uint32_t)));
   ctx->dr = {};                                             // (d_graft: candidates from here on, no dereplication's array)
-  SWA_TRY(swa_reserve(ctx, ctx->d_graft_work, kCtlWords * sizeof(uint64_t) + (uint64_t)w * 32));
-  auto * ctl = static_cast<unsigned long long *>(ctx->d_graft_work.ptr);
-  auto * slot = ctl + kCtlWords, * pairs0 = slot + w, * pairs1 = pairs0 + w;
-  auto * heavy0 = reinterpret_cast<uint32_t *>(pairs1 + w), * heavy1 = heavy0 + w;
+  GraftWork gw;
+  SWA_TRY(swa_carve(ctx, ctx->d_graft_work, w, true, gw));
   auto * cand = static_cast<uint32_t *>(ctx->d_graft.ptr);
-  const uint32_t pair_bits = 32u + std::max(1u, bit_width_u32(n - 1u)), heavy_bits = std::max(1u, bit_width_u32(w - 1u));
-  size_t tmp_bytes = 0, need = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, need, pairs0, pairs1, heavy0, heavy1, (size_t)w, 0, pair_bits, ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
-  (void)rocprim::radix_sort_pairs(nullptr, need, heavy1, heavy0, pairs1, pairs0, (size_t)w, 0, heavy_bits, ctx->stream);
-  tmp_bytes = std::max(tmp_bytes, need);
+  const uint32_t pair_bits = 32u + std::max(1u, swa_bit_width(n - 1u)), heavy_bits = std::max(1u, swa_bit_width(w - 1u));
+  size_t asked[2] = {}, need = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, asked[0], gw.pairs[0], gw.pairs[1], gw.heavy[0], gw.heavy[1], (size_t)w, 0, pair_bits, ctx->stream);
+  (void)rocprim::radix_sort_pairs(nullptr, asked[1], gw.heavy[1], gw.heavy[0], gw.pairs[1], gw.pairs[0], (size_t)w, 0, heavy_bits, ctx->stream);
+  const size_t tmp_bytes = std::max(asked[0], asked[1]);
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, tmp_bytes + 16));
   if (graft_cand != nullptr) {
     ctx->res.fast.cand_ready = false;
     SWA_HIP(ctx, hipMemcpyAsync(cand, graft_cand, (uint64_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   }
-  const ClusterView cv = cluster_view(ctx);
-  const dim3 g(blocks_for(ctx, n)), b(256);
-  SWA_HIP(ctx, hipMemsetAsync(ctl + kCtlWinners, 0, sizeof(uint64_t), ctx->stream));
-  SWA_HIP(ctx, hipMemsetAsync(slot, 0xFF, (uint64_t)w * sizeof(uint64_t), ctx->stream));
-  hipLaunchKernelGGL(k_graft_min, g, b, 0, ctx->stream, cand, cv.sid, n, slot);
-  hipLaunchKernelGGL(k_graft_winners, g, b, 0, ctx->stream, cand, cv.sid, n, slot, pairs0, heavy0, ctl);
+  swa_cluster_arrays cl;
+  SWA_TRY(cluster_arrays(ctx, cl));
+  const dim3 g(swa_grid256(ctx, n)), b(256);
+  SWA_HIP(ctx, hipMemsetAsync(&gw.ctl->winners, 0, sizeof(uint64_t), ctx->stream));
+  SWA_HIP(ctx, hipMemsetAsync(gw.slot, 0xFF, (uint64_t)w * sizeof(uint64_t), ctx->stream));
+  hipLaunchKernelGGL(k_graft_min, g, b, 0, ctx->stream, cand, cl.swarmid, n, gw.slot);
+  hipLaunchKernelGGL(k_graft_winners, g, b, 0, ctx->stream, cand, cl.swarmid, n, gw.slot, gw.pairs[0], gw.heavy[0], gw.ctl);
   SWA_HIP(ctx, hipGetLastError());
   uint64_t winners = 0;
-  SWA_HIP(ctx, hipMemcpyAsync(&winners, ctl + kCtlWinners, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipMemcpyAsync(&winners, &gw.ctl->winners, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's candidates are free again, too)
   ctx->res.fast.cand_ready = true;
   const uint32_t made = (uint32_t)winners;
@@ -418,21 +406,16 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
   // (before the sums grow: the call with room starts from the same candidates — the winners keep theirs — and the same sums)
   if (wanted && made > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_graft_device: result arrays too small"); }
   need = tmp_bytes;
-  SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, pairs0, pairs1, heavy0, heavy1, (size_t)made, 0, pair_bits, ctx->stream));
+  SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, gw.pairs[0], gw.pairs[1], gw.heavy[0], gw.heavy[1], (size_t)made, 0, pair_bits, ctx->stream));
   need = tmp_bytes;
-  SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, heavy1, heavy0, pairs1, pairs0, (size_t)made, 0, heavy_bits, ctx->stream));
-  // the sorted winners lie in heavy0 / pairs0; light swarm -> heavy1, parent | child -> the two halves of pairs1
-  auto * light_d = heavy1, * parent_d = reinterpret_cast<uint32_t *>(pairs1), * child_d = parent_d + w;
-  hipLaunchKernelGGL(k_graft_apply, dim3(blocks_for(ctx, made)), b, 0, ctx->stream, heavy0, pairs0, cv.sid, made, light_d, parent_d, child_d, swarm_sums(ctx));
+  SWA_HIP(ctx, rocprim::radix_sort_pairs(ctx->d_scan_hits.ptr, need, gw.heavy[1], gw.heavy[0], gw.pairs[1], gw.pairs[0], (size_t)made, 0, heavy_bits, ctx->stream));
+  // the sorted winners lie in gw.heavy[0] / gw.pairs[0]; the results go where GraftWork says
+  hipLaunchKernelGGL(k_graft_apply, dim3(swa_grid256(ctx, made)), b, 0, ctx->stream, gw.heavy[0], gw.pairs[0], cl.swarmid, made, gw.light_out, gw.parent_out,
+                     gw.child_out, sums);
   SWA_HIP(ctx, hipGetLastError());
   ctx->res.fast.sums_grafted = true;
   const uint64_t bytes = (uint64_t)made * sizeof(uint32_t);
-  if (heavy_swarm != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(heavy_swarm, heavy0, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
-  if (light_swarm != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(light_swarm, light_d, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
-  if (parent != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(parent, parent_d, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
-  if (child != nullptr) { SWA_HIP(ctx, hipMemcpyAsync(child, child_d, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SWA_OK;
+  return swa_download(ctx, {{heavy_swarm, gw.heavy[0], bytes}, {light_swarm, gw.light_out, bytes}, {parent, gw.parent_out, bytes}, {child, gw.child_out, bytes}});
 }
 
 // ---- shard owners ------------------------------------------------------------------------------------------------------
@@ -461,24 +444,16 @@ extern "C" int swa_d1_shard_owners_device(swa_ctx * ctx, uint32_t nshards, uint8
   SWA_HIP(ctx, hipSetDevice(ctx->device));
   ctx->res.fast.owners_ready = false;
   const uint32_t n = ctx->db.n;
-  const uint64_t words = ((uint64_t)n + 3u) / 4u, tiles = (words + kOwnerBlock - 1u) / kOwnerBlock;
-  const uint64_t owner_bytes = ((uint64_t)n + 4u + 7u) & ~uint64_t(7);
-  SWA_TRY(swa_reserve(ctx, ctx->d_shard_owner, owner_bytes + (tiles + 1u) * sizeof(uint64_t) + tiles * sizeof(uint32_t)));
-  auto * owner = static_cast<uint8_t *>(ctx->d_shard_owner.ptr);
-  auto * base = reinterpret_cast<unsigned long long *>(owner + owner_bytes);
-  auto * counts = reinterpret_cast<uint32_t *>(base + tiles + 1u);
+  ShardOwners so;
+  SWA_TRY(swa_carve(ctx, ctx->d_shard_owner, n, true, so));
+  const uint64_t tiles = owner_tiles(n);
   const auto * role = static_cast<const uint8_t *>(ctx->d_swarm_role.ptr);
-  hipLaunchKernelGGL(k_owner_counts, dim3((uint32_t)tiles), dim3(kOwnerBlock), 0, ctx->stream, role, n, counts);
-  hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(kOwnerTurn), 0, ctx->stream, counts, (uint32_t)tiles, base);
-  hipLaunchKernelGGL(k_owner_write, dim3((uint32_t)tiles), dim3(kOwnerBlock), 0, ctx->stream, role, n, base, (uint32_t)tiles, nshards, owner);
+  hipLaunchKernelGGL(k_owner_counts, dim3((uint32_t)tiles), dim3(kOwnerBlock), 0, ctx->stream, role, n, so.counts);
+  hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(kOwnerTurn), 0, ctx->stream, so.counts, (uint32_t)tiles, so.base);
+  hipLaunchKernelGGL(k_owner_write, dim3((uint32_t)tiles), dim3(kOwnerBlock), 0, ctx->stream, role, n, so.base, (uint32_t)tiles, nshards, so.owner);
   SWA_HIP(ctx, hipGetLastError());
   uint64_t h = 0;
-  SWA_HIP(ctx, hipMemcpyAsync(&h, base + tiles, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-  if (owners != nullptr) {
-    swa_touch_pages(owners, n);
-    SWA_HIP(ctx, hipMemcpyAsync(owners, owner, n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  SWA_TRY(swa_download(ctx, {{&h, so.base + tiles, sizeof(h)}, {owners, so.owner, n}}));
   *heavy = h;
   ctx->res.fast.owners_ready = true;
   ctx->res.fast.owners_shards = nshards;
@@ -488,7 +463,7 @@ extern "C" int swa_d1_shard_owners_device(swa_ctx * ctx, uint32_t nshards, uint8
 
 int swa_d1_roles_from_owners(swa_ctx * ctx, const uint8_t * d_owner, uint32_t shard, uint8_t * d_role) {
   const uint32_t n = ctx->db.n;
-  hipLaunchKernelGGL(k_roles_from_owners, dim3(blocks_for(ctx, n / 4u + 1u)), dim3(256), 0, ctx->stream, d_owner, shard, n, d_role);
+  hipLaunchKernelGGL(k_roles_from_owners, dim3(swa_grid256(ctx, n / 4u + 1u)), dim3(256), 0, ctx->stream, d_owner, shard, n, d_role);
   SWA_HIP(ctx, hipGetLastError());
   return SWA_OK;
 }

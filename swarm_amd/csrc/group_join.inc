@@ -167,11 +167,6 @@ struct PairStage {
 };
 
 // ---- host -------------------------------------------------------------------------------------------------------------
-inline int join_grid(const swa_ctx * ctx, uint64_t items) {
-  const uint64_t blocks = (items + 255) / 256, cap = (uint64_t)ctx->num_cus * 8;
-  return (int)std::max<uint64_t>(1, std::min(blocks, cap));
-}
-
 // room for a table of up to `asize` slots over n amplicons with up to per_a keys a creator; the caps are the route's
 inline int join_reserve(swa_ctx * ctx, uint64_t asize, uint32_t n, uint32_t per_a, uint64_t member_cap, uint32_t item_cap) {
   SWA_TRY(swa_reserve(ctx, ctx->d_fkeys, asize * sizeof(uint64_t)));
@@ -204,7 +199,7 @@ inline JoinTable join_table(swa_ctx * ctx, uint64_t asize, uint32_t n, uint32_t 
 template <class Shape, class KeyKernels, class Scan>
 int join_run(swa_ctx * ctx, const JoinTable & t, uint32_t min_product, uint32_t * counter, uint32_t item_cap, KeyKernels && key_kernels,
              Scan && scan) {
-  const dim3 gn(join_grid(ctx, t.n)), ga(join_grid(ctx, t.asize)), b(256);
+  const dim3 gn(swa_grid256(ctx, t.n)), ga(swa_grid256(ctx, t.asize)), b(256);
   hipLaunchKernelGGL(k_join_clear, ga, b, 0, ctx->stream, t);
   key_kernels(gn, b);
   hipLaunchKernelGGL(k_join_totals, ga, b, 0, ctx->stream, t, min_product);

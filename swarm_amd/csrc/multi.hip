@@ -80,11 +80,6 @@ __global__ __launch_bounds__(256) void k_min_u32(uint32_t * __restrict__ acc, co
   }
 }
 
-int blocks_for(const swa_ctx * ctx, uint64_t items) {
-  const uint64_t b = (items + 255) / 256, cap = (uint64_t)ctx->num_cus * 8;
-  return (int)std::max<uint64_t>(1, std::min(b, cap));
-}
-
 // runs f(rank) on one host thread per rank; first non-zero status wins
 int on_all(swa_multi * m, const std::function<int(int)> & f) {
   const int world = (int)m->ctx.size();
@@ -416,7 +411,7 @@ extern "C" int swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, 
       if (hipMemcpyAsync(m->gathered.ptr, m->ctx[(size_t)r]->d_graft.ptr, (uint64_t)n * sizeof(uint32_t), hipMemcpyDefault, c0->stream) != hipSuccess) {
         return fail(m, SWA_E_DEVICE, "device-to-device copy of graft candidates failed");
       }
-      hipLaunchKernelGGL(k_min_u32, dim3(blocks_for(c0, n)), dim3(256), 0, c0->stream, static_cast<uint32_t *>(c0->d_graft.ptr),
+      hipLaunchKernelGGL(k_min_u32, dim3(swa_grid256(c0, n)), dim3(256), 0, c0->stream, static_cast<uint32_t *>(c0->d_graft.ptr),
                          static_cast<const uint32_t *>(m->gathered.ptr), (uint64_t)n);
     }
   }
@@ -503,7 +498,7 @@ extern "C" int swa_multi_d1_fastidious_resident(swa_multi * m, uint64_t light_nt
       if (hipMemcpyAsync(m->gathered.ptr, m->ctx[(size_t)r]->d_graft.ptr, (uint64_t)n * sizeof(uint32_t), hipMemcpyDefault, c0->stream) != hipSuccess) {
         return fail(m, SWA_E_DEVICE, "device-to-device copy of graft candidates failed");
       }
-      hipLaunchKernelGGL(k_min_u32, dim3(blocks_for(c0, n)), dim3(256), 0, c0->stream, static_cast<uint32_t *>(c0->d_graft.ptr),
+      hipLaunchKernelGGL(k_min_u32, dim3(swa_grid256(c0, n)), dim3(256), 0, c0->stream, static_cast<uint32_t *>(c0->d_graft.ptr),
                          static_cast<const uint32_t *>(m->gathered.ptr), (uint64_t)n);
     }
   }
@@ -603,7 +598,7 @@ static int dn_graph_on_root(swa_multi * m, int no_cluster_breaking, bool residen
       ma.keys = keys; ma.vals = vals; ma.world = (uint32_t)world;
       for (int r = 0; r <= world; ++r) { ma.at[r] = at[(size_t)r]; }
       ma.out_keys = keys + all + 1; ma.out_vals = vals + all + 1;
-      hipLaunchKernelGGL(k_merge_sorted_lists, dim3(blocks_for(c0, all)), dim3(256), 0, c0->stream, ma);
+      hipLaunchKernelGGL(k_merge_sorted_lists, dim3(swa_grid256(c0, all)), dim3(256), 0, c0->stream, ma);
       SWA_HIP(c0, hipGetLastError());
     }
     const unsigned long long * sorted = all != 0 ? keys + all + 1 : nullptr;

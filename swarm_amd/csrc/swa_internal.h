@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -543,6 +544,40 @@ __device__ __forceinline__ uint64_t swa_shfl_down_u64(uint64_t v, unsigned d) {
   return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
 }
 
+// ---- runs of equal keys along a wave -------------------------------------------------------------------------------------
+// One position of a sorted order per lane: the keys never fall from lane to lane.  A segmented inclusive scan over the 64
+// lanes, six steps, reduces every run of equal keys into its LAST lane; the payload P moves itself up d lanes (P::shfl_up:
+// the fields it has, no others) and takes in what arrived (P::absorb).  Returns whether the lane is the last of its run,
+// and the run's length.  Every lane takes part: the loop around it runs to swa_wave_span(count), lanes beyond the count
+// carry a key no position has and write nothing.  The callers (k_swarm_sums, k_graft_apply, k_dt_maxradius, k_d0_sums)
+// store plainly where the run is the whole cluster and add with one atomic per (wave, cluster) otherwise.
+struct swa_run { bool last; uint32_t length; };
+template <class P> __device__ __forceinline__ swa_run swa_wave_run_reduce(uint32_t key, P & p) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t length = 1;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t key2 = __shfl_up(key, d, 64), length2 = __shfl_up(length, d, 64);
+    const P p2 = p.shfl_up(d);
+    if (lane >= d && key2 == key) { p.absorb(p2); length += length2; }
+  }
+  const uint32_t next = __shfl_down(key, 1, 64);
+  return swa_run{lane == 63u || next != key, length};
+}
+// positions of a grid-stride loop in which whole waves take part: the count rounded up to the wave
+__device__ __forceinline__ uint64_t swa_wave_span(uint64_t count) { return (count + 63u) & ~uint64_t(63); }
+
+// whether v stands in the strictly ascending row of p (nb[offsets[p] .. offsets[p + 1])), by bisection; at = where, if it does
+__device__ __forceinline__ bool swa_row_find(const uint64_t * __restrict__ offsets, const uint32_t * __restrict__ nb, uint32_t p, uint32_t v, uint64_t & at) {
+  uint64_t lo = offsets[p], hi = offsets[p + 1];
+  const uint64_t end = hi;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (nb[mid] < v) { lo = mid + 1; } else { hi = mid; }
+  }
+  return (at = lo) < end && nb[lo] == v;
+}
+
 // Word `w` of the microvariant of `seed` (len nt, nw = ceil(len/32) valid words,
 // zero padded) described by (type, pos, base): what generate_variant_sequence
 // (src/variants.cc:78-115) materialises nucleotide by nucleotide, computed here
@@ -594,6 +629,64 @@ inline void swa_touch_pages(void * ptr, size_t bytes) {
     }
   });
 }
+
+// The download tail of a call: every destination's pages are faulted in BEFORE any copy is queued (swa_touch_pages writes a
+// zero byte a page: behind a queued copy it would race with it), then the copies, then one wait; null and empty ones are skipped
+struct swa_copy { void * to; const void * from; uint64_t bytes; };
+inline int swa_download(swa_ctx * ctx, std::initializer_list<swa_copy> copies, bool wait = true) {
+  for (const swa_copy & c : copies) { swa_touch_pages(c.to, c.bytes); }
+  for (const swa_copy & c : copies) {
+    if (c.to != nullptr && c.bytes != 0) { SWA_HIP(ctx, hipMemcpyAsync(c.to, c.from, c.bytes, hipMemcpyDeviceToHost, ctx->stream)); }
+  }
+  if (wait) { SWA_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
+  return SWA_OK;
+}
+
+inline int swa_grid256(const swa_ctx * ctx, uint64_t items) { return swa_grid_for(ctx, items, 256, 8); }   // 256 items a workgroup, 8 a CU at most
+inline uint32_t swa_bit_width(uint64_t v) { uint32_t b = 0; while (v != 0u) { ++b; v >>= 1; } return b; }
+
+// ---- buffers that hold several arrays --------------------------------------------------------------------------------------
+// A struct of named pointers says in lay(carver, count) how its buffer is cut up: take(count, a, b ...) gives each of its
+// arguments `count` elements at its type's alignment (hipMalloc's buffers are 256-byte aligned), one behind the other.
+// swa_carve runs lay() from a null base for the size to reserve and from the buffer for the pointers — no second formula —
+// and fails with SWA_E_INTERNAL if the walk ends beyond the buffer.  extent(first): the bytes from an array taken earlier
+// up to here, what ONE fill may cover when it clears several arrays.
+struct swa_extent { void * ptr; uint64_t bytes; };
+struct swa_carver {
+  uintptr_t base;
+  uint64_t used = 0;
+  template <class T, class... R> void take(uint64_t count, T *& first, R *&... rest) {
+    used = (used + alignof(T) - 1) & ~uint64_t(alignof(T) - 1);
+    first = reinterpret_cast<T *>(base + used);
+    used += count * sizeof(T);
+    if constexpr (sizeof...(rest) != 0) { take(count, rest...); }
+  }
+  void spare(uint64_t bytes) { used += bytes; }             // room nobody names (kept: no buffer is smaller than it used to be)
+  swa_extent extent(void * first) const { return swa_extent{first, base + used - reinterpret_cast<uintptr_t>(first)}; }
+};
+template <class L> int swa_carve(swa_ctx * ctx, swa_dbuf & buf, uint64_t count, bool grow, L & out) {
+  swa_carver size{0}, c{0};
+  out.lay(size, count);
+  if (grow) { SWA_TRY(swa_reserve(ctx, buf, size.used)); }
+  c.base = reinterpret_cast<uintptr_t>(buf.ptr);
+  out.lay(c, count);
+  if (buf.ptr == nullptr || c.used > buf.bytes) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "a buffer's layout ends beyond the buffer"); }
+  return SWA_OK;
+}
+
+// d_cluster (swa_d1_cluster_device), n amplicons: among its work arrays what the clustering leaves for swa_d1_cluster_fetch,
+// fast_graft.inc, dn_tables.inc and swa_dn_parent_diffs: swarmid, gen, parent, order (swarm s = order[begins[s], begins[s + 1]))
+struct swa_cluster_arrays {
+  uint32_t * label, * gen, * parent, * swarmid, * ids_in, * order, * seed_rank, * begins, * stamp;
+  unsigned long long * keys_in, * keys_out;                 // sort keys, read as 32-bit ones where they are narrow
+  uint8_t * is_seed;
+  void lay(swa_carver & c, uint64_t n) {
+    c.take(n, label, gen, parent, swarmid, ids_in, order, seed_rank);
+    c.take(n + 4, begins);                                  // (n + 1 are used: begins[swarms] = n)
+    c.take(n, stamp, keys_in, keys_out, is_seed);
+    c.spare(4 * n + 128);                                   // (a tenth array of n words that nobody uses has always been part of it)
+  }
+};
 
 #include <chrono>
 inline void swa_lap(swa_ctx * ctx, const char * what) {
