@@ -683,6 +683,13 @@ int  swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, uint64_t l
    downloaded; swa_d1_network_fetch, swa_d1_cluster_device and the calls behind it then work on that context.  After a
    failure rank 0 holds no resident network. */
 int  swa_multi_d1_network_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total, int * has_duplicates);
+/* How the ranks got the members of their anchor groups in the last swa_multi_d1_network / swa_multi_d1_network_resident call:
+   SWA_MULTI_BUILD_NONE (no call yet, or the call failed before the build), _ROUTED (every rank keyed its slice and the
+   key records travelled to their owners), _STREAMED (every rank walked the whole database because it was asked to:
+   SWARM_AMD_MULTI_BUILD=streamed, or one rank), _OVERFLOWED (the routed build was tried, a destination region of a rank's
+   outgoing lists was too small — many amplicons sharing one window key — and the ranks then streamed). */
+enum { SWA_MULTI_BUILD_NONE = 0, SWA_MULTI_BUILD_ROUTED = 1, SWA_MULTI_BUILD_STREAMED = 2, SWA_MULTI_BUILD_OVERFLOWED = 3 };
+int  swa_multi_d1_last_build(const swa_multi * m);
 /* = swa_d1_fastidious_resident on swa_multi_ctx(m, 0), the heavy amplicons divided among the ranks: needs rank 0's clustering
    and the flags of swa_d1_light_flags_device on it (SWA_E_ARG otherwise).  The owner bytes (swa_d1_shard_owners_device, S =
    the ranks) go from rank 0 to every rank (ncclBroadcast; device-to-device copies between ranks on one GPU), every rank runs
@@ -709,6 +716,12 @@ int  swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64_t * offse
                         uint64_t cap, uint64_t * total);
 int  swa_multi_dn_graph_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total);
 int  swa_multi_dn_graph_totals(swa_multi * m, uint64_t * out3);
+/* Debug entry: the merge rank 0 runs on the gathered shares (k_merge_sorted_lists, launched as swa_multi_dn_graph launches
+   it), from host arrays to host arrays on the context's stream.  List r = [at[r], at[r + 1]) of keys / vals, every list
+   sorted by key, at[0] = 0, at[] not descending, 1 <= world <= 64 (SWA_E_ARG otherwise); out_keys / out_vals take
+   at[world] entries: the lists merged by key, equal keys in list order.  at[world] = 0: nothing is launched or written. */
+int  swa_merge_sorted_lists(swa_ctx * ctx, const uint64_t * keys, const uint32_t * vals, const uint64_t * at, uint32_t world,
+                            uint64_t * out_keys, uint32_t * out_vals);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,7 @@ EXPORTS = [
     "swa_d1_graft_candidates_fetch", "swa_d1_result_install_graft", "swa_d1_result_detail_fetches",
     "swa_d1_network_fetch_diffs", "swa_d1_shard_owners_device", "swa_d1_shard_owner_for", "swa_d1_shard_owner_plan",
     "swa_multi_d1_network_resident", "swa_multi_d1_fastidious_resident", "swa_multi_dn_graph_resident",
+    "swa_multi_d1_last_build", "swa_merge_sorted_lists",
 ]
 
 
@@ -145,6 +146,7 @@ def load_library() -> C.CDLL:
     lib.swa_d1_result_install_graft.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.swa_d1_shard_owners_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p]
     lib.swa_d1_shard_owner_for.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, u32p]
+    lib.swa_merge_sorted_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.swa_d1_shard_owner_plan.argtypes = [C.c_void_p]
     lib.swa_d1_result_detail_fetches.argtypes = [C.c_void_p]
     lib.swa_d1_result_detail_fetches.restype = C.c_uint32
@@ -941,6 +943,25 @@ class Context:
         self._check(self.lib.swa_d1_shard_owners_device(self.h, int(nshards), _ptr(owners), C.byref(heavy)))
         return owners, int(heavy.value)
 
+    def merge_sorted_lists(self, keys, vals, at, world: int | None = None, out_keys=None, out_vals=None):
+        """swa_merge_sorted_lists: the merge rank 0 of a MultiContext runs on the gathered shares of a d >= 2 graph, on host
+        arrays: list r = keys / vals [at[r], at[r + 1]), sorted by key; (merged keys, merged values), equal keys in list
+        order.  world: len(at) - 1 unless given; out_keys / out_vals: arrays to write into (at[world] entries at least)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        at = np.ascontiguousarray(at, dtype=np.uint64)
+        if world is None:
+            world = len(at) - 1
+        count = int(at[world]) if 0 <= world < len(at) else 0
+        if len(keys) < count or len(vals) < count:
+            raise ValueError("merge_sorted_lists: fewer keys or values than at[world]")
+        out_keys = np.zeros(count, dtype=np.uint64) if out_keys is None else out_keys
+        out_vals = np.zeros(count, dtype=np.uint32) if out_vals is None else out_vals
+        if out_keys.dtype != np.uint64 or out_vals.dtype != np.uint32 or len(out_keys) < count or len(out_vals) < count:
+            raise ValueError("merge_sorted_lists: out_keys u64 / out_vals u32 of at[world] entries")
+        self._check(self.lib.swa_merge_sorted_lists(self.h, _ptr(keys), _ptr(vals), _ptr(at), int(world), _ptr(out_keys), _ptr(out_vals)))
+        return out_keys, out_vals
+
     def d1_graft_device(self, graft_cand=None, cap: int | None = None):
         """swa_d1_graft_device: (heavy swarm, light swarm, parent, child) of the G grafts in chain order.  graft_cand: n
         candidates on the host, or None for those the last fastidious pass left in HBM.  cap: entries of the result arrays
@@ -1499,6 +1520,10 @@ def nw_align_host(dseq: np.ndarray, dlen: int, qseq: np.ndarray, qlen: int, mism
 
 # ---- d = 1 on several GPUs from one process (multi.hip) -----------------------------------------
 
+MULTI_BUILD_NONE, MULTI_BUILD_ROUTED, MULTI_BUILD_STREAMED, MULTI_BUILD_OVERFLOWED = range(4)
+MULTI_BUILD_NAMES = ("none", "routed records", "streamed on request", "streamed after overflow")
+
+
 class MultiContext:
     """swa_multi_*: one context + stream + host thread per listed device inside the library; RCCL for the exchange
     when the devices are distinct, device-to-device copies when a device is listed twice."""
@@ -1521,6 +1546,7 @@ class MultiContext:
         lib.swa_multi_d1_network_resident.argtypes = [C.c_void_p, C.c_int, u64p, C.POINTER(C.c_int)]
         lib.swa_multi_d1_fastidious_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.swa_multi_dn_graph_resident.argtypes = [C.c_void_p, C.c_int, u64p]
+        lib.swa_multi_d1_last_build.argtypes = [C.c_void_p]
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
         rc = lib.swa_multi_create(arr, len(devices), C.byref(h))
@@ -1592,6 +1618,11 @@ class MultiContext:
         dup = C.c_int(0)
         self._check(self.lib.swa_multi_d1_network_resident(self.h, int(no_cluster_breaking), C.byref(total), C.byref(dup)))
         return int(total.value)
+
+    def last_build(self) -> str:
+        """swa_multi_d1_last_build: how the ranks got the members of their anchor groups in the last d1_network /
+        d1_network_resident call: one of MULTI_BUILD_NAMES."""
+        return MULTI_BUILD_NAMES[self.lib.swa_multi_d1_last_build(self.h)]
 
     def dn_graph_resident(self, d: int, no_cluster_breaking: bool = False, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
         """swa_multi_dn_begin + swa_multi_dn_graph_resident: the whole d >= 2 graph left resident on rank 0's GPU (ctx(0):

@@ -37,6 +37,7 @@ struct swa_multi {
   swa_dbuf gathered;                   // on rank 0: what the ranks send there (their link lists, graft candidates, graph shares)
   std::vector<swa_dbuf> routed, routed_counts, inbox;   // routed index build: a rank's outgoing id lists, their counts, what it received
   std::vector<uint64_t> link_cap;
+  int last_build = SWA_MULTI_BUILD_NONE;   // of the last swa_multi_d1_network* call (swa_multi_d1_last_build)
   std::string err;
 };
 
@@ -72,6 +73,13 @@ __global__ __launch_bounds__(256) void k_merge_sorted_lists(const MergeArgs a) {
     }
     a.out_keys[pos] = key; a.out_vals[pos] = a.vals[idx];
   }
+}
+
+// the one launch of the merge (dn_graph_on_root, swa_merge_sorted_lists): a.at[a.world] != 0
+int launch_merge(swa_ctx * c, const MergeArgs & a) {
+  hipLaunchKernelGGL(k_merge_sorted_lists, dim3(swa_grid256(c, a.at[a.world])), dim3(256), 0, c->stream, a);
+  SWA_HIP(c, hipGetLastError());
+  return SWA_OK;
 }
 
 __global__ __launch_bounds__(256) void k_min_u32(uint32_t * __restrict__ acc, const uint32_t * __restrict__ other, uint64_t n) {
@@ -198,7 +206,12 @@ extern "C" int swa_multi_db_upload(swa_multi * m, const swa_db_view * host) {
 // ncclSend / ncclRecv over RCCL, device-to-device copies when the ranks share a device —, every rank builds its indexes
 // from what it received, starting at the partition (round 6: rounds 4-5 sent the ids and keyed them again at the owner,
 // one random line fetch each).
-// *routed = false when a destination region overflowed (never with hashed ownership): the caller builds the other way.
+// *routed = false when a destination region overflowed: the caller builds the other way.  Hashed ownership spreads DISTINCT
+// keys evenly, so a region — 1.5 x its even share + 1024 records — holds what a slice sends one owner; amplicons that share
+// a window key (primers or conserved flanks left on: one key for the whole database) all go to that key's owner, and a
+// slice of more than the region's records then overflows it (n > 8192 at two ranks, > 6144 at three).  Nothing of the
+// attempt is used afterwards: the counts are on this stack, m->routed is written anew by the next attempt, and the
+// streamed build starts from a cleared index under the same ownership and the same sampled windows.
 static int routed_index_build(swa_multi * m, std::vector<int> & dup, bool * routed) {
   const int world = (int)m->ctx.size();
   const uint32_t n = m->ctx[0]->db.n;
@@ -220,7 +233,7 @@ static int routed_index_build(swa_multi * m, std::vector<int> & dup, bool * rout
     return (int)SWA_OK;
   });
   if (rc != SWA_OK) { return rc; }
-  for (int r = 0; r < world; ++r) { if (cnt[(size_t)r][lists] != 0) { return SWA_OK; } }
+  for (int r = 0; r < world; ++r) { if (cnt[(size_t)r][lists] != 0) { m->last_build = SWA_MULTI_BUILD_OVERFLOWED; return SWA_OK; } }
   // rank r receives, per index, the lists of the sources in rank order: inbox[r] = [index 0: s = 0, 1, ..][index 1: ..]
   std::vector<uint32_t> m0((size_t)world, 0), m1((size_t)world, 0);
   for (int r = 0; r < world; ++r) {
@@ -260,6 +273,7 @@ static int routed_index_build(swa_multi * m, std::vector<int> & dup, bool * rout
     }
   }
   *routed = true;
+  m->last_build = SWA_MULTI_BUILD_ROUTED;
   return on_all(m, [&](int r) {
     swa_ctx * c = m->ctx[(size_t)r];
     const uint64_t * in = static_cast<const uint64_t *>(m->inbox[(size_t)r].ptr);
@@ -273,6 +287,7 @@ static int d1_network_on_root(swa_multi * m, int no_cluster_breaking, bool resid
                               uint64_t * total, int * has_duplicates) {
   const int world = (int)m->ctx.size();
   const uint32_t n = m->ctx[0]->db.n;
+  m->last_build = SWA_MULTI_BUILD_NONE;
   if (n == 0) { return fail(m, SWA_E_ARG, "swa_multi_d1_network: no database"); }
   m->ctx[0]->res.csr_ready = false;                            // (whatever fails below: no resident network on rank 0)
   m->ctx[0]->res.cluster_ready = false;
@@ -290,6 +305,8 @@ static int d1_network_on_root(swa_multi * m, int no_cluster_breaking, bool resid
       if (has_duplicates != nullptr) { *has_duplicates = 0; for (int d : dup) { *has_duplicates |= d; } }
       return rc;
     }
+  } else {
+    m->last_build = SWA_MULTI_BUILD_STREAMED;
   }
   rc = on_all(m, [&](int r) {
     swa_ctx * c = m->ctx[(size_t)r];
@@ -374,6 +391,8 @@ extern "C" int swa_multi_d1_network_resident(swa_multi * m, int no_cluster_break
   if (m == nullptr || total == nullptr) { return SWA_E_ARG; }
   return d1_network_on_root(m, no_cluster_breaking, true, nullptr, nullptr, 0, total, has_duplicates);
 }
+
+extern "C" int swa_multi_d1_last_build(const swa_multi * m) { return m != nullptr ? m->last_build : SWA_MULTI_BUILD_NONE; }
 
 // B2 on all GPUs: heavy amplicons split over the ranks, graft_cand combined with MIN, heavy counters summed
 extern "C" int swa_multi_d1_fastidious(swa_multi * m, const uint8_t * is_light, uint64_t light_nt, uint32_t bloom_bits,
@@ -598,8 +617,7 @@ static int dn_graph_on_root(swa_multi * m, int no_cluster_breaking, bool residen
       ma.keys = keys; ma.vals = vals; ma.world = (uint32_t)world;
       for (int r = 0; r <= world; ++r) { ma.at[r] = at[(size_t)r]; }
       ma.out_keys = keys + all + 1; ma.out_vals = vals + all + 1;
-      hipLaunchKernelGGL(k_merge_sorted_lists, dim3(swa_grid256(c0, all)), dim3(256), 0, c0->stream, ma);
-      SWA_HIP(c0, hipGetLastError());
+      SWA_TRY(launch_merge(c0, ma));
     }
     const unsigned long long * sorted = all != 0 ? keys + all + 1 : nullptr;
     const uint32_t * svals = all != 0 ? vals + all + 1 : nullptr;
@@ -637,4 +655,45 @@ extern "C" int swa_multi_dn_graph_totals(swa_multi * m, uint64_t * out3) {
     out3[0] += t[0]; out3[1] += t[1]; out3[2] = std::max(out3[2], t[2]);
   }
   return SWA_OK;
+}
+
+// debug entry: k_merge_sorted_lists on lists from the host, launched as dn_graph_on_root launches it
+extern "C" int swa_merge_sorted_lists(swa_ctx * ctx, const uint64_t * keys, const uint32_t * vals, const uint64_t * at, uint32_t world,
+                                      uint64_t * out_keys, uint32_t * out_vals) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  if (world < 1 || world > 64) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_merge_sorted_lists: world outside 1 .. 64"); }
+  if (at == nullptr || at[0] != 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_merge_sorted_lists: at[0] must be 0"); }
+  for (uint32_t r = 0; r < world; ++r) {
+    if (at[r + 1] < at[r]) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_merge_sorted_lists: at[] descends"); }
+  }
+  const uint64_t all = at[world];
+  if (all == 0) { return SWA_OK; }
+  if (keys == nullptr || vals == nullptr || out_keys == nullptr || out_vals == nullptr) {
+    return swa_fail_msg(ctx, SWA_E_ARG, "swa_merge_sorted_lists: null buffer");
+  }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  // [all keys | merged keys] and [all values | merged values], as rank 0 lays them out
+  swa_dbuf kbuf, vbuf;
+  auto run = [&]() -> int {
+    SWA_TRY(swa_reserve(ctx, kbuf, (2 * all + 2) * sizeof(uint64_t)));
+    SWA_TRY(swa_reserve(ctx, vbuf, (2 * all + 2) * sizeof(uint32_t)));
+    auto * dk = static_cast<unsigned long long *>(kbuf.ptr);
+    auto * dv = static_cast<uint32_t *>(vbuf.ptr);
+    SWA_HIP(ctx, hipMemcpyAsync(dk, keys, all * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    SWA_HIP(ctx, hipMemcpyAsync(dv, vals, all * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    MergeArgs ma{};
+    ma.keys = dk; ma.vals = dv; ma.world = world;
+    for (uint32_t r = 0; r <= world; ++r) { ma.at[r] = at[r]; }
+    ma.out_keys = dk + all + 1; ma.out_vals = dv + all + 1;
+    SWA_TRY(launch_merge(ctx, ma));
+    SWA_HIP(ctx, hipMemcpyAsync(out_keys, ma.out_keys, all * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SWA_HIP(ctx, hipMemcpyAsync(out_vals, ma.out_vals, all * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SWA_OK;
+  };
+  const int rc = run();
+  if (rc != SWA_OK) { (void)hipStreamSynchronize(ctx->stream); }
+  swa_release(kbuf);
+  swa_release(vbuf);
+  return rc;
 }
