@@ -421,7 +421,9 @@ int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]);
    Integer sums, minima and maxima only: every result is independent of scheduling.
    What ends what: an upload, index build, network or clustering call ends all of it (as for swa_d1_cluster_fetch).
    swa_d1_fastidious, _shard and _resident leave the clustering and the sums in place (they work in buffers of their own)
-   and replace the candidates; swa_derep ends the candidates.
+   and replace the candidates; swa_derep ends the candidates.  Whatever ends or replaces the candidates — a caller's
+   candidates handed to swa_d1_graft_device included — ends the grafts made from them and their layout
+   (swa_d1_graft_layout_device), and so does the start of every swa_d1_graft_device call.
 
    swa_d1_swarm_sums_device (src/algod1.cc:1232-1257, where the reference adds them up while it clusters): per swarm, in
    swarm order, the sum of the members' abundances, of their lengths, the members of abundance 1 and the deepest
@@ -449,7 +451,18 @@ int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]);
    NULL).  The candidates of the children that did not win are withdrawn (SWA_NO_AMPLICON) in HBM, and the heavy swarms'
    sums grow by their light swarms' mass, length and singletons (the deepest generation stays, like the reference).  A
    further call starts from the swarms' own sums again.
-   swa_d1_graft_candidates_fetch: the n candidates as they lie in HBM (after swa_d1_graft_device: the winners'). */
+   swa_d1_graft_candidates_fetch: the n candidates as they lie in HBM (after swa_d1_graft_device: the winners').
+   swa_d1_graft_layout_device: the grafted clustering as ONE layout, made from the grafts a completed swa_d1_graft_device
+   left in HBM (SWA_E_ARG without one; G = 0 is one, and the layout is then the clustering's own).  With own[s] the members
+   of swarm s before grafting: attached[s] = 1 iff s is some graft's light swarm; grown[s] = own[s] for an attached swarm,
+   else own[s] plus own of the light swarms it won; the printed swarms are the unattached ones, in swarm order;
+   printed_order[n] holds, for every printed swarm, its own members in the order of swarm_members, then the members of
+   each light swarm of its chain, in chain order; new_begin[s], for EVERY swarm, is where the own members of s begin in
+   printed_order — a printed swarm with everything grafted is printed_order[new_begin[s], new_begin[s] + grown[s]), its
+   own members the first own[s] of them.  summary3 = {w - G, the largest grown among the printed swarms, G}.  Integer
+   scans and one scatter; any output may be NULL and the arrays stay in HBM either way; SWA_E_CAPACITY when nswarms (the
+   entries of the per-swarm arrays) is below the number of swarms.  A second call returns the same arrays.
+   swa_d1_graft_layout_info: out4 = {1 when a layout is in place else 0, and then: amplicons, swarms, grafts}; no device. */
 int swa_d1_swarm_sums_device(swa_ctx * ctx, uint64_t * mass, uint64_t * sumlen, uint32_t * singletons, uint32_t * maxgen,
                              uint32_t nswarms);
 int swa_d1_light_flags_device(swa_ctx * ctx, uint64_t boundary, uint8_t * is_light, uint64_t stats5[5]);
@@ -457,6 +470,9 @@ int swa_d1_fastidious_resident(swa_ctx * ctx, uint64_t light_nt, uint32_t bloom_
 int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, uint32_t * heavy_swarm, uint32_t * light_swarm,
                         uint32_t * parent, uint32_t * child, uint32_t cap, uint32_t * grafts);
 int swa_d1_graft_candidates_fetch(swa_ctx * ctx, uint32_t * graft_cand);
+int swa_d1_graft_layout_device(swa_ctx * ctx, uint32_t * printed_order, uint32_t * new_begin, uint32_t * grown,
+                               uint8_t * attached, uint32_t nswarms, uint64_t summary3[3]);
+int swa_d1_graft_layout_info(const swa_ctx * ctx, uint64_t out4[4]);
 /* Shard owners: who expands which heavy amplicon when the second pass is divided among S shards (swa_d1_fastidious_shard:
    shard s takes the heavy amplicons whose ordinal h among the H heavy ones, in amplicon order, lies in
    [floor(H s / S), floor(H (s + 1) / S))).  swa_d1_shard_owners_device makes, from the flags of the last

@@ -88,6 +88,20 @@ uint32_t swa_d1_graft(swa_d1_result * res, const uint32_t * graft_cand);
    does not have, a light swarm listed twice, attached already or with a chain of its own, a heavy swarm that is attached. */
 int  swa_d1_result_install_graft(swa_d1_result * res, const uint32_t * heavy_swarm, const uint32_t * light_swarm,
                                  const uint32_t * parent, const uint32_t * child, uint32_t grafts);
+/* The same from the layout swa_d1_graft_layout_device left in the context's HBM, with no per-graft array on the host, no
+   chain and no one-thread pass: the printed member order is downloaded into the result's own member order (one DMA after
+   swa_d1_result_prepare), the three per-swarm arrays beside it, and one loop over the swarms, by all threads, sets every
+   swarm's bounds [begin, begin + grown), the end of its own members, its size and whether it is attached; the largest
+   swarm and the swarm count come from the layout's summary.  The writers print the same bytes.  On a result whose details
+   are still in HBM nothing else is fetched; when the details are asked for, mass, length and singletons are summed over a
+   swarm's whole range, the deepest generation over its own members (the reference leaves a heavy swarm's alone), and
+   graft_cand comes from swa_d1_graft_candidates_fetch (the winners').  SWA_E_ARG, a text in swa_d1_result_error and a result
+   left as it was when the context holds no layout, the layout is of another n or number of swarms, or the result holds grafts
+   already.  What ends the layout (swarm_amd.h: what ends what) must not happen before the details are fetched.
+   swa_d1_result_graft_route: how the result's grafts came — 0 none, 1 swa_d1_graft, 2 swa_d1_result_install_graft,
+   3 swa_d1_result_adopt_layout. */
+int  swa_d1_result_adopt_layout(swa_d1_result * res, swa_ctx * ctx);
+uint32_t swa_d1_result_graft_route(const swa_d1_result * res);
 /* how often swarm id, generation and parent were downloaded for this result (0 for a plain -o run, with or without -f) */
 uint32_t swa_d1_result_detail_fetches(const swa_d1_result * res);
 /* writers (path "-" = stdout): -o/-r, -s, -i, -w, -j  (src/algod1.cc:755-1062) */

@@ -84,6 +84,7 @@ EXPORTS = [
     "swa_d1_write_stats", "swa_d1_write_structure", "swa_d1_write_seeds", "swa_d1_write_network",
     "swa_d1_swarm_sums_device", "swa_d1_light_flags_device", "swa_d1_fastidious_resident", "swa_d1_graft_device",
     "swa_d1_graft_candidates_fetch", "swa_d1_result_install_graft", "swa_d1_result_detail_fetches",
+    "swa_d1_graft_layout_device", "swa_d1_graft_layout_info", "swa_d1_result_adopt_layout", "swa_d1_result_graft_route",
     "swa_d1_network_fetch_diffs", "swa_d1_shard_owners_device", "swa_d1_shard_owner_for", "swa_d1_shard_owner_plan",
     "swa_multi_d1_network_resident", "swa_multi_d1_fastidious_resident", "swa_multi_dn_graph_resident",
     "swa_multi_d1_last_build", "swa_merge_sorted_lists",
@@ -144,6 +145,11 @@ def load_library() -> C.CDLL:
     lib.swa_d1_graft_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, u32p]
     lib.swa_d1_graft_candidates_fetch.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_result_install_graft.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.swa_d1_graft_layout_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.swa_d1_graft_layout_info.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_result_adopt_layout.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_result_graft_route.argtypes = [C.c_void_p]
+    lib.swa_d1_result_graft_route.restype = C.c_uint32
     lib.swa_d1_shard_owners_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p]
     lib.swa_d1_shard_owner_for.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, u32p]
     lib.swa_merge_sorted_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -464,6 +470,18 @@ class D1Clusters:
         rc = self.lib.swa_d1_result_install_graft(self.h, *(_ptr(a) if len(a) else None for a in four), len(four[0]))
         if rc != SWA_OK:
             raise SwaError(rc, "swa_d1_result_install_graft failed: " + self.lib.swa_d1_result_error(self.h).decode())
+
+    def adopt_layout(self, ctx: "Context") -> None:
+        """swa_d1_result_adopt_layout: the layout Context.d1_graft_layout_device left in HBM becomes the result's member order
+        and bounds — no chain, no per-graft array; the writers print what they print after graft() / install_graft().  A
+        lazy result keeps needing its context."""
+        rc = self.lib.swa_d1_result_adopt_layout(self.h, ctx.h)
+        if rc != SWA_OK:
+            raise SwaError(rc, "swa_d1_result_adopt_layout failed: " + self.lib.swa_d1_result_error(self.h).decode())
+
+    def graft_route(self) -> int:
+        """swa_d1_result_graft_route: 0 no grafts, 1 graft(), 2 install_graft(), 3 adopt_layout()"""
+        return int(self.lib.swa_d1_result_graft_route(self.h))
 
     def detail_fetches(self) -> int:
         """swa_d1_result_detail_fetches: downloads of swarm id / generation / parent made for this result"""
@@ -965,11 +983,15 @@ class Context:
     def d1_graft_device(self, graft_cand=None, cap: int | None = None):
         """swa_d1_graft_device: (heavy swarm, light swarm, parent, child) of the G grafts in chain order.  graft_cand: n
         candidates on the host, or None for those the last fastidious pass left in HBM.  cap: entries of the result arrays
-        (default: asked for first); SwaError(SWA_E_CAPACITY) whose `grafts` is the need when it is too small."""
+        (default: asked for first); SwaError(SWA_E_CAPACITY) whose `grafts` is the need when it is too small.  cap = 0: no
+        arrays are wanted — the grafts stay in HBM for d1_graft_layout_device, four empty arrays come back."""
         cand = None if graft_cand is None else np.ascontiguousarray(graft_cand, dtype=np.uint32)
         if cand is not None and len(cand) != self.n:
             raise ValueError("d1_graft_device: one candidate per amplicon of the resident database")
         made = C.c_uint32(0)
+        if cap is not None and int(cap) == 0:
+            self._check(self.lib.swa_d1_graft_device(self.h, _ptr(cand), None, None, None, None, 0, C.byref(made)))
+            return tuple(np.zeros(0, dtype=np.uint32) for _ in range(4))
         if cap is None:
             rc = self._check(self.lib.swa_d1_graft_device(self.h, _ptr(cand), None, None, None, _ptr(np.zeros(1, dtype=np.uint32)), 0,
                                                           C.byref(made)), allow=(SWA_E_CAPACITY,))
@@ -983,6 +1005,34 @@ class Context:
             err.grafts = int(made.value)
             raise err
         return tuple(a[:made.value] for a in four)
+
+    def d1_graft_layout_info(self) -> dict:
+        """swa_d1_graft_layout_info: whether a layout is in place, and of how many amplicons, swarms and grafts"""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.swa_d1_graft_layout_info(self.h, _ptr(out)))
+        return {"in_place": bool(out[0]), "n": int(out[1]), "swarms": int(out[2]), "grafts": int(out[3])}
+
+    def d1_graft_layout_device(self, fetch: bool = True, nswarms: int | None = None) -> dict:
+        """swa_d1_graft_layout_device: the grafted clustering laid out in HBM from the grafts of the last d1_graft_device call.
+        {"printed_order": u32[n], "new_begin": u32[w], "grown": u32[w], "attached": u8[w] (all None when fetch is False),
+        "summary": [printed swarms, largest printed swarm, grafts]}.  nswarms: entries of the per-swarm arrays (default:
+        the swarms of the clustering; fewer: SwaError(SWA_E_CAPACITY))."""
+        summary = np.zeros(3, dtype=np.uint64)
+        if nswarms is None or not fetch:
+            self._check(self.lib.swa_d1_graft_layout_device(self.h, None, None, None, None, 0xFFFFFFFF if nswarms is None else int(nswarms), _ptr(summary)))
+            if nswarms is None:
+                nswarms = self.d1_graft_layout_info()["swarms"]
+        out = {"printed_order": None, "new_begin": None, "grown": None, "attached": None}
+        if fetch:
+            room = max(int(nswarms), 1)
+            out = {"printed_order": np.zeros(self.n, dtype=np.uint32), "new_begin": np.zeros(room, dtype=np.uint32),
+                   "grown": np.zeros(room, dtype=np.uint32), "attached": np.zeros(room, dtype=np.uint8)}
+            self._check(self.lib.swa_d1_graft_layout_device(self.h, _ptr(out["printed_order"]), _ptr(out["new_begin"]), _ptr(out["grown"]),
+                                                            _ptr(out["attached"]), int(nswarms), _ptr(summary)))
+            for k in ("new_begin", "grown", "attached"):
+                out[k] = out[k][:int(nswarms)]
+        out["summary"] = [int(v) for v in summary]
+        return out
 
     def d1_graft_candidates(self) -> np.ndarray:
         """swa_d1_graft_candidates_fetch: the candidates as they lie in HBM (after d1_graft_device: the winners' only)"""

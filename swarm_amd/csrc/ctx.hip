@@ -169,7 +169,7 @@ extern "C" void swa_ctx_destroy(swa_ctx * ctx) {
                        &ctx->d_aitems[0], &ctx->d_aitems[1],
                        &ctx->d_frole, &ctx->d_fkeys, &ctx->d_fcnt, &ctx->d_foff, &ctx->d_fslot, &ctx->d_fmembers, &ctx->d_fitems,
                        &ctx->d_fpairs, &ctx->d_dn_keys, &ctx->d_dn_vals, &ctx->d_cluster, &ctx->d_cluster_ctl, &ctx->d_words_stage,
-                       &ctx->d_swarm_sums, &ctx->d_swarm_role, &ctx->d_graft_work, &ctx->d_shard_owner, &ctx->d_dn_tables, &ctx->d_d0, &ctx->d_d0_tab,
+                       &ctx->d_swarm_sums, &ctx->d_swarm_role, &ctx->d_graft_work, &ctx->d_graft_layout, &ctx->d_shard_owner, &ctx->d_dn_tables, &ctx->d_d0, &ctx->d_d0_tab,
                        &ctx->d_nw_ids, &ctx->d_nw_lists, &ctx->d_nw_res, &ctx->d_nw_text, &ctx->d_nw_gather, &ctx->d_nw_bits}) {
     swa_release(*b);
   }

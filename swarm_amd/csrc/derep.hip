@@ -97,7 +97,7 @@ extern "C" int swa_derep_resident(swa_ctx * ctx) {
   SWA_TRY(swa_reserve(ctx, ctx->d_counts, tsize * sizeof(uint32_t)));                 // minimum claimant per slot
   SWA_TRY(swa_reserve(ctx, ctx->d_cursor, uint64_t(n) * sizeof(uint32_t)));           // slot of every amplicon
   SWA_TRY(swa_reserve(ctx, ctx->d_graft, uint64_t(n) * sizeof(uint32_t)));            // result
-  ctx->res.fast.cand_ready = false;                         // (d_graft no longer holds graft candidates)
+  ctx->res.fast.candidates_end();                           // (d_graft no longer holds graft candidates)
   SWA_TRY(swa_reserve(ctx, ctx->d_list_a, uint64_t(n) * sizeof(uint32_t)));
   SWA_TRY(swa_reserve(ctx, ctx->d_list_b, uint64_t(n) * sizeof(uint32_t)));
   ctx->ix.table_repurposed();                             // d_table becomes the key table

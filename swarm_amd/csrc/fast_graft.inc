@@ -17,6 +17,13 @@
 //   rocPRIM           winners by (heavy swarm, pair): a radix sort on the pair, a stable one on the heavy swarm's bits
 //   k_graft_apply     light swarm / parent / child of every graft in chain order; the heavy swarms' sums grown by their
 //                     lights', a wave's run of one heavy swarm reduced first in the same way
+//   k_layout_grafts   the grafted clustering as one layout (swa_d1_graft_layout_device), from those arrays: the light swarms
+//                     marked attached, their sizes in chain order, where every heavy swarm's run of grafts begins and ends
+//   rocPRIM           an exclusive scan of those sizes (E)
+//   k_layout_grown    grown[s] = own[s] + E[end of its run] - E[start of it]; the largest printed swarm
+//   rocPRIM           an exclusive scan of the printed swarms' grown sizes: where each begins in the printed order
+//   k_layout_lights   where every light swarm begins: behind its heavy swarm's own members and the lights before it in the chain
+//   k_layout_move     printed_order[new_begin[swarm] + place in the swarm] = member, one thread a member position
 // Integer sums, minima and maxima only: every result is independent of scheduling.
 
 namespace {
@@ -162,6 +169,90 @@ __global__ __launch_bounds__(256) void k_graft_apply(const uint32_t * __restrict
     const swa_run run = swa_wave_run_reduce(h, r);            // (every lane takes part)
     if (i >= grafts || !run.last) { continue; }
     atomicAdd(&sums.mass[h], r.mass); atomicAdd(&sums.sumlen[h], r.len); atomicAdd(&sums.singles[h], r.singles);   // (maxgen untouched, like the reference)
+  }
+}
+
+// ---- the grafted clustering as one layout -----------------------------------------------------------------------------------
+// The chain a heavy swarm's light swarms form says in which order the members are printed: a permutation of the member order,
+// fixed by the grafts in chain order (heavy[0], light_out).  With own[s] = begins[s + 1] - begins[s] and E the exclusive scan of
+// own[light[i]] over the grafts (E[G] = their total):
+//   grown[h]            = own[h] + E[end of h's run of grafts] - E[start of it]       (a swarm without grafts: own[h])
+//   new_begin[printed]  = the exclusive scan over the swarms of (attached ? 0 : grown)
+//   new_begin[light[i]] = new_begin[h] + own[h] + E[i] - E[start of h's run]          (h = heavy[i])
+//   printed_order[new_begin[s] + k - begins[s]] = order[k]                            (s = swarm of the member at position k)
+// d_graft_layout, w swarms of n amplicons; n and the scans' room are set before lay() runs.  rocPRIM's room comes first (it has
+// the buffer's own alignment); one fill clears the runs' bounds, the largest printed swarm and the attached bytes (`cleared`).
+struct GraftLayout {
+  uint64_t n = 0, tmp_bytes = 0;
+  unsigned long long * tmp = nullptr;
+  uint32_t * printed_order = nullptr, * new_begin = nullptr, * grown = nullptr, * scan_in = nullptr, * sizes = nullptr, * ends = nullptr;
+  uint32_t * run_first = nullptr, * run_end = nullptr, * largest = nullptr;
+  uint8_t * attached = nullptr;
+  swa_extent cleared{nullptr, 0};
+  void lay(swa_carver & c, uint64_t w) {
+    c.take((tmp_bytes + 7u) / 8u, tmp);
+    c.take(n, printed_order);
+    c.take(w, new_begin, grown, scan_in);
+    c.take(w + 1u, sizes, ends);                             // (entry G of the sizes is 0: ends[G] = the total)
+    c.take(w, run_first, run_end);
+    c.take(1, largest);
+    c.take(w, attached);
+    cleared = c.extent(run_first);
+    c.spare(64);
+  }
+};
+
+// graft i hangs light swarm light[i] on heavy[i]; the grafts of one heavy swarm are a run [run_first, run_end) of the arrays
+// (both 0 for a swarm without one: cleared before the launch).  Position G closes the sizes.
+__global__ __launch_bounds__(256) void k_layout_grafts(const uint32_t * __restrict__ heavy, const uint32_t * __restrict__ light,
+                                                       const uint32_t * __restrict__ begins, uint32_t grafts, GraftLayout out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= grafts; i += (uint64_t)gridDim.x * blockDim.x) {
+    if (i == grafts) { out.sizes[i] = 0; continue; }
+    const uint32_t h = heavy[i], l = light[i];
+    out.attached[l] = 1;
+    out.sizes[i] = begins[l + 1u] - begins[l];
+    if (i == 0 || heavy[i - 1u] != h) { out.run_first[h] = (uint32_t)i; }
+    if (i + 1u == grafts || heavy[i + 1u] != h) { out.run_end[h] = (uint32_t)i + 1u; }
+  }
+}
+
+// grown[s], what the scan over the printed swarms adds up, and *largest = the most members a printed swarm has (a maximum a wave)
+__global__ __launch_bounds__(256) void k_layout_grown(const uint32_t * __restrict__ begins, uint32_t nswarms, GraftLayout out) {
+  uint32_t most = 0;
+  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nswarms; s += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = begins[s + 1u] - begins[s] + out.ends[out.run_end[s]] - out.ends[out.run_first[s]];
+    const uint32_t printed = out.attached[s] != 0 ? 0u : g;
+    out.grown[s] = g;
+    out.scan_in[s] = printed;
+    most = printed > most ? printed : most;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const uint32_t other = __shfl_xor(most, d, 64);
+    most = other > most ? other : most;
+  }
+  if ((threadIdx.x & 63u) == 0u && most != 0u) { atomicMax(out.largest, most); }
+}
+
+// (new_begin of a heavy swarm is read, that of its light swarms written: no light swarm is anybody's heavy swarm)
+__global__ __launch_bounds__(256) void k_layout_lights(const uint32_t * __restrict__ heavy, const uint32_t * __restrict__ light,
+                                                       const uint32_t * __restrict__ begins, uint32_t grafts, GraftLayout out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < grafts; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t h = heavy[i];
+    out.new_begin[light[i]] = out.new_begin[h] + (begins[h + 1u] - begins[h]) + out.ends[i] - out.ends[out.run_first[h]];
+  }
+}
+
+// one thread a member position: coalesced reads of the order, an even load whatever the swarms' sizes
+__global__ __launch_bounds__(256) void k_layout_move(const uint32_t * __restrict__ order, const uint32_t * __restrict__ sid,
+                                                     const uint32_t * __restrict__ begins, const uint32_t * __restrict__ new_begin, uint32_t n,
+                                                     uint32_t * __restrict__ printed_order) {
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t a = order[k], s = sid[a];
+    const uint32_t at = new_begin[s] + ((uint32_t)k - begins[s]);
+    // (always so for grafts as swa_d1_graft_device makes them from light children and heavy parents; a caller's candidates
+    // that hang a swarm on a swarm that hangs itself lay nothing sensible out, and write nowhere else)
+    if (at < n) { printed_order[at] = a; }
   }
 }
 
@@ -369,6 +460,8 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
     }
   }
   SWA_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->res.fast.grafts_ready = false;                       // (the grafts of the call before, and their layout, end here)
+  ctx->res.fast.layout_ready = false;
   if (ctx->res.fast.sums_grafted) { ctx->res.fast.sums_ready = false; ctx->res.fast.sums_grafted = false; }   // (every call grows the swarms' own sums)
   SwarmSums sums;
   SWA_TRY(ensure_swarm_sums(ctx, sums));
@@ -384,7 +477,7 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
   const size_t tmp_bytes = std::max(asked[0], asked[1]);
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_hits, tmp_bytes + 16));
   if (graft_cand != nullptr) {
-    ctx->res.fast.cand_ready = false;
+    ctx->res.fast.candidates_end();
     SWA_HIP(ctx, hipMemcpyAsync(cand, graft_cand, (uint64_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   }
   swa_cluster_arrays cl;
@@ -401,7 +494,8 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
   ctx->res.fast.cand_ready = true;
   const uint32_t made = (uint32_t)winners;
   *grafts = made;
-  if (made == 0) { return SWA_OK; }
+  ctx->res.fast.grafts = made;
+  if (made == 0) { ctx->res.fast.grafts_ready = true; return SWA_OK; }
   const bool wanted = heavy_swarm != nullptr || light_swarm != nullptr || parent != nullptr || child != nullptr;
   // (before the sums grow: the call with room starts from the same candidates — the winners keep theirs — and the same sums)
   if (wanted && made > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_graft_device: result arrays too small"); }
@@ -414,8 +508,65 @@ extern "C" int swa_d1_graft_device(swa_ctx * ctx, const uint32_t * graft_cand, u
                      gw.child_out, sums);
   SWA_HIP(ctx, hipGetLastError());
   ctx->res.fast.sums_grafted = true;
+  ctx->res.fast.grafts_ready = true;                        // (in chain order in d_graft_work: swa_d1_graft_layout_device)
   const uint64_t bytes = (uint64_t)made * sizeof(uint32_t);
   return swa_download(ctx, {{heavy_swarm, gw.heavy[0], bytes}, {light_swarm, gw.light_out, bytes}, {parent, gw.parent_out, bytes}, {child, gw.child_out, bytes}});
+}
+
+// The grafted clustering laid out in HBM (GraftLayout above): the member order as the writers print it — every printed swarm's
+// own members, then those of the light swarms of its chain, in chain order —, where every swarm's own members begin in it,
+// how many members it has with everything grafted, whether it hangs on another.  Needs a completed swa_d1_graft_device (G = 0:
+// the layout is the clustering's own); made once, a second call downloads the same arrays.  Any output may be null.
+extern "C" int swa_d1_graft_layout_device(swa_ctx * ctx, uint32_t * printed_order, uint32_t * new_begin, uint32_t * grown, uint8_t * attached,
+                                          uint32_t nswarms, uint64_t summary3[3]) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  SWA_TRY(need_clustering(ctx, "swa_d1_graft_layout_device"));
+  if (!ctx->res.fast.grafts_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_graft_layout_device: no grafts in place (a completed swa_d1_graft_device)"); }
+  const uint32_t n = ctx->db.n, w = ctx->res.cluster_nswarms, made = ctx->res.fast.grafts;
+  if (nswarms < w) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_graft_layout_device: the arrays hold fewer entries than there are swarms"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  GraftLayout gl;
+  gl.n = n;
+  size_t asked = 0;                                         // (both scans are of w + 1 entries at most)
+  (void)rocprim::exclusive_scan(nullptr, asked, gl.sizes, gl.ends, 0u, (size_t)w + 1u, rocprim::plus<uint32_t>(), ctx->stream);
+  gl.tmp_bytes = asked;
+  if (!ctx->res.fast.layout_ready) {
+    SWA_TRY(swa_carve(ctx, ctx->d_graft_layout, w, true, gl));
+    GraftWork gw;
+    SWA_TRY(swa_carve(ctx, ctx->d_graft_work, w, false, gw));
+    swa_cluster_arrays cl;
+    SWA_TRY(cluster_arrays(ctx, cl));
+    const dim3 b(256);
+    SWA_HIP(ctx, hipMemsetAsync(gl.cleared.ptr, 0, gl.cleared.bytes, ctx->stream));
+    hipLaunchKernelGGL(k_layout_grafts, dim3(swa_grid256(ctx, (uint64_t)made + 1u)), b, 0, ctx->stream, gw.heavy[0], gw.light_out, cl.begins, made, gl);
+    size_t need = asked;
+    SWA_HIP(ctx, rocprim::exclusive_scan(gl.tmp, need, gl.sizes, gl.ends, 0u, (size_t)made + 1u, rocprim::plus<uint32_t>(), ctx->stream));
+    hipLaunchKernelGGL(k_layout_grown, dim3(swa_grid256(ctx, w)), b, 0, ctx->stream, cl.begins, w, gl);
+    need = asked;
+    SWA_HIP(ctx, rocprim::exclusive_scan(gl.tmp, need, gl.scan_in, gl.new_begin, 0u, (size_t)w, rocprim::plus<uint32_t>(), ctx->stream));
+    if (made != 0) {
+      hipLaunchKernelGGL(k_layout_lights, dim3(swa_grid256(ctx, made)), b, 0, ctx->stream, gw.heavy[0], gw.light_out, cl.begins, made, gl);
+    }
+    hipLaunchKernelGGL(k_layout_move, dim3(swa_grid256(ctx, n)), b, 0, ctx->stream, cl.order, cl.swarmid, cl.begins, gl.new_begin, n, gl.printed_order);
+    SWA_HIP(ctx, hipGetLastError());
+    uint32_t largest = 0;
+    SWA_TRY(swa_download(ctx, {{&largest, gl.largest, sizeof(largest)}}));
+    ctx->res.fast.layout_largest = largest;
+    ctx->res.fast.layout_ready = true;
+  } else {
+    SWA_TRY(swa_carve(ctx, ctx->d_graft_layout, w, false, gl));
+  }
+  if (summary3 != nullptr) { summary3[0] = w - made; summary3[1] = ctx->res.fast.layout_largest; summary3[2] = made; }
+  const uint64_t w4 = (uint64_t)w * sizeof(uint32_t);
+  return swa_download(ctx, {{printed_order, gl.printed_order, (uint64_t)n * sizeof(uint32_t)}, {new_begin, gl.new_begin, w4}, {grown, gl.grown, w4}, {attached, gl.attached, w}});
+}
+
+// {whether a layout is in place, amplicons and swarms of the clustering it lays out, grafts}; no device
+extern "C" int swa_d1_graft_layout_info(const swa_ctx * ctx, uint64_t out4[4]) {
+  if (ctx == nullptr || out4 == nullptr) { return SWA_E_ARG; }
+  const bool there = ctx->res.cluster_ready && ctx->res.csr_ready && ctx->res.fast.layout_ready;
+  out4[0] = there ? 1u : 0u; out4[1] = there ? ctx->db.n : 0u; out4[2] = there ? ctx->res.cluster_nswarms : 0u; out4[3] = there ? ctx->res.fast.grafts : 0u;
+  return SWA_OK;
 }
 
 // ---- shard owners ------------------------------------------------------------------------------------------------------

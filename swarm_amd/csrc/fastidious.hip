@@ -508,7 +508,7 @@ static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, const
                                  uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters) {
   SWA_TRY(swa_prepare_hashing(ctx));                         // the Zobrist table
   const uint32_t n = ctx->db.n;
-  ctx->res.fast.cand_ready = false;
+  ctx->res.fast.candidates_end();
   // the numbers of the reference's log line (src/algod1.cc:1337-1357, 1383-1403; bloomflex.cc:91-115)
   uint32_t k = static_cast<uint32_t>(0.4 * static_cast<double>(bloom_bits));
   if (k < 1) { k = 1; }

@@ -35,9 +35,12 @@ struct swa_d1_result {
     // list through ampinfo[].next)
     uint32_t graft_head, graft_tail, graft_next;
     uint32_t attached;                      // this (light) swarm hangs on another one
+    // an adopted layout (swa_d1_result_adopt_layout) has no chain: [begin, end) holds the grafted members too, behind the
+    // swarm's own, which end here
+    uint32_t own_end;
   };
   static constexpr Swarm empty_swarm() {
-    return Swarm{0, 0, 0, 0, 0, 0, 0, 0, SWA_NO_AMPLICON, SWA_NO_AMPLICON, SWA_NO_AMPLICON, 0};
+    return Swarm{0, 0, 0, 0, 0, 0, 0, 0, SWA_NO_AMPLICON, SWA_NO_AMPLICON, SWA_NO_AMPLICON, 0, 0};
   }
   swa_vec<Swarm> swarms;
   swa_vec<uint32_t> graft_cand;             // per amplicon, after swa_d1_graft
@@ -55,6 +58,8 @@ struct swa_d1_result {
   // swa_d1_result_install_graft on a result whose details are still lazy: the grafts, folded into the sums and graft_cand
   // when the details are made after all (need_details)
   std::vector<uint32_t> pending_heavy, pending_light, pending_parent, pending_child;
+  // how the grafts came (swa_d1_result_graft_route): 0 none, 1 the host's walk, 2 installed, 3 an adopted layout
+  uint32_t graft_route = 0;
   // swa_d1_result_prepare: order and the download area of the swarms' bounds sized ahead — and pinned, when the runtime agreed
   swa_vec<uint32_t> begin_tmp;
   bool prepared = false, pinned_order = false, pinned_begin = false;
@@ -118,10 +123,17 @@ bool need_details(const swa_d1_result * cr) {
     r->error = swa_last_error(r->lazy_ctx);
     return false;
   }
+  // an adopted layout: the winners' candidates lie in HBM (the losers' withdrawn), and [begin, end) holds the grafted members
+  const bool adopted = r->graft_route == 3;
+  if (adopted && swa_d1_graft_candidates_fetch(r->lazy_ctx, r->graft_cand.data()) != SWA_OK) {
+    r->error = swa_last_error(r->lazy_ctx);
+    return false;
+  }
   const auto & gen = r->generation;
 #pragma omp parallel for schedule(dynamic, 1024) num_threads(swa_host_team())
   for (int64_t s = 0; s < (int64_t)r->swarms.size(); ++s) {
     auto & sw = r->swarms[(size_t)s];
+    const uint32_t own_end = adopted ? sw.own_end : sw.end;   // (the deepest generation is the swarm's own, like the reference)
     for (uint32_t k = sw.begin; k < sw.end; ++k) {
       // (members of consecutive swarms are consecutive in `order`: what the sums read 16 members ahead is asked for now)
       if (k + 16u < n) { const uint32_t f = r->order[k + 16u]; __builtin_prefetch(&db->abundance[f]); __builtin_prefetch(&db->seqlen[f]); __builtin_prefetch(&gen[f]); }
@@ -129,7 +141,7 @@ bool need_details(const swa_d1_result * cr) {
       sw.mass += db->abundance[a];
       sw.sumlen += db->seqlen[a];
       if (db->abundance[a] == 1) { ++sw.singletons; }
-      sw.maxgen = std::max(sw.maxgen, gen[a]);
+      if (k < own_end) { sw.maxgen = std::max(sw.maxgen, gen[a]); }
     }
   }
   ++r->detail_fetches;
@@ -446,6 +458,7 @@ extern "C" int swa_d1_cluster(const swa_hostdb * db, const uint64_t * offsets, c
   *out = r;
   const uint32_t n = db->n;
   r->n = n;
+  r->lazy_db = db;
   fill_parallel(r->swarmid, n, (uint32_t)SWA_NO_AMPLICON);
   fill_parallel(r->parent, n, (uint32_t)SWA_NO_AMPLICON);
   fill_parallel(r->generation, n, 0u);
@@ -643,6 +656,7 @@ static uint32_t graft_sorted_pairs_in_parallel(swa_d1_result * r, const uint64_t
   }
   r->largest = largest;
   r->swarmcount_adjusted -= nwin;
+  r->graft_route = 1;
   return (uint32_t)nwin;
 }
 
@@ -707,6 +721,7 @@ extern "C" uint32_t swa_d1_graft(swa_d1_result * r, const uint32_t * graft_cand)
     --r->swarmcount_adjusted;
     ++grafts;
   }
+  r->graft_route = 1;
   return grafts;
 }
 
@@ -763,8 +778,61 @@ extern "C" int swa_d1_result_install_graft(swa_d1_result * r, const uint32_t * h
     r->largest = std::max(r->largest, heavy.size);
   }
   r->swarmcount_adjusted -= grafts;
+  r->graft_route = 2;
   return SWA_OK;
 }
+
+// The layout swa_d1_graft_layout_device left in HBM adopted as the result's own: the printed member order into `order` (one
+// DMA where swa_d1_result_prepare pinned it), the three per-swarm arrays, one loop over the swarms by all threads.  No chain,
+// no per-graft array, no walk: the writers find a printed swarm's members, grafted ones included, in order[begin, end).
+extern "C" int swa_d1_result_adopt_layout(swa_d1_result * r, swa_ctx * ctx) {
+  if (r == nullptr || ctx == nullptr) { return SWA_E_ARG; }
+  auto refuse = [&](const char * why) { r->error = std::string("swa_d1_result_adopt_layout: ") + why; return SWA_E_ARG; };
+  uint64_t info[4] = {};
+  if (swa_d1_graft_layout_info(ctx, info) != SWA_OK || info[0] == 0) { return refuse("the context holds no layout (swa_d1_graft_layout_device)"); }
+  if (info[1] != r->n || info[2] != r->swarms.size()) { return refuse("the layout is of another clustering than this result"); }
+  if (r->graft_route != 0) { return refuse("the result holds grafts already"); }
+  const size_t w = r->swarms.size();
+  swa_vec<uint32_t> new_begin(w), grown(w);
+  swa_vec<uint8_t> attached(w);
+  // (a result with its details on the host has its sums: the candidates are needed before anything is changed)
+  swa_vec<uint32_t> kept;
+  if (r->details) {
+    kept.resize(r->n);
+    if (swa_d1_graft_candidates_fetch(ctx, kept.data()) != SWA_OK) { r->error = swa_last_error(ctx); return SWA_E_DEVICE; }
+  }
+  uint64_t summary[3] = {};
+  if (swa_d1_graft_layout_device(ctx, r->order.data(), new_begin.data(), grown.data(), attached.data(), (uint32_t)w, summary) != SWA_OK) {
+    r->error = swa_last_error(ctx);
+    return SWA_E_DEVICE;
+  }
+  const bool sums = r->details;                              // (else need_details makes them over [begin, end))
+  const swa_hostdb * db = r->lazy_db;
+#pragma omp parallel for schedule(static) num_threads(swa_host_team())
+  for (int64_t s = 0; s < (int64_t)w; ++s) {
+    auto & sw = r->swarms[(size_t)s];
+    const uint32_t own = sw.end - sw.begin;
+    sw.begin = new_begin[(size_t)s];
+    sw.own_end = sw.begin + own;
+    sw.end = sw.begin + grown[(size_t)s];
+    sw.size = grown[(size_t)s];
+    sw.attached = attached[(size_t)s];
+    if (!sums) { continue; }
+    for (uint32_t k = sw.own_end; k < sw.end; ++k) {
+      const uint32_t a = r->order[k];
+      sw.mass += db->abundance[a];
+      sw.sumlen += db->seqlen[a];
+      if (db->abundance[a] == 1) { ++sw.singletons; }         // maxgen untouched, like the reference
+    }
+  }
+  if (sums) { r->graft_cand.swap(kept); }
+  r->largest = (uint32_t)summary[1];
+  r->swarmcount_adjusted = summary[0];
+  r->graft_route = 3;
+  return SWA_OK;
+}
+
+extern "C" uint32_t swa_d1_result_graft_route(const swa_d1_result * r) { return r == nullptr ? 0u : r->graft_route; }
 
 extern "C" uint32_t swa_d1_result_detail_fetches(const swa_d1_result * r) { return r == nullptr ? 0u : r->detail_fetches; }
 
@@ -783,25 +851,35 @@ extern "C" int swa_d1_write_swarms(const swa_d1_result * r, const swa_hostdb * d
     // pass 1: the ids this piece prints, in printing order, and where every printed swarm ends.  Own members are a run
     // of `order`; grafted light swarms (--fastidious: millions of one-member swarms hung on the heavy ones) are a chain
     // through the swarm table — the next link's record is asked for while this one's members are copied.
-    std::vector<uint32_t> ids, ends;
-    if (begin < end) { ids.reserve((size_t)r->swarms[end - 1].end - r->swarms[begin].begin + 64); ends.reserve(end - begin); }
+    // An adopted layout has no chain and nothing to copy: the printed swarms of a piece are one run of `order`.
+    std::vector<uint32_t> own_ids, ends;
+    const uint32_t * ids = nullptr;
+    const bool adopted = r->graft_route == 3;
+    if (begin < end) { ends.reserve(end - begin); }
+    if (begin < end && !adopted) { own_ids.reserve((size_t)r->swarms[end - 1].end - r->swarms[begin].begin + 64); }
     for (size_t k = begin; k < end; ++k) {
       const auto & s = r->swarms[k];
       if (s.attached != 0) { continue; }
-      ids.insert(ids.end(), order + s.begin, order + s.end);
+      if (adopted) {
+        if (ids == nullptr) { ids = order + s.begin; }
+        ends.push_back((uint32_t)(order + s.end - ids));
+        continue;
+      }
+      own_ids.insert(own_ids.end(), order + s.begin, order + s.end);
       for (uint32_t g = s.graft_head; g != SWA_NO_AMPLICON;) {
         const auto & l = r->swarms[g];
         if (l.graft_next != SWA_NO_AMPLICON) { __builtin_prefetch(&r->swarms[l.graft_next]); }
-        ids.insert(ids.end(), order + l.begin, order + l.end);
+        own_ids.insert(own_ids.end(), order + l.begin, order + l.end);
         g = l.graft_next;
       }
-      ends.push_back((uint32_t)ids.size());
+      ends.push_back((uint32_t)own_ids.size());
     }
+    if (!adopted) { ids = own_ids.data(); }
+    const size_t total = ends.empty() ? 0 : ends.back();
     // pass 2: a member's identifier is three dependent random reads away — its entry pointer, the entry, the header
     // text: what the walk needs 24, 16 and 8 members ahead is asked for now (without that: ~100 ms of cache misses at
     // 10 M amplicons on 16 threads, lease r5f)
-    sink.reserve(std::min<size_t>(ids.size() * (db->longest_header + 2u) + 64, (size_t)8 << 20));
-    const size_t total = ids.size();
+    sink.reserve(std::min<size_t>(total * (db->longest_header + 2u) + 64, (size_t)8 << 20));
     size_t at = 0;
     for (const uint32_t stop : ends) {
       bool first = true;

@@ -521,9 +521,13 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       // One context with the clustering still in HBM (the usual run): sums, flags, candidates and grafting stay on the GPU
       // (swa_d1_light_flags_device .. swa_d1_graft_device) — with several GPUs rank 0's, the second pass shared out from its
       // flags (swa_multi_d1_fastidious_resident).  A clustering made on the host takes the host's bookkeeping;
-      // SWARM_AMD_FASTIDIOUS=host selects it for comparison.
+      // SWARM_AMD_FASTIDIOUS=host selects it for comparison.  The grafts do not come home: the grafted clustering is laid out
+      // in HBM and the result adopts it (swa_d1_graft_layout_device, swa_d1_result_adopt_layout; =layout, the default by
+      // measurement: profiles/r25/NOTES.md).  =install keeps the route before it for comparison: four arrays of G entries
+      // downloaded and installed into the result by one thread (swa_d1_result_install_graft).
       const char * fast_route = std::getenv("SWARM_AMD_FASTIDIOUS");
       const bool on_device = resident && !(fast_route != nullptr && std::strcmp(fast_route, "host") == 0);
+      const bool by_layout = on_device && !(fast_route != nullptr && std::strcmp(fast_route, "install") == 0);
       swa_vec<uint8_t> is_light(on_device ? 0 : n);         // (every entry is written by swa_d1_light_flags: each amplicon is in one swarm)
       uint64_t st[5];
       if (on_device) { if (swa_d1_light_flags_device(ctx, (uint64_t)o.boundary, nullptr, st) != SWA_OK) { die(swa_last_error(ctx)); } }
@@ -581,7 +585,13 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
         std::fprintf(g_log, "Heavy variants: %" PRIu64 "\n", counters[1]);
         std::fprintf(g_log, "Got %" PRIu64 " graft candidates\n", counters[2]);
         uint32_t grafts = 0;
-        if (on_device) {
+        if (by_layout) {
+          if (swa_d1_graft_device(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &grafts) != SWA_OK) { die(swa_last_error(ctx)); }
+          if (swa_d1_graft_layout_device(ctx, nullptr, nullptr, nullptr, nullptr, (uint32_t)sum[3], nullptr) != SWA_OK) { die(swa_last_error(ctx)); }
+          stamp("grafts laid out on the device");
+          const int adopted = swa_d1_result_adopt_layout(res, ctx);
+          if (adopted != SWA_OK) { die(swa_d1_result_error(res)); }
+        } else if (on_device) {
           // (a graft needs a candidate and a light swarm of its own: never more than either)
           const uint32_t room = (uint32_t)std::min<uint64_t>(counters[2], st[0]);
           swa_vec<uint32_t> chain((size_t)room * 4);

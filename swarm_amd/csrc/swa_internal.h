@@ -240,6 +240,12 @@ struct swa_resident {
     bool owners_ready = false;                 // d_shard_owner: the owner byte of every amplicon, made from d_swarm_role (swa_d1_shard_owners_device)
     uint32_t owners_shards = 0;                // ... for so many shards,
     uint64_t owners_heavy = 0;                 // and how many heavy amplicons it counted
+    bool grafts_ready = false;                 // d_graft_work: the grafts of a completed swa_d1_graft_device, in chain order,
+    uint32_t grafts = 0;                       // ... so many of them (0: the call made none)
+    bool layout_ready = false;                 // d_graft_layout: the grafted clustering laid out (swa_d1_graft_layout_device),
+    uint32_t layout_largest = 0;               // ... and the members of its largest printed swarm
+    // what ends the candidates ends the grafts made from them and their layout (as does the next swa_d1_graft_device call)
+    void candidates_end() { cand_ready = false; grafts_ready = false; layout_ready = false; }
   } fast;
   // what the d >= 2 graph route derives from the clustering in place and keeps in HBM (dn_tables.inc): every member's radius,
   // the deepest radius of every swarm, the -i links in acceptance order; ended with the clustering
@@ -352,6 +358,9 @@ struct swa_ctx {
   // --fastidious on the clustering in place (fast_graft.inc): the per-swarm sums, the role byte of every amplicon, and the
   // grafting's slots, winner lists and result arrays
   swa_dbuf d_swarm_sums, d_swarm_role, d_graft_work;
+  // the grafted clustering as one layout (fast_graft.inc: GraftLayout): the member order as the writers print it, and per swarm
+  // where its members lie in it, how many it has with everything grafted, whether it hangs on another
+  swa_dbuf d_graft_layout;
   // the shard owner of every amplicon (fast_graft.inc): owner u8[n + 4, rounded up to 8] | tile bases u64[tiles + 1] | tile counts u32[tiles];
   // on the other ranks of a swa_multi the owner bytes alone, as rank 0 sent them
   swa_dbuf d_shard_owner;
