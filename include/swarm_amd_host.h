@@ -77,21 +77,28 @@ const uint32_t * swa_d1_result_generation(const swa_d1_result * res);  /* [n] */
 /* is_light[n] <- swarm mass < boundary; stats5 = {light swarms, amplicons in light swarms,
    nt in light swarms, heavy swarms, amplicons in heavy swarms} (src/algod1.cc:1291-1328) */
 int  swa_d1_light_flags(const swa_d1_result * res, int64_t boundary, uint8_t * is_light, uint64_t * stats5);
-/* attach_candidates (src/algod1.cc:274-336): graft_cand[n] as returned by swa_d1_fastidious;
-   returns the number of grafts made */
+/* attach_candidates (src/algod1.cc:274-336): graft_cand[n] as returned by swa_d1_fastidious; returns the number of
+   grafts made.  A grafted result holds one form: a printed swarm's members — its own, then those of the light swarms it
+   won, in the order it won them — are one range of the member order, an attached swarm's range lies inside its heavy
+   swarm's, and every writer reads ranges.  The winners are decided as the reference's walk over the sorted (parent, child)
+   pairs decides them, for well-formed candidates: no parent lies in a swarm that is some child's swarm.  Ill-formed
+   candidates (and candidates that are no amplicon, or a result that holds grafts already) make no graft: swa_d1_graft
+   returns 0, leaves the result untouched, and sets swa_d1_result_error. */
 uint32_t swa_d1_graft(swa_d1_result * res, const uint32_t * graft_cand);
-/* The same from the four arrays of swa_d1_graft_device (grafts in chain order: heavy swarm, light swarm, parent amplicon,
-   child amplicon), one pass over them: chain links, the grown sizes, the largest swarm, the swarm count, graft_cand of the
-   winning children.  On a result whose details are still in HBM (swa_d1_cluster_resident_lazy) nothing is fetched: the
-   sums and graft_cand are settled when a writer or accessor asks for the details, and -s, -w, -i, -u come out as after
-   swa_d1_graft.  SWA_E_ARG (nothing installed) for arrays that are no graft of this result: a swarm or amplicon it
-   does not have, a light swarm listed twice, attached already or with a chain of its own, a heavy swarm that is attached. */
+/* The same from the four arrays of swa_d1_graft_device (grafts in chain order — by heavy swarm, ascending, a heavy swarm's
+   in the order it won them: heavy swarm, light swarm, parent amplicon, child amplicon): the same layout made on the host,
+   by all threads, with the grown sizes, the largest swarm, the swarm count and graft_cand of the winning children.  On a
+   result whose details are still in HBM (swa_d1_cluster_resident_lazy) nothing is fetched: the sums and graft_cand are
+   settled when a writer or accessor asks for the details, and -s, -w, -i, -u come out as after swa_d1_graft.  SWA_E_ARG,
+   a text in swa_d1_result_error and a result left as it was for arrays that are no graft of this result: a swarm or
+   amplicon it does not have, heavy swarms that do not ascend, a light swarm listed twice, a heavy swarm that is somebody's
+   light swarm, a result that holds grafts already. */
 int  swa_d1_result_install_graft(swa_d1_result * res, const uint32_t * heavy_swarm, const uint32_t * light_swarm,
                                  const uint32_t * parent, const uint32_t * child, uint32_t grafts);
-/* The same from the layout swa_d1_graft_layout_device left in the context's HBM, with no per-graft array on the host, no
-   chain and no one-thread pass: the printed member order is downloaded into the result's own member order (one DMA after
-   swa_d1_result_prepare), the three per-swarm arrays beside it, and one loop over the swarms, by all threads, sets every
-   swarm's bounds [begin, begin + grown), the end of its own members, its size and whether it is attached; the largest
+/* The same from the layout swa_d1_graft_layout_device left in the context's HBM, with no per-graft array on the host and
+   nothing to check or move: the printed member order is downloaded into the result's own member order (one DMA after
+   swa_d1_result_prepare), the three per-swarm arrays beside it, and the loop over the swarms that ends every route sets
+   each swarm's bounds [begin, begin + grown), the end of its own members, its size and whether it is attached; the largest
    swarm and the swarm count come from the layout's summary.  The writers print the same bytes.  On a result whose details
    are still in HBM nothing else is fetched; when the details are asked for, mass, length and singletons are summed over a
    swarm's whole range, the deepest generation over its own members (the reference leaves a heavy swarm's alone), and

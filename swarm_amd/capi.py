@@ -459,11 +459,13 @@ class D1Clusters:
         return flags, [int(x) for x in stats]
 
     def graft(self, graft_cand: np.ndarray) -> int:
+        """swa_d1_graft: the grafts decided from the candidates and laid out in the member order; 0 (result untouched, a text
+        in swa_d1_result_error) for ill-formed candidates."""
         g = np.ascontiguousarray(graft_cand, dtype=np.uint32)
         return int(self.lib.swa_d1_graft(self.h, _ptr(g)))
 
     def install_graft(self, heavy_swarm, light_swarm, parent, child) -> None:
-        """swa_d1_result_install_graft: the grafts of Context.d1_graft_device (chain order) installed as graft() would
+        """swa_d1_result_install_graft: the grafts of Context.d1_graft_device (chain order) laid out as graft() would
         leave them; a lazy result downloads nothing for it."""
         four = [np.ascontiguousarray(a, dtype=np.uint32) for a in (heavy_swarm, light_swarm, parent, child)]
         assert len({len(a) for a in four}) == 1
@@ -473,7 +475,7 @@ class D1Clusters:
 
     def adopt_layout(self, ctx: "Context") -> None:
         """swa_d1_result_adopt_layout: the layout Context.d1_graft_layout_device left in HBM becomes the result's member order
-        and bounds — no chain, no per-graft array; the writers print what they print after graft() / install_graft().  A
+        and bounds — no per-graft array, nothing moved on the host; the writers print what they print after graft() / install_graft().  A
         lazy result keeps needing its context."""
         rc = self.lib.swa_d1_result_adopt_layout(self.h, ctx.h)
         if rc != SWA_OK:

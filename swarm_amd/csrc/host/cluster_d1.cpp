@@ -3,9 +3,9 @@
 //
 // Behaviour mirrors algo_d1_run's host part (src/algod1.cc:1185-1280 clustering,
 // 214-336 grafting, 755-1095 writers) so that every output file is byte-identical.
-// Shape is this repo's own: swarms are contiguous ranges of one discovery-order array
-// (the reference threads a linked list through ampinfo[].next); the light swarms grafted onto a
-// heavy one form a chain through the swarm table.
+// Shape is this repo's own: swarms are contiguous ranges of one member array (the reference threads a
+// linked list through ampinfo[].next); grafting moves the members of the light swarms behind those of
+// the heavy swarm that won them, so a printed swarm stays one range (lay_out_grafts).
 #include "hostdb.h"
 #include "nw_host.h"
 #include "out.h"
@@ -25,23 +25,16 @@
 struct swa_d1_result {
   uint32_t n = 0;
   swa_vec<uint32_t> swarmid, parent, generation;   // (swa_vec: sized without a serial fill, see hostdb.h)
-  swa_vec<uint32_t> order;                  // amplicons in discovery order, swarm after swarm
+  swa_vec<uint32_t> order;                  // amplicons in printed order: discovery order, swarm after swarm, until grafts are laid out
   struct Swarm {                            // plain data: the table of 1.6 M swarms (10 M amplicons) is filled by all threads
     uint64_t mass, sumlen;
     uint32_t seed, size, singletons, maxgen;
-    uint32_t begin, end;                    // own members = order[begin, end)
-    // light swarms grafted onto this one, in graft order: a chain through the swarm table
-    // (head / tail on the heavy swarm, next on each light one; the reference threads a similar
-    // list through ampinfo[].next)
-    uint32_t graft_head, graft_tail, graft_next;
-    uint32_t attached;                      // this (light) swarm hangs on another one
-    // an adopted layout (swa_d1_result_adopt_layout) has no chain: [begin, end) holds the grafted members too, behind the
-    // swarm's own, which end here
-    uint32_t own_end;
+    // printed members = order[begin, end): the swarm's own, order[begin, own_end), then those of the light swarms grafted
+    // onto it, in graft order (own_end == end without grafts).  An attached swarm keeps its bounds, inside its heavy swarm's.
+    uint32_t begin, own_end, end;
+    uint32_t attached;                      // this (light) swarm hangs on another one: it prints nothing itself
   };
-  static constexpr Swarm empty_swarm() {
-    return Swarm{0, 0, 0, 0, 0, 0, 0, 0, SWA_NO_AMPLICON, SWA_NO_AMPLICON, SWA_NO_AMPLICON, 0, 0};
-  }
+  static constexpr Swarm empty_swarm() { return Swarm{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
   swa_vec<Swarm> swarms;
   swa_vec<uint32_t> graft_cand;             // per amplicon, after swa_d1_graft
   uint64_t swarmcount_adjusted = 0;
@@ -55,10 +48,10 @@ struct swa_d1_result {
   const swa_hostdb * lazy_db = nullptr;
   bool details = true;
   uint32_t detail_fetches = 0;              // downloads of swarm id / generation / parent made for this result (swa_d1_result_detail_fetches)
-  // swa_d1_result_install_graft on a result whose details are still lazy: the grafts, folded into the sums and graft_cand
-  // when the details are made after all (need_details)
-  std::vector<uint32_t> pending_heavy, pending_light, pending_parent, pending_child;
-  // how the grafts came (swa_d1_result_graft_route): 0 none, 1 the host's walk, 2 installed, 3 an adopted layout
+  // the winning (child << 32 | parent) pairs of swa_d1_graft / swa_d1_result_install_graft, until they are written into
+  // graft_cand: at once, or when the details of a lazy result are made after all (keep_winners)
+  swa_vec<uint64_t> winners;
+  // how the grafts came (swa_d1_result_graft_route): 0 none, 1 decided on the host, 2 installed, 3 an adopted layout
   uint32_t graft_route = 0;
   // swa_d1_result_prepare: order and the download area of the swarms' bounds sized ahead — and pinned, when the runtime agreed
   swa_vec<uint32_t> begin_tmp;
@@ -83,17 +76,50 @@ void fill_parallel(V & v, size_t n, T value) {
 template <typename F>
 void for_each_member(const swa_d1_result * r, const swa_d1_result::Swarm & s, F && f) {
   for (uint32_t k = s.begin; k < s.end; ++k) { f(r->order[k]); }
-  for (uint32_t g = s.graft_head; g != SWA_NO_AMPLICON; g = r->swarms[g].graft_next) {
-    const auto & l = r->swarms[g];
-    for (uint32_t k = l.begin; k < l.end; ++k) { f(r->order[k]); }
-  }
 }
 
 // what a swarm costs a writer that walks its members: its own and those of the light swarms grafted onto it (which print
 // nothing themselves) — swa_format_in_weighted_pieces
 inline uint64_t printed_members(const swa_d1_result * r, size_t k) {
   const auto & s = r->swarms[k];
-  return s.attached != 0 ? 0u : 1u + std::max<uint32_t>(s.size, s.end - s.begin);
+  return s.attached != 0 ? 0u : 1u + (s.end - s.begin);
+}
+
+// SWARM_AMD_CLUSTER_TIMING: what a phase took since the one before it
+struct Laps {
+  const bool on = std::getenv("SWARM_AMD_CLUSTER_TIMING") != nullptr;
+  double last = omp_get_wtime();
+  void operator()(const char * what) {
+    if (!on) { return; }
+    const double now = omp_get_wtime();
+    std::fprintf(stderr, "[cluster] %-24s %8.3f ms\n", what, 1000.0 * (now - last));
+    last = now;
+  }
+};
+
+// order[first, last) added to a swarm's mass, length and singletons; its deepest generation raised to that of
+// order[first, own_last) — a heavy swarm's stays its own, like the reference
+void add_members(const swa_d1_result * r, swa_d1_result::Swarm & sw, uint32_t first, uint32_t last, uint32_t own_last) {
+  const swa_hostdb * db = r->lazy_db;
+  const auto & gen = r->generation;
+  for (uint32_t k = first; k < last; ++k) {
+    // (members of consecutive swarms are consecutive in `order`: what the sums read 16 members ahead is asked for now)
+    if (k + 16u < r->n) { const uint32_t f = r->order[k + 16u]; __builtin_prefetch(&db->abundance[f]); __builtin_prefetch(&db->seqlen[f]); __builtin_prefetch(&gen[f]); }
+    const uint32_t a = r->order[k];
+    sw.mass += db->abundance[a];
+    sw.sumlen += db->seqlen[a];
+    if (db->abundance[a] == 1) { ++sw.singletons; }
+    if (k < own_last) { sw.maxgen = std::max(sw.maxgen, gen[a]); }
+  }
+}
+
+// graft_cand = the winners' candidates and nobody else's (the losers' are withdrawn)
+void keep_winners(swa_d1_result * r) {
+  fill_parallel(r->graft_cand, r->n, (uint32_t)SWA_NO_AMPLICON);
+  const int64_t g64 = (int64_t)r->winners.size();
+#pragma omp parallel for schedule(static) if (g64 >= 100000) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) { r->graft_cand[(uint32_t)(r->winners[(size_t)i] >> 32)] = (uint32_t)r->winners[(size_t)i]; }
+  swa_vec<uint64_t>().swap(r->winners);
 }
 
 constexpr uint32_t kParallelOutputFrom = 200000;   // amplicons from which the writers format on several threads
@@ -115,47 +141,24 @@ bool need_details(const swa_d1_result * cr) {
   if (cr->lazy_ctx == nullptr) { return false; }
   auto * r = const_cast<swa_d1_result *>(cr);
   const uint32_t n = r->n;
-  const swa_hostdb * db = r->lazy_db;
   r->swarmid.resize(n); r->parent.resize(n); r->generation.resize(n);
   // (the fetch faults the arrays' pages in on the library's worker threads before the copies land: swa_touch_pages)
-  fill_parallel(r->graft_cand, n, (uint32_t)SWA_NO_AMPLICON);
   if (swa_d1_cluster_fetch(r->lazy_ctx, r->swarmid.data(), r->generation.data(), r->parent.data()) != SWA_OK) {
     r->error = swa_last_error(r->lazy_ctx);
     return false;
   }
-  // an adopted layout: the winners' candidates lie in HBM (the losers' withdrawn), and [begin, end) holds the grafted members
-  const bool adopted = r->graft_route == 3;
-  if (adopted && swa_d1_graft_candidates_fetch(r->lazy_ctx, r->graft_cand.data()) != SWA_OK) {
-    r->error = swa_last_error(r->lazy_ctx);
-    return false;
-  }
-  const auto & gen = r->generation;
+  // the winners' candidates (the losers' withdrawn): in HBM behind an adopted layout, else the pairs that were installed
+  if (r->graft_route == 3) {
+    r->graft_cand.resize(n);
+    if (swa_d1_graft_candidates_fetch(r->lazy_ctx, r->graft_cand.data()) != SWA_OK) { r->error = swa_last_error(r->lazy_ctx); return false; }
+  } else { keep_winners(r); }
+  // (an attached swarm's sums are its own: its range lies inside its heavy swarm's, which counts those members too)
 #pragma omp parallel for schedule(dynamic, 1024) num_threads(swa_host_team())
   for (int64_t s = 0; s < (int64_t)r->swarms.size(); ++s) {
     auto & sw = r->swarms[(size_t)s];
-    const uint32_t own_end = adopted ? sw.own_end : sw.end;   // (the deepest generation is the swarm's own, like the reference)
-    for (uint32_t k = sw.begin; k < sw.end; ++k) {
-      // (members of consecutive swarms are consecutive in `order`: what the sums read 16 members ahead is asked for now)
-      if (k + 16u < n) { const uint32_t f = r->order[k + 16u]; __builtin_prefetch(&db->abundance[f]); __builtin_prefetch(&db->seqlen[f]); __builtin_prefetch(&gen[f]); }
-      const uint32_t a = r->order[k];
-      sw.mass += db->abundance[a];
-      sw.sumlen += db->seqlen[a];
-      if (db->abundance[a] == 1) { ++sw.singletons; }
-      if (k < own_end) { sw.maxgen = std::max(sw.maxgen, gen[a]); }
-    }
+    add_members(r, sw, sw.begin, sw.end, sw.own_end);
   }
   ++r->detail_fetches;
-  // grafts installed while the details were lazy: the heavy swarms' sums grow by their light swarms' (no light swarm is
-  // anybody's heavy swarm, so the order does not matter), the winning children keep their candidate
-  for (size_t i = 0; i < r->pending_heavy.size(); ++i) {
-    auto & heavy = r->swarms[r->pending_heavy[i]];
-    const auto & light = r->swarms[r->pending_light[i]];
-    heavy.singletons += light.singletons;
-    heavy.mass += light.mass;
-    heavy.sumlen += light.sumlen;                         // maxgen untouched, like the reference
-    r->graft_cand[r->pending_child[i]] = r->pending_parent[i];
-  }
-  for (auto * v : {&r->pending_heavy, &r->pending_light, &r->pending_parent, &r->pending_child}) { std::vector<uint32_t>().swap(*v); }
   r->details = true;
   r->lazy_ctx = nullptr;                                    // (nothing of the context is needed from here on)
   return true;
@@ -193,14 +196,7 @@ void cluster_by_fixed_points(const swa_hostdb * db, const uint64_t * offsets, co
   const uint32_t n = db->n;
   const int64_t n64 = (int64_t)n;
   constexpr uint32_t kUnset = SWA_NO_AMPLICON;
-  const bool timing = std::getenv("SWARM_AMD_CLUSTER_TIMING") != nullptr;
-  double t_last = omp_get_wtime();
-  auto lap = [&](const char * what) {
-    if (!timing) { return; }
-    const double now = omp_get_wtime();
-    std::fprintf(stderr, "[cluster] %-24s %8.3f ms\n", what, 1000.0 * (now - t_last));
-    t_last = now;
-  };
+  Laps lap;
   // 1. seed(v): push the smaller label along every edge until nothing changes
   swa_vec<uint32_t> label(n);
   swa_vec<uint8_t> active, next_active;
@@ -327,21 +323,21 @@ void cluster_by_fixed_points(const swa_hostdb * db, const uint64_t * offsets, co
   }
   lap("placement");
   uint32_t largest = 0, maxgen = 0;
-#pragma omp parallel for schedule(dynamic, 1024) reduction(max : largest) reduction(max : maxgen) num_threads(swa_host_team())
+#pragma omp parallel for schedule(dynamic, 1024) num_threads(swa_host_team())
   for (int64_t s = 0; s < (int64_t)nswarms; ++s) {
-    auto & sw = r->swarms[(size_t)s];
+    const auto & sw = r->swarms[(size_t)s];
     std::sort(r->order.begin() + sw.begin, r->order.begin() + sw.end, [&](uint32_t x, uint32_t y) {
       return gen[x] != gen[y] ? gen[x] < gen[y] : x < y;
     });
+  }
+  // (the sums read ahead in `order`, into the next swarms' members: after the sorts)
+#pragma omp parallel for schedule(dynamic, 1024) reduction(max : largest) reduction(max : maxgen) num_threads(swa_host_team())
+  for (int64_t s = 0; s < (int64_t)nswarms; ++s) {
+    auto & sw = r->swarms[(size_t)s];
     sw.seed = r->order[sw.begin];
+    sw.own_end = sw.end;
     sw.size = sw.end - sw.begin;
-    for (uint32_t k = sw.begin; k < sw.end; ++k) {
-      const uint32_t a = r->order[k];
-      sw.mass += db->abundance[a];
-      sw.sumlen += db->seqlen[a];
-      if (db->abundance[a] == 1) { ++sw.singletons; }
-      sw.maxgen = std::max(sw.maxgen, gen[a]);
-    }
+    add_members(r, sw, sw.begin, sw.end, sw.end);
     largest = std::max(largest, sw.size);
     maxgen = std::max(maxgen, sw.maxgen);
   }
@@ -409,14 +405,7 @@ static int cluster_resident(swa_ctx * ctx, const swa_hostdb * db, swa_d1_result 
   *out = r;
   const uint32_t n = db->n;
   r->n = n;
-  const bool timing = std::getenv("SWARM_AMD_CLUSTER_TIMING") != nullptr;
-  double t_last = omp_get_wtime();
-  auto lap = [&](const char * what) {
-    if (!timing) { return; }
-    const double now = omp_get_wtime();
-    std::fprintf(stderr, "[cluster] %-24s %8.3f ms\n", what, 1000.0 * (now - t_last));
-    t_last = now;
-  };
+  Laps lap;
   if (n == 0) { return SWA_OK; }
   if (prepared == nullptr) {
     r->order.resize(n);                                     // (every entry is written by the download below)
@@ -438,7 +427,7 @@ static int cluster_resident(swa_ctx * ctx, const swa_hostdb * db, swa_d1_result 
     auto & sw = r->swarms[(size_t)s];
     sw = swa_d1_result::empty_swarm();
     sw.begin = begin[(size_t)s];
-    sw.end = begin[(size_t)s + 1];
+    sw.own_end = sw.end = begin[(size_t)s + 1];
     sw.seed = r->order[sw.begin];
     sw.size = sw.end - sw.begin;
     largest = std::max(largest, sw.size);
@@ -524,11 +513,10 @@ extern "C" int swa_d1_cluster(const swa_hostdb * db, const uint64_t * offsets, c
       gen_end = (uint32_t)r->order.size();
       if (!fresh.empty()) { ++gen; }
     }
-    sw.end = (uint32_t)r->order.size();
+    sw.own_end = sw.end = (uint32_t)r->order.size();
     sw.size = sw.end - sw.begin;
-    sw.maxgen = gen;
     r->largest = std::max(r->largest, sw.size);
-    r->maxgen = std::max(r->maxgen, sw.maxgen);
+    r->maxgen = std::max(r->maxgen, gen);
     r->swarms.push_back(sw);
   }
   // per-amplicon results and per-swarm sums: independent gathers / scatters over `order`
@@ -537,14 +525,7 @@ extern "C" int swa_d1_cluster(const swa_hostdb * db, const uint64_t * offsets, c
     r->parent[a] = order_parent[k];
     r->generation[a] = order_generation[k];
   }
-  for (auto & sw : r->swarms) {
-    for (uint32_t k = sw.begin; k < sw.end; ++k) {
-      const uint32_t a = r->order[k];
-      sw.mass += db->abundance[a];
-      sw.sumlen += db->seqlen[a];
-      if (db->abundance[a] == 1) { ++sw.singletons; }
-    }
-  }
+  for (auto & sw : r->swarms) { add_members(r, sw, sw.begin, sw.end, sw.end); }   // (the deepest generation with them)
   r->swarmcount_adjusted = r->swarms.size();
   return SWA_OK;
 }
@@ -584,82 +565,134 @@ extern "C" int swa_d1_light_flags(const swa_d1_result * r, int64_t boundary, uin
 }
 
 // ---- grafting (src/algod1.cc:214-241 attach, 274-336 attach_candidates) -----------------
-// The attach loop of swa_d1_graft (below: its sequential form, which IS the reference's, src/algod1.cc:214-241, 274-336) over
-// millions of sorted (parent, child) pairs, by all threads.  What the sequential walk decides, restated without the walk:
-//   * a light swarm hangs on the parent of the FIRST pair, in sorted order, whose child is one of its members (later pairs
-//     find it attached: their child's candidate is withdrawn) — a minimum over pair numbers, per light swarm;
-//   * a heavy swarm's chain holds the light swarms it won in the order of those winning pairs, and its sums grow by theirs.
-// So: the winning pair of every light swarm by an atomic minimum; the winners, in pair order, keyed (heavy swarm, rank among
-// the winners) and sorted; every heavy swarm's run of that list linked and summed by one thread.  (3.2 M pairs, 1.5 M grafts at
-// 10 M amplicons with 30 % light ones: the sequential walk was 45 of the 61 ms this phase took.)
-static uint32_t graft_sorted_pairs_in_parallel(swa_d1_result * r, const uint64_t * pairs, size_t npairs, int blocks) {
-  const size_t nswarms = r->swarms.size();
-  swa_vec<uint32_t> first_pair;
-  fill_parallel(first_pair, nswarms, 0xFFFFFFFFu);                       // (npairs <= n < 2^32 - 1)
-  const int64_t np64 = (int64_t)npairs;
-#pragma omp parallel for schedule(static) num_threads(swa_host_team())
-  for (int64_t at = 0; at < np64; ++at) {
-    if (at + 16 < np64) { __builtin_prefetch(&r->swarmid[(uint32_t)pairs[at + 16]]); }
-    uint32_t * slot = &first_pair[r->swarmid[(uint32_t)pairs[at]]];
-    uint32_t seen = __atomic_load_n(slot, __ATOMIC_RELAXED);
-    while ((uint32_t)at < seen && !__atomic_compare_exchange_n(slot, &seen, (uint32_t)at, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
+// The reference hangs a light swarm's member list behind its heavy swarm's.  Here a printed swarm is one range of `order`, so
+// G grafts in chain order — heavy[i] wins light[i]; by heavy swarm, a heavy swarm's in the order it won them — are a new
+// layout of the swarms in `order`, in closed form (own[s] = end - begin before the grafts):
+//   grown[s]            = own[s] + own[] of the light swarms s won
+//   new_begin[printed]  = exclusive scan, in swarm order, of (attached ? 0 : grown)
+//   new_begin[light[i]] = new_begin[h] + own[h] + own[] of the light swarms h = heavy[i] won before light[i]
+//   every swarm's members move as one block: order'[new_begin[s] + k] = order[begin[s] + k]
+// Whoever decided the grafts — swa_d1_graft here, swa_d1_graft_device on the GPU — ends in this form (the GPU can make the
+// layout as well: swa_d1_result_adopt_layout).
+namespace {
+
+// Every swarm's bounds, size and `attached` from a layout whose member order is in place; where the details are on the host
+// the grafted members join their heavy swarm's mass, length and singletons (else need_details sums over [begin, end)).
+void set_layout(swa_d1_result * r, const uint32_t * new_begin, const uint32_t * grown, const uint8_t * attached) {
+  const int64_t w64 = (int64_t)r->swarms.size();
+  // (the heavy swarms come first and hold all the grafted members: not one thread's share)
+#pragma omp parallel for schedule(dynamic, 1024) if (r->n >= kParallelOutputFrom) num_threads(swa_host_team())
+  for (int64_t s = 0; s < w64; ++s) {
+    auto & sw = r->swarms[(size_t)s];
+    const uint32_t own = sw.end - sw.begin;
+    sw.begin = new_begin[s];
+    sw.own_end = sw.begin + own;
+    sw.end = sw.begin + grown[s];
+    sw.size = grown[s];
+    sw.attached = attached[s];
+    if (r->details) { add_members(r, sw, sw.own_end, sw.end, sw.own_end); }
   }
-  // the winners in pair order (a block's share goes behind the shares of the blocks before it); the losers' candidates withdrawn
-  std::vector<uint64_t> before((size_t)blocks + 1, 0);
-#pragma omp parallel for schedule(static, 1) num_threads(swa_host_team())
+}
+
+// The layout of `grafts` grafts in chain order, made and taken over.  SWA_E_ARG, a text in r->error and nothing changed for
+// what is no graft of this result: grafts on top of grafts, a swarm it does not have, heavy swarms that do not ascend, a light
+// swarm listed twice, a heavy swarm that is somebody's light swarm.
+int lay_out_grafts(swa_d1_result * r, const uint32_t * heavy, const uint32_t * light, uint32_t grafts) {
+  auto refuse = [&](const char * why) { r->error = std::string("not a graft of this clustering: ") + why; return SWA_E_ARG; };
+  if (r->graft_route != 0) { return refuse("the result holds grafts already"); }
+  const size_t w = r->swarms.size();
+  const int64_t w64 = (int64_t)w, g64 = (int64_t)grafts;
+  const bool wide = r->n >= kParallelOutputFrom;
+  swa_vec<uint8_t> attached;
+  fill_parallel(attached, w, (uint8_t)0);
+  bool fits = true;
+#pragma omp parallel for schedule(static) reduction(&& : fits) if (wide) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) {
+    fits = fits && heavy[i] < w && light[i] < w && (i == 0 || heavy[i - 1] <= heavy[i]) &&
+           __atomic_exchange_n(&attached[light[i]], (uint8_t)1, __ATOMIC_RELAXED) == 0;
+  }
+  if (!fits) { return refuse("a swarm it does not have, heavy swarms out of order or a light swarm twice"); }
+#pragma omp parallel for schedule(static) reduction(&& : fits) if (wide) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) { fits = fits && attached[heavy[i]] == 0; }
+  if (!fits) { return refuse("a swarm hangs on a swarm that is attached itself"); }
+  // grown, and how far behind its heavy swarm's begin every light swarm lies: a heavy swarm's run of grafts by one thread
+  swa_vec<uint32_t> grown(w), new_begin(w), behind(grafts);
+#pragma omp parallel for schedule(static) if (wide) num_threads(swa_host_team())
+  for (int64_t s = 0; s < w64; ++s) { grown[(size_t)s] = r->swarms[(size_t)s].end - r->swarms[(size_t)s].begin; }
+#pragma omp parallel for schedule(dynamic, 4096) if (wide) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) {
+    const uint32_t h = heavy[i];
+    if (i > 0 && heavy[i - 1] == h) { continue; }           // (not the first of its run)
+    uint32_t at = grown[h];
+    for (int64_t j = i; j < g64 && heavy[j] == h; ++j) { behind[(size_t)j] = at; at += grown[light[j]]; }   // (no light swarm grows)
+    grown[h] = at;
+  }
+  // where the printed swarms begin: a block's share goes behind the shares of the blocks before it
+  const int blocks = wide ? std::max(1, swa_host_team()) : 1;
+  std::vector<uint32_t> before((size_t)blocks + 1, 0);
+#pragma omp parallel for schedule(static, 1) if (wide) num_threads(swa_host_team())
   for (int b = 0; b < blocks; ++b) {
-    uint64_t c = 0;
-    for (int64_t at = np64 * b / blocks; at < np64 * (b + 1) / blocks; ++at) {
-      const uint32_t child = (uint32_t)pairs[at];
-      if (first_pair[r->swarmid[child]] == (uint32_t)at) { ++c; } else { r->graft_cand[child] = SWA_NO_AMPLICON; }
-    }
+    uint32_t c = 0;
+    for (int64_t s = w64 * b / blocks; s < w64 * (b + 1) / blocks; ++s) { c += attached[(size_t)s] != 0 ? 0u : grown[(size_t)s]; }
     before[(size_t)b + 1] = c;
   }
   for (int b = 0; b < blocks; ++b) { before[(size_t)b + 1] += before[(size_t)b]; }
-  const size_t nwin = before[(size_t)blocks];
-  swa_vec<uint64_t> keyed(nwin);                                        // heavy swarm << 32 | rank among the winners
-  swa_vec<uint32_t> light_of(nwin);                                     // the light swarm of every winner, by rank
-#pragma omp parallel for schedule(static, 1) num_threads(swa_host_team())
+  uint32_t largest = 0;
+#pragma omp parallel for schedule(static, 1) reduction(max : largest) if (wide) num_threads(swa_host_team())
   for (int b = 0; b < blocks; ++b) {
-    uint64_t rank = before[(size_t)b];
-    for (int64_t at = np64 * b / blocks; at < np64 * (b + 1) / blocks; ++at) {
-      const uint32_t parent = (uint32_t)(pairs[at] >> 32), child = (uint32_t)pairs[at];
-      const uint32_t light_id = r->swarmid[child];
-      if (first_pair[light_id] != (uint32_t)at) { continue; }
-      keyed[rank] = ((uint64_t)r->swarmid[parent] << 32) | rank;
-      light_of[rank] = light_id;
-      ++rank;
+    uint32_t at = before[(size_t)b];
+    for (int64_t s = w64 * b / blocks; s < w64 * (b + 1) / blocks; ++s) {
+      if (attached[(size_t)s] != 0) { continue; }
+      new_begin[(size_t)s] = at;
+      at += grown[(size_t)s];
+      largest = std::max(largest, grown[(size_t)s]);
     }
   }
-  __gnu_parallel::sort(keyed.begin(), keyed.end());
-  // every heavy swarm's run: linked in order, summed — runs are found from their first entries, one thread per run
-  uint32_t largest = r->largest;
-  const int64_t nw64 = (int64_t)nwin;
-#pragma omp parallel for schedule(dynamic, 4096) reduction(max : largest) num_threads(swa_host_team())
-  for (int64_t i = 0; i < nw64; ++i) {
-    const uint32_t heavy_id = (uint32_t)(keyed[(size_t)i] >> 32);
-    if (i > 0 && (uint32_t)(keyed[(size_t)i - 1] >> 32) == heavy_id) { continue; }      // (not the first of its run)
-    auto & heavy = r->swarms[heavy_id];
-    for (int64_t j = i; j < nw64 && (uint32_t)(keyed[(size_t)j] >> 32) == heavy_id; ++j) {
-      const uint32_t light_id = light_of[(uint32_t)keyed[(size_t)j]];
-      auto & light = r->swarms[light_id];
-      if (heavy.graft_head == SWA_NO_AMPLICON) { heavy.graft_head = light_id; }
-      else { r->swarms[heavy.graft_tail].graft_next = light_id; }
-      heavy.graft_tail = light_id;
-      heavy.size += light.size;
-      heavy.singletons += light.singletons;
-      heavy.mass += light.mass;
-      heavy.sumlen += light.sumlen;                 // maxgen untouched, like the reference
-      light.attached = 1;
+#pragma omp parallel for schedule(static) if (wide) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) { new_begin[light[i]] = new_begin[heavy[i]] + behind[(size_t)i]; }
+  // the move, swarm by swarm, and back into the result's own array (which may be pinned: it stays the one it was)
+  if (grafts != 0) {
+    swa_vec<uint32_t> moved(r->n);
+#pragma omp parallel for schedule(dynamic, 1024) if (wide) num_threads(swa_host_team())
+    for (int64_t s = 0; s < w64; ++s) {
+      const auto & sw = r->swarms[(size_t)s];
+      std::copy(r->order.begin() + sw.begin, r->order.begin() + sw.end, moved.begin() + new_begin[(size_t)s]);
     }
-    largest = std::max(largest, heavy.size);
+#pragma omp parallel for schedule(static) if (wide) num_threads(swa_host_team())
+    for (int64_t k = 0; k < (int64_t)r->n; ++k) { r->order[(size_t)k] = moved[(size_t)k]; }
   }
+  set_layout(r, new_begin.data(), grown.data(), attached.data());
   r->largest = largest;
-  r->swarmcount_adjusted -= nwin;
-  r->graft_route = 1;
-  return (uint32_t)nwin;
+  r->swarmcount_adjusted = w - grafts;
+  return SWA_OK;
 }
 
+// grafts in chain order and the pairs that won them: laid out, the winners' candidates kept — now, or with the details
+int install(swa_d1_result * r, const uint32_t * heavy, const uint32_t * light, const uint32_t * parent, const uint32_t * child,
+            uint32_t grafts, uint32_t route) {
+  const int64_t g64 = (int64_t)grafts;
+  bool ours = true;
+#pragma omp parallel for schedule(static) reduction(&& : ours) if (g64 >= 100000) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) { ours = ours && parent[i] < r->n && child[i] < r->n; }
+  if (!ours) { r->error = "not a graft of this clustering: an amplicon it does not have"; return SWA_E_ARG; }
+  const int rc = lay_out_grafts(r, heavy, light, grafts);
+  if (rc != SWA_OK) { return rc; }
+  r->winners.resize(grafts);
+#pragma omp parallel for schedule(static) if (g64 >= 100000) num_threads(swa_host_team())
+  for (int64_t i = 0; i < g64; ++i) { r->winners[(size_t)i] = ((uint64_t)child[i] << 32) | parent[i]; }
+  if (r->details) { keep_winners(r); }
+  r->graft_route = route;
+  return SWA_OK;
+}
+
+}  // namespace
+
+// What the reference's walk over the sorted (parent, child) pairs decides (src/algod1.cc:263-336), restated without the walk:
+//   * a light swarm hangs on the parent of the FIRST pair, in sorted order, whose child is one of its members (later pairs
+//     find it attached: their child's candidate is withdrawn) — a minimum over pair numbers, per light swarm;
+//   * a heavy swarm prints the light swarms it won in the order of those winning pairs.
+// So: the winning pair of every light swarm by an atomic minimum; the winners keyed (heavy swarm, number of the pair) and
+// sorted — the grafts in chain order.  (3.2 M pairs, 1.5 M grafts at 10 M amplicons with 30 % light ones.)
 extern "C" uint32_t swa_d1_graft(swa_d1_result * r, const uint32_t * graft_cand) {
   if (!need_details(r)) { return 0; }
   // (parent << 32 | child): sorting the packed pairs is the (parent, child) order of
@@ -667,15 +700,17 @@ extern "C" uint32_t swa_d1_graft(swa_d1_result * r, const uint32_t * graft_cand)
   const int64_t n64 = (int64_t)r->n;
   const int blocks = std::max(1, swa_host_team());
   std::vector<uint64_t> before((size_t)blocks + 1, 0);        // candidates in the blocks before each block
-#pragma omp parallel for schedule(static, 1) num_threads(swa_host_team())
+  bool strays = false;
+#pragma omp parallel for schedule(static, 1) reduction(|| : strays) num_threads(swa_host_team())
   for (int b = 0; b < blocks; ++b) {
     uint64_t c = 0;
     for (int64_t i = n64 * b / blocks; i < n64 * (b + 1) / blocks; ++i) {
-      r->graft_cand[(size_t)i] = graft_cand[i];
       c += graft_cand[i] != SWA_NO_AMPLICON ? 1u : 0u;
+      strays = strays || (graft_cand[i] != SWA_NO_AMPLICON && graft_cand[i] >= r->n);
     }
     before[(size_t)b + 1] = c;
   }
+  if (strays) { r->error = "swa_d1_graft: a candidate that is no amplicon of this result"; return 0; }
   for (int b = 0; b < blocks; ++b) { before[(size_t)b + 1] += before[(size_t)b]; }
   swa_vec<uint64_t> pairs(before[(size_t)blocks]);
 #pragma omp parallel for schedule(static, 1) num_threads(swa_host_team())
@@ -686,105 +721,60 @@ extern "C" uint32_t swa_d1_graft(swa_d1_result * r, const uint32_t * graft_cand)
     }
   }
   __gnu_parallel::sort(pairs.begin(), pairs.end());
-  const size_t npairs = pairs.size();
-  if (npairs >= 50000 && blocks >= 3) { return graft_sorted_pairs_in_parallel(r, pairs.data(), npairs, blocks); }
-  uint32_t grafts = 0;
-  // (a chain of dependent random reads — swarm of the child, swarm of the parent, both swarms' records — the ids of the
-  // pairs 16 ahead and the records of the pairs 8 ahead are asked for early)
-  for (size_t at = 0; at < npairs; ++at) {
-    if (at + 16 < npairs) {
-      __builtin_prefetch(&r->swarmid[(uint32_t)pairs[at + 16]]);
-      __builtin_prefetch(&r->swarmid[(uint32_t)(pairs[at + 16] >> 32)]);
-    }
-    if (at + 8 < npairs) {
-      __builtin_prefetch(&r->swarms[r->swarmid[(uint32_t)pairs[at + 8]]], 1);
-      __builtin_prefetch(&r->swarms[r->swarmid[(uint32_t)(pairs[at + 8] >> 32)]], 1);
-    }
-    const uint64_t packed = pairs[at];
-    const uint32_t parent = (uint32_t)(packed >> 32), child = (uint32_t)packed;
-    auto & light = r->swarms[r->swarmid[child]];
-    if (light.attached != 0) {
-      r->graft_cand[child] = SWA_NO_AMPLICON;       // this light swarm already hangs somewhere
-      continue;
-    }
-    auto & heavy = r->swarms[r->swarmid[parent]];
-    const uint32_t light_id = r->swarmid[child];
-    if (heavy.graft_head == SWA_NO_AMPLICON) { heavy.graft_head = light_id; }
-    else { r->swarms[heavy.graft_tail].graft_next = light_id; }
-    heavy.graft_tail = light_id;
-    heavy.size += light.size;
-    heavy.singletons += light.singletons;
-    heavy.mass += light.mass;
-    heavy.sumlen += light.sumlen;                   // maxgen untouched, like the reference
-    light.attached = 1;
-    r->largest = std::max(r->largest, heavy.size);
-    --r->swarmcount_adjusted;
-    ++grafts;
+  const int64_t np64 = (int64_t)pairs.size();
+  const bool wide = np64 >= 50000;
+  swa_vec<uint32_t> first_pair;
+  fill_parallel(first_pair, r->swarms.size(), 0xFFFFFFFFu);              // (pairs <= n < 2^32 - 1)
+#pragma omp parallel for schedule(static) if (wide) num_threads(swa_host_team())
+  for (int64_t at = 0; at < np64; ++at) {
+    if (at + 16 < np64) { __builtin_prefetch(&r->swarmid[(uint32_t)pairs[at + 16]]); }
+    uint32_t * slot = &first_pair[r->swarmid[(uint32_t)pairs[at]]];
+    uint32_t seen = __atomic_load_n(slot, __ATOMIC_RELAXED);
+    while ((uint32_t)at < seen && !__atomic_compare_exchange_n(slot, &seen, (uint32_t)at, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
   }
-  r->graft_route = 1;
-  return grafts;
+  // the winners in pair order (a block's share goes behind the shares of the blocks before it)
+  auto wins = [&](int64_t at) { return first_pair[r->swarmid[(uint32_t)pairs[at]]] == (uint32_t)at; };
+#pragma omp parallel for schedule(static, 1) if (wide) num_threads(swa_host_team())
+  for (int b = 0; b < blocks; ++b) {
+    uint64_t c = 0;
+    for (int64_t at = np64 * b / blocks; at < np64 * (b + 1) / blocks; ++at) { c += wins(at) ? 1u : 0u; }
+    before[(size_t)b + 1] = c;
+  }
+  for (int b = 0; b < blocks; ++b) { before[(size_t)b + 1] += before[(size_t)b]; }
+  const int64_t nwin = (int64_t)before[(size_t)blocks];
+  swa_vec<uint64_t> keyed(nwin);                                        // heavy swarm << 32 | number of the winning pair
+#pragma omp parallel for schedule(static, 1) if (wide) num_threads(swa_host_team())
+  for (int b = 0; b < blocks; ++b) {
+    uint64_t rank = before[(size_t)b];
+    for (int64_t at = np64 * b / blocks; at < np64 * (b + 1) / blocks; ++at) {
+      if (wins(at)) { keyed[rank++] = ((uint64_t)r->swarmid[(uint32_t)(pairs[at] >> 32)] << 32) | (uint64_t)at; }
+    }
+  }
+  __gnu_parallel::sort(keyed.begin(), keyed.end());
+  swa_vec<uint32_t> four((size_t)nwin * 4);
+  uint32_t * heavy = four.data(), * light = heavy + nwin, * parent = light + nwin, * child = parent + nwin;
+#pragma omp parallel for schedule(static) if (wide) num_threads(swa_host_team())
+  for (int64_t i = 0; i < nwin; ++i) {
+    const uint64_t pair = pairs[(uint32_t)keyed[(size_t)i]];
+    heavy[i] = (uint32_t)(keyed[(size_t)i] >> 32);
+    parent[i] = (uint32_t)(pair >> 32);
+    child[i] = (uint32_t)pair;
+    light[i] = r->swarmid[child[i]];
+  }
+  return install(r, heavy, light, parent, child, (uint32_t)nwin, 1) == SWA_OK ? (uint32_t)nwin : 0u;
 }
 
-// The grafts swa_d1_graft_device made (chain order: by heavy swarm, then by the winning pair) installed into the result:
-// what swa_d1_graft leaves — chain links, `attached`, the grown sizes, `largest`, the adjusted swarm count, graft_cand of the
-// winning children — in one pass over the G entries.  The per-swarm sums and graft_cand of a result whose details are still
-// on the device are settled when somebody asks for the details (need_details); a plain -o never does.
+// The grafts swa_d1_graft_device made (chain order), with the pairs that won them: what swa_d1_graft leaves.  On a result
+// whose details are still on the device nothing is fetched: the sums and graft_cand are settled when somebody asks for the
+// details (need_details); a plain -o never does.
 extern "C" int swa_d1_result_install_graft(swa_d1_result * r, const uint32_t * heavy_swarm, const uint32_t * light_swarm,
                                            const uint32_t * parent, const uint32_t * child, uint32_t grafts) {
   if (r == nullptr || (grafts != 0 && (heavy_swarm == nullptr || light_swarm == nullptr || parent == nullptr || child == nullptr))) { return SWA_E_ARG; }
-  const size_t nswarms = r->swarms.size();
-  // checked before anything is linked: swarms and amplicons of this result, every light swarm once and free, no heavy
-  // swarm among the light ones (a light swarm is marked 2 while the check runs)
-  bool fits = true;
-  uint32_t marked = 0;
-  for (; fits && marked < grafts; ++marked) {
-    const uint32_t i = marked;
-    fits = heavy_swarm[i] < nswarms && light_swarm[i] < nswarms && parent[i] < r->n && child[i] < r->n &&
-           r->swarms[light_swarm[i]].attached == 0 && r->swarms[light_swarm[i]].graft_head == SWA_NO_AMPLICON;
-    if (fits) { r->swarms[light_swarm[i]].attached = 2; }
-  }
-  if (!fits) { --marked; }                                   // (the entry that failed was not marked)
-  for (uint32_t i = 0; fits && i < grafts; ++i) { fits = r->swarms[heavy_swarm[i]].attached == 0; }
-  for (uint32_t i = 0; i < marked; ++i) { r->swarms[light_swarm[i]].attached = 0; }
-  if (!fits) {
-    r->error = "swa_d1_result_install_graft: not a graft of this clustering";
-    return SWA_E_ARG;
-  }
-  const bool lazy = !r->details;
-  if (lazy) {
-    r->pending_heavy.insert(r->pending_heavy.end(), heavy_swarm, heavy_swarm + grafts);
-    r->pending_light.insert(r->pending_light.end(), light_swarm, light_swarm + grafts);
-    r->pending_parent.insert(r->pending_parent.end(), parent, parent + grafts);
-    r->pending_child.insert(r->pending_child.end(), child, child + grafts);
-  } else {
-    // (the candidates of the children that did not win are withdrawn: only the winners keep one)
-    fill_parallel(r->graft_cand, r->n, (uint32_t)SWA_NO_AMPLICON);
-  }
-  for (uint32_t i = 0; i < grafts; ++i) {
-    const uint32_t light_id = light_swarm[i];
-    auto & heavy = r->swarms[heavy_swarm[i]];
-    auto & light = r->swarms[light_id];
-    if (heavy.graft_head == SWA_NO_AMPLICON) { heavy.graft_head = light_id; }
-    else { r->swarms[heavy.graft_tail].graft_next = light_id; }
-    heavy.graft_tail = light_id;
-    heavy.size += light.size;
-    if (!lazy) {
-      heavy.singletons += light.singletons;
-      heavy.mass += light.mass;
-      heavy.sumlen += light.sumlen;                 // maxgen untouched, like the reference
-      r->graft_cand[child[i]] = parent[i];
-    }
-    light.attached = 1;
-    r->largest = std::max(r->largest, heavy.size);
-  }
-  r->swarmcount_adjusted -= grafts;
-  r->graft_route = 2;
-  return SWA_OK;
+  return install(r, heavy_swarm, light_swarm, parent, child, grafts, 2);
 }
 
 // The layout swa_d1_graft_layout_device left in HBM adopted as the result's own: the printed member order into `order` (one
-// DMA where swa_d1_result_prepare pinned it), the three per-swarm arrays, one loop over the swarms by all threads.  No chain,
-// no per-graft array, no walk: the writers find a printed swarm's members, grafted ones included, in order[begin, end).
+// DMA where swa_d1_result_prepare pinned it) and the three per-swarm arrays; nothing to decide, check or move here.
 extern "C" int swa_d1_result_adopt_layout(swa_d1_result * r, swa_ctx * ctx) {
   if (r == nullptr || ctx == nullptr) { return SWA_E_ARG; }
   auto refuse = [&](const char * why) { r->error = std::string("swa_d1_result_adopt_layout: ") + why; return SWA_E_ARG; };
@@ -806,26 +796,8 @@ extern "C" int swa_d1_result_adopt_layout(swa_d1_result * r, swa_ctx * ctx) {
     r->error = swa_last_error(ctx);
     return SWA_E_DEVICE;
   }
-  const bool sums = r->details;                              // (else need_details makes them over [begin, end))
-  const swa_hostdb * db = r->lazy_db;
-#pragma omp parallel for schedule(static) num_threads(swa_host_team())
-  for (int64_t s = 0; s < (int64_t)w; ++s) {
-    auto & sw = r->swarms[(size_t)s];
-    const uint32_t own = sw.end - sw.begin;
-    sw.begin = new_begin[(size_t)s];
-    sw.own_end = sw.begin + own;
-    sw.end = sw.begin + grown[(size_t)s];
-    sw.size = grown[(size_t)s];
-    sw.attached = attached[(size_t)s];
-    if (!sums) { continue; }
-    for (uint32_t k = sw.own_end; k < sw.end; ++k) {
-      const uint32_t a = r->order[k];
-      sw.mass += db->abundance[a];
-      sw.sumlen += db->seqlen[a];
-      if (db->abundance[a] == 1) { ++sw.singletons; }         // maxgen untouched, like the reference
-    }
-  }
-  if (sums) { r->graft_cand.swap(kept); }
+  set_layout(r, new_begin.data(), grown.data(), attached.data());
+  if (r->details) { r->graft_cand.swap(kept); }
   r->largest = (uint32_t)summary[1];
   r->swarmcount_adjusted = summary[0];
   r->graft_route = 3;
@@ -848,33 +820,17 @@ extern "C" int swa_d1_write_swarms(const swa_d1_result * r, const swa_hostdb * d
   // members ahead is asked for now (without that: ~100 ms of cache misses at 10 M amplicons on 16 threads, lease r5f).
   const uint32_t * order = r->order.data();
   auto format_range = [&](BufOut & sink, size_t begin, size_t end) {
-    // pass 1: the ids this piece prints, in printing order, and where every printed swarm ends.  Own members are a run
-    // of `order`; grafted light swarms (--fastidious: millions of one-member swarms hung on the heavy ones) are a chain
-    // through the swarm table — the next link's record is asked for while this one's members are copied.
-    // An adopted layout has no chain and nothing to copy: the printed swarms of a piece are one run of `order`.
-    std::vector<uint32_t> own_ids, ends;
+    // pass 1: where every printed swarm of this piece ends.  The printed swarms of a piece are one run of `order`, grafted
+    // members included (lay_out_grafts).
+    std::vector<uint32_t> ends;
     const uint32_t * ids = nullptr;
-    const bool adopted = r->graft_route == 3;
     if (begin < end) { ends.reserve(end - begin); }
-    if (begin < end && !adopted) { own_ids.reserve((size_t)r->swarms[end - 1].end - r->swarms[begin].begin + 64); }
     for (size_t k = begin; k < end; ++k) {
       const auto & s = r->swarms[k];
       if (s.attached != 0) { continue; }
-      if (adopted) {
-        if (ids == nullptr) { ids = order + s.begin; }
-        ends.push_back((uint32_t)(order + s.end - ids));
-        continue;
-      }
-      own_ids.insert(own_ids.end(), order + s.begin, order + s.end);
-      for (uint32_t g = s.graft_head; g != SWA_NO_AMPLICON;) {
-        const auto & l = r->swarms[g];
-        if (l.graft_next != SWA_NO_AMPLICON) { __builtin_prefetch(&r->swarms[l.graft_next]); }
-        own_ids.insert(own_ids.end(), order + l.begin, order + l.end);
-        g = l.graft_next;
-      }
-      ends.push_back((uint32_t)own_ids.size());
+      if (ids == nullptr) { ids = order + s.begin; }
+      ends.push_back((uint32_t)(order + s.end - ids));
     }
-    if (!adopted) { ids = own_ids.data(); }
     const size_t total = ends.empty() ? 0 : ends.back();
     // pass 2: a member's identifier is three dependent random reads away — its entry pointer, the entry, the header
     // text: what the walk needs 24, 16 and 8 members ahead is asked for now (without that: ~100 ms of cache misses at

@@ -475,14 +475,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       int dup = 0;
       rc = swa_d1_index_build(ctx, &dup);
       if (rc != SWA_OK && preparing.joinable()) { preparing.join(); }     // (no exit under a thread that is talking to the runtime)
-      if (rc == SWA_E_DUPLICATES) {
-        die("some fasta entries have identical sequences.\n"
-            "Swarm expects dereplicated fasta files.\n"
-            "Such files can be produced with swarm or vsearch:\n"
-            " swarm -d 0 -w derep.fasta -o /dev/null input.fasta\n"
-            "or\n"
-            " vsearch --derep_fulllength input.fasta --sizein --sizeout --output derep.fasta\n");
-      }
+      if (rc == SWA_E_DUPLICATES) { die(dup_text); }
       if (rc != SWA_OK) { die(swa_last_error(ctx)); }
       phase(o, "Hashing sequences:");
       // the network stays in HBM: the agglomeration runs on it there; it only comes to the host for -j
@@ -524,7 +517,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       // SWARM_AMD_FASTIDIOUS=host selects it for comparison.  The grafts do not come home: the grafted clustering is laid out
       // in HBM and the result adopts it (swa_d1_graft_layout_device, swa_d1_result_adopt_layout; =layout, the default by
       // measurement: profiles/r25/NOTES.md).  =install keeps the route before it for comparison: four arrays of G entries
-      // downloaded and installed into the result by one thread (swa_d1_result_install_graft).
+      // downloaded, and the same layout made on the host (swa_d1_result_install_graft).
       const char * fast_route = std::getenv("SWARM_AMD_FASTIDIOUS");
       const bool on_device = resident && !(fast_route != nullptr && std::strcmp(fast_route, "host") == 0);
       const bool by_layout = on_device && !(fast_route != nullptr && std::strcmp(fast_route, "install") == 0);

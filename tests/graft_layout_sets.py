@@ -6,7 +6,7 @@ light[i]; sorted by heavy swarm, then by the winning pair: tests/graft_sets.py, 
 unattached swarms in swarm order: a swarm's own members, then the members of each light swarm of its chain, in chain order.
 
   closed_form_layout   that order and where every swarm lies in it, by integer scans (the statement the device is held to)
-  walk_chains          the same by building the chains and walking them, the way for_each_member of cluster_d1.cpp does
+  walk_chains          the same by building the chains and walking them, the way the reference's writers do
 
 and the block graphs the GPU tests adopt: swarm k = the next sizes[k] ids, its first id linked to all the others."""
 import numpy as np

@@ -1,17 +1,18 @@
 """The grafting of --fastidious in closed form (tests/graft_sets.py: closed_form — the smallest packed pair per light swarm,
-the winners sorted by heavy swarm and pair) against the reference's sequential walk over the sorted pairs, which
-D1Clusters.graft takes below 50 000 pairs; and the install step (swa_d1_result_install_graft), which must leave a result as
-that walk leaves it.  Random small clusterings, random candidates, a few hundred amplicons each; no GPU.
+the winners sorted by heavy swarm and pair), which is what the reference's sequential walk over the sorted pairs decides,
+against D1Clusters.graft; and the install step (swa_d1_result_install_graft), which must leave a result as graft leaves
+it.  Random small clusterings, random candidates, a few hundred amplicons each; no GPU.
 
-The walk's result is read off what the writers print: -o (who is printed with whom, in which order: the chains), -s (size,
-mass, singletons, deepest generation of every printed swarm) and -i (the winning children's candidates)."""
+The result is read off what the writers print: -o (who is printed with whom, in which order: a heavy swarm's own members,
+then those of the light swarms it won, in the order it won them), -s (size, mass, singletons, deepest generation of every
+printed swarm) and -i (the winning children's candidates); -w, -u and -r as well where two results are compared."""
 import filecmp
 
 import numpy as np
 import pytest
 
 import graft_sets as GS
-from swarm_amd import D1Clusters, HostDb
+from swarm_amd import D1Clusters, HostDb, d1_write_uclust
 
 
 def _clustered(case, tmp_path):
@@ -31,10 +32,13 @@ def _id(token: bytes) -> int:
 
 
 def _written(cl, tmp_path, tag):
-    paths = {k: tmp_path / f"{tag}.{k}" for k in "osi"}
+    paths = {k: tmp_path / f"{tag}.{k}" for k in "osiwur"}
     cl.write_swarms(paths["o"])
     cl.write_stats(paths["s"])
     cl.write_structure(paths["i"])
+    cl.write_seeds(paths["w"])
+    d1_write_uclust(cl, paths["u"])
+    cl.write_swarms(paths["r"], mothur=True)
     return paths
 
 
@@ -96,7 +100,7 @@ def test_the_cases_exercise_the_walk():
 
 def test_install_refuses_what_is_no_graft(tmp_path):
     """a swarm the result does not have, a light swarm listed twice, a heavy swarm that is itself attached: SWA_E_ARG,
-    nothing installed"""
+    nothing installed; candidates that hang a swarm on an attached swarm: graft() makes none"""
     from swarm_amd import SwaError, capi
     case = GS.make_case(*GS.CASES[2])
     hdb, cl = _clustered(case, tmp_path)
@@ -114,5 +118,9 @@ def test_install_refuses_what_is_no_graft(tmp_path):
             cl.install_graft(*four)
         assert e.value.code == capi.SWA_E_ARG
         assert cl.summary() == before
+    # the same from candidates: a member of a free swarm names a member of a light swarm that is won itself — no graft at all
+    ill = case.cand.copy()
+    ill[case.want.order[case.want.begins[free]]] = case.want.order[case.want.begins[g.light[0]]]
+    assert cl.graft(ill) == 0 and cl.summary() == before and cl.graft_route() == 0
     cl.install_graft(g.heavy, g.light, g.parent, g.child)
     assert cl.summary()["swarms"] == before["swarms"] - len(g.heavy)

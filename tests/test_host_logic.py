@@ -467,7 +467,7 @@ def test_parallel_writers_equal_serial(tmp_path):
         "graft = np.full(n, 0xFFFFFFFF, dtype=np.uint32)\n"
         "pick = light[rng.random(len(light)) < 0.5]\n"
         "graft[pick] = heavy[rng.integers(0, len(heavy), len(pick))]\n"
-        "assert len(pick) > 60000, len(pick)      # (from 50 000 pairs on the attach loop runs on all threads: graft_sorted_pairs_in_parallel)\n"
+        "assert len(pick) > 60000, len(pick)      # (from 50 000 pairs on swa_d1_graft decides the winners on all threads)\n"
         "assert cl.graft(graft) > 100\n"
         "cl.write_swarms(sys.argv[1] + '.go'); cl.write_structure(sys.argv[1] + '.gi'); cl.write_stats(sys.argv[1] + '.gs')\n")
     outs = []
