@@ -101,6 +101,7 @@ extern "C" int swa_ctx_create(int device, void * stream, swa_ctx ** out) {
 // at the first kernel launch (~0.25 s in all at 10 M amplicons).  A caller that has something else to do meanwhile
 // (reading a FASTA file) runs this on a helper thread right after swa_ctx_create.
 void swa_warm_d1(swa_ctx * ctx);          // d1.hip
+void swa_warm_d1_part(swa_ctx * ctx);     // d1_part.hip: the partition and the rows of the d = 1 step
 void swa_warm_fastidious(swa_ctx * ctx);  // fastidious.hip
 void swa_warm_cluster(swa_ctx * ctx);     // cluster_gpu.hip
 void swa_warm_dn(swa_ctx * ctx);          // dn_graph.hip
@@ -121,7 +122,7 @@ extern "C" int swa_ctx_warmup_for(swa_ctx * ctx, int differences) {
   SWA_HIP(ctx, hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_warm, dim3(1), dim3(64), 0, ctx->stream, static_cast<uint32_t *>(d));
   const bool all = differences < 1;
-  if (all || differences == 1) { swa_warm_d1(ctx); swa_warm_fastidious(ctx); }
+  if (all || differences == 1) { swa_warm_d1(ctx); swa_warm_d1_part(ctx); swa_warm_fastidious(ctx); }
   swa_warm_cluster(ctx);
   if (all || differences >= 2) { swa_warm_dn(ctx); swa_warm_align(ctx); swa_warm_qgram(ctx); swa_warm_scan(ctx); }
   SWA_HIP(ctx, hipMemcpyAsync(host.data(), d, 4096, hipMemcpyDeviceToHost, ctx->stream));

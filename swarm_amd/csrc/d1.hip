@@ -19,16 +19,18 @@
 //   * the hash table is one 16-byte slot per entry (hash, amplicon id): one transaction
 //     per probe step instead of the reference's three arrays;
 //   * hits leave a wave through its own segment of the edge buffer (one writer per segment,
-//     no atomics); the partition of d1_stream.inc sorts the segments' links into the canonical CSR.
+//     no atomics); the partition of d1_part.hip sorts the segments' links into the canonical CSR.
 //
 // All arithmetic is 64-bit integer XOR/shift/compare; results are bit-exact.
 //
 // In this unit: hashing, the table, the plain probe (MODE 0 / 2), the anchored passes (d1_anchor.inc), the streaming index
-// build and the CSR assembly (d1_stream.inc), the guard, the multi-GPU route and link-exchange entry points, the debug
-// readers.  The --fastidious pass is a unit of its own (fastidious.hip); the few host functions it calls here are declared
-// in one block of swa_internal.h ("what fastidious.hip takes from d1.hip"), the device code both compile is in
+// build (d1_stream.inc), the guard, the multi-GPU route entry points, the debug readers.  The partition engine, the CSR
+// assembly and the link exchange are a unit of their own (d1_part.hip), called through the six functions of
+// d1_internal.h.  The --fastidious pass is a unit of its own (fastidious.hip); the few host functions it calls here are
+// declared in one block of swa_internal.h ("what fastidious.hip takes from d1.hip"), the device code both compile is in
 // d1_common.inc and d1_probe.inc.
-#include "swa_internal.h"
+#include "d1_internal.h"
+using namespace swa_d1;
 
 #include <algorithm>
 #include <type_traits>   // (d1_stream.inc: std::conditional, std::true_type)
@@ -151,150 +153,6 @@ __global__ __launch_bounds__(256) void k_dup_check(const uint64_t * __restrict__
 
 #include "d1_anchor.inc"
 
-// ---- exclusive scans (a workgroup's: d1_stream.inc too; the fastidious pass's offsets), the per-wave segments' totals and flat list ------
-constexpr int kScanItems = 8;
-constexpr int kScanBlock = 256;
-constexpr int kScanTile = kScanItems * kScanBlock;
-
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t * smem, uint64_t & total) {
-  // v: per-thread value; returns exclusive prefix within the block (256 threads)
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  uint64_t incl = v;
-#pragma unroll
-  for (unsigned d = 1; d < 64; d <<= 1) {
-    const uint64_t t = swa_shfl_up_u64(incl, d);
-    if (lane >= (int)d) { incl += t; }
-  }
-  if (lane == 63) { smem[wave] = incl; }
-  __syncthreads();
-  uint64_t wave_off = 0;
-  uint64_t tot = 0;
-  for (int w = 0; w < kScanBlock / 64; ++w) {
-    if (w < wave) { wave_off += smem[w]; }
-    tot += smem[w];
-  }
-  __syncthreads();
-  total = tot;
-  return wave_off + incl - v;
-}
-
-// swa_scan_offsets (the fastidious groups' member offsets): exclusive scan of counts[0, n) into 64-bit offsets[0, n], three launches
-__global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const uint32_t * __restrict__ counts, uint32_t n,
-                                                           uint64_t * __restrict__ tile_sums) {
-  __shared__ uint64_t smem[4];
-  const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-  uint64_t v = 0;
-  for (int i = 0; i < kScanItems; ++i) { if (base + i < n) { v += counts[base + i]; } }
-  uint64_t total;
-  (void)block_exclusive_scan(v, smem, total);
-  if (threadIdx.x == 0) { tile_sums[blockIdx.x] = total; }
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_scan_sums(uint64_t * tile_sums, uint32_t tiles) {
-  __shared__ uint64_t smem[4];
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < tiles; base += kScanBlock) {
-    const uint32_t i = base + threadIdx.x;
-    const uint64_t v = (i < tiles) ? tile_sums[i] : 0;
-    uint64_t total;
-    const uint64_t ex = block_exclusive_scan(v, smem, total);
-    if (i < tiles) { tile_sums[i] = carry + ex; }
-    carry += total;
-  }
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_scan_apply(const uint32_t * __restrict__ counts, uint32_t n,
-                                                           const uint64_t * __restrict__ tile_sums,
-                                                           uint64_t * __restrict__ offsets) {
-  __shared__ uint64_t smem[4];
-  const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-  uint32_t c[kScanItems];
-  uint64_t v = 0;
-  for (int i = 0; i < kScanItems; ++i) {
-    c[i] = (base + i < n) ? counts[base + i] : 0u;
-    v += c[i];
-  }
-  uint64_t total;
-  uint64_t run = tile_sums[blockIdx.x] + block_exclusive_scan(v, smem, total);
-  for (int i = 0; i < kScanItems; ++i) {
-    if (base + i < n) { offsets[base + i] = run; }
-    run += c[i];
-    if (base + i + 1 == n) { offsets[n] = run; }
-  }
-}
-
-// total and largest fill of the per-wave edge segments -> out[0], out[1]; the members the pair kernels staged (the
-// guard; seg_fill + nseg, + 2 nseg: pass 0, pass 1) -> out[2], out[3]
-// (one workgroup of 1024 threads, eight loads in flight per thread: the 8192 fills of an MI355X in one round — with 256
-// threads and a load per turn this single workgroup took 11 us of every step)
-// ... and the count of fallback seeds next to them in the head of the status block (fallback_copy: the host's one copy).
-// The CSR route takes all of this in the first k_part_tiles of its link partition (d1_stream.inc: SegArgs); this kernel
-// serves the edge-list route.
-__global__ __launch_bounds__(1024) void k_seg_reduce(const uint32_t * __restrict__ seg_fill, uint32_t nseg,
-                                                     unsigned long long * out, const uint32_t * fallback, uint32_t * fallback_copy) {
-  __shared__ unsigned long long ssum[16], smax[16], sst0[16], sst1[16];
-  unsigned long long sum = 0, mx = 0, st0 = 0, st1 = 0;
-  for (uint32_t base = 0; base < nseg; base += 8192u) {
-    uint32_t v[8], s0[8], s1[8];
-#pragma unroll
-    for (uint32_t k = 0; k < 8u; ++k) {
-      const uint32_t i = base + k * 1024u + threadIdx.x;
-      v[k] = i < nseg ? seg_fill[i] : 0u;
-      s0[k] = i < nseg ? seg_fill[(uint64_t)nseg + i] : 0u;
-      s1[k] = i < nseg ? seg_fill[2ull * nseg + i] : 0u;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 8u; ++k) { sum += v[k]; mx = mx > v[k] ? mx : v[k]; st0 += s0[k]; st1 += s1[k]; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long s2 = swa_shfl_xor_u64(sum, o), m2 = swa_shfl_xor_u64(mx, o);
-    sum += s2; mx = mx > m2 ? mx : m2;
-    st0 += swa_shfl_xor_u64(st0, o); st1 += swa_shfl_xor_u64(st1, o);
-  }
-  if ((threadIdx.x & 63u) == 0u) { ssum[threadIdx.x >> 6] = sum; smax[threadIdx.x >> 6] = mx; sst0[threadIdx.x >> 6] = st0; sst1[threadIdx.x >> 6] = st1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long s = 0, m = 0, a0 = 0, a1 = 0;
-    for (int w = 0; w < 16; ++w) { s += ssum[w]; m = m > smax[w] ? m : smax[w]; a0 += sst0[w]; a1 += sst1[w]; }
-    out[0] = s; out[1] = m; out[2] = a0; out[3] = a1;
-    *fallback_copy = *fallback;
-  }
-}
-
-// start of every segment in the compacted edge list: exclusive prefix sum of the fills
-__global__ __launch_bounds__(256) void k_seg_bases(const uint32_t * __restrict__ seg_fill, uint32_t nseg,
-                                                   unsigned long long * __restrict__ bases) {
-  __shared__ unsigned long long part[256];
-  const uint32_t chunk = (nseg + 255u) / 256u;
-  const uint32_t lo = threadIdx.x * chunk, hi = min(nseg, lo + chunk);
-  unsigned long long sum = 0;
-  for (uint32_t i = lo; i < hi; ++i) { sum += seg_fill[i]; }
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long run = 0;
-    for (int t = 0; t < 256; ++t) { const unsigned long long v = part[t]; part[t] = run; run += v; }
-  }
-  __syncthreads();
-  unsigned long long at = part[threadIdx.x];
-  for (uint32_t i = lo; i < hi; ++i) { bases[i] = at; at += seg_fill[i]; }
-}
-
-// per-wave segments -> one flat list of (source << 32 | target) links, in no particular order
-__global__ __launch_bounds__(256) void k_seg_compact(const uint64_t * __restrict__ edges,
-                                                     const uint32_t * __restrict__ seg_fill, uint32_t nseg, uint64_t seg_cap,
-                                                     const unsigned long long * __restrict__ bases,
-                                                     uint64_t * __restrict__ out, uint64_t cap) {
-  for (uint32_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-    const uint64_t fill = min((uint64_t)seg_fill[s], seg_cap);
-    const uint64_t base = bases[s];
-    for (uint64_t i = threadIdx.x; i < fill; i += blockDim.x) {
-      if (base + i < cap) { out[base + i] = edges[(uint64_t)s * seg_cap + i]; }
-    }
-  }
-}
-
 #include "d1_stream.inc"
 
 }  // namespace
@@ -311,17 +169,6 @@ int swa_grid_for(const swa_ctx * ctx, uint64_t items, int per_block, int max_per
 void swa_warm_d1(swa_ctx * ctx) {
   hipLaunchKernelGGL(k_table_clear, dim3(1), dim3(64), 0, ctx->stream, static_cast<swa_slot *>(nullptr), (uint64_t)0,
                      static_cast<uint64_t *>(nullptr), (uint64_t)0);
-}
-
-// (the member offsets of the --fastidious groups: its only caller is the pair route of fastidious.hip)
-int swa_scan_offsets(swa_ctx * ctx, const uint32_t * counts, uint32_t n, uint64_t * offsets) {
-  static_assert(kScanTile == (int)kScanOffsetsTile, "swa_scan_offsets: the tile the caller sized d_scan_tmp for");
-  const uint32_t tiles = (uint32_t)(((uint64_t)n + kScanTile - 1) / kScanTile);
-  auto * sums = static_cast<uint64_t *>(ctx->d_scan_tmp.ptr);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, counts, n, sums);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, ctx->stream, sums, tiles);
-  hipLaunchKernelGGL(k_scan_apply, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, counts, n, sums, offsets);
-  return SWA_OK;
 }
 
 // d_table and d_bloom cleared and filled again: with all amplicons (swa_ensure_full_index) or with those a byte array marks
@@ -441,157 +288,6 @@ __global__ void k_set_guard_made(unsigned long long * guard, uint32_t made0, uin
 
 // ---- the streaming build (d1_stream.inc) ------------------------------------------------------
 
-using PartPlan = swa_part_levels;                  // (host_tables.cpp: swa_plan_levels, swa_part_plan_for, swa_csr_plan_for)
-
-// One multi-level partition (d1_stream.inc) over up to kMaxIdx record sets.  Level l reads what level l - 1 wrote
-// (ping / pong) and leaves, in starts[], the first record of every bucket; the last level's buckets are the result.
-struct PartJob {
-  uint32_t nidx = 1;
-  const unsigned long long * in[kMaxIdx] = {};      // level-0 input (may be buf[i][1])
-  unsigned long long * buf[kMaxIdx][2] = {};
-  const uint64_t * cstart0[kMaxIdx] = {};           // level-0 chunks (nullptr: regular, PartIdx::cstride)
-  uint64_t cstride0[kMaxIdx] = {};
-  const uint32_t * csize0[kMaxIdx] = {};
-  uint32_t csize_cap = 0, chunks0 = 1;
-  bool single0 = true;
-  uint64_t max_records = 0, max_tiles0 = 0;         // host-side upper bounds (per set)
-  uint64_t out_cap = 0;                             // entries every buf[][] holds
-  uint32_t bias = 0, top_bit = 32;
-  uint32_t tile = 4096;                             // records per tile: 4096 (links), 2048 / 4096 / 8192 (key records: run_partition)
-  bool hist0_done = false;                          // the flat counts of level 0 are there already (k_keys<W, true>)
-  bool tiles0_done = false;                         // ... and its tile table (one chunk of a size the host knows)
-  const SegArgs * seg = nullptr;                    // level 0's chunks are the per-wave link segments: k_part_tiles reduces their fills on the way
-  PartPlan plan{};
-  // scratch, per set
-  uint32_t * cnt[kMaxIdx] = {}; uint32_t * ctile[kMaxIdx] = {}; uint64_t * starts[kMaxIdx] = {}; uint32_t * partial[kMaxIdx] = {};
-  uint32_t * total[kMaxIdx] = {};
-  uint64_t starts_stride = 0;
-  // results
-  const unsigned long long * out[kMaxIdx] = {}; const uint64_t * bstart[kMaxIdx] = {};
-  uint32_t buckets = 0;
-  int last = 0;                                     // buf[i][last] holds the result, buf[i][last ^ 1] is free
-};
-
-// scratch sizes of a job (entries): flat counts, tile table, chunk starts (per half), scan partials
-static void part_scratch(const PartJob & j, uint64_t * cnt, uint64_t * ctile, uint64_t * starts_half, uint64_t * partial) {
-  uint64_t chunks = j.chunks0, c_max = 0, t_max = 0, s_max = 0;
-  bool single = j.single0;
-  for (uint32_t l = 0; l < j.plan.levels; ++l) {
-    const uint64_t tiles = (l == 0 ? j.max_tiles0 : j.max_records / j.tile + chunks + 1);
-    c_max = std::max(c_max, (tiles << j.plan.bits[l]) + 2);
-    t_max = std::max(t_max, chunks + 2 + tiles + 2);              // (the tile table of the chunks, and behind it the chunk of every tile)
-    chunks = (single ? 1 : chunks) << j.plan.bits[l];
-    single = false;
-    s_max = std::max(s_max, chunks + 2);
-  }
-  *cnt = c_max; *ctile = t_max; *starts_half = s_max; *partial = c_max / kFlatChunk + 2;
-}
-
-// several small buffers zeroed by ONE launch (a step clears about ten; each hipMemsetAsync is a launch of 4-5 us)
-struct ClearList { uint32_t * p[8]; uint64_t words[8]; uint32_t n; };
-__global__ __launch_bounds__(256) void k_clear_many(const ClearList c) {
-  for (uint32_t k = 0; k < c.n; ++k) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.words[k]; i += (uint64_t)gridDim.x * blockDim.x) { c.p[k][i] = 0u; }
-  }
-}
-static void clear_add(ClearList & c, void * p, uint64_t bytes) {          // (bytes: a multiple of 4)
-  c.p[c.n] = static_cast<uint32_t *>(p); c.words[c.n] = bytes / 4; ++c.n;
-}
-static int clear_launch(swa_ctx * ctx, const ClearList & c) {
-  uint64_t most = 0;
-  for (uint32_t k = 0; k < c.n; ++k) { most = std::max(most, c.words[k]); }
-  if (c.n == 0 || most == 0) { return SWA_OK; }
-  hipLaunchKernelGGL(k_clear_many, dim3(swa_grid_for(ctx, most, 256, 8)), dim3(256), 0, ctx->stream, c);
-  SWA_HIP(ctx, hipGetLastError());
-  return SWA_OK;
-}
-
-// The forms of a level, chosen by the job: 512 bins in tiles of 2048 (key records) or 4096 (links: the first level of
-// several chunks cuts its tiles from the chunks laid end to end — part_span); 1024 bins for the one-level key partition,
-// in tiles of 8192 when k_keys has taken the histogram, else of 4096 (routed builds).
-static int run_partition(swa_ctx * ctx, PartJob & j) {
-  uint64_t chunks = j.chunks0;
-  bool single = j.single0;
-  uint32_t used_bits = 0;
-  const int cu_grid = ctx->num_cus * 8;
-  for (uint32_t l = 0; l < j.plan.levels; ++l) {
-    const uint32_t bits = j.plan.bits[l];
-    used_bits += bits;
-    const bool wide = bits > kPartMaxBits;                      // (1024 bins: the one-level key partition)
-    const bool hist_done = l == 0 && j.hist0_done;
-    // (k_part_hist holds tiles of up to 4096)
-    const bool have_form = wide ? j.tile == 4096 || (j.tile == 8192 && hist_done) : j.tile == 2048 || j.tile == 4096;
-    if (!have_form) { return swa_fail_msg(ctx, SWA_E_ARG, "partition: no kernel for this tile and bin count"); }
-    PartArgs a{};
-    a.single_seg = single ? 1u : 0u; a.bits = bits; a.shift = j.top_bit - used_bits; a.bias = j.bias; a.tile = j.tile;
-    a.span = (single && l == 0 && chunks > 1 && j.tile == 4096 && !wide && !hist_done) ? 1u : 0u;
-    // runs of 16 consecutive tiles per XCD (xcd_tile; measured at 10 M amplicons: key partition 0.44 -> 0.33 ms, link partition
-    // 0.39 -> 0.36, the same for runs of 8 .. 64) — unless there are fewer tiles than workgroups in flight, where the runs
-    // would leave XCDs without work
-    const uint64_t tiles = (l == 0 ? j.max_tiles0 : j.max_records / j.tile + chunks + 1);
-    a.run_bits = tiles >= (uint64_t)cu_grid ? 4u : 0u;
-    for (uint32_t i = 0; i < j.nidx; ++i) {
-      PartIdx & p = a.p[i];
-      p.in = l == 0 ? j.in[i] : j.buf[i][(l - 1) & 1u];
-      p.out = j.buf[i][l & 1u];
-      p.out_cap = j.out_cap;
-      p.cstart = l == 0 ? j.cstart0[i] : j.starts[i] + ((l - 1) & 1u) * j.starts_stride;
-      p.cstride = l == 0 ? j.cstride0[i] : 0;
-      p.csize = l == 0 ? j.csize0[i] : nullptr;
-      p.csize_cap = j.csize_cap;
-      p.chunks = (uint32_t)chunks;
-      p.ctile = j.ctile[i]; p.cnt = j.cnt[i];
-      p.tchunk = j.ctile[i] + chunks + 1; p.tchunk_cap = (uint32_t)std::min<uint64_t>(tiles + 1, 0xFFFFFFFFu);
-      p.next_start = j.starts[i] + (l & 1u) * j.starts_stride;
-      p.total = j.total[i];
-    }
-    // (a multiple of 8 workgroups: turn v of the tile loops then stays on XCD v mod 8 — xcd_tile)
-    const dim3 grid_t((unsigned)((std::min<uint64_t>(std::max<uint64_t>(tiles, 1), (uint64_t)cu_grid) + 7) & ~7ull), j.nidx);
-    if (hist_done && j.tiles0_done) { /* (k_keys has left the three entries of the single chunk's table) */ }
-    else if (l == 0 && j.seg != nullptr) {
-      if (chunks > 2048) { hipLaunchKernelGGL((k_part_tiles<1024, true>), dim3(1, 1), dim3(1024), 0, ctx->stream, a, *j.seg); }
-      else { hipLaunchKernelGGL((k_part_tiles<256, true>), dim3(1, 1), dim3(256), 0, ctx->stream, a, *j.seg); }
-    }
-    else if (chunks > 2048) { hipLaunchKernelGGL(k_part_tiles<1024>, dim3(1, j.nidx), dim3(1024), 0, ctx->stream, a, SegArgs{}); }
-    else { hipLaunchKernelGGL(k_part_tiles<256>, dim3(1, j.nidx), dim3(256), 0, ctx->stream, a, SegArgs{}); }
-    if (hist_done) { /* (k_keys has left the counts) */ }
-    else if (wide) { hipLaunchKernelGGL((k_part_hist<1024, kPartTileMax, 256>), grid_t, dim3(256), 0, ctx->stream, a); }
-    else if (a.span != 0u) { hipLaunchKernelGGL((k_part_hist<512, kPartTileMax, 256, true>), grid_t, dim3(256), 0, ctx->stream, a); }
-    else { hipLaunchKernelGGL((k_part_hist<512, kPartTileMax, 256>), grid_t, dim3(256), 0, ctx->stream, a); }
-    FlatScanArgs f{};
-    f.unit_bits = bits;
-    for (uint32_t i = 0; i < j.nidx; ++i) { f.v[i] = j.cnt[i]; f.units[i] = j.ctile[i] + chunks; f.partial[i] = j.partial[i]; f.total[i] = j.total[i]; }
-    const dim3 grid_f((unsigned)std::min<uint64_t>(((tiles << bits) + 1 + kFlatChunk - 1) / kFlatChunk, (uint64_t)cu_grid), j.nidx);
-    hipLaunchKernelGGL(k_flat_sums, grid_f, dim3(256), 0, ctx->stream, f);
-    hipLaunchKernelGGL(k_flat_apply, grid_f, dim3(256), 0, ctx->stream, f);
-    // (512 threads a workgroup — key partition 0.269 -> 0.239, link partition 0.317 -> 0.303 ms at 10 M against 256 —, 1024
-    // for the tile of 8192, whose 76 KB of LDS are asked for: the attribute belongs to the function on a device, once per context)
-    if (wide && j.tile == 8192) {
-      constexpr size_t lds = part_scatter_lds(8192, 1024);
-      if (!ctx->part_lds_opt_in) {
-        SWA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter<8192, 1024, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->part_lds_opt_in = true;
-      }
-      hipLaunchKernelGGL((k_part_scatter<8192, 1024, 1024>), grid_t, dim3(1024), lds, ctx->stream, a);
-    }
-    else if (wide) { hipLaunchKernelGGL((k_part_scatter<4096, 1024, 512>), grid_t, dim3(512), part_scatter_lds(4096, 1024), ctx->stream, a); }
-    else if (j.tile == 2048) { hipLaunchKernelGGL((k_part_scatter<2048, 512, 512>), grid_t, dim3(512), part_scatter_lds(2048, 512), ctx->stream, a); }
-    else if (a.span != 0u) { hipLaunchKernelGGL((k_part_scatter<4096, 512, 512, true>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
-    else { hipLaunchKernelGGL((k_part_scatter<4096, 512, 512>), grid_t, dim3(512), part_scatter_lds(4096, 512), ctx->stream, a); }
-    // (the scatter has written the bucket starts on its way: part_write_starts)
-    chunks = (single ? 1 : chunks) << bits;
-    single = false;
-    SWA_HIP(ctx, hipGetLastError());
-  }
-  j.buckets = (uint32_t)chunks;
-  j.last = (int)((j.plan.levels - 1) & 1u);
-  for (uint32_t i = 0; i < j.nidx; ++i) {
-    j.out[i] = j.buf[i][j.last];
-    j.bstart[i] = j.starts[i] + (uint64_t)j.last * j.starts_stride;
-  }
-  return SWA_OK;
-}
-
 // the amplicon lines of the uploaded database (once per upload; needs the abundance ranks)
 int swa_ensure_lines(swa_ctx * ctx) {
   const uint32_t lq = line_quads_for(ctx);
@@ -670,7 +366,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
   j.max_tiles0 = records / j.tile + 2;
   j.chunks0 = 1; j.single0 = true; j.top_bit = 32; j.bias = 0;
   uint64_t e_cnt, e_tile, e_start, e_partial;
-  part_scratch(j, &e_cnt, &e_tile, &e_start, &e_partial);
+  swa_part_scratch(j, &e_cnt, &e_tile, &e_start, &e_partial);
   const uint64_t buckets = 1ull << total_bits;
   e_partial = std::max<uint64_t>(e_partial, ((uint64_t)kListsPerIndex * buckets + 1) / kFlatChunk + 2);
   for (int i = 0; i < 2; ++i) {
@@ -702,7 +398,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
     clear_add(c, ctx->d_stream[kSbOver].ptr, ((uint64_t)n + 8) & ~3ull);
     // (the entry behind the last bucket's counts of each index: the scan of the counts reads one past the end)
     for (int i = 0; i < 2; ++i) { clear_add(c, static_cast<uint32_t *>(ctx->d_stream[kSbKind + i].ptr) + (uint64_t)kListsPerIndex * buckets, sizeof(uint32_t)); }
-    SWA_TRY(clear_launch(ctx, c));
+    SWA_TRY(swa_clear_launch(ctx, c));
   }
   swa_lap(ctx, "buffers reserved, counters cleared");
   uint32_t * dflags = st->flags;                            // (cleared above — a new index — or by the caller: a retry, a network call's build)
@@ -778,7 +474,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
   // sequences, which the prefix pass of the pair kernels now does on the sequences themselves)
   j.starts_stride = e_start + 2;
   swa_t0(ctx, kTimeKeyPartition);
-  SWA_TRY(run_partition(ctx, j));
+  SWA_TRY(swa_part_run(ctx, j));
   swa_t1(ctx, kTimeKeyPartition);
   swa_lap(ctx, "key partition");
   ctx->ix.part_starts_at = (uint64_t)(j.bstart[0] - j.starts[0]);   // (the same place in both indexes' buffers)
@@ -852,8 +548,7 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
     hipLaunchKernelGGL(k_group_lists<true>, grid_l, dim3(256), 0, ctx->stream, la);
   } else {
     const dim3 grid_k((unsigned)std::min<uint64_t>(((uint64_t)kListsPerIndex * buckets + kFlatChunk) / kFlatChunk, (uint64_t)ctx->num_cus * 8), 2);
-    hipLaunchKernelGGL(k_flat_sums, grid_k, dim3(256), 0, ctx->stream, f);
-    hipLaunchKernelGGL(k_flat_apply, grid_k, dim3(256), 0, ctx->stream, f);
+    swa_flat_scan(ctx, grid_k, f);
     hipLaunchKernelGGL(k_group_lists<false>, grid_l, dim3(256), 0, ctx->stream, la);
   }
   ctx->ix.lists_form = plan.lists_inline ? 1 : 0;
@@ -864,94 +559,6 @@ static int build_stream_index(swa_ctx * ctx, const RouteLists & route) {
   ctx->ix.stream_index = true;
   ctx->ix.guard_index = true;
   return SWA_OK;
-}
-
-// the list of the buckets k_csr_bucket leaves to whole workgroups, its count in front: a word per bucket of the CSR over `count` sources
-static uint64_t csr_heavy_bytes(uint32_t count) { return ((1ull << swa_csr_plan_for(count).lv.total) + 2) * sizeof(uint32_t); }
-
-// CSR of the links in the per-wave segments by the streaming route: the links partitioned by the top bits of their
-// source (relative to `first`) until a bucket holds 2^r consecutive sources, then one wave per bucket (k_csr_bucket).
-// link_cap: entries of the two internal link buffers; a run with more links than that leaves garbage and is repeated
-// by the caller with bigger buffers (the total is known after the host has synchronised).
-// (the chunks of the first level: `chunks` runs of links, run c = links[cstart[c] .. + min(csize[c], csize_cap)) — the per-wave
-// segments of the pair kernels, or the ranks' lists of a multi-GPU job gathered on one device)
-static int csr_from_chunks(swa_ctx * ctx, uint32_t first, uint32_t count, const unsigned long long * links, const uint64_t * d_cstart, uint64_t cstride,
-                           const uint32_t * d_csize, uint32_t chunks, uint32_t csize_cap, uint64_t max_tiles0, uint64_t link_cap,
-                           uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap, const SegArgs * seg = nullptr, bool heavy_cleared = false) {
-  const swa_csr_plan plan = swa_csr_plan_for(count);          // (host_tables.cpp)
-  const uint32_t nbits = plan.nbits, r = plan.r;
-  PartJob j;
-  j.nidx = 1;
-  j.plan = plan.lv;
-  j.max_records = link_cap;
-  j.out_cap = link_cap;
-  j.tile = 4096;
-  j.max_tiles0 = max_tiles0;
-  j.chunks0 = chunks; j.single0 = true; j.top_bit = nbits; j.bias = first;
-  j.csize_cap = csize_cap;
-  uint64_t e_cnt, e_tile, e_start, e_partial;
-  part_scratch(j, &e_cnt, &e_tile, &e_start, &e_partial);
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbLinkA], (link_cap + 1) * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbLinkB], (link_cap + 1) * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbCnt], e_cnt * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbTile], e_tile * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbStart], (2 * e_start + 4) * sizeof(uint64_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbPartial], e_partial * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbScal], 64 * sizeof(uint64_t)));
-  j.in[0] = links;
-  j.buf[0][0] = static_cast<unsigned long long *>(ctx->d_stream[kSbLinkA].ptr);
-  j.buf[0][1] = static_cast<unsigned long long *>(ctx->d_stream[kSbLinkB].ptr);
-  j.cstart0[0] = d_cstart; j.cstride0[0] = cstride;
-  j.csize0[0] = d_csize;
-  j.seg = d_csize != nullptr && j.nidx == 1 ? seg : nullptr;
-  j.cnt[0] = static_cast<uint32_t *>(ctx->d_stream[kSbCnt].ptr);
-  j.ctile[0] = static_cast<uint32_t *>(ctx->d_stream[kSbTile].ptr);
-  j.starts[0] = static_cast<uint64_t *>(ctx->d_stream[kSbStart].ptr);
-  ctx->ix.part_starts_valid = false;                             // (the prefix index's bucket starts lay there: selectors 17 / 18)
-  j.partial[0] = static_cast<uint32_t *>(ctx->d_stream[kSbPartial].ptr);
-  j.total[0] = &swa_status(ctx)->links_sorted;
-  j.starts_stride = e_start + 2;
-  swa_t0(ctx, kTimeLinkPartition);
-  SWA_TRY(run_partition(ctx, j));
-  swa_t1(ctx, kTimeLinkPartition);
-  CsrArgs c{};
-  c.links = j.out[0]; c.bstart = j.bstart[0]; c.buckets = j.buckets; c.r = r; c.first = first; c.count = count;
-  c.offsets = d_offsets; c.neighbours = d_neighbours; c.cap = d_neighbours != nullptr ? cap : 0;
-  const void * heavy_before = ctx->d_stream[kSbHeavy].ptr;
-  SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbHeavy], csr_heavy_bytes(count)));
-  c.heavy = static_cast<uint32_t *>(ctx->d_stream[kSbHeavy].ptr) + 1;
-  c.heavy_count = static_cast<uint32_t *>(ctx->d_stream[kSbHeavy].ptr);
-  c.end_copy = &swa_status(ctx)->csr_end;
-  // (the anchored network call has cleared the count with its other counters — launch_network_anchored — unless the
-  // buffer is a new one since)
-  if (!heavy_cleared || ctx->d_stream[kSbHeavy].ptr != heavy_before) { SWA_HIP(ctx, hipMemsetAsync(c.heavy_count, 0, sizeof(uint32_t), ctx->stream)); }
-  swa_t0(ctx, kTimeCsrRows);
-  // (as many workgroups as are resident together — every wave walks its share of the buckets; a grid of 8 a CU ran a second,
-  // partly empty round behind the first)
-  static const int csr_per_cu[2] = {
-    [] { int nb = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_csr_bucket<8>, 256, 0) == hipSuccess && nb > 0 ? nb : 4; }(),
-    [] { int nb = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_csr_bucket<9>, 256, 0) == hipSuccess && nb > 0 ? nb : 4; }() };
-  const dim3 cgrid((unsigned)std::min<uint64_t>(((uint64_t)j.buckets + 3) / 4, (uint64_t)ctx->num_cus * (uint64_t)csr_per_cu[r <= 8 ? 0 : 1]));
-  if (r <= 8) { hipLaunchKernelGGL(k_csr_bucket<8>, cgrid, dim3(256), 0, ctx->stream, c); }
-  else { hipLaunchKernelGGL(k_csr_bucket<9>, cgrid, dim3(256), 0, ctx->stream, c); }
-  hipLaunchKernelGGL(k_csr_bucket_big, dim3((unsigned)ctx->num_cus * 4), dim3(256), 0, ctx->stream, c);
-  swa_t1(ctx, kTimeCsrRows);
-  SWA_HIP(ctx, hipGetLastError());
-  return SWA_OK;
-}
-
-static int launch_csr_stream(swa_ctx * ctx, uint32_t first, uint32_t count, uint32_t nseg, uint64_t link_cap, uint64_t * d_offsets,
-                             uint32_t * d_neighbours, uint64_t cap, bool heavy_cleared) {
-  // (the first level's k_part_tiles also makes of the segment fills what k_seg_reduce does: SegArgs)
-  swa_status_block * st = swa_status(ctx);
-  SegArgs seg{};
-  seg.staged = static_cast<const uint32_t *>(ctx->d_seg_fill.ptr) + nseg;
-  seg.out = reinterpret_cast<unsigned long long *>(st->stats) + kStatSeg;
-  seg.fallback = st->counters + kCounterFallback; seg.fallback_copy = &st->fallback_copy;
-  const uint64_t tiles_per_seg = (ctx->seg_cap + 4096 - 1) / 4096;
-  return csr_from_chunks(ctx, first, count, static_cast<const unsigned long long *>(ctx->d_edges.ptr), nullptr, ctx->seg_cap,
-                         static_cast<const uint32_t *>(ctx->d_seg_fill.ptr), nseg, (uint32_t)std::min<uint64_t>(ctx->seg_cap, 0xFFFFFFFFu),
-                         (uint64_t)nseg * tiles_per_seg + 2, link_cap, d_offsets, d_neighbours, cap, &seg, heavy_cleared);
 }
 
 // the pair kernels by (pass, record width W in words, window width NW in words): W = 5 / 8 / 15 / 21 (width_words), NW = 1 / 2
@@ -1029,7 +636,7 @@ static int launch_network_anchored(swa_ctx * ctx, int ncb, uint32_t first, uint3
   // (the CSR stage's count of buckets left to whole workgroups: csr_from_chunks)
   SWA_TRY(swa_reserve(ctx, ctx->d_stream[kSbHeavy], csr_heavy_bytes(count)));
   clear_add(clears, ctx->d_stream[kSbHeavy].ptr, sizeof(uint32_t));
-  SWA_TRY(clear_launch(ctx, clears));
+  SWA_TRY(swa_clear_launch(ctx, clears));
   const bool zlds = 4ull * ctx->zobrist_len * sizeof(uint64_t) <= kMaxZobristLds;
   const uint32_t maxwords = (ctx->db.longest + 31u) >> 5;
   swa_t0(ctx, kTimeNetwork);
@@ -1619,18 +1226,11 @@ static int network_run(swa_ctx * ctx, int no_cluster_breaking, uint32_t first, u
     // Offsets are always complete; neighbours only if they fit.
     swa_t0(ctx, kTimeCsr);
     if (d_edge_list != nullptr) {
-      SWA_TRY(swa_reserve(ctx, ctx->d_seg_base, uint64_t(nseg) * sizeof(uint64_t)));
-      hipLaunchKernelGGL(k_seg_reduce, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
-                         nseg, reinterpret_cast<unsigned long long *>(st->stats) + kStatSeg, st->counters + kCounterFallback, &st->fallback_copy);
-      hipLaunchKernelGGL(k_seg_bases, dim3(1), dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(ctx->d_seg_fill.ptr), nseg,
-                         static_cast<unsigned long long *>(ctx->d_seg_base.ptr));
-      hipLaunchKernelGGL(k_seg_compact, dim3(std::min<uint32_t>(nseg, (uint32_t)ctx->num_cus * 8u)), dim3(256), 0, ctx->stream,
-                         static_cast<const uint64_t *>(ctx->d_edges.ptr), static_cast<const uint32_t *>(ctx->d_seg_fill.ptr),
-                         nseg, ctx->seg_cap, static_cast<const unsigned long long *>(ctx->d_seg_base.ptr), d_edge_list, cap);
+      SWA_TRY(swa_d1_seg_compact(ctx, nseg, d_edge_list, cap));
     } else {
       // CSR: the links sorted by source with the partition primitive
       stream_link_cap = std::max<uint64_t>(std::max<uint64_t>(cap, stream_link_cap), 2ull * count + 1024);
-      SWA_TRY(launch_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap, ctx->ix.anchor_usable));
+      SWA_TRY(swa_d1_csr_stream(ctx, first, count, nseg, stream_link_cap, d_offsets, d_neighbours, cap, ctx->ix.anchor_usable));
     }
     SWA_HIP(ctx, hipGetLastError());
     swa_t1(ctx, kTimeCsr);
@@ -1727,86 +1327,6 @@ extern "C" int swa_d1_network_edges_device(swa_ctx * ctx, int no_cluster_breakin
     return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_network_edges: bad range or null buffer");
   }
   return network_run_guarded(ctx, no_cluster_breaking, first, count, nullptr, nullptr, d_edge_list, cap, total);
-}
-
-// The link exchange of a multi-GPU job, second half (include/swarm_amd.h): the CSR of the sources [first, first + count)
-// from `lists` runs of (source << 32 | target) links as they lie on this context's device — the pieces a rank received, or
-// the ranks' lists gathered on one device (multi.hip) — by the partition + row kernels of the single-GPU step (levels by
-// source bits, then a wave per 256 sources) instead of a 64-bit radix sort of everything.  Every link lands in a row, so the
-// need is the sum of the counts: known before anything is launched, and nothing is read back.
-extern "C" int swa_d1_csr_from_lists(swa_ctx * ctx, const uint64_t * d_links, const uint64_t * starts, const uint64_t * counts, uint32_t lists,
-                                     uint32_t first, uint32_t count, uint64_t * d_offsets, uint32_t * d_neighbours, uint64_t cap, uint64_t * total) {
-  if (ctx == nullptr) { return SWA_E_ARG; }
-  if (count == 0 || (uint64_t)first + count > 0x100000000ull || d_offsets == nullptr || total == nullptr || (d_neighbours == nullptr && cap != 0) ||
-      (lists != 0 && (starts == nullptr || counts == nullptr))) {
-    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_csr_from_lists: bad range or null buffer");
-  }
-  SWA_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t chunks = std::max<uint32_t>(lists, 1u);      // (no list: one without links)
-  uint64_t all = 0, tiles = 2;
-  std::vector<uint64_t> h_start(chunks, 0);
-  std::vector<uint32_t> h_size(chunks, 0);
-  for (uint32_t r = 0; r < lists; ++r) {
-    if (counts[r] > 0xFFFFFFFFull) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_csr_from_lists: a list of more than 2^32 links"); }
-    h_start[r] = starts[r]; h_size[r] = (uint32_t)counts[r];
-    all += counts[r]; tiles += (counts[r] + 4095) / 4096;
-  }
-  if (all != 0 && d_links == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_csr_from_lists: null link buffer"); }
-  *total = all;
-  SWA_TRY(swa_reserve(ctx, ctx->d_seg_base, ((uint64_t)chunks * 3 / 2 + 2) * sizeof(uint64_t)));
-  auto * d_start = static_cast<uint64_t *>(ctx->d_seg_base.ptr);
-  auto * d_size = reinterpret_cast<uint32_t *>(d_start + chunks);
-  SWA_HIP(ctx, hipMemcpyAsync(d_start, h_start.data(), chunks * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  SWA_HIP(ctx, hipMemcpyAsync(d_size, h_size.data(), chunks * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the host vectors are temporaries)
-  SWA_TRY(csr_from_chunks(ctx, first, count, reinterpret_cast<const unsigned long long *>(d_links), d_start, 0, d_size, chunks, 0xFFFFFFFFu, tiles,
-                          all + 1, d_offsets, d_neighbours, cap));
-  if (all > cap) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_csr_from_lists: neighbour buffer too small"); }
-  return SWA_OK;
-}
-
-// The link exchange, first half: a flat link list split by the rank that owns each link's source (d1_stream.inc: k_links_split).
-extern "C" int swa_d1_links_split(swa_ctx * ctx, const uint64_t * d_links, uint64_t m, const uint32_t * bounds, uint32_t world,
-                                  uint64_t * d_out, uint64_t * d_counts) {
-  if (ctx == nullptr) { return SWA_E_ARG; }
-  if (world == 0 || world > kRouteMaxWorld || bounds == nullptr || d_counts == nullptr || (m != 0 && (d_links == nullptr || d_out == nullptr)) ||
-      ((reinterpret_cast<uintptr_t>(d_links) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_counts)) & 7u) != 0) {
-    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_links_split: bad argument (1..64 ranks, 8-byte aligned buffers)");
-  }
-  SplitArgs a{};
-  for (uint32_t r = 0; r <= world; ++r) {
-    if (r == 0 ? bounds[0] != 0 : bounds[r] < bounds[r - 1]) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_links_split: bounds must begin at 0 and ascend"); }
-    a.bounds[r] = bounds[r];
-  }
-  SWA_HIP(ctx, hipSetDevice(ctx->device));
-  SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, ((uint64_t)world + 1) * sizeof(uint64_t), ctx->stream));
-  if (m == 0) {                                              // (nothing but the clear — and the counts are final on return here too)
-    SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SWA_OK;
-  }
-  static_assert(kRouteMaxWorld * sizeof(uint64_t) <= sizeof(swa_status_block::cursors), "a run cursor for every rank");
-  auto * cursor = reinterpret_cast<unsigned long long *>(swa_status(ctx)->cursors);
-  SWA_HIP(ctx, hipMemsetAsync(cursor, 0, (uint64_t)world * sizeof(uint64_t), ctx->stream));
-  a.head = (uint32_t)((reinterpret_cast<uintptr_t>(d_links) >> 3) & 1u);
-  a.links = reinterpret_cast<const unsigned long long *>(d_links) - a.head;
-  a.end = a.head + m;
-  a.world = world;
-  a.counts = reinterpret_cast<unsigned long long *>(d_counts);
-  a.cursor = cursor;
-  a.out = reinterpret_cast<unsigned long long *>(d_out);
-  const uint64_t tiles = (a.end + kSplitTile - 1) / kSplitTile;
-  const dim3 grid((unsigned)std::min<uint64_t>(tiles, (uint64_t)ctx->num_cus * 8));
-  hipLaunchKernelGGL(k_links_split<false>, grid, dim3(kSplitThreads), 0, ctx->stream, a);
-  hipLaunchKernelGGL(k_links_split<true>, grid, dim3(kSplitThreads), 0, ctx->stream, a);
-  SWA_HIP(ctx, hipGetLastError());
-  // ONE read, of the links no rank owns, into the pinned mirror of the status block: the counts are final when this returns
-  uint64_t * beyond = ctx->h_status->cursors;
-  SWA_HIP(ctx, hipMemcpyAsync(beyond, d_counts + world, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (*beyond != 0) {
-    return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_links_split: " + std::to_string(*beyond) + " links with a source beyond the last rank's range (not written)");
-  }
-  return SWA_OK;
 }
 
 extern "C" int swa_d1_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count, uint32_t world, uint32_t * d_ids, uint64_t cap,

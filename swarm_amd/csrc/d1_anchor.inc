@@ -38,7 +38,6 @@ __device__ __forceinline__ uint32_t anchor_owner(uint64_t mixed, uint32_t world)
 }
 
 constexpr uint32_t kRoutePerThread = 8;
-constexpr uint32_t kRouteMaxWorld = 64;
 
 __global__ __launch_bounds__(256) void k_anchor_route(const uint64_t * __restrict__ seqs, const uint64_t * __restrict__ seq_off,
                                                       const uint32_t * __restrict__ seqlen, uint32_t first, uint32_t count,

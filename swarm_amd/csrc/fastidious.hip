@@ -400,7 +400,7 @@ static int fastidious_pair_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_hea
   const uint32_t item_cap = item_cap64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)item_cap64;
   SWA_TRY(join_reserve(ctx, asize_max, n, 3u, member_cap, item_cap));
   SWA_TRY(swa_reserve(ctx, ctx->d_scan_tmp, ((asize_max + kScanOffsetsTile - 1) / kScanOffsetsTile) * sizeof(uint64_t)));
-  // (the offsets by the three-launch scan of d1.hip, not rocPRIM's as at d >= 2: DESIGN.md 3.5 has the measurement)
+  // (the offsets by the three-launch scan of d1_part.hip, not rocPRIM's as at d >= 2: DESIGN.md 3.5 has the measurement)
   auto scan = [&](const JoinTable & t) -> int { return swa_scan_offsets(ctx, t.tot, (uint32_t)t.asize, t.offsets); };
   if (ctx->fast_pair_cap == 0) {
     ctx->fast_pair_cap = 4ull * n_light + (1ull << 20);

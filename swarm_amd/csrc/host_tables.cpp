@@ -187,8 +187,8 @@ extern "C" int swa_d1_fastidious_plan_modes(uint32_t longest, uint32_t pair_long
 
 extern "C" uint32_t swa_d1_fastidious_sites_cap(uint32_t sites_cap) { return swa_fast_sites_cap_in_effect(sites_cap); }
 
-// ---- the forms of the key partition and of the link partition (d1.hip: build_stream_index, csr_from_chunks) ----------
-// Pure host arithmetic, no HIP call: what d1.hip launches and what swa_d1_part_plan reports have this one source.
+// ---- the forms of the key partition and of the link partition (d1.hip: build_stream_index; d1_part.hip: csr_from_chunks) ----------
+// Pure host arithmetic, no HIP call: what swa_part_run (d1_part.hip) launches and what swa_d1_part_plan reports have this one source.
 
 // total_bits spread over as few levels of at most max_bits as hold them, the earlier levels one bit wider where it does not divide
 swa_part_levels swa_plan_levels(uint32_t total_bits, uint32_t max_bits) {

@@ -342,7 +342,7 @@ static int d1_network_on_root(swa_multi * m, int no_cluster_breaking, bool resid
     rc = gather_to_root_v(m, src, m->gathered.ptr, count, sizeof(uint64_t));
     if (rc != SWA_OK) { return rc; }
   }
-  // 3. rank 0: the gathered lists -> CSR (-> host).  The partition + row kernels of the single-GPU step (d1.hip: csr_from_chunks,
+  // 3. rank 0: the gathered lists -> CSR (-> host).  The partition + row kernels of the single-GPU step (d1_part.hip: csr_from_chunks,
   // the ranks' lists as the chunks of its first level) where round 3 ran a 64-bit radix sort over all links.
   swa_ctx * c0 = m->ctx[0];
   if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }

@@ -194,7 +194,7 @@ struct swa_d1_index {
   uint32_t anchor_w = 32;        // width of the anchor windows in nt: 32, 64 or 128 (wider: fewer pairs per group; needs 2 w + 1 nt)
   bool head_clear_pending = false;   // index_build has left the clear of the status block's head to the streaming build's own clear
   bool guard_index = false;      // guard[0, kGuardCall) of the status block describe the index in place (made by the streaming build since the last clear)
-  // streaming index build / CSR assembly (d1_stream.inc)
+  // streaming index build (d1_stream.inc) / CSR assembly (d1_part.hip)
   uint32_t list_counts[2 * 4 * 8] = {};   // items per work list of the index in place ([index][width class][8]: the status block's counters + kCounterBase)
   bool list_counts_ready = false;
   uint64_t list_regions_items = 0;   // entries of an index's item buffer (d1.hip: list_regions)
@@ -345,7 +345,7 @@ struct swa_ctx {
   swa_dbuf d_dn_keys, d_dn_vals;
   uint32_t dn_owner_rank = 0, dn_owner_world = 1;   // swa_dn_set_ownership: this context finds the pairs of the window groups (and short sequences) it owns
 
-  swa_dbuf d_stream[30];         // streaming index build / CSR assembly (d1_stream.inc): indexed by kSb* (below)
+  swa_dbuf d_stream[30];         // streaming index build (d1_stream.inc) / CSR assembly (d1_part.hip): indexed by kSb* (below)
 
   uint32_t guard_retries = 0;                  // steps repeated after the guard found counts that did not balance
   swa_dbuf d_words_stage;                      // swa_db_stage_words: the reader's word pools, file order
@@ -406,7 +406,7 @@ void swa_release(swa_dbuf & buf);
 int swa_hash_sequences(swa_ctx * ctx);                           // d1.hip: Zobrist table + d_seqhash + d_aux
 
 // ---- what fastidious.hip takes from d1.hip ----------------------------------------------------------------------------
-// Host functions, defined in d1.hip, whose kernels stay in its code object.  All enqueue on ctx->stream and return SWA_OK
+// Host functions, defined in d1.hip (swa_scan_offsets: in d1_part.hip), whose kernels stay in that unit's code object.  All enqueue on ctx->stream and return SWA_OK
 // or the error they recorded.
 int swa_prepare_hashing(swa_ctx * ctx);        // the Zobrist table for this database's longest sequence in HBM (uploaded when its length changes), room for d_seqhash / d_aux
 int swa_ensure_full_index(swa_ctx * ctx);      // hashes of ALL amplicons, the database-wide table and its Bloom filter: built unless swa_d1_index::full_index says they stand
@@ -500,7 +500,7 @@ swa_fast_plan swa_fast_plan_modes(uint32_t longest, uint32_t pair_longest, int l
                                   uint32_t sites_cap);
 void swa_fast_plan_report(const swa_fast_plan & p, uint32_t out[8]);
 
-// The forms of the two partitions of the d = 1 step (host_tables.cpp: pure arithmetic; d1.hip launches from it,
+// The forms of the two partitions of the d = 1 step (host_tables.cpp: pure arithmetic; d1.hip and d1_part.hip launch from it,
 // swa_d1_part_plan_for / swa_d1_csr_plan_for / swa_d1_part_plan report it)
 #define SWA_PART_MAX_BITS 9u                        // bits per partition level (512 bins); the one-level key partition takes 10
 #define SWA_PART_WIDE_BITS 10u

@@ -1,5 +1,5 @@
 """Inputs and restated arithmetic for the tests of SWA_FAST_LONG=pairs and SWA_FAST_COUNT=sites (swarm_amd/csrc/d1_fast.inc:
-k_fast_count_sites_words; d1.hip: fast_plan), on top of tests/fastidious_sets.py and tests/fastidious_split_sets.py.  Not
+k_fast_count_sites_words; fastidious.hip: fast_plan), on top of tests/fastidious_sets.py and tests/fastidious_split_sets.py.  Not
 product code.
 
 The sets are fastidious_split_sets' by name: "1005", "1025", "2049" = edit_atlas(L, L, small) alone —

@@ -1,4 +1,4 @@
-"""Inputs for the tests of SWA_FAST_LONG=split (swarm_amd/csrc/d1.hip: fast_plan; include/swarm_amd.h), built from
+"""Inputs for the tests of SWA_FAST_LONG=split (swarm_amd/csrc/fastidious.hip: fast_plan; include/swarm_amd.h), built from
 tests/fastidious_sets.py.  Not product code.
 
 The pair route holds sequences of up to CAP = 1004 nt.  Under the switch, a database with longer sequences keeps the

@@ -1,4 +1,4 @@
-"""Inputs for the tests of the d = 1 plain route (swarm_amd/csrc/d1.hip: enumerate_variants, k_d1_probe, k_d1_flex,
+"""Inputs for the tests of the d = 1 plain route (swarm_amd/csrc/d1_probe.inc: enumerate_variants, k_d1_probe; fastidious.hip: k_d1_flex,
 fastidious_bloom_route), in closed form.  Not product code.
 
 enumerate_variants deals the positions 0 .. len of a sequence to the 64 lanes of a wave: lane l owns [l K, (l + 1) K),

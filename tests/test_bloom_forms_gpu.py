@@ -1,4 +1,4 @@
-"""The Bloom route of the --fastidious pass (swarm_amd/csrc/d1.hip: fastidious_bloom_route, k_d1_flex<ZLDS, PASS 0 / 1>,
+"""The Bloom route of the --fastidious pass (swarm_amd/csrc/fastidious.hip: fastidious_bloom_route, k_d1_flex<ZLDS, PASS 0 / 1>,
 k_d1_probe<ZLDS, 1>) against S.oracle_fastidious, at the edges of enumerate_variants' lane partition and through every
 branch of its batch loop.  It serves every pair with a member shorter than 112 nt and every pair of a database whose
 longest sequence exceeds 1004 nt.

@@ -1,4 +1,4 @@
-"""Every kernel form of the --fastidious pass (seam B2; swarm_amd/csrc/d1.hip: fast_plan, d1_fast.inc) against the
+"""Every kernel form of the --fastidious pass (seam B2; swarm_amd/csrc/fastidious.hip: fast_plan, d1_fast.inc) against the
 oracle, with the longest sequence of the database on each boundary of the dispatch and next to it.
 
 The pass chooses its kernels from the longest sequence alone (swa_d1_fastidious_plan reports the choice, the launches

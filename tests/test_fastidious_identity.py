@@ -363,7 +363,7 @@ def test_two_edit_test_on_register_words_is_exact():
     assert yes > 1500 and no > 500
 
 
-# ---- the work item list of the pair route (d1.hip: fastidious_pair_route; group_join.inc: k_join_items<FastTiles>) ----------
+# ---- the work item list of the pair route (fastidious.hip: fastidious_pair_route; group_join.inc: k_join_items<FastTiles>) ----------
 def _items_of(l: int, h: int) -> int:
     """k_join_items<FastTiles>: a group's 64 x 64 tiles, dealt to at most kFastStride = 64 items; none without both kinds"""
     if l == 0 or h == 0:
@@ -402,7 +402,7 @@ def test_item_cap_holds_for_adversarial_group_shapes():
             assert sum(_items_of(l, h) for l, h in groups) <= _item_cap(n_light, n_heavy), (name, n)
 
 
-# ---- the dispatch table of the pass (d1.hip: fast_plan), restated in tests/fastidious_sets.py -----------------------------
+# ---- the dispatch table of the pass (fastidious.hip: fast_plan), restated in tests/fastidious_sets.py -----------------------------
 def test_restated_plan_gives_the_dispatch_table():
     spans = []                                                # (first, last, plan[:5] + [plan[6]]) of every run of equal plans
     for longest in range(34, 3300):

@@ -1,5 +1,5 @@
 """SWA_FAST_LONG=pairs and SWA_FAST_COUNT=sites on the GPU (seam B2; swarm_amd/csrc/d1_fast.inc: k_fast_count_sites_words,
-d1.hip: fast_plan) against the oracle.
+fastidious.hip: fast_plan) against the oracle.
 
   pairs   a database whose longest sequence exceeds 1004 nt keeps the pair route for every pair whose two lengths lie in
           [112, C], C = 327 584 nt or SWA_FAST_SITES_CAP; the count kernel of the whole pass is k_fast_count_sites_words

@@ -1,4 +1,4 @@
-"""SWA_FAST_LONG=split on the GPU (seam B2; swarm_amd/csrc/d1.hip: fast_plan, d1_fast.inc) against the oracle: a database
+"""SWA_FAST_LONG=split on the GPU (seam B2; swarm_amd/csrc/fastidious.hip: fast_plan, d1_fast.inc) against the oracle: a database
 with sequences longer than the pair route's cap (1004 nt) keeps the pair route for the pairs whose two lengths lie in
 [112, cap]; every other pair takes the Bloom route.  Without the switch such a database takes the Bloom route for every
 pair (tests/test_fastidious_forms_gpu.py pins that).

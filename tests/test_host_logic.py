@@ -576,7 +576,7 @@ def test_hostdb_errors_in_the_reference_order(tmp_path, text, d):
 
 
 def test_xcd_tile_mapping_visits_every_tile_once():
-    """swarm_amd/csrc/d1_stream.inc: xcd_tile(v) — which tile the workgroup of turn v takes, so that runs of 2^run_bits
+    """swarm_amd/csrc/d1_internal.h: xcd_tile(v) — which tile the workgroup of turn v takes, so that runs of 2^run_bits
     consecutive tiles stay on XCD v mod 8.  The partition kernels walk v over [0, tiles rounded up to 8 << run_bits) and
     skip tiles beyond the end: that must reach every tile exactly once, and a run must stay on one XCD.  (The formula
     restated; the kernels themselves are checked end to end by tests/test_stream_gpu.py.)"""

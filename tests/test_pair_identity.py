@@ -300,7 +300,7 @@ def test_shortened_chains_answer_as_the_full_chains(W, NW):
 
 # ---- round 6: the tiled kernel's items and the room the host gives them -----------------------------------------------------------
 def _tiled_item_count(members: int, cols: int = 4) -> int:
-    """tiled_item_count (d1_anchor.inc): a row tile of 64 members against its column tiles, `cols` (kTiledCols) at a time"""
+    """tiled_item_count (d1_common.inc): a row tile of 64 members against its column tiles, `cols` (kTiledCols) at a time"""
     tiles = (members + 63) // 64
     return sum((tiles - r + cols - 1) // cols for r in range(tiles))
 

@@ -1,5 +1,5 @@
-"""The d = 1 network on the plain route (swarm_amd/csrc/d1.hip: enumerate_variants, k_seqhash, k_table_insert,
-k_d1_probe<ZLDS, MODE 0 / 2>, the per-wave link segments) against the oracle at the places where that code changes
+"""The d = 1 network on the plain route (swarm_amd/csrc/d1_probe.inc: enumerate_variants, k_d1_probe<ZLDS, MODE 0 / 2>;
+d1.hip: k_seqhash, k_table_insert, the per-wave link segments) against the oracle at the places where that code changes
 behaviour.  Every other route falls back on it; the other tests reach it through random sets only.
 
   lane edges   enumerate_variants deals positions [l K, (l + 1) K) to lane l, K = ceil((len + 1) / 64): full stars (every

@@ -1,4 +1,4 @@
-"""The two ways k_csr_bucket (swarm_amd/csrc/d1_stream.inc) sorts the rows of the CSR, restated on the CPU with the same
+"""The two ways k_csr_bucket (swarm_amd/csrc/d1_part.hip) sorts the rows of the CSR, restated on the CPU with the same
 index arithmetic and checked against sorted(): the bitonic network over a row padded with the largest value to 4 / 8 /
 16 / 32 entries (sort_row_in_registers: comparator (i, i ^ j) ascending where i & k == 0, descending otherwise, for
 k = 2, 4, .. N and j = k / 2, .. 1), and the rank sort of a row of up to 64 targets by one wave (wave_rank_sort64: a

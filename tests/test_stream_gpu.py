@@ -1,4 +1,4 @@
-"""The streaming index build and CSR assembly (swarm_amd/csrc/d1_stream.inc) on the GPU, stage by stage: in fresh
+"""The streaming index build and CSR assembly (swarm_amd/csrc/d1_stream.inc, d1_part.hip) on the GPU, stage by stage: in fresh
 processes (first use of the device, fresh allocations) the d=1 network under the streaming index with either CSR
 assembly equals the oracle's — whole database, a sub-range, no-cluster-breaking — the amplicon
 lines equal the database they were made from, and the anchor indexes as they lie in HBM are consistent (every amplicon

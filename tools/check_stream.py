@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/check_stream.py [n=200000] — triage of the streaming index build / CSR assembly (d1_stream.inc) on the GPU:
+"""tools/check_stream.py [n=200000] — triage of the streaming index build / CSR assembly (d1_stream.inc, d1_part.hip) on the GPU:
 the d=1 network of one synthetic set under the streaming index and the streaming CSR assembly, compared with the C
 oracle's network (whole database and one sub-range), and the amplicon lines read back and compared with the database,
 so that a difference names the stage that made it.  Exit status 0 = all identical."""

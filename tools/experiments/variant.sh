@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/experiments/variant.sh NAME "-DX=1 ..." : libswarm_amd_NAME.so = this tree with one unit compiled under extra flags
-# UNIT=fastidious (default d1): the unit — d1.hip (the d = 1 network) or fastidious.hip (the --fastidious pass)
+# UNIT=d1 (default: index build and network step) | d1_part (partition and rows: k_part_*, k_flat_*, k_csr_bucket*, k_seg_*, k_links_split) |
+# fastidious (the --fastidious pass); tools/experiments/regs.sh lists every kernel's unit
 # (A/B of kernel variants on one lease: SWARM_AMD_LIB=swarm_amd/lib/libswarm_amd_NAME.so python bench.py ...)
 set -e
 cd "$(dirname "$0")/../../swarm_amd/csrc"
