@@ -667,7 +667,7 @@ int swa_dn_tables_fetch(swa_ctx * ctx, uint32_t * radius, uint64_t * mass, uint3
 /* out3 = {q-gram comparisons, aligned pairs, kernel launches} of the last swa_dn_graph */
 int swa_dn_graph_totals(swa_ctx * ctx, uint64_t * out3);
 
-/* ---- d = 1 on several GPUs of one node --------------------------------
+/* ---- d = 1 (and, below, d = 0) on several GPUs of one node --------------------------------
    Replaces the thread fan-out of src/algod1.cc:1166-1167 / src/utils/threads.h:145-162: one context, stream and
    host thread per listed device inside the calling process; the database replicated, the probing divided by
    ownership of anchor groups (swa_d1_set_ownership): routed index build (every rank keys its own slice and the key
@@ -712,6 +712,30 @@ int  swa_multi_d1_last_build(const swa_multi * m);
    its share, the candidates are combined in rank 0's HBM, where swa_d1_graft_device(ctx0, NULL, ...) reads them; graft_cand
    may be NULL: they are then not downloaded.  counters as swa_multi_d1_fastidious. */
 int  swa_multi_d1_fastidious_resident(swa_multi * m, uint64_t light_nt, uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
+
+/* ---- d = 0 on several GPUs ------------------------------------------------------------------------------------------
+   The bucket search of dereplicating() (src/derep.cc:276-354) divided among the ranks by ownership of the sequence
+   hashes.  The database is replicated (swa_multi_db_upload); rank r hashes the slice [n r / world, n (r + 1) / world) only,
+   groups its (hash, id) records by owner on the GPU — runs sized exactly from a count pass: a read with 10^6 copies sends
+   10^6 records to one owner, nothing overflows —, the records travel all-to-all (grouped ncclSend / ncclRecv, device-to-
+   device copies between ranks on one GPU; one rank takes the same path), every owner runs the search of swa_derep over
+   what it received (all copies of a sequence are there, so the re-key rounds stay local), and rank 0 gathers
+   first_identical << 32 | id of every read and writes the array into its HBM.
+   swa_multi_derep_resident (src/derep.cc:276-354) = swa_derep_resident on swa_multi_ctx(m, 0): swa_d0_cluster_device,
+   swa_d0_cluster_fetch and swa_d0_cluster_resident then work on that context.  On every rank the call ends the previous
+   dereplication and a d = 1 index; no rank but rank 0 holds a resident array afterwards (swa_d0_cluster_device on another
+   rank's context: SWA_E_ARG), none after a failure.  SWA_E_INTERNAL if the owners do not hold exactly n records.
+   swa_multi_derep (src/derep.cc:276-354) = swa_derep: the resident form plus one download, first_identical = u32[n].
+   swa_multi_derep_owner_for (src/derep.cc:276-354 keeps one table; here a hash has one owner): *owner = the rank of
+   `world` (1 .. 64, SWA_E_ARG otherwise) that dereplicates every read whose Zobrist hash is `hash` — a pure function of the
+   full 64-bit hash of the first round (the 64-bit finaliser of MurmurHash3, then the high word of its product with world),
+   not of the narrowed or re-mixed key of a later round; needs no device.
+   swa_multi_derep_totals (src/derep.cc:276-354), of the last call: received[world] = the records every owner got (their sum
+   is n; 0: an empty inbox), out2 = {rounds of the owner that needed most, records routed}. */
+int  swa_multi_derep_resident(swa_multi * m);
+int  swa_multi_derep(swa_multi * m, uint32_t * first_identical);
+int  swa_multi_derep_owner_for(uint64_t hash, uint32_t world, uint32_t * owner);
+int  swa_multi_derep_totals(swa_multi * m, uint64_t * received, uint64_t * out2);
 
 
 /* ---- d >= 2 on several GPUs (second paragraph) --------------------------------------------------

@@ -1576,6 +1576,29 @@ MULTI_BUILD_NONE, MULTI_BUILD_ROUTED, MULTI_BUILD_STREAMED, MULTI_BUILD_OVERFLOW
 MULTI_BUILD_NAMES = ("none", "routed records", "streamed on request", "streamed after overflow")
 
 
+_MULTI_DEREP_EXPORTS = ["swa_multi_derep_resident", "swa_multi_derep", "swa_multi_derep_owner_for", "swa_multi_derep_totals"]
+EXPORTS.extend(_MULTI_DEREP_EXPORTS)
+
+
+def _declare_multi_derep(lib) -> None:
+    lib.swa_multi_derep_resident.argtypes = [C.c_void_p]
+    lib.swa_multi_derep.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_multi_derep_owner_for.argtypes = [C.c_uint64, C.c_uint32, u32p]
+    lib.swa_multi_derep_totals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def derep_owner_for(hash: int, world: int) -> int:
+    """swa_multi_derep_owner_for: the rank (of world, 1 .. 64) that dereplicates every read whose Zobrist hash is `hash` in
+    MultiContext.derep — a pure function of the full 64-bit hash; needs no device."""
+    lib = load_library()
+    _declare_multi_derep(lib)
+    owner = C.c_uint32(0)
+    rc = lib.swa_multi_derep_owner_for(int(hash) & 0xFFFFFFFFFFFFFFFF, int(world), C.byref(owner))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_multi_derep_owner_for: bad argument")
+    return int(owner.value)
+
+
 class MultiContext:
     """swa_multi_*: one context + stream + host thread per listed device inside the library; RCCL for the exchange
     when the devices are distinct, device-to-device copies when a device is listed twice."""
@@ -1599,6 +1622,7 @@ class MultiContext:
         lib.swa_multi_d1_fastidious_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.swa_multi_dn_graph_resident.argtypes = [C.c_void_p, C.c_int, u64p]
         lib.swa_multi_d1_last_build.argtypes = [C.c_void_p]
+        _declare_multi_derep(lib)
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
         rc = lib.swa_multi_create(arr, len(devices), C.byref(h))
@@ -1654,6 +1678,26 @@ class MultiContext:
         if rc == SWA_E_CAPACITY:
             self._check(lib.swa_multi_dn_graph(self.h, int(no_cluster_breaking), _ptr(offsets), _ptr(nb), _ptr(df), total.value, C.byref(total)))
         return offsets, nb[:total.value], df[:total.value]
+
+    # ---- d = 0
+    def derep_resident(self) -> None:
+        """swa_multi_derep_resident: the identical-sequence search divided among the ranks, first_identical left in rank 0's
+        HBM (ctx(0): d0_cluster_device, D0Clusters.from_device)."""
+        self._check(self.lib.swa_multi_derep_resident(self.h))
+
+    def derep(self) -> np.ndarray:
+        """swa_multi_derep: derep_resident plus the download — per amplicon the smallest index with the identical sequence."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        self._check(self.lib.swa_multi_derep(self.h, _ptr(out)))
+        return out
+
+    def derep_totals(self) -> dict:
+        """swa_multi_derep_totals, of the last derep / derep_resident call: received (the records every owner got), rounds (of
+        the owner that needed most), routed (records that travelled: n)."""
+        received = np.zeros(self.lib.swa_multi_size(self.h), dtype=np.uint64)
+        out2 = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.swa_multi_derep_totals(self.h, _ptr(received), _ptr(out2)))
+        return {"received": received, "rounds": int(out2[0]), "routed": int(out2[1])}
 
     def ctx(self, rank: int = 0) -> "Context":
         """swa_multi_ctx: rank's context as a Context that neither owns nor closes the handle (it lives as long as this

@@ -76,30 +76,205 @@ __global__ __launch_bounds__(256) void k_derep_resolve(const uint64_t * __restri
   }
 }
 
-}  // namespace
+// ---- several GPUs: the reads of a rank's slice travel to the rank that owns their hash -----------------------------------
+// (swa_multi_derep_resident, multi.hip.)  Rank r hashes the slice [n r / world, n (r + 1) / world) only — k_derep_hash_slice,
+// the hash stream of k_seqhash without the XOR streams and the anchor metadata that only d = 1 reads —, and
+// k_derep_route<false / true> groups the (hash, id) records by owner in the count-then-place form of k_links_split
+// (d1_part.hip).  The owner is a function of the full 64-bit hash, re-mixed so that it shares no bits with the slot
+// k_derep_claim takes from it and never changes with the round: all copies of a sequence meet on one rank in every round.
 
-// What swa_derep does up to the download: first_identical stays in HBM (d_graft) for swa_d0_cluster_device.
-extern "C" int swa_derep_resident(swa_ctx * ctx) {
-  if (ctx == nullptr) { return SWA_E_ARG; }
-  ctx->dr = {};                                             // the previous dereplication and its tables end here
-  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: no database"); }
-  SWA_HIP(ctx, hipSetDevice(ctx->device));
+// fmix64 of MurmurHash3, then the high word of the product with world: [0, world) without a division
+__host__ __device__ __forceinline__ uint32_t derep_owner(uint64_t h, uint32_t world) {
+  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull;
+  h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull;
+  h ^= h >> 33;
+#ifdef __HIP_DEVICE_COMPILE__
+  return (uint32_t)__umul64hi(h, (uint64_t)world);
+#else
+  return (uint32_t)(((unsigned __int128)h * world) >> 64);
+#endif
+}
+
+template <bool ZLDS>
+__global__ __launch_bounds__(256) void k_derep_hash_slice(const uint64_t * __restrict__ seqs, const uint64_t * __restrict__ seq_off,
+                                                          const uint32_t * __restrict__ seqlen, const uint64_t * __restrict__ zobrist,
+                                                          uint32_t zlen, uint32_t first, uint32_t count, uint64_t * __restrict__ out) {
+  extern __shared__ uint64_t lds[];
+  const uint64_t * zob = zobrist;
+  if (ZLDS) {
+    for (uint32_t i = threadIdx.x; i < 4u * zlen; i += blockDim.x) { lds[i] = zobrist[i]; }
+    __syncthreads();
+    zob = lds;
+  }
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+    const uint64_t * s = seqs + seq_off[first + k];
+    const uint32_t len = seqlen[first + k];
+    uint64_t h = 0, word = 0;
+    for (uint32_t p = 0; p < len; ++p) {
+      if ((p & 31u) == 0u) { word = s[p >> 5]; }
+      h ^= zob[4u * p + (uint32_t)(word & 3u)];
+      word >>= 2;
+    }
+    out[k] = h;
+  }
+}
+
+// Record k of the slice is (hash[k], first + k).  Two launches over tiles of 2048 records, a lane reading two hashes at a
+// time (16 bytes; `hash` is 16-byte aligned):
+//   <false>  counts: a histogram per workgroup in LDS over all its tiles, then ONE global atomic per destination it met;
+//   <true>   places: every workgroup turns the counts into the runs' first places (a scan over at most 64 values by one
+//            wave), and per tile: the histogram in LDS, whose atomic returns the record's rank among the tile's records
+//            for its owner, one global atomic per owner the tile met to reserve room in that run, the tile's records put
+//            in owner order in LDS and written as one contiguous piece per owner — hashes to out_hash, ids to out_id, at
+//            the same position.
+// The runs are exactly as long as the counts say: a read with 10^6 copies sends 10^6 records to one owner, and nothing
+// overflows.  The order inside a run depends on scheduling; what the owner makes of it, a minimum, does not.
+constexpr uint32_t kDerepMaxWorld = 64, kRouteTile = 2048, kRouteThreads = 256;
+constexpr uint32_t kRoutePairs = kRouteTile / (2u * kRouteThreads);
+struct RouteArgs {
+  const unsigned long long * hash;
+  uint32_t first, count, world;
+  uint32_t * counts;                 // [world] records per owner
+  uint32_t * cursor;                 // [world] (places) records of every run that have their place so far
+  unsigned long long * out_hash;     // [count]
+  uint32_t * out_id;                 // [count]
+};
+
+template <bool PLACE>
+__global__ __launch_bounds__(kRouteThreads) void k_derep_route(const RouteArgs a) {
+  __shared__ uint32_t hist[kDerepMaxWorld], lstart[kDerepMaxWorld], gbase[kDerepMaxWorld];
+  __shared__ uint32_t present;
+  __shared__ __attribute__((aligned(16))) unsigned long long stage_h[PLACE ? kRouteTile : 1];
+  __shared__ uint32_t stage_i[PLACE ? kRouteTile : 1];
+  const uint32_t tid = threadIdx.x, world = a.world;
+  if (tid < kDerepMaxWorld) { hist[tid] = 0u; }
+  // (places) first place of run `tid`: the counts before it — lane d of the first wave keeps it
+  uint32_t run_start = 0u;
+  if (PLACE && tid < 64u) {
+    const uint32_t mine = tid < world ? a.counts[tid] : 0u;
+    uint32_t incl = mine;
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64); if (tid >= d) { incl += up; } }
+    run_start = incl - mine;
+  }
+  __syncthreads();
+  const uint64_t tiles = ((uint64_t)a.count + kRouteTile - 1u) / kRouteTile;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    unsigned long long rec[2u * kRoutePairs];
+    uint32_t valid = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kRoutePairs; ++k) {
+      const uint64_t j = t * kRouteTile + (uint64_t)k * (2u * kRouteThreads) + 2u * tid;
+      const bool v0 = j < a.count, v1 = j + 1u < a.count;
+      rec[2u * k] = rec[2u * k + 1u] = 0ull;
+      if (v1) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(a.hash + j);
+        rec[2u * k] = (unsigned long long)q.x | (unsigned long long)q.y << 32;
+        rec[2u * k + 1u] = (unsigned long long)q.z | (unsigned long long)q.w << 32;
+      } else if (v0) { rec[2u * k] = a.hash[j]; }
+      valid |= (v0 ? 1u : 0u) << (2u * k) | (v1 ? 1u : 0u) << (2u * k + 1u);
+    }
+    uint32_t pos[2u * kRoutePairs];                              // owner << 16 | rank among the tile's records for it
+#pragma unroll
+    for (uint32_t k = 0; k < 2u * kRoutePairs; ++k) {
+      pos[k] = 0u;
+      if ((valid >> k & 1u) != 0u) {
+        const uint32_t d = derep_owner(rec[k], world);
+        pos[k] = d << 16 | atomicAdd(&hist[d], 1u);
+      }
+    }
+    if (!PLACE) { continue; }                                    // (the histogram runs on over the workgroup's tiles)
+    __syncthreads();
+    if (tid < 64u) {
+      // the tile's records per owner, where each owner's piece begins in the staging area, and the room reserved for it
+      const uint32_t h = tid < world ? hist[tid] : 0u;
+      uint32_t incl = h;
+#pragma unroll
+      for (unsigned d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64); if (tid >= d) { incl += up; } }
+      lstart[tid] = incl - h;
+      if (h != 0u) { gbase[tid] = run_start + atomicAdd(&a.cursor[tid], h); }
+      if (tid == 63u) { present = incl; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < 2u * kRoutePairs; ++k) {
+      if ((valid >> k & 1u) != 0u) {
+        const uint32_t at = lstart[pos[k] >> 16] + (pos[k] & 0xFFFFu);
+        stage_h[at] = rec[k];
+        stage_i[at] = a.first + (uint32_t)(t * kRouteTile) + (k >> 1) * (2u * kRouteThreads) + 2u * tid + (k & 1u);
+      }
+    }
+    __syncthreads();
+    const uint32_t staged = present;
+#pragma unroll
+    for (uint32_t k = 0; k < kRouteTile / kRouteThreads; ++k) {
+      const uint32_t j = k * kRouteThreads + tid;
+      if (j < staged) {
+        // the owner whose piece holds place j: the last d with lstart[d] <= j (an owner the tile did not meet begins where
+        // the next one does; behind the last rank every lstart is `staged`)
+        uint32_t d = 0;
+#pragma unroll
+        for (uint32_t step = kDerepMaxWorld / 2u; step != 0u; step >>= 1) { if (lstart[d + step] <= j) { d += step; } }
+        const uint32_t g = gbase[d] + (j - lstart[d]);
+        if (g < a.count) { a.out_hash[g] = stage_h[j]; a.out_id[g] = stage_i[j]; }   // (always, when the slice is what the counting launch saw)
+      }
+    }
+    if (tid < kDerepMaxWorld) { hist[tid] = 0u; }
+    __syncthreads();
+  }
+  if (!PLACE) {
+    __syncthreads();
+    if (tid < world && hist[tid] != 0u) { atomicAdd(&a.counts[tid], hist[tid]); }
+  }
+}
+
+// an owner: the hashes it received into its own d_seqhash, where k_derep_claim looks them up by id
+__global__ __launch_bounds__(256) void k_derep_scatter(const uint64_t * __restrict__ in_hash, const uint32_t * __restrict__ in_id, uint32_t count,
+                                                       uint32_t n, uint64_t * __restrict__ seqhash) {
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < count; t += gridDim.x * blockDim.x) {
+    const uint32_t i = in_id[t];
+    if (i < n) { seqhash[i] = in_hash[t]; }
+  }
+}
+
+// ... and what it found, for the way home: first_identical[id] << 32 | id
+__global__ __launch_bounds__(256) void k_derep_pack(const uint32_t * __restrict__ in_id, uint32_t count, uint32_t n,
+                                                    const uint32_t * __restrict__ first_identical, unsigned long long * __restrict__ packed) {
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < count; t += gridDim.x * blockDim.x) {
+    const uint32_t i = in_id[t];
+    packed[t] = (unsigned long long)(i < n ? first_identical[i] : SWA_NO_AMPLICON) << 32 | i;
+  }
+}
+
+// rank 0: the owners' packed words into first_identical[]
+__global__ __launch_bounds__(256) void k_derep_home(const unsigned long long * __restrict__ packed, uint32_t count, uint32_t n,
+                                                    uint32_t * __restrict__ first_identical) {
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < count; t += gridDim.x * blockDim.x) {
+    const unsigned long long w = packed[t];
+    if ((uint32_t)w < n) { first_identical[(uint32_t)w] = (uint32_t)(w >> 32); }
+  }
+}
+
+// The rounds of the search over the amplicons of `list` (nullptr: all n of the database) against a table of `tsize` slots:
+// claim, resolve, and again with a re-mixed key over whoever failed verification, until nobody is left.  d_seqhash holds the
+// hash of every listed amplicon; first_identical[i] of every listed i is left in d_graft.  Serves swa_derep_resident (every
+// amplicon, swa_hashtable_size(n)) and an owner of swa_multi_derep_resident (its inbox, swa_hashtable_size(received)).
+// *rounds (may be null): how many rounds ran.
+int derep_rounds(swa_ctx * ctx, const uint32_t * list, uint32_t count, uint64_t tsize, uint32_t * rounds) {
   const uint32_t n = ctx->db.n;
-  SWA_TRY(swa_hash_sequences(ctx));
   // test hook: narrow the key so that distinct sequences collide (exercises the re-key rounds)
   uint32_t keybits = 64;
   if (const char * bits = std::getenv("SWA_DEREP_KEY_BITS")) {
     const int b = std::atoi(bits);
     if (b >= 1 && b < 64) { keybits = (uint32_t)b; }
   }
-  const uint64_t tsize = swa_hashtable_size(n);
   SWA_TRY(swa_reserve(ctx, ctx->d_table, tsize * sizeof(unsigned long long)));        // keys
   SWA_TRY(swa_reserve(ctx, ctx->d_counts, tsize * sizeof(uint32_t)));                 // minimum claimant per slot
   SWA_TRY(swa_reserve(ctx, ctx->d_cursor, uint64_t(n) * sizeof(uint32_t)));           // slot of every amplicon
   SWA_TRY(swa_reserve(ctx, ctx->d_graft, uint64_t(n) * sizeof(uint32_t)));            // result
   ctx->res.fast.candidates_end();                           // (d_graft no longer holds graft candidates)
-  SWA_TRY(swa_reserve(ctx, ctx->d_list_a, uint64_t(n) * sizeof(uint32_t)));
-  SWA_TRY(swa_reserve(ctx, ctx->d_list_b, uint64_t(n) * sizeof(uint32_t)));
+  SWA_TRY(swa_reserve(ctx, ctx->d_list_a, uint64_t(count) * sizeof(uint32_t)));
+  SWA_TRY(swa_reserve(ctx, ctx->d_list_b, uint64_t(count) * sizeof(uint32_t)));
   ctx->ix.table_repurposed();                             // d_table becomes the key table
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_table.ptr, 0, tsize * sizeof(unsigned long long), ctx->stream));
   SWA_HIP(ctx, hipMemsetAsync(ctx->d_counts.ptr, 0xFF, tsize * sizeof(uint32_t), ctx->stream));
@@ -110,9 +285,9 @@ extern "C" int swa_derep_resident(swa_ctx * ctx) {
   auto * result = static_cast<uint32_t *>(ctx->d_graft.ptr);
   uint32_t * next_count = swa_status(ctx)->flags + kFlagDerepLeft;
   uint32_t * lists[2] = {static_cast<uint32_t *>(ctx->d_list_a.ptr), static_cast<uint32_t *>(ctx->d_list_b.ptr)};
-  const uint32_t * active = nullptr;                       // round 0: every amplicon
-  uint32_t count = n;
-  for (uint32_t round = 0; count > 0; ++round) {
+  const uint32_t * active = list;                          // round 0: every amplicon (of the list)
+  uint32_t round = 0;
+  for (; count > 0; ++round) {
     if (round > 64) { return swa_fail_msg(ctx, SWA_E_DEVICE, "swa_derep: key collisions did not resolve"); }
     uint32_t * next = lists[round & 1u];
     const int grid = (int)std::min<uint64_t>((uint64_t(count) + 255) / 256, (uint64_t)ctx->num_cus * 16);
@@ -129,6 +304,21 @@ extern "C" int swa_derep_resident(swa_ctx * ctx) {
     active = next;
     count = left;
   }
+  if (rounds != nullptr) { *rounds = round; }
+  return SWA_OK;
+}
+
+}  // namespace
+
+// What swa_derep does up to the download: first_identical stays in HBM (d_graft) for swa_d0_cluster_device.
+extern "C" int swa_derep_resident(swa_ctx * ctx) {
+  if (ctx == nullptr) { return SWA_E_ARG; }
+  ctx->dr = {};                                             // the previous dereplication and its tables end here
+  if (ctx->db.n == 0) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: no database"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = ctx->db.n;
+  SWA_TRY(swa_hash_sequences(ctx));
+  SWA_TRY(derep_rounds(ctx, nullptr, n, swa_hashtable_size(n), nullptr));
   ctx->dr.first_ready = true;
   return SWA_OK;
 }
@@ -139,6 +329,92 @@ extern "C" int swa_derep(swa_ctx * ctx, uint32_t * first_identical) {
   if (first_identical == nullptr) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_derep: bad argument"); }
   SWA_TRY(swa_derep_resident(ctx));
   return swa_download(ctx, {{first_identical, ctx->d_graft.ptr, uint64_t(ctx->db.n) * sizeof(uint32_t)}});
+}
+
+// ---- several GPUs: one rank's steps of swa_multi_derep_resident (multi.hip runs the exchange between them) -------------------
+uint32_t swa_derep_owner_of(uint64_t hash, uint32_t world) { return derep_owner(hash, world); }
+
+extern "C" int swa_multi_derep_owner_for(uint64_t hash, uint32_t world, uint32_t * owner) {
+  if (owner == nullptr || world < 1 || world > kDerepMaxWorld) { return SWA_E_ARG; }
+  *owner = derep_owner(hash, world);
+  return SWA_OK;
+}
+
+int swa_derep_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count, uint32_t world, swa_dbuf & work, uint32_t * counts) {
+  if (ctx == nullptr || counts == nullptr || world < 1 || world > kDerepMaxWorld) { return SWA_E_ARG; }
+  // On every rank the previous dereplication ends, and neither d_table nor the partly filled d_seqhash serves a later d = 1 call
+  ctx->dr = {};
+  ctx->ix.table_repurposed();
+  const uint32_t n = ctx->db.n;
+  if (n == 0 || first > n || count > n - first) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_multi_derep: no database, or a slice beyond it"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  SWA_TRY(swa_prepare_hashing(ctx));
+  SWA_TRY(swa_reserve(ctx, work, swa_derep_routed::bytes(count)));
+  const swa_derep_routed w(work.ptr, count);
+  // counts and run cursors: the status block's cursor words, as 32-bit ones
+  static_assert(2 * kDerepMaxWorld * sizeof(uint32_t) <= sizeof(swa_status_block::cursors), "a count and a run cursor for every rank");
+  auto * d_counts = reinterpret_cast<uint32_t *>(swa_status(ctx)->cursors);
+  SWA_HIP(ctx, hipMemsetAsync(d_counts, 0, 2 * kDerepMaxWorld * sizeof(uint32_t), ctx->stream));
+  if (count != 0) {
+    const size_t zbytes = 4ull * ctx->zobrist_len * sizeof(uint64_t);
+    const int hgrid = swa_grid256(ctx, count);
+    const auto * zob = static_cast<const uint64_t *>(ctx->d_zobrist.ptr);
+    if (zbytes <= 48u * 1024u) {
+      hipLaunchKernelGGL(k_derep_hash_slice<true>, dim3(hgrid), dim3(256), zbytes, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen,
+                         zob, ctx->zobrist_len, first, count, w.slice_hash);
+    } else {
+      hipLaunchKernelGGL(k_derep_hash_slice<false>, dim3(hgrid), dim3(256), 0, ctx->stream, ctx->db.seqs, ctx->db.seq_off, ctx->db.seqlen,
+                         zob, ctx->zobrist_len, first, count, w.slice_hash);
+    }
+    RouteArgs a{};
+    a.hash = reinterpret_cast<const unsigned long long *>(w.slice_hash);
+    a.first = first; a.count = count; a.world = world;
+    a.counts = d_counts; a.cursor = d_counts + kDerepMaxWorld;
+    a.out_hash = reinterpret_cast<unsigned long long *>(w.hash); a.out_id = w.id;
+    const uint64_t tiles = ((uint64_t)count + kRouteTile - 1) / kRouteTile;
+    const dim3 grid((unsigned)std::min<uint64_t>(tiles, (uint64_t)ctx->num_cus * 8));
+    hipLaunchKernelGGL(k_derep_route<false>, grid, dim3(kRouteThreads), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_derep_route<true>, grid, dim3(kRouteThreads), 0, ctx->stream, a);
+    SWA_HIP(ctx, hipGetLastError());
+  }
+  // ONE read of the counts, into the pinned mirror of the status block
+  auto * h_counts = reinterpret_cast<uint32_t *>(ctx->h_status->cursors);
+  SWA_HIP(ctx, hipMemcpyAsync(h_counts, d_counts, kDerepMaxWorld * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  uint64_t sum = 0;
+  for (uint32_t r = 0; r < world; ++r) { counts[r] = h_counts[r]; sum += h_counts[r]; }
+  if (sum != count) { return swa_fail_msg(ctx, SWA_E_INTERNAL, "swa_multi_derep: the routed records do not add up to the slice"); }
+  return SWA_OK;
+}
+
+int swa_derep_owner_rounds(swa_ctx * ctx, const uint64_t * in_hash, const uint32_t * in_id, uint32_t received, uint64_t * packed, uint32_t * rounds) {
+  if (ctx == nullptr || rounds == nullptr) { return SWA_E_ARG; }
+  *rounds = 0;
+  if (received == 0) { return SWA_OK; }                        // (an empty inbox: a slice of nothing, or hashes that all live elsewhere)
+  const uint32_t n = ctx->db.n;
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  const dim3 g((unsigned)swa_grid256(ctx, received)), b(256);
+  hipLaunchKernelGGL(k_derep_scatter, g, b, 0, ctx->stream, in_hash, in_id, received, n, static_cast<uint64_t *>(ctx->d_seqhash.ptr));
+  SWA_TRY(derep_rounds(ctx, in_id, received, swa_hashtable_size(received), rounds));
+  hipLaunchKernelGGL(k_derep_pack, g, b, 0, ctx->stream, in_id, received, n, static_cast<const uint32_t *>(ctx->d_graft.ptr),
+                     reinterpret_cast<unsigned long long *>(packed));
+  SWA_HIP(ctx, hipGetLastError());
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SWA_OK;
+}
+
+int swa_derep_home(swa_ctx * ctx, const uint64_t * packed) {
+  if (ctx == nullptr || packed == nullptr) { return SWA_E_ARG; }
+  const uint32_t n = ctx->db.n;
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  SWA_TRY(swa_reserve(ctx, ctx->d_graft, uint64_t(n) * sizeof(uint32_t)));
+  ctx->res.fast.candidates_end();
+  hipLaunchKernelGGL(k_derep_home, dim3((unsigned)swa_grid256(ctx, n)), dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned long long *>(packed),
+                     n, n, static_cast<uint32_t *>(ctx->d_graft.ptr));
+  SWA_HIP(ctx, hipGetLastError());
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->dr.first_ready = true;
+  return SWA_OK;
 }
 
 // ---- the clusters, their sums and their order, from the resident array (src/derep.cc:276-354, 67-90) --------------------

@@ -7,8 +7,12 @@
 //   d >= 2     swa_dn_cluster (the whole graph of pairs within d at once, or one swa_scan_step per swarm generation)
 //   d = 0      swa_derep_resident -> swa_d0_cluster_resident (SWARM_AMD_D0=host: swa_derep -> swa_d0_cluster)
 //
+// Several GPUs (SWARM_AMD_DEVICES): every d.  d = 1 and d >= 2 leave their network on rank 0's GPU, d = 0 its
+// first_identical array (swa_multi_derep_resident; SWARM_AMD_D0=host: swa_multi_derep), and from there on the run is the
+// single-GPU one on rank 0's context.
+//
 // Environment (no new flags, to stay drop-in): SWARM_AMD_DEVICE = HIP device ordinal (default 0);
-// SWARM_AMD_DEVICES = 0,1,2,... : d >= 1 on several GPUs (swa_multi_*: one rank per entry, RCCL exchange).
+// SWARM_AMD_DEVICES = 0,1,2,... : several GPUs (swa_multi_*: one rank per entry, RCCL exchange).
 #include <chrono>
 #include <future>
 #include <thread>
@@ -293,7 +297,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
       p = (*end == ',') ? end + 1 : end;
     }
   }
-  const bool use_multi = devices.size() > 1 && o.differences >= 1;
+  const bool use_multi = devices.size() > 1;
   swa_ctx * early_ctx = nullptr;
   int early_rc = SWA_OK;
   std::thread early;
@@ -358,7 +362,7 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
 
   const uint32_t n = uview.n;
   swa_ctx * ctx = nullptr;
-  swa_multi * multi = nullptr;           // d >= 1 on several GPUs: SWARM_AMD_DEVICES=0,1,2,... (one rank per entry)
+  swa_multi * multi = nullptr;           // several GPUs: SWARM_AMD_DEVICES=0,1,2,... (one rank per entry)
   if (n > 0) {
     if (use_multi) {
       if (swa_multi_create(devices.data(), (int)devices.size(), &multi) != SWA_OK) {
@@ -391,13 +395,16 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     const char * d0_route = std::getenv("SWARM_AMD_D0");
     const bool d0_device = !(d0_route != nullptr && std::strcmp(d0_route, "host") == 0);
     swa_d0_result * res = nullptr;
+    // (several GPUs: the search divided among the ranks, the array on rank 0's GPU — ctx — or downloaded from there)
     if (n > 0 && d0_device) {
-      if (swa_derep_resident(ctx) != SWA_OK) { die(swa_last_error(ctx)); }
+      if (multi != nullptr) { if (swa_multi_derep_resident(multi) != SWA_OK) { die(swa_multi_last_error(multi)); } }
+      else if (swa_derep_resident(ctx) != SWA_OK) { die(swa_last_error(ctx)); }
       stamp("dereplicated");                                 // (its last round has been waited for)
       if (swa_d0_cluster_resident(ctx, db, &res) != SWA_OK) { die(swa_last_error(ctx)); }
     } else {
       std::vector<uint32_t> first_identical(n);
-      if (n > 0 && swa_derep(ctx, first_identical.data()) != SWA_OK) { die(swa_last_error(ctx)); }
+      if (n > 0 && multi != nullptr) { if (swa_multi_derep(multi, first_identical.data()) != SWA_OK) { die(swa_multi_last_error(multi)); } }
+      else if (n > 0 && swa_derep(ctx, first_identical.data()) != SWA_OK) { die(swa_last_error(ctx)); }
       stamp("dereplicated");
       if (swa_d0_cluster(db, first_identical.data(), &res) != SWA_OK) { die("dereplication failed"); }
     }

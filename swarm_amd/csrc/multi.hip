@@ -15,6 +15,9 @@
 // from its flags in HBM and broadcasts (swa_multi_d1_fastidious_resident) —, graft_cand is combined with
 // swa_rccl().AllReduce(min) (src/algod1.cc:244-258 keeps the smallest heavy id), the two heavy-side counters add up.
 //
+// d = 0 (derep_on_root below): the reads of a rank's slice travel to the rank that owns their hash, the owners dereplicate,
+// first_identical[] is assembled on rank 0.  d >= 2: the bulk graph divided by ownership of window groups (further below).
+//
 // The same code runs with several contexts on ONE device (SWARM_AMD_DEVICES=0,0: what a one-GPU box can
 // test); RCCL refuses two ranks on one GPU, so that configuration moves the same bytes with device-to-
 // device copies instead.  Results are identical to a single GPU by construction and by test
@@ -38,6 +41,8 @@ struct swa_multi {
   std::vector<swa_dbuf> routed, routed_counts, inbox;   // routed index build: a rank's outgoing id lists, their counts, what it received
   std::vector<uint64_t> link_cap;
   int last_build = SWA_MULTI_BUILD_NONE;   // of the last swa_multi_d1_network* call (swa_multi_d1_last_build)
+  std::vector<uint64_t> derep_received;    // of the last swa_multi_derep* call (swa_multi_derep_totals): records every owner received,
+  uint64_t derep_rounds = 0, derep_routed = 0;   // the rounds of the slowest owner, the records routed
   std::string err;
 };
 
@@ -529,6 +534,123 @@ extern "C" int swa_multi_d1_fastidious_resident(swa_multi * m, uint64_t light_nt
   }
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c0->stream) != hipSuccess) { return fail(m, SWA_E_DEVICE, "combining the graft candidates failed"); }
   c0->res.fast.cand_ready = true;                              // (d_graft on rank 0: the candidates of the whole pass)
+  return SWA_OK;
+}
+
+// ---- d = 0 on several GPUs: the reads travel to the owner of their hash (src/derep.cc:276-354) ------------------------------
+// The routed build of d = 1, applied to hashes.  Every rank hashes its slice of the replicated database and groups the
+// (hash, id) records by owner (swa_derep_route_slice: k_derep_hash_slice, k_derep_route); the counts come to the host once,
+// the inboxes are reserved from them — exactly: a read with 10^6 copies sends 10^6 records to one owner, so there is no
+// region cap, no overflow and no other build —, and the records travel all-to-all: grouped ncclSend / ncclRecv, device-to-
+// device copies when the ranks share a device; one rank takes the same path.  Every owner dereplicates what it received
+// (swa_derep_owner_rounds: the re-key rounds stay local, all copies of a sequence are there) and packs first << 32 | id;
+// rank 0 gathers the packed words and writes first_identical[] into its d_graft (swa_derep_home): from there on
+// swa_multi_ctx(m, 0) is a context after swa_derep_resident.
+static int derep_on_root(swa_multi * m) {
+  const int world = (int)m->ctx.size();
+  const uint32_t n = m->ctx[0]->db.n;
+  m->derep_received.assign((size_t)world, 0);
+  m->derep_rounds = m->derep_routed = 0;
+  for (swa_ctx * c : m->ctx) { c->dr = {}; }                   // (whatever fails below: no rank holds a resident array)
+  if (n == 0) { return fail(m, SWA_E_ARG, "swa_multi_derep: no database"); }
+  // 1. every rank hashes and routes its slice
+  std::vector<uint32_t> first((size_t)world + 1, 0);
+  for (int r = 0; r <= world; ++r) { first[(size_t)r] = (uint32_t)((uint64_t)n * (uint64_t)r / (uint64_t)world); }
+  std::vector<std::vector<uint32_t>> cnt((size_t)world, std::vector<uint32_t>((size_t)world, 0));
+  int rc = on_all(m, [&](int r) {
+    return swa_derep_route_slice(m->ctx[(size_t)r], first[(size_t)r], first[(size_t)r + 1] - first[(size_t)r], (uint32_t)world, m->routed[(size_t)r],
+                                 cnt[(size_t)r].data());
+  });
+  if (rc != SWA_OK) { return rc; }
+  // 2. the exchange: rank r receives the runs for it of the sources in rank order
+  std::vector<uint64_t> received((size_t)world, 0);
+  for (int r = 0; r < world; ++r) {
+    for (int s2 = 0; s2 < world; ++s2) { received[(size_t)r] += cnt[(size_t)s2][(size_t)r]; }
+    swa_ctx * c = m->ctx[(size_t)r];
+    if (hipSetDevice(c->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
+    rc = swa_reserve(c, m->inbox[(size_t)r], swa_derep_inbox::bytes(received[(size_t)r]));
+    if (rc == SWA_OK) { rc = swa_reserve(c, m->links[(size_t)r], (received[(size_t)r] + 2) * sizeof(uint64_t)); }
+    if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c)); }
+  }
+  if (!m->comms.empty()) { NCCL_OK(m, swa_rccl().GroupStart()); }
+  for (int r = 0; r < world; ++r) {
+    const swa_derep_inbox in(m->inbox[(size_t)r].ptr, received[(size_t)r]);
+    uint64_t at = 0;
+    for (int s2 = 0; s2 < world; ++s2) {
+      const uint32_t count = cnt[(size_t)s2][(size_t)r];
+      if (count == 0) { continue; }
+      const swa_derep_routed out(m->routed[(size_t)s2].ptr, first[(size_t)s2 + 1] - first[(size_t)s2]);
+      uint64_t run = 0;                                        // where the run for r begins in the source's arrays
+      for (int d = 0; d < r; ++d) { run += cnt[(size_t)s2][(size_t)d]; }
+      if (!m->comms.empty()) {
+        NCCL_OK(m, swa_rccl().Send(out.hash + run, count, ncclUint64, r, m->comms[(size_t)s2], m->ctx[(size_t)s2]->stream));
+        NCCL_OK(m, swa_rccl().Recv(in.hash + at, count, ncclUint64, s2, m->comms[(size_t)r], m->ctx[(size_t)r]->stream));
+        NCCL_OK(m, swa_rccl().Send(out.id + run, count, ncclUint32, r, m->comms[(size_t)s2], m->ctx[(size_t)s2]->stream));
+        NCCL_OK(m, swa_rccl().Recv(in.id + at, count, ncclUint32, s2, m->comms[(size_t)r], m->ctx[(size_t)r]->stream));
+      } else {
+        if (hipSetDevice(m->devices[(size_t)r]) != hipSuccess ||
+            hipMemcpyAsync(in.hash + at, out.hash + run, (size_t)count * sizeof(uint64_t), hipMemcpyDefault, m->ctx[(size_t)r]->stream) != hipSuccess ||
+            hipMemcpyAsync(in.id + at, out.id + run, (size_t)count * sizeof(uint32_t), hipMemcpyDefault, m->ctx[(size_t)r]->stream) != hipSuccess) {
+          return fail(m, SWA_E_DEVICE, "device-to-device copy of routed dereplication records failed");
+        }
+      }
+      at += count;
+    }
+  }
+  if (!m->comms.empty()) { NCCL_OK(m, swa_rccl().GroupEnd()); }
+  for (int k = 0; k < world; ++k) {
+    if (hipSetDevice(m->devices[(size_t)k]) != hipSuccess || hipStreamSynchronize(m->ctx[(size_t)k]->stream) != hipSuccess) {
+      return fail(m, SWA_E_DEVICE, "synchronising the exchange of the dereplication records failed");
+    }
+  }
+  // 3. every owner dereplicates what it received
+  std::vector<uint32_t> rounds((size_t)world, 0);
+  rc = on_all(m, [&](int r) {
+    const swa_derep_inbox in(m->inbox[(size_t)r].ptr, received[(size_t)r]);
+    return swa_derep_owner_rounds(m->ctx[(size_t)r], in.hash, in.id, (uint32_t)received[(size_t)r], static_cast<uint64_t *>(m->links[(size_t)r].ptr),
+                                  &rounds[(size_t)r]);
+  });
+  if (rc != SWA_OK) { return rc; }
+  // 4. home: every id exactly once
+  uint64_t all = 0;
+  for (int r = 0; r < world; ++r) { all += received[(size_t)r]; m->derep_rounds = std::max<uint64_t>(m->derep_rounds, rounds[(size_t)r]); }
+  m->derep_received = received;
+  m->derep_routed = all;
+  if (all != n) { return fail(m, SWA_E_INTERNAL, "swa_multi_derep: the owners hold " + std::to_string(all) + " records of " + std::to_string(n) + " reads"); }
+  swa_ctx * c0 = m->ctx[0];
+  if (hipSetDevice(c0->device) != hipSuccess) { return fail(m, SWA_E_DEVICE, "hipSetDevice"); }
+  rc = swa_reserve(c0, m->gathered, (all + 2) * sizeof(uint64_t));
+  if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
+  std::vector<const void *> src((size_t)world);
+  for (int r = 0; r < world; ++r) { src[(size_t)r] = m->links[(size_t)r].ptr; }
+  rc = gather_to_root_v(m, src, m->gathered.ptr, received, sizeof(uint64_t));
+  if (rc != SWA_OK) { return rc; }
+  rc = swa_derep_home(c0, static_cast<const uint64_t *>(m->gathered.ptr));
+  if (rc != SWA_OK) { return fail(m, rc, swa_last_error(c0)); }
+  return SWA_OK;
+}
+
+// = swa_derep_resident on swa_multi_ctx(m, 0), the search divided among the ranks by ownership of the hashes
+extern "C" int swa_multi_derep_resident(swa_multi * m) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  return derep_on_root(m);
+}
+
+// ... plus the download: swa_derep's array
+extern "C" int swa_multi_derep(swa_multi * m, uint32_t * first_identical) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  if (first_identical == nullptr) { return fail(m, SWA_E_ARG, "swa_multi_derep: bad argument"); }
+  SWA_TRY(derep_on_root(m));
+  swa_ctx * c0 = m->ctx[0];
+  const int rc = swa_download(c0, {{first_identical, c0->d_graft.ptr, uint64_t(c0->db.n) * sizeof(uint32_t)}});
+  return rc != SWA_OK ? fail(m, rc, swa_last_error(c0)) : (int)SWA_OK;
+}
+
+// received[world]: the records every owner got in the last call; out2 = {rounds of the slowest owner, records routed}
+extern "C" int swa_multi_derep_totals(swa_multi * m, uint64_t * received, uint64_t * out2) {
+  if (m == nullptr || received == nullptr || out2 == nullptr) { return SWA_E_ARG; }
+  for (size_t r = 0; r < m->ctx.size(); ++r) { received[r] = r < m->derep_received.size() ? m->derep_received[r] : 0; }
+  out2[0] = m->derep_rounds; out2[1] = m->derep_routed;
   return SWA_OK;
 }
 

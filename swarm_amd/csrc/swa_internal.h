@@ -49,6 +49,7 @@ struct swa_status_block {
   uint32_t pad1[127];
   uint32_t counters[256];        // kCounter*: work counters of the d = 1 step (kCounterWords)
   uint64_t cursors[64];          // swa_d1_links_split: the run cursor of every rank; in the mirror [0] receives the links no rank owns
+                                 // (swa_derep_route_slice: as 32-bit words, 64 counts and 64 run cursors; the mirror receives the counts)
   uint8_t pad2[1536];
 };
 static_assert(std::is_standard_layout<swa_status_block>::value, "status block: plain data");
@@ -257,7 +258,8 @@ struct swa_resident {
   } tables;
 };
 
-// the dereplication in place (derep.hip): ended by swa_db_upload* / swa_db_attach, by the start of every swa_derep* and by
+// the dereplication in place (derep.hip): ended by swa_db_upload* / swa_db_attach, by the start of every swa_derep* (on every
+// rank of a swa_multi by the start of every swa_multi_derep*, which leaves a new one on rank 0 alone) and by
 // every call that writes d_graft, where its array lies (the --fastidious pass, swa_d1_graft_device with a caller's candidates)
 struct swa_derep_facts {
   bool first_ready = false;      // d_graft holds first_identical[] of the database in place (swa_derep_resident)
@@ -435,6 +437,34 @@ int swa_d1_roles_from_owners(swa_ctx * ctx, const uint8_t * d_owner, uint32_t sh
 // home only when graft_cand is not null
 int swa_d1_fastidious_owned(swa_ctx * ctx, const uint8_t * d_owner, uint32_t shard, uint64_t n_light, uint64_t n_heavy, uint64_t light_nt,
                             uint32_t bloom_bits, uint32_t * graft_cand, uint64_t * counters);
+
+// derep.hip, for multi.hip (swa_multi_derep_resident): the steps of one rank.  Every one returns with the context's stream
+// synchronised: the exchange between them runs on other contexts' streams, which do not order against this one.
+// A rank's outgoing records: the hashes of its slice, then the (hash, id) records in owner order — two arrays, one position
+struct swa_derep_routed {
+  uint64_t * slice_hash, * hash; uint32_t * id;
+  static uint64_t bytes(uint64_t count) { return (2 * (count + (count & 1u)) + 2) * sizeof(uint64_t) + (count + 2) * sizeof(uint32_t); }
+  explicit swa_derep_routed(void * base, uint64_t count) {
+    slice_hash = static_cast<uint64_t *>(base);                  // (16-byte aligned: k_derep_route reads two at a time)
+    hash = slice_hash + count + (count & 1u);
+    id = reinterpret_cast<uint32_t *>(hash + count + (count & 1u));
+  }
+};
+// ... and what a rank received: the same two arrays
+struct swa_derep_inbox {
+  uint64_t * hash; uint32_t * id;
+  static uint64_t bytes(uint64_t count) { return (count + 2) * sizeof(uint64_t) + (count + 2) * sizeof(uint32_t); }
+  explicit swa_derep_inbox(void * base, uint64_t count) { hash = static_cast<uint64_t *>(base); id = reinterpret_cast<uint32_t *>(hash + count); }
+};
+uint32_t swa_derep_owner_of(uint64_t hash, uint32_t world);     // the rank that dereplicates every read with this round-0 hash
+// the previous dereplication of this context ends; hashes [first, first + count) and routes them by owner into `work`
+// (reserved here, laid out as swa_derep_routed(work.ptr, count)); counts[world] on the host
+int swa_derep_route_slice(swa_ctx * ctx, uint32_t first, uint32_t count, uint32_t world, swa_dbuf & work, uint32_t * counts);
+// the owner's rounds over the `received` records of its inbox (device arrays); packed[t] = first_identical << 32 | id of
+// record t (device, `received` words); *rounds = how many rounds ran
+int swa_derep_owner_rounds(swa_ctx * ctx, const uint64_t * in_hash, const uint32_t * in_id, uint32_t received, uint64_t * packed, uint32_t * rounds);
+// rank 0: the n packed words of all owners (device) into d_graft; leaves the state of swa_derep_resident
+int swa_derep_home(swa_ctx * ctx, const uint64_t * packed);
 
 // RAII-less timing brackets: swa_t0(ctx, slot) ... swa_t1(ctx, slot).  The slots: swa_timing_read reports [0, 8),
 // swa_timing_read_stream [8, 16), both by position (include/swarm_amd.h)
