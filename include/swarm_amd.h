@@ -588,6 +588,19 @@ int swa_scan_totals(swa_ctx * ctx, uint64_t * out3);
    overflowed, re-lists of the candidate list, batches whose hits were fetched by copy (more than the pinned mirror
    holds)}; the three counts run from the creation of the context */
 int swa_scan_debug_state(swa_ctx * ctx, uint64_t * out4);
+/* Ownership of the pool, for the scan divided among several contexts (swa_multi_scan_*).  Whether (seed, target) is a hit
+   depends on the pair alone, so every context can scan a part of the pool against all seeds.  Amplicon id belongs to rank
+   (id >> 5) % world: block-cyclic in blocks of 32 amplicons (one turn of a workgroup of the pool kernel, 4 KB of contiguous
+   signatures; the shares stay even while lowest_unswarmed rises).
+   swa_scan_set_ownership(rank, world): the context scans its own amplicons only — its estimates, pool flags and candidate
+     list mean something for those alone, its hits are its share of the hits.  (0, 1), the state of a new context, is the
+     whole pool.  1 <= world <= 64, rank < world (SWA_E_ARG otherwise); a change ends the scan in progress: swa_scan_begin next.
+   swa_scan_owner_for(id, world): the owner; a pure function, no device.
+   swa_scan_share_for(n, lowest_unswarmed, rank, world, out2): out2 = {how many amplicons of [lowest_unswarmed, n) the rank
+     owns, the first of them (n when there is none)}; a pure function, no device; SWA_E_ARG for world = 0 or rank >= world. */
+int swa_scan_set_ownership(swa_ctx * ctx, uint32_t rank, uint32_t world);
+uint32_t swa_scan_owner_for(uint32_t id, uint32_t world);
+int swa_scan_share_for(uint32_t n, uint32_t lowest_unswarmed, uint32_t rank, uint32_t world, uint32_t * out2);
 
 /* ---- B5: the uclust alignments ------------------------------------------------------------
    Seam B5 (src/algod1.cc:880-925, src/algo.cc:608-659, src/nw.cc:237-255): npairs global alignments of amplicon
@@ -756,6 +769,28 @@ int  swa_multi_dn_graph(swa_multi * m, int no_cluster_breaking, uint64_t * offse
                         uint64_t cap, uint64_t * total);
 int  swa_multi_dn_graph_resident(swa_multi * m, int no_cluster_breaking, uint64_t * total);
 int  swa_multi_dn_graph_totals(swa_multi * m, uint64_t * out3);
+/* The fused scan (swa_scan_*) divided among the ranks by ownership of the pool (swa_scan_set_ownership: rank r scans the
+   amplicons i with (i >> 5) % world == r against every seed) — what src/scan.cc:221-256 does with threads.
+   swa_multi_scan_begin comes after swa_multi_dn_begin: ownership and swa_scan_begin on every rank.
+   swa_multi_scan_batch / _step / _fetch take the arguments of the single-context calls and keep their contract: triples
+   sorted by (seed index, id), SWA_E_CAPACITY with the whole count in *nhits, every returned target leaves the pool; the
+   same refusals with SWA_E_ARG.  One host thread enqueues the batch on every rank's stream, then finishes rank by rank; a
+   rank whose pair arrays overflowed repeats its sequence alone; a rank that owns no amplicon at or above lowest_unswarmed
+   launches nothing; the ranks' hit lists are merged on the host.  No collective: ranks on one device and ranks on
+   distinct devices run the same code.  (A rank that launches nothing for a first generation does not mark the initial
+   seed either: as the name says, everything below lowest_unswarmed counts as swarmed, so lowest_unswarmed must not fall
+   back below an earlier initial seed — the greedy loop's never does.)
+   swa_multi_scan_totals: out3 = {q-gram comparisons, aligned pairs — summed over the ranks, and those of a single context,
+   because the shares partition the candidates —, launch sequences = batches since swa_multi_scan_begin (not a sum)}.
+   The per-rank state (swa_scan_debug_state, swa_scan_totals) stays readable through swa_multi_ctx(m, r). */
+int  swa_multi_scan_begin(swa_multi * m);
+int  swa_multi_scan_batch(swa_multi * m, uint32_t nseeds, const uint32_t * seeds, const uint32_t * radii, uint32_t lowest_unswarmed,
+                          int first_generation, int no_cluster_breaking, uint32_t * hit_seedidx, uint32_t * hit_ids,
+                          uint32_t * hit_diffs, uint32_t cap, uint32_t * nhits);
+int  swa_multi_scan_step(swa_multi * m, uint32_t seed, uint32_t lowest_unswarmed, int first_generation, uint32_t radius,
+                         int no_cluster_breaking, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap, uint32_t * nhits);
+int  swa_multi_scan_fetch(swa_multi * m, uint32_t * hit_seedidx, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap);
+int  swa_multi_scan_totals(swa_multi * m, uint64_t * out3);
 /* Debug entry: the merge rank 0 runs on the gathered shares (k_merge_sorted_lists, launched as swa_multi_dn_graph launches
    it), from host arrays to host arrays on the context's stream.  List r = [at[r], at[r + 1]) of keys / vals, every list
    sorted by key, at[0] = 0, at[] not descending, 1 <= world <= 64 (SWA_E_ARG otherwise); out_keys / out_vals take

@@ -139,7 +139,9 @@ typedef struct swa_dn_result swa_dn_result;
 int  swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                     uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out);
 /* the same on the GPUs of a swa_multi (d >= 2 graph divided by ownership of window groups: swa_multi_dn_graph and the walk on
-   the host, or — where swa_multi_cluster_on_device() — swa_multi_dn_graph_resident and the walk and tables on rank 0's GPU) */
+   the host, or — where swa_multi_cluster_on_device() — swa_multi_dn_graph_resident and the walk and tables on rank 0's GPU;
+   where the fused scan serves, the same greedy loop over swa_multi_scan_*, the pool divided among the ranks, unless
+   SWARM_AMD_MULTI_SCAN=root leaves it to rank 0 alone: the comparison switch) */
 int  swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
                           uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out);
 /* SWARM_AMD_MULTI_CLUSTER=device|host: where a run on several GPUs clusters what the exchange assembled on rank 0 — there
@@ -150,6 +152,9 @@ const char * swa_dn_result_error(const swa_dn_result * res);
 /* 1 when the bulk graph (swa_dn_graph*) served the clustering, 0 when the fused scan did.  SWARM_AMD_DN=scan|graph
    choose; without it the graph serves d <= 8 (where swa_dn_graph_supported) and the scan everything else. */
 int  swa_dn_result_over_graph(const swa_dn_result * res);
+/* the ranks the fused scan ran on: 0 when the bulk graph served, 1 for one context (swa_dn_cluster, SWARM_AMD_MULTI_SCAN=root),
+   else the ranks of the swa_multi */
+uint32_t swa_dn_result_scan_ranks(const swa_dn_result * res);
 /* The graph route's swarm tables are made on the host from five downloaded arrays (SWARM_AMD_DN_TABLES=host, the default) or
    in HBM (=device: swa_dn_tables_device).  On the device route the links stay in HBM until the first writer that reads them
    (-i, -u) asks; this is how often they were downloaded for this result (0 for a run that writes -o, -s, -w alone; else 1).

@@ -1357,17 +1357,29 @@ class DnClusters:
     q-gram / alignment step executed on the GPU (swa_scan_step)."""
 
     def __init__(self, ctx: "Context", hdb: HostDb, differences: int, no_cluster_breaking: bool = False,
-                 penalties=None):
+                 penalties=None, multi: "MultiContext | None" = None):
         self.lib = load_library()
         _declare_dn(self.lib)
+        _declare_multi_scan(self.lib)
         self.hdb = hdb
-        self.ctx = ctx
+        self.ctx = ctx                    # (multi: rank 0's, which the writers use)
+        self.multi = multi
         mm, go, ge = penalties or reduced_penalties()
         h = C.c_void_p()
-        rc = self.lib.swa_dn_cluster(ctx.h, hdb.h, differences, int(no_cluster_breaking), mm, go, ge, C.byref(h))
+        if multi is not None:
+            rc = self.lib.swa_dn_cluster_multi(multi.h, hdb.h, differences, int(no_cluster_breaking), mm, go, ge, C.byref(h))
+        else:
+            rc = self.lib.swa_dn_cluster(ctx.h, hdb.h, differences, int(no_cluster_breaking), mm, go, ge, C.byref(h))
         self.h = h
         if rc != SWA_OK:
             raise SwaError(rc, self.lib.swa_dn_result_error(h).decode() if h else "swa_dn_cluster failed")
+
+    def route(self):
+        """(route, ranks): ("graph", 0) when the bulk graph served, else ("scan", the ranks the fused scan ran on: 1 for one
+        context — also rank 0 alone under SWARM_AMD_MULTI_SCAN=root —, else the ranks of the MultiContext)"""
+        self.lib.swa_dn_result_over_graph.argtypes = [C.c_void_p]
+        ranks = int(self.lib.swa_dn_result_scan_ranks(self.h))
+        return ("graph", 0) if self.lib.swa_dn_result_over_graph(self.h) else ("scan", ranks)
 
     def summary(self) -> dict:
         out = np.zeros(3, dtype=np.uint64)
@@ -1387,6 +1399,8 @@ class DnClusters:
         if self.lib.swa_dn_result_over_graph(self.h):
             self.ctx._check(self.lib.swa_dn_graph_totals(self.ctx.h, _p64(out)))
             return {"route": "graph", "qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
+        if self.multi is not None and self.route()[1] > 1:
+            return {"route": "scan", **self.multi.scan_totals()}
         self.ctx._check(self.lib.swa_scan_totals(self.ctx.h, _p64(out)))
         return {"route": "scan", "qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
 
@@ -1576,6 +1590,50 @@ MULTI_BUILD_NONE, MULTI_BUILD_ROUTED, MULTI_BUILD_STREAMED, MULTI_BUILD_OVERFLOW
 MULTI_BUILD_NAMES = ("none", "routed records", "streamed on request", "streamed after overflow")
 
 
+_MULTI_SCAN_EXPORTS = ["swa_scan_set_ownership", "swa_scan_owner_for", "swa_scan_share_for", "swa_multi_scan_begin", "swa_multi_scan_batch",
+                       "swa_multi_scan_step", "swa_multi_scan_fetch", "swa_multi_scan_totals", "swa_dn_result_scan_ranks"]
+EXPORTS.extend(_MULTI_SCAN_EXPORTS)
+
+
+def _declare_multi_scan(lib) -> None:
+    lib.swa_scan_set_ownership.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.swa_scan_owner_for.argtypes = [C.c_uint32, C.c_uint32]
+    lib.swa_scan_owner_for.restype = C.c_uint32
+    lib.swa_scan_share_for.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+    lib.swa_multi_dn_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+    lib.swa_multi_scan_begin.argtypes = [C.c_void_p]
+    lib.swa_multi_scan_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_uint32, u32p]
+    lib.swa_multi_scan_step.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_uint32, u32p]
+    lib.swa_multi_scan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.swa_multi_scan_totals.argtypes = [C.c_void_p, u64p]
+    lib.swa_dn_result_scan_ranks.argtypes = [C.c_void_p]
+    lib.swa_dn_result_scan_ranks.restype = C.c_uint32
+    lib.swa_dn_cluster_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.POINTER(C.c_void_p)]
+
+
+def scan_owner_for(id: int, world: int) -> int:
+    """swa_scan_owner_for: the rank of `world` that scans amplicon `id` in MultiContext.scan_batch — (id >> 5) % world,
+    block-cyclic in blocks of 32; a pure function, needs no device."""
+    lib = load_library()
+    _declare_multi_scan(lib)
+    return int(lib.swa_scan_owner_for(int(id), int(world)))
+
+
+def scan_share_for(n: int, lowest_unswarmed: int, rank: int, world: int):
+    """swa_scan_share_for: (how many amplicons of [lowest_unswarmed, n) `rank` of `world` owns, the first of them — n when
+    there is none); a pure function, needs no device."""
+    lib = load_library()
+    _declare_multi_scan(lib)
+    out = np.zeros(2, dtype=np.uint32)
+    rc = lib.swa_scan_share_for(int(n), int(lowest_unswarmed), int(rank), int(world), out.ctypes.data_as(u32p))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_scan_share_for: bad argument")
+    return int(out[0]), int(out[1])
+
+
 _MULTI_DEREP_EXPORTS = ["swa_multi_derep_resident", "swa_multi_derep", "swa_multi_derep_owner_for", "swa_multi_derep_totals"]
 EXPORTS.extend(_MULTI_DEREP_EXPORTS)
 
@@ -1623,6 +1681,7 @@ class MultiContext:
         lib.swa_multi_dn_graph_resident.argtypes = [C.c_void_p, C.c_int, u64p]
         lib.swa_multi_d1_last_build.argtypes = [C.c_void_p]
         _declare_multi_derep(lib)
+        _declare_multi_scan(lib)
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
         rc = lib.swa_multi_create(arr, len(devices), C.byref(h))
@@ -1645,6 +1704,13 @@ class MultiContext:
         v = DbView(hdb.n, hdb.longest, _ptr(hdb.seqs), _ptr(hdb.seq_off), _ptr(hdb.seqlen), _ptr(hdb.abundance))
         self._check(self.lib.swa_multi_db_upload(self.h, C.byref(v)))
         self.n = hdb.n
+
+    def upload_db(self, seqs, seq_off, seqlen, abundance, longest: int) -> None:
+        """Host numpy arrays (db order) -> every rank's HBM, as Context.upload_db."""
+        n = int(seqlen.shape[0])
+        v = DbView(n, int(longest), _ptr(seqs), _ptr(seq_off), _ptr(seqlen), _ptr(abundance))
+        self._check(self.lib.swa_multi_db_upload(self.h, C.byref(v)))
+        self.n = n
 
     def d1_network(self, no_cluster_breaking: bool = False):
         offsets = np.zeros(self.n + 1, dtype=np.uint64)
@@ -1698,6 +1764,49 @@ class MultiContext:
         out2 = np.zeros(2, dtype=np.uint64)
         self._check(self.lib.swa_multi_derep_totals(self.h, _ptr(received), _ptr(out2)))
         return {"received": received, "rounds": int(out2[0]), "routed": int(out2[1])}
+
+    # ---- d >= 2: the fused scan divided among the ranks by ownership of the pool (scan_owner_for)
+    def size(self) -> int:
+        return int(self.lib.swa_multi_size(self.h))
+
+    def dn_begin(self, d: int, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13) -> None:
+        """swa_multi_dn_begin: q-gram signatures and the scoring for d on every rank"""
+        self._check(self.lib.swa_multi_dn_begin(self.h, mismatch, gapopen, gapextend, d))
+
+    def scan_begin(self) -> None:
+        """swa_multi_scan_begin (after dn_begin): ownership and swa_scan_begin on every rank"""
+        self._check(self.lib.swa_multi_scan_begin(self.h))
+
+    def scan_batch(self, seeds, radii, lowest_unswarmed: int, first_generation: bool, ncb: bool, cap: int | None = None):
+        """swa_multi_scan_batch, as Context.scan_batch: (return code, nhits, seed indices, ids, diffs)"""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        radii = np.ascontiguousarray(radii, dtype=np.uint32)
+        assert seeds.shape == radii.shape
+        cap = self.n if cap is None else int(cap)
+        sidx, ids, diffs = (np.zeros(max(1, cap), dtype=np.uint32) for _ in range(3))
+        nh = C.c_uint32(0)
+        rc = self.lib.swa_multi_scan_batch(self.h, seeds.shape[0], _ptr(seeds), _ptr(radii), int(lowest_unswarmed), int(first_generation),
+                                           int(ncb), _ptr(sidx), _ptr(ids), _ptr(diffs), cap, C.byref(nh))
+        k = min(int(nh.value), cap) if rc == SWA_OK else 0
+        return rc, int(nh.value), sidx[:k], ids[:k], diffs[:k]
+
+    def scan_fetch(self, nhits: int):
+        """swa_multi_scan_fetch: the merged (seed indices, ids, diffs) of the most recent scan_batch"""
+        sidx, ids, diffs = (np.zeros(max(1, int(nhits)), dtype=np.uint32) for _ in range(3))
+        self._check(self.lib.swa_multi_scan_fetch(self.h, _ptr(sidx), _ptr(ids), _ptr(diffs), int(nhits)))
+        return sidx[:nhits], ids[:nhits], diffs[:nhits]
+
+    def scan_totals(self) -> dict:
+        """swa_multi_scan_totals: comparisons and pairs summed over the ranks, launch sequences = batches"""
+        out = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.swa_multi_scan_totals(self.h, _p64(out)))
+        return {"qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
+
+    def dn_cluster(self, hdb: "HostDb", differences: int, no_cluster_breaking: bool = False, penalties=None) -> "DnClusters":
+        """swa_dn_cluster_multi on a database uploaded with upload_hostdb: a DnClusters whose route() names what served —
+        ("graph", 0), ("scan", ranks) for the scan divided among the ranks, ("scan", 1) for rank 0 alone
+        (SWARM_AMD_MULTI_SCAN=root)."""
+        return DnClusters(self.ctx(0), hdb, differences, no_cluster_breaking, penalties, multi=self)
 
     def ctx(self, rank: int = 0) -> "Context":
         """swa_multi_ctx: rank's context as a Context that neither owns nor closes the handle (it lives as long as this

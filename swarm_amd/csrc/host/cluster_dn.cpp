@@ -43,6 +43,7 @@ struct swa_dn_result {
   int64_t differences = 0;
   uint64_t pen_mismatch = 18, pen_gapopen = 24, pen_gapextend = 13;
   bool over_graph = false;                // the bulk graph served (dn_graph.hip), not the fused scan
+  uint32_t scan_ranks = 0;                // the fused scan served, on this many ranks (1: one context alone); 0: it did not
   std::string error;
 };
 
@@ -298,87 +299,28 @@ static bool need_links(const swa_dn_result * cr) {
   return true;
 }
 
-// SWARM_AMD_MULTI_CLUSTER=device|host: where a run on several GPUs clusters what the exchange assembled on rank 0.  The
-// default follows the measurement of profiles/r23/NOTES.md (two ranks on one MI355X; from the assembled network or graph to
-// the clustering: 20 ms against 255 at d = 1 on 10 M x 150, 104 against 252 with -f, 2.4 against 68 at d = 3 on 1 M x 400).
-extern "C" int swa_multi_cluster_on_device(void) {
-  const char * where = std::getenv("SWARM_AMD_MULTI_CLUSTER");
-  return where == nullptr || std::strcmp(where, "host") != 0 ? 1 : 0;
-}
+// ---- the greedy loop over the fused scan, once, for whoever scans: one context, or the ranks of a swa_multi -----------------
+namespace {
+struct CtxScanner {
+  swa_ctx * ctx;
+  int batch(uint32_t nseeds, const uint32_t * seeds, const uint32_t * radii, uint32_t lo, int first, int ncb, uint32_t * sidx, uint32_t * ids,
+            uint32_t * diffs, uint32_t cap, uint32_t * nh) { return swa_scan_batch(ctx, nseeds, seeds, radii, lo, first, ncb, sidx, ids, diffs, cap, nh); }
+  int fetch(uint32_t * sidx, uint32_t * ids, uint32_t * diffs, uint32_t cap) { return swa_scan_fetch(ctx, sidx, ids, diffs, cap); }
+  const char * error() { return swa_last_error(ctx); }
+};
+struct MultiScanner {
+  swa_multi * multi;
+  int batch(uint32_t nseeds, const uint32_t * seeds, const uint32_t * radii, uint32_t lo, int first, int ncb, uint32_t * sidx, uint32_t * ids,
+            uint32_t * diffs, uint32_t cap, uint32_t * nh) { return swa_multi_scan_batch(multi, nseeds, seeds, radii, lo, first, ncb, sidx, ids, diffs, cap, nh); }
+  int fetch(uint32_t * sidx, uint32_t * ids, uint32_t * diffs, uint32_t cap) { return swa_multi_scan_fetch(multi, sidx, ids, diffs, cap); }
+  const char * error() { return swa_multi_last_error(multi); }
+};
+}  // namespace
 
-// d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups (and of the short
-// sequences, whose pairs are found by brute force); a database the graph route cannot serve (d > 16, or too many candidate
-// pairs with a sequence too short for d + 1 windows) or does not serve by default (graph_route_wanted) is clustered by
-// rank 0 alone with the fused scan.  The merged graph stays on rank 0's GPU, where the walk and the tables of the single-GPU
-// graph route run on it (swa_multi_dn_graph_resident), unless SWARM_AMD_MULTI_CLUSTER=host asks for the download and the host's walk.
-extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
-                                    uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
-  if (multi == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
-  if (db->n != 0 && graph_route_wanted(differences)) {
-    int rc = swa_multi_dn_begin(multi, mismatch, gapopen, gapextend, (uint64_t)differences);
-    if (rc != SWA_OK) {                                       // (no silent single-rank run behind a failed start: ADVICE r03)
-      auto * r = new swa_dn_result();
-      *out = r;
-      r->differences = differences;
-      r->error = swa_multi_last_error(multi);
-      return rc;
-    }
-    if (swa_multi_dn_graph_supported(multi) != 0) {
-      auto * r = new swa_dn_result();
-      *out = r;
-      r->differences = differences;
-      r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
-      r->over_graph = true;
-      swa_ctx * ctx0 = swa_multi_ctx(multi, 0);
-      // (the switches of the single-GPU walk keep their meaning: SWARM_AMD_DN_WALK=host, and d >= 255, walk on the host)
-      const char * walk = std::getenv("SWARM_AMD_DN_WALK");
-      if (swa_multi_cluster_on_device() == 0 || (walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) {
-        return cluster_over_graph(ctx0, multi, db, no_cluster_breaking, r);
-      }
-      return tables_on_device() ? cluster_on_device_tables(ctx0, multi, db, no_cluster_breaking, r) : cluster_on_device(ctx0, multi, db, no_cluster_breaking, r);
-    }
-  }
-  return swa_dn_cluster(swa_multi_ctx(multi, 0), db, differences, no_cluster_breaking, mismatch, gapopen, gapextend, out);
-}
-
-extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
-                              uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
-  if (ctx == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
-  auto * r = new swa_dn_result();
-  *out = r;
-  r->differences = differences;
-  r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
+template <class Scanner>
+static int greedy_over_scan(Scanner & scan, const swa_hostdb * db, int no_cluster_breaking, swa_dn_result * r) {
   const uint32_t n = db->n;
-  if (n == 0) { return SWA_OK; }
-  dn_stamp("clustering: start");
-  int rc = swa_qgram_build(ctx);
-  dn_stamp("q-gram signatures");
-  if (rc == SWA_OK) { rc = swa_search_begin(ctx, mismatch, gapopen, gapextend, (uint64_t)differences); }
-  if (rc == SWA_OK) { rc = swa_scan_begin(ctx); }
-  dn_stamp("search / scan begin");
-  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
-
-  // Bulk route (dn_graph.hip): the GPU returns the whole graph of pairs within d differences at once and the greedy
-  // loop below runs over that CSR, like d = 1.  Taken when the sequences without room for d + 1 windows are few enough
-  // for their pairs to be found by brute force (swa_dn_graph_supported).
-  // SWARM_AMD_DN=scan keeps the fused scan (one launch sequence per swarm generation), =graph insists on the graph
-  // (and is how 9 <= d <= 16 reach it: graph_route_wanted).
-  const char * route = std::getenv("SWARM_AMD_DN");
-  const bool want_graph = route != nullptr && std::strcmp(route, "graph") == 0;
-  if (graph_route_wanted(differences) && swa_dn_graph_supported(ctx) != 0) {
-    r->over_graph = true;
-    // (SWARM_AMD_DN_WALK=host: the graph downloaded and walked on the host — comparison switch)
-    const char * walk = std::getenv("SWARM_AMD_DN_WALK");
-    // (differences of 255 are what the device walk's parent-difference bytes use for "no link": d >= 255 walks on the host)
-    if ((walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) { return cluster_over_graph(ctx, nullptr, db, no_cluster_breaking, r); }
-    (void)swa_dn_set_ownership(ctx, 0, 1);                    // (a context that served one rank's share before: the whole graph)
-    return tables_on_device() ? cluster_on_device_tables(ctx, nullptr, db, no_cluster_breaking, r) : cluster_on_device(ctx, nullptr, db, no_cluster_breaking, r);
-  }
-  if (want_graph) {
-    r->error = differences > 16 ? "SWARM_AMD_DN=graph: the graph route serves d <= 16" : "SWARM_AMD_DN=graph: a sequence is too short for d + 1 windows";
-    return SWA_E_ARG;
-  }
-
+  int rc = SWA_OK;
   std::vector<uint8_t> swarmed(n, 0);
   std::vector<uint32_t> hit_ids(n), hit_diffs(n), hit_sidx(n), batch_ids, batch_radii;
   std::vector<swa_dn_result::Member> queue;
@@ -392,8 +334,9 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
     queue.clear();
     queue.push_back({seed, 0, 0});
     uint32_t nh = 0;
-    rc = swa_scan_step(ctx, seed, seed + 1, 1, 0, no_cluster_breaking, hit_ids.data(), hit_diffs.data(), n, &nh);
-    if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+    const uint32_t no_radius = 0;
+    rc = scan.batch(1, &seed, &no_radius, seed + 1, 1, no_cluster_breaking, hit_sidx.data(), hit_ids.data(), hit_diffs.data(), n, &nh);
+    if (rc != SWA_OK) { r->error = scan.error(); return rc; }
     for (uint32_t k = 0; k < nh; ++k) {                    // first generation, pool (= id) order
       swarmed[hit_ids[k]] = 1;
       queue.push_back({hit_ids[k], 1, hit_diffs[k]});
@@ -414,13 +357,13 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
       batch_ids.resize(nb);
       batch_radii.resize(nb);
       for (uint32_t k = 0; k < nb; ++k) { batch_ids[k] = queue[next + k].id; batch_radii[k] = queue[next + k].radius; }
-      rc = swa_scan_batch(ctx, nb, batch_ids.data(), batch_radii.data(), seed + 1, 0, no_cluster_breaking,
-                          hit_sidx.data(), hit_ids.data(), hit_diffs.data(), (uint32_t)hit_ids.size(), &nh);
+      rc = scan.batch(nb, batch_ids.data(), batch_radii.data(), seed + 1, 0, no_cluster_breaking,
+                      hit_sidx.data(), hit_ids.data(), hit_diffs.data(), (uint32_t)hit_ids.size(), &nh);
       if (rc == SWA_E_CAPACITY) {
         hit_sidx.resize(nh); hit_ids.resize(nh); hit_diffs.resize(nh);
-        rc = swa_scan_fetch(ctx, hit_sidx.data(), hit_ids.data(), hit_diffs.data(), nh);
+        rc = scan.fetch(hit_sidx.data(), hit_ids.data(), hit_diffs.data(), nh);
       }
-      if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+      if (rc != SWA_OK) { r->error = scan.error(); return rc; }
       const size_t batch_first = next;
       uint32_t h = 0;
       for (uint32_t b = 0; b < nb; ++b) {
@@ -456,12 +399,122 @@ extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t diff
   return SWA_OK;
 }
 
+// SWARM_AMD_MULTI_CLUSTER=device|host: where a run on several GPUs clusters what the exchange assembled on rank 0.  The
+// default follows the measurement of profiles/r23/NOTES.md (two ranks on one MI355X; from the assembled network or graph to
+// the clustering: 20 ms against 255 at d = 1 on 10 M x 150, 104 against 252 with -f, 2.4 against 68 at d = 3 on 1 M x 400).
+extern "C" int swa_multi_cluster_on_device(void) {
+  const char * where = std::getenv("SWARM_AMD_MULTI_CLUSTER");
+  return where == nullptr || std::strcmp(where, "host") != 0 ? 1 : 0;
+}
+
+// d >= 2 on several GPUs (SWARM_AMD_DEVICES): the bulk graph shared out by ownership of window groups (and of the short
+// sequences, whose pairs are found by brute force); a database the graph route cannot serve (d > 16, or too many candidate
+// pairs with a sequence too short for d + 1 windows) or does not serve by default (graph_route_wanted) is clustered with
+// the fused scan divided among the ranks by ownership of the pool (swa_multi_scan_*: the same greedy loop, greedy_over_scan),
+// or by rank 0 alone where SWARM_AMD_MULTI_SCAN=root asks for the comparison.  The merged graph stays on rank 0's GPU, where
+// the walk and the tables of the single-GPU graph route run on it (swa_multi_dn_graph_resident), unless SWARM_AMD_MULTI_CLUSTER=host asks for the download and the host's walk.
+extern "C" int swa_dn_cluster_multi(swa_multi * multi, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
+                                    uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
+  if (multi == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
+  if (db->n != 0 && graph_route_wanted(differences)) {
+    int rc = swa_multi_dn_begin(multi, mismatch, gapopen, gapextend, (uint64_t)differences);
+    if (rc != SWA_OK) {                                       // (no silent single-rank run behind a failed start: ADVICE r03)
+      auto * r = new swa_dn_result();
+      *out = r;
+      r->differences = differences;
+      r->error = swa_multi_last_error(multi);
+      return rc;
+    }
+    if (swa_multi_dn_graph_supported(multi) != 0) {
+      auto * r = new swa_dn_result();
+      *out = r;
+      r->differences = differences;
+      r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
+      r->over_graph = true;
+      swa_ctx * ctx0 = swa_multi_ctx(multi, 0);
+      // (the switches of the single-GPU walk keep their meaning: SWARM_AMD_DN_WALK=host, and d >= 255, walk on the host)
+      const char * walk = std::getenv("SWARM_AMD_DN_WALK");
+      if (swa_multi_cluster_on_device() == 0 || (walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) {
+        return cluster_over_graph(ctx0, multi, db, no_cluster_breaking, r);
+      }
+      return tables_on_device() ? cluster_on_device_tables(ctx0, multi, db, no_cluster_breaking, r) : cluster_on_device(ctx0, multi, db, no_cluster_breaking, r);
+    }
+  }
+  // the fused scan.  (SWARM_AMD_DN=graph where the graph cannot serve: rank 0's single-context call words the refusal.)
+  const char * route = std::getenv("SWARM_AMD_DN");
+  const char * share = std::getenv("SWARM_AMD_MULTI_SCAN");
+  const bool on_root = (share != nullptr && std::strcmp(share, "root") == 0) || (route != nullptr && std::strcmp(route, "graph") == 0) || db->n == 0;
+  if (on_root) { return swa_dn_cluster(swa_multi_ctx(multi, 0), db, differences, no_cluster_breaking, mismatch, gapopen, gapextend, out); }
+  auto * r = new swa_dn_result();
+  *out = r;
+  r->differences = differences;
+  r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
+  dn_stamp("clustering: start");
+  int rc = swa_multi_dn_begin(multi, mismatch, gapopen, gapextend, (uint64_t)differences);
+  dn_stamp("q-gram signatures");
+  if (rc == SWA_OK) { rc = swa_multi_scan_begin(multi); }
+  dn_stamp("search / scan begin");
+  if (rc != SWA_OK) { r->error = swa_multi_last_error(multi); return rc; }
+  MultiScanner scanner{multi};
+  r->scan_ranks = (uint32_t)swa_multi_size(multi);
+  rc = greedy_over_scan(scanner, db, no_cluster_breaking, r);
+  dn_stamp("scan: swarms made");
+  return rc;
+}
+
+extern "C" int swa_dn_cluster(swa_ctx * ctx, const swa_hostdb * db, int64_t differences, int no_cluster_breaking,
+                              uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, swa_dn_result ** out) {
+  if (ctx == nullptr || db == nullptr || out == nullptr || differences < 2) { return SWA_E_ARG; }
+  auto * r = new swa_dn_result();
+  *out = r;
+  r->differences = differences;
+  r->pen_mismatch = mismatch; r->pen_gapopen = gapopen; r->pen_gapextend = gapextend;
+  const uint32_t n = db->n;
+  if (n == 0) { return SWA_OK; }
+  dn_stamp("clustering: start");
+  int rc = swa_qgram_build(ctx);
+  dn_stamp("q-gram signatures");
+  if (rc == SWA_OK) { rc = swa_search_begin(ctx, mismatch, gapopen, gapextend, (uint64_t)differences); }
+  if (rc == SWA_OK) { rc = swa_scan_set_ownership(ctx, 0, 1); }   // (a context that scanned one rank's share before: the whole pool)
+  if (rc == SWA_OK) { rc = swa_scan_begin(ctx); }
+  dn_stamp("search / scan begin");
+  if (rc != SWA_OK) { r->error = swa_last_error(ctx); return rc; }
+
+  // Bulk route (dn_graph.hip): the GPU returns the whole graph of pairs within d differences at once and the greedy
+  // loop below runs over that CSR, like d = 1.  Taken when the sequences without room for d + 1 windows are few enough
+  // for their pairs to be found by brute force (swa_dn_graph_supported).
+  // SWARM_AMD_DN=scan keeps the fused scan (one launch sequence per swarm generation), =graph insists on the graph
+  // (and is how 9 <= d <= 16 reach it: graph_route_wanted).
+  const char * route = std::getenv("SWARM_AMD_DN");
+  const bool want_graph = route != nullptr && std::strcmp(route, "graph") == 0;
+  if (graph_route_wanted(differences) && swa_dn_graph_supported(ctx) != 0) {
+    r->over_graph = true;
+    // (SWARM_AMD_DN_WALK=host: the graph downloaded and walked on the host — comparison switch)
+    const char * walk = std::getenv("SWARM_AMD_DN_WALK");
+    // (differences of 255 are what the device walk's parent-difference bytes use for "no link": d >= 255 walks on the host)
+    if ((walk != nullptr && std::strcmp(walk, "host") == 0) || differences >= 255) { return cluster_over_graph(ctx, nullptr, db, no_cluster_breaking, r); }
+    (void)swa_dn_set_ownership(ctx, 0, 1);                    // (a context that served one rank's share before: the whole graph)
+    return tables_on_device() ? cluster_on_device_tables(ctx, nullptr, db, no_cluster_breaking, r) : cluster_on_device(ctx, nullptr, db, no_cluster_breaking, r);
+  }
+  if (want_graph) {
+    r->error = differences > 16 ? "SWARM_AMD_DN=graph: the graph route serves d <= 16" : "SWARM_AMD_DN=graph: a sequence is too short for d + 1 windows";
+    return SWA_E_ARG;
+  }
+
+  CtxScanner scanner{ctx};
+  r->scan_ranks = 1;
+  rc = greedy_over_scan(scanner, db, no_cluster_breaking, r);
+  dn_stamp("scan: swarms made");
+  return rc;
+}
+
 extern "C" void swa_dn_result_free(swa_dn_result * r) { delete r; }
 extern "C" const char * swa_dn_result_error(const swa_dn_result * r) { return r != nullptr ? r->error.c_str() : ""; }
 
 // {number of swarms, largest swarm, max generations} — the log's summary (src/algo.cc:699-705)
 extern "C" uint32_t swa_dn_result_link_fetches(const swa_dn_result * r) { return r != nullptr ? r->link_fetches : 0u; }
 extern "C" int swa_dn_result_over_graph(const swa_dn_result * r) { return r != nullptr && r->over_graph ? 1 : 0; }
+extern "C" uint32_t swa_dn_result_scan_ranks(const swa_dn_result * r) { return r != nullptr ? r->scan_ranks : 0u; }
 
 extern "C" void swa_dn_result_summary(const swa_dn_result * r, uint64_t * out3) {
   out3[0] = r->swarms.size();

@@ -632,6 +632,11 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
                             : swa_dn_cluster(ctx, db, o.differences, o.no_break ? 1 : 0, (uint64_t)o.pen_mismatch, (uint64_t)o.pen_gapopen,
                                              (uint64_t)o.pen_gapextend, &res);
       if (rc != SWA_OK) { die(res != nullptr ? swa_dn_result_error(res) : "clustering failed"); }
+      if (multi != nullptr && std::getenv("SWARM_AMD_MULTI_REPORT") != nullptr && swa_dn_result_scan_ranks(res) != 0) {
+        const uint32_t ranks = swa_dn_result_scan_ranks(res);  // (SWARM_AMD_MULTI_SCAN=root: rank 0 alone, the comparison)
+        if (ranks > 1) { std::fprintf(stderr, "multi: scan divided among %u ranks\n", ranks); }
+        else { std::fprintf(stderr, "multi: scan on rank 0 alone\n"); }
+      }
     } else {
       rc = SWA_OK;
     }

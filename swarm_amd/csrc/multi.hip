@@ -16,7 +16,9 @@
 // swa_rccl().AllReduce(min) (src/algod1.cc:244-258 keeps the smallest heavy id), the two heavy-side counters add up.
 //
 // d = 0 (derep_on_root below): the reads of a rank's slice travel to the rank that owns their hash, the owners dereplicate,
-// first_identical[] is assembled on rank 0.  d >= 2: the bulk graph divided by ownership of window groups (further below).
+// first_identical[] is assembled on rank 0.  d >= 2: the bulk graph divided by ownership of window groups (further below),
+// and the fused scan divided by ownership of the pool (swa_multi_scan_*, at the end: no exchange at all, every rank's hits
+// come to the host through its own pinned mirror and are merged there).
 //
 // The same code runs with several contexts on ONE device (SWARM_AMD_DEVICES=0,0: what a one-GPU box can
 // test); RCCL refuses two ranks on one GPU, so that configuration moves the same bytes with device-to-
@@ -43,6 +45,10 @@ struct swa_multi {
   int last_build = SWA_MULTI_BUILD_NONE;   // of the last swa_multi_d1_network* call (swa_multi_d1_last_build)
   std::vector<uint64_t> derep_received;    // of the last swa_multi_derep* call (swa_multi_derep_totals): records every owner received,
   uint64_t derep_rounds = 0, derep_routed = 0;   // the rounds of the slowest owner, the records routed
+  bool scan_ready = false;                 // swa_multi_scan_begin has run
+  uint64_t scan_batches = 0;               // swa_multi_scan_batch calls since then (swa_multi_scan_totals)
+  struct ScanHit { uint32_t sidx, id, diff; };
+  std::vector<ScanHit> scan_hits;          // the merged hits of the last swa_multi_scan_batch (swa_multi_scan_fetch)
   std::string err;
 };
 
@@ -775,6 +781,133 @@ extern "C" int swa_multi_dn_graph_totals(swa_multi * m, uint64_t * out3) {
     uint64_t t[3] = {0, 0, 0};
     (void)swa_dn_graph_totals(c, t);
     out3[0] += t[0]; out3[1] += t[1]; out3[2] = std::max(out3[2], t[2]);
+  }
+  return SWA_OK;
+}
+
+// ---- d >= 2 on several GPUs: the fused scan (scan.hip) divided by ownership of the pool --------------------------------
+// What src/scan.cc:221-256 does with threads: the targets of one search shared out.  Rank r scans the amplicons i with
+// (i >> 5) % world == r (swa_scan_set_ownership) against every seed of the batch.  One host thread enqueues the launch
+// sequence on every rank's stream first and then finishes rank by rank (no thread per generation: starting and joining
+// `world` threads costs more than a late generation's kernels); a rank whose pair arrays overflowed is redone alone, a rank
+// with no amplicon of its own at or above lowest_unswarmed launches nothing.  Every rank's hits arrive sorted through its
+// pinned mirror; they are merged here by (seed index, id).  No RCCL call: the same code serves ranks on one device and
+// ranks on distinct devices.
+extern "C" int swa_multi_scan_begin(swa_multi * m) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  m->scan_ready = false;
+  const int world = (int)m->ctx.size();
+  const int rc = on_all(m, [&](int r) {
+    swa_ctx * c = m->ctx[(size_t)r];
+    SWA_TRY(swa_scan_set_ownership(c, (uint32_t)r, (uint32_t)world));
+    return swa_scan_begin(c);
+  });
+  if (rc != SWA_OK) { return rc; }
+  m->scan_ready = true;
+  m->scan_batches = 0;
+  m->scan_hits.clear();
+  return SWA_OK;
+}
+
+extern "C" int swa_multi_scan_fetch(swa_multi * m, uint32_t * hit_seedidx, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  const size_t got = m->scan_hits.size();
+  if (got > cap) { return fail(m, SWA_E_CAPACITY, "swa_multi_scan_fetch: hit buffer too small"); }
+  if (got != 0 && (hit_ids == nullptr || hit_diffs == nullptr)) { return fail(m, SWA_E_ARG, "swa_multi_scan_fetch: null buffer"); }
+  for (size_t k = 0; k < got; ++k) {
+    if (hit_seedidx != nullptr) { hit_seedidx[k] = m->scan_hits[k].sidx; }
+    hit_ids[k] = m->scan_hits[k].id;
+    hit_diffs[k] = m->scan_hits[k].diff;
+  }
+  return SWA_OK;
+}
+
+extern "C" int swa_multi_scan_batch(swa_multi * m, uint32_t nseeds, const uint32_t * seeds, const uint32_t * radii, uint32_t lowest_unswarmed,
+                                    int first_generation, int no_cluster_breaking, uint32_t * hit_seedidx, uint32_t * hit_ids,
+                                    uint32_t * hit_diffs, uint32_t cap, uint32_t * nhits) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  if (!m->scan_ready) { return fail(m, SWA_E_ARG, "swa_multi_scan_batch: call swa_multi_scan_begin first"); }
+  const int world = (int)m->ctx.size();
+  const swa_scan_call call{nseeds, seeds, radii, lowest_unswarmed, first_generation, no_cluster_breaking};
+  if (const char * why = swa_scan_check_call(m->ctx[0], call, hit_seedidx, hit_ids, hit_diffs, cap, nhits)) {
+    return fail(m, SWA_E_ARG, std::string("swa_multi_scan_batch: ") + why);
+  }
+  for (int r = 0; r < world; ++r) {                            // (a rank that was given other work since swa_multi_scan_begin)
+    swa_ctx * c = m->ctx[(size_t)r];
+    if (!c->up.scan_ready || c->scan_world != (uint32_t)world || c->scan_rank != (uint32_t)r) {
+      return fail(m, SWA_E_ARG, "swa_multi_scan_batch: rank " + std::to_string(r) + " has left the scan, call swa_multi_scan_begin again");
+    }
+  }
+  ++m->scan_batches;
+  m->scan_hits.clear();
+  const uint32_t n = m->ctx[0]->db.n;
+  std::vector<char> active((size_t)world, 0);
+  auto failed = [&](int r, int rc) { return fail(m, rc, "rank " + std::to_string(r) + ": " + swa_last_error(m->ctx[(size_t)r])); };
+  // 1. every rank with a share: its launch sequence on its stream
+  for (int r = 0; r < world; ++r) {
+    swa_ctx * c = m->ctx[(size_t)r];
+    uint32_t share[2] = {0, 0};
+    (void)swa_scan_share_for(n, lowest_unswarmed, (uint32_t)r, (uint32_t)world, share);
+    c->scan_perm.clear();
+    if (share[0] == 0 && world > 1) {
+      if (first_generation != 0) { c->scan_cand_bound = 0; }   // (as swa_scan_enqueue leaves a rank that launches nothing)
+      continue;
+    }
+    active[(size_t)r] = 1;
+    ++c->scan_launches;
+    const int rc = swa_scan_enqueue(c, call);
+    if (rc != SWA_OK) {
+      for (int k = 0; k < r; ++k) { if (active[(size_t)k]) { (void)hipSetDevice(m->devices[(size_t)k]); (void)hipStreamSynchronize(m->ctx[(size_t)k]->stream); } }
+      return failed(r, rc);
+    }
+  }
+  // 2. rank by rank: wait, read its mirror (a rank that overflowed its pair arrays repeats its sequence alone)
+  int bad_rank = -1, bad_rc = SWA_OK;
+  uint64_t total = 0;
+  for (int r = 0; r < world; ++r) {
+    if (!active[(size_t)r]) { continue; }
+    uint32_t got = 0;
+    const int rc = swa_scan_finish(m->ctx[(size_t)r], call, &got);
+    if (rc != SWA_OK && bad_rank < 0) { bad_rank = r; bad_rc = rc; }     // (the others are still waited for)
+    total += got;
+  }
+  if (bad_rank >= 0) { return failed(bad_rank, bad_rc); }
+  // 3. the ranks' sorted lists merged by (seed index, id)
+  m->scan_hits.reserve(total);
+  for (int r = 0; r < world; ++r) {
+    if (!active[(size_t)r]) { continue; }
+    swa_ctx * c = m->ctx[(size_t)r];
+    const auto * triples = reinterpret_cast<const swa_multi::ScanHit *>(c->scan_host.data() + 4);
+    const size_t before = m->scan_hits.size();
+    for (uint32_t at : c->scan_perm) { m->scan_hits.push_back(triples[at]); }
+    std::inplace_merge(m->scan_hits.begin(), m->scan_hits.begin() + (std::ptrdiff_t)before, m->scan_hits.end(),
+                       [](const swa_multi::ScanHit & x, const swa_multi::ScanHit & y) { return x.sidx != y.sidx ? x.sidx < y.sidx : x.id < y.id; });
+  }
+  *nhits = (uint32_t)total;
+  if (total > cap) { return fail(m, SWA_E_CAPACITY, "swa_multi_scan_batch: hit buffer too small, use swa_multi_scan_fetch"); }
+  return swa_multi_scan_fetch(m, hit_seedidx, hit_ids, hit_diffs, cap);
+}
+
+// single (sub)seed convenience form
+extern "C" int swa_multi_scan_step(swa_multi * m, uint32_t seed, uint32_t lowest_unswarmed, int first_generation, uint32_t radius,
+                                   int no_cluster_breaking, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap, uint32_t * nhits) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  std::vector<uint32_t> idx(cap > 0 ? cap : 1);
+  return swa_multi_scan_batch(m, 1, &seed, &radius, lowest_unswarmed, first_generation, no_cluster_breaking, idx.data(), hit_ids, hit_diffs, cap, nhits);
+}
+
+// out3 = {q-gram comparisons and aligned pairs, summed over the ranks (the shares partition the candidates: the numbers of
+// a single context), launch sequences = batches since swa_multi_scan_begin (not a sum)}
+extern "C" int swa_multi_scan_totals(swa_multi * m, uint64_t * out3) {
+  if (m == nullptr || out3 == nullptr) { return SWA_E_ARG; }
+  if (!m->scan_ready) { return fail(m, SWA_E_ARG, "swa_multi_scan_totals: no scan state"); }
+  out3[0] = out3[1] = 0;
+  out3[2] = m->scan_batches;
+  for (size_t r = 0; r < m->ctx.size(); ++r) {
+    uint64_t t[3] = {0, 0, 0};
+    const int rc = swa_scan_totals(m->ctx[r], t);
+    if (rc != SWA_OK) { return fail(m, rc, "rank " + std::to_string(r) + ": " + swa_last_error(m->ctx[r])); }
+    out3[0] += t[0]; out3[1] += t[1];
   }
   return SWA_OK;
 }

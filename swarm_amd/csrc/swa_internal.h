@@ -332,6 +332,7 @@ struct swa_ctx {
   uint64_t scan_launches = 0;
   uint64_t scan_compare_discount = 0;   // comparisons of passes that overflowed the pair arrays and were redone
   uint64_t scan_redone = 0, scan_relists = 0, scan_by_copy = 0;   // swa_scan_debug_state
+  uint32_t scan_rank = 0, scan_world = 1;   // swa_scan_set_ownership: the part of the pool this context scans
 
   // fastidious state
   swa_dbuf d_light, d_graft, d_bloomflex, d_fpatterns, d_queue, d_fcounters;
@@ -406,6 +407,20 @@ inline void swa_lap(swa_ctx * ctx, const char * what);
 int swa_reserve(swa_ctx * ctx, swa_dbuf & buf, size_t bytes);   // grow-only hipMalloc
 void swa_release(swa_dbuf & buf);
 int swa_hash_sequences(swa_ctx * ctx);                           // d1.hip: Zobrist table + d_seqhash + d_aux
+
+// ---- what multi.hip takes from scan.hip: one batch of the fused d >= 2 scan in two halves ---------------------------------
+// the arguments of swa_scan_batch; seeds and radii stay the caller's and valid until swa_scan_finish has returned
+struct swa_scan_call {
+  uint32_t nseeds;
+  const uint32_t * seeds, * radii;
+  uint32_t lowest_unswarmed;
+  int first_generation, no_cluster_breaking;
+};
+// nullptr, or why swa_scan_batch refuses these arguments
+const char * swa_scan_check_call(const swa_ctx * ctx, const swa_scan_call & call, const uint32_t * hit_seedidx, const uint32_t * hit_ids,
+                                 const uint32_t * hit_diffs, uint32_t cap, const uint32_t * nhits);
+int swa_scan_enqueue(swa_ctx * ctx, const swa_scan_call & call);                  // the launch sequence on ctx->stream; does not wait
+int swa_scan_finish(swa_ctx * ctx, const swa_scan_call & call, uint32_t * nhits); // waits; redoes an overflowed pass; leaves the sorted hits for swa_scan_fetch
 
 // ---- what fastidious.hip takes from d1.hip ----------------------------------------------------------------------------
 // Host functions, defined in d1.hip (swa_scan_offsets: in d1_part.hip), whose kernels stay in that unit's code object.  All enqueue on ctx->stream and return SWA_OK
