@@ -276,7 +276,18 @@ int swa_d1_guard_retries(const swa_ctx * ctx);
 
 /* Introspection used by the parity tests (bit-exact against the oracle): copies to host.
    what: 0 seqhash u64[n] · 1 Bloom bitmap u64[table_size/8] · 2 Zobrist table
-   u64[4*(longest+2)] (0..2 build the database-wide structures on demand)
+   u64[4*(longest+2)] · 3 the per-amplicon records of the hash kernel, n records of 64 bytes: u64 h, dall, iall, a32,
+   d32, i32 (the Zobrist hash, the deletion and insertion XOR streams, and the three restricted to positions below
+   pb), u32 pb (first position of the run of equal nucleotides that holds position anchor width - 1; the width itself
+   for a shorter sequence, whose restricted streams are the full ones), u32[3] zero (0..3 build the database-wide
+   structures on demand)
+   · 4 facts of the uploaded database as the host holds them, u32[8]: the shortest sequence, the sequences of every
+   width class (up to 160, 256, 480, 672 nt, longer), SWA_MAX_ZOBRIST_LDS of this build, 0; SWA_E_ARG when no build
+   has read them · 5 the window sample of this upload as the host saw it, u32[16]: per candidate offset 0 / 32 / 64 /
+   96 the sampled amplicons too short for it [4] and the sampled amplicons in stranded groups [4], the stride, the
+   number of samples, the offset and the window width chosen FROM THE SAMPLE (swa_d1_anchor_windows tells what the
+   first build's safety net made of it), 1 when a sample was drawn (0 under SWA_D1_WINDOWS=0, all of the above 0
+   then), 0, 0, 0; SWA_E_ARG when no build has chosen windows (4 and 5 copy host memory: no kernel runs, nothing changes)
    · 10 / 11 member ids in group order of the streaming prefix / suffix index u32[n] · 12 / 13 their work-item
    buffers · 14 the counters u32[64] · 15 the amplicon lines (tools/check_index.py, tools/check_stream.py)
    · 17 / 18 the bucket starts of the key partition of the prefix / suffix index, u64[buckets + 1] with buckets =

@@ -64,6 +64,12 @@ class DbView(C.Structure):
                 ("seqlen", C.c_void_p), ("abundance", C.c_void_p)]
 
 
+# struct swa_aux (csrc/d1_common.inc): what k_seqhash writes per amplicon, selector 3 of swa_d1_debug_read
+AUX_DTYPE = np.dtype([("h", "<u8"), ("dall", "<u8"), ("iall", "<u8"), ("a32", "<u8"), ("d32", "<u8"), ("i32", "<u8"),
+                      ("pb", "<u4"), ("pad", "<u4", (3,))])
+assert AUX_DTYPE.itemsize == 64
+
+
 class DbUnorderedView(C.Structure):
     """swa_db_unordered_view: the reader's word pools in file order + where every amplicon's words begin"""
     _fields_ = [("n", C.c_uint32), ("longest", C.c_uint32), ("pieces", C.c_uint32), ("piece_words", C.c_void_p),
@@ -893,6 +899,25 @@ class Context:
         out = np.zeros(count, dtype=np.uint64)
         self._check(self.lib.swa_d1_debug_read(self.h, what, _ptr(out), out.nbytes))
         return out
+
+    def d1_aux(self) -> np.ndarray:
+        """Selector 3 of swa_d1_debug_read: the record k_seqhash writes per amplicon (AUX_DTYPE), n of them."""
+        out = np.zeros(self.n, dtype=AUX_DTYPE)
+        self._check(self.lib.swa_d1_debug_read(self.h, 3, _ptr(out), out.nbytes))
+        return out
+
+    def d1_db_facts(self) -> dict:
+        """Selector 4: what the host keeps of k_db_lengths — the shortest sequence and the sequences per width class (up
+        to 160, 256, 480, 672 nt, longer) — and SWA_MAX_ZOBRIST_LDS of the build."""
+        w = self.d1_debug(4, 4).view(np.uint32)
+        return {"shortest": int(w[0]), "class_pop": [int(v) for v in w[1:6]], "max_zobrist_lds": int(w[6])}
+
+    def d1_window_sample(self) -> dict:
+        """Selector 5: the window sample of this upload as choose_anchor_windows saw it, and the choice made from it (before
+        the safety net of the first build)."""
+        w = self.d1_debug(5, 8).view(np.uint32)
+        return {"too_short": [int(v) for v in w[0:4]], "mass": [int(v) for v in w[4:8]], "stride": int(w[8]), "samples": int(w[9]),
+                "offset": int(w[10]), "width": int(w[11]), "taken": bool(w[12])}
 
     def d1_lists_form(self) -> int:
         """swa_d1_lists_form: the form the work lists of the streaming index in place were built with (lists_form_for)"""

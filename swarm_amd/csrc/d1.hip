@@ -832,11 +832,18 @@ static int choose_anchor_windows(swa_ctx * ctx) {
   uint32_t host[8] = {};
   SWA_HIP(ctx, hipMemcpyAsync(host, stats, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
   SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // (kept for swa_d1_debug_read 5; sample_offset / sample_w: the ends, unless a candidate below qualifies)
+  swa_db_facts::d1_facts & facts = ctx->up.d1;
+  memcpy(facts.sample_stats, host, sizeof(host));
+  facts.sample_stride = stride; facts.sample_count = samples;
+  facts.sample_offset = 0; facts.sample_w = ctx->ix.anchor_w;
+  facts.sample_taken = true;
   for (uint32_t c = 0; c < kSampleCandidates; ++c) {
     const bool few_short = host[c] <= samples / 64u || c == 0;
     if (host[4 + c] <= samples / 64u && few_short) {
       ctx->ix.anchor_a = ctx->ix.anchor_b = 32u * c;
       ctx->ix.anchor_w = 32u * anchor_nwin_for(shortest, 32u * c, max_nwin);
+      facts.sample_offset = ctx->ix.anchor_a; facts.sample_w = ctx->ix.anchor_w;
       return SWA_OK;
     }
     if (!few_short) { break; }                               // (larger offsets only strand more seeds)
@@ -1482,6 +1489,34 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
     SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SWA_OK;
   }
+  if (what == 4 || what == 5) {
+    // host-side facts of the uploaded database, copied as they stand (no kernel, no index touched).  4: u32[8] = the shortest
+    // sequence, the populations of the width classes [0 .. kWidthClasses] (the last: beyond the pair kernels), SWA_MAX_ZOBRIST_LDS
+    // of this build, 0 (ensure_db_lengths).  5: u32[16] = the window sample choose_anchor_windows drew for this upload:
+    // too short [4], stranded mass [4] per candidate offset 0 / 32 / 64 / 96, stride, samples, the offset and the width chosen
+    // from the sample (the safety net of the first build may since have moved swa_d1_anchor_windows), 1 if a sample was drawn
+    // (0 under SWA_D1_WINDOWS=0: the words before it are 0 then), 0, 0, 0
+    const swa_db_facts::d1_facts & facts = ctx->up.d1;
+    uint32_t words[16] = {};
+    size_t bytes = 0;
+    if (what == 4) {
+      if (!facts.props_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: the lengths of this database were never read"); }
+      words[0] = facts.db_shortest;
+      for (uint32_t c = 0; c <= kWidthClasses; ++c) { words[1 + c] = facts.class_pop[c]; }
+      words[2 + kWidthClasses] = SWA_MAX_ZOBRIST_LDS;
+      bytes = 8 * sizeof(uint32_t);
+    } else {
+      if (!facts.windows_ready) { return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: no anchor windows were chosen for this database"); }
+      memcpy(words, facts.sample_stats, sizeof(facts.sample_stats));
+      words[8] = facts.sample_stride; words[9] = facts.sample_count;
+      words[10] = facts.sample_offset; words[11] = facts.sample_w;
+      words[12] = facts.sample_taken ? 1u : 0u;
+      bytes = 16 * sizeof(uint32_t);
+    }
+    if (out_bytes < bytes) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_debug_read: buffer too small"); }
+    memcpy(out, words, bytes);
+    return SWA_OK;
+  }
   SWA_TRY(swa_ensure_full_index(ctx));
   const void * src = nullptr;
   size_t bytes = 0;
@@ -1489,6 +1524,7 @@ extern "C" int swa_d1_debug_read(swa_ctx * ctx, int what, void * out, size_t out
     case 0: src = ctx->d_seqhash.ptr; bytes = uint64_t(ctx->db.n) * sizeof(uint64_t); break;
     case 1: src = ctx->d_bloom.ptr; bytes = ctx->ix.bloom_words * sizeof(uint64_t); break;
     case 2: src = ctx->d_zobrist.ptr; bytes = 4ull * ctx->zobrist_len * sizeof(uint64_t); break;
+    case 3: src = ctx->d_aux.ptr; bytes = uint64_t(ctx->db.n) * sizeof(swa_aux); break;
     default: return swa_fail_msg(ctx, SWA_E_ARG, "swa_d1_debug_read: unknown selector");
   }
   if (out_bytes < bytes) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_debug_read: buffer too small"); }

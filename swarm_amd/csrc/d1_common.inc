@@ -31,6 +31,7 @@ struct alignas(16) swa_aux {     // per amplicon, written by k_seqhash
   uint32_t pb;
   uint32_t pad[3];
 };
+static_assert(sizeof(swa_aux) == 64, "swa_aux: the record swa_d1_debug_read 3 hands out (capi.py: AUX_DTYPE)");
 
 struct swa_item { uint32_t begin, size, chunk; };      // members [begin, begin + size) of the group-order id list; chunk (tiled kernel): row tile | column part << 6
 struct swa_fallback { uint32_t seed, range; };         // range: 0 all positions, 1 the neighbours that share the prefix-side window, 2 the others

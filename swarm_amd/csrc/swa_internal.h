@@ -159,6 +159,12 @@ struct swa_db_facts {
     bool windows_ready = false;    // the anchor windows of this database are known (choose_anchor_windows + the safety net):
     uint32_t windows_chosen = 0;   // anchor_a = anchor_b = this
     uint32_t windows_w = 32;       // ... and anchor_w = this
+    // the window sample as choose_anchor_windows saw it (its scratch is reused by the build: this host copy is all that is
+    // left of it) and what it chose from it, before the safety net of the first build may replace windows_chosen
+    bool sample_taken = false;     // a sample was drawn for this upload (not under SWA_D1_WINDOWS=0)
+    uint32_t sample_stats[8] = {}; // [0..4) sampled amplicons too short for candidate offset 32 c, [4..8) their stranded mass
+    uint32_t sample_stride = 0, sample_count = 0;   // every sample_stride-th amplicon, sample_count of them
+    uint32_t sample_offset = 0, sample_w = 32;      // the choice made from the sample: anchor_a = anchor_b, anchor_w
     bool lines_ready = false;      // d_lines holds this database's amplicon lines (made once per upload), lines_w words each
     uint32_t lines_quads = 0;      // ... of this many 16-byte quads each (4, 8 or 16)
     // length classes of the database against the pair route's cap (k_fast_length_classes; read once per upload, and only
