@@ -424,6 +424,16 @@ int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]);
    [2] the task cap in effect (1 GiB of tasks, or SWA_FAST_TASK_CAP; never below 7 longest + 4), [3] the most tasks a batch
    that ran produced (<= [2]).  All zero when the Bloom route did not run. */
 int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]);
+/* Of the last swa_d1_fastidious[_shard | _resident] call, the filter of the Bloom route (bloomflex.cc:91-115) as its light pass
+   left it: facts[0] fsize, its 64-bit words (n_bytes >> 3 with n_bytes = (m - 1) / 8 + 1), [1] m, its bits (7 bloom_bits a
+   nucleotide of the light amplicons handed to the route, at least 64), [2] k, the bits of a pattern (int(0.4 bloom_bits), at
+   least 1), [3] bloom_bits as passed, [4] the tasks (heavy microvariants that passed the filter) summed over the batches that
+   ran to the end — a batch that was redone smaller counts as it ran, not twice — [5..7] 0.  words may be NULL: the facts
+   alone.  Otherwise it receives the fsize words (inverted polarity: a cleared bit is a set one of the reference's filter),
+   cap_words = the room in words; SWA_E_CAPACITY when it is less than fsize (the facts are valid).  All zero, and words
+   untouched, when that call did not run the Bloom route, and after a database upload.  A copy: no kernel runs and nothing of
+   the pass changes.  Each shard of a sharded pass builds the whole filter; [4] is the shard's own. */
+int swa_d1_fastidious_bloom_read(swa_ctx * ctx, uint64_t facts[8], uint64_t * words, uint64_t cap_words);
 
 /* ---- B2 on the clustering in place: swarm sums, light flags, candidates and grafting without the host ----------------
    The reference does its fastidious bookkeeping on the host, around the two passes above; a caller that binds seam B2 and

@@ -82,7 +82,7 @@ EXPORTS = [
     "swa_d1_cluster_resident_prepared", "swa_host_pin", "swa_host_unpin", "swa_ctx_warmup_downloads",
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_links_split", "swa_d1_csr_from_lists",
-    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_bloom_batches", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_fastidious_plan_modes", "swa_d1_fastidious_sites_cap", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_d1_lists_form_for", "swa_d1_lists_form", "swa_qgram_build", "swa_qgram_diff",
+    "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_bloom_batches", "swa_d1_fastidious_bloom_read", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_fastidious_plan_modes", "swa_d1_fastidious_sites_cap", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_d1_lists_form_for", "swa_d1_lists_form", "swa_qgram_build", "swa_qgram_diff",
     "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
@@ -165,6 +165,7 @@ def load_library() -> C.CDLL:
     lib.swa_d1_fastidious_plan.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_totals.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_bloom_batches.argtypes = [C.c_void_p, C.c_void_p]
+    lib.swa_d1_fastidious_bloom_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     lib.swa_d1_fastidious_split.argtypes = [C.c_void_p, C.c_void_p]
     lib.swa_d1_fastidious_plan_for.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.swa_d1_fastidious_plan_modes.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
@@ -1095,6 +1096,20 @@ class Context:
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.swa_d1_fastidious_bloom_batches(self.h, _ptr(out)))
         return [int(v) for v in out]
+
+    def d1_fastidious_bloom_read(self, words: bool = True, cap_words: int | None = None):
+        """swa_d1_fastidious_bloom_read of the last d1_fastidious call: ([fsize, m, k, bloom_bits, tasks of the batches that
+        ran, 0, 0, 0], the fsize words of the filter as the light pass left them); the array is None with words=False and
+        when the Bloom route did not run.  cap_words: the room offered instead of fsize (less: SwaError(SWA_E_CAPACITY))."""
+        facts = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.swa_d1_fastidious_bloom_read(self.h, _ptr(facts), None, 0))
+        fsize = int(facts[0])
+        if not words or fsize == 0:
+            return [int(v) for v in facts], None
+        room = fsize if cap_words is None else int(cap_words)
+        out = np.zeros(max(room, 1), dtype=np.uint64)
+        self._check(self.lib.swa_d1_fastidious_bloom_read(self.h, _ptr(facts), _ptr(out), room))
+        return [int(v) for v in facts], out[:fsize]
 
     # ---- B3
     def qgram_build(self) -> None:

@@ -233,6 +233,7 @@ static void invalidate(swa_ctx * ctx) {   // a new database: what was known of t
   ctx->ix = {};
   ctx->res = {};
   ctx->dr = {};
+  for (uint64_t & t : ctx->fast_bloom) { t = 0; }          // (swa_d1_fastidious_bloom_read: the filter in d_bloomflex was another database's)
 }
 
 extern "C" int swa_db_upload(swa_ctx * ctx, const swa_db_view * h) {

@@ -242,6 +242,7 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
   // (the two words of a batch, cleared and read with one call each)
   static_assert(offsetof(swa_fast_counters, batch_variants) == offsetof(swa_fast_counters, batch_tasks) + sizeof(uint64_t), "batch_tasks, batch_variants: neighbours");
   uint64_t done = 0;
+  uint64_t tasks_run = 0;                                    // tasks of the batches that ran to the end (a redone batch is counted once, as it ran)
   uint64_t batch = task_cap / maxv;                          // cannot overflow
   double rate = -1.0;                                        // observed tasks per heavy amplicon
   while (done < n_heavy) {
@@ -267,6 +268,7 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
     ++ctx->fast_batches[0];
     if (got[0] > task_cap) { ++ctx->fast_batches[1]; continue; }   // optimistic batch did not fit: redo it smaller
     if (got[0] > ctx->fast_batches[3]) { ctx->fast_batches[3] = got[0]; }
+    tasks_run += got[0];
     if (got[0] > 0) {
       a.count = static_cast<uint32_t>(got[0]);
       const int pgrid = swa_grid_for(ctx, a.count, kWaves, 8);
@@ -276,6 +278,8 @@ static int fastidious_bloom_route(swa_ctx * ctx, uint32_t n_light, uint32_t n_he
     }
     done += want;
   }
+  // what swa_d1_fastidious_bloom_read reports: written once the route has run to its end
+  ctx->fast_bloom[0] = fsize; ctx->fast_bloom[1] = m; ctx->fast_bloom[2] = k; ctx->fast_bloom[3] = bloom_bits; ctx->fast_bloom[4] = tasks_run;
   return SWA_OK;
 }
 
@@ -383,6 +387,19 @@ extern "C" int swa_d1_fastidious_totals(swa_ctx * ctx, uint64_t out[4]) {
 extern "C" int swa_d1_fastidious_bloom_batches(swa_ctx * ctx, uint64_t out[4]) {
   if (ctx == nullptr || out == nullptr) { return SWA_E_ARG; }
   for (int i = 0; i < 4; ++i) { out[i] = ctx->fast_batches[i]; }
+  return SWA_OK;
+}
+
+// copies: no kernel runs, nothing of the pass changes (the pass ended with the stream idle, so the words are settled)
+extern "C" int swa_d1_fastidious_bloom_read(swa_ctx * ctx, uint64_t facts[8], uint64_t * words, uint64_t cap_words) {
+  if (ctx == nullptr || facts == nullptr) { return SWA_E_ARG; }
+  for (int i = 0; i < 8; ++i) { facts[i] = i < 5 ? ctx->fast_bloom[i] : 0; }
+  const uint64_t fsize = ctx->fast_bloom[0];
+  if (words == nullptr || fsize == 0) { return SWA_OK; }
+  if (cap_words < fsize) { return swa_fail_msg(ctx, SWA_E_CAPACITY, "swa_d1_fastidious_bloom_read: the filter has more words than the buffer"); }
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  SWA_HIP(ctx, hipMemcpyAsync(words, ctx->d_bloomflex.ptr, fsize * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  SWA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SWA_OK;
 }
 
@@ -520,6 +537,7 @@ static int fastidious_with_roles(swa_ctx * ctx, const uint8_t * host_role, const
   const bool pair_route = plan.pair_route;
   for (uint64_t & t : ctx->fast_totals) { t = 0; }
   for (uint64_t & t : ctx->fast_batches) { t = 0; }
+  for (uint64_t & t : ctx->fast_bloom) { t = 0; }
   const uint32_t min_len = pair_route ? kFastMinLen : 0xFFFFFFFFu;
   const uint32_t max_len = plan.max_len;                     // (0xFFFFFFFF without a division at the long end)
 

@@ -348,6 +348,8 @@ struct swa_ctx {
   uint64_t fast_pair_cap = 0;
   uint64_t fast_totals[4] = {};  // of the last pass: pairs found, light / heavy amplicons of the Bloom route's bands, attempts of the pair list
   uint64_t fast_batches[4] = {}; // of the last pass's Bloom route: k_d1_flex<., 1> launches, those that overflowed and were redone, the task cap, the most tasks of a batch that ran
+  uint64_t fast_bloom[5] = {};   // ... and its filter: words (fsize), m, k, the bits asked for, tasks of the batches that ran to the end; all 0 when the route
+                                 // did not run, and after an upload (d_bloomflex then holds another database's filter): swa_d1_fastidious_bloom_read
 
   // d >= 2 in bulk (dn_graph.hip)
   uint64_t dn_pair_cap = 0, dn_comparisons = 0, dn_aligned = 0, dn_launches = 0, dn_edges = 0, dn_work = 0;
