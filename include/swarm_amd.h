@@ -20,7 +20,7 @@
  *         src/qgram.h:31-35)                                         swa_qgram_diff
  *   B4    search_begin + search_do (src/scan.h:30-37, 259)           swa_search_begin / swa_search_do
  *   B5    nw() per H line of the uclust writers (src/algod1.cc:896-  swa_nw_batch
- *         925, src/algo.cc:620-655, src/nw.cc:237-255)
+ *         925, src/algo.cc:620-655, src/nw.cc:237-255)               (several GPUs: swa_multi_nw_batch)
  *
  * Amplicon numbering everywhere = the reference's db order after db_read():
  * abundance descending, then header ascending (src/db.cc:388-413).  Sequences are
@@ -713,7 +713,10 @@ int swa_dn_graph_totals(swa_ctx * ctx, uint64_t * out3);
    host flags (swa_multi_d1_fastidious) or by owner bytes made on rank 0's GPU and broadcast (swa_multi_d1_fastidious_resident)
    —, graft_cand combined with ncclAllReduce(min).  librccl.so is
    loaded when the first handle with ranks on distinct devices is created, not with the library.  A device may be listed more than once (several ranks on one GPU: the exchange then uses
-   device-to-device copies — RCCL admits one rank per GPU); results never depend on the device list. */
+   device-to-device copies — RCCL admits one rank per GPU); results never depend on the device list.
+   Every route of the command line is divided among the ranks: d = 0 and the d >= 2 graph and scan routes further below,
+   and the alignments of the uclust writers (seam B5: swa_multi_nw_batch, at the end of this section — no exchange at all,
+   every rank aligns a contiguous run of a batch's pairs). */
 typedef struct swa_multi swa_multi;
 int  swa_multi_create(const int * devices, int ndevices, swa_multi ** out);
 void swa_multi_destroy(swa_multi * m);
@@ -812,6 +815,39 @@ int  swa_multi_scan_step(swa_multi * m, uint32_t seed, uint32_t lowest_unswarmed
                          int no_cluster_breaking, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap, uint32_t * nhits);
 int  swa_multi_scan_fetch(swa_multi * m, uint32_t * hit_seedidx, uint32_t * hit_ids, uint32_t * hit_diffs, uint32_t cap);
 int  swa_multi_scan_totals(swa_multi * m, uint64_t * out3);
+
+/* ---- B5 on several GPUs: the uclust alignments divided among the ranks (src/algod1.cc:880-925, src/algo.cc:608-659) ----
+   Whether (member, seed) aligns with some CIGAR depends on the pair alone and the database is replicated
+   (swa_multi_db_upload), so rank r aligns the contiguous pairs [bounds[r], bounds[r + 1]) of the batch with swa_nw_batch on
+   its own context and stream, one host thread a rank: the one-thread host parts of a batch overlap as well as the kernels,
+   also between ranks that share a device.  No collective and no kernel of its own; ranks on one device and ranks on
+   distinct devices run the same code.
+   swa_multi_nw_batch takes the arguments of swa_nw_batch and gives its outputs, bit for bit the same for any device list:
+   diffs, columns, cigar_end (cumulative over the whole batch), the CIGAR text back to back, *cigar_total = the need;
+   SWA_E_CAPACITY when the text does not fit or `cigar` is NULL with text to write — all other results are complete then, and
+   a second call with room gives the same bytes.  Every rank writes diffs, columns and cigar_end at its slice's offset and
+   its text where no other rank writes — the caller's buffer at the weight of the lower slices where the slice's bound fits
+   there, else a buffer of its own —; the texts are then moved together in rank order and every rank's ends raised by the
+   totals of the ranks below it.  A rank with an empty slice launches nothing, its counters are zero.  A failing rank ends
+   the call with its code and "rank r: ..." in swa_multi_last_error, after every thread has been joined (an id >= n: SWA_E_ARG
+   from the rank whose slice holds it; such a pair weighs nothing where the batch is divided).  SWA_E_ARG for a handle without a database when there are pairs.
+   swa_multi_nw_batch_totals / _tiers / _text_full: the counters of swa_nw_batch_totals / _tiers / _text_full summed over the
+   ranks.  The tier sums are those of a single context as long as no pair found a CIGAR buffer full (text_full = 0 on both
+   sides: the device's text buffer is sized per slice).  A rank's own counters stay readable through swa_multi_ctx(m, r).
+   swa_multi_nw_bounds_for: the division; a pure function, no device.  With w_k = seqlen[d_ids[k]] + seqlen[q_ids[k]] (also
+   the bound of the pair's CIGAR), P(k) the sum of w_j over j < k and W = P(npairs): bounds[0] = 0, bounds[world] = npairs,
+   and for 0 < r < world bounds[r] = the smallest k with P(k) >= floor(r W / world) (the product split, so that it stays
+   inside 64 bits).  bounds holds world + 1 entries.  SWA_E_ARG for world = 0, world > 64, a null array with npairs > 0 or
+   an id >= n.  The weight is a first rule: how a pair's cost follows its lengths across the tiers — cells grow with the
+   product of the lengths and with the band, the host parts with the pair count and the text — has not been measured. */
+int  swa_multi_nw_batch(swa_multi * m, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
+                        const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
+                        uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total);
+int  swa_multi_nw_batch_totals(swa_multi * m, uint64_t * out4);
+int  swa_multi_nw_batch_tiers(swa_multi * m, uint64_t * out8);
+int  swa_multi_nw_batch_text_full(swa_multi * m, uint64_t * out1);
+int  swa_multi_nw_bounds_for(uint64_t npairs, const uint32_t * d_ids, const uint32_t * q_ids, const uint32_t * seqlen, uint32_t n,
+                             uint32_t world, uint64_t * bounds);
 /* Debug entry: the merge rank 0 runs on the gathered shares (k_merge_sorted_lists, launched as swa_multi_dn_graph launches
    it), from host arrays to host arrays on the context's stream.  List r = [at[r], at[r + 1]) of keys / vals, every list
    sorted by key, at[0] = 0, at[] not descending, 1 <= world <= 64 (SWA_E_ARG otherwise); out_keys / out_vals take

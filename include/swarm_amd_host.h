@@ -128,6 +128,12 @@ int swa_d1_write_uclust(const swa_d1_result * res, const swa_hostdb * db, const 
 int swa_d1_write_uclust_gpu(swa_ctx * ctx, const swa_d1_result * res, const swa_hostdb * db, const char * path,
                             int usearch_abundance, int64_t append_abundance, uint64_t mismatch, uint64_t gapopen,
                             uint64_t gapextend);
+/* ... and with every chunk's alignments divided among the ranks of `multi` (swa_multi_nw_batch; every rank holds the same
+   database: swa_multi_db_upload).  The same file for any device list; the [nw] lines under SWARM_AMD_TIMING show the
+   sums over the ranks. */
+int swa_d1_write_uclust_multi(swa_multi * multi, const swa_d1_result * res, const swa_hostdb * db, const char * path,
+                              int usearch_abundance, int64_t append_abundance, uint64_t mismatch, uint64_t gapopen,
+                              uint64_t gapextend);
 
 /* ---- d >= 2 host side: the greedy loop of algo_run over the GPU's fused scan step ------- */
 typedef struct swa_dn_result swa_dn_result;
@@ -174,6 +180,9 @@ int swa_dn_write_uclust(const swa_dn_result * res, const swa_hostdb * db, const 
 /* the same file with the alignments on the GPU (as swa_d1_write_uclust_gpu) */
 int swa_dn_write_uclust_gpu(swa_ctx * ctx, const swa_dn_result * res, const swa_hostdb * db, const char * path,
                             int usearch_abundance, int64_t append_abundance);
+/* ... divided among the ranks of `multi` (as swa_d1_write_uclust_multi) */
+int swa_dn_write_uclust_multi(swa_multi * multi, const swa_dn_result * res, const swa_hostdb * db, const char * path,
+                              int usearch_abundance, int64_t append_abundance);
 
 /* ---- the uclust aligner on the host (src/nw.cc:237-255): what both -u writers print, and what swa_nw_batch must equal ----
    dseq / qseq 2-bit packed.  Returns the differences (columns - matches); *columns = alignment length; the CIGAR into

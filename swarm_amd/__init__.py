@@ -6,4 +6,4 @@
 
 The product never imports oracle/ and has no CPU fallback.
 """
-from .capi import Context, MultiContext, D0Clusters, D1Clusters, DnClusters, derep, HostDb, SwaError, d1_write_uclust, nw_align_host, reduced_penalties, build_library, load_library, scan_owner_for, scan_share_for  # noqa: F401
+from .capi import Context, MultiContext, D0Clusters, D1Clusters, DnClusters, derep, HostDb, SwaError, d1_write_uclust, nw_align_host, reduced_penalties, build_library, load_library, scan_owner_for, scan_share_for, nw_bounds_for  # noqa: F401

@@ -1274,30 +1274,8 @@ class Context:
     def nw_batch(self, d_ids, q_ids, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
         """Seam B5 (swa_nw_batch): global alignments of amplicons d_ids[k] (member) against q_ids[k] (seed) of the
         resident database -> (diffs, columns, list of CIGAR strings)."""
-        lib = self.lib
-        _declare_dn(lib)
-        d_ids = np.ascontiguousarray(d_ids, dtype=np.uint32)
-        q_ids = np.ascontiguousarray(q_ids, dtype=np.uint32)
-        m = len(d_ids)
-        assert len(q_ids) == m
-        diffs = np.zeros(m, dtype=np.uint32)
-        cols = np.zeros(m, dtype=np.uint32)
-        ends = np.zeros(m, dtype=np.uint64)
-        total = C.c_uint64(0)
-        cap = 16 * m + 64
-        while True:
-            buf = C.create_string_buffer(max(cap, 1))
-            rc = lib.swa_nw_batch(self.h, mismatch, gapopen, gapextend, m, _ptr(d_ids), _ptr(q_ids), _ptr(diffs),
-                                  _ptr(cols), _ptr(ends), buf, cap, C.byref(total))
-            if rc == SWA_E_CAPACITY and total.value > cap:
-                cap = int(total.value)
-                continue
-            self._check(rc)
-            break
-        raw = buf.raw[:int(total.value)]
-        starts = np.concatenate(([0], ends[:-1])).astype(np.int64) if m else []
-        cigars = [raw[int(a):int(b)].decode() for a, b in zip(starts, ends)]
-        return diffs, cols, cigars
+        _declare_dn(self.lib)
+        return _nw_batch_call(self.lib.swa_nw_batch, self, d_ids, q_ids, mismatch, gapopen, gapextend)
 
     def nw_batch_totals(self) -> list:
         """pairs of the last nw_batch: [16-lane, 32-lane, 64-lane LDS tier, left by the LDS tiers (wide tiers + host)]"""
@@ -1320,6 +1298,32 @@ class Context:
         out = np.zeros(1, dtype=np.uint64)
         self._check(self.lib.swa_nw_batch_text_full(self.h, _p64(out)))
         return int(out[0])
+
+
+def _nw_batch_call(fn, owner, d_ids, q_ids, mismatch, gapopen, gapextend):
+    """swa_nw_batch or swa_multi_nw_batch on owner.h, with their capacity protocol -> (diffs, columns, CIGAR strings)"""
+    d_ids = np.ascontiguousarray(d_ids, dtype=np.uint32)
+    q_ids = np.ascontiguousarray(q_ids, dtype=np.uint32)
+    m = len(d_ids)
+    assert len(q_ids) == m
+    diffs = np.zeros(m, dtype=np.uint32)
+    cols = np.zeros(m, dtype=np.uint32)
+    ends = np.zeros(m, dtype=np.uint64)
+    total = C.c_uint64(0)
+    cap = 16 * m + 64
+    while True:
+        buf = C.create_string_buffer(max(cap, 1))
+        rc = fn(owner.h, mismatch, gapopen, gapextend, m, _ptr(d_ids), _ptr(q_ids), _ptr(diffs), _ptr(cols), _ptr(ends), buf, cap,
+                C.byref(total))
+        if rc == SWA_E_CAPACITY and total.value > cap:
+            cap = int(total.value)
+            continue
+        owner._check(rc)
+        break
+    raw = buf.raw[:int(total.value)]
+    starts = np.concatenate(([0], ends[:-1])).astype(np.int64) if m else []
+    cigars = [raw[int(a):int(b)].decode() for a, b in zip(starts, ends)]
+    return diffs, cols, cigars
 
 
 # ---- d >= 2: host greedy loop over the GPU's fused scan step ---------------------------------
@@ -1457,8 +1461,13 @@ class DnClusters:
     def write_seeds(self, path, usearch=False) -> None:
         assert self.lib.swa_dn_write_seeds(self.h, self.hdb.h, str(path).encode(), int(usearch)) == SWA_OK
 
-    def write_uclust(self, path, usearch=False, append_abundance=0, ctx: "Context | None" = None) -> None:
-        """-u; with ctx= the alignments run on that context's GPU (seam B5, swa_dn_write_uclust_gpu)."""
+    def write_uclust(self, path, usearch=False, append_abundance=0, ctx: "Context | MultiContext | None" = None) -> None:
+        """-u; with ctx= the alignments run on that context's GPU (seam B5, swa_dn_write_uclust_gpu), or divided among the
+        ranks of a MultiContext (swa_dn_write_uclust_multi)."""
+        if isinstance(ctx, MultiContext):
+            ctx._check(self.lib.swa_dn_write_uclust_multi(ctx.h, self.h, self.hdb.h, str(path).encode(), int(usearch),
+                                                          append_abundance))
+            return
         if ctx is not None:
             ctx._check(self.lib.swa_dn_write_uclust_gpu(ctx.h, self.h, self.hdb.h, str(path).encode(), int(usearch),
                                                         append_abundance))
@@ -1594,11 +1603,16 @@ class D0Clusters:
 
 
 def d1_write_uclust(clusters: "D1Clusters", path, usearch=False, append_abundance=0, penalties=None,
-                    ctx: "Context | None" = None) -> None:
-    """-u for d = 1; with ctx= the alignments run on that context's GPU (seam B5, swa_d1_write_uclust_gpu)."""
+                    ctx: "Context | MultiContext | None" = None) -> None:
+    """-u for d = 1; with ctx= the alignments run on that context's GPU (seam B5, swa_d1_write_uclust_gpu), or divided
+    among the ranks of a MultiContext (swa_d1_write_uclust_multi)."""
     lib = load_library()
     _declare_dn(lib)
     mm, go, ge = penalties or reduced_penalties()
+    if isinstance(ctx, MultiContext):
+        ctx._check(lib.swa_d1_write_uclust_multi(ctx.h, clusters.h, clusters.hdb.h, str(path).encode(), int(usearch),
+                                                 append_abundance, mm, go, ge))
+        return
     if ctx is not None:
         ctx._check(lib.swa_d1_write_uclust_gpu(ctx.h, clusters.h, clusters.hdb.h, str(path).encode(), int(usearch),
                                                append_abundance, mm, go, ge))
@@ -1674,6 +1688,41 @@ def scan_share_for(n: int, lowest_unswarmed: int, rank: int, world: int):
     return int(out[0]), int(out[1])
 
 
+_MULTI_NW_EXPORTS = ["swa_multi_nw_batch", "swa_multi_nw_batch_totals", "swa_multi_nw_batch_tiers", "swa_multi_nw_batch_text_full",
+                     "swa_multi_nw_bounds_for", "swa_d1_write_uclust_multi", "swa_dn_write_uclust_multi"]
+EXPORTS.extend(_MULTI_NW_EXPORTS)
+
+
+def _declare_multi_nw(lib) -> None:
+    lib.swa_multi_nw_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    lib.swa_multi_nw_batch_totals.argtypes = [C.c_void_p, u64p]
+    lib.swa_multi_nw_batch_tiers.argtypes = [C.c_void_p, u64p]
+    lib.swa_multi_nw_batch_text_full.argtypes = [C.c_void_p, u64p]
+    lib.swa_multi_nw_bounds_for.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.swa_dn_write_uclust_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64]
+    lib.swa_d1_write_uclust_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint64,
+                                              C.c_uint64, C.c_uint64]
+
+
+def nw_bounds_for(d_ids, q_ids, seqlen, world: int) -> np.ndarray:
+    """swa_multi_nw_bounds_for: how MultiContext.nw_batch divides a batch — rank r of `world` aligns the pairs
+    [bounds[r], bounds[r + 1]), cut where the running sum of seqlen[d] + seqlen[q] passes r / world of the whole; a pure
+    function, needs no device.  world + 1 entries (uint64)."""
+    lib = load_library()
+    _declare_multi_nw(lib)
+    d_ids = np.ascontiguousarray(d_ids, dtype=np.uint32)
+    q_ids = np.ascontiguousarray(q_ids, dtype=np.uint32)
+    seqlen = np.ascontiguousarray(seqlen, dtype=np.uint32)
+    assert len(d_ids) == len(q_ids)
+    world = int(world)
+    bounds = np.zeros(max(world, 0) + 1, dtype=np.uint64)
+    rc = lib.swa_multi_nw_bounds_for(len(d_ids), _ptr(d_ids), _ptr(q_ids), _ptr(seqlen), len(seqlen), world & 0xFFFFFFFF, _ptr(bounds))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_multi_nw_bounds_for: bad argument")
+    return bounds
+
+
 _MULTI_DEREP_EXPORTS = ["swa_multi_derep_resident", "swa_multi_derep", "swa_multi_derep_owner_for", "swa_multi_derep_totals"]
 EXPORTS.extend(_MULTI_DEREP_EXPORTS)
 
@@ -1722,6 +1771,7 @@ class MultiContext:
         lib.swa_multi_d1_last_build.argtypes = [C.c_void_p]
         _declare_multi_derep(lib)
         _declare_multi_scan(lib)
+        _declare_multi_nw(lib)
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
         rc = lib.swa_multi_create(arr, len(devices), C.byref(h))
@@ -1841,6 +1891,30 @@ class MultiContext:
         out = np.zeros(3, dtype=np.uint64)
         self._check(self.lib.swa_multi_scan_totals(self.h, _p64(out)))
         return {"qgram_comparisons": int(out[0]), "aligned_pairs": int(out[1]), "launch_sequences": int(out[2])}
+
+    # ---- seam B5: the -u alignments divided among the ranks (nw_bounds_for)
+    def nw_batch(self, d_ids, q_ids, mismatch: int = 18, gapopen: int = 24, gapextend: int = 13):
+        """swa_multi_nw_batch, as Context.nw_batch and with its results for any device list: (diffs, columns, list of CIGAR
+        strings)."""
+        return _nw_batch_call(self.lib.swa_multi_nw_batch, self, d_ids, q_ids, mismatch, gapopen, gapextend)
+
+    def nw_batch_totals(self) -> list:
+        """Context.nw_batch_totals of the last nw_batch, summed over the ranks"""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.swa_multi_nw_batch_totals(self.h, _p64(out)))
+        return [int(v) for v in out]
+
+    def nw_batch_tiers(self) -> list:
+        """Context.nw_batch_tiers of the last nw_batch, summed over the ranks (a rank's own: ctx(r).nw_batch_tiers())"""
+        out = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.swa_multi_nw_batch_tiers(self.h, _p64(out)))
+        return [int(v) for v in out]
+
+    def nw_batch_text_full(self) -> int:
+        """Context.nw_batch_text_full of the last nw_batch, summed over the ranks"""
+        out = np.zeros(1, dtype=np.uint64)
+        self._check(self.lib.swa_multi_nw_batch_text_full(self.h, _p64(out)))
+        return int(out[0])
 
     def dn_cluster(self, hdb: "HostDb", differences: int, no_cluster_breaking: bool = False, penalties=None) -> "DnClusters":
         """swa_dn_cluster_multi on a database uploaded with upload_hostdb: a DnClusters whose route() names what served —

@@ -984,11 +984,17 @@ extern "C" int swa_d1_write_uclust(const swa_d1_result * r, const swa_hostdb * d
 // -u with the alignments on the GPU (seam B5): the same lines as swa_d1_write_uclust, the pairs aligned by swa_nw_batch
 extern "C" int swa_d1_write_uclust_gpu(swa_ctx * ctx, const swa_d1_result * r, const swa_hostdb * db, const char * path, int usearch,
                                        int64_t append_abundance, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend) {
+  return swa_d1_write_uclust_with(swa_uclust_on_ctx(ctx), r, db, path, usearch, append_abundance, mismatch, gapopen, gapextend);
+}
+
+// ... by whoever the aligner names: that context, or the ranks of a swa_multi (uclust_multi.cpp)
+int swa_d1_write_uclust_with(const swa_uclust_aligner & aligner, const swa_d1_result * r, const swa_hostdb * db, const char * path, int usearch,
+                             int64_t append_abundance, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend) {
   if (!need_details(r)) { return details_failed(r); }
   BufOut o(path);
   if (!o.ok()) { return SWA_E_ARG; }
   const std::vector<uint32_t> number = output_numbers(r);
-  return swa_uclust_gpu(ctx, db, o, r->swarms.size(), r->n >= kParallelUclustFrom, mismatch, gapopen, gapextend,
+  return swa_uclust_gpu(aligner, db, o, r->swarms.size(), r->n >= kParallelUclustFrom, mismatch, gapopen, gapextend,
     [&](size_t k, auto && push) {
       const auto & s = r->swarms[k];
       if (s.attached != 0) { return; }

@@ -637,10 +637,16 @@ extern "C" int swa_dn_write_uclust(const swa_dn_result * r, const swa_hostdb * d
 // -u with the alignments on the GPU (seam B5): the same lines as swa_dn_write_uclust, the pairs aligned by swa_nw_batch
 extern "C" int swa_dn_write_uclust_gpu(swa_ctx * ctx, const swa_dn_result * r, const swa_hostdb * db, const char * path, int usearch,
                                        int64_t append_abundance) {
+  return swa_dn_write_uclust_with(swa_uclust_on_ctx(ctx), r, db, path, usearch, append_abundance);
+}
+
+// ... by whoever the aligner names: that context, or the ranks of a swa_multi (uclust_multi.cpp)
+int swa_dn_write_uclust_with(const swa_uclust_aligner & aligner, const swa_dn_result * r, const swa_hostdb * db, const char * path, int usearch,
+                             int64_t append_abundance) {
   if (!need_links(r)) { return SWA_E_DEVICE; }               // (before swa_nw_batch starts on the context)
   BufOut o(path);
   if (!o.ok()) { return SWA_E_ARG; }
-  return swa_uclust_gpu(ctx, db, o, r->swarms.size(), r->order.size() >= 200, r->pen_mismatch, r->pen_gapopen, r->pen_gapextend,
+  return swa_uclust_gpu(aligner, db, o, r->swarms.size(), r->order.size() >= 200, r->pen_mismatch, r->pen_gapopen, r->pen_gapextend,
     [&](size_t k, auto && push) {
       const auto & s = r->swarms[k];
       const uint32_t seed = r->order[s.begin];

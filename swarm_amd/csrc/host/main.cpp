@@ -250,6 +250,27 @@ void check_gpu_writer(int rc, swa_ctx * ctx, const char * what, const swa_d1_res
   check_writer(rc, what, res);
 }
 
+// ... on several GPUs (swa_*_write_uclust_multi): the failing rank's words
+void check_multi_writer(int rc, swa_multi * multi, const char * what, const swa_d1_result * res = nullptr) {
+  if (rc != SWA_OK && rc != SWA_E_ARG && swa_multi_last_error(multi)[0] != '\0' && (res == nullptr || swa_d1_result_error(res)[0] == '\0')) {
+    die(swa_multi_last_error(multi));
+  }
+  check_writer(rc, what, res);
+}
+
+// Several GPUs: the -u alignments are divided among the ranks (swa_multi_nw_batch) unless SWARM_AMD_MULTI_NW=root leaves them
+// to rank 0 alone — the comparison switch: the files are the same.  One line under SWARM_AMD_MULTI_REPORT says which.
+bool uclust_divided(swa_multi * multi) {
+  if (multi == nullptr) { return false; }
+  const char * route = std::getenv("SWARM_AMD_MULTI_NW");
+  const bool divided = swa_multi_size(multi) > 1 && !(route != nullptr && std::strcmp(route, "root") == 0);
+  if (std::getenv("SWARM_AMD_MULTI_REPORT") != nullptr) {
+    if (divided) { std::fprintf(stderr, "multi: -u alignments divided among %d ranks\n", swa_multi_size(multi)); }
+    else { std::fprintf(stderr, "multi: -u alignments on rank 0 alone\n"); }
+  }
+  return divided;
+}
+
 }  // namespace
 
 // The command line proper.  The executable (host/launcher.cpp) is a few lines that set the OpenMP wait policy and load this
@@ -610,7 +631,11 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     phase(o, "Writing swarms:   ");
     if (!o.seeds.empty()) { check_writer(swa_d1_write_seeds(res, db, o.seeds.c_str(), o.usearch), "seeds", res); phase(o, "Writing seeds:    "); }
     if (!o.structure.empty()) { check_writer(swa_d1_write_structure(res, db, o.structure.c_str(), o.usearch), "internal structure", res); phase(o, "Writing structure:"); }
-    if (!o.uclust.empty()) {
+    if (!o.uclust.empty() && uclust_divided(multi)) {
+      check_multi_writer(swa_d1_write_uclust_multi(multi, res, db, o.uclust.c_str(), o.usearch, o.append_abundance, (uint64_t)o.pen_mismatch,
+                                                   (uint64_t)o.pen_gapopen, (uint64_t)o.pen_gapextend), multi, "uclust", res);
+      phase(o, "Writing UCLUST:   ");
+    } else if (!o.uclust.empty()) {
       check_gpu_writer(swa_d1_write_uclust_gpu(ctx, res, db, o.uclust.c_str(), o.usearch, o.append_abundance, (uint64_t)o.pen_mismatch,
                                                (uint64_t)o.pen_gapopen, (uint64_t)o.pen_gapextend), ctx, "uclust", res);
       phase(o, "Writing UCLUST:   ");
@@ -646,7 +671,11 @@ extern "C" int swa_cli_main(int argc, char ** argv) {
     if (res != nullptr) {
       check_writer(swa_dn_write_swarms(res, db, o.output.c_str(), o.mothur, o.usearch, o.append_abundance), "output");
       if (!o.structure.empty()) { check_writer(swa_dn_write_structure(res, db, o.structure.c_str(), o.usearch), "internal structure"); }
-      if (!o.uclust.empty()) { check_gpu_writer(swa_dn_write_uclust_gpu(ctx, res, db, o.uclust.c_str(), o.usearch, o.append_abundance), ctx, "uclust"); }
+      if (!o.uclust.empty() && uclust_divided(multi)) {
+        check_multi_writer(swa_dn_write_uclust_multi(multi, res, db, o.uclust.c_str(), o.usearch, o.append_abundance), multi, "uclust");
+      } else if (!o.uclust.empty()) {
+        check_gpu_writer(swa_dn_write_uclust_gpu(ctx, res, db, o.uclust.c_str(), o.usearch, o.append_abundance), ctx, "uclust");
+      }
       if (!o.stats.empty()) { check_writer(swa_dn_write_stats(res, db, o.stats.c_str(), o.usearch), "statistics"); }
       if (!o.seeds.empty()) { check_writer(swa_dn_write_seeds(res, db, o.seeds.c_str(), o.usearch), "seeds"); phase(o, "Writing seeds:    "); }
       swa_dn_result_summary(res, sum);

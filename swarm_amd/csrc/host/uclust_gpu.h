@@ -1,6 +1,7 @@
 // uclust_gpu.h — the -u writers on the GPU (seam B5): the H lines' pairs collected in printing order, aligned by
 // swa_nw_batch in chunks of bounded size, and formatted by the multi-threaded formatter while the GPU aligns the next
-// chunk.  The d = 1 and d >= 2 writers differ only in how they walk their swarms.
+// chunk.  The d = 1 and d >= 2 writers differ only in how they walk their swarms; who aligns a chunk — one context, or
+// the ranks of a swa_multi among which swa_multi_nw_batch divides it (uclust_multi.cpp) — is the aligner they are given.
 #pragma once
 
 #include <cstdio>
@@ -23,6 +24,39 @@ struct swa_uclust_chunk {
   int rc = SWA_OK;
 };
 
+// Who aligns a chunk: swa_nw_batch and its three counter calls, or calls with their arguments and results, on `handle`.
+struct swa_uclust_aligner {
+  void * handle = nullptr;            // NULL only for a result without H lines
+  int (*batch)(void * handle, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs, const uint32_t * d_ids,
+               const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns, uint64_t * cigar_end, char * cigar, uint64_t cigar_cap,
+               uint64_t * cigar_total) = nullptr;
+  int (*totals)(void * handle, uint64_t * out4) = nullptr;
+  int (*tiers)(void * handle, uint64_t * out8) = nullptr;
+  int (*text_full)(void * handle, uint64_t * out1) = nullptr;
+};
+
+// one context: the _gpu writers
+inline swa_uclust_aligner swa_uclust_on_ctx(swa_ctx * ctx) {
+  swa_uclust_aligner a;
+  a.handle = ctx;
+  a.batch = [](void * h, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs, const uint32_t * d_ids, const uint32_t * q_ids,
+               uint32_t * diffs, uint32_t * columns, uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total) {
+    return swa_nw_batch(static_cast<swa_ctx *>(h), mismatch, gapopen, gapextend, npairs, d_ids, q_ids, diffs, columns, cigar_end, cigar, cigar_cap,
+                        cigar_total);
+  };
+  a.totals = [](void * h, uint64_t * out4) { return swa_nw_batch_totals(static_cast<swa_ctx *>(h), out4); };
+  a.tiers = [](void * h, uint64_t * out8) { return swa_nw_batch_tiers(static_cast<swa_ctx *>(h), out8); };
+  a.text_full = [](void * h, uint64_t * out1) { return swa_nw_batch_text_full(static_cast<swa_ctx *>(h), out1); };
+  return a;
+}
+
+// The writers proper (cluster_d1.cpp, cluster_dn.cpp), behind swa_d1_write_uclust_gpu / _multi and swa_dn_write_uclust_gpu /
+// _multi: the arguments of the _gpu writers, the aligner in the context's place.
+int swa_d1_write_uclust_with(const swa_uclust_aligner & aligner, const swa_d1_result * res, const swa_hostdb * db, const char * path, int usearch,
+                             int64_t append_abundance, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend);
+int swa_dn_write_uclust_with(const swa_uclust_aligner & aligner, const swa_dn_result * res, const swa_hostdb * db, const char * path, int usearch,
+                             int64_t append_abundance);
+
 // pairs per chunk: SWA_NW_CHUNK (a test hook: many chunks on small inputs), else 2^20
 inline uint64_t swa_uclust_chunk_pairs() {
   const char * e = std::getenv("SWA_NW_CHUNK");
@@ -33,7 +67,7 @@ inline uint64_t swa_uclust_chunk_pairs() {
 // collect(k, push): push(member, seed) for every H line of swarm k, in printing order.  weight(k): what swarm k costs to
 // format.  format(sink, k, chunk, p): prints swarm k, whose first H line is pair p of the chunk.
 template <class Collect, class Weight, class Format>
-int swa_uclust_gpu(swa_ctx * ctx, const swa_hostdb * db, BufOut & o, size_t nswarms, bool parallel, uint64_t mismatch,
+int swa_uclust_gpu(const swa_uclust_aligner & aligner, const swa_hostdb * db, BufOut & o, size_t nswarms, bool parallel, uint64_t mismatch,
                    uint64_t gapopen, uint64_t gapextend, Collect && collect, Weight && weight, Format && format) {
   const uint64_t cap = swa_uclust_chunk_pairs();
   auto fill = [&](swa_uclust_chunk & c, size_t from) {
@@ -61,14 +95,14 @@ int swa_uclust_gpu(swa_ctx * ctx, const swa_hostdb * db, BufOut & o, size_t nswa
     uint64_t total = 0;
     // (a result without H lines needs no context, and the command line has none for an empty input)
     if (n == 0) { c.rc = SWA_OK; return; }
-    if (ctx == nullptr) { c.rc = SWA_E_ARG; return; }
-    c.rc = swa_nw_batch(ctx, mismatch, gapopen, gapextend, n, c.d.data(), c.q.data(), c.diffs.data(), c.columns.data(),
-                        c.cigar_end.data(), c.cigar.get(), c.cigar_cap, &total);
+    if (aligner.handle == nullptr) { c.rc = SWA_E_ARG; return; }
+    c.rc = aligner.batch(aligner.handle, mismatch, gapopen, gapextend, n, c.d.data(), c.q.data(), c.diffs.data(), c.columns.data(),
+                         c.cigar_end.data(), c.cigar.get(), c.cigar_cap, &total);
     uint64_t t[4] = {};
-    if (c.rc == SWA_OK && swa_nw_batch_totals(ctx, t) == SWA_OK) { for (int i = 0; i < 4; ++i) { tiers[i] += t[i]; } }
+    if (c.rc == SWA_OK && aligner.totals(aligner.handle, t) == SWA_OK) { for (int i = 0; i < 4; ++i) { tiers[i] += t[i]; } }
     uint64_t t8[8] = {}, full = 0;
-    if (c.rc == SWA_OK && swa_nw_batch_tiers(ctx, t8) == SWA_OK) { for (int i = 0; i < 8; ++i) { all[i] += t8[i]; } }
-    if (c.rc == SWA_OK && swa_nw_batch_text_full(ctx, &full) == SWA_OK) { text_full += full; }
+    if (c.rc == SWA_OK && aligner.tiers(aligner.handle, t8) == SWA_OK) { for (int i = 0; i < 8; ++i) { all[i] += t8[i]; } }
+    if (c.rc == SWA_OK && aligner.text_full(aligner.handle, &full) == SWA_OK) { text_full += full; }
   };
   swa_uclust_chunk cur, next;
   fill(cur, 0);

@@ -18,7 +18,8 @@
 // d = 0 (derep_on_root below): the reads of a rank's slice travel to the rank that owns their hash, the owners dereplicate,
 // first_identical[] is assembled on rank 0.  d >= 2: the bulk graph divided by ownership of window groups (further below),
 // and the fused scan divided by ownership of the pool (swa_multi_scan_*, at the end: no exchange at all, every rank's hits
-// come to the host through its own pinned mirror and are merged there).
+// come to the host through its own pinned mirror and are merged there).  The -u alignments (seam B5): every batch cut into a
+// contiguous run of pairs a rank, aligned by swa_nw_batch on a host thread a rank (swa_multi_nw_batch, near the end).
 //
 // The same code runs with several contexts on ONE device (SWARM_AMD_DEVICES=0,0: what a one-GPU box can
 // test); RCCL refuses two ranks on one GPU, so that configuration moves the same bytes with device-to-
@@ -29,7 +30,10 @@
 #include "rccl_late.h"
 
 #include <algorithm>
+#include <cstring>
 #include <functional>
+#include <memory>
+#include <new>
 #include <set>
 #include <thread>
 #include <vector>
@@ -909,6 +913,129 @@ extern "C" int swa_multi_scan_totals(swa_multi * m, uint64_t * out3) {
     if (rc != SWA_OK) { return fail(m, rc, "rank " + std::to_string(r) + ": " + swa_last_error(m->ctx[r])); }
     out3[0] += t[0]; out3[1] += t[1];
   }
+  return SWA_OK;
+}
+
+// ---- B5 on several GPUs: the -u alignments divided among the ranks -------------------------------------------------------
+// Whether (member, seed) aligns with some CIGAR depends on the pair alone, and every rank holds the whole database: rank r
+// aligns the contiguous pairs [bounds[r], bounds[r + 1]) with swa_nw_batch on its own context, one host thread a rank, so the
+// one-thread host parts of a batch (planning a slice, assembling it) overlap as well as the kernels — also between ranks that
+// share a device.  No collective, no kernel of its own: the tier kernels of nw_trace.hip on every rank's stream.
+namespace {
+
+// floor(r * W / world) without the 64-bit product: r * (W / world) <= W, and r, W % world < 64
+uint64_t nw_share_target(uint64_t W, uint32_t r, uint32_t world) { return (W / world) * r + (W % world) * r / world; }
+
+// bounds[0 .. world] of swa_multi_nw_bounds_for and at[r] = P(bounds[r]), the weight below every boundary.  strict: an id
+// >= n is refused; else such a pair weighs nothing (the rank that gets it refuses it, and so names itself).
+int nw_bounds(uint64_t npairs, const uint32_t * d_ids, const uint32_t * q_ids, const uint32_t * seqlen, uint32_t n, uint32_t world,
+              bool strict, uint64_t * bounds, uint64_t * at) {
+  auto weight = [&](uint64_t k) -> uint64_t {
+    return d_ids[k] < n && q_ids[k] < n ? (uint64_t)seqlen[d_ids[k]] + seqlen[q_ids[k]] : 0;
+  };
+  uint64_t W = 0;
+  for (uint64_t k = 0; k < npairs; ++k) {
+    if (strict && (d_ids[k] >= n || q_ids[k] >= n)) { return SWA_E_ARG; }
+    W += weight(k);
+  }
+  bounds[0] = 0;
+  if (at != nullptr) { at[0] = 0; }
+  uint32_t r = 1;
+  uint64_t P = 0;
+  for (uint64_t k = 0; k <= npairs && r < world; ++k) {      // P = P(k)
+    while (r < world && P >= nw_share_target(W, r, world)) { bounds[r] = k; if (at != nullptr) { at[r] = P; } ++r; }
+    if (k < npairs) { P += weight(k); }
+  }
+  bounds[world] = npairs;
+  if (at != nullptr) { at[world] = W; }
+  return SWA_OK;
+}
+
+}  // namespace
+
+extern "C" int swa_multi_nw_bounds_for(uint64_t npairs, const uint32_t * d_ids, const uint32_t * q_ids, const uint32_t * seqlen, uint32_t n,
+                                       uint32_t world, uint64_t * bounds) {
+  if (world < 1 || world > 64 || bounds == nullptr) { return SWA_E_ARG; }
+  if (npairs > 0 && (d_ids == nullptr || q_ids == nullptr || seqlen == nullptr)) { return SWA_E_ARG; }
+  return nw_bounds(npairs, d_ids, q_ids, seqlen, n, world, true, bounds, nullptr);
+}
+
+extern "C" int swa_multi_nw_batch(swa_multi * m, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
+                                  const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
+                                  uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total) {
+  if (m == nullptr) { return SWA_E_ARG; }
+  const int world = (int)m->ctx.size();
+  if (npairs > 0 && (d_ids == nullptr || q_ids == nullptr || diffs == nullptr || columns == nullptr || cigar_end == nullptr)) {
+    return fail(m, SWA_E_ARG, "swa_multi_nw_batch: null result array");
+  }
+  swa_ctx * c0 = m->ctx[0];
+  if (npairs > 0 && c0->db.seqs == nullptr) { return fail(m, SWA_E_ARG, "swa_multi_nw_batch: no database resident"); }
+  int rc = swa_nw_host_seqlen(c0);
+  if (rc != SWA_OK) { return fail(m, rc, std::string("rank 0: ") + swa_last_error(c0)); }
+  std::vector<uint64_t> bounds((size_t)world + 1, 0), at((size_t)world + 1, 0), total((size_t)world, 0);
+  (void)nw_bounds(npairs, d_ids, q_ids, c0->up.nw_seqlen.data(), c0->db.n, (uint32_t)world, false, bounds.data(), at.data());
+  // A rank's text goes where no other rank writes: into the caller's buffer at the weight of the lower slices — a pair's
+  // weight bounds its CIGAR — where the slice's whole bound fits there, else into a buffer of the rank's own.
+  std::vector<std::unique_ptr<char[]>> own((size_t)world);
+  rc = on_all(m, [&](int r) {
+    swa_ctx * c = m->ctx[(size_t)r];
+    const uint64_t lo = bounds[(size_t)r], count = bounds[(size_t)r + 1] - lo;
+    if (count == 0) {                                          // nothing launched: the counters of a batch without pairs
+      for (auto & v : c->nw_totals) { v = 0; }
+      c->nw_text_full = 0;
+      return (int)SWA_OK;
+    }
+    const uint64_t room = at[(size_t)r + 1] - at[(size_t)r];
+    char * text = nullptr;
+    if (cigar != nullptr && at[(size_t)r + 1] <= cigar_cap) { text = cigar + at[(size_t)r]; }
+    else {
+      own[(size_t)r].reset(new (std::nothrow) char[std::max<uint64_t>(room, 1)]);
+      if (!own[(size_t)r]) { return swa_fail_msg(c, SWA_E_NOMEM, "swa_multi_nw_batch: no memory for the slice's CIGAR text"); }
+      text = own[(size_t)r].get();
+    }
+    return swa_nw_batch(c, mismatch, gapopen, gapextend, count, d_ids + lo, q_ids + lo, diffs + lo, columns + lo, cigar_end + lo, text, room,
+                        &total[(size_t)r]);
+  });
+  if (rc != SWA_OK) { return rc; }
+  // the texts together in rank order (a slice only ever moves down: its text is no longer than its bound), every rank's
+  // ends raised by the totals of the ranks below it
+  uint64_t sum = 0;
+  for (int r = 0; r < world; ++r) {
+    const uint64_t lo = bounds[(size_t)r], hi = bounds[(size_t)r + 1], bytes = total[(size_t)r];
+    if (lo == hi) { continue; }
+    if (sum != 0) { for (uint64_t k = lo; k < hi; ++k) { cigar_end[k] += sum; } }
+    const char * src = own[(size_t)r] ? own[(size_t)r].get() : cigar + at[(size_t)r];
+    if (cigar != nullptr && bytes != 0 && sum < cigar_cap && src != cigar + sum) {
+      std::memmove(cigar + sum, src, (size_t)std::min<uint64_t>(bytes, cigar_cap - sum));
+    }
+    sum += bytes;
+  }
+  if (cigar_total != nullptr) { *cigar_total = sum; }
+  if (sum > cigar_cap || (cigar == nullptr && sum > 0)) {
+    return fail(m, SWA_E_CAPACITY, "swa_multi_nw_batch: CIGAR buffer too small (*cigar_total = need)");
+  }
+  return SWA_OK;
+}
+
+// the counters of the last swa_multi_nw_batch summed over the ranks (a rank's own: swa_nw_batch_* on swa_multi_ctx(m, r))
+extern "C" int swa_multi_nw_batch_totals(swa_multi * m, uint64_t * out4) {
+  if (m == nullptr || out4 == nullptr) { return SWA_E_ARG; }
+  for (int i = 0; i < 4; ++i) { out4[i] = 0; }
+  for (swa_ctx * c : m->ctx) { uint64_t t[4] = {}; (void)swa_nw_batch_totals(c, t); for (int i = 0; i < 4; ++i) { out4[i] += t[i]; } }
+  return SWA_OK;
+}
+
+extern "C" int swa_multi_nw_batch_tiers(swa_multi * m, uint64_t * out8) {
+  if (m == nullptr || out8 == nullptr) { return SWA_E_ARG; }
+  for (int i = 0; i < 8; ++i) { out8[i] = 0; }
+  for (swa_ctx * c : m->ctx) { uint64_t t[8] = {}; (void)swa_nw_batch_tiers(c, t); for (int i = 0; i < 8; ++i) { out8[i] += t[i]; } }
+  return SWA_OK;
+}
+
+extern "C" int swa_multi_nw_batch_text_full(swa_multi * m, uint64_t * out1) {
+  if (m == nullptr || out1 == nullptr) { return SWA_E_ARG; }
+  *out1 = 0;
+  for (swa_ctx * c : m->ctx) { uint64_t t = 0; (void)swa_nw_batch_text_full(c, &t); *out1 += t; }
   return SWA_OK;
 }
 

@@ -632,6 +632,11 @@ void assemble(swa_ctx * ctx, uint32_t m, const std::vector<uint32_t> & hl, const
 
 }  // namespace
 
+int swa_nw_host_seqlen(swa_ctx * ctx) {
+  SWA_HIP(ctx, hipSetDevice(ctx->device));
+  return host_seqlen(ctx);
+}
+
 extern "C" int swa_nw_batch(swa_ctx * ctx, uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t npairs,
                             const uint32_t * d_ids, const uint32_t * q_ids, uint32_t * diffs, uint32_t * columns,
                             uint64_t * cigar_end, char * cigar, uint64_t cigar_cap, uint64_t * cigar_total) {

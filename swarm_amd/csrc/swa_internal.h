@@ -427,6 +427,9 @@ struct swa_scan_call {
 // nullptr, or why swa_scan_batch refuses these arguments
 const char * swa_scan_check_call(const swa_ctx * ctx, const swa_scan_call & call, const uint32_t * hit_seedidx, const uint32_t * hit_ids,
                                  const uint32_t * hit_diffs, uint32_t cap, const uint32_t * nhits);
+// nw_trace.hip: the lengths of the resident database on the host (ctx->up.nw_seqlen), downloaded once a database — what
+// swa_nw_batch sorts its pairs into tiers by, and swa_multi_nw_batch divides them among the ranks by
+int swa_nw_host_seqlen(swa_ctx * ctx);
 int swa_scan_enqueue(swa_ctx * ctx, const swa_scan_call & call);                  // the launch sequence on ctx->stream; does not wait
 int swa_scan_finish(swa_ctx * ctx, const swa_scan_call & call, uint32_t * nhits); // waits; redoes an overflowed pass; leaves the sorted hits for swa_scan_fetch
 
