@@ -555,7 +555,14 @@ int swa_search_uses_wavefront(const swa_ctx * ctx);
    *saturation = 255 or 65535 (the reference's 8- or 16-bit mode); *lds_bytes = the dynamic LDS a workgroup of the form
    stages (0 for SWA_FORM_GENERIC, which keeps its state in global scratch: 24 B a thread per nucleotide of the longest
    sequence, within 2 GiB).  A form whose staging does not fit the device's LDS is never chosen.  Any output may be
-   NULL.  SWA_E_ARG before swa_search_begin, without a database, or when the longest sequence is too long even for
+   NULL.
+   The WIDE forms serve the bands that exceed the 64 lanes of k_align<64> (2 W + 3 > 64, W = d * max(mismatch, gapopen +
+   gapextend) / gapextend + 1): k_align_wide<K> gives a pair one wave and a lane K = 2, 4, 8 adjacent band offsets, so
+   W <= 62, 126, 254, with the results of SWA_FORM_GENERIC bit for bit.  They are opt-in: chosen only while the
+   environment has SWA_ALIGN_WIDE=1 (read at every call) and their staging (64 B a word of the longest sequence) fits
+   the LDS; otherwise such bands take SWA_FORM_GENERIC as before.
+   swa_align_wide_for: that choice as a pure function of the scoring and d, out = {W, saturation, K}; K = 0 when the band
+   fits 64 lanes or exceeds 254.  SWA_E_ARG for what swa_search_begin refuses.  SWA_E_ARG before swa_search_begin, without a database, or when the longest sequence is too long even for
    the generic kernel (one thread's scratch above 2 GiB, ~89 M nt); every alignment launch then fails the same way. */
 typedef enum {
   SWA_FORM_WFA16 = 1,          /* k_align_wfa<16>: wavefront, four pairs a wave */
@@ -564,8 +571,15 @@ typedef enum {
   SWA_FORM_BANDED32_LEN = 4,   /* k_align<32, true> */
   SWA_FORM_BANDED64 = 5,       /* k_align<64, false> */
   SWA_FORM_BANDED64_LEN = 6,   /* k_align<64, true> */
-  SWA_FORM_GENERIC = 7         /* k_align_generic: one thread a pair, any band, any length */
+  SWA_FORM_GENERIC = 7,        /* k_align_generic: one thread a pair, any band, any length */
+  SWA_FORM_WIDE2 = 8,          /* k_align_wide<2, false>: one wave a pair, two band offsets a lane */
+  SWA_FORM_WIDE2_LEN = 9,      /* k_align_wide<2, true> */
+  SWA_FORM_WIDE4 = 10,         /* k_align_wide<4, false> */
+  SWA_FORM_WIDE4_LEN = 11,     /* k_align_wide<4, true> */
+  SWA_FORM_WIDE8 = 12,         /* k_align_wide<8, false> */
+  SWA_FORM_WIDE8_LEN = 13      /* k_align_wide<8, true> */
 } swa_align_form;
+int swa_align_wide_for(uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t d, uint64_t out[3]);
 int swa_search_form(swa_ctx * ctx, int with_lengths, int * form, uint32_t * saturation, uint64_t * lds_bytes);
 /* diffs[i] == the reference's nw() value (src/nw.cc, which its search8/search16 + backtrack
    follow) whenever that value is <= d; otherwise some value > d.  Known exceptions, where the

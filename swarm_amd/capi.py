@@ -83,7 +83,7 @@ EXPORTS = [
     "swa_db_upload", "swa_db_attach", "swa_db_stage_words", "swa_db_upload_unordered", "swa_hostdb_unordered_view", "swa_hostdb_read_fasta_staged", "swa_cli_main", "swa_d1_index_build", "swa_d1_index_build_range", "swa_d1_set_ownership", "swa_d1_route_slice", "swa_d1_index_build_routed", "swa_d1_route_slice_records", "swa_d1_index_build_records", "swa_d1_network", "swa_d1_network_edges_device", "swa_d1_network_device", "swa_d1_guard_retries",
     "swa_d1_links_split", "swa_d1_csr_from_lists",
     "swa_d1_debug_read", "swa_d1_table_size", "swa_search_uses_wavefront", "swa_d1_fastidious", "swa_d1_fastidious_shard", "swa_d1_fastidious_plan", "swa_d1_fastidious_totals", "swa_d1_fastidious_bloom_batches", "swa_d1_fastidious_bloom_read", "swa_d1_fastidious_split", "swa_d1_fastidious_plan_for", "swa_d1_fastidious_plan_modes", "swa_d1_fastidious_sites_cap", "swa_d1_part_plan_for", "swa_d1_part_plan", "swa_d1_csr_plan_for", "swa_d1_lists_form_for", "swa_d1_lists_form", "swa_qgram_build", "swa_qgram_diff",
-    "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_timing_enable", "swa_timing_read",
+    "swa_qgram_debug_read", "swa_search_begin", "swa_search_do", "swa_search_form", "swa_align_wide_for", "swa_timing_enable", "swa_timing_read",
     "swa_hostdb_read_fasta", "swa_hostdb_free", "swa_hostdb_error", "swa_hostdb_view", "swa_hostdb_nucleotides",
     "swa_hostdb_header", "swa_d1_cluster", "swa_d1_result_free", "swa_d1_result_summary", "swa_d1_result_swarmid",
     "swa_d1_result_parent", "swa_d1_result_generation", "swa_d1_light_flags", "swa_d1_graft", "swa_d1_write_swarms",
@@ -180,6 +180,7 @@ def load_library() -> C.CDLL:
     lib.swa_qgram_diff.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.swa_qgram_debug_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.swa_search_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+    lib.swa_align_wide_for.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.swa_search_do.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]
     lib.swa_timing_enable.argtypes = [C.c_void_p, C.c_int]
@@ -289,6 +290,16 @@ def lists_form_for(buckets: int) -> int:
     if form < 0:
         raise SwaError(2, "swa_d1_lists_form_for: bad argument")
     return form
+
+
+def align_wide_for(mismatch: int, gapopen: int, gapextend: int, d: int) -> tuple:
+    """swa_align_wide_for: (W, saturation, K) of a reduced scoring and d — the band half-width, 255 or 65535, and the
+    offsets a lane of the wide alignment form (2, 4, 8; 0 when the band fits 64 lanes or exceeds W = 254)."""
+    out = np.zeros(3, dtype=np.uint64)
+    rc = load_library().swa_align_wide_for(int(mismatch), int(gapopen), int(gapextend), int(d), _ptr(out))
+    if rc != SWA_OK:
+        raise SwaError(rc, "swa_align_wide_for: bad argument")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def csr_plan_for(count: int) -> list:
@@ -1207,7 +1218,8 @@ class Context:
         self.lib.swa_search_uses_wavefront.argtypes = [C.c_void_p]
         return bool(self.lib.swa_search_uses_wavefront(self.h))
 
-    SEARCH_FORMS = {1: "wfa16", 2: "wfa32", 3: "banded32", 4: "banded32_len", 5: "banded64", 6: "banded64_len", 7: "generic"}
+    SEARCH_FORMS = {1: "wfa16", 2: "wfa32", 3: "banded32", 4: "banded32_len", 5: "banded64", 6: "banded64_len", 7: "generic",
+                    8: "wide2", 9: "wide2_len", 10: "wide4", 11: "wide4_len", 12: "wide8", 13: "wide8_len"}
 
     def search_form(self, with_lengths: bool = True) -> tuple:
         """(form, saturation, LDS bytes a workgroup) of the alignment kernel a launch takes for the penalties / d of

@@ -252,6 +252,189 @@ __global__ __launch_bounds__(256) void k_align(const AlignArgs a) {
   }
 }
 
+// Bands wider than a wave (2W + 3 > 64): one wave aligns one pair and every lane keeps K = 2, 4 or 8 ADJACENT band
+// offsets in registers (the layout of k_nw_trace_wide, nw_trace.hip).  Offset index x = lane * K + j stands for band offset
+// x - 1 - W; x = 0 and x > 2W + 1 are guards that never compute a cell and so hold the "outside the band" value for
+// ever (lane 0's j = 0 and lane 63's j = K - 1, whose DPP shifts have no source, are among them): needs 2W + 3 <= 64 K.
+// The cells are those of k_align above, value for value.  On an anti-diagonal step only the offsets of one parity are
+// live, K / 2 a lane; they read their neighbours of the OTHER parity, which the step leaves alone, so a step updates
+// its cells in place.  Inside a lane the neighbours are registers; only j = 0 takes the horizontal state of the lane
+// below's top offset and j = K - 1 the vertical state of the lane above's offset 0 — K is even, so a step whose live
+// parity is even needs the first and one whose live parity is odd the second: one shuffle a step (two with lengths).
+// W is a run-time value, so which parity is live on step s, (s + 1 + W) & 1, is wave-uniform but no compile-time
+// fact: the step is instantiated for both parities, which keeps j a compile-time index into the register arrays, and
+// the order of the two is chosen once a pair from W's parity.
+template <int K, bool WANT_LEN>
+__global__ __launch_bounds__(256) void k_align_wide(const AlignArgs a) {
+  static_assert(K == 2 || K == 4 || K == 8, "an even number of offsets a lane");
+  extern __shared__ uint64_t lds[];
+  constexpr int kGroups = 4;                                  // waves = pairs a workgroup
+  constexpr int kShift = K == 2 ? 1 : K == 4 ? 2 : 3;
+  const int group = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  uint64_t * qw = lds + (size_t)(2 * group) * a.maxwords;     // this wave's query words
+  uint64_t * dw = qw + a.maxwords;                            // this wave's target words
+
+  const uint32_t SAT = a.sat;
+  const int W = a.W;
+  const int o0 = lane * K - 1 - W;                            // band offset of j = 0
+  const uint32_t go = a.gapopen, ge = a.gapextend, mm = a.mismatch;
+  constexpr uint32_t kBigCount = 0xFFFFu;
+  const uint32_t kOutside = SAT | (kBigCount << 16);
+  uint32_t in_band = 0;                                       // bit j: offset index lane * K + j lies in 1 .. 2W + 1
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const int x = lane * K + j;
+    in_band |= (x >= 1 && x <= 2 * W + 1) ? 1u << j : 0u;
+  }
+
+  const uint32_t ntargets = a.ntargets_dev != nullptr ? min(*a.ntargets_dev, a.ntargets) : a.ntargets;
+  for (uint32_t pair = blockIdx.x * kGroups + group; pair < ntargets; pair += gridDim.x * kGroups) {
+    const uint32_t target = a.targets[pair];
+    const uint32_t query = a.queries != nullptr ? a.queries[pair] : a.query;
+    const uint32_t dl = a.seqlen[target];
+    const uint32_t ql = a.seqlen[query];
+    {
+      const uint64_t * gd = a.seqs + a.seq_off[target];
+      const uint64_t * gq = a.seqs + a.seq_off[query];
+      const uint32_t dn = (dl + 31u) >> 5;
+      const uint32_t qn = (ql + 31u) >> 5;
+      for (uint32_t w = lane; w < dn; w += 64) { dw[w] = gd[w]; }
+      for (uint32_t w = lane; w < qn; w += 64) { qw[w] = gq[w]; }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+
+    const int delta = (int)ql - (int)dl;
+    const bool feasible = (delta <= W) && (-delta <= W) && dl != 0u && ql != 0u;
+    // per offset: the last cell it computed (H, A_M, length) and what that cell hands down (E | A_I << 16) and right
+    // (F | A_D << 16), packed as in k_align
+    uint32_t Hown[K], AMown[K], LMown[K], dn_pk[K], rt_pk[K], dn_len[K], rt_len[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      Hown[j] = 0; AMown[j] = 0; LMown[j] = 0;
+      dn_pk[j] = kOutside; rt_pk[j] = kOutside; dn_len[j] = 0; rt_len[j] = 0;
+    }
+    if (feasible) {
+      const int last = (int)dl + (int)ql - 2;
+      const int rmax = (int)dl - 1, cmax = (int)ql - 1;
+      // one anti-diagonal: the offsets j of parity PAR
+      auto step = [&](const int s, auto par_tag) {
+        constexpr int PAR = decltype(par_tag)::value;
+        const uint32_t su = (uint32_t)s;
+        // row 0 / column 0 (nw.cc:66-79): wave-uniform functions of the step
+        const uint32_t edge_h = s == 0 ? 0u : sat_add(go, su * ge, SAT);
+        const uint32_t edge_pk = sat_add(2u * go, (su + 2u) * ge, SAT) | ((su + 1u) << 16);
+        uint32_t in_pk, in_len = 0;                           // what crosses the lanes on this step
+        if (PAR == 0) {
+          in_pk = from_lane_below(rt_pk[K - 1]);              // cell (r, c-1) of j = 0
+          if (WANT_LEN) { in_len = from_lane_below(rt_len[K - 1]); }
+        } else {
+          in_pk = from_lane_above(dn_pk[0]);                  // cell (r-1, c) of j = K - 1
+          if (WANT_LEN) { in_len = from_lane_above(dn_len[0]); }
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          if ((j & 1) != PAR) { continue; }
+          const int rs = s - (o0 + j);
+          const int r = rs >> 1;
+          const int c = s - r;
+          // in the band, (s - offset) even by the parity, and inside the matrix
+          const bool act = ((in_band >> j) & 1u) != 0u && (uint32_t)r <= (uint32_t)rmax && (uint32_t)c <= (uint32_t)cmax;
+          const uint32_t rc = (uint32_t)min(max(r, 0), rmax);  // clamped: idle offsets read something valid
+          const uint32_t cc = (uint32_t)min(max(c, 0), cmax);
+          const uint32_t dnt = (uint32_t)(dw[rc >> 5] >> ((rc & 31u) << 1));
+          const uint32_t qnt = (uint32_t)(qw[cc >> 5] >> ((cc & 31u) << 1));
+          const uint32_t mis = ((dnt ^ qnt) & 3u) != 0u ? 1u : 0u;
+          const uint32_t above_pk = j == K - 1 ? in_pk : dn_pk[j == K - 1 ? j : j + 1];
+          const uint32_t below_pk = j == 0 ? in_pk : rt_pk[j == 0 ? j : j - 1];
+          const bool row0 = r == 0, col0 = c == 0;
+          const uint32_t hd = (row0 || col0) ? edge_h : Hown[j];
+          const uint32_t amd = (row0 || col0) ? su : AMown[j];
+          const uint32_t left_pk = row0 ? edge_pk : above_pk;   // "left" / "top" as in nw.cc
+          const uint32_t top_pk = col0 ? edge_pk : below_pk;
+          const uint32_t left = left_pk & 0xFFFFu, aiv = left_pk >> 16;
+          const uint32_t top = top_pk & 0xFFFFu, adh = top_pk >> 16;
+
+          const uint32_t dp = sat_add(hd, mis ? mm : 0u, SAT);
+          const bool up = top < dp;                            // nw.cc:91
+          uint32_t h = dp < top ? dp : top;
+          h = h < left ? h : left;
+          const bool lb = left == h;                           // nw.cc:94
+          const uint32_t d2 = sat_add(h, go + ge, SAT);
+          const uint32_t l2 = sat_add(left, ge, SAT);
+          const uint32_t t2 = sat_add(top, ge, SAT);
+          const bool eu = t2 < d2;                             // nw.cc:102
+          const bool el = l2 < d2;                             // nw.cc:103
+          const uint32_t via_l = aiv + 1u, via_t = adh + 1u, via_d = amd + mis;
+          uint32_t am = select_u32(up, via_t, via_d);
+          am = select_u32(lb, via_l, am);
+          am = am < kBigCount ? am : kBigCount;
+          uint32_t ai = select_u32(el, via_l, am);
+          uint32_t ad = select_u32(eu, via_t, am);
+          ai = ai < kBigCount ? ai : kBigCount;
+          ad = ad < kBigCount ? ad : kBigCount;
+          Hown[j] = act ? h : Hown[j];
+          AMown[j] = act ? am : AMown[j];
+          dn_pk[j] = act ? ((d2 < l2 ? d2 : l2) | (ai << 16)) : dn_pk[j];
+          rt_pk[j] = act ? ((d2 < t2 ? d2 : t2) | (ad << 16)) : rt_pk[j];
+          if (WANT_LEN) {
+            const uint32_t above_len = j == K - 1 ? in_len : dn_len[j == K - 1 ? j : j + 1];
+            const uint32_t below_len = j == 0 ? in_len : rt_len[j == 0 ? j : j - 1];
+            const uint32_t lmd = (row0 || col0) ? su : LMown[j];
+            const uint32_t liv = row0 ? su + 1u : above_len;
+            const uint32_t ldh = col0 ? su + 1u : below_len;
+            const uint32_t lm = lb ? liv + 1u : (up ? ldh + 1u : lmd + 1u);
+            LMown[j] = act ? lm : LMown[j];
+            dn_len[j] = act ? (el ? liv + 1u : lm) : dn_len[j];
+            rt_len[j] = act ? (eu ? ldh + 1u : lm) : rt_len[j];
+          }
+        }
+      };
+      // offset index x has j's parity and is live on step s when s - (x - 1 - W) is even: j of parity (s + 1 + W) & 1
+      using Even = std::integral_constant<int, 0>;
+      using Odd = std::integral_constant<int, 1>;
+      if ((W & 1) != 0) {
+#pragma unroll 1
+        for (int s = 0; s <= last; s += 2) {
+          step(s, Even{});
+          if (s < last) { step(s + 1, Odd{}); }
+        }
+      } else {
+#pragma unroll 1
+        for (int s = 0; s <= last; s += 2) {
+          step(s, Odd{});
+          if (s < last) { step(s + 1, Even{}); }
+        }
+      }
+    }
+    // the end cell (dl - 1, ql - 1) lies on offset delta: index x = delta + W + 1, held by one (lane, j)
+    if (!feasible) {
+      if (lane == 0) {
+        a.diffs[pair] = SAT;
+        if (a.scores != nullptr) { a.scores[pair] = SAT; }
+        if (a.alnlens != nullptr) { a.alnlens[pair] = 0; }
+      }
+    } else {
+      const int xe = delta + W + 1;
+      if (lane == (xe >> kShift)) {
+        uint32_t h_end = Hown[0], am_end = AMown[0], lm_end = LMown[0];
+#pragma unroll
+        for (int j = 1; j < K; ++j) {
+          if ((xe & (K - 1)) == j) { h_end = Hown[j]; am_end = AMown[j]; lm_end = LMown[j]; }
+        }
+        // like the reference: a saturated score means "no alignment", diff = SAT (search8.cc:776-810)
+        const bool overflow = h_end >= SAT;
+        a.diffs[pair] = overflow ? SAT : am_end;
+        if (a.scores != nullptr) { a.scores[pair] = h_end; }
+        if (a.alnlens != nullptr) { a.alnlens[pair] = overflow ? 0 : lm_end; }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 // ---- wavefront formulation (the fast path) -------------------------------------------------
 // For near-identical pairs — the only ones the caller keeps — filling even a banded matrix is
 // wasteful: ~(Lq + Lt) dependent anti-diagonal steps.  The wavefront recurrences of gap-affine
@@ -586,6 +769,28 @@ __global__ __launch_bounds__(256) void k_widen(const uint32_t * __restrict__ in,
 
 }  // namespace
 
+// The band, the saturation and the wide form (k_align_wide<K>) of a scoring and d, as a pure function: out = {W,
+// saturation, K}.  K = the fewest offsets a lane (2, 4, 8) whose 64 K offset indices hold the band and its two guards,
+// 0 when the band fits the 64 lanes of k_align<64> or exceeds W = 254.
+extern "C" int swa_align_wide_for(uint64_t mismatch, uint64_t gapopen, uint64_t gapextend, uint64_t d, uint64_t out[3]) {
+  if (out == nullptr || mismatch == 0 || gapextend == 0 || mismatch > 65535 || gapopen > 65535 || gapextend > 65535 ||
+      d == 0 || d > 255) {
+    return SWA_E_ARG;
+  }
+  // 8- or 16-bit arithmetic exactly as set_bit_mode decides (src/algo.cc:96-120)
+  const uint64_t diff_saturation = std::min<uint64_t>(255 / mismatch, 255 / (gapopen + gapextend));
+  const uint64_t W = d * std::max<uint64_t>(mismatch, gapopen + gapextend) / gapextend + 1;
+  out[0] = W;
+  out[1] = d > diff_saturation ? 65535u : 255u;
+  out[2] = 0;
+  if (2 * W + 3 > 64) {
+    for (const uint64_t k : {2u, 4u, 8u}) {
+      if (2 * W + 3 <= 64 * k) { out[2] = k; break; }
+    }
+  }
+  return SWA_OK;
+}
+
 namespace {
 
 // The form an alignment launch takes (swa_align_form) and what its launch needs.  Chosen from the penalties, d and the
@@ -634,6 +839,18 @@ AlignPlan align_plan(const swa_ctx * ctx, bool with_lengths) {
     if (lds <= ctx->max_lds) {
       p.form = wide ? (with_lengths ? SWA_FORM_BANDED64_LEN : SWA_FORM_BANDED64)
                     : (with_lengths ? SWA_FORM_BANDED32_LEN : SWA_FORM_BANDED32);
+      p.lds = lds;
+      return p;
+    }
+  }
+  // bands wider than a wave: k_align_wide<K>, opt-in (test / comparison switch, read at every call)
+  const char * want_wide = std::getenv("SWA_ALIGN_WIDE");
+  uint64_t wide_for[3] = {0, 0, 0};
+  if (want_wide != nullptr && want_wide[0] == '1' && swa_align_wide_for(mm, go, ge, d, wide_for) == SWA_OK && wide_for[2] != 0) {
+    const size_t lds = sizeof(uint64_t) * (size_t)p.maxwords * 2 * 4;
+    if (lds <= ctx->max_lds) {
+      const int base = wide_for[2] == 2 ? SWA_FORM_WIDE2 : wide_for[2] == 4 ? SWA_FORM_WIDE4 : SWA_FORM_WIDE8;
+      p.form = base + (with_lengths ? 1 : 0);
       p.lds = lds;
       return p;
     }
@@ -730,8 +947,8 @@ int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, 
     hipLaunchKernelGGL(k_align_generic, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, ctx->stream, a,
                        static_cast<uint32_t *>(ctx->d_queue.ptr), (uint32_t)nthreads, qcap);
   } else {
-    const bool wide = p.form == SWA_FORM_BANDED64 || p.form == SWA_FORM_BANDED64_LEN;
-    const int groups = wide ? 4 : 8;
+    const bool narrow = p.form == SWA_FORM_BANDED32 || p.form == SWA_FORM_BANDED32_LEN;
+    const int groups = narrow ? 8 : 4;
     uint64_t blocks = ((uint64_t)max_count + groups - 1) / groups;
     if (blocks > cap) { blocks = cap; }
     if (blocks < 1) { blocks = 1; }
@@ -739,6 +956,12 @@ int swa_align_launch(swa_ctx * ctx, uint32_t query, const uint32_t * d_queries, 
       case SWA_FORM_BANDED64_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align<64, true>, blocks, 256, a)); break;
       case SWA_FORM_BANDED32_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align<32, true>, blocks, 256, a)); break;
       case SWA_FORM_BANDED64: SWA_TRY(align_launch_staged(ctx, p, k_align<64, false>, blocks, 256, a)); break;
+      case SWA_FORM_WIDE2: SWA_TRY(align_launch_staged(ctx, p, k_align_wide<2, false>, blocks, 256, a)); break;
+      case SWA_FORM_WIDE2_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align_wide<2, true>, blocks, 256, a)); break;
+      case SWA_FORM_WIDE4: SWA_TRY(align_launch_staged(ctx, p, k_align_wide<4, false>, blocks, 256, a)); break;
+      case SWA_FORM_WIDE4_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align_wide<4, true>, blocks, 256, a)); break;
+      case SWA_FORM_WIDE8: SWA_TRY(align_launch_staged(ctx, p, k_align_wide<8, false>, blocks, 256, a)); break;
+      case SWA_FORM_WIDE8_LEN: SWA_TRY(align_launch_staged(ctx, p, k_align_wide<8, true>, blocks, 256, a)); break;
       default: SWA_TRY(align_launch_staged(ctx, p, k_align<32, false>, blocks, 256, a)); break;
     }
   }
